@@ -1,6 +1,6 @@
 """Benchmark of the hot path: Newton iterations per second of the monolithic ALE-FSI time step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--tets T]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--tets T] [--dump-outputs DIR]
 
 One "step" = one time step of the offset-stenosis problem exactly as the product driver runs it
 (``vasp_amd.monolithic.advance``: pre_solve data, quasi-Newton solve through the C-ABI, state shift, post_solve
@@ -28,6 +28,10 @@ it the main run, with ``dtype`` saying so).
 Output: ONE JSON line on rank 0: metric, value, `roofline` of the kernel group with the largest share of GPU time in the
 timed region (orthogonalisation kernels included, their bytes exact from the number of columns streamed), `kernels` (the
 whole table the choice was made from), `cpu_baseline`.
+
+``--dump-outputs DIR``: after the timed steps, what the last one handed its caller is written to DIR as float64 .npy files
+(see ``dump_outputs``), so that two builds run with the same arguments - same mesh, same initial state, same steps - can be
+compared output for output.
 """
 from __future__ import annotations
 
@@ -61,6 +65,8 @@ KERNEL_GROUPS = {"k_gcr_dots": ["k_gcr_dots<", "k_gcr_axpy<"],
                  "k_sweep_sb_b3<0>": ["k_sweep_sb_b3<0>"], "Schur": ["k_sweep_schur_tiled", "k_sweep_csr_mixed", "k_sweep_csr_f32", "k_spmv<2,"],
                  "k_residual": ["k_residual<", "k_residual_gather"], "k_jacobian": ["k_jacobian<2,"]}
 FP64_STORAGE_ENV = {"FSI_KRYLOV_FP32": "0", "FSI_OPERATOR_FP32": "0", "FSI_SCHUR_FP32": "0", "FSI_SWEEPS_FP16": "0"}
+DUMP_BUDGET_BYTES = 64_000_000      # --dump-outputs: all files together, headers included
+NEWTON_HISTORY_COLUMNS = ("residual", "rel_res", "recomputed", "lin_iters", "lin_relres")
 
 
 def self_launch(args) -> int:
@@ -71,7 +77,8 @@ def self_launch(args) -> int:
            "--master-addr", "127.0.0.1", "--master-port", str(port), str(Path(__file__).resolve()),
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--tets", str(args.tets),
            "--dt", str(args.dt), "--storage", args.storage] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []) \
-          + (["--tets-per-gpu", str(args.tets_per_gpu)] if args.tets_per_gpu else [])
+          + (["--tets-per-gpu", str(args.tets_per_gpu)] if args.tets_per_gpu else []) \
+          + (["--dump-outputs", str(Path(args.dump_outputs).resolve())] if args.dump_outputs else [])
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     return subprocess.call(cmd, env=env)
@@ -97,6 +104,32 @@ def other_storage_run(args, storage: str) -> dict:
             "krylov_iterations": j["krylov_iterations"], "phase_ms": j["phase_ms"], "dtype": j["dtype"],
             "env": FP64_STORAGE_ENV if storage == "fp64" else {},
             "storage_precisions": j["config"]["storage_precisions"], "roofline": j["roofline"], "wall_s": time.perf_counter() - t0}
+
+
+def dump_outputs(folder: Path, x: np.ndarray, mesh, hist) -> dict:
+    """--dump-outputs: the state the last timed step leaves behind (``dvp_["n"]`` after the shift: displacement and velocity
+    per P2 node, (N2, 3), pressure per vertex, (V,)) and that step's Newton history (one row per iteration, columns
+    NEWTON_HISTORY_COLUMNS), all float64.  If the state does not fit DUMP_BUDGET_BYTES, every field keeps the same fraction of
+    its rows: displacement and velocity the same nodes, drawn with numpy's default_rng(0) and sorted, pressure vertices from the
+    same generator - fixed for a given mesh, so two builds write the same rows.  Returns {name: shape} and whether it sampled."""
+    d, v, p = mesh.split(x)
+    newton = np.asarray(hist, dtype=np.float64).reshape(-1, len(NEWTON_HISTORY_COLUMNS))
+    budget = DUMP_BUDGET_BYTES - newton.nbytes - 4 * 256             # .npy headers
+    frac = min(1.0, budget / x.nbytes)
+    rng = np.random.default_rng(0)
+
+    def rows(n):
+        k = int(n * frac)
+        return slice(None) if k >= n else np.sort(rng.choice(n, k, replace=False))
+
+    nodes = rows(len(d))
+    verts = rows(len(p))
+    arrays = {"displacement": d[nodes], "velocity": v[nodes], "pressure": p[verts], "newton_history": newton}
+    folder.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(folder / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": str(folder), "arrays": {k: list(a.shape) for k, a in arrays.items()}, "sampled": frac < 1.0,
+            "newton_history_columns": list(NEWTON_HISTORY_COLUMNS)}
 
 
 def cpu_baseline(desc, gpu: dict, budget_s: float = 25.0):
@@ -141,7 +174,11 @@ def main():
                          "this many tets per rank, `scaling` is \"weak\"")
     ap.add_argument("--profile-host", action="store_true", help="wall time of pre_solve / boundary data / Newton solve / shift / "
                                                                 "post_solve per step in the JSON line (host_ms_per_step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state and Newton history of the last one to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.storage == "default":
         args.storage = "mixed"
     if args.tets_per_gpu:
@@ -434,6 +471,10 @@ def main():
                                     "newton_iterations": sum(len(k) for k in krylov_per_solve[a:a + life]),
                                     "krylov_iterations": sum(sum(k) for k in krylov_per_solve[a:a + life])}
                                    for a in range(0, args.steps, life)]
+    if args.dump_outputs:      # collective when the ranks are symmetric: every rank gathers, rank 0 writes
+        x = hb.get_state("n")
+        if rank == 0:
+            out["dump_outputs"] = dump_outputs(Path(args.dump_outputs), x, mesh, hist)
     hb.close()                 # the context's HBM (Krylov store, matrices) is free again before anything else runs
     if rank == 0:
         out["config"]["storage"] = args.storage
