@@ -1,9 +1,9 @@
 """ctypes loader of ``vasp_amd/libfsi_kernel_shim.so`` (vasp_amd/csrc/fsi_kernel_shim.hip) and the host-side reference builders
-of the kernel tests (tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py).
+of the kernel tests (tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py, tests/test_gpu_product_kernels.py).
 
 The shim runs ONE ``fsi::launch_*`` call of libvaspfsi.so on host arrays; the builders restate, in numpy, what the library's
-host code hands those kernels: the LDS tiles of a graph (fsi_capi.hip, node tiles and Schur tiles) and the FP16 records of
-k_pack_h1 / k_pack_h3 / k_pack_sb.  The builders are tested on the CPU (tests/test_kernel_references.py), so that a failure
+host code hands those kernels: the LDS tiles of a graph (fsi_capi.hip, node tiles and Schur tiles), the FP16 records of
+k_pack_h1 / k_pack_h3 / k_pack_sb, and the monolithic matrix's column layout, padded FP32 copy and d-row pair form.  The builders are tested on the CPU (tests/test_kernel_references.py), so that a failure
 of a GPU test is one of the kernel, not of its reference."""
 from __future__ import annotations
 
@@ -29,7 +29,11 @@ _SIGS = {
     "shim_cheb_init_b3": "lppfppp", "shim_cheb_step_b3": "lppffppp",
     "shim_sweep_csr_f64": "lppppddpppp", "shim_sweep_csr_mixed": "lpppppddpppp", "shim_sweep_schur_tiled": "ilipppppddpppp",
     "shim_ctx_info": "ppi", "shim_ctx_array": "psppp", "shim_tile_limit": "",
+    "shim_expand_cols": "llpppppppp", "shim_spmv": "lpppplpi", "shim_spmv_node6": "llpppppplppp", "shim_drows_extract": "lpppppp",
+    "shim_pad_cols32": "lpppp", "shim_pad_vals32": "llppplllpli", "shim_spmv_node6p": "llppplpplppplppp",
+    "shim_matrix_finish": "lppppplpp", "shim_ctx_spmv": "pippp",
 }
+LAUNCH_REFUSED = 2           # fsi_kernels.hpp: a launch function refused its arguments and launched nothing
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "d": C.c_double, "s": C.c_char_p}
 _lib = None
 
@@ -62,21 +66,36 @@ def _arg(a):
     return a
 
 
+def status(name, *args):
+    """Run one shim entry point and return its status (0 ok, else see fsi_kernel_shim.hip); arrays as in call()."""
+    return getattr(load(), name)(*[_arg(a) for a in args])
+
+
 def call(name, *args):
     """Run one shim entry point; numpy arrays are passed by pointer (outputs are written in place)."""
-    lib = load()
-    rc = getattr(lib, name)(*[_arg(a) for a in args])
+    rc = status(name, *args)
     if rc != 0:
-        raise RuntimeError(f"{name}: {lib.shim_last_error().decode()}")
+        raise RuntimeError(f"{name}: {load().shim_last_error().decode()}")
     return rc
 
 
+def check(got, ref, bound, what):
+    """|got - ref| <= bound entry by entry (NaN fails), with the first offender in the message"""
+    got, ref, bound = (np.asarray(a, dtype=np.float64).ravel() for a in (got, ref, bound))
+    err = np.abs(got - ref)
+    bad = ~(err <= bound)
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise AssertionError(f"{what}: {bad.sum()} of {len(got)} outside the bound; first at {i}: got {got[i]!r}, "
+                             f"reference {ref[i]!r}, error {err[i]:.3e} > bound {bound[i]:.3e}")
+
+
 CTX_INFO = ("N2", "V", "nS", "sb_nblocks", "tiled", "tile_nodes", "tile_max_nu", "schur_tiled", "schur_tile", "s_tile_max_nu",
-            "sweeps_fp16")
+            "sweeps_fp16", "a32_ptail", "a32_tail_src", "a32_tail_nnz", "op32_ok", "kry_fp32", "drows_ok")
 _ELEM = {("f", 4): np.float32, ("f", 8): np.float64, ("i", 1): np.uint8, ("i", 2): np.uint16, ("i", 4): np.int32,
          ("i", 8): np.int64}
 _UNSIGNED = {"dd_rec", "vv_rec", "sb_rec", "s_rec"}
-_FLOAT = {"dd_chat", "vv_db32", "sb_vals", "sb_binv12", "s_vals", "s_vals32", "s_dinv", "dd_db", "rowscale"}
+_FLOAT = {"dd_chat", "vv_db32", "sb_vals", "sb_binv12", "s_vals", "s_vals32", "s_dinv", "dd_db", "rowscale", "A", "A32", "Ad64", "Ad32"}
 
 
 def ctx_info(ctx) -> dict:
@@ -84,6 +103,14 @@ def ctx_info(ctx) -> dict:
     out = np.zeros(len(CTX_INFO), dtype=np.int64)
     lib.shim_ctx_info(ctx, _arg(out), len(CTX_INFO))
     return dict(zip(CTX_INFO, (int(v) for v in out)))
+
+
+def ctx_spmv(ctx, working, x, y):
+    """fsi::host::spmv on the context's solver-ordered vectors (y written in place); returns (status, op32_products added,
+    drows_products added)"""
+    cnt = np.zeros(2, dtype=np.int64)
+    rc = status("shim_ctx_spmv", ctx, int(working), x, y, cnt)
+    return rc, int(cnt[0]), int(cnt[1])
 
 
 def ctx_ktheta(ctx) -> float:
@@ -213,3 +240,145 @@ def local_graph(n, rng, reach=24, max_deg=40, diag_only=()):
     rowptr[1:] = np.cumsum([len(r) for r in rows])
     cols = np.concatenate(rows).astype(np.int32) if n else np.zeros(0, dtype=np.int32)
     return rowptr, cols
+
+
+# ---- the monolithic matrix: structure, padded FP32 copy, d rows in pair form (fsi_solver.hip, fsi_capi.hip) ------------------
+def mono_graph(N2, V, rng, reach=24, max_deg=12, heavy=(), heavy_deg=(), diag_only=(), no_padj=()):
+    """A node graph as the monolithic layout reads it.  nadj_ptr / nadj: every node's neighbour ranks, ascending, itself included
+    (up to max_deg random ones within `reach`; node heavy[k] gets heavy_deg[k] neighbours from anywhere; diag_only nodes itself
+    alone).  vrank: V distinct vertex nodes, the node of pressure position q.  padj_ptr / padj: per node the pressure positions
+    of its vertex neighbours, ascending (a vertex node meets itself, so its pressure row has a diagonal), except the nodes in
+    no_padj, which get none (their rows have no pressure column, the pressure row of a vertex among them no diagonal)."""
+    assert 0 <= V <= N2
+    k = rng.integers(0, max_deg + 1, N2)
+    src = np.repeat(np.arange(N2, dtype=np.int64), k)
+    dst = np.clip(src + rng.integers(-reach, reach + 1, len(src)), 0, N2 - 1)
+    src, dst = np.concatenate([src, np.arange(N2)]), np.concatenate([dst, np.arange(N2)])
+    drop = np.isin(src, np.asarray(list(diag_only) + list(heavy), dtype=np.int64)) & (src != dst)
+    src, dst = src[~drop], dst[~drop]
+    for r, d in zip(heavy, heavy_deg):
+        nb = rng.choice(N2, size=min(d, N2), replace=False)
+        src, dst = np.concatenate([src, np.full(len(nb), r)]), np.concatenate([dst, nb])
+    code = np.unique(src * N2 + dst)
+    src, dst = code // N2, code % N2
+    nadj_ptr = np.concatenate([[0], np.cumsum(np.bincount(src, minlength=N2))]).astype(np.int64)
+    nadj = dst.astype(np.int32)
+    vrank = rng.choice(N2, size=V, replace=False).astype(np.int32)
+    pos = np.full(N2, -1, dtype=np.int64)
+    pos[vrank] = np.arange(V)
+    keep = pos[dst] >= 0
+    keep &= ~np.isin(src, np.asarray(list(no_padj), dtype=np.int64))
+    ps, pq = src[keep], pos[dst[keep]]
+    o = np.lexsort((pq, ps))
+    padj_ptr = np.concatenate([[0], np.cumsum(np.bincount(ps, minlength=N2))]).astype(np.int64)
+    padj = pq[o].astype(np.int32)
+    return nadj_ptr, nadj, padj_ptr, padj, vrank
+
+
+def expand_cols(N2, nadj_ptr, nadj, padj_ptr, padj, vrank):
+    """The k_expand_cols contract.  Rows: dof t of node r is row 6 r + t, pressure position q row 6 N2 + q.  Every row of node r
+    (and the pressure row of a vertex at r) holds, for each neighbour s of r in ascending order, the columns 6 s .. 6 s + 5, then
+    the columns 6 N2 + u of r's pressure neighbours u.  diagpos: the entry of column = row, -1 where the row has none.
+    Returns (rowptr, cols, diagpos)."""
+    V = len(vrank)
+    deg, pdeg = np.diff(nadj_ptr), np.diff(padj_ptr)
+    Lnode = 6 * deg + pdeg
+    rank = np.concatenate([np.repeat(np.arange(N2), 6), np.asarray(vrank, dtype=np.int64)])
+    L = Lnode[rank]
+    rowptr = np.concatenate([[0], np.cumsum(L)]).astype(np.int64)
+    n = 6 * N2 + V
+    # the column pattern of each node, once
+    nrow = np.concatenate([np.repeat(6 * np.asarray(nadj, dtype=np.int64), 6) + np.tile(np.arange(6), len(nadj)),
+                           6 * N2 + np.asarray(padj, dtype=np.int64)])
+    owner = np.concatenate([np.repeat(np.repeat(np.arange(N2), deg), 6), np.repeat(np.arange(N2), pdeg)])
+    o = np.argsort(owner, kind="stable")
+    pattern, pptr = nrow[o], np.concatenate([[0], np.cumsum(Lnode)])
+    row = np.repeat(np.arange(n), L)
+    t = np.arange(rowptr[-1]) - rowptr[row]
+    cols = pattern[pptr[rank[row]] + t].astype(np.int32)
+    diagpos = np.full(n, -1, dtype=np.int64)
+    hit = np.flatnonzero(cols == row)
+    diagpos[row[hit]] = hit
+    return rowptr, cols, diagpos
+
+
+def pad_layout(N2, rowptr):
+    """The FP32 copy's layout (fsi_capi.hip): node r's six value rows padded to Lp = L rounded up to a multiple of 4, block at
+    p32[r] (entries), index row at p32[r] / 6; the pressure rows unpadded behind, at ptail.  Returns (p32, ptail, tail_src,
+    nnz_tail)."""
+    L = rowptr[6 * np.arange(N2) + 1] - rowptr[6 * np.arange(N2)]
+    p32 = np.concatenate([[0], np.cumsum(6 * ((L + 3) & ~3))]).astype(np.int64)
+    tail_src = int(rowptr[6 * N2])
+    return p32, int(p32[-1]), tail_src, int(rowptr[-1]) - tail_src
+
+
+def pad_copy(N2, rowptr, cols, A, v_rows_only=False):
+    """What k_pad_cols32 / k_pad_vals32 (+ k_round_to_f32 on the pressure rows) write: (cols32, A32, written), the padding entries
+    with column 0 and value 0, written[i] whether entry i of A32 is written (value rows 0 .. 2 are not with v_rows_only)."""
+    p32, ptail, tail_src, nnz_tail = pad_layout(N2, rowptr)
+    L = rowptr[6 * np.arange(N2) + 1] - rowptr[6 * np.arange(N2)]
+    Lp = (L + 3) & ~3
+    cols32 = np.zeros(ptail // 6, dtype=np.int32)
+    A32 = np.zeros(ptail + nnz_tail, dtype=np.float32)
+    written = np.ones(len(A32), dtype=bool)
+    r = np.repeat(np.arange(N2), 6 * L)
+    t = np.arange(tail_src) - rowptr[6 * r]
+    first = t < L[r]                                                  # entries of the first row of each node
+    cols32[p32[r[first]] // 6 + t[first]] = cols[:tail_src][first]
+    k = t // L[r]                                                     # value row 0 .. 5 of the node's block
+    tt = t - k * L[r]
+    A32[p32[r] + k * Lp[r] + tt] = np.asarray(A[:tail_src], dtype=np.float32)
+    A32[ptail:] = np.asarray(A[tail_src:], dtype=np.float32)
+    if v_rows_only:
+        blk = np.repeat(np.arange(N2), 6 * Lp)
+        kk = (np.arange(ptail) - p32[blk]) // Lp[blk]
+        written[:ptail] = kk >= 3
+    return cols32, A32, written
+
+
+def drows_entries(N2, rowptr, nadj_ptr):
+    """The entries of the d rows (value rows 0 .. 2 of every node) and where the pair form keeps them: (entry, slot) with slot
+    the index into the [pairs x 6] pair array or -1 where the forms leave a structural zero"""
+    rows = (6 * np.arange(N2)[:, None] + np.arange(3)).ravel()
+    L = rowptr[rows + 1] - rowptr[rows]
+    row = np.repeat(rows, L)
+    entry = np.repeat(rowptr[rows], L) + (np.arange(L.sum()) - np.repeat(np.concatenate([[0], np.cumsum(L)[:-1]]), L))
+    r, i = row // 6, row % 6
+    t = entry - rowptr[row]
+    c = t % 6
+    deg6 = 6 * (nadj_ptr[r + 1] - nadj_ptr[r])
+    kept = (t < deg6) & ((c == i) | (c == i + 3))
+    slot = np.where(kept, 6 * (nadj_ptr[r] + t // 6) + np.where(c == i, i, 3 + i), -1)
+    return entry, slot
+
+
+def drows_extract(N2, rowptr, A, nadj_ptr):
+    """k_drows_extract: the d rows in pair form [dd_0 dd_1 dd_2 dv_0 dv_1 dv_2] per node pair (row (r, i) keeps, for neighbour k,
+    the entries of columns d_i and v_i), and the verdict: True if any other entry of a d row is not exactly zero"""
+    entry, slot = drows_entries(N2, rowptr, nadj_ptr)
+    ad = np.zeros(6 * int(nadj_ptr[N2]), dtype=np.float64)
+    kept = slot >= 0
+    ad[slot[kept]] = A[entry[kept]]
+    return ad, bool(np.any(A[entry[~kept]] != 0.0))
+
+
+def drows_expand(N2, rowptr, ad, nadj_ptr, nnz):
+    """The inverse of drows_extract: a length-nnz array holding the d rows the pair form stands for (zero elsewhere)"""
+    entry, slot = drows_entries(N2, rowptr, nadj_ptr)
+    out = np.zeros(nnz, dtype=np.float64)
+    kept = slot >= 0
+    out[entry[kept]] = np.asarray(ad, dtype=np.float64)[slot[kept]]
+    return out
+
+
+def csr_product(rowptr, cols, vals, x):
+    """(y, S, L) of y = A x in extended precision: y, sum_j |a_ij x_j| and the row lengths (float64)"""
+    n = len(rowptr) - 1
+    p = np.asarray(vals, dtype=np.longdouble) * np.asarray(x, dtype=np.longdouble)[cols]
+    y, S = np.zeros(n, dtype=np.longdouble), np.zeros(n, dtype=np.longdouble)
+    L = np.diff(rowptr)
+    nz = L > 0
+    if p.size:
+        y[nz] = np.add.reduceat(p, rowptr[:-1][nz])
+        S[nz] = np.add.reduceat(np.abs(p), rowptr[:-1][nz])
+    return y.astype(np.float64), S.astype(np.float64), L.astype(np.float64)

@@ -22,14 +22,7 @@ EPS = np.finfo(np.float64).eps
 C1, C2 = 0.61, 1.37
 
 
-def check(got, ref, bound, what):
-    got, ref, bound = (np.asarray(a, dtype=np.float64).ravel() for a in (got, ref, bound))
-    err = np.abs(got - ref)
-    bad = ~(err <= bound)
-    if bad.any():
-        i = int(np.flatnonzero(bad)[0])
-        raise AssertionError(f"{what}: {bad.sum()} of {len(got)} outside the bound; first at {i}: got {got[i]!r}, "
-                             f"reference {ref[i]!r}, error {err[i]:.3e} > bound {bound[i]:.3e}")
+check = ks.check
 
 
 # ---- synthetic node graphs -------------------------------------------------------------------------------------------------

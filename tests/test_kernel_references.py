@@ -1,5 +1,6 @@
 """CPU self-tests of the host-side references the kernel tests build on (tests/kernel_shim.py), so that a failure of
-tests/test_gpu_gcr_kernels.py or tests/test_gpu_sweep_kernels.py is one of a kernel, not of its reference."""
+tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py or tests/test_gpu_product_kernels.py is one of a kernel, not of
+its reference."""
 import numpy as np
 import pytest
 
@@ -70,3 +71,157 @@ def test_fp16_record_emulation_round_trips():
 def test_tile_limit_is_the_librarys():
     """the synthetic limit cases build a tile of exactly TILE_LIMIT distinct neighbours: it must be the library's tile_limit()"""
     assert ks.load().shim_tile_limit() == ks.TILE_LIMIT
+
+
+# ---- the monolithic matrix's references (tests/test_gpu_product_kernels.py) ---------------------------------------------------
+def small_mono(N2, V, seed, **kw):
+    rng = np.random.default_rng(seed)
+    g = ks.mono_graph(N2, V, rng, **kw)
+    return rng, g, ks.expand_cols(N2, *g)
+
+
+MONO_CASES = [(1, 0, {}), (1, 1, {}), (5, 3, dict(diag_only=[2])), (37, 20, dict(heavy=[4], heavy_deg=[30], no_padj=[])),
+              (300, 120, dict(heavy=[0, 7], heavy_deg=[100, 60], diag_only=[299], max_deg=20))]
+
+
+@pytest.mark.parametrize("N2,V,kw", MONO_CASES)
+def test_monolithic_layout_is_the_node_graph_expanded(N2, V, kw):
+    """expand_cols against a loop over rows: the six columns of every neighbour, ascending, then the pressure columns"""
+    rng, (nadj_ptr, nadj, padj_ptr, padj, vrank), (rowptr, cols, diagpos) = small_mono(N2, V, N2 + V, **kw)
+    same_node = np.diff(np.repeat(np.arange(N2), np.diff(nadj_ptr))) == 0
+    assert np.all(np.diff(nadj)[same_node] > 0)                              # neighbours ascending
+    for row in range(6 * N2 + V):
+        r = row // 6 if row < 6 * N2 else int(vrank[row - 6 * N2])
+        want = [6 * int(s) + e for s in nadj[nadj_ptr[r]:nadj_ptr[r + 1]] for e in range(6)]
+        want += [6 * N2 + int(u) for u in padj[padj_ptr[r]:padj_ptr[r + 1]]]
+        got = cols[rowptr[row]:rowptr[row + 1]]
+        np.testing.assert_array_equal(got, want)
+        hit = np.flatnonzero(got == row)
+        assert diagpos[row] == (rowptr[row] + hit[0] if len(hit) else -1)
+    # every node row has its diagonal; a vertex node meets itself in its pressure neighbours
+    assert np.all(diagpos[:6 * N2] >= 0)
+    assert np.all(diagpos[6 * N2:] >= 0)
+
+
+def test_monolithic_graph_reaches_the_edges():
+    """the generator's knobs do what the GPU tests rely on: more than 64 neighbours, rows over 256 / 512 entries, a diagonal-only
+    node, node rows without pressure columns and pressure rows without a pressure column"""
+    N2, V = 400, 150
+    nadj_ptr, nadj, padj_ptr, padj, vrank = ks.mono_graph(N2, V, np.random.default_rng(3), heavy=[10, 11], heavy_deg=[95, 50],
+                                                         diag_only=[3], no_padj=range(40))
+    deg, pdeg = np.diff(nadj_ptr), np.diff(padj_ptr)
+    assert deg[10] >= 95 and deg[11] >= 50 and deg[3] == 1 and nadj[nadj_ptr[3]] == 3
+    L = 6 * deg + pdeg
+    assert L[10] > 512 and 256 < L[11] <= 512
+    assert not pdeg[:40].any() and pdeg[40:].any()
+    rowptr, cols, diagpos = ks.expand_cols(N2, nadj_ptr, nadj, padj_ptr, padj, vrank)
+    nodiag = vrank < 40
+    assert nodiag.any() and (~nodiag).any()
+    assert np.all(diagpos[6 * N2:][nodiag] == -1) and np.all(diagpos[6 * N2:][~nodiag] >= 0)
+
+
+@pytest.mark.parametrize("N2,V,kw", MONO_CASES)
+def test_padded_layout_covers_every_entry_once(N2, V, kw):
+    """pad_copy against a loop over nodes as fsi_capi.hip / k_pad_*32 state it; every entry of A lands once, padding is value 0
+    and column 0, the pressure rows follow unpadded; all four L mod 4 are met over the cases"""
+    rng, g, (rowptr, cols, diagpos) = small_mono(N2, V, N2 + V + 1, **kw)
+    nnz = int(rowptr[-1])
+    A = np.arange(1, nnz + 1, dtype=np.float64)                     # exact in FP32 here, and distinct
+    for v_rows_only in (False, True):
+        cols32, A32, written = ks.pad_copy(N2, rowptr, cols, A, v_rows_only)
+        p32, ptail, tail_src, nnz_tail = ks.pad_layout(N2, rowptr)
+        assert ptail + nnz_tail == len(A32) and tail_src == rowptr[6 * N2] and nnz_tail == nnz - tail_src
+        for r in range(N2):
+            s0, L = rowptr[6 * r], rowptr[6 * r + 1] - rowptr[6 * r]
+            Lp = (L + 3) // 4 * 4
+            assert p32[r + 1] - p32[r] == 6 * Lp and p32[r] % 24 == 0          # 16-byte aligned value and index rows
+            assert all(rowptr[6 * r + k] == s0 + k * L for k in range(6))
+            np.testing.assert_array_equal(cols32[p32[r] // 6:p32[r] // 6 + Lp], list(cols[s0:s0 + L]) + [0] * (Lp - L))
+            for k in range(6):
+                blk = A32[p32[r] + k * Lp:p32[r] + (k + 1) * Lp]
+                np.testing.assert_array_equal(blk, list(A[s0 + k * L:s0 + (k + 1) * L]) + [0] * (Lp - L))
+                assert written[p32[r] + k * Lp:p32[r] + (k + 1) * Lp].all() == (k >= 3 or not v_rows_only)
+        np.testing.assert_array_equal(A32[ptail:], A[tail_src:])
+        assert written[ptail:].all()
+        got = A32[written & (A32 != 0)]
+        want = A[:tail_src] if not v_rows_only else A[np.concatenate([np.arange(rowptr[6 * r + 3], rowptr[6 * r + 6]) for r in range(N2)])]
+        np.testing.assert_array_equal(np.sort(got), np.sort(np.concatenate([want, A[tail_src:]])))
+
+
+def test_padded_layout_meets_every_row_length_mod_4():
+    seen = set()
+    for N2, V, kw in MONO_CASES:
+        _, _, (rowptr, _, _) = small_mono(N2, V, N2 + V + 1, **kw)
+        seen |= set(((rowptr[6 * np.arange(N2) + 1] - rowptr[6 * np.arange(N2)]) % 4).tolist())
+    assert seen == {0, 1, 2, 3}
+
+
+def pair_matrix(N2, rowptr, rng, nadj_ptr):
+    """random values, the d rows reduced to the pair pattern"""
+    A = rng.uniform(-1, 1, int(rowptr[-1]))
+    entry, slot = ks.drows_entries(N2, rowptr, nadj_ptr)
+    A[entry[slot < 0]] = 0.0
+    return A
+
+
+@pytest.mark.parametrize("N2,V,kw", MONO_CASES)
+def test_pair_extraction_round_trips(N2, V, kw):
+    """extraction then expansion gives the d rows back; the pair values are the entries of columns d_i / v_i of each neighbour,
+    found through the column indices (not through positions)"""
+    rng, (nadj_ptr, nadj, padj_ptr, padj, vrank), (rowptr, cols, diagpos) = small_mono(N2, V, N2 + V + 2, **kw)
+    A = pair_matrix(N2, rowptr, rng, nadj_ptr)
+    ad, bad = ks.drows_extract(N2, rowptr, A, nadj_ptr)
+    assert not bad and len(ad) == 6 * len(nadj)
+    back = ks.drows_expand(N2, rowptr, ad, nadj_ptr, len(A))
+    drow = np.zeros(len(A), dtype=bool)
+    for r in range(N2):
+        drow[rowptr[6 * r]:rowptr[6 * r + 3]] = True
+    np.testing.assert_array_equal(back[drow], A[drow])
+    assert not back[~drow].any()
+    for r in range(N2):
+        for i in range(3):
+            row = 6 * r + i
+            c = dict(zip(cols[rowptr[row]:rowptr[row + 1]].tolist(), A[rowptr[row]:rowptr[row + 1]]))
+            for k in range(nadj_ptr[r], nadj_ptr[r + 1]):
+                s = int(nadj[k])
+                assert ad[6 * k + i] == c[6 * s + i] and ad[6 * k + 3 + i] == c[6 * s + 3 + i]
+
+
+@pytest.mark.parametrize("where", ["d column", "v column", "pressure column"])
+def test_pair_verdict_fires_on_one_off_pattern_entry(where):
+    N2, V = 37, 20
+    rng, (nadj_ptr, nadj, padj_ptr, padj, vrank), (rowptr, cols, diagpos) = small_mono(N2, V, 9, heavy=[4], heavy_deg=[30])
+    A = pair_matrix(N2, rowptr, rng, nadj_ptr)
+    assert not ks.drows_extract(N2, rowptr, A, nadj_ptr)[1]
+    r = int(np.argmax(np.diff(padj_ptr)))                     # a node with pressure columns
+    row = 6 * r + 1                                           # the d_y row of node r
+    rc = cols[rowptr[row]:rowptr[row + 1]]
+    want = {"d column": lambda c: c < 6 * N2 and c % 6 == 2, "v column": lambda c: c < 6 * N2 and c % 6 == 5,
+            "pressure column": lambda c: c >= 6 * N2}[where]
+    t = next(t for t, c in enumerate(rc.tolist()) if want(c))
+    B = A.copy()
+    B[rowptr[row] + t] = 2.0 ** -40
+    assert ks.drows_extract(N2, rowptr, B, nadj_ptr)[1]
+    # the same entry in a v row is none of the pair form's business
+    C = A.copy()
+    vrow = 6 * r + 4
+    C[rowptr[vrow] + t] = 0.5
+    assert not ks.drows_extract(N2, rowptr, C, nadj_ptr)[1]
+
+
+def test_shim_signatures_match_the_library_source():
+    """the ctypes argument codes of kernel_shim against the parameter lists of fsi_kernel_shim.hip (a wrong code would pass a
+    pointer where the library reads an int64, and a GPU test would fail for the wrong reason)"""
+    import re
+    src = (ks.LIB_PATH.parent / "csrc" / "fsi_kernel_shim.hip").read_text()
+    decl = {m.group(1): m.group(2) for m in re.finditer(r"^(?:int|double) (shim_\w+)\(([^)]*)\)", src, re.M)}
+
+    def code(param):
+        param = " ".join(param.split())
+        if "*" in param:
+            return "s" if param.startswith("const char*") else "p"
+        ty = param.rsplit(" ", 1)[0]
+        return {"int64_t": "l", "int": "i", "float": "f", "double": "d"}[ty]
+    for name, sig in ks._SIGS.items():
+        params = [p for p in decl[name].split(",") if p.strip()]
+        assert "".join(code(p) for p in params) == sig, name

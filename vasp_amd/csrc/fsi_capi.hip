@@ -1014,7 +1014,7 @@ int fsi_create_tuned(const FsiMeshDesc* mesh, const FsiParams* prm, int device, 
     HIPCHK(ctx->blk.alloc((size_t)20 * 3 * N2 + 16));
   }
   HIPCHK(hipMemsetAsync(ctx->A_pre.p, 0, ctx->nnz * sizeof(double), ctx->stream));
-  HIPCHK(ctx->iflags.alloc(n + 16));
+  HIPCHK(ctx->iflags.alloc(FsiCtx::IFLAG_BCMASK + n));
   // Krylov space: sized from free memory (the recycled directions are what 288 GB of HBM are used for)
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));

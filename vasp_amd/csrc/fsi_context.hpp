@@ -131,6 +131,8 @@ struct FsiCtx {
   fsi::DevBuf<double> cellvals;              // per-cell diagnostics (fsi_flow_stats)
   fsi::DevBuf<int32_t> gv_idx;               // fsi_get_values: solver indices of the requested dofs
   fsi::DevBuf<int32_t> iflags;               // device-side error / counters
+  // iflags slots: 0 .. 3 preconditioner checks and ILU(0) counters, 4 the d rows' pair-form verdict, 16 .. 16 + ndof - 1 bcmask
+  static constexpr int IFLAG_DROWS = 4, IFLAG_BCMASK = 16;
 
   // boundary data
   int64_t nbc = 0;

@@ -4,9 +4,11 @@
 // buffers and upload the inputs (outputs are uploaded too, so that a sentinel the caller placed shows whether the kernel wrote
 // where it must not), run ONE launch function on a private stream, synchronise, check hipGetLastError, copy the outputs back.
 // A null host pointer is passed to the launch as a null device pointer.  Status: 0 = ok, nonzero = HIP error
-// (shim_last_error() says which).
+// (shim_last_error() says which), or the launch function's own nonzero status passed through (LAUNCH_REFUSED of fsi_kernels.hpp:
+// the launch refused its arguments and launched nothing; the outputs are still copied back).
 //
 // Vectors of the node-block sweeps are float4 per node (component 3 is padding), as the preconditioner holds them.
+#include "fsi_host.hpp"
 #include "fsi_kernels.hpp"
 
 #include <cstring>
@@ -65,6 +67,15 @@ struct Call {
   do {                            \
     if (call.ok()) __VA_ARGS__;   \
     return call.finish(what);     \
+  } while (0)
+// as SHIM_RUN, for launch functions that return a status of their own
+#define SHIM_RUN_STATUS(call, what, ...)                                                   \
+  do {                                                                                     \
+    int st_ = 0;                                                                           \
+    if (call.ok()) st_ = __VA_ARGS__;                                                      \
+    if (const int e_ = call.finish(what)) return e_;                                       \
+    if (st_) g_err = std::string(what) + ": refused its arguments (status " + std::to_string(st_) + "), nothing launched"; \
+    return st_;                                                                            \
   } while (0)
 
 }  // namespace
@@ -393,11 +404,117 @@ int shim_sweep_schur_tiled(int tile_rows, int64_t n, int max_nu, const int64_t* 
 
 int shim_tile_limit() { return tile_limit(); }
 
+// ---- fsi_solver.hip: the monolithic matrix's structure and products -----------------------------------------------------------
+// Node graph: nadj_ptr [N2 + 1], nadj [npairs = nadj_ptr[N2]]; pressure graph: padj_ptr [N2 + 1], padj [padj_ptr[N2]]; vrank [V];
+// rows: 6 N2 node rows then V pressure rows, rowptr [6 N2 + V + 1], nnz = rowptr[6 N2 + V].  x and y: 6 N2 + V entries.
+int shim_expand_cols(int64_t N2, int64_t V, const int64_t* nadj_ptr, const int32_t* nadj, const int64_t* padj_ptr, const int32_t* padj,
+                     const int32_t* vrank, const int64_t* rowptr, int32_t* cols, int64_t* diagpos) {
+  Call c;
+  const int64_t n = 6 * N2 + V;
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const int32_t* dn = c.in(nadj, (size_t)nadj_ptr[N2]);
+  const int64_t* dpp = c.in(padj_ptr, (size_t)N2 + 1);
+  const int32_t* dpa = c.in(padj, (size_t)padj_ptr[N2]);
+  const int32_t* dvr = c.in(vrank, (size_t)V);
+  const int64_t* drp = c.in(rowptr, (size_t)n + 1);
+  int32_t* dc = c.io(cols, (size_t)rowptr[n]);
+  int64_t* ddp = c.io(diagpos, (size_t)n);
+  SHIM_RUN(c, "launch_expand_cols", launch_expand_cols(c.st, N2, V, dnp, dn, dpp, dpa, dvr, drp, dc, ddp));
+}
+// generic CSR over n rows; x: nx entries
+int shim_spmv(int64_t n, const int64_t* rowptr, const int32_t* cols, const double* vals, const double* x, int64_t nx, double* y, int tag) {
+  Call c;
+  const int64_t* drp = c.in(rowptr, (size_t)n + 1);
+  const int32_t* dc = c.in(cols, (size_t)rowptr[n]);
+  const double* dv = c.in(vals, (size_t)rowptr[n]);
+  const double* dx = c.in(x, (size_t)nx);
+  double* dy = c.io(y, (size_t)n);
+  SHIM_RUN(c, "launch_spmv", launch_spmv(c.st, n, drp, dc, dv, dx, dy, tag));
+}
+// vrank, nadj_ptr, nadj may each be null (npairs: the length of nadj, and ad64 holds 6 npairs)
+int shim_spmv_node6(int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals, const int32_t* vrank,
+                    const int64_t* nadj_ptr, const int32_t* nadj, int64_t npairs, const double* x, double* y, const double* ad64) {
+  Call c;
+  const int64_t n = 6 * N2 + V;
+  const int64_t* drp = c.in(rowptr, (size_t)n + 1);
+  const int32_t* dc = c.in(cols, (size_t)rowptr[n]);
+  const double* dv = c.in(vals, (size_t)rowptr[n]);
+  const PRowGraph g{c.in(vrank, (size_t)V), c.in(nadj_ptr, (size_t)N2 + 1), c.in(nadj, (size_t)npairs)};
+  const double* dx = c.in(x, (size_t)n);
+  double* dy = c.io(y, (size_t)n);
+  const double* dad = c.in(ad64, (size_t)(6 * npairs));
+  SHIM_RUN_STATUS(c, "launch_spmv_node6", launch_spmv_node6(c.st, N2, V, drp, dc, dv, g, dx, dy, dad));
+}
+// node rows only: rowptr [6 N2 + 1], A [rowptr[6 N2]]; ad64 / ad32 [6 nadj_ptr[N2]] (ad32 may be null); flag [1]
+int shim_drows_extract(int64_t N2, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr, double* ad64, float* ad32,
+                       int32_t* flag) {
+  Call c;
+  const int64_t npairs = nadj_ptr[N2];
+  const int64_t* drp = c.in(rowptr, (size_t)(6 * N2) + 1);
+  const double* dA = c.in(A, (size_t)rowptr[6 * N2]);
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  double* d64 = c.io(ad64, (size_t)(6 * npairs));
+  float* d32 = c.io(ad32, (size_t)(6 * npairs));
+  int32_t* df = c.io(flag, 1);
+  SHIM_RUN(c, "launch_drows_extract", launch_drows_extract(c.st, N2, drp, dA, dnp, d64, d32, df));
+}
+// p32 [N2 + 1] (entries, six value rows per node block); cols32 [p32[N2] / 6]
+int shim_pad_cols32(int64_t N2, const int64_t* rowptr, const int32_t* cols, const int64_t* p32, int32_t* cols32) {
+  Call c;
+  const int64_t* drp = c.in(rowptr, (size_t)(6 * N2) + 1);
+  const int32_t* dc = c.in(cols, (size_t)rowptr[6 * N2]);
+  const int64_t* dp = c.in(p32, (size_t)N2 + 1);
+  int32_t* dc32 = c.io(cols32, (size_t)(p32[N2] / 6));
+  SHIM_RUN(c, "launch_pad_cols32", launch_pad_cols32(c.st, N2, drp, dc, dp, dc32));
+}
+// A [rowptr[6 N2 + V]]; A32 [n32]
+int shim_pad_vals32(int64_t N2, int64_t V, const int64_t* rowptr, const double* A, const int64_t* p32, int64_t ptail, int64_t nnz_tail,
+                    int64_t tail_src, float* A32, int64_t n32, int v_rows_only) {
+  Call c;
+  const int64_t* drp = c.in(rowptr, (size_t)(6 * N2 + V) + 1);
+  const double* dA = c.in(A, (size_t)rowptr[6 * N2 + V]);
+  const int64_t* dp = c.in(p32, (size_t)N2 + 1);
+  float* d32 = c.io(A32, (size_t)n32);
+  SHIM_RUN(c, "launch_pad_vals32", launch_pad_vals32(c.st, N2, V, drp, dA, dp, ptail, nnz_tail, tail_src, d32, v_rows_only != 0));
+}
+// vals [n32]; the pressure rows' values at vals + tail_shift + rowptr[row]; ad32 [6 npairs] or null
+int shim_spmv_node6p(int64_t N2, int64_t V, const int64_t* p32, const int32_t* cols32, const float* vals, int64_t n32, const int64_t* rowptr,
+                     const int32_t* cols, int64_t tail_shift, const int32_t* vrank, const int64_t* nadj_ptr, const int32_t* nadj, int64_t npairs,
+                     const double* x, double* y, const float* ad32) {
+  Call c;
+  const int64_t n = 6 * N2 + V;
+  const int64_t* dp = c.in(p32, (size_t)N2 + 1);
+  const int32_t* dc32 = c.in(cols32, (size_t)(p32[N2] / 6));
+  const float* dv = c.in(vals, (size_t)n32);
+  const int64_t* drp = c.in(rowptr, (size_t)n + 1);
+  const int32_t* dc = c.in(cols, (size_t)rowptr[n]);
+  const PRowGraph g{c.in(vrank, (size_t)V), c.in(nadj_ptr, (size_t)N2 + 1), c.in(nadj, (size_t)npairs)};
+  const double* dx = c.in(x, (size_t)n);
+  double* dy = c.io(y, (size_t)n);
+  const float* dad = c.in(ad32, (size_t)(6 * npairs));
+  SHIM_RUN_STATUS(c, "launch_spmv_node6p", launch_spmv_node6p(c.st, N2, V, dp, dc32, dv, drp, dc, tail_shift, g, dx, dy, dad));
+}
+// n rows; A (in place), Apre [rowptr[n]]; bc [nbc] (may repeat); rowscale, bcmask [n]
+int shim_matrix_finish(int64_t n, const int64_t* rowptr, const int64_t* diagpos, double* A, const double* Apre, const int32_t* bc,
+                       int64_t nbc, double* rowscale, int32_t* bcmask) {
+  Call c;
+  const int64_t* drp = c.in(rowptr, (size_t)n + 1);
+  const int64_t* ddp = c.in(diagpos, (size_t)n);
+  double* dA = c.io(A, (size_t)rowptr[n]);
+  const double* dpre = c.in(Apre, (size_t)rowptr[n]);
+  const int32_t* dbc = c.in(bc, (size_t)nbc);
+  double* drs = c.io(rowscale, (size_t)n);
+  int32_t* dbm = c.io(bcmask, (size_t)n);
+  SHIM_RUN(c, "launch_matrix_finish", launch_matrix_finish(c.st, n, drp, ddp, dA, dpre, dbc, nbc, drs, dbm));
+}
+
 // ---- a live context's preconditioner arrays (FsiCtx of fsi_context.hpp, as the library was compiled) -----------------------
-// shim_ctx_info: N2, V, nS, sb_nblocks, tiled, tile_nodes, tile_max_nu, schur_tiled, schur_tile, s_tile_max_nu, sweeps_fp16
+// shim_ctx_info: N2, V, nS, sb_nblocks, tiled, tile_nodes, tile_max_nu, schur_tiled, schur_tile, s_tile_max_nu, sweeps_fp16,
+// a32_ptail, a32_tail_src, a32_tail_nnz, op32_ok, kry_fp32, drows_ok
 int shim_ctx_info(const FsiCtx* ctx, int64_t* out, int nout) {
   const int64_t v[] = {ctx->N2, ctx->V, ctx->nS, ctx->sb_nblocks, ctx->tiled, ctx->tile_nodes, ctx->tile_max_nu,
-                       ctx->schur_tiled, ctx->schur_tile, ctx->s_tile_max_nu, ctx->sweeps_fp16};
+                       ctx->schur_tiled, ctx->schur_tile, ctx->s_tile_max_nu, ctx->sweeps_fp16,
+                       ctx->a32_ptail, ctx->a32_tail_src, ctx->a32_tail_nnz, ctx->op32_ok, ctx->kry_fp32, ctx->drows_ok};
   const int k = (int)(sizeof(v) / sizeof(v[0]));
   for (int i = 0; i < nout && i < k; ++i) out[i] = v[i];
   return k;
@@ -413,7 +530,8 @@ int shim_ctx_array(const FsiCtx* ctx, const char* name, void* host, int64_t* cou
                          E(tile_ulist), E(vv_db32),   E(vv_rec),  E(sb_ptr),     E(sb_col),      E(sb_vals),     E(sb_rec),
                          E(sb_binv12),  E(s_rowptr),  E(s_cols),  E(s_diagpos),  E(s_vals),      E(s_vals32),    E(s_rec),
                          E(s_ploc),     E(s_tile_uptr), E(s_tile_ulist), E(s_dinv), E(dd_db),    E(rowscale),    E(snode),
-                         E(solver2user), E(node_solid)};
+                         E(solver2user), E(node_solid), E(rowptr),    E(cols),        E(diagpos),     E(A),           E(vrank),
+                         E(padj_ptr),   E(padj),      E(A32),     E(a32_ptr),    E(a32_cols),    E(Ad64),        E(Ad32)};
 #undef E
   for (const Entry& t : table) {
     if (std::strcmp(t.name, name) != 0) continue;
@@ -427,6 +545,28 @@ int shim_ctx_array(const FsiCtx* ctx, const char* name, void* host, int64_t* cou
   }
   g_err = std::string("shim_ctx_array: unknown array ") + name;
   return 2;
+}
+
+// y = the context's monolithic product of x (solver ordering, row-equilibrated: no permutation, no un-scaling), through
+// fsi::host::spmv(ctx, x, y, working); x, y [ndof].  counters [2]: what the call added to op32_products and drows_products.
+// Status: 0, 1 = HIP error, else the FSI_ERR_* of host::spmv (ctx->err in shim_last_error()).
+int shim_ctx_spmv(FsiCtx* ctx, int working, const double* x, double* y, int64_t* counters) {
+  Call c;
+  const int64_t n = ctx->ndof;
+  const double* dx = c.in(x, (size_t)n);
+  double* dy = c.io(y, (size_t)n);
+  if (c.ok()) c.note(hipSetDevice(ctx->device));
+  const int64_t op0 = ctx->op32_products, dr0 = ctx->drows_products;
+  int rc = 0;
+  if (c.ok()) {
+    rc = fsi::host::spmv(ctx, dx, dy, working != 0);
+    c.note(hipStreamSynchronize(ctx->stream));
+  }
+  counters[0] = ctx->op32_products - op0;
+  counters[1] = ctx->drows_products - dr0;
+  if (const int e = c.finish("host::spmv")) return e;
+  if (rc) g_err = "host::spmv: " + ctx->err;
+  return rc;
 }
 
 }  // extern "C"

@@ -171,9 +171,12 @@ void launch_pad_vals32(hipStream_t st, int64_t N2, int64_t V, const int64_t* row
 // something else and the products must keep the full rows
 void launch_drows_extract(hipStream_t st, int64_t N2, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr, double* ad64,
                           float* ad32, int32_t* flag);
-void launch_spmv_node6p(hipStream_t st, int64_t N2, int64_t V, const int64_t* p32, const int32_t* cols32, const float* vals,
-                        const int64_t* rowptr, const int32_t* cols, int64_t tail_shift, const PRowGraph& g, const double* x, double* y,
-                        const float* ad32 = nullptr);
+// status of the products that can refuse their arguments: 0 launched, LAUNCH_REFUSED nothing launched (d rows in pair form without
+// the node graph they are indexed by)
+constexpr int LAUNCH_REFUSED = 2;
+int launch_spmv_node6p(hipStream_t st, int64_t N2, int64_t V, const int64_t* p32, const int32_t* cols32, const float* vals,
+                       const int64_t* rowptr, const int32_t* cols, int64_t tail_shift, const PRowGraph& g, const double* x, double* y,
+                       const float* ad32 = nullptr);
 void launch_round_to_f32(hipStream_t st, int64_t n, const double* a, float* b);
 void launch_spmv(hipStream_t st, int64_t n, const int64_t* rowptr, const int32_t* cols, const double* vals,
                  const double* x, double* y, int tag = SPMV_FIELD_BLOCK);
@@ -294,8 +297,8 @@ void launch_mg_prolong(hipStream_t st, int64_t N2, const int32_t* par, const flo
                        float* e4);
 void launch_residual_rows(hipStream_t st, int64_t nrows, const int32_t* rows, const int64_t* ptr, const int32_t* col,
                           const int64_t* src, const double* vals, const double* x, const double* b, double* y);
-void launch_spmv_node6(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals,
-                       const PRowGraph& g, const double* x, double* y, const double* ad64 = nullptr);
+int launch_spmv_node6(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals,
+                      const PRowGraph& g, const double* x, double* y, const double* ad64 = nullptr);      // status: LAUNCH_REFUSED above
 void launch_sweep_csr_mixed(hipStream_t st, int64_t n, const int64_t* rowptr, const int32_t* cols, const float* vals,
                             const int64_t* diagpos, const double* dvals, double c1, double c2, const double* din, double* dout,
                             double* x, double* r);

@@ -52,7 +52,7 @@ int fsi_assemble_jacobian(FsiCtx* ctx) {
                     ctx->rowptr.p, ctx->nadj_ptr.p, ctx->A.p, cell_colours(ctx), ctx->tune.jacobian_waves, ctx->tune.jacobian_mfma);
     if (getenv("FSI_DEBUG")) { HIPCHK(hipStreamSynchronize(ctx->stream)); fprintf(stderr, "[fsi] jacobian kernel done\n"); fflush(stderr); }
     launch_matrix_finish(ctx->stream, ctx->ndof, ctx->rowptr.p, ctx->diagpos.p, ctx->A.p, ctx->A_pre.p, ctx->mbc_dofs.p,
-                         ctx->nmbc, ctx->rowscale.p, ctx->iflags.p + 16);
+                         ctx->nmbc, ctx->rowscale.p, ctx->iflags.p + FsiCtx::IFLAG_BCMASK);
     HIPCHK(hipGetLastError());
     if (getenv("FSI_DEBUG")) { HIPCHK(hipStreamSynchronize(ctx->stream)); fprintf(stderr, "[fsi] matrix finish done\n"); fflush(stderr); }
   }
@@ -76,10 +76,10 @@ int fsi_assemble_jacobian(FsiCtx* ctx) {
     const size_t npairs6 = 6 * (size_t)ctx->nadj.n;
     if (!ctx->Ad64.p) HIPCHK(ctx->Ad64.alloc(npairs6));
     if (copy32 && !ctx->Ad32.p) HIPCHK(ctx->Ad32.alloc(npairs6));
-    HIPCHK(hipMemsetAsync(ctx->iflags.p + 20, 0, sizeof(int32_t), ctx->stream));
-    launch_drows_extract(ctx->stream, ctx->N2, ctx->rowptr.p, ctx->A.p, ctx->nadj_ptr.p, ctx->Ad64.p, copy32 ? ctx->Ad32.p : nullptr, ctx->iflags.p + 20);
+    HIPCHK(hipMemsetAsync(ctx->iflags.p + FsiCtx::IFLAG_DROWS, 0, sizeof(int32_t), ctx->stream));
+    launch_drows_extract(ctx->stream, ctx->N2, ctx->rowptr.p, ctx->A.p, ctx->nadj_ptr.p, ctx->Ad64.p, copy32 ? ctx->Ad32.p : nullptr, ctx->iflags.p + FsiCtx::IFLAG_DROWS);
     int32_t found = 1;
-    HIPCHK(hipMemcpyAsync(&found, ctx->iflags.p + 20, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&found, ctx->iflags.p + FsiCtx::IFLAG_DROWS, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ctx->drows_ok = found == 0;
     if (getenv("FSI_DEBUG")) fprintf(stderr, "[fsi] displacement rows of the outer product in pair form: %s\n", ctx->drows_ok ? "yes" : "no (other entries found)");

@@ -392,17 +392,21 @@ static void spmv_node6_any(hipStream_t st, int64_t N2, int64_t V, const int64_t*
   else hipLaunchKernelGGL((k_spmv_node6<VT, false>), dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, vals, x, y);
   spmv_prows<VT>(st, N2, V, rowptr, cols, vals, g, x, y);      // pressure rows
 }
-// ad64 != nullptr: the d rows from their pair form (k_drows_extract found nothing else in them)
-void launch_spmv_node6(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals,
-                       const PRowGraph& g, const double* x, double* y, const double* ad64) {
-  if (ad64 && g.nadj_ptr && g.nadj) {
+// ad64 != nullptr: the d rows from their pair form (k_drows_extract found nothing else in them).  The pair form is indexed by the
+// node graph: without it nothing is launched and LAUNCH_REFUSED returned (the six-row kernel instead would read d rows that a
+// pair-form copy need not hold).
+int launch_spmv_node6(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals,
+                      const PRowGraph& g, const double* x, double* y, const double* ad64) {
+  if (ad64) {
+    if (!g.nadj_ptr || !g.nadj) return LAUNCH_REFUSED;
     int64_t blocks = (N2 + 3) / 4;
     blocks = (blocks + 7) & ~(int64_t)7;
     hipLaunchKernelGGL(k_spmv_node6c<true>, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, vals, g.nadj_ptr, g.nadj, ad64, x, y);
     spmv_prows<double>(st, N2, V, rowptr, cols, vals, g, x, y);
-    return;
+    return 0;
   }
   spmv_node6_any<double>(st, N2, V, rowptr, cols, vals, g, x, y);
+  return 0;
 }
 // ---- FP32 copy of the Jacobian in its own layout --------------------------------------------------------------------
 // The copy only serves k_spmv_node6p, so it is laid out for it: the six value rows of a node (and one row of column
@@ -522,17 +526,19 @@ void launch_pad_vals32(hipStream_t st, int64_t N2, int64_t V, const int64_t* row
   if (V > 0 && nnz_tail > 0) launch_round_to_f32(st, nnz_tail, A + tail_src, A32 + ptail);
 }
 // y = A32 x: padded node rows, then the pressure rows (their values at vals + ptail, indexed by the rows' own pointers
-// shifted by tail_shift = ptail - rowptr[6 N2])
-void launch_spmv_node6p(hipStream_t st, int64_t N2, int64_t V, const int64_t* p32, const int32_t* cols32, const float* vals,
-                        const int64_t* rowptr, const int32_t* cols, int64_t tail_shift, const PRowGraph& g, const double* x, double* y,
-                        const float* ad32) {
+// shifted by tail_shift = ptail - rowptr[6 N2]).  ad32 != nullptr: the d rows in pair form, which needs the node graph; without it
+// nothing is launched and LAUNCH_REFUSED returned (value rows 0 .. 2 of a copy made with v_rows_only hold nothing).
+int launch_spmv_node6p(hipStream_t st, int64_t N2, int64_t V, const int64_t* p32, const int32_t* cols32, const float* vals,
+                       const int64_t* rowptr, const int32_t* cols, int64_t tail_shift, const PRowGraph& g, const double* x, double* y,
+                       const float* ad32) {
   constexpr bool xcd = true;        // XCD-aware node mapping: -9 % HBM traffic (round 2)
-  if (ad32 && g.nadj_ptr && g.nadj) {      // d rows in pair form
+  if (ad32) {      // d rows in pair form
+    if (!g.nadj_ptr || !g.nadj) return LAUNCH_REFUSED;
     int64_t blocks = (N2 + 3) / 4;
     blocks = (blocks + 7) & ~(int64_t)7;
     hipLaunchKernelGGL(k_spmv_node6pc<true>, dim3((unsigned)blocks), dim3(256), 0, st, N2, p32, cols32, vals, g.nadj_ptr, g.nadj, ad32, x, y);
     spmv_prows<float>(st, N2, V, rowptr, cols, vals + tail_shift, g, x, y);
-    return;
+    return 0;
   }
   // one wave per node, no grid-stride loop: measured 1.87 ms per product against 2.23 ms with 8192 workgroups looping
   // (row lengths differ by 3x between edge and vertex nodes; the hardware scheduler balances what a static stride cannot)
@@ -545,6 +551,7 @@ void launch_spmv_node6p(hipStream_t st, int64_t N2, int64_t V, const int64_t* p3
   // the pressure-row kernels index values and columns with the rows' own pointers: hand them the value array shifted so that
   // vals32[rowptr[row]] is the row's first value
   spmv_prows<float>(st, N2, V, rowptr, cols, vals + tail_shift, g, x, y);
+  return 0;
 }
 __global__ __launch_bounds__(256) void k_round_to_f32(int64_t n, const double* __restrict__ a, float* __restrict__ b) {
   GRID_STRIDE(i, n) b[i] = (float)a[i];
