@@ -1,9 +1,11 @@
 """ctypes loader of ``vasp_amd/libfsi_kernel_shim.so`` (vasp_amd/csrc/fsi_kernel_shim.hip) and the host-side reference builders
-of the kernel tests (tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py, tests/test_gpu_product_kernels.py).
+of the kernel tests (tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py, tests/test_gpu_product_kernels.py,
+tests/test_gpu_coarse_kernels.py).
 
 The shim runs ONE ``fsi::launch_*`` call of libvaspfsi.so on host arrays; the builders restate, in numpy, what the library's
 host code hands those kernels: the LDS tiles of a graph (fsi_capi.hip, node tiles and Schur tiles), the FP16 records of
-k_pack_h1 / k_pack_h3 / k_pack_sb, and the monolithic matrix's column layout, padded FP32 copy and d-row pair form.  The builders are tested on the CPU (tests/test_kernel_references.py), so that a failure
+k_pack_h1 / k_pack_h3 / k_pack_sb, the monolithic matrix's column layout, padded FP32 copy and d-row pair form, and the P2 -> P1
+hierarchy of the two coarse levels with the contracts of their kernels.  The builders are tested on the CPU (tests/test_kernel_references.py), so that a failure
 of a GPU test is one of the kernel, not of its reference."""
 from __future__ import annotations
 
@@ -32,6 +34,12 @@ _SIGS = {
     "shim_expand_cols": "llpppppppp", "shim_spmv": "lpppplpi", "shim_spmv_node6": "llpppppplppp", "shim_drows_extract": "lpppppp",
     "shim_pad_cols32": "lpppp", "shim_pad_vals32": "llppplllpli", "shim_spmv_node6p": "llppplpplppplppp",
     "shim_matrix_finish": "lppppplpp", "shim_ctx_spmv": "pippp",
+    "shim_mg_d0": "lppppppp", "shim_mg_rap": "llpppppppppppppp", "shim_mg_coarse_finish": "llppppppppp",
+    "shim_mg_restrict": "llpppppppfppp", "shim_mg_prolong": "llppppp", "shim_sbmg_flags": "lpppp",
+    "shim_sbmg_rap": "lllppppppppppppppp", "shim_sbmg_coarse_finish": "llpppppppp", "shim_sbmg_restrict": "lllpppppppppppl",
+    "shim_sbmg_prolong": "llpppppppl", "shim_sb_binv": "llppplpp", "shim_sb_dinv": "llppplp", "shim_dinv_f32": "lppplp",
+    "shim_diag_inverse": "lpplp", "shim_block_scale_d": "lpp", "shim_solid_cycle_init": "llpppfpppp", "shim_gather3_f32": "llppp",
+    "shim_scatter3_f32": "llppp",
 }
 LAUNCH_REFUSED = 2           # fsi_kernels.hpp: a launch function refused its arguments and launched nothing
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "d": C.c_double, "s": C.c_char_p}
@@ -53,6 +61,8 @@ def load():
         lib.shim_last_error.restype = C.c_char_p
         lib.shim_ctx_ktheta.argtypes = [C.c_void_p]
         lib.shim_ctx_ktheta.restype = C.c_double
+        lib.shim_ctx_coarse.argtypes = [C.c_void_p, C.c_int32]
+        lib.shim_ctx_coarse.restype = C.c_double
         _lib = lib
     return _lib
 
@@ -91,11 +101,14 @@ def check(got, ref, bound, what):
 
 
 CTX_INFO = ("N2", "V", "nS", "sb_nblocks", "tiled", "tile_nodes", "tile_max_nu", "schur_tiled", "schur_tile", "s_tile_max_nu",
-            "sweeps_fp16", "a32_ptail", "a32_tail_src", "a32_tail_nnz", "op32_ok", "kry_fp32", "drows_ok")
+            "sweeps_fp16", "a32_ptail", "a32_tail_src", "a32_tail_nnz", "op32_ok", "kry_fp32", "drows_ok",
+            "mg_nc", "mg_cnnz", "mg_ready", "sbmg_nc", "sbmg_nblk", "sbmg_ready", "bcr_ready")
 _ELEM = {("f", 4): np.float32, ("f", 8): np.float64, ("i", 1): np.uint8, ("i", 2): np.uint16, ("i", 4): np.int32,
          ("i", 8): np.int64}
 _UNSIGNED = {"dd_rec", "vv_rec", "sb_rec", "s_rec"}
-_FLOAT = {"dd_chat", "vv_db32", "sb_vals", "sb_binv12", "s_vals", "s_vals32", "s_dinv", "dd_db", "rowscale", "A", "A32", "Ad64", "Ad32"}
+_FLOAT = {"dd_chat", "vv_db32", "sb_vals", "sb_binv12", "s_vals", "s_vals32", "s_dinv", "dd_db", "rowscale", "A", "A32", "Ad64", "Ad32",
+          "mg_pw", "mg_chw", "mg_Ac", "mg_cc", "mg_d0", "mg_dcinv4", "sbmg_pw", "sbmg_chw", "sbmg_cvals", "sbmg_cbinv12",
+          "sb_binv9", "sb_dinv", "dd_dinv32", "vvf_dinv32"}
 
 
 def ctx_info(ctx) -> dict:
@@ -115,6 +128,15 @@ def ctx_spmv(ctx, working, x, y):
 
 def ctx_ktheta(ctx) -> float:
     return float(load().shim_ctx_ktheta(ctx))
+
+
+COARSE = ("mg_gersh", "sbmg_gersh", "mg_clmax", "sbmg_clmax")
+
+
+def ctx_coarse(ctx) -> dict:
+    """the coarse levels' row-sum bounds (of the last rebuild) and the largest eigenvalues their Chebyshev intervals use"""
+    lib = load()
+    return {name: float(lib.shim_ctx_coarse(ctx, k)) for k, name in enumerate(COARSE)}
 
 
 def ctx_array(ctx, name: str) -> np.ndarray:
@@ -382,3 +404,348 @@ def csr_product(rowptr, cols, vals, x):
         y[nz] = np.add.reduceat(p, rowptr[:-1][nz])
         S[nz] = np.add.reduceat(np.abs(p), rowptr[:-1][nz])
     return y.astype(np.float64), S.astype(np.float64), L.astype(np.float64)
+
+
+# ---- the two-level coarse levels (fsi_capi.hip hierarchy builder; fsi_block.hip k_mg_* / k_sbmg_*) and the diagonal scalings --
+U32 = 2.0 ** -24
+UFC_EDGES = ((2, 3), (1, 3), (1, 2), (0, 3), (0, 2), (0, 1))      # local edge e of a P2 tet joins these local vertices
+
+
+def edge_ends(tet_nodes, N2, V):
+    """[N2][2] end vertices of every edge-midpoint node (-1 for vertices), as the library takes them: from the LAST cell in the
+    order given that holds the edge, in that cell's local vertex order (so an edge's two ends may come either way round)"""
+    tn = np.asarray(tet_nodes, dtype=np.int64).reshape(-1, 10)
+    nd = tn[:, 4:].ravel()
+    a = tn[:, [e[0] for e in UFC_EDGES]].ravel()
+    b = tn[:, [e[1] for e in UFC_EDGES]].ravel()
+    u, first_rev = np.unique(nd[::-1], return_index=True)
+    last = len(nd) - 1 - first_rev
+    ends = np.full((N2, 2), -1, dtype=np.int64)
+    ends[u, 0], ends[u, 1] = a[last], b[last]
+    return ends
+
+
+def children(par, pw, nc):
+    """(chptr, child, chw): the transpose of the parent lists, per coarse node its fine nodes in ascending order with the weights"""
+    par, pw = np.asarray(par).reshape(-1, 2), np.asarray(pw, dtype=np.float32).reshape(-1, 2)
+    fine = np.repeat(np.arange(len(par)), 2)
+    keep = pw.ravel() != 0
+    p, f, w = par.ravel()[keep].astype(np.int64), fine[keep], pw.ravel()[keep]
+    o = np.argsort(p, kind="stable")                                # fine nodes stay ascending within a coarse node
+    chptr = np.concatenate([[0], np.cumsum(np.bincount(p, minlength=nc))]).astype(np.int64)
+    return chptr, f[o].astype(np.int32), w[o].astype(np.float32)
+
+
+def _vertex_pairs(tet_nodes):
+    """(i, j) of every two vertices that share a cell (itself included), unique"""
+    tv = np.asarray(tet_nodes, dtype=np.int64).reshape(-1, 10)[:, :4]
+    i, j = np.repeat(tv, 4, axis=1).ravel(), np.tile(tv, (1, 4)).ravel()
+    code = np.unique(i * (tv.max() + 1) + j)
+    return code // (tv.max() + 1), code % (tv.max() + 1)
+
+
+def p1_hierarchy(tet_nodes, V, rank2node, snode=None):
+    """The P2 -> P1 hierarchy fsi_capi.hip builds, restated.  tet_nodes: [cells][10] in the library's cell order, rank2node: node
+    of every solver rank (node = solver2user[6 r] // 3).  Displacement level (snode None): coarse node i = the i-th vertex in rank
+    order (cfine[i] its rank); par / pw [N2][2]: a vertex its own coarse node with weights (1, 0), a midpoint its edge's two ends
+    (edge_ends) with (1/2, 1/2); chptr / child / chw their transpose in fine-rank order; cptr / ccol: the vertices that share a
+    cell with coarse node i, ascending.  Compact solid level (snode: the ranks of the solid nodes, ascending; fine node = index
+    into snode): the same on the solid nodes, cfine holding compact indices; None where an edge's end vertex is not a solid node
+    (the library then switches the level off)."""
+    rank2node = np.asarray(rank2node, dtype=np.int64)
+    N2 = len(rank2node)
+    rk = np.empty(N2, dtype=np.int64)
+    rk[rank2node] = np.arange(N2)
+    ends = edge_ends(tet_nodes, N2, V)
+    pi, pj = _vertex_pairs(tet_nodes)
+    if snode is None:
+        fine_rank = np.arange(N2)
+    else:
+        fine_rank = np.asarray(snode, dtype=np.int64)
+    nf = len(fine_rank)
+    fidx = np.full(N2, -1, dtype=np.int64)                           # rank -> fine index
+    fidx[fine_rank] = np.arange(nf)
+    is_v = rank2node[fine_rank] < V
+    cfine = np.flatnonzero(is_v)
+    cidx = np.full(nf, -1, dtype=np.int64)
+    cidx[cfine] = np.arange(len(cfine))
+    nc = len(cfine)
+    par = np.zeros((nf, 2), dtype=np.int64)
+    pw = np.zeros((nf, 2), dtype=np.float32)
+    par[cfine, 0] = par[cfine, 1] = cidx[cfine]
+    pw[cfine, 0] = 1.0
+    mid = np.flatnonzero(~is_v)
+    e = ends[rank2node[fine_rank[mid]]]
+    assert (e >= 0).all() and (e < V).all(), "a midpoint without its edge"
+    fe = fidx[rk[e]]
+    if (fe < 0).any():
+        return None
+    par[mid] = cidx[fe]
+    pw[mid] = 0.5
+    chptr, child, chw = children(par, pw, nc)
+    # coarse pattern: vertex pairs sharing a cell, both coarse nodes of this level; ascending in rank = ascending in coarse index
+    ci = np.where(fidx[rk[pi]] >= 0, cidx[np.maximum(fidx[rk[pi]], 0)], -1)
+    cj = np.where(fidx[rk[pj]] >= 0, cidx[np.maximum(fidx[rk[pj]], 0)], -1)
+    keep = (ci >= 0) & (cj >= 0)
+    code = np.unique(ci[keep] * nc + cj[keep])
+    cptr = np.concatenate([[0], np.cumsum(np.bincount(code // nc, minlength=nc))]).astype(np.int64)
+    return dict(nc=nc, par=par.ravel().astype(np.int32), pw=pw.ravel(), chptr=chptr, child=child, chw=chw, cptr=cptr,
+                ccol=(code % nc).astype(np.int32), cfine=cfine.astype(np.int32))
+
+
+def prolongation(par, pw, nc):
+    """P as scipy CSR [fine x coarse]: P[a, par[a][k]] = pw[a][k]"""
+    import scipy.sparse as sp
+    par, pw = np.asarray(par, dtype=np.int64).reshape(-1, 2), np.asarray(pw, dtype=np.float64).reshape(-1, 2)
+    n = len(par)
+    return sp.csr_matrix((pw.ravel(), (np.repeat(np.arange(n), 2), par.ravel())), shape=(n, nc))
+
+
+def galerkin(P, A0, free):
+    """P^T A0_free P, A0_free = A0 with the rows and columns of the non-free (Dirichlet / identity) fine nodes removed"""
+    import scipy.sparse as sp
+    Df = sp.diags(np.asarray(free, dtype=np.float64))
+    return (P.T @ (Df @ A0 @ Df) @ P).tocsr()
+
+
+def _coarse_lookup(cptr, ccol, nc, i, j):
+    """entry of column j in coarse row i (the last such entry), -1 where the row has none"""
+    row = np.repeat(np.arange(nc), np.diff(cptr))
+    key = row * np.int64(nc) + np.asarray(ccol, dtype=np.int64)
+    o = np.argsort(key, kind="stable")
+    ks_ = key[o]
+    q = np.asarray(i, dtype=np.int64) * nc + np.asarray(j, dtype=np.int64)
+    pos = np.searchsorted(ks_, q, side="right") - 1
+    ok = (pos >= 0) & (ks_[np.maximum(pos, 0)] == q)
+    return np.where(ok, o[np.maximum(pos, 0)], -1)
+
+
+def _rap_terms(nc, chptr, child, chw, fptr, fcol, free, par, pw):
+    """every contribution of a RAP kernel in its walk order: coarse row i, child slot k, fine entry ee, parent j, the FP32 weight
+    product float(w_i w_j).  Children and neighbours that are not free are skipped, parent slots of weight 0 as well."""
+    nch = np.diff(chptr)
+    i = np.repeat(np.arange(nc), nch)
+    k = np.arange(len(child))
+    a = np.asarray(child, dtype=np.int64)
+    m = free[a]
+    i, k, a = i[m], k[m], a[m]
+    deg = fptr[a + 1] - fptr[a]
+    rep = np.repeat(np.arange(len(a)), deg)
+    ee = fptr[a][rep] + (np.arange(deg.sum()) - np.repeat(np.cumsum(deg) - deg, deg))
+    i, k, a = i[rep], k[rep], a[rep]
+    b = np.asarray(fcol, dtype=np.int64)[ee]
+    m = free[b]
+    i, k, a, ee, b = i[m], k[m], a[m], ee[m], b[m]
+    par, pw = np.asarray(par).reshape(-1, 2), np.asarray(pw, dtype=np.float32).reshape(-1, 2)
+    out = []
+    for pj in range(2):
+        wj = pw[b, pj]
+        m = wj != 0
+        ww = (np.asarray(chw, dtype=np.float32)[k[m]] * wj[m]).astype(np.float32)
+        out.append((i[m], k[m], a[m], ee[m], par[b[m], pj].astype(np.int64), ww))
+    return tuple(np.concatenate([o[t] for o in out]) for t in range(6))
+
+
+def _rap_gather(nc, cptr, ccol, i, j, terms, absterms):
+    """(sum, magnitude sum, count) per coarse entry of the contributions (i, j, term); missed: rows of <= 64 entries (the only
+    ones the kernels check, see k_mg_rap) that receive a contribution with no entry of its column"""
+    e = _coarse_lookup(cptr, ccol, nc, i, j)
+    n = int(cptr[-1])
+    L = np.zeros(n)
+    np.add.at(L, e[e >= 0], 1.0)
+    shape = (n,) + terms.shape[1:]
+    val, mag = np.zeros(shape), np.zeros(shape)
+    np.add.at(val, e[e >= 0], terms[e >= 0])
+    np.add.at(mag, e[e >= 0], absterms[e >= 0])
+    short = np.diff(cptr) <= 64
+    missed = bool(np.any((e < 0) & short[i]))
+    # every lane whose column occurs twice in a row takes the full sum
+    row = np.repeat(np.arange(nc), np.diff(cptr))
+    last = _coarse_lookup(cptr, ccol, nc, row, ccol)
+    return val[last], mag[last], L[last], missed
+
+
+def mg_d0(N2, nadj_ptr, nadj, db, rowscale, rowflag):
+    """k_mg_d0: d0[r] = float(db[3 e] / rowscale[6 r]) at the row's (last) diagonal pair e, 0 on a Dirichlet row (rowflag[3 r]) or a
+    row without a diagonal; mixed: a node whose three rowflags differ (flags[1] bit 32)"""
+    row = np.repeat(np.arange(N2), np.diff(nadj_ptr))
+    e = np.arange(len(row))
+    last = np.full(N2, -1, dtype=np.int64)
+    dg = np.asarray(nadj) == row
+    np.maximum.at(last, row[dg], e[dg])
+    f = np.asarray(rowflag).reshape(-1, 3)
+    d = np.where(last >= 0, np.asarray(db)[3 * np.maximum(last, 0)] / np.asarray(rowscale)[6 * np.arange(N2)], 0.0)
+    d = np.where(f[:, 0] != 0, 0.0, d)
+    mixed = bool(np.any((f[:, 0] != f[:, 1]) | (f[:, 0] != f[:, 2])))
+    return d.astype(np.float32), mixed
+
+
+def mg_rap(nc, chptr, child, chw, nadj_ptr, nadj, db, rowscale, rowflag, par, pw, cptr, ccol):
+    """k_mg_rap: Ac[e] = sum over the contributions to (i, ccol[e]) of (double)float(w_i w_j) * (db[3 ee] * (1 / rowscale[6 a])),
+    children a and neighbours b with rowflag[3 .] set skipped.  Returns (Ac, sum |terms|, count, missed) in FP64."""
+    free = np.asarray(rowflag).reshape(-1, 3)[:, 0] == 0
+    i, k, a, ee, j, ww = _rap_terms(nc, chptr, child, chw, np.asarray(nadj_ptr), nadj, free, par, pw)
+    t = ww.astype(np.float64) * (np.asarray(db)[3 * ee] * (1.0 / np.asarray(rowscale)[6 * a]))
+    return _rap_gather(nc, cptr, ccol, i, j, t, np.abs(t))
+
+
+def _row_sequential_sum(cptr, v):
+    """FP32 sum of v over each row in entry order, one rounding per addition (as a single thread adds)"""
+    n = len(cptr) - 1
+    L = np.diff(cptr)
+    s = np.zeros(n, dtype=np.float32)
+    v = np.asarray(v, dtype=np.float32)
+    for t in range(int(L.max()) if n else 0):
+        m = L > t
+        s[m] = (s[m] + v[cptr[:-1][m] + t]).astype(np.float32)
+    return s
+
+
+def mg_coarse_finish(nc, cptr, ccol, Ac, cfine, rowflag):
+    """k_mg_coarse_finish: d = Ac at the row's (last) diagonal entry, 0 without one; an identity row where the vertex's fine row is
+    a Dirichlet row or !(d > 0) (cc 1 on the diagonal entry, 0 elsewhere, cflag 1, dcinv 0), else cc = float(Ac / d),
+    dcinv = float(1 / d); dcinv4 pads 0; rowmax = the largest FP32 sum of |cc| over a row, added in entry order.
+    Returns (cc, cflag [3 nc], dcinv4 [4 nc], rowmax)."""
+    row = np.repeat(np.arange(nc), np.diff(cptr))
+    e = np.arange(len(row))
+    dg = np.full(nc, -1, dtype=np.int64)
+    m = np.asarray(ccol) == row
+    np.maximum.at(dg, row[m], e[m])
+    Ac = np.asarray(Ac, dtype=np.float64)
+    d = np.where(dg >= 0, Ac[np.maximum(dg, 0)], 0.0)
+    ident = (np.asarray(rowflag).reshape(-1, 3)[np.asarray(cfine, dtype=np.int64), 0] != 0) | ~(d > 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cc = np.where(ident[row], (e == dg[row]).astype(np.float64), Ac / d[row]).astype(np.float32)
+        di = np.where(ident, 0.0, 1.0 / d).astype(np.float32)
+    cflag = np.repeat(ident.astype(np.uint8), 3)
+    dcinv4 = np.zeros((nc, 4), dtype=np.float32)
+    dcinv4[:, :3] = di[:, None]
+    rs = np.abs(cc)
+    rowmax = _row_sequential_sum(cptr, rs).max() if nc else np.float32(0)
+    return cc, cflag, dcinv4.ravel(), np.float32(rowmax)
+
+
+def mg_restrict(nc, chptr, child, chw, d0, r4, dcinv4):
+    """k_mg_restrict: rc = dcinv * sum_k float(chw_k d0[a_k]) r[a_k] per component.  Returns (value, bound) [nc][3] in FP64, the
+    bound (L + 10) 2^-24 |dcinv| sum |terms| with L the children of the coarse node"""
+    a = np.asarray(child, dtype=np.int64)
+    w = (np.asarray(chw, dtype=np.float32) * np.asarray(d0, dtype=np.float32)[a]).astype(np.float64)
+    r = np.asarray(r4, dtype=np.float32).reshape(-1, 4)[a, :3].astype(np.float64)
+    t = w[:, None] * r
+    i = np.repeat(np.arange(nc), np.diff(chptr))
+    s, S = np.zeros((nc, 3)), np.zeros((nc, 3))
+    np.add.at(s, i, t)
+    np.add.at(S, i, np.abs(t))
+    di = np.asarray(dcinv4, dtype=np.float32).reshape(-1, 4)[:, :1].astype(np.float64)
+    L = np.diff(chptr)[:, None].astype(np.float64)
+    return di * s, (L + 10) * U32 * np.abs(di) * S
+
+
+def mg_prolong(par, pw, live, xc4):
+    """k_mg_prolong / k_sbmg_prolong: e[a] = pw0 x[par0] + pw1 x[par1] where live[a] (d0 != 0, resp. !flag), else 0.  Returns
+    (value, bound) [N][3]: bound 2 * 2^-24 (|pw0 x0| + |pw1 x1|), 0 on the rows that must be exactly zero"""
+    par, pw = np.asarray(par, dtype=np.int64).reshape(-1, 2), np.asarray(pw, dtype=np.float32).reshape(-1, 2).astype(np.float64)
+    x = np.asarray(xc4, dtype=np.float32).reshape(-1, 4)[:, :3].astype(np.float64)
+    u, v = pw[:, :1] * x[par[:, 0]], pw[:, 1:] * x[par[:, 1]]
+    live = np.asarray(live, dtype=bool)[:, None]
+    return np.where(live, u + v, 0.0), np.where(live, 2 * U32 * (np.abs(u) + np.abs(v)), 0.0)
+
+
+def sbmg_flags(nS, sb_ptr, sb_col, vals):
+    """k_sbmg_flags: 0 where each of the node's three rows has a non-zero outside the diagonal entry of its diagonal block, else 1"""
+    v = np.asarray(vals, dtype=np.float32).reshape(-1, 3, 3)[:sb_ptr[nS]]
+    row = np.repeat(np.arange(nS), np.diff(sb_ptr))
+    dg = np.asarray(sb_col)[:len(row)] == row
+    off = v != 0
+    off[dg] &= ~np.eye(3, dtype=bool)
+    per = np.zeros((nS, 3), dtype=np.int64)
+    np.add.at(per, row, off.any(axis=2).astype(np.int64))
+    return (~(per > 0).all(axis=1)).astype(np.uint8)
+
+
+def sbmg_rap(nc, chptr, child, chw, sb_ptr, sb_col, vals, snode, rowscale, flag, par, pw, cptr, ccol):
+    """k_sbmg_rap: cvals[e][c][t] = sum over the contributions of float(w_i w_j) * vals[ee][c][t] * float(1 / rowscale[6 r + 3 + c])
+    (r = snode[a]), flagged children / neighbours skipped.  Returns (cvals [n][9], sum |terms|, count, missed) in FP64."""
+    free = np.asarray(flag) == 0
+    i, k, a, ee, j, ww = _rap_terms(nc, chptr, child, chw, np.asarray(sb_ptr), sb_col, free, par, pw)
+    r = np.asarray(snode, dtype=np.int64)[a]
+    isc = (1.0 / np.asarray(rowscale)[6 * r[:, None] + 3 + np.arange(3)]).astype(np.float32).astype(np.float64)
+    v = np.asarray(vals, dtype=np.float32).reshape(-1, 3, 3)[ee].astype(np.float64)
+    t = (ww.astype(np.float64)[:, None, None] * v * isc[:, :, None]).reshape(-1, 9)
+    return _rap_gather(nc, cptr, ccol, i, j, t, np.abs(t))
+
+
+def inv3(a):
+    """inverse of [n][3][3] blocks by the adjugate in extended precision (np.longdouble); returns (inverse, det) in that type"""
+    a = np.asarray(a, dtype=np.longdouble).reshape(-1, 3, 3)
+    c = np.empty_like(a)
+    for r in range(3):
+        for s in range(3):
+            m = np.delete(np.delete(a, r, axis=1), s, axis=2)
+            c[:, s, r] = (-1) ** (r + s) * (m[:, 0, 0] * m[:, 1, 1] - m[:, 0, 1] * m[:, 1, 0])
+    det = a[:, 0, 0] * c[:, 0, 0] + a[:, 0, 1] * c[:, 1, 0] + a[:, 0, 2] * c[:, 2, 0]
+    with np.errstate(divide="ignore", invalid="ignore"):      # singular blocks: inf / nan, replaced by the callers' rules
+        return c / det[:, None, None], det
+
+
+def inverse_bound(a, inv, u, c=16.0):
+    """elementwise c u |A^-1| |A| |A^-1| of [n][3][3] blocks"""
+    ai, aa = np.abs(np.asarray(inv, dtype=np.float64)), np.abs(np.asarray(a, dtype=np.float64).reshape(-1, 3, 3))
+    return c * u * (ai @ aa @ ai)
+
+
+def sbmg_coarse_finish(nc, cptr, ccol, cvals, cfine, flag):
+    """k_sbmg_coarse_finish, the decisions and the exact parts: the (last) diagonal block a (identity without one); an identity row
+    where the fine vertex is flagged, the row has no diagonal block, !(det a > 0) or !(a00 > 0) - there every block of the row is
+    replaced by 0 and the diagonal one by I, cbinv = I, cflag 1.  Returns (ident [nc], cvals after, inverse reference [nc][3][3]
+    (extended precision, identity on identity rows), the diagonal blocks [nc][3][3])."""
+    row = np.repeat(np.arange(nc), np.diff(cptr))
+    e = np.arange(len(row))
+    dg = np.full(nc, -1, dtype=np.int64)
+    m = np.asarray(ccol) == row
+    np.maximum.at(dg, row[m], e[m])
+    cv = np.asarray(cvals, dtype=np.float32).reshape(-1, 3, 3)
+    a = np.tile(np.eye(3, dtype=np.float32), (nc, 1, 1))
+    a[dg >= 0] = cv[dg[dg >= 0]]
+    inv, det = inv3(a)
+    ident = (np.asarray(flag)[np.asarray(cfine, dtype=np.int64)] != 0) | (dg < 0) | ~(det > 0) | ~(a[:, 0, 0] > 0)
+    after = cv.copy()
+    irow = ident[row]
+    after[irow] = 0
+    after[irow & (e == dg[row])] = np.eye(3, dtype=np.float32)
+    inv[ident] = np.eye(3)
+    return ident, after.reshape(-1), inv, a
+
+
+def sbmg_rowmax(nc, cptr, cvals, cbinv12, ident):
+    """the largest row sum max_c sum_e sum_j |(B^-1 C_e)_cj| with the kernel's own B^-1 (cbinv12) on the blocks it kept; 1 on
+    identity rows.  Returns (value, bound) in FP64"""
+    b = np.asarray(cbinv12, dtype=np.float32).reshape(-1, 3, 4)[:, :, :3].astype(np.float64)
+    cv = np.asarray(cvals, dtype=np.float32).reshape(-1, 3, 3).astype(np.float64)
+    row = np.repeat(np.arange(nc), np.diff(cptr))
+    p = np.einsum("eck,ekj->ecj", b[row], cv)
+    pm = np.einsum("eck,ekj->ecj", np.abs(b[row]), np.abs(cv))
+    s, S = np.zeros((nc, 3)), np.zeros((nc, 3))
+    np.add.at(s, row, np.abs(p).sum(axis=2))
+    np.add.at(S, row, pm.sum(axis=2))
+    L = 3 * np.diff(cptr)[:, None] + 8.0
+    s = np.where(ident[:, None], 1.0, s)
+    bnd = np.where(ident[:, None], 0.0, L * U32 * S)
+    return float(s.max()) if nc else 0.0, float(bnd.max()) if nc else 0.0
+
+
+def sbmg_restrict(nc, chptr, child, chw, snode, rowscale, flag, cflag, r4):
+    """k_sbmg_restrict: rc = sum over the free children of chw r[a] / float(rowscale[6 snode[a] + 3 + c]), 0 on identity coarse
+    rows (cflag).  Returns (value, bound) [nc][3] in FP64, bound (L + 10) 2^-24 sum |terms|"""
+    a = np.asarray(child, dtype=np.int64)
+    i = np.repeat(np.arange(nc), np.diff(chptr))
+    m = (np.asarray(flag)[a] == 0) & (np.asarray(cflag)[i] == 0)
+    a, i = a[m], i[m]
+    w = np.asarray(chw, dtype=np.float32)[m].astype(np.float64)
+    rs = np.asarray(rowscale)[6 * np.asarray(snode, dtype=np.int64)[a][:, None] + 3 + np.arange(3)].astype(np.float32).astype(np.float64)
+    t = w[:, None] * np.asarray(r4, dtype=np.float32).reshape(-1, 4)[a, :3].astype(np.float64) / rs
+    s, S = np.zeros((nc, 3)), np.zeros((nc, 3))
+    np.add.at(s, i, t)
+    np.add.at(S, i, np.abs(t))
+    L = np.diff(chptr)[:, None].astype(np.float64)
+    return s, (L + 10) * U32 * S

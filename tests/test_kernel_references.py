@@ -1,6 +1,6 @@
 """CPU self-tests of the host-side references the kernel tests build on (tests/kernel_shim.py), so that a failure of
-tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py or tests/test_gpu_product_kernels.py is one of a kernel, not of
-its reference."""
+tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py, tests/test_gpu_product_kernels.py or
+tests/test_gpu_coarse_kernels.py is one of a kernel, not of its reference."""
 import numpy as np
 import pytest
 
@@ -225,3 +225,249 @@ def test_shim_signatures_match_the_library_source():
     for name, sig in ks._SIGS.items():
         params = [p for p in decl[name].split(",") if p.strip()]
         assert "".join(code(p) for p in params) == sig, name
+
+
+# ---- the two-level hierarchy and the coarse-level contracts (kernel_shim.p1_hierarchy, mg_* / sbmg_*) ------------------------
+def _mesh(which):
+    from vasp_amd.mesh import FsiMesh
+    from vasp_amd.meshgen import generate
+    from pathlib import Path
+    if which == "fixture":
+        return FsiMesh.read(Path(__file__).parent / "golden" / "offset_stenosis" / "offset_stenosis.h5")
+    g = generate(3000)
+    return FsiMesh.from_arrays(g["coords"], g["tets"], g["cell_markers"], g["facets"], g["facet_markers"])
+
+
+def _cell_graph(tet_nodes, rk, N2):
+    """pattern of a matrix on the P2 cell graph (nodes that share a cell), in rank order, as scipy CSR of ones"""
+    import scipy.sparse as sp
+    t = rk[np.asarray(tet_nodes, dtype=np.int64)]
+    i, j = np.repeat(t, 10, axis=1).ravel(), np.tile(t, (1, 10)).ravel()
+    G = sp.csr_matrix((np.ones(len(i)), (i, j)), shape=(N2, N2))
+    G.data[:] = 1.0
+    return G
+
+
+@pytest.mark.parametrize("which", ["fixture", "generated"])
+@pytest.mark.parametrize("order", ["identity", "random"])
+def test_p1_hierarchy_is_the_edge_structure(which, order):
+    mesh = _mesh(which)
+    V, N2 = mesh.num_vertices, mesh.num_nodes
+    rng = np.random.default_rng(5)
+    rank2node = np.arange(N2) if order == "identity" else rng.permutation(N2)
+    rk = np.empty(N2, dtype=np.int64)
+    rk[rank2node] = np.arange(N2)
+    cells = rng.permutation(len(mesh.tet_nodes))       # the library's cell order is its own: the orientation rule must not care
+    h = ks.p1_hierarchy(mesh.tet_nodes[cells], V, rank2node)
+    nc, par, pw = h["nc"], h["par"].reshape(-1, 2), h["pw"].reshape(-1, 2)
+    assert nc == V
+    cfine = h["cfine"].astype(np.int64)
+    np.testing.assert_array_equal(cfine, np.flatnonzero(rank2node < V))    # vertices in rank order
+    cnode = rank2node[cfine]
+    is_v = rank2node < V
+    np.testing.assert_array_equal(par[is_v, 0], np.searchsorted(cfine, np.flatnonzero(is_v)))
+    np.testing.assert_array_equal(par[is_v, 1], par[is_v, 0])
+    np.testing.assert_array_equal(pw[is_v], np.tile([1.0, 0.0], (V, 1)).astype(np.float32))
+    # every midpoint's parents are its edge's two ends, weights 1/2
+    mid = np.flatnonzero(~is_v)
+    ends = np.sort(cnode[par[mid]], axis=1)
+    np.testing.assert_array_equal(ends, mesh.edges[rank2node[mid] - V])
+    assert (pw[mid] == np.float32(0.5)).all()
+    # child / chw: exactly the transpose of par / pw, fine ranks ascending
+    P = ks.prolongation(par, pw, nc)
+    PT = P.T.tocsr()
+    PT.eliminate_zeros()
+    PT.sort_indices()
+    np.testing.assert_array_equal(h["chptr"], PT.indptr)
+    np.testing.assert_array_equal(h["child"], PT.indices)
+    np.testing.assert_array_equal(h["chw"], PT.data.astype(np.float32))
+    # ccol: exactly the pattern of P^T A P for a matrix A on the P2 cell graph
+    G = _cell_graph(mesh.tet_nodes, rk, N2)
+    Pat = (abs(P).T @ G @ abs(P)).tocsr()
+    Pat.sort_indices()
+    np.testing.assert_array_equal(h["cptr"], Pat.indptr)
+    np.testing.assert_array_equal(h["ccol"], Pat.indices)
+    # the compact solid variant on the nodes of the solid cells
+    solid = np.zeros(N2, dtype=bool)
+    solid[rk[mesh.tet_nodes[mesh.cell_markers == 2].ravel()]] = True
+    snode = np.flatnonzero(solid)
+    hs = ks.p1_hierarchy(mesh.tet_nodes[cells], V, rank2node, snode)
+    assert hs is not None and hs["nc"] == int((rank2node[snode] < V).sum())
+    Ps = ks.prolongation(hs["par"], hs["pw"], hs["nc"])
+    # the compact level is the full one restricted to the solid nodes
+    cmap = np.full(nc, -1, dtype=np.int64)
+    cmap[np.searchsorted(cfine, snode[hs["cfine"]])] = np.arange(hs["nc"])
+    Psub = P[snode].tocsc()[:, np.flatnonzero(cmap >= 0)]
+    assert abs(Psub - Ps).max() == 0 and Psub.nnz == Ps.nnz
+    Gs = G[snode][:, snode]
+    Pats = (abs(Ps).T @ Gs @ abs(Ps)).tocsr()
+    Pats.sort_indices()
+    np.testing.assert_array_equal(hs["cptr"], Pats.indptr)
+    np.testing.assert_array_equal(hs["ccol"], Pats.indices)
+    # refused: a midpoint in the set without one of its end vertices
+    r_mid = snode[~(rank2node[snode] < V)][0]
+    end0 = rk[mesh.edges[rank2node[r_mid] - V][0]]
+    assert ks.p1_hierarchy(mesh.tet_nodes[cells], V, rank2node, snode[snode != end0]) is None
+
+
+def test_edge_ends_follow_the_last_cell():
+    # two cells share the edge (0, 1), in opposite local order: the later cell decides
+    tn = np.array([[0, 1, 2, 3, 4, 5, 6, 7, 8, 9], [1, 0, 2, 10, 11, 12, 6, 13, 14, 9]], dtype=np.int64)
+    e = ks.edge_ends(tn, 15, 4)
+    assert tuple(e[9]) == (1, 0)            # local edge 5 = (0, 1) of the second cell: vertices 1, 0
+    assert tuple(ks.edge_ends(tn[::-1], 15, 4)[9]) == (0, 1)
+
+
+def test_galerkin_is_the_dense_product():
+    import scipy.sparse as sp
+    rng = np.random.default_rng(2)
+    nf, nc = 23, 7
+    par = rng.integers(0, nc, (nf, 2)).astype(np.int32)
+    pw = rng.random((nf, 2)).astype(np.float32)
+    pw[3] = (1.0, 0.0)
+    A = sp.random(nf, nf, density=0.3, random_state=3, format="csr") + sp.eye(nf)
+    free = np.ones(nf, dtype=bool)
+    free[[2, 11]] = False
+    Pd = np.zeros((nf, nc))
+    for a in range(nf):
+        for k in range(2):
+            Pd[a, par[a, k]] += pw[a, k]
+    Ad = A.toarray()
+    Ad[~free] = 0
+    Ad[:, ~free] = 0
+    np.testing.assert_allclose(ks.galerkin(ks.prolongation(par, pw, nc), A, free).toarray(), Pd.T @ Ad @ Pd, rtol=1e-14, atol=1e-14)
+
+
+def _small_level(rng, nc=30, nmid=50, deg=5):
+    """a random hierarchy (vertices + midpoints with two distinct parents), its fine graph and the full coarse pattern"""
+    import scipy.sparse as sp
+    N2 = nc + nmid
+    par = np.zeros((N2, 2), dtype=np.int32)
+    pw = np.zeros((N2, 2), dtype=np.float32)
+    par[:nc, 0] = par[:nc, 1] = np.arange(nc)
+    pw[:nc, 0] = 1.0
+    a = rng.integers(0, nc, nmid)
+    par[nc:, 0], par[nc:, 1] = a, (a + 1 + rng.integers(0, nc - 1, nmid)) % nc
+    pw[nc:] = 0.5
+    nadj_ptr, nadj = ks.local_graph(N2, rng, reach=N2, max_deg=deg)
+    chptr, child, chw = ks.children(par, pw, nc)
+    G = sp.csr_matrix((np.ones(len(nadj)), nadj, nadj_ptr), shape=(N2, N2))
+    P = ks.prolongation(par, pw, nc)
+    Pat = (abs(P).T @ G @ abs(P) + sp.eye(nc)).tocsr()
+    Pat.sort_indices()
+    return N2, par, pw, nadj_ptr, nadj, chptr, child, chw, Pat.indptr.astype(np.int64), Pat.indices.astype(np.int32), P
+
+
+def test_mg_rap_reference_is_the_galerkin_product():
+    """with dyadic weights every term is exact: the reference's sums equal P^T A0_free P, a0_ab = db_ab / rowscale_a"""
+    import scipy.sparse as sp
+    rng = np.random.default_rng(4)
+    N2, par, pw, nadj_ptr, nadj, chptr, child, chw, cptr, ccol, P = _small_level(rng)
+    nc = len(cptr) - 1
+    db = rng.standard_normal(3 * len(nadj))
+    rowscale = rng.uniform(0.5, 2.0, 6 * N2)
+    rowflag = np.zeros(3 * N2, dtype=np.uint8)
+    rowflag[3 * np.array([1, 40, 41])] = 1
+    Ac, S, L, missed = ks.mg_rap(nc, chptr, child, chw, nadj_ptr, nadj, db, rowscale, rowflag, par, pw, cptr, ccol)
+    assert not missed
+    row = np.repeat(np.arange(N2), np.diff(nadj_ptr))
+    A0 = sp.csr_matrix((db[0::3] / rowscale[6 * row], nadj, nadj_ptr), shape=(N2, N2))
+    G = ks.galerkin(P, A0, rowflag[0::3] == 0).toarray()
+    crow = np.repeat(np.arange(nc), np.diff(cptr))
+    np.testing.assert_allclose(Ac, G[crow, ccol], rtol=0, atol=1e-12 * np.abs(G).max())
+    assert (S >= np.abs(Ac)).all() and (L >= (S > 0)).all()
+    # a coarse pattern without one of the product's entries: reported in a row of <= 64 entries only
+    e = int(np.flatnonzero((ccol != crow) & (S > 0))[0])
+    cptr2 = cptr.copy()
+    cptr2[crow[e] + 1:] -= 1
+    assert ks.mg_rap(nc, chptr, child, chw, nadj_ptr, nadj, db, rowscale, rowflag, par, pw, cptr2, np.delete(ccol, e))[3]
+
+
+def test_mg_d0_and_finish_identity_rules():
+    N2 = 4
+    nadj_ptr = np.array([0, 2, 4, 5, 6], dtype=np.int64)
+    nadj = np.array([0, 1, 1, 0, 0, 3], dtype=np.int32)        # node 2 has no diagonal
+    db = np.arange(1.0, 19.0)
+    rowscale = np.full(6 * N2, 2.0)
+    rowflag = np.zeros(3 * N2, dtype=np.uint8)
+    rowflag[3:6] = 1                                            # node 1: Dirichlet
+    d0, mixed = ks.mg_d0(N2, nadj_ptr, nadj, db, rowscale, rowflag)
+    np.testing.assert_array_equal(d0, np.float32([1.0 / 2, 0, 0, 16.0 / 2]))
+    assert not mixed
+    rowflag[7] = 1
+    assert ks.mg_d0(N2, nadj_ptr, nadj, db, rowscale, rowflag)[1]
+    # finish: row 0 regular, row 1 Dirichlet vertex, row 2 diagonal <= 0, row 3 no diagonal
+    cptr = np.array([0, 2, 4, 6, 7], dtype=np.int64)
+    ccol = np.array([0, 1, 0, 1, 2, 3, 2], dtype=np.int32)
+    Ac = np.array([4.0, -1.0, 2.0, 3.0, -5.0, 1.0, 7.0])
+    cfine = np.array([0, 1, 2, 3], dtype=np.int32)
+    rowflag = np.zeros(12, dtype=np.uint8)
+    rowflag[3] = 1
+    cc, cflag, dcinv4, rowmax = ks.mg_coarse_finish(4, cptr, ccol, Ac, cfine, rowflag)
+    np.testing.assert_array_equal(cc, np.float32([1.0, -0.25, 0, 1, 1, 0, 0]))
+    np.testing.assert_array_equal(cflag, np.repeat(np.uint8([0, 1, 1, 1]), 3))
+    np.testing.assert_array_equal(dcinv4.reshape(-1, 4), np.float32([[0.25] * 3 + [0], [0] * 4, [0] * 4, [0] * 4]))
+    assert rowmax == np.float32(1.25)
+
+
+def test_sbmg_finish_identity_rules_and_block_inverse():
+    rng = np.random.default_rng(6)
+    blocks = [np.diag([3.0, 2.0, 4.0]) + 0.3 * rng.standard_normal((3, 3)),       # regular, non-symmetric
+              np.array([[1.0, 2, 0], [0, 0, 0], [0.5, 0, 1]]),                      # det = 0
+              np.diag([1.0, 1.0, -1.0]) + np.array([[0, 0.2, 0], [0, 0, 0], [0.1, 0, 0]]),   # det < 0
+              np.array([[-1.0, 0, 0.1], [0, -1, 0], [0, 0.3, 1]]),                  # a00 <= 0 with det > 0
+              np.diag([2.0, 2.0, 2.0])]                                              # fine vertex flagged
+    nc = len(blocks) + 1                                                             # + a row without a diagonal block
+    cptr = np.array([0, 2, 3, 4, 5, 6, 7], dtype=np.int64)
+    ccol = np.array([0, 5, 1, 2, 3, 4, 0], dtype=np.int32)
+    cv = np.zeros((7, 3, 3), dtype=np.float32)
+    for i, b in enumerate(blocks):
+        cv[cptr[i]] = b
+    cv[1] = rng.standard_normal((3, 3))
+    cv[6] = rng.standard_normal((3, 3))
+    flag = np.array([0, 0, 0, 0, 1, 0], dtype=np.uint8)
+    ident, after, inv, a = ks.sbmg_coarse_finish(nc, cptr, ccol, cv.ravel(), np.arange(nc, dtype=np.int32), flag)
+    np.testing.assert_array_equal(ident, [False, True, True, True, True, True])
+    after = after.reshape(-1, 3, 3)
+    np.testing.assert_array_equal(after[:2], cv[:2])                                  # a kept row is untouched
+    for e in (2, 3, 4, 5):
+        np.testing.assert_array_equal(after[e], np.eye(3))
+    np.testing.assert_array_equal(after[6], 0)                                        # no diagonal block: the row is zeroed
+    np.testing.assert_allclose(np.asarray(inv[0], dtype=np.float64), np.linalg.inv(cv[0].astype(np.float64)), rtol=1e-13)
+    # the extended-precision inverse of non-symmetric blocks is the inverse, not its transpose
+    A = rng.standard_normal((50, 3, 3)) + 4 * np.eye(3)
+    inv50, _ = ks.inv3(A)
+    err = np.abs(np.asarray(inv50, dtype=np.float64) @ A - np.eye(3)).max()
+    assert err < 1e-14
+    assert np.abs(np.asarray(inv50, dtype=np.float64).transpose(0, 2, 1) @ A - np.eye(3)).max() > 1e-3
+
+
+def test_sbmg_rap_reference_is_the_block_galerkin_product():
+    import scipy.sparse as sp
+    rng = np.random.default_rng(8)
+    nS, par, pw, sb_ptr, sb_col, chptr, child, chw, cptr, ccol, P = _small_level(rng)
+    nc = len(cptr) - 1
+    vals = rng.standard_normal(9 * len(sb_col)).astype(np.float32)
+    N2 = nS + 5
+    snode = np.sort(rng.choice(N2, nS, replace=False)).astype(np.int32)
+    rowscale = 2.0 ** rng.integers(-2, 3, 6 * N2).astype(np.float64)     # powers of two: every product below is exact
+    flag = np.zeros(nS, dtype=np.uint8)
+    flag[[3, 33]] = 1
+    cv, S, L, missed = ks.sbmg_rap(nc, chptr, child, chw, sb_ptr, sb_col, vals, snode, rowscale, flag, par, pw, cptr, ccol)
+    assert not missed
+    row = np.repeat(np.arange(nS), np.diff(sb_ptr))
+    isc = 1.0 / rowscale.reshape(-1, 6)[snode, 3:]
+    B = vals.reshape(-1, 3, 3).astype(np.float64) * isc[row][:, :, None]
+    A = sp.bsr_matrix((B, sb_col, sb_ptr), shape=(3 * nS, 3 * nS)).tocsr()
+    G = ks.galerkin(sp.kron(P, sp.eye(3)).tocsr(), A, np.repeat(flag == 0, 3)).toarray()
+    crow = np.repeat(np.arange(nc), np.diff(cptr))
+    ref = np.stack([G[3 * crow + c, 3 * ccol + t] for c in range(3) for t in range(3)], axis=1)
+    np.testing.assert_allclose(cv, ref, rtol=0, atol=1e-12 * np.abs(ref).max())
+    # k_sbmg_flags: a node whose second row holds its diagonal alone is flagged
+    v2 = vals.reshape(-1, 3, 3).copy()
+    i = 7
+    v2[sb_ptr[i]:sb_ptr[i + 1], 1, :] = 0
+    dg = sb_ptr[i] + int(np.flatnonzero(sb_col[sb_ptr[i]:sb_ptr[i + 1]] == i)[0])
+    v2[dg, 1, 1] = 5.0
+    f = ks.sbmg_flags(nS, sb_ptr, sb_col, v2.ravel())
+    assert f[i] == 1 and f.sum() == 1

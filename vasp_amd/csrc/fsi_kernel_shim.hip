@@ -11,6 +11,7 @@
 #include "fsi_host.hpp"
 #include "fsi_kernels.hpp"
 
+#include <cmath>
 #include <cstring>
 
 using namespace fsi;
@@ -508,19 +509,269 @@ int shim_matrix_finish(int64_t n, const int64_t* rowptr, const int64_t* diagpos,
   SHIM_RUN(c, "launch_matrix_finish", launch_matrix_finish(c.st, n, drp, ddp, dA, dpre, dbc, nbc, drs, dbm));
 }
 
+// ---- the two-level (P2 -> P1) coarse levels and the diagonal scalings (fsi_block.hip) ---------------------------------------
+// Every flags / rowmax_bits argument is in/out (four / one int32), so that a test can pre-fill it.  Vectors of nodes are float4.
+// db [3 nnz], rowscale [6 N2], rowflag [3 N2] with nnz = nadj_ptr[N2]; d0 [N2]; flags [4]
+int shim_mg_d0(int64_t N2, const int64_t* nadj_ptr, const int32_t* nadj, const double* db, const double* rowscale,
+               const uint8_t* rowflag, float* d0, int32_t* flags) {
+  Call c;
+  const int64_t nnz = nadj_ptr[N2];
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const int32_t* dn = c.in(nadj, (size_t)nnz);
+  const double* ddb = c.in(db, 3 * (size_t)nnz);
+  const double* drs = c.in(rowscale, 6 * (size_t)N2);
+  const uint8_t* drf = c.in(rowflag, 3 * (size_t)N2);
+  float* dd0 = c.io(d0, (size_t)N2);
+  int32_t* dfl = c.io(flags, 4);
+  SHIM_RUN(c, "launch_mg_d0", launch_mg_d0(c.st, N2, dnp, dn, ddb, drs, drf, dd0, dfl));
+}
+// chptr [nc+1], child / chw [chptr[nc]], par / pw [2 N2], cptr [nc+1], ccol / Ac [cptr[nc]]
+int shim_mg_rap(int64_t nc, int64_t N2, const int64_t* chptr, const int32_t* child, const float* chw, const int64_t* nadj_ptr,
+                const int32_t* nadj, const double* db, const double* rowscale, const uint8_t* rowflag, const int32_t* par,
+                const float* pw, const int64_t* cptr, const int32_t* ccol, double* Ac, int32_t* flags) {
+  Call c;
+  const int64_t nnz = nadj_ptr[N2], nch = chptr[nc], cnnz = cptr[nc];
+  const int64_t* dchp = c.in(chptr, (size_t)nc + 1);
+  const int32_t* dch = c.in(child, (size_t)nch);
+  const float* dchw = c.in(chw, (size_t)nch);
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const int32_t* dn = c.in(nadj, (size_t)nnz);
+  const double* ddb = c.in(db, 3 * (size_t)nnz);
+  const double* drs = c.in(rowscale, 6 * (size_t)N2);
+  const uint8_t* drf = c.in(rowflag, 3 * (size_t)N2);
+  const int32_t* dpar = c.in(par, 2 * (size_t)N2);
+  const float* dpw = c.in(pw, 2 * (size_t)N2);
+  const int64_t* dcp = c.in(cptr, (size_t)nc + 1);
+  const int32_t* dcc = c.in(ccol, (size_t)cnnz);
+  double* dAc = c.io(Ac, (size_t)cnnz);
+  int32_t* dfl = c.io(flags, 4);
+  SHIM_RUN(c, "launch_mg_rap", launch_mg_rap(c.st, nc, dchp, dch, dchw, dnp, dn, ddb, drs, drf, dpar, dpw, dcp, dcc, dAc, dfl));
+}
+// cfine [nc], rowflag [3 N2]; cc [cptr[nc]], cflag [3 nc], dcinv4 [4 nc], rowmax_bits [1]
+int shim_mg_coarse_finish(int64_t nc, int64_t N2, const int64_t* cptr, const int32_t* ccol, const double* Ac, const int32_t* cfine,
+                          const uint8_t* rowflag, float* cc, uint8_t* cflag, float* dcinv4, int32_t* rowmax_bits) {
+  Call c;
+  const int64_t cnnz = cptr[nc];
+  const int64_t* dcp = c.in(cptr, (size_t)nc + 1);
+  const int32_t* dcc = c.in(ccol, (size_t)cnnz);
+  const double* dAc = c.in(Ac, (size_t)cnnz);
+  const int32_t* dcf = c.in(cfine, (size_t)nc);
+  const uint8_t* drf = c.in(rowflag, 3 * (size_t)N2);
+  float* dcv = c.io(cc, (size_t)cnnz);
+  uint8_t* dcfl = c.io(cflag, 3 * (size_t)nc);
+  float* ddi = c.io(dcinv4, 4 * (size_t)nc);
+  int32_t* drm = c.io(rowmax_bits, 1);
+  SHIM_RUN(c, "launch_mg_coarse_finish", launch_mg_coarse_finish(c.st, nc, dcp, dcc, dAc, dcf, drf, dcv, dcfl, ddi, drm));
+}
+// d0 / r4: [N2] / [4 N2]; dcinv4, rc4 and the optional Chebyshev start cx / cr / cd (all null or none): [4 nc]
+int shim_mg_restrict(int64_t nc, int64_t N2, const int64_t* chptr, const int32_t* child, const float* chw, const float* d0,
+                     const float* r4, const float* dcinv4, float* rc4, float inv_theta, float* cx, float* cr, float* cd) {
+  Call c;
+  const int64_t nch = chptr[nc];
+  const int64_t* dchp = c.in(chptr, (size_t)nc + 1);
+  const int32_t* dch = c.in(child, (size_t)nch);
+  const float* dchw = c.in(chw, (size_t)nch);
+  const float* dd0 = c.in(d0, (size_t)N2);
+  const float* dr4 = c.in(r4, 4 * (size_t)N2);
+  const float* ddi = c.in(dcinv4, 4 * (size_t)nc);
+  float* drc = c.io(rc4, 4 * (size_t)nc);
+  float* dcx = c.io(cx, 4 * (size_t)nc);
+  float* dcr = c.io(cr, 4 * (size_t)nc);
+  float* dcd = c.io(cd, 4 * (size_t)nc);
+  SHIM_RUN(c, "launch_mg_restrict", launch_mg_restrict(c.st, nc, dchp, dch, dchw, dd0, dr4, ddi, drc, inv_theta, dcx, dcr, dcd));
+}
+// par / pw [2 N2], d0 [N2], xc4 [4 nc], e4 [4 N2]
+int shim_mg_prolong(int64_t N2, int64_t nc, const int32_t* par, const float* pw, const float* d0, const float* xc4, float* e4) {
+  Call c;
+  const int32_t* dpar = c.in(par, 2 * (size_t)N2);
+  const float* dpw = c.in(pw, 2 * (size_t)N2);
+  const float* dd0 = c.in(d0, (size_t)N2);
+  const float* dxc = c.in(xc4, 4 * (size_t)nc);
+  float* de = c.io(e4, 4 * (size_t)N2);
+  SHIM_RUN(c, "launch_mg_prolong", launch_mg_prolong(c.st, N2, dpar, dpw, dd0, dxc, de));
+}
+// sb_ptr [nS+1], sb_col [sb_ptr[nS]], vals [9 sb_ptr[nS]], flag [nS]
+int shim_sbmg_flags(int64_t nS, const int64_t* sb_ptr, const int32_t* sb_col, const float* vals, uint8_t* flag) {
+  Call c;
+  const int64_t nb = sb_ptr[nS];
+  const int64_t* dsp = c.in(sb_ptr, (size_t)nS + 1);
+  const int32_t* dsc = c.in(sb_col, (size_t)nb);
+  const float* dv = c.in(vals, 9 * (size_t)nb);
+  uint8_t* dfl = c.io(flag, (size_t)nS);
+  SHIM_RUN(c, "launch_sbmg_flags", launch_sbmg_flags(c.st, nS, dsp, dsc, dv, dfl));
+}
+// snode / flag [nS], rowscale [6 N2], par / pw [2 nS]; cvals [9 cptr[nc]]
+int shim_sbmg_rap(int64_t nc, int64_t nS, int64_t N2, const int64_t* chptr, const int32_t* child, const float* chw,
+                  const int64_t* sb_ptr, const int32_t* sb_col, const float* vals, const int32_t* snode, const double* rowscale,
+                  const uint8_t* flag, const int32_t* par, const float* pw, const int64_t* cptr, const int32_t* ccol, float* cvals,
+                  int32_t* flags) {
+  Call c;
+  const int64_t nb = sb_ptr[nS], nch = chptr[nc], cnnz = cptr[nc];
+  const int64_t* dchp = c.in(chptr, (size_t)nc + 1);
+  const int32_t* dch = c.in(child, (size_t)nch);
+  const float* dchw = c.in(chw, (size_t)nch);
+  const int64_t* dsp = c.in(sb_ptr, (size_t)nS + 1);
+  const int32_t* dsc = c.in(sb_col, (size_t)nb);
+  const float* dv = c.in(vals, 9 * (size_t)nb);
+  const int32_t* dsn = c.in(snode, (size_t)nS);
+  const double* drs = c.in(rowscale, 6 * (size_t)N2);
+  const uint8_t* dfl = c.in(flag, (size_t)nS);
+  const int32_t* dpar = c.in(par, 2 * (size_t)nS);
+  const float* dpw = c.in(pw, 2 * (size_t)nS);
+  const int64_t* dcp = c.in(cptr, (size_t)nc + 1);
+  const int32_t* dcc = c.in(ccol, (size_t)cnnz);
+  float* dcv = c.io(cvals, 9 * (size_t)cnnz);
+  int32_t* dflags = c.io(flags, 4);
+  SHIM_RUN(c, "launch_sbmg_rap",
+           launch_sbmg_rap(c.st, nc, dchp, dch, dchw, dsp, dsc, dv, dsn, drs, dfl, dpar, dpw, dcp, dcc, dcv, dflags));
+}
+// cvals [9 cptr[nc]] in place, cfine [nc], flag [nS]; cbinv12 [12 nc], cflag [nc], rowmax_bits [1]
+int shim_sbmg_coarse_finish(int64_t nc, int64_t nS, const int64_t* cptr, const int32_t* ccol, float* cvals, const int32_t* cfine,
+                            const uint8_t* flag, float* cbinv12, uint8_t* cflag, int32_t* rowmax_bits) {
+  Call c;
+  const int64_t cnnz = cptr[nc];
+  const int64_t* dcp = c.in(cptr, (size_t)nc + 1);
+  const int32_t* dcc = c.in(ccol, (size_t)cnnz);
+  float* dcv = c.io(cvals, 9 * (size_t)cnnz);
+  const int32_t* dcf = c.in(cfine, (size_t)nc);
+  const uint8_t* dfl = c.in(flag, (size_t)nS);
+  float* dbi = c.io(cbinv12, 12 * (size_t)nc);
+  uint8_t* dcfl = c.io(cflag, (size_t)nc);
+  int32_t* drm = c.io(rowmax_bits, 1);
+  SHIM_RUN(c, "launch_sbmg_coarse_finish", launch_sbmg_coarse_finish(c.st, nc, dcp, dcc, dcv, dcf, dfl, dbi, dcfl, drm));
+}
+// r4 [4 nS], rc4 [4 nc]; the optional exact-solve right-hand side: bpos [nc], bd [nbd] (both null or neither)
+int shim_sbmg_restrict(int64_t nc, int64_t nS, int64_t N2, const int64_t* chptr, const int32_t* child, const float* chw,
+                       const int32_t* snode, const double* rowscale, const uint8_t* flag, const uint8_t* cflag, const float* r4,
+                       float* rc4, const int32_t* bpos, double* bd, int64_t nbd) {
+  Call c;
+  const int64_t nch = chptr[nc];
+  const int64_t* dchp = c.in(chptr, (size_t)nc + 1);
+  const int32_t* dch = c.in(child, (size_t)nch);
+  const float* dchw = c.in(chw, (size_t)nch);
+  const int32_t* dsn = c.in(snode, (size_t)nS);
+  const double* drs = c.in(rowscale, 6 * (size_t)N2);
+  const uint8_t* dfl = c.in(flag, (size_t)nS);
+  const uint8_t* dcfl = c.in(cflag, (size_t)nc);
+  const float* dr4 = c.in(r4, 4 * (size_t)nS);
+  float* drc = c.io(rc4, 4 * (size_t)nc);
+  const int32_t* dbp = c.in(bpos, (size_t)nc);
+  double* dbd = c.io(bd, (size_t)nbd);
+  SHIM_RUN(c, "launch_sbmg_restrict", launch_sbmg_restrict(c.st, nc, dchp, dch, dchw, dsn, drs, dfl, dcfl, dr4, drc, dbp, dbd));
+}
+// par / pw [2 nS], flag [nS], xc4 [4 nc] (may be null with xd), e4 [4 nS]; the optional exact-solve answer: bpos [nc], xd [nxd]
+int shim_sbmg_prolong(int64_t nS, int64_t nc, const int32_t* par, const float* pw, const uint8_t* flag, const float* xc4, float* e4,
+                      const int32_t* bpos, const double* xd, int64_t nxd) {
+  Call c;
+  const int32_t* dpar = c.in(par, 2 * (size_t)nS);
+  const float* dpw = c.in(pw, 2 * (size_t)nS);
+  const uint8_t* dfl = c.in(flag, (size_t)nS);
+  const float* dxc = c.in(xc4, 4 * (size_t)nc);
+  float* de = c.io(e4, 4 * (size_t)nS);
+  const int32_t* dbp = c.in(bpos, (size_t)nc);
+  const double* dxd = c.in(xd, (size_t)nxd);
+  SHIM_RUN(c, "launch_sbmg_prolong", launch_sbmg_prolong(c.st, nS, dpar, dpw, dfl, dxc, de, dbp, dxd));
+}
+// snode [nS], diagpos3 [3 N2], Avv [nA]; binv12 [12 nS], binv9 [9 nS]
+int shim_sb_binv(int64_t nS, int64_t N2, const int32_t* snode, const int64_t* diagpos3, const double* Avv, int64_t nA, float* binv12,
+                 double* binv9) {
+  Call c;
+  const int32_t* dsn = c.in(snode, (size_t)nS);
+  const int64_t* ddp = c.in(diagpos3, 3 * (size_t)N2);
+  const double* dA = c.in(Avv, (size_t)nA);
+  float* db12 = c.io(binv12, 12 * (size_t)nS);
+  double* db9 = c.io(binv9, 9 * (size_t)nS);
+  SHIM_RUN(c, "launch_sb_binv", launch_sb_binv(c.st, nS, dsn, ddp, dA, db12, db9));
+}
+// dinv [4 nS]
+int shim_sb_dinv(int64_t nS, int64_t N2, const int32_t* snode, const int64_t* diagpos3, const double* Avv, int64_t nA, float* dinv) {
+  Call c;
+  const int32_t* dsn = c.in(snode, (size_t)nS);
+  const int64_t* ddp = c.in(diagpos3, 3 * (size_t)N2);
+  const double* dA = c.in(Avv, (size_t)nA);
+  float* ddi = c.io(dinv, 4 * (size_t)nS);
+  SHIM_RUN(c, "launch_sb_dinv", launch_sb_dinv(c.st, nS, dsn, ddp, dA, ddi));
+}
+// mask (may be null) / diagpos [3 nn], A [nA], dinv4 [4 nn]
+int shim_dinv_f32(int64_t nn, const double* mask, const int64_t* diagpos, const double* A, int64_t nA, float* dinv4) {
+  Call c;
+  const double* dm = c.in(mask, 3 * (size_t)nn);
+  const int64_t* ddp = c.in(diagpos, 3 * (size_t)nn);
+  const double* dA = c.in(A, (size_t)nA);
+  float* ddi = c.io(dinv4, 4 * (size_t)nn);
+  SHIM_RUN(c, "launch_dinv_f32", launch_dinv_f32(c.st, nn, dm, ddp, dA, ddi));
+}
+// diagpos / dinv [n], A [nA]
+int shim_diag_inverse(int64_t n, const int64_t* diagpos, const double* A, int64_t nA, double* dinv) {
+  Call c;
+  const int64_t* ddp = c.in(diagpos, (size_t)n);
+  const double* dA = c.in(A, (size_t)nA);
+  double* ddi = c.io(dinv, (size_t)n);
+  SHIM_RUN(c, "launch_diag_inverse", launch_diag_inverse(c.st, n, ddp, dA, ddi));
+}
+// binv9 [9 nS], y [3 nS] in place
+int shim_block_scale_d(int64_t nS, const double* binv9, double* y) {
+  Call c;
+  const double* db9 = c.in(binv9, 9 * (size_t)nS);
+  double* dy = c.io(y, 3 * (size_t)nS);
+  SHIM_RUN(c, "launch_block_scale_d", launch_block_scale_d(c.st, nS, db9, dy));
+}
+// snode [nS], full [nfull], binv12 [12 nS]; x, r, d, d2 [4 nS]
+int shim_solid_cycle_init(int64_t nS, int64_t nfull, const int32_t* snode, const double* full, const float* binv12, float scale,
+                          float* x, float* r, float* d, float* d2) {
+  Call c;
+  const int32_t* dsn = c.in(snode, (size_t)nS);
+  const double* dfu = c.in(full, (size_t)nfull);
+  const float* db12 = c.in(binv12, 12 * (size_t)nS);
+  float* dx = c.io(x, 4 * (size_t)nS);
+  float* dr = c.io(r, 4 * (size_t)nS);
+  float* dd = c.io(d, 4 * (size_t)nS);
+  float* dd2 = c.io(d2, 4 * (size_t)nS);
+  SHIM_RUN(c, "launch_solid_cycle_init", launch_solid_cycle_init(c.st, nS, dsn, dfu, db12, scale, dx, dr, dd, dd2));
+}
+// comp [4 nS]
+int shim_gather3_f32(int64_t nS, int64_t nfull, const int32_t* snode, const double* full, float* comp) {
+  Call c;
+  const int32_t* dsn = c.in(snode, (size_t)nS);
+  const double* dfu = c.in(full, (size_t)nfull);
+  float* dco = c.io(comp, 4 * (size_t)nS);
+  SHIM_RUN(c, "launch_gather3_f32", launch_gather3_f32(c.st, nS, dsn, dfu, dco));
+}
+// full [nfull] in place
+int shim_scatter3_f32(int64_t nS, int64_t nfull, const int32_t* snode, const float* comp, double* full) {
+  Call c;
+  const int32_t* dsn = c.in(snode, (size_t)nS);
+  const float* dco = c.in(comp, 4 * (size_t)nS);
+  double* dfu = c.io(full, (size_t)nfull);
+  SHIM_RUN(c, "launch_scatter3_f32", launch_scatter3_f32(c.st, nS, dsn, dco, dfu));
+}
+
 // ---- a live context's preconditioner arrays (FsiCtx of fsi_context.hpp, as the library was compiled) -----------------------
 // shim_ctx_info: N2, V, nS, sb_nblocks, tiled, tile_nodes, tile_max_nu, schur_tiled, schur_tile, s_tile_max_nu, sweeps_fp16,
-// a32_ptail, a32_tail_src, a32_tail_nnz, op32_ok, kry_fp32, drows_ok
+// a32_ptail, a32_tail_src, a32_tail_nnz, op32_ok, kry_fp32, drows_ok, mg_nc, mg_cnnz, mg_ready, sbmg_nc, sbmg_nblk, sbmg_ready,
+// bcr_ready (new fields go at the end: tests/kernel_shim.py reads them by position)
 int shim_ctx_info(const FsiCtx* ctx, int64_t* out, int nout) {
   const int64_t v[] = {ctx->N2, ctx->V, ctx->nS, ctx->sb_nblocks, ctx->tiled, ctx->tile_nodes, ctx->tile_max_nu,
                        ctx->schur_tiled, ctx->schur_tile, ctx->s_tile_max_nu, ctx->sweeps_fp16,
-                       ctx->a32_ptail, ctx->a32_tail_src, ctx->a32_tail_nnz, ctx->op32_ok, ctx->kry_fp32, ctx->drows_ok};
+                       ctx->a32_ptail, ctx->a32_tail_src, ctx->a32_tail_nnz, ctx->op32_ok, ctx->kry_fp32, ctx->drows_ok,
+                       ctx->mg_nc, ctx->mg_cnnz, ctx->mg_ready, ctx->sbmg_nc, ctx->sbmg_nblk, ctx->sbmg_ready, fsi::host::bcr_ready(ctx)};
   const int k = (int)(sizeof(v) / sizeof(v[0]));
   for (int i = 0; i < nout && i < k; ++i) out[i] = v[i];
   return k;
 }
 // the factor of the solid columns' displacement entries folded into the velocity block (Avv~ = Avv + ktheta Avd, k_extract_blocks)
 double shim_ctx_ktheta(const FsiCtx* ctx) { return ctx->scheme.k * ctx->scheme.th0; }
+// the coarse levels' eigenvalue bounds: 0 mg_gersh, 1 sbmg_gersh (the row-sum bounds of the last rebuild), 2 mg_clmax, 3 sbmg_clmax
+// (what the Chebyshev intervals use); NaN for any other index
+double shim_ctx_coarse(const FsiCtx* ctx, int which) {
+  switch (which) {
+    case 0: return ctx->mg_gersh;
+    case 1: return ctx->sbmg_gersh;
+    case 2: return ctx->mg_clmax;
+    case 3: return ctx->sbmg_clmax;
+    default: return std::nan("");
+  }
+}
 // Copies the named device array into host (when host is not null); *count / *elem: its length and element size.
 // Status 2: no such name.
 int shim_ctx_array(const FsiCtx* ctx, const char* name, void* host, int64_t* count, int* elem) {
@@ -531,7 +782,12 @@ int shim_ctx_array(const FsiCtx* ctx, const char* name, void* host, int64_t* cou
                          E(sb_binv12),  E(s_rowptr),  E(s_cols),  E(s_diagpos),  E(s_vals),      E(s_vals32),    E(s_rec),
                          E(s_ploc),     E(s_tile_uptr), E(s_tile_ulist), E(s_dinv), E(dd_db),    E(rowscale),    E(snode),
                          E(solver2user), E(node_solid), E(rowptr),    E(cols),        E(diagpos),     E(A),           E(vrank),
-                         E(padj_ptr),   E(padj),      E(A32),     E(a32_ptr),    E(a32_cols),    E(Ad64),        E(Ad32)};
+                         E(padj_ptr),   E(padj),      E(A32),     E(a32_ptr),    E(a32_cols),    E(Ad64),        E(Ad32),
+                         E(mg_par),     E(mg_pw),     E(mg_chptr), E(mg_child),  E(mg_chw),      E(mg_cptr),     E(mg_ccol),
+                         E(mg_cfine),   E(mg_Ac),     E(mg_cc),   E(mg_d0),      E(mg_dcinv4),   E(mg_cflag),    E(sbmg_par),
+                         E(sbmg_pw),    E(sbmg_chptr), E(sbmg_child), E(sbmg_chw), E(sbmg_cptr),  E(sbmg_ccol),   E(sbmg_cfine),
+                         E(sbmg_cvals), E(sbmg_cbinv12), E(sbmg_flag), E(sbmg_cflag), E(sb_binv9), E(sb_dinv),   E(dd_dinv32),
+                         E(vvf_dinv32)};
 #undef E
   for (const Entry& t : table) {
     if (std::strcmp(t.name, name) != 0) continue;
