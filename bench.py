@@ -1,6 +1,6 @@
 """Benchmark of the hot path: Newton iterations per second of the monolithic ALE-FSI time step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--tets T] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--tets T] [--dump-outputs DIR] [--full]
 
 One "step" = one time step of the offset-stenosis problem exactly as the product driver runs it
 (``vasp_amd.monolithic.advance``: pre_solve data, quasi-Newton solve through the C-ABI, state shift, post_solve
@@ -20,14 +20,19 @@ Storage precisions.  BASELINE.json configs[1] reads "FP64": the HEADLINE run (``
 of the solver in FP64 (Krylov basis, the Jacobian in every product, Schur sweeps; FP32 only where the preconditioner's sweeps ran
 in FP32 from round 1) and reports ``dtype: "f64"``.  The mixed-storage mode the library selects by itself (FP32 Krylov basis and
 Jacobian copy inside the iterations, FP16 preconditioner records; Newton residual, Jacobian, every accumulation and every
-linear-solve verdict FP64) is the same 20 steps once more in a child process: ``value_mixed_storage`` (``--storage mixed`` makes
-it the main run, with ``dtype`` saying so).
+linear-solve verdict FP64) is the same 20 steps once more in a child process with ``--full``: ``value_mixed_storage``
+(``--storage mixed`` makes it the main run, with ``dtype`` saying so).
 
 ``--tets-per-gpu T`` (BASELINE.json configs[4]: 10 M tets on 8 GPUs): the mesh grows with the number of ranks, ``scaling: "weak"``.
 
 Output: ONE JSON line on rank 0: metric, value, `roofline` of the kernel group with the largest share of GPU time in the
 timed region (orthogonalisation kernels included, their bytes exact from the number of columns streamed), `kernels` (the
-whole table the choice was made from), `cpu_baseline`.
+whole table the choice was made from; all of it from this run's own timers).
+
+A plain run does only what that line needs: set-up, warm-up, the timed steps, the dump if asked for, the line.  ``--full``
+adds what takes runs of its own, after the main run has released its context: the other storage mode in a child process
+(``value_<mode>_storage``, skipped by ``--no-side-line``) and `cpu_baseline`, the CPU port timed on the host (skipped by
+``--no-cpu-baseline``); both on one GPU only.
 
 ``--dump-outputs DIR``: after the timed steps, what the last one handed its caller is written to DIR as float64 .npy files
 (see ``dump_outputs``), so that two builds run with the same arguments - same mesh, same initial state, same steps - can be
@@ -40,6 +45,7 @@ import contextlib
 import io
 import json
 import os
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -76,7 +82,8 @@ def self_launch(args) -> int:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), str(Path(__file__).resolve()),
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--tets", str(args.tets),
-           "--dt", str(args.dt), "--storage", args.storage] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []) \
+           "--dt", str(args.dt), "--storage", args.storage] + (["--full"] if args.full else []) \
+          + (["--no-cpu-baseline"] if args.no_cpu_baseline else []) \
           + (["--tets-per-gpu", str(args.tets_per_gpu)] if args.tets_per_gpu else []) \
           + (["--dump-outputs", str(Path(args.dump_outputs).resolve())] if args.dump_outputs else [])
     env = dict(os.environ)
@@ -90,7 +97,7 @@ def other_storage_run(args, storage: str) -> dict:
     the storage of the Krylov basis, of the Jacobian copy used inside the iterations and of the preconditioner's matrices.  This
     process has released its context before the child starts."""
     cmd = [sys.executable, str(Path(__file__).resolve()), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--tets", str(args.tets), "--dt", str(args.dt), "--no-cpu-baseline", "--storage", storage, "--no-side-line"]
+           "--tets", str(args.tets), "--dt", str(args.dt), "--storage", storage]       # a plain run: no side line, no CPU baseline
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     if storage == "mixed":          # this process exported the all-FP64 switches for its own context: the child must not inherit them
         env = {k: v for k, v in env.items() if k not in FP64_STORAGE_ENV}
@@ -162,13 +169,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--tets", type=int, default=int(os.environ.get("VASPFSI_BENCH_TETS", 1000000)))
     ap.add_argument("--dt", type=float, default=1e-3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the main run, also the other storage mode in a child process and the CPU baseline (one GPU only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--storage", choices=("fp64", "mixed", "default"), default="fp64",
                     help="fp64 (the headline: BASELINE.json configs[1] says FP64): every storage-precision choice off - FP64 Krylov "
                          "basis, FP64 Jacobian in every product, FP64 Schur sweeps, FP32 instead of FP16 sweep matrices; mixed "
                          "(= default, the library's own policy): FP32 basis and Jacobian copy inside the iterations, FP16 records")
     ap.add_argument("--no-side-line", "--no-fp64-line", dest="no_side_line", action="store_true",
-                    help="skip the second run in the other storage mode (value_mixed_storage / value_fp64_storage)")
+                    help="with --full: skip the second run in the other storage mode (value_mixed_storage / value_fp64_storage)")
     ap.add_argument("--tets-per-gpu", type=int, default=0,
                     help="weak scaling (BASELINE.json configs[4]: 10 M tets on 8 GPUs = 1 250 000 per GPU): the mesh has about "
                          "this many tets per rank, `scaling` is \"weak\"")
@@ -476,15 +485,16 @@ def main():
         if rank == 0:
             out["dump_outputs"] = dump_outputs(Path(args.dump_outputs), x, mesh, hist)
     hb.close()                 # the context's HBM (Krylov store, matrices) is free again before anything else runs
+    shutil.rmtree(tmp, ignore_errors=True)          # the generated mesh (~350 MB at 1 M tets)
     if rank == 0:
         out["config"]["storage"] = args.storage
-        if world == 1 and not args.no_side_line:      # the same steps once more in the other storage mode
+        if args.full and world == 1 and not args.no_side_line:      # the same steps once more in the other storage mode
             other = "mixed" if args.storage == "fp64" else "fp64"
             side = other_storage_run(args, other)
             out[f"value_{other}_storage"] = side.get("value")        # Newton-iterations/s of the same 20 steps
             out[f"ms_per_step_{other}_storage"] = side.get("ms_per_step")
             out[f"{other}_storage"] = side
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res_k = next(v for k, v in table.items() if k.startswith("k_residual"))
             jac_k = next(v for k, v in table.items() if k.startswith("k_jacobian"))
             spmv_k = next(v for k, v in table.items() if k.startswith("k_spmv"))
