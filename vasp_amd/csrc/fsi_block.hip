@@ -980,6 +980,154 @@ void launch_sweep_tiled_h(hipStream_t st, int nv, int tn, int64_t N2, int max_nu
   else
     hipLaunchKernelGGL((k_sweep_tiled_h<3, 256>), dim3(tiles), dim3(th), lds, st, N2, nadj_ptr, static_cast<const uint2*>(rec), tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r);
 }
+// ---- FP32 records for the fine-level sweeps of the FP32 path ---------------------------------------------------------------
+// The same values as k_sweep_tiled_f32<3> / k_sweep_sb_b3<0> read, packed with their column so that a pair or block comes in a
+// few wide loads: (three value bits, local index) in 16 bytes, a 3x3 solid block and its column in 40 bytes read as five 8-byte
+// loads.  The sums are those of the kernels they replace, term for term.  (An 8-byte record of the displacement block's one
+// ratio and index was measured and left out: 141 against 127 us per sweep alone - 8 bytes per pair instead of 6.)
+__global__ void k_pack_f3(int64_t n, const float* __restrict__ v, const uint16_t* __restrict__ loc, uint4* __restrict__ rec) {
+  GS(e, n) rec[e] = make_uint4(__float_as_uint(v[3 * e]), __float_as_uint(v[3 * e + 1]), __float_as_uint(v[3 * e + 2]), (uint32_t)loc[e]);
+}
+// rec[5 b + 0..4]: (a0 a1), (a2 a3), (a4 a5), (a6 a7), (a8 column)
+__global__ void k_pack_sb_f32(int64_t nb, const float* __restrict__ v, const int32_t* __restrict__ col, uint2* __restrict__ rec) {
+  GS(b, nb) {
+    const float* a = v + 9 * b;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) rec[5 * b + k] = make_uint2(__float_as_uint(a[2 * k]), __float_as_uint(a[2 * k + 1]));
+    rec[5 * b + 4] = make_uint2(__float_as_uint(a[8]), (uint32_t)col[b]);
+  }
+}
+void launch_pack_f3(hipStream_t st, int64_t n, const float* v, const uint16_t* loc, void* rec) {
+  hipLaunchKernelGGL(k_pack_f3, dim3(gridn(n)), dim3(256), 0, st, n, v, loc, static_cast<uint4*>(rec));
+}
+void launch_pack_sb_f32(hipStream_t st, int64_t nb, const float* v, const int32_t* col, void* rec) {
+  hipLaunchKernelGGL(k_pack_sb_f32, dim3(gridn(nb)), dim3(256), 0, st, nb, v, col, static_cast<uint2*>(rec));
+}
+// Where k_sweep_tiled_r takes a pair's values and local index from: the 16-byte records of the fluid block (Rec3), or the two
+// arrays k_sweep_tiled_f32<1> reads for the displacement block (Arr1: value and index in two loads, kept in a uint2)
+struct TileSrcRec3 {
+  const uint4* __restrict__ rec;
+  using Rec = uint4;
+  __device__ Rec operator()(int64_t e) const { return rec[e]; }
+};
+struct TileSrcArr1 {
+  const float* __restrict__ vals;
+  const uint16_t* __restrict__ ploc;
+  using Rec = uint2;
+  __device__ Rec operator()(int64_t e) const { return make_uint2(__float_as_uint(vals[e]), (uint32_t)ploc[e]); }
+};
+// k_sweep_tiled_f32 from a pair source: the one-ratio form (NV = 1) with two rows ahead in flight as in k_sweep_tiled_h, the
+// 16-byte records of NV = 3 with one row ahead: two rows of them are 48 VGPRs of records, 79 in all, 6 waves per SIMD instead of 8,
+// and measured slower (197 - 206 against 182 - 191 us per sweep alone).
+template <int NV, int TN, class Src>
+__global__ __launch_bounds__(1024) void k_sweep_tiled_r(int64_t N2, const int64_t* __restrict__ nadj_ptr, const Src src,
+                                                        const int64_t* __restrict__ tile_uptr, const int32_t* __restrict__ ulist,
+                                                        const uint8_t* __restrict__ rowflag, const float* __restrict__ dinv,
+                                                        float c1, float c2, const float* __restrict__ din, float* __restrict__ dout,
+                                                        float* __restrict__ x, float* __restrict__ r) {
+  using Rec = typename Src::Rec;
+  extern __shared__ __attribute__((aligned(16))) float4 sx[];
+  __shared__ __attribute__((aligned(16))) int64_t sptr[TN + 2];
+  __shared__ __attribute__((aligned(16))) float4 ssum[TN];
+  const int64_t tile = xcd_tile((N2 + TN - 1) / TN);
+  if (tile < 0) return;
+  const int64_t u0 = tile_uptr[tile], nu = tile_uptr[tile + 1] - u0;
+  const float4* d4 = reinterpret_cast<const float4*>(din);
+  const int64_t r0 = tile * TN;
+  const int nrows = (int)((r0 + TN < N2 ? r0 + TN : N2) - r0);
+  const int nth = blockDim.x, ngrp = nth >> 4;
+  for (int64_t i = threadIdx.x; i < nu; i += 4 * nth) {        // index -> entry is a dependent pair of loads: four pairs in flight
+    const int64_t i1 = i + nth, i2 = i + 2 * nth, i3 = i + 3 * nth;
+    const int32_t k0 = ulist[u0 + i], k1 = i1 < nu ? ulist[u0 + i1] : 0, k2 = i2 < nu ? ulist[u0 + i2] : 0, k3 = i3 < nu ? ulist[u0 + i3] : 0;
+    const float4 v0 = d4[k0], v1 = d4[k1], v2 = d4[k2], v3 = d4[k3];
+    sx[i] = v0;
+    if (i1 < nu) sx[i1] = v1;
+    if (i2 < nu) sx[i2] = v2;
+    if (i3 < nu) sx[i3] = v3;
+  }
+  for (int i = threadIdx.x; i <= nrows; i += nth) sptr[i] = nadj_ptr[r0 + i];
+  __syncthreads();
+  const int sub = threadIdx.x & 15, g = threadIdx.x >> 4;
+  constexpr int KS = 4;
+  constexpr bool AHEAD2 = NV == 1;
+  Rec cr[KS], nr[KS], n2[KS];
+  auto zero = [](Rec& q) { if constexpr (NV == 1) q = make_uint2(0u, 0u); else q = make_uint4(0u, 0u, 0u, 0u); };      // value +0, index 0
+  auto prefetch = [&](int i, Rec (&q)[KS]) {
+    const int64_t e0 = sptr[i], e1 = sptr[i + 1];
+#pragma unroll
+    for (int k = 0; k < KS; ++k) {
+      const int64_t e = e0 + sub + 16 * k;
+      if (e < e1) q[k] = src(e); else zero(q[k]);               // a zero record: value +0, local index 0
+    }
+  };
+  auto fma3 = [&](const Rec q, float& s0, float& s1, float& s2) {
+    if constexpr (NV == 1) {
+      const float c = __uint_as_float(q.x);
+      const float4 xv = sx[q.y];
+      s0 += c * xv.x; s1 += c * xv.y; s2 += c * xv.z;
+    } else {
+      const float4 xv = sx[q.w];
+      s0 += __uint_as_float(q.x) * xv.x; s1 += __uint_as_float(q.y) * xv.y; s2 += __uint_as_float(q.z) * xv.z;
+    }
+  };
+  int i = g;
+  if (i < nrows) prefetch(i, cr);
+  if (AHEAD2 && i + ngrp < nrows) prefetch(i + ngrp, nr);
+  while (i < nrows) {
+    const int ni = i + ngrp;
+    if (AHEAD2 && ni + ngrp < nrows) prefetch(ni + ngrp, n2);
+    if (!AHEAD2 && ni < nrows) prefetch(ni, nr);
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    fma3(cr[0], s0, s1, s2);
+    fma3(cr[1], s0, s1, s2);
+    const int len = (int)(sptr[i + 1] - sptr[i]);
+    if (__builtin_amdgcn_ballot_w64(len > 32) != 0) { fma3(cr[2], s0, s1, s2); fma3(cr[3], s0, s1, s2); }
+    for (int64_t e = sptr[i] + sub + 16 * KS; e < sptr[i + 1]; e += 16) fma3(src(e), s0, s1, s2);      // more than 64 pairs
+    s0 = group_sum<16>(s0); s1 = group_sum<16>(s1); s2 = group_sum<16>(s2);
+    if (sub == 0) ssum[i] = make_float4(s0, s1, s2, 0.f);
+#pragma unroll
+    for (int k = 0; k < KS; ++k) { cr[k] = nr[k]; if (AHEAD2) nr[k] = n2[k]; }
+    i = ni;
+  }
+  __syncthreads();
+  const float* sflat = reinterpret_cast<const float*>(ssum);
+  for (int idx = threadIdx.x; idx < 4 * nrows; idx += nth) {
+    const int64_t gi = 4 * r0 + idx;
+    const int comp = idx & 3;
+    const float di = din[gi];
+    float t = sflat[idx];
+    if (rowflag && comp < 3 && rowflag[3 * (r0 + (idx >> 2)) + comp]) t = di;
+    const float ri = r[gi] - t;
+    x[gi] += di;
+    r[gi] = ri;
+    dout[gi] = comp < 3 ? c1 * di + c2 * ri * (dinv ? dinv[gi] : 1.f) : 0.f;
+  }
+}
+#define TILED_R(NV_, SRC)                                                                                                     \
+  do {                                                                                                                   \
+    if (tn == 128) hipLaunchKernelGGL((k_sweep_tiled_r<NV_, 128, SRC>), dim3(tiles), dim3(th), lds, st, N2, nadj_ptr, src, tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r); \
+    else hipLaunchKernelGGL((k_sweep_tiled_r<NV_, 256, SRC>), dim3(tiles), dim3(th), lds, st, N2, nadj_ptr, src, tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r); \
+  } while (0)
+void launch_sweep_tiled_r3(hipStream_t st, int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const void* rec,
+                           const int64_t* tile_uptr, const int32_t* ulist, const uint8_t* rowflag, const float* dinv, float c1,
+                           float c2, const float* din, float* dout, float* x, float* r) {
+  const int th = tn == 128 ? 256 : 512;
+  const unsigned tiles = xcd_grid((N2 + tn - 1) / tn);
+  const size_t lds = (size_t)max_nu * sizeof(float4);
+  const TileSrcRec3 src{static_cast<const uint4*>(rec)};
+  TILED_R(3, TileSrcRec3);
+}
+// the one-ratio form on the arrays of k_sweep_tiled_f32 (value and local index in two loads), two rows ahead in flight
+void launch_sweep_tiled_a1(hipStream_t st, int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const float* vals,
+                           const uint16_t* ploc, const int64_t* tile_uptr, const int32_t* ulist, const uint8_t* rowflag,
+                           const float* dinv, float c1, float c2, const float* din, float* dout, float* x, float* r) {
+  const int th = tn == 128 ? 256 : 512;
+  const unsigned tiles = xcd_grid((N2 + tn - 1) / tn);
+  const size_t lds = (size_t)max_nu * sizeof(float4);
+  const TileSrcArr1 src{vals, ploc};
+  TILED_R(1, TileSrcArr1);
+}
+#undef TILED_R
 // k_sweep_sb_b3<0> on the packed 24-byte block records.  LPR lanes per row with 32 / LPR blocks in flight per lane: the sweep is a chain
 // of three dependent loads (row pointer -> record -> gathered d) per round of resident waves, and 150 k rows of 16 lanes are 4.6 rounds;
 // 8 lanes per row are half the rounds with twice the loads in flight per lane (measured at 1.12 M tets, A / B on one box: 16 lanes
@@ -1775,6 +1923,76 @@ void launch_sweep_schur_tiled(hipStream_t st, int tile_rows, int64_t n, int max_
   else
     hipLaunchKernelGGL(k_sweep_schur_tiled<256>, dim3(tiles), dim3(256), lds, st, n, rowptr, rec, tile_uptr, ulist, dinv, c1, c2, din, dout, x, r);
 }
+// The all-FP64 Schur sweep on the same tiles: FP64 values in CSR order and the 16-bit tile-local column (10 bytes per entry instead
+// of 12, and no gather of d from global memory).  Bitwise equal to k_sweep_csr_mixed<8, 8, double>: 8 lanes per row, lane sub
+// takes entries sub + 8 j + 64 t in the same order and form, the same group_sum, the same update with the division by the diagonal
+// (the stored s_dinv of the FP16 form rounds differently).
+template <int SCHUR_TILE>
+__global__ __launch_bounds__(256) void k_sweep_schur_tiled_f64(int64_t n, const int64_t* __restrict__ rowptr,
+                                                               const double* __restrict__ vals, const uint16_t* __restrict__ ploc,
+                                                               const int64_t* __restrict__ tile_uptr, const int32_t* __restrict__ ulist,
+                                                               const int64_t* __restrict__ diagpos, double c1, double c2,
+                                                               const double* __restrict__ din, double* __restrict__ dout,
+                                                               double* __restrict__ x, double* __restrict__ r) {
+  extern __shared__ __attribute__((aligned(16))) double sxd[];
+  __shared__ int64_t sptr[SCHUR_TILE + 1];
+  __shared__ double ssum[SCHUR_TILE];
+  const int64_t tile = xcd_tile((n + SCHUR_TILE - 1) / SCHUR_TILE);
+  if (tile < 0) return;
+  const int64_t r0 = tile * SCHUR_TILE;
+  const int nrows = (int)((r0 + SCHUR_TILE < n ? r0 + SCHUR_TILE : n) - r0);
+  const int64_t u0 = tile_uptr[tile], nu = tile_uptr[tile + 1] - u0;
+  for (int64_t i = threadIdx.x; i < nu; i += 1024) {              // four dependent index -> entry pairs in flight
+    const int64_t i1 = i + 256, i2 = i + 512, i3 = i + 768;
+    const int32_t k0 = ulist[u0 + i], k1 = i1 < nu ? ulist[u0 + i1] : 0, k2 = i2 < nu ? ulist[u0 + i2] : 0, k3 = i3 < nu ? ulist[u0 + i3] : 0;
+    const double v0 = din[k0], v1 = din[k1], v2 = din[k2], v3 = din[k3];
+    sxd[i] = v0;
+    if (i1 < nu) sxd[i1] = v1;
+    if (i2 < nu) sxd[i2] = v2;
+    if (i3 < nu) sxd[i3] = v3;
+  }
+  for (int i = threadIdx.x; i <= nrows; i += 256) sptr[i] = rowptr[r0 + i];
+  __syncthreads();
+  const int sub = threadIdx.x & 7, g = threadIdx.x >> 3;          // 8 lanes per row, 32 rows per pass
+  for (int row = g; row < nrows; row += 32) {
+    const int64_t b = sptr[row + 1];
+    double s = 0.0;
+    for (int64_t e = sptr[row] + sub; e < b; e += 64) {
+      double v[8];
+      int k[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {                                // past the end: value +0, local index 0 (a staged entry)
+        const bool in = e + 8 * j < b;
+        v[j] = in ? vals[e + 8 * j] : 0.0;
+        k[j] = in ? (int)ploc[e + 8 * j] : 0;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s += v[j] * sxd[k[j]];
+    }
+    s = group_sum<8>(s);
+    if (sub == 0) ssum[row] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < nrows) {
+    const int64_t row = r0 + threadIdx.x;
+    const double di = din[row], ri = r[row] - ssum[threadIdx.x];
+    x[row] += di;
+    r[row] = ri;
+    dout[row] = c1 * di + c2 * ri / vals[diagpos[row]];
+  }
+}
+void launch_sweep_schur_tiled_f64(hipStream_t st, int tile_rows, int64_t n, int max_nu, const int64_t* rowptr, const double* vals,
+                                  const uint16_t* ploc, const int64_t* tile_uptr, const int32_t* ulist, const int64_t* diagpos,
+                                  double c1, double c2, const double* din, double* dout, double* x, double* r) {
+  const unsigned tiles = xcd_grid((n + tile_rows - 1) / tile_rows);
+  const size_t lds = (size_t)max_nu * sizeof(double);
+#define SCHUR_F64(TR) hipLaunchKernelGGL(k_sweep_schur_tiled_f64<TR>, dim3(tiles), dim3(256), lds, st, n, rowptr, vals, ploc, tile_uptr, ulist, diagpos, c1, c2, din, dout, x, r)
+  if (tile_rows == 32) SCHUR_F64(32);
+  else if (tile_rows == 64) SCHUR_F64(64);
+  else if (tile_rows == 128) SCHUR_F64(128);
+  else SCHUR_F64(256);
+#undef SCHUR_F64
+}
 // One Chebyshev sweep of the solid block in a single launch: t = A d_in (3x3 block-CSR, 16 lanes per node), then on the
 // first three lanes of the group (one component each)  r -= t,  x += d_in,  d_out = c1 d_in + c2 B^-1 r.
 // d is ping-ponged because other nodes still gather d_in; the product never goes through memory.
@@ -1848,6 +2066,63 @@ void launch_sweep_sb_b3(hipStream_t st, int64_t nS, const int64_t* sb_ptr, const
   else
     hipLaunchKernelGGL(k_sweep_sb_b3<1>, dim3((unsigned)blocks), dim3(256), 0, st, nS, sb_ptr, sb_col, vals, binv12, c1, c2, din,
                        dout, x, r);
+}
+// k_sweep_sb_b3<0> on the 40-byte FP32 records of k_pack_sb_f32: a block and its column in five 8-byte loads instead of ten
+// 4-byte ones; 16 lanes per row, the two 16-block strips and the bracketing of the sums as there
+__global__ __launch_bounds__(256) void k_sweep_sb_r(int64_t nS, const int64_t* __restrict__ sb_ptr, const uint2* __restrict__ rec,
+                                                    const float* __restrict__ binv12, float c1, float c2,
+                                                    const float* __restrict__ din, float* __restrict__ dout,
+                                                    float* __restrict__ x, float* __restrict__ r) {
+  const int sub = threadIdx.x & 15;
+  const int64_t nlb = (nS + 15) / 16, nwg = gridDim.x, span = xcd_span(nlb);
+  for (int64_t lb0 = blockIdx.x; lb0 < span; lb0 += nwg) {
+  const int64_t lb = xcd_unit(lb0, nlb);
+  const int64_t i = lb * 16 + (threadIdx.x >> 4);
+  if (lb >= 0 && i < nS) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    const int64_t bend = sb_ptr[i + 1];
+    for (int64_t b = sb_ptr[i] + sub; b < bend; b += 32) {
+      const bool p1 = b + 16 < bend;
+      const int64_t b1 = p1 ? b + 16 : b;
+      const uint2* pa = rec + 5 * b;
+      const uint2* pq = rec + 5 * b1;
+      const uint2 a01 = pa[0], a23 = pa[1], a45 = pa[2], a67 = pa[3], a8c = pa[4];
+      const uint2 q01 = pq[0], q23 = pq[1], q45 = pq[2], q67 = pq[3], q8c = pq[4];
+      const float4 xv = reinterpret_cast<const float4*>(din)[a8c.y];
+      float4 yv = reinterpret_cast<const float4*>(din)[q8c.y];
+      if (!p1) yv = make_float4(0.f, 0.f, 0.f, 0.f);
+      const float a0 = __uint_as_float(a01.x), a1 = __uint_as_float(a01.y), a2 = __uint_as_float(a23.x), a3 = __uint_as_float(a23.y),
+                  a4 = __uint_as_float(a45.x), a5 = __uint_as_float(a45.y), a6 = __uint_as_float(a67.x), a7 = __uint_as_float(a67.y),
+                  a8 = __uint_as_float(a8c.x);
+      const float q0 = __uint_as_float(q01.x), q1 = __uint_as_float(q01.y), q2 = __uint_as_float(q23.x), q3 = __uint_as_float(q23.y),
+                  q4 = __uint_as_float(q45.x), q5 = __uint_as_float(q45.y), q6 = __uint_as_float(q67.x), q7 = __uint_as_float(q67.y),
+                  q8 = __uint_as_float(q8c.x);
+      s0 += (a0 * xv.x + a1 * xv.y + a2 * xv.z) + (q0 * yv.x + q1 * yv.y + q2 * yv.z);
+      s1 += (a3 * xv.x + a4 * xv.y + a5 * xv.z) + (q3 * yv.x + q4 * yv.y + q5 * yv.z);
+      s2 += (a6 * xv.x + a7 * xv.y + a8 * xv.z) + (q6 * yv.x + q7 * yv.y + q8 * yv.z);
+    }
+    s0 = group_sum<16>(s0); s1 = group_sum<16>(s1); s2 = group_sum<16>(s2);
+    float rc = 0.f, dc = 0.f;
+    if (sub < 3) {
+      dc = din[4 * i + sub];
+      rc = r[4 * i + sub] - (sub == 0 ? s0 : (sub == 1 ? s1 : s2));
+    }
+    const float r0 = dpp_f<0x00>(rc), r1 = dpp_f<0x55>(rc), r2 = dpp_f<0xAA>(rc);
+    if (sub < 3) {
+      const float4 brow = reinterpret_cast<const float4*>(binv12 + 12 * i)[sub];
+      x[4 * i + sub] += dc;
+      r[4 * i + sub] = rc;
+      dout[4 * i + sub] = c1 * dc + c2 * (brow.x * r0 + brow.y * r1 + brow.z * r2);
+    }
+  }
+  }
+}
+void launch_sweep_sb_r(hipStream_t st, int64_t nS, const int64_t* sb_ptr, const void* rec, const float* binv12, float c1, float c2,
+                       const float* din, float* dout, float* x, float* r) {
+  int64_t blocks = xcd_grid((nS + 15) / 16);
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(k_sweep_sb_r, dim3((unsigned)blocks), dim3(256), 0, st, nS, sb_ptr, static_cast<const uint2*>(rec), binv12, c1, c2,
+                     din, dout, x, r);
 }
 void launch_sb_binv(hipStream_t st, int64_t nS, const int32_t* snode, const int64_t* diagpos3, const double* Avv,
                     float* binv12, double* binv9) {

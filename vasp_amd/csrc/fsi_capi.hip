@@ -197,7 +197,7 @@ int fsi_destroy(FsiCtx* ctx) {
   ctx->sb_ptr.release(); ctx->sb_src.release(); ctx->sb_vals.release(); ctx->sb_dinv.release();
   ctx->sb_binv12.release(); ctx->sb_binv9.release();
   ctx->dd_db32.release(); ctx->vv_db32.release(); ctx->dd_dinv32.release(); ctx->vvf_dinv32.release();
-  ctx->adv_rowmask.release(); ctx->vv_dinv.release(); ctx->Avp32.release(); ctx->Apv32.release(); ctx->dd_chat.release(); ctx->ones32.release(); ctx->dd_rowflag.release(); ctx->dd_rec.release(); ctx->vv_rec.release(); ctx->sb_rec.release();
+  ctx->adv_rowmask.release(); ctx->vv_dinv.release(); ctx->Avp32.release(); ctx->Apv32.release(); ctx->dd_chat.release(); ctx->ones32.release(); ctx->dd_rowflag.release(); ctx->dd_rec.release(); ctx->vv_rec.release(); ctx->sb_rec.release(); ctx->vv_rec32.release(); ctx->sb_rec32.release();
   ctx->tile_ploc.release(); ctx->tile_uptr.release(); ctx->tile_ulist.release();
   for (auto* b : {&ctx->ss_rowptr, &ctx->ss_diagpos, &ctx->ss_src}) b->release();
   for (auto* b : {&ctx->node_solid, &ctx->vrank, &ctx->cols3, &ctx->cols_vp, &ctx->cols_pv, &ctx->cols_pp}) b->release();

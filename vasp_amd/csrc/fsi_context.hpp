@@ -319,6 +319,7 @@ struct FsiCtx {
   fsi::DevBuf<uint8_t> adv_rowmask;          // [N2] 1: the node's A_dv rows have entries (solid nodes), 0: all zero, not streamed
   bool sweeps_fp16 = true;                   // FSI_SWEEPS_FP16=0: FP32 matrix values in the fine-level sweeps (k_sweep_tiled_f32 / k_sweep_sb_b3)
   fsi::DevBuf<uint32_t> dd_rec, vv_rec, sb_rec;   // packed FP16 records: [pairs], [pairs][2], [blocks][6] 32-bit words
+  fsi::DevBuf<uint32_t> vv_rec32, sb_rec32;   // FP32 records of the FP32 sweeps (k_pack_f3 / k_pack_sb_f32): [pairs][4], [blocks][10] 32-bit words
   bool fused_sweeps = true;                  // FSI_FUSED_SWEEPS=0: product and Chebyshev update of the FP32 sweeps as two launches
 
   float sbmg_gersh = 2.f, mg_gersh = 2.f;     // the row-sum bounds of the two coarse levels (fallback of the self-test)

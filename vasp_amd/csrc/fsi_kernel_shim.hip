@@ -253,6 +253,45 @@ int shim_sweep_tiled_h(int nv, int tn, int64_t N2, int max_nu, const int64_t* na
   SHIM_RUN(c, "launch_sweep_tiled_h",
            launch_sweep_tiled_h(c.st, nv, tn, N2, max_nu, dp, drec, du, dul, df, ddv, c1, c2, ddi, ddo, dx, dr));
 }
+// rec: the records of launch_pack_f3 (4 words per pair)
+int shim_sweep_tiled_r3(int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const uint32_t* rec, const int64_t* tile_uptr,
+                        const int32_t* ulist, const uint8_t* rowflag, const float* dinv, float c1, float c2, float* din, float* dout,
+                        float* x, float* r) {
+  Call c;
+  const int64_t np = nadj_ptr[N2], nt = tiles_of(N2, tn);
+  const int64_t* dp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const uint32_t* drec = c.in(rec, (size_t)(4 * np));
+  const int64_t* du = c.in(tile_uptr, (size_t)nt + 1);
+  const int32_t* dul = c.in(ulist, (size_t)tile_uptr[nt]);
+  const uint8_t* df = c.in(rowflag, (size_t)(3 * N2));
+  const float* ddv = c.in(dinv, (size_t)(4 * N2));
+  float* ddi = c.io(din, (size_t)(4 * N2));
+  float* ddo = c.io(dout, (size_t)(4 * N2));
+  float* dx = c.io(x, (size_t)(4 * N2));
+  float* dr = c.io(r, (size_t)(4 * N2));
+  SHIM_RUN(c, "launch_sweep_tiled_r3",
+           launch_sweep_tiled_r3(c.st, tn, N2, max_nu, dp, drec, du, dul, df, ddv, c1, c2, ddi, ddo, dx, dr));
+}
+// the one-ratio sweep (as shim_sweep_tiled_f32 with nv = 1) with two rows ahead in flight
+int shim_sweep_tiled_a1(int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const float* vals, const uint16_t* ploc,
+                        const int64_t* tile_uptr, const int32_t* ulist, const uint8_t* rowflag, const float* dinv, float c1, float c2,
+                        float* din, float* dout, float* x, float* r) {
+  Call c;
+  const int64_t np = nadj_ptr[N2], nt = tiles_of(N2, tn);
+  const int64_t* dp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const float* dv = c.in(vals, (size_t)np);
+  const uint16_t* dl = c.in(ploc, (size_t)np);
+  const int64_t* du = c.in(tile_uptr, (size_t)nt + 1);
+  const int32_t* dul = c.in(ulist, (size_t)tile_uptr[nt]);
+  const uint8_t* df = c.in(rowflag, (size_t)(3 * N2));
+  const float* ddv = c.in(dinv, (size_t)(4 * N2));
+  float* ddi = c.io(din, (size_t)(4 * N2));
+  float* ddo = c.io(dout, (size_t)(4 * N2));
+  float* dx = c.io(x, (size_t)(4 * N2));
+  float* dr = c.io(r, (size_t)(4 * N2));
+  SHIM_RUN(c, "launch_sweep_tiled_a1",
+           launch_sweep_tiled_a1(c.st, tn, N2, max_nu, dp, dv, dl, du, dul, df, ddv, c1, c2, ddi, ddo, dx, dr));
+}
 // FP16 records.  h1: rec[e] = half(v[e]) | loc[e] << 16.  h3: rec[2e] = half(v[3e]) | half(v[3e+1]) << 16,
 // rec[2e+1] = half(v[3e+2]) | loc[e] << 16.  sb: per 3x3 block six words (a0 a1)(a2 a3)(a4 a5)(a6 a7)(a8 0)(column).
 // half() is the device's float -> _Float16 conversion (round to nearest even).
@@ -276,6 +315,22 @@ int shim_pack_sb(int64_t nb, const float* v, const int32_t* col, uint32_t* rec) 
   const int32_t* dc = c.in(col, (size_t)nb);
   uint32_t* drec = c.io(rec, (size_t)(6 * nb));
   SHIM_RUN(c, "launch_pack_sb", launch_pack_sb(c.st, nb, dv, dc, drec));
+}
+// FP32 records (bits of the floats, as stored).  f3: rec[4e..4e+2] = v[3e..3e+2], rec[4e+3] = loc[e].  sb_f32: per 3x3 block
+// ten words a0 .. a8, column.
+int shim_pack_f3(int64_t n, const float* v, const uint16_t* loc, uint32_t* rec) {
+  Call c;
+  const float* dv = c.in(v, (size_t)(3 * n));
+  const uint16_t* dl = c.in(loc, (size_t)n);
+  uint32_t* drec = c.io(rec, (size_t)(4 * n));
+  SHIM_RUN(c, "launch_pack_f3", launch_pack_f3(c.st, n, dv, dl, drec));
+}
+int shim_pack_sb_f32(int64_t nb, const float* v, const int32_t* col, uint32_t* rec) {
+  Call c;
+  const float* dv = c.in(v, (size_t)(9 * nb));
+  const int32_t* dc = c.in(col, (size_t)nb);
+  uint32_t* drec = c.io(rec, (size_t)(10 * nb));
+  SHIM_RUN(c, "launch_pack_sb_f32", launch_pack_sb_f32(c.st, nb, dv, dc, drec));
 }
 // n floats; dinv may not be null
 int shim_cheb_init_f32(int64_t n, const float* rhs, const float* dinv, float inv_theta, float* x, float* r, float* d) {
@@ -321,6 +376,20 @@ int shim_sweep_sb_b3(int64_t nS, const int64_t* sb_ptr, const int32_t* sb_col, c
   float* dx = c.io(x, (size_t)(4 * nS));
   float* dr = c.io(r, (size_t)(4 * nS));
   SHIM_RUN(c, "launch_sweep_sb_b3", launch_sweep_sb_b3(c.st, nS, dp, dc, dv, dbi, c1, c2, ddi, ddo, dx, dr, level));
+}
+// rec: the records of launch_pack_sb_f32 (10 words per block)
+int shim_sweep_sb_r(int64_t nS, const int64_t* sb_ptr, const uint32_t* rec, const float* binv12, float c1, float c2, float* din,
+                    float* dout, float* x, float* r) {
+  Call c;
+  const int64_t nb = sb_ptr[nS];
+  const int64_t* dp = c.in(sb_ptr, (size_t)nS + 1);
+  const uint32_t* drec = c.in(rec, (size_t)(10 * nb));
+  const float* dbi = c.in(binv12, (size_t)(12 * nS));
+  float* ddi = c.io(din, (size_t)(4 * nS));
+  float* ddo = c.io(dout, (size_t)(4 * nS));
+  float* dx = c.io(x, (size_t)(4 * nS));
+  float* dr = c.io(r, (size_t)(4 * nS));
+  SHIM_RUN(c, "launch_sweep_sb_r", launch_sweep_sb_r(c.st, nS, dp, drec, dbi, c1, c2, ddi, ddo, dx, dr));
 }
 int shim_sweep_sb_h(int64_t nS, const int64_t* sb_ptr, const uint32_t* rec, const float* binv12, float c1, float c2, float* din,
                     float* dout, float* x, float* r) {
@@ -401,6 +470,25 @@ int shim_sweep_schur_tiled(int tile_rows, int64_t n, int max_nu, const int64_t* 
   double* dr = c.io(r, (size_t)n);
   SHIM_RUN(c, "launch_sweep_schur_tiled",
            launch_sweep_schur_tiled(c.st, tile_rows, n, max_nu, dp, drec, du, dul, ddv, c1, c2, ddi, ddo, dx, dr));
+}
+// FP64 values in CSR order with the 16-bit tile-local columns ploc; tiles of tile_rows rows: tile_uptr, ulist
+int shim_sweep_schur_tiled_f64(int tile_rows, int64_t n, int max_nu, const int64_t* rowptr, const double* vals, const uint16_t* ploc,
+                               const int64_t* tile_uptr, const int32_t* ulist, const int64_t* diagpos, double c1, double c2,
+                               double* din, double* dout, double* x, double* r) {
+  Call c;
+  const int64_t nnz = rowptr[n], nt = (n + tile_rows - 1) / tile_rows;
+  const int64_t* dp = c.in(rowptr, (size_t)n + 1);
+  const double* dv = c.in(vals, (size_t)nnz);
+  const uint16_t* dl = c.in(ploc, (size_t)nnz);
+  const int64_t* du = c.in(tile_uptr, (size_t)nt + 1);
+  const int32_t* dul = c.in(ulist, (size_t)tile_uptr[nt]);
+  const int64_t* dg = c.in(diagpos, (size_t)n);
+  double* ddi = c.io(din, (size_t)n);
+  double* ddo = c.io(dout, (size_t)n);
+  double* dx = c.io(x, (size_t)n);
+  double* dr = c.io(r, (size_t)n);
+  SHIM_RUN(c, "launch_sweep_schur_tiled_f64",
+           launch_sweep_schur_tiled_f64(c.st, tile_rows, n, max_nu, dp, dv, dl, du, dul, dg, c1, c2, ddi, ddo, dx, dr));
 }
 
 int shim_tile_limit() { return tile_limit(); }
@@ -787,7 +875,7 @@ int shim_ctx_array(const FsiCtx* ctx, const char* name, void* host, int64_t* cou
                          E(mg_cfine),   E(mg_Ac),     E(mg_cc),   E(mg_d0),      E(mg_dcinv4),   E(mg_cflag),    E(sbmg_par),
                          E(sbmg_pw),    E(sbmg_chptr), E(sbmg_child), E(sbmg_chw), E(sbmg_cptr),  E(sbmg_ccol),   E(sbmg_cfine),
                          E(sbmg_cvals), E(sbmg_cbinv12), E(sbmg_flag), E(sbmg_cflag), E(sb_binv9), E(sb_dinv),   E(dd_dinv32),
-                         E(vvf_dinv32)};
+                         E(vvf_dinv32),  E(vv_rec32),   E(sb_rec32)};
 #undef E
   for (const Entry& t : table) {
     if (std::strcmp(t.name, name) != 0) continue;

@@ -267,6 +267,17 @@ void launch_sweep_tiled_h(hipStream_t st, int nv, int tn, int64_t N2, int max_nu
                           float c2, const float* din, float* dout, float* x, float* r);
 void launch_sweep_sb_h(hipStream_t st, int64_t nS, const int64_t* sb_ptr, const void* rec, const float* binv12, float c1, float c2,
                        const float* din, float* dout, float* x, float* r);
+// FP32 records of the FP32 fine-level sweeps (k_pack_f3 / k_pack_sb_f32; bitwise the sums of k_sweep_tiled_f32 / k_sweep_sb_b3<0>)
+void launch_pack_f3(hipStream_t st, int64_t n, const float* v, const uint16_t* loc, void* rec);
+void launch_pack_sb_f32(hipStream_t st, int64_t nb, const float* v, const int32_t* col, void* rec);
+void launch_sweep_tiled_r3(hipStream_t st, int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const void* rec,
+                           const int64_t* tile_uptr, const int32_t* ulist, const uint8_t* rowflag, const float* dinv, float c1,
+                           float c2, const float* din, float* dout, float* x, float* r);
+void launch_sweep_tiled_a1(hipStream_t st, int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const float* vals,
+                           const uint16_t* ploc, const int64_t* tile_uptr, const int32_t* ulist, const uint8_t* rowflag,
+                           const float* dinv, float c1, float c2, const float* din, float* dout, float* x, float* r);
+void launch_sweep_sb_r(hipStream_t st, int64_t nS, const int64_t* sb_ptr, const void* rec, const float* binv12, float c1, float c2,
+                       const float* din, float* dout, float* x, float* r);
 void launch_sweep_sc_f32(hipStream_t st, int64_t N2, const int64_t* nadj_ptr, const int32_t* nadj, const float* chat,
                          const uint8_t* rowflag, float c1, float c2, const float* din, float* dout, float* x, float* r);
 void launch_spmv_sc_f32(hipStream_t st, int64_t N2, const int64_t* nadj_ptr, const int32_t* nadj, const float* chat,
@@ -305,6 +316,9 @@ void launch_sweep_csr_mixed(hipStream_t st, int64_t n, const int64_t* rowptr, co
 void launch_sweep_schur_tiled(hipStream_t st, int tile_rows, int64_t n, int max_nu, const int64_t* rowptr, const uint32_t* rec,
                               const int64_t* tile_uptr, const int32_t* ulist, const double* dinv, double c1, double c2,
                               const double* din, double* dout, double* x, double* r);
+void launch_sweep_schur_tiled_f64(hipStream_t st, int tile_rows, int64_t n, int max_nu, const int64_t* rowptr, const double* vals,
+                                  const uint16_t* ploc, const int64_t* tile_uptr, const int32_t* ulist, const int64_t* diagpos,
+                                  double c1, double c2, const double* din, double* dout, double* x, double* r);
 void launch_sbmg_flags(hipStream_t st, int64_t nS, const int64_t* sb_ptr, const int32_t* sb_col, const float* vals, uint8_t* flag);
 void launch_sbmg_rap(hipStream_t st, int64_t nc, const int64_t* chptr, const int32_t* child, const float* chw,
                      const int64_t* sb_ptr, const int32_t* sb_col, const float* vals, const int32_t* snode,

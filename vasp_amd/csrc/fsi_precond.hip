@@ -85,6 +85,9 @@ void cheb_db_f32(FsiCtx* ctx, const float* db, const float* dinv, const double* 
       if (ctx->sweeps_fp16 && db == ctx->vv_db32.p)
         launch_sweep_tiled_h(st, 3, ctx->tile_nodes, ctx->N2, ctx->tile_max_nu, ctx->nadj_ptr.p, ctx->vv_rec.p, ctx->tile_uptr.p, ctx->tile_ulist.p, nullptr,
                              dinv, (float)(rn * rho), (float)(2.0 * rn / de), da, db_, fx, fr);
+      else if (ctx->vv_rec32.p && db == ctx->vv_db32.p)
+        launch_sweep_tiled_r3(st, ctx->tile_nodes, ctx->N2, ctx->tile_max_nu, ctx->nadj_ptr.p, ctx->vv_rec32.p, ctx->tile_uptr.p, ctx->tile_ulist.p, nullptr,
+                             dinv, (float)(rn * rho), (float)(2.0 * rn / de), da, db_, fx, fr);
       else
         launch_sweep_tiled_f32(st, 3, ctx->tile_nodes, ctx->N2, ctx->tile_max_nu, ctx->nadj_ptr.p, db, ctx->tile_ploc.p, ctx->tile_uptr.p, ctx->tile_ulist.p,
                                nullptr, dinv, (float)(rn * rho), (float)(2.0 * rn / de), da, db_, fx, fr);
@@ -178,6 +181,8 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
           if (timed) (void)hipEventRecord(ctx->ss_ev0[sample], st);
           if (ctx->sweeps_fp16 && ctx->sb_rec.p)
             launch_sweep_sb_h(st, ctx->nS, ctx->sb_ptr.p, ctx->sb_rec.p, ctx->sb_binv12.p, c1, c2, dcur, dnext, fx, fr);
+          else if (ctx->sb_rec32.p)
+            launch_sweep_sb_r(st, ctx->nS, ctx->sb_ptr.p, ctx->sb_rec32.p, ctx->sb_binv12.p, c1, c2, dcur, dnext, fx, fr);
           else
             launch_sweep_sb_b3(st, ctx->nS, ctx->sb_ptr.p, ctx->sb_col.p, ctx->sb_vals.p, ctx->sb_binv12.p, c1, c2, dcur, dnext, fx, fr);
           if (timed) (void)hipEventRecord(ctx->ss_ev1[sample], st);
@@ -232,8 +237,12 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
         const double rn = 1.0 / (2.0 * sig - rho);
         if (timed) (void)hipEventRecord(ctx->ss_ev0[k], st);
         if (fused) {
-          launch_sweep_sb_b3(st, ctx->nS, ctx->sb_ptr.p, ctx->sb_col.p, ctx->sb_vals.p, ctx->sb_binv12.p, (float)(rn * rho),
-                             (float)(2.0 * rn / de), dcur, dnext, fx, fr);
+          if (ctx->sb_rec32.p)
+            launch_sweep_sb_r(st, ctx->nS, ctx->sb_ptr.p, ctx->sb_rec32.p, ctx->sb_binv12.p, (float)(rn * rho), (float)(2.0 * rn / de),
+                              dcur, dnext, fx, fr);
+          else
+            launch_sweep_sb_b3(st, ctx->nS, ctx->sb_ptr.p, ctx->sb_col.p, ctx->sb_vals.p, ctx->sb_binv12.p, (float)(rn * rho),
+                               (float)(2.0 * rn / de), dcur, dnext, fx, fr);
           std::swap(dcur, dnext);
           if (timed) (void)hipEventRecord(ctx->ss_ev1[k], st);
         } else {
@@ -337,7 +346,11 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
       const double rn = 1.0 / (2.0 * sig - rho);
       const bool timed = ctx->sample_budget > 0 && k < 4 && ctx->sch_ev0[0];
       if (timed) (void)hipEventRecord(ctx->sch_ev0[k], st);
-      launch_sweep_csr_f64(st, V, ctx->s_rowptr.p, ctx->s_cols.p, ctx->s_vals.p, ctx->s_diagpos.p, rn * rho, 2.0 * rn / de, pa, pb, dp, pr);
+      if (ctx->schur_tiled)      // the tiles of the FP16 form with the FP64 values: bitwise the sweep of launch_sweep_csr_f64
+        launch_sweep_schur_tiled_f64(st, ctx->schur_tile, V, ctx->s_tile_max_nu, ctx->s_rowptr.p, ctx->s_vals.p, ctx->s_ploc.p,
+                                     ctx->s_tile_uptr.p, ctx->s_tile_ulist.p, ctx->s_diagpos.p, rn * rho, 2.0 * rn / de, pa, pb, dp, pr);
+      else
+        launch_sweep_csr_f64(st, V, ctx->s_rowptr.p, ctx->s_cols.p, ctx->s_vals.p, ctx->s_diagpos.p, rn * rho, 2.0 * rn / de, pa, pb, dp, pr);
       if (timed) { (void)hipEventRecord(ctx->sch_ev1[k], st); ctx->sch_samples_pending = k + 1; }
       std::swap(pa, pb);
       rho = rn;
@@ -412,9 +425,9 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
         if (ctx->sweeps_fp16)
           launch_sweep_tiled_h(st, 1, ctx->tile_nodes, N2, ctx->tile_max_nu, ctx->nadj_ptr.p, ctx->dd_rec.p, ctx->tile_uptr.p, ctx->tile_ulist.p,
                                ctx->dd_rowflag.p, nullptr, c1, c2, dcur, dnext, fx, fr);
-        else
-          launch_sweep_tiled_f32(st, 1, ctx->tile_nodes, N2, ctx->tile_max_nu, ctx->nadj_ptr.p, ctx->dd_chat.p, ctx->tile_ploc.p, ctx->tile_uptr.p, ctx->tile_ulist.p,
-                                 ctx->dd_rowflag.p, nullptr, c1, c2, dcur, dnext, fx, fr);
+        else      // k_sweep_tiled_f32<1> with two rows ahead in flight (same arrays, same sums)
+          launch_sweep_tiled_a1(st, ctx->tile_nodes, N2, ctx->tile_max_nu, ctx->nadj_ptr.p, ctx->dd_chat.p, ctx->tile_ploc.p, ctx->tile_uptr.p,
+                                ctx->tile_ulist.p, ctx->dd_rowflag.p, nullptr, c1, c2, dcur, dnext, fx, fr);
         if (timed) { (void)hipEventRecord(ctx->sc_ev1[k_sample], st); ctx->sc_samples_pending = k_sample + 1; }
         std::swap(dcur, dnext);
       };
@@ -686,6 +699,9 @@ int refresh_preconditioner(FsiCtx* ctx) {
         if (!ctx->dd_rec.p) { HIPCHK(ctx->dd_rec.alloc(npairs)); HIPCHK(ctx->vv_rec.alloc(2 * npairs)); }
         launch_pack_h1(st, npairs, ctx->dd_chat.p, ctx->tile_ploc.p, ctx->dd_rec.p);
         launch_pack_h3(st, npairs, ctx->vv_db32.p, ctx->tile_ploc.p, ctx->vv_rec.p);
+      } else if (ctx->tiled && ctx->fused_sweeps && ctx->sweeps_fp32) {   // FP32 records of the fluid block (k_pack_f3): three values and the index in one load
+        if (!ctx->vv_rec32.p) HIPCHK(ctx->vv_rec32.alloc(4 * npairs));
+        launch_pack_f3(st, npairs, ctx->vv_db32.p, ctx->tile_ploc.p, ctx->vv_rec32.p);
       }
       launch_dinv_f32(st, ctx->N2, nullptr, ctx->diagpos3.p, ctx->Mdd.vals.p, ctx->dd_dinv32.p);
       launch_dinv_f32(st, ctx->N2, ctx->mask_f.p, ctx->diagpos3.p, ctx->Mvv.vals.p, ctx->vvf_dinv32.p);
@@ -695,6 +711,9 @@ int refresh_preconditioner(FsiCtx* ctx) {
     if (ctx->sweeps_fp16 && ctx->solid_fp32 && ctx->sb_nblocks > 0) {
       if (!ctx->sb_rec.p) HIPCHK(ctx->sb_rec.alloc(6 * ctx->sb_nblocks));
       launch_pack_sb(st, ctx->sb_nblocks, ctx->sb_vals.p, ctx->sb_col.p, ctx->sb_rec.p);
+    } else if (ctx->solid_fp32 && ctx->solid_block_jacobi && ctx->solid_fused && ctx->sb_nblocks > 0) {      // FP32 records: a block and its column in 40 bytes (k_pack_sb_f32)
+      if (!ctx->sb_rec32.p) HIPCHK(ctx->sb_rec32.alloc(10 * ctx->sb_nblocks));
+      launch_pack_sb_f32(st, ctx->sb_nblocks, ctx->sb_vals.p, ctx->sb_col.p, ctx->sb_rec32.p);
     }
     launch_sb_dinv(st, ctx->nS, ctx->snode.p, ctx->diagpos3.p, ctx->Mvv.vals.p, ctx->sb_dinv.p);
     launch_sb_binv(st, ctx->nS, ctx->snode.p, ctx->diagpos3.p, ctx->Mvv.vals.p, ctx->sb_binv12.p, ctx->sb_binv9.p);
