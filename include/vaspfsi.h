@@ -309,6 +309,27 @@ int fsi_stress_strain(FsiCtx* ctx, int64_t n, const int32_t* cells, double* out)
 int fsi_wall_shear_stress(FsiCtx* ctx, int64_t nf, const int32_t* facet_cells, const int32_t* facet_local, double mu,
                           double* out);
 
+/* ---- hemodynamic indices accumulated on the device over a run (fsi_hemo.hip) --------------------------------- */
+/* Replaces: the set-up of compute_hemodyanamics [REF src/vasp/postprocessing/postprocessing_fenics/compute_hemodynamics.py:
+ * 160-255]: opens a session on the listed exterior facets (cell + local index of the opposite vertex, as
+ * fsi_wall_shear_stress; a facet may not be listed twice) with dynamic viscosity mu > 0 and the time between two samples
+ * dt_sample > 0.  Replaces any open session; the accumulators start at zero.  Not for partitioned contexts. */
+int fsi_hemo_begin(FsiCtx* ctx, int64_t nf, const int32_t* facet_cells, const int32_t* facet_local, double mu,
+                   double dt_sample);
+/* Replaces: one iteration of the frame loop of compute_hemodyanamics [REF .../compute_hemodynamics.py:257-319]: tau of
+ * dvp_["n"] (bit for bit fsi_wall_shear_stress) added to the sums behind the indices.  wss_out (nullable): tau, (nf,3,3)
+ * as fsi_wall_shear_stress.  As in the reference, tau_prev is zero before the first sample: its TWSSG term is |tau_1| / dt.
+ * FSI_ERR_INVALID without an open session. */
+int fsi_hemo_sample(FsiCtx* ctx, double* wss_out);
+/* Replaces: the closing arithmetic of compute_hemodyanamics [REF .../compute_hemodynamics.py:321-350]: with n samples,
+ * per DG1 dof of the boundary mesh (facet f, vertex k -> 3 f + k; vertices in the order of fsi_wall_shear_stress)
+ * out[5][nf][3] = TAWSS = sum|tau| / n, OSI = (1 - |sum tau / n| / TAWSS) / 2, RRT = 1 / |sum tau / n|, ECAP = OSI / TAWSS,
+ * TWSSG = sum of the P1-projected |(tau - tau_prev) / dt_sample| / n; IEEE inf / NaN where a denominator vanishes.
+ * *samples (nullable) = n.  FSI_ERR_INVALID without a session or before the first sample.  The session stays open. */
+int fsi_hemo_indices(FsiCtx* ctx, double* out, int64_t* samples);
+/* Closes the session and frees its device memory (fsi_destroy does the same). */
+int fsi_hemo_end(FsiCtx* ctx);
+
 /* ---- timing of the device kernels (HIP events on the solver stream) ---------------------------------- */
 typedef struct FsiTimers {
   double residual_ms;  int64_t residual_calls;

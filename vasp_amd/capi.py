@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -148,6 +148,10 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_set_newton_forcing.argtypes = [vp, dbl]
     lib.fsi_stress_strain.argtypes = [vp, i64, vp, vp]
     lib.fsi_wall_shear_stress.argtypes = [vp, i64, vp, vp, dbl, vp]
+    lib.fsi_hemo_begin.argtypes = [vp, i64, vp, vp, dbl, dbl]
+    lib.fsi_hemo_sample.argtypes = [vp, vp]
+    lib.fsi_hemo_indices.argtypes = [vp, vp, C.POINTER(i64)]
+    lib.fsi_hemo_end.argtypes = [vp]
     lib.fsi_num_dofs.argtypes = [vp]
     lib.fsi_num_dofs.restype = i64
     lib.fsi_matrix_nnz.argtypes = [vp]
@@ -443,6 +447,35 @@ class HipBackend:
         out = np.empty((len(fc), 3, 3))
         self._check(self.lib.fsi_wall_shear_stress(self.ctx, len(fc), _ptr(fc), _ptr(fl), float(mu), _ptr(out)))
         return out
+
+    HEMO_INDICES = ("TAWSS", "OSI", "RRT", "ECAP", "TWSSG")
+
+    def hemodynamics_begin(self, facet_cells, facet_local, mu: float, dt_sample: float) -> None:
+        """Open the device-side hemodynamics session (fsi_hemo_begin) on exterior facets (cell, opposite local vertex) with
+        dynamic viscosity ``mu`` and ``dt_sample`` between two samples; replaces an open session."""
+        fc = np.ascontiguousarray(self.cell_u2i[np.asarray(facet_cells, dtype=np.int64)], dtype=np.int32)
+        fl = np.ascontiguousarray(facet_local, dtype=np.int32)
+        self._check(self.lib.fsi_hemo_begin(self.ctx, len(fc), _ptr(fc), _ptr(fl), float(mu), float(dt_sample)))
+        self._hemo_nf = len(fc)
+
+    def hemodynamics_sample(self, wss: bool = False):
+        """Add the WSS of dvp_["n"] to the session's sums (fsi_hemo_sample); with ``wss`` return it, (nf, 3, 3) as
+        ``wall_shear_stress``, else None."""
+        out = np.empty((getattr(self, "_hemo_nf", 0), 3, 3)) if wss else None
+        self._check(self.lib.fsi_hemo_sample(self.ctx, _ptr(out) if wss else None))
+        return out
+
+    def hemodynamics_indices(self) -> dict:
+        """TAWSS, OSI, RRT, ECAP, TWSSG as (nf, 3) arrays (DG1 dofs of the boundary mesh) and ``samples``."""
+        out = np.empty((5, getattr(self, "_hemo_nf", 0), 3))
+        n = C.c_int64(0)
+        self._check(self.lib.fsi_hemo_indices(self.ctx, _ptr(out), C.byref(n)))
+        res = {k: out[i].copy() for i, k in enumerate(self.HEMO_INDICES)}
+        res["samples"] = int(n.value)
+        return res
+
+    def hemodynamics_end(self) -> None:
+        self._check(self.lib.fsi_hemo_end(self.ctx))
 
     def tuning(self) -> dict:
         """The FsiTuning the context was created with."""

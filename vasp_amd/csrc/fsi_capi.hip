@@ -191,6 +191,7 @@ int fsi_destroy(FsiCtx* ctx) {
   ctx->enbr.release();
   ctx->epnbr.release();
   ctx->cellvals.release();
+  ctx->hemo.release();
   for (auto* b : {&ctx->Adv, &ctx->Avp, &ctx->Apv, &ctx->App, &ctx->blk, &ctx->Mdd.vals, &ctx->Mvv.vals, &ctx->mask_s, &ctx->mask_f, &ctx->ss_vals, &ctx->dd_db, &ctx->vv_db, &ctx->adv_db, &ctx->s_vals}) b->release();
   ctx->s_rowptr.release(); ctx->s_diagpos.release(); ctx->s_cols.release();
   for (auto* b : {&ctx->snode, &ctx->ss_cols, &ctx->sb_col, &ctx->sb_row, &ctx->sb_stride}) b->release();
@@ -1497,6 +1498,125 @@ int fsi_wall_shear_stress(FsiCtx* ctx, int64_t nf, const int32_t* facet_cells, c
     for (int k = 0; k < 3; ++k)
       for (int i = 0; i < 3; ++i) out[(f * 3 + k) * 3 + i] = h[((size_t)slot[f] * 4 + VERTS[facet_local[f]][k]) * 3 + i];
   dc.release(); dm.release(); dout.release();
+  return FSI_OK;
+}
+
+namespace {
+HemoAcc hemo_acc(FsiCtx* ctx) {
+  double* a = ctx->hemo.acc.p;
+  const int64_t nd = 3 * ctx->hemo.nf;
+  return HemoAcc{a, a + 3 * nd, a + 6 * nd, a + 7 * nd};
+}
+}  // namespace
+
+int fsi_hemo_begin(FsiCtx* ctx, int64_t nf, const int32_t* facet_cells, const int32_t* facet_local, double mu,
+                   double dt_sample) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (nf <= 0 || !facet_cells || !facet_local || !(mu > 0.0) || !(dt_sample > 0.0)) {
+    ctx->err = "fsi_hemo_begin: needs nf > 0 facets, mu > 0 and dt_sample > 0";
+    return FSI_ERR_INVALID;
+  }
+  if (ctx->part) { ctx->err = "fsi_hemo_begin: partitioned contexts are not supported"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  // as fsi_wall_shear_stress: one projection per boundary cell, a mask of its listed facets, and here the user index of each
+  std::vector<int32_t> ucell, mask, fidx;
+  {
+    std::vector<std::pair<int32_t, int64_t>> order((size_t)nf);
+    for (int64_t f = 0; f < nf; ++f) {
+      if (facet_cells[f] < 0 || facet_cells[f] >= ctx->C || facet_local[f] < 0 || facet_local[f] > 3) {
+        ctx->err = "fsi_hemo_begin: facet cell / local index out of range";
+        return FSI_ERR_INVALID;
+      }
+      order[f] = {facet_cells[f], f};
+    }
+    std::sort(order.begin(), order.end());
+    for (int64_t k = 0; k < nf; ++k) {
+      const int64_t f = order[k].second;
+      if (k == 0 || order[k].first != order[k - 1].first) {
+        ucell.push_back(order[k].first);
+        mask.push_back(0);
+        for (int j = 0; j < 4; ++j) fidx.push_back(-1);
+      }
+      if (mask.back() & (1 << facet_local[f])) { ctx->err = "fsi_hemo_begin: a facet is listed twice"; return FSI_ERR_INVALID; }
+      mask.back() |= 1 << facet_local[f];
+      fidx[(ucell.size() - 1) * 4 + facet_local[f]] = (int32_t)f;
+    }
+  }
+  // 12-point degree-6 rule on the reference triangle (FIAT _triangle_scheme(6), oracle.fsi_oracle.triangle12)
+  double tw[12], tl[12][3];
+  {
+    const double pa[2] = {0.063089014491502, 0.249286745170910}, pw[2] = {0.050844906370207, 0.116786275726379};
+    double px[12], py[12];
+    int q = 0;
+    for (int o = 0; o < 2; ++o) {
+      const double a = pa[o], b = 1.0 - 2.0 * a;
+      const double xy[3][2] = {{a, a}, {b, a}, {a, b}};
+      for (int k = 0; k < 3; ++k, ++q) { px[q] = xy[k][0]; py[q] = xy[k][1]; tw[q] = pw[o] / 2.0; }
+    }
+    const double a = 0.053145049844817, b = 0.310352451033784, c = 1.0 - a - b;
+    const double xy[6][2] = {{a, b}, {b, a}, {a, c}, {c, a}, {b, c}, {c, b}};
+    for (int k = 0; k < 6; ++k, ++q) { px[q] = xy[k][0]; py[q] = xy[k][1]; tw[q] = 0.082851075618374 / 2.0; }
+    for (q = 0; q < 12; ++q) { tl[q][0] = 1.0 - px[q] - py[q]; tl[q][1] = px[q]; tl[q][2] = py[q]; }
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hemo_upload_tables(tw, &tl[0][0]));
+  auto& h = ctx->hemo;
+  h.release();
+  h.nf = nf;
+  h.ncell = (int64_t)ucell.size();
+  h.mu = mu;
+  h.dt = dt_sample;
+  HIPCHK(h.cells.alloc(ucell.size()));
+  HIPCHK(h.mask.alloc(mask.size()));
+  HIPCHK(h.fidx.alloc(fidx.size()));
+  HIPCHK(h.acc.alloc((size_t)nf * 24));
+  HIPCHK(h.out.alloc((size_t)nf * 15));
+  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
+  HIPCHK(hipMemcpyAsync(h.cells.p, ucell.data(), ucell.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(h.mask.p, mask.data(), mask.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(h.fidx.p, fidx.data(), fidx.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(h.acc.p, 0, h.acc.n * sizeof(double), ctx->stream));   // zero whatever FSI_DEBUG_POISON filled in
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  h.open = true;
+  return FSI_OK;
+}
+
+int fsi_hemo_sample(FsiCtx* ctx, double* wss_out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto& h = ctx->hemo;
+  if (!h.open) { ctx->err = "fsi_hemo_sample: no hemodynamics session (fsi_hemo_begin first)"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  launch_hemo_sample(ctx->stream, h.ncell, elem_arrays(ctx), ctx->U.p, h.cells.p, h.mask.p, h.fidx.p, h.mu, h.dt, hemo_acc(ctx),
+                     wss_out ? h.out.p : nullptr);
+  HIPCHK(hipGetLastError());
+  h.samples += 1;
+  if (wss_out) {
+    HIPCHK(hipMemcpyAsync(wss_out, h.out.p, (size_t)h.nf * 9 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  return FSI_OK;
+}
+
+int fsi_hemo_indices(FsiCtx* ctx, double* out, int64_t* samples) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto& h = ctx->hemo;
+  if (!h.open) { ctx->err = "fsi_hemo_indices: no hemodynamics session (fsi_hemo_begin first)"; return FSI_ERR_INVALID; }
+  if (h.samples == 0) { ctx->err = "fsi_hemo_indices: no sample taken yet"; return FSI_ERR_INVALID; }
+  if (!out) { ctx->err = "fsi_hemo_indices: null output"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  launch_hemo_finish(ctx->stream, 3 * h.nf, (double)h.samples, hemo_acc(ctx), h.out.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, h.out.p, (size_t)h.nf * 15 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (samples) *samples = h.samples;
+  return FSI_OK;
+}
+
+int fsi_hemo_end(FsiCtx* ctx) {
+  if (!ctx) return FSI_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->hemo.release();
   return FSI_OK;
 }
 

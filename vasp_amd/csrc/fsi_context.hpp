@@ -374,4 +374,16 @@ struct FsiCtx {
   // host copy of the mesh needed after create
   std::vector<double> h_coords;
   std::vector<int32_t> h_tet_nodes;
+
+  // hemodynamics session (fsi_hemo_begin .. fsi_hemo_end): boundary cells, their facet masks and the user-order facet
+  // index of each (cell, local facet), uploaded once; accumulators per DG1 dof of the boundary mesh (fsi_hemo.hip)
+  struct Hemo {
+    bool open = false;
+    int64_t nf = 0, ncell = 0, samples = 0;
+    double mu = 0.0, dt = 0.0;
+    fsi::DevBuf<int32_t> cells, mask, fidx;  // [ncell], [ncell], [ncell][4] (-1: facet not listed)
+    fsi::DevBuf<double> acc;                 // [3 nf]: sum_tau[3], tau_prev[3], sum_mag, sum_twssg per dof
+    fsi::DevBuf<double> out;                 // [5][3 nf]: the indices, or one WSS frame [nf][3][3]
+    void release() { cells.release(); mask.release(); fidx.release(); acc.release(); out.release(); open = false; nf = ncell = samples = 0; }
+  } hemo;
 };

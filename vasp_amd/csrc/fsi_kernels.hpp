@@ -132,6 +132,18 @@ void launch_stress_strain(hipStream_t st, int64_t ncell, const ElemArrays& ea, c
 void launch_wss(hipStream_t st, int64_t ncell, const ElemArrays& ea, const double* U, const int32_t* cells, const int32_t* fmask,
                 double mu, double* out);
 
+// fsi_hemo.hip — hemodynamic indices accumulated over the saved frames of a run (per DG1 dof of the boundary mesh)
+struct HemoAcc {
+  double* sum_tau;      // [ndof][3]  sum of tau
+  double* tau_prev;     // [ndof][3]  tau of the previous sample (0 before the first)
+  double* sum_mag;      // [ndof]     sum of |tau|
+  double* sum_twssg;    // [ndof]     sum of the projected |(tau - tau_prev) / dt|
+};
+hipError_t hemo_upload_tables(const double* w, const double* lam);      // triangle rule: w[12], lam[12][3]
+void launch_hemo_sample(hipStream_t st, int64_t ncell, const ElemArrays& ea, const double* U, const int32_t* cells,
+                        const int32_t* fmask, const int32_t* fidx, double mu, double dt, const HemoAcc& acc, double* wss_out);
+void launch_hemo_finish(hipStream_t st, int64_t ndof, double samples, const HemoAcc& acc, double* out);
+
 // fsi_solver.hip — sparse / dense vector kernels
 void launch_expand_cols(hipStream_t st, int64_t N2, int64_t V, const int64_t* nadj_ptr, const int32_t* nadj,
                         const int64_t* padj_ptr, const int32_t* padj, const int32_t* prow_rank, const int64_t* rowptr,

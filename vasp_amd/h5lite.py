@@ -478,6 +478,7 @@ class H5Series:
         self._group_header = sg._header                      # object header of the series group: message body at + 16 + 8
         self._parent_entry = root._snod_entry[series]        # its symbol-table entry in the root group (cached bt / heap at + 24)
         self.names, self.addr = [], {}
+        self._bt_heap = {}                                   # children that are groups: their (B-tree, heap), cached in their entries
         self._f = open(path, "w+b")
         self._f.write(data)
         self._eof = len(data)
@@ -505,12 +506,27 @@ class H5Series:
         hdr = w._dataset_header(arr.shape, arr.dtype, daddr if arr.nbytes else UNDEF, arr.nbytes, attrs)
         self._write_at(w.origin, bytes(w.buf))
         self._eof = w.origin + len(w.buf)
+        self._link(name, hdr)
+
+    def append_group(self, name: str, group: Group) -> None:
+        """``/<series>/<name>`` as a whole group (datasets and subgroups) - one ``write_checkpoint`` frame, say - appended
+        the same way: its objects at the end of the file, then the series group's tables."""
+        if name in self.addr:
+            raise H5Error(f"/{self.series}/{name} exists")
+        w = _Writer(origin=_pad8(self._eof))
+        hdr = w._write_group(group)
+        self._write_at(w.origin, bytes(w.buf))
+        self._eof = w.origin + len(w.buf)
+        self._bt_heap[name] = group._bt_heap
+        self._link(name, hdr)
+
+    def _link(self, name: str, hdr: int) -> None:
         self.names.append(name)
         self.addr[name] = hdr
         # 2. the group's tables into the inactive metadata region
         names = sorted(self.names)
         probe = _Writer(origin=0)
-        probe._group_tables(names, self.addr, {})
+        probe._group_tables(names, self.addr, self._bt_heap)
         need = _pad8(len(probe.buf))
         if self._regions is None or need > self._cap:
             self._cap = max(self._reserve, 2 * need)
@@ -521,7 +537,7 @@ class H5Series:
             self._active = 1
         region = self._regions[1 - self._active]
         t = _Writer(origin=region)
-        bt, heap = t._group_tables(names, self.addr, {})
+        bt, heap = t._group_tables(names, self.addr, self._bt_heap)
         self._write_at(region, bytes(t.buf))
         self._active = 1 - self._active
         # 3. switch over: group header, parent's cached copy, end-of-file address

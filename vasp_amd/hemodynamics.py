@@ -1,0 +1,210 @@
+"""Hemodynamic indices of a run: the boundary facets of the fluid, their triangle mesh and the files of
+`<results>/Hemodynamic_indices/`, libhdf5-free.
+
+Counterpart of ``vasp-compute-hemo`` [REF src/vasp/postprocessing/postprocessing_fenics/compute_hemodynamics.py:160-372],
+whose arithmetic runs on the device during the run (``HipBackend.hemodynamics_*``, csrc/fsi_hemo.hip).  What is written:
+
+* ``WSS.{h5,xdmf}``: the time series of the sampled frames, ``/WSS/WSS_k/vector`` (k = 0, 1, ...), in DOLFIN's
+  ``XDMFFile.write_checkpoint`` layout for a vector DG1 function on triangles; ``cell_dofs``, ``x_cell_dofs``, ``cells`` and
+  ``mesh/{geometry,topology}`` sit under ``WSS_0``, where the reference's consumer reads them
+  [REF src/vasp/postprocessing/postprocessing_h5py/postprocessing_h5py_common.py:198-251] and its XDMF template points
+  [REF :639-670].  Frames are appended in place (``h5lite.H5Series.append_group``): one frame in memory at a time.
+* ``TAWSS``, ``OSI``, ``RRT``, ``ECAP``, ``TWSSG``: one scalar DG1 function each, ``/<name>/<name>_0``, at time 0.
+
+Dofs follow ``output.checkpoint``: DG1 node 3 f + k is vertex k of facet f, global dof = ncomp * node + component
+(interleaved ``vector``), ``cell_dofs`` component-major per cell.  The vertices of facet f are the local vertices of its
+cell without the opposite one, ascending - the order of ``HipBackend.wall_shear_stress``.  Geometry is the undeformed mesh.
+"""
+from __future__ import annotations
+
+import os
+from pathlib import Path
+from typing import Dict, Tuple
+
+import numpy as np
+
+from .h5lite import Dataset, Group, H5Series, write_h5
+from .mesh import FsiMesh
+
+INDEX_NAMES = ("TAWSS", "OSI", "RRT", "ECAP", "TWSSG")
+FACET_VERTS = np.array([[1, 2, 3], [0, 2, 3], [0, 1, 3], [0, 1, 2]])       # local vertices of the facet opposite vertex i
+
+
+def fluid_boundary_facets(mesh: FsiMesh, fluid_ids) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Exterior facets of the fluid sub-mesh (cells whose marker is in ``fluid_ids``): wall, inlet and outlet caps - what
+    DOLFIN's ``BoundaryMesh(fluid_mesh, "exterior")`` holds.  Returns (facet id, cell, local index of the opposite vertex),
+    in facet-id order."""
+    fc = mesh.facet_cells
+    is_f = np.isin(mesh.cell_markers, np.atleast_1d(np.asarray(fluid_ids)))
+    c0, c1 = fc[:, 0], fc[:, 1]
+    f0 = is_f[c0]
+    f1 = np.where(c1 >= 0, is_f[np.maximum(c1, 0)], False)
+    sel = np.nonzero(f0 ^ f1)[0]                       # exactly one fluid cell: boundary of the fluid sub-mesh
+    cell = np.where(f0[sel], c0[sel], c1[sel])
+    tv = mesh.tets[cell]                                # (n, 4)
+    on_facet = (tv[:, :, None] == mesh.facets[sel][:, None, :]).any(axis=2)
+    local = np.argmin(on_facet, axis=1)                 # the one vertex of the cell not on the facet
+    return sel, cell, local
+
+
+def boundary_triangles(mesh: FsiMesh, cells, local) -> Tuple[np.ndarray, np.ndarray]:
+    """Triangle mesh of the listed facets: (geometry (nv, 3): the original coordinates of the vertices it uses, compacted;
+    topology (nf, 3): per facet its vertices in DG1 dof order)."""
+    tri = mesh.tets[np.asarray(cells)[:, None], FACET_VERTS[np.asarray(local)]]
+    used, topo = np.unique(tri, return_inverse=True)
+    return np.ascontiguousarray(mesh.coords[used], dtype=np.float64), topo.reshape(-1, 3).astype(np.int64)
+
+
+def _dg1_group(values: np.ndarray, geometry: np.ndarray, topology: np.ndarray, dofmap: bool) -> Group:
+    """``<name>_k`` of ``write_checkpoint``: ``vector`` of a DG1 function on triangles (values (nf, 3[, ncomp])), with the
+    dof map and the mesh when ``dofmap``."""
+    nf = len(topology)
+    ncomp = 1 if values.ndim == 2 else values.shape[2]
+    g = Group()
+    g["vector"] = Dataset(np.ascontiguousarray(values, dtype=np.float64).reshape(-1, 1))
+    if dofmap:
+        nodes = np.arange(3 * nf, dtype=np.int64).reshape(nf, 3)
+        cell_dofs = (ncomp * nodes[:, :, None] + np.arange(ncomp)[None, None, :]).transpose(0, 2, 1).reshape(-1)
+        g["cell_dofs"] = Dataset(cell_dofs.astype(np.int64))
+        g["x_cell_dofs"] = Dataset((np.arange(nf + 1) * 3 * ncomp).astype(np.int64))
+        g["cells"] = Dataset(np.arange(nf, dtype=np.int64))
+        mg = Group()
+        mg["geometry"] = Dataset(np.ascontiguousarray(geometry, dtype=np.float64))
+        mg["topology"] = Dataset(np.ascontiguousarray(topology, dtype=np.int64), {"celltype": "triangle"})
+        g["mesh"] = mg
+    return g
+
+
+def _xdmf_grid(name: str, k: int, t: float, nf: int, nv: int, ncomp: int) -> str:
+    h5, first = f"{name}.h5", f"{name}/{name}_0"
+    ndofs = 3 * nf * ncomp
+    att = "Vector" if ncomp == 3 else "Scalar"
+    return f'''      <Grid Name="{name}_{k}" GridType="Uniform">
+        <Topology NumberOfElements="{nf}" TopologyType="Triangle" NodesPerElement="3">
+          <DataItem Dimensions="{nf} 3" NumberType="UInt" Format="HDF">{h5}:{first}/mesh/topology</DataItem>
+        </Topology>
+        <Geometry GeometryType="XYZ">
+          <DataItem Dimensions="{nv} 3" Format="HDF">{h5}:{first}/mesh/geometry</DataItem>
+        </Geometry>
+         <Time Value="{float(t)!r}" />
+        <Attribute ItemType="FiniteElementFunction" ElementFamily="DG" ElementDegree="1" ElementCell="triangle" Name="{name}" Center="Other" AttributeType="{att}">
+          <DataItem Dimensions="{ndofs} 1" NumberType="UInt" Format="HDF">{h5}:{first}/cell_dofs</DataItem>
+          <DataItem Dimensions="{ndofs} 1" NumberType="Float" Format="HDF">{h5}:{name}/{name}_{k}/vector</DataItem>
+          <DataItem Dimensions="{nf + 1} 1" NumberType="UInt" Format="HDF">{h5}:{first}/x_cell_dofs</DataItem>
+          <DataItem Dimensions="{nf} 1" NumberType="UInt" Format="HDF">{h5}:{first}/cells</DataItem>
+        </Attribute>
+      </Grid>
+'''
+
+
+def _xdmf_head(name: str) -> str:
+    return f'''<?xml version="1.0"?>
+<Xdmf Version="3.0">
+  <Domain>
+    <Grid GridType="Collection" CollectionType="Temporal" Name="{name}">
+'''
+
+
+XDMF_FOOTER = "    </Grid>\n  </Domain>\n</Xdmf>\n"
+
+
+class HemodynamicsWriter:
+    """``<results>/Hemodynamic_indices/``: ``write_wss`` appends one WSS frame (h5 and XDMF grow in place),
+    ``write_indices`` writes the five index files once."""
+
+    def __init__(self, folder, geometry: np.ndarray, topology: np.ndarray):
+        self.folder = Path(folder)
+        self.folder.mkdir(parents=True, exist_ok=True)
+        self.geometry, self.topology = geometry, topology
+        self.frames = 0
+        self._wss = None
+
+    def write_wss(self, tau: np.ndarray, t: float) -> None:
+        """tau (nf, 3, 3): the frame's WSS at the facet vertices."""
+        nf, nv = len(self.topology), len(self.geometry)
+        if tau.shape != (nf, 3, 3):
+            raise ValueError(f"WSS frame of shape {tau.shape}, expected {(nf, 3, 3)}")
+        if self._wss is None:
+            self._wss = H5Series(self.folder / "WSS.h5", Group(), "WSS")
+        k = self.frames
+        self._wss.append_group(f"WSS_{k}", _dg1_group(tau, self.geometry, self.topology, dofmap=k == 0))
+        path = self.folder / "WSS.xdmf"
+        grid = _xdmf_grid("WSS", k, t, nf, nv, 3)
+        if k == 0:
+            path.write_text(_xdmf_head("WSS") + grid + XDMF_FOOTER)
+        else:                                   # the new grid overwrites the closing tags, which follow it again
+            with open(path, "r+b") as f:
+                f.seek(-len(XDMF_FOOTER.encode()), os.SEEK_END)
+                f.write((grid + XDMF_FOOTER).encode())
+        self.frames += 1
+
+    def write_indices(self, indices: Dict[str, np.ndarray]) -> None:
+        """indices: TAWSS, OSI, RRT, ECAP, TWSSG as (nf, 3) arrays; each to ``<name>.{h5,xdmf}`` at time 0."""
+        nf, nv = len(self.topology), len(self.geometry)
+        for name in INDEX_NAMES:
+            vals = np.asarray(indices[name], dtype=np.float64)
+            if vals.shape != (nf, 3):
+                raise ValueError(f"{name} of shape {vals.shape}, expected {(nf, 3)}")
+            outer, root = Group(), Group()
+            outer[f"{name}_0"] = _dg1_group(vals, self.geometry, self.topology, dofmap=True)
+            root[name] = outer
+            write_h5(self.folder / f"{name}.h5", root)
+            (self.folder / f"{name}.xdmf").write_text(_xdmf_head(name) + _xdmf_grid(name, 0, 0.0, nf, nv, 1) + XDMF_FOOTER)
+
+    def close(self) -> None:
+        if self._wss is not None:
+            self._wss.close()
+            self._wss = None
+
+
+def osi_range_message(osi: np.ndarray, tol: float = 1e-12) -> str:
+    """The reference's closing check [REF compute_hemodynamics.py:366-372] as a log line."""
+    nan = int(np.isnan(osi).sum())                     # 0 / 0 where a dof never saw any shear
+    lo, hi = (float(np.nanmin(osi)), float(np.nanmax(osi))) if nan < osi.size else (np.nan, np.nan)
+    ok = nan == 0 and -tol <= lo < 0.5 and -tol < hi <= 0.5 + tol
+    return (f"OSI range [{lo:.6g}, {hi:.6g}]" + (f" ({nan} dofs NaN)" if nan else "") + ": "
+            + ("within 0 to 0.5" if ok else "NOT within 0 to 0.5"))
+
+
+def hemodynamics_refusal(v: dict, world: int, backend_cls) -> str:
+    """Why ``--hemodynamics`` cannot run with the resolved parameters ``v`` ('' if it can)."""
+    if not v.get("save_step"):
+        return "--hemodynamics samples the saved frames: it needs --save-step"
+    if v.get("restart_folder"):
+        return "--hemodynamics does not carry its sums through a checkpoint: it cannot be used with --restart-folder"
+    if world > 1:
+        return "--hemodynamics runs on one rank only (WORLD_SIZE > 1)"
+    if backend_cls is not None and not hasattr(backend_cls, "hemodynamics_begin"):
+        return f"--hemodynamics needs a backend with hemodynamics_begin ({getattr(backend_cls, '__name__', backend_cls)} has none)"
+    return ""
+
+
+class HemodynamicsRun:
+    """The driver's side of ``--hemodynamics``: the session on the exterior facets of the fluid (``dx_f_id``), one WSS
+    frame per saved Visualization frame, the indices at the end.  ``dt_sample`` = dt * save_step; mu = ``mu_f`` (its first
+    entry when it is a list, as the reference's ``vasp-compute-hemo`` takes one viscosity)."""
+
+    def __init__(self, backend, mesh: FsiMesh, ns: dict):
+        mu = ns["mu_f"][0] if isinstance(ns["mu_f"], (list, tuple)) else ns["mu_f"]
+        dt_sample = float(ns["dt"]) * int(ns["save_step"])
+        _, cells, local = fluid_boundary_facets(mesh, ns["dx_f_id"])
+        geometry, topology = boundary_triangles(mesh, cells, local)
+        self.backend = backend
+        backend.hemodynamics_begin(cells, local, float(mu), dt_sample)
+        self.writer = HemodynamicsWriter(Path(ns["results_folder"]) / "Hemodynamic_indices", geometry, topology)
+
+    def sample(self, t: float) -> None:
+        self.writer.write_wss(self.backend.hemodynamics_sample(wss=True), t)
+
+    def finish(self, out=print) -> None:
+        """The five index files (over the frames sampled so far) and the reference's OSI range check as a log line."""
+        try:
+            if self.writer.frames == 0:
+                out("Hemodynamic indices: no frame was sampled, nothing written")
+                return
+            ind = self.backend.hemodynamics_indices()
+            self.writer.write_indices(ind)
+            out(f"Hemodynamic indices of {ind['samples']} frames written to {self.writer.folder}")
+            out(osi_range_message(ind["OSI"]))
+        finally:
+            self.writer.close()

@@ -11,8 +11,10 @@ from __future__ import annotations
 
 import argparse
 import ast
+import contextlib
 import importlib
 import importlib.util
+import io
 import json
 import re
 import sys
@@ -65,6 +67,9 @@ def parse(argv: Optional[List[str]] = None) -> Dict[str, object]:
     ap.add_argument("--checkpoint-step", dest="checkpoint_step", type=int, default=None)
     ap.add_argument("--killtime", type=float, default=None)
     ap.add_argument("--new-arguments", dest="new_arguments", nargs="*", default=[])
+    ap.add_argument("--hemodynamics", action="store_const", const=True, default=None,
+                    help="accumulate WSS, TAWSS, OSI, RRT, ECAP and TWSSG on the device over the saved frames and write "
+                         "<results>/Hemodynamic_indices/ (what vasp-compute-hemo writes afterwards)")
     ap.add_argument("-c", "--config", dest="config", default=None,
                     help="config file with `key = value` lines (keys: the option names without dashes, or any problem-file "
                          "parameter); the command line wins over the file [REF docs/simulation.md:19-31]")
@@ -219,6 +224,36 @@ def default_backend(desc):
     return HipBackend(desc)
 
 
+def parameters(argv: Optional[List[str]] = None):
+    """The command line (and -c file) over the problem's ``set_problem_parameters`` over the defaults: (args, hook, v)."""
+    args = parse(argv)
+    problem = load_problem(args.pop("problem"))
+    hook = lambda name: getattr(problem, name, getattr(_defaults, name))
+    v = {k: (list(x) if isinstance(x, list) else x) for k, x in _defaults.default_variables.items()}
+    v = hook("set_problem_parameters")(default_variables=v, **args)
+    v.update(args)
+    return args, hook, v
+
+
+def _refuse_hemodynamics(argv, backend_factory, world: int) -> None:
+    """--hemodynamics: refuse before anything is built, on every rank (a refusal on rank 0 alone would leave the workers
+    waiting in run_worker)."""
+    args = parse(argv)
+    if not args.get("hemodynamics"):
+        return
+    from .hemodynamics import hemodynamics_refusal
+    with contextlib.redirect_stdout(io.StringIO()):
+        _, _, v = parameters(argv)
+    if backend_factory is default_backend:
+        from .capi import HipBackend
+        cls = HipBackend
+    else:
+        cls = backend_factory if isinstance(backend_factory, type) else None
+    why = hemodynamics_refusal(v, world, cls)
+    if why:
+        raise SystemExit(why)
+
+
 def prepare(argv: Optional[List[str]] = None):
     """Everything ``run`` does before the time loop: parameters, folders, mesh, hooks up to ``create_bcs``.
 
@@ -226,13 +261,7 @@ def prepare(argv: Optional[List[str]] = None):
     library consumes, a callable giving the current Dirichlet values, the interface-pressure object (or None) and the
     hook lookup.
     """
-    args = parse(argv)
-    problem = load_problem(args.pop("problem"))
-    hook = lambda name: getattr(problem, name, getattr(_defaults, name))
-
-    v = {k: (list(x) if isinstance(x, list) else x) for k, x in _defaults.default_variables.items()}
-    v = hook("set_problem_parameters")(default_variables=v, **args)
-    v.update(args)
+    args, hook, v = parameters(argv)
     build_properties(v)
     ns: Dict[str, object] = dict(v)
     ns["default_variables"] = v
@@ -370,6 +399,7 @@ def run(argv: Optional[List[str]] = None, backend_factory: Callable = default_ba
     import os
     rank0 = _rank() == 0
     world = int(os.environ.get("WORLD_SIZE", 1))
+    _refuse_hemodynamics(argv, backend_factory, world)
     driver_mode = world > 1 and backend_factory is default_backend and not os.environ.get("VASPFSI_SYMMETRIC")
     if driver_mode and not rank0:
         # Ranks 1 .. N-1 of `python -m torch.distributed.run --nproc-per-node N -m vasp_amd.monolithic ...`: they never read the
@@ -424,6 +454,12 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
     viz = None
     if ns.get("save_step") and rank0:
         viz = VisualizationWriter(ns["visualization_folder"], mesh, ns["save_deg"], run_index=restart_run)
+    hemo = None
+    if ns.get("hemodynamics"):                    # single rank, no restart, save_step set: run() checked it
+        from .hemodynamics import HemodynamicsRun
+        if not hasattr(backend, "hemodynamics_begin"):
+            raise SystemExit(f"--hemodynamics needs a backend with hemodynamics_begin ({type(backend).__name__} has none)")
+        hemo = HemodynamicsRun(backend, mesh, ns)
     first_step_num = ns["counter"]
 
     dt, T = float(ns["dt"]), float(ns["T"])
@@ -448,6 +484,8 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
                 checkpoint(ns["checkpoint_folder"], mesh, x, ns["default_variables"], t, ns["counter"])
         if viz is not None and ns["counter"] % int(ns["save_step"]) == 0:
             viz.write(ns["dvp_"]["n"].vector(), t)
+            if hemo is not None:
+                hemo.sample(t)
         elif ns.get("save_step") and ns["counter"] % int(ns["save_step"]) == 0:
             ns["dvp_"]["n"].vector()              # partitioned: every rank takes part in the gather
         ns["counter"] += 1
@@ -458,6 +496,8 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
         out("Solved for timestep %d, t = %.4f in %.1f s" % (ns["counter"], t, _time.perf_counter() - t0))
     if viz is not None:
         viz.close()
+    if hemo is not None:
+        hemo.finish(out)
     ns["time_loop_seconds"] = _time.perf_counter() - t_loop
     ns["newton_iterations"] = total_newton
     ns["solver_events"] = events_seen
