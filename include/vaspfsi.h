@@ -330,6 +330,23 @@ int fsi_hemo_indices(FsiCtx* ctx, double* out, int64_t* samples);
 /* Closes the session and frees its device memory (fsi_destroy does the same). */
 int fsi_hemo_end(FsiCtx* ctx);
 
+/* ---- solid stress / strain sampled on the device over a run (fsi_stress.hip) ------------------------------- */
+/* Replaces: the set-up of compute_stress_strain [REF src/vasp/postprocessing/postprocessing_fenics/compute_stress_strain.py:
+ * 160-187]: opens a session on n > 0 listed SOLID cells (indices in the mesh handed to fsi_create, as fsi_stress_strain),
+ * checked and uploaded once.  Replaces any open session; the sums start at zero.  Not for partitioned contexts. */
+int fsi_stress_begin(FsiCtx* ctx, int64_t n, const int32_t* cells);
+/* Replaces: one iteration of the frame loop of compute_stress_strain [REF .../compute_stress_strain.py:188-250]: the frame
+ * of dvp_["n"]'s displacement on the session's cells (bit for bit fsi_stress_strain), its eight principal values per cell
+ * added to the session's sums (MPStress_avg / MPStrain_avg .vector().axpy(1.0, ...)).  frame_out (nullable): (n, 80) as
+ * fsi_stress_strain.  FSI_ERR_INVALID without an open session. */
+int fsi_stress_sample(FsiCtx* ctx, double* frame_out);
+/* Replaces: the closing averages of compute_stress_strain [REF .../compute_stress_strain.py:255-257]: with n samples
+ * out[2][ncell][4] = MaxPrincipalStress_avg, MaxPrincipalStrain_avg = the sums of the sampled DG1 coefficients / n.
+ * *samples (nullable) = n.  FSI_ERR_INVALID without a session or before the first sample.  The session stays open. */
+int fsi_stress_averages(FsiCtx* ctx, double* out, int64_t* samples);
+/* Closes the session and frees its device memory (fsi_destroy does the same). */
+int fsi_stress_end(FsiCtx* ctx);
+
 /* ---- timing of the device kernels (HIP events on the solver stream) ---------------------------------- */
 typedef struct FsiTimers {
   double residual_ms;  int64_t residual_calls;

@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -152,6 +152,10 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_hemo_sample.argtypes = [vp, vp]
     lib.fsi_hemo_indices.argtypes = [vp, vp, C.POINTER(i64)]
     lib.fsi_hemo_end.argtypes = [vp]
+    lib.fsi_stress_begin.argtypes = [vp, i64, vp]
+    lib.fsi_stress_sample.argtypes = [vp, vp]
+    lib.fsi_stress_averages.argtypes = [vp, vp, C.POINTER(i64)]
+    lib.fsi_stress_end.argtypes = [vp]
     lib.fsi_num_dofs.argtypes = [vp]
     lib.fsi_num_dofs.restype = i64
     lib.fsi_matrix_nnz.argtypes = [vp]
@@ -437,8 +441,7 @@ class HipBackend:
         cells = np.ascontiguousarray(self.cell_u2i[np.asarray(cells, dtype=np.int64)], dtype=np.int32)
         out = np.empty((len(cells), 80))
         self._check(self.lib.fsi_stress_strain(self.ctx, len(cells), _ptr(cells), _ptr(out)))
-        return dict(TrueStress=out[:, :36].reshape(-1, 4, 3, 3), GreenLagrangeStrain=out[:, 36:72].reshape(-1, 4, 3, 3),
-                    MaxPrincipalStress=out[:, 72:76].copy(), MaxPrincipalStrain=out[:, 76:80].copy())
+        return self._stress_frame(out)
 
     def wall_shear_stress(self, facet_cells, facet_local, mu: float):
         """(nf, 3, 3) projected tangential traction at the vertices of exterior facets (cell, opposite local vertex)."""
@@ -476,6 +479,35 @@ class HipBackend:
 
     def hemodynamics_end(self) -> None:
         self._check(self.lib.fsi_hemo_end(self.ctx))
+
+    @staticmethod
+    def _stress_frame(out: np.ndarray) -> dict:
+        return dict(TrueStress=out[:, :36].reshape(-1, 4, 3, 3), GreenLagrangeStrain=out[:, 36:72].reshape(-1, 4, 3, 3),
+                    MaxPrincipalStress=out[:, 72:76].copy(), MaxPrincipalStrain=out[:, 76:80].copy())
+
+    def stress_strain_begin(self, cells) -> None:
+        """Open the device-side stress / strain session (fsi_stress_begin) on solid ``cells`` (user order, as
+        ``stress_strain``); replaces an open session."""
+        ci = np.ascontiguousarray(self.cell_u2i[np.asarray(cells, dtype=np.int64)], dtype=np.int32)
+        self._check(self.lib.fsi_stress_begin(self.ctx, len(ci), _ptr(ci)))
+        self._stress_n = len(ci)
+
+    def stress_strain_sample(self, frame: bool = False):
+        """Sample dvp_["n"] (fsi_stress_sample): the principal values go to the session's sums; with ``frame`` return the
+        frame, keyed as ``stress_strain`` (bitwise equal to it), else None."""
+        out = np.empty((getattr(self, "_stress_n", 0), 80)) if frame else None
+        self._check(self.lib.fsi_stress_sample(self.ctx, _ptr(out) if frame else None))
+        return self._stress_frame(out) if frame else None
+
+    def stress_strain_averages(self) -> dict:
+        """MaxPrincipalStress_avg and MaxPrincipalStrain_avg as (n, 4) arrays (DG1 coefficients per cell) and ``samples``."""
+        out = np.empty((2, getattr(self, "_stress_n", 0), 4))
+        k = C.c_int64(0)
+        self._check(self.lib.fsi_stress_averages(self.ctx, _ptr(out), C.byref(k)))
+        return dict(MaxPrincipalStress_avg=out[0].copy(), MaxPrincipalStrain_avg=out[1].copy(), samples=int(k.value))
+
+    def stress_strain_end(self) -> None:
+        self._check(self.lib.fsi_stress_end(self.ctx))
 
     def tuning(self) -> dict:
         """The FsiTuning the context was created with."""

@@ -192,6 +192,7 @@ int fsi_destroy(FsiCtx* ctx) {
   ctx->epnbr.release();
   ctx->cellvals.release();
   ctx->hemo.release();
+  ctx->stress.release();
   for (auto* b : {&ctx->Adv, &ctx->Avp, &ctx->Apv, &ctx->App, &ctx->blk, &ctx->Mdd.vals, &ctx->Mvv.vals, &ctx->mask_s, &ctx->mask_f, &ctx->ss_vals, &ctx->dd_db, &ctx->vv_db, &ctx->adv_db, &ctx->s_vals}) b->release();
   ctx->s_rowptr.release(); ctx->s_diagpos.release(); ctx->s_cols.release();
   for (auto* b : {&ctx->snode, &ctx->ss_cols, &ctx->sb_col, &ctx->sb_row, &ctx->sb_stride}) b->release();
@@ -1617,6 +1618,71 @@ int fsi_hemo_end(FsiCtx* ctx) {
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->hemo.release();
+  return FSI_OK;
+}
+
+int fsi_stress_begin(FsiCtx* ctx, int64_t n, const int32_t* cells) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (n <= 0 || !cells) { ctx->err = "fsi_stress_begin: needs n > 0 cells"; return FSI_ERR_INVALID; }
+  if (ctx->part) { ctx->err = "fsi_stress_begin: partitioned contexts are not supported"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  std::vector<int32_t> kinds((size_t)ctx->C);
+  HIPCHK(hipMemcpy(kinds.data(), ctx->cell_kind.p, (size_t)ctx->C * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < n; ++i) {
+    if (cells[i] < 0 || cells[i] >= ctx->C) { ctx->err = "fsi_stress_begin: cell out of range"; return FSI_ERR_INVALID; }
+    if (kinds[cells[i]] != 1) { ctx->err = "fsi_stress_begin: cell is not a solid cell"; return FSI_ERR_INVALID; }
+  }
+  auto& s = ctx->stress;
+  s.release();
+  s.n = n;
+  HIPCHK(s.cells.alloc((size_t)n));
+  HIPCHK(s.frame.alloc((size_t)n * 80));
+  HIPCHK(s.sums.alloc((size_t)n * 8));
+  HIPCHK(s.avg.alloc((size_t)n * 8));
+  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
+  HIPCHK(hipMemcpyAsync(s.cells.p, cells, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(s.sums.p, 0, s.sums.n * sizeof(double), ctx->stream));  // zero whatever FSI_DEBUG_POISON filled in
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  s.open = true;
+  return FSI_OK;
+}
+
+int fsi_stress_sample(FsiCtx* ctx, double* frame_out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto& s = ctx->stress;
+  if (!s.open) { ctx->err = "fsi_stress_sample: no stress / strain session (fsi_stress_begin first)"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  launch_stress_sample(ctx->stream, s.n, elem_arrays(ctx), elem_params(ctx), ctx->U.p, s.cells.p, s.frame.p, s.sums.p);
+  HIPCHK(hipGetLastError());
+  s.samples += 1;
+  if (frame_out) {
+    HIPCHK(hipMemcpyAsync(frame_out, s.frame.p, (size_t)s.n * 80 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  return FSI_OK;
+}
+
+int fsi_stress_averages(FsiCtx* ctx, double* out, int64_t* samples) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto& s = ctx->stress;
+  if (!s.open) { ctx->err = "fsi_stress_averages: no stress / strain session (fsi_stress_begin first)"; return FSI_ERR_INVALID; }
+  if (s.samples == 0) { ctx->err = "fsi_stress_averages: no sample taken yet"; return FSI_ERR_INVALID; }
+  if (!out) { ctx->err = "fsi_stress_averages: null output"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  launch_stress_average(ctx->stream, s.n, (double)s.samples, s.sums.p, s.avg.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, s.avg.p, (size_t)s.n * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (samples) *samples = s.samples;
+  return FSI_OK;
+}
+
+int fsi_stress_end(FsiCtx* ctx) {
+  if (!ctx) return FSI_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->stress.release();
   return FSI_OK;
 }
 

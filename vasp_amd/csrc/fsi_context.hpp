@@ -386,4 +386,16 @@ struct FsiCtx {
     fsi::DevBuf<double> out;                 // [5][3 nf]: the indices, or one WSS frame [nf][3][3]
     void release() { cells.release(); mask.release(); fidx.release(); acc.release(); out.release(); open = false; nf = ncell = samples = 0; }
   } hemo;
+
+  // stress / strain session (fsi_stress_begin .. fsi_stress_end): the solid cells, checked and uploaded once; the last
+  // sampled frame and the running sums of the principal values per cell (fsi_stress.hip)
+  struct Stress {
+    bool open = false;
+    int64_t n = 0, samples = 0;
+    fsi::DevBuf<int32_t> cells;              // [n]
+    fsi::DevBuf<double> frame;               // [n][80]: the layout of fsi_stress_strain
+    fsi::DevBuf<double> sums;                // [n][8]: MaxPrincipalStress[4], MaxPrincipalStrain[4] summed over the samples
+    fsi::DevBuf<double> avg;                 // [2][n][4]
+    void release() { cells.release(); frame.release(); sums.release(); avg.release(); open = false; n = samples = 0; }
+  } stress;
 };

@@ -132,6 +132,12 @@ void launch_stress_strain(hipStream_t st, int64_t ncell, const ElemArrays& ea, c
 void launch_wss(hipStream_t st, int64_t ncell, const ElemArrays& ea, const double* U, const int32_t* cells, const int32_t* fmask,
                 double mu, double* out);
 
+// fsi_stress.hip — solid stress / strain sampled over the saved frames of a run (per listed solid cell)
+hipError_t upload_stress_tables(const double* qw, const double* dN, const double* L);   // fsi_stress.hip's table copies
+void launch_stress_sample(hipStream_t st, int64_t ncell, const ElemArrays& ea, const ElemParams& ep, const double* U,
+                          const int32_t* cells, double* frame, double* sums);           // frame [n][80], sums [n][8]
+void launch_stress_average(hipStream_t st, int64_t ncell, double samples, const double* sums, double* out);   // out [2][n][4]
+
 // fsi_hemo.hip — hemodynamic indices accumulated over the saved frames of a run (per DG1 dof of the boundary mesh)
 struct HemoAcc {
   double* sum_tau;      // [ndof][3]  sum of tau

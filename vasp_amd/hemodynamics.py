@@ -55,39 +55,45 @@ def boundary_triangles(mesh: FsiMesh, cells, local) -> Tuple[np.ndarray, np.ndar
     return np.ascontiguousarray(mesh.coords[used], dtype=np.float64), topo.reshape(-1, 3).astype(np.int64)
 
 
-def _dg1_group(values: np.ndarray, geometry: np.ndarray, topology: np.ndarray, dofmap: bool) -> Group:
-    """``<name>_k`` of ``write_checkpoint``: ``vector`` of a DG1 function on triangles (values (nf, 3[, ncomp])), with the
-    dof map and the mesh when ``dofmap``."""
-    nf = len(topology)
-    ncomp = 1 if values.ndim == 2 else values.shape[2]
+CELLS = {"triangle": ("Triangle", 3), "tetrahedron": ("Tetrahedron", 4)}      # XDMF topology type, vertices per cell
+ATTRIBUTE_TYPES = {1: "Scalar", 3: "Vector", 9: "Tensor"}                       # by the number of components
+
+
+def _dg1_group(values: np.ndarray, geometry: np.ndarray, topology: np.ndarray, dofmap: bool,
+               celltype: str = "triangle") -> Group:
+    """``<name>_k`` of ``write_checkpoint``: ``vector`` of a DG1 function (values (ncell, vertices per cell[, component
+    shape]), interleaved per node, components row-major), with the dof map and the mesh when ``dofmap``."""
+    nf, nvc = len(topology), CELLS[celltype][1]
+    ncomp = int(np.prod(values.shape[2:], dtype=np.int64))
     g = Group()
     g["vector"] = Dataset(np.ascontiguousarray(values, dtype=np.float64).reshape(-1, 1))
     if dofmap:
-        nodes = np.arange(3 * nf, dtype=np.int64).reshape(nf, 3)
+        nodes = np.arange(nvc * nf, dtype=np.int64).reshape(nf, nvc)
         cell_dofs = (ncomp * nodes[:, :, None] + np.arange(ncomp)[None, None, :]).transpose(0, 2, 1).reshape(-1)
         g["cell_dofs"] = Dataset(cell_dofs.astype(np.int64))
-        g["x_cell_dofs"] = Dataset((np.arange(nf + 1) * 3 * ncomp).astype(np.int64))
+        g["x_cell_dofs"] = Dataset((np.arange(nf + 1) * nvc * ncomp).astype(np.int64))
         g["cells"] = Dataset(np.arange(nf, dtype=np.int64))
         mg = Group()
         mg["geometry"] = Dataset(np.ascontiguousarray(geometry, dtype=np.float64))
-        mg["topology"] = Dataset(np.ascontiguousarray(topology, dtype=np.int64), {"celltype": "triangle"})
+        mg["topology"] = Dataset(np.ascontiguousarray(topology, dtype=np.int64), {"celltype": celltype})
         g["mesh"] = mg
     return g
 
 
-def _xdmf_grid(name: str, k: int, t: float, nf: int, nv: int, ncomp: int) -> str:
+def _xdmf_grid(name: str, k: int, t: float, nf: int, nv: int, ncomp: int, celltype: str = "triangle") -> str:
     h5, first = f"{name}.h5", f"{name}/{name}_0"
-    ndofs = 3 * nf * ncomp
-    att = "Vector" if ncomp == 3 else "Scalar"
+    topo_type, nvc = CELLS[celltype]
+    ndofs = nvc * nf * ncomp
+    att = ATTRIBUTE_TYPES[ncomp]
     return f'''      <Grid Name="{name}_{k}" GridType="Uniform">
-        <Topology NumberOfElements="{nf}" TopologyType="Triangle" NodesPerElement="3">
-          <DataItem Dimensions="{nf} 3" NumberType="UInt" Format="HDF">{h5}:{first}/mesh/topology</DataItem>
+        <Topology NumberOfElements="{nf}" TopologyType="{topo_type}" NodesPerElement="{nvc}">
+          <DataItem Dimensions="{nf} {nvc}" NumberType="UInt" Format="HDF">{h5}:{first}/mesh/topology</DataItem>
         </Topology>
         <Geometry GeometryType="XYZ">
           <DataItem Dimensions="{nv} 3" Format="HDF">{h5}:{first}/mesh/geometry</DataItem>
         </Geometry>
          <Time Value="{float(t)!r}" />
-        <Attribute ItemType="FiniteElementFunction" ElementFamily="DG" ElementDegree="1" ElementCell="triangle" Name="{name}" Center="Other" AttributeType="{att}">
+        <Attribute ItemType="FiniteElementFunction" ElementFamily="DG" ElementDegree="1" ElementCell="{celltype}" Name="{name}" Center="Other" AttributeType="{att}">
           <DataItem Dimensions="{ndofs} 1" NumberType="UInt" Format="HDF">{h5}:{first}/cell_dofs</DataItem>
           <DataItem Dimensions="{ndofs} 1" NumberType="Float" Format="HDF">{h5}:{name}/{name}_{k}/vector</DataItem>
           <DataItem Dimensions="{nf + 1} 1" NumberType="UInt" Format="HDF">{h5}:{first}/x_cell_dofs</DataItem>

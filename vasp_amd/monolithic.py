@@ -70,6 +70,9 @@ def parse(argv: Optional[List[str]] = None) -> Dict[str, object]:
     ap.add_argument("--hemodynamics", action="store_const", const=True, default=None,
                     help="accumulate WSS, TAWSS, OSI, RRT, ECAP and TWSSG on the device over the saved frames and write "
                          "<results>/Hemodynamic_indices/ (what vasp-compute-hemo writes afterwards)")
+    ap.add_argument("--stress-strain", dest="stress_strain", action="store_const", const=True, default=None,
+                    help="compute the Cauchy stress, Green-Lagrange strain and their largest principal values on the device "
+                         "at every saved frame and write <results>/StressStrain/ (what vasp-compute-stress writes afterwards)")
     ap.add_argument("-c", "--config", dest="config", default=None,
                     help="config file with `key = value` lines (keys: the option names without dashes, or any problem-file "
                          "parameter); the command line wins over the file [REF docs/simulation.md:19-31]")
@@ -235,13 +238,14 @@ def parameters(argv: Optional[List[str]] = None):
     return args, hook, v
 
 
-def _refuse_hemodynamics(argv, backend_factory, world: int) -> None:
-    """--hemodynamics: refuse before anything is built, on every rank (a refusal on rank 0 alone would leave the workers
-    waiting in run_worker)."""
+def _refuse_sessions(argv, backend_factory, world: int) -> None:
+    """--hemodynamics, --stress-strain: refuse before anything is built, on every rank (a refusal on rank 0 alone would leave
+    the workers waiting in run_worker)."""
     args = parse(argv)
-    if not args.get("hemodynamics"):
+    if not (args.get("hemodynamics") or args.get("stress_strain")):
         return
     from .hemodynamics import hemodynamics_refusal
+    from .stress_strain import stress_strain_refusal
     with contextlib.redirect_stdout(io.StringIO()):
         _, _, v = parameters(argv)
     if backend_factory is default_backend:
@@ -249,9 +253,10 @@ def _refuse_hemodynamics(argv, backend_factory, world: int) -> None:
         cls = HipBackend
     else:
         cls = backend_factory if isinstance(backend_factory, type) else None
-    why = hemodynamics_refusal(v, world, cls)
-    if why:
-        raise SystemExit(why)
+    for key, refusal in (("hemodynamics", hemodynamics_refusal), ("stress_strain", stress_strain_refusal)):
+        why = refusal(v, world, cls) if v.get(key) else ""
+        if why:
+            raise SystemExit(why)
 
 
 def prepare(argv: Optional[List[str]] = None):
@@ -399,7 +404,7 @@ def run(argv: Optional[List[str]] = None, backend_factory: Callable = default_ba
     import os
     rank0 = _rank() == 0
     world = int(os.environ.get("WORLD_SIZE", 1))
-    _refuse_hemodynamics(argv, backend_factory, world)
+    _refuse_sessions(argv, backend_factory, world)
     driver_mode = world > 1 and backend_factory is default_backend and not os.environ.get("VASPFSI_SYMMETRIC")
     if driver_mode and not rank0:
         # Ranks 1 .. N-1 of `python -m torch.distributed.run --nproc-per-node N -m vasp_amd.monolithic ...`: they never read the
@@ -460,6 +465,12 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
         if not hasattr(backend, "hemodynamics_begin"):
             raise SystemExit(f"--hemodynamics needs a backend with hemodynamics_begin ({type(backend).__name__} has none)")
         hemo = HemodynamicsRun(backend, mesh, ns)
+    stress = None
+    if ns.get("stress_strain"):                   # as --hemodynamics: run() checked it
+        from .stress_strain import StressStrainRun
+        if not hasattr(backend, "stress_strain_begin"):
+            raise SystemExit(f"--stress-strain needs a backend with stress_strain_begin ({type(backend).__name__} has none)")
+        stress = StressStrainRun(backend, mesh, ns)
     first_step_num = ns["counter"]
 
     dt, T = float(ns["dt"]), float(ns["T"])
@@ -486,6 +497,8 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
             viz.write(ns["dvp_"]["n"].vector(), t)
             if hemo is not None:
                 hemo.sample(t)
+            if stress is not None:
+                stress.sample(t)
         elif ns.get("save_step") and ns["counter"] % int(ns["save_step"]) == 0:
             ns["dvp_"]["n"].vector()              # partitioned: every rank takes part in the gather
         ns["counter"] += 1
@@ -498,6 +511,8 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
         viz.close()
     if hemo is not None:
         hemo.finish(out)
+    if stress is not None:
+        stress.finish(out)
     ns["time_loop_seconds"] = _time.perf_counter() - t_loop
     ns["newton_iterations"] = total_newton
     ns["solver_events"] = events_seen
