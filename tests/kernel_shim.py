@@ -1,11 +1,13 @@
 """ctypes loader of ``vasp_amd/libfsi_kernel_shim.so`` (vasp_amd/csrc/fsi_kernel_shim.hip) and the host-side reference builders
 of the kernel tests (tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py, tests/test_gpu_product_kernels.py,
-tests/test_gpu_coarse_kernels.py).
+tests/test_gpu_coarse_kernels.py, tests/test_gpu_bcr_kernels.py).
 
 The shim runs ONE ``fsi::launch_*`` call of libvaspfsi.so on host arrays; the builders restate, in numpy, what the library's
 host code hands those kernels: the LDS tiles of a graph (fsi_capi.hip, node tiles and Schur tiles), the FP16 records of
 k_pack_h1 / k_pack_h3 / k_pack_sb, the monolithic matrix's column layout, padded FP32 copy and d-row pair form, and the P2 -> P1
-hierarchy of the two coarse levels with the contracts of their kernels.  The builders are tested on the CPU (tests/test_kernel_references.py), so that a failure
+hierarchy of the two coarse levels with the contracts of their kernels, and the exact coarse solve by block cyclic reduction
+(fsi_bcr.hip: the reduction restated on a block-tridiagonal matrix, its blocked Gauss-Jordan inverse, synthetic tube graphs whose
+breadth-first levels are known).  The builders are tested on the CPU (tests/test_kernel_references.py), so that a failure
 of a GPU test is one of the kernel, not of its reference."""
 from __future__ import annotations
 
@@ -40,6 +42,8 @@ _SIGS = {
     "shim_sbmg_prolong": "llpppppppl", "shim_sb_binv": "llppplpp", "shim_sb_dinv": "llppplp", "shim_dinv_f32": "lppplp",
     "shim_diag_inverse": "lpplp", "shim_block_scale_d": "lpp", "shim_solid_cycle_init": "llpppfpppp", "shim_gather3_f32": "llppp",
     "shim_scatter3_f32": "llppp",
+    "shim_bcr_invert": "lpplplp", "shim_bcr_gemm": "lppplplp", "shim_bcr_apply": "ilpplppl", "shim_bcr_fill": "lpppdpl",
+    "shim_bcr_gather": "lpppl", "shim_bcr_scatter": "lpplp", "shim_bcr_run": "lppipdipppppppplpl",
 }
 LAUNCH_REFUSED = 2           # fsi_kernels.hpp: a launch function refused its arguments and launched nothing
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "d": C.c_double, "s": C.c_char_p}
@@ -749,3 +753,296 @@ def sbmg_restrict(nc, chptr, child, chw, snode, rowscale, flag, cflag, r4):
     np.add.at(S, i, np.abs(t))
     L = np.diff(chptr)[:, None].astype(np.float64)
     return s, (L + 10) * U32 * S
+
+
+# ---- the exact coarse solve by block cyclic reduction (fsi_bcr.hip) ----------------------------------------------------------
+BCR_PANEL = 32
+BCR_RUN_STATS = ("usable", "blocks", "max_block", "levels", "bytes32", "bytes64", "setup_flops", "launches", "planned", "tasks",
+                 "n32", "n64")
+
+
+def bcr_reference(A, off, operators=False):
+    """Block cyclic reduction of a block-tridiagonal matrix (blocks off[k]:off[k+1]) exactly as fsi_bcr.hip schedules it:
+    operators in FP32, vectors FP64.  Returns solve(rhs); with operators=True also the FP64 operators in the planner's task
+    order: per reduction level its forward tasks [G_jl | G_jr], then its backward tasks [D_e^-1 | H_ea | H_ec], last the top
+    D_t^-1, each as (level, kind 0 forward / 1 backward / 2 top, block, W, input segments [("b" | "x", block)])."""
+    K = len(off) - 1
+    blk = lambda i, j: A[off[i]:off[i + 1], off[j]:off[j + 1]].copy()
+    D = {k: blk(k, k) for k in range(K)}
+    L = {k: (blk(k, k - 1) if k > 0 else None) for k in range(K)}
+    U = {k: (blk(k, k + 1) if k + 1 < K else None) for k in range(K)}
+    active, levels, ops = list(range(K)), [], []
+    while len(active) > 1:
+        na = len(active)
+        Dinv = {active[i]: np.linalg.inv(D[active[i]]) for i in range(1, na, 2)}
+        fwd, bwd, newL, newU = [], [], {}, {}
+        for i in range(1, na, 2):
+            e, a, c = active[i], active[i - 1], (active[i + 1] if i + 1 < na else None)
+            W, segs = [Dinv[e], -Dinv[e] @ L[e]], [("b", e), ("x", a)]
+            if c is not None:
+                W.append(-Dinv[e] @ U[e]); segs.append(("x", c))
+            bwd.append((e, np.hstack(W), segs))
+        for i in range(0, na, 2):
+            j, l, r = active[i], (active[i - 1] if i > 0 else None), (active[i + 1] if i + 1 < na else None)
+            W, segs = [], []
+            newL[j] = newU[j] = None
+            if l is not None:
+                Gl = -L[j] @ Dinv[l]; W.append(Gl); segs.append(("b", l)); D[j] = D[j] + Gl @ U[l]
+                if i >= 2:
+                    newL[j] = Gl @ L[l]
+            if r is not None:
+                Gr = -U[j] @ Dinv[r]; W.append(Gr); segs.append(("b", r)); D[j] = D[j] + Gr @ L[r]
+                if i + 2 < na:
+                    newU[j] = Gr @ U[r]
+            if W:
+                fwd.append((j, np.hstack(W), segs))
+        for i in range(0, na, 2):
+            L[active[i]], U[active[i]] = newL[active[i]], newU[active[i]]
+        lv = len(levels)
+        ops += [(lv, 0, j, W, sg) for j, W, sg in fwd] + [(lv, 1, e, W, sg) for e, W, sg in bwd]
+        levels.append(([(j, W.astype(np.float32), sg) for j, W, sg in fwd], [(e, W.astype(np.float32), sg) for e, W, sg in bwd]))
+        active = active[0::2]
+    Dt = np.linalg.inv(D[active[0]])
+    ops.append((len(levels), 2, active[0], Dt, [("b", active[0])]))
+    top = (active[0], Dt.astype(np.float32))
+
+    def solve(rhs):
+        b, x = rhs.astype(np.float64).copy(), np.zeros(len(rhs))
+        seg = lambda v, k: v[off[k]:off[k + 1]]
+        for fwd, _ in levels:
+            upd = {j: seg(b, j) + W.astype(np.float64) @ np.concatenate([seg(b, k) for _, k in segs]) for j, W, segs in fwd}
+            for j, v in upd.items():
+                b[off[j]:off[j + 1]] = v
+        x[off[top[0]]:off[top[0] + 1]] = top[1].astype(np.float64) @ seg(b, top[0])
+        for _, bwd in reversed(levels):
+            for e, W, segs in bwd:
+                x[off[e]:off[e + 1]] = W.astype(np.float64) @ np.concatenate([seg(b if s == "b" else x, k) for s, k in segs])
+        return x
+    return (solve, ops) if operators else solve
+
+
+def bcr_tasks_of(ops, off):
+    """the task table of shim_bcr_run ([n][16]) and an FP32 arena for operators in bcr_reference's order (rows padded to a
+    multiple of 4 columns, as bcr_plan lays them out)"""
+    tasks, chunks, a32 = [], [], 0
+    for lv, kind, blk, W, segs in ops:
+        rows, cols = W.shape
+        ldw = (cols + 3) & ~3
+        t = [a32, rows, ldw, off[blk], len(segs)] + [0] * 9 + [lv, kind]
+        for k, (src, b) in enumerate(segs):
+            t[5 + 3 * k:8 + 3 * k] = [off[b], off[b + 1] - off[b], 1 if src == "x" else 0]
+        Wp = np.zeros((rows, ldw), dtype=np.float32)
+        Wp[:, :cols] = W
+        chunks.append(Wp.ravel())
+        a32 += rows * ldw
+        tasks.append(t)
+    return np.asarray(tasks, dtype=np.int64), np.concatenate(chunks)
+
+
+def bcr_task_operator(task, arena32):
+    """the FP32 operator W [rows][columns of its segments] of a task row of shim_bcr_run (padding columns dropped)"""
+    w, rows, ldw, nseg = int(task[0]), int(task[1]), int(task[2]), int(task[4])
+    cols = sum(int(task[6 + 3 * k]) for k in range(nseg))
+    return np.asarray(arena32[w:w + rows * ldw], dtype=np.float32).reshape(rows, ldw)[:, :cols]
+
+
+def bcr_task_apply(tasks, arena32, rhs, absolute=False):
+    """The solve of fsi_bcr.hip (forward levels, top, backward levels in reverse) with the given FP32 operators and FP64
+    vectors, in the solve's own order.  absolute: with |W| and |rhs| - every term's magnitude carried through, the scale of the
+    round-off bound of the kernels' sums."""
+    tasks = np.asarray(tasks).reshape(-1, 16)
+    b, x = np.array(rhs, dtype=np.float64), np.zeros(len(rhs))
+    if absolute:
+        b = np.abs(b)
+    nlev = int(tasks[:, 14].max())
+
+    def run(t):
+        W = bcr_task_operator(t, arena32).astype(np.float64)
+        W = np.abs(W) if absolute else W
+        v = np.concatenate([(x if t[7 + 3 * k] else b)[t[5 + 3 * k]:t[5 + 3 * k] + t[6 + 3 * k]] for k in range(int(t[4]))])
+        return W @ v
+    for lv in range(nlev):
+        for t in tasks[(tasks[:, 14] == lv) & (tasks[:, 15] == 0)]:
+            b[t[3]:t[3] + t[1]] += run(t)
+    for t in tasks[tasks[:, 15] == 2]:
+        x[t[3]:t[3] + t[1]] = run(t)
+    for lv in reversed(range(nlev)):
+        for t in tasks[(tasks[:, 14] == lv) & (tasks[:, 15] == 1)]:
+            x[t[3]:t[3] + t[1]] = run(t)
+    return x
+
+
+def gj_inverse(A):
+    """The blocked Gauss-Jordan of k_bcr_panel / k_bcr_gemm without pivoting, in FP64: per panel of 32 columns the pivot block's
+    inverse P, R = P A[panel rows, :] (P itself on the panel's columns), the column panel C (its own rows zeroed), then
+    A[panel rows] = R, A[:, panel] = 0 outside the panel rows, A -= C R.  Returns (inverse, bad): bad when a pivot of the
+    in-panel Gauss-Jordan is not finite or |pivot| <= 1e-290 (where the kernel raises its flag and divides by 1)."""
+    A = np.array(A, dtype=np.float64)
+    m = len(A)
+    bad = False
+    for k0 in range(0, m, BCR_PANEL):
+        nb = min(BCR_PANEL, m - k0)
+        Ps, Q = A[k0:k0 + nb, k0:k0 + nb].copy(), np.eye(nb)
+        for p in range(nb):
+            piv = Ps[p, p]
+            b = not (abs(piv) > 1e-290) or not np.isfinite(piv)
+            bad |= b
+            ip = 1.0 if b else 1.0 / piv
+            Ps[p, p + 1:] *= ip
+            Q[p] *= ip
+            for r in range(nb):
+                if r != p:
+                    f = Ps[r, p]
+                    Ps[r, p + 1:] -= f * Ps[p, p + 1:]
+                    Q[r] -= f * Q[p]
+        R = Q @ A[k0:k0 + nb]
+        R[:, k0:k0 + nb] = Q
+        C = A[:, k0:k0 + nb].copy()
+        C[k0:k0 + nb] = 0.0
+        A[:, k0:k0 + nb] = 0.0
+        A[k0:k0 + nb] = R
+        A -= C @ R
+    return A, bad
+
+
+def bcr_inverse_layout(ms, ld32s=None):
+    """Arenas of a batch of in-place inverses as bcr_plan lays them out: per block m x m values, then its panel scratch cb [m][32]
+    and rb [32][m]; FP32 copies at o32 with row length ld32 (>= m; a multiple of 4 by default, -1: no copy).  Returns (desc
+    [n][6] int64 for shim_bcr_invert, n64, n32, offsets of the blocks)."""
+    desc, a64, a32, offs = [], 0, 0, []
+    for k, m in enumerate(ms):
+        ld32 = ((m + 3) & ~3) if ld32s is None else ld32s[k]
+        a = a64; a64 += m * m
+        cb = a64; a64 += m * BCR_PANEL
+        rb = a64; a64 += m * BCR_PANEL
+        o32 = -1
+        if ld32 >= 0:
+            o32 = a32; a32 += m * ld32; a32 = (a32 + 3) & ~3
+        desc.append([a, o32, cb, rb, m, ld32])
+        offs.append(a)
+    return np.asarray(desc, dtype=np.int64).reshape(-1, 6), a64, a32, offs
+
+
+def gemm_tiles(M, N):
+    """bcr_gemm_tiles: the (ti, tj) of the 64 x 64 tiles of an M x N product, row-tile major"""
+    return [(ti, tj) for ti in range((M + 63) // 64) for tj in range((N + 63) // 64)]
+
+
+def task_tiles(rows):
+    """bcr_task_tiles: first row of every 16-row tile of a solve task, and the rows k_bcr_apply's four waves write from it"""
+    return [(r0, [r0 + 4 * w + k for w in range(4) for k in range(4) if r0 + 4 * w + k < rows]) for r0 in range(0, rows, 16)]
+
+
+def tube_graph(tubes, rng, shuffle=True):
+    """Synthetic walls: every tube a list of ring sizes (nodes), each node linked to itself and to every node of its own ring and
+    of the rings beside it.  Ids are shuffled, then in each tube the smallest id is moved into ring 0, so that the planner's
+    breadth-first search starts at that end: from a root in ring 0 of R rings the farthest set is ring R - 1 alone when R >= 3,
+    or R == 2 with a single-node ring 0, or R == 1 with a single node (asserted), and the levels are the rings counted from the
+    far end: level = R - 1 - ring, shared by the tubes.  Returns dict(nc, cptr, ccol, level, pos, tube, ring, m) with pos the
+    planner's numbering (by level, ascending id inside one) and m the unknowns per level."""
+    ids, ring_of, tube_of, lev = [], [], [], []
+    nid = 0
+    for t, rings in enumerate(tubes):
+        R = len(rings)
+        assert R >= 3 or rings[0] == 1, "ring 0 must be a single node below three rings"
+        for k, n in enumerate(rings):
+            ids.append(np.arange(nid, nid + n)); nid += n
+            ring_of += [k] * n; tube_of += [t] * n; lev += [R - 1 - k] * n
+    nc = nid
+    ring_of, tube_of, lev = np.asarray(ring_of), np.asarray(tube_of), np.asarray(lev)
+    perm = rng.permutation(nc) if shuffle else np.arange(nc)          # node id of generator slot s
+    for t in range(len(tubes)):
+        slots = np.flatnonzero(tube_of == t)
+        smin = slots[np.argmin(perm[slots])]
+        s0 = slots[ring_of[slots] == 0][0]
+        perm[smin], perm[s0] = perm[s0], perm[smin]
+    rows, cols = [], []
+    start = 0
+    for t, rings in enumerate(tubes):
+        offs = np.concatenate([[0], np.cumsum(rings)]) + start
+        for k in range(len(rings)):
+            mine = np.arange(offs[k], offs[k + 1])
+            nb = np.arange(offs[max(k - 1, 0)], offs[min(k + 2, len(rings))])
+            rows.append(np.repeat(mine, len(nb))); cols.append(np.tile(nb, len(mine)))
+        start = offs[-1]
+    r, c = perm[np.concatenate(rows)], perm[np.concatenate(cols)]
+    o = np.lexsort((c, r))
+    r, c = r[o], c[o]
+    cptr = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=nc))]).astype(np.int64)
+    level = np.empty(nc, dtype=np.int32)
+    level[perm] = lev
+    ring = np.empty(nc, dtype=np.int64); ring[perm] = ring_of
+    tube = np.empty(nc, dtype=np.int64); tube[perm] = tube_of
+    order = np.lexsort((np.arange(nc), level))
+    pos = np.empty(nc, dtype=np.int32)
+    pos[order] = np.arange(nc)
+    return dict(nc=nc, cptr=cptr, ccol=c.astype(np.int32), level=level, pos=pos, tube=tube, ring=ring,
+                m=3 * np.bincount(level).astype(np.int64))
+
+
+def tube_values(g, kappa, rng, skew=0.3):
+    """FP32 3x3 blocks [nnz][9] of a non-symmetric operator on a tube graph whose condition number is about kappa: a block
+    graph Laplacian with random definite edge blocks (symmetric part), a skew-symmetric part of relative size `skew` on the
+    edges, and sigma I on the diagonal with sigma = lambda_max / kappa.  The symmetric part stays definite, so elimination without
+    pivoting does not break down."""
+    nc, cptr, ccol = g["nc"], g["cptr"], g["ccol"]
+    row = np.repeat(np.arange(nc), np.diff(cptr))
+    nnz = len(ccol)
+    lo, hi = np.minimum(row, ccol).astype(np.int64), np.maximum(row, ccol).astype(np.int64)
+    key = lo * nc + hi
+    uk, inv = np.unique(key, return_inverse=True)
+    B = rng.standard_normal((len(uk), 3, 3))
+    Me = np.einsum("eij,ekj->eik", B, B) / 3 + 0.3 * np.eye(3)           # definite edge blocks, one per unordered pair
+    Ke = skew * rng.standard_normal((len(uk), 3, 3))
+    off = row != ccol
+    vals = np.zeros((nnz, 3, 3))
+    up = off & (row < ccol)
+    vals[off] = -Me[inv[off]]
+    vals[up] += Ke[inv[up]]
+    vals[off & ~up] -= np.transpose(Ke[inv[off & ~up]], (0, 2, 1))
+    diag = np.flatnonzero(~off)
+    dsum = np.zeros((nc, 3, 3))
+    np.add.at(dsum, row[off], Me[inv[off]])
+    lmax = 2.0 * np.abs(dsum).sum(axis=2).max() if nc > 1 else 1.0
+    vals[diag] = dsum[row[diag]] + (lmax / kappa) * np.eye(3)
+    return vals.reshape(nnz, 9).astype(np.float32)
+
+
+def tube_dense(g, cvals, shift=0.0):
+    """the dense FP64 operator of FP32 block values in the solve's own (planner's) order, A + shift blockdiag(A) formed as k_bcr_fill
+    forms it: (1 + shift) * double(v) on a node's own block"""
+    nc, cptr, ccol, pos = g["nc"], g["cptr"], g["ccol"], g["pos"].astype(np.int64)
+    row = np.repeat(np.arange(nc), np.diff(cptr))
+    v = np.asarray(cvals, dtype=np.float32).reshape(-1, 3, 3).astype(np.float64)
+    f = np.where(row == ccol, 1.0 + shift, 1.0)
+    A = np.zeros((3 * nc, 3 * nc))
+    for a in range(3):
+        for b in range(3):
+            A[3 * pos[row] + a, 3 * pos[ccol] + b] = f * v[:, a, b]
+    return A
+
+
+def bcr_run(g, value_sets, shift, rhs=None, rc4=None, arena=False):
+    """shim_bcr_run on a tube graph: returns dict(stats, ready, pos, x [sets][nrhs][3 nc], xc4 [sets][nrhs][4 nc], arena32,
+    tasks [ntasks][16]); x / xc4 start as NaN sentinels (left where a refresh was not ready)"""
+    nc, cptr, ccol = g["nc"], g["cptr"], g["ccol"]
+    sets = np.ascontiguousarray(np.asarray(value_sets, dtype=np.float32).reshape(len(value_sets), -1))
+    nrhs = len(rhs) if rhs is not None else (0 if rc4 is None else len(rc4))
+    rhs = None if rhs is None else np.ascontiguousarray(np.asarray(rhs, dtype=np.float64))
+    rc4 = None if rc4 is None else np.ascontiguousarray(np.asarray(rc4, dtype=np.float32))
+    stats = np.zeros(len(BCR_RUN_STATS), dtype=np.int64)
+    ready = np.full(len(sets), -1, dtype=np.int32)
+    pos = np.full(nc, -1, dtype=np.int32)
+    x = np.full((len(sets), nrhs, 3 * nc), np.nan)
+    xc4 = np.full((len(sets), nrhs, 4 * nc), np.nan, dtype=np.float32)
+    cap32 = cap_t = 0
+    a32 = tk = None
+    if arena:                                   # a plan-only call first for the sizes
+        call("shim_bcr_run", nc, cptr, ccol, 0, sets, shift, 0, None, None, stats, None, None, None, None, None, 0, None, 0)
+        cap32, cap_t = int(stats[10]), int(stats[9])
+        a32 = np.full(max(cap32, 1), np.nan, dtype=np.float32)
+        tk = np.full((max(cap_t, 1), 16), -7, dtype=np.int64)
+    call("shim_bcr_run", nc, cptr, ccol, len(sets), sets, shift, nrhs, rhs, rc4, stats, ready, pos, x if rhs is not None else None,
+         xc4 if rc4 is not None else None, a32, cap32, tk, cap_t)
+    return dict(stats=dict(zip(BCR_RUN_STATS, (int(v) for v in stats))), ready=ready, pos=pos, x=x, xc4=xc4, arena32=a32,
+                tasks=None if tk is None else tk[:cap_t])

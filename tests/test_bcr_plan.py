@@ -3,7 +3,7 @@
 The level is solved by block cyclic reduction over breadth-first levels of the solid vertices; what the planner must deliver is
 (i) a numbering in which the operator is block tridiagonal - every edge of the graph joins equal or neighbouring levels - with
 blocks of one cross-section of the wall, and (ii) sizes that decide whether the method is used at all.  The arithmetic of the
-reduction itself is restated in numpy on that numbering (``bcr_reference``) and solved against a dense factorisation; the HIP
+reduction itself is restated in numpy on that numbering (``kernel_shim.bcr_reference``) and solved against a dense factorisation; the HIP
 kernels are held to the same dense solve on the GPU (tests/test_gpu_parity.py::test_exact_coarse_solve_*)."""
 import ctypes
 
@@ -12,6 +12,7 @@ import pytest
 import scipy.sparse as sp
 
 from vasp_amd import capi
+from kernel_shim import bcr_reference
 
 
 def wall_graph(tets):
@@ -39,60 +40,6 @@ def plan(nc, cptr, ccol):
     assert rc == 0
     keys = ("usable", "blocks", "max_block", "levels", "bytes32", "bytes64", "setup_flops", "launches")
     return dict(zip(keys, (int(v) for v in stats))), pos, level
-
-
-def bcr_reference(A, off):
-    """Block cyclic reduction of a block-tridiagonal matrix (blocks off[k]:off[k+1]) exactly as fsi_bcr.hip schedules it:
-    operators in FP32, vectors FP64.  Returns solve(rhs)."""
-    K = len(off) - 1
-    blk = lambda i, j: A[off[i]:off[i + 1], off[j]:off[j + 1]].copy()
-    D = {k: blk(k, k) for k in range(K)}
-    L = {k: (blk(k, k - 1) if k > 0 else None) for k in range(K)}
-    U = {k: (blk(k, k + 1) if k + 1 < K else None) for k in range(K)}
-    active, levels = list(range(K)), []
-    while len(active) > 1:
-        na = len(active)
-        Dinv = {active[i]: np.linalg.inv(D[active[i]]) for i in range(1, na, 2)}
-        fwd, bwd, newL, newU = [], [], {}, {}
-        for i in range(1, na, 2):
-            e, a, c = active[i], active[i - 1], (active[i + 1] if i + 1 < na else None)
-            W, segs = [Dinv[e], -Dinv[e] @ L[e]], [("b", e), ("x", a)]
-            if c is not None:
-                W.append(-Dinv[e] @ U[e]); segs.append(("x", c))
-            bwd.append((e, np.hstack(W).astype(np.float32), segs))
-        for i in range(0, na, 2):
-            j, l, r = active[i], (active[i - 1] if i > 0 else None), (active[i + 1] if i + 1 < na else None)
-            W, segs = [], []
-            newL[j] = newU[j] = None
-            if l is not None:
-                Gl = -L[j] @ Dinv[l]; W.append(Gl); segs.append(("b", l)); D[j] = D[j] + Gl @ U[l]
-                if i >= 2:
-                    newL[j] = Gl @ L[l]
-            if r is not None:
-                Gr = -U[j] @ Dinv[r]; W.append(Gr); segs.append(("b", r)); D[j] = D[j] + Gr @ L[r]
-                if i + 2 < na:
-                    newU[j] = Gr @ U[r]
-            if W:
-                fwd.append((j, np.hstack(W).astype(np.float32), segs))
-        for i in range(0, na, 2):
-            L[active[i]], U[active[i]] = newL[active[i]], newU[active[i]]
-        levels.append((fwd, bwd))
-        active = active[0::2]
-    top = (active[0], np.linalg.inv(D[active[0]]).astype(np.float32))
-
-    def solve(rhs):
-        b, x = rhs.astype(np.float64).copy(), np.zeros(len(rhs))
-        seg = lambda v, k: v[off[k]:off[k + 1]]
-        for fwd, _ in levels:
-            upd = {j: seg(b, j) + W.astype(np.float64) @ np.concatenate([seg(b, k) for _, k in segs]) for j, W, segs in fwd}
-            for j, v in upd.items():
-                b[off[j]:off[j + 1]] = v
-        x[off[top[0]]:off[top[0] + 1]] = top[1].astype(np.float64) @ seg(b, top[0])
-        for _, bwd in reversed(levels):
-            for e, W, segs in bwd:
-                x[off[e]:off[e + 1]] = W.astype(np.float64) @ np.concatenate([seg(b if s == "b" else x, k) for s, k in segs])
-        return x
-    return solve
 
 
 @pytest.mark.parametrize("tets", [6000, 48000])

@@ -1,6 +1,6 @@
 """CPU self-tests of the host-side references the kernel tests build on (tests/kernel_shim.py), so that a failure of
-tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py, tests/test_gpu_product_kernels.py or
-tests/test_gpu_coarse_kernels.py is one of a kernel, not of its reference."""
+tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py, tests/test_gpu_product_kernels.py,
+tests/test_gpu_coarse_kernels.py or tests/test_gpu_bcr_kernels.py is one of a kernel, not of its reference."""
 import numpy as np
 import pytest
 
@@ -471,3 +471,99 @@ def test_sbmg_rap_reference_is_the_block_galerkin_product():
     v2[dg, 1, 1] = 5.0
     f = ks.sbmg_flags(nS, sb_ptr, sb_col, v2.ravel())
     assert f[i] == 1 and f.sum() == 1
+
+
+# ---- the exact coarse solve by block cyclic reduction (kernel_shim.gj_inverse, tube_graph, bcr_reference) -------------------
+def _dominant(m, rng):
+    """a non-symmetric, diagonally dominant m x m block"""
+    A = rng.standard_normal((m, m))
+    return A + np.diag(np.abs(A).sum(axis=1) + 1.0)
+
+
+@pytest.mark.parametrize("m", [1, 2, 3, 31, 32, 33, 63, 64, 65, 97])
+def test_blocked_gauss_jordan_restatement_is_the_inverse(m):
+    rng = np.random.default_rng(m)
+    A = _dominant(m, rng)
+    X, bad = ks.gj_inverse(A)
+    ref = np.linalg.inv(A)
+    assert not bad
+    ai, aa = np.abs(ref), np.abs(A)
+    ks.check(X, ref, 8 * (m + 4) * np.finfo(float).eps * (ai @ aa @ ai), f"gj_inverse m={m}")
+
+
+@pytest.mark.parametrize("k", [0, 31, 32, 33])
+def test_blocked_gauss_jordan_restatement_flags_a_zero_pivot(k):
+    A = _dominant(40, np.random.default_rng(k))
+    A[k, k] = 0.0
+    A[k, :] = 0.0
+    assert ks.gj_inverse(A)[1]
+    B = np.eye(3)
+    B[1, 1] = 1.0
+    B[0, 1], B[1, 0] = 1.0, 1.0               # the second pivot vanishes only after the first elimination: 1 - 1 * 1
+    assert ks.gj_inverse(B)[1]
+
+
+def test_bcr_tile_builders_cover_every_output_once():
+    for M in (1, 15, 16, 17, 63, 64, 65, 130):
+        for N in (1, 16, 17, 64, 65, 130):
+            hit = np.zeros((M, N), dtype=np.int64)
+            for ti, tj in ks.gemm_tiles(M, N):                      # a workgroup: four waves, 32 x 32 each
+                for w in range(4):
+                    i0, j0 = 64 * ti + 32 * (w >> 1), 64 * tj + 32 * (w & 1)
+                    hit[i0:min(i0 + 32, M), j0:min(j0 + 32, N)] += 1
+            assert (hit == 1).all(), (M, N)
+    for rows in (1, 2, 3, 4, 5, 15, 16, 17, 65, 433):
+        got = sorted(r for _, rs in ks.task_tiles(rows) for r in rs)
+        assert got == list(range(rows)), rows
+    desc, n64, n32, _ = ks.bcr_inverse_layout([1, 33, 2, 65], ld32s=[4, 36, -1, 72])
+    used64, used32 = np.zeros(n64, dtype=np.int64), np.zeros(n32, dtype=np.int64)
+    for a, o32, cb, rb, m, ld32 in desc:
+        for first, count in ((a, m * m), (cb, 32 * m), (rb, 32 * m)):
+            used64[first:first + count] += 1
+        if o32 >= 0:
+            used32[o32:o32 + m * ld32] += 1
+    assert (used64 == 1).all() and used32.max() == 1
+
+
+@pytest.mark.parametrize("tubes", [[[1]], [[1, 10]], [[11, 1, 10]], [[10, 11, 22, 72, 144, 72, 22, 11, 1]],
+                                   [[1, 10, 11], [22, 11, 10, 1, 10, 33]], [[1] * 17], [[30, 10, 1, 22, 11, 72, 144, 1]]])
+def test_tube_graph_levels_are_the_planners(tubes):
+    """the breadth-first levels and the numbering fsi_bcr_plan_graph derives are the rings the generator claims"""
+    g = ks.tube_graph(tubes, np.random.default_rng(len(tubes[0])))
+    lib = capi.load_library()
+    stats = np.zeros(8, dtype=np.int64)
+    pos, level = np.empty(g["nc"], dtype=np.int32), np.empty(g["nc"], dtype=np.int32)
+    assert lib.fsi_bcr_plan_graph(g["nc"], capi._ptr(g["cptr"]), capi._ptr(g["ccol"]), capi._ptr(stats), capi._ptr(pos),
+                                  capi._ptr(level)) == 0
+    np.testing.assert_array_equal(level, g["level"])
+    np.testing.assert_array_equal(pos, g["pos"])
+    assert stats[0] == 1 and stats[1] == len(g["m"]) and stats[2] == g["m"].max()
+    assert not np.array_equal(g["pos"], np.arange(g["nc"])) or g["nc"] <= 2
+    want = np.zeros(max(len(t) for t in tubes), dtype=np.int64)
+    for t in tubes:
+        want[:len(t)] += 3 * np.asarray(t[::-1])
+    np.testing.assert_array_equal(g["m"], want)
+
+
+def test_planner_takes_rings_of_666_nodes_and_declines_667():
+    lib = capi.load_library()
+    for n, usable in ((666, 1), (667, 0)):
+        g = ks.tube_graph([[n, 1, n]], np.random.default_rng(n))
+        stats = np.zeros(8, dtype=np.int64)
+        lib.fsi_bcr_plan_graph(g["nc"], capi._ptr(g["cptr"]), capi._ptr(g["ccol"]), capi._ptr(stats), None, None)
+        assert stats[0] == usable and stats[2] == 3 * n
+
+
+def test_task_table_restatement_is_the_reference_solve():
+    """bcr_task_apply on the reference's own FP32 operators, laid out as a task table, is bcr_reference's solve"""
+    rng = np.random.default_rng(3)
+    g = ks.tube_graph([[1, 10, 11], [22, 11, 10, 1, 10]], rng)
+    A = ks.tube_dense(g, ks.tube_values(g, 1e2, rng), 2e-4)
+    off = np.concatenate([[0], np.cumsum(g["m"])])
+    solve, ops = ks.bcr_reference(A, off, operators=True)
+    tasks, a32 = ks.bcr_tasks_of([(lv, k, b, W.astype(np.float32), sg) for lv, k, b, W, sg in ops], off)
+    rhs = rng.standard_normal(len(A))
+    x = ks.bcr_task_apply(tasks, a32, rhs)
+    np.testing.assert_allclose(x, solve(rhs), rtol=0, atol=1e-12 * np.abs(x).max())
+    assert np.linalg.norm(A @ x - rhs) <= 1e-5 * np.linalg.norm(rhs)
+    assert (ks.bcr_task_apply(tasks, a32, rhs, absolute=True) >= np.abs(x)).all()

@@ -13,8 +13,9 @@
 // Operators are stored in FP32 (5 K m^2 values: 71 MB at 140 k tets, 0.56 GB at 1.12 M - the solve streams them once),
 // vectors and every accumulation are FP64; the set-up (dense inverses by a blocked Gauss-Jordan, products on the FP64 matrix
 // pipe: v_mfma_f64_16x16x4_f64) is FP64 throughout.  No pivoting across blocks: the level is the Galerkin operator of an
-// elasticity + mass matrix whose Schur complements stay definite; a non-finite or vanishing pivot is reported and the cycle
-// falls back to its sweeps for that Jacobian.
+// elasticity + mass matrix whose Schur complements stay definite; a non-finite or vanishing pivot, or an operator that is not
+// finite as it is stored in FP32 (k_bcr_copy32, k_bcr_gemm), is reported and the cycle falls back to its sweeps for that Jacobian.
+// Descriptors: fsi_bcr.hpp; launch functions (also run one at a time by the test shim): fsi_kernels.hpp.
 //
 // Built once (bcr_plan, host: BFS levels, reduction schedule, descriptor tables), refreshed with the Jacobian (bcr_refresh),
 // applied inside precondition_block (bcr_solve).  The reference has no counterpart: its linear solver is MUMPS
@@ -24,54 +25,6 @@
 #include <queue>
 
 namespace fsi {
-
-struct BcrSeg { int32_t off, len, src; };                    // input segment of a solve task: src 0 = b, 1 = x
-struct BcrTask {                                             // out[rows] (+)= W[rows][ldw] . concat(segments)
-  int64_t w;                                                 // offset of W in the FP32 arena
-  int32_t rows, ldw, out, nseg;
-  BcrSeg seg[3];
-};
-struct BcrTile { int32_t task, row0; };                      // 16 rows of a task: one workgroup
-struct BcrGemm {                                             // C = beta C + alpha (A1 B1 + A2 B2), optional FP32 copy
-  int64_t a1, b1, a2, b2, c, o32;
-  int32_t M, N, K1, K2, lda1, ldb1, lda2, ldb2, ldc, ld32;
-  double alpha, beta;
-};
-struct BcrGemmTile { int32_t task, ti, tj; };                // 64 x 64 tile of C: one workgroup
-struct BcrInv {                                              // in-place inverse of an m x m block (+ FP32 copy)
-  int64_t a, o32, cb, rb;                                    // cb [m][32], rb [32][m]: column / row panel scratch of the blocked Gauss-Jordan
-  int32_t m, ld, ld32;
-};
-constexpr int BCR_PANEL = 32;
-
-struct BcrRange { int64_t first = 0, count = 0; };
-struct BcrLevelHost {
-  BcrRange inv, invupd, gemm1, gemm2, fwd, bwd;            // invupd: tiles of the rank-32 updates A += -Cb Rb of the inverses
-  int inv_maxm = 0, fwd_maxld = 0, bwd_maxld = 0;
-};
-
-struct BcrData {
-  bool planned = false, ready = false;
-  int64_t nc = 0, n = 0, K = 0;
-  int max_block = 0;
-  DevBuf<int32_t> pos;                                       // coarse node -> position in BFS-level order
-  DevBuf<int64_t> fill_dst;                                  // per sparse 3x3 block: offset of its (0,0) entry in the FP64 arena
-  DevBuf<int32_t> fill_ld;
-  int64_t nfill = 0, level0_doubles = 0;
-  DevBuf<double> arena64, b, x;
-  DevBuf<float> arena32;
-  DevBuf<BcrTask> tasks;
-  DevBuf<BcrTile> tiles;
-  DevBuf<BcrGemm> gemms;
-  DevBuf<BcrGemmTile> gtiles;
-  DevBuf<BcrInv> invs;
-  DevBuf<int32_t> flag;                                      // device: bit 0 = a pivot vanished / was not finite
-  std::vector<BcrLevelHost> levels;
-  BcrRange top_inv, top_invupd, top_task;
-  int top_m = 0, top_ld = 0;
-  int64_t bytes32 = 0, bytes64 = 0, setup_flops = 0;
-  int launches_per_solve = 0;
-};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // kernels
@@ -187,9 +140,9 @@ __global__ __launch_bounds__(256) void k_bcr_copy32(const BcrInv* __restrict__ t
   bool bad = false;
   for (int idx = threadIdx.x; idx < T.m * T.m; idx += 256) {
     const int i = idx / T.m, j = idx - i * T.m;
-    const double v = A[(size_t)i * T.ld + j];
-    bad = bad || !isfinite(v);
-    O[(size_t)i * T.ld32 + j] = (float)v;
+    const float v = (float)A[(size_t)i * T.ld + j];
+    bad = bad || !isfinite(v);                     // the FP32 value that is stored: an FP64-finite inverse beyond FLT_MAX is inf
+    O[(size_t)i * T.ld32 + j] = v;
   }
   if (bad) atomicOr(flag, 1);
 }
@@ -201,7 +154,8 @@ __global__ __launch_bounds__(256) void k_bcr_copy32(const BcrInv* __restrict__ t
 // row / column is re-read by the 4 - 7 workgroups beside it.
 typedef double v4d __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void k_bcr_gemm(const BcrGemmTile* __restrict__ tiles, const BcrGemm* __restrict__ tasks,
-                                                  double* __restrict__ arena, float* __restrict__ arena32) {
+                                                  double* __restrict__ arena, float* __restrict__ arena32,
+                                                  int32_t* __restrict__ flag) {
   const BcrGemmTile tl = tiles[blockIdx.x];
   const BcrGemm G = tasks[tl.task];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -229,6 +183,7 @@ __global__ __launch_bounds__(256) void k_bcr_gemm(const BcrGemmTile* __restrict_
   }
   double* C = G.c >= 0 ? arena + G.c : nullptr;
   float* O = G.o32 >= 0 ? arena32 + G.o32 : nullptr;
+  bool bad = false;
   for (int a = 0; a < 2; ++a)
     for (int b = 0; b < 2; ++b)
       for (int r = 0; r < 4; ++r) {
@@ -239,8 +194,13 @@ __global__ __launch_bounds__(256) void k_bcr_gemm(const BcrGemmTile* __restrict_
           if (G.beta != 0.0) v += G.beta * C[(size_t)row * G.ldc + col];
           C[(size_t)row * G.ldc + col] = v;
         }
-        if (O) O[(size_t)row * G.ld32 + col] = (float)v;
+        if (O) {                                   // an operator of the solve: it must be finite as stored
+          const float f = (float)v;
+          bad = bad || !isfinite(f);
+          O[(size_t)row * G.ld32 + col] = f;
+        }
       }
+  if (bad) atomicOr(flag, 1);
 }
 
 // One launch of the solve: every workgroup takes 16 rows of one task, stages the task's input vector (<= three segments of b /
@@ -282,9 +242,41 @@ __global__ __launch_bounds__(256) void k_bcr_apply(const BcrTile* __restrict__ t
   }
 }
 
-namespace host {
-
 static int64_t grid1(int64_t n) { return std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 4096)); }
+
+void launch_bcr_fill(hipStream_t st, int64_t nblk, const float* cvals, const int64_t* dst, const int32_t* ld, double shift, double* arena64) {
+  hipLaunchKernelGGL(k_bcr_fill, dim3((unsigned)grid1(nblk)), dim3(256), 0, st, nblk, cvals, dst, ld, shift, arena64);
+}
+void launch_bcr_gather(hipStream_t st, int64_t nc, const int32_t* pos, const float* rc4, double* b) {
+  hipLaunchKernelGGL(k_bcr_gather, dim3((unsigned)grid1(nc)), dim3(256), 0, st, nc, pos, rc4, b);
+}
+void launch_bcr_scatter(hipStream_t st, int64_t nc, const int32_t* pos, const double* x, float* xc4) {
+  hipLaunchKernelGGL(k_bcr_scatter, dim3((unsigned)grid1(nc)), dim3(256), 0, st, nc, pos, x, xc4);
+}
+void launch_bcr_invert(hipStream_t st, const BcrInv* invs, int64_t ninv, const BcrGemmTile* upd, int64_t nupd, const BcrGemm* gemms,
+                       int maxm, double* arena64, float* arena32, int32_t* flag) {
+  if (ninv == 0) return;
+  for (int k0 = 0; k0 < maxm; k0 += BCR_PANEL) {
+    hipLaunchKernelGGL(k_bcr_panel, dim3((unsigned)ninv), dim3(256), 0, st, invs, k0, arena64, flag);
+    hipLaunchKernelGGL(k_bcr_gemm, dim3((unsigned)nupd), dim3(256), 0, st, upd, gemms, arena64, arena32, flag);
+  }
+  hipLaunchKernelGGL(k_bcr_copy32, dim3((unsigned)ninv), dim3(256), 0, st, invs, arena64, arena32, flag);
+}
+void launch_bcr_gemm(hipStream_t st, const BcrGemmTile* tiles, int64_t ntiles, const BcrGemm* gemms, double* arena64, float* arena32,
+                     int32_t* flag) {
+  if (ntiles == 0) return;
+  hipLaunchKernelGGL(k_bcr_gemm, dim3((unsigned)ntiles), dim3(256), 0, st, tiles, gemms, arena64, arena32, flag);
+}
+void launch_bcr_apply(hipStream_t st, bool forward, const BcrTile* tiles, int64_t ntiles, const BcrTask* tasks, int maxld, const float* W,
+                      double* b, double* x) {
+  if (ntiles == 0) return;
+  if (forward)
+    hipLaunchKernelGGL(k_bcr_apply<true>, dim3((unsigned)ntiles), dim3(256), (size_t)maxld * sizeof(double), st, tiles, tasks, W, b, x);
+  else
+    hipLaunchKernelGGL(k_bcr_apply<false>, dim3((unsigned)ntiles), dim3(256), (size_t)maxld * sizeof(double), st, tiles, tasks, W, b, x);
+}
+
+namespace host {
 
 void bcr_free(FsiCtx* ctx) {
   if (!ctx->bcr) return;
@@ -393,23 +385,20 @@ int bcr_plan(FsiCtx* ctx, int64_t nc, const std::vector<int64_t>& cptr, const st
   std::vector<BcrGemmTile> gtiles;
   std::vector<BcrInv> invs;
   auto add_gemm = [&](const BcrGemm& g) {
-    const int32_t id = (int32_t)gemms.size();
+    bcr_gemm_tiles(g, (int32_t)gemms.size(), gtiles);
     gemms.push_back(g);
-    for (int ti = 0; ti < (g.M + 63) / 64; ++ti)
-      for (int tj = 0; tj < (g.N + 63) / 64; ++tj) gtiles.push_back(BcrGemmTile{id, ti, tj});
     d->setup_flops += 2LL * g.M * g.N * ((int64_t)g.K1 + g.K2);
   };
   // an in-place inverse: its panel scratch and the tiles of its rank-32 updates A += -Cb Rb (one k_bcr_gemm launch per panel)
   auto add_inverse = [&](int64_t D, int64_t o32, int m, int ld32) {
     const int64_t cb = alloc64(m, BCR_PANEL), rb = alloc64(BCR_PANEL, m);
-    invs.push_back(BcrInv{D, o32, cb, rb, m, m, ld32});
-    add_gemm(BcrGemm{cb, rb, -1, -1, D, -1, m, m, BCR_PANEL, 0, BCR_PANEL, m, 0, 0, m, 0, -1.0, 1.0});
+    invs.push_back(bcr_inverse(D, o32, cb, rb, m, ld32));
+    add_gemm(bcr_inverse_update(invs.back()));
     d->setup_flops += 2LL * m * m * (int64_t)(m - BCR_PANEL);       // (add_gemm counted one panel; the update runs once per panel)
   };
   auto add_task = [&](const BcrTask& t) {
-    const int32_t id = (int32_t)tasks.size();
+    bcr_task_tiles(t, (int32_t)tasks.size(), tiles);
     tasks.push_back(t);
-    for (int r0 = 0; r0 < t.rows; r0 += 16) tiles.push_back(BcrTile{id, r0});
   };
   std::vector<int32_t> active(K);
   std::iota(active.begin(), active.end(), 0);
@@ -574,25 +563,17 @@ int bcr_refresh(FsiCtx* ctx) {
   // rounding - an exact A_c^-1 amplifies exactly those (a factor 1 - lambda~ / lambda of either sign), where the truncated Chebyshev
   // solve it replaces never inverted anything below lmax / kappa.  The shift is that floor as a Tikhonov term: modes above it are
   // solved exactly, modes below it are damped as before (FsiTuning.bcr_shift; 0 = the exact level).
-  hipLaunchKernelGGL(k_bcr_fill, dim3((unsigned)grid1(d->nfill)), dim3(256), 0, st, d->nfill, ctx->sbmg_cvals.p, d->fill_dst.p, d->fill_ld.p,
-                     ctx->tune.bcr_shift, d->arena64.p);
-  auto invert = [&](const BcrRange& r, const BcrRange& upd, int maxm) -> int {
-    if (r.count == 0) return FSI_OK;
-    for (int k0 = 0; k0 < maxm; k0 += BCR_PANEL) {
-      hipLaunchKernelGGL(k_bcr_panel, dim3((unsigned)r.count), dim3(256), 0, st, d->invs.p + r.first, k0, d->arena64.p, d->flag.p);
-      hipLaunchKernelGGL(k_bcr_gemm, dim3((unsigned)upd.count), dim3(256), 0, st, d->gtiles.p + upd.first, d->gemms.p, d->arena64.p, d->arena32.p);
-    }
-    hipLaunchKernelGGL(k_bcr_copy32, dim3((unsigned)r.count), dim3(256), 0, st, d->invs.p + r.first, d->arena64.p, d->arena32.p, d->flag.p);
-    return FSI_OK;
+  launch_bcr_fill(st, d->nfill, ctx->sbmg_cvals.p, d->fill_dst.p, d->fill_ld.p, ctx->tune.bcr_shift, d->arena64.p);
+  auto invert = [&](const BcrRange& r, const BcrRange& upd, int maxm) {
+    launch_bcr_invert(st, d->invs.p + r.first, r.count, d->gtiles.p + upd.first, upd.count, d->gemms.p, maxm, d->arena64.p, d->arena32.p,
+                      d->flag.p);
   };
   for (const BcrLevelHost& lv : d->levels) {
-    FSICHK(invert(lv.inv, lv.invupd, lv.inv_maxm));
-    if (lv.gemm1.count)
-      hipLaunchKernelGGL(k_bcr_gemm, dim3((unsigned)lv.gemm1.count), dim3(256), 0, st, d->gtiles.p + lv.gemm1.first, d->gemms.p, d->arena64.p, d->arena32.p);
-    if (lv.gemm2.count)
-      hipLaunchKernelGGL(k_bcr_gemm, dim3((unsigned)lv.gemm2.count), dim3(256), 0, st, d->gtiles.p + lv.gemm2.first, d->gemms.p, d->arena64.p, d->arena32.p);
+    invert(lv.inv, lv.invupd, lv.inv_maxm);
+    launch_bcr_gemm(st, d->gtiles.p + lv.gemm1.first, lv.gemm1.count, d->gemms.p, d->arena64.p, d->arena32.p, d->flag.p);
+    launch_bcr_gemm(st, d->gtiles.p + lv.gemm2.first, lv.gemm2.count, d->gemms.p, d->arena64.p, d->arena32.p, d->flag.p);
   }
-  FSICHK(invert(d->top_inv, d->top_invupd, d->top_m));
+  invert(d->top_inv, d->top_invupd, d->top_m);
   HIPCHK(hipGetLastError());
   int32_t flag[4] = {0, 0, 0, 0};
   HIPCHK(hipMemcpyAsync(flag, d->flag.p, sizeof flag, hipMemcpyDeviceToHost, st));
@@ -605,18 +586,13 @@ int bcr_refresh(FsiCtx* ctx) {
 // x_c = A_c^-1 r_c on the float4-padded coarse vectors of the solid cycle (rc4 in, xc4 out), queued on `st`.
 int bcr_solve(FsiCtx* ctx, const float* rc4, float* xc4, hipStream_t st) {
   BcrData* d = ctx->bcr;
-  if (rc4) hipLaunchKernelGGL(k_bcr_gather, dim3((unsigned)grid1(d->nc)), dim3(256), 0, st, d->nc, d->pos.p, rc4, d->b.p);
+  if (rc4) launch_bcr_gather(st, d->nc, d->pos.p, rc4, d->b.p);
   for (const BcrLevelHost& lv : d->levels)
-    if (lv.fwd.count)
-      hipLaunchKernelGGL(k_bcr_apply<true>, dim3((unsigned)lv.fwd.count), dim3(256), (size_t)lv.fwd_maxld * sizeof(double), st,
-                         d->tiles.p + lv.fwd.first, d->tasks.p, d->arena32.p, d->b.p, d->x.p);
-  hipLaunchKernelGGL(k_bcr_apply<false>, dim3((unsigned)d->top_task.count), dim3(256), (size_t)d->top_ld * sizeof(double), st,
-                     d->tiles.p + d->top_task.first, d->tasks.p, d->arena32.p, d->b.p, d->x.p);
+    launch_bcr_apply(st, true, d->tiles.p + lv.fwd.first, lv.fwd.count, d->tasks.p, lv.fwd_maxld, d->arena32.p, d->b.p, d->x.p);
+  launch_bcr_apply(st, false, d->tiles.p + d->top_task.first, d->top_task.count, d->tasks.p, d->top_ld, d->arena32.p, d->b.p, d->x.p);
   for (auto it = d->levels.rbegin(); it != d->levels.rend(); ++it)
-    if (it->bwd.count)
-      hipLaunchKernelGGL(k_bcr_apply<false>, dim3((unsigned)it->bwd.count), dim3(256), (size_t)it->bwd_maxld * sizeof(double), st,
-                         d->tiles.p + it->bwd.first, d->tasks.p, d->arena32.p, d->b.p, d->x.p);
-  if (xc4) hipLaunchKernelGGL(k_bcr_scatter, dim3((unsigned)grid1(d->nc)), dim3(256), 0, st, d->nc, d->pos.p, d->x.p, xc4);
+    launch_bcr_apply(st, false, d->tiles.p + it->bwd.first, it->bwd.count, d->tasks.p, it->bwd_maxld, d->arena32.p, d->b.p, d->x.p);
+  if (xc4) launch_bcr_scatter(st, d->nc, d->pos.p, d->x.p, xc4);
   return FSI_OK;
 }
 const int32_t* bcr_pos(const FsiCtx* ctx) { return ctx->bcr->pos.p; }

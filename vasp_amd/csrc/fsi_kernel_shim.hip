@@ -834,6 +834,229 @@ int shim_scatter3_f32(int64_t nS, int64_t nfull, const int32_t* snode, const flo
   SHIM_RUN(c, "launch_scatter3_f32", launch_scatter3_f32(c.st, nS, dsn, dco, dfu));
 }
 
+// ---- fsi_bcr.hip: the exact coarse solve by block cyclic reduction -----------------------------------------------------------
+// Descriptors come as flat int64 / double rows (no dependence on the structs' padding); the tile lists are built by the
+// planner's own builders (fsi_bcr.hpp).  Every descriptor is checked against the array lengths first: status LAUNCH_REFUSED
+// (nothing launched) for one that would reach outside them.
+namespace {
+bool within(int64_t first, int64_t last, int64_t n) { return first >= 0 && last >= first && last < n; }
+int refuse(const char* what, int64_t i) {
+  g_err = std::string(what) + ": descriptor " + std::to_string(i) + " reaches outside its arrays, nothing launched";
+  return LAUNCH_REFUSED;
+}
+}  // namespace
+
+// desc [ninv][6]: a, o32 (-1: no FP32 copy), cb, rb, m, ld32 - in place on arena64 [n64], copies into arena32 [n32]; flag [1]
+int shim_bcr_invert(int64_t ninv, const int64_t* desc, double* arena64, int64_t n64, float* arena32, int64_t n32, int32_t* flag) {
+  std::vector<BcrInv> invs;
+  std::vector<BcrGemm> gemms;
+  std::vector<BcrGemmTile> tiles;
+  int maxm = 0;
+  for (int64_t i = 0; i < ninv; ++i) {
+    const int64_t* q = desc + 6 * i;
+    const int m = (int)q[4];
+    const BcrInv v = bcr_inverse(q[0], q[1], q[2], q[3], m, (int)q[5]);
+    if (m < 1 || !within(v.a, v.a + (int64_t)m * m - 1, n64) || !within(v.cb, v.cb + (int64_t)m * BCR_PANEL - 1, n64) ||
+        !within(v.rb, v.rb + (int64_t)m * BCR_PANEL - 1, n64) || (v.o32 >= 0 && (v.ld32 < m || !within(v.o32, v.o32 + (int64_t)(m - 1) * v.ld32 + m - 1, n32))))
+      return refuse("shim_bcr_invert", i);
+    invs.push_back(v);
+    bcr_gemm_tiles(bcr_inverse_update(v), (int32_t)gemms.size(), tiles);
+    gemms.push_back(bcr_inverse_update(v));
+    maxm = std::max(maxm, m);
+  }
+  Call c;
+  const BcrInv* dinv = c.in(invs.data(), invs.size());
+  const BcrGemm* dg = c.in(gemms.data(), gemms.size());
+  const BcrGemmTile* dt = c.in(tiles.data(), tiles.size());
+  double* d64 = c.io(arena64, (size_t)n64);
+  float* d32 = c.io(arena32, (size_t)n32);
+  int32_t* df = c.io(flag, 1);
+  SHIM_RUN(c, "launch_bcr_invert", launch_bcr_invert(c.st, dinv, ninv, dt, (int64_t)tiles.size(), dg, maxm, d64, d32, df));
+}
+// idesc [ng][16]: a1, b1, a2, b2, c, o32, M, N, K1, K2, lda1, ldb1, lda2, ldb2, ldc, ld32; ddesc [ng][2]: alpha, beta; flag [1]
+int shim_bcr_gemm(int64_t ng, const int64_t* idesc, const double* ddesc, double* arena64, int64_t n64, float* arena32, int64_t n32,
+                  int32_t* flag) {
+  std::vector<BcrGemm> gemms;
+  std::vector<BcrGemmTile> tiles;
+  for (int64_t i = 0; i < ng; ++i) {
+    const int64_t* q = idesc + 16 * i;
+    BcrGemm g{q[0], q[1], q[2], q[3], q[4], q[5], (int32_t)q[6], (int32_t)q[7], (int32_t)q[8], (int32_t)q[9], (int32_t)q[10],
+              (int32_t)q[11], (int32_t)q[12], (int32_t)q[13], (int32_t)q[14], (int32_t)q[15], ddesc[2 * i], ddesc[2 * i + 1]};
+    bool ok = g.M >= 1 && g.N >= 1;
+    for (int prod = 0; prod < 2 && ok; ++prod) {
+      const int64_t ao = prod ? g.a2 : g.a1, bo = prod ? g.b2 : g.b1;
+      const int64_t K = prod ? g.K2 : g.K1, lda = prod ? g.lda2 : g.lda1, ldb = prod ? g.ldb2 : g.ldb1;
+      if (ao < 0 || bo < 0 || K <= 0) continue;
+      ok = lda >= K && ldb >= g.N && within(ao, ao + (g.M - 1) * lda + K - 1, n64) && within(bo, bo + (K - 1) * ldb + g.N - 1, n64);
+    }
+    if (ok && g.c >= 0) ok = g.ldc >= g.N && within(g.c, g.c + (int64_t)(g.M - 1) * g.ldc + g.N - 1, n64);
+    if (ok && g.o32 >= 0) ok = g.ld32 >= g.N && within(g.o32, g.o32 + (int64_t)(g.M - 1) * g.ld32 + g.N - 1, n32);
+    if (!ok) return refuse("shim_bcr_gemm", i);
+    bcr_gemm_tiles(g, (int32_t)gemms.size(), tiles);
+    gemms.push_back(g);
+  }
+  Call c;
+  const BcrGemm* dg = c.in(gemms.data(), gemms.size());
+  const BcrGemmTile* dt = c.in(tiles.data(), tiles.size());
+  double* d64 = c.io(arena64, (size_t)n64);
+  float* d32 = c.io(arena32, (size_t)n32);
+  int32_t* df = c.io(flag, 1);
+  SHIM_RUN(c, "launch_bcr_gemm", launch_bcr_gemm(c.st, dt, (int64_t)tiles.size(), dg, d64, d32, df));
+}
+// tdesc [nt][14]: w, rows, ldw, out, nseg, then (off, len, src) of three segments; W [nW] floats; b, x [n] (b in place when
+// forward, x when backward)
+int shim_bcr_apply(int forward, int64_t nt, const int64_t* tdesc, const float* W, int64_t nW, double* b, double* x, int64_t n) {
+  std::vector<BcrTask> tasks;
+  std::vector<BcrTile> tiles;
+  int maxld = 0;
+  for (int64_t i = 0; i < nt; ++i) {
+    const int64_t* q = tdesc + 14 * i;
+    BcrTask t{q[0], (int32_t)q[1], (int32_t)q[2], (int32_t)q[3], (int32_t)q[4], {}};
+    bool ok = t.rows >= 1 && t.ldw >= 4 && t.ldw % 4 == 0 && t.w % 4 == 0 && t.ldw <= 8000 && t.nseg >= 0 && t.nseg <= 3 &&
+              within(t.w, t.w + (int64_t)t.rows * t.ldw - 1, nW) && within(t.out, (int64_t)t.out + t.rows - 1, n);
+    int64_t cols = 0;
+    for (int k = 0; k < 3 && ok; ++k) {
+      t.seg[k] = BcrSeg{(int32_t)q[5 + 3 * k], (int32_t)q[6 + 3 * k], (int32_t)q[7 + 3 * k]};
+      if (k >= t.nseg) continue;
+      cols += t.seg[k].len;
+      ok = t.seg[k].len >= 0 && (t.seg[k].len == 0 || within(t.seg[k].off, (int64_t)t.seg[k].off + t.seg[k].len - 1, n));
+    }
+    if (!ok || cols > t.ldw) return refuse("shim_bcr_apply", i);
+    bcr_task_tiles(t, (int32_t)tasks.size(), tiles);
+    tasks.push_back(t);
+    maxld = std::max(maxld, (int)t.ldw);
+  }
+  Call c;
+  const BcrTask* dts = c.in(tasks.data(), tasks.size());
+  const BcrTile* dtl = c.in(tiles.data(), tiles.size());
+  const float* dW = c.in(W, (size_t)nW);
+  double* db = c.io(b, (size_t)n);
+  double* dx = c.io(x, (size_t)n);
+  SHIM_RUN(c, "launch_bcr_apply", launch_bcr_apply(c.st, forward != 0, dtl, (int64_t)tiles.size(), dts, maxld, dW, db, dx));
+}
+// cvals [9 nblk], dst / ld [nblk]; arena64 [n64] in place
+int shim_bcr_fill(int64_t nblk, const float* cvals, const int64_t* dst, const int32_t* ld, double shift, double* arena64, int64_t n64) {
+  for (int64_t e = 0; e < nblk; ++e) {
+    const int64_t l = ld[e] < 0 ? -(int64_t)ld[e] : ld[e];
+    if (dst[e] >= 0 && (l < 3 || !within(dst[e], dst[e] + 2 * l + 2, n64))) return refuse("shim_bcr_fill", e);
+  }
+  Call c;
+  const float* dcv = c.in(cvals, 9 * (size_t)nblk);
+  const int64_t* dd = c.in(dst, (size_t)nblk);
+  const int32_t* dl = c.in(ld, (size_t)nblk);
+  double* d64 = c.io(arena64, (size_t)n64);
+  SHIM_RUN(c, "launch_bcr_fill", launch_bcr_fill(c.st, nblk, dcv, dd, dl, shift, d64));
+}
+// pos [nc]; rc4 / xc4 [4 nc]; b / x [n]
+int shim_bcr_gather(int64_t nc, const int32_t* pos, const float* rc4, double* b, int64_t n) {
+  for (int64_t i = 0; i < nc; ++i) if (!within(3 * (int64_t)pos[i], 3 * (int64_t)pos[i] + 2, n)) return refuse("shim_bcr_gather", i);
+  Call c;
+  const int32_t* dp = c.in(pos, (size_t)nc);
+  const float* dr = c.in(rc4, 4 * (size_t)nc);
+  double* db = c.io(b, (size_t)n);
+  SHIM_RUN(c, "launch_bcr_gather", launch_bcr_gather(c.st, nc, dp, dr, db));
+}
+int shim_bcr_scatter(int64_t nc, const int32_t* pos, const double* x, int64_t n, float* xc4) {
+  for (int64_t i = 0; i < nc; ++i) if (!within(3 * (int64_t)pos[i], 3 * (int64_t)pos[i] + 2, n)) return refuse("shim_bcr_scatter", i);
+  Call c;
+  const int32_t* dp = c.in(pos, (size_t)nc);
+  const double* dx = c.in(x, (size_t)n);
+  float* dxc = c.io(xc4, 4 * (size_t)nc);
+  SHIM_RUN(c, "launch_bcr_scatter", launch_bcr_scatter(c.st, nc, dp, dx, dxc));
+}
+
+// The whole solve on a bare context: bcr_plan on the pattern (cptr [nc + 1], ccol), then for every value set s (cvals [nsets][9
+// cptr[nc]], FP32 3x3 blocks as the solid cycle's coarse level holds them) bcr_refresh with tune.bcr_shift = shift and, where it
+// left the solve ready, nrhs solves two ways: rhs [nrhs][3 nc] (FP64, the solve's own order) written straight to bcr_rhs ->
+// x [nsets][nrhs][3 nc]; rc4 [nrhs][4 nc] (node order) through the production gather / scatter -> xc4 [nsets][nrhs][4 nc].
+// stats [12]: usable, blocks, max_block, levels, bytes32, bytes64, setup_flops, launches, planned, number of tasks, FP32 arena
+// floats, FP64 arena doubles.  ready [nsets], pos [nc].  Of the last value set, when their capacities suffice: arena32 [cap32],
+// tasks [cap_tasks][16] (w, rows, ldw, out, nseg, 3 x (off, len, src), level, kind 0 forward / 1 backward / 2 top), in the
+// planner's order.  Any output may be null.
+int shim_bcr_run(int64_t nc, const int64_t* cptr, const int32_t* ccol, int nsets, const float* cvals, double shift, int nrhs,
+                 const double* rhs, const float* rc4, int64_t* stats, int32_t* ready, int32_t* pos, double* x, float* xc4,
+                 float* arena32, int64_t cap32, int64_t* tasks, int64_t cap_tasks) {
+  FsiCtx* ctx = new FsiCtx();
+  hipError_t e = hipSuccess;
+  auto note = [&](hipError_t y) { if (e == hipSuccess && y != hipSuccess) e = y; };
+  note(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+  ctx->tune.bcr_shift = shift;
+  const int64_t nnz = cptr[nc];
+  std::vector<int64_t> p(cptr, cptr + nc + 1);
+  std::vector<int32_t> cc(ccol, ccol + nnz);
+  host::BcrPlanStats st;
+  int rc = e == hipSuccess ? host::bcr_plan(ctx, nc, p, cc, &st) : 0;
+  BcrData* d = ctx->bcr;
+  const bool planned = d && d->planned;
+  if (stats) {
+    const int64_t v[] = {st.usable, st.blocks, st.max_block, st.levels, st.bytes32, st.bytes64, st.setup_flops, st.launches, planned,
+                         planned ? (int64_t)d->tasks.n : 0, planned ? (int64_t)d->arena32.n : 0, planned ? (int64_t)d->arena64.n : 0};
+    std::copy(v, v + 12, stats);
+  }
+  const int64_t n = 3 * nc;
+  float* drc = nullptr;
+  float* dxc = nullptr;
+  if (planned && rc == 0) {
+    if (pos) note(hipMemcpy(pos, d->pos.p, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost));
+    note(ctx->sbmg_cvals.alloc(9 * (size_t)nnz));
+    note(hipMalloc(&drc, 4 * (size_t)nc * sizeof(float)));
+    note(hipMalloc(&dxc, 4 * (size_t)nc * sizeof(float)));
+    for (int s = 0; s < nsets && e == hipSuccess && rc == 0; ++s) {
+      note(hipMemcpy(ctx->sbmg_cvals.p, cvals + 9 * (size_t)nnz * s, 9 * (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
+      if (e == hipSuccess) rc = host::bcr_refresh(ctx);
+      const bool ok = host::bcr_ready(ctx);
+      if (ready) ready[s] = ok;
+      for (int r = 0; r < nrhs && ok && e == hipSuccess && rc == 0; ++r) {
+        if (rhs && x) {
+          note(hipMemcpy(host::bcr_rhs(ctx), rhs + (size_t)n * r, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+          if (e == hipSuccess) rc = host::bcr_solve(ctx, nullptr, nullptr, ctx->stream);
+          note(hipGetLastError());
+          note(hipStreamSynchronize(ctx->stream));
+          note(hipMemcpy(x + (size_t)n * (r + (size_t)nrhs * s), host::bcr_sol(ctx), (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        if (rc4 && xc4 && rc == 0) {
+          note(hipMemcpy(drc, rc4 + 4 * (size_t)nc * r, 4 * (size_t)nc * sizeof(float), hipMemcpyHostToDevice));
+          note(hipMemcpy(dxc, xc4 + 4 * (size_t)nc * (r + (size_t)nrhs * s), 4 * (size_t)nc * sizeof(float), hipMemcpyHostToDevice));
+          if (e == hipSuccess) rc = host::bcr_solve(ctx, drc, dxc, ctx->stream);
+          note(hipGetLastError());
+          note(hipStreamSynchronize(ctx->stream));
+          note(hipMemcpy(xc4 + 4 * (size_t)nc * (r + (size_t)nrhs * s), dxc, 4 * (size_t)nc * sizeof(float), hipMemcpyDeviceToHost));
+        }
+      }
+    }
+    if (arena32 && cap32 >= (int64_t)d->arena32.n && e == hipSuccess)
+      note(hipMemcpy(arena32, d->arena32.p, d->arena32.n * sizeof(float), hipMemcpyDeviceToHost));
+    if (tasks && cap_tasks >= (int64_t)d->tasks.n && e == hipSuccess) {
+      std::vector<BcrTask> ht(d->tasks.n);
+      std::vector<BcrTile> hl(d->tiles.n);
+      note(hipMemcpy(ht.data(), d->tasks.p, ht.size() * sizeof(BcrTask), hipMemcpyDeviceToHost));
+      note(hipMemcpy(hl.data(), d->tiles.p, hl.size() * sizeof(BcrTile), hipMemcpyDeviceToHost));
+      std::vector<int64_t> lev(ht.size(), -1), kind(ht.size(), -1);
+      auto tag = [&](const BcrRange& r, int64_t l, int64_t k) {
+        for (int64_t t = r.first; t < r.first + r.count; ++t) { lev[hl[t].task] = l; kind[hl[t].task] = k; }
+      };
+      for (size_t l = 0; l < d->levels.size(); ++l) { tag(d->levels[l].fwd, (int64_t)l, 0); tag(d->levels[l].bwd, (int64_t)l, 1); }
+      tag(d->top_task, (int64_t)d->levels.size(), 2);
+      for (size_t t = 0; t < ht.size(); ++t) {
+        int64_t* q = tasks + 16 * t;
+        q[0] = ht[t].w; q[1] = ht[t].rows; q[2] = ht[t].ldw; q[3] = ht[t].out; q[4] = ht[t].nseg;
+        for (int k = 0; k < 3; ++k) { q[5 + 3 * k] = ht[t].seg[k].off; q[6 + 3 * k] = ht[t].seg[k].len; q[7 + 3 * k] = ht[t].seg[k].src; }
+        q[14] = lev[t]; q[15] = kind[t];
+      }
+    }
+  }
+  if (drc) (void)hipFree(drc);
+  if (dxc) (void)hipFree(dxc);
+  host::bcr_free(ctx);
+  ctx->sbmg_cvals.release();
+  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+  const std::string err = ctx->err;
+  delete ctx;
+  if (e != hipSuccess) { g_err = std::string("shim_bcr_run: ") + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")"; return 1; }
+  if (rc != 0) { g_err = "shim_bcr_run: " + err; return rc; }
+  return 0;
+}
+
 // ---- a live context's preconditioner arrays (FsiCtx of fsi_context.hpp, as the library was compiled) -----------------------
 // shim_ctx_info: N2, V, nS, sb_nblocks, tiled, tile_nodes, tile_max_nu, schur_tiled, schur_tile, s_tile_max_nu, sweeps_fp16,
 // a32_ptail, a32_tail_src, a32_tail_nnz, op32_ok, kry_fp32, drows_ok, mg_nc, mg_cnnz, mg_ready, sbmg_nc, sbmg_nblk, sbmg_ready,

@@ -1,5 +1,6 @@
 // Declarations shared by the HIP translation units of libvaspfsi.so.
 #pragma once
+#include "fsi_bcr.hpp"
 #include "fsi_context.hpp"
 
 namespace fsi {
@@ -371,5 +372,19 @@ void launch_mask_ripple(hipStream_t st, int64_t n, const double* mask, double* x
 void launch_mask_scale(hipStream_t st, int64_t n, const double* mask, const int64_t* diagpos, const double* A, double* y);
 void launch_residual_csr(hipStream_t st, int64_t n, const int64_t* rowptr, const int32_t* cols, const double* vals,
                          const double* x, const double* b, double* y);
+// fsi_bcr.hip: the exact coarse solve.  Every descriptor pointer is the device table already offset to the first entry the
+// launch takes; task / gemm ids inside the tiles index the whole table (tasks, gemms).  flag [1]: bit 0 set on a vanished or
+// non-finite pivot and on a non-finite FP32 operator.
+void launch_bcr_fill(hipStream_t st, int64_t nblk, const float* cvals, const int64_t* dst, const int32_t* ld, double shift, double* arena64);
+void launch_bcr_gather(hipStream_t st, int64_t nc, const int32_t* pos, const float* rc4, double* b);
+void launch_bcr_scatter(hipStream_t st, int64_t nc, const int32_t* pos, const double* x, float* xc4);
+// ninv in-place inverses (panels of 32 up to maxm, each followed by its rank-32 updates: nupd tiles), then their FP32 copies
+void launch_bcr_invert(hipStream_t st, const BcrInv* invs, int64_t ninv, const BcrGemmTile* upd, int64_t nupd, const BcrGemm* gemms,
+                       int maxm, double* arena64, float* arena32, int32_t* flag);
+void launch_bcr_gemm(hipStream_t st, const BcrGemmTile* tiles, int64_t ntiles, const BcrGemm* gemms, double* arena64, float* arena32,
+                     int32_t* flag);
+// forward: b[out + r] += W[r] . in;  backward: x[out + r] = W[r] . in.  maxld: the largest ldw of the tiles' tasks (LDS)
+void launch_bcr_apply(hipStream_t st, bool forward, const BcrTile* tiles, int64_t ntiles, const BcrTask* tasks, int maxld, const float* W,
+                      double* b, double* x);
 
 }  // namespace fsi
