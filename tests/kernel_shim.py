@@ -1,6 +1,6 @@
 """ctypes loader of ``vasp_amd/libfsi_kernel_shim.so`` (vasp_amd/csrc/fsi_kernel_shim.hip) and the host-side reference builders
 of the kernel tests (tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py, tests/test_gpu_product_kernels.py,
-tests/test_gpu_coarse_kernels.py, tests/test_gpu_bcr_kernels.py).
+tests/test_gpu_coarse_kernels.py, tests/test_gpu_bcr_kernels.py, tests/test_gpu_block_kernels.py).
 
 The shim runs ONE ``fsi::launch_*`` call of libvaspfsi.so on host arrays; the builders restate, in numpy, what the library's
 host code hands those kernels: the LDS tiles of a graph (fsi_capi.hip, node tiles and Schur tiles), the FP16 records of
@@ -44,6 +44,15 @@ _SIGS = {
     "shim_scatter3_f32": "llppp",
     "shim_bcr_invert": "lpplplp", "shim_bcr_gemm": "lppplplp", "shim_bcr_apply": "ilpplppl", "shim_bcr_fill": "lpppdpl",
     "shim_bcr_gather": "lpppl", "shim_bcr_scatter": "lpplp", "shim_bcr_run": "lppipdipppppppplpl",
+    "shim_tail": "", "shim_block_structure": "llpppppppppppp", "shim_extract_blocks": "lldppppppppppppppppp",
+    "shim_extract_db": "lpppppi", "shim_extract_chat": "lpppppp", "shim_db_rowmask": "lppp", "shim_mask_outside": "lppp",
+    "shim_to_f32": "lpp", "shim_gather_vals": "lpplp", "shim_sb_gather": "llpppplp", "shim_schur_full": "llppppppppppppppppp",
+    "shim_pres_rhs32": "llpppppppp", "shim_vel_correct32": "llppppppp", "shim_vel_correct": "lpppplpplppp",
+    "shim_pres_rows": "lppppdppppldpdp", "shim_cheb_init": "lppppldppp",
+    "shim_cheb_step": "lpppplddppp", "shim_db_rows_sub": "llppppppp", "shim_spmv_db": "lpppppp",
+    "shim_residual_csr": "lpppplpp", "shim_residual_rows": "lppppplplppl", "shim_split": "llpppp", "shim_merge": "llpppp",
+    "shim_merge_f32d": "llpppp", "shim_pad_init_f32": "lpppfppp", "shim_pad_to_f32": "lppp", "shim_unpad_from_f32": "lpp",
+    "shim_mask_ripple": "lpp", "shim_mask_scale": "lppplp",
 }
 LAUNCH_REFUSED = 2           # fsi_kernels.hpp: a launch function refused its arguments and launched nothing
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "d": C.c_double, "s": C.c_char_p}
@@ -112,7 +121,8 @@ _ELEM = {("f", 4): np.float32, ("f", 8): np.float64, ("i", 1): np.uint8, ("i", 2
 _UNSIGNED = {"dd_rec", "vv_rec", "sb_rec", "s_rec"}
 _FLOAT = {"dd_chat", "vv_db32", "sb_vals", "sb_binv12", "s_vals", "s_vals32", "s_dinv", "dd_db", "rowscale", "A", "A32", "Ad64", "Ad32",
           "mg_pw", "mg_chw", "mg_Ac", "mg_cc", "mg_d0", "mg_dcinv4", "sbmg_pw", "sbmg_chw", "sbmg_cvals", "sbmg_cbinv12",
-          "sb_binv9", "sb_dinv", "dd_dinv32", "vvf_dinv32"}
+          "sb_binv9", "sb_dinv", "dd_dinv32", "vvf_dinv32", "Mdd.vals", "Mvv.vals", "Adv", "Avp", "Apv", "App", "Avp32", "Apv32",
+          "vv_db", "adv_db", "dd_db32", "vv_dinv", "mask_f", "mask_s", "ss_vals"}
 
 
 def ctx_info(ctx) -> dict:
@@ -134,7 +144,8 @@ def ctx_ktheta(ctx) -> float:
     return float(load().shim_ctx_ktheta(ctx))
 
 
-COARSE = ("mg_gersh", "sbmg_gersh", "mg_clmax", "sbmg_clmax")
+COARSE = ("mg_gersh", "sbmg_gersh", "mg_clmax", "sbmg_clmax", "lmax_s", "lmax_f", "lmax_p", "lmax_d", "cheb_kappa_s", "cheb_kappa_f",
+          "cheb_kappa_p", "cheb_kappa_d", "dd_is_db", "adv_is_db", "dd_is_scalar", "adv_solid_only", "pv32_ok")
 
 
 def ctx_coarse(ctx) -> dict:
@@ -1046,3 +1057,280 @@ def bcr_run(g, value_sets, shift, rhs=None, rc4=None, arena=False):
          xc4 if rc4 is not None else None, a32, cap32, tk, cap_t)
     return dict(stats=dict(zip(BCR_RUN_STATS, (int(v) for v in stats))), ready=ready, pos=pos, x=x, xc4=xc4, arena32=a32,
                 tasks=None if tk is None else tk[:cap_t])
+
+
+# ---- the field split, the Schur complement and the pressure step (fsi_block.hip; tests/test_gpu_block_kernels.py) ------------
+# The restatements below go through scipy: the monolithic matrix is a CSR matrix of entry NUMBERS, its field blocks are taken by
+# row / column sets, and only the result is laid out in the kernels' arrays.  None of them repeats a kernel's index arithmetic.
+TAIL = 8                     # fsi_kernel_shim.hip SHIM_TAIL: sentinel entries behind every output of the block entry points
+EPS64 = float(np.finfo(np.float64).eps)
+SCHUR_ROW_LIMIT = 1024       # fsi_block.hip MAXS2: entries of a Schur row the LDS accumulator holds
+
+
+def out(n, dtype, fill):
+    """an output array of n entries plus the TAIL sentinels, all set to `fill`"""
+    return np.full(int(n) + TAIL, fill, dtype=dtype)
+
+
+def tail_untouched(a, n, fill):
+    t = a[int(n):]
+    return len(t) == TAIL and (np.all(np.isnan(t)) if isinstance(fill, float) and np.isnan(fill) else np.all(t == fill))
+
+
+def shaped_graph(N2, V, rng, shapes=(), reach=24, max_deg=12, vertices_first=False):
+    """mono_graph with chosen nodes of an exact shape: shapes is a list of (deg, pdeg, is_vertex), each given to one node (distinct,
+    drawn at random among the vertices / the other nodes): the node has exactly deg neighbours (itself included) of which exactly
+    pdeg are vertices.  Returns (graph, nodes) with nodes[k] the node of shapes[k]."""
+    import scipy.sparse as sp
+    vrank = (np.arange(V) if vertices_first else rng.choice(N2, size=V, replace=False)).astype(np.int32)
+    isv = np.zeros(N2, dtype=bool)
+    isv[vrank] = True
+    k = rng.integers(0, max_deg + 1, N2)
+    src = np.repeat(np.arange(N2, dtype=np.int64), k)
+    dst = np.clip(src + rng.integers(-reach, reach + 1, len(src)), 0, N2 - 1)
+    vs, os_ = np.flatnonzero(isv), np.flatnonzero(~isv)
+    want_v = np.array([bool(sh[2]) for sh in shapes], dtype=bool)
+    nodes = np.zeros(len(shapes), dtype=np.int64)
+    nodes[want_v] = rng.choice(vs, size=int(want_v.sum()), replace=False) if want_v.any() else []
+    nodes[~want_v] = rng.choice(os_, size=int((~want_v).sum()), replace=False) if (~want_v).any() else []
+    keep = ~np.isin(src, nodes)
+    src, dst = [src[keep], np.arange(N2)], [dst[keep], np.arange(N2)]
+    for r, (deg, pdeg, _) in zip(nodes, shapes):
+        pv = pdeg - int(isv[r])
+        po = deg - pdeg - int(not isv[r])
+        assert pv >= 0 and po >= 0, "the node itself counts: a vertex has pdeg >= 1, any other node deg - pdeg >= 1"
+        nb = np.concatenate([rng.choice(vs[vs != r], size=pv, replace=False), rng.choice(os_[os_ != r], size=po, replace=False)])
+        src.append(np.full(len(nb), r))
+        dst.append(nb)
+    G = sp.csr_matrix((np.ones(sum(map(len, src))), (np.concatenate(src), np.concatenate(dst))), shape=(N2, N2))
+    G.sum_duplicates()
+    G.sort_indices()
+    pos = np.full(N2, -1, dtype=np.int64)
+    pos[vrank] = np.arange(V)
+    Pm = sp.csr_matrix((np.ones(V), (vrank.astype(np.int64), np.arange(V))), shape=(N2, V))
+    PA = (G @ Pm).tocsr()
+    PA.sort_indices()
+    g = (G.indptr.astype(np.int64), G.indices.astype(np.int32), PA.indptr.astype(np.int64), PA.indices.astype(np.int32), vrank)
+    return g, nodes
+
+
+def entry_matrix(N2, V, graph):
+    """The monolithic pattern (expand_cols) as a scipy CSR matrix whose values are the entry numbers + 1, and the row / column
+    sets of the three fields (d, v, p)"""
+    import scipy.sparse as sp
+    rowptr, cols, _ = expand_cols(N2, *graph)
+    n = 6 * N2 + V
+    E = sp.csr_matrix((np.arange(1, rowptr[-1] + 1, dtype=np.float64), cols, rowptr), shape=(n, n))
+    assert E.has_sorted_indices
+    Dd = np.arange(6 * N2).reshape(N2, 6)[:, :3].ravel()
+    return E, Dd, Dd + 3, 6 * N2 + np.arange(V)
+
+
+def _blk(E, rows, cols):
+    B = E[rows][:, cols].tocsr()
+    B.sort_indices()
+    return B
+
+
+def block_structure(N2, V, graph):
+    """The structure arrays of launch_block_structure (and rowptr_pv / rowptr_pp / cols_pp, which the host builds): each block is
+    the CSR pattern of the monolithic matrix restricted to its row and column sets."""
+    E, Dd, Vd, Pd = entry_matrix(N2, V, graph)
+    vv, vp, pv, pp = _blk(E, Vd, Vd), _blk(E, Vd, Pd), _blk(E, Pd, Vd), _blk(E, Pd, Pd)
+    i64, i32 = (lambda a: np.ascontiguousarray(a, dtype=np.int64)), (lambda a: np.ascontiguousarray(a, dtype=np.int32))
+    row = np.repeat(np.arange(3 * N2), np.diff(vv.indptr))
+    diagpos3 = np.full(3 * N2, -1, dtype=np.int64)
+    hit = np.flatnonzero(vv.indices == row)
+    diagpos3[row[hit]] = hit
+    return dict(rowptr3=i64(vv.indptr), cols3=i32(vv.indices), diagpos3=diagpos3, rowptr_vp=i64(vp.indptr), cols_vp=i32(vp.indices),
+                rowptr_pv=i64(pv.indptr), cols_pv=i32(pv.indices), rowptr_pp=i64(pp.indptr), cols_pp=i32(pp.indices))
+
+
+def extract_blocks(N2, V, graph, A, node_solid, ktheta):
+    """The six value arrays of launch_extract_blocks in the block_structure layout.  Avv = A_vv + A_vd K, Apv = A_pv + A_pd K with
+    K = ktheta on the displacement columns of solid nodes (the d and v columns of a node share their pattern, so A_vd lies on A_vv's).
+    Also: Avv_mag / Apv_mag = |e_v| + |ktheta e_d| (|e_v| off the solid columns), Avv_solid / Apv_solid the entries in solid
+    columns, and the parts e_v, e_d themselves (Avv_v, Avv_d, Apv_v, Apv_d)."""
+    E, Dd, Vd, Pd = entry_matrix(N2, V, graph)
+    A = np.asarray(A, dtype=np.float64)
+    val = lambda B: A[B.data.astype(np.int64) - 1]      # noqa: E731
+    res = dict(Add=val(_blk(E, Dd, Dd)), Adv=val(_blk(E, Dd, Vd)), Avp=val(_blk(E, Vd, Pd)), App=val(_blk(E, Pd, Pd)))
+    for name, rows in (("Avv", Vd), ("Apv", Pd)):
+        Bv, Bd = _blk(E, rows, Vd), _blk(E, rows, Dd)
+        assert np.array_equal(Bv.indptr, Bd.indptr) and np.array_equal(Bv.indices, Bd.indices)
+        sol = np.asarray(node_solid)[Bv.indices // 3] != 0
+        ev, ed = val(Bv), val(Bd)
+        res[name] = np.where(sol, ev + ktheta * ed, ev)
+        res[name + "_mag"] = np.abs(ev) + np.where(sol, np.abs(ktheta * ed), 0.0)
+        res[name + "_solid"], res[name + "_v"], res[name + "_d"] = sol, ev, ed
+    return res
+
+
+def assemble_blocks(N2, V, graph, st, b, node_solid, ktheta):
+    """the inverse of extract_blocks (K undone): the monolithic value array"""
+    E, Dd, Vd, Pd = entry_matrix(N2, V, graph)
+    A = np.full(E.nnz, np.nan)
+    put = lambda rows, cols, v: A.__setitem__(_blk(E, rows, cols).data.astype(np.int64) - 1, v)      # noqa: E731
+    put(Dd, Dd, b["Add"]); put(Dd, Vd, b["Adv"]); put(Vd, Pd, b["Avp"]); put(Pd, Pd, b["App"])
+    put(Vd, Dd, b["Avv_d"]); put(Pd, Dd, b["Apv_d"])
+    put(Vd, Vd, np.where(b["Avv_solid"], b["Avv"] - ktheta * b["Avv_d"], b["Avv"]))
+    put(Pd, Vd, np.where(b["Apv_solid"], b["Apv"] - ktheta * b["Apv_d"], b["Apv"]))
+    return A
+
+
+def _group_sum(key, v, n):
+    """sum of the longdouble values v by integer key into n bins"""
+    res = np.zeros(n, dtype=np.longdouble)
+    if len(key):
+        o = np.argsort(key, kind="stable")
+        ks_, vs = key[o], np.asarray(v, dtype=np.longdouble)[o]
+        first = np.flatnonzero(np.concatenate([[True], ks_[1:] != ks_[:-1]]))
+        res[ks_[first]] = np.add.reduceat(vs, first)
+    return res
+
+
+def schur_pattern(V, st):
+    """s_rowptr, s_cols: the columns of A_pp and of (pattern of A_pv) x (pattern of A_vp), ascending per row"""
+    import scipy.sparse as sp
+    n3 = len(st["rowptr3"]) - 1
+    one = lambda ptr, col, shape: sp.csr_matrix((np.ones(len(col)), col, ptr), shape=shape)      # noqa: E731
+    Pt = (one(st["rowptr_pp"], st["cols_pp"], (V, V)) + one(st["rowptr_pv"], st["cols_pv"], (V, n3)) @
+          one(st["rowptr_vp"], st["cols_vp"], (n3, V))).tocsr()
+    Pt.sort_indices()
+    return Pt.indptr.astype(np.int64), Pt.indices.astype(np.int32)
+
+
+def schur_full(V, st, s_rowptr, s_cols, Apv, App, Avp, Avv):
+    """S = A_pp - Apv diag(Avv)^-1 A_vp entry by entry on the given pattern: (S, sum |terms|, number of terms, rows over the
+    limit), the sums in extended precision.  A term is an A_pp entry or one product (Apv_qR / Avv_RR) Avp_Rc; exact zeros of Apv,
+    Avp, App are no terms (the kernel skips them).  Rows longer than SCHUR_ROW_LIMIT are listed and left out (S = NaN there)."""
+    ld = np.longdouble
+    nS = int(s_rowptr[V])
+    skey = np.repeat(np.arange(V, dtype=np.int64), np.diff(s_rowptr)) * max(V, 1) + s_cols
+    rows_pp = np.repeat(np.arange(V, dtype=np.int64), np.diff(st["rowptr_pp"]))
+    # products: every Apv entry (q, R) with every Avp entry (R, c)
+    rows_pv = np.repeat(np.arange(V, dtype=np.int64), np.diff(st["rowptr_pv"]))
+    R = st["cols_pv"].astype(np.int64)
+    cnt = np.diff(st["rowptr_vp"])[R]
+    e = np.repeat(np.arange(len(R)), cnt)
+    t = st["rowptr_vp"][R[e]] + (np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+    coef = np.asarray(Apv, dtype=ld)[e] / np.asarray(Avv, dtype=ld)[st["diagpos3"][R[e]]]
+    term = -coef * np.asarray(Avp, dtype=ld)[t]
+    live = (np.asarray(Apv)[e] != 0.0) & (np.asarray(Avp)[t] != 0.0)
+    key = np.concatenate([rows_pp * max(V, 1) + st["cols_pp"], (rows_pv[e] * max(V, 1) + st["cols_vp"][t])[live]])
+    val = np.concatenate([np.asarray(App, dtype=ld), term[live]])
+    nz = np.concatenate([np.asarray(App) != 0.0, np.ones(int(live.sum()), dtype=bool)])
+    key, val = key[nz], val[nz]
+    where = np.searchsorted(skey, key)
+    assert np.all(where < nS) and np.array_equal(skey[where], key), "a term outside the Schur pattern"
+    S, mag = _group_sum(where, val, nS), _group_sum(where, np.abs(val), nS)
+    L = np.bincount(where, minlength=nS).astype(np.float64)
+    over = np.flatnonzero(np.diff(s_rowptr) > SCHUR_ROW_LIMIT)
+    S = S.astype(np.float64)
+    for q in over:
+        S[s_rowptr[q]:s_rowptr[q + 1]] = np.nan
+    return S, mag.astype(np.float64), L, over
+
+
+def db_extract(N2, graph, st, vals):
+    """k_extract_db: db[e][i] = the (i, i) entry of node pair e's 3x3 block, and whether any other entry is not zero"""
+    import scipy.sparse as sp
+    n3 = 3 * N2
+    M = sp.csr_matrix((np.arange(1, len(vals) + 1, dtype=np.float64), st["cols3"], st["rowptr3"]), shape=(n3, n3))
+    nadj_ptr, nadj = graph[0], graph[1].astype(np.int64)
+    r = np.repeat(np.arange(N2), np.diff(nadj_ptr))
+    vals = np.asarray(vals)
+    db = np.stack([vals[np.asarray(M[3 * r + i, 3 * nadj + i]).ravel().astype(np.int64) - 1] for i in range(3)], axis=1)
+    used = np.zeros(len(vals), dtype=bool)
+    for i in range(3):
+        used[np.asarray(M[3 * r + i, 3 * nadj + i]).ravel().astype(np.int64) - 1] = True
+    return db.ravel(), bool(np.any(vals[~used] != 0.0))
+
+
+def db_terms(N2, graph, db, x):
+    """per row 3r + i of y = db x: (y, sum |terms|, L) in extended precision"""
+    nadj_ptr, nadj = graph[0], graph[1].astype(np.int64)
+    p = np.asarray(db, dtype=np.longdouble).reshape(-1, 3) * np.asarray(x, dtype=np.longdouble).reshape(-1, 3)[nadj]
+    y, S = np.zeros((N2, 3), dtype=np.longdouble), np.zeros((N2, 3), dtype=np.longdouble)
+    deg = np.diff(nadj_ptr)
+    nz = deg > 0
+    if len(p):
+        y[nz] = np.add.reduceat(p, nadj_ptr[:-1][nz], axis=0)
+        S[nz] = np.add.reduceat(np.abs(p), nadj_ptr[:-1][nz], axis=0)
+    return y.ravel(), S.ravel(), np.repeat(deg, 3).astype(np.float64)
+
+
+def rowmask(N2, graph, db):
+    """k_db_rowmask: 1 where the node has a non-zero db entry"""
+    r = np.repeat(np.arange(N2), np.diff(graph[0]))
+    return (np.bincount(r, weights=(np.asarray(db).reshape(-1, 3) != 0.0).any(axis=1), minlength=N2) > 0).astype(np.uint8)
+
+
+def chat_extract(N2, graph, db):
+    """k_extract_chat: (chat, rowflag [3 N2], spread) - a row is an identity row when no off-diagonal pair entry of its component
+    is non-zero; chat = the ratio to the diagonal in the first free component (1 on the diagonal / 0 elsewhere when all three
+    rows of the node are identity rows); spread[e] = the largest |ratio_i - ratio_ref| over the other free components (what the
+    kernel's flag bit 4 tests against 1e-9 |c| + 1e-12)."""
+    nadj_ptr, nadj = graph[0], graph[1].astype(np.int64)
+    db = np.asarray(db, dtype=np.float64).reshape(-1, 3)
+    r = np.repeat(np.arange(N2), np.diff(nadj_ptr))
+    isd = nadj == r
+    assert np.array_equal(np.bincount(r[isd], minlength=N2), np.ones(N2)), "every node needs its diagonal pair"
+    de = np.flatnonzero(isd)
+    ident = np.stack([np.bincount(r, weights=((db[:, i] != 0.0) & ~isd), minlength=N2) == 0 for i in range(3)], axis=1)
+    ref = np.argmax(~ident, axis=1)
+    with np.errstate(all="ignore"):
+        ratio = db / db[de[r]]
+        c = ratio[np.arange(len(r)), ref[r]]
+        chat = np.where(ident.all(axis=1)[r], isd.astype(np.float64), c)
+        spread = np.where(~ident[r] & ~ident.all(axis=1)[r][:, None], np.abs(ratio - c[:, None]), 0.0).max(axis=1, initial=0.0)
+    return chat, ident.astype(np.uint8).ravel(), spread
+
+
+def ripple(n, mask=None):
+    """k_mask_ripple: h = i * 0x9E3779B97F4A7C15; h ^= h >> 29; h *= 0xBF58476D1CE4E5B9; h ^= h >> 32 (mod 2^64);
+    x = mask * ((h & 0xFFFF) / 65535 - 0.5)"""
+    with np.errstate(over="ignore"):
+        h = np.arange(n, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        h ^= h >> np.uint64(29)
+        h *= np.uint64(0xBF58476D1CE4E5B9)
+        h ^= h >> np.uint64(32)
+    x = (h & np.uint64(0xFFFF)).astype(np.float64) / 65535.0 - 0.5
+    return x if mask is None else np.asarray(mask, dtype=np.float64) * x
+
+
+def power_lmax(apply, scale, n, mask=None, steps=40, dtype=np.float64):
+    """power_lmax_op of fsi_precond.hip: x = ripple; 40 times y = scale(apply(x)), lam = |y| / |x|, x = y / |y|; returns lam (the
+    library stores 1.2 lam).  apply / scale work in `dtype`."""
+    x = ripple(n, mask).astype(dtype)
+    lam = dtype(1.0)
+    for _ in range(steps):
+        y = scale(apply(x))
+        xx, yy = np.dot(x, x), np.dot(y, y)
+        if not (xx > 0 and yy > 0 and np.isfinite(yy)):
+            break
+        lam = np.sqrt(yy / xx)
+        x = y * (dtype(1.0) / np.sqrt(yy))
+    return float(lam)
+
+
+def live_blocks(hb):
+    """The field blocks of a live context restated with scipy from the assembled Jacobian (fsi_get_matrix, user layout, mapped
+    through solver2user and row-equilibrated by rowscale).  Solver layout: node rank r holds d rows 6r + i and v rows 6r + 3 + i,
+    pressure position q row 6 N2 + q.  Avv~ = Avv + ktheta Avd and Apv~ = Apv + ktheta Apd on the displacement columns of solid
+    nodes (k_extract_blocks); the _mag matrices hold |e_v| + |ktheta e_d|."""
+    import scipy.sparse as sp
+    info = ctx_info(hb.ctx)
+    N2, V = info["N2"], info["V"]
+    s2u, rs = ctx_array(hb.ctx, "solver2user").astype(np.int64), ctx_array(hb.ctx, "rowscale")
+    assert hb.ndof == 6 * N2 + V == len(s2u)
+    M = hb.matrix()[s2u][:, s2u].tocsr()             # every stored entry kept: the pattern below is the matrix graph
+    M.data *= np.repeat(rs, np.diff(M.indptr))
+    node = np.arange(N2)
+    Dd = (6 * node[:, None] + np.arange(3)).ravel()
+    Vd, Pd = Dd + 3, 6 * N2 + np.arange(V)
+    K = sp.diags(ctx_ktheta(hb.ctx) * np.repeat(ctx_array(hb.ctx, "node_solid") != 0, 3).astype(np.float64))
+    return dict(N2=N2, V=V, M=M, Dd=Dd, Vd=Vd, Pd=Pd, K=K, Add=M[Dd][:, Dd].tocsr(), Adv=M[Dd][:, Vd].tocsr(),
+                Avv_t=(M[Vd][:, Vd] + M[Vd][:, Dd] @ K).tocsr(), Avv_mag=(abs(M[Vd][:, Vd]) + abs(M[Vd][:, Dd]) @ K).tocsr(),
+                Apv_t=(M[Pd][:, Vd] + M[Pd][:, Dd] @ K).tocsr(), Apv_mag=(abs(M[Pd][:, Vd]) + abs(M[Pd][:, Dd]) @ K).tocsr(),
+                App=M[Pd][:, Pd].tocsr(), Avp=M[Vd][:, Pd].tocsr())

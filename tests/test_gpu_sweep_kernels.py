@@ -521,20 +521,9 @@ def test_live_context_operators_are_the_jacobian_blocks(live_ctx):
     info = ks.ctx_info(hb.ctx)
     A = lambda name: ks.ctx_array(hb.ctx, name)      # noqa: E731
     N2, V = info["N2"], info["V"]
-    s2u, rs = A("solver2user").astype(np.int64), A("rowscale")
-    assert hb.ndof == 6 * N2 + V == len(s2u)
-    M = hb.matrix()[s2u][:, s2u].tocsr()             # every stored entry kept: the pattern below is the matrix graph
-    M.data *= np.repeat(rs, np.diff(M.indptr))
-    node = np.arange(N2)
-    Dd = (6 * node[:, None] + np.arange(3)).ravel()
-    Vd, Pd = Dd + 3, 6 * N2 + np.arange(V)
-    K = sp.diags(ks.ctx_ktheta(hb.ctx) * np.repeat(A("node_solid") != 0, 3).astype(np.float64))
-    Add = M[Dd][:, Dd].tocsr()
-    Avv_t = (M[Vd][:, Vd] + M[Vd][:, Dd] @ K).tocsr()
-    Avv_mag = (abs(M[Vd][:, Vd]) + abs(M[Vd][:, Dd]) @ K).tocsr()
-    Apv_t = (M[Pd][:, Vd] + M[Pd][:, Dd] @ K).tocsr()
-    Apv_mag = abs(M[Pd][:, Vd]) + abs(M[Pd][:, Dd]) @ K
-    App, Avp = M[Pd][:, Pd].tocsr(), M[Vd][:, Pd].tocsr()
+    lb = ks.live_blocks(hb)                          # the scipy restatement, shared with tests/test_gpu_block_kernels.py
+    M, Vd, Pd, node = lb["M"], lb["Vd"], lb["Pd"], np.arange(N2)
+    Add, Avv_t, Avv_mag, Apv_t, Apv_mag, App, Avp = (lb[k] for k in ("Add", "Avv_t", "Avv_mag", "Apv_t", "Apv_mag", "App", "Avp"))
 
     # displacement pair values: dd_db[3e + i] = Add[3r + i, 3b + i], i.e. a0_ab = dd_db / rowscale_a is the assembled entry
     nadj_ptr, nadj = A("nadj_ptr"), A("nadj").astype(np.int64)

@@ -567,3 +567,162 @@ def test_task_table_restatement_is_the_reference_solve():
     np.testing.assert_allclose(x, solve(rhs), rtol=0, atol=1e-12 * np.abs(x).max())
     assert np.linalg.norm(A @ x - rhs) <= 1e-5 * np.linalg.norm(rhs)
     assert (ks.bcr_task_apply(tasks, a32, rhs, absolute=True) >= np.abs(x)).all()
+
+
+# ---- the field split, the Schur complement and the pressure step (kernel_shim.block_structure ... power_lmax) ----------------------
+def _product_cases():
+    import test_gpu_product_kernels as tp
+    return tp.CASES
+
+
+@pytest.mark.parametrize("name", ["N1_V1", "N5_V3", "N8_V0", "N37_V20", "N1100_V400", "N70001_V9001"])
+def test_field_blocks_reassemble_to_the_monolithic_matrix(name):
+    """extract_blocks followed by assemble_blocks (K undone) gives back every entry except the pressure columns of the d rows,
+    which no block holds"""
+    N2, V, kw = _product_cases()[name]
+    rng = np.random.default_rng(sum(map(ord, name)))
+    g = ks.mono_graph(N2, V, rng, **kw)
+    rowptr, cols, _ = ks.expand_cols(N2, *g)
+    A = rng.uniform(-1, 1, int(rowptr[-1]))
+    solid = (rng.random(N2) < 0.3).astype(np.int32)
+    st = ks.block_structure(N2, V, g)
+    b = ks.extract_blocks(N2, V, g, A, solid, 0.37)
+    back = ks.assemble_blocks(N2, V, g, st, b, solid, 0.37)
+    row = np.repeat(np.arange(6 * N2 + V), np.diff(rowptr))
+    held = ~((row < 6 * N2) & (row % 6 < 3) & (cols >= 6 * N2))
+    assert np.array_equal(np.isnan(back), ~held)
+    # exact off the solid columns; on them (e_v + k e_d) - k e_d rounds twice
+    err = np.abs(back[held] - A[held])
+    assert err.max(initial=0.0) <= 4 * np.finfo(np.float64).eps * (1 + 0.37)
+    scol = np.zeros(6 * N2 + V, dtype=bool)
+    scol[:6 * N2] = np.repeat(solid != 0, 6) & (np.arange(6 * N2) % 6 >= 3)
+    exact = held & ~(scol[cols] & ((row >= 6 * N2) | (row % 6 >= 3)))
+    assert np.array_equal(back[exact], A[exact])
+    # the structure is a partition: the blocks' sizes add up to the entries held
+    sizes = 2 * len(st["cols3"]) * 2 + len(st["cols_vp"]) + 2 * len(st["cols_pv"]) + len(st["cols_pp"])
+    assert sizes == held.sum()
+
+
+def test_schur_restatement_is_the_dense_complement():
+    import scipy.sparse as sp
+    rng = np.random.default_rng(2)
+    N2, V = 60, 25
+    g, _ = ks.shaped_graph(N2, V, rng, [(17, 9, True), (16, 0, False)])
+    rowptr, _, _ = ks.expand_cols(N2, *g)
+    A = rng.uniform(-1, 1, int(rowptr[-1]))
+    A[::11] = 0.0
+    dpos = ks.expand_cols(N2, *g)[2]
+    A[dpos[dpos >= 0]] = rng.uniform(0.5, 2.0, (dpos >= 0).sum())
+    solid = (rng.random(N2) < 0.3).astype(np.int32)
+    st = ks.block_structure(N2, V, g)
+    b = ks.extract_blocks(N2, V, g, A, solid, 0.37)
+    sr, sc = ks.schur_pattern(V, st)
+    assert all(np.all(np.diff(sc[sr[q]:sr[q + 1]]) > 0) for q in range(V))
+    S, mag, L, over = ks.schur_full(V, st, sr, sc, b["Apv"], b["App"], b["Avp"], b["Avv"])
+    m = lambda ptr, col, v, sh: sp.csr_matrix((v, col, ptr), shape=sh).toarray()      # noqa: E731
+    Apv, Avp = m(st["rowptr_pv"], st["cols_pv"], b["Apv"], (V, 3 * N2)), m(st["rowptr_vp"], st["cols_vp"], b["Avp"], (3 * N2, V))
+    dense = m(st["rowptr_pp"], st["cols_pp"], b["App"], (V, V)) - Apv @ np.diag(1.0 / b["Avv"][st["diagpos3"]]) @ Avp
+    assert not len(over) and not np.allclose(dense, dense.T)
+    got = m(sr, sc, S, (V, V))
+    assert np.abs(got - dense).max() <= 64 * np.finfo(np.float64).eps * mag.max()
+    assert np.all(dense[m(sr, sc, np.ones(len(sc)), (V, V)) == 0] == 0.0), "the pattern misses an entry of the complement"
+    assert L.max() > 8 and np.all(mag >= np.abs(S))
+
+
+def test_ripple_is_the_hash_of_the_kernel_comment():
+    """h = i * 0x9E3779B97F4A7C15, h ^= h >> 29, h *= 0xBF58476D1CE4E5B9, h ^= h >> 32 in 64-bit arithmetic, here with Python's
+    unbounded integers reduced by hand"""
+    M = (1 << 64) - 1
+    ref = []
+    for i in range(6):
+        h = (i * 0x9E3779B97F4A7C15) & M
+        h ^= h >> 29
+        h = (h * 0xBF58476D1CE4E5B9) & M
+        h ^= h >> 32
+        ref.append((h & 0xFFFF) / 65535.0 - 0.5)
+    x = ks.ripple(100000)
+    assert x[0] == -0.5 and np.array_equal(x[:6], np.array(ref))
+    assert x.min() >= -0.5 and x.max() <= 0.5 and abs(x.mean()) < 0.01
+    mask = (np.arange(100000) % 3 == 0).astype(np.float64)
+    assert np.array_equal(ks.ripple(100000, mask), mask * x)
+
+
+def test_component_diagonal_restatements():
+    rng = np.random.default_rng(4)
+    N2, V = 40, 12
+    g, _ = ks.shaped_graph(N2, V, rng, [(17, 9, True)])
+    st = ks.block_structure(N2, V, g)
+    npairs = int(g[0][-1])
+    vals = rng.uniform(-1, 1, 9 * npairs)
+    db, off = ks.db_extract(N2, g, st, vals)
+    assert off
+    # the dense 3 N2 x 3 N2 matrix of db is the component-diagonal part of the dense matrix of vals
+    import scipy.sparse as sp
+    D = sp.csr_matrix((vals, st["cols3"], st["rowptr3"]), shape=(3 * N2, 3 * N2)).toarray()
+    keep = (np.arange(3 * N2)[:, None] % 3) == (np.arange(3 * N2)[None, :] % 3)
+    x = rng.standard_normal(3 * N2)
+    y, S, L = ks.db_terms(N2, g, db, x)
+    assert np.allclose(y, (D * keep) @ x, rtol=0, atol=1e-13) and np.all(S >= np.abs(y) - 1e-15)
+    assert ks.db_extract(N2, g, st, np.where(keep[np.repeat(np.arange(3 * N2), np.diff(st["rowptr3"])), st["cols3"]], vals, 0.0))[1] is False
+    db0 = db.reshape(-1, 3).copy()
+    db0[g[0][5]:g[0][6]] = 0.0
+    m = ks.rowmask(N2, g, db0.ravel())
+    assert m[5] == 0 and m.sum() == N2 - 1
+    # chat: identity rows, the reference component, the spread
+    r = np.repeat(np.arange(N2), np.diff(g[0]))
+    isd = g[1] == r
+    c = np.where(isd, 1.0, rng.uniform(0.5, 2, npairs))
+    dbc = c[:, None] * np.array([1.0, 2.0, 4.0])
+    dbc[(r == 3) & ~isd, 0] = 0.0                      # node 3: component 0 is an identity row, the reference is component 1
+    dbc[(r == 4) & ~isd] = 0.0                         # node 4: all identity
+    chat, flag, spread = ks.chat_extract(N2, g, dbc.ravel())
+    assert np.array_equal(chat, np.where((r == 4), isd.astype(float), c)) and spread.max() == 0.0
+    assert flag.reshape(-1, 3)[3].tolist() == [1, 0, 0] and flag.reshape(-1, 3)[4].tolist() == [1, 1, 1]
+    e = np.flatnonzero((r == 7) & ~isd)[0]
+    dbc[e, 2] *= 1 + 1e-6
+    assert 1e-7 < ks.chat_extract(N2, g, dbc.ravel())[2].max() < 1e-5
+
+
+def test_power_iteration_restatement_finds_the_largest_eigenvalue():
+    rng = np.random.default_rng(5)
+    n = 50
+    Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+    lam = np.linspace(0.1, 1.0, n)
+    lam[-1] = 3.0
+    A = Q @ np.diag(lam) @ Q.T
+    d = np.full(n, 2.0)
+    got = ks.power_lmax(lambda x: A @ x, lambda y: y / d, n)
+    assert abs(got - 1.5) < 1e-6
+    mask = (np.arange(n) < 30).astype(np.float64)
+    got = ks.power_lmax(lambda x: A @ x, lambda y: mask * y / d, n, mask)
+    assert abs(got - np.abs(np.linalg.eigvals((A / d[:, None])[:30, :30])).max()) < 1e-3
+    assert abs(ks.power_lmax(lambda x: A.astype(np.longdouble) @ x, lambda y: y / d, n, dtype=np.longdouble) - 1.5) < 1e-6
+
+
+def test_the_block_cases_reach_the_edges():
+    import test_gpu_block_kernels as tb
+    c = tb.graph_case("N700_V300")
+    deg, pdeg = np.diff(c["g"][0]), np.diff(c["g"][2])
+    assert {1, 15, 16, 17, 47, 48, 49, 63, 64, 65, 100} <= set(deg.tolist())
+    assert {0, 1, 7, 8, 9, 17, 24} <= set(pdeg.tolist())
+    vdeg = deg[c["g"][4]]                                  # k_pres_rhs32: the strips a pressure row takes
+    for lo, hi in ((1, 16), (17, 48), (49, 64), (65, 1000)):
+        assert ((vdeg >= lo) & (vdeg <= hi)).any()
+    assert [tb.CASES[k][0] for k in ("N1_V1", "N31_V9", "N32_V32", "N33_V17")] == [1, 31, 32, 33]
+    for name, (covered, size) in tb.CAPS.items():
+        assert size > covered, name
+    # the over-limit Schur row exists in the case meant to have one and in no other
+    for name in tb.CASES:
+        cc = tb.graph_case(name)
+        assert np.diff(ks.schur_pattern(cc["V"], cc["st"])[0]).max(initial=0) <= ks.SCHUR_ROW_LIMIT
+    for longest, n_over in ((1024, 0), (1025, 1)):
+        N2, g = tb.limit_graph(longest)
+        lens = np.diff(ks.schur_pattern(N2, ks.block_structure(N2, N2, g))[0])
+        assert lens[0] == 1024 and lens[1] == longest and (lens > ks.SCHUR_ROW_LIMIT).sum() == n_over
+    # the solid sets: none, all, about a tenth, the heavy nodes
+    for kind, lo, hi in (("none", 0, 0), ("all", 700, 700), ("tenth", 40, 110), ("heavy", 8, 40)):
+        s = tb.blocks_case("N700_V300", kind)["solid"]
+        assert lo <= s.sum() <= hi, kind
+    assert np.all(deg[tb.blocks_case("N700_V300", "heavy")["solid"] != 0] >= 47)
+    b = tb.blocks_case("N700_V300")["b"]
+    assert (b["Apv"] == 0).any() and np.signbit(b["Avp"][b["Avp"] == 0]).any()

@@ -75,6 +75,7 @@ void launch_block_structure(hipStream_t st, int64_t N2, int64_t V, const int64_t
   const unsigned g3 = (unsigned)((3 * N2 + 1 + 255) / 256);
   hipLaunchKernelGGL(k_b3_structure, dim3(g3), dim3(256), 0, st, N2, nadj_ptr, nadj, rowptr3, cols3, diagpos3);
   hipLaunchKernelGGL(k_vp_structure, dim3(g3), dim3(256), 0, st, N2, padj_ptr, padj, rowptr_vp, cols_vp);
+  if (V <= 0) return;                      // no pressure rows, no A_pv structure
   hipLaunchKernelGGL(k_pv_structure, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, V, vrank, nadj_ptr, nadj,
                      rowptr_pv, cols_pv);
 }
@@ -199,6 +200,7 @@ void launch_schur_full(hipStream_t st, int64_t V, const int64_t* s_rowptr, const
                        const int64_t* rowptr_pv, const double* Apv, const int64_t* rowptr_pp, const double* App,
                        const int64_t* rowptr_vp, const double* Avp, const int64_t* diagpos3, const double* Avv, double* S,
                        int32_t* flags) {
+  if (V <= 0) return;                      // no pressure rows: an empty grid is no valid launch
   const unsigned blocks = (unsigned)(V < 32768 ? V : 32768);
   hipLaunchKernelGGL(k_schur_full, dim3(blocks), dim3(64), 0, st, V, s_rowptr, s_cols, vrank, nadj_ptr, nadj, padj_ptr, padj,
                      rowptr_pv, Apv, rowptr_pp, App, rowptr_vp, Avp, diagpos3, Avv, S, flags);
@@ -353,6 +355,7 @@ void launch_vel_correct32(hipStream_t st, int64_t N2, const int64_t* padj_ptr, c
 }
 void launch_pres_rhs32(hipStream_t st, int64_t V, const int32_t* vrank, const int64_t* nadj_ptr, const int32_t* nadj,
                        const int64_t* rowptr_pv, const float* apv, const double* w, const double* c, double* y) {
+  if (V <= 0) return;
   int64_t blocks = (V + 15) / 16;
   if (blocks > 32768) blocks = 32768;
   hipLaunchKernelGGL(k_pres_rhs32, dim3((unsigned)blocks), dim3(256), 0, st, V, vrank, nadj_ptr, nadj, rowptr_pv, apv, w, c, y);
@@ -381,6 +384,7 @@ __global__ __launch_bounds__(256) void k_pres_rows(int64_t V, const int64_t* __r
 void launch_pres_rows(hipStream_t st, int64_t V, const int64_t* rowptr_pp, const int32_t* cols_pp, const double* App,
                       const double* x, double alpha, const int64_t* rowptr_pv, const int32_t* cols_pv, const double* Apv,
                       const double* w, double beta, const double* c, double gamma, double* y) {
+  if (V <= 0) return;
   int64_t blocks = (V + 3) / 4;
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(k_pres_rows, dim3((unsigned)blocks), dim3(256), 0, st, V, rowptr_pp, cols_pp, App, x, alpha, rowptr_pv,

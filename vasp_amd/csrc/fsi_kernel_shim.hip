@@ -1057,6 +1057,369 @@ int shim_bcr_run(int64_t nc, const int64_t* cptr, const int32_t* ccol, int nsets
   return 0;
 }
 
+// ---- fsi_block.hip: field split, Schur complement and the pressure step (tests/test_gpu_block_kernels.py) --------------------
+// Every OUTPUT array of the entries below is SHIM_TAIL elements longer than the launch needs: the caller fills the tail with a
+// sentinel, the shim uploads and returns it with the rest, and a kernel that writes past its end shows there.
+static constexpr size_t SHIM_TAIL = 8;
+int shim_tail() { return (int)SHIM_TAIL; }
+// launch_block_structure (k_b3_structure, k_vp_structure, k_pv_structure): rowptr3, rowptr_vp [3 N2 + 1], cols3 [9 pairs],
+// diagpos3 [3 N2], cols_vp [3 ppairs], cols_pv [rowptr_pv[V]]; rowptr_pv [V + 1] is an input
+int shim_block_structure(int64_t N2, int64_t V, const int64_t* nadj_ptr, const int32_t* nadj, const int64_t* padj_ptr, const int32_t* padj,
+                         const int32_t* vrank, int64_t* rowptr3, int32_t* cols3, int64_t* diagpos3, int64_t* rowptr_vp, int32_t* cols_vp,
+                         const int64_t* rowptr_pv, int32_t* cols_pv) {
+  Call c;
+  const int64_t np = nadj_ptr[N2], pp = padj_ptr[N2];
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const int32_t* dn = c.in(nadj, (size_t)np);
+  const int64_t* dpp = c.in(padj_ptr, (size_t)N2 + 1);
+  const int32_t* dpa = c.in(padj, (size_t)pp);
+  const int32_t* dvr = c.in(vrank, (size_t)V);
+  int64_t* dr3 = c.io(rowptr3, (size_t)(3 * N2 + 1) + SHIM_TAIL);
+  int32_t* dc3 = c.io(cols3, (size_t)(9 * np) + SHIM_TAIL);
+  int64_t* dd3 = c.io(diagpos3, (size_t)(3 * N2) + SHIM_TAIL);
+  int64_t* drvp = c.io(rowptr_vp, (size_t)(3 * N2 + 1) + SHIM_TAIL);
+  int32_t* dcvp = c.io(cols_vp, (size_t)(3 * pp) + SHIM_TAIL);
+  const int64_t* drpv = c.in(rowptr_pv, (size_t)V + 1);
+  int32_t* dcpv = c.io(cols_pv, (size_t)rowptr_pv[V] + SHIM_TAIL);
+  SHIM_RUN(c, "launch_block_structure",
+           launch_block_structure(c.st, N2, V, dnp, dn, dpp, dpa, dvr, dr3, dc3, dd3, drvp, dcvp, drpv, dcpv));
+}
+// A: the monolithic values on rowptr [6 N2 + V + 1]; Add, Adv, Avv [9 pairs], Avp [3 ppairs], Apv [rowptr_pv[V]], App [rowptr_pp[V]]
+int shim_extract_blocks(int64_t N2, int64_t V, double ktheta, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr,
+                        const int32_t* nadj, const int64_t* padj_ptr, const int32_t* vrank, const int32_t* node_solid,
+                        const int64_t* rowptr3, const int64_t* rowptr_vp, const int64_t* rowptr_pv, const int64_t* rowptr_pp, double* Add,
+                        double* Adv, double* Avv, double* Avp, double* Apv, double* App) {
+  Call c;
+  const int64_t n = 6 * N2 + V, np = nadj_ptr[N2], pp = padj_ptr[N2];
+  const int64_t* drp = c.in(rowptr, (size_t)n + 1);
+  const double* dA = c.in(A, (size_t)rowptr[n]);
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const int32_t* dn = c.in(nadj, (size_t)np);
+  const int64_t* dpp = c.in(padj_ptr, (size_t)N2 + 1);
+  const int32_t* dvr = c.in(vrank, (size_t)V);
+  const int32_t* dso = c.in(node_solid, (size_t)N2);
+  const int64_t* dr3 = c.in(rowptr3, (size_t)(3 * N2 + 1));
+  const int64_t* drvp = c.in(rowptr_vp, (size_t)(3 * N2 + 1));
+  const int64_t* drpv = c.in(rowptr_pv, (size_t)V + 1);
+  const int64_t* drpp = c.in(rowptr_pp, (size_t)V + 1);
+  double* dAdd = c.io(Add, (size_t)(9 * np) + SHIM_TAIL);
+  double* dAdv = c.io(Adv, (size_t)(9 * np) + SHIM_TAIL);
+  double* dAvv = c.io(Avv, (size_t)(9 * np) + SHIM_TAIL);
+  double* dAvp = c.io(Avp, (size_t)(3 * pp) + SHIM_TAIL);
+  double* dApv = c.io(Apv, (size_t)rowptr_pv[V] + SHIM_TAIL);
+  double* dApp = c.io(App, (size_t)rowptr_pp[V] + SHIM_TAIL);
+  SHIM_RUN(c, "launch_extract_blocks",
+           launch_extract_blocks(c.st, N2, V, ktheta, drp, dA, dnp, dn, dpp, dvr, dso, dr3, drvp, drpv, drpp, dAdd, dAdv, dAvv, dAvp,
+                                 dApv, dApp));
+}
+// vals [9 pairs] on rowptr3; db [3 pairs]; flags [4]
+int shim_extract_db(int64_t N2, const int64_t* nadj_ptr, const int64_t* rowptr3, const double* vals, double* db, int32_t* flags,
+                    int check) {
+  Call c;
+  const int64_t np = nadj_ptr[N2];
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const int64_t* dr3 = c.in(rowptr3, (size_t)(3 * N2 + 1));
+  const double* dv = c.in(vals, (size_t)(9 * np));
+  double* ddb = c.io(db, (size_t)(3 * np) + SHIM_TAIL);
+  int32_t* df = c.io(flags, 4);
+  SHIM_RUN(c, "launch_extract_db", launch_extract_db(c.st, N2, np, dnp, dr3, dv, ddb, df, check));
+}
+// db [3 pairs]; chat [pairs]; rowflag [3 N2]; flags [4]
+int shim_extract_chat(int64_t N2, const int64_t* nadj_ptr, const int32_t* nadj, const double* db, float* chat, uint8_t* rowflag,
+                      int32_t* flags) {
+  Call c;
+  const int64_t np = nadj_ptr[N2];
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const int32_t* dn = c.in(nadj, (size_t)np);
+  const double* ddb = c.in(db, (size_t)(3 * np));
+  float* dc = c.io(chat, (size_t)np + SHIM_TAIL);
+  uint8_t* drf = c.io(rowflag, (size_t)(3 * N2) + SHIM_TAIL);
+  int32_t* df = c.io(flags, 4);
+  SHIM_RUN(c, "launch_extract_chat", launch_extract_chat(c.st, N2, dnp, dn, ddb, dc, drf, df));
+}
+int shim_db_rowmask(int64_t N2, const int64_t* nadj_ptr, const double* db, uint8_t* rowmask) {
+  Call c;
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const double* ddb = c.in(db, (size_t)(3 * nadj_ptr[N2]));
+  uint8_t* dm = c.io(rowmask, (size_t)N2 + SHIM_TAIL);
+  SHIM_RUN(c, "launch_db_rowmask", launch_db_rowmask(c.st, N2, dnp, ddb, dm));
+}
+int shim_mask_outside(int64_t N2, const uint8_t* rowmask, const int32_t* node_set, int32_t* flags) {
+  Call c;
+  const uint8_t* dm = c.in(rowmask, (size_t)N2);
+  const int32_t* ds = c.in(node_set, (size_t)N2);
+  int32_t* df = c.io(flags, 4);
+  SHIM_RUN(c, "launch_mask_outside", launch_mask_outside(c.st, N2, dm, ds, df));
+}
+int shim_to_f32(int64_t n, const double* a, float* b) {
+  Call c;
+  const double* da = c.in(a, (size_t)n);
+  float* db = c.io(b, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_to_f32", launch_to_f32(c.st, n, da, db));
+}
+int shim_gather_vals(int64_t n, const int64_t* pos, const double* src, int64_t nsrc, double* dst) {
+  for (int64_t i = 0; i < n; ++i)
+    if (pos[i] < 0 || pos[i] >= nsrc) { g_err = "shim_gather_vals: position " + std::to_string(i) + " outside src"; return 3; }
+  Call c;
+  const int64_t* dp = c.in(pos, (size_t)n);
+  const double* ds = c.in(src, (size_t)nsrc);
+  double* dd = c.io(dst, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_gather_vals", launch_gather_vals(c.st, n, dp, ds, dd));
+}
+// sb_row [nb] (row index < nS into sb_stride [nS]), sb_src [nb]; Avv [nA]; vals [9 nb]
+int shim_sb_gather(int64_t nb, int64_t nS, const int32_t* sb_row, const int64_t* sb_src, const int32_t* sb_stride, const double* Avv,
+                   int64_t nA, float* vals) {
+  for (int64_t b = 0; b < nb; ++b) {
+    const bool ok = sb_row[b] >= 0 && sb_row[b] < nS && sb_src[b] >= 0 && sb_stride[sb_row[b]] >= 0 &&
+                    sb_src[b] + 2 * (int64_t)sb_stride[sb_row[b]] + 2 < nA;
+    if (!ok) { g_err = "shim_sb_gather: block " + std::to_string(b) + " reads outside Avv"; return 3; }
+  }
+  Call c;
+  const int32_t* dr = c.in(sb_row, (size_t)nb);
+  const int64_t* ds = c.in(sb_src, (size_t)nb);
+  const int32_t* dst = c.in(sb_stride, (size_t)nS);
+  const double* dA = c.in(Avv, (size_t)nA);
+  float* dv = c.io(vals, (size_t)(9 * nb) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_sb_gather", launch_sb_gather(c.st, nb, dr, ds, dst, dA, dv));
+}
+// S [s_rowptr[V]]; flags [4]; the block arrays as launch_block_structure / launch_extract_blocks lay them out
+int shim_schur_full(int64_t V, int64_t N2, const int64_t* s_rowptr, const int32_t* s_cols, const int32_t* vrank, const int64_t* nadj_ptr,
+                    const int32_t* nadj, const int64_t* padj_ptr, const int32_t* padj, const int64_t* rowptr_pv, const double* Apv,
+                    const int64_t* rowptr_pp, const double* App, const int64_t* rowptr_vp, const double* Avp, const int64_t* diagpos3,
+                    const double* Avv, double* S, int32_t* flags) {
+  Call c;
+  const int64_t np = nadj_ptr[N2], pp = padj_ptr[N2];
+  const int64_t* dsr = c.in(s_rowptr, (size_t)V + 1);
+  const int32_t* dsc = c.in(s_cols, (size_t)s_rowptr[V]);
+  const int32_t* dvr = c.in(vrank, (size_t)V);
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const int32_t* dn = c.in(nadj, (size_t)np);
+  const int64_t* dpp = c.in(padj_ptr, (size_t)N2 + 1);
+  const int32_t* dpa = c.in(padj, (size_t)pp);
+  const int64_t* drpv = c.in(rowptr_pv, (size_t)V + 1);
+  const double* dApv = c.in(Apv, (size_t)rowptr_pv[V]);
+  const int64_t* drpp = c.in(rowptr_pp, (size_t)V + 1);
+  const double* dApp = c.in(App, (size_t)rowptr_pp[V]);
+  const int64_t* drvp = c.in(rowptr_vp, (size_t)(3 * N2 + 1));
+  const double* dAvp = c.in(Avp, (size_t)(3 * pp));
+  const int64_t* dd3 = c.in(diagpos3, (size_t)(3 * N2));
+  const double* dAvv = c.in(Avv, (size_t)(9 * np));
+  double* dS = c.io(S, (size_t)s_rowptr[V] + SHIM_TAIL);
+  int32_t* df = c.io(flags, 4);
+  SHIM_RUN(c, "launch_schur_full",
+           launch_schur_full(c.st, V, dsr, dsc, dvr, dnp, dn, dpp, dpa, drpv, dApv, drpp, dApp, drvp, dAvp, dd3, dAvv, dS, df));
+}
+// apv [rowptr_pv[V]] floats, w [3 N2], c [V], y [V]
+int shim_pres_rhs32(int64_t V, int64_t N2, const int32_t* vrank, const int64_t* nadj_ptr, const int32_t* nadj, const int64_t* rowptr_pv,
+                    const float* apv, const double* w, const double* cc, double* y) {
+  Call c;
+  const int32_t* dvr = c.in(vrank, (size_t)V);
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const int32_t* dn = c.in(nadj, (size_t)nadj_ptr[N2]);
+  const int64_t* drpv = c.in(rowptr_pv, (size_t)V + 1);
+  const float* da = c.in(apv, (size_t)rowptr_pv[V]);
+  const double* dw = c.in(w, (size_t)(3 * N2));
+  const double* dc = c.in(cc, (size_t)V);
+  double* dy = c.io(y, (size_t)V + SHIM_TAIL);
+  SHIM_RUN(c, "launch_pres_rhs32", launch_pres_rhs32(c.st, V, dvr, dnp, dn, drpv, da, dw, dc, dy));
+}
+// avp [3 ppairs] floats, dp [V], dinv [3 N2], vs [3 N2] (may be null), dv [3 N2]
+int shim_vel_correct32(int64_t N2, int64_t V, const int64_t* padj_ptr, const int32_t* padj, const float* avp, const double* dp,
+                       const double* dinv, const double* vs, double* dv) {
+  Call c;
+  const int64_t pp = padj_ptr[N2];
+  const int64_t* dpp = c.in(padj_ptr, (size_t)N2 + 1);
+  const int32_t* dpa = c.in(padj, (size_t)pp);
+  const float* da = c.in(avp, (size_t)(3 * pp));
+  const double* ddp = c.in(dp, (size_t)V);
+  const double* ddi = c.in(dinv, (size_t)(3 * N2));
+  const double* dvs = c.in(vs, (size_t)(3 * N2));
+  double* ddv = c.io(dv, (size_t)(3 * N2) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_vel_correct32", launch_vel_correct32(c.st, N2, dpp, dpa, da, ddp, ddi, dvs, ddv));
+}
+// CSR (rowptr [n3 + 1], cols, vals) x dp [ndp]; Avv [nA] read at diagpos3 [n3] when dinv [n3] is null; vs [n3] may be null
+int shim_vel_correct(int64_t n3, const int64_t* rowptr, const int32_t* cols, const double* vals, const double* dp, int64_t ndp,
+                     const int64_t* diagpos3, const double* Avv, int64_t nA, const double* vs, double* dv, const double* dinv) {
+  Call c;
+  const int64_t* drp = c.in(rowptr, (size_t)n3 + 1);
+  const int32_t* dc = c.in(cols, (size_t)rowptr[n3]);
+  const double* dvl = c.in(vals, (size_t)rowptr[n3]);
+  const double* ddp = c.in(dp, (size_t)ndp);
+  const int64_t* dd3 = c.in(diagpos3, (size_t)n3);
+  const double* dA = c.in(Avv, (size_t)nA);
+  const double* dvs = c.in(vs, (size_t)n3);
+  double* ddv = c.io(dv, (size_t)n3 + SHIM_TAIL);
+  const double* ddi = c.in(dinv, (size_t)n3);
+  SHIM_RUN(c, "launch_vel_correct", launch_vel_correct(c.st, n3, drp, dc, dvl, ddp, dd3, dA, dvs, ddv, ddi));
+}
+// y [V] = alpha App x + beta Apv w + gamma c; x [V], w [nw], c [V] (x, w, c may be null where their factor is zero)
+int shim_pres_rows(int64_t V, const int64_t* rowptr_pp, const int32_t* cols_pp, const double* App, const double* x, double alpha,
+                   const int64_t* rowptr_pv, const int32_t* cols_pv, const double* Apv, const double* w, int64_t nw, double beta,
+                   const double* cc, double gamma, double* y) {
+  Call c;
+  const int64_t* drpp = c.in(rowptr_pp, (size_t)V + 1);
+  const int32_t* dcpp = c.in(cols_pp, (size_t)rowptr_pp[V]);
+  const double* dApp = c.in(App, (size_t)rowptr_pp[V]);
+  const double* dx = c.in(x, (size_t)V);
+  const int64_t* drpv = c.in(rowptr_pv, (size_t)V + 1);
+  const int32_t* dcpv = c.in(cols_pv, (size_t)rowptr_pv[V]);
+  const double* dApv = c.in(Apv, (size_t)rowptr_pv[V]);
+  const double* dw = c.in(w, (size_t)nw);
+  const double* dc = c.in(cc, (size_t)V);
+  double* dy = c.io(y, (size_t)V + SHIM_TAIL);
+  SHIM_RUN(c, "launch_pres_rows",
+           launch_pres_rows(c.st, V, drpp, dcpp, dApp, dx, alpha, drpv, dcpv, dApv, dw, beta, dc, gamma, dy));
+}
+// mask [n] may be null; A [nA] read at diagpos [n]; x, r, d [n]
+int shim_cheb_init(int64_t n, const double* mask, const double* rhs, const int64_t* diagpos, const double* A, int64_t nA,
+                   double inv_theta, double* x, double* r, double* d) {
+  Call c;
+  const double* dm = c.in(mask, (size_t)n);
+  const double* drh = c.in(rhs, (size_t)n);
+  const int64_t* ddp = c.in(diagpos, (size_t)n);
+  const double* dA = c.in(A, (size_t)nA);
+  double* dx = c.io(x, (size_t)n + SHIM_TAIL);
+  double* dr = c.io(r, (size_t)n + SHIM_TAIL);
+  double* dd = c.io(d, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_cheb_init", launch_cheb_init(c.st, n, dm, drh, ddp, dA, inv_theta, dx, dr, dd));
+}
+int shim_cheb_step(int64_t n, const double* mask, const double* t, const int64_t* diagpos, const double* A, int64_t nA, double c1,
+                   double c2, double* x, double* r, double* d) {
+  Call c;
+  const double* dm = c.in(mask, (size_t)n);
+  const double* dt = c.in(t, (size_t)n);
+  const int64_t* ddp = c.in(diagpos, (size_t)n);
+  const double* dA = c.in(A, (size_t)nA);
+  double* dx = c.io(x, (size_t)n + SHIM_TAIL);
+  double* dr = c.io(r, (size_t)n + SHIM_TAIL);
+  double* dd = c.io(d, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_cheb_step", launch_cheb_step(c.st, n, dm, dt, ddp, dA, c1, c2, dx, dr, dd));
+}
+// list [nl] node ranks < N2; db [3 pairs]; rowmask [N2] may be null; x, y [3 N2] (y in place)
+int shim_db_rows_sub(int64_t nl, int64_t N2, const int32_t* list, const int64_t* nadj_ptr, const int32_t* nadj, const double* db,
+                     const uint8_t* rowmask, const double* x, double* y) {
+  for (int64_t i = 0; i < nl; ++i)
+    if (list[i] < 0 || list[i] >= N2) { g_err = "shim_db_rows_sub: list entry " + std::to_string(i) + " is no node"; return 3; }
+  Call c;
+  const int64_t np = nadj_ptr[N2];
+  const int32_t* dl = c.in(list, (size_t)nl);
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const int32_t* dn = c.in(nadj, (size_t)np);
+  const double* ddb = c.in(db, (size_t)(3 * np));
+  const uint8_t* dm = c.in(rowmask, (size_t)N2);
+  const double* dx = c.in(x, (size_t)(3 * N2));
+  double* dy = c.io(y, (size_t)(3 * N2) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_db_rows_sub", launch_db_rows_sub(c.st, nl, dl, dnp, dn, ddb, dm, dx, dy));
+}
+int shim_spmv_db(int64_t N2, const int64_t* nadj_ptr, const int32_t* nadj, const double* db, const double* x, double* y,
+                 const uint8_t* rowmask) {
+  Call c;
+  const int64_t np = nadj_ptr[N2];
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const int32_t* dn = c.in(nadj, (size_t)np);
+  const double* ddb = c.in(db, (size_t)(3 * np));
+  const double* dx = c.in(x, (size_t)(3 * N2));
+  double* dy = c.io(y, (size_t)(3 * N2) + SHIM_TAIL);
+  const uint8_t* dm = c.in(rowmask, (size_t)N2);
+  SHIM_RUN(c, "launch_spmv_db", launch_spmv_db(c.st, N2, dnp, dn, ddb, dx, dy, dm));
+}
+// y [n] = b - A x on a CSR matrix with columns < nx
+int shim_residual_csr(int64_t n, const int64_t* rowptr, const int32_t* cols, const double* vals, const double* x, int64_t nx,
+                      const double* b, double* y) {
+  Call c;
+  const int64_t* drp = c.in(rowptr, (size_t)n + 1);
+  const int32_t* dc = c.in(cols, (size_t)rowptr[n]);
+  const double* dv = c.in(vals, (size_t)rowptr[n]);
+  const double* dx = c.in(x, (size_t)nx);
+  const double* db = c.in(b, (size_t)n);
+  double* dy = c.io(y, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_residual_csr", launch_residual_csr(c.st, n, drp, dc, dv, dx, db, dy));
+}
+// rows [nrows] < ny; ptr [nrows + 1]; col, src [ptr[nrows]] (col < nx, src < nvals); b, y [ny] (y in place)
+int shim_residual_rows(int64_t nrows, const int32_t* rows, const int64_t* ptr, const int32_t* col, const int64_t* src, const double* vals,
+                       int64_t nvals, const double* x, int64_t nx, const double* b, double* y, int64_t ny) {
+  for (int64_t i = 0; i < nrows; ++i)
+    if (rows[i] < 0 || rows[i] >= ny) { g_err = "shim_residual_rows: row " + std::to_string(i) + " outside y"; return 3; }
+  const int64_t ne = nrows > 0 ? ptr[nrows] : 0;
+  for (int64_t t = 0; t < ne; ++t)
+    if (col[t] < 0 || col[t] >= nx || src[t] < 0 || src[t] >= nvals) { g_err = "shim_residual_rows: entry " + std::to_string(t) + " out of range"; return 3; }
+  Call c;
+  const int32_t* dr = c.in(rows, (size_t)nrows);
+  const int64_t* dp = c.in(ptr, (size_t)nrows + 1);
+  const int32_t* dc = c.in(col, (size_t)ne);
+  const int64_t* ds = c.in(src, (size_t)ne);
+  const double* dv = c.in(vals, (size_t)nvals);
+  const double* dx = c.in(x, (size_t)nx);
+  const double* db = c.in(b, (size_t)ny);
+  double* dy = c.io(y, (size_t)ny + SHIM_TAIL);
+  SHIM_RUN(c, "launch_residual_rows", launch_residual_rows(c.st, nrows, dr, dp, dc, ds, dv, dx, db, dy));
+}
+// r [6 N2 + V] -> rd, rv [3 N2], rp [V]
+int shim_split(int64_t N2, int64_t V, const double* r, double* rd, double* rv, double* rp) {
+  Call c;
+  const double* dr = c.in(r, (size_t)(6 * N2 + V));
+  double* drd = c.io(rd, (size_t)(3 * N2) + SHIM_TAIL);
+  double* drv = c.io(rv, (size_t)(3 * N2) + SHIM_TAIL);
+  double* drp = c.io(rp, (size_t)V + SHIM_TAIL);
+  SHIM_RUN(c, "launch_split", launch_split(c.st, N2, V, dr, drd, drv, drp));
+}
+int shim_merge(int64_t N2, int64_t V, const double* zd, const double* zv, const double* zp, double* z) {
+  Call c;
+  const double* dzd = c.in(zd, (size_t)(3 * N2));
+  const double* dzv = c.in(zv, (size_t)(3 * N2));
+  const double* dzp = c.in(zp, (size_t)V);
+  double* dz = c.io(z, (size_t)(6 * N2 + V) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_merge", launch_merge(c.st, N2, V, dzd, dzv, dzp, dz));
+}
+int shim_merge_f32d(int64_t N2, int64_t V, const float* xd4, const double* zv, const double* zp, double* z) {
+  Call c;
+  const float* dxd = c.in(xd4, (size_t)(4 * N2));
+  const double* dzv = c.in(zv, (size_t)(3 * N2));
+  const double* dzp = c.in(zp, (size_t)V);
+  double* dz = c.io(z, (size_t)(6 * N2 + V) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_merge_f32d", launch_merge_f32d(c.st, N2, V, dxd, dzv, dzp, dz));
+}
+// a [3 nn]; scale4 [4 nn] may be null; dinv4, x, r, d [4 nn]
+int shim_pad_init_f32(int64_t nn, const double* a, const float* scale4, const float* dinv4, float inv_theta, float* x, float* r,
+                      float* d) {
+  Call c;
+  const double* da = c.in(a, (size_t)(3 * nn));
+  const float* ds = c.in(scale4, (size_t)(4 * nn));
+  const float* ddi = c.in(dinv4, (size_t)(4 * nn));
+  float* dx = c.io(x, (size_t)(4 * nn) + SHIM_TAIL);
+  float* dr = c.io(r, (size_t)(4 * nn) + SHIM_TAIL);
+  float* dd = c.io(d, (size_t)(4 * nn) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_pad_init_f32", launch_pad_init_f32(c.st, nn, da, ds, ddi, inv_theta, dx, dr, dd));
+}
+int shim_pad_to_f32(int64_t nn, const double* a, const float* scale4, float* b) {
+  Call c;
+  const double* da = c.in(a, (size_t)(3 * nn));
+  const float* ds = c.in(scale4, (size_t)(4 * nn));
+  float* db = c.io(b, (size_t)(4 * nn) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_pad_to_f32", launch_pad_to_f32(c.st, nn, da, ds, db));
+}
+int shim_unpad_from_f32(int64_t nn, const float* a, double* b) {
+  Call c;
+  const float* da = c.in(a, (size_t)(4 * nn));
+  double* db = c.io(b, (size_t)(3 * nn) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_unpad_from_f32", launch_unpad_from_f32(c.st, nn, da, db));
+}
+int shim_mask_ripple(int64_t n, const double* mask, double* x) {
+  Call c;
+  const double* dm = c.in(mask, (size_t)n);
+  double* dx = c.io(x, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_mask_ripple", launch_mask_ripple(c.st, n, dm, dx));
+}
+// y [n] in place; A [nA] read at diagpos [n]
+int shim_mask_scale(int64_t n, const double* mask, const int64_t* diagpos, const double* A, int64_t nA, double* y) {
+  Call c;
+  const double* dm = c.in(mask, (size_t)n);
+  const int64_t* ddp = c.in(diagpos, (size_t)n);
+  const double* dA = c.in(A, (size_t)nA);
+  double* dy = c.io(y, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_mask_scale", launch_mask_scale(c.st, n, dm, ddp, dA, dy));
+}
+
 // ---- a live context's preconditioner arrays (FsiCtx of fsi_context.hpp, as the library was compiled) -----------------------
 // shim_ctx_info: N2, V, nS, sb_nblocks, tiled, tile_nodes, tile_max_nu, schur_tiled, schur_tile, s_tile_max_nu, sweeps_fp16,
 // a32_ptail, a32_tail_src, a32_tail_nnz, op32_ok, kry_fp32, drows_ok, mg_nc, mg_cnnz, mg_ready, sbmg_nc, sbmg_nblk, sbmg_ready,
@@ -1073,13 +1436,28 @@ int shim_ctx_info(const FsiCtx* ctx, int64_t* out, int nout) {
 // the factor of the solid columns' displacement entries folded into the velocity block (Avv~ = Avv + ktheta Avd, k_extract_blocks)
 double shim_ctx_ktheta(const FsiCtx* ctx) { return ctx->scheme.k * ctx->scheme.th0; }
 // the coarse levels' eigenvalue bounds: 0 mg_gersh, 1 sbmg_gersh (the row-sum bounds of the last rebuild), 2 mg_clmax, 3 sbmg_clmax
-// (what the Chebyshev intervals use); NaN for any other index
+// (what the Chebyshev intervals use); 4 .. 7 lmax_s, lmax_f, lmax_p, lmax_d (the fine blocks' intervals end there), 8 .. 11
+// cheb_kappa_s, _f, _p, _d, 12 .. 16 the flags dd_is_db, adv_is_db, dd_is_scalar, adv_solid_only, pv32_ok as 0 / 1; NaN for any
+// other index
 double shim_ctx_coarse(const FsiCtx* ctx, int which) {
   switch (which) {
     case 0: return ctx->mg_gersh;
     case 1: return ctx->sbmg_gersh;
     case 2: return ctx->mg_clmax;
     case 3: return ctx->sbmg_clmax;
+    case 4: return ctx->lmax_s;
+    case 5: return ctx->lmax_f;
+    case 6: return ctx->lmax_p;
+    case 7: return ctx->lmax_d;
+    case 8: return ctx->cheb_kappa_s;
+    case 9: return ctx->cheb_kappa_f;
+    case 10: return ctx->cheb_kappa_p;
+    case 11: return ctx->cheb_kappa_d;
+    case 12: return ctx->dd_is_db;
+    case 13: return ctx->adv_is_db;
+    case 14: return ctx->dd_is_scalar;
+    case 15: return ctx->adv_solid_only;
+    case 16: return ctx->pv32_ok;
     default: return std::nan("");
   }
 }
@@ -1098,7 +1476,13 @@ int shim_ctx_array(const FsiCtx* ctx, const char* name, void* host, int64_t* cou
                          E(mg_cfine),   E(mg_Ac),     E(mg_cc),   E(mg_d0),      E(mg_dcinv4),   E(mg_cflag),    E(sbmg_par),
                          E(sbmg_pw),    E(sbmg_chptr), E(sbmg_child), E(sbmg_chw), E(sbmg_cptr),  E(sbmg_ccol),   E(sbmg_cfine),
                          E(sbmg_cvals), E(sbmg_cbinv12), E(sbmg_flag), E(sbmg_cflag), E(sb_binv9), E(sb_dinv),   E(dd_dinv32),
-                         E(vvf_dinv32),  E(vv_rec32),   E(sb_rec32)};
+                         E(vvf_dinv32),  E(vv_rec32),   E(sb_rec32),
+                         E(rowptr3),    E(cols3),     E(diagpos3), E(rowptr_vp), E(cols_vp),     E(rowptr_pv),   E(cols_pv),
+                         E(rowptr_pp),  E(cols_pp),   E(Mdd.vals), E(Mvv.vals),  E(Adv),         E(Avp),         E(Apv),
+                         E(App),        E(Avp32),     E(Apv32),   E(vv_db),      E(adv_db),      E(dd_db32),     E(adv_rowmask),
+                         E(vv_dinv),    E(mask_f),    E(mask_s),  E(ss_vals),    E(ss_src),      E(ss_rowptr),   E(ss_cols),
+                         E(ss_diagpos), E(fs_rows),   E(fs_ptr),  E(fs_col),     E(fs_src),      E(sb_row),      E(sb_src),
+                         E(sb_stride),  E(s_diagpos)};
 #undef E
   for (const Entry& t : table) {
     if (std::strcmp(t.name, name) != 0) continue;
