@@ -347,6 +347,48 @@ int fsi_stress_averages(FsiCtx* ctx, double* out, int64_t* samples);
 /* Closes the session and frees its device memory (fsi_destroy does the same). */
 int fsi_stress_end(FsiCtx* ctx);
 
+/* ---- band-pass filtered fields and vibration amplitudes over a run (fsi_band.hip) -------------------------- */
+/* One session per quantity (0 = d, 1 = v, 2 = p); the three can be open together, and beside the hemodynamics and the
+ * stress / strain session.  Rows are (node, component) pairs, row = ncomp * i + component for the i-th listed node, ncomp = 3
+ * for d / v and 1 for p - a fetched frame is the (n, ncomp) array a Visualization file holds.  All data are FP64. */
+#define FSI_BAND_RAW 0
+#define FSI_BAND_FILTERED 1
+#define FSI_BAND_AMPLITUDE 2
+#define FSI_BAND_MAGNITUDE 3
+/* Replaces: create_transformed_matrix, the second pass over the Visualization files that builds the node x time matrix
+ * [REF src/vasp/postprocessing/postprocessing_h5py/postprocessing_h5py_common.py:154-409].  Opens a session on n listed nodes
+ * (P2 node ids for d / v, vertex ids for p); where nodes_b (nullable) is >= 0 the row is the mean of the two nodes' values (the
+ * pressure at an edge node of the save_deg 2 output).  capacity: frames the history can take.  The bytes of the history, the
+ * filtered series (capacity + 66 frames) and three work frames are compared with the free device memory: if less than 1/16
+ * of the device would stay free for the context, FSI_ERR_INVALID with both byte counts in fsi_last_error and nothing
+ * allocated - no paging, no truncation.  Replaces an open session of the quantity.  Not for partitioned contexts. */
+int fsi_band_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* nodes, const int32_t* nodes_b, int64_t capacity);
+/* Replaces: reading one frame of <quantity>.h5 [REF .../postprocessing_h5py_common.py:154-409, its frame loop]: the session's rows of
+ * dvp_["n"] go to the next frame of the history, stream-ordered behind the time step; the host does not wait.
+ * FSI_ERR_INVALID when the history is full. */
+int fsi_band_sample(FsiCtx* ctx, int32_t quantity);
+/* Replaces: the node loop of create_hi_pass_viz [REF .../create_hi_pass_viz.py:190-215] around butter_bandpass_filter
+ * [REF .../spectrograms.py:534-555]: scipy.signal.filtfilt(b, a, row) of every row over the frames recorded so far, in
+ * scipy's arithmetic (odd extension by padlen, transposed direct form II, zi scaled by the first extended / last forward
+ * sample), bit for bit.  ntaps = len(b) = len(a) in 2 .. 11, a[0] = 1, zi[ntaps - 1] = scipy.signal.lfilter_zi(b, a),
+ * padlen <= 33 and < the number of frames (where scipy raises).  The raw history is kept: another band can follow. */
+int fsi_band_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* b, const double* a, const double* zi,
+                    int32_t padlen);
+/* Replaces: calculate_windowed_rms [REF .../postprocessing_h5py_common.py:685-731] as create_hi_pass_viz uses it (:218-230):
+ * selects the amplitude of the filtered series for the fetches that follow.  window > 0: sqrt(convolve(y^2, ones(window) /
+ * window, "valid")) centred by (window - 1) / 2 frames, zero outside; window = 0: the filtered series itself (the reference's
+ * low-pass case).  window may not exceed the number of frames. */
+int fsi_band_amplitude(FsiCtx* ctx, int32_t quantity, int32_t window);
+/* Replaces: the "Saving data" loops of create_hi_pass_viz [REF .../create_hi_pass_viz.py:233-245,327-341,377-390]: one frame
+ * of the raw history, the filtered series or its amplitude (out[n][ncomp]), or of the amplitude's magnitude over the
+ * components (out[n]; for p the amplitude itself).  For the last two, max_out / argmax_out (nullable) receive the largest
+ * magnitude of the frame and the first node that has it (numpy.argmax).  out is nullable.  Amplitude frames are computed
+ * when fetched, cheapest in ascending order; a frame's value does not depend on the order. */
+int fsi_band_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, double* out, double* max_out,
+                   int64_t* argmax_out);
+/* Closes the session of the quantity and frees its device memory (fsi_destroy does the same). */
+int fsi_band_end(FsiCtx* ctx, int32_t quantity);
+
 /* ---- timing of the device kernels (HIP events on the solver stream) ---------------------------------- */
 typedef struct FsiTimers {
   double residual_ms;  int64_t residual_calls;

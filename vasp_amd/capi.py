@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_end", "fsi_band_begin", "fsi_band_sample", "fsi_band_filter", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -156,6 +156,12 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_stress_sample.argtypes = [vp, vp]
     lib.fsi_stress_averages.argtypes = [vp, vp, C.POINTER(i64)]
     lib.fsi_stress_end.argtypes = [vp]
+    lib.fsi_band_begin.argtypes = [vp, i32, i64, vp, vp, i64]
+    lib.fsi_band_sample.argtypes = [vp, i32]
+    lib.fsi_band_filter.argtypes = [vp, i32, i32, vp, vp, vp, i32]
+    lib.fsi_band_amplitude.argtypes = [vp, i32, i32]
+    lib.fsi_band_fetch.argtypes = [vp, i32, i32, i64, vp, C.POINTER(dbl), C.POINTER(i64)]
+    lib.fsi_band_end.argtypes = [vp, i32]
     lib.fsi_num_dofs.argtypes = [vp]
     lib.fsi_num_dofs.restype = i64
     lib.fsi_matrix_nnz.argtypes = [vp]
@@ -508,6 +514,52 @@ class HipBackend:
 
     def stress_strain_end(self) -> None:
         self._check(self.lib.fsi_stress_end(self.ctx))
+
+    BAND_QUANTITY = {"d": 0, "v": 1, "p": 2}
+    BAND_WHAT = {"raw": 0, "filtered": 1, "amplitude": 2, "magnitude": 3}
+
+    def hi_pass_begin(self, quantity: str, nodes, nodes_b=None, capacity: int = 1) -> None:
+        """Open the band-pass session of ``quantity`` ('d', 'v' or 'p'; fsi_band_begin) on ``nodes`` (P2 node ids, vertex
+        ids for 'p'; with ``nodes_b`` >= 0 a row is the mean of the two nodes) for up to ``capacity`` frames; replaces an open
+        session of the quantity.  Raises FsiError when the history would not fit the device."""
+        q = self.BAND_QUANTITY[quantity]
+        a = np.ascontiguousarray(nodes, dtype=np.int32)
+        b = None if nodes_b is None else np.ascontiguousarray(nodes_b, dtype=np.int32)
+        if b is not None and b.shape != a.shape:
+            raise ValueError("nodes_b must have the shape of nodes")
+        self._check(self.lib.fsi_band_begin(self.ctx, q, len(a), _ptr(a), None if b is None else _ptr(b), int(capacity)))
+        if not hasattr(self, "_band_shape"):
+            self._band_shape = {}
+        self._band_shape[quantity] = (len(a), 1 if quantity == "p" else 3)
+
+    def hi_pass_sample(self, quantity: str) -> None:
+        """Record the session's rows of dvp_["n"] as the next frame of its history (fsi_band_sample)."""
+        self._check(self.lib.fsi_band_sample(self.ctx, self.BAND_QUANTITY[quantity]))
+
+    def hi_pass_filter(self, quantity: str, b, a, zi, padlen: int) -> None:
+        """scipy.signal.filtfilt(b, a, .) of every row over the recorded frames (fsi_band_filter); zi = lfilter_zi(b, a)."""
+        b, a, zi = (np.ascontiguousarray(x, dtype=np.float64) for x in (b, a, zi))
+        if len(a) != len(b) or len(zi) != len(b) - 1:
+            raise ValueError("b and a must have one length, zi one less")
+        self._check(self.lib.fsi_band_filter(self.ctx, self.BAND_QUANTITY[quantity], len(b), _ptr(b), _ptr(a), _ptr(zi), int(padlen)))
+
+    def hi_pass_amplitude(self, quantity: str, window: int) -> None:
+        """Select the amplitude of the filtered series (fsi_band_amplitude): flat-window RMS over ``window`` frames, or the
+        series itself with ``window`` 0."""
+        self._check(self.lib.fsi_band_amplitude(self.ctx, self.BAND_QUANTITY[quantity], int(window)))
+
+    def hi_pass_fetch(self, quantity: str, what: str, frame: int, with_max: bool = False):
+        """One frame 'raw', 'filtered' or 'amplitude' as (n, ncomp), or 'magnitude' as (n,) (fsi_band_fetch); with
+        ``with_max`` (amplitude, magnitude) also the frame's largest magnitude and the first node that has it."""
+        n, ncomp = self._band_shape[quantity]
+        out = np.empty(n) if what == "magnitude" else np.empty((n, ncomp))
+        mx, am = C.c_double(0.0), C.c_int64(0)
+        self._check(self.lib.fsi_band_fetch(self.ctx, self.BAND_QUANTITY[quantity], self.BAND_WHAT[what], int(frame), _ptr(out),
+                                            C.byref(mx) if with_max else None, C.byref(am) if with_max else None))
+        return (out, mx.value, int(am.value)) if with_max else out
+
+    def hi_pass_end(self, quantity: str) -> None:
+        self._check(self.lib.fsi_band_end(self.ctx, self.BAND_QUANTITY[quantity]))
 
     def tuning(self) -> dict:
         """The FsiTuning the context was created with."""

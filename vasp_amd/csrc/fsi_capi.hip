@@ -193,6 +193,7 @@ int fsi_destroy(FsiCtx* ctx) {
   ctx->cellvals.release();
   ctx->hemo.release();
   ctx->stress.release();
+  for (auto& b : ctx->band) b.release();
   for (auto* b : {&ctx->Adv, &ctx->Avp, &ctx->Apv, &ctx->App, &ctx->blk, &ctx->Mdd.vals, &ctx->Mvv.vals, &ctx->mask_s, &ctx->mask_f, &ctx->ss_vals, &ctx->dd_db, &ctx->vv_db, &ctx->adv_db, &ctx->s_vals}) b->release();
   ctx->s_rowptr.release(); ctx->s_diagpos.release(); ctx->s_cols.release();
   for (auto* b : {&ctx->snode, &ctx->ss_cols, &ctx->sb_col, &ctx->sb_row, &ctx->sb_stride}) b->release();
@@ -1683,6 +1684,178 @@ int fsi_stress_end(FsiCtx* ctx) {
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->stress.release();
+  return FSI_OK;
+}
+
+namespace {
+// the open session of quantity q (0 d, 1 v, 2 p), or null with ctx->err set
+FsiCtx::Band* band_session(FsiCtx* ctx, int32_t q, const char* fn) {
+  if (q < 0 || q > 2) { ctx->err = std::string(fn) + ": quantity must be 0 (d), 1 (v) or 2 (p)"; return nullptr; }
+  if (!ctx->band[q].open) { ctx->err = std::string(fn) + ": no band-pass session for this quantity (fsi_band_begin first)"; return nullptr; }
+  return &ctx->band[q];
+}
+}  // namespace
+
+int fsi_band_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* nodes, const int32_t* nodes_b, int64_t capacity) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (quantity < 0 || quantity > 2) { ctx->err = "fsi_band_begin: quantity must be 0 (d), 1 (v) or 2 (p)"; return FSI_ERR_INVALID; }
+  if (n <= 0 || !nodes || capacity <= 0) { ctx->err = "fsi_band_begin: needs n > 0 nodes and a capacity > 0 frames"; return FSI_ERR_INVALID; }
+  if (ctx->part) { ctx->err = "fsi_band_begin: partitioned contexts are not supported"; return FSI_ERR_INVALID; }
+  const int ncomp = quantity == 2 ? 1 : 3;
+  const int64_t limit = quantity == 2 ? ctx->V : ctx->N2, off = quantity == 2 ? 6 * ctx->N2 : 3 * ctx->N2 * quantity;
+  if (n > 2 * ctx->ndof) { ctx->err = "fsi_band_begin: more nodes than the problem has dofs"; return FSI_ERR_INVALID; }
+  const int64_t nrow = n * ncomp;
+  std::vector<int32_t> i0((size_t)nrow), i1((size_t)nrow, -1);
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t a = nodes[i], b = nodes_b ? nodes_b[i] : -1;
+    if (a < 0 || a >= limit || b >= limit) { ctx->err = "fsi_band_begin: node out of range"; return FSI_ERR_INVALID; }
+    for (int k = 0; k < ncomp; ++k) {
+      i0[i * ncomp + k] = ctx->h_user2solver[off + (int64_t)ncomp * a + k];
+      if (b >= 0) i1[i * ncomp + k] = ctx->h_user2solver[off + (int64_t)ncomp * b + k];
+    }
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  auto& s = ctx->band[quantity];
+  s.release();
+  // history + filtered series + one frame each of sums, amplitudes and magnitudes, against what the device has free: the context
+  // keeps 1/16 of the device for what it allocates later (a refreshed preconditioner, staging buffers) - nothing is paged or cut
+  const double need_d = 8.0 * (double)nrow * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN + 2.0) + 8.0 * (double)n + 8.0 * (double)nrow;
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  const double reserve = (double)total_b / 16.0;
+  if (need_d > (double)free_b - reserve) {
+    char msg[320];
+    snprintf(msg, sizeof msg, "fsi_band_begin: the session needs %.0f bytes (%lld rows x %lld frames, raw and filtered), the device has %zu bytes "
+             "free of which %.0f stay with the context", need_d, (long long)nrow, (long long)capacity, free_b, reserve);
+    ctx->err = msg;
+    return FSI_ERR_INVALID;
+  }
+  s.ncomp = ncomp; s.nnode = n; s.nrow = nrow; s.capacity = capacity;
+  HIPCHK(s.idx0.alloc((size_t)nrow));
+  HIPCHK(s.idx1.alloc((size_t)nrow));
+  HIPCHK(s.hist.alloc((size_t)nrow * (size_t)capacity));
+  HIPCHK(s.work.alloc((size_t)nrow * (size_t)(capacity + 2 * BAND_MAX_PADLEN)));
+  HIPCHK(s.acc.alloc((size_t)nrow));
+  HIPCHK(s.amp.alloc((size_t)nrow));
+  HIPCHK(s.mag.alloc((size_t)n));
+  HIPCHK(s.part_val.alloc(BAND_ARGMAX_BLOCKS + 1));
+  HIPCHK(s.part_idx.alloc(BAND_ARGMAX_BLOCKS + 1));
+  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
+  HIPCHK(hipMemcpyAsync(s.idx0.p, i0.data(), (size_t)nrow * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(s.idx1.p, i1.data(), (size_t)nrow * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  s.open = true;
+  return FSI_OK;
+}
+
+int fsi_band_sample(FsiCtx* ctx, int32_t quantity) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_sample");
+  if (!s) return FSI_ERR_INVALID;
+  if (s->frames >= s->capacity) { ctx->err = "fsi_band_sample: the history is full (capacity declared at fsi_band_begin)"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  launch_band_sample(ctx->stream, s->nrow, ctx->U.p, s->idx0.p, s->idx1.p, s->hist.p + (size_t)s->frames * s->nrow);
+  HIPCHK(hipGetLastError());
+  s->frames += 1;
+  s->nfilt = 0;               // the filtered series no longer covers the history
+  s->window = -1;
+  return FSI_OK;
+}
+
+int fsi_band_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* b, const double* a, const double* zi, int32_t padlen) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_filter");
+  if (!s) return FSI_ERR_INVALID;
+  if (ntaps < 2 || ntaps > BAND_MAX_TAPS || !b || !a || !zi || padlen < 0 || padlen > BAND_MAX_PADLEN) {
+    ctx->err = "fsi_band_filter: needs 2 .. 11 coefficients b, a, their zi and 0 <= padlen <= 33";
+    return FSI_ERR_INVALID;
+  }
+  if (a[0] != 1.0) { ctx->err = "fsi_band_filter: a[0] must be 1 (normalised coefficients, as scipy.signal.butter returns them)"; return FSI_ERR_INVALID; }
+  if (s->frames <= padlen) {      // scipy: "The length of the input vector x must be greater than padlen"
+    ctx->err = "fsi_band_filter: " + std::to_string(s->frames) + " recorded frames, the filter needs more than padlen = " + std::to_string(padlen);
+    return FSI_ERR_INVALID;
+  }
+  BandCoef c{};
+  for (int k = 0; k < ntaps; ++k) { c.b[k] = b[k]; c.a[k] = a[k]; }
+  for (int k = 0; k < ntaps - 1; ++k) c.zi[k] = zi[k];
+  HIPCHK(hipSetDevice(ctx->device));
+  launch_band_filter(ctx->stream, s->nrow, s->frames, padlen, c, s->hist.p, s->work.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  s->padlen = padlen;
+  s->nfilt = s->frames;
+  s->window = -1;
+  s->acc_start = -1;
+  return FSI_OK;
+}
+
+int fsi_band_amplitude(FsiCtx* ctx, int32_t quantity, int32_t window) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_amplitude");
+  if (!s) return FSI_ERR_INVALID;
+  if (s->nfilt == 0) { ctx->err = "fsi_band_amplitude: no filtered series (fsi_band_filter first)"; return FSI_ERR_INVALID; }
+  if (window < 0 || window > s->nfilt) {
+    ctx->err = "fsi_band_amplitude: window of " + std::to_string(window) + " frames, the series has " + std::to_string(s->nfilt);
+    return FSI_ERR_INVALID;
+  }
+  s->window = window;
+  s->acc_start = -1;
+  return FSI_OK;
+}
+
+int fsi_band_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, double* out, double* max_out, int64_t* argmax_out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_fetch");
+  if (!s) return FSI_ERR_INVALID;
+  if (what < FSI_BAND_RAW || what > FSI_BAND_MAGNITUDE) { ctx->err = "fsi_band_fetch: what must be FSI_BAND_RAW .. FSI_BAND_MAGNITUDE"; return FSI_ERR_INVALID; }
+  const int64_t nfr = what == FSI_BAND_RAW ? s->frames : s->nfilt;
+  if (what != FSI_BAND_RAW && nfr == 0) { ctx->err = "fsi_band_fetch: no filtered series (fsi_band_filter first)"; return FSI_ERR_INVALID; }
+  if (frame < 0 || frame >= nfr) { ctx->err = "fsi_band_fetch: frame out of range"; return FSI_ERR_INVALID; }
+  if (what >= FSI_BAND_AMPLITUDE && s->window < 0) { ctx->err = "fsi_band_fetch: no amplitude (fsi_band_amplitude first)"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* y = s->work.p + (size_t)s->padlen * s->nrow;        // the filtered series without its guard frames
+  const double* src = nullptr;
+  if (what == FSI_BAND_RAW) src = s->hist.p + (size_t)frame * s->nrow;
+  else if (what == FSI_BAND_FILTERED || s->window == 0) src = y + (size_t)frame * s->nrow;   // low-pass: the amplitude is the series (:222-230)
+  else {
+    // calculate_windowed_rms: RMS[i - pad] for pad <= i < pad + n - w + 1 with pad = (n - len_RMS) // 2, zero outside.  The
+    // value of a frame does not depend on the order of the fetches: window `start` is recomputed when start is a multiple of
+    // BAND_RMS_REFRESH and advanced from start - 1 otherwise.
+    const int64_t w = s->window, n = s->nfilt, start = frame - (w - 1) / 2;
+    if (start < 0 || start + w > n) {
+      HIPCHK(hipMemsetAsync(s->amp.p, 0, (size_t)s->nrow * sizeof(double), ctx->stream));
+    } else {
+      int64_t from = start - start % BAND_RMS_REFRESH;
+      if (s->acc_start >= from && s->acc_start < start) from = s->acc_start + 1;
+      else if (s->acc_start == start) from = start - start % BAND_RMS_REFRESH;     // asked twice: the same arithmetic again
+      for (int64_t k = from; k <= start; ++k)
+        launch_band_rms(ctx->stream, s->nrow, y, k, (int)w, k % BAND_RMS_REFRESH == 0, s->acc.p, s->amp.p);
+      HIPCHK(hipGetLastError());
+      s->acc_start = start;
+    }
+    src = s->amp.p;
+  }
+  if (what == FSI_BAND_MAGNITUDE || max_out || argmax_out) {
+    if (what < FSI_BAND_AMPLITUDE) { ctx->err = "fsi_band_fetch: maximum / argmax are those of the amplitude magnitude"; return FSI_ERR_INVALID; }
+    launch_band_magnitude(ctx->stream, s->nnode, s->ncomp, src, s->mag.p);
+    launch_band_argmax(ctx->stream, s->nnode, s->mag.p, s->part_val.p, s->part_idx.p);
+    HIPCHK(hipGetLastError());
+    if (max_out) HIPCHK(hipMemcpyAsync(max_out, s->part_val.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (argmax_out) HIPCHK(hipMemcpyAsync(argmax_out, s->part_idx.p, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (what == FSI_BAND_MAGNITUDE) src = s->mag.p;
+  }
+  if (out) HIPCHK(hipMemcpyAsync(out, src, (size_t)(what == FSI_BAND_MAGNITUDE ? s->nnode : s->nrow) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return FSI_OK;
+}
+
+int fsi_band_end(FsiCtx* ctx, int32_t quantity) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (quantity < 0 || quantity > 2) { ctx->err = "fsi_band_end: quantity must be 0 (d), 1 (v) or 2 (p)"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->band[quantity].release();
   return FSI_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/vaspfsi.h"
+#include "fsi_band.hpp"
 #include "fsi_element.hpp"
 
 namespace fsi {
@@ -398,4 +399,24 @@ struct FsiCtx {
     fsi::DevBuf<double> avg;                 // [2][n][4]
     void release() { cells.release(); frame.release(); sums.release(); avg.release(); open = false; n = samples = 0; }
   } stress;
+
+  // band-pass sessions (fsi_band_begin .. fsi_band_end), one per quantity d, v, p: the rows' solver indices, the raw history
+  // hist[capacity][nrow], the filtered series work[capacity + 2 BAND_MAX_PADLEN][nrow] (the filtered frame k is frame
+  // padlen + k), and one frame each of running sums, amplitudes and amplitude magnitudes (fsi_band.hip)
+  struct Band {
+    bool open = false;
+    int ncomp = 0, padlen = 0;
+    int window = -1;                         // -1: no amplitude asked for; 0: the filtered series itself (low-pass); > 0: RMS window
+    int64_t nnode = 0, nrow = 0, capacity = 0, frames = 0;
+    int64_t nfilt = 0;                       // frames the filtered series holds (0: not filtered since the last sample)
+    int64_t acc_start = -1;                  // window start the running sums stand at (-1: none)
+    fsi::DevBuf<int32_t> idx0, idx1;         // [nrow]; idx1 < 0: the row is U[idx0], else the mean of the two
+    fsi::DevBuf<double> hist, work, acc, amp, mag, part_val;
+    fsi::DevBuf<int64_t> part_idx;
+    void release() {
+      idx0.release(); idx1.release(); hist.release(); work.release(); acc.release(); amp.release(); mag.release();
+      part_val.release(); part_idx.release();
+      open = false; ncomp = padlen = 0; window = -1; nnode = nrow = capacity = frames = nfilt = 0; acc_start = -1;
+    }
+  } band[3];
 };

@@ -73,6 +73,15 @@ def parse(argv: Optional[List[str]] = None) -> Dict[str, object]:
     ap.add_argument("--stress-strain", dest="stress_strain", action="store_const", const=True, default=None,
                     help="compute the Cauchy stress, Green-Lagrange strain and their largest principal values on the device "
                          "at every saved frame and write <results>/StressStrain/ (what vasp-compute-stress writes afterwards)")
+    ap.add_argument("--hi-pass", dest="hi_pass", nargs="+", default=None, metavar="Q",
+                    help="record d, v and / or p at every saved frame on the device and write the band-pass filtered fields "
+                         "to <results>/Visualization_hi_pass/ (what vasp-create-hi-pass-viz writes afterwards)")
+    ap.add_argument("--hi-pass-bands", dest="hi_pass_bands", nargs="+", type=_coerce, default=None, metavar="HZ",
+                    help="pairs of a lower and an upper frequency, one filtered series each (default: 25 1000)")
+    ap.add_argument("--hi-pass-window", dest="hi_pass_window", type=int, default=None,
+                    help="frames of the RMS window of --hi-pass-amplitude (default: 250)")
+    ap.add_argument("--hi-pass-amplitude", dest="hi_pass_amplitude", action="store_const", const=True, default=None,
+                    help="also write the windowed RMS amplitude of every filtered series and its table of percentiles")
     ap.add_argument("-c", "--config", dest="config", default=None,
                     help="config file with `key = value` lines (keys: the option names without dashes, or any problem-file "
                          "parameter); the command line wins over the file [REF docs/simulation.md:19-31]")
@@ -239,12 +248,13 @@ def parameters(argv: Optional[List[str]] = None):
 
 
 def _refuse_sessions(argv, backend_factory, world: int) -> None:
-    """--hemodynamics, --stress-strain: refuse before anything is built, on every rank (a refusal on rank 0 alone would leave
+    """--hemodynamics, --stress-strain, --hi-pass: refuse before anything is built, on every rank (a refusal on rank 0 alone would leave
     the workers waiting in run_worker)."""
     args = parse(argv)
-    if not (args.get("hemodynamics") or args.get("stress_strain")):
+    if not (args.get("hemodynamics") or args.get("stress_strain") or args.get("hi_pass")):
         return
     from .hemodynamics import hemodynamics_refusal
+    from .hi_pass import hi_pass_refusal
     from .stress_strain import stress_strain_refusal
     with contextlib.redirect_stdout(io.StringIO()):
         _, _, v = parameters(argv)
@@ -253,7 +263,8 @@ def _refuse_sessions(argv, backend_factory, world: int) -> None:
         cls = HipBackend
     else:
         cls = backend_factory if isinstance(backend_factory, type) else None
-    for key, refusal in (("hemodynamics", hemodynamics_refusal), ("stress_strain", stress_strain_refusal)):
+    for key, refusal in (("hemodynamics", hemodynamics_refusal), ("stress_strain", stress_strain_refusal),
+                         ("hi_pass", hi_pass_refusal)):
         why = refusal(v, world, cls) if v.get(key) else ""
         if why:
             raise SystemExit(why)
@@ -471,6 +482,10 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
         if not hasattr(backend, "stress_strain_begin"):
             raise SystemExit(f"--stress-strain needs a backend with stress_strain_begin ({type(backend).__name__} has none)")
         stress = StressStrainRun(backend, mesh, ns)
+    hipass = None
+    if ns.get("hi_pass"):                         # as --hemodynamics: run() checked it; a backend without the device session
+        from .hi_pass import HiPassRun            # records on the host (vasp_amd/hi_pass.py: HostBandSession)
+        hipass = HiPassRun(backend, mesh, ns)
     first_step_num = ns["counter"]
 
     dt, T = float(ns["dt"]), float(ns["T"])
@@ -499,6 +514,8 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
                 hemo.sample(t)
             if stress is not None:
                 stress.sample(t)
+            if hipass is not None:
+                hipass.sample(ns["dvp_"]["n"].vector)
         elif ns.get("save_step") and ns["counter"] % int(ns["save_step"]) == 0:
             ns["dvp_"]["n"].vector()              # partitioned: every rank takes part in the gather
         ns["counter"] += 1
@@ -513,6 +530,8 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
         hemo.finish(out)
     if stress is not None:
         stress.finish(out)
+    if hipass is not None:                        # also after a killturtle / killtime stop: on the frames recorded so far
+        hipass.finish(out)
     ns["time_loop_seconds"] = _time.perf_counter() - t_loop
     ns["newton_iterations"] = total_newton
     ns["solver_events"] = events_seen
