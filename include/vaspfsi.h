@@ -389,6 +389,57 @@ int fsi_band_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, d
 /* Closes the session of the quantity and frees its device memory (fsi_destroy does the same). */
 int fsi_band_end(FsiCtx* ctx, int32_t quantity);
 
+/* ---- average spectrograms and power spectra over a run (fsi_spec.hip) -------------------------------------- */
+/* One session per quantity (0 = d, 1 = v, 2 = p), with a history of its own on a node list of its own: it can be open beside
+ * the band-pass session of the same quantity, and beside every other session.  A row is one time series: one component of a
+ * listed node, its three components stacked (row = component * n + i), or the magnitude of the vector, taken when the frame is
+ * recorded.  The pressure has one component: ncomp_mode is ignored for it.  All data are FP64. */
+#define FSI_SPEC_X 0
+#define FSI_SPEC_Y 1
+#define FSI_SPEC_Z 2
+#define FSI_SPEC_ALL 3
+#define FSI_SPEC_MAG 4
+#define FSI_SPEC_SPECTRUM 0 /* power scaled by 1 / sum(w)^2 */
+#define FSI_SPEC_DENSITY 1  /* power scaled by 1 / (fs sum(w^2)) */
+/* Replaces: read_spectrogram_data's pass over the Visualization files into <quantity>_<component>.npz and its selection of the
+ * sampled rows [REF src/vasp/postprocessing/postprocessing_h5py/spectrograms.py:291-329; postprocessing_h5py_common.py:154-409].
+ * nodes / nodes_b as in fsi_band_begin (a node may be listed more than once: the reference draws with replacement).  The bytes
+ * of the raw and the filtered history (capacity and capacity + 66 frames) and of what the transforms allocate at the end (64 bins
+ * of a periodogram's tables, the means of capacity / 4 segments) are compared with the free device memory as in
+ * fsi_band_begin: FSI_ERR_INVALID with both byte counts, nothing allocated.  Replaces an open session of the quantity; a
+ * refused call leaves it as it was, its bytes counted as taken.  Not for partitioned contexts. */
+int fsi_spec_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* nodes, const int32_t* nodes_b, int32_t ncomp_mode,
+                   int64_t capacity);
+/* Replaces: reading one frame of <quantity>.h5 [REF .../postprocessing_h5py_common.py:154-409, its frame loop]: the session's rows
+ * of dvp_["n"] (or their magnitude) go to the next frame of the history, stream-ordered; the host does not wait.
+ * FSI_ERR_INVALID when the history is full. */
+int fsi_spec_sample(FsiCtx* ctx, int32_t quantity);
+/* Replaces: filter_time_data [REF .../spectrograms.py:558-583]: scipy.signal.filtfilt(b, a, row) of every row, by the band-pass
+ * session's kernel (bit for bit; arguments as fsi_band_filter; the reference's high-pass is butter(6, lowcut / (fs / 2),
+ * "highpass"): 7 coefficients, padlen 21), and selects the filtered series as the source of the transforms that follow.
+ * ntaps = 0 (b, a, zi ignored) selects the raw series.  Recording a frame selects the raw series again. */
+int fsi_spec_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* b, const double* a, const double* zi,
+                    int32_t padlen);
+/* Replaces: df.iloc[row] of the sampled matrix [REF .../spectrograms.py:320-321]: out[rows] = one frame of the raw (filtered =
+ * 0) or of the filtered history. */
+int fsi_spec_fetch(FsiCtx* ctx, int32_t quantity, int32_t filtered, int64_t frame, double* out);
+/* Replaces: the row loop of get_spectrogram around scipy.signal.spectrogram(row, fs, nperseg, noverlap, nfft, window, scaling)
+ * and its average [REF .../spectrograms.py:446-463]: out_power[(nfft / 2 + 1)][nseg], nseg = (frames - noverlap) / (nperseg -
+ * noverlap), the mean over the rows of the one-sided power of every segment, each segment detrended by its mean (scipy's
+ * default) and multiplied by window[nperseg]; every bin doubled but DC and, for an even nfft, Nyquist.  nfft >= nperseg: the
+ * padding is never multiplied.  The rows are added in a fixed order without atomics: the same call returns the same bits.  The
+ * cos / sin tables are made on the host in slabs of bins sized against the free device memory; when the means, the result and
+ * one slab of 64 bins do not fit beside the 1/16 of the device the context keeps: FSI_ERR_INVALID with both byte counts,
+ * nothing allocated, nothing paged, out_power untouched.  The same for nfft > 2^26, the longest table the host is asked for. */
+int fsi_spec_spectrogram(FsiCtx* ctx, int32_t quantity, int64_t nperseg, int64_t noverlap, int64_t nfft, const double* window,
+                         int32_t scaling, double fs, double* out_power);
+/* Replaces: the row loop of get_psd around scipy.signal.periodogram(row, fs, window, scaling) and its average
+ * [REF .../spectrograms.py:409-419]: out_power[frames / 2 + 1], the spectrogram of one segment of all recorded frames with nfft =
+ * frames (any length, odd included), window[frames]. */
+int fsi_spec_periodogram(FsiCtx* ctx, int32_t quantity, const double* window, int32_t scaling, double fs, double* out_power);
+/* Closes the session of the quantity and frees its device memory (fsi_destroy does the same). */
+int fsi_spec_end(FsiCtx* ctx, int32_t quantity);
+
 /* ---- timing of the device kernels (HIP events on the solver stream) ---------------------------------- */
 typedef struct FsiTimers {
   double residual_ms;  int64_t residual_calls;

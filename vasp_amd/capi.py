@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_end", "fsi_band_begin", "fsi_band_sample", "fsi_band_filter", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_end", "fsi_band_begin", "fsi_band_sample", "fsi_band_filter", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_end", "fsi_spec_begin", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -162,6 +162,13 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_band_amplitude.argtypes = [vp, i32, i32]
     lib.fsi_band_fetch.argtypes = [vp, i32, i32, i64, vp, C.POINTER(dbl), C.POINTER(i64)]
     lib.fsi_band_end.argtypes = [vp, i32]
+    lib.fsi_spec_begin.argtypes = [vp, i32, i64, vp, vp, i32, i64]
+    lib.fsi_spec_sample.argtypes = [vp, i32]
+    lib.fsi_spec_filter.argtypes = [vp, i32, i32, vp, vp, vp, i32]
+    lib.fsi_spec_fetch.argtypes = [vp, i32, i32, i64, vp]
+    lib.fsi_spec_spectrogram.argtypes = [vp, i32, i64, i64, i64, vp, i32, dbl, vp]
+    lib.fsi_spec_periodogram.argtypes = [vp, i32, vp, i32, dbl, vp]
+    lib.fsi_spec_end.argtypes = [vp, i32]
     lib.fsi_num_dofs.argtypes = [vp]
     lib.fsi_num_dofs.restype = i64
     lib.fsi_matrix_nnz.argtypes = [vp]
@@ -242,6 +249,7 @@ class HipBackend:
         import os
         self.lib = load_library()
         self.ctx = C.c_void_p()
+        self._spec_shape = {}        # spec_begin: quantity -> [rows, recorded frames]
         self.lin_rtol, self.lin_max_it, self.lin_solver = lin_rtol, lin_max_it, lin_solver
         coords = np.ascontiguousarray(desc["coords"], dtype=np.float64)
         # cells are handed to the library in a locality order (VASPFSI_CELL_ORDER=mesh: as the caller numbers them); cell
@@ -560,6 +568,77 @@ class HipBackend:
 
     def hi_pass_end(self, quantity: str) -> None:
         self._check(self.lib.fsi_band_end(self.ctx, self.BAND_QUANTITY[quantity]))
+
+    SPEC_MODE = {"x": 0, "y": 1, "z": 2, "all": 3, "mag": 4}
+    SPEC_SCALING = {"spectrum": 0, "density": 1}
+
+    def spec_begin(self, quantity: str, nodes, nodes_b=None, component: str = "all", capacity: int = 1) -> None:
+        """Open the spectrogram session of ``quantity`` (fsi_spec_begin) on ``nodes`` (as ``hi_pass_begin``; a node may be
+        listed twice) for up to ``capacity`` frames.  ``component``: 'x', 'y', 'z', 'all' (the three stacked, component-major)
+        or 'mag' (taken when a frame is recorded); the pressure has one.  Raises FsiError when the history does not fit."""
+        a = np.ascontiguousarray(nodes, dtype=np.int32)
+        b = None if nodes_b is None else np.ascontiguousarray(nodes_b, dtype=np.int32)
+        if b is not None and b.shape != a.shape:
+            raise ValueError("nodes_b must have the shape of nodes")
+        self._check(self.lib.fsi_spec_begin(self.ctx, self.BAND_QUANTITY[quantity], len(a), _ptr(a), None if b is None else _ptr(b),
+                                            self.SPEC_MODE[component], int(capacity)))
+        self._spec_shape[quantity] = [len(a) * (3 if component == "all" and quantity != "p" else 1), 0]
+
+    def spec_sample(self, quantity: str) -> None:
+        """Record the session's rows of dvp_["n"] as the next frame of its history (fsi_spec_sample)."""
+        self._check(self.lib.fsi_spec_sample(self.ctx, self.BAND_QUANTITY[quantity]))
+        self._spec_shape[quantity][1] += 1
+
+    def spec_filter(self, quantity: str, b=None, a=None, zi=None, padlen: int = 0) -> None:
+        """scipy.signal.filtfilt(b, a, .) of every row, the source of the transforms that follow (fsi_spec_filter); without
+        coefficients: the raw series."""
+        if b is None:
+            self._check(self.lib.fsi_spec_filter(self.ctx, self.BAND_QUANTITY[quantity], 0, None, None, None, 0))
+            return
+        b, a, zi = (np.ascontiguousarray(x, dtype=np.float64) for x in (b, a, zi))
+        if len(a) != len(b) or len(zi) != len(b) - 1:
+            raise ValueError("b and a must have one length, zi one less")
+        self._check(self.lib.fsi_spec_filter(self.ctx, self.BAND_QUANTITY[quantity], len(b), _ptr(b), _ptr(a), _ptr(zi), int(padlen)))
+
+    def _spec_open(self, quantity: str):
+        """[rows, recorded frames] of the open session; without one, the library's own refusal."""
+        if quantity not in self._spec_shape:
+            self._check(self.lib.fsi_spec_sample(self.ctx, self.BAND_QUANTITY[quantity]))     # "fsi_spec_begin first"
+        return self._spec_shape[quantity]
+
+    def spec_fetch(self, quantity: str, frame: int, filtered: bool = False) -> np.ndarray:
+        """One frame of the raw or the filtered history: (rows,) (fsi_spec_fetch)."""
+        out = np.empty(self._spec_open(quantity)[0])
+        self._check(self.lib.fsi_spec_fetch(self.ctx, self.BAND_QUANTITY[quantity], int(bool(filtered)), int(frame), _ptr(out)))
+        return out
+
+    def spec_spectrogram(self, quantity: str, nperseg: int, noverlap: int, nfft: int, window, scaling: str, fs: float) -> np.ndarray:
+        """The mean over the rows of scipy.signal.spectrogram's power: (nfft // 2 + 1, segments) (fsi_spec_spectrogram)."""
+        w = np.ascontiguousarray(window, dtype=np.float64)
+        if w.shape != (int(nperseg),):
+            raise ValueError("the window must have nperseg entries")
+        frames = self._spec_open(quantity)[1]
+        if not 0 <= noverlap < nperseg <= max(frames, 1):
+            raise ValueError("needs 0 <= noverlap < nperseg <= recorded frames")
+        nseg = (frames - int(noverlap)) // (int(nperseg) - int(noverlap))
+        out = np.empty((int(nfft) // 2 + 1, max(nseg, 0)))
+        self._check(self.lib.fsi_spec_spectrogram(self.ctx, self.BAND_QUANTITY[quantity], int(nperseg), int(noverlap), int(nfft), _ptr(w),
+                                                  self.SPEC_SCALING[scaling], float(fs), _ptr(out)))
+        return out
+
+    def spec_periodogram(self, quantity: str, window, scaling: str, fs: float) -> np.ndarray:
+        """The mean over the rows of scipy.signal.periodogram's power: (frames // 2 + 1,) (fsi_spec_periodogram)."""
+        w = np.ascontiguousarray(window, dtype=np.float64)
+        frames = self._spec_open(quantity)[1]
+        if w.shape != (frames,):
+            raise ValueError("the window must have one entry per recorded frame")
+        out = np.empty(frames // 2 + 1)
+        self._check(self.lib.fsi_spec_periodogram(self.ctx, self.BAND_QUANTITY[quantity], _ptr(w), self.SPEC_SCALING[scaling], float(fs), _ptr(out)))
+        return out
+
+    def spec_end(self, quantity: str) -> None:
+        self._check(self.lib.fsi_spec_end(self.ctx, self.BAND_QUANTITY[quantity]))
+        self._spec_shape.pop(quantity, None)
 
     def tuning(self) -> dict:
         """The FsiTuning the context was created with."""

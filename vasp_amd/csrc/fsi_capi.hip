@@ -3,6 +3,7 @@
 // Host-side logic follows turtleFSI's monolithic.py / newtonsolver.py as VaSP uses them; the
 // arithmetic runs in the HIP kernels of fsi_assembly.hip / fsi_solver.hip.
 #include "fsi_host.hpp"
+#include "fsi_spec.hpp"
 
 using namespace fsi;
 using namespace fsi::host;
@@ -194,6 +195,7 @@ int fsi_destroy(FsiCtx* ctx) {
   ctx->hemo.release();
   ctx->stress.release();
   for (auto& b : ctx->band) b.release();
+  for (auto& b : ctx->spec) b.release();
   for (auto* b : {&ctx->Adv, &ctx->Avp, &ctx->Apv, &ctx->App, &ctx->blk, &ctx->Mdd.vals, &ctx->Mvv.vals, &ctx->mask_s, &ctx->mask_f, &ctx->ss_vals, &ctx->dd_db, &ctx->vv_db, &ctx->adv_db, &ctx->s_vals}) b->release();
   ctx->s_rowptr.release(); ctx->s_diagpos.release(); ctx->s_cols.release();
   for (auto* b : {&ctx->snode, &ctx->ss_cols, &ctx->sb_col, &ctx->sb_row, &ctx->sb_stride}) b->release();
@@ -1856,6 +1858,267 @@ int fsi_band_end(FsiCtx* ctx, int32_t quantity) {
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->band[quantity].release();
+  return FSI_OK;
+}
+
+namespace {
+// the open spectrogram session of quantity q (0 d, 1 v, 2 p), or null with ctx->err set
+FsiCtx::Spec* spec_session(FsiCtx* ctx, int32_t q, const char* fn) {
+  if (q < 0 || q > 2) { ctx->err = std::string(fn) + ": quantity must be 0 (d), 1 (v) or 2 (p)"; return nullptr; }
+  if (!ctx->spec[q].open) { ctx->err = std::string(fn) + ": no spectrogram session for this quantity (fsi_spec_begin first)"; return nullptr; }
+  return &ctx->spec[q];
+}
+
+// The average over the session's rows of the one-sided power of nseg segments of K frames, `step` frames apart, transformed
+// at length nfft >= K: mean, then per slab of bins the host's tables, k_spec_power and k_spec_reduce.  out[(nfft / 2 + 1)][nseg].
+int spec_power(FsiCtx* ctx, FsiCtx::Spec* s, const char* fn, int64_t K, int64_t step, int64_t nseg, int64_t nfft, const double* window,
+               int32_t scaling, double fs, double* out) {
+  const int64_t nbins = nfft / 2 + 1, nblk = spec_blocks(s->nrow);
+  double sw = 0.0, sw2 = 0.0;
+  for (int64_t j = 0; j < K; ++j) { sw += window[j]; sw2 += window[j] * window[j]; }
+  const double scale = scaling == FSI_SPEC_DENSITY ? 1.0 / (fs * sw2) : 1.0 / (sw * sw);
+  if (!std::isfinite(scale) || scale <= 0.0) { ctx->err = std::string(fn) + ": the window gives no finite scale"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  // what one call holds on the device: means, window and result, and per bin of a slab two table columns and the row blocks'
+  // partial sums.  The slab is as many bins as fit beside the 1/16 of the device the context keeps (at most 1 GiB of tables:
+  // they are made on the host); if not even one pass of SPEC_BINS bins fits, the call is refused - nothing is paged.
+  const double fixed = 8.0 * ((double)nseg * (double)s->nrow + (double)K + (double)nbins * (double)nseg);
+  const double per_bin = 8.0 * (2.0 * (double)K + (double)nseg * (double)nblk);
+  const int64_t min_slab = nbins < SPEC_BINS ? nbins : SPEC_BINS;
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  const double reserve = (double)total_b / 16.0, avail = (double)free_b - reserve - fixed;
+  if (avail < per_bin * (double)min_slab) {
+    char msg[460];
+    snprintf(msg, sizeof msg, "%s: the transform needs %.0f bytes (tables of %lld frames x %lld of %lld bins, cos and sin, %lld segments x %lld rows of "
+             "means and partial sums, and the result), the device has %zu bytes free of which %.0f stay with the context", fn,
+             fixed + per_bin * (double)min_slab, (long long)K, (long long)min_slab, (long long)nbins, (long long)nseg, (long long)s->nrow,
+             free_b, reserve);
+    ctx->err = msg;
+    return FSI_ERR_INVALID;
+  }
+  // the host makes the tables: cos / sin of nfft angles and one slab's columns.  A transform length whose tables the host
+  // should not be asked for is refused like one that does not fit the device, not left to std::bad_alloc
+  if (nfft > SPEC_MAX_NFFT) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: nfft = %lld, the host's cos / sin tables are limited to %lld angles", fn, (long long)nfft, (long long)SPEC_MAX_NFFT);
+    ctx->err = msg;
+    return FSI_ERR_INVALID;
+  }
+  int64_t slab = nbins;
+  const double cap = std::min(avail / per_bin, (double)(1ll << 30) / (16.0 * (double)K));
+  if ((double)slab > cap) slab = std::max<int64_t>(min_slab, (int64_t)cap / SPEC_BINS * SPEC_BINS);
+  struct Bufs {
+    DevBuf<double> mean, w, Ct, St, part, res;
+    ~Bufs() { mean.release(); w.release(); Ct.release(); St.release(); part.release(); res.release(); }
+  } bufs;
+  auto &mean = bufs.mean, &w = bufs.w, &Ct = bufs.Ct, &St = bufs.St, &part = bufs.part, &res = bufs.res;
+  HIPCHK(mean.alloc((size_t)(nseg * s->nrow)));
+  HIPCHK(w.alloc((size_t)K));
+  HIPCHK(Ct.alloc((size_t)(K * slab)));
+  HIPCHK(St.alloc((size_t)(K * slab)));
+  HIPCHK(part.alloc((size_t)(nseg * nblk * slab)));
+  HIPCHK(res.alloc((size_t)(nbins * nseg)));
+  HIPCHK(hipDeviceSynchronize());
+  int rc = FSI_OK;
+  std::string why;
+  auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && rc == FSI_OK) { rc = FSI_ERR_DEVICE; why = std::string(what) + ": " + hipGetErrorString(e); } return e == hipSuccess; };
+  const double* x = s->filtered ? s->work.p + (size_t)s->padlen * s->nrow : s->hist.p;
+  // cos / sin(2 pi m / nfft), m = 0 .. nfft - 1, once; a table entry is that of m = j k mod nfft
+  std::vector<double> cosm, sinm, hc, hs;
+  try {
+    cosm.resize((size_t)nfft); sinm.resize((size_t)nfft); hc.resize((size_t)(K * slab)); hs.resize((size_t)(K * slab));
+  } catch (const std::bad_alloc&) {
+    ctx->err = std::string(fn) + ": the host has no memory for the cos / sin tables (" + std::to_string(16 * (nfft + K * slab)) + " bytes)";
+    return FSI_ERR_INVALID;
+  }
+  const long double tau = 2.0L * 3.14159265358979323846264338327950288L;      // the angle in extended precision: an entry is the
+  for (int64_t m = 0; m < nfft; ++m) {                                       // correctly rounded cos / sin to within its last bit
+    const long double ang = tau * (long double)m / (long double)nfft;
+    cosm[m] = (double)cosl(ang);
+    sinm[m] = (double)sinl(ang);
+  }
+  if (chk(hipMemcpyAsync(w.p, window, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "window upload")) {
+    launch_spec_mean(ctx->stream, s->nrow, K, step, nseg, x, mean.p);
+    chk(hipGetLastError(), "k_spec_mean");
+  }
+  for (int64_t bin0 = 0; bin0 < nbins && rc == FSI_OK; bin0 += slab) {
+    const int64_t nb = std::min(slab, nbins - bin0);
+    for (int64_t j = 0; j < K; ++j)
+      for (int64_t b = 0; b < nb; ++b) {
+        const int64_t m = (int64_t)(((unsigned __int128)j * (unsigned __int128)(bin0 + b)) % (unsigned __int128)nfft);
+        hc[j * nb + b] = cosm[m];
+        hs[j * nb + b] = sinm[m];
+      }
+    if (!chk(hipMemcpyAsync(Ct.p, hc.data(), (size_t)(K * nb) * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "table upload")) break;
+    if (!chk(hipMemcpyAsync(St.p, hs.data(), (size_t)(K * nb) * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "table upload")) break;
+    launch_spec_power(ctx->stream, s->nrow, K, step, nseg, nb, bin0, nfft % 2 == 0 ? nfft / 2 : -1, scale, x, mean.p, w.p, Ct.p, St.p, part.p);
+    launch_spec_reduce(ctx->stream, s->nrow, nseg, nb, bin0, part.p, res.p);
+    if (!chk(hipGetLastError(), "k_spec_power")) break;
+    if (!chk(hipStreamSynchronize(ctx->stream), "k_spec_power")) break;      // the host tables are refilled for the next slab
+  }
+  if (rc == FSI_OK && chk(hipMemcpyAsync(out, res.p, (size_t)(nbins * nseg) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "result"))
+    chk(hipStreamSynchronize(ctx->stream), "result");
+  if (rc != FSI_OK) ctx->err = std::string(fn) + ": " + why;
+  return rc;
+}
+}  // namespace
+
+int fsi_spec_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* nodes, const int32_t* nodes_b, int32_t ncomp_mode, int64_t capacity) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (quantity < 0 || quantity > 2) { ctx->err = "fsi_spec_begin: quantity must be 0 (d), 1 (v) or 2 (p)"; return FSI_ERR_INVALID; }
+  if (n <= 0 || !nodes || capacity <= 0) { ctx->err = "fsi_spec_begin: needs n > 0 nodes and a capacity > 0 frames"; return FSI_ERR_INVALID; }
+  if (ncomp_mode < FSI_SPEC_X || ncomp_mode > FSI_SPEC_MAG) { ctx->err = "fsi_spec_begin: ncomp_mode must be FSI_SPEC_X .. FSI_SPEC_MAG"; return FSI_ERR_INVALID; }
+  if (ctx->part) { ctx->err = "fsi_spec_begin: partitioned contexts are not supported"; return FSI_ERR_INVALID; }
+  if (n > 2 * ctx->ndof) { ctx->err = "fsi_spec_begin: more nodes than the problem has dofs"; return FSI_ERR_INVALID; }
+  const bool scalar = quantity == 2;
+  const int mode = scalar ? FSI_SPEC_X : ncomp_mode;              // the pressure has one component
+  const int ncomp = scalar ? 1 : 3;
+  const int64_t limit = scalar ? ctx->V : ctx->N2, off = scalar ? 6 * ctx->N2 : 3 * ctx->N2 * quantity;
+  const int64_t nsamp = mode >= FSI_SPEC_ALL ? 3 * n : n, nrow = mode == FSI_SPEC_ALL ? 3 * n : n;
+  std::vector<int32_t> i0((size_t)nsamp), i1((size_t)nsamp, -1);
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t a = nodes[i], b = nodes_b ? nodes_b[i] : -1;
+    if (a < 0 || a >= limit || b >= limit) { ctx->err = "fsi_spec_begin: node out of range"; return FSI_ERR_INVALID; }
+    for (int c = 0; c < (mode >= FSI_SPEC_ALL ? 3 : 1); ++c) {
+      const int comp = scalar ? 0 : (mode >= FSI_SPEC_ALL ? c : mode);
+      i0[c * n + i] = ctx->h_user2solver[off + (int64_t)ncomp * a + comp];
+      if (b >= 0) i1[c * n + i] = ctx->h_user2solver[off + (int64_t)ncomp * b + comp];
+    }
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  auto& s = ctx->spec[quantity];
+  // raw and filtered history and the sampled vector of the magnitude, against what the device has free, as fsi_band_begin;
+  // with them what the transforms allocate at the end of the run, so that a history that fits here is not refused there:
+  // one pass of SPEC_BINS bins of a periodogram's tables over all frames, and the means of capacity / 4 segments
+  const double need_d = 8.0 * (double)nrow * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN) + 16.0 * (double)nsamp +
+                        16.0 * SPEC_BINS * (double)capacity + 8.0 * (double)nrow * ((double)capacity / 4.0 + 2.0);
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  const double reserve = (double)total_b / 16.0;
+  if (need_d > (double)free_b - reserve) {
+    char msg[420];
+    snprintf(msg, sizeof msg, "fsi_spec_begin: the session needs %.0f bytes (%lld rows x %lld frames, raw and filtered, and the transforms' tables), the device has %zu bytes "
+             "free of which %.0f stay with the context", need_d, (long long)nrow, (long long)capacity, free_b, reserve);
+    ctx->err = msg;
+    return FSI_ERR_INVALID;
+  }
+  s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
+  s.mode = mode; s.nnode = n; s.nrow = nrow; s.nsamp = nsamp; s.capacity = capacity;
+  HIPCHK(s.idx0.alloc((size_t)nsamp));
+  HIPCHK(s.idx1.alloc((size_t)nsamp));
+  HIPCHK(s.hist.alloc((size_t)nrow * (size_t)capacity));
+  HIPCHK(s.work.alloc((size_t)nrow * (size_t)(capacity + 2 * BAND_MAX_PADLEN)));
+  if (mode == FSI_SPEC_MAG) HIPCHK(s.tmp.alloc((size_t)nsamp));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpyAsync(s.idx0.p, i0.data(), (size_t)nsamp * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(s.idx1.p, i1.data(), (size_t)nsamp * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  s.open = true;
+  return FSI_OK;
+}
+
+int fsi_spec_sample(FsiCtx* ctx, int32_t quantity) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto* s = spec_session(ctx, quantity, "fsi_spec_sample");
+  if (!s) return FSI_ERR_INVALID;
+  if (s->frames >= s->capacity) { ctx->err = "fsi_spec_sample: the history is full (capacity declared at fsi_spec_begin)"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  double* dst = s->hist.p + (size_t)s->frames * s->nrow;
+  if (s->mode == FSI_SPEC_MAG) {
+    launch_band_sample(ctx->stream, s->nsamp, ctx->U.p, s->idx0.p, s->idx1.p, s->tmp.p);
+    launch_spec_magnitude(ctx->stream, s->nnode, s->tmp.p, dst);
+  } else {
+    launch_band_sample(ctx->stream, s->nrow, ctx->U.p, s->idx0.p, s->idx1.p, dst);
+  }
+  HIPCHK(hipGetLastError());
+  s->frames += 1;
+  s->filtered = false;        // a filtered series no longer covers the history
+  return FSI_OK;
+}
+
+int fsi_spec_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* b, const double* a, const double* zi, int32_t padlen) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto* s = spec_session(ctx, quantity, "fsi_spec_filter");
+  if (!s) return FSI_ERR_INVALID;
+  if (ntaps == 0) { s->filtered = false; return FSI_OK; }
+  if (ntaps < 2 || ntaps > BAND_MAX_TAPS || !b || !a || !zi || padlen < 0 || padlen > BAND_MAX_PADLEN) {
+    ctx->err = "fsi_spec_filter: needs 0 (the raw series) or 2 .. 11 coefficients b, a, their zi and 0 <= padlen <= 33";
+    return FSI_ERR_INVALID;
+  }
+  if (a[0] != 1.0) { ctx->err = "fsi_spec_filter: a[0] must be 1 (normalised coefficients, as scipy.signal.butter returns them)"; return FSI_ERR_INVALID; }
+  if (s->frames <= padlen) {
+    ctx->err = "fsi_spec_filter: " + std::to_string(s->frames) + " recorded frames, the filter needs more than padlen = " + std::to_string(padlen);
+    return FSI_ERR_INVALID;
+  }
+  BandCoef c{};
+  for (int k = 0; k < ntaps; ++k) { c.b[k] = b[k]; c.a[k] = a[k]; }
+  for (int k = 0; k < ntaps - 1; ++k) c.zi[k] = zi[k];
+  HIPCHK(hipSetDevice(ctx->device));
+  launch_band_filter(ctx->stream, s->nrow, s->frames, padlen, c, s->hist.p, s->work.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  s->padlen = padlen;
+  s->filtered = true;
+  return FSI_OK;
+}
+
+int fsi_spec_fetch(FsiCtx* ctx, int32_t quantity, int32_t filtered, int64_t frame, double* out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto* s = spec_session(ctx, quantity, "fsi_spec_fetch");
+  if (!s) return FSI_ERR_INVALID;
+  if (!out) { ctx->err = "fsi_spec_fetch: out is NULL"; return FSI_ERR_INVALID; }
+  if (filtered && !s->filtered) { ctx->err = "fsi_spec_fetch: no filtered series (fsi_spec_filter first)"; return FSI_ERR_INVALID; }
+  if (frame < 0 || frame >= s->frames) { ctx->err = "fsi_spec_fetch: frame out of range"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* src = (filtered ? s->work.p + (size_t)s->padlen * s->nrow : s->hist.p) + (size_t)frame * s->nrow;
+  HIPCHK(hipMemcpyAsync(out, src, (size_t)s->nrow * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return FSI_OK;
+}
+
+int fsi_spec_spectrogram(FsiCtx* ctx, int32_t quantity, int64_t nperseg, int64_t noverlap, int64_t nfft, const double* window,
+                         int32_t scaling, double fs, double* out_power) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto* s = spec_session(ctx, quantity, "fsi_spec_spectrogram");
+  if (!s) return FSI_ERR_INVALID;
+  if (!window || !out_power || (scaling != FSI_SPEC_SPECTRUM && scaling != FSI_SPEC_DENSITY) || !(fs > 0.0)) {
+    ctx->err = "fsi_spec_spectrogram: needs a window, an output, scaling FSI_SPEC_SPECTRUM or FSI_SPEC_DENSITY and fs > 0";
+    return FSI_ERR_INVALID;
+  }
+  if (nperseg < 1 || noverlap < 0 || noverlap >= nperseg || nfft < nperseg) {
+    ctx->err = "fsi_spec_spectrogram: needs nperseg >= 1, 0 <= noverlap < nperseg and nfft >= nperseg";
+    return FSI_ERR_INVALID;
+  }
+  if (s->frames < nperseg) {
+    ctx->err = "fsi_spec_spectrogram: " + std::to_string(s->frames) + " recorded frames, one segment needs nperseg = " + std::to_string(nperseg);
+    return FSI_ERR_INVALID;
+  }
+  const int64_t step = nperseg - noverlap, nseg = (s->frames - noverlap) / step;
+  if (nseg > 65535) { ctx->err = "fsi_spec_spectrogram: more than 65535 segments"; return FSI_ERR_INVALID; }
+  return spec_power(ctx, s, "fsi_spec_spectrogram", nperseg, step, nseg, nfft, window, scaling, fs, out_power);
+}
+
+int fsi_spec_periodogram(FsiCtx* ctx, int32_t quantity, const double* window, int32_t scaling, double fs, double* out_power) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto* s = spec_session(ctx, quantity, "fsi_spec_periodogram");
+  if (!s) return FSI_ERR_INVALID;
+  if (!window || !out_power || (scaling != FSI_SPEC_SPECTRUM && scaling != FSI_SPEC_DENSITY) || !(fs > 0.0)) {
+    ctx->err = "fsi_spec_periodogram: needs a window, an output, scaling FSI_SPEC_SPECTRUM or FSI_SPEC_DENSITY and fs > 0";
+    return FSI_ERR_INVALID;
+  }
+  if (s->frames < 1) { ctx->err = "fsi_spec_periodogram: no recorded frames"; return FSI_ERR_INVALID; }
+  return spec_power(ctx, s, "fsi_spec_periodogram", s->frames, s->frames, 1, s->frames, window, scaling, fs, out_power);
+}
+
+int fsi_spec_end(FsiCtx* ctx, int32_t quantity) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (quantity < 0 || quantity > 2) { ctx->err = "fsi_spec_end: quantity must be 0 (d), 1 (v) or 2 (p)"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->spec[quantity].release();
   return FSI_OK;
 }
 

@@ -419,4 +419,20 @@ struct FsiCtx {
       open = false; ncomp = padlen = 0; window = -1; nnode = nrow = capacity = frames = nfilt = 0; acc_start = -1;
     }
   } band[3];
+
+  // spectrogram sessions (fsi_spec_begin .. fsi_spec_end), one per quantity d, v, p, with a history of their own on a row
+  // list of their own, in the band-pass session's layout: hist[capacity][nrow] raw, work[capacity + 2 BAND_MAX_PADLEN][nrow]
+  // filtered (frame k at padlen + k).  mode: 0 / 1 / 2 one component, 3 the three stacked (row = c * nnode + i), 4 the
+  // magnitude, taken at sample time from tmp[3 nnode].  Means, tables and partial sums live for one call (fsi_spec.hip).
+  struct Spec {
+    bool open = false, filtered = false;
+    int mode = 0, padlen = 0;
+    int64_t nnode = 0, nrow = 0, nsamp = 0, capacity = 0, frames = 0;
+    fsi::DevBuf<int32_t> idx0, idx1;         // [nsamp]: the sampled entries (nsamp = nrow, or 3 nnode for the magnitude)
+    fsi::DevBuf<double> hist, work, tmp;
+    void release() {
+      idx0.release(); idx1.release(); hist.release(); work.release(); tmp.release();
+      open = filtered = false; mode = padlen = 0; nnode = nrow = nsamp = capacity = frames = 0;
+    }
+  } spec[3];
 };

@@ -82,6 +82,8 @@ def parse(argv: Optional[List[str]] = None) -> Dict[str, object]:
                     help="frames of the RMS window of --hi-pass-amplitude (default: 250)")
     ap.add_argument("--hi-pass-amplitude", dest="hi_pass_amplitude", action="store_const", const=True, default=None,
                     help="also write the windowed RMS amplitude of every filtered series and its table of percentiles")
+    from .spectrogram import add_arguments as add_spectrogram_arguments
+    add_spectrogram_arguments(ap, _coerce)
     ap.add_argument("-c", "--config", dest="config", default=None,
                     help="config file with `key = value` lines (keys: the option names without dashes, or any problem-file "
                          "parameter); the command line wins over the file [REF docs/simulation.md:19-31]")
@@ -248,13 +250,14 @@ def parameters(argv: Optional[List[str]] = None):
 
 
 def _refuse_sessions(argv, backend_factory, world: int) -> None:
-    """--hemodynamics, --stress-strain, --hi-pass: refuse before anything is built, on every rank (a refusal on rank 0 alone would leave
+    """--hemodynamics, --stress-strain, --hi-pass, --spectrogram: refuse before anything is built, on every rank (a refusal on rank 0 alone would leave
     the workers waiting in run_worker)."""
     args = parse(argv)
-    if not (args.get("hemodynamics") or args.get("stress_strain") or args.get("hi_pass")):
+    if not (args.get("hemodynamics") or args.get("stress_strain") or args.get("hi_pass") or args.get("spectrogram")):
         return
     from .hemodynamics import hemodynamics_refusal
     from .hi_pass import hi_pass_refusal
+    from .spectrogram import spectrogram_refusal
     from .stress_strain import stress_strain_refusal
     with contextlib.redirect_stdout(io.StringIO()):
         _, _, v = parameters(argv)
@@ -264,7 +267,7 @@ def _refuse_sessions(argv, backend_factory, world: int) -> None:
     else:
         cls = backend_factory if isinstance(backend_factory, type) else None
     for key, refusal in (("hemodynamics", hemodynamics_refusal), ("stress_strain", stress_strain_refusal),
-                         ("hi_pass", hi_pass_refusal)):
+                         ("hi_pass", hi_pass_refusal), ("spectrogram", spectrogram_refusal)):
         why = refusal(v, world, cls) if v.get(key) else ""
         if why:
             raise SystemExit(why)
@@ -486,6 +489,10 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
     if ns.get("hi_pass"):                         # as --hemodynamics: run() checked it; a backend without the device session
         from .hi_pass import HiPassRun            # records on the host (vasp_amd/hi_pass.py: HostBandSession)
         hipass = HiPassRun(backend, mesh, ns)
+    spectro = None
+    if ns.get("spectrogram"):                     # as --hi-pass, on a history and a node list of its own
+        from .spectrogram import SpectrogramRun   # (vasp_amd/spectrogram.py: HostSpecSession without the device session)
+        spectro = SpectrogramRun(backend, mesh, ns)
     first_step_num = ns["counter"]
 
     dt, T = float(ns["dt"]), float(ns["T"])
@@ -516,6 +523,8 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
                 stress.sample(t)
             if hipass is not None:
                 hipass.sample(ns["dvp_"]["n"].vector)
+            if spectro is not None:
+                spectro.sample(ns["dvp_"]["n"].vector)
         elif ns.get("save_step") and ns["counter"] % int(ns["save_step"]) == 0:
             ns["dvp_"]["n"].vector()              # partitioned: every rank takes part in the gather
         ns["counter"] += 1
@@ -532,6 +541,8 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
         stress.finish(out)
     if hipass is not None:                        # also after a killturtle / killtime stop: on the frames recorded so far
         hipass.finish(out)
+    if spectro is not None:
+        spectro.finish(out)
     ns["time_loop_seconds"] = _time.perf_counter() - t_loop
     ns["newton_iterations"] = total_newton
     ns["solver_events"] = events_seen

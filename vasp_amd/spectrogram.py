@@ -1,0 +1,543 @@
+"""Average spectrograms, power spectra, chromagrams and the spectral bandedness index of a run: `<results>/Spectrograms/`.
+
+Counterpart of ``vasp-create-spectrograms-chromagrams`` and ``vasp-create-spectrum``
+[REF src/vasp/postprocessing/postprocessing_h5py/create_spectrograms_chromagrams.py:21-219, create_spectrum.py:19-72,
+spectrograms.py:160-329,381-499,558-583,685-745,796-814], whose row loops around ``scipy.signal.spectrogram`` /
+``periodogram`` run on the device on a history recorded during the run (``HipBackend.spec_*``, csrc/fsi_spec.hip).  Because
+the transform is a matrix product on the FP64 matrix pipe, the sample can be every node of the region (``sampling All``) or
+a seeded draw; the reference's unseeded draw of 1000 nodes exists only because its row loop is slow.  This module holds
+
+* the region and sampling rules of ``read_spectrogram_data`` on the nodes of the run's own output (``select_nodes``);
+* the window arithmetic, the chroma filter bank (a restatement of the librosa formula the reference carries), the
+  chromagram and the SBI;
+* ``HostSpecSession``: the device session in NumPy - the same table, the same explicit detrend, the same order of the
+  sum over the rows - for a backend without ``spec_begin`` and as the yardstick of the GPU tests;
+* the pipeline, the writer of the reference's CSV files and the driver's side of ``--spectrogram`` (``SpectrogramRun``).
+
+Two of the reference's habits are kept on purpose: with a single row ``get_psd`` ignores the scaling it is given and
+returns scipy's default ``"density"`` (spectrograms.py:418-419), and the periodogram's window is always ``blackmanharris``
+whatever ``--spectrogram-window`` says (:410-419).
+
+Times: the frames are ``dt * save_step`` apart; ``T = frames * dt * save_step``, ``start_t = 0`` (the reference's default),
+``fs = frames / T``.
+
+Not done: ``domain`` sampling, the ``wss`` quantity, the PNG figures, ``sonify_point``, ``--stride``.
+"""
+from __future__ import annotations
+
+from pathlib import Path
+from typing import Dict, List, Optional
+
+import numpy as np
+
+from .hi_pass import expected_frames, filtfilt_rows, output_nodes
+from .mesh import FsiMesh
+
+HP_ORDER = 6                                    # filter_time_data(order=6, btype="highpass") [REF spectrograms.py:558]
+HP_PADLEN = 3 * (HP_ORDER + 1)                  # filtfilt's default for 7 coefficients
+N_CHROMA = 24                                   # [REF create_spectrograms_chromagrams.py:112]
+MIN_COLOR = {"d": -42, "v": -20, "p": -5}       # [REF spectrograms.py:133-147]
+COMPONENTS = ("all", "x", "y", "z", "mag")
+SAMPLINGS = ("RandomPoint", "PointList", "All")
+ROWS = 128                                      # csrc/fsi_spec.hpp: SPEC_ROWS
+PI_L = np.longdouble("3.14159265358979323846264338327950288")
+
+
+# ------------------------------------------------------------------------------------------------
+# options
+# ------------------------------------------------------------------------------------------------
+
+def add_arguments(ap, coerce) -> None:
+    """The ``--spectrogram*`` options of ``vasp_amd.monolithic`` (defaults: ``options``)."""
+    ap.add_argument("--spectrogram", dest="spectrogram", nargs="+", default=None, metavar="Q",
+                    help="record d, v and / or p at every saved frame on the device and write the average spectrogram, "
+                         "chromagram, SBI and power spectrum of a region to <results>/Spectrograms/ (what "
+                         "vasp-create-spectrograms-chromagrams and vasp-create-spectrum write afterwards)")
+    ap.add_argument("--spectrogram-region", dest="spectrogram_region", default=None, help="sphere (default) or box")
+    ap.add_argument("--spectrogram-fsi-region", dest="spectrogram_fsi_region", nargs="+", type=coerce, default=None,
+                    help="x y z r of the sphere, or x_min x_max y_min y_max z_min z_max of the box (default: the problem's fsi_region)")
+    ap.add_argument("--spectrogram-interface-only", dest="spectrogram_interface_only", action="store_const", const=True, default=None)
+    ap.add_argument("--spectrogram-component", dest="spectrogram_component", default=None, help="all (default), x, y, z or mag")
+    ap.add_argument("--spectrogram-sampling", dest="spectrogram_sampling", default=None,
+                    help="RandomPoint (default: n-samples region nodes drawn with --spectrogram-seed), PointList or All (every region node)")
+    ap.add_argument("--spectrogram-n-samples", dest="spectrogram_n_samples", type=int, default=None, help="default 1000")
+    ap.add_argument("--spectrogram-point-ids", dest="spectrogram_point_ids", nargs="+", type=coerce, default=None)
+    ap.add_argument("--spectrogram-seed", dest="spectrogram_seed", type=int, default=None, help="seed of the draw (default 0)")
+    ap.add_argument("--spectrogram-lowcut", dest="spectrogram_lowcut", type=float, default=None, help="high-pass cut-off in Hz (default 25)")
+    ap.add_argument("--spectrogram-overlap-frac", dest="spectrogram_overlap_frac", type=float, default=None, help="default 0.75")
+    ap.add_argument("--spectrogram-window", dest="spectrogram_window", default=None,
+                    help="a parameter-free scipy.signal.get_window name (default blackmanharris)")
+    ap.add_argument("--spectrogram-num-windows-per-sec", dest="spectrogram_num_windows_per_sec", type=coerce, default=None, help="default 4")
+    ap.add_argument("--spectrogram-min-color", dest="spectrogram_min_color", type=coerce, default=None,
+                    help="lower clamp of the log spectrogram (default: -42 for d, -20 for v, -5 for p)")
+
+
+def quantities(v: dict) -> List[str]:
+    q = v.get("spectrogram") or []
+    q = [q] if isinstance(q, str) else list(q)
+    bad = [x for x in q if x not in MIN_COLOR]
+    if bad:
+        raise SystemExit(f"--spectrogram takes d, v and / or p, got {bad}")
+    return [x for x in ("d", "v", "p") if x in q]
+
+
+def options(v: dict) -> dict:
+    """The resolved ``spectrogram_*`` parameters with the reference's defaults [REF spectrograms.py:56-105]."""
+    get = lambda key, default: default if v.get("spectrogram_" + key) is None else v["spectrogram_" + key]
+    o = dict(region=str(get("region", "sphere")), fsi_region=get("fsi_region", v.get("fsi_region")),
+             interface_only=bool(get("interface_only", False)), component=str(get("component", "all")),
+             sampling=str(get("sampling", "RandomPoint")), n_samples=int(get("n_samples", 1000)),
+             point_ids=get("point_ids", None), seed=int(get("seed", 0)), lowcut=float(get("lowcut", 25)),
+             overlap_frac=float(get("overlap_frac", 0.75)), window=str(get("window", "blackmanharris")),
+             num_windows_per_sec=get("num_windows_per_sec", 4), min_color=get("min_color", None))
+    if o["region"] not in ("sphere", "box"):
+        raise SystemExit(f"--spectrogram-region takes sphere or box, got {o['region']!r} ('domain' sampling is not built)")
+    if o["component"] not in COMPONENTS:
+        raise SystemExit(f"--spectrogram-component takes one of {', '.join(COMPONENTS)}, got {o['component']!r}")
+    if o["sampling"] not in SAMPLINGS:
+        raise SystemExit(f"--spectrogram-sampling takes one of {', '.join(SAMPLINGS)}, got {o['sampling']!r}")
+    fr = None if o["fsi_region"] is None else [float(x) for x in np.atleast_1d(o["fsi_region"])]
+    if fr is None or len(fr) != (4 if o["region"] == "sphere" else 6):
+        raise SystemExit("--spectrogram-fsi-region takes x y z r for a sphere and x_min x_max y_min y_max z_min z_max for a box")
+    o["fsi_region"] = fr
+    if o["point_ids"] is not None:
+        o["point_ids"] = [int(x) for x in np.atleast_1d(o["point_ids"])]
+    if o["sampling"] == "PointList" and not o["point_ids"]:
+        raise SystemExit("--spectrogram-sampling PointList needs --spectrogram-point-ids")
+    if o["sampling"] == "RandomPoint" and o["n_samples"] < 1:
+        raise SystemExit("--spectrogram-n-samples must be at least 1")
+    if not 0.0 <= o["overlap_frac"] < 1.0:
+        raise SystemExit("--spectrogram-overlap-frac must be in [0, 1)")
+    try:
+        window_values(o["window"], 8)
+    except Exception as e:
+        raise SystemExit(f"--spectrogram-window: {o['window']!r} is not a parameter-free scipy.signal.get_window name ({e})")
+    return o
+
+
+# ------------------------------------------------------------------------------------------------
+# window arithmetic
+# ------------------------------------------------------------------------------------------------
+
+def shift_bit_length(x: int) -> int:
+    """The smallest power of two >= x [REF spectrograms.py:381-394]."""
+    return 1 << (int(x) - 1).bit_length()
+
+
+def window_values(name: str, n: int) -> np.ndarray:
+    """``scipy.signal.get_window(name, n)`` (periodic), as scipy's spectrogram and periodogram call it."""
+    from scipy.signal import get_window
+    return np.asarray(get_window(str(name), int(n)), dtype=np.float64)
+
+
+def window_plan(n: int, T: float, num_windows_per_sec, overlap_frac: float) -> dict:
+    """The segment sizes of ``create_spectrogram_composite`` / ``get_spectrogram`` for n frames over T seconds
+    [REF create_spectrograms_chromagrams.py:50, spectrograms.py:446-453]: ``num_windows`` stays the float numpy makes of it
+    (the file names print it so), ``nseg`` is scipy's count of whole segments."""
+    num_windows = np.round(num_windows_per_sec * T) + 3
+    per = int(n / num_windows)
+    nperseg = shift_bit_length(per) if per >= 1 else 0
+    noverlap = int(overlap_frac * nperseg)
+    step = nperseg - noverlap
+    nseg = (n - noverlap) // step if nperseg >= 1 and step >= 1 and n >= nperseg else 0
+    return dict(num_windows=num_windows, nperseg=nperseg, noverlap=noverlap, nfft=2 * nperseg, nseg=int(nseg))
+
+
+def highpass_design(fs: float, lowcut: float) -> dict:
+    """``butter(6, lowcut / (fs / 2), "highpass")`` [REF spectrograms.py:516-525,558], ``lfilter_zi`` and filtfilt's padlen."""
+    from scipy.signal import butter, lfilter_zi
+    b, a = butter(HP_ORDER, lowcut / (0.5 * fs), btype="highpass")
+    return dict(b=np.asarray(b, dtype=np.float64), a=np.asarray(a, dtype=np.float64), zi=np.asarray(lfilter_zi(b, a)),
+                padlen=3 * max(len(a), len(b)))
+
+
+# ------------------------------------------------------------------------------------------------
+# chroma, SBI
+# ------------------------------------------------------------------------------------------------
+
+def chroma_filterbank(sr: float, n_fft: int, n_chroma: int = N_CHROMA, ctroct: float = 5.0, octwidth: float = 2.0) -> np.ndarray:
+    """The chroma filter bank of the reference's tools (the librosa chroma filter at tuning 0, [REF chroma_filters.py:397-531]),
+    written from its definition; (n_chroma, n_fft // 2 + 1), float32 as the reference's.
+
+    FFT bin k > 0 has the pitch ``p_k = n_chroma log2(f_k / 27.5 Hz)`` in chroma steps, ``f_k = k sr / n_fft``; the 0 Hz bin is put
+    1.5 octaves below bin 1.  Chroma class c answers to bin k with ``exp(-2 (d / s_k)^2)``: d is p_k - c wrapped into
+    [-n_chroma / 2, n_chroma / 2), s_k the distance to the next bin's pitch but at least one step (1 for the last bin).  Every
+    bin's column is scaled to unit Euclidean length, then weighted by ``exp(-((p_k / n_chroma - ctroct) / octwidth)^2 / 2)``, the
+    preference for the octaves around ``ctroct``; class 0 is C, a quarter octave above A."""
+    classes = np.arange(n_chroma, dtype=np.float64)[:, None]
+    pitch = np.empty(n_fft)
+    pitch[1:] = n_chroma * np.log2(np.arange(1, n_fft) * (sr / n_fft) / 27.5)
+    pitch[0] = pitch[1] - 1.5 * n_chroma
+    spacing = np.ones(n_fft)
+    spacing[:-1] = np.maximum(np.diff(pitch), 1.0)
+    half = n_chroma // 2
+    wrapped = np.mod(pitch[None, :] - classes + half, n_chroma) - half
+    bank = np.exp(-2.0 * np.square(wrapped / spacing[None, :]))
+    bank /= np.linalg.norm(bank, axis=0)[None, :]
+    bank *= np.exp(-0.5 * np.square((pitch / n_chroma - ctroct) / octwidth))[None, :]
+    from_c = (np.arange(n_chroma) + n_chroma // 4) % n_chroma            # row c of the result is the class a quarter octave above c
+    return bank[from_c, :n_fft // 2 + 1].astype(np.float32)
+
+
+def chromagram(Pxx: np.ndarray, fs: float, n_fft: int, n_chroma: int = N_CHROMA) -> np.ndarray:
+    """The chroma filter bank applied to a (bins, segments) power, every segment's classes scaled to sum 1 - the reference's
+    ``norm="sum"`` [REF spectrograms.py:685-727], which the entropy below needs."""
+    energy = chroma_filterbank(fs, n_fft, n_chroma) @ Pxx
+    return energy / energy.sum(axis=0, keepdims=True)
+
+
+def sbi(chroma: np.ndarray, n_chroma: int = N_CHROMA) -> np.ndarray:
+    """Spectral bandedness index per segment, ``1 + sum_c c log c / log n_chroma``: 0 for a flat chromagram, 1 for a single
+    class [REF spectrograms.py:730-745]."""
+    return 1.0 + (chroma * np.log(chroma)).sum(axis=0) / np.log(n_chroma)
+
+
+# ------------------------------------------------------------------------------------------------
+# the device's arithmetic in NumPy
+# ------------------------------------------------------------------------------------------------
+
+def spec_tables(K: int, nfft: int, bin0: int, nb: int):
+    """C, S (nb, K): cos / sin(2 pi (j k mod nfft) / nfft) for the bins k = bin0 .. bin0 + nb - 1, the angle formed in
+    extended precision and the value rounded to FP64 once - what fsi_capi.hip uploads."""
+    m = np.arange(nfft, dtype=np.longdouble)
+    ang = (np.longdouble(2) * PI_L) * m / np.longdouble(nfft)
+    cosm, sinm = np.cos(ang).astype(np.float64), np.sin(ang).astype(np.float64)
+    jk = np.outer(np.arange(bin0, bin0 + nb, dtype=np.int64), np.arange(K, dtype=np.int64)) % nfft
+    return cosm[jk], sinm[jk]
+
+
+def block_sums(P: np.ndarray) -> np.ndarray:
+    """(bins, rows) -> (bins, row blocks): the sum over the rows of every block of ROWS rows in k_spec_power's order - in a
+    lane the block's eight 16-row tiles one after the other, then a four-step butterfly over the 16 lanes."""
+    nb, rows = P.shape
+    nblk = -(-rows // ROWS)
+    full = np.zeros((nb, nblk * ROWS))
+    full[:, :rows] = P
+    tiles = full.reshape(nb, nblk, ROWS // 16, 16)
+    lane = np.zeros((nb, nblk, 16))
+    for a in range(ROWS // 16):
+        lane = lane + tiles[:, :, a, :]
+    for half in (8, 4, 2, 1):
+        lane = lane[:, :, :half] + lane[:, :, half:2 * half]
+    return lane[:, :, 0]
+
+
+def mean_power(x: np.ndarray, K: int, step: int, nseg: int, nfft: int, window: np.ndarray, scaling: str, fs: float,
+               max_table_bytes: int = 1 << 27) -> np.ndarray:
+    """(nfft // 2 + 1, nseg): the average over the rows of x (frames, rows) of the one-sided power of nseg segments of K
+    frames, ``step`` apart - fsi_spec.hip operation for operation except the order inside a dot product (BLAS here, the
+    matrix pipe's there)."""
+    x = np.asarray(x, dtype=np.float64)
+    rows = x.shape[1]
+    w = np.asarray(window, dtype=np.float64)
+    sw = sw2 = 0.0
+    for v in w:
+        sw += float(v)
+        sw2 += float(v) * float(v)
+    scale = 1.0 / (fs * sw2) if scaling == "density" else 1.0 / (sw * sw)
+    nbins = nfft // 2 + 1
+    last_single = nfft // 2 if nfft % 2 == 0 else -1
+    out = np.empty((nbins, nseg))
+    slab = max(1, min(nbins, max_table_bytes // (16 * K)))
+    chunk = 32 * ROWS
+    for seg in range(nseg):
+        xs = x[seg * step:seg * step + K]
+        acc = np.zeros(rows)
+        for j in range(K):
+            acc = acc + xs[j]
+        Y = w[:, None] * (xs - (acc / float(K))[None, :])
+        for bin0 in range(0, nbins, slab):
+            nb = min(slab, nbins - bin0)
+            C, S = spec_tables(K, nfft, bin0, nb)
+            parts = []
+            for r0 in range(0, rows, chunk):
+                re, im = C @ Y[:, r0:r0 + chunk], S @ Y[:, r0:r0 + chunk]
+                parts.append(block_sums((re * re + im * im) * scale))
+            part = np.concatenate(parts, axis=1)
+            g = np.arange(bin0, bin0 + nb)
+            part = np.where(((g == 0) | (g == last_single))[:, None], part, 2.0 * part)
+            tot = np.zeros(nb)
+            for k in range(part.shape[1]):
+                tot = tot + part[:, k]
+            out[bin0:bin0 + nb, seg] = tot / float(rows)
+    return out
+
+
+class HostSpecSession:
+    """The session of one quantity on the host, method for method ``HipBackend.spec_*`` without the quantity argument."""
+
+    def __init__(self, nrows: int, capacity: int):
+        self.nrows, self.capacity = int(nrows), int(capacity)
+        self.raw: List[np.ndarray] = []
+        self.filtered = None
+
+    def sample(self, rows: np.ndarray) -> None:
+        if len(self.raw) >= self.capacity:
+            raise RuntimeError("spectrogram history is full (capacity declared at begin)")
+        self.raw.append(np.array(rows, dtype=np.float64).reshape(self.nrows))
+        self.filtered = None
+
+    def filter(self, b=None, a=None, zi=None, padlen: int = 0) -> None:
+        self.filtered = None if b is None else filtfilt_rows(b, a, np.stack(self.raw), zi, padlen)
+
+    def fetch(self, frame: int, filtered: bool = False) -> np.ndarray:
+        return self.filtered[frame] if filtered else self.raw[frame]
+
+    def _source(self) -> np.ndarray:
+        return self.filtered if self.filtered is not None else np.stack(self.raw)
+
+    def spectrogram(self, nperseg: int, noverlap: int, nfft: int, window, scaling: str, fs: float) -> np.ndarray:
+        x = self._source()
+        step = nperseg - noverlap
+        return mean_power(x, nperseg, step, (len(x) - noverlap) // step, nfft, window, scaling, fs)
+
+    def periodogram(self, window, scaling: str, fs: float) -> np.ndarray:
+        x = self._source()
+        return mean_power(x, len(x), len(x), 1, len(x), window, scaling, fs)[:, 0]
+
+
+def component_rows(values: np.ndarray, component: str) -> np.ndarray:
+    """The rows of one frame from the (nodes, ncomp) values at the sampled nodes: a component, the three stacked
+    component-major, or the magnitude; a scalar has one."""
+    values = np.asarray(values, dtype=np.float64)
+    if values.ndim == 1 or values.shape[1] == 1:
+        return values.reshape(-1)
+    if component == "all":
+        return values.T.reshape(-1)
+    if component == "mag":
+        return np.sqrt((values[:, 0] * values[:, 0] + values[:, 1] * values[:, 1]) + values[:, 2] * values[:, 2])
+    return values[:, "xyz".index(component)].copy()
+
+
+# ------------------------------------------------------------------------------------------------
+# region and sampling rules
+# ------------------------------------------------------------------------------------------------
+
+def degree_of(quantity: str, save_deg: int) -> int:
+    """The output the rows live on: the run's save_deg, the pressure at degree 1 (the reference's choice when no degree is
+    given [REF create_spectrograms_chromagrams.py:237])."""
+    return 1 if quantity == "p" else int(save_deg)
+
+
+def region_ids(mesh: FsiMesh, deg: int, quantity: str, v: dict, o: dict) -> np.ndarray:
+    """Ids, on the degree-``deg`` output node list, of the nodes the spectrogram of ``quantity`` may sample
+    [REF spectrograms.py:221-266]: solid nodes for d, fluid nodes for v and p, the nodes the two share with
+    ``interface_only``; of those, the ones strictly inside the sphere or the open box."""
+    cells = mesh.tet_nodes if deg >= 2 else mesh.tets
+    coords = mesh.node_coords if deg >= 2 else mesh.coords
+    as_list = lambda x: list(x) if isinstance(x, (list, tuple)) else [x]
+    fluid = np.unique(cells[np.isin(mesh.cell_markers, as_list(v["dx_f_id"]))])
+    solid = np.unique(cells[np.isin(mesh.cell_markers, as_list(v["dx_s_id"]))])
+    if o["interface_only"]:
+        ids = np.intersect1d(fluid, solid)
+    else:
+        ids = solid if quantity == "d" else fluid
+    fr = o["fsi_region"]
+    if o["region"] == "sphere":
+        inside = np.where(np.linalg.norm(coords - np.array(fr[:3]), axis=1) < fr[3])[0]
+    else:
+        inside = np.where((coords[:, 0] > fr[0]) & (coords[:, 0] < fr[1]) & (coords[:, 1] > fr[2]) & (coords[:, 1] < fr[3])
+                          & (coords[:, 2] > fr[4]) & (coords[:, 2] < fr[5]))[0]
+    return np.intersect1d(inside, ids)
+
+
+def select_nodes(mesh: FsiMesh, save_deg: int, quantity: str, v: dict, o: dict) -> dict:
+    """The sampled rows of one quantity: ``ids`` on the output node list, the (nodes, nodes_b) a session is opened on, and
+    the two name parts of the files [REF spectrograms.py:268-287].  RandomPoint draws n_samples region nodes with
+    replacement, as the reference does, from ``numpy.random.default_rng(seed)``; All is every region node once."""
+    deg = degree_of(quantity, save_deg)
+    region = region_ids(mesh, deg, quantity, v, o)
+    if len(region) == 0:
+        raise SystemExit(f"--spectrogram {quantity}: no nodes found in the specified fsi region: {o['fsi_region']}")
+    comp = o["component"]
+    suffix = ""
+    if o["sampling"] == "RandomPoint":
+        ids = np.random.default_rng(o["seed"]).choice(region, o["n_samples"])
+        name = f"{quantity}_{comp}_n_samples_{o['n_samples']}"
+    elif o["sampling"] == "PointList":
+        ids = np.array(o["point_ids"], dtype=np.int64)
+        limit = mesh.num_nodes if deg >= 2 else mesh.num_vertices
+        if ((ids < 0) | (ids >= limit)).any():
+            raise SystemExit(f"--spectrogram-point-ids: ids must be in 0 .. {limit - 1} (the degree-{deg} output of {quantity})")
+        name, suffix = f"{quantity}_{comp}", f"_PointList_{o['point_ids']}"
+    else:
+        ids, name = region, f"{quantity}_{comp}"
+    nodes, nodes_b = output_nodes(mesh, deg, quantity)
+    return dict(ids=np.asarray(ids, dtype=np.int64), nodes=nodes[ids], nodes_b=None if nodes_b is None else nodes_b[ids],
+                name=name, case_suffix=suffix, degree=deg)
+
+
+# ------------------------------------------------------------------------------------------------
+# pipeline and files
+# ------------------------------------------------------------------------------------------------
+
+def pipeline(session, nrows: int, n: int, T: float, start_t: float, o: dict, min_color) -> dict:
+    """``create_spectrogram_composite`` and ``create_spectrum`` on a session (``HostSpecSession`` or its device twin behind
+    the same calls) that holds n frames of nrows rows: the clamped log spectrogram of the high-passed rows, the chromagram
+    and SBI of the raw rows' spectrogram, and the log of the raw rows' average periodogram."""
+    fs = n / T
+    plan = window_plan(n, T, o["num_windows_per_sec"], o["overlap_frac"])
+    K, nov, nfft = plan["nperseg"], plan["noverlap"], plan["nfft"]
+    w = window_values(o["window"], K)
+    freqs = np.fft.rfftfreq(nfft, 1 / fs)
+    bins = np.arange(K / 2, n - K / 2 + 1, K - nov) / float(fs) + start_t
+
+    def scaled(P):                      # get_spectrogram's guard and spectrogram_scaling [REF spectrograms.py:471,491-497]
+        P = np.array(P)
+        P[P < 0] = 1e-16
+        with np.errstate(divide="ignore"):
+            L = np.log(P)
+        L[L < min_color] = min_color
+        return L
+
+    hp = highpass_design(fs, o["lowcut"])
+    session.filter(hp["b"], hp["a"], hp["zi"], hp["padlen"])
+    P_filtered = session.spectrogram(K, nov, nfft, w, "spectrum", fs)
+    session.filter()
+    P_raw = session.spectrogram(K, nov, nfft, w, "spectrum", fs)
+    chroma = chromagram(np.exp(scaled(P_raw)), fs, nfft)
+    scaling = "spectrum" if nrows > 1 else "density"          # get_psd's single-row branch drops the scaling it is given
+    P_psd = session.periodogram(window_values("blackmanharris", n), scaling, fs)
+    with np.errstate(divide="ignore"):
+        log_psd = np.log(P_psd)
+    return dict(plan=plan, fs=fs, freqs=freqs, bins=bins, spectrogram=scaled(P_filtered), chroma=chroma, sbi=sbi(chroma),
+                psd_freqs=np.fft.rfftfreq(n, 1 / fs), psd=log_psd, power_filtered=P_filtered, power_raw=P_raw, power_psd=P_psd,
+                psd_scaling=scaling)
+
+
+def file_names(name: str, case: str, num_windows, min_color) -> Dict[str, str]:
+    """[REF create_spectrograms_chromagrams.py:192,203,214; create_spectrum.py:60]"""
+    stem = f"{name}_{case}_{num_windows}_windows"
+    return dict(spectrogram=f"{stem}_thresh{min_color}_spectrogram.csv", chromagram=f"{stem}_chromagram.csv", sbi=f"{stem}_SBI.csv",
+                psd=f"{name}_psd_no_filter_{case}.csv")
+
+
+def write_files(folder, name: str, case: str, res: dict, min_color) -> Dict[str, Path]:
+    """The four CSV files, readable by whatever reads the reference's [REF create_spectrograms_chromagrams.py:197-219;
+    create_spectrum.py:68-69]: comma-separated ``np.savetxt`` tables; spectrogram and chromagram under a ``# `` header line of
+    the segment times with two decimals, one row per frequency / chroma class with the frequency / the class's place in
+    linspace(0, 1, 24) in front; SBI as (time, SBI) rows; the spectrum as (frequency, log power) rows."""
+    folder = Path(folder)
+    folder.mkdir(parents=True, exist_ok=True)
+    paths = {k: folder / f for k, f in file_names(name, case, res["plan"]["num_windows"], min_color).items()}
+    times = ",".join(f"{t:.2f}" for t in res["bins"])
+    classes = np.linspace(0, 1, len(res["chroma"]))
+    tables = dict(spectrogram=(np.column_stack([res["freqs"], res["spectrogram"]]), times),
+                  chromagram=(np.column_stack([classes, res["chroma"]]), times),
+                  sbi=(np.column_stack([res["bins"], res["sbi"]]), "t (s), SBI"),
+                  psd=(np.column_stack([res["psd_freqs"], res["psd"]]), "Freqs(Hz),spectrum"))
+    for key, (table, header) in tables.items():
+        np.savetxt(paths[key], table, delimiter=",", header=header)
+    return paths
+
+
+# ------------------------------------------------------------------------------------------------
+# the driver's side
+# ------------------------------------------------------------------------------------------------
+
+def spectrogram_refusal(v: dict, world: int, backend_cls) -> str:
+    """Why ``--spectrogram`` cannot run with the resolved parameters ``v`` ('' if it can); as ``hi_pass_refusal``."""
+    quantities(v)
+    o = options(v)
+    if not v.get("save_step"):
+        return "--spectrogram records the saved frames: it needs --save-step"
+    if v.get("restart_folder"):
+        return "--spectrogram does not carry its history through a checkpoint: it cannot be used with --restart-folder"
+    if world > 1:
+        return "--spectrogram runs on one rank only (WORLD_SIZE > 1)"
+    frames = expected_frames(v)
+    if frames < HP_PADLEN + 1:
+        return f"--spectrogram: the run saves {frames} frames, the high-pass filter needs at least padlen + 1 = {HP_PADLEN + 1}"
+    T = frames * float(v["dt"]) * int(v["save_step"])
+    plan = window_plan(frames, T, o["num_windows_per_sec"], o["overlap_frac"])
+    if plan["nseg"] < 2:
+        return (f"--spectrogram: {frames} frames over {T:g} s in {plan['num_windows']:g} windows (--spectrogram-num-windows-per-sec) give "
+                f"segments of {plan['nperseg']} frames and {plan['nseg']} of them: a spectrogram needs at least two")
+    return ""
+
+
+class _DeviceSession:
+    """``HipBackend.spec_*`` of one quantity behind ``HostSpecSession``'s calls."""
+
+    def __init__(self, backend, q: str):
+        self.backend, self.q = backend, q
+
+    def filter(self, b=None, a=None, zi=None, padlen: int = 0) -> None:
+        self.backend.spec_filter(self.q, b, a, zi, padlen)
+
+    def spectrogram(self, *args):
+        return self.backend.spec_spectrogram(self.q, *args)
+
+    def periodogram(self, *args):
+        return self.backend.spec_periodogram(self.q, *args)
+
+
+class SpectrogramRun:
+    """The driver's side of ``--spectrogram``: per quantity one session on the sampled nodes, one recorded frame per saved
+    frame, and at the end the four files.  A backend without ``spec_begin`` records and transforms on the host."""
+
+    def __init__(self, backend, mesh: FsiMesh, ns: dict):
+        self.backend, self.mesh = backend, mesh
+        self.quantities = quantities(ns)
+        self.opts = options(ns)
+        self.save_deg = int(ns["save_deg"])
+        self.dt_files = float(ns["dt"]) * int(ns["save_step"])
+        self.folder = Path(ns["results_folder"]) / "Spectrograms"
+        self.case = Path(ns["results_folder"]).parent.name
+        capacity = expected_frames(ns) + 1
+        self.device = hasattr(backend, "spec_begin")
+        self.sel = {q: select_nodes(mesh, self.save_deg, q, ns, self.opts) for q in self.quantities}     # an empty region ends the run here
+        self.host: Dict[str, HostSpecSession] = {}
+        self.frames = 0
+        for q in self.quantities:
+            s = self.sel[q]
+            if self.device:
+                backend.spec_begin(q, s["nodes"], s["nodes_b"], self.opts["component"], capacity)
+            else:
+                self.host[q] = HostSpecSession(self.rows(q), capacity)
+
+    def rows(self, q: str) -> int:
+        return len(self.sel[q]["ids"]) * (3 if q != "p" and self.opts["component"] == "all" else 1)
+
+    def min_color(self, q: str):
+        return MIN_COLOR[q] if self.opts["min_color"] is None else self.opts["min_color"]
+
+    def _host_rows(self, q: str, state: np.ndarray) -> np.ndarray:
+        d, v, p = self.mesh.split(state)
+        s = self.sel[q]
+        if q == "p":
+            a = p[s["nodes"]]
+            if s["nodes_b"] is not None:
+                b = s["nodes_b"]
+                a = np.where(b < 0, a, 0.5 * (a + p[np.maximum(b, 0)]))
+            return a
+        return component_rows((d if q == "d" else v)[s["nodes"]], self.opts["component"])
+
+    def sample(self, state=None) -> None:
+        """Record dvp_["n"]; ``state``: a callable giving the host copy, used only without the device session."""
+        for q in self.quantities:
+            if self.device:
+                self.backend.spec_sample(q)
+            else:
+                self.host[q].sample(self._host_rows(q, state()))
+        self.frames += 1
+
+    def finish(self, out=print) -> None:
+        n = self.frames
+        try:
+            T = n * self.dt_files
+            plan = window_plan(n, T, self.opts["num_windows_per_sec"], self.opts["overlap_frac"]) if n else dict(nseg=0)
+            if n <= HP_PADLEN or plan["nseg"] < 2:
+                out(f"Spectrograms: {n} frames recorded, too few for the high-pass filter (more than {HP_PADLEN}) and two segments: "
+                    "nothing written")
+                return
+            for q in self.quantities:
+                session = _DeviceSession(self.backend, q) if self.device else self.host[q]
+                res = pipeline(session, self.rows(q), n, T, 0.0, self.opts, self.min_color(q))
+                write_files(self.folder, self.sel[q]["name"], self.case + self.sel[q]["case_suffix"], res, self.min_color(q))
+            out(f"Spectrograms of {n} frames ({', '.join(self.quantities)}; {self.opts['sampling']}, "
+                f"{', '.join(str(self.rows(q)) for q in self.quantities)} rows) written to {self.folder}")
+        finally:
+            if self.device:
+                for q in self.quantities:
+                    self.backend.spec_end(q)
