@@ -361,7 +361,8 @@ int fsi_stress_end(FsiCtx* ctx);
  * pressure at an edge node of the save_deg 2 output).  capacity: frames the history can take.  The bytes of the history, the
  * filtered series (capacity + 66 frames) and three work frames are compared with the free device memory: if less than 1/16
  * of the device would stay free for the context, FSI_ERR_INVALID with both byte counts in fsi_last_error and nothing
- * allocated - no paging, no truncation.  Replaces an open session of the quantity.  Not for partitioned contexts. */
+ * allocated - no paging, no truncation.  Replaces an open session of the quantity; a refused call (node out of range,
+ * capacity, device memory) leaves it as it was, its bytes counted as taken.  Not for partitioned contexts. */
 int fsi_band_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* nodes, const int32_t* nodes_b, int64_t capacity);
 /* Replaces: reading one frame of <quantity>.h5 [REF .../postprocessing_h5py_common.py:154-409, its frame loop]: the session's rows of
  * dvp_["n"] go to the next frame of the history, stream-ordered behind the time step; the host does not wait.

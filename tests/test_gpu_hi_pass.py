@@ -203,6 +203,35 @@ def test_a_history_beyond_device_memory_is_refused_and_the_context_still_steps(s
         hb.close()
 
 
+def test_a_refused_begin_leaves_the_open_session_of_the_quantity_as_it_was(cylinder_case):
+    """As fsi_spec_begin: a begin refused for a node out of range or for a history beyond the device keeps the history the
+    caller had - its frames can be fetched and the next sample goes behind them."""
+    from vasp_amd.capi import FsiError, HipBackend
+    mesh, desc = cylinder_case[0]["mesh"], cylinder_case[1]
+    V, N2 = mesh.num_vertices, mesh.num_nodes
+    hb = HipBackend(desc)
+    try:
+        states = 1e-4 * np.random.default_rng(9).standard_normal((4, hb.ndof))
+        hb.hi_pass_begin("v", np.arange(V), None, 8)
+        for k in range(3):
+            hb.set_state("n", states[k])
+            hb.hi_pass_sample("v")
+        third = states[2, 3 * N2:3 * N2 + 3 * V].reshape(V, 3)
+        assert np.array_equal(hb.hi_pass_fetch("v", "raw", 2), third)
+        with pytest.raises(FsiError, match="node out of range"):
+            hb.hi_pass_begin("v", [N2], None, 8)
+        total_b = hb.device_memory()[1]
+        with pytest.raises(FsiError, match=r"needs \d+ bytes .* has \d+ bytes free"):
+            hb.hi_pass_begin("v", np.arange(V), None, int(total_b // (8 * 3 * V)) + 1)      # the raw history alone exceeds the device
+        assert np.array_equal(hb.hi_pass_fetch("v", "raw", 2), third)
+        hb.set_state("n", states[3])
+        hb.hi_pass_sample("v")
+        assert np.array_equal(hb.hi_pass_fetch("v", "raw", 3), states[3, 3 * N2:3 * N2 + 3 * V].reshape(V, 3))
+        assert np.array_equal(hb.hi_pass_fetch("v", "raw", 2), third)
+    finally:
+        hb.close()
+
+
 def test_all_sessions_side_by_side_and_destroy_without_end(cylinder_case):
     from vasp_amd.capi import HipBackend
     from vasp_amd.hemodynamics import fluid_boundary_facets

@@ -100,6 +100,36 @@ def test_amplitude_magnitude_is_numpys_norm():
     assert np.array_equal(hp.amplitude_magnitude(a[:, :1]), a[:, 0])
 
 
+def _host_sessions(capacity):
+    from vasp_amd.spectrogram import HostSpecSession
+    return hp.HostBandSession(3, capacity), HostSpecSession(6, capacity)
+
+
+def test_the_two_host_sessions_record_and_filter_the_same_history():
+    """One recording half (HostHistory): the same frames in, the same bytes out of both sessions, raw and filtered."""
+    frames = np.random.default_rng(5).standard_normal((40, 6))
+    prm = hp.design(1e-3, 25.0, 1000.0)
+    band, spec = _host_sessions(40)
+    for s in (band, spec):
+        for f in frames:
+            s.sample(f)
+        s.filter(prm["b"], prm["a"], prm["zi"], prm["padlen"])
+    for k in range(40):
+        assert band.fetch("raw", k).tobytes() == spec.fetch(k).tobytes() == frames[k].tobytes(), k
+        assert band.fetch("filtered", k).tobytes() == spec.fetch(k, filtered=True).tobytes(), k
+    assert band.fetch("raw", 0).shape == (2, 3) and spec.fetch(0).shape == (6,)
+    assert np.array_equal(np.stack(spec.filtered), hp.filtfilt_rows(prm["b"], prm["a"], frames, prm["zi"], prm["padlen"]))
+
+
+def test_both_host_sessions_refuse_a_frame_beyond_their_capacity():
+    for s, name in zip(_host_sessions(3), ("hi-pass", "spectrogram")):
+        for _ in range(3):
+            s.sample(np.zeros(6))
+        with pytest.raises(RuntimeError, match=name + r" history is full \(capacity declared at begin\)"):
+            s.sample(np.zeros(6))
+        assert len(s.raw) == 3
+
+
 # ---- the band rules ---------------------------------------------------------------------------------------------------
 
 def test_band_rules_give_the_reference_numbers():

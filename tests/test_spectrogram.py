@@ -493,6 +493,8 @@ def test_header_and_binding_agree_on_the_spec_entry_points():
         assert hasattr(capi.HipBackend, meth)
     src = (ROOT / "vasp_amd" / "csrc" / "fsi_spec.hip").read_text()
     assert "__builtin_amdgcn_mfma_f64_16x16x4f64" in src and "atomicAdd" not in src
-    assert "launch_band_sample" in (ROOT / "vasp_amd" / "csrc" / "fsi_capi.hip").read_text().split("int fsi_spec_sample")[1].split("int fsi_spec_fetch")[0]
+    sessions = (ROOT / "vasp_amd" / "csrc" / "fsi_sessions.hip").read_text()      # the band-pass session's sampling kernel, through the shared history
+    assert "history_sample(" in sessions.split("int fsi_spec_sample")[1].split("int fsi_spec_fetch")[0]
+    assert "launch_band_sample" in sessions.split("int history_sample")[1].split("int history_filter")[0]
     hpp = (ROOT / "vasp_amd" / "csrc" / "fsi_spec.hpp").read_text()
     assert int(re.search(r"SPEC_ROWS = (\d+)", hpp).group(1)) == sp.ROWS

@@ -1,5 +1,5 @@
 // Band-pass filtered fields and vibration amplitudes of a run (fsi_band.hip): sizes, the filter's coefficients as a kernel
-// argument, and the launchers the C-ABI (fsi_band_* in fsi_capi.hip) calls.
+// argument, and the launchers the C-ABI (fsi_band_* in fsi_sessions.hip) calls.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -3,7 +3,6 @@
 // Host-side logic follows turtleFSI's monolithic.py / newtonsolver.py as VaSP uses them; the
 // arithmetic runs in the HIP kernels of fsi_assembly.hip / fsi_solver.hip.
 #include "fsi_host.hpp"
-#include "fsi_spec.hpp"
 
 using namespace fsi;
 using namespace fsi::host;
@@ -1502,623 +1501,6 @@ int fsi_wall_shear_stress(FsiCtx* ctx, int64_t nf, const int32_t* facet_cells, c
     for (int k = 0; k < 3; ++k)
       for (int i = 0; i < 3; ++i) out[(f * 3 + k) * 3 + i] = h[((size_t)slot[f] * 4 + VERTS[facet_local[f]][k]) * 3 + i];
   dc.release(); dm.release(); dout.release();
-  return FSI_OK;
-}
-
-namespace {
-HemoAcc hemo_acc(FsiCtx* ctx) {
-  double* a = ctx->hemo.acc.p;
-  const int64_t nd = 3 * ctx->hemo.nf;
-  return HemoAcc{a, a + 3 * nd, a + 6 * nd, a + 7 * nd};
-}
-}  // namespace
-
-int fsi_hemo_begin(FsiCtx* ctx, int64_t nf, const int32_t* facet_cells, const int32_t* facet_local, double mu,
-                   double dt_sample) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (nf <= 0 || !facet_cells || !facet_local || !(mu > 0.0) || !(dt_sample > 0.0)) {
-    ctx->err = "fsi_hemo_begin: needs nf > 0 facets, mu > 0 and dt_sample > 0";
-    return FSI_ERR_INVALID;
-  }
-  if (ctx->part) { ctx->err = "fsi_hemo_begin: partitioned contexts are not supported"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  // as fsi_wall_shear_stress: one projection per boundary cell, a mask of its listed facets, and here the user index of each
-  std::vector<int32_t> ucell, mask, fidx;
-  {
-    std::vector<std::pair<int32_t, int64_t>> order((size_t)nf);
-    for (int64_t f = 0; f < nf; ++f) {
-      if (facet_cells[f] < 0 || facet_cells[f] >= ctx->C || facet_local[f] < 0 || facet_local[f] > 3) {
-        ctx->err = "fsi_hemo_begin: facet cell / local index out of range";
-        return FSI_ERR_INVALID;
-      }
-      order[f] = {facet_cells[f], f};
-    }
-    std::sort(order.begin(), order.end());
-    for (int64_t k = 0; k < nf; ++k) {
-      const int64_t f = order[k].second;
-      if (k == 0 || order[k].first != order[k - 1].first) {
-        ucell.push_back(order[k].first);
-        mask.push_back(0);
-        for (int j = 0; j < 4; ++j) fidx.push_back(-1);
-      }
-      if (mask.back() & (1 << facet_local[f])) { ctx->err = "fsi_hemo_begin: a facet is listed twice"; return FSI_ERR_INVALID; }
-      mask.back() |= 1 << facet_local[f];
-      fidx[(ucell.size() - 1) * 4 + facet_local[f]] = (int32_t)f;
-    }
-  }
-  // 12-point degree-6 rule on the reference triangle (FIAT _triangle_scheme(6), oracle.fsi_oracle.triangle12)
-  double tw[12], tl[12][3];
-  {
-    const double pa[2] = {0.063089014491502, 0.249286745170910}, pw[2] = {0.050844906370207, 0.116786275726379};
-    double px[12], py[12];
-    int q = 0;
-    for (int o = 0; o < 2; ++o) {
-      const double a = pa[o], b = 1.0 - 2.0 * a;
-      const double xy[3][2] = {{a, a}, {b, a}, {a, b}};
-      for (int k = 0; k < 3; ++k, ++q) { px[q] = xy[k][0]; py[q] = xy[k][1]; tw[q] = pw[o] / 2.0; }
-    }
-    const double a = 0.053145049844817, b = 0.310352451033784, c = 1.0 - a - b;
-    const double xy[6][2] = {{a, b}, {b, a}, {a, c}, {c, a}, {b, c}, {c, b}};
-    for (int k = 0; k < 6; ++k, ++q) { px[q] = xy[k][0]; py[q] = xy[k][1]; tw[q] = 0.082851075618374 / 2.0; }
-    for (q = 0; q < 12; ++q) { tl[q][0] = 1.0 - px[q] - py[q]; tl[q][1] = px[q]; tl[q][2] = py[q]; }
-  }
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hemo_upload_tables(tw, &tl[0][0]));
-  auto& h = ctx->hemo;
-  h.release();
-  h.nf = nf;
-  h.ncell = (int64_t)ucell.size();
-  h.mu = mu;
-  h.dt = dt_sample;
-  HIPCHK(h.cells.alloc(ucell.size()));
-  HIPCHK(h.mask.alloc(mask.size()));
-  HIPCHK(h.fidx.alloc(fidx.size()));
-  HIPCHK(h.acc.alloc((size_t)nf * 24));
-  HIPCHK(h.out.alloc((size_t)nf * 15));
-  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
-  HIPCHK(hipMemcpyAsync(h.cells.p, ucell.data(), ucell.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(h.mask.p, mask.data(), mask.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(h.fidx.p, fidx.data(), fidx.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemsetAsync(h.acc.p, 0, h.acc.n * sizeof(double), ctx->stream));   // zero whatever FSI_DEBUG_POISON filled in
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  h.open = true;
-  return FSI_OK;
-}
-
-int fsi_hemo_sample(FsiCtx* ctx, double* wss_out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto& h = ctx->hemo;
-  if (!h.open) { ctx->err = "fsi_hemo_sample: no hemodynamics session (fsi_hemo_begin first)"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  launch_hemo_sample(ctx->stream, h.ncell, elem_arrays(ctx), ctx->U.p, h.cells.p, h.mask.p, h.fidx.p, h.mu, h.dt, hemo_acc(ctx),
-                     wss_out ? h.out.p : nullptr);
-  HIPCHK(hipGetLastError());
-  h.samples += 1;
-  if (wss_out) {
-    HIPCHK(hipMemcpyAsync(wss_out, h.out.p, (size_t)h.nf * 9 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  return FSI_OK;
-}
-
-int fsi_hemo_indices(FsiCtx* ctx, double* out, int64_t* samples) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto& h = ctx->hemo;
-  if (!h.open) { ctx->err = "fsi_hemo_indices: no hemodynamics session (fsi_hemo_begin first)"; return FSI_ERR_INVALID; }
-  if (h.samples == 0) { ctx->err = "fsi_hemo_indices: no sample taken yet"; return FSI_ERR_INVALID; }
-  if (!out) { ctx->err = "fsi_hemo_indices: null output"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  launch_hemo_finish(ctx->stream, 3 * h.nf, (double)h.samples, hemo_acc(ctx), h.out.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, h.out.p, (size_t)h.nf * 15 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (samples) *samples = h.samples;
-  return FSI_OK;
-}
-
-int fsi_hemo_end(FsiCtx* ctx) {
-  if (!ctx) return FSI_ERR_INVALID;
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  ctx->hemo.release();
-  return FSI_OK;
-}
-
-int fsi_stress_begin(FsiCtx* ctx, int64_t n, const int32_t* cells) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (n <= 0 || !cells) { ctx->err = "fsi_stress_begin: needs n > 0 cells"; return FSI_ERR_INVALID; }
-  if (ctx->part) { ctx->err = "fsi_stress_begin: partitioned contexts are not supported"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  std::vector<int32_t> kinds((size_t)ctx->C);
-  HIPCHK(hipMemcpy(kinds.data(), ctx->cell_kind.p, (size_t)ctx->C * sizeof(int32_t), hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < n; ++i) {
-    if (cells[i] < 0 || cells[i] >= ctx->C) { ctx->err = "fsi_stress_begin: cell out of range"; return FSI_ERR_INVALID; }
-    if (kinds[cells[i]] != 1) { ctx->err = "fsi_stress_begin: cell is not a solid cell"; return FSI_ERR_INVALID; }
-  }
-  auto& s = ctx->stress;
-  s.release();
-  s.n = n;
-  HIPCHK(s.cells.alloc((size_t)n));
-  HIPCHK(s.frame.alloc((size_t)n * 80));
-  HIPCHK(s.sums.alloc((size_t)n * 8));
-  HIPCHK(s.avg.alloc((size_t)n * 8));
-  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
-  HIPCHK(hipMemcpyAsync(s.cells.p, cells, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemsetAsync(s.sums.p, 0, s.sums.n * sizeof(double), ctx->stream));  // zero whatever FSI_DEBUG_POISON filled in
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  s.open = true;
-  return FSI_OK;
-}
-
-int fsi_stress_sample(FsiCtx* ctx, double* frame_out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto& s = ctx->stress;
-  if (!s.open) { ctx->err = "fsi_stress_sample: no stress / strain session (fsi_stress_begin first)"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  launch_stress_sample(ctx->stream, s.n, elem_arrays(ctx), elem_params(ctx), ctx->U.p, s.cells.p, s.frame.p, s.sums.p);
-  HIPCHK(hipGetLastError());
-  s.samples += 1;
-  if (frame_out) {
-    HIPCHK(hipMemcpyAsync(frame_out, s.frame.p, (size_t)s.n * 80 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  return FSI_OK;
-}
-
-int fsi_stress_averages(FsiCtx* ctx, double* out, int64_t* samples) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto& s = ctx->stress;
-  if (!s.open) { ctx->err = "fsi_stress_averages: no stress / strain session (fsi_stress_begin first)"; return FSI_ERR_INVALID; }
-  if (s.samples == 0) { ctx->err = "fsi_stress_averages: no sample taken yet"; return FSI_ERR_INVALID; }
-  if (!out) { ctx->err = "fsi_stress_averages: null output"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  launch_stress_average(ctx->stream, s.n, (double)s.samples, s.sums.p, s.avg.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, s.avg.p, (size_t)s.n * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (samples) *samples = s.samples;
-  return FSI_OK;
-}
-
-int fsi_stress_end(FsiCtx* ctx) {
-  if (!ctx) return FSI_ERR_INVALID;
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  ctx->stress.release();
-  return FSI_OK;
-}
-
-namespace {
-// the open session of quantity q (0 d, 1 v, 2 p), or null with ctx->err set
-FsiCtx::Band* band_session(FsiCtx* ctx, int32_t q, const char* fn) {
-  if (q < 0 || q > 2) { ctx->err = std::string(fn) + ": quantity must be 0 (d), 1 (v) or 2 (p)"; return nullptr; }
-  if (!ctx->band[q].open) { ctx->err = std::string(fn) + ": no band-pass session for this quantity (fsi_band_begin first)"; return nullptr; }
-  return &ctx->band[q];
-}
-}  // namespace
-
-int fsi_band_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* nodes, const int32_t* nodes_b, int64_t capacity) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (quantity < 0 || quantity > 2) { ctx->err = "fsi_band_begin: quantity must be 0 (d), 1 (v) or 2 (p)"; return FSI_ERR_INVALID; }
-  if (n <= 0 || !nodes || capacity <= 0) { ctx->err = "fsi_band_begin: needs n > 0 nodes and a capacity > 0 frames"; return FSI_ERR_INVALID; }
-  if (ctx->part) { ctx->err = "fsi_band_begin: partitioned contexts are not supported"; return FSI_ERR_INVALID; }
-  const int ncomp = quantity == 2 ? 1 : 3;
-  const int64_t limit = quantity == 2 ? ctx->V : ctx->N2, off = quantity == 2 ? 6 * ctx->N2 : 3 * ctx->N2 * quantity;
-  if (n > 2 * ctx->ndof) { ctx->err = "fsi_band_begin: more nodes than the problem has dofs"; return FSI_ERR_INVALID; }
-  const int64_t nrow = n * ncomp;
-  std::vector<int32_t> i0((size_t)nrow), i1((size_t)nrow, -1);
-  for (int64_t i = 0; i < n; ++i) {
-    const int32_t a = nodes[i], b = nodes_b ? nodes_b[i] : -1;
-    if (a < 0 || a >= limit || b >= limit) { ctx->err = "fsi_band_begin: node out of range"; return FSI_ERR_INVALID; }
-    for (int k = 0; k < ncomp; ++k) {
-      i0[i * ncomp + k] = ctx->h_user2solver[off + (int64_t)ncomp * a + k];
-      if (b >= 0) i1[i * ncomp + k] = ctx->h_user2solver[off + (int64_t)ncomp * b + k];
-    }
-  }
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  auto& s = ctx->band[quantity];
-  s.release();
-  // history + filtered series + one frame each of sums, amplitudes and magnitudes, against what the device has free: the context
-  // keeps 1/16 of the device for what it allocates later (a refreshed preconditioner, staging buffers) - nothing is paged or cut
-  const double need_d = 8.0 * (double)nrow * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN + 2.0) + 8.0 * (double)n + 8.0 * (double)nrow;
-  size_t free_b = 0, total_b = 0;
-  HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  const double reserve = (double)total_b / 16.0;
-  if (need_d > (double)free_b - reserve) {
-    char msg[320];
-    snprintf(msg, sizeof msg, "fsi_band_begin: the session needs %.0f bytes (%lld rows x %lld frames, raw and filtered), the device has %zu bytes "
-             "free of which %.0f stay with the context", need_d, (long long)nrow, (long long)capacity, free_b, reserve);
-    ctx->err = msg;
-    return FSI_ERR_INVALID;
-  }
-  s.ncomp = ncomp; s.nnode = n; s.nrow = nrow; s.capacity = capacity;
-  HIPCHK(s.idx0.alloc((size_t)nrow));
-  HIPCHK(s.idx1.alloc((size_t)nrow));
-  HIPCHK(s.hist.alloc((size_t)nrow * (size_t)capacity));
-  HIPCHK(s.work.alloc((size_t)nrow * (size_t)(capacity + 2 * BAND_MAX_PADLEN)));
-  HIPCHK(s.acc.alloc((size_t)nrow));
-  HIPCHK(s.amp.alloc((size_t)nrow));
-  HIPCHK(s.mag.alloc((size_t)n));
-  HIPCHK(s.part_val.alloc(BAND_ARGMAX_BLOCKS + 1));
-  HIPCHK(s.part_idx.alloc(BAND_ARGMAX_BLOCKS + 1));
-  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
-  HIPCHK(hipMemcpyAsync(s.idx0.p, i0.data(), (size_t)nrow * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(s.idx1.p, i1.data(), (size_t)nrow * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  s.open = true;
-  return FSI_OK;
-}
-
-int fsi_band_sample(FsiCtx* ctx, int32_t quantity) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_sample");
-  if (!s) return FSI_ERR_INVALID;
-  if (s->frames >= s->capacity) { ctx->err = "fsi_band_sample: the history is full (capacity declared at fsi_band_begin)"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  launch_band_sample(ctx->stream, s->nrow, ctx->U.p, s->idx0.p, s->idx1.p, s->hist.p + (size_t)s->frames * s->nrow);
-  HIPCHK(hipGetLastError());
-  s->frames += 1;
-  s->nfilt = 0;               // the filtered series no longer covers the history
-  s->window = -1;
-  return FSI_OK;
-}
-
-int fsi_band_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* b, const double* a, const double* zi, int32_t padlen) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_filter");
-  if (!s) return FSI_ERR_INVALID;
-  if (ntaps < 2 || ntaps > BAND_MAX_TAPS || !b || !a || !zi || padlen < 0 || padlen > BAND_MAX_PADLEN) {
-    ctx->err = "fsi_band_filter: needs 2 .. 11 coefficients b, a, their zi and 0 <= padlen <= 33";
-    return FSI_ERR_INVALID;
-  }
-  if (a[0] != 1.0) { ctx->err = "fsi_band_filter: a[0] must be 1 (normalised coefficients, as scipy.signal.butter returns them)"; return FSI_ERR_INVALID; }
-  if (s->frames <= padlen) {      // scipy: "The length of the input vector x must be greater than padlen"
-    ctx->err = "fsi_band_filter: " + std::to_string(s->frames) + " recorded frames, the filter needs more than padlen = " + std::to_string(padlen);
-    return FSI_ERR_INVALID;
-  }
-  BandCoef c{};
-  for (int k = 0; k < ntaps; ++k) { c.b[k] = b[k]; c.a[k] = a[k]; }
-  for (int k = 0; k < ntaps - 1; ++k) c.zi[k] = zi[k];
-  HIPCHK(hipSetDevice(ctx->device));
-  launch_band_filter(ctx->stream, s->nrow, s->frames, padlen, c, s->hist.p, s->work.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  s->padlen = padlen;
-  s->nfilt = s->frames;
-  s->window = -1;
-  s->acc_start = -1;
-  return FSI_OK;
-}
-
-int fsi_band_amplitude(FsiCtx* ctx, int32_t quantity, int32_t window) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_amplitude");
-  if (!s) return FSI_ERR_INVALID;
-  if (s->nfilt == 0) { ctx->err = "fsi_band_amplitude: no filtered series (fsi_band_filter first)"; return FSI_ERR_INVALID; }
-  if (window < 0 || window > s->nfilt) {
-    ctx->err = "fsi_band_amplitude: window of " + std::to_string(window) + " frames, the series has " + std::to_string(s->nfilt);
-    return FSI_ERR_INVALID;
-  }
-  s->window = window;
-  s->acc_start = -1;
-  return FSI_OK;
-}
-
-int fsi_band_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, double* out, double* max_out, int64_t* argmax_out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_fetch");
-  if (!s) return FSI_ERR_INVALID;
-  if (what < FSI_BAND_RAW || what > FSI_BAND_MAGNITUDE) { ctx->err = "fsi_band_fetch: what must be FSI_BAND_RAW .. FSI_BAND_MAGNITUDE"; return FSI_ERR_INVALID; }
-  const int64_t nfr = what == FSI_BAND_RAW ? s->frames : s->nfilt;
-  if (what != FSI_BAND_RAW && nfr == 0) { ctx->err = "fsi_band_fetch: no filtered series (fsi_band_filter first)"; return FSI_ERR_INVALID; }
-  if (frame < 0 || frame >= nfr) { ctx->err = "fsi_band_fetch: frame out of range"; return FSI_ERR_INVALID; }
-  if (what >= FSI_BAND_AMPLITUDE && s->window < 0) { ctx->err = "fsi_band_fetch: no amplitude (fsi_band_amplitude first)"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  const double* y = s->work.p + (size_t)s->padlen * s->nrow;        // the filtered series without its guard frames
-  const double* src = nullptr;
-  if (what == FSI_BAND_RAW) src = s->hist.p + (size_t)frame * s->nrow;
-  else if (what == FSI_BAND_FILTERED || s->window == 0) src = y + (size_t)frame * s->nrow;   // low-pass: the amplitude is the series (:222-230)
-  else {
-    // calculate_windowed_rms: RMS[i - pad] for pad <= i < pad + n - w + 1 with pad = (n - len_RMS) // 2, zero outside.  The
-    // value of a frame does not depend on the order of the fetches: window `start` is recomputed when start is a multiple of
-    // BAND_RMS_REFRESH and advanced from start - 1 otherwise.
-    const int64_t w = s->window, n = s->nfilt, start = frame - (w - 1) / 2;
-    if (start < 0 || start + w > n) {
-      HIPCHK(hipMemsetAsync(s->amp.p, 0, (size_t)s->nrow * sizeof(double), ctx->stream));
-    } else {
-      int64_t from = start - start % BAND_RMS_REFRESH;
-      if (s->acc_start >= from && s->acc_start < start) from = s->acc_start + 1;
-      else if (s->acc_start == start) from = start - start % BAND_RMS_REFRESH;     // asked twice: the same arithmetic again
-      for (int64_t k = from; k <= start; ++k)
-        launch_band_rms(ctx->stream, s->nrow, y, k, (int)w, k % BAND_RMS_REFRESH == 0, s->acc.p, s->amp.p);
-      HIPCHK(hipGetLastError());
-      s->acc_start = start;
-    }
-    src = s->amp.p;
-  }
-  if (what == FSI_BAND_MAGNITUDE || max_out || argmax_out) {
-    if (what < FSI_BAND_AMPLITUDE) { ctx->err = "fsi_band_fetch: maximum / argmax are those of the amplitude magnitude"; return FSI_ERR_INVALID; }
-    launch_band_magnitude(ctx->stream, s->nnode, s->ncomp, src, s->mag.p);
-    launch_band_argmax(ctx->stream, s->nnode, s->mag.p, s->part_val.p, s->part_idx.p);
-    HIPCHK(hipGetLastError());
-    if (max_out) HIPCHK(hipMemcpyAsync(max_out, s->part_val.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (argmax_out) HIPCHK(hipMemcpyAsync(argmax_out, s->part_idx.p, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (what == FSI_BAND_MAGNITUDE) src = s->mag.p;
-  }
-  if (out) HIPCHK(hipMemcpyAsync(out, src, (size_t)(what == FSI_BAND_MAGNITUDE ? s->nnode : s->nrow) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return FSI_OK;
-}
-
-int fsi_band_end(FsiCtx* ctx, int32_t quantity) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (quantity < 0 || quantity > 2) { ctx->err = "fsi_band_end: quantity must be 0 (d), 1 (v) or 2 (p)"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  ctx->band[quantity].release();
-  return FSI_OK;
-}
-
-namespace {
-// the open spectrogram session of quantity q (0 d, 1 v, 2 p), or null with ctx->err set
-FsiCtx::Spec* spec_session(FsiCtx* ctx, int32_t q, const char* fn) {
-  if (q < 0 || q > 2) { ctx->err = std::string(fn) + ": quantity must be 0 (d), 1 (v) or 2 (p)"; return nullptr; }
-  if (!ctx->spec[q].open) { ctx->err = std::string(fn) + ": no spectrogram session for this quantity (fsi_spec_begin first)"; return nullptr; }
-  return &ctx->spec[q];
-}
-
-// The average over the session's rows of the one-sided power of nseg segments of K frames, `step` frames apart, transformed
-// at length nfft >= K: mean, then per slab of bins the host's tables, k_spec_power and k_spec_reduce.  out[(nfft / 2 + 1)][nseg].
-int spec_power(FsiCtx* ctx, FsiCtx::Spec* s, const char* fn, int64_t K, int64_t step, int64_t nseg, int64_t nfft, const double* window,
-               int32_t scaling, double fs, double* out) {
-  const int64_t nbins = nfft / 2 + 1, nblk = spec_blocks(s->nrow);
-  double sw = 0.0, sw2 = 0.0;
-  for (int64_t j = 0; j < K; ++j) { sw += window[j]; sw2 += window[j] * window[j]; }
-  const double scale = scaling == FSI_SPEC_DENSITY ? 1.0 / (fs * sw2) : 1.0 / (sw * sw);
-  if (!std::isfinite(scale) || scale <= 0.0) { ctx->err = std::string(fn) + ": the window gives no finite scale"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  // what one call holds on the device: means, window and result, and per bin of a slab two table columns and the row blocks'
-  // partial sums.  The slab is as many bins as fit beside the 1/16 of the device the context keeps (at most 1 GiB of tables:
-  // they are made on the host); if not even one pass of SPEC_BINS bins fits, the call is refused - nothing is paged.
-  const double fixed = 8.0 * ((double)nseg * (double)s->nrow + (double)K + (double)nbins * (double)nseg);
-  const double per_bin = 8.0 * (2.0 * (double)K + (double)nseg * (double)nblk);
-  const int64_t min_slab = nbins < SPEC_BINS ? nbins : SPEC_BINS;
-  size_t free_b = 0, total_b = 0;
-  HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  const double reserve = (double)total_b / 16.0, avail = (double)free_b - reserve - fixed;
-  if (avail < per_bin * (double)min_slab) {
-    char msg[460];
-    snprintf(msg, sizeof msg, "%s: the transform needs %.0f bytes (tables of %lld frames x %lld of %lld bins, cos and sin, %lld segments x %lld rows of "
-             "means and partial sums, and the result), the device has %zu bytes free of which %.0f stay with the context", fn,
-             fixed + per_bin * (double)min_slab, (long long)K, (long long)min_slab, (long long)nbins, (long long)nseg, (long long)s->nrow,
-             free_b, reserve);
-    ctx->err = msg;
-    return FSI_ERR_INVALID;
-  }
-  // the host makes the tables: cos / sin of nfft angles and one slab's columns.  A transform length whose tables the host
-  // should not be asked for is refused like one that does not fit the device, not left to std::bad_alloc
-  if (nfft > SPEC_MAX_NFFT) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: nfft = %lld, the host's cos / sin tables are limited to %lld angles", fn, (long long)nfft, (long long)SPEC_MAX_NFFT);
-    ctx->err = msg;
-    return FSI_ERR_INVALID;
-  }
-  int64_t slab = nbins;
-  const double cap = std::min(avail / per_bin, (double)(1ll << 30) / (16.0 * (double)K));
-  if ((double)slab > cap) slab = std::max<int64_t>(min_slab, (int64_t)cap / SPEC_BINS * SPEC_BINS);
-  struct Bufs {
-    DevBuf<double> mean, w, Ct, St, part, res;
-    ~Bufs() { mean.release(); w.release(); Ct.release(); St.release(); part.release(); res.release(); }
-  } bufs;
-  auto &mean = bufs.mean, &w = bufs.w, &Ct = bufs.Ct, &St = bufs.St, &part = bufs.part, &res = bufs.res;
-  HIPCHK(mean.alloc((size_t)(nseg * s->nrow)));
-  HIPCHK(w.alloc((size_t)K));
-  HIPCHK(Ct.alloc((size_t)(K * slab)));
-  HIPCHK(St.alloc((size_t)(K * slab)));
-  HIPCHK(part.alloc((size_t)(nseg * nblk * slab)));
-  HIPCHK(res.alloc((size_t)(nbins * nseg)));
-  HIPCHK(hipDeviceSynchronize());
-  int rc = FSI_OK;
-  std::string why;
-  auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && rc == FSI_OK) { rc = FSI_ERR_DEVICE; why = std::string(what) + ": " + hipGetErrorString(e); } return e == hipSuccess; };
-  const double* x = s->filtered ? s->work.p + (size_t)s->padlen * s->nrow : s->hist.p;
-  // cos / sin(2 pi m / nfft), m = 0 .. nfft - 1, once; a table entry is that of m = j k mod nfft
-  std::vector<double> cosm, sinm, hc, hs;
-  try {
-    cosm.resize((size_t)nfft); sinm.resize((size_t)nfft); hc.resize((size_t)(K * slab)); hs.resize((size_t)(K * slab));
-  } catch (const std::bad_alloc&) {
-    ctx->err = std::string(fn) + ": the host has no memory for the cos / sin tables (" + std::to_string(16 * (nfft + K * slab)) + " bytes)";
-    return FSI_ERR_INVALID;
-  }
-  const long double tau = 2.0L * 3.14159265358979323846264338327950288L;      // the angle in extended precision: an entry is the
-  for (int64_t m = 0; m < nfft; ++m) {                                       // correctly rounded cos / sin to within its last bit
-    const long double ang = tau * (long double)m / (long double)nfft;
-    cosm[m] = (double)cosl(ang);
-    sinm[m] = (double)sinl(ang);
-  }
-  if (chk(hipMemcpyAsync(w.p, window, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "window upload")) {
-    launch_spec_mean(ctx->stream, s->nrow, K, step, nseg, x, mean.p);
-    chk(hipGetLastError(), "k_spec_mean");
-  }
-  for (int64_t bin0 = 0; bin0 < nbins && rc == FSI_OK; bin0 += slab) {
-    const int64_t nb = std::min(slab, nbins - bin0);
-    for (int64_t j = 0; j < K; ++j)
-      for (int64_t b = 0; b < nb; ++b) {
-        const int64_t m = (int64_t)(((unsigned __int128)j * (unsigned __int128)(bin0 + b)) % (unsigned __int128)nfft);
-        hc[j * nb + b] = cosm[m];
-        hs[j * nb + b] = sinm[m];
-      }
-    if (!chk(hipMemcpyAsync(Ct.p, hc.data(), (size_t)(K * nb) * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "table upload")) break;
-    if (!chk(hipMemcpyAsync(St.p, hs.data(), (size_t)(K * nb) * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "table upload")) break;
-    launch_spec_power(ctx->stream, s->nrow, K, step, nseg, nb, bin0, nfft % 2 == 0 ? nfft / 2 : -1, scale, x, mean.p, w.p, Ct.p, St.p, part.p);
-    launch_spec_reduce(ctx->stream, s->nrow, nseg, nb, bin0, part.p, res.p);
-    if (!chk(hipGetLastError(), "k_spec_power")) break;
-    if (!chk(hipStreamSynchronize(ctx->stream), "k_spec_power")) break;      // the host tables are refilled for the next slab
-  }
-  if (rc == FSI_OK && chk(hipMemcpyAsync(out, res.p, (size_t)(nbins * nseg) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "result"))
-    chk(hipStreamSynchronize(ctx->stream), "result");
-  if (rc != FSI_OK) ctx->err = std::string(fn) + ": " + why;
-  return rc;
-}
-}  // namespace
-
-int fsi_spec_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* nodes, const int32_t* nodes_b, int32_t ncomp_mode, int64_t capacity) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (quantity < 0 || quantity > 2) { ctx->err = "fsi_spec_begin: quantity must be 0 (d), 1 (v) or 2 (p)"; return FSI_ERR_INVALID; }
-  if (n <= 0 || !nodes || capacity <= 0) { ctx->err = "fsi_spec_begin: needs n > 0 nodes and a capacity > 0 frames"; return FSI_ERR_INVALID; }
-  if (ncomp_mode < FSI_SPEC_X || ncomp_mode > FSI_SPEC_MAG) { ctx->err = "fsi_spec_begin: ncomp_mode must be FSI_SPEC_X .. FSI_SPEC_MAG"; return FSI_ERR_INVALID; }
-  if (ctx->part) { ctx->err = "fsi_spec_begin: partitioned contexts are not supported"; return FSI_ERR_INVALID; }
-  if (n > 2 * ctx->ndof) { ctx->err = "fsi_spec_begin: more nodes than the problem has dofs"; return FSI_ERR_INVALID; }
-  const bool scalar = quantity == 2;
-  const int mode = scalar ? FSI_SPEC_X : ncomp_mode;              // the pressure has one component
-  const int ncomp = scalar ? 1 : 3;
-  const int64_t limit = scalar ? ctx->V : ctx->N2, off = scalar ? 6 * ctx->N2 : 3 * ctx->N2 * quantity;
-  const int64_t nsamp = mode >= FSI_SPEC_ALL ? 3 * n : n, nrow = mode == FSI_SPEC_ALL ? 3 * n : n;
-  std::vector<int32_t> i0((size_t)nsamp), i1((size_t)nsamp, -1);
-  for (int64_t i = 0; i < n; ++i) {
-    const int32_t a = nodes[i], b = nodes_b ? nodes_b[i] : -1;
-    if (a < 0 || a >= limit || b >= limit) { ctx->err = "fsi_spec_begin: node out of range"; return FSI_ERR_INVALID; }
-    for (int c = 0; c < (mode >= FSI_SPEC_ALL ? 3 : 1); ++c) {
-      const int comp = scalar ? 0 : (mode >= FSI_SPEC_ALL ? c : mode);
-      i0[c * n + i] = ctx->h_user2solver[off + (int64_t)ncomp * a + comp];
-      if (b >= 0) i1[c * n + i] = ctx->h_user2solver[off + (int64_t)ncomp * b + comp];
-    }
-  }
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  auto& s = ctx->spec[quantity];
-  // raw and filtered history and the sampled vector of the magnitude, against what the device has free, as fsi_band_begin;
-  // with them what the transforms allocate at the end of the run, so that a history that fits here is not refused there:
-  // one pass of SPEC_BINS bins of a periodogram's tables over all frames, and the means of capacity / 4 segments
-  const double need_d = 8.0 * (double)nrow * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN) + 16.0 * (double)nsamp +
-                        16.0 * SPEC_BINS * (double)capacity + 8.0 * (double)nrow * ((double)capacity / 4.0 + 2.0);
-  size_t free_b = 0, total_b = 0;
-  HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  const double reserve = (double)total_b / 16.0;
-  if (need_d > (double)free_b - reserve) {
-    char msg[420];
-    snprintf(msg, sizeof msg, "fsi_spec_begin: the session needs %.0f bytes (%lld rows x %lld frames, raw and filtered, and the transforms' tables), the device has %zu bytes "
-             "free of which %.0f stay with the context", need_d, (long long)nrow, (long long)capacity, free_b, reserve);
-    ctx->err = msg;
-    return FSI_ERR_INVALID;
-  }
-  s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
-  s.mode = mode; s.nnode = n; s.nrow = nrow; s.nsamp = nsamp; s.capacity = capacity;
-  HIPCHK(s.idx0.alloc((size_t)nsamp));
-  HIPCHK(s.idx1.alloc((size_t)nsamp));
-  HIPCHK(s.hist.alloc((size_t)nrow * (size_t)capacity));
-  HIPCHK(s.work.alloc((size_t)nrow * (size_t)(capacity + 2 * BAND_MAX_PADLEN)));
-  if (mode == FSI_SPEC_MAG) HIPCHK(s.tmp.alloc((size_t)nsamp));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpyAsync(s.idx0.p, i0.data(), (size_t)nsamp * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(s.idx1.p, i1.data(), (size_t)nsamp * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  s.open = true;
-  return FSI_OK;
-}
-
-int fsi_spec_sample(FsiCtx* ctx, int32_t quantity) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = spec_session(ctx, quantity, "fsi_spec_sample");
-  if (!s) return FSI_ERR_INVALID;
-  if (s->frames >= s->capacity) { ctx->err = "fsi_spec_sample: the history is full (capacity declared at fsi_spec_begin)"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  double* dst = s->hist.p + (size_t)s->frames * s->nrow;
-  if (s->mode == FSI_SPEC_MAG) {
-    launch_band_sample(ctx->stream, s->nsamp, ctx->U.p, s->idx0.p, s->idx1.p, s->tmp.p);
-    launch_spec_magnitude(ctx->stream, s->nnode, s->tmp.p, dst);
-  } else {
-    launch_band_sample(ctx->stream, s->nrow, ctx->U.p, s->idx0.p, s->idx1.p, dst);
-  }
-  HIPCHK(hipGetLastError());
-  s->frames += 1;
-  s->filtered = false;        // a filtered series no longer covers the history
-  return FSI_OK;
-}
-
-int fsi_spec_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* b, const double* a, const double* zi, int32_t padlen) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = spec_session(ctx, quantity, "fsi_spec_filter");
-  if (!s) return FSI_ERR_INVALID;
-  if (ntaps == 0) { s->filtered = false; return FSI_OK; }
-  if (ntaps < 2 || ntaps > BAND_MAX_TAPS || !b || !a || !zi || padlen < 0 || padlen > BAND_MAX_PADLEN) {
-    ctx->err = "fsi_spec_filter: needs 0 (the raw series) or 2 .. 11 coefficients b, a, their zi and 0 <= padlen <= 33";
-    return FSI_ERR_INVALID;
-  }
-  if (a[0] != 1.0) { ctx->err = "fsi_spec_filter: a[0] must be 1 (normalised coefficients, as scipy.signal.butter returns them)"; return FSI_ERR_INVALID; }
-  if (s->frames <= padlen) {
-    ctx->err = "fsi_spec_filter: " + std::to_string(s->frames) + " recorded frames, the filter needs more than padlen = " + std::to_string(padlen);
-    return FSI_ERR_INVALID;
-  }
-  BandCoef c{};
-  for (int k = 0; k < ntaps; ++k) { c.b[k] = b[k]; c.a[k] = a[k]; }
-  for (int k = 0; k < ntaps - 1; ++k) c.zi[k] = zi[k];
-  HIPCHK(hipSetDevice(ctx->device));
-  launch_band_filter(ctx->stream, s->nrow, s->frames, padlen, c, s->hist.p, s->work.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  s->padlen = padlen;
-  s->filtered = true;
-  return FSI_OK;
-}
-
-int fsi_spec_fetch(FsiCtx* ctx, int32_t quantity, int32_t filtered, int64_t frame, double* out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = spec_session(ctx, quantity, "fsi_spec_fetch");
-  if (!s) return FSI_ERR_INVALID;
-  if (!out) { ctx->err = "fsi_spec_fetch: out is NULL"; return FSI_ERR_INVALID; }
-  if (filtered && !s->filtered) { ctx->err = "fsi_spec_fetch: no filtered series (fsi_spec_filter first)"; return FSI_ERR_INVALID; }
-  if (frame < 0 || frame >= s->frames) { ctx->err = "fsi_spec_fetch: frame out of range"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  const double* src = (filtered ? s->work.p + (size_t)s->padlen * s->nrow : s->hist.p) + (size_t)frame * s->nrow;
-  HIPCHK(hipMemcpyAsync(out, src, (size_t)s->nrow * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return FSI_OK;
-}
-
-int fsi_spec_spectrogram(FsiCtx* ctx, int32_t quantity, int64_t nperseg, int64_t noverlap, int64_t nfft, const double* window,
-                         int32_t scaling, double fs, double* out_power) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = spec_session(ctx, quantity, "fsi_spec_spectrogram");
-  if (!s) return FSI_ERR_INVALID;
-  if (!window || !out_power || (scaling != FSI_SPEC_SPECTRUM && scaling != FSI_SPEC_DENSITY) || !(fs > 0.0)) {
-    ctx->err = "fsi_spec_spectrogram: needs a window, an output, scaling FSI_SPEC_SPECTRUM or FSI_SPEC_DENSITY and fs > 0";
-    return FSI_ERR_INVALID;
-  }
-  if (nperseg < 1 || noverlap < 0 || noverlap >= nperseg || nfft < nperseg) {
-    ctx->err = "fsi_spec_spectrogram: needs nperseg >= 1, 0 <= noverlap < nperseg and nfft >= nperseg";
-    return FSI_ERR_INVALID;
-  }
-  if (s->frames < nperseg) {
-    ctx->err = "fsi_spec_spectrogram: " + std::to_string(s->frames) + " recorded frames, one segment needs nperseg = " + std::to_string(nperseg);
-    return FSI_ERR_INVALID;
-  }
-  const int64_t step = nperseg - noverlap, nseg = (s->frames - noverlap) / step;
-  if (nseg > 65535) { ctx->err = "fsi_spec_spectrogram: more than 65535 segments"; return FSI_ERR_INVALID; }
-  return spec_power(ctx, s, "fsi_spec_spectrogram", nperseg, step, nseg, nfft, window, scaling, fs, out_power);
-}
-
-int fsi_spec_periodogram(FsiCtx* ctx, int32_t quantity, const double* window, int32_t scaling, double fs, double* out_power) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = spec_session(ctx, quantity, "fsi_spec_periodogram");
-  if (!s) return FSI_ERR_INVALID;
-  if (!window || !out_power || (scaling != FSI_SPEC_SPECTRUM && scaling != FSI_SPEC_DENSITY) || !(fs > 0.0)) {
-    ctx->err = "fsi_spec_periodogram: needs a window, an output, scaling FSI_SPEC_SPECTRUM or FSI_SPEC_DENSITY and fs > 0";
-    return FSI_ERR_INVALID;
-  }
-  if (s->frames < 1) { ctx->err = "fsi_spec_periodogram: no recorded frames"; return FSI_ERR_INVALID; }
-  return spec_power(ctx, s, "fsi_spec_periodogram", s->frames, s->frames, 1, s->frames, window, scaling, fs, out_power);
-}
-
-int fsi_spec_end(FsiCtx* ctx, int32_t quantity) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (quantity < 0 || quantity > 2) { ctx->err = "fsi_spec_end: quantity must be 0 (d), 1 (v) or 2 (p)"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  ctx->spec[quantity].release();
   return FSI_OK;
 }
 

@@ -400,39 +400,42 @@ struct FsiCtx {
     void release() { cells.release(); frame.release(); sums.release(); avg.release(); open = false; n = samples = 0; }
   } stress;
 
-  // band-pass sessions (fsi_band_begin .. fsi_band_end), one per quantity d, v, p: the rows' solver indices, the raw history
-  // hist[capacity][nrow], the filtered series work[capacity + 2 BAND_MAX_PADLEN][nrow] (the filtered frame k is frame
-  // padlen + k), and one frame each of running sums, amplitudes and amplitude magnitudes (fsi_band.hip)
-  struct Band {
+  // the recorded history of a band-pass or a spectrogram session: the solver indices of the sampled entries, the raw history
+  // hist[capacity][nrow] and the filtered series work[capacity + 2 BAND_MAX_PADLEN][nrow] (the filtered frame k is frame
+  // padlen + k).  A row is a sampled entry (nsamp = nrow) or, with tmp, the magnitude of three of them (nsamp = 3 nnode).
+  struct History {
     bool open = false;
-    int ncomp = 0, padlen = 0;
+    bool filtered = false;                   // the filtered series covers the history (no frame recorded since the filter ran)
+    int padlen = 0;
+    int64_t nnode = 0, nrow = 0, nsamp = 0, capacity = 0, frames = 0;
+    fsi::DevBuf<int32_t> idx0, idx1;         // [nsamp]; idx1 < 0: the entry is U[idx0], else the mean of the two
+    fsi::DevBuf<double> hist, work, tmp;
+    void release() {
+      idx0.release(); idx1.release(); hist.release(); work.release(); tmp.release();
+      open = filtered = false; padlen = 0; nnode = nrow = nsamp = capacity = frames = 0;
+    }
+  };
+
+  // band-pass sessions (fsi_band_begin .. fsi_band_end), one per quantity d, v, p: a history whose row is component c of
+  // listed node i at i * ncomp + c, and one frame each of running sums, amplitudes and amplitude magnitudes (fsi_band.hip)
+  struct Band : History {
+    int ncomp = 0;
     int window = -1;                         // -1: no amplitude asked for; 0: the filtered series itself (low-pass); > 0: RMS window
-    int64_t nnode = 0, nrow = 0, capacity = 0, frames = 0;
-    int64_t nfilt = 0;                       // frames the filtered series holds (0: not filtered since the last sample)
     int64_t acc_start = -1;                  // window start the running sums stand at (-1: none)
-    fsi::DevBuf<int32_t> idx0, idx1;         // [nrow]; idx1 < 0: the row is U[idx0], else the mean of the two
-    fsi::DevBuf<double> hist, work, acc, amp, mag, part_val;
+    fsi::DevBuf<double> acc, amp, mag, part_val;
     fsi::DevBuf<int64_t> part_idx;
     void release() {
-      idx0.release(); idx1.release(); hist.release(); work.release(); acc.release(); amp.release(); mag.release();
-      part_val.release(); part_idx.release();
-      open = false; ncomp = padlen = 0; window = -1; nnode = nrow = capacity = frames = nfilt = 0; acc_start = -1;
+      History::release();
+      acc.release(); amp.release(); mag.release(); part_val.release(); part_idx.release();
+      ncomp = 0; window = -1; acc_start = -1;
     }
   } band[3];
 
   // spectrogram sessions (fsi_spec_begin .. fsi_spec_end), one per quantity d, v, p, with a history of their own on a row
-  // list of their own, in the band-pass session's layout: hist[capacity][nrow] raw, work[capacity + 2 BAND_MAX_PADLEN][nrow]
-  // filtered (frame k at padlen + k).  mode: 0 / 1 / 2 one component, 3 the three stacked (row = c * nnode + i), 4 the
-  // magnitude, taken at sample time from tmp[3 nnode].  Means, tables and partial sums live for one call (fsi_spec.hip).
-  struct Spec {
-    bool open = false, filtered = false;
-    int mode = 0, padlen = 0;
-    int64_t nnode = 0, nrow = 0, nsamp = 0, capacity = 0, frames = 0;
-    fsi::DevBuf<int32_t> idx0, idx1;         // [nsamp]: the sampled entries (nsamp = nrow, or 3 nnode for the magnitude)
-    fsi::DevBuf<double> hist, work, tmp;
-    void release() {
-      idx0.release(); idx1.release(); hist.release(); work.release(); tmp.release();
-      open = filtered = false; mode = padlen = 0; nnode = nrow = nsamp = capacity = frames = 0;
-    }
+  // list of their own.  mode: 0 / 1 / 2 one component, 3 the three stacked (row = c * nnode + i), 4 the magnitude, taken at
+  // sample time.  Means, tables and partial sums live for one call (fsi_spec.hip).
+  struct Spec : History {
+    int mode = 0;
+    void release() { History::release(); mode = 0; }
   } spec[3];
 };

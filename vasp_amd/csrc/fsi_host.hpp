@@ -2,6 +2,7 @@
 //   fsi_capi.hip     the ABI itself: context set-up (fsi_create), boundary data, partition, state access, timers
 //   fsi_newton.hip   fsi_assemble_residual / _jacobian, fsi_solve, fsi_newton_solve (turtleFSI's newtonsolver policy)
 //   fsi_krylov.hip   recycled GCR (solve_gcr), BiCGStab, the monolithic product
+//   fsi_sessions.hip the post-processing sessions of a run: fsi_hemo_* / fsi_stress_* / fsi_band_* / fsi_spec_*
 //   fsi_precond.hip  the field-split block preconditioner: one application (two streams), refresh at a new Jacobian
 // The kernels are in fsi_assembly / fsi_solver / fsi_block / fsi_gcr / fsi_post .hip (declared in fsi_kernels.hpp).
 #pragma once

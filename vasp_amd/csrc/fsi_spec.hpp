@@ -1,5 +1,5 @@
 // Average spectrograms and power spectra of a recorded history (fsi_spec.hip): tile sizes and the launchers the C-ABI
-// (fsi_spec_* in fsi_capi.hip) calls.  The history is the band-pass session's: src[frame][row], FP64, rows contiguous.
+// (fsi_spec_* in fsi_sessions.hip) calls.  The history is the band-pass session's: src[frame][row], FP64, rows contiguous.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -199,7 +199,7 @@ class HemodynamicsRun:
         backend.hemodynamics_begin(cells, local, float(mu), dt_sample)
         self.writer = HemodynamicsWriter(Path(ns["results_folder"]) / "Hemodynamic_indices", geometry, topology)
 
-    def sample(self, t: float) -> None:
+    def sample(self, t: float, state=None) -> None:
         self.writer.write_wss(self.backend.hemodynamics_sample(wss=True), t)
 
     def finish(self, out=print) -> None:

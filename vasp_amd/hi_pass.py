@@ -17,7 +17,7 @@ Not done: the reference's ``strain`` / ``stress`` quantities, its ``multiband`` 
 from __future__ import annotations
 
 from pathlib import Path
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 
@@ -168,23 +168,43 @@ def amplitude_magnitude(amp: np.ndarray) -> np.ndarray:
     return np.sqrt((amp[:, 0] * amp[:, 0] + amp[:, 1] * amp[:, 1]) + amp[:, 2] * amp[:, 2])
 
 
-class HostBandSession:
-    """The session of one quantity on the host, method for method ``HipBackend.hi_pass_*`` without the quantity argument:
-    for a backend that has no device session."""
+class HostHistory:
+    """The recording half of a host session: the raw frames, up to the capacity declared at begin, and their filtfilt."""
+    what = ""
 
-    def __init__(self, ncomp: int, capacity: int):
-        self.ncomp, self.capacity = ncomp, int(capacity)
+    def __init__(self, shape, capacity: int):
+        self.shape, self.capacity = shape, int(capacity)
         self.raw: List[np.ndarray] = []
-        self.filtered = self.amp = None
+        self.filtered = None
 
     def sample(self, frame: np.ndarray) -> None:
         if len(self.raw) >= self.capacity:
-            raise RuntimeError("hi-pass history is full (capacity declared at begin)")
-        self.raw.append(np.array(frame, dtype=np.float64).reshape(-1, self.ncomp))
-        self.filtered = self.amp = None
+            raise RuntimeError(f"{self.what} history is full (capacity declared at begin)")
+        self.raw.append(np.array(frame, dtype=np.float64).reshape(self.shape))
+        self.filtered = None
+
+    def filter(self, b=None, a=None, zi=None, padlen: int = 0) -> None:
+        self.filtered = None if b is None else filtfilt_rows(b, a, np.stack(self.raw), zi, padlen)
+
+    def end(self) -> None:
+        pass
+
+
+class HostBandSession(HostHistory):
+    """The session of one quantity on the host, method for method ``HipBackend.hi_pass_*`` without the quantity argument:
+    for a backend that has no device session."""
+    what = "hi-pass"
+
+    def __init__(self, ncomp: int, capacity: int):
+        super().__init__((-1, ncomp), capacity)
+        self.ncomp, self.amp = ncomp, None
+
+    def sample(self, frame: np.ndarray) -> None:
+        super().sample(frame)
+        self.amp = None
 
     def filter(self, b, a, zi, padlen: int) -> None:
-        self.filtered = filtfilt_rows(b, a, np.stack(self.raw), zi, padlen)
+        super().filter(b, a, zi, padlen)
         self.amp = None
 
     def amplitude(self, window: int) -> None:
@@ -198,6 +218,49 @@ class HostBandSession:
         mag = amplitude_magnitude(self.amp[frame])
         out = mag if what == "magnitude" else self.amp[frame]
         return (out, float(mag.max()), int(np.argmax(mag))) if with_max else out
+
+
+class DeviceSession:
+    """``HipBackend.<prefix>_*`` of one quantity behind the host session's method names."""
+
+    def __init__(self, backend, prefix: str, q: str):
+        self.backend, self.prefix, self.q = backend, prefix, q
+
+    def __getattr__(self, name: str):
+        call = getattr(self.backend, f"{self.prefix}_{name}")
+        return lambda *args: call(self.q, *args)
+
+
+class SessionRun:
+    """What the driver's sides of ``--hi-pass`` and ``--spectrogram`` share: per quantity one session, on the device or, for a
+    backend without ``<prefix>_begin``, on the host; one recorded frame per saved frame; every session ended after ``write``."""
+    prefix = ""
+
+    def open_sessions(self, backend, ns: dict, begin_args, host_session) -> None:
+        """``begin_args(q)``: the device session's arguments before the capacity; ``host_session(q, capacity)``: its host twin."""
+        self.device = hasattr(backend, self.prefix + "_begin")
+        self.frames = 0
+        self.sessions = {}
+        capacity = expected_frames(ns) + 1
+        for q in self.quantities:
+            if self.device:
+                self.sessions[q] = DeviceSession(backend, self.prefix, q)
+                self.sessions[q].begin(*begin_args(q), capacity)
+            else:
+                self.sessions[q] = host_session(q, capacity)
+
+    def sample(self, t: float, state) -> None:
+        """Record dvp_["n"]; ``state``: a callable giving the host copy, used only without the device session."""
+        for q, s in self.sessions.items():
+            s.sample() if self.device else s.sample(self._host_frame(q, state()))
+        self.frames += 1
+
+    def finish(self, out=print) -> None:
+        try:
+            self.write(out)
+        finally:
+            for s in self.sessions.values():
+                s.end()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -352,11 +415,12 @@ def output_nodes(mesh: FsiMesh, save_deg: int, quantity: str):
             np.concatenate([np.full(V, -1), e[:, 1]]).astype(np.int32))
 
 
-class HiPassRun:
+class HiPassRun(SessionRun):
     """The driver's side of ``--hi-pass``: one session per quantity on the Visualization writer's nodes, one recorded frame
     per saved frame, and at the end per band the filtered series, with ``--hi-pass-amplitude`` its amplitude and table.
     Times in the files are ``k * time_between_files + 0.0``, the reference's default start time; ``time_between_files`` is
     dt * save_step, the spacing of the frames (the reference takes dt * stride and notes the doubt, :621-634)."""
+    prefix = "hi_pass"
 
     def __init__(self, backend, mesh: FsiMesh, ns: dict):
         from .output import refine_topology
@@ -367,21 +431,13 @@ class HiPassRun:
         self.amplitude = bool(ns.get("hi_pass_amplitude"))
         self.window = int(ns.get("hi_pass_window") or 250)
         self.dt_files = float(ns["dt"]) * int(ns["save_step"])
-        capacity = expected_frames(ns) + 1
         if self.save_deg >= 2:
             geometry, topology = mesh.node_coords, refine_topology(mesh)
         else:
             geometry, topology = mesh.coords, mesh.tets
         self.writer = HiPassWriter(Path(ns["results_folder"]) / "Visualization_hi_pass", geometry, topology)
-        self.device = hasattr(backend, "hi_pass_begin")
-        self.host: Dict[str, HostBandSession] = {}
-        self.frames = 0
-        for q in self.quantities:
-            if self.device:
-                nodes, nodes_b = output_nodes(mesh, self.save_deg, q)
-                backend.hi_pass_begin(q, nodes, nodes_b, capacity)
-            else:
-                self.host[q] = HostBandSession(1 if q == "p" else 3, capacity)
+        self.open_sessions(backend, ns, lambda q: output_nodes(mesh, self.save_deg, q),
+                           lambda q, capacity: HostBandSession(1 if q == "p" else 3, capacity))
 
     def _host_frame(self, q: str, state: np.ndarray) -> np.ndarray:
         d, v, p = self.mesh.split(state)
@@ -394,62 +450,33 @@ class HiPassRun:
         f = d if q == "d" else v
         return f if self.save_deg >= 2 else f[:V]
 
-    def sample(self, state=None) -> None:
-        """Record dvp_["n"]; ``state``: a callable giving the host copy, used only without the device session."""
-        for q in self.quantities:
-            if self.device:
-                self.backend.hi_pass_sample(q)
-            else:
-                self.host[q].sample(self._host_frame(q, state()))
-        self.frames += 1
-
-    # one session, device or host, behind the same four calls
-    def _filter(self, q, prm):
-        if self.device:
-            self.backend.hi_pass_filter(q, prm["b"], prm["a"], prm["zi"], prm["padlen"])
-        else:
-            self.host[q].filter(prm["b"], prm["a"], prm["zi"], prm["padlen"])
-
-    def _amplitude(self, q, window):
-        self.backend.hi_pass_amplitude(q, window) if self.device else self.host[q].amplitude(window)
-
-    def _fetch(self, q, what, k, with_max=False):
-        if self.device:
-            return self.backend.hi_pass_fetch(q, what, k, with_max)
-        return self.host[q].fetch(what, k, with_max)
-
-    def finish(self, out=print) -> None:
+    def write(self, out) -> None:
         n = self.frames
-        try:
-            for q in self.quantities:
-                ncomp = 1 if q == "p" else 3
-                for lo, hi in self.bands:
-                    prm = design(self.dt_files, lo, hi)
-                    viz = f"{VIZ_TYPE[q]}_{prm['name']}"
-                    if n <= prm["padlen"]:
-                        out(f"Hi-pass {viz}: {n} frames recorded, the filter needs more than {prm['padlen']}: nothing written")
-                        continue
-                    self._filter(q, prm)
-                    self.writer.write_series(viz, (self._fetch(q, "filtered", k) for k in range(n)), n, ncomp, self.dt_files, 0.0)
-                    if not self.amplitude:
-                        continue
-                    lowpass = prm["btype"] == "lowpass"
-                    if not lowpass and n < self.window:
-                        out(f"Hi-pass {viz}: {n} frames recorded, fewer than the window of {self.window}: no amplitude written")
-                        continue
-                    self._amplitude(q, 0 if lowpass else self.window)
-                    table = np.empty((n, 13))
+        for q, session in self.sessions.items():
+            ncomp = 1 if q == "p" else 3
+            for lo, hi in self.bands:
+                prm = design(self.dt_files, lo, hi)
+                viz = f"{VIZ_TYPE[q]}_{prm['name']}"
+                if n <= prm["padlen"]:
+                    out(f"Hi-pass {viz}: {n} frames recorded, the filter needs more than {prm['padlen']}: nothing written")
+                    continue
+                session.filter(prm["b"], prm["a"], prm["zi"], prm["padlen"])
+                self.writer.write_series(viz, (session.fetch("filtered", k) for k in range(n)), n, ncomp, self.dt_files, 0.0)
+                if not self.amplitude:
+                    continue
+                lowpass = prm["btype"] == "lowpass"
+                if not lowpass and n < self.window:
+                    out(f"Hi-pass {viz}: {n} frames recorded, fewer than the window of {self.window}: no amplitude written")
+                    continue
+                session.amplitude(0 if lowpass else self.window)
+                table = np.empty((n, 13))
 
-                    def amp_frames():
-                        for k in range(n):
-                            amp, mx, am = self._fetch(q, "amplitude", k, True)
-                            table[k] = amplitude_row(k * self.dt_files + 0.0, amplitude_magnitude(amp), mx, am)
-                            yield amp
+                def amp_frames():
+                    for k in range(n):
+                        amp, mx, am = session.fetch("amplitude", k, True)
+                        table[k] = amplitude_row(k * self.dt_files + 0.0, amplitude_magnitude(amp), mx, am)
+                        yield amp
 
-                    self.writer.write_series(f"{viz}_amplitude", amp_frames(), n, ncomp, self.dt_files, 0.0)
-                    self.writer.write_table(viz, table)
-            out(f"Hi-pass fields of {n} frames ({', '.join(self.quantities)}) written to {self.writer.folder}")
-        finally:
-            if self.device:
-                for q in self.quantities:
-                    self.backend.hi_pass_end(q)
+                self.writer.write_series(f"{viz}_amplitude", amp_frames(), n, ncomp, self.dt_files, 0.0)
+                self.writer.write_table(viz, table)
+        out(f"Hi-pass fields of {n} frames ({', '.join(self.quantities)}) written to {self.writer.folder}")

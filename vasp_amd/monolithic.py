@@ -249,16 +249,25 @@ def parameters(argv: Optional[List[str]] = None):
     return args, hook, v
 
 
+# The post-processing options that sample the saved frames, in the order they sample and finish: the key in ns, the module
+# (imported only when the option is given), its refusal function and Run class, and the backend method without which the
+# option is an error (None: the module records on the host instead).
+SESSIONS = (("hemodynamics", "hemodynamics", "hemodynamics_refusal", "HemodynamicsRun", "hemodynamics_begin"),
+            ("stress_strain", "stress_strain", "stress_strain_refusal", "StressStrainRun", "stress_strain_begin"),
+            ("hi_pass", "hi_pass", "hi_pass_refusal", "HiPassRun", None),
+            ("spectrogram", "spectrogram", "spectrogram_refusal", "SpectrogramRun", None))
+
+
+def _session_part(module: str, name: str):
+    return getattr(importlib.import_module("." + module, __package__), name)
+
+
 def _refuse_sessions(argv, backend_factory, world: int) -> None:
     """--hemodynamics, --stress-strain, --hi-pass, --spectrogram: refuse before anything is built, on every rank (a refusal on rank 0 alone would leave
     the workers waiting in run_worker)."""
     args = parse(argv)
-    if not (args.get("hemodynamics") or args.get("stress_strain") or args.get("hi_pass") or args.get("spectrogram")):
+    if not any(args.get(key) for key, *_ in SESSIONS):
         return
-    from .hemodynamics import hemodynamics_refusal
-    from .hi_pass import hi_pass_refusal
-    from .spectrogram import spectrogram_refusal
-    from .stress_strain import stress_strain_refusal
     with contextlib.redirect_stdout(io.StringIO()):
         _, _, v = parameters(argv)
     if backend_factory is default_backend:
@@ -266,9 +275,8 @@ def _refuse_sessions(argv, backend_factory, world: int) -> None:
         cls = HipBackend
     else:
         cls = backend_factory if isinstance(backend_factory, type) else None
-    for key, refusal in (("hemodynamics", hemodynamics_refusal), ("stress_strain", stress_strain_refusal),
-                         ("hi_pass", hi_pass_refusal), ("spectrogram", spectrogram_refusal)):
-        why = refusal(v, world, cls) if v.get(key) else ""
+    for key, module, refusal, _, _ in SESSIONS:
+        why = _session_part(module, refusal)(v, world, cls) if v.get(key) else ""
         if why:
             raise SystemExit(why)
 
@@ -473,26 +481,13 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
     viz = None
     if ns.get("save_step") and rank0:
         viz = VisualizationWriter(ns["visualization_folder"], mesh, ns["save_deg"], run_index=restart_run)
-    hemo = None
-    if ns.get("hemodynamics"):                    # single rank, no restart, save_step set: run() checked it
-        from .hemodynamics import HemodynamicsRun
-        if not hasattr(backend, "hemodynamics_begin"):
-            raise SystemExit(f"--hemodynamics needs a backend with hemodynamics_begin ({type(backend).__name__} has none)")
-        hemo = HemodynamicsRun(backend, mesh, ns)
-    stress = None
-    if ns.get("stress_strain"):                   # as --hemodynamics: run() checked it
-        from .stress_strain import StressStrainRun
-        if not hasattr(backend, "stress_strain_begin"):
-            raise SystemExit(f"--stress-strain needs a backend with stress_strain_begin ({type(backend).__name__} has none)")
-        stress = StressStrainRun(backend, mesh, ns)
-    hipass = None
-    if ns.get("hi_pass"):                         # as --hemodynamics: run() checked it; a backend without the device session
-        from .hi_pass import HiPassRun            # records on the host (vasp_amd/hi_pass.py: HostBandSession)
-        hipass = HiPassRun(backend, mesh, ns)
-    spectro = None
-    if ns.get("spectrogram"):                     # as --hi-pass, on a history and a node list of its own
-        from .spectrogram import SpectrogramRun   # (vasp_amd/spectrogram.py: HostSpecSession without the device session)
-        spectro = SpectrogramRun(backend, mesh, ns)
+    sessions = []                                 # single rank, no restart, save_step set: run() checked it
+    for key, module, _, run_cls, needs in SESSIONS:
+        if not ns.get(key):
+            continue
+        if needs and not hasattr(backend, needs):
+            raise SystemExit(f"--{key.replace('_', '-')} needs a backend with {needs} ({type(backend).__name__} has none)")
+        sessions.append(_session_part(module, run_cls)(backend, mesh, ns))
     first_step_num = ns["counter"]
 
     dt, T = float(ns["dt"]), float(ns["T"])
@@ -517,14 +512,8 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
                 checkpoint(ns["checkpoint_folder"], mesh, x, ns["default_variables"], t, ns["counter"])
         if viz is not None and ns["counter"] % int(ns["save_step"]) == 0:
             viz.write(ns["dvp_"]["n"].vector(), t)
-            if hemo is not None:
-                hemo.sample(t)
-            if stress is not None:
-                stress.sample(t)
-            if hipass is not None:
-                hipass.sample(ns["dvp_"]["n"].vector)
-            if spectro is not None:
-                spectro.sample(ns["dvp_"]["n"].vector)
+            for session in sessions:
+                session.sample(t, ns["dvp_"]["n"].vector)
         elif ns.get("save_step") and ns["counter"] % int(ns["save_step"]) == 0:
             ns["dvp_"]["n"].vector()              # partitioned: every rank takes part in the gather
         ns["counter"] += 1
@@ -535,14 +524,8 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
         out("Solved for timestep %d, t = %.4f in %.1f s" % (ns["counter"], t, _time.perf_counter() - t0))
     if viz is not None:
         viz.close()
-    if hemo is not None:
-        hemo.finish(out)
-    if stress is not None:
-        stress.finish(out)
-    if hipass is not None:                        # also after a killturtle / killtime stop: on the frames recorded so far
-        hipass.finish(out)
-    if spectro is not None:
-        spectro.finish(out)
+    for session in sessions:                      # also after a killturtle / killtime stop: on the frames recorded so far
+        session.finish(out)
     ns["time_loop_seconds"] = _time.perf_counter() - t_loop
     ns["newton_iterations"] = total_newton
     ns["solver_events"] = events_seen

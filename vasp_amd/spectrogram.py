@@ -30,7 +30,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from .hi_pass import expected_frames, filtfilt_rows, output_nodes
+from .hi_pass import HostHistory, SessionRun, expected_frames, output_nodes
 from .mesh import FsiMesh
 
 HP_ORDER = 6                                    # filter_time_data(order=6, btype="highpass") [REF spectrograms.py:558]
@@ -198,7 +198,7 @@ def sbi(chroma: np.ndarray, n_chroma: int = N_CHROMA) -> np.ndarray:
 
 def spec_tables(K: int, nfft: int, bin0: int, nb: int):
     """C, S (nb, K): cos / sin(2 pi (j k mod nfft) / nfft) for the bins k = bin0 .. bin0 + nb - 1, the angle formed in
-    extended precision and the value rounded to FP64 once - what fsi_capi.hip uploads."""
+    extended precision and the value rounded to FP64 once - what fsi_sessions.hip uploads."""
     m = np.arange(nfft, dtype=np.longdouble)
     ang = (np.longdouble(2) * PI_L) * m / np.longdouble(nfft)
     cosm, sinm = np.cos(ang).astype(np.float64), np.sin(ang).astype(np.float64)
@@ -263,22 +263,13 @@ def mean_power(x: np.ndarray, K: int, step: int, nseg: int, nfft: int, window: n
     return out
 
 
-class HostSpecSession:
+class HostSpecSession(HostHistory):
     """The session of one quantity on the host, method for method ``HipBackend.spec_*`` without the quantity argument."""
+    what = "spectrogram"
 
     def __init__(self, nrows: int, capacity: int):
-        self.nrows, self.capacity = int(nrows), int(capacity)
-        self.raw: List[np.ndarray] = []
-        self.filtered = None
-
-    def sample(self, rows: np.ndarray) -> None:
-        if len(self.raw) >= self.capacity:
-            raise RuntimeError("spectrogram history is full (capacity declared at begin)")
-        self.raw.append(np.array(rows, dtype=np.float64).reshape(self.nrows))
-        self.filtered = None
-
-    def filter(self, b=None, a=None, zi=None, padlen: int = 0) -> None:
-        self.filtered = None if b is None else filtfilt_rows(b, a, np.stack(self.raw), zi, padlen)
+        super().__init__(int(nrows), capacity)
+        self.nrows = int(nrows)
 
     def fetch(self, frame: int, filtered: bool = False) -> np.ndarray:
         return self.filtered[frame] if filtered else self.raw[frame]
@@ -456,25 +447,10 @@ def spectrogram_refusal(v: dict, world: int, backend_cls) -> str:
     return ""
 
 
-class _DeviceSession:
-    """``HipBackend.spec_*`` of one quantity behind ``HostSpecSession``'s calls."""
-
-    def __init__(self, backend, q: str):
-        self.backend, self.q = backend, q
-
-    def filter(self, b=None, a=None, zi=None, padlen: int = 0) -> None:
-        self.backend.spec_filter(self.q, b, a, zi, padlen)
-
-    def spectrogram(self, *args):
-        return self.backend.spec_spectrogram(self.q, *args)
-
-    def periodogram(self, *args):
-        return self.backend.spec_periodogram(self.q, *args)
-
-
-class SpectrogramRun:
+class SpectrogramRun(SessionRun):
     """The driver's side of ``--spectrogram``: per quantity one session on the sampled nodes, one recorded frame per saved
     frame, and at the end the four files.  A backend without ``spec_begin`` records and transforms on the host."""
+    prefix = "spec"
 
     def __init__(self, backend, mesh: FsiMesh, ns: dict):
         self.backend, self.mesh = backend, mesh
@@ -484,17 +460,9 @@ class SpectrogramRun:
         self.dt_files = float(ns["dt"]) * int(ns["save_step"])
         self.folder = Path(ns["results_folder"]) / "Spectrograms"
         self.case = Path(ns["results_folder"]).parent.name
-        capacity = expected_frames(ns) + 1
-        self.device = hasattr(backend, "spec_begin")
         self.sel = {q: select_nodes(mesh, self.save_deg, q, ns, self.opts) for q in self.quantities}     # an empty region ends the run here
-        self.host: Dict[str, HostSpecSession] = {}
-        self.frames = 0
-        for q in self.quantities:
-            s = self.sel[q]
-            if self.device:
-                backend.spec_begin(q, s["nodes"], s["nodes_b"], self.opts["component"], capacity)
-            else:
-                self.host[q] = HostSpecSession(self.rows(q), capacity)
+        self.open_sessions(backend, ns, lambda q: (self.sel[q]["nodes"], self.sel[q]["nodes_b"], self.opts["component"]),
+                           lambda q, capacity: HostSpecSession(self.rows(q), capacity))
 
     def rows(self, q: str) -> int:
         return len(self.sel[q]["ids"]) * (3 if q != "p" and self.opts["component"] == "all" else 1)
@@ -502,7 +470,7 @@ class SpectrogramRun:
     def min_color(self, q: str):
         return MIN_COLOR[q] if self.opts["min_color"] is None else self.opts["min_color"]
 
-    def _host_rows(self, q: str, state: np.ndarray) -> np.ndarray:
+    def _host_frame(self, q: str, state: np.ndarray) -> np.ndarray:
         d, v, p = self.mesh.split(state)
         s = self.sel[q]
         if q == "p":
@@ -513,31 +481,16 @@ class SpectrogramRun:
             return a
         return component_rows((d if q == "d" else v)[s["nodes"]], self.opts["component"])
 
-    def sample(self, state=None) -> None:
-        """Record dvp_["n"]; ``state``: a callable giving the host copy, used only without the device session."""
-        for q in self.quantities:
-            if self.device:
-                self.backend.spec_sample(q)
-            else:
-                self.host[q].sample(self._host_rows(q, state()))
-        self.frames += 1
-
-    def finish(self, out=print) -> None:
+    def write(self, out) -> None:
         n = self.frames
-        try:
-            T = n * self.dt_files
-            plan = window_plan(n, T, self.opts["num_windows_per_sec"], self.opts["overlap_frac"]) if n else dict(nseg=0)
-            if n <= HP_PADLEN or plan["nseg"] < 2:
-                out(f"Spectrograms: {n} frames recorded, too few for the high-pass filter (more than {HP_PADLEN}) and two segments: "
-                    "nothing written")
-                return
-            for q in self.quantities:
-                session = _DeviceSession(self.backend, q) if self.device else self.host[q]
-                res = pipeline(session, self.rows(q), n, T, 0.0, self.opts, self.min_color(q))
-                write_files(self.folder, self.sel[q]["name"], self.case + self.sel[q]["case_suffix"], res, self.min_color(q))
-            out(f"Spectrograms of {n} frames ({', '.join(self.quantities)}; {self.opts['sampling']}, "
-                f"{', '.join(str(self.rows(q)) for q in self.quantities)} rows) written to {self.folder}")
-        finally:
-            if self.device:
-                for q in self.quantities:
-                    self.backend.spec_end(q)
+        T = n * self.dt_files
+        plan = window_plan(n, T, self.opts["num_windows_per_sec"], self.opts["overlap_frac"]) if n else dict(nseg=0)
+        if n <= HP_PADLEN or plan["nseg"] < 2:
+            out(f"Spectrograms: {n} frames recorded, too few for the high-pass filter (more than {HP_PADLEN}) and two segments: "
+                "nothing written")
+            return
+        for q, session in self.sessions.items():
+            res = pipeline(session, self.rows(q), n, T, 0.0, self.opts, self.min_color(q))
+            write_files(self.folder, self.sel[q]["name"], self.case + self.sel[q]["case_suffix"], res, self.min_color(q))
+        out(f"Spectrograms of {n} frames ({', '.join(self.quantities)}; {self.opts['sampling']}, "
+            f"{', '.join(str(self.rows(q)) for q in self.quantities)} rows) written to {self.folder}")

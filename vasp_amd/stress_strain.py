@@ -127,7 +127,7 @@ class StressStrainRun:
         backend.stress_strain_begin(cells)
         self.writer = StressStrainWriter(Path(ns["results_folder"]) / "StressStrain", geometry, topology)
 
-    def sample(self, t: float) -> None:
+    def sample(self, t: float, state=None) -> None:
         self.writer.write_frame(self.backend.stress_strain_sample(frame=True), t)
 
     def finish(self, out=print) -> None:
