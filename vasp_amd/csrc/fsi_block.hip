@@ -12,6 +12,8 @@
 // All of it is HBM-bound gather/scatter work; bytes are those of the matrices touched (stated at the launchers).
 #include "fsi_kernels.hpp"
 
+#include <type_traits>
+
 namespace fsi {
 
 __device__ inline double wsum(double v) {
@@ -721,32 +723,66 @@ __global__ __launch_bounds__(256) void k_spmv_tiled_f32(int64_t N2, const int64_
     i = ni;
   }
 }
+// ---- launch geometry and dispatch of the tiled kernels -----------------------------------------------------------------------
 // (the launchers take the context's tile size tn = 128 | 256: FsiTuning.tile_nodes, 0 = by the number of nodes)
-#define TILED_DISPATCH(KERNEL, THREADS, ...)                                                                                     \
-  do {                                                                                                                           \
-    if (nv == 1 && tn == 128) hipLaunchKernelGGL((KERNEL<1, 128>), dim3(tiles), dim3(THREADS), lds, st, __VA_ARGS__);           \
-    else if (nv == 1) hipLaunchKernelGGL((KERNEL<1, 256>), dim3(tiles), dim3(THREADS), lds, st, __VA_ARGS__);                   \
-    else if (tn == 128) hipLaunchKernelGGL((KERNEL<3, 128>), dim3(tiles), dim3(THREADS), lds, st, __VA_ARGS__);                 \
-    else hipLaunchKernelGGL((KERNEL<3, 256>), dim3(tiles), dim3(THREADS), lds, st, __VA_ARGS__);                                \
-  } while (0)
+// The dynamic LDS is sized for the largest tile; on the 1.12 M-tet mesh the tiles gather 889 distinct neighbours in the
+// median and 1325 at most, 21 KB, so LDS does not limit the occupancy.  Splitting the tiles into two launches by size was
+// measured: slower, 159 against 143 us.
+struct TiledGeom {
+  unsigned tiles;      // workgroups: the tiles in the XCD-aware order
+  int th;              // threads of a fused sweep: 16 lanes per node, 8 rounds per tile (measured at 256 nodes: 1024 threads no gain over 512)
+  size_t lds;          // the gathered entries of the largest tile
+};
+static TiledGeom tiled_geom(int tn, int64_t N2, int max_nu) {
+  return {xcd_grid((N2 + tn - 1) / tn), tn == 128 ? 256 : 512, (size_t)max_nu * sizeof(float4)};
+}
+template <int V> using Int = std::integral_constant<int, V>;
+template <class F> static void dispatch_tn(int tn, F f) {
+  if (tn == 128) f(Int<128>{});
+  else f(Int<256>{});
+}
+template <class F> static void dispatch_nv_tn(int nv, int tn, F f) {
+  dispatch_tn(tn, [&](auto TN) {
+    if (nv == 1) f(Int<1>{}, TN);
+    else f(Int<3>{}, TN);
+  });
+}
 void launch_spmv_tiled_f32(hipStream_t st, int nv, int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const float* vals,
                            const uint16_t* ploc, const int64_t* tile_uptr, const int32_t* ulist, const uint8_t* rowflag,
                            const float* x, float* y) {
-  const unsigned tiles = xcd_grid((N2 + tn - 1) / tn);
-  const size_t lds = (size_t)max_nu * sizeof(float4);
-  TILED_DISPATCH(k_spmv_tiled_f32, 256, N2, nadj_ptr, vals, ploc, tile_uptr, ulist, rowflag, x, y);
+  const TiledGeom g = tiled_geom(tn, N2, max_nu);
+  dispatch_nv_tn(nv, tn, [&](auto NV, auto TN) {
+    hipLaunchKernelGGL((k_spmv_tiled_f32<NV(), TN()>), dim3(g.tiles), dim3(256), g.lds, st, N2, nadj_ptr, vals, ploc, tile_uptr, ulist,
+                       rowflag, x, y);
+  });
 }
+// ---- the fused tiled sweeps ---------------------------------------------------------------------------------------------------
 // One Chebyshev sweep on the tiled operator in a single launch (the product never goes through memory):
 //   t = A d_in;  x += d_in;  r -= t;  d_out = c1 d_in + c2 dinv r      (d is ping-ponged: other tiles still gather d_in)
 // Workgroups of up to 1024 threads: the tile's LDS (up to 64 KB) allows two workgroups per CU whatever their size, and the
 // row loop is bound by load latency, so 32 waves per CU instead of 8 is what the kernel is after.
-template <int NV, int TN>
-__global__ __launch_bounds__(1024) void k_sweep_tiled_f32(int64_t N2, const int64_t* __restrict__ nadj_ptr,
-                                                          const float* __restrict__ vals, const uint16_t* __restrict__ ploc,
-                                                          const int64_t* __restrict__ tile_uptr, const int32_t* __restrict__ ulist,
-                                                          const uint8_t* __restrict__ rowflag, const float* __restrict__ dinv,
-                                                          float c1, float c2, const float* __restrict__ din, float* __restrict__ dout,
-                                                          float* __restrict__ x, float* __restrict__ r) {
+//
+// sweep_tiled is the one body of k_sweep_tiled_f32 / _h / _r.  Where a pair's values and local index come from is its Src:
+//   Rec, load(e)     the pair e as one record (what a lane keeps in registers while the pair is in flight); Rec{}, all bits
+//                    zero, is value +0 and local index 0 in every format: the record of a strip past the row's end
+//   fma3(q, sx, ..)  s += values x the gathered entry
+//   AHEAD            rows of records in flight ahead of the one being summed, 1 | 2
+// The (value, local index) pairs of the group's NEXT node(s) are in flight while the current node is multiplied and reduced.
+// Four 16-pair strips are prefetched: a P2 edge node has ~22 neighbours, a vertex node ~65.  (Measured alternatives, all
+// slower on MI355X: two strips + a loop of dependent loads for the long rows, 184 us; the rows of a tile sorted into long
+// and short ones with five / two strips, 152 us; this form 142 us.)
+// AHEAD = 2, the records of TWO rows ahead: a row is ~28 pairs of 4 - 8 bytes over 16 lanes, and one row ahead left ~32 KB in
+// flight per CU, which paced the one-ratio form at ~3.7 TB/s (119.9 -> 112.1 us per displacement sweep at 1.12 M tets, A / B on
+// one box; the 8-byte records of the fluid block: 144 us either way).  The 16-byte records of the FP32 fluid block stay at one
+// row ahead: two rows of them are 48 VGPRs of records, 79 in all, 6 waves per SIMD instead of 8, and measured slower
+// (197 - 206 against 182 - 191 us per sweep alone).
+template <int TN, class Src>
+__device__ __forceinline__ void sweep_tiled(int64_t N2, const int64_t* __restrict__ nadj_ptr, const Src src,
+                                            const int64_t* __restrict__ tile_uptr, const int32_t* __restrict__ ulist,
+                                            const uint8_t* __restrict__ rowflag, const float* __restrict__ dinv, float c1, float c2,
+                                            const float* __restrict__ din, float* __restrict__ dout, float* __restrict__ x,
+                                            float* __restrict__ r) {
+  using Rec = typename Src::Rec;
   extern __shared__ __attribute__((aligned(16))) float4 sx[];
   __shared__ __attribute__((aligned(16))) int64_t sptr[TN + 2];
   __shared__ __attribute__((aligned(16))) float4 ssum[TN];   // the tile's products; the update below reads them coalesced
@@ -769,52 +805,37 @@ __global__ __launch_bounds__(1024) void k_sweep_tiled_f32(int64_t N2, const int6
   for (int i = threadIdx.x; i <= nrows; i += nth) sptr[i] = nadj_ptr[r0 + i];
   __syncthreads();
   const int sub = threadIdx.x & 15, g = threadIdx.x >> 4;
-  // The (value, local index) pairs of the group's NEXT node are in flight while the current node is multiplied and reduced.
-  // Four 16-pair strips are prefetched: a P2 edge node has ~22 neighbours, a vertex node ~65.  (Measured alternatives, all
-  // slower on MI355X: two strips + a loop of dependent loads for the long rows, 184 us; the rows of a tile sorted into long
-  // and short ones with five / two strips, 152 us; this form 142 us.)
   constexpr int KS = 4;
-  float cv[KS][NV], nv_[KS][NV];
-  int cl[KS], nl[KS];
-  auto prefetch = [&](int i, float (&v)[KS][NV], int (&l)[KS]) {
+  constexpr bool AHEAD2 = Src::AHEAD == 2;
+  Rec cr[KS], nr[KS], n2[KS];
+  auto prefetch = [&](int i, Rec (&q)[KS]) {
     const int64_t e0 = sptr[i], e1 = sptr[i + 1];
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
       const int64_t e = e0 + sub + 16 * k;
-      const bool in = e < e1;
-      l[k] = in ? (int)ploc[e] : 0;
-#pragma unroll
-      for (int c = 0; c < NV; ++c) v[k][c] = in ? vals[NV * e + c] : 0.f;
+      if (e < e1) q[k] = src.load(e); else q[k] = Rec{};               // a zero record: value +0, local index 0
     }
   };
   int i = g;
-  if (i < nrows) prefetch(i, cv, cl);
+  if (i < nrows) prefetch(i, cr);
+  if (AHEAD2 && i + ngrp < nrows) prefetch(i + ngrp, nr);
   while (i < nrows) {
     const int ni = i + ngrp;
-    if (ni < nrows) prefetch(ni, nv_, nl);
+    if (AHEAD2 && ni + ngrp < nrows) prefetch(ni + ngrp, n2);
+    if (!AHEAD2 && ni < nrows) prefetch(ni, nr);
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    auto strip = [&](int k) {
-      const float4 xv = sx[cl[k]];
-      if (NV == 1) { s0 += cv[k][0] * xv.x; s1 += cv[k][0] * xv.y; s2 += cv[k][0] * xv.z; }
-      else { s0 += cv[k][0] * xv.x; s1 += cv[k][NV > 1 ? 1 : 0] * xv.y; s2 += cv[k][NV > 2 ? 2 : 0] * xv.z; }
-    };
-    strip(0);
-    strip(1);
+    Src::fma3(cr[0], sx, s0, s1, s2);
+    Src::fma3(cr[1], sx, s0, s1, s2);
     const int len = (int)(sptr[i + 1] - sptr[i]);
-    if (__builtin_amdgcn_ballot_w64(len > 32) != 0) { strip(2); strip(3); }        // wave-uniform: some node of the wave is long
-    for (int64_t e = sptr[i] + sub + 16 * KS; e < sptr[i + 1]; e += 16) {           // rows with more than 64 pairs
-      const float4 xv = sx[ploc[e]];
-      if (NV == 1) { const float c = vals[e]; s0 += c * xv.x; s1 += c * xv.y; s2 += c * xv.z; }
-      else { const float* c = vals + NV * e; s0 += c[0] * xv.x; s1 += c[NV > 1 ? 1 : 0] * xv.y; s2 += c[NV > 2 ? 2 : 0] * xv.z; }
+    if (__builtin_amdgcn_ballot_w64(len > 32) != 0) {                               // wave-uniform: some node of the wave is long
+      Src::fma3(cr[2], sx, s0, s1, s2);
+      Src::fma3(cr[3], sx, s0, s1, s2);
     }
+    for (int64_t e = sptr[i] + sub + 16 * KS; e < sptr[i + 1]; e += 16) Src::fma3(src.load(e), sx, s0, s1, s2);      // rows with more than 64 pairs
     s0 = group_sum<16>(s0); s1 = group_sum<16>(s1); s2 = group_sum<16>(s2);
     if (sub == 0) ssum[i] = make_float4(s0, s1, s2, 0.f);
 #pragma unroll
-    for (int k = 0; k < KS; ++k) {
-      cl[k] = nl[k];
-#pragma unroll
-      for (int c = 0; c < NV; ++c) cv[k][c] = nv_[k][c];
-    }
+    for (int k = 0; k < KS; ++k) { cr[k] = nr[k]; if (AHEAD2) nr[k] = n2[k]; }
     i = ni;
   }
   // Chebyshev update of the tile's rows, one float per thread and round: the tile's entries of d, r, x are 4 KB of
@@ -834,16 +855,48 @@ __global__ __launch_bounds__(1024) void k_sweep_tiled_f32(int64_t N2, const int6
     dout[gi] = comp < 3 ? c1 * di + c2 * ri * (dinv ? dinv[gi] : 1.f) : 0.f;
   }
 }
-// (The dynamic LDS is sized for the largest tile; on the 1.12 M-tet mesh the tiles gather 889 distinct neighbours in the
-// median and 1325 at most, 21 KB, so LDS does not limit the occupancy.  Splitting the tiles into two launches by size was
-// measured: slower, 159 against 143 us.)
+// FP32 pairs, kept as the bits they were loaded as: (ratio, local index) of the displacement block, (three component-diagonal
+// values, local index) of the fluid velocity block
+__device__ inline void fma3_f32(const uint2 q, const float4* sx, float& s0, float& s1, float& s2) {
+  const float c = __uint_as_float(q.x);
+  const float4 xv = sx[q.y];
+  s0 += c * xv.x; s1 += c * xv.y; s2 += c * xv.z;
+}
+__device__ inline void fma3_f32(const uint4 q, const float4* sx, float& s0, float& s1, float& s2) {
+  const float4 xv = sx[q.w];
+  s0 += __uint_as_float(q.x) * xv.x; s1 += __uint_as_float(q.y) * xv.y; s2 += __uint_as_float(q.z) * xv.z;
+}
+// the pairs as the arrays of k_spmv_tiled_f32 hold them: NV values and a 16-bit index per pair, NV + 1 loads
+template <int NV, int AHEAD_>
+struct TileSrcArr {
+  const float* __restrict__ vals;
+  const uint16_t* __restrict__ ploc;
+  using Rec = std::conditional_t<NV == 1, uint2, uint4>;
+  static constexpr int AHEAD = AHEAD_;
+  __device__ Rec load(int64_t e) const {
+    if constexpr (NV == 1) return make_uint2(__float_as_uint(vals[e]), (uint32_t)ploc[e]);
+    else return make_uint4(__float_as_uint(vals[3 * e]), __float_as_uint(vals[3 * e + 1]), __float_as_uint(vals[3 * e + 2]), (uint32_t)ploc[e]);
+  }
+  static __device__ void fma3(const Rec q, const float4* sx, float& s0, float& s1, float& s2) { fma3_f32(q, sx, s0, s1, s2); }
+};
+// NV = 1: one ratio per pair (displacement block), NV = 3: component-diagonal values (fluid velocity block); one row ahead
+template <int NV, int TN>
+__global__ __launch_bounds__(1024) void k_sweep_tiled_f32(int64_t N2, const int64_t* __restrict__ nadj_ptr,
+                                                          const float* __restrict__ vals, const uint16_t* __restrict__ ploc,
+                                                          const int64_t* __restrict__ tile_uptr, const int32_t* __restrict__ ulist,
+                                                          const uint8_t* __restrict__ rowflag, const float* __restrict__ dinv,
+                                                          float c1, float c2, const float* __restrict__ din, float* __restrict__ dout,
+                                                          float* __restrict__ x, float* __restrict__ r) {
+  sweep_tiled<TN>(N2, nadj_ptr, TileSrcArr<NV, 1>{vals, ploc}, tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r);
+}
 void launch_sweep_tiled_f32(hipStream_t st, int nv, int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const float* vals,
                             const uint16_t* ploc, const int64_t* tile_uptr, const int32_t* ulist, const uint8_t* rowflag,
                             const float* dinv, float c1, float c2, const float* din, float* dout, float* x, float* r) {
-  const int th = tn == 128 ? 256 : 512;      // 16 lanes per node, 8 rounds per tile (measured at 256 nodes: 1024 threads no gain over 512)
-  const unsigned tiles = xcd_grid((N2 + tn - 1) / tn);
-  const size_t lds = (size_t)max_nu * sizeof(float4);
-  TILED_DISPATCH(k_sweep_tiled_f32, th, N2, nadj_ptr, vals, ploc, tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r);
+  const TiledGeom g = tiled_geom(tn, N2, max_nu);
+  dispatch_nv_tn(nv, tn, [&](auto NV, auto TN) {
+    hipLaunchKernelGGL((k_sweep_tiled_f32<NV(), TN()>), dim3(g.tiles), dim3(g.th), g.lds, st, N2, nadj_ptr, vals, ploc, tile_uptr, ulist,
+                       rowflag, dinv, c1, c2, din, dout, x, r);
+  });
 }
 // ---- FP16 matrix values for the fine-level sweeps ---------------------------------------------------------------------
 // The sweeps are a fixed polynomial in a matrix that only has to resemble the block it preconditions; rounding its VALUES
@@ -878,111 +931,47 @@ void launch_pack_h3(hipStream_t st, int64_t n, const float* v, const uint16_t* l
 void launch_pack_sb(hipStream_t st, int64_t nb, const float* v, const int32_t* col, void* rec) {
   hipLaunchKernelGGL(k_pack_sb, dim3(gridn(nb)), dim3(256), 0, st, nb, v, col, static_cast<uint2*>(rec));
 }
-template <int NV> struct TileRec;
-template <> struct TileRec<1> { using type = uint32_t; };
-template <> struct TileRec<3> { using type = uint2; };
+// the packed records as pair sources of sweep_tiled: two rows ahead
+struct TileSrcHalf1 {
+  const uint32_t* __restrict__ rec;
+  using Rec = uint32_t;
+  static constexpr int AHEAD = 2;
+  __device__ Rec load(int64_t e) const { return rec[e]; }
+  static __device__ void fma3(const Rec q, const float4* sx, float& s0, float& s1, float& s2) {
+    const float c = h2f(q & 0xffffu);
+    const float4 xv = sx[q >> 16];
+    s0 += c * xv.x; s1 += c * xv.y; s2 += c * xv.z;
+  }
+};
+struct TileSrcHalf3 {
+  const uint2* __restrict__ rec;
+  using Rec = uint2;
+  static constexpr int AHEAD = 2;
+  __device__ Rec load(int64_t e) const { return rec[e]; }
+  static __device__ void fma3(const Rec q, const float4* sx, float& s0, float& s1, float& s2) {
+    const float4 xv = sx[q.y >> 16];
+    s0 += h2f(q.x & 0xffffu) * xv.x; s1 += h2f(q.x >> 16) * xv.y; s2 += h2f(q.y & 0xffffu) * xv.z;
+  }
+};
+template <int NV> using TileSrcHalf = std::conditional_t<NV == 1, TileSrcHalf1, TileSrcHalf3>;
 // k_sweep_tiled_f32 on the packed records
 template <int NV, int TN>
 __global__ __launch_bounds__(1024) void k_sweep_tiled_h(int64_t N2, const int64_t* __restrict__ nadj_ptr,
-                                                        const typename TileRec<NV>::type* __restrict__ rec,
+                                                        const typename TileSrcHalf<NV>::Rec* __restrict__ rec,
                                                         const int64_t* __restrict__ tile_uptr, const int32_t* __restrict__ ulist,
                                                         const uint8_t* __restrict__ rowflag, const float* __restrict__ dinv,
                                                         float c1, float c2, const float* __restrict__ din, float* __restrict__ dout,
                                                         float* __restrict__ x, float* __restrict__ r) {
-  using Rec = typename TileRec<NV>::type;
-  extern __shared__ __attribute__((aligned(16))) float4 sx[];
-  __shared__ __attribute__((aligned(16))) int64_t sptr[TN + 2];
-  __shared__ __attribute__((aligned(16))) float4 ssum[TN];
-  const int64_t tile = xcd_tile((N2 + TN - 1) / TN);
-  if (tile < 0) return;
-  const int64_t u0 = tile_uptr[tile], nu = tile_uptr[tile + 1] - u0;
-  const float4* d4 = reinterpret_cast<const float4*>(din);
-  const int64_t r0 = tile * TN;
-  const int nrows = (int)((r0 + TN < N2 ? r0 + TN : N2) - r0);
-  const int nth = blockDim.x, ngrp = nth >> 4;
-  for (int64_t i = threadIdx.x; i < nu; i += 4 * nth) {        // index -> entry is a dependent pair of loads: four pairs in flight
-    const int64_t i1 = i + nth, i2 = i + 2 * nth, i3 = i + 3 * nth;
-    const int32_t k0 = ulist[u0 + i], k1 = i1 < nu ? ulist[u0 + i1] : 0, k2 = i2 < nu ? ulist[u0 + i2] : 0, k3 = i3 < nu ? ulist[u0 + i3] : 0;
-    const float4 v0 = d4[k0], v1 = d4[k1], v2 = d4[k2], v3 = d4[k3];
-    sx[i] = v0;
-    if (i1 < nu) sx[i1] = v1;
-    if (i2 < nu) sx[i2] = v2;
-    if (i3 < nu) sx[i3] = v3;
-  }
-  for (int i = threadIdx.x; i <= nrows; i += nth) sptr[i] = nadj_ptr[r0 + i];
-  __syncthreads();
-  const int sub = threadIdx.x & 15, g = threadIdx.x >> 4;
-  constexpr int KS = 4;
-  Rec cr[KS], nr[KS];
-  auto zero = [](Rec& q) { if constexpr (NV == 1) q = 0u; else q = make_uint2(0u, 0u); };
-  auto prefetch = [&](int i, Rec (&q)[KS]) {
-    const int64_t e0 = sptr[i], e1 = sptr[i + 1];
-#pragma unroll
-    for (int k = 0; k < KS; ++k) {
-      const int64_t e = e0 + sub + 16 * k;
-      if (e < e1) q[k] = rec[e]; else zero(q[k]);               // a zero record: value +0, local index 0
-    }
-  };
-  auto fma3 = [&](const Rec q, float& s0, float& s1, float& s2) {
-    if constexpr (NV == 1) {
-      const float c = h2f(q & 0xffffu);
-      const float4 xv = sx[q >> 16];
-      s0 += c * xv.x; s1 += c * xv.y; s2 += c * xv.z;
-    } else {
-      const float4 xv = sx[q.y >> 16];
-      s0 += h2f(q.x & 0xffffu) * xv.x; s1 += h2f(q.x >> 16) * xv.y; s2 += h2f(q.y & 0xffffu) * xv.z;
-    }
-  };
-  // The records of TWO rows ahead are in flight while a row is summed: a row is ~28 pairs of 4 - 8 bytes over 16 lanes, and one row
-  // ahead left ~32 KB in flight per CU, which paced the one-ratio form at ~3.7 TB/s (119.9 -> 112.1 us per displacement sweep at
-  // 1.12 M tets, A / B on one box; the 8-byte records of the fluid block: 144 us either way).
-  int i = g;
-  Rec n2[KS];
-  if (i < nrows) prefetch(i, cr);
-  if (i + ngrp < nrows) prefetch(i + ngrp, nr);
-  while (i < nrows) {
-    const int ni = i + ngrp;
-    if (ni + ngrp < nrows) prefetch(ni + ngrp, n2);
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    fma3(cr[0], s0, s1, s2);
-    fma3(cr[1], s0, s1, s2);
-    const int len = (int)(sptr[i + 1] - sptr[i]);
-    if (__builtin_amdgcn_ballot_w64(len > 32) != 0) { fma3(cr[2], s0, s1, s2); fma3(cr[3], s0, s1, s2); }
-    for (int64_t e = sptr[i] + sub + 16 * KS; e < sptr[i + 1]; e += 16) fma3(rec[e], s0, s1, s2);      // more than 64 pairs
-    s0 = group_sum<16>(s0); s1 = group_sum<16>(s1); s2 = group_sum<16>(s2);
-    if (sub == 0) ssum[i] = make_float4(s0, s1, s2, 0.f);
-#pragma unroll
-    for (int k = 0; k < KS; ++k) { cr[k] = nr[k]; nr[k] = n2[k]; }
-    i = ni;
-  }
-  __syncthreads();
-  const float* sflat = reinterpret_cast<const float*>(ssum);
-  for (int idx = threadIdx.x; idx < 4 * nrows; idx += nth) {
-    const int64_t gi = 4 * r0 + idx;
-    const int comp = idx & 3;
-    const float di = din[gi];
-    float t = sflat[idx];
-    if (rowflag && comp < 3 && rowflag[3 * (r0 + (idx >> 2)) + comp]) t = di;
-    const float ri = r[gi] - t;
-    x[gi] += di;
-    r[gi] = ri;
-    dout[gi] = comp < 3 ? c1 * di + c2 * ri * (dinv ? dinv[gi] : 1.f) : 0.f;
-  }
+  sweep_tiled<TN>(N2, nadj_ptr, TileSrcHalf<NV>{rec}, tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r);
 }
 void launch_sweep_tiled_h(hipStream_t st, int nv, int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const void* rec,
                           const int64_t* tile_uptr, const int32_t* ulist, const uint8_t* rowflag, const float* dinv, float c1,
                           float c2, const float* din, float* dout, float* x, float* r) {
-  const int th = tn == 128 ? 256 : 512;
-  const unsigned tiles = xcd_grid((N2 + tn - 1) / tn);
-  const size_t lds = (size_t)max_nu * sizeof(float4);
-  if (nv == 1 && tn == 128)
-    hipLaunchKernelGGL((k_sweep_tiled_h<1, 128>), dim3(tiles), dim3(th), lds, st, N2, nadj_ptr, static_cast<const uint32_t*>(rec), tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r);
-  else if (nv == 1)
-    hipLaunchKernelGGL((k_sweep_tiled_h<1, 256>), dim3(tiles), dim3(th), lds, st, N2, nadj_ptr, static_cast<const uint32_t*>(rec), tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r);
-  else if (tn == 128)
-    hipLaunchKernelGGL((k_sweep_tiled_h<3, 128>), dim3(tiles), dim3(th), lds, st, N2, nadj_ptr, static_cast<const uint2*>(rec), tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r);
-  else
-    hipLaunchKernelGGL((k_sweep_tiled_h<3, 256>), dim3(tiles), dim3(th), lds, st, N2, nadj_ptr, static_cast<const uint2*>(rec), tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r);
+  const TiledGeom g = tiled_geom(tn, N2, max_nu);
+  dispatch_nv_tn(nv, tn, [&](auto NV, auto TN) {
+    hipLaunchKernelGGL((k_sweep_tiled_h<NV(), TN()>), dim3(g.tiles), dim3(g.th), g.lds, st, N2, nadj_ptr,
+                       static_cast<const typename TileSrcHalf<NV()>::Rec*>(rec), tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r);
+  });
 }
 // ---- FP32 records for the fine-level sweeps of the FP32 path ---------------------------------------------------------------
 // The same values as k_sweep_tiled_f32<3> / k_sweep_sb_b3<0> read, packed with their column so that a pair or block comes in a
@@ -1007,131 +996,67 @@ void launch_pack_f3(hipStream_t st, int64_t n, const float* v, const uint16_t* l
 void launch_pack_sb_f32(hipStream_t st, int64_t nb, const float* v, const int32_t* col, void* rec) {
   hipLaunchKernelGGL(k_pack_sb_f32, dim3(gridn(nb)), dim3(256), 0, st, nb, v, col, static_cast<uint2*>(rec));
 }
-// Where k_sweep_tiled_r takes a pair's values and local index from: the 16-byte records of the fluid block (Rec3), or the two
-// arrays k_sweep_tiled_f32<1> reads for the displacement block (Arr1: value and index in two loads, kept in a uint2)
+// The 16-byte records of the fluid block as a pair source; one row ahead (see sweep_tiled)
 struct TileSrcRec3 {
   const uint4* __restrict__ rec;
   using Rec = uint4;
-  __device__ Rec operator()(int64_t e) const { return rec[e]; }
+  static constexpr int AHEAD = 1;
+  __device__ Rec load(int64_t e) const { return rec[e]; }
+  static __device__ void fma3(const Rec q, const float4* sx, float& s0, float& s1, float& s2) { fma3_f32(q, sx, s0, s1, s2); }
 };
-struct TileSrcArr1 {
-  const float* __restrict__ vals;
-  const uint16_t* __restrict__ ploc;
-  using Rec = uint2;
-  __device__ Rec operator()(int64_t e) const { return make_uint2(__float_as_uint(vals[e]), (uint32_t)ploc[e]); }
-};
-// k_sweep_tiled_f32 from a pair source: the one-ratio form (NV = 1) with two rows ahead in flight as in k_sweep_tiled_h, the
-// 16-byte records of NV = 3 with one row ahead: two rows of them are 48 VGPRs of records, 79 in all, 6 waves per SIMD instead of 8,
-// and measured slower (197 - 206 against 182 - 191 us per sweep alone).
+// the two arrays k_sweep_tiled_f32<1> reads for the displacement block, with two rows ahead in flight as in k_sweep_tiled_h
+using TileSrcArr1 = TileSrcArr<1, 2>;
+// k_sweep_tiled_f32 from a pair source
 template <int NV, int TN, class Src>
 __global__ __launch_bounds__(1024) void k_sweep_tiled_r(int64_t N2, const int64_t* __restrict__ nadj_ptr, const Src src,
                                                         const int64_t* __restrict__ tile_uptr, const int32_t* __restrict__ ulist,
                                                         const uint8_t* __restrict__ rowflag, const float* __restrict__ dinv,
                                                         float c1, float c2, const float* __restrict__ din, float* __restrict__ dout,
                                                         float* __restrict__ x, float* __restrict__ r) {
-  using Rec = typename Src::Rec;
-  extern __shared__ __attribute__((aligned(16))) float4 sx[];
-  __shared__ __attribute__((aligned(16))) int64_t sptr[TN + 2];
-  __shared__ __attribute__((aligned(16))) float4 ssum[TN];
-  const int64_t tile = xcd_tile((N2 + TN - 1) / TN);
-  if (tile < 0) return;
-  const int64_t u0 = tile_uptr[tile], nu = tile_uptr[tile + 1] - u0;
-  const float4* d4 = reinterpret_cast<const float4*>(din);
-  const int64_t r0 = tile * TN;
-  const int nrows = (int)((r0 + TN < N2 ? r0 + TN : N2) - r0);
-  const int nth = blockDim.x, ngrp = nth >> 4;
-  for (int64_t i = threadIdx.x; i < nu; i += 4 * nth) {        // index -> entry is a dependent pair of loads: four pairs in flight
-    const int64_t i1 = i + nth, i2 = i + 2 * nth, i3 = i + 3 * nth;
-    const int32_t k0 = ulist[u0 + i], k1 = i1 < nu ? ulist[u0 + i1] : 0, k2 = i2 < nu ? ulist[u0 + i2] : 0, k3 = i3 < nu ? ulist[u0 + i3] : 0;
-    const float4 v0 = d4[k0], v1 = d4[k1], v2 = d4[k2], v3 = d4[k3];
-    sx[i] = v0;
-    if (i1 < nu) sx[i1] = v1;
-    if (i2 < nu) sx[i2] = v2;
-    if (i3 < nu) sx[i3] = v3;
-  }
-  for (int i = threadIdx.x; i <= nrows; i += nth) sptr[i] = nadj_ptr[r0 + i];
-  __syncthreads();
-  const int sub = threadIdx.x & 15, g = threadIdx.x >> 4;
-  constexpr int KS = 4;
-  constexpr bool AHEAD2 = NV == 1;
-  Rec cr[KS], nr[KS], n2[KS];
-  auto zero = [](Rec& q) { if constexpr (NV == 1) q = make_uint2(0u, 0u); else q = make_uint4(0u, 0u, 0u, 0u); };      // value +0, index 0
-  auto prefetch = [&](int i, Rec (&q)[KS]) {
-    const int64_t e0 = sptr[i], e1 = sptr[i + 1];
-#pragma unroll
-    for (int k = 0; k < KS; ++k) {
-      const int64_t e = e0 + sub + 16 * k;
-      if (e < e1) q[k] = src(e); else zero(q[k]);               // a zero record: value +0, local index 0
-    }
-  };
-  auto fma3 = [&](const Rec q, float& s0, float& s1, float& s2) {
-    if constexpr (NV == 1) {
-      const float c = __uint_as_float(q.x);
-      const float4 xv = sx[q.y];
-      s0 += c * xv.x; s1 += c * xv.y; s2 += c * xv.z;
-    } else {
-      const float4 xv = sx[q.w];
-      s0 += __uint_as_float(q.x) * xv.x; s1 += __uint_as_float(q.y) * xv.y; s2 += __uint_as_float(q.z) * xv.z;
-    }
-  };
-  int i = g;
-  if (i < nrows) prefetch(i, cr);
-  if (AHEAD2 && i + ngrp < nrows) prefetch(i + ngrp, nr);
-  while (i < nrows) {
-    const int ni = i + ngrp;
-    if (AHEAD2 && ni + ngrp < nrows) prefetch(ni + ngrp, n2);
-    if (!AHEAD2 && ni < nrows) prefetch(ni, nr);
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    fma3(cr[0], s0, s1, s2);
-    fma3(cr[1], s0, s1, s2);
-    const int len = (int)(sptr[i + 1] - sptr[i]);
-    if (__builtin_amdgcn_ballot_w64(len > 32) != 0) { fma3(cr[2], s0, s1, s2); fma3(cr[3], s0, s1, s2); }
-    for (int64_t e = sptr[i] + sub + 16 * KS; e < sptr[i + 1]; e += 16) fma3(src(e), s0, s1, s2);      // more than 64 pairs
-    s0 = group_sum<16>(s0); s1 = group_sum<16>(s1); s2 = group_sum<16>(s2);
-    if (sub == 0) ssum[i] = make_float4(s0, s1, s2, 0.f);
-#pragma unroll
-    for (int k = 0; k < KS; ++k) { cr[k] = nr[k]; if (AHEAD2) nr[k] = n2[k]; }
-    i = ni;
-  }
-  __syncthreads();
-  const float* sflat = reinterpret_cast<const float*>(ssum);
-  for (int idx = threadIdx.x; idx < 4 * nrows; idx += nth) {
-    const int64_t gi = 4 * r0 + idx;
-    const int comp = idx & 3;
-    const float di = din[gi];
-    float t = sflat[idx];
-    if (rowflag && comp < 3 && rowflag[3 * (r0 + (idx >> 2)) + comp]) t = di;
-    const float ri = r[gi] - t;
-    x[gi] += di;
-    r[gi] = ri;
-    dout[gi] = comp < 3 ? c1 * di + c2 * ri * (dinv ? dinv[gi] : 1.f) : 0.f;
-  }
+  sweep_tiled<TN>(N2, nadj_ptr, src, tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r);
 }
-#define TILED_R(NV_, SRC)                                                                                                     \
-  do {                                                                                                                   \
-    if (tn == 128) hipLaunchKernelGGL((k_sweep_tiled_r<NV_, 128, SRC>), dim3(tiles), dim3(th), lds, st, N2, nadj_ptr, src, tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r); \
-    else hipLaunchKernelGGL((k_sweep_tiled_r<NV_, 256, SRC>), dim3(tiles), dim3(th), lds, st, N2, nadj_ptr, src, tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x, r); \
-  } while (0)
+template <int NV, class Src>
+static void launch_sweep_tiled_src(hipStream_t st, int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const Src src,
+                                   const int64_t* tile_uptr, const int32_t* ulist, const uint8_t* rowflag, const float* dinv, float c1,
+                                   float c2, const float* din, float* dout, float* x, float* r) {
+  const TiledGeom g = tiled_geom(tn, N2, max_nu);
+  dispatch_tn(tn, [&](auto TN) {
+    hipLaunchKernelGGL((k_sweep_tiled_r<NV, TN(), Src>), dim3(g.tiles), dim3(g.th), g.lds, st, N2, nadj_ptr, src, tile_uptr, ulist, rowflag,
+                       dinv, c1, c2, din, dout, x, r);
+  });
+}
 void launch_sweep_tiled_r3(hipStream_t st, int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const void* rec,
                            const int64_t* tile_uptr, const int32_t* ulist, const uint8_t* rowflag, const float* dinv, float c1,
                            float c2, const float* din, float* dout, float* x, float* r) {
-  const int th = tn == 128 ? 256 : 512;
-  const unsigned tiles = xcd_grid((N2 + tn - 1) / tn);
-  const size_t lds = (size_t)max_nu * sizeof(float4);
-  const TileSrcRec3 src{static_cast<const uint4*>(rec)};
-  TILED_R(3, TileSrcRec3);
+  launch_sweep_tiled_src<3>(st, tn, N2, max_nu, nadj_ptr, TileSrcRec3{static_cast<const uint4*>(rec)}, tile_uptr, ulist, rowflag, dinv,
+                            c1, c2, din, dout, x, r);
 }
 // the one-ratio form on the arrays of k_sweep_tiled_f32 (value and local index in two loads), two rows ahead in flight
 void launch_sweep_tiled_a1(hipStream_t st, int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const float* vals,
                            const uint16_t* ploc, const int64_t* tile_uptr, const int32_t* ulist, const uint8_t* rowflag,
                            const float* dinv, float c1, float c2, const float* din, float* dout, float* x, float* r) {
-  const int th = tn == 128 ? 256 : 512;
-  const unsigned tiles = xcd_grid((N2 + tn - 1) / tn);
-  const size_t lds = (size_t)max_nu * sizeof(float4);
-  const TileSrcArr1 src{vals, ploc};
-  TILED_R(1, TileSrcArr1);
+  launch_sweep_tiled_src<1>(st, tn, N2, max_nu, nadj_ptr, TileSrcArr1{vals, ploc}, tile_uptr, ulist, rowflag, dinv, c1, c2, din, dout, x,
+                            r);
 }
-#undef TILED_R
+// The B^-1 r epilogue of the solid sweeps.  A row's lanes hold its products s0 s1 s2 (already summed over the row); lanes 0 - 2
+// of the row do one component each:  r -= t,  x += d_in,  d_out = c1 d_in + c2 B^-1 r  with row sub of the node's 3x3 inverse
+// (binv12: three rows of four floats).  All lanes of the row's first quad have to call it.
+__device__ __forceinline__ void sb_update(int64_t i, int sub, float s0, float s1, float s2, const float* __restrict__ binv12, float c1,
+                                          float c2, const float* __restrict__ din, float* __restrict__ dout, float* __restrict__ x,
+                                          float* __restrict__ r) {
+  float rc = 0.f, dc = 0.f;
+  if (sub < 3) {
+    dc = din[4 * i + sub];
+    rc = r[4 * i + sub] - (sub == 0 ? s0 : (sub == 1 ? s1 : s2));
+  }
+  const float r0 = dpp_f<0x00>(rc), r1 = dpp_f<0x55>(rc), r2 = dpp_f<0xAA>(rc);      // lanes 0-2 of the row, seen from its first quad
+  if (sub < 3) {
+    const float4 brow = reinterpret_cast<const float4*>(binv12 + 12 * i)[sub];
+    x[4 * i + sub] += dc;
+    r[4 * i + sub] = rc;
+    dout[4 * i + sub] = c1 * dc + c2 * (brow.x * r0 + brow.y * r1 + brow.z * r2);
+  }
+}
 // k_sweep_sb_b3<0> on the packed 24-byte block records.  LPR lanes per row with 32 / LPR blocks in flight per lane: the sweep is a chain
 // of three dependent loads (row pointer -> record -> gathered d) per round of resident waves, and 150 k rows of 16 lanes are 4.6 rounds;
 // 8 lanes per row are half the rounds with twice the loads in flight per lane (measured at 1.12 M tets, A / B on one box: 16 lanes
@@ -1173,18 +1098,7 @@ __global__ __launch_bounds__(256) void k_sweep_sb_h(int64_t nS, const int64_t* _
       }
     }
     s0 = group_sum<LPR>(s0); s1 = group_sum<LPR>(s1); s2 = group_sum<LPR>(s2);
-    float rc = 0.f, dc = 0.f;
-    if (sub < 3) {
-      dc = din[4 * i + sub];
-      rc = r[4 * i + sub] - (sub == 0 ? s0 : (sub == 1 ? s1 : s2));
-    }
-    const float r0 = dpp_f<0x00>(rc), r1 = dpp_f<0x55>(rc), r2 = dpp_f<0xAA>(rc);      // lanes 0-2 of the row, seen from its first quad
-    if (sub < 3) {
-      const float4 brow = reinterpret_cast<const float4*>(binv12 + 12 * i)[sub];
-      x[4 * i + sub] += dc;
-      r[4 * i + sub] = rc;
-      dout[4 * i + sub] = c1 * dc + c2 * (brow.x * r0 + brow.y * r1 + brow.z * r2);
-    }
+    sb_update(i, sub, s0, s1, s2, binv12, c1, c2, din, dout, x, r);
   }
 }
 void launch_sweep_sb_h(hipStream_t st, int64_t nS, const int64_t* sb_ptr, const void* rec, const float* binv12, float c1, float c2,
@@ -1859,18 +1773,20 @@ void launch_sweep_csr_f64(hipStream_t st, int64_t n, const int64_t* rowptr, cons
   hipLaunchKernelGGL((k_sweep_csr_mixed<8, 8, double>), dim3((unsigned)blocks), dim3(256), 0, st, n, rowptr, cols, vals, diagpos, vals, c1, c2,
                      din, dout, x, r);
 }
-// The Schur sweep on packed records (FP16 value + 16-bit tile-local column, 4 bytes per entry instead of 8) with the d entries
-// of a 256-row tile's columns staged once in LDS (FP64; the tile of a two-ring pattern sees ~2-3 k distinct columns).
-// Vectors stay FP64 as in k_sweep_csr_mixed; a rounded matrix is still one linear operator.
-// SCHUR_TILE rows per workgroup (64 | 128 | 256, chosen per context from the number of pressure rows: FsiTuning.schur_tile_rows).
+// The Schur sweep on tiles of SCHUR_TILE rows with the d entries of a tile's columns staged once in LDS (FP64; the tile of a
+// two-ring pattern sees ~2-3 k distinct columns) and 16-bit tile-local columns.  Vectors are FP64 as in k_sweep_csr_mixed.
+// SCHUR_TILE rows per workgroup (32 | 64 | 128 | 256, chosen per context from the number of pressure rows: FsiTuning.schur_tile_rows).
 // A sweep is a chain of dependent steps per workgroup - stage the tile's distinct columns, 32 rows per pass, update - and at the
 // per-GPU sizes of a partitioned run (24 k rows: 94 tiles of 256 rows on 256 CUs) its length, not the chip, sets the time.
-template <int SCHUR_TILE>
-__global__ __launch_bounds__(256) void k_sweep_schur_tiled(int64_t n, const int64_t* __restrict__ rowptr,
-                                                           const uint32_t* __restrict__ rec, const int64_t* __restrict__ tile_uptr,
-                                                           const int32_t* __restrict__ ulist, const double* __restrict__ dinv,
-                                                           double c1, double c2, const double* __restrict__ din,
-                                                           double* __restrict__ dout, double* __restrict__ x, double* __restrict__ r) {
+// sweep_schur_tiled is the one body of k_sweep_schur_tiled and k_sweep_schur_tiled_f64; its Src supplies
+//   Rec, load(e), value(q), col(q)   entry e as a record, its value as a double and its local column; Rec{}, all bits zero, is
+//                                    value +0 and local index 0 (a staged entry): the record of an entry past the row's end
+//   dnext(c1, di, c2, ri, row)       the new direction: c1 di + c2 ri over the row's diagonal, in the source's own form
+template <int SCHUR_TILE, class Src>
+__device__ __forceinline__ void sweep_schur_tiled(int64_t n, const int64_t* __restrict__ rowptr, const Src src,
+                                                  const int64_t* __restrict__ tile_uptr, const int32_t* __restrict__ ulist, double c1,
+                                                  double c2, const double* __restrict__ din, double* __restrict__ dout,
+                                                  double* __restrict__ x, double* __restrict__ r) {
   extern __shared__ __attribute__((aligned(16))) double sxd[];
   __shared__ int64_t sptr[SCHUR_TILE + 1];
   __shared__ double ssum[SCHUR_TILE];
@@ -1895,11 +1811,11 @@ __global__ __launch_bounds__(256) void k_sweep_schur_tiled(int64_t n, const int6
     const int64_t b = sptr[row + 1];
     double s = 0.0;
     for (int64_t e = sptr[row] + sub; e < b; e += 64) {
-      uint32_t q[8];
+      typename Src::Rec q[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) q[j] = e + 8 * j < b ? rec[e + 8 * j] : 0u;      // zero record: value +0, local index 0
+      for (int j = 0; j < 8; ++j) q[j] = e + 8 * j < b ? src.load(e + 8 * j) : typename Src::Rec{};
 #pragma unroll
-      for (int j = 0; j < 8; ++j) s += (double)h2f(q[j] & 0xffffu) * sxd[q[j] >> 16];
+      for (int j = 0; j < 8; ++j) s += Src::value(q[j]) * sxd[Src::col(q[j])];
     }
     s = group_sum<8>(s);
     if (sub == 0) ssum[row] = s;
@@ -1910,27 +1826,58 @@ __global__ __launch_bounds__(256) void k_sweep_schur_tiled(int64_t n, const int6
     const double di = din[row], ri = r[row] - ssum[threadIdx.x];
     x[row] += di;
     r[row] = ri;
-    dout[row] = c1 * di + c2 * ri * dinv[row];
+    dout[row] = src.dnext(c1, di, c2, ri, row);
   }
+}
+template <class F> static void dispatch_schur_rows(int tile_rows, F f) {
+  if (tile_rows == 32) f(Int<32>{});
+  else if (tile_rows == 64) f(Int<64>{});
+  else if (tile_rows == 128) f(Int<128>{});
+  else f(Int<256>{});
+}
+// Packed records (FP16 value + 16-bit tile-local column, 4 bytes per entry instead of 8) and the stored inverse diagonal; a
+// rounded matrix is still one linear operator.
+struct SchurSrcHalf {
+  const uint32_t* __restrict__ rec;
+  const double* __restrict__ dinv;
+  using Rec = uint32_t;
+  __device__ Rec load(int64_t e) const { return rec[e]; }
+  static __device__ double value(Rec q) { return (double)h2f(q & 0xffffu); }
+  static __device__ uint32_t col(Rec q) { return q >> 16; }
+  __device__ double dnext(double c1, double di, double c2, double ri, int64_t row) const { return c1 * di + c2 * ri * dinv[row]; }
+};
+template <int SCHUR_TILE>
+__global__ __launch_bounds__(256) void k_sweep_schur_tiled(int64_t n, const int64_t* __restrict__ rowptr,
+                                                           const uint32_t* __restrict__ rec, const int64_t* __restrict__ tile_uptr,
+                                                           const int32_t* __restrict__ ulist, const double* __restrict__ dinv,
+                                                           double c1, double c2, const double* __restrict__ din,
+                                                           double* __restrict__ dout, double* __restrict__ x, double* __restrict__ r) {
+  sweep_schur_tiled<SCHUR_TILE>(n, rowptr, SchurSrcHalf{rec, dinv}, tile_uptr, ulist, c1, c2, din, dout, x, r);
 }
 void launch_sweep_schur_tiled(hipStream_t st, int tile_rows, int64_t n, int max_nu, const int64_t* rowptr, const uint32_t* rec,
                               const int64_t* tile_uptr, const int32_t* ulist, const double* dinv, double c1, double c2,
                               const double* din, double* dout, double* x, double* r) {
   const unsigned tiles = xcd_grid((n + tile_rows - 1) / tile_rows);
   const size_t lds = (size_t)max_nu * sizeof(double);
-  if (tile_rows == 32)
-    hipLaunchKernelGGL(k_sweep_schur_tiled<32>, dim3(tiles), dim3(256), lds, st, n, rowptr, rec, tile_uptr, ulist, dinv, c1, c2, din, dout, x, r);
-  else if (tile_rows == 64)
-    hipLaunchKernelGGL(k_sweep_schur_tiled<64>, dim3(tiles), dim3(256), lds, st, n, rowptr, rec, tile_uptr, ulist, dinv, c1, c2, din, dout, x, r);
-  else if (tile_rows == 128)
-    hipLaunchKernelGGL(k_sweep_schur_tiled<128>, dim3(tiles), dim3(256), lds, st, n, rowptr, rec, tile_uptr, ulist, dinv, c1, c2, din, dout, x, r);
-  else
-    hipLaunchKernelGGL(k_sweep_schur_tiled<256>, dim3(tiles), dim3(256), lds, st, n, rowptr, rec, tile_uptr, ulist, dinv, c1, c2, din, dout, x, r);
+  dispatch_schur_rows(tile_rows, [&](auto TR) {
+    hipLaunchKernelGGL(k_sweep_schur_tiled<TR()>, dim3(tiles), dim3(256), lds, st, n, rowptr, rec, tile_uptr, ulist, dinv, c1, c2, din,
+                       dout, x, r);
+  });
 }
 // The all-FP64 Schur sweep on the same tiles: FP64 values in CSR order and the 16-bit tile-local column (10 bytes per entry instead
 // of 12, and no gather of d from global memory).  Bitwise equal to k_sweep_csr_mixed<8, 8, double>: 8 lanes per row, lane sub
 // takes entries sub + 8 j + 64 t in the same order and form, the same group_sum, the same update with the division by the diagonal
 // (the stored s_dinv of the FP16 form rounds differently).
+struct SchurSrcF64 {
+  const double* __restrict__ vals;
+  const uint16_t* __restrict__ ploc;
+  const int64_t* __restrict__ diagpos;
+  struct Rec { double v; int k; };
+  __device__ Rec load(int64_t e) const { return {vals[e], (int)ploc[e]}; }
+  static __device__ double value(const Rec& q) { return q.v; }
+  static __device__ int col(const Rec& q) { return q.k; }
+  __device__ double dnext(double c1, double di, double c2, double ri, int64_t row) const { return c1 * di + c2 * ri / vals[diagpos[row]]; }
+};
 template <int SCHUR_TILE>
 __global__ __launch_bounds__(256) void k_sweep_schur_tiled_f64(int64_t n, const int64_t* __restrict__ rowptr,
                                                                const double* __restrict__ vals, const uint16_t* __restrict__ ploc,
@@ -1938,104 +1885,86 @@ __global__ __launch_bounds__(256) void k_sweep_schur_tiled_f64(int64_t n, const 
                                                                const int64_t* __restrict__ diagpos, double c1, double c2,
                                                                const double* __restrict__ din, double* __restrict__ dout,
                                                                double* __restrict__ x, double* __restrict__ r) {
-  extern __shared__ __attribute__((aligned(16))) double sxd[];
-  __shared__ int64_t sptr[SCHUR_TILE + 1];
-  __shared__ double ssum[SCHUR_TILE];
-  const int64_t tile = xcd_tile((n + SCHUR_TILE - 1) / SCHUR_TILE);
-  if (tile < 0) return;
-  const int64_t r0 = tile * SCHUR_TILE;
-  const int nrows = (int)((r0 + SCHUR_TILE < n ? r0 + SCHUR_TILE : n) - r0);
-  const int64_t u0 = tile_uptr[tile], nu = tile_uptr[tile + 1] - u0;
-  for (int64_t i = threadIdx.x; i < nu; i += 1024) {              // four dependent index -> entry pairs in flight
-    const int64_t i1 = i + 256, i2 = i + 512, i3 = i + 768;
-    const int32_t k0 = ulist[u0 + i], k1 = i1 < nu ? ulist[u0 + i1] : 0, k2 = i2 < nu ? ulist[u0 + i2] : 0, k3 = i3 < nu ? ulist[u0 + i3] : 0;
-    const double v0 = din[k0], v1 = din[k1], v2 = din[k2], v3 = din[k3];
-    sxd[i] = v0;
-    if (i1 < nu) sxd[i1] = v1;
-    if (i2 < nu) sxd[i2] = v2;
-    if (i3 < nu) sxd[i3] = v3;
-  }
-  for (int i = threadIdx.x; i <= nrows; i += 256) sptr[i] = rowptr[r0 + i];
-  __syncthreads();
-  const int sub = threadIdx.x & 7, g = threadIdx.x >> 3;          // 8 lanes per row, 32 rows per pass
-  for (int row = g; row < nrows; row += 32) {
-    const int64_t b = sptr[row + 1];
-    double s = 0.0;
-    for (int64_t e = sptr[row] + sub; e < b; e += 64) {
-      double v[8];
-      int k[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {                                // past the end: value +0, local index 0 (a staged entry)
-        const bool in = e + 8 * j < b;
-        v[j] = in ? vals[e + 8 * j] : 0.0;
-        k[j] = in ? (int)ploc[e + 8 * j] : 0;
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += v[j] * sxd[k[j]];
-    }
-    s = group_sum<8>(s);
-    if (sub == 0) ssum[row] = s;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < nrows) {
-    const int64_t row = r0 + threadIdx.x;
-    const double di = din[row], ri = r[row] - ssum[threadIdx.x];
-    x[row] += di;
-    r[row] = ri;
-    dout[row] = c1 * di + c2 * ri / vals[diagpos[row]];
-  }
+  sweep_schur_tiled<SCHUR_TILE>(n, rowptr, SchurSrcF64{vals, ploc, diagpos}, tile_uptr, ulist, c1, c2, din, dout, x, r);
 }
 void launch_sweep_schur_tiled_f64(hipStream_t st, int tile_rows, int64_t n, int max_nu, const int64_t* rowptr, const double* vals,
                                   const uint16_t* ploc, const int64_t* tile_uptr, const int32_t* ulist, const int64_t* diagpos,
                                   double c1, double c2, const double* din, double* dout, double* x, double* r) {
   const unsigned tiles = xcd_grid((n + tile_rows - 1) / tile_rows);
   const size_t lds = (size_t)max_nu * sizeof(double);
-#define SCHUR_F64(TR) hipLaunchKernelGGL(k_sweep_schur_tiled_f64<TR>, dim3(tiles), dim3(256), lds, st, n, rowptr, vals, ploc, tile_uptr, ulist, diagpos, c1, c2, din, dout, x, r)
-  if (tile_rows == 32) SCHUR_F64(32);
-  else if (tile_rows == 64) SCHUR_F64(64);
-  else if (tile_rows == 128) SCHUR_F64(128);
-  else SCHUR_F64(256);
-#undef SCHUR_F64
+  dispatch_schur_rows(tile_rows, [&](auto TR) {
+    hipLaunchKernelGGL(k_sweep_schur_tiled_f64<TR()>, dim3(tiles), dim3(256), lds, st, n, rowptr, vals, ploc, tile_uptr, ulist, diagpos,
+                       c1, c2, din, dout, x, r);
+  });
 }
 // One Chebyshev sweep of the solid block in a single launch: t = A d_in (3x3 block-CSR, 16 lanes per node), then on the
-// first three lanes of the group (one component each)  r -= t,  x += d_in,  d_out = c1 d_in + c2 B^-1 r.
+// first three lanes of the group (one component each)  r -= t,  x += d_in,  d_out = c1 d_in + c2 B^-1 r  (sb_update).
 // d is ping-ponged because other nodes still gather d_in; the product never goes through memory.
-template <int LEVEL>      // LEVEL only names the instantiation: 0 = solid nodes, 1 = coarse level (solid vertices) of the two-level cycle
+// sweep_sb_rows16 is the frame of the 16-lane forms: row_sum(b, bend, s0, s1, s2) adds the lane's blocks b, b + 16, .. < bend
+// (workgroups in the XCD-aware order of xcd_tile; a grid-stride loop over the logical workgroups keeps the launch's cap)
+template <class RowSum>
+__device__ __forceinline__ void sweep_sb_rows16(int64_t nS, const int64_t* __restrict__ sb_ptr, const float* __restrict__ binv12,
+                                                float c1, float c2, const float* __restrict__ din, float* __restrict__ dout,
+                                                float* __restrict__ x, float* __restrict__ r, RowSum row_sum) {
+  const int sub = threadIdx.x & 15;
+  const int64_t nlb = (nS + 15) / 16, nwg = gridDim.x, span = xcd_span(nlb);
+  for (int64_t lb0 = blockIdx.x; lb0 < span; lb0 += nwg) {
+    const int64_t lb = xcd_unit(lb0, nlb);
+    const int64_t i = lb * 16 + (threadIdx.x >> 4);
+    if (lb >= 0 && i < nS) {
+      float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+      row_sum(sb_ptr[i] + sub, sb_ptr[i + 1], s0, s1, s2);
+      s0 = group_sum<16>(s0); s1 = group_sum<16>(s1); s2 = group_sum<16>(s2);
+      sb_update(i, sub, s0, s1, s2, binv12, c1, c2, din, dout, x, r);
+    }
+  }
+}
+// Two 16-block strips per round, issued together (index -> gathered d is a dependent pair of loads; an edge node's ~22
+// blocks take one round instead of two, a vertex node's ~65 three instead of five); the strip past the end re-reads
+// the first one with its d zeroed.  src.load(b): the nine values of block b, row-major, and its column.
+struct SbBlock { float a[9]; int col; };
+template <class Src>
+__device__ __forceinline__ void sb_sum_two_strips(const Src src, const float* __restrict__ din, int64_t b, int64_t bend, float& s0,
+                                                  float& s1, float& s2) {
+  for (; b < bend; b += 32) {
+    const bool p1 = b + 16 < bend;
+    const SbBlock A = src.load(b), Q = src.load(p1 ? b + 16 : b);
+    const float4 xv = reinterpret_cast<const float4*>(din)[A.col];
+    float4 yv = reinterpret_cast<const float4*>(din)[Q.col];
+    if (!p1) yv = make_float4(0.f, 0.f, 0.f, 0.f);
+    s0 += (A.a[0] * xv.x + A.a[1] * xv.y + A.a[2] * xv.z) + (Q.a[0] * yv.x + Q.a[1] * yv.y + Q.a[2] * yv.z);
+    s1 += (A.a[3] * xv.x + A.a[4] * xv.y + A.a[5] * xv.z) + (Q.a[3] * yv.x + Q.a[4] * yv.y + Q.a[5] * yv.z);
+    s2 += (A.a[6] * xv.x + A.a[7] * xv.y + A.a[8] * xv.z) + (Q.a[6] * yv.x + Q.a[7] * yv.y + Q.a[8] * yv.z);
+  }
+}
+struct SbSrcArr {       // nine floats and sb_col: ten 4-byte loads
+  const int32_t* __restrict__ sb_col;
+  const float* __restrict__ vals;
+  __device__ SbBlock load(int64_t b) const {
+    const float* a = vals + 9 * b;
+    return {{a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]}, sb_col[b]};
+  }
+};
+struct SbSrcRec {       // the 40-byte FP32 records of k_pack_sb_f32: five 8-byte loads
+  const uint2* __restrict__ rec;
+  __device__ SbBlock load(int64_t b) const {
+    const uint2* p = rec + 5 * b;
+    const uint2 a01 = p[0], a23 = p[1], a45 = p[2], a67 = p[3], a8c = p[4];
+    return {{__uint_as_float(a01.x), __uint_as_float(a01.y), __uint_as_float(a23.x), __uint_as_float(a23.y), __uint_as_float(a45.x),
+             __uint_as_float(a45.y), __uint_as_float(a67.x), __uint_as_float(a67.y), __uint_as_float(a8c.x)}, (int)a8c.y};
+  }
+};
+template <int LEVEL>      // 0 = solid nodes: two strips; 1 = coarse level (solid vertices) of the two-level cycle: ~15 blocks per row, one strip
 __global__ __launch_bounds__(256) void k_sweep_sb_b3(int64_t nS, const int64_t* __restrict__ sb_ptr,
                                                      const int32_t* __restrict__ sb_col, const float* __restrict__ vals,
                                                      const float* __restrict__ binv12, float c1, float c2,
                                                      const float* __restrict__ din, float* __restrict__ dout,
                                                      float* __restrict__ x, float* __restrict__ r) {
-  const int sub = threadIdx.x & 15;
-  // (workgroups in the XCD-aware order of xcd_tile; a grid-stride loop over the logical workgroups keeps the launch's cap)
-  const int64_t nlb = (nS + 15) / 16, nwg = gridDim.x, span = xcd_span(nlb);
-  for (int64_t lb0 = blockIdx.x; lb0 < span; lb0 += nwg) {
-  const int64_t lb = xcd_unit(lb0, nlb);
-  const int64_t i = lb * 16 + (threadIdx.x >> 4);
-  if (lb >= 0 && i < nS) {
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    const int64_t bend = sb_ptr[i + 1];
-    if (LEVEL == 0) {
-      // two 16-block strips per round, issued together (index -> gathered d is a dependent pair of loads; an edge node's ~22
-      // blocks take one round instead of two, a vertex node's ~65 three instead of five); the strip past the end re-reads
-      // the first one with its d zeroed
-      for (int64_t b = sb_ptr[i] + sub; b < bend; b += 32) {
-        const bool p1 = b + 16 < bend;
-        const int64_t b1 = p1 ? b + 16 : b;
-        const int k0 = sb_col[b], k1 = sb_col[b1];
-        const float* a = vals + 9 * b;
-        const float* q = vals + 9 * b1;
-        const float a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], a4 = a[4], a5 = a[5], a6 = a[6], a7 = a[7], a8 = a[8];
-        const float q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5], q6 = q[6], q7 = q[7], q8 = q[8];
-        const float4 xv = reinterpret_cast<const float4*>(din)[k0];
-        float4 yv = reinterpret_cast<const float4*>(din)[k1];
-        if (!p1) yv = make_float4(0.f, 0.f, 0.f, 0.f);
-        s0 += (a0 * xv.x + a1 * xv.y + a2 * xv.z) + (q0 * yv.x + q1 * yv.y + q2 * yv.z);
-        s1 += (a3 * xv.x + a4 * xv.y + a5 * xv.z) + (q3 * yv.x + q4 * yv.y + q5 * yv.z);
-        s2 += (a6 * xv.x + a7 * xv.y + a8 * xv.z) + (q6 * yv.x + q7 * yv.y + q8 * yv.z);
-      }
+  sweep_sb_rows16(nS, sb_ptr, binv12, c1, c2, din, dout, x, r, [&](int64_t b, int64_t bend, float& s0, float& s1, float& s2) {
+    if constexpr (LEVEL == 0) {
+      sb_sum_two_strips(SbSrcArr{sb_col, vals}, din, b, bend, s0, s1, s2);
     } else {
-      for (int64_t b = sb_ptr[i] + sub; b < bend; b += 16) {
+      for (; b < bend; b += 16) {
         const float4 xv = reinterpret_cast<const float4*>(din)[sb_col[b]];
         const float* a = vals + 9 * b;
         const float x0 = xv.x, x1 = xv.y, x2 = xv.z;
@@ -2044,21 +1973,7 @@ __global__ __launch_bounds__(256) void k_sweep_sb_b3(int64_t nS, const int64_t* 
         s2 += a[6] * x0 + a[7] * x1 + a[8] * x2;
       }
     }
-    s0 = group_sum<16>(s0); s1 = group_sum<16>(s1); s2 = group_sum<16>(s2);
-    float rc = 0.f, dc = 0.f;
-    if (sub < 3) {
-      dc = din[4 * i + sub];
-      rc = r[4 * i + sub] - (sub == 0 ? s0 : (sub == 1 ? s1 : s2));
-    }
-    const float r0 = dpp_f<0x00>(rc), r1 = dpp_f<0x55>(rc), r2 = dpp_f<0xAA>(rc);      // lanes 0-2 of the row, seen from its first quad
-    if (sub < 3) {
-      const float4 brow = reinterpret_cast<const float4*>(binv12 + 12 * i)[sub];
-      x[4 * i + sub] += dc;
-      r[4 * i + sub] = rc;
-      dout[4 * i + sub] = c1 * dc + c2 * (brow.x * r0 + brow.y * r1 + brow.z * r2);
-    }
-  }
-  }
+  });
 }
 void launch_sweep_sb_b3(hipStream_t st, int64_t nS, const int64_t* sb_ptr, const int32_t* sb_col, const float* vals,
                         const float* binv12, float c1, float c2, const float* din, float* dout, float* x, float* r, int level) {
@@ -2077,49 +1992,9 @@ __global__ __launch_bounds__(256) void k_sweep_sb_r(int64_t nS, const int64_t* _
                                                     const float* __restrict__ binv12, float c1, float c2,
                                                     const float* __restrict__ din, float* __restrict__ dout,
                                                     float* __restrict__ x, float* __restrict__ r) {
-  const int sub = threadIdx.x & 15;
-  const int64_t nlb = (nS + 15) / 16, nwg = gridDim.x, span = xcd_span(nlb);
-  for (int64_t lb0 = blockIdx.x; lb0 < span; lb0 += nwg) {
-  const int64_t lb = xcd_unit(lb0, nlb);
-  const int64_t i = lb * 16 + (threadIdx.x >> 4);
-  if (lb >= 0 && i < nS) {
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    const int64_t bend = sb_ptr[i + 1];
-    for (int64_t b = sb_ptr[i] + sub; b < bend; b += 32) {
-      const bool p1 = b + 16 < bend;
-      const int64_t b1 = p1 ? b + 16 : b;
-      const uint2* pa = rec + 5 * b;
-      const uint2* pq = rec + 5 * b1;
-      const uint2 a01 = pa[0], a23 = pa[1], a45 = pa[2], a67 = pa[3], a8c = pa[4];
-      const uint2 q01 = pq[0], q23 = pq[1], q45 = pq[2], q67 = pq[3], q8c = pq[4];
-      const float4 xv = reinterpret_cast<const float4*>(din)[a8c.y];
-      float4 yv = reinterpret_cast<const float4*>(din)[q8c.y];
-      if (!p1) yv = make_float4(0.f, 0.f, 0.f, 0.f);
-      const float a0 = __uint_as_float(a01.x), a1 = __uint_as_float(a01.y), a2 = __uint_as_float(a23.x), a3 = __uint_as_float(a23.y),
-                  a4 = __uint_as_float(a45.x), a5 = __uint_as_float(a45.y), a6 = __uint_as_float(a67.x), a7 = __uint_as_float(a67.y),
-                  a8 = __uint_as_float(a8c.x);
-      const float q0 = __uint_as_float(q01.x), q1 = __uint_as_float(q01.y), q2 = __uint_as_float(q23.x), q3 = __uint_as_float(q23.y),
-                  q4 = __uint_as_float(q45.x), q5 = __uint_as_float(q45.y), q6 = __uint_as_float(q67.x), q7 = __uint_as_float(q67.y),
-                  q8 = __uint_as_float(q8c.x);
-      s0 += (a0 * xv.x + a1 * xv.y + a2 * xv.z) + (q0 * yv.x + q1 * yv.y + q2 * yv.z);
-      s1 += (a3 * xv.x + a4 * xv.y + a5 * xv.z) + (q3 * yv.x + q4 * yv.y + q5 * yv.z);
-      s2 += (a6 * xv.x + a7 * xv.y + a8 * xv.z) + (q6 * yv.x + q7 * yv.y + q8 * yv.z);
-    }
-    s0 = group_sum<16>(s0); s1 = group_sum<16>(s1); s2 = group_sum<16>(s2);
-    float rc = 0.f, dc = 0.f;
-    if (sub < 3) {
-      dc = din[4 * i + sub];
-      rc = r[4 * i + sub] - (sub == 0 ? s0 : (sub == 1 ? s1 : s2));
-    }
-    const float r0 = dpp_f<0x00>(rc), r1 = dpp_f<0x55>(rc), r2 = dpp_f<0xAA>(rc);
-    if (sub < 3) {
-      const float4 brow = reinterpret_cast<const float4*>(binv12 + 12 * i)[sub];
-      x[4 * i + sub] += dc;
-      r[4 * i + sub] = rc;
-      dout[4 * i + sub] = c1 * dc + c2 * (brow.x * r0 + brow.y * r1 + brow.z * r2);
-    }
-  }
-  }
+  sweep_sb_rows16(nS, sb_ptr, binv12, c1, c2, din, dout, x, r, [&](int64_t b, int64_t bend, float& s0, float& s1, float& s2) {
+    sb_sum_two_strips(SbSrcRec{rec}, din, b, bend, s0, s1, s2);
+  });
 }
 void launch_sweep_sb_r(hipStream_t st, int64_t nS, const int64_t* sb_ptr, const void* rec, const float* binv12, float c1, float c2,
                        const float* din, float* dout, float* x, float* r) {

@@ -215,82 +215,69 @@ int shim_spmv_tiled_f32(int nv, int tn, int64_t N2, int max_nu, const int64_t* n
   float* dy = c.io(y, (size_t)(4 * N2));
   SHIM_RUN(c, "launch_spmv_tiled_f32", launch_spmv_tiled_f32(c.st, nv, tn, N2, max_nu, dp, dv, dl, du, dul, df, dx, dy));
 }
+// what the four tiled sweep entries share on the device: the graph's row pointers, the tiles, rowflag, dinv and the four vectors
+struct TiledSweepArgs {
+  const int64_t *dp, *du;
+  const int32_t* dul;
+  const uint8_t* df;
+  const float* ddv;
+  float *ddi, *ddo, *dx, *dr;
+  TiledSweepArgs(Call& c, int tn, int64_t N2, const int64_t* nadj_ptr, const int64_t* tile_uptr, const int32_t* ulist,
+                 const uint8_t* rowflag, const float* dinv, float* din, float* dout, float* x, float* r) {
+    const int64_t nt = tiles_of(N2, tn);
+    dp = c.in(nadj_ptr, (size_t)N2 + 1);
+    du = c.in(tile_uptr, (size_t)nt + 1);
+    dul = c.in(ulist, (size_t)tile_uptr[nt]);
+    df = c.in(rowflag, (size_t)(3 * N2));
+    ddv = c.in(dinv, (size_t)(4 * N2));
+    ddi = c.io(din, (size_t)(4 * N2));
+    ddo = c.io(dout, (size_t)(4 * N2));
+    dx = c.io(x, (size_t)(4 * N2));
+    dr = c.io(r, (size_t)(4 * N2));
+  }
+};
 int shim_sweep_tiled_f32(int nv, int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const float* vals, const uint16_t* ploc,
                          const int64_t* tile_uptr, const int32_t* ulist, const uint8_t* rowflag, const float* dinv, float c1,
                          float c2, float* din, float* dout, float* x, float* r) {
   Call c;
-  const int64_t np = nadj_ptr[N2], nt = tiles_of(N2, tn);
-  const int64_t* dp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const int64_t np = nadj_ptr[N2];
   const float* dv = c.in(vals, (size_t)(nv * np));
   const uint16_t* dl = c.in(ploc, (size_t)np);
-  const int64_t* du = c.in(tile_uptr, (size_t)nt + 1);
-  const int32_t* dul = c.in(ulist, (size_t)tile_uptr[nt]);
-  const uint8_t* df = c.in(rowflag, (size_t)(3 * N2));
-  const float* ddv = c.in(dinv, (size_t)(4 * N2));
-  float* ddi = c.io(din, (size_t)(4 * N2));
-  float* ddo = c.io(dout, (size_t)(4 * N2));
-  float* dx = c.io(x, (size_t)(4 * N2));
-  float* dr = c.io(r, (size_t)(4 * N2));
+  const TiledSweepArgs a(c, tn, N2, nadj_ptr, tile_uptr, ulist, rowflag, dinv, din, dout, x, r);
   SHIM_RUN(c, "launch_sweep_tiled_f32",
-           launch_sweep_tiled_f32(c.st, nv, tn, N2, max_nu, dp, dv, dl, du, dul, df, ddv, c1, c2, ddi, ddo, dx, dr));
+           launch_sweep_tiled_f32(c.st, nv, tn, N2, max_nu, a.dp, dv, dl, a.du, a.dul, a.df, a.ddv, c1, c2, a.ddi, a.ddo, a.dx, a.dr));
 }
 // rec: the records of launch_pack_h1 (nv = 1: 1 word per pair) / launch_pack_h3 (nv = 3: 2 words per pair)
 int shim_sweep_tiled_h(int nv, int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const uint32_t* rec, const int64_t* tile_uptr,
                        const int32_t* ulist, const uint8_t* rowflag, const float* dinv, float c1, float c2, float* din, float* dout,
                        float* x, float* r) {
   Call c;
-  const int64_t np = nadj_ptr[N2], nt = tiles_of(N2, tn);
-  const int64_t* dp = c.in(nadj_ptr, (size_t)N2 + 1);
-  const uint32_t* drec = c.in(rec, (size_t)((nv == 1 ? 1 : 2) * np));
-  const int64_t* du = c.in(tile_uptr, (size_t)nt + 1);
-  const int32_t* dul = c.in(ulist, (size_t)tile_uptr[nt]);
-  const uint8_t* df = c.in(rowflag, (size_t)(3 * N2));
-  const float* ddv = c.in(dinv, (size_t)(4 * N2));
-  float* ddi = c.io(din, (size_t)(4 * N2));
-  float* ddo = c.io(dout, (size_t)(4 * N2));
-  float* dx = c.io(x, (size_t)(4 * N2));
-  float* dr = c.io(r, (size_t)(4 * N2));
+  const uint32_t* drec = c.in(rec, (size_t)((nv == 1 ? 1 : 2) * nadj_ptr[N2]));
+  const TiledSweepArgs a(c, tn, N2, nadj_ptr, tile_uptr, ulist, rowflag, dinv, din, dout, x, r);
   SHIM_RUN(c, "launch_sweep_tiled_h",
-           launch_sweep_tiled_h(c.st, nv, tn, N2, max_nu, dp, drec, du, dul, df, ddv, c1, c2, ddi, ddo, dx, dr));
+           launch_sweep_tiled_h(c.st, nv, tn, N2, max_nu, a.dp, drec, a.du, a.dul, a.df, a.ddv, c1, c2, a.ddi, a.ddo, a.dx, a.dr));
 }
 // rec: the records of launch_pack_f3 (4 words per pair)
 int shim_sweep_tiled_r3(int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const uint32_t* rec, const int64_t* tile_uptr,
                         const int32_t* ulist, const uint8_t* rowflag, const float* dinv, float c1, float c2, float* din, float* dout,
                         float* x, float* r) {
   Call c;
-  const int64_t np = nadj_ptr[N2], nt = tiles_of(N2, tn);
-  const int64_t* dp = c.in(nadj_ptr, (size_t)N2 + 1);
-  const uint32_t* drec = c.in(rec, (size_t)(4 * np));
-  const int64_t* du = c.in(tile_uptr, (size_t)nt + 1);
-  const int32_t* dul = c.in(ulist, (size_t)tile_uptr[nt]);
-  const uint8_t* df = c.in(rowflag, (size_t)(3 * N2));
-  const float* ddv = c.in(dinv, (size_t)(4 * N2));
-  float* ddi = c.io(din, (size_t)(4 * N2));
-  float* ddo = c.io(dout, (size_t)(4 * N2));
-  float* dx = c.io(x, (size_t)(4 * N2));
-  float* dr = c.io(r, (size_t)(4 * N2));
+  const uint32_t* drec = c.in(rec, (size_t)(4 * nadj_ptr[N2]));
+  const TiledSweepArgs a(c, tn, N2, nadj_ptr, tile_uptr, ulist, rowflag, dinv, din, dout, x, r);
   SHIM_RUN(c, "launch_sweep_tiled_r3",
-           launch_sweep_tiled_r3(c.st, tn, N2, max_nu, dp, drec, du, dul, df, ddv, c1, c2, ddi, ddo, dx, dr));
+           launch_sweep_tiled_r3(c.st, tn, N2, max_nu, a.dp, drec, a.du, a.dul, a.df, a.ddv, c1, c2, a.ddi, a.ddo, a.dx, a.dr));
 }
 // the one-ratio sweep (as shim_sweep_tiled_f32 with nv = 1) with two rows ahead in flight
 int shim_sweep_tiled_a1(int tn, int64_t N2, int max_nu, const int64_t* nadj_ptr, const float* vals, const uint16_t* ploc,
                         const int64_t* tile_uptr, const int32_t* ulist, const uint8_t* rowflag, const float* dinv, float c1, float c2,
                         float* din, float* dout, float* x, float* r) {
   Call c;
-  const int64_t np = nadj_ptr[N2], nt = tiles_of(N2, tn);
-  const int64_t* dp = c.in(nadj_ptr, (size_t)N2 + 1);
+  const int64_t np = nadj_ptr[N2];
   const float* dv = c.in(vals, (size_t)np);
   const uint16_t* dl = c.in(ploc, (size_t)np);
-  const int64_t* du = c.in(tile_uptr, (size_t)nt + 1);
-  const int32_t* dul = c.in(ulist, (size_t)tile_uptr[nt]);
-  const uint8_t* df = c.in(rowflag, (size_t)(3 * N2));
-  const float* ddv = c.in(dinv, (size_t)(4 * N2));
-  float* ddi = c.io(din, (size_t)(4 * N2));
-  float* ddo = c.io(dout, (size_t)(4 * N2));
-  float* dx = c.io(x, (size_t)(4 * N2));
-  float* dr = c.io(r, (size_t)(4 * N2));
+  const TiledSweepArgs a(c, tn, N2, nadj_ptr, tile_uptr, ulist, rowflag, dinv, din, dout, x, r);
   SHIM_RUN(c, "launch_sweep_tiled_a1",
-           launch_sweep_tiled_a1(c.st, tn, N2, max_nu, dp, dv, dl, du, dul, df, ddv, c1, c2, ddi, ddo, dx, dr));
+           launch_sweep_tiled_a1(c.st, tn, N2, max_nu, a.dp, dv, dl, a.du, a.dul, a.df, a.ddv, c1, c2, a.ddi, a.ddo, a.dx, a.dr));
 }
 // FP16 records.  h1: rec[e] = half(v[e]) | loc[e] << 16.  h3: rec[2e] = half(v[3e]) | half(v[3e+1]) << 16,
 // rec[2e+1] = half(v[3e+2]) | loc[e] << 16.  sb: per 3x3 block six words (a0 a1)(a2 a3)(a4 a5)(a6 a7)(a8 0)(column).
