@@ -3,7 +3,7 @@ of the kernel tests (tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels
 tests/test_gpu_coarse_kernels.py, tests/test_gpu_bcr_kernels.py, tests/test_gpu_block_kernels.py).
 
 The shim runs ONE ``fsi::launch_*`` call of libvaspfsi.so on host arrays; the builders restate, in numpy, what the library's
-host code hands those kernels: the LDS tiles of a graph (fsi_capi.hip, node tiles and Schur tiles), the FP16 records of
+host code hands those kernels: the LDS tiles of a graph (fsi_setup.hip build_tiles, node tiles and Schur tiles), the FP16 records of
 k_pack_h1 / k_pack_h3 / k_pack_sb, the monolithic matrix's column layout, padded FP32 copy and d-row pair form, and the P2 -> P1
 hierarchy of the two coarse levels with the contracts of their kernels, and the exact coarse solve by block cyclic reduction
 (fsi_bcr.hip: the reduction restated on a block-tridiagonal matrix, its blocked Gauss-Jordan inverse, synthetic tube graphs whose
@@ -171,11 +171,11 @@ def ctx_array(ctx, name: str) -> np.ndarray:
 
 # ---- reference builders ------------------------------------------------------------------------------------------------------
 TILE_LIMIT = 3584            # fsi_block.hip TILE_LIMIT: distinct neighbour nodes of a node tile (tile_limit(); checked on the GPU)
-SCHUR_TILE_LIMIT = 7000      # fsi_capi.hip: distinct columns of a Schur tile (56 KB of LDS as doubles)
+SCHUR_TILE_LIMIT = 7000      # fsi_setup.hip: distinct columns of a Schur tile (56 KB of LDS as doubles)
 
 
 def build_tiles(rowptr, cols, rows_per_tile, limit):
-    """Tiles of consecutive rows as fsi_capi.hip builds them: per tile the sorted distinct columns of its rows (ulist, tile t at
+    """Tiles of consecutive rows as fsi_setup.hip builds them: per tile the sorted distinct columns of its rows (ulist, tile t at
     uptr[t] .. uptr[t + 1]) and per entry the column's index in its tile's list (ploc).  Returns (uptr, ulist, ploc, max_nu), or
     None when a tile has more than `limit` distinct columns (the library then does not use the tiled kernels)."""
     n = len(rowptr) - 1
@@ -279,7 +279,7 @@ def local_graph(n, rng, reach=24, max_deg=40, diag_only=()):
     return rowptr, cols
 
 
-# ---- the monolithic matrix: structure, padded FP32 copy, d rows in pair form (fsi_solver.hip, fsi_capi.hip) ------------------
+# ---- the monolithic matrix: structure, padded FP32 copy, d rows in pair form (fsi_solver.hip, fsi_setup.hip) -----------------
 def mono_graph(N2, V, rng, reach=24, max_deg=12, heavy=(), heavy_deg=(), diag_only=(), no_padj=()):
     """A node graph as the monolithic layout reads it.  nadj_ptr / nadj: every node's neighbour ranks, ascending, itself included
     (up to max_deg random ones within `reach`; node heavy[k] gets heavy_deg[k] neighbours from anywhere; diag_only nodes itself
@@ -340,7 +340,7 @@ def expand_cols(N2, nadj_ptr, nadj, padj_ptr, padj, vrank):
 
 
 def pad_layout(N2, rowptr):
-    """The FP32 copy's layout (fsi_capi.hip): node r's six value rows padded to Lp = L rounded up to a multiple of 4, block at
+    """The FP32 copy's layout (fsi_setup.hip): node r's six value rows padded to Lp = L rounded up to a multiple of 4, block at
     p32[r] (entries), index row at p32[r] / 6; the pressure rows unpadded behind, at ptail.  Returns (p32, ptail, tail_src,
     nnz_tail)."""
     L = rowptr[6 * np.arange(N2) + 1] - rowptr[6 * np.arange(N2)]
@@ -421,7 +421,7 @@ def csr_product(rowptr, cols, vals, x):
     return y.astype(np.float64), S.astype(np.float64), L.astype(np.float64)
 
 
-# ---- the two-level coarse levels (fsi_capi.hip hierarchy builder; fsi_block.hip k_mg_* / k_sbmg_*) and the diagonal scalings --
+# ---- the two-level coarse levels (fsi_setup.hip build_hierarchy; fsi_block.hip k_mg_* / k_sbmg_*) and the diagonal scalings --
 U32 = 2.0 ** -24
 UFC_EDGES = ((2, 3), (1, 3), (1, 2), (0, 3), (0, 2), (0, 1))      # local edge e of a P2 tet joins these local vertices
 
@@ -460,7 +460,7 @@ def _vertex_pairs(tet_nodes):
 
 
 def p1_hierarchy(tet_nodes, V, rank2node, snode=None):
-    """The P2 -> P1 hierarchy fsi_capi.hip builds, restated.  tet_nodes: [cells][10] in the library's cell order, rank2node: node
+    """The P2 -> P1 hierarchy fsi_setup.hip builds, restated.  tet_nodes: [cells][10] in the library's cell order, rank2node: node
     of every solver rank (node = solver2user[6 r] // 3).  Displacement level (snode None): coarse node i = the i-th vertex in rank
     order (cfine[i] its rank); par / pw [N2][2]: a vertex its own coarse node with weights (1, 0), a midpoint its edge's two ends
     (edge_ends) with (1/2, 1/2); chptr / child / chw their transpose in fine-rank order; cptr / ccol: the vertices that share a

@@ -7,7 +7,7 @@ FP32 copies are used as the float32 values themselves, FP16 records as the test'
 the library packs the same bits).  With exact inputs the bound is the accumulation rounding alone: (row length + 8) u sum |a_ij d_j|
 per row, u = 2^-24 for FP32 accumulation, eps64 for FP64 - a dropped, doubled or misplaced entry misses it by orders of magnitude.
 
-a) synthetic operators (graphs, values and tiles built in numpy as fsi_capi.hip builds them), b) live contexts on two meshes: their
+a) synthetic operators (graphs, values and tiles built in numpy as fsi_setup.hip builds them), b) live contexts on two meshes: their
 records and tiles, their FP64 operators against a scipy restatement from the assembled Jacobian (displacement pairs, solid
 blocks, the Schur complement on its full pattern), and one sweep of each record kernel on the context's own structure."""
 import numpy as np
@@ -509,6 +509,36 @@ def test_live_context_records_and_tiles(live_ctx):
     # which variants the context runs: tiled sweeps fused with the update (bit 0) on FP16 records (bit 1)
     flags = hb.timers()["sweep_flags"]
     assert flags & 1 and flags & 2, f"sweep_flags {flags:#x}: the pinned tuning should run the fused FP16-record sweeps"
+
+
+@pytest.mark.parametrize("tiles, tile_nodes, schur_tile", [(1, 128, 32), (1, 256, 256), (0, 256, 64)])
+def test_live_context_tiles_at_every_tile_size(stenosis_case, tiles, tile_nodes, schur_tile):
+    """The node tiles and the Schur tiles of a fresh context (fsi_setup.hip builds both with one function) are ks.build_tiles on
+    the context's own graphs, entry for entry, at the other sizes FsiTuning offers; with tiles = 0 there are no node tiles."""
+    from vasp_amd.capi import HipBackend
+    hb = HipBackend(stenosis_case[1], tuning=dict(tiles=tiles, tile_nodes=tile_nodes, schur_tile_rows=schur_tile))
+    try:
+        info = ks.ctx_info(hb.ctx)
+        A = lambda name: ks.ctx_array(hb.ctx, name)      # noqa: E731
+        assert info["tile_nodes"] == tile_nodes and info["schur_tile"] == schur_tile, info
+        if tiles:
+            uptr, ulist, ploc, max_nu = ks.build_tiles(A("nadj_ptr"), A("nadj"), tile_nodes, ks.TILE_LIMIT)
+            assert info["tiled"] == 1
+            np.testing.assert_array_equal(A("tile_uptr"), uptr)
+            np.testing.assert_array_equal(A("tile_ulist"), ulist)
+            np.testing.assert_array_equal(A("tile_ploc"), ploc)
+            assert info["tile_max_nu"] == max_nu
+        else:
+            assert info["tiled"] == 0 and info["tile_max_nu"] == 0
+            assert len(A("tile_uptr")) == 0 and len(A("tile_ulist")) == 0 and len(A("tile_ploc")) == 0
+        suptr, sulist, sploc, smax = ks.build_tiles(A("s_rowptr"), A("s_cols"), schur_tile, ks.SCHUR_TILE_LIMIT)
+        assert info["schur_tiled"] == 1
+        np.testing.assert_array_equal(A("s_tile_uptr"), suptr)
+        np.testing.assert_array_equal(A("s_tile_ulist"), sulist)
+        np.testing.assert_array_equal(A("s_ploc"), sploc)
+        assert info["s_tile_max_nu"] == smax
+    finally:
+        hb.close()
 
 
 def test_live_context_operators_are_the_jacobian_blocks(live_ctx):

@@ -122,7 +122,7 @@ def test_monolithic_graph_reaches_the_edges():
 
 @pytest.mark.parametrize("N2,V,kw", MONO_CASES)
 def test_padded_layout_covers_every_entry_once(N2, V, kw):
-    """pad_copy against a loop over nodes as fsi_capi.hip / k_pad_*32 state it; every entry of A lands once, padding is value 0
+    """pad_copy against a loop over nodes as fsi_setup.hip / k_pad_*32 state it; every entry of A lands once, padding is value 0
     and column 0, the pressure rows follow unpadded; all four L mod 4 are met over the cases"""
     rng, g, (rowptr, cols, diagpos) = small_mono(N2, V, N2 + V + 1, **kw)
     nnz = int(rowptr[-1])

@@ -280,11 +280,7 @@ namespace host {
 
 void bcr_free(FsiCtx* ctx) {
   if (!ctx->bcr) return;
-  BcrData* d = ctx->bcr;
-  d->pos.release(); d->fill_dst.release(); d->fill_ld.release(); d->arena64.release(); d->b.release(); d->x.release();
-  d->arena32.release(); d->tasks.release(); d->tiles.release(); d->gemms.release(); d->gtiles.release(); d->invs.release();
-  d->flag.release();
-  delete d;
+  delete ctx->bcr;
   ctx->bcr = nullptr;
 }
 

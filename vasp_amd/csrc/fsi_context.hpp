@@ -19,9 +19,11 @@ constexpr int NLOC = 64;      // local dofs per tet: 30 (d) + 30 (v) + 4 (p)
 constexpr int MAX_REGIONS = 8;
 
 template <class T>
-struct DevBuf {
+struct DevBuf {      // owns its device memory: freed with the buffer, never copied
   T* p = nullptr;
   size_t n = 0;
+  DevBuf() = default; DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   hipError_t alloc(size_t count) {
     release();
     n = count;
@@ -70,6 +72,7 @@ struct PhaseTimer {
 }  // namespace fsi
 
 struct FsiCtx {
+  ~FsiCtx();      // fsi_setup.hip.  The context's device must be current when it runs: the buffers below free themselves on it.
   FsiTuning tune{};                          // what the context was created with (fsi_create_tuned); the fields below are set from it
   int device = 0;
   hipStream_t stream = nullptr;
@@ -234,8 +237,6 @@ struct FsiCtx {
   int solid_mg = 1;
   bool sbmg_ready = false;
   int64_t sbmg_nc = 0, sbmg_nblk = 0;
-  std::vector<int32_t> h_snode, h_sb_col;    // host copies for the hierarchy set-up
-  std::vector<int64_t> h_sb_ptr;
   fsi::DevBuf<int32_t> sbmg_par, sbmg_ccol, sbmg_child, sbmg_cfine;
   fsi::DevBuf<float> sbmg_pw, sbmg_chw, sbmg_cvals, sbmg_cbinv12, sbmg_work;
   fsi::DevBuf<int64_t> sbmg_cptr, sbmg_chptr;

@@ -1,5 +1,6 @@
 // Host side of libvaspfsi.so: what the translation units behind the C-ABI share.
-//   fsi_capi.hip     the ABI itself: context set-up (fsi_create), boundary data, partition, state access, timers
+//   fsi_capi.hip     the ABI itself: boundary data, partition, state access, products, probes, timers
+//   fsi_setup.hip    fsi_create / fsi_create_tuned as a sequence of stages, fsi_destroy and the context's destructor
 //   fsi_newton.hip   fsi_assemble_residual / _jacobian, fsi_solve, fsi_newton_solve (turtleFSI's newtonsolver policy)
 //   fsi_krylov.hip   recycled GCR (solve_gcr), BiCGStab, the monolithic product
 //   fsi_sessions.hip the post-processing sessions of a run: fsi_hemo_* / fsi_stress_* / fsi_band_* / fsi_spec_*

@@ -1034,9 +1034,6 @@ int shim_bcr_run(int64_t nc, const int64_t* cptr, const int32_t* ccol, int nsets
   }
   if (drc) (void)hipFree(drc);
   if (dxc) (void)hipFree(dxc);
-  host::bcr_free(ctx);
-  ctx->sbmg_cvals.release();
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   const std::string err = ctx->err;
   delete ctx;
   if (e != hipSuccess) { g_err = std::string("shim_bcr_run: ") + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")"; return 1; }
