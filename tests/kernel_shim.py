@@ -1,13 +1,16 @@
 """ctypes loader of ``vasp_amd/libfsi_kernel_shim.so`` (vasp_amd/csrc/fsi_kernel_shim.hip) and the host-side reference builders
 of the kernel tests (tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py, tests/test_gpu_product_kernels.py,
-tests/test_gpu_coarse_kernels.py, tests/test_gpu_bcr_kernels.py, tests/test_gpu_block_kernels.py).
+tests/test_gpu_coarse_kernels.py, tests/test_gpu_bcr_kernels.py, tests/test_gpu_block_kernels.py, tests/test_gpu_ilu_kernels.py,
+tests/test_gpu_vector_kernels.py).
 
 The shim runs ONE ``fsi::launch_*`` call of libvaspfsi.so on host arrays; the builders restate, in numpy, what the library's
 host code hands those kernels: the LDS tiles of a graph (fsi_setup.hip build_tiles, node tiles and Schur tiles), the FP16 records of
 k_pack_h1 / k_pack_h3 / k_pack_sb, the monolithic matrix's column layout, padded FP32 copy and d-row pair form, and the P2 -> P1
 hierarchy of the two coarse levels with the contracts of their kernels, and the exact coarse solve by block cyclic reduction
 (fsi_bcr.hip: the reduction restated on a block-tridiagonal matrix, its blocked Gauss-Jordan inverse, synthetic tube graphs whose
-breadth-first levels are known).  The builders are tested on the CPU (tests/test_kernel_references.py), so that a failure
+breadth-first levels are known), and for the multicolour ILU(0) path matrices that obey the contract of its level kernels, the
+definition of ILU(0) as a check of a given factor and the triangular solves' own equations, each with its rounding bound.  The
+builders are tested on the CPU (tests/test_kernel_references.py), so that a failure
 of a GPU test is one of the kernel, not of its reference."""
 from __future__ import annotations
 
@@ -53,6 +56,12 @@ _SIGS = {
     "shim_residual_csr": "lpppplpp", "shim_residual_rows": "lppppplplppl", "shim_split": "llpppp", "shim_merge": "llpppp",
     "shim_merge_f32d": "llpppp", "shim_pad_init_f32": "lpppfppp", "shim_pad_to_f32": "lppp", "shim_unpad_from_f32": "lpp",
     "shim_mask_ripple": "lpp", "shim_mask_scale": "lppplp",
+    "shim_ilu0": "lipppppppp", "shim_sptrsv": "lipppppppppp", "shim_ctx_levels": "ppi",
+    "shim_fill": "ldp", "shim_copy": "lpp", "shim_axpy": "ldpp", "shim_axpby": "ldpdpp", "shim_scale": "ldp", "shim_mul": "lppp",
+    "shim_div": "lppp", "shim_negate": "lpp", "shim_gather": "lplpp", "shim_scatter": "lpppl", "shim_gather3": "llppp",
+    "shim_scatter3": "llppp", "shim_round_to_f32": "lpp", "shim_add_indexed": "lppdpl", "shim_add_at": "lppdpl",
+    "shim_bc_rhs": "lppppl", "shim_bc_set": "lpppl", "shim_robin_residual": "lppppddpppl", "shim_f32_ripple4": "lp",
+    "shim_f32_sumsq": "lpp",
 }
 LAUNCH_REFUSED = 2           # fsi_kernels.hpp: a launch function refused its arguments and launched nothing
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "d": C.c_double, "s": C.c_char_p}
@@ -122,7 +131,7 @@ _UNSIGNED = {"dd_rec", "vv_rec", "sb_rec", "s_rec"}
 _FLOAT = {"dd_chat", "vv_db32", "sb_vals", "sb_binv12", "s_vals", "s_vals32", "s_dinv", "dd_db", "rowscale", "A", "A32", "Ad64", "Ad32",
           "mg_pw", "mg_chw", "mg_Ac", "mg_cc", "mg_d0", "mg_dcinv4", "sbmg_pw", "sbmg_chw", "sbmg_cvals", "sbmg_cbinv12",
           "sb_binv9", "sb_dinv", "dd_dinv32", "vvf_dinv32", "Mdd.vals", "Mvv.vals", "Adv", "Avp", "Apv", "App", "Avp32", "Apv32",
-          "vv_db", "adv_db", "dd_db32", "vv_dinv", "mask_f", "mask_s", "ss_vals"}
+          "vv_db", "adv_db", "dd_db32", "vv_dinv", "mask_f", "mask_s", "ss_vals", "LU"}
 
 
 def ctx_info(ctx) -> dict:
@@ -1334,3 +1343,274 @@ def live_blocks(hb):
                 Avv_t=(M[Vd][:, Vd] + M[Vd][:, Dd] @ K).tocsr(), Avv_mag=(abs(M[Vd][:, Vd]) + abs(M[Vd][:, Dd]) @ K).tocsr(),
                 Apv_t=(M[Pd][:, Vd] + M[Pd][:, Dd] @ K).tocsr(), Apv_mag=(abs(M[Pd][:, Vd]) + abs(M[Pd][:, Dd]) @ K).tocsr(),
                 App=M[Pd][:, Pd].tocsr(), Avp=M[Vd][:, Pd].tocsr())
+
+
+# ---- multicolour ILU(0) and its triangular solves (fsi_solver.hip k_ilu0_level / k_sptrsv_level; tests/test_gpu_ilu_kernels.py) --
+# Nothing below repeats the kernels' arithmetic: the factor is held to the DEFINITION of ILU(0), (L U)_ij = a_ij on the pattern,
+# and the solves to their own equations row by row, each with the rounding bound of the operation count involved.
+ILU_MAXROW = 1024            # fsi_solver.hip MAXROW: entries of a row the factorisation's LDS tile holds
+
+
+def level_layout(levels):
+    """levels: [(ngroups, group_rows)], numbered in order.  Returns (n, first, ngroups, group_rows, level_of, group_of) with
+    group_of a number that is distinct for every group of the matrix."""
+    ng = np.array([l[0] for l in levels], dtype=np.int64)
+    gr = np.array([l[1] for l in levels], dtype=np.int32)
+    rows = ng * gr
+    first = np.concatenate([[0], np.cumsum(rows)[:-1]]).astype(np.int64) if len(levels) else np.zeros(0, dtype=np.int64)
+    n = int(rows.sum())
+    level_of = np.repeat(np.arange(len(levels)), rows)
+    gfirst = np.concatenate([[0], np.cumsum(ng)[:-1]]) if len(levels) else np.zeros(0, dtype=np.int64)
+    within = np.arange(n) - first[level_of]
+    group_of = gfirst[level_of] + within // np.maximum(gr[level_of], 1)
+    return n, first, ng, gr, level_of, group_of
+
+
+def level_violations(levels, rowptr, cols):
+    """The contract of the level kernels: entries (i, j) with i and j in the same level but in different groups (there must be none)"""
+    n, _, _, _, level_of, group_of = level_layout(levels)
+    assert n == len(rowptr) - 1
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    return int(np.count_nonzero((level_of[row] == level_of[cols]) & (group_of[row] != group_of[cols])))
+
+
+def level_matrix(levels, rng, symmetric=True, row_len=30, couple_group=True, own_group_only=False, heavy=(), heavy_len=(),
+                 diag_first=(), diag_last=(), isolated=(), zero_lower=0.0, dominance=1.25):
+    """A CSR matrix that obeys the contract of k_ilu0_level / k_sptrsv_level on `levels` = [(ngroups, group_rows)]: a row may
+    reference any row of another level and any row of its own group (below and above itself), never another group of its own
+    level.  Columns ascending, a diagonal entry in every row.
+      row_len        about this many entries per row: the own group (with couple_group) and rows of other levels drawn at random
+      couple_group   every row holds all rows of its own group (a node's d / v rows)
+      own_group_only nothing but the own group: the matrix is block diagonal and ILU(0) is the exact LU of every block
+      symmetric      the pattern is made symmetric (the contract is symmetric, so it survives)
+      heavy, heavy_len   rows with exactly that many entries (1 = the diagonal alone); a row in diag_first / diag_last has the
+                     diagonal as its first / last entry.  These rows are set after the symmetrisation.
+      isolated       rows no other row references (their column is removed everywhere else)
+      zero_lower     this fraction of the strictly lower entries is exactly 0.0
+      dominance      |a_ii| = dominance * sum_j |a_ij|: strictly diagonally dominant by rows, so every pivot stays away from zero
+    Returns a dict: n, the level arrays first / ngroups / group_rows, rowptr, cols, diagpos, vals."""
+    n, first, ng, gr, level_of, group_of = level_layout(levels)
+    heavy = [int(r) for r in heavy]
+    special = set(heavy)
+    # the entries outside the own group are drawn among the rows of the OTHER levels (none if there is no other level)
+    own = (ng * gr)[level_of] if n else np.zeros(0, dtype=np.int64)
+    k = np.maximum(row_len - 1 - (gr[level_of] - 1 if couple_group else 0), 0) if n else np.zeros(0, dtype=np.int64)
+    k = np.where(own_group_only | (own == n), 0, (k + 1) // 2 if symmetric else k)
+    i = np.repeat(np.arange(n, dtype=np.int64), k)
+    u = rng.integers(0, np.maximum(n - own[i], 1))
+    j = np.where(u < first[level_of[i]], u, u + own[i])
+    if not symmetric:          # a one-sided band besides the random entries, so that the two triangles differ in size too
+        extra = np.arange(n, dtype=np.int64)
+        i, j = np.concatenate([i, extra, extra]), np.concatenate([j, (extra * 7 + 3) % max(n, 1), (extra * 13 + 5) % max(n, 1)])
+    if couple_group or own_group_only:
+        gstart = first[level_of] + ((np.arange(n) - first[level_of]) // gr[level_of]) * gr[level_of]
+        for t in range(int(gr.max()) if len(gr) else 0):
+            ok = t < gr[level_of]
+            i, j = np.concatenate([i, np.arange(n)[ok]]), np.concatenate([j, (gstart + t)[ok]])
+    if symmetric:
+        i, j = np.concatenate([i, j]), np.concatenate([j, i])
+    i, j = np.concatenate([i, np.arange(n)]), np.concatenate([j, np.arange(n)])
+    keep = (level_of[i] != level_of[j]) | (group_of[i] == group_of[j])
+    keep &= ~np.isin(i, np.asarray(heavy, dtype=np.int64))
+    keep &= ~(np.isin(j, np.asarray(list(isolated), dtype=np.int64)) & (i != j))
+    i, j = i[keep], j[keep]
+    for r, L in zip(heavy, heavy_len):
+        allowed = np.flatnonzero(((level_of != level_of[r]) | (group_of == group_of[r])) & (np.arange(n) != r)
+                                 & ~np.isin(np.arange(n), np.asarray(list(isolated), dtype=np.int64)))
+        if r in diag_first:
+            allowed = allowed[allowed > r]
+        if r in diag_last:
+            allowed = allowed[allowed < r]
+        assert len(allowed) >= L - 1, f"row {r}: only {len(allowed)} columns allowed, {L - 1} wanted"
+        pick = rng.choice(allowed, size=L - 1, replace=False)
+        i, j = np.concatenate([i, np.full(L, r)]), np.concatenate([j, pick, [r]])
+    code = np.unique(i * n + j)
+    i, j = code // max(n, 1), code % max(n, 1)
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(i, minlength=n))]).astype(np.int64)
+    cols = j.astype(np.int32)
+    diagpos = np.flatnonzero(i == j).astype(np.int64)
+    assert len(diagpos) == n
+    vals = rng.uniform(-1.0, 1.0, len(cols))
+    lower = np.flatnonzero(j < i)
+    if zero_lower > 0 and len(lower):
+        vals[lower[rng.random(len(lower)) < zero_lower]] = 0.0
+    vals[diagpos] = 0.0
+    off = np.zeros(n)
+    np.add.at(off, i, np.abs(vals))
+    vals[diagpos] = np.where(rng.random(n) < 0.5, -1.0, 1.0) * (dominance * off + 1.0)
+    for r in special | set(int(r) for r in diag_first) | set(int(r) for r in diag_last):
+        if r in diag_first:
+            assert diagpos[r] == rowptr[r]
+        if r in diag_last:
+            assert diagpos[r] == rowptr[r + 1] - 1
+    return dict(n=n, first=first, ngroups=ng, group_rows=gr, rowptr=rowptr, cols=cols, diagpos=diagpos, vals=vals,
+                level_of=level_of, group_of=group_of)
+
+
+def ilu0_ikj(rowptr, cols, diagpos, vals, group_of=None, fault=None):
+    """ILU(0) restated in plain FP64, row by row in the IKJ order: for every lower entry (i, k) in column order l = a_ik / u_kk,
+    then a_ij -= l u_kj at every j > k that row i holds.  fault (negative controls of the identity check, each applied once, at the
+    first place it can be): "drop_update" skips one update, "neighbour_column" applies one update to the entry next to the matching
+    one, "stale_pivot" divides by the UNFACTORED diagonal of a row of the same group (what a wave would read if it did not wait
+    for its own stores; group_of is needed for it).  Returns (LU, whether the fault was applied)."""
+    n = len(rowptr) - 1
+    LU = np.array(vals, dtype=np.float64)
+    done = fault is None
+    for i in range(n):
+        s, e, d = int(rowptr[i]), int(rowptr[i + 1]), int(diagpos[i])
+        where = {int(c): s + t for t, c in enumerate(cols[s:e])}
+        for t in range(s, d):
+            k = int(cols[t])
+            piv = LU[diagpos[k]]
+            if fault == "stale_pivot" and not done and group_of[k] == group_of[i] and vals[diagpos[k]] != piv:
+                piv, done = vals[diagpos[k]], True
+            l = LU[t] / piv
+            LU[t] = l
+            for q in range(int(diagpos[k]) + 1, int(rowptr[k + 1])):
+                p = where.get(int(cols[q]))
+                if p is None:
+                    continue
+                if not done and fault == "drop_update" and LU[q] != 0.0 and l != 0.0:
+                    done = True
+                    continue
+                if not done and fault == "neighbour_column" and p + 1 < e and LU[q] != 0.0 and l != 0.0:
+                    p, done = p + 1, True
+                LU[p] -= l * LU[q]
+    return LU, done
+
+
+def ilu0_identity(rowptr, cols, diagpos, A, LU):
+    """The definition of ILU(0) as a check of a given factor, in extended precision, row by row.  For every pattern entry (i, j):
+    s_ij = sum over k < min(i, j) with (i, k) and (k, j) in the pattern of l_ik u_kj, plus u_ij (j >= i) or l_ij u_jj (j < i);
+    S_ij the same sum over absolute values plus |a_ij|; n_ij the number of terms.  Returns (err, bound) per entry with
+    err = |a_ij - s_ij| and bound = (n_ij + 2) eps S_ij: the componentwise backward error of Doolittle elimination
+    (Higham, Accuracy and Stability of Numerical Algorithms, theorem 9.3: |A - LU| <= gamma_n |L||U|) restricted to the pattern;
+    it holds for any order of the updates and with or without contraction into FMAs."""
+    ld = np.longdouble
+    n = len(rowptr) - 1
+    lu, a = np.asarray(LU, dtype=ld), np.asarray(A, dtype=ld)
+    err, bound = np.zeros(len(cols), dtype=ld), np.zeros(len(cols), dtype=ld)
+    for i in range(n):
+        s, e, d = int(rowptr[i]), int(rowptr[i + 1]), int(diagpos[i])
+        ci = cols[s:e]
+        acc, mag, cnt = np.zeros(e - s, dtype=ld), np.zeros(e - s, dtype=ld), np.ones(e - s, dtype=np.int64)
+        for t in range(s, d):
+            k = int(cols[t])
+            us, ue = int(diagpos[k]) + 1, int(rowptr[k + 1])
+            pos = np.searchsorted(ci, cols[us:ue])
+            hit = pos < len(ci)
+            hit[hit] = ci[pos[hit]] == cols[us:ue][hit]
+            p = lu[t] * lu[us:ue][hit]
+            acc[pos[hit]] += p                     # the columns of a row are distinct: no index repeats
+            mag[pos[hit]] += np.abs(p)
+            cnt[pos[hit]] += 1
+        last = np.concatenate([lu[s:d] * lu[diagpos[cols[s:d]]], lu[d:e]])
+        acc += last
+        mag += np.abs(last)
+        err[s:e] = np.abs(a[s:e] - acc)
+        bound[s:e] = (cnt + 2) * ld(EPS64) * (mag + np.abs(a[s:e]))
+    return err, bound
+
+
+def _triangles(rowptr, cols, diagpos, LU):
+    import scipy.sparse as sp
+    n = len(rowptr) - 1
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    low = cols < row
+    # (the unit diagonal goes in with the entries: a sum of two sparse matrices would drop the factor's explicit zeros)
+    d = np.arange(n)
+    L = sp.csr_matrix((np.concatenate([np.asarray(LU, dtype=np.float64)[low], np.ones(n)]),
+                       (np.concatenate([row[low], d]), np.concatenate([cols[low], d]))), shape=(n, n))
+    U = sp.csr_matrix((np.asarray(LU, dtype=np.float64)[~low], (row[~low], cols[~low])), shape=(n, n))
+    return row, L, U
+
+
+def _sample(M, row, cols):
+    """the entries of the sparse matrix M at the positions (row, cols), zero where M holds none"""
+    M = M.tocsr()
+    M.sort_indices()
+    n = M.shape[1]
+    mrow = np.repeat(np.arange(M.shape[0]), np.diff(M.indptr))
+    key = mrow.astype(np.int64) * n + M.indices
+    want = row.astype(np.int64) * n + cols
+    p = np.searchsorted(key, want)
+    ok = p < len(key)
+    ok[ok] = key[p[ok]] == want[ok]
+    out = np.zeros(len(want), dtype=M.dtype)
+    out[ok] = M.data[p[ok]]
+    return out
+
+
+def ilu0_identity_f64(rowptr, cols, diagpos, A, LU):
+    """ilu0_identity through scipy's FP64 sparse products, for matrices too large for the row loops: (L U), (|L| |U|) and the term
+    counts sampled on the pattern.  The sums are formed in FP64 here, so the check's own rounding is of the size of the bound:
+    callers hold err to TWICE the bound returned."""
+    row, L, U = _triangles(rowptr, cols, diagpos, LU)
+    s = _sample(L @ U, row, cols)
+    S = _sample(abs(L) @ abs(U), row, cols) + np.abs(A)
+    Lp, Up = L.copy(), U.copy()
+    Lp.data[:] = 1.0
+    Up.data[:] = 1.0
+    cnt = _sample(Lp @ Up, row, cols)               # explicit zeros of the factor count as terms, as in ilu0_identity
+    return np.abs(np.asarray(A) - s), (cnt + 2) * EPS64 * S
+
+
+def _row_sums(rowptr, p):
+    """the sums of p over the rows of a CSR structure (zero for an empty row)"""
+    out = np.zeros(len(rowptr) - 1, dtype=p.dtype)
+    nz = np.diff(rowptr) > 0
+    if len(p):
+        out[nz] = np.add.reduceat(p, rowptr[:-1][nz])
+    return out
+
+
+def sptrsv_residuals(rowptr, cols, diagpos, LU, rhs, y, x):
+    """The two triangular solves held to their own equations, row by row in extended precision; the bounds hold for any order of
+    a row's sum.  Forward (unit lower): |rhs_i - y_i - sum_{j<i} l_ij y_j| <= (L_i + 2) eps (|rhs_i| + |y_i| + sum |l_ij y_j|);
+    backward: |y_i - sum_{j>=i} u_ij x_j| <= (U_i + 3) eps (|y_i| + sum |u_ij x_j|), L_i / U_i the entries of the two parts of
+    row i.  Returns (err_forward, bound_forward, err_backward, bound_backward)."""
+    ld = np.longdouble
+    n = len(rowptr) - 1
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    low = cols < row
+    lu, yl, xl, rl = (np.asarray(v, dtype=ld) for v in (LU, y, x, rhs))
+    pl = np.where(low, lu * yl[cols], ld(0))
+    pu = np.where(~low, lu * xl[cols], ld(0))
+    nl = _row_sums(rowptr, low.astype(np.int64))
+    nu = np.diff(rowptr) - nl
+    ef = np.abs(rl - yl - _row_sums(rowptr, pl))
+    bf = (nl + 2) * ld(EPS64) * (np.abs(rl) + np.abs(yl) + _row_sums(rowptr, np.abs(pl)))
+    eb = np.abs(yl - _row_sums(rowptr, pu))
+    bb = (nu + 3) * ld(EPS64) * (np.abs(yl) + _row_sums(rowptr, np.abs(pu)))
+    return ef, bf, eb, bb
+
+
+def worst_ratio(err, bound):
+    """max err / bound (an error where the bound is zero counts as inf, NaN as inf)"""
+    err, bound = np.asarray(err, dtype=np.longdouble).ravel(), np.asarray(bound, dtype=np.longdouble).ravel()
+    if len(err) == 0:
+        return 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(err == 0, 0, err / bound)
+    r = np.where(np.isnan(r), np.inf, r)
+    return float(r.max())
+
+
+def ctx_levels(ctx):
+    """[(first_row, ngroups, group_rows)] of a live context's multicolour ordering"""
+    lib = load()
+    k = lib.shim_ctx_levels(ctx, None, 0)
+    out = np.zeros(3 * max(k, 1), dtype=np.int64)
+    lib.shim_ctx_levels(ctx, _arg(out), k)
+    return [tuple(int(v) for v in out[3 * i:3 * i + 3]) for i in range(k)]
+
+
+def f32_ripple4(nnodes):
+    """k_f32_ripple4 restated with numpy integers: node i gets h = low 32 bits of (i * 2654435761) xor low 32 bits of (i >> 7),
+    and the float4 (h & 1023, (h >> 10) & 1023, (h >> 20) & 1023) / 512 - 1 with a zero fourth lane (all exact in FP32)"""
+    i = np.arange(nnodes, dtype=np.uint64)
+    h = ((i * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)).astype(np.uint32) ^ ((i >> np.uint64(7)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    out = np.zeros((nnodes, 4), dtype=np.float32)
+    for c, sh in enumerate((0, 10, 20)):
+        out[:, c] = ((h >> np.uint32(sh)) & np.uint32(1023)).astype(np.float32) / np.float32(512.0) - np.float32(1.0)
+    return out.reshape(-1)

@@ -1,6 +1,7 @@
 """CPU self-tests of the host-side references the kernel tests build on (tests/kernel_shim.py), so that a failure of
 tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py, tests/test_gpu_product_kernels.py,
-tests/test_gpu_coarse_kernels.py or tests/test_gpu_bcr_kernels.py is one of a kernel, not of its reference."""
+tests/test_gpu_coarse_kernels.py, tests/test_gpu_bcr_kernels.py or tests/test_gpu_ilu_kernels.py is one of a kernel, not of its
+reference."""
 import numpy as np
 import pytest
 
@@ -726,3 +727,137 @@ def test_the_block_cases_reach_the_edges():
     assert np.all(deg[tb.blocks_case("N700_V300", "heavy")["solid"] != 0] >= 47)
     b = tb.blocks_case("N700_V300")["b"]
     assert (b["Apv"] == 0).any() and np.signbit(b["Avp"][b["Avp"] == 0]).any()
+
+
+# ---- multicolour ILU(0) and its triangular solves (tests/test_gpu_ilu_kernels.py) ---------------------------------------------
+ILU_MIXED = [(40, 6), (33, 6), (1, 6), (0, 6), (25, 1), (17, 1)]
+
+
+@pytest.mark.parametrize("symmetric", [True, False])
+def test_level_matrix_obeys_the_level_contract(symmetric):
+    m = ks.level_matrix(ILU_MIXED, np.random.default_rng(3), symmetric=symmetric, zero_lower=0.1)
+    n, rowptr, cols, diagpos, vals = m["n"], m["rowptr"], m["cols"], m["diagpos"], m["vals"]
+    assert n == 6 * 74 + 42 and len(rowptr) == n + 1
+    assert ks.level_violations(ILU_MIXED, rowptr, cols) == 0
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    assert np.all((np.diff(cols) > 0) | (np.diff(row) > 0))                  # ascending, distinct columns in every row
+    np.testing.assert_array_equal(cols[diagpos], np.arange(n))              # a diagonal entry in every row
+    assert 20 <= np.diff(rowptr).mean() <= 70
+    off = np.zeros(n)
+    np.add.at(off, row, np.abs(vals))
+    off -= np.abs(vals[diagpos])
+    assert np.all(np.abs(vals[diagpos]) > off)                              # strictly dominant by rows
+    assert np.count_nonzero(vals[cols < row] == 0.0) > 10                    # exactly zero lower entries
+    # rows reference their own group below AND above themselves, and other levels
+    g = m["group_of"]
+    same = g[row] == g[cols]
+    assert np.any(same & (cols > row)) and np.any(same & (cols < row)) and np.any(~same)
+    import scipy.sparse as sp
+    P = sp.csr_matrix((np.ones(len(cols)), cols, rowptr), shape=(n, n))
+    assert ((P != P.T).nnz == 0) == symmetric
+    # a violation is seen
+    bad = cols.copy()
+    r = int(m["first"][0]) + 2                                               # row 2 of group 0 of level 0 -> a column of group 1
+    bad[rowptr[r]] = 6
+    assert ks.level_violations(ILU_MIXED, rowptr, bad) == 1
+
+
+def test_level_matrix_row_lengths_and_diagonal_positions():
+    levels = [(40, 6), (200, 6), (30, 1), (20, 1)]
+    n = 40 * 6 + 200 * 6 + 50
+    heavy = [3, n - 5, 250, 251, 252, 253, 1447, 1460]
+    m = ks.level_matrix(levels, np.random.default_rng(5), heavy=heavy, heavy_len=[1024, 1024, 1, 63, 64, 65, 129, 1025],
+                        diag_first=[3], diag_last=[n - 5], isolated=[1460])
+    L = np.diff(m["rowptr"])
+    assert [int(L[r]) for r in heavy] == [1024, 1024, 1, 63, 64, 65, 129, 1025]
+    assert m["diagpos"][3] == m["rowptr"][3] and m["diagpos"][n - 5] == m["rowptr"][n - 4] - 1
+    assert ks.level_violations(levels, m["rowptr"], m["cols"]) == 0
+    row = np.repeat(np.arange(n), L)
+    assert np.count_nonzero((m["cols"] == 1460) & (row != 1460)) == 0        # no other row depends on the isolated one
+    assert L[np.setdiff1d(np.arange(n), heavy)].max() <= ks.ILU_MAXROW
+
+
+def test_own_group_only_matrix_is_block_diagonal_and_well_conditioned():
+    m = ks.level_matrix([(7, 6), (3, 1), (5, 6)], np.random.default_rng(8), own_group_only=True)
+    import scipy.sparse as sp
+    A = sp.csr_matrix((m["vals"], m["cols"], m["rowptr"]), shape=(m["n"],) * 2).toarray()
+    g = m["group_of"]
+    assert np.all(A[g[:, None] != g[None, :]] == 0.0)
+    for k in np.unique(g):
+        B = A[np.ix_(g == k, g == k)]
+        assert np.all(B != 0.0) and np.linalg.cond(B) < 100
+
+
+def test_ilu0_identity_accepts_the_plain_factor_and_sees_each_fault():
+    """What makes the GPU test of k_ilu0_level meaningful: a plain FP64 IKJ factor passes the identity check, and each of the three
+    ways the kernel could be subtly wrong - a missed update, the unfactored pivot of a row of the same group, an update applied
+    to the neighbouring column - fails it."""
+    for symmetric in (True, False):
+        m = ks.level_matrix(ILU_MIXED, np.random.default_rng(11), symmetric=symmetric, zero_lower=0.1)
+        rp, co, dp, A = m["rowptr"], m["cols"], m["diagpos"], m["vals"]
+        LU, _ = ks.ilu0_ikj(rp, co, dp, A)
+        err, bound = ks.ilu0_identity(rp, co, dp, A, LU)
+        r = ks.worst_ratio(err, bound)
+        print(f"plain IKJ factor (symmetric {symmetric}): worst error / bound {r:.3f}")
+        assert r <= 1.0
+        e64, b64 = ks.ilu0_identity_f64(rp, co, dp, A, LU)                   # the scipy form of the same check
+        assert ks.worst_ratio(e64, 2 * b64) <= 1.0
+        np.testing.assert_allclose(np.asarray(b64, dtype=np.float64), np.asarray(bound, dtype=np.float64), rtol=1e-12)
+        for fault in ("drop_update", "stale_pivot", "neighbour_column"):
+            bad, applied = ks.ilu0_ikj(rp, co, dp, A, group_of=m["group_of"], fault=fault)
+            assert applied, fault
+            err, bound = ks.ilu0_identity(rp, co, dp, A, bad)
+            assert ks.worst_ratio(err, bound) > 1e3, fault
+            e64, b64 = ks.ilu0_identity_f64(rp, co, dp, A, bad)
+            assert ks.worst_ratio(e64, 2 * b64) > 1e3, fault
+
+
+def test_ilu0_identity_is_exact_lu_on_block_diagonal_matrices():
+    m = ks.level_matrix([(5, 6), (4, 1)], np.random.default_rng(12), own_group_only=True)
+    LU, _ = ks.ilu0_ikj(m["rowptr"], m["cols"], m["diagpos"], m["vals"])
+    import scipy.sparse as sp
+    lu = sp.csr_matrix((LU, m["cols"], m["rowptr"]), shape=(m["n"],) * 2).toarray()
+    A = sp.csr_matrix((m["vals"], m["cols"], m["rowptr"]), shape=(m["n"],) * 2).toarray()
+    Lf, Uf = np.tril(lu, -1) + np.eye(m["n"]), np.triu(lu)
+    assert np.abs(Lf @ Uf - A).max() <= 50 * ks.EPS64 * np.abs(A).max()
+
+
+def test_sptrsv_residuals_accept_a_plain_solve_and_see_a_wrong_one():
+    m = ks.level_matrix(ILU_MIXED, np.random.default_rng(13), symmetric=False)
+    rp, co, dp = m["rowptr"], m["cols"], m["diagpos"]
+    LU, _ = ks.ilu0_ikj(rp, co, dp, m["vals"])
+    n = m["n"]
+    rhs = np.random.default_rng(14).standard_normal(n)
+    y, x = np.zeros(n), np.zeros(n)
+    for i in range(n):
+        s, d = rp[i], dp[i]
+        y[i] = rhs[i] - np.dot(LU[s:d], y[co[s:d]])
+    for i in range(n - 1, -1, -1):
+        d, e = dp[i], rp[i + 1]
+        x[i] = (y[i] - np.dot(LU[d + 1:e], x[co[d + 1:e]])) / LU[d]
+    ef, bf, eb, bb = ks.sptrsv_residuals(rp, co, dp, LU, rhs, y, x)
+    assert ks.worst_ratio(ef, bf) <= 1.0 and ks.worst_ratio(eb, bb) <= 1.0
+    import scipy.sparse as sp
+    lu = sp.csr_matrix((LU, co, rp), shape=(n, n)).toarray()
+    ref = np.linalg.solve(np.triu(lu), np.linalg.solve(np.tril(lu, -1) + np.eye(n), rhs))
+    assert np.abs(x - ref).max() <= 1e-12 * np.abs(ref).max()
+    y2 = y.copy()
+    y2[n // 2] *= 1 + 1e-12                                                  # a stale value in one row
+    ef, bf, eb, bb = ks.sptrsv_residuals(rp, co, dp, LU, rhs, y2, x)
+    assert ks.worst_ratio(ef, bf) > 10 and ks.worst_ratio(eb, bb) > 10
+    x2 = x.copy()
+    x2[5] = x[6]
+    assert ks.worst_ratio(*ks.sptrsv_residuals(rp, co, dp, LU, rhs, y, x2)[2:]) > 1e3
+
+
+def test_f32_ripple4_reference():
+    x = ks.f32_ripple4(1000).reshape(-1, 4)
+    assert np.all(x[:, 3] == 0) and np.all(np.abs(x[:, :3]) <= 1) and np.all(x[:, :3] * 512 == np.round(x[:, :3] * 512))
+    # node 300: h = (300 * 2654435761 mod 2^32) xor 2, by hand in Python integers
+    h = ((300 * 2654435761) & 0xFFFFFFFF) ^ (300 >> 7)
+    np.testing.assert_array_equal(x[300, :3], [(h & 1023) / 512 - 1, ((h >> 10) & 1023) / 512 - 1, ((h >> 20) & 1023) / 512 - 1])
+    assert len(np.unique(x[:, 0])) > 300                                      # not a constant
+    big = ks.f32_ripple4(4096 * 256 + 257).reshape(-1, 4)                     # node numbers beyond 2^20: the product needs 64 bits
+    i = 4096 * 256 + 200
+    h = ((i * 2654435761) & 0xFFFFFFFF) ^ (i >> 7)
+    assert big[i, 2] == ((h >> 20) & 1023) / 512 - 1

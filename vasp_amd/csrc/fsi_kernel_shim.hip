@@ -1404,6 +1404,236 @@ int shim_mask_scale(int64_t n, const double* mask, const int64_t* diagpos, const
   SHIM_RUN(c, "launch_mask_scale", launch_mask_scale(c.st, n, dm, ddp, dA, dy));
 }
 
+// ---- fsi_solver.hip: multicolour ILU(0) and its triangular solves (tests/test_gpu_ilu_kernels.py) ---------------------------
+// Levels: nlevels x (level_first, level_ngroups, level_group_rows).  The matrix is checked on the host before anything is
+// launched, because the kernels trust it: levels inside 0 .. n, columns inside 0 .. n, every row's diagpos inside the row.
+// Status 3 (nothing launched) otherwise.
+namespace {
+int levels_checked(const char* who, int64_t n, int nlevels, const int64_t* first, const int64_t* ngroups, const int32_t* group_rows,
+                   const int64_t* rowptr, const int32_t* cols, const int64_t* diagpos, std::vector<Level>& levels) {
+  auto bad = [&](const std::string& what) { g_err = std::string(who) + ": " + what; return 3; };
+  if (n < 0 || nlevels < 0 || rowptr[0] != 0) return bad("bad sizes");
+  for (int64_t i = 0; i < n; ++i) {
+    if (rowptr[i + 1] < rowptr[i]) return bad("rowptr decreases at row " + std::to_string(i));
+    if (diagpos[i] < rowptr[i] || diagpos[i] >= rowptr[i + 1]) return bad("row " + std::to_string(i) + " has no diagonal entry inside the row");
+    if (cols[diagpos[i]] != i) return bad("diagpos of row " + std::to_string(i) + " is not its diagonal");
+  }
+  for (int64_t t = 0; t < rowptr[n]; ++t)
+    if (cols[t] < 0 || cols[t] >= n) return bad("column outside the matrix at entry " + std::to_string(t));
+  levels.clear();
+  for (int l = 0; l < nlevels; ++l) {
+    if (first[l] < 0 || ngroups[l] < 0 || group_rows[l] < 1 || first[l] + ngroups[l] * group_rows[l] > n)
+      return bad("level " + std::to_string(l) + " outside the matrix");
+    levels.push_back(Level{first[l], ngroups[l], group_rows[l]});
+  }
+  return 0;
+}
+}  // namespace
+// LU [rowptr[n]] in place (+ SHIM_TAIL); counters [4] in/out
+int shim_ilu0(int64_t n, int nlevels, const int64_t* level_first, const int64_t* level_ngroups, const int32_t* level_group_rows,
+              const int64_t* rowptr, const int32_t* cols, const int64_t* diagpos, double* LU, int32_t* counters) {
+  std::vector<Level> levels;
+  if (const int rc = levels_checked("shim_ilu0", n, nlevels, level_first, level_ngroups, level_group_rows, rowptr, cols, diagpos, levels))
+    return rc;
+  Call c;
+  const int64_t* drp = c.in(rowptr, (size_t)n + 1);
+  const int32_t* dc = c.in(cols, (size_t)rowptr[n]);
+  const int64_t* ddp = c.in(diagpos, (size_t)n);
+  double* dLU = c.io(LU, (size_t)rowptr[n] + SHIM_TAIL);
+  int32_t* dcn = c.io(counters, 4);
+  SHIM_RUN(c, "launch_ilu0_levels", launch_ilu0_levels(c.st, levels, drp, dc, ddp, dLU, dcn));
+}
+// rhs [n]; tmp (the forward result y) and x [n + SHIM_TAIL], both returned
+int shim_sptrsv(int64_t n, int nlevels, const int64_t* level_first, const int64_t* level_ngroups, const int32_t* level_group_rows,
+                const int64_t* rowptr, const int32_t* cols, const int64_t* diagpos, const double* LU, const double* rhs, double* tmp,
+                double* x) {
+  std::vector<Level> levels;
+  if (const int rc = levels_checked("shim_sptrsv", n, nlevels, level_first, level_ngroups, level_group_rows, rowptr, cols, diagpos, levels))
+    return rc;
+  Call c;
+  const int64_t* drp = c.in(rowptr, (size_t)n + 1);
+  const int32_t* dc = c.in(cols, (size_t)rowptr[n]);
+  const int64_t* ddp = c.in(diagpos, (size_t)n);
+  const double* dLU = c.in(LU, (size_t)rowptr[n]);
+  const double* drhs = c.in(rhs, (size_t)n);
+  double* dtmp = c.io(tmp, (size_t)n + SHIM_TAIL);
+  double* dx = c.io(x, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_sptrsv_levels", launch_sptrsv_levels(c.st, levels, drp, dc, ddp, dLU, drhs, dtmp, dx));
+}
+
+// ---- fsi_solver.hip / fsi_block.hip: boundary terms and small vector launchers (tests/test_gpu_vector_kernels.py) ------------
+// Outputs of n entries carry SHIM_TAIL sentinels; an indexed target has its own length (nt) and the indices are checked on the
+// host first (status 3, nothing launched).
+extern "C++" {
+namespace {
+template <class I>
+int indices_checked(const char* who, const I* idx, int64_t n, int64_t nt) {
+  for (int64_t i = 0; i < n; ++i)
+    if (idx[i] < 0 || (int64_t)idx[i] >= nt) { g_err = std::string(who) + ": index " + std::to_string(i) + " outside the target"; return 3; }
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+int shim_fill(int64_t n, double v, double* x) {
+  Call c;
+  double* dx = c.io(x, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_fill", launch_fill(c.st, dx, n, v));
+}
+int shim_copy(int64_t n, const double* s, double* d) {
+  Call c;
+  const double* ds = c.in(s, (size_t)n);
+  double* dd = c.io(d, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_copy", launch_copy(c.st, dd, ds, n));
+}
+int shim_axpy(int64_t n, double a, const double* x, double* y) {
+  Call c;
+  const double* dx = c.in(x, (size_t)n);
+  double* dy = c.io(y, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_axpy", launch_axpy(c.st, dy, a, dx, n));
+}
+int shim_axpby(int64_t n, double a, const double* x, double b, const double* y, double* z) {
+  Call c;
+  const double* dx = c.in(x, (size_t)n);
+  const double* dy = c.in(y, (size_t)n);
+  double* dz = c.io(z, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_axpby", launch_axpby(c.st, dz, a, dx, b, dy, n));
+}
+int shim_scale(int64_t n, double a, double* y) {
+  Call c;
+  double* dy = c.io(y, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_scale", launch_scale(c.st, dy, a, n));
+}
+int shim_mul(int64_t n, const double* x, const double* y, double* z) {
+  Call c;
+  const double* dx = c.in(x, (size_t)n);
+  const double* dy = c.in(y, (size_t)n);
+  double* dz = c.io(z, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_mul", launch_mul(c.st, dz, dx, dy, n));
+}
+int shim_div(int64_t n, const double* x, const double* y, double* z) {
+  Call c;
+  const double* dx = c.in(x, (size_t)n);
+  const double* dy = c.in(y, (size_t)n);
+  double* dz = c.io(z, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_div", launch_div(c.st, dz, dx, dy, n));
+}
+int shim_negate(int64_t n, const double* F, double* b) {
+  Call c;
+  const double* dF = c.in(F, (size_t)n);
+  double* db = c.io(b, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_negate", launch_negate(c.st, db, dF, n));
+}
+// d[i] = s[idx[i]]: s [ns], d [n + SHIM_TAIL]
+int shim_gather(int64_t n, const double* s, int64_t ns, const int32_t* idx, double* d) {
+  if (const int rc = indices_checked("shim_gather", idx, n, ns)) return rc;
+  Call c;
+  const double* ds = c.in(s, (size_t)ns);
+  const int32_t* di = c.in(idx, (size_t)n);
+  double* dd = c.io(d, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_gather", launch_gather(c.st, dd, ds, di, n));
+}
+// d[idx[i]] = s[i]: s [n], d [nd] in place
+int shim_scatter(int64_t n, const double* s, const int32_t* idx, double* d, int64_t nd) {
+  if (const int rc = indices_checked("shim_scatter", idx, n, nd)) return rc;
+  Call c;
+  const double* ds = c.in(s, (size_t)n);
+  const int32_t* di = c.in(idx, (size_t)n);
+  double* dd = c.io(d, (size_t)nd);
+  SHIM_RUN(c, "launch_scatter", launch_scatter(c.st, dd, ds, di, n));
+}
+// comp[3 k + i] = full[3 snode[k] + i]: full [3 nnodes], comp [3 nS + SHIM_TAIL]
+int shim_gather3(int64_t nS, int64_t nnodes, const int32_t* snode, const double* full, double* comp) {
+  if (const int rc = indices_checked("shim_gather3", snode, nS, nnodes)) return rc;
+  Call c;
+  const int32_t* dsn = c.in(snode, (size_t)nS);
+  const double* dfu = c.in(full, (size_t)(3 * nnodes));
+  double* dco = c.io(comp, (size_t)(3 * nS) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_gather3", launch_gather3(c.st, nS, dsn, dfu, dco));
+}
+// full [3 nnodes] in place
+int shim_scatter3(int64_t nS, int64_t nnodes, const int32_t* snode, const double* comp, double* full) {
+  if (const int rc = indices_checked("shim_scatter3", snode, nS, nnodes)) return rc;
+  Call c;
+  const int32_t* dsn = c.in(snode, (size_t)nS);
+  const double* dco = c.in(comp, (size_t)(3 * nS));
+  double* dfu = c.io(full, (size_t)(3 * nnodes));
+  SHIM_RUN(c, "launch_scatter3", launch_scatter3(c.st, nS, dsn, dco, dfu));
+}
+int shim_round_to_f32(int64_t n, const double* a, float* b) {
+  Call c;
+  const double* da = c.in(a, (size_t)n);
+  float* db = c.io(b, (size_t)n + SHIM_TAIL);
+  SHIM_RUN(c, "launch_round_to_f32", launch_round_to_f32(c.st, n, da, db));
+}
+// y[idx[i]] += a coef[i]: y [ny] in place
+int shim_add_indexed(int64_t n, const int32_t* idx, const double* coef, double a, double* y, int64_t ny) {
+  if (const int rc = indices_checked("shim_add_indexed", idx, n, ny)) return rc;
+  Call c;
+  const int32_t* di = c.in(idx, (size_t)n);
+  const double* dco = c.in(coef, (size_t)n);
+  double* dy = c.io(y, (size_t)ny);
+  SHIM_RUN(c, "launch_add_indexed", launch_add_indexed(c.st, dy, di, dco, a, n));
+}
+// vals[pos[i]] += a v[i]: vals [nvals] in place
+int shim_add_at(int64_t n, const int64_t* pos, const double* v, double a, double* vals, int64_t nvals) {
+  if (const int rc = indices_checked("shim_add_at", pos, n, nvals)) return rc;
+  Call c;
+  const int64_t* dp = c.in(pos, (size_t)n);
+  const double* dv = c.in(v, (size_t)n);
+  double* dvals = c.io(vals, (size_t)nvals);
+  SHIM_RUN(c, "launch_add_at", launch_add_at(c.st, dvals, dp, dv, a, n));
+}
+// b[bc[i]] = g[i] - U[bc[i]]: b (in place), U [nu]
+int shim_bc_rhs(int64_t n, const int32_t* bc, const double* g, const double* U, double* b, int64_t nu) {
+  if (const int rc = indices_checked("shim_bc_rhs", bc, n, nu)) return rc;
+  Call c;
+  const int32_t* dbc = c.in(bc, (size_t)n);
+  const double* dg = c.in(g, (size_t)n);
+  const double* dU = c.in(U, (size_t)nu);
+  double* db = c.io(b, (size_t)nu);
+  SHIM_RUN(c, "launch_bc_rhs", launch_bc_rhs(c.st, db, dU, dbc, dg, n));
+}
+// U[bc[i]] = g[i]: U [nu] in place
+int shim_bc_set(int64_t n, const int32_t* bc, const double* g, double* U, int64_t nu) {
+  if (const int rc = indices_checked("shim_bc_set", bc, n, nu)) return rc;
+  Call c;
+  const int32_t* dbc = c.in(bc, (size_t)n);
+  const double* dg = c.in(g, (size_t)n);
+  double* dU = c.io(U, (size_t)nu);
+  SHIM_RUN(c, "launch_bc_set", launch_bc_set(c.st, dU, dbc, dg, n));
+}
+// urow [nrows], ptr [nrows + 1], col / val [ptr[nrows]]; U, U1, F (in place) [nu]
+int shim_robin_residual(int64_t nrows, const int32_t* urow, const int32_t* ptr, const int32_t* col, const double* val, double th0,
+                        double th1, const double* U, const double* U1, double* F, int64_t nu) {
+  if (const int rc = indices_checked("shim_robin_residual rows", urow, nrows, nu)) return rc;
+  for (int64_t k = 0; k < nrows; ++k)
+    if (ptr[k] < 0 || ptr[k + 1] < ptr[k]) { g_err = "shim_robin_residual: ptr decreases at row " + std::to_string(k); return 3; }
+  const int64_t ne = ptr[nrows];
+  if (const int rc = indices_checked("shim_robin_residual columns", col, ne, nu)) return rc;
+  Call c;
+  const int32_t* dur = c.in(urow, (size_t)nrows);
+  const int32_t* dp = c.in(ptr, (size_t)nrows + 1);
+  const int32_t* dcl = c.in(col, (size_t)ne);
+  const double* dv = c.in(val, (size_t)ne);
+  const double* dU = c.in(U, (size_t)nu);
+  const double* dU1 = c.in(U1, (size_t)nu);
+  double* dF = c.io(F, (size_t)nu);
+  SHIM_RUN(c, "launch_robin_residual", launch_robin_residual(c.st, nrows, dur, dp, dcl, dv, th0, th1, dU, dU1, dF));
+}
+// x [4 nnodes + SHIM_TAIL]
+int shim_f32_ripple4(int64_t nnodes, float* x) {
+  Call c;
+  float* dx = c.io(x, (size_t)(4 * nnodes) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_f32_ripple4", launch_f32_ripple4(c.st, nnodes, dx));
+}
+// out [1 + SHIM_TAIL]
+int shim_f32_sumsq(int64_t n, const float* x, double* out) {
+  Call c;
+  const float* dx = c.in(x, (size_t)n);
+  double* dout = c.io(out, 1 + SHIM_TAIL);
+  SHIM_RUN(c, "launch_f32_sumsq", launch_f32_sumsq(c.st, n, dx, dout));
+}
+
 // ---- a live context's preconditioner arrays (FsiCtx of fsi_context.hpp, as the library was compiled) -----------------------
 // shim_ctx_info: N2, V, nS, sb_nblocks, tiled, tile_nodes, tile_max_nu, schur_tiled, schur_tile, s_tile_max_nu, sweeps_fp16,
 // a32_ptail, a32_tail_src, a32_tail_nnz, op32_ok, kry_fp32, drows_ok, mg_nc, mg_cnnz, mg_ready, sbmg_nc, sbmg_nblk, sbmg_ready,
@@ -1466,7 +1696,7 @@ int shim_ctx_array(const FsiCtx* ctx, const char* name, void* host, int64_t* cou
                          E(App),        E(Avp32),     E(Apv32),   E(vv_db),      E(adv_db),      E(dd_db32),     E(adv_rowmask),
                          E(vv_dinv),    E(mask_f),    E(mask_s),  E(ss_vals),    E(ss_src),      E(ss_rowptr),   E(ss_cols),
                          E(ss_diagpos), E(fs_rows),   E(fs_ptr),  E(fs_col),     E(fs_src),      E(sb_row),      E(sb_src),
-                         E(sb_stride),  E(s_diagpos)};
+                         E(sb_stride),  E(s_diagpos),  E(LU),       E(user2solver)};
 #undef E
   for (const Entry& t : table) {
     if (std::strcmp(t.name, name) != 0) continue;
@@ -1480,6 +1710,17 @@ int shim_ctx_array(const FsiCtx* ctx, const char* name, void* host, int64_t* cou
   }
   g_err = std::string("shim_ctx_array: unknown array ") + name;
   return 2;
+}
+
+// the colours of the multicolour ordering: out [3 x nmax] = (first_row, ngroups, group_rows) per level; returns their number
+int shim_ctx_levels(const FsiCtx* ctx, int64_t* out, int nmax) {
+  const int k = (int)ctx->levels.size();
+  for (int i = 0; i < k && i < nmax; ++i) {
+    out[3 * i] = ctx->levels[i].first_row;
+    out[3 * i + 1] = ctx->levels[i].ngroups;
+    out[3 * i + 2] = ctx->levels[i].group_rows;
+  }
+  return k;
 }
 
 // y = the context's monolithic product of x (solver ordering, row-equilibrated: no permutation, no un-scaling), through

@@ -114,7 +114,7 @@ void launch_expand_cols(hipStream_t st, int64_t N2, int64_t V, const int64_t* na
                         const int64_t* padj_ptr, const int32_t* padj, const int32_t* vrank, const int64_t* rowptr,
                         int32_t* cols, int64_t* diagpos) {
   const int64_t n = 6 * N2 + V;
-  hipLaunchKernelGGL(k_expand_cols, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, N2, V, nadj_ptr, nadj,
+  if (n > 0) hipLaunchKernelGGL(k_expand_cols, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, N2, V, nadj_ptr, nadj,
                      padj_ptr, padj, vrank, rowptr, cols, diagpos);
 }
 void launch_fill(hipStream_t st, double* x, int64_t n, double v) { LAUNCH1D(k_fill, st, n, x, n, v); }
@@ -388,7 +388,8 @@ static void spmv_node6_any(hipStream_t st, int64_t N2, int64_t V, const int64_t*
   constexpr bool xcd = true;        // XCD-aware node mapping: -9 % HBM traffic (round 2)
   int64_t blocks = (N2 + 3) / 4;                                 // one wave per node (see launch_spmv_node6p)
   blocks = (blocks + 7) & ~(int64_t)7;
-  if (xcd) hipLaunchKernelGGL((k_spmv_node6<VT, true>), dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, vals, x, y);
+  if (blocks <= 0) {}      // no node rows (an empty grid is an invalid launch)
+  else if (xcd) hipLaunchKernelGGL((k_spmv_node6<VT, true>), dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, vals, x, y);
   else hipLaunchKernelGGL((k_spmv_node6<VT, false>), dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, vals, x, y);
   spmv_prows<VT>(st, N2, V, rowptr, cols, vals, g, x, y);      // pressure rows
 }
@@ -401,7 +402,7 @@ int launch_spmv_node6(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowp
     if (!g.nadj_ptr || !g.nadj) return LAUNCH_REFUSED;
     int64_t blocks = (N2 + 3) / 4;
     blocks = (blocks + 7) & ~(int64_t)7;
-    hipLaunchKernelGGL(k_spmv_node6c<true>, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, vals, g.nadj_ptr, g.nadj, ad64, x, y);
+    if (blocks > 0) hipLaunchKernelGGL(k_spmv_node6c<true>, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, vals, g.nadj_ptr, g.nadj, ad64, x, y);
     spmv_prows<double>(st, N2, V, rowptr, cols, vals, g, x, y);
     return 0;
   }
@@ -515,14 +516,14 @@ __global__ __launch_bounds__(256) void k_spmv_node6pc(int64_t N2, const int64_t*
 }
 void launch_pad_cols32(hipStream_t st, int64_t N2, const int64_t* rowptr, const int32_t* cols, const int64_t* p32, int32_t* cols32) {
   int64_t blocks = std::min<int64_t>((N2 + 3) / 4, 8192);
-  hipLaunchKernelGGL(k_pad_cols32, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, p32, cols32);
+  if (blocks > 0) hipLaunchKernelGGL(k_pad_cols32, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, p32, cols32);
 }
 // node rows padded (k_pad_vals32), pressure rows as they are behind them at entry offset ptail
 // (v_rows_only: the d rows are served from their pair form - k_spmv_node6pc never reads value rows 0 .. 2 of the copy)
 void launch_pad_vals32(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const double* A, const int64_t* p32,
                        int64_t ptail, int64_t nnz_tail, int64_t tail_src, float* A32, bool v_rows_only) {
   int64_t blocks = std::min<int64_t>((N2 + 3) / 4, 8192);
-  hipLaunchKernelGGL(k_pad_vals32, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, A, p32, A32, v_rows_only ? 3 : 0);
+  if (blocks > 0) hipLaunchKernelGGL(k_pad_vals32, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, A, p32, A32, v_rows_only ? 3 : 0);
   if (V > 0 && nnz_tail > 0) launch_round_to_f32(st, nnz_tail, A + tail_src, A32 + ptail);
 }
 // y = A32 x: padded node rows, then the pressure rows (their values at vals + ptail, indexed by the rows' own pointers
@@ -536,7 +537,7 @@ int launch_spmv_node6p(hipStream_t st, int64_t N2, int64_t V, const int64_t* p32
     if (!g.nadj_ptr || !g.nadj) return LAUNCH_REFUSED;
     int64_t blocks = (N2 + 3) / 4;
     blocks = (blocks + 7) & ~(int64_t)7;
-    hipLaunchKernelGGL(k_spmv_node6pc<true>, dim3((unsigned)blocks), dim3(256), 0, st, N2, p32, cols32, vals, g.nadj_ptr, g.nadj, ad32, x, y);
+    if (blocks > 0) hipLaunchKernelGGL(k_spmv_node6pc<true>, dim3((unsigned)blocks), dim3(256), 0, st, N2, p32, cols32, vals, g.nadj_ptr, g.nadj, ad32, x, y);
     spmv_prows<float>(st, N2, V, rowptr, cols, vals + tail_shift, g, x, y);
     return 0;
   }
@@ -546,7 +547,8 @@ int launch_spmv_node6p(hipStream_t st, int64_t N2, int64_t V, const int64_t* p32
   int64_t blocks = (N2 + 3) / 4;
   if (blocks > bmax) blocks = bmax;
   blocks = (blocks + 7) & ~(int64_t)7;
-  if (xcd) hipLaunchKernelGGL(k_spmv_node6p<true>, dim3((unsigned)blocks), dim3(256), 0, st, N2, p32, cols32, vals, x, y);
+  if (blocks <= 0) {}      // no node rows
+  else if (xcd) hipLaunchKernelGGL(k_spmv_node6p<true>, dim3((unsigned)blocks), dim3(256), 0, st, N2, p32, cols32, vals, x, y);
   else hipLaunchKernelGGL(k_spmv_node6p<false>, dim3((unsigned)blocks), dim3(256), 0, st, N2, p32, cols32, vals, x, y);
   // the pressure-row kernels index values and columns with the rows' own pointers: hand them the value array shifted so that
   // vals32[rowptr[row]] is the row's first value
@@ -557,12 +559,14 @@ __global__ __launch_bounds__(256) void k_round_to_f32(int64_t n, const double* _
   GRID_STRIDE(i, n) b[i] = (float)a[i];
 }
 void launch_round_to_f32(hipStream_t st, int64_t n, const double* a, float* b) {
+  if (n <= 0) return;      // nothing to round (an empty grid is an invalid launch)
   int64_t blocks = (n + 255) / 256;
   if (blocks > 65536) blocks = 65536;
   hipLaunchKernelGGL(k_round_to_f32, dim3((unsigned)blocks), dim3(256), 0, st, n, a, b);
 }
 void launch_spmv(hipStream_t st, int64_t n, const int64_t* rowptr, const int32_t* cols, const double* vals,
                  const double* x, double* y, int tag) {
+  if (n <= 0) return;      // no rows (an empty grid is an invalid launch)
   int64_t blocks = (n + 3) / 4;
   if (blocks > 8192) blocks = 8192;
   if (tag == SPMV_MONOLITHIC)
@@ -633,6 +637,14 @@ void launch_dot(hipStream_t st, const double* x, const double* y, int64_t n, dou
 // goes through agent-scope stores/loads (write-through, L1-bypassing), drained with s_waitcnt before the next row.
 // Launch boundaries order the colours, so there is no spinning anywhere.
 // counters[1]: error flags (1 = row too long, 2 = zero / non-finite pivot).
+// Every row must have a diagonal entry (diagpos[row] >= rowptr[row]): the kernel indexes its LDS tile with
+// diagpos[row] - rowptr[row].  The library's matrix has one in every row before any factorisation runs, by construction
+// in fsi_create: number_nodes (fsi_setup.hip) puts the pair (a, a) of every node of every cell into the node graph and
+// refuses a node that belongs to no cell, so every node is its own neighbour and k_expand_cols finds the diagonal of its
+// six rows; a vertex is then its own pressure neighbour too (build_node_graph keeps the neighbours below V), and
+// build_pressure_blocks refuses a context ("vertex missing from its own neighbour list") where it is not.  The -1 that
+// k_expand_cols leaves in a row without a diagonal therefore never reaches a context that refresh_preconditioner sees;
+// k_matrix_finish / ident_zeros only decide the VALUE of that entry (1 in an all-zero or Dirichlet row).
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_ilu0_level(int64_t first_row, int64_t ngroups, int group_rows,
                                                    const int64_t* __restrict__ rowptr,
