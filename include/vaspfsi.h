@@ -375,6 +375,22 @@ int fsi_band_sample(FsiCtx* ctx, int32_t quantity);
  * padlen <= 33 and < the number of frames (where scipy raises).  The raw history is kept: another band can follow. */
 int fsi_band_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* b, const double* a, const double* zi,
                     int32_t padlen);
+/* Replaces: the frame selection of create_transformed_matrix [REF .../postprocessing_h5py_common.py:285-307: start, stop and
+ * stride over the Visualization files] and the start_t of the files that follow.  The filter, the amplitude, the fetches of
+ * filtered / amplitude / magnitude frames and fsi_band_trace work on the recorded frames first, first + stride, ..., count of
+ * them (frame k of these calls is recorded frame first + k * stride); a raw fetch keeps its index in the history.  Needs
+ * stride >= 1 and first + (count - 1) * stride < the number of recorded frames; count = -1: as many as fit.  Invalidates the
+ * filtered series and the amplitude.  fsi_band_sample resets the selection to every recorded frame.  Unlike the reference,
+ * which drops the last frames of its range, every selected frame is kept. */
+int fsi_band_select(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count, int64_t stride);
+/* Replaces: one further band of the multiband loop of create_hi_pass_viz [REF .../create_hi_pass_viz.py:191-198], which
+ * filters a row that is already filtered: y <- filtfilt(b, a, y) of every row of the filtered series, in the arithmetic of
+ * fsi_band_filter, bit for bit, inside the series' own buffer (no device memory is allocated).  Arguments and checks as
+ * fsi_band_filter; FSI_ERR_INVALID with "no filtered series (fsi_band_filter first)" when there is none, and when padlen
+ * exceeds the previous stage's (every order-5 band-pass and band-stop has 33; put a longer filter first).  Invalidates the
+ * amplitude; the raw history is kept. */
+int fsi_band_filter_next(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* b, const double* a, const double* zi,
+                         int32_t padlen);
 /* Replaces: calculate_windowed_rms [REF .../postprocessing_h5py_common.py:685-731] as create_hi_pass_viz uses it (:218-230):
  * selects the amplitude of the filtered series for the fetches that follow.  window > 0: sqrt(convolve(y^2, ones(window) /
  * window, "valid")) centred by (window - 1) / 2 frames, zero outside; window = 0: the filtered series itself (the reference's
@@ -387,6 +403,12 @@ int fsi_band_amplitude(FsiCtx* ctx, int32_t quantity, int32_t window);
  * when fetched, cheapest in ascending order; a frame's value does not depend on the order. */
 int fsi_band_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, double* out, double* max_out,
                    int64_t* argmax_out);
+/* Replaces: create_point_trace [REF .../postprocessing_h5py_common.py:470-483] and the frames * full-frame reads behind it:
+ * the time series of npoints listed nodes over the selected frames, from the raw history (what = FSI_BAND_RAW) or the
+ * filtered series (FSI_BAND_FILTERED), in one copy.  points[npoints]: indices into the session's node list (0 <= . < n, else
+ * FSI_ERR_INVALID "node out of range"; a node may be listed twice).  out[npoints][frames][1 + ncomp]: the magnitude
+ * sqrt((x x + y y) + z z) first (for p the value itself), then the ncomp values. */
+int fsi_band_trace(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t npoints, const int32_t* points, double* out);
 /* Closes the session of the quantity and frees its device memory (fsi_destroy does the same). */
 int fsi_band_end(FsiCtx* ctx, int32_t quantity);
 

@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_end", "fsi_band_begin", "fsi_band_sample", "fsi_band_filter", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_end", "fsi_spec_begin", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_end", "fsi_band_begin", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_end", "fsi_spec_begin", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -161,6 +161,9 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_band_filter.argtypes = [vp, i32, i32, vp, vp, vp, i32]
     lib.fsi_band_amplitude.argtypes = [vp, i32, i32]
     lib.fsi_band_fetch.argtypes = [vp, i32, i32, i64, vp, C.POINTER(dbl), C.POINTER(i64)]
+    lib.fsi_band_select.argtypes = [vp, i32, i64, i64, i64]
+    lib.fsi_band_filter_next.argtypes = [vp, i32, i32, vp, vp, vp, i32]
+    lib.fsi_band_trace.argtypes = [vp, i32, i32, i64, vp, vp]
     lib.fsi_band_end.argtypes = [vp, i32]
     lib.fsi_spec_begin.argtypes = [vp, i32, i64, vp, vp, i32, i64]
     lib.fsi_spec_sample.argtypes = [vp, i32]
@@ -537,12 +540,16 @@ class HipBackend:
             raise ValueError("nodes_b must have the shape of nodes")
         self._check(self.lib.fsi_band_begin(self.ctx, q, len(a), _ptr(a), None if b is None else _ptr(b), int(capacity)))
         if not hasattr(self, "_band_shape"):
-            self._band_shape = {}
+            self._band_shape, self._band_frames = {}, {}
         self._band_shape[quantity] = (len(a), 1 if quantity == "p" else 3)
+        self._band_frames[quantity] = [0, 0]          # frames recorded, frames selected: the size of a trace
 
     def hi_pass_sample(self, quantity: str) -> None:
         """Record the session's rows of dvp_["n"] as the next frame of its history (fsi_band_sample)."""
         self._check(self.lib.fsi_band_sample(self.ctx, self.BAND_QUANTITY[quantity]))
+        frames = self._band_frames[quantity]
+        frames[0] += 1
+        frames[1] = frames[0]                         # a new frame resets the selection to every recorded frame
 
     def hi_pass_filter(self, quantity: str, b, a, zi, padlen: int) -> None:
         """scipy.signal.filtfilt(b, a, .) of every row over the recorded frames (fsi_band_filter); zi = lfilter_zi(b, a)."""
@@ -550,6 +557,31 @@ class HipBackend:
         if len(a) != len(b) or len(zi) != len(b) - 1:
             raise ValueError("b and a must have one length, zi one less")
         self._check(self.lib.fsi_band_filter(self.ctx, self.BAND_QUANTITY[quantity], len(b), _ptr(b), _ptr(a), _ptr(zi), int(padlen)))
+
+    def hi_pass_select(self, quantity: str, first: int = 0, count: int = -1, stride: int = 1) -> int:
+        """Form the filtered series, the amplitude and the traces on the recorded frames ``first, first + stride, ...``,
+        ``count`` of them (-1: as many as fit) (fsi_band_select); a raw fetch keeps absolute frame indices.  Returns the
+        number of selected frames."""
+        first, count, stride = int(first), int(count), int(stride)
+        self._check(self.lib.fsi_band_select(self.ctx, self.BAND_QUANTITY[quantity], first, count, stride))
+        frames = self._band_frames[quantity]
+        frames[1] = (frames[0] - 1 - first) // stride + 1 if count == -1 else count
+        return frames[1]
+
+    def hi_pass_filter_next(self, quantity: str, b, a, zi, padlen: int) -> None:
+        """One more stage on the filtered series, y <- filtfilt(b, a, y), in place on the device (fsi_band_filter_next)."""
+        b, a, zi = (np.ascontiguousarray(x, dtype=np.float64) for x in (b, a, zi))
+        if len(a) != len(b) or len(zi) != len(b) - 1:
+            raise ValueError("b and a must have one length, zi one less")
+        self._check(self.lib.fsi_band_filter_next(self.ctx, self.BAND_QUANTITY[quantity], len(b), _ptr(b), _ptr(a), _ptr(zi), int(padlen)))
+
+    def hi_pass_trace(self, quantity: str, what: str, points) -> np.ndarray:
+        """The series of the listed nodes (indices into the session's node list) over the selected frames, 'raw' or
+        'filtered', as (points, frames, 1 + ncomp) with the magnitude first (fsi_band_trace): one copy from the device."""
+        pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1)
+        out = np.empty((len(pts), self._band_frames[quantity][1], 1 + self._band_shape[quantity][1]))
+        self._check(self.lib.fsi_band_trace(self.ctx, self.BAND_QUANTITY[quantity], self.BAND_WHAT[what], len(pts), _ptr(pts), _ptr(out)))
+        return out
 
     def hi_pass_amplitude(self, quantity: str, window: int) -> None:
         """Select the amplitude of the filtered series (fsi_band_amplitude): flat-window RMS over ``window`` frames, or the

@@ -21,7 +21,15 @@
 //                      would give other numbers than the tool this replaces: floating-point contraction is off in this file,
 //                      and FP64 multiply / add / subtract are correctly rounded, which reproduces the host bit for bit.
 //                      Loads run UNR frames ahead of the recurrence: the dependency chain is y -> z[0] -> y (three FP64
-//                      operations per sample), not the memory system.
+//                      operations per sample), not the memory system.  Its input is a view of the history: frames first,
+//                      first + stride, ... (the launcher offsets the pointer, xs is the distance of two selected frames).
+//   k_band_filter_next: the same filtfilt of the filtered series itself, y <- filtfilt(b, a, y), inside work: stage k of a
+//                      multiband cascade (create_hi_pass_viz.py:191-198).  The forward pass overwrites its input as it goes:
+//                      the head of the extension reads ahead of the write position, the body reads the element it is about
+//                      to overwrite, and only the tail extension needs inputs that are gone - the last padlen + 1 samples,
+//                      kept per lane in LDS (34 x 64 doubles, 17 KiB; indexed by a loop counter, which registers cannot be).
+//   k_band_trace     : the rows of a few listed nodes over all selected frames, raw or filtered, with their magnitude
+//                      (create_point_trace, postprocessing_h5py_common.py:470-483): out[point][frame][1 + ncomp].
 //   k_band_rms       : flat-window RMS sqrt(convolve(y^2, ones(w) / w, "valid")), frame by frame: the sum of squares of a
 //                      window is advanced from the previous window's (+ newest^2 - oldest^2) and recomputed exactly every
 //                      BAND_RMS_REFRESH windows, so that rounding cannot accumulate; clamped at zero before the square root
@@ -47,6 +55,23 @@ __device__ __forceinline__ double band_step(const BandCoef& c, double (&z)[NZ], 
   return y;
 }
 
+// the second half of filtfilt: the forward result w[0 .. L) filtered from its last sample to its first, in place
+__device__ __forceinline__ void band_backward(const BandCoef& c, double (&z)[NZ], double* w, int64_t nrow, int64_t L) {
+  {
+    const double yl = w[(L - 1) * nrow];
+#pragma unroll
+    for (int k = 0; k < NZ; ++k) z[k] = c.zi[k] * yl;
+  }
+  for (int64_t j0 = L - 1; j0 >= 0; j0 -= UNR) {
+    double v[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) v[u] = j0 - u >= 0 ? w[(j0 - u) * nrow] : 0.0;
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+      if (j0 - u >= 0) w[(j0 - u) * nrow] = band_step(c, z, v[u]);
+  }
+}
+
 __global__ __launch_bounds__(256) void k_band_sample(int64_t nrow, const double* __restrict__ U, const int32_t* __restrict__ idx0,
                                                      const int32_t* __restrict__ idx1, double* __restrict__ dst) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -57,16 +82,16 @@ __global__ __launch_bounds__(256) void k_band_sample(int64_t nrow, const double*
 }
 
 __global__ __launch_bounds__(64) void k_band_filter(int64_t nrow, int64_t n, int p, BandCoef c, const double* __restrict__ hist,
-                                                    double* __restrict__ work) {
+                                                    int64_t xs, double* __restrict__ work) {
   const int64_t r = (int64_t)blockIdx.x * 64 + threadIdx.x;
   if (r >= nrow) return;
   const int64_t L = n + 2 * (int64_t)p;
   const double* x = hist + r;
   double* w = work + r;
-  const double x0 = x[0], xl = x[(n - 1) * nrow];
+  const double x0 = x[0], xl = x[(n - 1) * xs];
   double z[NZ];
   {
-    const double e0 = 2.0 * x0 - x[(int64_t)p * nrow];
+    const double e0 = 2.0 * x0 - x[(int64_t)p * xs];
 #pragma unroll
     for (int k = 0; k < NZ; ++k) z[k] = c.zi[k] * e0;
   }
@@ -75,27 +100,68 @@ __global__ __launch_bounds__(64) void k_band_filter(int64_t nrow, int64_t n, int
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const int64_t j = j0 + u;                      // uniform over the wavefront
-      if (j < p) v[u] = 2.0 * x0 - x[(p - j) * nrow];
-      else if (j < p + n) v[u] = x[(j - p) * nrow];
-      else if (j < L) v[u] = 2.0 * xl - x[(n - 2 - (j - p - n)) * nrow];
+      if (j < p) v[u] = 2.0 * x0 - x[(p - j) * xs];
+      else if (j < p + n) v[u] = x[(j - p) * xs];
+      else if (j < L) v[u] = 2.0 * xl - x[(n - 2 - (j - p - n)) * xs];
       else v[u] = 0.0;
     }
 #pragma unroll
     for (int u = 0; u < UNR; ++u)
       if (j0 + u < L) w[(j0 + u) * nrow] = band_step(c, z, v[u]);
   }
+  band_backward(c, z, w, nrow, L);
+}
+
+// The series is x[i] = w[(q + i) nrow], i < n, left by a stage of padlen q >= p; the result takes w[0 .. n + 2 p), the series at
+// w[p ..].  One pointer: input and output alias.  A batch's loads are all issued before its stores, and every load of a batch
+// is at or ahead of the batch's first store (head: q + p - j > j for j < p <= q; body: q + j - p >= j), so no load sees a
+// value of this stage.
+__global__ __launch_bounds__(64) void k_band_filter_next(int64_t nrow, int64_t n, int q, int p, BandCoef c, double* work) {
+  __shared__ double tail[BAND_MAX_PADLEN + 1][64];   // tail[k][lane] = x[n - 1 - p + k], k <= p: a lane reads its own column only
+  const int64_t r = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (r >= nrow) return;
+  const int lane = threadIdx.x;
+  const int64_t L = n + 2 * (int64_t)p;
+  double* w = work + r;
+  const double* x = w + (int64_t)q * nrow;
+  const double x0 = x[0], xl = x[(n - 1) * nrow];
+  for (int k = 0; k <= p; ++k) tail[k][lane] = x[(n - 1 - p + k) * nrow];      // n > p: the index is >= 0
+  double z[NZ];
   {
-    const double yl = w[(L - 1) * nrow];
+    const double e0 = 2.0 * x0 - x[(int64_t)p * nrow];
 #pragma unroll
-    for (int k = 0; k < NZ; ++k) z[k] = c.zi[k] * yl;
+    for (int k = 0; k < NZ; ++k) z[k] = c.zi[k] * e0;
   }
-  for (int64_t j0 = L - 1; j0 >= 0; j0 -= UNR) {     // backward, in place
+  for (int64_t j0 = 0; j0 < L; j0 += UNR) {          // forward over the extended series, over its own input
     double v[UNR];
 #pragma unroll
-    for (int u = 0; u < UNR; ++u) v[u] = j0 - u >= 0 ? w[(j0 - u) * nrow] : 0.0;
+    for (int u = 0; u < UNR; ++u) {
+      const int64_t j = j0 + u;                      // uniform over the wavefront
+      if (j < p) v[u] = 2.0 * x0 - x[(p - j) * nrow];
+      else if (j < p + n) v[u] = x[(j - p) * nrow];
+      else if (j < L) v[u] = 2.0 * xl - tail[p - 1 - (j - p - n)][lane];       // x[n - 2 - (j - p - n)]
+      else v[u] = 0.0;
+    }
 #pragma unroll
     for (int u = 0; u < UNR; ++u)
-      if (j0 - u >= 0) w[(j0 - u) * nrow] = band_step(c, z, v[u]);
+      if (j0 + u < L) w[(j0 + u) * nrow] = band_step(c, z, v[u]);
+  }
+  band_backward(c, z, w, nrow, L);
+}
+
+__global__ __launch_bounds__(256) void k_band_trace(int64_t total, int64_t nframes, int ncomp, const int32_t* __restrict__ points,
+                                                    const double* __restrict__ src, int64_t xs, double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // (point, frame)
+  if (i >= total) return;
+  const double* x = src + (i % nframes) * xs + (int64_t)ncomp * points[i / nframes];
+  double* o = out + i * (1 + ncomp);
+  if (ncomp == 3) {
+    const double a = x[0], b = x[1], c = x[2];
+    o[0] = sqrt((a * a + b * b) + c * c);
+    o[1] = a; o[2] = b; o[3] = c;
+  } else {
+    o[0] = x[0];
+    o[1] = x[0];
   }
 }
 
@@ -174,8 +240,21 @@ void launch_band_sample(hipStream_t st, int64_t nrow, const double* U, const int
 }
 
 void launch_band_filter(hipStream_t st, int64_t nrow, int64_t nframes, int padlen, const BandCoef& c, const double* hist,
-                        double* work) {
-  if (nrow > 0) hipLaunchKernelGGL(k_band_filter, dim3((unsigned)((nrow + 63) / 64)), dim3(64), 0, st, nrow, nframes, padlen, c, hist, work);
+                        int64_t stride, double* work) {
+  if (nrow > 0)
+    hipLaunchKernelGGL(k_band_filter, dim3((unsigned)((nrow + 63) / 64)), dim3(64), 0, st, nrow, nframes, padlen, c, hist, stride * nrow, work);
+}
+
+void launch_band_filter_next(hipStream_t st, int64_t nrow, int64_t nframes, int padlen_prev, int padlen, const BandCoef& c, double* work) {
+  if (nrow > 0)
+    hipLaunchKernelGGL(k_band_filter_next, dim3((unsigned)((nrow + 63) / 64)), dim3(64), 0, st, nrow, nframes, padlen_prev, padlen, c, work);
+}
+
+void launch_band_trace(hipStream_t st, int64_t nrow, int ncomp, int64_t npoints, const int32_t* points, int64_t nframes,
+                       const double* src, int64_t stride, double* out) {
+  const int64_t total = npoints * nframes;
+  if (total > 0)
+    hipLaunchKernelGGL(k_band_trace, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, nframes, ncomp, points, src, stride * nrow, out);
 }
 
 void launch_band_rms(hipStream_t st, int64_t nrow, const double* y, int64_t start, int window, bool recompute, double* acc,

@@ -18,9 +18,17 @@ struct BandCoef {
 
 // hist[frame][row] <- the rows of the resident state: U[idx0[row]], or 0.5 * (U[idx0[row]] + U[idx1[row]]) where idx1 >= 0
 void launch_band_sample(hipStream_t st, int64_t nrow, const double* U, const int32_t* idx0, const int32_t* idx1, double* dst);
-// scipy.signal.filtfilt(b, a, hist[:, row]) of every row into work[padlen + frame][row]; work has nframes + 2 padlen frames
+// scipy.signal.filtfilt(b, a, hist[::stride, row]) of every row over nframes frames, the first at hist, into
+// work[padlen + frame][row]; work has nframes + 2 padlen frames
 void launch_band_filter(hipStream_t st, int64_t nrow, int64_t nframes, int padlen, const BandCoef& c, const double* hist,
-                        double* work);
+                        int64_t stride, double* work);
+// the same of the filtered series itself, in place: work[padlen_prev + frame][row] -> work[padlen + frame][row]; needs
+// padlen <= padlen_prev (the head of the extension is written below the series it is formed from)
+void launch_band_filter_next(hipStream_t st, int64_t nrow, int64_t nframes, int padlen_prev, int padlen, const BandCoef& c, double* work);
+// out[point][frame][1 + ncomp] = |.|, then the ncomp values of node points[point] in frame src[frame * stride][.]; a frame
+// is [nrow / ncomp][ncomp].  |.| = sqrt((x x + y y) + z z), for ncomp 1 the value itself
+void launch_band_trace(hipStream_t st, int64_t nrow, int ncomp, int64_t npoints, const int32_t* points, int64_t nframes,
+                       const double* src, int64_t stride, double* out);
 // amp[row] = sqrt(sum of y[start .. start + window - 1][row]^2 / window); the sum is recomputed (recompute) or advanced from
 // the window that started one frame earlier (acc)
 void launch_band_rms(hipStream_t st, int64_t nrow, const double* y, int64_t start, int window, bool recompute, double* acc,

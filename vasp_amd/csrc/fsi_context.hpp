@@ -423,12 +423,16 @@ struct FsiCtx {
     int ncomp = 0;
     int window = -1;                         // -1: no amplitude asked for; 0: the filtered series itself (low-pass); > 0: RMS window
     int64_t acc_start = -1;                  // window start the running sums stand at (-1: none)
+    // the view the filtered series, the amplitude and a trace are formed on (fsi_band_select): frames sel_first, sel_first +
+    // sel_stride, ..., sel_count of them; sel_count < 0: every recorded frame.  A raw fetch keeps absolute frame indices.
+    int64_t sel_first = 0, sel_stride = 1, sel_count = -1;
     fsi::DevBuf<double> acc, amp, mag, part_val;
     fsi::DevBuf<int64_t> part_idx;
     void release() {
       History::release();
       acc.release(); amp.release(); mag.release(); part_val.release(); part_idx.release();
       ncomp = 0; window = -1; acc_start = -1;
+      sel_first = 0; sel_stride = 1; sel_count = -1;
     }
   } band[3];
 

@@ -27,6 +27,8 @@ S* open_session(FsiCtx* ctx, S (&all)[3], int32_t q, const char* fn, const char*
 }
 FsiCtx::Band* band_session(FsiCtx* ctx, int32_t q, const char* fn) { return open_session(ctx, ctx->band, q, fn, "band-pass", "fsi_band_begin"); }
 FsiCtx::Spec* spec_session(FsiCtx* ctx, int32_t q, const char* fn) { return open_session(ctx, ctx->spec, q, fn, "spectrogram", "fsi_spec_begin"); }
+// frames of the band-pass session's view of its history (fsi_band_select): those the filtered series and the amplitude have
+int64_t band_frames(const FsiCtx::Band* s) { return s->sel_count < 0 ? s->frames : s->sel_count; }
 
 // The argument checks of a begin call and the solver indices of the entries it samples at n listed nodes: i0 / i1, i1 < 0
 // where an entry is one node's value and not the mean of two.  *mode (FSI_SPEC_*): one component of every node or, from
@@ -101,23 +103,34 @@ int history_sample(FsiCtx* ctx, FsiCtx::History* s, const char* fn, const char* 
   return FSI_OK;
 }
 
-// scipy.signal.filtfilt of every row over the frames recorded so far into work; ntaps_range: the counts the caller's message names
-int history_filter(FsiCtx* ctx, FsiCtx::History* s, const char* fn, const char* ntaps_range, int32_t ntaps, const double* b,
-                   const double* a, const double* zi, int32_t padlen) {
+// The checks of a filter call on a series of `frames` frames, and its coefficients as the kernels take them; ntaps_range: the
+// counts the caller's message names
+int filter_coef(FsiCtx* ctx, const char* fn, const char* ntaps_range, int32_t ntaps, const double* b, const double* a, const double* zi,
+                int32_t padlen, int64_t frames, BandCoef* c) {
   if (ntaps < 2 || ntaps > BAND_MAX_TAPS || !b || !a || !zi || padlen < 0 || padlen > BAND_MAX_PADLEN) {
     ctx->err = std::string(fn) + ": needs " + ntaps_range + " coefficients b, a, their zi and 0 <= padlen <= 33";
     return FSI_ERR_INVALID;
   }
   if (a[0] != 1.0) { ctx->err = std::string(fn) + ": a[0] must be 1 (normalised coefficients, as scipy.signal.butter returns them)"; return FSI_ERR_INVALID; }
-  if (s->frames <= padlen) {      // scipy: "The length of the input vector x must be greater than padlen"
-    ctx->err = std::string(fn) + ": " + std::to_string(s->frames) + " recorded frames, the filter needs more than padlen = " + std::to_string(padlen);
+  if (frames <= padlen) {      // scipy: "The length of the input vector x must be greater than padlen"
+    ctx->err = std::string(fn) + ": " + std::to_string(frames) + " recorded frames, the filter needs more than padlen = " + std::to_string(padlen);
     return FSI_ERR_INVALID;
   }
-  BandCoef c{};
-  for (int k = 0; k < ntaps; ++k) { c.b[k] = b[k]; c.a[k] = a[k]; }
-  for (int k = 0; k < ntaps - 1; ++k) c.zi[k] = zi[k];
+  *c = BandCoef{};
+  for (int k = 0; k < ntaps; ++k) { c->b[k] = b[k]; c->a[k] = a[k]; }
+  for (int k = 0; k < ntaps - 1; ++k) c->zi[k] = zi[k];
+  return FSI_OK;
+}
+
+// scipy.signal.filtfilt of every row into work, over the frames recorded so far or, with count >= 0, over the count frames
+// first, first + stride, ... of them
+int history_filter(FsiCtx* ctx, FsiCtx::History* s, const char* fn, const char* ntaps_range, int32_t ntaps, const double* b,
+                   const double* a, const double* zi, int32_t padlen, int64_t first = 0, int64_t stride = 1, int64_t count = -1) {
+  const int64_t frames = count < 0 ? s->frames : count;
+  BandCoef c;
+  FSICHK(filter_coef(ctx, fn, ntaps_range, ntaps, b, a, zi, padlen, frames, &c));
   HIPCHK(hipSetDevice(ctx->device));
-  launch_band_filter(ctx->stream, s->nrow, s->frames, padlen, c, s->hist.p, s->work.p);
+  launch_band_filter(ctx->stream, s->nrow, frames, padlen, c, s->hist.p + (size_t)first * s->nrow, stride, s->work.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));
   s->padlen = padlen;
@@ -449,6 +462,26 @@ int fsi_band_sample(FsiCtx* ctx, int32_t quantity) {
   if (!s) return FSI_ERR_INVALID;
   FSICHK(history_sample(ctx, s, "fsi_band_sample", "fsi_band_begin"));
   s->window = -1;
+  s->sel_first = 0; s->sel_stride = 1; s->sel_count = -1;      // a selection covers the frames it was made on
+  return FSI_OK;
+}
+
+int fsi_band_select(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count, int64_t stride) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_select");
+  if (!s) return FSI_ERR_INVALID;
+  const bool fits = stride >= 1 && first >= 0 && first < s->frames && (count == -1 || (count >= 1 && count - 1 <= (s->frames - 1 - first) / stride));
+  if (!fits) {
+    ctx->err = "fsi_band_select: needs stride >= 1, first >= 0, count >= 1 or -1 and first + (count - 1) * stride < the " +
+               std::to_string(s->frames) + " recorded frames";
+    return FSI_ERR_INVALID;
+  }
+  s->sel_first = first;
+  s->sel_stride = stride;
+  s->sel_count = count == -1 ? (s->frames - 1 - first) / stride + 1 : count;
+  s->filtered = false;
+  s->window = -1;
+  s->acc_start = -1;
   return FSI_OK;
 }
 
@@ -456,7 +489,29 @@ int fsi_band_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* 
   if (!ctx) return FSI_ERR_INVALID;
   auto* s = band_session(ctx, quantity, "fsi_band_filter");
   if (!s) return FSI_ERR_INVALID;
-  FSICHK(history_filter(ctx, s, "fsi_band_filter", "2 .. 11", ntaps, b, a, zi, padlen));
+  FSICHK(history_filter(ctx, s, "fsi_band_filter", "2 .. 11", ntaps, b, a, zi, padlen, s->sel_first, s->sel_stride, band_frames(s)));
+  s->window = -1;
+  s->acc_start = -1;
+  return FSI_OK;
+}
+
+int fsi_band_filter_next(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* b, const double* a, const double* zi, int32_t padlen) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_filter_next");
+  if (!s) return FSI_ERR_INVALID;
+  BandCoef c;
+  FSICHK(filter_coef(ctx, "fsi_band_filter_next", "2 .. 11", ntaps, b, a, zi, padlen, band_frames(s), &c));
+  if (!s->filtered) { ctx->err = "fsi_band_filter_next: no filtered series (fsi_band_filter first)"; return FSI_ERR_INVALID; }
+  if (padlen > s->padlen) {     // the stage works inside work: its extension may not reach into the series it is formed from
+    ctx->err = "fsi_band_filter_next: padlen = " + std::to_string(padlen) + " after a stage of padlen = " + std::to_string(s->padlen) +
+               ": a stage's padlen may not exceed the previous one's (put the longer filter first)";
+    return FSI_ERR_INVALID;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  launch_band_filter_next(ctx->stream, s->nrow, band_frames(s), s->padlen, padlen, c, s->work.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  s->padlen = padlen;
   s->window = -1;
   s->acc_start = -1;
   return FSI_OK;
@@ -467,8 +522,8 @@ int fsi_band_amplitude(FsiCtx* ctx, int32_t quantity, int32_t window) {
   auto* s = band_session(ctx, quantity, "fsi_band_amplitude");
   if (!s) return FSI_ERR_INVALID;
   if (!s->filtered) { ctx->err = "fsi_band_amplitude: no filtered series (fsi_band_filter first)"; return FSI_ERR_INVALID; }
-  if (window < 0 || window > s->frames) {
-    ctx->err = "fsi_band_amplitude: window of " + std::to_string(window) + " frames, the series has " + std::to_string(s->frames);
+  if (window < 0 || window > band_frames(s)) {
+    ctx->err = "fsi_band_amplitude: window of " + std::to_string(window) + " frames, the series has " + std::to_string(band_frames(s));
     return FSI_ERR_INVALID;
   }
   s->window = window;
@@ -482,7 +537,8 @@ int fsi_band_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, d
   if (!s) return FSI_ERR_INVALID;
   if (what < FSI_BAND_RAW || what > FSI_BAND_MAGNITUDE) { ctx->err = "fsi_band_fetch: what must be FSI_BAND_RAW .. FSI_BAND_MAGNITUDE"; return FSI_ERR_INVALID; }
   if (what != FSI_BAND_RAW && !s->filtered) { ctx->err = "fsi_band_fetch: no filtered series (fsi_band_filter first)"; return FSI_ERR_INVALID; }
-  if (frame < 0 || frame >= s->frames) { ctx->err = "fsi_band_fetch: frame out of range"; return FSI_ERR_INVALID; }
+  // a raw frame keeps its index in the history; the filtered series and the amplitude have the selected frames
+  if (frame < 0 || frame >= (what == FSI_BAND_RAW ? s->frames : band_frames(s))) { ctx->err = "fsi_band_fetch: frame out of range"; return FSI_ERR_INVALID; }
   if (what >= FSI_BAND_AMPLITUDE && s->window < 0) { ctx->err = "fsi_band_fetch: no amplitude (fsi_band_amplitude first)"; return FSI_ERR_INVALID; }
   HIPCHK(hipSetDevice(ctx->device));
   const double* src = nullptr;
@@ -492,7 +548,7 @@ int fsi_band_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, d
     // calculate_windowed_rms: RMS[i - pad] for pad <= i < pad + n - w + 1 with pad = (n - len_RMS) // 2, zero outside.  The
     // value of a frame does not depend on the order of the fetches: window `start` is recomputed when start is a multiple of
     // BAND_RMS_REFRESH and advanced from start - 1 otherwise.
-    const int64_t w = s->window, n = s->frames, start = frame - (w - 1) / 2;
+    const int64_t w = s->window, n = band_frames(s), start = frame - (w - 1) / 2;
     if (start < 0 || start + w > n) {
       HIPCHK(hipMemsetAsync(s->amp.p, 0, (size_t)s->nrow * sizeof(double), ctx->stream));
     } else {
@@ -516,6 +572,35 @@ int fsi_band_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, d
     if (what == FSI_BAND_MAGNITUDE) src = s->mag.p;
   }
   if (out) HIPCHK(hipMemcpyAsync(out, src, (size_t)(what == FSI_BAND_MAGNITUDE ? s->nnode : s->nrow) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return FSI_OK;
+}
+
+int fsi_band_trace(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t npoints, const int32_t* points, double* out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_trace");
+  if (!s) return FSI_ERR_INVALID;
+  if (what != FSI_BAND_RAW && what != FSI_BAND_FILTERED) { ctx->err = "fsi_band_trace: what must be FSI_BAND_RAW or FSI_BAND_FILTERED"; return FSI_ERR_INVALID; }
+  if (npoints <= 0 || !points || !out) { ctx->err = "fsi_band_trace: needs npoints > 0 points and an output"; return FSI_ERR_INVALID; }
+  if (what == FSI_BAND_FILTERED && !s->filtered) { ctx->err = "fsi_band_trace: no filtered series (fsi_band_filter first)"; return FSI_ERR_INVALID; }
+  for (int64_t i = 0; i < npoints; ++i)
+    if (points[i] < 0 || points[i] >= s->nnode) { ctx->err = "fsi_band_trace: node out of range"; return FSI_ERR_INVALID; }
+  const int64_t frames = band_frames(s);
+  if (frames < 1) { ctx->err = "fsi_band_trace: no recorded frames"; return FSI_ERR_INVALID; }
+  const size_t nout = (size_t)npoints * (size_t)frames * (size_t)(1 + s->ncomp);
+  HIPCHK(hipSetDevice(ctx->device));
+  DevBuf<int32_t> pts;          // live for this call
+  DevBuf<double> res;
+  HIPCHK(pts.alloc((size_t)npoints));
+  HIPCHK(res.alloc(nout));
+  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
+  HIPCHK(hipMemcpyAsync(pts.p, points, (size_t)npoints * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  if (what == FSI_BAND_RAW)
+    launch_band_trace(ctx->stream, s->nrow, s->ncomp, npoints, pts.p, frames, s->hist.p + (size_t)s->sel_first * s->nrow, s->sel_stride, res.p);
+  else
+    launch_band_trace(ctx->stream, s->nrow, s->ncomp, npoints, pts.p, frames, history_frame(s, true, 0), 1, res.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, res.p, nout * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return FSI_OK;
 }

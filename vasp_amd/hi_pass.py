@@ -10,9 +10,13 @@ This module holds
   scaled by the first / last sample) and the reference's windowed RMS - vectorised over rows.  Every operation is an
   element-wise IEEE operation in scipy's order, so a row's result equals ``scipy.signal.filtfilt`` bit for bit.  It is the
   path of a backend without the device session (``HostBandSession``) and the yardstick of the GPU tests;
-* the writer of the reference's files and the driver's side of ``--hi-pass`` (``HiPassRun``).
+* the writer of the reference's files and the driver's side of ``--hi-pass`` (``HiPassRun``): one series per band, with
+  ``--hi-pass-multiband`` one more that went through all bands in order, each passed or stopped
+  [REF create_hi_pass_viz.py:532-545,191-198,651-657]; a frame window and stride (``--hi-pass-stride``,
+  ``--hi-pass-start-time``, ``--hi-pass-end-time``); the raw series of listed nodes (``--hi-pass-point-ids``).
 
-Not done: the reference's ``strain`` / ``stress`` quantities, its ``multiband`` mode, ``--stride`` and the point traces.
+What a filter stage and a trace cost on a mesh of the benchmark's size has not been measured.
+Not done: the reference's ``strain`` / ``stress`` quantities.
 """
 from __future__ import annotations
 
@@ -50,17 +54,35 @@ def band_parameters(time_between_files: float, lowcut: float, highcut: float) ->
                 name=name)
 
 
-def design(time_between_files: float, lowcut: float, highcut: float) -> dict:
+def stage_refusal(time_between_files: float, lowcut: float, highcut: float) -> str:
+    """Why a band cannot be a stage of a multiband cascade ('' if it can).  There the reference hands the band to scipy as it
+    is [REF create_hi_pass_viz.py:193-198] - ``highcut`` is not clipped - and scipy raises unless 0 < Wn < 1."""
+    nyq = 0.5 * (int(1 / time_between_files) - 1)
+    if 0.0 < lowcut < highcut < nyq:
+        return ""
+    return (f"--hi-pass-multiband: band {lowcut:g} - {highcut:g} Hz cannot be a stage, it needs 0 < lower < upper < fs / 2 = "
+            f"{nyq:g} Hz (a stage's upper frequency is not clipped)")
+
+
+def design(time_between_files: float, lowcut: float, highcut: float, btype: Optional[str] = None) -> dict:
     """``band_parameters`` plus b, a [REF spectrograms.py:516-529], ``zi = lfilter_zi(b, a)`` and filtfilt's default
-    ``padlen = 3 max(len(a), len(b))``."""
+    ``padlen = 3 max(len(a), len(b))``.  ``btype`` "bandstop" or "bandpass": a stage of a multiband cascade - the band as it
+    is (``highcut`` not clipped, no low-pass below 0.1 Hz), stopped [REF spectrograms.py:522-523] or passed (:528-529)."""
     from scipy.signal import butter, lfilter_zi
     prm = band_parameters(time_between_files, lowcut, highcut)
     nyq = 0.5 * prm["fs"]
+    if btype is not None:
+        if btype not in ("bandstop", "bandpass"):
+            raise ValueError(f"btype must be None, 'bandstop' or 'bandpass', got {btype!r}")
+        why = stage_refusal(time_between_files, lowcut, highcut)
+        if why:
+            raise ValueError(why)
+        prm.update(highcut=highcut, btype=btype)
     low, high = prm["lowcut"] / nyq, prm["highcut"] / nyq
     if prm["btype"] == "lowpass":
         b, a = butter(ORDER, high, btype="lowpass")
     else:
-        b, a = butter(ORDER, [low, high], btype="bandpass")
+        b, a = butter(ORDER, [low, high], btype=prm["btype"])
     prm.update(b=np.asarray(b, dtype=np.float64), a=np.asarray(a, dtype=np.float64), zi=np.asarray(lfilter_zi(b, a)),
                padlen=3 * max(len(a), len(b)))
     return prm
@@ -168,6 +190,27 @@ def amplitude_magnitude(amp: np.ndarray) -> np.ndarray:
     return np.sqrt((amp[:, 0] * amp[:, 0] + amp[:, 1] * amp[:, 1]) + amp[:, 2] * amp[:, 2])
 
 
+def pass_stop_list(band_list, words=None) -> List[str]:
+    """"pass" or "stop" per band of a multiband cascade: the reference's rule - a band wider than 1000 Hz passes, a narrower
+    one is stopped [REF create_hi_pass_viz.py:541-545] - or the words given (``--hi-pass-pass-stop``)."""
+    if words is None:
+        return ["pass" if hi - lo > 1000 else "stop" for lo, hi in band_list]
+    words = [words] if isinstance(words, str) else [str(w) for w in words]
+    if len(words) != len(band_list):
+        raise SystemExit(f"--hi-pass-pass-stop takes one word per band: {len(words)} words for {len(band_list)} bands")
+    bad = [w for w in words if w not in ("pass", "stop")]
+    if bad:
+        raise SystemExit(f"--hi-pass-pass-stop takes the words pass and stop, got {bad}")
+    return words
+
+
+def multiband_name(viz_type: str, band_list, words) -> str:
+    """The reference's chained file name [REF create_hi_pass_viz.py:102-103]."""
+    for (lo, hi), word in zip(band_list, words):
+        viz_type = f"{viz_type}_{word}_{int(np.rint(lo))}_to_{int(np.rint(hi))}"
+    return viz_type
+
+
 class HostHistory:
     """The recording half of a host session: the raw frames, up to the capacity declared at begin, and their filtfilt."""
     what = ""
@@ -197,15 +240,47 @@ class HostBandSession(HostHistory):
 
     def __init__(self, ncomp: int, capacity: int):
         super().__init__((-1, ncomp), capacity)
-        self.ncomp, self.amp = ncomp, None
+        self.ncomp, self.amp, self.view = ncomp, None, slice(None)
 
     def sample(self, frame: np.ndarray) -> None:
         super().sample(frame)
-        self.amp = None
+        self.amp, self.view = None, slice(None)
+
+    def selected(self) -> np.ndarray:
+        return np.stack(self.raw)[self.view]
+
+    def select(self, first: int = 0, count: int = -1, stride: int = 1) -> int:
+        frames = len(self.raw)
+        fits = stride >= 1 and 0 <= first < frames and (count == -1 or (count >= 1 and first + (count - 1) * stride < frames))
+        if not fits:
+            raise RuntimeError(f"hi-pass select: needs stride >= 1, first >= 0, count >= 1 or -1 and first + (count - 1) * stride "
+                               f"< the {frames} recorded frames")
+        count = (frames - 1 - first) // stride + 1 if count == -1 else count
+        self.view = slice(first, first + (count - 1) * stride + 1, stride)
+        self.filtered = self.amp = None
+        return count
 
     def filter(self, b, a, zi, padlen: int) -> None:
-        super().filter(b, a, zi, padlen)
+        self.filtered = filtfilt_rows(b, a, self.selected(), zi, padlen)
         self.amp = None
+
+    def filter_next(self, b, a, zi, padlen: int) -> None:
+        if self.filtered is None:
+            raise RuntimeError("hi-pass filter_next: no filtered series (filter first)")
+        self.filtered = filtfilt_rows(b, a, self.filtered, zi, padlen)
+        self.amp = None
+
+    def trace(self, what: str, points) -> np.ndarray:
+        """(points, frames, 1 + ncomp): the magnitude, then the row of each listed node over the selected frames."""
+        if what == "filtered" and self.filtered is None:
+            raise RuntimeError("hi-pass trace: no filtered series (filter first)")
+        x = self.selected() if what == "raw" else self.filtered
+        pts = np.asarray(points, dtype=np.int64).reshape(-1)
+        if len(pts) and (pts.min() < 0 or pts.max() >= x.shape[1]):
+            raise RuntimeError("hi-pass trace: node out of range")
+        rows = x[:, pts].transpose(1, 0, 2)
+        mag = np.stack([amplitude_magnitude(r) for r in rows])
+        return np.concatenate([mag[:, :, None], rows], axis=2)
 
     def amplitude(self, window: int) -> None:
         self.amp = self.filtered if window == 0 else windowed_rms_running(self.filtered, window)
@@ -368,16 +443,65 @@ def bands(v: dict) -> List[Tuple[float, float]]:
     return [(float(flat[2 * i]), float(flat[2 * i + 1])) for i in range(len(flat) // 2)]
 
 
-def expected_frames(v: dict) -> int:
-    """Frames the time loop of ``monolithic`` saves with these parameters (``while t <= T + dt / 10``, a frame when
-    ``counter % save_step == 0``)."""
+def saved_times(v: dict) -> List[float]:
+    """The times of the frames the time loop of ``monolithic`` saves with these parameters (``while t <= T + dt / 10``, a
+    frame when ``counter % save_step == 0``)."""
     dt, T, step = float(v["dt"]), float(v["T"]), int(v["save_step"])
-    t, counter, n = float(v.get("t", 0.0)), int(v.get("counter", 0)), 0
+    t, counter, times = float(v.get("t", 0.0)), int(v.get("counter", 0)), []
     while t <= T + dt / 10:
         t += dt
-        n += counter % step == 0
+        if counter % step == 0:
+            times.append(t)
         counter += 1
-    return n
+    return times
+
+
+def expected_frames(v: dict) -> int:
+    """Frames the time loop saves with these parameters."""
+    return len(saved_times(v))
+
+
+def multiband(v: dict) -> List[str]:
+    """[] without ``--hi-pass-multiband``, else "pass" / "stop" per band of ``--hi-pass-bands``.  Fewer than two bands are
+    refused, as the reference asserts [REF create_hi_pass_viz.py:100-101]."""
+    if not v.get("hi_pass_multiband"):
+        if v.get("hi_pass_pass_stop") is not None:
+            raise SystemExit("--hi-pass-pass-stop belongs to --hi-pass-multiband")
+        return []
+    band_list = bands(v)
+    if len(band_list) < 2:
+        raise SystemExit(f"--hi-pass-multiband needs at least two bands in --hi-pass-bands, got {len(band_list)}")
+    return pass_stop_list(band_list, v.get("hi_pass_pass_stop"))
+
+
+def point_ids(v: dict) -> List[int]:
+    ids = v.get("hi_pass_point_ids")
+    ids = [] if ids is None else list(np.atleast_1d(ids))
+    bad = [i for i in ids if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or i < 0]
+    if bad:
+        raise SystemExit(f"--hi-pass-point-ids takes indices >= 0 into the written nodes, got {bad}")
+    return [int(i) for i in ids]
+
+
+def frame_window(v: dict) -> Tuple[int, float, Optional[float]]:
+    """(stride, start time, end time or None) of ``--hi-pass-stride``, ``--hi-pass-start-time``, ``--hi-pass-end-time``."""
+    stride = v.get("hi_pass_stride")
+    stride = 1 if stride is None else stride
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
+        raise SystemExit(f"--hi-pass-stride must be an integer >= 1, got {stride!r}")
+    t0, t1 = v.get("hi_pass_start_time"), v.get("hi_pass_end_time")
+    t0 = 0.0 if t0 is None else float(t0)
+    t1 = None if t1 is None else float(t1)
+    if t0 < 0.0 or (t1 is not None and t1 < t0):
+        raise SystemExit(f"--hi-pass-start-time / --hi-pass-end-time: need 0 <= start <= end, got {t0:g} and {t1}")
+    return int(stride), t0, t1
+
+
+def select_frames(times, dt: float, stride: int, t0: float, t1: Optional[float]) -> Tuple[int, int]:
+    """(first, count) of the saved frames k with ``k % stride == 0`` and ``t0 <= t_k <= t1`` (t1 None: no upper limit; the
+    comparisons allow dt / 10, as the time loop's own does): frames first, first + stride, ..."""
+    keep = [k for k in range(0, len(times), stride) if times[k] >= t0 - dt / 10 and (t1 is None or times[k] <= t1 + dt / 10)]
+    return (keep[0], len(keep)) if keep else (0, 0)
 
 
 def hi_pass_refusal(v: dict, world: int, backend_cls) -> str:
@@ -389,16 +513,28 @@ def hi_pass_refusal(v: dict, world: int, backend_cls) -> str:
         return "--hi-pass does not carry its history through a checkpoint: it cannot be used with --restart-folder"
     if world > 1:
         return "--hi-pass runs on one rank only (WORLD_SIZE > 1)"
-    frames = expected_frames(v)
+    stride, t0, t1 = frame_window(v)
+    words, _ = multiband(v), point_ids(v)
+    whole = stride == 1 and t0 == 0.0 and t1 is None
+    frames = select_frames(saved_times(v), float(v["dt"]), stride, t0, t1)[1]
+    saves = f"saves {frames} frames" if whole else f"saves {frames} frames in the window and stride asked for"
     for lo, hi in bands(v):
         if frames < padlen_of(lo) + 1:
-            return (f"--hi-pass: the run saves {frames} frames, the filter of band {lo:g} - {hi:g} Hz needs at least "
+            return (f"--hi-pass: the run {saves}, the filter of band {lo:g} - {hi:g} Hz needs at least "
                     f"padlen + 1 = {padlen_of(lo) + 1}")
+    if words:
+        dt_files = float(v["dt"]) * int(v["save_step"]) * stride
+        for lo, hi in bands(v):
+            why = stage_refusal(dt_files, lo, hi)
+            if why:
+                return why
+        if frames < 3 * (2 * ORDER + 1) + 1:        # a stage is a band-pass or band-stop: 11 coefficients whatever the band
+            return f"--hi-pass-multiband: the run {saves}, a stage needs at least padlen + 1 = {3 * (2 * ORDER + 1) + 1}"
     window = int(v.get("hi_pass_window") or 250)
     if window < 1:
         return "--hi-pass-window must be at least 1"
     if v.get("hi_pass_amplitude") and frames < window:
-        return f"--hi-pass-amplitude: the run saves {frames} frames, fewer than the window of {window} (--hi-pass-window)"
+        return f"--hi-pass-amplitude: the run {saves}, fewer than the window of {window} (--hi-pass-window)"
     return ""
 
 
@@ -415,11 +551,18 @@ def output_nodes(mesh: FsiMesh, save_deg: int, quantity: str):
             np.concatenate([np.full(V, -1), e[:, 1]]).astype(np.int32))
 
 
+TRACE_HEADER = {1: "time (s), Magnitude", 3: "time (s), Magnitude, X Component, Y Component, Z Component"}      # [REF postprocessing_h5py_common.py:482]
+
+
 class HiPassRun(SessionRun):
     """The driver's side of ``--hi-pass``: one session per quantity on the Visualization writer's nodes, one recorded frame
-    per saved frame, and at the end per band the filtered series, with ``--hi-pass-amplitude`` its amplitude and table.
-    Times in the files are ``k * time_between_files + 0.0``, the reference's default start time; ``time_between_files`` is
-    dt * save_step, the spacing of the frames (the reference takes dt * stride and notes the doubt, :621-634)."""
+    per saved frame, and at the end per band the filtered series, with ``--hi-pass-amplitude`` its amplitude and table; with
+    ``--hi-pass-multiband`` one more series that went through all bands in order; with ``--hi-pass-point-ids`` the recorded
+    series of those nodes.  All of it on the saved frames k with ``k % stride == 0`` and ``T0 <= t_k <= T1``
+    (``--hi-pass-stride``, ``--hi-pass-start-time``, ``--hi-pass-end-time``; every selected frame is kept, where the reference
+    drops the last ones, postprocessing_h5py_common.py:285,307).  Times in the files are ``T0 + k * time_between_files``, T0
+    being the reference's ``start_t``; ``time_between_files`` is dt * save_step * stride, the spacing of the selected frames
+    (the reference takes dt * stride and notes the doubt, :621-634)."""
     prefix = "hi_pass"
 
     def __init__(self, backend, mesh: FsiMesh, ns: dict):
@@ -428,16 +571,31 @@ class HiPassRun(SessionRun):
         self.save_deg = int(ns["save_deg"])
         self.quantities = quantities(ns)
         self.bands = bands(ns)
+        self.pass_stop = multiband(ns)
+        self.point_ids = point_ids(ns)
+        self.stride, self.t0, self.t1 = frame_window(ns)
         self.amplitude = bool(ns.get("hi_pass_amplitude"))
         self.window = int(ns.get("hi_pass_window") or 250)
-        self.dt_files = float(ns["dt"]) * int(ns["save_step"])
+        self.dt = float(ns["dt"])
+        self.dt_files = self.dt * int(ns["save_step"]) * self.stride
+        self.times: List[float] = []
         if self.save_deg >= 2:
             geometry, topology = mesh.node_coords, refine_topology(mesh)
         else:
             geometry, topology = mesh.coords, mesh.tets
+        for q in self.quantities:
+            n = len(output_nodes(mesh, self.save_deg, q)[0])
+            bad = [i for i in self.point_ids if i >= n]
+            if bad:
+                raise SystemExit(f"--hi-pass-point-ids: {bad} out of range, {VIZ_TYPE[q]} is written on {n} nodes")
         self.writer = HiPassWriter(Path(ns["results_folder"]) / "Visualization_hi_pass", geometry, topology)
+        self.trace_folder = Path(ns["results_folder"]) / "Visualization_separate_domain"      # [REF create_hi_pass_viz.py:565,639]
         self.open_sessions(backend, ns, lambda q: output_nodes(mesh, self.save_deg, q),
                            lambda q, capacity: HostBandSession(1 if q == "p" else 3, capacity))
+
+    def sample(self, t: float, state) -> None:
+        super().sample(t, state)
+        self.times.append(float(t))
 
     def _host_frame(self, q: str, state: np.ndarray) -> np.ndarray:
         d, v, p = self.mesh.split(state)
@@ -450,10 +608,48 @@ class HiPassRun(SessionRun):
         f = d if q == "d" else v
         return f if self.save_deg >= 2 else f[:V]
 
+    def _write_filtered(self, out, session, viz: str, n: int, ncomp: int, rms: bool) -> None:
+        """The session's filtered series as ``viz`` and, with --hi-pass-amplitude, its amplitude (the windowed RMS, or for
+        ``rms`` False - the reference's low-pass case - the series itself) and table."""
+        self.writer.write_series(viz, (session.fetch("filtered", k) for k in range(n)), n, ncomp, self.dt_files, self.t0)
+        if not self.amplitude:
+            return
+        if rms and n < self.window:
+            out(f"Hi-pass {viz}: {n} frames recorded, fewer than the window of {self.window}: no amplitude written")
+            return
+        session.amplitude(self.window if rms else 0)
+        table = np.empty((n, 13))
+
+        def amp_frames():
+            for k in range(n):
+                amp, mx, am = session.fetch("amplitude", k, True)
+                table[k] = amplitude_row(k * self.dt_files + self.t0, amplitude_magnitude(amp), mx, am)
+                yield amp
+
+        self.writer.write_series(f"{viz}_amplitude", amp_frames(), n, ncomp, self.dt_files, self.t0)
+        self.writer.write_table(viz, table)
+
+    def _write_traces(self, session, q: str, n: int) -> None:
+        """``<viz_type>_point_id_<id>.csv``: time, magnitude and components of the recorded rows of each listed node
+        [REF postprocessing_h5py_common.py:470-483], the times being T0 + k * time_between_files, one per frame."""
+        self.trace_folder.mkdir(parents=True, exist_ok=True)
+        trace = np.asarray(session.trace("raw", self.point_ids))
+        for i, rows in zip(self.point_ids, trace):
+            data = np.empty((n, rows.shape[1] + 1 if q != "p" else 2))
+            data[:, 0] = self.t0 + np.arange(n) * self.dt_files
+            data[:, 1:] = rows if q != "p" else rows[:, :1]
+            np.savetxt(self.trace_folder / f"{VIZ_TYPE[q]}_point_id_{i}.csv", data, delimiter=",", header=TRACE_HEADER[1 if q == "p" else 3])
+
     def write(self, out) -> None:
-        n = self.frames
+        first, n = select_frames(self.times, self.dt, self.stride, self.t0, self.t1)
+        if n == 0:
+            out(f"Hi-pass: none of the {self.frames} recorded frames lies in the window and stride asked for: nothing written")
+            return
         for q, session in self.sessions.items():
             ncomp = 1 if q == "p" else 3
+            session.select(first, n, self.stride)
+            if self.point_ids:
+                self._write_traces(session, q, n)
             for lo, hi in self.bands:
                 prm = design(self.dt_files, lo, hi)
                 viz = f"{VIZ_TYPE[q]}_{prm['name']}"
@@ -461,22 +657,18 @@ class HiPassRun(SessionRun):
                     out(f"Hi-pass {viz}: {n} frames recorded, the filter needs more than {prm['padlen']}: nothing written")
                     continue
                 session.filter(prm["b"], prm["a"], prm["zi"], prm["padlen"])
-                self.writer.write_series(viz, (session.fetch("filtered", k) for k in range(n)), n, ncomp, self.dt_files, 0.0)
-                if not self.amplitude:
-                    continue
-                lowpass = prm["btype"] == "lowpass"
-                if not lowpass and n < self.window:
-                    out(f"Hi-pass {viz}: {n} frames recorded, fewer than the window of {self.window}: no amplitude written")
-                    continue
-                session.amplitude(0 if lowpass else self.window)
-                table = np.empty((n, 13))
-
-                def amp_frames():
-                    for k in range(n):
-                        amp, mx, am = session.fetch("amplitude", k, True)
-                        table[k] = amplitude_row(k * self.dt_files + 0.0, amplitude_magnitude(amp), mx, am)
-                        yield amp
-
-                self.writer.write_series(f"{viz}_amplitude", amp_frames(), n, ncomp, self.dt_files, 0.0)
-                self.writer.write_table(viz, table)
+                self._write_filtered(out, session, viz, n, ncomp, prm["btype"] != "lowpass")
+            if not self.pass_stop:
+                continue
+            # the recorded rows through all bands in order [REF create_hi_pass_viz.py:191-198].  Its amplitude is the windowed
+            # RMS, as a band-pass's: the reference itself raises NameError here (filter_type_single is undefined, :222)
+            viz = multiband_name(VIZ_TYPE[q], self.bands, self.pass_stop)
+            stages = [design(self.dt_files, lo, hi, "bandpass" if word == "pass" else "bandstop")
+                      for (lo, hi), word in zip(self.bands, self.pass_stop)]
+            if n <= max(prm["padlen"] for prm in stages):
+                out(f"Hi-pass {viz}: {n} frames recorded, the filter needs more than {max(prm['padlen'] for prm in stages)}: nothing written")
+                continue
+            for k, prm in enumerate(stages):
+                (session.filter_next if k else session.filter)(prm["b"], prm["a"], prm["zi"], prm["padlen"])
+            self._write_filtered(out, session, viz, n, ncomp, True)
         out(f"Hi-pass fields of {n} frames ({', '.join(self.quantities)}) written to {self.writer.folder}")

@@ -82,6 +82,20 @@ def parse(argv: Optional[List[str]] = None) -> Dict[str, object]:
                     help="frames of the RMS window of --hi-pass-amplitude (default: 250)")
     ap.add_argument("--hi-pass-amplitude", dest="hi_pass_amplitude", action="store_const", const=True, default=None,
                     help="also write the windowed RMS amplitude of every filtered series and its table of percentiles")
+    ap.add_argument("--hi-pass-multiband", dest="hi_pass_multiband", action="store_const", const=True, default=None,
+                    help="also write one series per quantity that went through all bands of --hi-pass-bands in order, each "
+                         "passed (wider than 1000 Hz) or stopped")
+    ap.add_argument("--hi-pass-pass-stop", dest="hi_pass_pass_stop", nargs="+", default=None, metavar="WORD",
+                    help="pass or stop, one word per band of --hi-pass-multiband, instead of the 1000 Hz rule")
+    ap.add_argument("--hi-pass-stride", dest="hi_pass_stride", type=int, default=None,
+                    help="form every --hi-pass output on every S-th saved frame (default: 1)")
+    ap.add_argument("--hi-pass-start-time", dest="hi_pass_start_time", type=float, default=None,
+                    help="first time of the --hi-pass outputs, and the time their files start at (default: 0)")
+    ap.add_argument("--hi-pass-end-time", dest="hi_pass_end_time", type=float, default=None,
+                    help="last time of the --hi-pass outputs (default: the last saved frame)")
+    ap.add_argument("--hi-pass-point-ids", dest="hi_pass_point_ids", nargs="+", type=_coerce, default=None, metavar="ID",
+                    help="write the recorded series of these nodes (indices into the nodes of the Visualization files) to "
+                         "<results>/Visualization_separate_domain/<field>_point_id_<ID>.csv")
     from .spectrogram import add_arguments as add_spectrogram_arguments
     add_spectrogram_arguments(ap, _coerce)
     ap.add_argument("-c", "--config", dest="config", default=None,
