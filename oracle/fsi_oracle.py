@@ -139,11 +139,20 @@ class FsiOracle:
       robin_facets (nr,6), robin_k (nr,), robin_c (nr,)  (optional),
       bc_dofs (nb,) unique Dirichlet dofs (list order already resolved: later BC wins).
     Global dof layout: [d: 3*N2 | v: 3*N2 | p: V], component-minor.
+
+    ``dtype=np.longdouble`` evaluates the element routines in extended precision (numpy only; complex step in
+    ``np.clongdouble``, step 1e-40) from the same FP64 inputs: the tables and coordinates are the FP64 ones, promoted.
+    ``geom`` (C,10) gives the per-cell geometry as data instead of deriving it from the coordinates: Jinv[k][j] =
+    d xi_k / d x_j row-major (9) and |det| (1), the layout of the HIP kernels' ``geom`` array.  Both serve the
+    kernel tests (tests/kernel_shim.py), which judge a kernel against a reference that starts from identical inputs.
     """
 
-    def __init__(self, desc, impl: str = "auto"):
+    def __init__(self, desc, impl: str = "auto", dtype=np.float64, geom=None):
         self.D = desc
-        self.x = np.asarray(desc["coords"], dtype=float)
+        self.dtype = dtype = np.dtype(dtype).type
+        self.cdtype = np.result_type(dtype, np.complex128).type
+        self.cstep = 1e-30 if dtype is np.float64 else 1e-40
+        self.x = np.asarray(desc["coords"], dtype=dtype)
         self.tets = np.asarray(desc["tets"])
         self.tn = np.asarray(desc["tet_nodes"])
         self.N2 = int(desc["num_nodes"])
@@ -156,9 +165,15 @@ class FsiOracle:
         # quadrature + tabulation -------------------------------------------------------------
         self.qp, self.qw = keast24()
         self.N, self.dNref, self.L, self.dL = tabulate_p2(self.qp)
-        xc = self.x[self.tets]                                          # (C,4,3)
-        Jm = np.stack([xc[:, 1] - xc[:, 0], xc[:, 2] - xc[:, 0], xc[:, 3] - xc[:, 0]], axis=2)  # dx/dxi
-        Jinv, det = _inv3(Jm)
+        if dtype is not np.float64:                                     # the FP64 tables, promoted
+            self.qw, self.N, self.dNref, self.L, self.dL = (a.astype(dtype) for a in (self.qw, self.N, self.dNref, self.L, self.dL))
+        if geom is None:
+            xc = self.x[self.tets]                                      # (C,4,3)
+            Jm = np.stack([xc[:, 1] - xc[:, 0], xc[:, 2] - xc[:, 0], xc[:, 3] - xc[:, 0]], axis=2)  # dx/dxi
+            Jinv, det = _inv3(Jm)
+        else:
+            geom = np.asarray(geom, dtype=dtype).reshape(len(self.tets), 10)
+            Jinv, det = geom[:, :9].reshape(-1, 3, 3), geom[:, 9]       # |det|: the orientation is in Jinv alone
         self.detJ = det
         self.wdet = np.abs(det)[:, None] * self.qw[None, :]             # (C,Q)
         # physical gradients: dN/dx_j = sum_k dN/dxi_k * dxi_k/dx_j
@@ -174,7 +189,7 @@ class FsiOracle:
         # the same element arithmetic in C under OpenMP (oracle/fsi_oracle_c.c), used when its library is there;
         # ORACLE_IMPL=numpy forces the numpy definition below (tests/test_oracle_c.py holds the two together)
         self.c = None
-        if impl != "numpy":
+        if impl != "numpy" and dtype is np.float64 and geom is None:
             from . import c_oracle
             if c_oracle.available():
                 self.c = c_oracle.CElements(self)
@@ -264,7 +279,7 @@ class FsiOracle:
                 J = _det3(F)
                 I1 = np.einsum("cqii->cq", C)
                 I2 = 0.5 * (I1 ** 2 - np.einsum("cqij,cqji->cq", C, C))
-                Jm23 = J ** (-2.0 / 3.0)
+                Jm23 = J ** (-self.dtype(2) / self.dtype(3))
                 I1b, I2b = Jm23 * I1, Jm23 ** 2 * I2
                 a1 = (2.0 * (C10 + C11 * (I2b - 3.0)) * Jm23)[..., None, None]
                 a2 = (2.0 * (C01 + C11 * (I1b - 3.0)) * Jm23 ** 2)[..., None, None]
@@ -318,11 +333,11 @@ class FsiOracle:
         """(J_linear, J_nonlinear) element matrices (C,64,64) = d R_e / d U^n_e by complex step."""
         if self.c is not None:
             return self.c.jacobians(np.asarray(U, dtype=float), np.asarray(U1, dtype=float))
-        h = 1e-30
-        loc, loc1 = self.gather(U).astype(complex), self.gather(U1).astype(complex)
+        h = self.cstep
+        loc, loc1 = self.gather(U).astype(self.cdtype), self.gather(U1).astype(self.cdtype)
         C = len(loc)
-        Jl = np.zeros((C, 64, 64))
-        Jn = np.zeros((C, 64, 64))
+        Jl = np.zeros((C, 64, 64), dtype=self.dtype)
+        Jn = np.zeros((C, 64, 64), dtype=self.dtype)
         for cells, fn in self._groups():
             a, b = loc[cells], loc1[cells]
             for j in range(64):

@@ -1,7 +1,7 @@
 """ctypes loader of ``vasp_amd/libfsi_kernel_shim.so`` (vasp_amd/csrc/fsi_kernel_shim.hip) and the host-side reference builders
 of the kernel tests (tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py, tests/test_gpu_product_kernels.py,
 tests/test_gpu_coarse_kernels.py, tests/test_gpu_bcr_kernels.py, tests/test_gpu_block_kernels.py, tests/test_gpu_ilu_kernels.py,
-tests/test_gpu_vector_kernels.py).
+tests/test_gpu_vector_kernels.py, tests/test_gpu_element_kernels.py, tests/test_gpu_element_jacobian.py).
 
 The shim runs ONE ``fsi::launch_*`` call of libvaspfsi.so on host arrays; the builders restate, in numpy, what the library's
 host code hands those kernels: the LDS tiles of a graph (fsi_setup.hip build_tiles, node tiles and Schur tiles), the FP16 records of
@@ -9,7 +9,11 @@ k_pack_h1 / k_pack_h3 / k_pack_sb, the monolithic matrix's column layout, padded
 hierarchy of the two coarse levels with the contracts of their kernels, and the exact coarse solve by block cyclic reduction
 (fsi_bcr.hip: the reduction restated on a block-tridiagonal matrix, its blocked Gauss-Jordan inverse, synthetic tube graphs whose
 breadth-first levels are known), and for the multicolour ILU(0) path matrices that obey the contract of its level kernels, the
-definition of ILU(0) as a check of a given factor and the triangular solves' own equations, each with its rounding bound.  The
+definition of ILU(0) as a check of a given factor and the triangular solves' own equations, each with its rounding bound, and for
+the element kernels of fsi_assembly.hip the tables fsi_setup.hip hands them (element_structure), cell lists with materials and
+states (ElementCase), the project's oracle in extended precision as the reference of element vectors and matrices with the
+bound per block of a cell (K_RESIDUAL, K_JACOBIAN: four times what the oracle's own FP64 evaluation orders reach), and
+restatements of the geometry, the L2 integrand, the cell statistics and the probe interpolation in np.longdouble.  The
 builders are tested on the CPU (tests/test_kernel_references.py), so that a failure
 of a GPU test is one of the kernel, not of its reference."""
 from __future__ import annotations
@@ -62,6 +66,9 @@ _SIGS = {
     "shim_scatter3": "llppp", "shim_round_to_f32": "lpp", "shim_add_indexed": "lppdpl", "shim_add_at": "lppdpl",
     "shim_bc_rhs": "lppppl", "shim_bc_set": "lpppl", "shim_robin_residual": "lppppddpppl", "shim_f32_ripple4": "lp",
     "shim_f32_sumsq": "lpp",
+    "shim_geometry": "llppp", "shim_elem_residual": "lll" + "p" * 10 + "ll" + "p" * 6,
+    "shim_elem_jacobian": "iiilll" + "p" * 14 + "ippp", "shim_l2norm": "llpppp", "shim_stat_parts": "",
+    "shim_cell_stats": "lllppppp", "shim_probe": "lllppppp",
 }
 LAUNCH_REFUSED = 2           # fsi_kernels.hpp: a launch function refused its arguments and launched nothing
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "d": C.c_double, "s": C.c_char_p}
@@ -1614,3 +1621,501 @@ def f32_ripple4(nnodes):
     for c, sh in enumerate((0, 10, 20)):
         out[:, c] = ((h >> np.uint32(sh)) & np.uint32(1023)).astype(np.float32) / np.float32(512.0) - np.float32(1.0)
     return out.reshape(-1)
+
+
+# ---- the element kernels (fsi_assembly.hip; tests/test_gpu_element_kernels.py, tests/test_gpu_element_jacobian.py) -----------
+U64 = 2.0 ** -53
+LD = np.longdouble
+DELTA_S, ALPHA_L = 1.0e7, 1.0        # oracle.fsi_oracle.DELTA and the "constant" Laplace lifting: the Scheme the library is given
+PART_LINEAR, PART_NONLINEAR = 1, 2   # fsi_element.hpp
+FIELD_SLICES = (slice(0, 30), slice(30, 60), slice(60, 64))
+# oracle order [d_x(10) d_y d_z v_x v_y v_z p(4)] -> Re order [node][d_x d_y d_z v_x v_y v_z], p(4): RE_OF_ORACLE[l] is where the
+# oracle's local entry l sits in a row of Re
+RE_OF_ORACLE = np.array([6 * (l % 10) + 3 * (l // 30) + (l % 30) // 10 if l < 60 else l for l in range(64)])
+
+
+def re_from_oracle(x):
+    """[..., 64] element vectors in the oracle's local order -> in the order of k_residual's Re"""
+    y = np.empty_like(x)
+    y[..., RE_OF_ORACLE] = x
+    return y
+
+
+def oracle_from_re(y):
+    """the inverse of re_from_oracle"""
+    return np.asarray(y)[..., RE_OF_ORACLE]
+
+
+def element_structure(tet_nodes, V, rank_of_node):
+    """What fsi_setup.hip builds for the element kernels from a P2 cell list (vertices are the nodes below V, local vertices first)
+    and the rank of every node: cell_rank [C][10], cell_prow [C][4], cell_dofs [C][64] (local order of the oracle, solver
+    numbering: dof t of the node at rank r is 6 r + t, the pressure of the q-th vertex in rank order 6 N2 + q), the node graph in
+    ranks nadj_ptr / nadj (nodes that share a cell, itself included, ascending) and its vertex part padj_ptr / padj (pressure
+    positions, ascending), vrank [V], the monolithic rowptr / cols / diagpos through expand_cols, enbr [C][10][10] (where node b
+    stands among the neighbours of node a), epnbr [C][10][4] (where vertex b stands among its vertex neighbours), and the residual
+    gather's incidences inc_ptr / inc by rank and pinc_ptr / pinc by pressure position, each entry 16 * cell + local node,
+    ascending.  Nodes in no cell have empty rows and no incidences."""
+    from types import SimpleNamespace
+    tn = np.asarray(tet_nodes, dtype=np.int64).reshape(-1, 10)
+    rk = np.asarray(rank_of_node, dtype=np.int64)
+    C, N2 = len(tn), len(rk)
+    assert sorted(rk.tolist()) == list(range(N2)) and tn[:, :4].max() < V <= N2 and tn[:, 4:].min() >= V
+    cr = rk[tn]
+    order = np.argsort(rk[:V])                                     # vertices in rank order
+    prank = np.empty(V, dtype=np.int64)
+    prank[order] = np.arange(V)
+    vrank = rk[:V][order]
+    prow = 6 * N2 + prank[tn[:, :4]]
+    dofs = np.empty((C, 64), dtype=np.int64)
+    for cmp in range(3):
+        dofs[:, 10 * cmp:10 * cmp + 10] = 6 * cr + cmp
+        dofs[:, 30 + 10 * cmp:40 + 10 * cmp] = 6 * cr + 3 + cmp
+    dofs[:, 60:] = prow
+    # the node graph: pairs of ranks that share a cell
+    ra, rb = np.repeat(cr[:, :, None], 10, axis=2), np.repeat(cr[:, None, :], 10, axis=1)
+    code = np.unique(ra * N2 + rb)
+    src, dst = code // N2, code % N2
+    nadj_ptr = np.concatenate([[0], np.cumsum(np.bincount(src, minlength=N2))]).astype(np.int64)
+    enbr = np.searchsorted(code, ra * N2 + rb) - nadj_ptr[ra]
+    pos_of_rank = np.full(N2, -1, dtype=np.int64)
+    pos_of_rank[vrank] = np.arange(V)
+    isv = pos_of_rank[dst] >= 0
+    pcode = src[isv] * V + pos_of_rank[dst[isv]]                   # ascending: the positions rise with the ranks
+    assert np.all(np.diff(pcode) > 0)
+    padj_ptr = np.concatenate([[0], np.cumsum(np.bincount(src[isv], minlength=N2))]).astype(np.int64)
+    pa, pb = np.repeat(cr[:, :, None], 4, axis=2), np.repeat(prank[tn[:, None, :4]], 10, axis=1)
+    epnbr = np.searchsorted(pcode, pa * V + pb) - padj_ptr[pa]
+    rowptr, cols, diagpos = expand_cols(N2, nadj_ptr, dst.astype(np.int32), padj_ptr, (pcode % V).astype(np.int32), vrank)
+    cell = np.arange(C, dtype=np.int64)
+
+    def incidences(owner, nown, nloc):
+        e = (16 * cell[:, None] + np.arange(nloc)).ravel()
+        o = np.argsort(owner.ravel(), kind="stable")               # cells ascending inside an owner
+        return np.concatenate([[0], np.cumsum(np.bincount(owner.ravel(), minlength=nown))]).astype(np.int64), e[o].astype(np.int32)
+    inc_ptr, inc = incidences(cr, N2, 10)
+    pinc_ptr, pinc = incidences(prow - 6 * N2, V, 4)
+    assert enbr.max() < 65536 and (epnbr.max() if V else 0) < 65536
+    return SimpleNamespace(C=C, N2=N2, V=V, ndof=6 * N2 + V, cell_rank=np.ascontiguousarray(cr, dtype=np.int32),
+                           cell_prow=np.ascontiguousarray(prow, dtype=np.int32), cell_dofs=np.ascontiguousarray(dofs, dtype=np.int32),
+                           nadj_ptr=nadj_ptr, nadj=dst.astype(np.int32), padj_ptr=padj_ptr, padj=(pcode % V).astype(np.int32),
+                           vrank=vrank.astype(np.int32), rowptr=rowptr, cols=cols, diagpos=diagpos,
+                           enbr=np.ascontiguousarray(enbr, dtype=np.uint16), epnbr=np.ascontiguousarray(epnbr, dtype=np.uint16),
+                           inc_ptr=inc_ptr, inc=inc, pinc_ptr=pinc_ptr, pinc=pinc)
+
+
+def element_positions(es):
+    """[C][64][64] position in the monolithic matrix of entry (i, j) of every element matrix (oracle's local order), as k_jacobian
+    computes it: rowptr[row] + 6 enbr[a][b] + 3 field + component for the d and v columns, rowptr[row] + 6 deg(a) + epnbr[a][b]
+    for the pressure columns, a the local node of row i"""
+    i = np.arange(64)
+    a = np.where(i < 60, i % 10, i - 60)                           # local node of a row / column
+    fc = np.where(i < 60, 3 * (i // 30) + (i % 30) // 10, 0)
+    r0 = es.rowptr[es.cell_dofs.astype(np.int64)]                  # [C][64]
+    deg6 = 6 * np.diff(es.nadj_ptr)[es.cell_rank.astype(np.int64)]  # [C][10]
+    nb = es.enbr.reshape(-1, 10, 10).astype(np.int64)
+    pb = es.epnbr.reshape(-1, 10, 4).astype(np.int64)
+    pos = np.empty((es.C, 64, 64), dtype=np.int64)
+    pos[:, :, :60] = r0[:, :, None] + 6 * nb[:, a][:, :, a[:60]] + fc[None, None, :60]
+    pos[:, :, 60:] = r0[:, :, None] + deg6[:, a][:, :, None] + pb[:, a]
+    return pos
+
+
+def geometry_reference(coords, tets):
+    """k_geometry's contract in extended precision from the FP64 coordinates: (Jinv [C][3][3] with Jinv[k][j] = d xi_k / d x_j,
+    det [C] signed, the edge matrix J [C][3][3] = d x_i / d xi_k), all np.longdouble"""
+    x = np.asarray(coords, dtype=LD)[np.asarray(tets, dtype=np.int64)]
+    J = np.stack([x[:, 1] - x[:, 0], x[:, 2] - x[:, 0], x[:, 3] - x[:, 0]], axis=2)
+    inv, det = inv3(J)
+    return inv, det, J
+
+
+def geometry_fp64(coords, tets):
+    """[C][10] the geometry array the element kernels read, rounded from geometry_reference"""
+    inv, det, _ = geometry_reference(coords, tets)
+    return np.ascontiguousarray(np.concatenate([inv.reshape(-1, 9), np.abs(det)[:, None]], axis=1), dtype=np.float64)
+
+
+def geometry_bound(coords, tets):
+    """(bound on the nine inverse entries [C][3][3], bound on |det| [C]) for the adjugate inverse in FP64 of the FP64 edge matrix:
+    inverse_bound's c u |A^-1| |A| |A^-1| with c = 16 for the inverse itself and 1 more for the rounding of the edge differences
+    (each entry of A carries at most u |A_ij|, which the inverse passes on as u |A^-1| |A| |A^-1| to first order; the differences
+    of the cells moved away from the origin are the case it is there for); the determinant's three products of a rounded
+    difference with a rounded cofactor are (2 + 1 + 2 + 1 + 2) u of the sum of the absolute products each, 10 u in all with the
+    two additions"""
+    inv, det, J = geometry_reference(coords, tets)
+    J64 = J.astype(np.float64)
+    a = np.abs(J64)
+    perm = (a[:, 0, 0] * (a[:, 1, 1] * a[:, 2, 2] + a[:, 1, 2] * a[:, 2, 1]) + a[:, 0, 1] * (a[:, 1, 0] * a[:, 2, 2] + a[:, 1, 2] * a[:, 2, 0])
+            + a[:, 0, 2] * (a[:, 1, 0] * a[:, 2, 1] + a[:, 1, 1] * a[:, 2, 0]))
+    return inverse_bound(J64, inv, U64, c=17.0), 10.0 * U64 * perm
+
+
+def elem_params(desc):
+    """(sc [5], fluid [8][2], solid [8][7]) of a description as the shim's ElemParams arrays"""
+    sc = np.array([desc["dt"], desc["theta"], 1.0 - desc["theta"], DELTA_S, ALPHA_L])
+    fluid, solid = np.zeros((8, 2)), np.zeros((8, 7))
+    for r, p in enumerate(desc["fluid_props"]):
+        fluid[r] = p
+    models = desc.get("solid_models", [0] * len(desc["solid_props"]))
+    for r, p in enumerate(desc["solid_props"]):
+        p = tuple(p) + (0.0,) * (6 - len(p))
+        solid[r] = p[:3] + (float(models[r]),) + p[3:6]
+    return sc, fluid, solid
+
+
+# Two fluid and three solid regions, so that region > 0 and model == 1 are read
+ELEMENT_FLUIDS = [(1000.0, 3.5e-3), (1060.0, 4.2e-3)]
+ELEMENT_SOLIDS = [(1000.0, 344827.6, 3103448.3, 0.0, 0.0, 0.0), (1200.0, 5.0e5, 2.0e6, 0.0, 0.0, 0.0),
+                  (1100.0, 3.0e5, 2.0e6, 1.0e5, 5.0e4, 1.0e4)]
+ELEMENT_MODELS = [0, 0, 1]
+
+
+class ElementCase:
+    """A cell list with everything one launch of an element kernel takes and everything its reference needs: the P2 mesh (coords,
+    node_coords, tets, tet_nodes), kinds and regions, a random node -> rank permutation with its element_structure (es), the FP64
+    geometry array the kernel and the reference both start from, the materials above, and a state scaled as random_state of
+    tests/test_gpu_parity.py, in the oracle's layout (U, U1) and in the solver's (Us, U1s)."""
+
+    def __init__(self, coords, tets, kind, region, seed, theta=0.51, dt=1.0e-3, node_coords=None, tet_nodes=None):
+        from vasp_amd.mesh import FsiMesh
+        rng = np.random.default_rng(seed)
+        if tet_nodes is None:
+            m = FsiMesh.from_arrays(coords, tets, np.asarray(kind) + 1)
+            assert np.array_equal(m.tets, tets), "cells must be vertex-sorted"
+            node_coords, tet_nodes = m.node_coords, m.tet_nodes
+        self.coords, self.tets = np.ascontiguousarray(coords, dtype=np.float64), np.ascontiguousarray(tets, dtype=np.int64)
+        self.node_coords, self.tet_nodes = node_coords, np.ascontiguousarray(tet_nodes, dtype=np.int64)
+        self.kind, self.region = np.ascontiguousarray(kind, dtype=np.int32), np.ascontiguousarray(region, dtype=np.int32)
+        self.C, self.V, self.N2 = len(self.tets), len(self.coords), len(node_coords)
+        self.rank = rng.permutation(self.N2)
+        self.es = element_structure(self.tet_nodes, self.V, self.rank)
+        self.geom = geometry_fp64(self.coords, self.tets)
+        self.desc = dict(coords=self.coords, tets=self.tets, tet_nodes=self.tet_nodes, num_nodes=self.N2, cell_kind=self.kind,
+                         cell_region=self.region, fluid_props=ELEMENT_FLUIDS, solid_props=ELEMENT_SOLIDS,
+                         solid_models=ELEMENT_MODELS, dt=dt, theta=theta)
+        self.params = elem_params(self.desc)
+        # h: the smallest altitude of any cell (1 / |grad lambda_k|), so that displacements of 0.02 h keep det(I + grad d) > 0 in
+        # flat cells too (the Mooney-Rivlin energy has a logarithm of it)
+        gl = self.geom[:, :9].reshape(-1, 3, 3)
+        gl = np.concatenate([-gl.sum(axis=1, keepdims=True), gl], axis=1)
+        h = float(1.0 / np.sqrt((gl ** 2).sum(axis=2)).max())
+        N2, ndof = self.N2, 6 * self.N2 + self.V
+        U, U1 = np.zeros(ndof), np.zeros(ndof)
+        U[:3 * N2] = 0.02 * h * rng.standard_normal(3 * N2)
+        U1[:3 * N2] = U[:3 * N2] + 0.002 * h * rng.standard_normal(3 * N2)
+        U[3 * N2:6 * N2] = 0.1 * rng.standard_normal(3 * N2)
+        U1[3 * N2:6 * N2] = U[3 * N2:6 * N2] + 0.01 * rng.standard_normal(3 * N2)
+        U[6 * N2:] = 10 * rng.standard_normal(self.V)
+        U1[6 * N2:] = U[6 * N2:] + rng.standard_normal(self.V)
+        self.U, self.U1 = U, U1
+        self.user_dofs = self.user_cell_dofs(self.tet_nodes, self.tets, N2)
+        self.Us, self.U1s = self.to_solver(U), self.to_solver(U1)
+
+    @staticmethod
+    def user_cell_dofs(tn, tets, N2):
+        cols = [off + 3 * tn + c for off in (0, 3 * N2) for c in range(3)]
+        return np.concatenate(cols + [6 * N2 + tets], axis=1)
+
+    def to_solver(self, X):
+        """a vector in the oracle's layout in the solver's; dofs of nodes in no cell are dropped (they stay 0)"""
+        Y = np.zeros(self.es.ndof, dtype=X.dtype)
+        Y[self.es.cell_dofs.ravel()] = X[self.user_dofs.ravel()]
+        return Y
+
+    def prefix(self, C):
+        """the first C cells on the same nodes, ranks and state (the other nodes then lie in no cell)"""
+        return self.subset(np.arange(C))
+
+    def subset(self, cells):
+        """the listed cells as a case of their own (same nodes, ranks and state)"""
+        import copy
+        cells = np.asarray(cells, dtype=np.int64)
+        s = copy.copy(self)
+        s.C, s.tets, s.tet_nodes, s.kind, s.region, s.geom = (len(cells), self.tets[cells], self.tet_nodes[cells], self.kind[cells],
+                                                              self.region[cells], self.geom[cells])
+        s.es = element_structure(s.tet_nodes, self.V, self.rank)
+        s.user_dofs = self.user_dofs[cells]
+        s.desc = dict(self.desc, tets=s.tets, tet_nodes=s.tet_nodes, cell_kind=s.kind, cell_region=s.region)
+        s.Us, s.U1s = s.to_solver(self.U), s.to_solver(self.U1)
+        return s
+
+    def with_theta(self, theta):
+        import copy
+        s = copy.copy(self)
+        s.desc = dict(self.desc, theta=theta)
+        s.params = elem_params(s.desc)
+        return s
+
+    def oracle(self, dtype=np.float64, impl="numpy", given_geometry=True):
+        """the project's oracle on this case: numpy in `dtype` from the case's FP64 geometry array, or (impl "c") the C restatement,
+        which derives its geometry from the coordinates"""
+        from oracle.fsi_oracle import FsiOracle
+        if impl == "c":
+            o = FsiOracle(self.desc)
+            assert o.c is not None, "the C oracle is not available"
+            return o
+        return FsiOracle(self.desc, impl="numpy", dtype=dtype, geom=self.geom if given_geometry else None)
+
+    def residual_reference(self, o=None):
+        """[C][64] R_linear + R_nonlinear of the oracle `o` (default: extended precision from the FP64 geometry array), oracle order"""
+        o = o or self.oracle(LD)
+        Rl, Rn = o.element_residuals(self.U.astype(o.dtype), self.U1.astype(o.dtype))
+        return Rl + Rn
+
+    def jacobian_reference(self, o=None):
+        """([C][64][64] J_linear, J_nonlinear) of the oracle `o` (default: complex step in extended precision)"""
+        o = o or self.oracle(LD)
+        return o.element_jacobians(self.U.astype(o.dtype), self.U1.astype(o.dtype))
+
+
+def tube_case(target, seed, theta=0.51):
+    """ElementCase on vasp_amd.meshgen.generate(target): a conforming tube of fluid cells in a solid wall; regions by cell index"""
+    from vasp_amd import meshgen
+    m = meshgen.generate(target)
+    C = len(m["tets"])
+    kind = (m["cell_markers"] == 2).astype(np.int32)
+    region = np.where(kind == 0, np.arange(C) % 2, np.arange(C) % 3)
+    return ElementCase(m["coords"], m["tets"], kind, region, seed, theta=theta)
+
+
+def hand_case(C, seed, theta=0.51, size=1.0e-3):
+    """1, 2 or 3 hand-built cells: a strip of tetrahedra on six points, a fluid cell, a solid Mooney-Rivlin cell and a solid
+    St. Venant-Kirchhoff cell in region 1; the cells' orientations alternate"""
+    pts = size * np.array([[0.0, 0.0, 0.0], [1.0, 0.1, 0.0], [0.2, 0.9, 0.1], [0.3, 0.2, 1.1], [1.2, 1.0, 0.9], [0.1, 1.1, 1.3]])
+    tets = np.array([[0, 1, 2, 3], [1, 2, 3, 4], [2, 3, 4, 5]])[:C]
+    kind, region = np.array([0, 1, 1])[:C], np.array([1, 2, 1])[:C]
+    return ElementCase(pts[:C + 3], tets, kind, region, seed, theta=theta)
+
+
+def node_disjoint(tet_nodes, cells=None, limit=None):
+    """Greedy colouring of the cells (in the order given) into lists that share no node: [lists of cell ids].  With `limit`, stop
+    once that many cells are placed."""
+    tn = np.asarray(tet_nodes, dtype=np.int64)
+    cells = np.arange(len(tn)) if cells is None else np.asarray(cells)
+    used, lists, placed = [], [], 0
+    for c in cells:
+        nodes = set(tn[c].tolist())
+        for k, u in enumerate(used):
+            if not (u & nodes):
+                u |= nodes
+                lists[k].append(int(c))
+                break
+        else:
+            used.append(set(nodes))
+            lists.append([int(c)])
+        placed += 1
+        if limit and placed >= limit:
+            break
+    return lists
+
+
+# The block bound.  For a cell and a block B (the d, v or p rows of its element vector; a (row field, column field) pair of its
+# element matrix) a kernel must satisfy |got - ref| <= K_B 2^-53 max_B |ref| against the oracle in extended precision, both from the
+# same FP64 geometry array, tables and state.  K_B = 4 x the larger of the two ratios the oracle's own FP64 evaluation orders reach
+# on the tests' inputs (numpy from the given geometry; C from the coordinates, against the extended-precision evaluation from the
+# coordinates), rounded up; the factor 4 covers a third summation order, FMA contraction and the pull-back of the gradient slots
+# to reference coordinates.  Measured on the CPU with measure_block_ratios() on block_ratio_cases(); the figures are in the
+# comments, tests/test_kernel_references.py asserts that both FP64 oracles stay within K_B / 4.  Index: [kind][block], kind 0 fluid,
+# 1 solid; residual blocks 0 d, 1 v, 2 p rows; Jacobian blocks [part][kind][row field][column field].  A block that is zero in the
+# reference has K = 0: the kernel must leave an exact zero (or, in the matrix, the prefill) there.
+def block_ratios(got, ref, kind):
+    """largest |got - ref| / (2^-53 max_B |ref|) per kind and block over the cells: vectors [C][64] -> [2][3]; matrices [C][64][64]
+    -> [2][3][3]; blocks the reference has zero count as 0 when got is zero too, else inf"""
+    got, ref = np.asarray(got, dtype=LD), np.asarray(ref, dtype=LD)
+    mat = ref.ndim == 3
+    out = np.zeros((2, 3, 3) if mat else (2, 3))
+    for k in (0, 1):
+        sel = np.flatnonzero(np.asarray(kind) == k)
+        if not len(sel):
+            continue
+        for bi, rs in enumerate(FIELD_SLICES):
+            for bj, cs in enumerate(FIELD_SLICES if mat else (None,)):
+                g, r = (got[sel][:, rs, cs], ref[sel][:, rs, cs]) if mat else (got[sel][:, rs], ref[sel][:, rs])
+                ax = tuple(range(1, r.ndim))
+                err, mx = np.abs(g - r).max(axis=ax), np.abs(r).max(axis=ax)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    q = np.where(err == 0, 0, err / (U64 * mx))
+                q = float(np.where(np.isnan(q), np.inf, q).max())
+                if mat:
+                    out[k, bi, bj] = q
+                else:
+                    out[k, bi] = q
+    return out
+
+
+def block_bound(ref, kind, K):
+    """K_B 2^-53 max_B |ref| spread over the entries: [C][64] for K [2][3], [C][64][64] for K [2][3][3]"""
+    ref = np.abs(np.asarray(ref, dtype=LD))
+    K = np.asarray(K, dtype=np.float64)
+    kind = np.asarray(kind, dtype=np.int64)
+    b = np.zeros(ref.shape, dtype=LD)
+    for bi, rs in enumerate(FIELD_SLICES):
+        if ref.ndim == 2:
+            b[:, rs] = (K[kind, bi] * U64 * ref[:, rs].max(axis=1))[:, None]
+        else:
+            for bj, cs in enumerate(FIELD_SLICES):
+                b[:, rs, cs] = (K[kind, bi, bj] * U64 * ref[:, rs, cs].max(axis=(1, 2)))[:, None, None]
+    return b
+
+
+_cases = {}
+
+
+def element_cases(name):
+    """The inputs of the element-kernel tests, built once per process.  "tube": the 6000-cell tube, theta 0.51; "tube_theta1": every
+    15th of its cells with theta = 1 (th1 == 0); "hand3" / "hand3_theta1": the three hand-built cells; "big": the 48000-cell tube;
+    "jac": up to 192 cells of the tube that share no node, fluid and solid cells alternating, every region among them"""
+    if name not in _cases:
+        if name == "tube":
+            _cases[name] = tube_case(6000, seed=11)
+        elif name == "tube_theta1":
+            t = element_cases("tube")
+            _cases[name] = t.with_theta(1.0).subset(np.arange(0, t.C, 15))
+        elif name == "hand3":
+            _cases[name] = hand_case(3, seed=5)
+        elif name == "hand3_theta1":
+            _cases[name] = hand_case(3, seed=6, theta=1.0)
+        elif name == "big":
+            _cases[name] = tube_case(48000, seed=12)
+        elif name == "jac":
+            t = element_cases("tube")
+            fl, so = np.flatnonzero(t.kind == 0), np.flatnonzero(t.kind == 1)
+            mixed = np.stack([fl[:len(so)], so], axis=1).ravel()          # fluid and solid cells in turn
+            _cases[name] = t.subset(np.array(node_disjoint(t.tet_nodes, mixed)[0][:192]))
+            assert _cases[name].C >= 150
+        else:
+            raise KeyError(name)
+    return _cases[name]
+
+
+RESIDUAL_RATIO_CASES = ("tube", "tube_theta1", "hand3", "hand3_theta1")
+
+
+def measure_residual_ratios(names=RESIDUAL_RATIO_CASES):
+    """{oracle: [2][3]} the largest block ratio of the oracle's two FP64 evaluation orders against extended precision over the cases"""
+    out = {"numpy": np.zeros((2, 3)), "c": np.zeros((2, 3))}
+    for n in names:
+        case = element_cases(n)
+        ref = case.residual_reference()
+        out["numpy"] = np.maximum(out["numpy"], block_ratios(case.residual_reference(case.oracle(np.float64)), ref, case.kind))
+        out["c"] = np.maximum(out["c"], block_ratios(case.residual_reference(case.oracle(impl="c")), ref, case.kind))
+    return out
+
+
+def measure_jacobian_ratios():
+    """{oracle: [2 parts][2][3][3]} the same for the element matrices of the "jac" case"""
+    case = element_cases("jac")
+    ref = case.jacobian_reference()
+    out = {}
+    for name, o in (("numpy", case.oracle(np.float64)), ("c", case.oracle(impl="c"))):
+        J = case.jacobian_reference(o)
+        out[name] = np.stack([block_ratios(J[p], ref[p], case.kind) for p in (0, 1)])
+    return out
+
+
+# CPU-measured ratios (measure_residual_ratios(), numpy / C, per kind the d, v, p rows) and K = 4 x the larger, rounded up to a
+# multiple of 4 that leaves the measurement a tenth of room under K / 4 (another compiler or numpy may move its last digit):
+#   fluid  4.5 / 7.6 -> 36     8.5 / 9.8 -> 44     6.8 / 20.7 -> 92
+#   solid  5.4 / 10.8 -> 48    84.7 / 92.2 -> 408 (the strain E = (F^T F - I) / 2 of a 2 % deformation cancels two digits before the
+#          stiffness multiplies it)                 p rows: zero
+K_RESIDUAL = np.array([[36.0, 44.0, 92.0], [48.0, 408.0, 0.0]])
+# measure_jacobian_ratios(), [part linear / nonlinear][kind][row field][column field]; the blocks not named are zero in the reference:
+#   linear     fluid (d,d) 3.8 / 6.0 -> 28   (v,v) 5.0 / 5.9 -> 28
+#              solid (d,d) 5.1 / 12.6 -> 56  (d,v) 6.4 / 12.8 -> 56  (v,v) 5.5 / 13.8 -> 64
+#   nonlinear  fluid (v,d) 5.1 / 6.4 -> 28   (v,v) 3.9 / 4.5 -> 20   (v,p) 3.6 / 5.1 -> 24   (p,d) 4.8 / 6.0 -> 28   (p,v) 4.1 / 5.3 -> 24
+#              solid (v,d) 4.9 / 12.3 -> 56
+# On an MI355X every block of every kernel stayed below half of its bound against the extended-precision reference (the figures are
+# in the headers of the two test files), so no constant had to be explained or touched.
+K_JACOBIAN = np.zeros((2, 2, 3, 3))
+K_JACOBIAN[0, 0, 0, 0], K_JACOBIAN[0, 0, 1, 1] = 28.0, 28.0
+K_JACOBIAN[0, 1, 0, 0], K_JACOBIAN[0, 1, 0, 1], K_JACOBIAN[0, 1, 1, 1] = 56.0, 56.0, 64.0
+K_JACOBIAN[1, 0, 1] = (28.0, 20.0, 24.0)
+K_JACOBIAN[1, 0, 2, :2] = (28.0, 24.0)
+K_JACOBIAN[1, 1, 1, 0] = 56.0
+
+
+def sequential_gather(Re, ptr, lst, mul, off):
+    """k_residual_gather's sum in FP64, by a loop over the incidences in the order of the list: out[r][t] = the entries
+    Re[cell][mul * local + off + t] of owner r's incidences added one after the other to 0.0 (t < mul)"""
+    Re = np.asarray(Re, dtype=np.float64).reshape(-1, 64)
+    n = len(ptr) - 1
+    deg = np.diff(ptr)
+    s = np.zeros((n, mul))
+    for k in range(int(deg.max()) if n else 0):
+        live = np.flatnonzero(deg > k)
+        e = np.asarray(lst, dtype=np.int64)[ptr[live] + k]
+        s[live] = s[live] + Re[e >> 4][np.arange(len(live))[:, None], (mul * (e & 15) + off)[:, None] + np.arange(mul)]
+    return s
+
+
+def assembled(es, elem_vals, absolute=False):
+    """sum of the element vectors [C][64] (oracle order) into the solver-layout vector, in extended precision"""
+    out = np.zeros(es.ndof, dtype=LD)
+    v = np.asarray(elem_vals, dtype=LD)
+    np.add.at(out, es.cell_dofs.astype(np.int64).ravel(), (np.abs(v) if absolute else v).ravel())
+    return out
+
+
+def l2_reference(case, X):
+    """(value, bound) of launch_l2norm: the Keast-24 integral of |d|^2 + |v|^2 + p^2 over the cells from the FP64 tables, geometry
+    weights and state, in extended precision.  Bound (terms + c) u sum |terms| with the squares of the absolute interpolations as
+    the terms: 2 x (10 products and additions + 1) for a squared P2 value, 7 additions of squares, 3 factors of the weight, and the
+    additions of the reduction (cells per wave, 6 shuffle steps, 2 per workgroup, blocks / 256 + 8 in k_sum_parts); c = 8"""
+    from oracle.fsi_oracle import keast24, tabulate_p2
+    qp, qw = keast24()
+    N, _, L, _ = tabulate_p2(qp)
+    N, L, qw = N.astype(LD), L.astype(LD), qw.astype(LD)
+    loc = np.asarray(X, dtype=LD)[case.es.cell_dofs.astype(np.int64)]             # [C][64]
+    w = case.geom[:, 9].astype(LD)[:, None] * qw[None, :]
+    f = loc[:, :60].reshape(-1, 6, 10)
+    val, vabs = np.einsum("qa,cfa->cqf", N, f), np.einsum("qa,cfa->cqf", np.abs(N), np.abs(f))
+    p, pabs = np.einsum("qa,ca->cq", L, loc[:, 60:]), np.einsum("qa,ca->cq", np.abs(L), np.abs(loc[:, 60:]))
+    value = (w * ((val ** 2).sum(axis=2) + p ** 2)).sum()
+    T = (w * ((vabs ** 2).sum(axis=2) + pabs ** 2)).sum()
+    blocks = min((case.C + 3) // 4, 4096)
+    terms = 2 * 11 + 7 + 3 + -(-case.C // (4 * blocks)) + 6 + 2 + -(-blocks // 256) + 8
+    return value, (terms + 8) * U64 * T
+
+
+def cell_stats_reference(case, X):
+    """launch_cell_stats per cell, in extended precision: (mean |v| [C], its bound, mean det(I + grad d) [C], its bound).  Bounds
+    (terms + c) u sum |terms| over the absolute interpolations: |v| from three 10-term sums, 3 squares, a root and the weight
+    (10 + 3 + 3 + 2), the determinant from gradients of 30 terms of 3-term physical gradients and the 6 products of the cofactor
+    expansion (33 + 3 + 9), then the 24 weighted points through 6 shuffle steps (+ 8); c = 8"""
+    from oracle.fsi_oracle import keast24, tabulate_p2
+    qp, qw = keast24()
+    N, dN, _, _ = tabulate_p2(qp)
+    N, dN, wq = N.astype(LD), dN.astype(LD), 6.0 * qw.astype(LD)
+    es = case.es
+    loc = np.asarray(X, dtype=LD)[es.cell_dofs.astype(np.int64)]
+    d = loc[:, :30].reshape(-1, 3, 10)
+    v = loc[:, 30:60].reshape(-1, 3, 10)
+    Jinv = case.geom[:, :9].astype(LD).reshape(-1, 3, 3)
+    G, Gabs = np.einsum("qak,ckj->cqaj", dN, Jinv), np.einsum("qak,ckj->cqaj", np.abs(dN), np.abs(Jinv))
+    vq, vqa = np.einsum("qa,cia->cqi", N, v), np.einsum("qa,cia->cqi", np.abs(N), np.abs(v))
+    sv = (wq * np.sqrt((vq ** 2).sum(axis=2))).sum(axis=1)
+    bv = (18 + 8 + 8) * U64 * (wq * np.sqrt((vqa ** 2).sum(axis=2))).sum(axis=1)
+    F = np.eye(3, dtype=LD) + np.einsum("cia,cqaj->cqij", d, G)
+    Fa = np.eye(3, dtype=LD) + np.einsum("cia,cqaj->cqij", np.abs(d), Gabs)
+    det = (F[..., 0, 0] * (F[..., 1, 1] * F[..., 2, 2] - F[..., 1, 2] * F[..., 2, 1])
+           - F[..., 0, 1] * (F[..., 1, 0] * F[..., 2, 2] - F[..., 1, 2] * F[..., 2, 0])
+           + F[..., 0, 2] * (F[..., 1, 0] * F[..., 2, 1] - F[..., 1, 1] * F[..., 2, 0]))
+    perm = (Fa[..., 0, 0] * (Fa[..., 1, 1] * Fa[..., 2, 2] + Fa[..., 1, 2] * Fa[..., 2, 1])
+            + Fa[..., 0, 1] * (Fa[..., 1, 0] * Fa[..., 2, 2] + Fa[..., 1, 2] * Fa[..., 2, 0])
+            + Fa[..., 0, 2] * (Fa[..., 1, 0] * Fa[..., 2, 1] + Fa[..., 1, 1] * Fa[..., 2, 0]))
+    sj = (wq * det).sum(axis=1)
+    bj = (45 + 8 + 8) * U64 * (wq * perm).sum(axis=1)
+    return sv, bv, sj, bj
+
+
+def probe_reference(case, cells, bary, X):
+    """launch_probe: (values [n][7] = d, v, p at the barycentric coordinates, bound) in extended precision; the basis from the FP64
+    coordinates (2 roundings each), 10 products and additions: (10 + 4) u sum |N| |X| (pressure: 4 + 2)"""
+    l = np.asarray(bary, dtype=LD).reshape(-1, 4)
+    Nb = np.concatenate([l * (2 * l - 1), 4 * l[:, [e[0] for e in UFC_EDGES]] * l[:, [e[1] for e in UFC_EDGES]]], axis=1)
+    loc = np.asarray(X, dtype=LD)[case.es.cell_dofs.astype(np.int64)[np.asarray(cells, dtype=np.int64)]]
+    f = loc[:, :60].reshape(-1, 6, 10)
+    val = np.concatenate([np.einsum("na,nfa->nf", Nb, f), np.einsum("na,na->n", l, loc[:, 60:])[:, None]], axis=1)
+    ab = np.concatenate([14 * U64 * np.einsum("na,nfa->nf", np.abs(Nb), np.abs(f)),
+                         6 * U64 * np.einsum("na,na->n", np.abs(l), np.abs(loc[:, 60:]))[:, None]], axis=1)
+    return val, ab

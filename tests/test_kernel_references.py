@@ -861,3 +861,133 @@ def test_f32_ripple4_reference():
     i = 4096 * 256 + 200
     h = ((i * 2654435761) & 0xFFFFFFFF) ^ (i >> 7)
     assert big[i, 2] == ((h >> 20) & 1023) / 512 - 1
+
+
+# ---- the element kernels' references (kernel_shim.element_structure ... probe_reference; tests/test_gpu_element_*.py) ------------
+def test_element_structure_names_the_right_columns_and_incidences():
+    """for every cell and local pair, cols[rowptr[row] + 6 enbr + 3 f + c] and the epnbr position are the column's dof; the dofs are
+    what k_residual computes from the ranks; the incidence lists hold every (cell, local node) once, under its owner, ascending"""
+    for case in (ks.element_cases("tube").prefix(700), ks.element_cases("hand3"), ks.element_cases("jac")):
+        es = case.es
+        dofs = es.cell_dofs.astype(np.int64)
+        pos = ks.element_positions(es)
+        np.testing.assert_array_equal(es.cols[pos], np.broadcast_to(dofs[:, None, :], pos.shape))
+        assert pos.min() >= 0 and np.all(pos < es.rowptr[dofs + 1][:, :, None]) and np.all(pos >= es.rowptr[dofs][:, :, None])
+        lane = np.arange(60)
+        np.testing.assert_array_equal(dofs[:, :60], 6 * es.cell_rank[:, lane % 10].astype(np.int64) + 3 * (lane // 30) + (lane % 30) // 10)
+        np.testing.assert_array_equal(dofs[:, 60:], es.cell_prow)
+        np.testing.assert_array_equal(es.vrank[es.cell_prow - 6 * es.N2], es.cell_rank[:, :4])       # a pressure row sits at its vertex
+        for ptr, lst, owner, nloc in ((es.inc_ptr, es.inc, es.cell_rank, 10), (es.pinc_ptr, es.pinc, es.cell_prow - 6 * es.N2, 4)):
+            assert len(lst) == nloc * es.C == ptr[-1] and len(np.unique(lst)) == len(lst)
+            own = np.repeat(np.arange(len(ptr) - 1), np.diff(ptr))
+            np.testing.assert_array_equal(owner[lst >> 4, lst & 15], own)
+            inside = np.ones(len(lst), dtype=bool)
+            inside[ptr[:-1][np.diff(ptr) > 0]] = False                       # first entry of every owner
+            assert np.all(np.diff(lst.astype(np.int64))[inside[1:]] > 0)
+    # a shifted epnbr index names another column (or leaves the row): the check above would catch it
+    es = ks.element_cases("hand3").es
+    bad = es.epnbr.copy()
+    bad[1, 2, 3] += 1
+    import copy
+    es2 = copy.copy(es)
+    es2.epnbr = bad
+    pos = ks.element_positions(es2)
+    hit = np.minimum(pos, len(es.cols) - 1)
+    assert not np.array_equal(es.cols[hit], np.broadcast_to(es.cell_dofs.astype(np.int64)[:, None, :], pos.shape))
+
+
+def test_element_local_reordering():
+    l = np.arange(64)
+    re = ks.re_from_oracle(l)
+    for f in range(2):
+        for c in range(3):
+            for a in range(10):
+                assert re[6 * a + 3 * f + c] == 30 * f + 10 * c + a
+    np.testing.assert_array_equal(re[60:], [60, 61, 62, 63])
+    x = np.random.default_rng(0).standard_normal((5, 64))
+    np.testing.assert_array_equal(ks.oracle_from_re(ks.re_from_oracle(x)), x)
+    np.testing.assert_array_equal(ks.re_from_oracle(ks.oracle_from_re(x)), x)
+
+
+def test_geometry_reference_inverts_the_edge_matrix():
+    case = ks.element_cases("tube")
+    inv, det, J = ks.geometry_reference(case.coords, case.tets)
+    assert (det > 0).any() and (det < 0).any()                              # vertex-sorted cells come in both orientations
+    assert np.abs(inv @ J - np.eye(3)).max() < 1e-15
+    bi, bd = ks.geometry_bound(case.coords, case.tets)
+    J64 = J.astype(np.float64)
+    from oracle.fsi_oracle import _inv3
+    inv64, det64 = _inv3(J64)                                               # the adjugate in FP64, as k_geometry
+    assert np.all(np.abs(inv64 - inv) <= bi)
+    assert np.all(np.abs(det64 - det) <= bd)
+    np.testing.assert_array_equal(case.geom[:, 9], np.abs(det).astype(np.float64))
+
+
+def test_fp64_oracles_stay_within_a_quarter_of_the_residual_block_bounds():
+    """K_RESIDUAL is 4 x what the oracle's own FP64 evaluation orders reach against extended precision on the tests' inputs: the
+    constants cannot be loosened without this failing to be tight, and the inputs are benign (no block of any cell is lost to
+    cancellation).  A reference with one pressure weight off by 1e-6, or without the last cell, is far outside the bound."""
+    r = ks.measure_residual_ratios()
+    for name in ("numpy", "c"):
+        assert np.all(r[name] <= ks.K_RESIDUAL / 4), (name, r[name])
+    assert np.all(np.maximum(r["numpy"], r["c"]) >= ks.K_RESIDUAL / 8 - 1e-9)       # and K is not more than 8 x the measurement
+    case = ks.element_cases("tube").prefix(17)
+    ref = case.residual_reference()
+    o = case.oracle(ks.LD)
+    o.L = o.L.copy()
+    o.L[5, 2] *= 1 + 1e-6                                                    # a deliberately wrong table entry
+    wrong = case.residual_reference(o)
+    q = ks.block_ratios(wrong, ref, case.kind)
+    assert q[0, 2] > 1e3 * ks.K_RESIDUAL[0, 2]
+    err = np.abs(wrong - ref) > ks.block_bound(ref, case.kind, ks.K_RESIDUAL)
+    assert err[case.kind == 0][:, 60:].any() and not err[case.kind == 1][:, 60:].any()
+    short = ref.copy()
+    short[-1] = 0
+    assert (np.abs(short - ref) > ks.block_bound(ref, case.kind, ks.K_RESIDUAL))[-1].any()
+
+
+def test_fp64_oracles_stay_within_a_quarter_of_the_jacobian_block_bounds():
+    r = ks.measure_jacobian_ratios()
+    for name in ("numpy", "c"):
+        assert np.all(r[name] <= ks.K_JACOBIAN / 4), (name, r[name])
+    assert np.all(np.maximum(r["numpy"], r["c"]) >= ks.K_JACOBIAN / 8 - 1e-9)
+    case = ks.element_cases("jac")
+    for k in (0, 1):
+        assert (case.kind == k).sum() >= 60 and len(np.unique(case.region[case.kind == k])) == (2, 3)[k]
+    assert len(np.unique(case.tet_nodes)) == 10 * case.C                     # no two cells share a node
+
+
+def test_sequential_gather_is_the_ordered_sum():
+    es = ks.element_cases("tube").prefix(300).es
+    Re = np.random.default_rng(3).integers(-1000, 1000, (es.C, 64)).astype(np.float64)     # integers: every order gives the same sum
+    F = np.concatenate([ks.sequential_gather(Re, es.inc_ptr, es.inc, 6, 0).ravel(), ks.sequential_gather(Re, es.pinc_ptr, es.pinc, 1, 60).ravel()])
+    ref = ks.assembled(es, ks.oracle_from_re(Re)).astype(np.float64)
+    np.testing.assert_array_equal(F, ref)
+    # order: 1e16, 1, -1e16 gives 0 in list order and would give 1 in any order that meets the large terms first
+    ptr, lst = np.array([0, 3]), np.array([0, 16, 32], dtype=np.int32)
+    R3 = np.zeros((3, 64))
+    R3[:, 0] = (1e16, 1.0, -1e16)
+    assert ks.sequential_gather(R3, ptr, lst, 6, 0)[0, 0] == 0.0
+
+
+def test_l2_statistics_and_probe_references():
+    case = ks.element_cases("tube").prefix(5)
+    o = case.oracle(np.float64)
+    val, bound = ks.l2_reference(case, case.Us)
+    assert abs(o.function_norm(case.U) ** 2 - float(val)) <= float(bound)
+    drop = ks.l2_reference(case.prefix(4), case.Us)[0]                       # the last cell of an odd C dropped: far outside the bound
+    assert abs(float(drop - val)) > 1e6 * float(bound)
+    sv, bv, sj, bj = ks.cell_stats_reference(case, np.zeros(case.es.ndof))
+    assert np.all(sv == 0) and np.all(np.abs(sj - 1) < 1e-14)        # the tabulated weights sum to 1/6 to 2e-15
+    # an affine displacement d = A x has det(I + A) everywhere, and v = const its own length
+    A = np.array([[0.1, 0.02, 0.0], [0.0, -0.05, 0.03], [0.01, 0.0, 0.2]])
+    X = np.zeros(6 * case.N2 + case.V)
+    X[:3 * case.N2] = (case.node_coords @ A.T).ravel()
+    X[3 * case.N2:6 * case.N2] = np.tile([3.0, 4.0, 12.0], case.N2)
+    sv, bv, sj, bj = ks.cell_stats_reference(case, case.to_solver(X))
+    assert np.all(np.abs(sv - 13) <= bv + 1e-16) and np.all(np.abs(sj - np.linalg.det(np.eye(3) + A)) <= bj + 1e-12)
+    cells = np.array([0, 3, 4], dtype=np.int32)
+    bary = np.array([[0, 1.0, 0, 0], [0.5, 0, 0.5, 0], [0.1, 0.2, 0.3, 0.4]])
+    got, b = ks.probe_reference(case, cells, bary, case.to_solver(X))
+    x = np.einsum("na,nai->ni", bary, case.coords[case.tets[cells]])
+    assert np.abs(got[:, :3] - x @ A.T).max() < 1e-15 and np.abs(got[:, 3:6] - [3.0, 4.0, 12.0]).max() < 1e-14

@@ -579,7 +579,9 @@ __global__ __launch_bounds__(64, WAVES) void k_jacobian(ElemArrays ea, ElemParam
 //              done in registers with gfx950's v_permlane32_swap / v_permlane16_swap (4 swaps per 32-bit half; no LDS).
 //   D: lane l holds rows (l >> 4) + 4 r, r = 0..3, of column 16 t + (l & 15): the scatter walks those.
 // The four pressure rows (one slot, K = 24) stay on the vector pipe.  tools/mfma_layout_check.hip checks both register maps
-// on the device; the parity tests compare the assembled matrix with the oracle's complex-step Jacobian entry by entry.
+// on the device; tests/test_gpu_element_jacobian.py compares this kernel's element matrices with the oracle's complex-step Jacobian in
+// extended precision entry by entry, under a bound per (row field, column field) block - the pressure columns of tile 3 and the
+// pressure rows among them -, and with k_jacobian<PART_NONLINEAR> under the same bounds.
 // ---------------------------------------------------------------------------------------------------------
 typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
 typedef double v4d_t __attribute__((ext_vector_type(4)));

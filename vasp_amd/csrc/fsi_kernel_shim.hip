@@ -1634,6 +1634,204 @@ int shim_f32_sumsq(int64_t n, const float* x, double* out) {
   SHIM_RUN(c, "launch_f32_sumsq", launch_f32_sumsq(c.st, n, dx, dout));
 }
 
+// ---- fsi_assembly.hip: the element kernels (tests/test_gpu_element_kernels.py, tests/test_gpu_element_jacobian.py) ------------
+// Host arrays throughout, no live context: the basis tables are uploaded by the entry itself.  Every index array is checked on the
+// host first (status 3, nothing launched): node ranks against N2, dofs against the state's length, incidences against C, and for the
+// Jacobian every position an element entry can be added at against its row of the matrix.  ElemParams as plain arrays: sc [5] =
+// (k, th0, th1, delta, alpha), fluid [8][2] = (rho, mu), solid [8][7] = (rho, mu, lam, model, C10, C01, C11).
+extern "C++" {
+namespace {
+ElemParams elem_params(const double* sc, const double* fluid, const double* solid) {
+  ElemParams ep;
+  ep.sc = Scheme{sc[0], sc[1], sc[2], sc[3], sc[4]};
+  for (int r = 0; r < MAX_REGIONS; ++r) {
+    ep.fluid[r] = FluidProps{fluid[2 * r], fluid[2 * r + 1]};
+    const double* p = solid + 7 * r;
+    ep.solid[r] = SolidProps{p[0], p[1], p[2], (int)p[3], p[4], p[5], p[6]};
+  }
+  return ep;
+}
+int kinds_checked(const char* who, const int32_t* kind, const int32_t* region, int64_t C) {
+  for (int64_t c = 0; c < C; ++c)
+    if (kind[c] < 0 || kind[c] > 1 || region[c] < 0 || region[c] >= MAX_REGIONS) {
+      g_err = std::string(who) + ": kind / region of cell " + std::to_string(c) + " outside the tables";
+      return 3;
+    }
+  return 0;
+}
+int ptr_checked(const char* who, const int64_t* ptr, int64_t n) {
+  if (ptr[0] != 0) { g_err = std::string(who) + ": pointer array does not start at 0"; return 3; }
+  for (int64_t i = 0; i < n; ++i)
+    if (ptr[i + 1] < ptr[i]) { g_err = std::string(who) + ": pointer array decreases at " + std::to_string(i); return 3; }
+  return 0;
+}
+// incidences 16 * cell + local index, local index below nloc
+int incidences_checked(const char* who, const int32_t* inc, int64_t n, int64_t C, int nloc) {
+  for (int64_t i = 0; i < n; ++i)
+    if (inc[i] < 0 || (inc[i] >> 4) >= C || (inc[i] & 15) >= nloc) { g_err = std::string(who) + ": incidence " + std::to_string(i) + " outside Re"; return 3; }
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+// coords [nv][3], tets [C][4]; geom [10 C + SHIM_TAIL]
+int shim_geometry(int64_t C, int64_t nv, const double* coords, const int32_t* tets, double* geom) {
+  if (const int rc = indices_checked("shim_geometry", tets, 4 * C, nv)) return rc;
+  Call c;
+  const double* dx = c.in(coords, (size_t)(3 * nv));
+  const int32_t* dt = c.in(tets, (size_t)(4 * C));
+  double* dg = c.io(geom, (size_t)(10 * C) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_geometry", launch_geometry(c.st, C, dx, dt, dg));
+}
+// U, U1 [nu]; the node ranks lie below nrank (6 nrank <= nu), the pressure rows below nu.
+// Gathered form (Re not null): Re [64 C + SHIM_TAIL] and F [6 N2 + V + SHIM_TAIL] are written, inc_ptr [N2 + 1] / inc and
+// pinc_ptr [V + 1] / pinc are the incidence lists the gather sums over (they need not be the mesh's own).
+// Atomic form (Re null): F [nu + SHIM_TAIL] in / out, N2, V and the lists unused.
+int shim_elem_residual(int64_t C, int64_t nu, int64_t nrank, const double* geom, const int32_t* cell_rank, const int32_t* cell_prow,
+                       const int32_t* cell_kind, const int32_t* cell_region, const double* sc, const double* fluid,
+                       const double* solid, const double* U, const double* U1, int64_t N2, int64_t V, const int64_t* inc_ptr,
+                       const int32_t* inc, const int64_t* pinc_ptr, const int32_t* pinc, double* Re, double* F) {
+  if (C < 1 || 6 * nrank > nu) { g_err = "shim_elem_residual: no cells, or node ranks beyond the state"; return 3; }
+  if (const int rc = indices_checked("shim_elem_residual ranks", cell_rank, 10 * C, nrank)) return rc;
+  if (const int rc = indices_checked("shim_elem_residual pressure rows", cell_prow, 4 * C, nu)) return rc;
+  if (const int rc = kinds_checked("shim_elem_residual", cell_kind, cell_region, C)) return rc;
+  if (Re) {
+    if (N2 < 0 || V < 0 || 6 * N2 + V < 1) { g_err = "shim_elem_residual: nothing to gather"; return 3; }
+    if (const int rc = ptr_checked("shim_elem_residual inc_ptr", inc_ptr, N2)) return rc;
+    if (const int rc = ptr_checked("shim_elem_residual pinc_ptr", pinc_ptr, V)) return rc;
+    if (const int rc = incidences_checked("shim_elem_residual inc", inc, inc_ptr[N2], C, 10)) return rc;
+    if (const int rc = incidences_checked("shim_elem_residual pinc", pinc, pinc_ptr[V], C, 4)) return rc;
+  }
+  Call c;
+  c.note(upload_tables());
+  ElemArrays ea{};
+  ea.geom = c.in(geom, (size_t)(10 * C));
+  ea.cell_rank = c.in(cell_rank, (size_t)(10 * C));
+  ea.cell_prow = c.in(cell_prow, (size_t)(4 * C));
+  ea.cell_kind = c.in(cell_kind, (size_t)C);
+  ea.cell_region = c.in(cell_region, (size_t)C);
+  const ElemParams ep = elem_params(sc, fluid, solid);
+  const double* dU = c.in(U, (size_t)nu);
+  const double* dU1 = c.in(U1, (size_t)nu);
+  ResidualGather rg;
+  double* dF;
+  if (Re) {
+    rg.Re = c.io(Re, (size_t)(NLOC * C) + SHIM_TAIL);
+    rg.N2 = N2; rg.V = V;
+    rg.inc_ptr = c.in(inc_ptr, (size_t)N2 + 1);
+    rg.inc = c.in(inc, (size_t)inc_ptr[N2]);
+    rg.pinc_ptr = c.in(pinc_ptr, (size_t)V + 1);
+    rg.pinc = c.in(pinc, (size_t)pinc_ptr[V]);
+    dF = c.io(F, (size_t)(6 * N2 + V) + SHIM_TAIL);
+  } else {
+    dF = c.io(F, (size_t)nu + SHIM_TAIL);
+  }
+  SHIM_RUN(c, "launch_residual", launch_residual(c.st, C, ea, ep, dU, dU1, dF, rg));
+}
+// part: PART_LINEAR (1) or PART_NONLINEAR (2).  U, U1 [nu]; rowptr [nu + 1]; nadj_ptr [N2 + 1]; vals [rowptr[nu] + SHIM_TAIL] in / out.
+// Colours: cells [ptr[ncolours]] sorted by colour, ptr [ncolours + 1] (host); ncolours == 0: one launch over all cells.
+int shim_elem_jacobian(int part, int jac_waves, int jac_mfma, int64_t C, int64_t nu, int64_t N2, const double* geom,
+                       const int32_t* cell_dofs, const int32_t* cell_kind, const int32_t* cell_region, const int32_t* cell_rank,
+                       const uint16_t* enbr, const uint16_t* epnbr, const double* sc, const double* fluid, const double* solid,
+                       const double* U, const double* U1, const int64_t* rowptr, const int64_t* nadj_ptr, int ncolours,
+                       const int32_t* cells, const int64_t* ptr, double* vals) {
+  if (C < 1 || (part != PART_LINEAR && part != PART_NONLINEAR) || ncolours < 0) { g_err = "shim_elem_jacobian: no cells, or no such part"; return 3; }
+  if (const int rc = indices_checked("shim_elem_jacobian dofs", cell_dofs, NLOC * C, nu)) return rc;
+  if (const int rc = indices_checked("shim_elem_jacobian ranks", cell_rank, 10 * C, N2)) return rc;
+  if (const int rc = kinds_checked("shim_elem_jacobian", cell_kind, cell_region, C)) return rc;
+  if (const int rc = ptr_checked("shim_elem_jacobian rowptr", rowptr, nu)) return rc;
+  if (const int rc = ptr_checked("shim_elem_jacobian nadj_ptr", nadj_ptr, N2)) return rc;
+  // every position the kernels can add at: row i of the element, column j, as k_jacobian computes it
+  for (int64_t cl = 0; cl < C; ++cl)
+    for (int i = 0; i < NLOC; ++i) {
+      const int64_t row = cell_dofs[cl * NLOC + i], r0 = rowptr[row], r1 = rowptr[row + 1];
+      const int ra = i < 60 ? i % 10 : i - 60;
+      const int32_t rk = cell_rank[cl * 10 + ra];
+      const int64_t deg6 = 6 * (nadj_ptr[rk + 1] - nadj_ptr[rk]);
+      for (int j = 0; j < NLOC; ++j) {
+        const int jf = j < 60 ? j / 30 : 2, jc = j < 60 ? (j % 30) / 10 : 0, jb = j < 60 ? j % 10 : j - 60;
+        const int64_t pos = jf < 2 ? r0 + 6 * (int64_t)enbr[cl * 100 + ra * 10 + jb] + 3 * jf + jc : r0 + deg6 + epnbr[cl * 40 + ra * 4 + jb];
+        if (pos < r0 || pos >= r1) {
+          g_err = "shim_elem_jacobian: entry (" + std::to_string(i) + ", " + std::to_string(j) + ") of cell " + std::to_string(cl) + " outside its row";
+          return 3;
+        }
+      }
+    }
+  int64_t nlist = 0;
+  if (ncolours > 0) {
+    if (const int rc = ptr_checked("shim_elem_jacobian colours", ptr, ncolours)) return rc;
+    nlist = ptr[ncolours];
+    if (const int rc = indices_checked("shim_elem_jacobian colour lists", cells, nlist, C)) return rc;
+  }
+  Call c;
+  c.note(upload_tables());
+  ElemArrays ea{};
+  ea.geom = c.in(geom, (size_t)(10 * C));
+  ea.cell_dofs = c.in(cell_dofs, (size_t)(NLOC * C));
+  ea.cell_kind = c.in(cell_kind, (size_t)C);
+  ea.cell_region = c.in(cell_region, (size_t)C);
+  ea.cell_rank = c.in(cell_rank, (size_t)(10 * C));
+  ea.enbr = c.in(enbr, (size_t)(100 * C));
+  ea.epnbr = c.in(epnbr, (size_t)(40 * C));
+  const ElemParams ep = elem_params(sc, fluid, solid);
+  const double* dU = c.in(U, (size_t)nu);
+  const double* dU1 = c.in(U1, (size_t)nu);
+  const int64_t* drp = c.in(rowptr, (size_t)nu + 1);
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  double* dv = c.io(vals, (size_t)rowptr[nu] + SHIM_TAIL);
+  CellColours cc;
+  cc.ncolours = ncolours;
+  if (ncolours > 0) { cc.cells = c.in(cells, (size_t)nlist); cc.ptr = ptr; }
+  SHIM_RUN(c, "launch_jacobian", launch_jacobian(c.st, part, C, ea, ep, dU, dU1, drp, dnp, dv, cc, jac_waves, jac_mfma));
+}
+// X [nu]; out [1 + SHIM_TAIL] = int |d|^2 + |v|^2 + p^2 over the cells
+int shim_l2norm(int64_t C, int64_t nu, const double* geom, const int32_t* cell_dofs, const double* X, double* out) {
+  if (C < 1) { g_err = "shim_l2norm: no cells"; return 3; }
+  if (const int rc = indices_checked("shim_l2norm", cell_dofs, NLOC * C, nu)) return rc;
+  Call c;
+  c.note(upload_tables());
+  ElemArrays ea{};
+  ea.geom = c.in(geom, (size_t)(10 * C));
+  ea.cell_dofs = c.in(cell_dofs, (size_t)(NLOC * C));
+  const double* dX = c.in(X, (size_t)nu);
+  std::vector<double> hs(4096 + 16);
+  double* part = c.in(hs.data(), hs.size());
+  double* dout = c.io(out, 1 + SHIM_TAIL);
+  SHIM_RUN(c, "launch_l2norm", launch_l2norm(c.st, C, ea, dX, part, dout));
+}
+int shim_stat_parts() { return STAT_PARTS; }
+// X [nu]; cellvals [2 C + 8 + 4 STAT_PARTS + SHIM_TAIL]: the cell means of |v| [C] and of det(I + grad d) [C], then (sum, min, max
+// of the first, min of the second), four unused, and the partials of the reduction's first stage
+int shim_cell_stats(int64_t C, int64_t nu, int64_t nrank, const double* geom, const int32_t* cell_rank, const int32_t* cell_prow,
+                    const double* X, double* cellvals) {
+  if (C < 1 || 6 * nrank > nu) { g_err = "shim_cell_stats: no cells, or node ranks beyond the state"; return 3; }
+  if (const int rc = indices_checked("shim_cell_stats ranks", cell_rank, 10 * C, nrank)) return rc;
+  if (const int rc = indices_checked("shim_cell_stats pressure rows", cell_prow, 4 * C, nu)) return rc;
+  Call c;
+  c.note(upload_tables());
+  ElemArrays ea{};
+  ea.geom = c.in(geom, (size_t)(10 * C));
+  ea.cell_rank = c.in(cell_rank, (size_t)(10 * C));
+  ea.cell_prow = c.in(cell_prow, (size_t)(4 * C));
+  const double* dX = c.in(X, (size_t)nu);
+  double* dcv = c.io(cellvals, (size_t)(2 * C + 8 + 4 * STAT_PARTS) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_cell_stats", launch_cell_stats(c.st, C, ea, dX, dcv, dcv + 2 * C));
+}
+// cells [n] (below C), bary [n][4], X [nu]; out [7 n + SHIM_TAIL] = d(3), v(3), p per point
+int shim_probe(int64_t n, int64_t C, int64_t nu, const int32_t* cell_dofs, const int32_t* cells, const double* bary, const double* X,
+               double* out) {
+  if (n < 1) { g_err = "shim_probe: no points"; return 3; }
+  if (const int rc = indices_checked("shim_probe dofs", cell_dofs, NLOC * C, nu)) return rc;
+  if (const int rc = indices_checked("shim_probe cells", cells, n, C)) return rc;
+  Call c;
+  ElemArrays ea{};
+  ea.cell_dofs = c.in(cell_dofs, (size_t)(NLOC * C));
+  const int32_t* dc = c.in(cells, (size_t)n);
+  const double* db = c.in(bary, (size_t)(4 * n));
+  const double* dX = c.in(X, (size_t)nu);
+  double* dout = c.io(out, (size_t)(7 * n) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_probe", launch_probe(c.st, n, ea, dc, db, dX, dout));
+}
+
 // ---- a live context's preconditioner arrays (FsiCtx of fsi_context.hpp, as the library was compiled) -----------------------
 // shim_ctx_info: N2, V, nS, sb_nblocks, tiled, tile_nodes, tile_max_nu, schur_tiled, schur_tile, s_tile_max_nu, sweeps_fp16,
 // a32_ptail, a32_tail_src, a32_tail_nnz, op32_ok, kry_fp32, drows_ok, mg_nc, mg_cnnz, mg_ready, sbmg_nc, sbmg_nblk, sbmg_ready,
