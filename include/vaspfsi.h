@@ -327,6 +327,20 @@ int fsi_hemo_sample(FsiCtx* ctx, double* wss_out);
  * TWSSG = sum of the P1-projected |(tau - tau_prev) / dt_sample| / n; IEEE inf / NaN where a denominator vanishes.
  * *samples (nullable) = n.  FSI_ERR_INVALID without a session or before the first sample.  The session stays open. */
 int fsi_hemo_indices(FsiCtx* ctx, double* out, int64_t* samples);
+/* Replaces: nothing in the reference, whose frame loop [REF .../compute_hemodynamics.py:257-319] cannot be left and entered
+ * again: the session's accumulator as it stands, for a checkpoint.  With nd = 3 nf DG1 dofs (facet f, vertex k -> 3 f + k)
+ * acc_out[24 nf] = sum_tau[nd][3], tau_prev[nd][3], sum_mag[nd], sum_twssg[nd], one block after the other: the sum of tau,
+ * the tau of the last sample, the sum of |tau| and the sum of the projected |(tau - tau_prev) / dt_sample|.  *samples
+ * (nullable) = the number of samples.  Stream-ordered behind the samples taken; finished when the call returns.
+ * FSI_ERR_INVALID without an open session, with a null acc_out and for a partitioned context. */
+int fsi_hemo_export(FsiCtx* ctx, double* acc_out, int64_t* samples);
+/* Replaces: the zero start of fsi_hemo_begin after a restart: acc[24 nf] (the layout of fsi_hemo_export, nf that of the
+ * open session - the caller checks that the exporting session had the same facets) and samples >= 0 replace the session's
+ * sums and its count, so the first TWSSG term of the continued run is formed with the tau_prev that was carried, not with
+ * zero.  A run that samples k states, exports, imports into a new session on the same facets and samples the rest forms
+ * the bits of an unsplit run.  FSI_ERR_INVALID without an open session, with a null acc, samples < 0 and for a partitioned
+ * context; a refused call leaves the session as it was. */
+int fsi_hemo_import(FsiCtx* ctx, const double* acc, int64_t samples);
 /* Closes the session and frees its device memory (fsi_destroy does the same). */
 int fsi_hemo_end(FsiCtx* ctx);
 
@@ -344,6 +358,15 @@ int fsi_stress_sample(FsiCtx* ctx, double* frame_out);
  * out[2][ncell][4] = MaxPrincipalStress_avg, MaxPrincipalStrain_avg = the sums of the sampled DG1 coefficients / n.
  * *samples (nullable) = n.  FSI_ERR_INVALID without a session or before the first sample.  The session stays open. */
 int fsi_stress_averages(FsiCtx* ctx, double* out, int64_t* samples);
+/* Replaces: nothing in the reference (its frame loop [REF .../compute_stress_strain.py:188-250] runs in one go): the
+ * session's sums for a checkpoint, sums_out[n][8] = per cell the sums of MaxPrincipalStress[4] and MaxPrincipalStrain[4]
+ * over the samples, and *samples (nullable) their number.  Stream-ordered; finished when the call returns.
+ * FSI_ERR_INVALID without an open session, with a null sums_out and for a partitioned context. */
+int fsi_stress_export(FsiCtx* ctx, double* sums_out, int64_t* samples);
+/* Replaces: the zero start of fsi_stress_begin after a restart: sums[n][8] (the layout of fsi_stress_export, n that of the
+ * open session) and samples >= 0 replace the session's sums and its count.  FSI_ERR_INVALID without an open session, with
+ * null sums, samples < 0 and for a partitioned context; a refused call leaves the session as it was. */
+int fsi_stress_import(FsiCtx* ctx, const double* sums, int64_t samples);
 /* Closes the session and frees its device memory (fsi_destroy does the same). */
 int fsi_stress_end(FsiCtx* ctx);
 
@@ -409,6 +432,19 @@ int fsi_band_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, d
  * FSI_ERR_INVALID "node out of range"; a node may be listed twice).  out[npoints][frames][1 + ncomp]: the magnitude
  * sqrt((x x + y y) + z z) first (for p the value itself), then the ncomp values. */
 int fsi_band_trace(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t npoints, const int32_t* points, double* out);
+/* Replaces: reading frames first .. first + count - 1 of <quantity>.h5 back [REF .../postprocessing_h5py_common.py:154-409],
+ * for a checkpoint: out[count][n][ncomp], the raw history's frames in one copy (the history is frame-major).  first is an
+ * index into the history, as in a raw fsi_band_fetch, whatever fsi_band_select holds.  Stream-ordered behind the frames
+ * sampled; finished when the call returns.  FSI_ERR_INVALID unless first >= 0, count >= 1 and first + count <= the recorded
+ * frames, with a null out, without an open session and for a partitioned context. */
+int fsi_band_export(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count, double* out);
+/* Replaces: count calls of fsi_band_sample after a restart: frames[count][n][ncomp] (what fsi_band_export gave, of a
+ * session on the same nodes) are appended to the history - the recorded frames grow by count, the filtered series and the
+ * amplitude are invalidated and the selection is reset to every recorded frame.  The filter, the amplitude and the traces
+ * of the continued history are those of one that was sampled in one go, bit for bit.  FSI_ERR_INVALID when the recorded
+ * frames + count exceed the capacity, with count < 1 or null frames, without an open session and for a partitioned context;
+ * a refused call leaves the session as it was. */
+int fsi_band_import(FsiCtx* ctx, int32_t quantity, int64_t count, const double* frames);
 /* Closes the session of the quantity and frees its device memory (fsi_destroy does the same). */
 int fsi_band_end(FsiCtx* ctx, int32_t quantity);
 
@@ -460,6 +496,14 @@ int fsi_spec_spectrogram(FsiCtx* ctx, int32_t quantity, int64_t nperseg, int64_t
  * [REF .../spectrograms.py:409-419]: out_power[frames / 2 + 1], the spectrogram of one segment of all recorded frames with nfft =
  * frames (any length, odd included), window[frames]. */
 int fsi_spec_periodogram(FsiCtx* ctx, int32_t quantity, const double* window, int32_t scaling, double fs, double* out_power);
+/* Replaces: reading rows back from <quantity>_<component>.npz [REF .../spectrograms.py:291-329], for a checkpoint:
+ * out[count][rows], frames first .. first + count - 1 of the raw history in one copy.  The rows are what was recorded: with
+ * FSI_SPEC_MAG the magnitudes.  Checks and refusals as fsi_band_export. */
+int fsi_spec_export(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count, double* out);
+/* Replaces: count calls of fsi_spec_sample after a restart: frames[count][rows] (what fsi_spec_export gave, of a session
+ * on the same rows) are appended to the history and, as recording a frame does, the raw series is selected.  Checks and
+ * refusals as fsi_band_import. */
+int fsi_spec_import(FsiCtx* ctx, int32_t quantity, int64_t count, const double* frames);
 /* Closes the session of the quantity and frees its device memory (fsi_destroy does the same). */
 int fsi_spec_end(FsiCtx* ctx, int32_t quantity);
 

@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_end", "fsi_band_begin", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_end", "fsi_spec_begin", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_spec_begin", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -151,10 +151,14 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_hemo_begin.argtypes = [vp, i64, vp, vp, dbl, dbl]
     lib.fsi_hemo_sample.argtypes = [vp, vp]
     lib.fsi_hemo_indices.argtypes = [vp, vp, C.POINTER(i64)]
+    lib.fsi_hemo_export.argtypes = [vp, vp, C.POINTER(i64)]
+    lib.fsi_hemo_import.argtypes = [vp, vp, i64]
     lib.fsi_hemo_end.argtypes = [vp]
     lib.fsi_stress_begin.argtypes = [vp, i64, vp]
     lib.fsi_stress_sample.argtypes = [vp, vp]
     lib.fsi_stress_averages.argtypes = [vp, vp, C.POINTER(i64)]
+    lib.fsi_stress_export.argtypes = [vp, vp, C.POINTER(i64)]
+    lib.fsi_stress_import.argtypes = [vp, vp, i64]
     lib.fsi_stress_end.argtypes = [vp]
     lib.fsi_band_begin.argtypes = [vp, i32, i64, vp, vp, i64]
     lib.fsi_band_sample.argtypes = [vp, i32]
@@ -164,6 +168,8 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_band_select.argtypes = [vp, i32, i64, i64, i64]
     lib.fsi_band_filter_next.argtypes = [vp, i32, i32, vp, vp, vp, i32]
     lib.fsi_band_trace.argtypes = [vp, i32, i32, i64, vp, vp]
+    lib.fsi_band_export.argtypes = [vp, i32, i64, i64, vp]
+    lib.fsi_band_import.argtypes = [vp, i32, i64, vp]
     lib.fsi_band_end.argtypes = [vp, i32]
     lib.fsi_spec_begin.argtypes = [vp, i32, i64, vp, vp, i32, i64]
     lib.fsi_spec_sample.argtypes = [vp, i32]
@@ -171,6 +177,8 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_spec_fetch.argtypes = [vp, i32, i32, i64, vp]
     lib.fsi_spec_spectrogram.argtypes = [vp, i32, i64, i64, i64, vp, i32, dbl, vp]
     lib.fsi_spec_periodogram.argtypes = [vp, i32, vp, i32, dbl, vp]
+    lib.fsi_spec_export.argtypes = [vp, i32, i64, i64, vp]
+    lib.fsi_spec_import.argtypes = [vp, i32, i64, vp]
     lib.fsi_spec_end.argtypes = [vp, i32]
     lib.fsi_num_dofs.argtypes = [vp]
     lib.fsi_num_dofs.restype = i64
@@ -494,6 +502,27 @@ class HipBackend:
         res["samples"] = int(n.value)
         return res
 
+    def _sums(self, what: str, sums, n: int) -> np.ndarray:
+        """The sums handed to an import as the library takes them; another size than the open session's is refused here,
+        where the size is known (the C call takes a pointer)."""
+        a = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1)
+        if a.size != n:
+            raise FsiError(1, f"{what}: sums of {a.size} values, the open session has {n}")
+        return a
+
+    def hemodynamics_export(self):
+        """(acc, samples): the session's accumulator, (24 nf,) in the layout of fsi_hemo_export, and its sample count."""
+        out = np.empty(24 * getattr(self, "_hemo_nf", 0))
+        n = C.c_int64(0)
+        self._check(self.lib.fsi_hemo_export(self.ctx, _ptr(out), C.byref(n)))
+        return out, int(n.value)
+
+    def hemodynamics_import(self, acc, samples: int) -> None:
+        """Replace the open session's accumulator and sample count by exported ones (fsi_hemo_import); an accumulator of
+        another number of facets is refused."""
+        a = self._sums("hemodynamics_import", acc, 24 * getattr(self, "_hemo_nf", 0))
+        self._check(self.lib.fsi_hemo_import(self.ctx, _ptr(a), int(samples)))
+
     def hemodynamics_end(self) -> None:
         self._check(self.lib.fsi_hemo_end(self.ctx))
 
@@ -522,6 +551,19 @@ class HipBackend:
         k = C.c_int64(0)
         self._check(self.lib.fsi_stress_averages(self.ctx, _ptr(out), C.byref(k)))
         return dict(MaxPrincipalStress_avg=out[0].copy(), MaxPrincipalStrain_avg=out[1].copy(), samples=int(k.value))
+
+    def stress_strain_export(self):
+        """(sums, samples): the session's sums, (n, 8) as fsi_stress_export, and its sample count."""
+        out = np.empty((getattr(self, "_stress_n", 0), 8))
+        k = C.c_int64(0)
+        self._check(self.lib.fsi_stress_export(self.ctx, _ptr(out), C.byref(k)))
+        return out, int(k.value)
+
+    def stress_strain_import(self, sums, samples: int) -> None:
+        """Replace the open session's sums and sample count by exported ones (fsi_stress_import); sums of another number of
+        cells are refused."""
+        a = self._sums("stress_strain_import", sums, 8 * getattr(self, "_stress_n", 0))
+        self._check(self.lib.fsi_stress_import(self.ctx, _ptr(a), int(samples)))
 
     def stress_strain_end(self) -> None:
         self._check(self.lib.fsi_stress_end(self.ctx))
@@ -598,6 +640,24 @@ class HipBackend:
                                             C.byref(mx) if with_max else None, C.byref(am) if with_max else None))
         return (out, mx.value, int(am.value)) if with_max else out
 
+    def hi_pass_export(self, quantity: str, first: int, count: int) -> np.ndarray:
+        """Raw frames ``first .. first + count - 1`` of the history as (count, n, ncomp), in one copy (fsi_band_export)."""
+        n, ncomp = self._band_shape[quantity]
+        out = np.empty((max(int(count), 0), n, ncomp))
+        self._check(self.lib.fsi_band_export(self.ctx, self.BAND_QUANTITY[quantity], int(first), int(count), _ptr(out)))
+        return out
+
+    def hi_pass_import(self, quantity: str, frames) -> None:
+        """Append exported frames, (count, n, ncomp), to the history as that many samples would have (fsi_band_import)."""
+        n, ncomp = self._band_shape[quantity]
+        x = np.ascontiguousarray(frames, dtype=np.float64)
+        if x.ndim < 1 or x.size != len(x) * n * ncomp:
+            raise FsiError(1, f"hi_pass_import: frames of shape {x.shape}, the open session has frames of {(n, ncomp)}")
+        self._check(self.lib.fsi_band_import(self.ctx, self.BAND_QUANTITY[quantity], len(x), _ptr(x)))
+        rec = self._band_frames[quantity]
+        rec[0] += len(x)
+        rec[1] = rec[0]
+
     def hi_pass_end(self, quantity: str) -> None:
         self._check(self.lib.fsi_band_end(self.ctx, self.BAND_QUANTITY[quantity]))
 
@@ -667,6 +727,21 @@ class HipBackend:
         out = np.empty(frames // 2 + 1)
         self._check(self.lib.fsi_spec_periodogram(self.ctx, self.BAND_QUANTITY[quantity], _ptr(w), self.SPEC_SCALING[scaling], float(fs), _ptr(out)))
         return out
+
+    def spec_export(self, quantity: str, first: int, count: int) -> np.ndarray:
+        """Raw frames ``first .. first + count - 1`` of the history as (count, rows), in one copy (fsi_spec_export)."""
+        out = np.empty((max(int(count), 0), self._spec_open(quantity)[0]))
+        self._check(self.lib.fsi_spec_export(self.ctx, self.BAND_QUANTITY[quantity], int(first), int(count), _ptr(out)))
+        return out
+
+    def spec_import(self, quantity: str, frames) -> None:
+        """Append exported frames, (count, rows), to the history as that many samples would have (fsi_spec_import)."""
+        shape = self._spec_open(quantity)
+        x = np.ascontiguousarray(frames, dtype=np.float64)
+        if x.ndim < 1 or x.size != len(x) * shape[0]:
+            raise FsiError(1, f"spec_import: frames of shape {x.shape}, the open session has {shape[0]} rows")
+        self._check(self.lib.fsi_spec_import(self.ctx, self.BAND_QUANTITY[quantity], len(x), _ptr(x)))
+        shape[1] += len(x)
 
     def spec_end(self, quantity: str) -> None:
         self._check(self.lib.fsi_spec_end(self.ctx, self.BAND_QUANTITY[quantity]))

@@ -143,6 +143,61 @@ const double* history_frame(const FsiCtx::History* s, bool filtered, int64_t k) 
   return (filtered ? s->work.p + (size_t)s->padlen * s->nrow : s->hist.p) + (size_t)k * s->nrow;
 }
 
+// the export and import calls refuse a partitioned context before anything else, as the begin calls do
+bool partitioned(FsiCtx* ctx, const char* fn) {
+  if (ctx->part) ctx->err = std::string(fn) + ": partitioned contexts are not supported";
+  return ctx->part;
+}
+
+// raw frames first .. first + count - 1 of the history to the host, out[count][nrow]: frame-major, so one copy, behind
+// whatever was sampled on the stream; it has finished when the call returns
+int history_export(FsiCtx* ctx, const FsiCtx::History* s, const char* fn, int64_t first, int64_t count, double* out) {
+  if (!out) { ctx->err = std::string(fn) + ": out is NULL"; return FSI_ERR_INVALID; }
+  if (first < 0 || count < 1 || first > s->frames - count) {
+    ctx->err = std::string(fn) + ": needs first >= 0, count >= 1 and first + count <= the " + std::to_string(s->frames) + " recorded frames";
+    return FSI_ERR_INVALID;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipMemcpyAsync(out, s->hist.p + (size_t)first * s->nrow, (size_t)count * (size_t)s->nrow * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return FSI_OK;
+}
+
+// count frames appended to the history from the host, frames[count][nrow], as count samples would have left them; the
+// caller's array is free again when the call returns
+int history_import(FsiCtx* ctx, FsiCtx::History* s, const char* fn, int64_t count, const double* frames) {
+  if (count < 1 || !frames) { ctx->err = std::string(fn) + ": needs count >= 1 frames"; return FSI_ERR_INVALID; }
+  if (count > s->capacity - s->frames) {
+    ctx->err = std::string(fn) + ": " + std::to_string(s->frames) + " recorded frames + " + std::to_string(count) + " exceed the capacity of " +
+               std::to_string(s->capacity);
+    return FSI_ERR_INVALID;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipMemcpyAsync(s->hist.p + (size_t)s->frames * s->nrow, frames, (size_t)count * (size_t)s->nrow * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  s->frames += count;
+  s->filtered = false;        // a filtered series no longer covers the history
+  return FSI_OK;
+}
+
+// sums of a hemodynamics or a stress / strain session to the host and back: n doubles, with the sample count
+int sums_export(FsiCtx* ctx, const char* fn, const double* sums, size_t n, int64_t have, double* out, int64_t* samples) {
+  if (!out) { ctx->err = std::string(fn) + ": null output"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipMemcpyAsync(out, sums, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (samples) *samples = have;
+  return FSI_OK;
+}
+int sums_import(FsiCtx* ctx, const char* fn, double* sums, size_t n, const double* in, int64_t samples, int64_t* have) {
+  if (!in || samples < 0) { ctx->err = std::string(fn) + ": needs the sums and samples >= 0"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipMemcpyAsync(sums, in, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *have = samples;
+  return FSI_OK;
+}
+
 template <class S>
 int end_session(FsiCtx* ctx, S (&all)[3], int32_t q, const char* fn) {
   if (q < 0 || q > 2) { ctx->err = std::string(fn) + ": quantity must be 0 (d), 1 (v) or 2 (p)"; return FSI_ERR_INVALID; }
@@ -353,6 +408,22 @@ int fsi_hemo_indices(FsiCtx* ctx, double* out, int64_t* samples) {
   return FSI_OK;
 }
 
+int fsi_hemo_export(FsiCtx* ctx, double* acc_out, int64_t* samples) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_hemo_export")) return FSI_ERR_INVALID;
+  auto& h = ctx->hemo;
+  if (!h.open) { ctx->err = "fsi_hemo_export: no hemodynamics session (fsi_hemo_begin first)"; return FSI_ERR_INVALID; }
+  return sums_export(ctx, "fsi_hemo_export", h.acc.p, (size_t)h.nf * 24, h.samples, acc_out, samples);
+}
+
+int fsi_hemo_import(FsiCtx* ctx, const double* acc, int64_t samples) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_hemo_import")) return FSI_ERR_INVALID;
+  auto& h = ctx->hemo;
+  if (!h.open) { ctx->err = "fsi_hemo_import: no hemodynamics session (fsi_hemo_begin first)"; return FSI_ERR_INVALID; }
+  return sums_import(ctx, "fsi_hemo_import", h.acc.p, (size_t)h.nf * 24, acc, samples, &h.samples);
+}
+
 int fsi_hemo_end(FsiCtx* ctx) {
   if (!ctx) return FSI_ERR_INVALID;
   HIPCHK(hipSetDevice(ctx->device));
@@ -416,6 +487,22 @@ int fsi_stress_averages(FsiCtx* ctx, double* out, int64_t* samples) {
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (samples) *samples = s.samples;
   return FSI_OK;
+}
+
+int fsi_stress_export(FsiCtx* ctx, double* sums_out, int64_t* samples) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_stress_export")) return FSI_ERR_INVALID;
+  auto& s = ctx->stress;
+  if (!s.open) { ctx->err = "fsi_stress_export: no stress / strain session (fsi_stress_begin first)"; return FSI_ERR_INVALID; }
+  return sums_export(ctx, "fsi_stress_export", s.sums.p, (size_t)s.n * 8, s.samples, sums_out, samples);
+}
+
+int fsi_stress_import(FsiCtx* ctx, const double* sums, int64_t samples) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_stress_import")) return FSI_ERR_INVALID;
+  auto& s = ctx->stress;
+  if (!s.open) { ctx->err = "fsi_stress_import: no stress / strain session (fsi_stress_begin first)"; return FSI_ERR_INVALID; }
+  return sums_import(ctx, "fsi_stress_import", s.sums.p, (size_t)s.n * 8, sums, samples, &s.samples);
 }
 
 int fsi_stress_end(FsiCtx* ctx) {
@@ -605,6 +692,25 @@ int fsi_band_trace(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t npoints,
   return FSI_OK;
 }
 
+int fsi_band_export(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count, double* out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_export")) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_export");
+  if (!s) return FSI_ERR_INVALID;
+  return history_export(ctx, s, "fsi_band_export", first, count, out);
+}
+
+int fsi_band_import(FsiCtx* ctx, int32_t quantity, int64_t count, const double* frames) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_import")) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_import");
+  if (!s) return FSI_ERR_INVALID;
+  FSICHK(history_import(ctx, s, "fsi_band_import", count, frames));
+  s->window = -1;
+  s->sel_first = 0; s->sel_stride = 1; s->sel_count = -1;      // as fsi_band_sample: a selection covers the frames it was made on
+  return FSI_OK;
+}
+
 int fsi_band_end(FsiCtx* ctx, int32_t quantity) {
   if (!ctx) return FSI_ERR_INVALID;
   return end_session(ctx, ctx->band, quantity, "fsi_band_end");
@@ -698,6 +804,22 @@ int fsi_spec_periodogram(FsiCtx* ctx, int32_t quantity, const double* window, in
   }
   if (s->frames < 1) { ctx->err = "fsi_spec_periodogram: no recorded frames"; return FSI_ERR_INVALID; }
   return spec_power(ctx, s, "fsi_spec_periodogram", s->frames, s->frames, 1, s->frames, window, scaling, fs, out_power);
+}
+
+int fsi_spec_export(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count, double* out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_spec_export")) return FSI_ERR_INVALID;
+  auto* s = spec_session(ctx, quantity, "fsi_spec_export");
+  if (!s) return FSI_ERR_INVALID;
+  return history_export(ctx, s, "fsi_spec_export", first, count, out);
+}
+
+int fsi_spec_import(FsiCtx* ctx, int32_t quantity, int64_t count, const double* frames) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_spec_import")) return FSI_ERR_INVALID;
+  auto* s = spec_session(ctx, quantity, "fsi_spec_import");
+  if (!s) return FSI_ERR_INVALID;
+  return history_import(ctx, s, "fsi_spec_import", count, frames);      // filtered = false: the raw series is selected
 }
 
 int fsi_spec_end(FsiCtx* ctx, int32_t quantity) {

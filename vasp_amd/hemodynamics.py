@@ -18,12 +18,14 @@ cell without the opposite one, ascending - the order of ``HipBackend.wall_shear_
 from __future__ import annotations
 
 import os
+import re
 from pathlib import Path
-from typing import Dict, Tuple
+from typing import Dict, List, Tuple
 
 import numpy as np
 
 from .h5lite import Dataset, Group, H5Series, write_h5
+from .hi_pass import check_fingerprint, load_array, restart_entry, restart_refusal, save_array, sessions_folder, sha256_of
 from .mesh import FsiMesh
 
 INDEX_NAMES = ("TAWSS", "OSI", "RRT", "ECAP", "TWSSG")
@@ -80,8 +82,11 @@ def _dg1_group(values: np.ndarray, geometry: np.ndarray, topology: np.ndarray, d
     return g
 
 
-def _xdmf_grid(name: str, k: int, t: float, nf: int, nv: int, ncomp: int, celltype: str = "triangle") -> str:
-    h5, first = f"{name}.h5", f"{name}/{name}_0"
+def _xdmf_grid(name: str, k: int, t: float, nf: int, nv: int, ncomp: int, celltype: str = "triangle", h5: str = "",
+               first: int = 0) -> str:
+    """The grid of frame k; ``h5``: the file that holds it (default ``<name>.h5``), ``first``: the frame of that file that
+    carries the dof map and the mesh."""
+    h5, first = h5 or f"{name}.h5", f"{name}/{name}_{first}"
     topo_type, nvc = CELLS[celltype]
     ndofs = nvc * nf * ncomp
     att = ATTRIBUTE_TYPES[ncomp]
@@ -114,35 +119,85 @@ def _xdmf_head(name: str) -> str:
 XDMF_FOOTER = "    </Grid>\n  </Domain>\n</Xdmf>\n"
 
 
-class HemodynamicsWriter:
-    """``<results>/Hemodynamic_indices/``: ``write_wss`` appends one WSS frame (h5 and XDMF grow in place),
-    ``write_indices`` writes the five index files once."""
+class Dg1Series:
+    """One DG1 time series: ``<name>.h5`` and its XDMF, both grown in place one frame at a time.
 
-    def __init__(self, folder, geometry: np.ndarray, topology: np.ndarray):
-        self.folder = Path(folder)
-        self.folder.mkdir(parents=True, exist_ok=True)
+    ``adopt`` > 0 continues the series after ``--restart-folder`` the way ``output.VisualizationWriter`` continues its own:
+    the first ``adopt`` grids of the XDMF stay (later ones, written after the checkpoint by a run that was killed, are cut),
+    new frames go to ``<name>_run_<N>.h5`` with continued frame numbers, and the first group of the new file carries the dof
+    map and the mesh, as frame 0 does in the first."""
+
+    def __init__(self, folder: Path, name: str, ncomp: int, celltype: str, geometry: np.ndarray, topology: np.ndarray, adopt: int = 0):
+        self.folder, self.name, self.ncomp, self.celltype = Path(folder), name, ncomp, celltype
         self.geometry, self.topology = geometry, topology
-        self.frames = 0
-        self._wss = None
+        self.frames = self._first = 0           # frames of the series, and the first of them in this run's file
+        self.file = f"{name}.h5"
+        self._h5 = None
+        if adopt:
+            self._adopt(int(adopt))
 
-    def write_wss(self, tau: np.ndarray, t: float) -> None:
-        """tau (nf, 3, 3): the frame's WSS at the facet vertices."""
-        nf, nv = len(self.topology), len(self.geometry)
-        if tau.shape != (nf, 3, 3):
-            raise ValueError(f"WSS frame of shape {tau.shape}, expected {(nf, 3, 3)}")
-        if self._wss is None:
-            self._wss = H5Series(self.folder / "WSS.h5", Group(), "WSS")
+    def _adopt(self, frames: int) -> None:
+        path = self.folder / f"{self.name}.xdmf"
+        text = path.read_text() if path.exists() else ""
+        starts = [m.start() for m in re.finditer(r'^      <Grid Name="%s_\d+"' % re.escape(self.name), text, flags=re.M)]
+        if len(starts) < frames or not text.endswith(XDMF_FOOTER):
+            raise SystemExit(f"{path} lists {len(starts)} frames, the saved session state continues a series of {frames}")
+        ends = starts[1:] + [len(text) - len(XDMF_FOOTER)]
+        path.write_text(text[:ends[frames - 1]] + XDMF_FOOTER)
+        runs = [int(p.stem.rsplit("_", 1)[1]) for p in self.folder.glob(f"{self.name}_run_*.h5") if p.stem.rsplit("_", 1)[1].isdigit()]
+        self.file = f"{self.name}_run_{1 + max(runs, default=0)}.h5"
+        self.frames = self._first = frames
+
+    def append(self, values: np.ndarray, t: float) -> None:
         k = self.frames
-        self._wss.append_group(f"WSS_{k}", _dg1_group(tau, self.geometry, self.topology, dofmap=k == 0))
-        path = self.folder / "WSS.xdmf"
-        grid = _xdmf_grid("WSS", k, t, nf, nv, 3)
+        if self._h5 is None:
+            self._h5 = H5Series(self.folder / self.file, Group(), self.name)
+        self._h5.append_group(f"{self.name}_{k}", _dg1_group(values, self.geometry, self.topology, dofmap=k == self._first,
+                                                            celltype=self.celltype))
+        path = self.folder / f"{self.name}.xdmf"
+        grid = _xdmf_grid(self.name, k, t, len(self.topology), len(self.geometry), self.ncomp, self.celltype, self.file, self._first)
         if k == 0:
-            path.write_text(_xdmf_head("WSS") + grid + XDMF_FOOTER)
+            path.write_text(_xdmf_head(self.name) + grid + XDMF_FOOTER)
         else:                                   # the new grid overwrites the closing tags, which follow it again
             with open(path, "r+b") as f:
                 f.seek(-len(XDMF_FOOTER.encode()), os.SEEK_END)
                 f.write((grid + XDMF_FOOTER).encode())
         self.frames += 1
+
+    def close(self) -> None:
+        if self._h5 is not None:
+            self._h5.close()
+            self._h5 = None
+
+
+def xdmf_frames(path) -> List[Tuple[float, str, int]]:
+    """(time, h5 file, frame number) of every grid of a DG1 series' XDMF, in its order."""
+    text = Path(path).read_text()
+    times = [float(x) for x in re.findall(r'<Time Value="(.+?)"', text)]
+    vectors = re.findall(r'"HDF">([^:<]+):[^<]*?_(\d+)/vector</DataItem>', text)
+    return [(t, f, int(k)) for t, (f, k) in zip(times, vectors)]
+
+
+class HemodynamicsWriter:
+    """``<results>/Hemodynamic_indices/``: ``write_wss`` appends one WSS frame (h5 and XDMF grow in place),
+    ``write_indices`` writes the five index files once.  ``adopt``: the frames of the WSS series a restarted run continues."""
+
+    def __init__(self, folder, geometry: np.ndarray, topology: np.ndarray, adopt: int = 0):
+        self.folder = Path(folder)
+        self.folder.mkdir(parents=True, exist_ok=True)
+        self.geometry, self.topology = geometry, topology
+        self._wss = Dg1Series(self.folder, "WSS", 3, "triangle", geometry, topology, adopt)
+
+    @property
+    def frames(self) -> int:
+        return self._wss.frames
+
+    def write_wss(self, tau: np.ndarray, t: float) -> None:
+        """tau (nf, 3, 3): the frame's WSS at the facet vertices."""
+        nf = len(self.topology)
+        if tau.shape != (nf, 3, 3):
+            raise ValueError(f"WSS frame of shape {tau.shape}, expected {(nf, 3, 3)}")
+        self._wss.append(tau, t)
 
     def write_indices(self, indices: Dict[str, np.ndarray]) -> None:
         """indices: TAWSS, OSI, RRT, ECAP, TWSSG as (nf, 3) arrays; each to ``<name>.{h5,xdmf}`` at time 0."""
@@ -158,9 +213,7 @@ class HemodynamicsWriter:
             (self.folder / f"{name}.xdmf").write_text(_xdmf_head(name) + _xdmf_grid(name, 0, 0.0, nf, nv, 1) + XDMF_FOOTER)
 
     def close(self) -> None:
-        if self._wss is not None:
-            self._wss.close()
-            self._wss = None
+        self._wss.close()
 
 
 def osi_range_message(osi: np.ndarray, tol: float = 1e-12) -> str:
@@ -177,7 +230,9 @@ def hemodynamics_refusal(v: dict, world: int, backend_cls) -> str:
     if not v.get("save_step"):
         return "--hemodynamics samples the saved frames: it needs --save-step"
     if v.get("restart_folder"):
-        return "--hemodynamics does not carry its sums through a checkpoint: it cannot be used with --restart-folder"
+        why = restart_refusal(v, HemodynamicsRun.key, HemodynamicsRun.words)
+        if why:
+            return why
     if world > 1:
         return "--hemodynamics runs on one rank only (WORLD_SIZE > 1)"
     if backend_cls is not None and not hasattr(backend_cls, "hemodynamics_begin"):
@@ -190,17 +245,40 @@ class HemodynamicsRun:
     frame per saved Visualization frame, the indices at the end.  ``dt_sample`` = dt * save_step; mu = ``mu_f`` (its first
     entry when it is a list, as the reference's ``vasp-compute-hemo`` takes one viscosity)."""
 
+    key, option = "hemodynamics", "--hemodynamics"
+    words = "--hemodynamics cannot continue under --restart-folder"
+
     def __init__(self, backend, mesh: FsiMesh, ns: dict):
         mu = ns["mu_f"][0] if isinstance(ns["mu_f"], (list, tuple)) else ns["mu_f"]
         dt_sample = float(ns["dt"]) * int(ns["save_step"])
         _, cells, local = fluid_boundary_facets(mesh, ns["dx_f_id"])
         geometry, topology = boundary_triangles(mesh, cells, local)
         self.backend = backend
+        self.fingerprint = dict(dt_sample=dt_sample, mu=float(mu), rows=len(cells), facets=sha256_of(cells, local))
+        self.times: List[float] = []
+        entry = restart_entry(ns, self.key, self.words)
+        if entry is not None:
+            check_fingerprint(self.option, "the wall shear stress", entry["fingerprint"], self.fingerprint)
         backend.hemodynamics_begin(cells, local, float(mu), dt_sample)
-        self.writer = HemodynamicsWriter(Path(ns["results_folder"]) / "Hemodynamic_indices", geometry, topology)
+        if entry is not None:                   # the sums, tau_prev and the count of the run that wrote the checkpoint
+            acc = load_array(sessions_folder(ns["restart_folder"]) / "hemodynamics.npy", entry["sha256"], self.option)
+            backend.hemodynamics_import(acc, int(entry["samples"]))
+            self.times = [float(x) for x in entry["times"]]
+        self.writer = HemodynamicsWriter(Path(ns["results_folder"]) / "Hemodynamic_indices", geometry, topology,
+                                         adopt=int(entry["series_frames"]) if entry is not None else 0)
 
     def sample(self, t: float, state=None) -> None:
         self.writer.write_wss(self.backend.hemodynamics_sample(wss=True), t)
+        self.times.append(float(t))
+
+    def save(self, folder, t: float, counter: int) -> dict:
+        """The accumulator to ``hemodynamics.npy``; returns the manifest's entry - None for a backend that cannot hand its
+        accumulator out: without an entry a restart with the option is refused."""
+        if not hasattr(self.backend, "hemodynamics_export"):
+            return None
+        acc, samples = self.backend.hemodynamics_export()
+        return dict(samples=samples, times=list(self.times), fingerprint=self.fingerprint, series_frames=self.writer.frames,
+                    sha256=save_array(Path(folder) / "hemodynamics.npy", acc))
 
     def finish(self, out=print) -> None:
         """The five index files (over the frames sampled so far) and the reference's OSI range check as a log line."""

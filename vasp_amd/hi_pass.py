@@ -13,13 +13,19 @@ This module holds
 * the writer of the reference's files and the driver's side of ``--hi-pass`` (``HiPassRun``): one series per band, with
   ``--hi-pass-multiband`` one more that went through all bands in order, each passed or stopped
   [REF create_hi_pass_viz.py:532-545,191-198,651-657]; a frame window and stride (``--hi-pass-stride``,
-  ``--hi-pass-start-time``, ``--hi-pass-end-time``); the raw series of listed nodes (``--hi-pass-point-ids``).
+  ``--hi-pass-start-time``, ``--hi-pass-end-time``); the raw series of listed nodes (``--hi-pass-point-ids``);
+* what the four post-processing options share to go through a checkpoint: the manifest and the files of
+  ``<results>/Checkpoint/sessions/`` and the checks of a restart (``save_sessions``, ``restart_entry``), and the saving and
+  restoring of a recorded history (``SessionRun``).
 
 What a filter stage and a trace cost on a mesh of the benchmark's size has not been measured.
 Not done: the reference's ``strain`` / ``stress`` quantities.
 """
 from __future__ import annotations
 
+import hashlib
+import json
+import os
 from pathlib import Path
 from typing import List, Optional, Tuple
 
@@ -229,6 +235,20 @@ class HostHistory:
     def filter(self, b=None, a=None, zi=None, padlen: int = 0) -> None:
         self.filtered = None if b is None else filtfilt_rows(b, a, np.stack(self.raw), zi, padlen)
 
+    def export(self, first: int, count: int) -> np.ndarray:
+        """Raw frames ``first .. first + count - 1``, frame-major: what ``HipBackend.<prefix>_export`` returns."""
+        if first < 0 or count < 1 or first + count > len(self.raw):
+            raise RuntimeError(f"{self.what} export: needs first >= 0, count >= 1 and first + count <= the {len(self.raw)} recorded frames")
+        return np.stack(self.raw[first:first + count])
+
+    def import_(self, frames) -> None:
+        """Append exported frames as that many samples would have; past the capacity nothing is appended."""
+        frames = np.asarray(frames, dtype=np.float64)
+        if len(self.raw) + len(frames) > self.capacity:
+            raise RuntimeError(f"{self.what} import: {len(self.raw)} recorded frames + {len(frames)} exceed the capacity of {self.capacity}")
+        for frame in frames:
+            self.sample(frame)
+
     def end(self) -> None:
         pass
 
@@ -302,8 +322,118 @@ class DeviceSession:
         self.backend, self.prefix, self.q = backend, prefix, q
 
     def __getattr__(self, name: str):
-        call = getattr(self.backend, f"{self.prefix}_{name}")
+        call = getattr(self.backend, f"{self.prefix}_{name.rstrip('_')}")       # import_ -> <prefix>_import
         return lambda *args: call(self.q, *args)
+
+
+# ------------------------------------------------------------------------------------------------
+# session state through a checkpoint: <results>/Checkpoint/sessions/
+# ------------------------------------------------------------------------------------------------
+
+MANIFEST = "sessions.json"
+SLAB_BYTES = 1 << 28                            # host memory of one export / import call of a history
+
+
+def sessions_folder(results) -> Path:
+    return Path(str(results)) / "Checkpoint" / "sessions"
+
+
+def sha256_of(*arrays) -> str:
+    """SHA-256 of the listed arrays' shapes, types and bytes (None: an absent list)."""
+    h = hashlib.sha256()
+    for a in arrays:
+        if a is None:
+            h.update(b"none;")
+            continue
+        a = np.ascontiguousarray(a)
+        h.update(f"{a.dtype.str}{a.shape};".encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def checkpoint_position(v: dict) -> Tuple[float, int]:
+    """(t, counter) of ``<restart_folder>/Checkpoint/default_variables.json``: where the restarted time loop starts."""
+    path = Path(str(v["restart_folder"])) / "Checkpoint" / "default_variables.json"
+    if not path.exists():
+        raise SystemExit(f"--restart-folder: {path} not found")
+    meta = json.loads(path.read_text())
+    return float(meta["t"]), int(meta["counter"])
+
+
+def restart_refusal(v: dict, key: str, words: str) -> str:
+    """Why the option ``key`` cannot continue from ``v["restart_folder"]`` ('' if it can): there is no saved state for it
+    (``words``: the option's own sentence, which names --restart-folder), or the state belongs to another checkpoint."""
+    path = sessions_folder(v["restart_folder"]) / MANIFEST
+    manifest = json.loads(path.read_text()) if path.exists() else None
+    if manifest is None or key not in manifest.get("sessions", {}):
+        return (f"{words}: the run in {v['restart_folder']} saved no state for the option (looked for "
+                f"{'an entry ' + repr(key) + ' in ' if manifest is not None else ''}{path})")
+    t, counter = checkpoint_position(v)
+    if int(manifest["counter"]) != counter or float(manifest["t"]) != t:
+        return (f"--restart-folder: the session state in {path} belongs to counter = {manifest['counter']}, t = {manifest['t']!r}, the "
+                f"checkpoint beside it to counter = {counter}, t = {t!r}: one of the two was written by another run")
+    return ""
+
+
+def restart_entry(v: dict, key: str, words: str) -> Optional[dict]:
+    """None without --restart-folder, else the saved entry of the option ``key``; SystemExit with ``restart_refusal``."""
+    if not v.get("restart_folder"):
+        return None
+    why = restart_refusal(v, key, words)
+    if why:
+        raise SystemExit(why)
+    return json.loads((sessions_folder(v["restart_folder"]) / MANIFEST).read_text())["sessions"][key]
+
+
+def check_fingerprint(option: str, what: str, saved: dict, now: dict) -> None:
+    """SystemExit naming every field in which what was recorded differs from what the restarted run would record."""
+    bad = [f"{k} (saved {saved.get(k)!r}, now {now.get(k)!r})" for k in now if saved.get(k) != now.get(k)]
+    if bad:
+        raise SystemExit(f"{option}: the saved state of {what} was recorded otherwise than this run would record, it differs in "
+                         + ", ".join(bad))
+
+
+def frame_times(v: dict, key: str, words: str) -> Tuple[List[float], int]:
+    """(times, saved): the times of the frames a run with the parameters ``v`` hands to the option ``key`` - under
+    --restart-folder those its saved state holds, then those the time loop saves from the checkpoint on - and how many of
+    them are saved ones."""
+    entry = restart_entry(v, key, words)
+    if entry is None:
+        return saved_times(v), 0
+    t, counter = checkpoint_position(v)
+    past = [float(x) for x in entry["times"]]
+    return past + saved_times(dict(v, t=t, counter=counter)), len(past)
+
+
+def save_sessions(sessions, results, t: float, counter: int) -> None:
+    """Every session's ``save`` into ``<results>/Checkpoint/sessions/``, then the manifest of what they wrote - last, under a
+    temporary name and renamed, so that a manifest always describes complete files.  It names the checkpoint it belongs to
+    and lists the running sessions only: a saved session that this run does not continue has missed frames."""
+    folder = sessions_folder(results)
+    folder.mkdir(parents=True, exist_ok=True)
+    entries = {s.key: s.save(folder, t, counter) for s in sessions}
+    manifest = dict(t=float(t), counter=int(counter), sessions={k: e for k, e in entries.items() if e is not None})
+    tmp = folder / ("tmp_" + MANIFEST)
+    tmp.write_text(json.dumps(manifest))
+    os.replace(tmp, folder / MANIFEST)
+
+
+def save_array(path: Path, a: np.ndarray) -> str:
+    """``a`` to ``path`` (.npy) through a temporary name; returns the SHA-256 the manifest keeps of it."""
+    tmp = path.with_name("tmp_" + path.name)
+    with open(tmp, "wb") as f:
+        np.save(f, np.ascontiguousarray(a, dtype=np.float64))
+    os.replace(tmp, path)
+    return sha256_of(a)
+
+
+def load_array(path: Path, sha256: str, option: str) -> np.ndarray:
+    if not path.exists():
+        raise SystemExit(f"{option}: {path} not found")
+    a = np.load(path)
+    if sha256_of(a) != sha256:
+        raise SystemExit(f"{option}: {path} is not the file the manifest beside it describes (SHA-256 differs)")
+    return a
 
 
 class SessionRun:
@@ -311,24 +441,72 @@ class SessionRun:
     backend without ``<prefix>_begin``, on the host; one recorded frame per saved frame; every session ended after ``write``."""
     prefix = ""
 
+    key = option = words = ""                       # the manifest's key, the option and its sentence about --restart-folder
+
     def open_sessions(self, backend, ns: dict, begin_args, host_session) -> None:
-        """``begin_args(q)``: the device session's arguments before the capacity; ``host_session(q, capacity)``: its host twin."""
+        """``begin_args(q)``: the device session's arguments before the capacity; ``host_session(q, capacity)``: its host twin.
+        Under --restart-folder the saved histories are checked against ``fingerprint(q)`` and imported."""
         self.device = hasattr(backend, self.prefix + "_begin")
-        self.frames = 0
+        self.frames = self.saved = 0                # recorded frames, and how many of them the history files hold
+        self.times: List[float] = []
         self.sessions = {}
-        capacity = expected_frames(ns) + 1
+        entry = restart_entry(ns, self.key, self.words)
+        if entry is not None:
+            missing = [q for q in self.quantities if q not in entry["quantities"]]
+            if missing:
+                raise SystemExit(f"{self.option} {' '.join(missing)}: the run in {ns['restart_folder']} recorded "
+                                 f"{' '.join(entry['quantities']) or 'none'}; a quantity added at a restart has no past")
+            for q in self.quantities:
+                check_fingerprint(self.option, q, entry["quantities"][q], self.fingerprint(q))
+            self.times = [float(x) for x in entry["times"]]
+            self.frames = self.saved = int(entry["frames"])
+        capacity = self.frames + expected_frames(ns) + 1
         for q in self.quantities:
             if self.device:
                 self.sessions[q] = DeviceSession(backend, self.prefix, q)
                 self.sessions[q].begin(*begin_args(q), capacity)
             else:
                 self.sessions[q] = host_session(q, capacity)
+        if self.saved:
+            folder = sessions_folder(ns["restart_folder"])
+            for q in self.quantities:
+                self._read_history(folder / f"{self.file_stem}_{q}.f64", q)
 
     def sample(self, t: float, state) -> None:
         """Record dvp_["n"]; ``state``: a callable giving the host copy, used only without the device session."""
         for q, s in self.sessions.items():
             s.sample() if self.device else s.sample(self._host_frame(q, state()))
         self.frames += 1
+        self.times.append(float(t))
+
+    def _slab(self, q: str) -> int:
+        return max(1, SLAB_BYTES // (8 * self.rows(q)))
+
+    def _read_history(self, path: Path, q: str) -> None:
+        """The first ``saved`` frames of a history file into the session, a slab at a time; bytes beyond them are the stale
+        tail of a save that ended before its manifest."""
+        rows, need = self.rows(q), 8 * self.rows(q) * self.saved
+        have = path.stat().st_size if path.exists() else 0
+        if have < need:
+            raise SystemExit(f"{self.option}: {path} holds {have} bytes, the {self.saved} frames of {rows} rows the manifest "
+                             f"beside it names need {need}")
+        with open(path, "rb") as f:
+            for k in range(0, self.saved, self._slab(q)):
+                count = min(self._slab(q), self.saved - k)
+                self.sessions[q].import_(np.fromfile(f, dtype="<f8", count=count * rows).reshape(count, rows))
+
+    def save(self, folder, t: float, counter: int) -> dict:
+        """The frames recorded since the last save appended to ``<file_stem>_<q>.f64`` (little-endian FP64 [frame][row]), a
+        slab at a time; returns the manifest's entry."""
+        for q, s in self.sessions.items():
+            path = Path(folder) / f"{self.file_stem}_{q}.f64"
+            with open(path, "r+b" if self.saved and path.exists() else "wb") as f:
+                f.seek(8 * self.rows(q) * self.saved)        # whatever lies beyond the last manifest's count is overwritten
+                for k in range(self.saved, self.frames, self._slab(q)):
+                    f.write(np.ascontiguousarray(s.export(k, min(self._slab(q), self.frames - k)), dtype="<f8").tobytes())
+                f.truncate()
+        self.saved = self.frames
+        return dict(frames=self.frames, times=list(self.times), quantities={q: self.fingerprint(q) for q in self.quantities})
 
     def finish(self, out=print) -> None:
         try:
@@ -510,14 +688,19 @@ def hi_pass_refusal(v: dict, world: int, backend_cls) -> str:
     if not v.get("save_step"):
         return "--hi-pass records the saved frames: it needs --save-step"
     if v.get("restart_folder"):
-        return "--hi-pass does not carry its history through a checkpoint: it cannot be used with --restart-folder"
+        why = restart_refusal(v, HiPassRun.key, HiPassRun.words)
+        if why:
+            return why
     if world > 1:
         return "--hi-pass runs on one rank only (WORLD_SIZE > 1)"
     stride, t0, t1 = frame_window(v)
     words, _ = multiband(v), point_ids(v)
     whole = stride == 1 and t0 == 0.0 and t1 is None
-    frames = select_frames(saved_times(v), float(v["dt"]), stride, t0, t1)[1]
+    times, past = frame_times(v, HiPassRun.key, HiPassRun.words)
+    frames = select_frames(times, float(v["dt"]), stride, t0, t1)[1]
     saves = f"saves {frames} frames" if whole else f"saves {frames} frames in the window and stride asked for"
+    if v.get("restart_folder"):
+        saves += f" ({past} saved before the restart and {len(times) - past} to come)"
     for lo, hi in bands(v):
         if frames < padlen_of(lo) + 1:
             return (f"--hi-pass: the run {saves}, the filter of band {lo:g} - {hi:g} Hz needs at least "
@@ -563,7 +746,8 @@ class HiPassRun(SessionRun):
     drops the last ones, postprocessing_h5py_common.py:285,307).  Times in the files are ``T0 + k * time_between_files``, T0
     being the reference's ``start_t``; ``time_between_files`` is dt * save_step * stride, the spacing of the selected frames
     (the reference takes dt * stride and notes the doubt, :621-634)."""
-    prefix = "hi_pass"
+    prefix = file_stem = key = "hi_pass"
+    option, words = "--hi-pass", "--hi-pass cannot be used with --restart-folder"
 
     def __init__(self, backend, mesh: FsiMesh, ns: dict):
         from .output import refine_topology
@@ -577,25 +761,28 @@ class HiPassRun(SessionRun):
         self.amplitude = bool(ns.get("hi_pass_amplitude"))
         self.window = int(ns.get("hi_pass_window") or 250)
         self.dt = float(ns["dt"])
-        self.dt_files = self.dt * int(ns["save_step"]) * self.stride
-        self.times: List[float] = []
+        self.dt_sample = self.dt * int(ns["save_step"])
+        self.dt_files = self.dt_sample * self.stride
+        self.nodes = {q: output_nodes(mesh, self.save_deg, q) for q in self.quantities}
         if self.save_deg >= 2:
             geometry, topology = mesh.node_coords, refine_topology(mesh)
         else:
             geometry, topology = mesh.coords, mesh.tets
         for q in self.quantities:
-            n = len(output_nodes(mesh, self.save_deg, q)[0])
+            n = len(self.nodes[q][0])
             bad = [i for i in self.point_ids if i >= n]
             if bad:
                 raise SystemExit(f"--hi-pass-point-ids: {bad} out of range, {VIZ_TYPE[q]} is written on {n} nodes")
         self.writer = HiPassWriter(Path(ns["results_folder"]) / "Visualization_hi_pass", geometry, topology)
         self.trace_folder = Path(ns["results_folder"]) / "Visualization_separate_domain"      # [REF create_hi_pass_viz.py:565,639]
-        self.open_sessions(backend, ns, lambda q: output_nodes(mesh, self.save_deg, q),
+        self.open_sessions(backend, ns, lambda q: self.nodes[q],
                            lambda q, capacity: HostBandSession(1 if q == "p" else 3, capacity))
 
-    def sample(self, t: float, state) -> None:
-        super().sample(t, state)
-        self.times.append(float(t))
+    def rows(self, q: str) -> int:
+        return len(self.nodes[q][0]) * (1 if q == "p" else 3)
+
+    def fingerprint(self, q: str) -> dict:
+        return dict(save_deg=self.save_deg, dt_sample=self.dt_sample, rows=self.rows(q), nodes=sha256_of(*self.nodes[q]))
 
     def _host_frame(self, q: str, state: np.ndarray) -> np.ndarray:
         d, v, p = self.mesh.split(state)

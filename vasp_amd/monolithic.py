@@ -495,7 +495,7 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
     viz = None
     if ns.get("save_step") and rank0:
         viz = VisualizationWriter(ns["visualization_folder"], mesh, ns["save_deg"], run_index=restart_run)
-    sessions = []                                 # single rank, no restart, save_step set: run() checked it
+    sessions = []                                 # single rank, save_step set: run() checked it; under --restart-folder they continue from Checkpoint/sessions
     for key, module, _, run_cls, needs in SESSIONS:
         if not ns.get(key):
             continue
@@ -520,7 +520,8 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
         # turtleFSI's stop controls: wall-clock budget, and the sentinel files a user drops into the results folder
         # (``killturtle``: checkpoint and stop; ``pauseturtle``: wait until it is removed)
         stop = stop_controls(results, killtime, t_loop, getattr(backend, "agree_flags", None), rank0, out)
-        if ns.get("checkpoint_step") and (ns["counter"] % int(ns["checkpoint_step"]) == 0 or stop):
+        checkpointed = bool(ns.get("checkpoint_step") and (ns["counter"] % int(ns["checkpoint_step"]) == 0 or stop))
+        if checkpointed:
             x = ns["dvp_"]["n"].vector()
             if rank0:
                 checkpoint(ns["checkpoint_folder"], mesh, x, ns["default_variables"], t, ns["counter"])
@@ -530,6 +531,8 @@ def _time_loop(ns, backend, bc_values, pressure, hook, out, rank0, quiet):
                 session.sample(t, ns["dvp_"]["n"].vector)
         elif ns.get("save_step") and ns["counter"] % int(ns["save_step"]) == 0:
             ns["dvp_"]["n"].vector()              # partitioned: every rank takes part in the gather
+        if checkpointed and sessions:             # behind this step's sample: the state holds every frame up to the checkpoint's time
+            _session_part("hi_pass", "save_sessions")(sessions, results, t, ns["counter"])
         ns["counter"] += 1
         ev = solver_events(backend)          # the silent refresh-and-retry is visible in the product log
         if any(ev.get(k, 0) > events_seen.get(k, 0) for k in ev):

@@ -30,7 +30,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from .hi_pass import HostHistory, SessionRun, expected_frames, output_nodes
+from .hi_pass import HostHistory, SessionRun, frame_times, output_nodes, restart_refusal, sha256_of
 from .mesh import FsiMesh
 
 HP_ORDER = 6                                    # filter_time_data(order=6, btype="highpass") [REF spectrograms.py:558]
@@ -433,12 +433,16 @@ def spectrogram_refusal(v: dict, world: int, backend_cls) -> str:
     if not v.get("save_step"):
         return "--spectrogram records the saved frames: it needs --save-step"
     if v.get("restart_folder"):
-        return "--spectrogram does not carry its history through a checkpoint: it cannot be used with --restart-folder"
+        why = restart_refusal(v, SpectrogramRun.key, SpectrogramRun.words)
+        if why:
+            return why
     if world > 1:
         return "--spectrogram runs on one rank only (WORLD_SIZE > 1)"
-    frames = expected_frames(v)
+    times, past = frame_times(v, SpectrogramRun.key, SpectrogramRun.words)
+    frames = len(times)
     if frames < HP_PADLEN + 1:
-        return f"--spectrogram: the run saves {frames} frames, the high-pass filter needs at least padlen + 1 = {HP_PADLEN + 1}"
+        split = f" ({past} saved before the restart and {frames - past} to come)" if v.get("restart_folder") else ""
+        return f"--spectrogram: the run saves {frames} frames{split}, the high-pass filter needs at least padlen + 1 = {HP_PADLEN + 1}"
     T = frames * float(v["dt"]) * int(v["save_step"])
     plan = window_plan(frames, T, o["num_windows_per_sec"], o["overlap_frac"])
     if plan["nseg"] < 2:
@@ -450,7 +454,8 @@ def spectrogram_refusal(v: dict, world: int, backend_cls) -> str:
 class SpectrogramRun(SessionRun):
     """The driver's side of ``--spectrogram``: per quantity one session on the sampled nodes, one recorded frame per saved
     frame, and at the end the four files.  A backend without ``spec_begin`` records and transforms on the host."""
-    prefix = "spec"
+    prefix, file_stem, key = "spec", "spectrogram", "spectrogram"
+    option, words = "--spectrogram", "--spectrogram cannot be used with --restart-folder"
 
     def __init__(self, backend, mesh: FsiMesh, ns: dict):
         self.backend, self.mesh = backend, mesh
@@ -466,6 +471,11 @@ class SpectrogramRun(SessionRun):
 
     def rows(self, q: str) -> int:
         return len(self.sel[q]["ids"]) * (3 if q != "p" and self.opts["component"] == "all" else 1)
+
+    def fingerprint(self, q: str) -> dict:
+        sel = self.sel[q]
+        return dict(save_deg=self.save_deg, dt_sample=self.dt_files, component="x" if q == "p" else self.opts["component"],
+                    rows=self.rows(q), nodes=sha256_of(sel["nodes"], sel["nodes_b"]))
 
     def min_color(self, q: str):
         return MIN_COLOR[q] if self.opts["min_color"] is None else self.opts["min_color"]

@@ -18,14 +18,14 @@ coordinates of the vertices they use, compacted in ascending vertex order.
 """
 from __future__ import annotations
 
-import os
 from pathlib import Path
-from typing import Dict, Tuple
+from typing import Dict, List, Tuple
 
 import numpy as np
 
-from .h5lite import Group, H5Series, write_h5
-from .hemodynamics import XDMF_FOOTER, _dg1_group, _xdmf_grid, _xdmf_head
+from .h5lite import Group, write_h5
+from .hemodynamics import XDMF_FOOTER, Dg1Series, _dg1_group, _xdmf_grid, _xdmf_head
+from .hi_pass import check_fingerprint, load_array, restart_entry, restart_refusal, save_array, sessions_folder, sha256_of
 from .mesh import FsiMesh
 
 FRAME_NAMES = ("TrueStress", "GreenLagrangeStrain", "MaxPrincipalStress", "MaxPrincipalStrain")
@@ -47,38 +47,27 @@ def solid_submesh(mesh: FsiMesh, cells) -> Tuple[np.ndarray, np.ndarray]:
 
 class StressStrainWriter:
     """``<results>/StressStrain/``: ``write_frame`` appends one frame to the four series (h5 and XDMF grow in place),
-    ``write_averages`` writes the two average files once."""
+    ``write_averages`` writes the two average files once.  ``adopt``: the frames of the four series a restarted run
+    continues (``hemodynamics.Dg1Series``)."""
 
-    def __init__(self, folder, geometry: np.ndarray, topology: np.ndarray):
+    def __init__(self, folder, geometry: np.ndarray, topology: np.ndarray, adopt: int = 0):
         self.folder = Path(folder)
         self.folder.mkdir(parents=True, exist_ok=True)
         self.geometry, self.topology = geometry, topology
-        self.frames = 0
-        self._series: Dict[str, H5Series] = {}
+        self.frames = int(adopt)
+        self._series = {name: Dg1Series(self.folder, name, COMPONENTS[name], "tetrahedron", geometry, topology, adopt)
+                        for name in FRAME_NAMES}
 
     def _shape(self, name: str) -> tuple:
         return (len(self.topology), 4, 3, 3) if COMPONENTS[name] == 9 else (len(self.topology), 4)
 
     def write_frame(self, frame: Dict[str, np.ndarray], t: float) -> None:
         """frame: the four fields keyed as ``HipBackend.stress_strain`` ((n, 4, 3, 3) tensors, (n, 4) principal values)."""
-        n, nv = len(self.topology), len(self.geometry)
         for name in FRAME_NAMES:
             if np.shape(frame[name]) != self._shape(name):
                 raise ValueError(f"{name} of shape {np.shape(frame[name])}, expected {self._shape(name)}")
-        k = self.frames
         for name in FRAME_NAMES:
-            if name not in self._series:
-                self._series[name] = H5Series(self.folder / f"{name}.h5", Group(), name)
-            self._series[name].append_group(f"{name}_{k}", _dg1_group(np.asarray(frame[name]), self.geometry, self.topology,
-                                                                      dofmap=k == 0, celltype="tetrahedron"))
-            path = self.folder / f"{name}.xdmf"
-            grid = _xdmf_grid(name, k, t, n, nv, COMPONENTS[name], celltype="tetrahedron")
-            if k == 0:
-                path.write_text(_xdmf_head(name) + grid + XDMF_FOOTER)
-            else:                               # the new grid overwrites the closing tags, which follow it again
-                with open(path, "r+b") as f:
-                    f.seek(-len(XDMF_FOOTER.encode()), os.SEEK_END)
-                    f.write((grid + XDMF_FOOTER).encode())
+            self._series[name].append(np.asarray(frame[name]), t)
         self.frames += 1
 
     def write_averages(self, averages: Dict[str, np.ndarray]) -> None:
@@ -98,7 +87,6 @@ class StressStrainWriter:
     def close(self) -> None:
         for s in self._series.values():
             s.close()
-        self._series = {}
 
 
 def stress_strain_refusal(v: dict, world: int, backend_cls) -> str:
@@ -106,7 +94,9 @@ def stress_strain_refusal(v: dict, world: int, backend_cls) -> str:
     if not v.get("save_step"):
         return "--stress-strain samples the saved frames: it needs --save-step"
     if v.get("restart_folder"):
-        return "--stress-strain does not carry its sums through a checkpoint: it cannot be used with --restart-folder"
+        why = restart_refusal(v, StressStrainRun.key, StressStrainRun.words)
+        if why:
+            return why
     if world > 1:
         return "--stress-strain runs on one rank only (WORLD_SIZE > 1)"
     if backend_cls is not None and not hasattr(backend_cls, "stress_strain_begin"):
@@ -118,17 +108,40 @@ class StressStrainRun:
     """The driver's side of ``--stress-strain``: the session on the solid cells (``dx_s_id``, every region), one frame per
     saved Visualization frame, the averages at the end."""
 
+    key, option = "stress_strain", "--stress-strain"
+    words = "--stress-strain cannot continue under --restart-folder"
+
     def __init__(self, backend, mesh: FsiMesh, ns: dict):
         cells = solid_cells(mesh, ns["dx_s_id"])
         if len(cells) == 0:
             raise SystemExit(f"--stress-strain: no cell carries a solid marker (dx_s_id = {ns['dx_s_id']})")
         geometry, topology = solid_submesh(mesh, cells)
         self.backend = backend
+        self.fingerprint = dict(dt_sample=float(ns["dt"]) * int(ns["save_step"]), rows=len(cells), cells=sha256_of(cells))
+        self.times: List[float] = []
+        entry = restart_entry(ns, self.key, self.words)
+        if entry is not None:
+            check_fingerprint(self.option, "the solid cells", entry["fingerprint"], self.fingerprint)
         backend.stress_strain_begin(cells)
-        self.writer = StressStrainWriter(Path(ns["results_folder"]) / "StressStrain", geometry, topology)
+        if entry is not None:                   # the sums and the count of the run that wrote the checkpoint
+            sums = load_array(sessions_folder(ns["restart_folder"]) / "stress_strain.npy", entry["sha256"], self.option)
+            backend.stress_strain_import(sums, int(entry["samples"]))
+            self.times = [float(x) for x in entry["times"]]
+        self.writer = StressStrainWriter(Path(ns["results_folder"]) / "StressStrain", geometry, topology,
+                                         adopt=int(entry["series_frames"]) if entry is not None else 0)
 
     def sample(self, t: float, state=None) -> None:
         self.writer.write_frame(self.backend.stress_strain_sample(frame=True), t)
+        self.times.append(float(t))
+
+    def save(self, folder, t: float, counter: int) -> dict:
+        """The sums to ``stress_strain.npy``; returns the manifest's entry - None for a backend that cannot hand its sums
+        out: without an entry a restart with the option is refused."""
+        if not hasattr(self.backend, "stress_strain_export"):
+            return None
+        sums, samples = self.backend.stress_strain_export()
+        return dict(samples=samples, times=list(self.times), fingerprint=self.fingerprint, series_frames=self.writer.frames,
+                    sha256=save_array(Path(folder) / "stress_strain.npy", sums))
 
     def finish(self, out=print) -> None:
         """The two average files (over the frames sampled so far) and one log line."""
