@@ -371,9 +371,10 @@ int fsi_stress_import(FsiCtx* ctx, const double* sums, int64_t samples);
 int fsi_stress_end(FsiCtx* ctx);
 
 /* ---- band-pass filtered fields and vibration amplitudes over a run (fsi_band.hip) -------------------------- */
-/* One session per quantity (0 = d, 1 = v, 2 = p); the three can be open together, and beside the hemodynamics and the
- * stress / strain session.  Rows are (node, component) pairs, row = ncomp * i + component for the i-th listed node, ncomp = 3
- * for d / v and 1 for p - a fetched frame is the (n, ncomp) array a Visualization file holds.  All data are FP64. */
+/* One session per quantity (0 = d, 1 = v, 2 = p; 3 = strain, 4 = stress: fsi_band_begin_cells); all can be open together, and
+ * beside the hemodynamics and the stress / strain session.  Rows are (node, component) pairs, row = ncomp * i + component for
+ * the i-th listed node, ncomp = 3 for d / v and 1 for p - a fetched frame is the (n, ncomp) array a Visualization file holds.
+ * All data are FP64. */
 #define FSI_BAND_RAW 0
 #define FSI_BAND_FILTERED 1
 #define FSI_BAND_AMPLITUDE 2
@@ -387,6 +388,26 @@ int fsi_stress_end(FsiCtx* ctx);
  * allocated - no paging, no truncation.  Replaces an open session of the quantity; a refused call (node out of range,
  * capacity, device memory) leaves it as it was, its bytes counted as taken.  Not for partitioned contexts. */
 int fsi_band_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* nodes, const int32_t* nodes_b, int64_t capacity);
+/* The two tensor quantities of a band-pass session, opened by fsi_band_begin_cells (fsi_band_begin refuses them). */
+#define FSI_BAND_STRAIN 3
+#define FSI_BAND_STRESS 4
+/* Replaces: create_transformed_matrix for quantity "strain" / "stress", the pass over StressStrain/GreenLagrangeStrain.h5 or
+ * TrueStress.h5 that builds the six dof x time component matrices 11, 12, 22, 23, 33, 31 = entries 0, 1, 4, 5, 8, 6 of the nine
+ * [REF src/vasp/postprocessing/postprocessing_h5py/postprocessing_h5py_common.py:198-260,349-354].  Opens the session of
+ * quantity FSI_BAND_STRAIN or FSI_BAND_STRESS on n > 0 listed SOLID cells (indices as fsi_stress_begin; range and kind are
+ * checked on the host before anything is uploaded).  A row is one component of one DG1 dof (local vertex a) of one listed
+ * cell: row = (4 i + a) * 6 + component for the i-th cell, so a "node" of the other band calls is a dof 4 i + a and ncomp = 6:
+ * 24 n rows, 4 n dofs.  The device-room refusal of fsi_band_begin applies to these counts.  Both quantities can be open
+ * together and beside every other session.  Replaces an open session of the quantity; a refused call leaves it as it was.
+ * Not for partitioned contexts.  The other fsi_band_* calls then serve the quantity:
+ *   fsi_band_sample  one frame of compute_stress_strain [REF src/vasp/postprocessing/postprocessing_fenics/
+ *                    compute_stress_strain.py:188-250] on the cells, the bits fsi_stress_sample puts into its frame;
+ *   fsi_band_fetch   FSI_BAND_MAGNITUDE / max_out / argmax_out: per dof the largest principal value of the amplitude tensor
+ *                    [[11,12,31],[12,22,23],[31,23,33]] by get_eig, exactly 0 where every entry is below 1e-8 in magnitude
+ *                    [REF .../create_hi_pass_viz.py:295-314] (out[4 n]); with window 0 of the filtered tensor (:229-230);
+ *   fsi_band_trace   refused: the reference writes no point traces for these quantities [REF .../create_hi_pass_viz.py:636-643];
+ *   filter, filter_next, select, amplitude, export, import, end: as for d, v, p, on the 24 n rows. */
+int fsi_band_begin_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* cells, int64_t capacity);
 /* Replaces: reading one frame of <quantity>.h5 [REF .../postprocessing_h5py_common.py:154-409, its frame loop]: the session's rows of
  * dvp_["n"] go to the next frame of the history, stream-ordered behind the time step; the host does not wait.
  * FSI_ERR_INVALID when the history is full. */

@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_spec_begin", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_spec_begin", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -161,6 +161,7 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_stress_import.argtypes = [vp, vp, i64]
     lib.fsi_stress_end.argtypes = [vp]
     lib.fsi_band_begin.argtypes = [vp, i32, i64, vp, vp, i64]
+    lib.fsi_band_begin_cells.argtypes = [vp, i32, i64, vp, i64]
     lib.fsi_band_sample.argtypes = [vp, i32]
     lib.fsi_band_filter.argtypes = [vp, i32, i32, vp, vp, vp, i32]
     lib.fsi_band_amplitude.argtypes = [vp, i32, i32]
@@ -568,7 +569,7 @@ class HipBackend:
     def stress_strain_end(self) -> None:
         self._check(self.lib.fsi_stress_end(self.ctx))
 
-    BAND_QUANTITY = {"d": 0, "v": 1, "p": 2}
+    BAND_QUANTITY = {"d": 0, "v": 1, "p": 2, "strain": 3, "stress": 4}
     BAND_WHAT = {"raw": 0, "filtered": 1, "amplitude": 2, "magnitude": 3}
 
     def hi_pass_begin(self, quantity: str, nodes, nodes_b=None, capacity: int = 1) -> None:
@@ -585,6 +586,19 @@ class HipBackend:
             self._band_shape, self._band_frames = {}, {}
         self._band_shape[quantity] = (len(a), 1 if quantity == "p" else 3)
         self._band_frames[quantity] = [0, 0]          # frames recorded, frames selected: the size of a trace
+
+    def hi_pass_begin_cells(self, quantity: str, cells, capacity: int = 1) -> None:
+        """Open the band-pass session of the tensor ``quantity`` ('strain': Green-Lagrange strain, 'stress': Cauchy stress;
+        fsi_band_begin_cells) on solid ``cells`` (user order, as ``stress_strain_begin``) for up to ``capacity`` frames;
+        replaces an open session of the quantity.  Its frames are (4 cells, 6): per DG1 dof 4 i + a the components 11, 12, 22,
+        23, 33, 31; the other ``hi_pass_*`` methods serve it, 'magnitude' being the largest principal value per dof."""
+        q = self.BAND_QUANTITY[quantity]
+        ci = np.ascontiguousarray(self.cell_u2i[np.asarray(cells, dtype=np.int64).reshape(-1)], dtype=np.int32)
+        self._check(self.lib.fsi_band_begin_cells(self.ctx, q, len(ci), _ptr(ci), int(capacity)))
+        if not hasattr(self, "_band_shape"):
+            self._band_shape, self._band_frames = {}, {}
+        self._band_shape[quantity] = (4 * len(ci), 6)
+        self._band_frames[quantity] = [0, 0]
 
     def hi_pass_sample(self, quantity: str) -> None:
         """Record the session's rows of dvp_["n"] as the next frame of its history (fsi_band_sample)."""

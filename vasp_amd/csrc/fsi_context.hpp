@@ -418,7 +418,9 @@ struct FsiCtx {
   };
 
   // band-pass sessions (fsi_band_begin .. fsi_band_end), one per quantity d, v, p: a history whose row is component c of
-  // listed node i at i * ncomp + c, and one frame each of running sums, amplitudes and amplitude magnitudes (fsi_band.hip)
+  // listed node i at i * ncomp + c, and one frame each of running sums, amplitudes and amplitude magnitudes (fsi_band.hip).
+  // Slots 3 and 4 (fsi_band_begin_cells): the Green-Lagrange strain and the Cauchy stress on listed solid cells - a "node"
+  // is a DG1 dof 4 ci + a, ncomp = 6, idx0 holds the cells and idx1 is unused (nsamp = the number of cells)
   struct Band : History {
     int ncomp = 0;
     int window = -1;                         // -1: no amplitude asked for; 0: the filtered series itself (low-pass); > 0: RMS window
@@ -434,7 +436,7 @@ struct FsiCtx {
       ncomp = 0; window = -1; acc_start = -1;
       sel_first = 0; sel_stride = 1; sel_count = -1;
     }
-  } band[3];
+  } band[5];
 
   // spectrogram sessions (fsi_spec_begin .. fsi_spec_end), one per quantity d, v, p, with a history of their own on a row
   // list of their own.  mode: 0 / 1 / 2 one component, 3 the three stacked (row = c * nnode + i), 4 the magnitude, taken at

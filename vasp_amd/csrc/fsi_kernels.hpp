@@ -138,6 +138,12 @@ hipError_t upload_stress_tables(const double* qw, const double* dN, const double
 void launch_stress_sample(hipStream_t st, int64_t ncell, const ElemArrays& ea, const ElemParams& ep, const double* U,
                           const int32_t* cells, double* frame, double* sums);           // frame [n][80], sums [n][8]
 void launch_stress_average(hipStream_t st, int64_t ncell, double samples, const double* sums, double* out);   // out [2][n][4]
+// the rows of a band-pass session on a tensor: dst[(4 ci + a) 6 + comp] = component 11, 12, 22, 23, 33, 31 of DG1 dof a of
+// GreenLagrangeStrain (strain) or TrueStress on cells[ci], the bits launch_stress_sample puts into its frame; and from six
+// amplitudes per dof mag[dof] = their largest principal value, 0 where every one is below 1e-8
+void launch_tensor_sample(hipStream_t st, int64_t ncell, const ElemArrays& ea, const ElemParams& ep, const double* U,
+                          const int32_t* cells, bool strain, double* dst);
+void launch_tensor_principal(hipStream_t st, int64_t nnode, const double* amp, double* mag);
 
 // fsi_hemo.hip — hemodynamic indices accumulated over the saved frames of a run (per DG1 dof of the boundary mesh)
 struct HemoAcc {

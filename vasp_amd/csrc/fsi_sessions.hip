@@ -18,14 +18,20 @@ HemoAcc hemo_acc(FsiCtx* ctx) {
 
 // ---- the recorded history of a band-pass or a spectrogram session (FsiCtx::History) ---------------------------------------
 
-// the open session of quantity q (0 d, 1 v, 2 p) among all[3], or null with ctx->err set
-template <class S>
-S* open_session(FsiCtx* ctx, S (&all)[3], int32_t q, const char* fn, const char* kind, const char* begin) {
-  if (q < 0 || q > 2) { ctx->err = std::string(fn) + ": quantity must be 0 (d), 1 (v) or 2 (p)"; return nullptr; }
+// the open session of quantity q (0 d, 1 v, 2 p; among five also 3 strain, 4 stress) among all[N], or null with ctx->err set
+template <int N> const char* quantity_range();
+template <> const char* quantity_range<3>() { return ": quantity must be 0 (d), 1 (v) or 2 (p)"; }
+template <> const char* quantity_range<5>() { return ": quantity must be 0 (d), 1 (v), 2 (p), 3 (strain) or 4 (stress)"; }
+template <class S, int N>
+S* open_session(FsiCtx* ctx, S (&all)[N], int32_t q, const char* fn, const char* kind, const char* begin) {
+  if (q < 0 || q >= N) { ctx->err = std::string(fn) + quantity_range<N>(); return nullptr; }
   if (!all[q].open) { ctx->err = std::string(fn) + ": no " + kind + " session for this quantity (" + begin + " first)"; return nullptr; }
   return &all[q];
 }
-FsiCtx::Band* band_session(FsiCtx* ctx, int32_t q, const char* fn) { return open_session(ctx, ctx->band, q, fn, "band-pass", "fsi_band_begin"); }
+bool tensor_quantity(int32_t q) { return q == FSI_BAND_STRAIN || q == FSI_BAND_STRESS; }
+FsiCtx::Band* band_session(FsiCtx* ctx, int32_t q, const char* fn) {
+  return open_session(ctx, ctx->band, q, fn, "band-pass", tensor_quantity(q) ? "fsi_band_begin_cells" : "fsi_band_begin");
+}
 FsiCtx::Spec* spec_session(FsiCtx* ctx, int32_t q, const char* fn) { return open_session(ctx, ctx->spec, q, fn, "spectrogram", "fsi_spec_begin"); }
 // frames of the band-pass session's view of its history (fsi_band_select): those the filtered series and the amplitude have
 int64_t band_frames(const FsiCtx::Band* s) { return s->sel_count < 0 ? s->frames : s->sel_count; }
@@ -198,9 +204,9 @@ int sums_import(FsiCtx* ctx, const char* fn, double* sums, size_t n, const doubl
   return FSI_OK;
 }
 
-template <class S>
-int end_session(FsiCtx* ctx, S (&all)[3], int32_t q, const char* fn) {
-  if (q < 0 || q > 2) { ctx->err = std::string(fn) + ": quantity must be 0 (d), 1 (v) or 2 (p)"; return FSI_ERR_INVALID; }
+template <class S, int N>
+int end_session(FsiCtx* ctx, S (&all)[N], int32_t q, const char* fn) {
+  if (q < 0 || q >= N) { ctx->err = std::string(fn) + quantity_range<N>(); return FSI_ERR_INVALID; }
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   all[q].release();
@@ -543,11 +549,58 @@ int fsi_band_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* node
   return history_open(ctx, s, n, nrow, capacity, i0, i1, false);
 }
 
+int fsi_band_begin_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* cells, int64_t capacity) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto refuse = [&](const char* why) { ctx->err = std::string("fsi_band_begin_cells: ") + why; return FSI_ERR_INVALID; };
+  if (!tensor_quantity(quantity)) return refuse("quantity must be 3 (strain) or 4 (stress)");
+  if (n <= 0 || !cells || capacity <= 0) return refuse("needs n > 0 cells and a capacity > 0 frames");
+  if (ctx->part) return refuse("partitioned contexts are not supported");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  std::vector<int32_t> kinds((size_t)ctx->C);      // as fsi_stress_begin: range and kind on the host, before anything is uploaded
+  HIPCHK(hipMemcpy(kinds.data(), ctx->cell_kind.p, (size_t)ctx->C * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < n; ++i) {
+    if (cells[i] < 0 || cells[i] >= ctx->C) return refuse("cell out of range");
+    if (kinds[cells[i]] != 1) return refuse("cell is not a solid cell");
+  }
+  // the bytes of fsi_band_begin with nrow = 24 n rows and nnode = 4 n DG1 dofs
+  const int64_t nnode = 4 * n, nrow = 6 * nnode;
+  const double need_d = 8.0 * (double)nrow * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN + 2.0) + 8.0 * (double)nnode + 8.0 * (double)nrow;
+  Room room;
+  FSICHK(device_room(ctx, &room));
+  if (need_d > (double)room.free_b - room.reserve) {
+    char msg[320];
+    snprintf(msg, sizeof msg, "fsi_band_begin_cells: the session needs %.0f bytes (%lld rows x %lld frames, raw and filtered), the device has %zu bytes "
+             "free of which %.0f stay with the context", need_d, (long long)nrow, (long long)capacity, room.free_b, room.reserve);
+    ctx->err = msg;
+    return FSI_ERR_INVALID;
+  }
+  auto& s = ctx->band[quantity];
+  s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
+  s.ncomp = 6;
+  HIPCHK(s.acc.alloc((size_t)nrow));
+  HIPCHK(s.amp.alloc((size_t)nrow));
+  HIPCHK(s.mag.alloc((size_t)nnode));
+  HIPCHK(s.part_val.alloc(BAND_ARGMAX_BLOCKS + 1));
+  HIPCHK(s.part_idx.alloc(BAND_ARGMAX_BLOCKS + 1));
+  const std::vector<int32_t> list(cells, cells + n), unused((size_t)n, -1);      // idx0: the cells
+  return history_open(ctx, s, nnode, nrow, capacity, list, unused, false);
+}
+
 int fsi_band_sample(FsiCtx* ctx, int32_t quantity) {
   if (!ctx) return FSI_ERR_INVALID;
   auto* s = band_session(ctx, quantity, "fsi_band_sample");
   if (!s) return FSI_ERR_INVALID;
-  FSICHK(history_sample(ctx, s, "fsi_band_sample", "fsi_band_begin"));
+  if (tensor_quantity(quantity)) {
+    if (s->frames >= s->capacity) { ctx->err = "fsi_band_sample: the history is full (capacity declared at fsi_band_begin_cells)"; return FSI_ERR_INVALID; }
+    HIPCHK(hipSetDevice(ctx->device));
+    launch_tensor_sample(ctx->stream, s->nsamp, elem_arrays(ctx), elem_params(ctx), ctx->U.p, s->idx0.p, quantity == FSI_BAND_STRAIN,
+                         s->hist.p + (size_t)s->frames * s->nrow);
+    HIPCHK(hipGetLastError());
+    s->frames += 1;
+    s->filtered = false;        // as history_sample
+  } else
+    FSICHK(history_sample(ctx, s, "fsi_band_sample", "fsi_band_begin"));
   s->window = -1;
   s->sel_first = 0; s->sel_stride = 1; s->sel_count = -1;      // a selection covers the frames it was made on
   return FSI_OK;
@@ -651,7 +704,8 @@ int fsi_band_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, d
   }
   if (what == FSI_BAND_MAGNITUDE || max_out || argmax_out) {
     if (what < FSI_BAND_AMPLITUDE) { ctx->err = "fsi_band_fetch: maximum / argmax are those of the amplitude magnitude"; return FSI_ERR_INVALID; }
-    launch_band_magnitude(ctx->stream, s->nnode, s->ncomp, src, s->mag.p);
+    if (tensor_quantity(quantity)) launch_tensor_principal(ctx->stream, s->nnode, src, s->mag.p);      // window 0: of the series itself (:229-230)
+    else launch_band_magnitude(ctx->stream, s->nnode, s->ncomp, src, s->mag.p);
     launch_band_argmax(ctx->stream, s->nnode, s->mag.p, s->part_val.p, s->part_idx.p);
     HIPCHK(hipGetLastError());
     if (max_out) HIPCHK(hipMemcpyAsync(max_out, s->part_val.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -667,6 +721,10 @@ int fsi_band_trace(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t npoints,
   if (!ctx) return FSI_ERR_INVALID;
   auto* s = band_session(ctx, quantity, "fsi_band_trace");
   if (!s) return FSI_ERR_INVALID;
+  if (tensor_quantity(quantity)) {      // the reference writes no point traces for these quantities (create_hi_pass_viz.py:636-643)
+    ctx->err = "fsi_band_trace: a strain / stress session has no point traces";
+    return FSI_ERR_INVALID;
+  }
   if (what != FSI_BAND_RAW && what != FSI_BAND_FILTERED) { ctx->err = "fsi_band_trace: what must be FSI_BAND_RAW or FSI_BAND_FILTERED"; return FSI_ERR_INVALID; }
   if (npoints <= 0 || !points || !out) { ctx->err = "fsi_band_trace: needs npoints > 0 points and an output"; return FSI_ERR_INVALID; }
   if (what == FSI_BAND_FILTERED && !s->filtered) { ctx->err = "fsi_band_trace: no filtered series (fsi_band_filter first)"; return FSI_ERR_INVALID; }

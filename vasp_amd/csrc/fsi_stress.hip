@@ -10,6 +10,18 @@
 //                      sums[ci][8] (MPStress_avg.vector().axpy(1.0, ...), :246-248).
 //   k_stress_average : one lane per averaged value: out[t][ci][a] = sums[ci][4 t + a] / n (the `/ counter` of :255-257).
 //
+// And the two kernels of a band-pass session on a tensor (fsi_band_begin_cells, quantity FSI_BAND_STRAIN / FSI_BAND_STRESS),
+// which replace the component matrices create_transformed_matrix builds from the StressStrain files
+// [REF src/vasp/postprocessing/postprocessing_h5py/postprocessing_h5py_common.py:250-259,349-354] and the eigenvalue loop of
+// create_hi_pass_viz [REF src/vasp/postprocessing/postprocessing_h5py/create_hi_pass_viz.py:295-314]:
+//
+//   k_tensor_sample    : one 64-lane workgroup per listed solid cell; the tensors of stress_strain_cell go to LDS, and lanes
+//                        0..23 write the 24 rows of the cell, row (4 ci + a) 6 + comp = entry 0, 1, 4, 5, 8, 6 (11, 12, 22,
+//                        23, 33, 31) of dof a of the asked tensor: 192 contiguous bytes per cell.  Here, because the Keast
+//                        tables of stress_strain_cell are this unit's copies.
+//   k_tensor_principal : one lane per DG1 dof: from its six amplitudes T = [[11,12,31],[12,22,23],[31,23,33]]; exactly 0 where
+//                        every |T_ij| < 1e-8, else max_eig_sym3(T) (get_eig).
+//
 // Every sum slot belongs to one lane of one workgroup and the samples are stream-ordered: no atomics, and the averages are
 // the sequential sums of the sampled values divided by n, bit for bit, run to run.  HBM traffic per cell and sample: the
 // gather of k_stress_strain (30 displacement values, 10 geometry doubles, the cell's dof row and region) in, 80 doubles
@@ -38,6 +50,29 @@ __global__ __launch_bounds__(256) void k_stress_average(int64_t n, double sample
   out[k] = sums[ci * 8 + 4 * t + a] / samples;
 }
 
+__global__ __launch_bounds__(64) void k_tensor_sample(ElemArrays ea, ElemParams ep, const double* __restrict__ U,
+                                                      const int32_t* __restrict__ cells, int strain, double* __restrict__ dst) {
+  __shared__ double oc[72];
+  const int64_t ci = blockIdx.x;
+  stress_strain_cell<false>(ea, ep, U, cells[ci], oc);
+  __syncthreads();
+  const int r = threadIdx.x;
+  if (r < 24) {
+    const int entry[6] = {0, 1, 4, 5, 8, 6};             // the tensors are not bitwise symmetric: 31 is entry 6, 12 entry 1
+    dst[ci * 24 + r] = oc[(strain ? 36 : 0) + (r / 6) * 9 + entry[r % 6]];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_tensor_principal(int64_t nnode, const double* __restrict__ amp, double* __restrict__ mag) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nnode) return;
+  const double* a = amp + 6 * i;                         // 11, 12, 22, 23, 33, 31
+  const double T[3][3] = {{a[0], a[1], a[5]}, {a[1], a[2], a[3]}, {a[5], a[3], a[4]}};
+  bool zero = true;
+  for (int k = 0; k < 6; ++k) zero = zero && fabs(a[k]) < 1e-8;
+  mag[i] = zero ? 0.0 : max_eig_sym3(T);
+}
+
 }  // namespace
 
 hipError_t upload_stress_tables(const double* qw, const double* dN, const double* L) {   // this unit's copies, at create
@@ -54,6 +89,14 @@ void launch_stress_sample(hipStream_t st, int64_t ncell, const ElemArrays& ea, c
 void launch_stress_average(hipStream_t st, int64_t ncell, double samples, const double* sums, double* out) {
   if (ncell > 0)
     hipLaunchKernelGGL(k_stress_average, dim3((unsigned)((8 * ncell + 255) / 256)), dim3(256), 0, st, ncell, samples, sums, out);
+}
+
+void launch_tensor_sample(hipStream_t st, int64_t ncell, const ElemArrays& ea, const ElemParams& ep, const double* U,
+                          const int32_t* cells, bool strain, double* dst) {
+  if (ncell > 0) hipLaunchKernelGGL(k_tensor_sample, dim3((unsigned)ncell), dim3(64), 0, st, ea, ep, U, cells, strain ? 1 : 0, dst);
+}
+void launch_tensor_principal(hipStream_t st, int64_t nnode, const double* amp, double* mag) {
+  if (nnode > 0) hipLaunchKernelGGL(k_tensor_principal, dim3((unsigned)((nnode + 255) / 256)), dim3(256), 0, st, nnode, amp, mag);
 }
 
 }  // namespace fsi

@@ -36,7 +36,9 @@ __device__ inline double max_eig_sym3(const double T[3][3]) {
 // compute_stress_strain [REF src/vasp/postprocessing/postprocessing_fenics/compute_stress_strain.py:188-263] on solid cell c,
 // run by one 64-lane workgroup (lanes = quadrature points, LDS for the projections).  oc[80]: TrueStress [4][9],
 // GreenLagrangeStrain [4][9], MaxPrincipalStress [4], MaxPrincipalStrain [4] (DG1 coefficient a = local vertex a).
-// Returns on lanes 0..7 the principal value the lane wrote to oc[72 + lane], 0 on the others.
+// Returns on lanes 0..7 the principal value the lane wrote to oc[72 + lane], 0 on the others.  PRINCIPAL false: the two
+// tensors only (oc[0 .. 72), the same instructions up to there), for a caller that keeps no principal values.
+template <bool PRINCIPAL = true>
 __device__ inline double stress_strain_cell(const ElemArrays& ea, const ElemParams& ep, const double* __restrict__ U, int64_t c,
                                            double* __restrict__ oc) {
   const int lane = threadIdx.x;
@@ -96,6 +98,7 @@ __device__ inline double stress_strain_cell(const ElemArrays& ea, const ElemPara
     const int a = o / 18, comp = o % 18;
     oc[(comp < 9 ? 0 : 36) + a * 9 + (comp % 9)] = sX[o];
   }
+  if (!PRINCIPAL) return 0.0;
   if (lane < NQ) {
     const double w = sJ[9] * p_qw[lane];
     for (int t = 0; t < 2; ++t) {

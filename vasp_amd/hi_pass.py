@@ -19,7 +19,7 @@ This module holds
   restoring of a recorded history (``SessionRun``).
 
 What a filter stage and a trace cost on a mesh of the benchmark's size has not been measured.
-Not done: the reference's ``strain`` / ``stress`` quantities.
+The reference's ``strain`` / ``stress`` quantities are ``--hi-pass-tensor`` (``hi_pass_tensor.py``), on the sessions of this module.
 """
 from __future__ import annotations
 
@@ -438,15 +438,15 @@ def load_array(path: Path, sha256: str, option: str) -> np.ndarray:
 
 class SessionRun:
     """What the driver's sides of ``--hi-pass`` and ``--spectrogram`` share: per quantity one session, on the device or, for a
-    backend without ``<prefix>_begin``, on the host; one recorded frame per saved frame; every session ended after ``write``."""
-    prefix = ""
+    backend without ``<prefix>_<begin>``, on the host; one recorded frame per saved frame; every session ended after ``write``."""
+    prefix, begin = "", "begin"                     # HipBackend.<prefix>_<begin> opens the device session
 
     key = option = words = ""                       # the manifest's key, the option and its sentence about --restart-folder
 
     def open_sessions(self, backend, ns: dict, begin_args, host_session) -> None:
         """``begin_args(q)``: the device session's arguments before the capacity; ``host_session(q, capacity)``: its host twin.
         Under --restart-folder the saved histories are checked against ``fingerprint(q)`` and imported."""
-        self.device = hasattr(backend, self.prefix + "_begin")
+        self.device = hasattr(backend, f"{self.prefix}_{self.begin}")
         self.frames = self.saved = 0                # recorded frames, and how many of them the history files hold
         self.times: List[float] = []
         self.sessions = {}
@@ -464,7 +464,7 @@ class SessionRun:
         for q in self.quantities:
             if self.device:
                 self.sessions[q] = DeviceSession(backend, self.prefix, q)
-                self.sessions[q].begin(*begin_args(q), capacity)
+                getattr(self.sessions[q], self.begin)(*begin_args(q), capacity)
             else:
                 self.sessions[q] = host_session(q, capacity)
         if self.saved:

@@ -96,6 +96,13 @@ def parse(argv: Optional[List[str]] = None) -> Dict[str, object]:
     ap.add_argument("--hi-pass-point-ids", dest="hi_pass_point_ids", nargs="+", type=_coerce, default=None, metavar="ID",
                     help="write the recorded series of these nodes (indices into the nodes of the Visualization files) to "
                          "<results>/Visualization_separate_domain/<field>_point_id_<ID>.csv")
+    ap.add_argument("--hi-pass-tensor", dest="hi_pass_tensor", nargs="+", default=None, metavar="Q",
+                    help="record the Green-Lagrange strain and / or the Cauchy stress (strain, stress) of the solid cells at every "
+                         "saved frame on the device and write the band-pass filtered tensors of --hi-pass-bands, with "
+                         "--hi-pass-amplitude their RMS amplitude and its largest principal value, to "
+                         "<results>/Visualization_hi_pass/ (what vasp-create-hi-pass-viz -q strain|stress writes afterwards)")
+    ap.add_argument("--hi-pass-tensor-window", dest="hi_pass_tensor_window", type=int, default=None,
+                    help="frames of the RMS window of the --hi-pass-tensor amplitudes (default: 50)")
     from .spectrogram import add_arguments as add_spectrogram_arguments
     add_spectrogram_arguments(ap, _coerce)
     ap.add_argument("-c", "--config", dest="config", default=None,
@@ -269,6 +276,7 @@ def parameters(argv: Optional[List[str]] = None):
 SESSIONS = (("hemodynamics", "hemodynamics", "hemodynamics_refusal", "HemodynamicsRun", "hemodynamics_begin"),
             ("stress_strain", "stress_strain", "stress_strain_refusal", "StressStrainRun", "stress_strain_begin"),
             ("hi_pass", "hi_pass", "hi_pass_refusal", "HiPassRun", None),
+            ("hi_pass_tensor", "hi_pass_tensor", "hi_pass_tensor_refusal", "HiPassTensorRun", "hi_pass_begin_cells"),
             ("spectrogram", "spectrogram", "spectrogram_refusal", "SpectrogramRun", None))
 
 
@@ -277,7 +285,7 @@ def _session_part(module: str, name: str):
 
 
 def _refuse_sessions(argv, backend_factory, world: int) -> None:
-    """--hemodynamics, --stress-strain, --hi-pass, --spectrogram: refuse before anything is built, on every rank (a refusal on rank 0 alone would leave
+    """--hemodynamics, --stress-strain, --hi-pass, --hi-pass-tensor, --spectrogram: refuse before anything is built, on every rank (a refusal on rank 0 alone would leave
     the workers waiting in run_worker)."""
     args = parse(argv)
     if not any(args.get(key) for key, *_ in SESSIONS):
