@@ -133,6 +133,8 @@ typedef struct FsiTuning {
   int32_t prec_streams;        /* 1: two chains of an application side by side on two HIP streams                                  */
   int32_t experiment;          /* measurement switches of the block factorisation, 0 in production: bit 0       */
                                /* pressure right-hand side from the fluid predictor only, bit 1 displacement block without velocity   */
+                               /* coupling, bit 2 every Chebyshev chain launches its last sweep (its product is read by nobody; by    */
+                               /* default the chain's consumer adds the last direction to x instead: same bits, one launch less)      */
   int32_t cheb4;               /* bit 0 / 1 / 2: 4th-kind Chebyshev sweeps in the solid cycle / displacement cycle / Schur solve   */
   int32_t coarse_power;        /* 1: coarse-level Chebyshev intervals from a power iteration (0: Gershgorin bound)                 */
   int32_t solid_mg, dd_mg;     /* two-level (P2 -> P1) cycles of the solid velocity block / the displacement block                 */
@@ -537,7 +539,8 @@ typedef struct FsiTimers {
   double precond_ms;   int64_t precond_calls;
   double ortho_ms;     int64_t ortho_calls;
   double krylov_ms;    int64_t krylov_solves;   int64_t krylov_iters;
-  int64_t inner_vv_iters;                    /* inner BiCGStab iterations of the block preconditioner: velocity block */
+  int64_t inner_vv_iters;                    /* fine-level Chebyshev product sweeps LAUNCHED by the block preconditioner (a chain whose  */
+                                             /* last sweep is left to its consumer counts one less): velocity block, solid + fluid part  */
   int64_t inner_schur_iters;                 /* ... pressure Schur complement                                          */
   int64_t inner_dd_iters;                    /* ... displacement block                                                 */
   int64_t precond_applies;

@@ -555,8 +555,16 @@ __global__ void k_pad_to_f32(int64_t nn, const double* __restrict__ a, const flo
     b[t] = c < 3 ? (float)a[3 * nd + c] * (scale4 ? scale4[t] : 1.f) : 0.f;
   }
 }
-__global__ void k_unpad_from_f32(int64_t nn, const float* __restrict__ a, double* __restrict__ b) {
-  GS(t, 3 * nn) b[t] = (double)a[4 * (t / 3) + t % 3];
+// The consumers of a Chebyshev chain's x (this kernel, k_merge_f32d, k_scatter3_f32, the two prolongations) take an optional
+// direction d: with it they read x + d, the sum the chain's last sweep would have stored (its x[i] += di, formed in the vectors'
+// own precision before any conversion), so that sweep - whose product nobody reads - is not launched (fsi_precond.hip)
+__global__ void k_unpad_from_f32(int64_t nn, const float* __restrict__ a, double* __restrict__ b, const float* __restrict__ d) {
+  GS(t, 3 * nn) {
+    const int64_t s = 4 * (t / 3) + t % 3;
+    float xi = a[s];
+    if (d) xi += d[s];
+    b[t] = (double)xi;
+  }
 }
 // pad_to_f32 + cheb_init_f32 in one launch: rhs = a (3 doubles per node) [* scale4], x = 0, r = rhs, d = rhs inv_theta dinv4
 __global__ void k_pad_init_f32(int64_t nn, const double* __restrict__ a, const float* __restrict__ scale4, const float* __restrict__ dinv4,
@@ -570,11 +578,13 @@ __global__ void k_pad_init_f32(int64_t nn, const double* __restrict__ a, const f
 }
 // merge with the displacement part taken straight from the sweeps' float4 result (unpad_from_f32 + merge in one launch)
 __global__ void k_merge_f32d(int64_t N2, int64_t V, const float* __restrict__ xd4, const double* __restrict__ zv,
-                             const double* __restrict__ zp, double* __restrict__ z) {
+                             const double* __restrict__ zp, double* __restrict__ z, const float* __restrict__ dd4) {
   GS(t, 3 * N2) {
     const int64_t nd = t / 3;
     const int i = (int)(t % 3);
-    z[6 * nd + i] = (double)xd4[4 * nd + i];
+    float xi = xd4[4 * nd + i];
+    if (dd4) xi += dd4[4 * nd + i];                  // x + d of the dropped last sweep (see k_unpad_from_f32)
+    z[6 * nd + i] = (double)xi;
     z[6 * nd + 3 + i] = zv[t];
   }
   GS(q, V) z[6 * N2 + q] = zp[q];
@@ -583,8 +593,9 @@ void launch_pad_init_f32(hipStream_t st, int64_t nn, const double* a, const floa
                          float* x, float* r, float* d) {
   hipLaunchKernelGGL(k_pad_init_f32, dim3(gridn(4 * nn)), dim3(256), 0, st, nn, a, scale4, dinv4, inv_theta, x, r, d);
 }
-void launch_merge_f32d(hipStream_t st, int64_t N2, int64_t V, const float* xd4, const double* zv, const double* zp, double* z) {
-  hipLaunchKernelGGL(k_merge_f32d, dim3(gridn(3 * N2)), dim3(256), 0, st, N2, V, xd4, zv, zp, z);
+void launch_merge_f32d(hipStream_t st, int64_t N2, int64_t V, const float* xd4, const double* zv, const double* zp, double* z,
+                       const float* dd4) {
+  hipLaunchKernelGGL(k_merge_f32d, dim3(gridn(3 * N2)), dim3(256), 0, st, N2, V, xd4, zv, zp, z, dd4);
 }
 // dinv4[4 nd + c] = mask / A[diagpos[3 nd + c]], pad 0  (mask may be null; one4: write 1 instead of the inverse diagonal)
 __global__ void k_dinv_f32(int64_t nn, const double* __restrict__ mask, const int64_t* __restrict__ diagpos,
@@ -1279,11 +1290,17 @@ __global__ void k_mg_restrict(int64_t nc, const int64_t* __restrict__ chptr, con
   }
 }
 __global__ void k_mg_prolong(int64_t N2, const int32_t* __restrict__ par, const float* __restrict__ pw,
-                             const float* __restrict__ d0, const float* __restrict__ xc4, float* __restrict__ e4) {
+                             const float* __restrict__ d0, const float* __restrict__ xc4, float* __restrict__ e4,
+                             const float* __restrict__ dc4) {
   GS(a, N2) {
     float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
     if (d0[a] != 0.f) {
-      const float4 u = reinterpret_cast<const float4*>(xc4)[par[2 * a]], v = reinterpret_cast<const float4*>(xc4)[par[2 * a + 1]];
+      float4 u = reinterpret_cast<const float4*>(xc4)[par[2 * a]], v = reinterpret_cast<const float4*>(xc4)[par[2 * a + 1]];
+      if (dc4) {                                      // x_c + d_c of the coarse level's dropped last sweep (see k_unpad_from_f32)
+        const float4 du = reinterpret_cast<const float4*>(dc4)[par[2 * a]], dv = reinterpret_cast<const float4*>(dc4)[par[2 * a + 1]];
+        u.x += du.x; u.y += du.y; u.z += du.z;
+        v.x += dv.x; v.y += dv.y; v.z += dv.z;
+      }
       const float wu = pw[2 * a], wv = pw[2 * a + 1];
       out = make_float4(wu * u.x + wv * v.x, wu * u.y + wv * v.y, wu * u.z + wv * v.z, 0.f);
     }
@@ -1315,8 +1332,8 @@ void launch_mg_restrict(hipStream_t st, int64_t nc, const int64_t* chptr, const 
   hipLaunchKernelGGL(k_mg_restrict, dim3(gridn(4 * nc)), dim3(256), 0, st, nc, chptr, child, chw, d0, r4, dcinv4, rc4, inv_theta, cx, cr, cd);
 }
 void launch_mg_prolong(hipStream_t st, int64_t N2, const int32_t* par, const float* pw, const float* d0, const float* xc4,
-                       float* e4) {
-  hipLaunchKernelGGL(k_mg_prolong, dim3(gridn(N2)), dim3(256), 0, st, N2, par, pw, d0, xc4, e4);
+                       float* e4, const float* dc4) {
+  hipLaunchKernelGGL(k_mg_prolong, dim3(gridn(N2)), dim3(256), 0, st, N2, par, pw, d0, xc4, e4, dc4);
 }
 
 void launch_extract_chat(hipStream_t st, int64_t N2, const int64_t* nadj_ptr, const int32_t* nadj, const double* db,
@@ -1340,8 +1357,8 @@ void launch_to_f32(hipStream_t st, int64_t n, const double* a, float* b) { hipLa
 void launch_pad_to_f32(hipStream_t st, int64_t nn, const double* a, const float* scale4, float* b) {
   hipLaunchKernelGGL(k_pad_to_f32, dim3(gridn(4 * nn)), dim3(256), 0, st, nn, a, scale4, b);
 }
-void launch_unpad_from_f32(hipStream_t st, int64_t nn, const float* a, double* b) {
-  hipLaunchKernelGGL(k_unpad_from_f32, dim3(gridn(3 * nn)), dim3(256), 0, st, nn, a, b);
+void launch_unpad_from_f32(hipStream_t st, int64_t nn, const float* a, double* b, const float* d) {
+  hipLaunchKernelGGL(k_unpad_from_f32, dim3(gridn(3 * nn)), dim3(256), 0, st, nn, a, b, d);
 }
 void launch_dinv_f32(hipStream_t st, int64_t nn, const double* mask, const int64_t* diagpos, const double* A, float* dinv4) {
   hipLaunchKernelGGL(k_dinv_f32, dim3(gridn(4 * nn)), dim3(256), 0, st, nn, mask, diagpos, A, dinv4);
@@ -1427,8 +1444,13 @@ __global__ void k_cheb_step_f32(int64_t n, const float* __restrict__ t, const fl
 __global__ void k_gather3_f32(int64_t nS, const int32_t* __restrict__ snode, const double* __restrict__ full, float* __restrict__ comp4) {
   GS(t, 4 * nS) comp4[t] = (t & 3) < 3 ? (float)full[3 * (int64_t)snode[t >> 2] + (t & 3)] : 0.f;
 }
-__global__ void k_scatter3_f32(int64_t nS, const int32_t* __restrict__ snode, const float* __restrict__ comp4, double* __restrict__ full) {
-  GS(t, 3 * nS) full[3 * (int64_t)snode[t / 3] + t % 3] = (double)comp4[4 * (t / 3) + t % 3];
+__global__ void k_scatter3_f32(int64_t nS, const int32_t* __restrict__ snode, const float* __restrict__ comp4, double* __restrict__ full,
+                               const float* __restrict__ d4) {
+  GS(t, 3 * nS) {
+    float xi = comp4[4 * (t / 3) + t % 3];
+    if (d4) xi += d4[4 * (t / 3) + t % 3];            // x + d of the dropped last sweep (see k_unpad_from_f32)
+    full[3 * (int64_t)snode[t / 3] + t % 3] = (double)xi;
+  }
 }
 // ---- 3x3 node-block Jacobi scaling for the solid sweeps: D_b^-1 per solid node (elasticity couples the components
 // of a node as strongly as neighbouring nodes; scaling by the block roughly sixths the condition number) ---------------
@@ -1649,7 +1671,7 @@ __global__ void k_sbmg_restrict(int64_t nc, const int64_t* __restrict__ chptr, c
 }
 __global__ void k_sbmg_prolong(int64_t nS, const int32_t* __restrict__ par, const float* __restrict__ pw,
                                const uint8_t* __restrict__ flag, const float* __restrict__ xc4, float* __restrict__ e4,
-                               const int32_t* __restrict__ bpos, const double* __restrict__ xd) {
+                               const int32_t* __restrict__ bpos, const double* __restrict__ xd, const float* __restrict__ dc4) {
   GS(a, nS) {
     float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
     if (!flag[a]) {
@@ -1661,6 +1683,11 @@ __global__ void k_sbmg_prolong(int64_t nS, const int32_t* __restrict__ par, cons
       } else {
         u = reinterpret_cast<const float4*>(xc4)[par[2 * a]];
         v = reinterpret_cast<const float4*>(xc4)[par[2 * a + 1]];
+        if (dc4) {                                  // x_c + d_c of the coarse level's dropped last sweep (see k_unpad_from_f32)
+          const float4 du = reinterpret_cast<const float4*>(dc4)[par[2 * a]], dv = reinterpret_cast<const float4*>(dc4)[par[2 * a + 1]];
+          u.x += du.x; u.y += du.y; u.z += du.z;
+          v.x += dv.x; v.y += dv.y; v.z += dv.z;
+        }
       }
       const float wu = pw[2 * a], wv = pw[2 * a + 1];
       out = make_float4(wu * u.x + wv * v.x, wu * u.y + wv * v.y, wu * u.z + wv * v.z, 0.f);
@@ -1691,8 +1718,8 @@ void launch_sbmg_restrict(hipStream_t st, int64_t nc, const int64_t* chptr, cons
   hipLaunchKernelGGL(k_sbmg_restrict, dim3(gridn(8 * nc)), dim3(256), 0, st, nc, chptr, child, chw, snode, rowscale, flag, cflag, r4, rc4, bpos, bd);
 }
 void launch_sbmg_prolong(hipStream_t st, int64_t nS, const int32_t* par, const float* pw, const uint8_t* flag, const float* xc4,
-                         float* e4, const int32_t* bpos, const double* xd) {
-  hipLaunchKernelGGL(k_sbmg_prolong, dim3(gridn(nS)), dim3(256), 0, st, nS, par, pw, flag, xc4, e4, bpos, xd);
+                         float* e4, const int32_t* bpos, const double* xd, const float* dc4) {
+  hipLaunchKernelGGL(k_sbmg_prolong, dim3(gridn(nS)), dim3(256), 0, st, nS, par, pw, flag, xc4, e4, bpos, xd, dc4);
 }
 
 // The same sweep with only the matrix VALUES in FP32 and every vector in FP64.  A rounded matrix is still one fixed linear
@@ -2038,8 +2065,8 @@ void launch_cheb_step_f32(hipStream_t st, int64_t n, const float* t, const float
 void launch_gather3_f32(hipStream_t st, int64_t nS, const int32_t* snode, const double* full, float* comp) {
   hipLaunchKernelGGL(k_gather3_f32, dim3(gridn(4 * nS)), dim3(256), 0, st, nS, snode, full, comp);
 }
-void launch_scatter3_f32(hipStream_t st, int64_t nS, const int32_t* snode, const float* comp, double* full) {
-  hipLaunchKernelGGL(k_scatter3_f32, dim3(gridn(3 * nS)), dim3(256), 0, st, nS, snode, comp, full);
+void launch_scatter3_f32(hipStream_t st, int64_t nS, const int32_t* snode, const float* comp, double* full, const float* d4) {
+  hipLaunchKernelGGL(k_scatter3_f32, dim3(gridn(3 * nS)), dim3(256), 0, st, nS, snode, comp, full, d4);
 }
 void launch_solid_cycle_init(hipStream_t st, int64_t nS, const int32_t* snode, const double* full, const float* binv12, float scale,
                              float* x, float* r, float* d, float* d2) {

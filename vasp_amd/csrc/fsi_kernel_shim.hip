@@ -1943,4 +1943,57 @@ int shim_ctx_spmv(FsiCtx* ctx, int working, const double* x, double* y, int64_t*
   return rc;
 }
 
+// ---- the x + d forms of a Chebyshev chain's consumers (the chain's last sweep is not launched, fsi_precond.hip) ---------------
+// As the entry points of the same names without _xd, with the direction d laid out as x; every output carries SHIM_TAIL
+// further elements that the launch must leave alone.
+int shim_unpad_from_f32_xd(int64_t nn, const float* a, const float* d, double* b) {
+  Call c;
+  const float* da = c.in(a, (size_t)(4 * nn));
+  const float* dd = c.in(d, (size_t)(4 * nn));
+  double* db = c.io(b, (size_t)(3 * nn) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_unpad_from_f32", launch_unpad_from_f32(c.st, nn, da, db, dd));
+}
+int shim_merge_f32d_xd(int64_t N2, int64_t V, const float* xd4, const float* dd4, const double* zv, const double* zp, double* z) {
+  Call c;
+  const float* dxd = c.in(xd4, (size_t)(4 * N2));
+  const float* ddd = c.in(dd4, (size_t)(4 * N2));
+  const double* dzv = c.in(zv, (size_t)(3 * N2));
+  const double* dzp = c.in(zp, (size_t)V);
+  double* dz = c.io(z, (size_t)(6 * N2 + V) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_merge_f32d", launch_merge_f32d(c.st, N2, V, dxd, dzv, dzp, dz, ddd));
+}
+// full [nfull] in place
+int shim_scatter3_f32_xd(int64_t nS, int64_t nfull, const int32_t* snode, const float* comp, const float* d4, double* full) {
+  Call c;
+  const int32_t* dsn = c.in(snode, (size_t)nS);
+  const float* dco = c.in(comp, 4 * (size_t)nS);
+  const float* dd = c.in(d4, 4 * (size_t)nS);
+  double* dfu = c.io(full, (size_t)nfull + SHIM_TAIL);
+  SHIM_RUN(c, "launch_scatter3_f32", launch_scatter3_f32(c.st, nS, dsn, dco, dfu, dd));
+}
+// par / pw [2 N2], d0 [N2], xc4 / dc4 [4 nc], e4 [4 N2]
+int shim_mg_prolong_xd(int64_t N2, int64_t nc, const int32_t* par, const float* pw, const float* d0, const float* xc4,
+                       const float* dc4, float* e4) {
+  Call c;
+  const int32_t* dpar = c.in(par, 2 * (size_t)N2);
+  const float* dpw = c.in(pw, 2 * (size_t)N2);
+  const float* dd0 = c.in(d0, (size_t)N2);
+  const float* dxc = c.in(xc4, 4 * (size_t)nc);
+  const float* ddc = c.in(dc4, 4 * (size_t)nc);
+  float* de = c.io(e4, 4 * (size_t)N2 + SHIM_TAIL);
+  SHIM_RUN(c, "launch_mg_prolong", launch_mg_prolong(c.st, N2, dpar, dpw, dd0, dxc, de, ddc));
+}
+// par / pw [2 nS], flag [nS], xc4 / dc4 [4 nc], e4 [4 nS]
+int shim_sbmg_prolong_xd(int64_t nS, int64_t nc, const int32_t* par, const float* pw, const uint8_t* flag, const float* xc4,
+                         const float* dc4, float* e4) {
+  Call c;
+  const int32_t* dpar = c.in(par, 2 * (size_t)nS);
+  const float* dpw = c.in(pw, 2 * (size_t)nS);
+  const uint8_t* dfl = c.in(flag, (size_t)nS);
+  const float* dxc = c.in(xc4, 4 * (size_t)nc);
+  const float* ddc = c.in(dc4, 4 * (size_t)nc);
+  float* de = c.io(e4, 4 * (size_t)nS + SHIM_TAIL);
+  SHIM_RUN(c, "launch_sbmg_prolong", launch_sbmg_prolong(c.st, nS, dpar, dpw, dfl, dxc, de, nullptr, nullptr, ddc));
+}
+
 }  // extern "C"

@@ -268,7 +268,8 @@ void launch_extract_db(hipStream_t st, int64_t N2, int64_t npairs, const int64_t
                        const double* vals, double* db, int32_t* flags, int check);
 void launch_pad_init_f32(hipStream_t st, int64_t nn, const double* a, const float* scale4, const float* dinv4, float inv_theta,
                          float* x, float* r, float* d);
-void launch_merge_f32d(hipStream_t st, int64_t N2, int64_t V, const float* xd4, const double* zv, const double* zp, double* z);
+void launch_merge_f32d(hipStream_t st, int64_t N2, int64_t V, const float* xd4, const double* zv, const double* zp, double* z,
+                       const float* dd4 = nullptr);      // dd4: the displacement part is xd4 + dd4 (the chain's dropped last sweep)
 void launch_mask_outside(hipStream_t st, int64_t N2, const uint8_t* rowmask, const int32_t* node_set, int32_t* flags);
 void launch_db_rows_sub(hipStream_t st, int64_t nl, const int32_t* list, const int64_t* nadj_ptr, const int32_t* nadj, const double* db,
                         const uint8_t* rowmask, const double* x, double* y);
@@ -311,7 +312,7 @@ void launch_spmv_db_f32(hipStream_t st, int64_t N2, const int64_t* nadj_ptr, con
                         const float* x, float* y);
 void launch_to_f32(hipStream_t st, int64_t n, const double* a, float* b);
 void launch_pad_to_f32(hipStream_t st, int64_t nn, const double* a, const float* scale4, float* b);
-void launch_unpad_from_f32(hipStream_t st, int64_t nn, const float* a, double* b);
+void launch_unpad_from_f32(hipStream_t st, int64_t nn, const float* a, double* b, const float* d = nullptr);   // d: b = a + d, summed in float
 void launch_dinv_f32(hipStream_t st, int64_t n, const double* mask, const int64_t* diagpos, const double* A, float* dinv);
 void launch_sb_binv(hipStream_t st, int64_t nS, const int32_t* snode, const int64_t* diagpos3, const double* Avv,
                     float* binv12, double* binv9);
@@ -330,7 +331,7 @@ void launch_mg_restrict(hipStream_t st, int64_t nc, const int64_t* chptr, const 
                         const float* d0, const float* r4, const float* dcinv4, float* rc4, float inv_theta = 0.f, float* cx = nullptr, float* cr = nullptr,
                         float* cd = nullptr);
 void launch_mg_prolong(hipStream_t st, int64_t N2, const int32_t* par, const float* pw, const float* d0, const float* xc4,
-                       float* e4);
+                       float* e4, const float* dc4 = nullptr);      // dc4: prolongs xc4 + dc4
 void launch_residual_rows(hipStream_t st, int64_t nrows, const int32_t* rows, const int64_t* ptr, const int32_t* col,
                           const int64_t* src, const double* vals, const double* x, const double* b, double* y);
 int launch_spmv_node6(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals,
@@ -355,7 +356,7 @@ void launch_sbmg_restrict(hipStream_t st, int64_t nc, const int64_t* chptr, cons
                           const int32_t* snode, const double* rowscale, const uint8_t* flag, const uint8_t* cflag,
                           const float* r4, float* rc4, const int32_t* bpos = nullptr, double* bd = nullptr);
 void launch_sbmg_prolong(hipStream_t st, int64_t nS, const int32_t* par, const float* pw, const uint8_t* flag, const float* xc4,
-                         float* e4, const int32_t* bpos = nullptr, const double* xd = nullptr);
+                         float* e4, const int32_t* bpos = nullptr, const double* xd = nullptr, const float* dc4 = nullptr);      // dc4 (xc4 form only): prolongs xc4 + dc4
 void launch_sweep_sb_b3(hipStream_t st, int64_t nS, const int64_t* sb_ptr, const int32_t* sb_col, const float* vals,
                         const float* binv12, float c1, float c2, const float* din, float* dout, float* x, float* r,
                         int level = 0);
@@ -370,7 +371,7 @@ void launch_cheb_step_f32(hipStream_t st, int64_t n, const float* t, const float
 void launch_gather3_f32(hipStream_t st, int64_t nS, const int32_t* snode, const double* full, float* comp);
 void launch_solid_cycle_init(hipStream_t st, int64_t nS, const int32_t* snode, const double* full, const float* binv12, float scale,
                              float* x, float* r, float* d, float* d2);
-void launch_scatter3_f32(hipStream_t st, int64_t nS, const int32_t* snode, const float* comp, double* full);
+void launch_scatter3_f32(hipStream_t st, int64_t nS, const int32_t* snode, const float* comp, double* full, const float* d4 = nullptr);   // d4: scatters comp + d4
 void launch_gather_vals(hipStream_t st, int64_t n, const int64_t* pos, const double* src, double* dst);
 void launch_gather3(hipStream_t st, int64_t nS, const int32_t* snode, const double* full, double* comp);
 void launch_scatter3(hipStream_t st, int64_t nS, const int32_t* snode, const double* comp, double* full);

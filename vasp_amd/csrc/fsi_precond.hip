@@ -1,4 +1,4 @@
-// The field-split block preconditioner of the monolithic Jacobian: one application (precondition_block: ~215 dependent
+// The field-split block preconditioner of the monolithic Jacobian: one application (precondition_block: ~210 dependent
 // launches on two HIP streams) and its refresh at every new Jacobian (refresh_preconditioner: field blocks, explicit Schur
 // complement, Galerkin coarse operators, eigenvalue estimates, self-test).  Kernels: fsi_block.hip.  DESIGN.md section 5.
 #include "fsi_host.hpp"
@@ -65,8 +65,15 @@ void schur_apply(FsiCtx* ctx, const double* in, double* out, double* w3) {
   launch_spmv(ctx->stream, ctx->V, ctx->s_rowptr.p, ctx->s_cols.p, ctx->s_vals.p, in, out, SPMV_FIELD_BLOCK);
 }
 
-// FP32 Chebyshev sweeps on a component-diagonal node-block matrix; dinv carries the Jacobi scaling and the mask
-void cheb_db_f32(FsiCtx* ctx, const float* db, const float* dinv, const double* rhs, double* x, double* W, int its,
+// The last sweep of a Chebyshev chain is not launched.  A sweep does  x += d_in;  r -= A d_in;  d_out = c1 d_in + c2 B^-1 r,
+// and what follows a chain reads x alone: the last product feeds only an r and a d that nobody reads.  The chain's consumer
+// takes x and the current direction and forms x + d itself, the same addition in the same precision (fsi_block.hip,
+// k_unpad_from_f32), so an application's output keeps its bits.  FsiTuning.experiment bit 2 launches every sweep as before.
+inline bool drop_last_sweep(const FsiCtx* ctx) { return (ctx->tune.experiment & 4) == 0; }
+
+// FP32 Chebyshev sweeps on a component-diagonal node-block matrix; dinv carries the Jacobi scaling and the mask.
+// Returns the number of product sweeps launched.
+int cheb_db_f32(FsiCtx* ctx, const float* db, const float* dinv, const double* rhs, double* x, double* W, int its,
                  double lmax, double kappa, hipStream_t st = nullptr) {
   const int64_t n = 4 * ctx->N2;                 // float4 per node
   if (!st) st = ctx->stream;
@@ -75,10 +82,11 @@ void cheb_db_f32(FsiCtx* ctx, const float* db, const float* dinv, const double* 
   const double lmin = lmax / kappa, th = 0.5 * (lmax + lmin), de = 0.5 * (lmax - lmin), sig = th / de;
   double rho = 1.0 / sig;
   (void)frhs;
+  const int launched = (its > 0 && drop_last_sweep(ctx)) ? its - 1 : its;      // without the chain's last sweep: the unpad adds its d
   launch_pad_init_f32(st, ctx->N2, rhs, nullptr, dinv, (float)(1.0 / th), fx, fr, fd);      // pad + initialise in one launch
   if (ctx->tiled && ctx->fused_sweeps) {
     float *da = fd, *db_ = ft;                   // d is ping-ponged; the product stays in registers
-    for (int k = 0; k < its; ++k) {
+    for (int k = 0; k < launched; ++k) {
       const bool timed = ctx->sample_budget > 0 && k < 4 && ctx->db_ev0[0] && ctx->db_samples_pending < 8;
       if (timed) (void)hipEventRecord(ctx->db_ev0[ctx->db_samples_pending], st);
       const double rn = 1.0 / (2.0 * sig - rho);
@@ -95,10 +103,10 @@ void cheb_db_f32(FsiCtx* ctx, const float* db, const float* dinv, const double* 
       std::swap(da, db_);
       rho = rn;
     }
-    launch_unpad_from_f32(st, ctx->N2, fx, x);
-    return;
+    launch_unpad_from_f32(st, ctx->N2, fx, x, launched < its ? da : nullptr);
+    return launched;
   }
-  for (int k = 0; k < its; ++k) {
+  for (int k = 0; k < launched; ++k) {
     const bool timed = ctx->sample_budget > 0 && k < 4 && ctx->db_ev0[0] && ctx->db_samples_pending < 8;
     if (timed) (void)hipEventRecord(ctx->db_ev0[ctx->db_samples_pending], st);
     if (ctx->tiled)
@@ -110,7 +118,8 @@ void cheb_db_f32(FsiCtx* ctx, const float* db, const float* dinv, const double* 
     launch_cheb_step_f32(st, n, ft, dinv, (float)(rn * rho), (float)(2.0 * rn / de), fx, fr, fd);
     rho = rn;
   }
-  launch_unpad_from_f32(st, ctx->N2, fx, x);
+  launch_unpad_from_f32(st, ctx->N2, fx, x, launched < its ? fd : nullptr);
+  return launched;
 }
 
 // z = M^-1 r with the approximate block factorisation (see fsi_block.hip):  (v,p) by SIMPLE with the d-eliminated
@@ -127,7 +136,7 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
   double *rd = W, *rv = W + n3, *rp = W + 2 * n3, *vs = W + 3 * n3, *tp = W + 4 * n3, *dp = W + 5 * n3, *dv = W + 6 * n3,
          *td = W + 7 * n3, *dd = W + 8 * n3, *IW = W + 9 * n3, *w3 = W + 19 * n3;     // IW: 10 vectors; its first 4 hold the (FP32, float4-padded) sweep work
   // Two chains side by side (prec_streams; default configuration only: FP32 solid cycle, FP32 fluid sweeps, FP16 / FP32 Schur
-  // sweeps with FP64 vectors, scalar displacement block).  The application is a chain of ~215 dependent launches, most of them
+  // sweeps with FP64 vectors, scalar displacement block).  The application is a chain of ~210 dependent launches, most of them
   // short of filling the chip (latency- and issue-bound sweeps on 0.1 - 0.6 GB of data), and its dependences are fewer than
   // its order: the fluid predictor does not need the solid one (block Jacobi instead of Gauss-Seidel between the two parts:
   // same Krylov counts, measured), and the displacement block needs the velocity on the SOLID rows only, where the pressure
@@ -142,6 +151,8 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
   // (the applications whose sweep launches are timed by event pairs issue both chains on the solver stream - the same arithmetic in
   // the same order per chain, and a pair brackets its kernel alone)
   hipStream_t sA = ctx->stream, sB = (conc && ctx->sample_budget <= 0) ? ctx->stream2 : ctx->stream;
+  const bool drop = drop_last_sweep(ctx);      // every chain below ends one sweep early and hands its consumer x and d
+  int sweeps_f = 0;                            // product sweeps launched by the fluid predictor
   launch_split(st, N2, V, r, rd, rv, rp);
   if (conc) { HIPCHK(hipEventRecord(ctx->ev_split, sA)); HIPCHK(hipStreamWaitEvent(sB, ctx->ev_split, 0)); }
   // velocity predictor: block Gauss-Seidel solid (elasticity-dominated, many cheap sweeps) -> fluid interior (mass-dominated)
@@ -149,7 +160,7 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
     double *xs = IW + 4 * n3, *xf = IW + 5 * n3, *rhs2 = IW + 6 * n3;
     double *cs_rhs = IW + 7 * n3, *cs_x = IW + 8 * n3;            // compact solid vectors (3 nS <= n3)
     if (conc)      // stream B, issued first: the fluid predictor straight from r_v (no coupling to the solid predictor), work area IW[6 n3, 10 n3)
-      cheb_db_f32(ctx, ctx->vv_db32.p, ctx->vvf_dinv32.p, rv, xf, IW + 6 * n3, ctx->cheb_its_f, ctx->lmax_f, ctx->cheb_kappa_f, sB);
+      sweeps_f = cheb_db_f32(ctx, ctx->vv_db32.p, ctx->vvf_dinv32.p, rv, xf, IW + 6 * n3, ctx->cheb_its_f, ctx->lmax_f, ctx->cheb_kappa_f, sB);
     if (ctx->solid_fp32) {
       const int64_t n = 4 * ctx->nS;               // float4 per solid node
       float* F = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(IW) + 15) & ~uintptr_t(15));   // float4 loads
@@ -165,6 +176,7 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
       else launch_cheb_init_f32(st, n, frhs, ctx->sb_dinv.p, (float)(1.0 / th), fx, fr, fd);
       if (fused && !cycle) HIPCHK(hipMemsetAsync(ft, 0, n * sizeof(float), st));     // second d buffer (ping-pong), pads stay zero
       float *dcur = fd, *dnext = ft;
+      const float* xs_d = nullptr;                 // the direction the scatter below adds to fx: that of the dropped last sweep
       if (fused && ctx->sbmg_ready) {
         // two-level cycle (see the displacement block): smoothing on [lmax/alpha, lmax], coarse solve on the solid vertices
         const double slmin = lmax / ctx->sbmg_alpha, sth = 0.5 * (lmax + slmin), sde = 0.5 * (lmax - slmin), ssig = sth / sde;
@@ -197,6 +209,7 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
         const int64_t nc = ctx->sbmg_nc, n4c = 4 * nc;
         float *cr = ctx->sbmg_work.p, *cd = cr + n4c, *cd2 = cr + 2 * n4c, *cx = cr + 3 * n4c, *crhs = cr + 4 * n4c;
         const bool exact = bcr_ready(ctx);
+        const float* cx_d = nullptr;                // the coarse chain's direction, when its last sweep is dropped
         launch_sbmg_restrict(st, nc, ctx->sbmg_chptr.p, ctx->sbmg_child.p, ctx->sbmg_chw.p, ctx->snode.p, ctx->rowscale.p,
                              ctx->sbmg_flag.p, ctx->sbmg_cflag.p, fr, crhs, exact ? bcr_pos(ctx) : nullptr, exact ? bcr_rhs(ctx) : nullptr);
         if (exact) {
@@ -211,28 +224,36 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
           launch_cheb_init_b3(st, nc, crhs, ctx->sbmg_cbinv12.p, (float)(1.0 / cth), cx, cr, cd);
           HIPCHK(hipMemsetAsync(cd2, 0, n4c * sizeof(float), st));
           float *ca = cd, *cb = cd2;
-          for (int k = 0; k < ctx->sbmg_cits; ++k) {
+          const int cits = (ctx->sbmg_cits > 0 && drop) ? ctx->sbmg_cits - 1 : ctx->sbmg_cits;
+          if (cits < ctx->sbmg_cits) cx_d = ca;
+          for (int k = 0; k < cits; ++k) {
             const double rn = 1.0 / (2.0 * csig - crho);
             launch_sweep_sb_b3(st, nc, ctx->sbmg_cptr.p, ctx->sbmg_ccol.p, ctx->sbmg_cvals.p, ctx->sbmg_cbinv12.p, (float)(rn * crho),
                                (float)(2.0 * rn / cde), ca, cb, cx, cr, 1);
             std::swap(ca, cb);
             crho = rn;
+            if (cx_d) cx_d = ca;
           }
         }
         launch_sbmg_prolong(st, ctx->nS, ctx->sbmg_par.p, ctx->sbmg_pw.p, ctx->sbmg_flag.p, cx, dcur,     // correction as the next direction
-                            exact ? bcr_pos(ctx) : nullptr, exact ? bcr_sol(ctx) : nullptr);
-        sweep(0.f, (float)sinit, -1);                          // x += P x_c, r -= A P x_c, restart the recurrence
+                            exact ? bcr_pos(ctx) : nullptr, exact ? bcr_sol(ctx) : nullptr, cx_d);
+        // the restart and the post-smoothing sweeps are one chain whose last sweep is left to the scatter (with sbmg_post = 0
+        // that is the restart itself: x += P x_c happens there, A P x_c is not formed)
+        const int tail = drop ? ctx->sbmg_post : ctx->sbmg_post + 1;
+        if (tail > 0) sweep(0.f, (float)sinit, -1);            // x += P x_c, r -= A P x_c, restart the recurrence
         srho = 1.0 / ssig;
-        for (int k = 0; k < ctx->sbmg_post; ++k) {
+        for (int k = 0; k + 1 < tail; ++k) {
           if (s4) { float c1, c2; s4c(k + 1, &c1, &c2); sweep(c1, c2, -1); continue; }
           const double rn = 1.0 / (2.0 * ssig - srho);
           sweep((float)(rn * srho), (float)(2.0 * rn / sde), -1);
           srho = rn;
         }
-        ctx->inner_its[0] += ctx->sbmg_pre + 1 + ctx->sbmg_post - ctx->cheb_its_s;    // counted below as cheb_its_s
+        if (drop) xs_d = dcur;
+        ctx->inner_its[0] += ctx->sbmg_pre + tail;
         ctx->ss_samples_pending = (ctx->sample_budget > 0 && ctx->ss_ev0[0]) ? std::min(8, ctx->sbmg_pre) : 0;
-      } else
-      for (int k = 0; k < ctx->cheb_its_s; ++k) {
+      } else {
+      const int its_s = (ctx->cheb_its_s > 0 && drop) ? ctx->cheb_its_s - 1 : ctx->cheb_its_s;
+      for (int k = 0; k < its_s; ++k) {
         const bool timed = ctx->sample_budget > 0 && k < 8 && ctx->ss_ev0[0];
         const double rn = 1.0 / (2.0 * sig - rho);
         if (timed) (void)hipEventRecord(ctx->ss_ev0[k], st);
@@ -253,13 +274,17 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
         }
         rho = rn;
       }
-      if (!(fused && ctx->sbmg_ready)) ctx->ss_samples_pending = (ctx->sample_budget > 0 && ctx->ss_ev0[0]) ? std::min(8, ctx->cheb_its_s) : 0;
+      if (its_s < ctx->cheb_its_s) xs_d = dcur;      // (unfused sweeps keep the direction in fd = dcur)
+      ctx->inner_its[0] += its_s;
+      ctx->ss_samples_pending = (ctx->sample_budget > 0 && ctx->ss_ev0[0]) ? std::min(8, its_s) : 0;
+      }
       // xs is written by this scatter alone (the sweeps' work areas end below it): its non-solid entries stay zero from one
       // application to the next, so the 3 N2-entry fill runs once per context instead of once per application
       if (ctx->xs_zeroed != xs) { launch_fill(st, xs, n3, 0.0); ctx->xs_zeroed = xs; }
-      launch_scatter3_f32(st, ctx->nS, ctx->snode.p, fx, xs);
+      launch_scatter3_f32(st, ctx->nS, ctx->snode.p, fx, xs, xs_d);
     } else {
     ctx->xs_zeroed = nullptr;
+    ctx->inner_its[0] += ctx->cheb_its_s;
     launch_gather3(st, ctx->nS, ctx->snode.p, rv, cs_rhs);
     {
       const CsrRef M = ss_ref(ctx);
@@ -292,12 +317,14 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
     }
     if (conc) {}
     else if (ctx->sweeps_fp32)
-      cheb_db_f32(ctx, ctx->vv_db32.p, ctx->vvf_dinv32.p, rhs2, xf, IW, ctx->cheb_its_f, ctx->lmax_f, ctx->cheb_kappa_f);
-    else
+      sweeps_f = cheb_db_f32(ctx, ctx->vv_db32.p, ctx->vvf_dinv32.p, rhs2, xf, IW, ctx->cheb_its_f, ctx->lmax_f, ctx->cheb_kappa_f);
+    else {
+      sweeps_f = ctx->cheb_its_f;
       cheb_solve_op(ctx, n3, [&](const double* in, double* out) { launch_spmv_db(st, N2, ctx->nadj_ptr.p, ctx->nadj.p, ctx->vv_db.p, in, out); },
                     ctx->Mvv.vals.p, ctx->diagpos3.p, ctx->mask_f.p, rhs2, xf, IW, ctx->cheb_its_f, ctx->lmax_f, ctx->cheb_kappa_f);
+    }
     launch_axpby(st, vs, 1.0, xs, 1.0, xf, n3);
-    ctx->inner_its[0] += ctx->cheb_its_s + ctx->cheb_its_f;
+    ctx->inner_its[0] += sweeps_f;               // (the solid part counted its own sweeps above)
   }
   // pressure: S dp = rp - Apv~ vs,  S x = App x - Apv~ D^-1 Avp x
   if (ctx->pv32_ok)
@@ -317,7 +344,8 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
       const bool p4 = (ctx->cheb4 & 4) != 0;
       launch_cheb_init(st, V, nullptr, tp, ctx->s_diagpos.p, ctx->s_vals.p, p4 ? 4.0 / (3.0 * lmax) : 1.0 / th, dp, pr, pa);
       const bool tiled16 = ctx->schur_tiled && ctx->sweeps_fp16 && ctx->s_rec.p;
-      for (int k = 0; k < ctx->cheb_its_p; ++k) {
+      const int its_p = drop ? ctx->cheb_its_p - 1 : ctx->cheb_its_p;
+      for (int k = 0; k < its_p; ++k) {
         const double rn = 1.0 / (2.0 * sig - rho);
         const int i4 = k + 1;
         const double c1 = p4 ? (2.0 * i4 - 1.0) / (2.0 * i4 + 3.0) : rn * rho;
@@ -334,15 +362,18 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
         std::swap(pa, pb);
         rho = rn;
       }
+      // the dropped last sweep's x += d: V doubles, a launch of its own in front of the velocity correction
+      if (its_p < ctx->cheb_its_p) launch_axpby(st, dp, 1.0, dp, 1.0, pa, V);
+      ctx->inner_its[1] += its_p;
     }
-    ctx->inner_its[1] += ctx->cheb_its_p;
   } else if (ctx->cheb_its_p > 0 && ctx->fused_sweeps) {
     // all-FP64 Schur sweeps, product fused with the Chebyshev update (one launch per sweep)
     const double lmax = ctx->lmax_p, lmin = lmax / ctx->cheb_kappa_p, th = 0.5 * (lmax + lmin), de = 0.5 * (lmax - lmin), sig = th / de;
     double rho = 1.0 / sig;
     double *pr = conc ? rp + V : IW, *pa = pr + V, *pb = pr + 2 * V;      // two chains: the Schur vectors live in the unused tail of rp, IW is stream A's
     launch_cheb_init(st, V, nullptr, tp, ctx->s_diagpos.p, ctx->s_vals.p, 1.0 / th, dp, pr, pa);
-    for (int k = 0; k < ctx->cheb_its_p; ++k) {
+    const int its_p = drop ? ctx->cheb_its_p - 1 : ctx->cheb_its_p;
+    for (int k = 0; k < its_p; ++k) {
       const double rn = 1.0 / (2.0 * sig - rho);
       const bool timed = ctx->sample_budget > 0 && k < 4 && ctx->sch_ev0[0];
       if (timed) (void)hipEventRecord(ctx->sch_ev0[k], st);
@@ -355,7 +386,8 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
       std::swap(pa, pb);
       rho = rn;
     }
-    ctx->inner_its[1] += ctx->cheb_its_p;
+    if (its_p < ctx->cheb_its_p) launch_axpby(st, dp, 1.0, dp, 1.0, pa, V);      // the dropped last sweep's x += d (see above)
+    ctx->inner_its[1] += its_p;
   } else if (ctx->cheb_its_p > 0) {
     int sample = 0;
     cheb_solve_op(ctx, V,
@@ -391,7 +423,7 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
   } else {
     launch_residual_csr(st, n3, ctx->rowptr3.p, ctx->cols3.p, ctx->Adv.p, dv, rd, td);
   }
-  const float* dd_f32 = nullptr;
+  const float *dd_f32 = nullptr, *dd_d = nullptr;      // dd_d: the displacement chain's direction, added by the merge (dropped last sweep)
   if (ctx->cheb_its_d > 0) {
     if (ctx->dd_is_scalar && ctx->sweeps_fp32) {
       // Jacobi-scaled system  (D^-1 A_dd) dd = D^-1 td  with the one-number-per-node-pair operator
@@ -402,7 +434,8 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
       const double lmax = ctx->lmax_d, lmin = lmax / ctx->cheb_kappa_d, th = 0.5 * (lmax + lmin), de = 0.5 * (lmax - lmin), sig = th / de;
       double rho = 1.0 / sig;
       const bool fused = ctx->tiled && ctx->fused_sweeps;
-      float *dcur = fd, *dnext = ft;               // fused sweeps ping-pong the direction; ft is otherwise the product
+      float *dcur = fd, *dnext = ft;               // fused sweeps ping-pong the direction; ft is otherwise the product (dcur stays fd)
+      const float* cx_d = nullptr;                 // the coarse chain's direction for the prolongation, when its last sweep is dropped
       auto fine_spmv = [&](int k_sample) {
         const bool timed = ctx->sample_budget > 0 && k_sample >= 0 && k_sample < 4 && ctx->sc_ev0[0];
         if (timed) (void)hipEventRecord(ctx->sc_ev0[k_sample], st);
@@ -455,7 +488,8 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
                              (float)(1.0 / cth), cx, cr, cd);
           (void)n4c;
           float *ca = cd, *cb = ct;
-          for (int k = 0; k < ctx->mg_cits; ++k) {
+          const int cits = (ctx->mg_cits > 0 && drop) ? ctx->mg_cits - 1 : ctx->mg_cits;
+          for (int k = 0; k < cits; ++k) {
             const double rn = 1.0 / (2.0 * csig - crho);
             if (ctx->fused_sweeps) {
               launch_sweep_sc_f32(st, nc, ctx->mg_cptr.p, ctx->mg_ccol.p, ctx->mg_cc.p, ctx->mg_cflag.p, (float)(rn * crho),
@@ -467,39 +501,48 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
             }
             crho = rn;
           }
+          if (cits < ctx->mg_cits) cx_d = ca;      // (unfused coarse sweeps keep the direction in cd = ca)
         }
-        launch_mg_prolong(st, N2, ctx->mg_par.p, ctx->mg_pw.p, ctx->mg_d0.p, cx, dcur);   // correction as the next direction
-        fine_sweep(0.f, (float)dinit, -1);                                             // x += P x_c, r -= C P x_c, restart
+        launch_mg_prolong(st, N2, ctx->mg_par.p, ctx->mg_pw.p, ctx->mg_d0.p, cx, dcur, cx_d);   // correction as the next direction
+        // restart + post-smoothing: one chain, its last sweep left to the merge (with mg_post = 0 the restart itself, see the solid cycle)
+        const int tail = drop ? ctx->mg_post : ctx->mg_post + 1;
+        if (tail > 0) fine_sweep(0.f, (float)dinit, -1);                               // x += P x_c, r -= C P x_c, restart
         srho = 1.0 / ssig;
-        for (int k = 0; k < ctx->mg_post; ++k) {
+        for (int k = 0; k + 1 < tail; ++k) {
           if (d4) { float c1, c2; d4c(k + 1, &c1, &c2); fine_sweep(c1, c2, -1); continue; }
           const double rn = 1.0 / (2.0 * ssig - srho);
           fine_sweep((float)(rn * srho), (float)(2.0 * rn / sde), -1);
           srho = rn;
         }
-        ctx->inner_its[2] += ctx->mg_pre + 1 + ctx->mg_post - ctx->cheb_its_d;     // counted below as cheb_its_d
+        if (drop) dd_d = dcur;
+        ctx->inner_its[2] += ctx->mg_pre + tail;
       } else {
         launch_pad_init_f32(st, N2, td, ctx->dd_dinv32.p, ctx->ones32.p, (float)(1.0 / th), fx, fr, fd);
-        for (int k = 0; k < ctx->cheb_its_d; ++k) {
+        const int its_d = drop ? ctx->cheb_its_d - 1 : ctx->cheb_its_d;
+        for (int k = 0; k < its_d; ++k) {
           const double rn = 1.0 / (2.0 * sig - rho);
           fine_sweep((float)(rn * rho), (float)(2.0 * rn / de), k);
           rho = rn;
         }
+        if (its_d < ctx->cheb_its_d) dd_d = dcur;
+        ctx->inner_its[2] += its_d;
       }
       dd_f32 = fx;                                  // the merge below takes the displacement part straight from the sweeps' result
-      if (ctx->debug_prec_apply > 0) launch_unpad_from_f32(st, N2, fx, dd);
+      if (ctx->debug_prec_apply > 0) launch_unpad_from_f32(st, N2, fx, dd, dd_d);
     } else if (ctx->dd_is_db && ctx->sweeps_fp32)
-      cheb_db_f32(ctx, ctx->dd_db32.p, ctx->dd_dinv32.p, td, dd, IW, ctx->cheb_its_d, ctx->lmax_d, ctx->cheb_kappa_d);
-    else if (ctx->dd_is_db)
+      ctx->inner_its[2] += cheb_db_f32(ctx, ctx->dd_db32.p, ctx->dd_dinv32.p, td, dd, IW, ctx->cheb_its_d, ctx->lmax_d, ctx->cheb_kappa_d);
+    else if (ctx->dd_is_db) {
+      ctx->inner_its[2] += ctx->cheb_its_d;
       cheb_solve_op(ctx, n3, [&](const double* in, double* out) { launch_spmv_db(st, N2, ctx->nadj_ptr.p, ctx->nadj.p, ctx->dd_db.p, in, out); },
                     ctx->Mdd.vals.p, ctx->diagpos3.p, nullptr, td, dd, IW, ctx->cheb_its_d, ctx->lmax_d, ctx->cheb_kappa_d);
-    else
+    } else {
+      ctx->inner_its[2] += ctx->cheb_its_d;
       cheb_solve(ctx, CsrRef{n3, ctx->rowptr3.p, ctx->cols3.p, ctx->Mdd.vals.p, ctx->diagpos3.p}, nullptr, td, dd, IW,
                  ctx->cheb_its_d, ctx->lmax_d, ctx->cheb_kappa_d);
-    ctx->inner_its[2] += ctx->cheb_its_d;
+    }
   }
   if (conc) HIPCHK(hipStreamWaitEvent(sA, ctx->ev_b, 0));
-  if (dd_f32) launch_merge_f32d(st, N2, V, dd_f32, dv, dp, z);
+  if (dd_f32) launch_merge_f32d(st, N2, V, dd_f32, dv, dp, z, dd_d);
   else launch_merge(st, N2, V, dd, dv, dp, z);
   if (ctx->debug_prec_apply > 0) {                 // FSI_DEBUG_PRECOND=2: non-finite entries of the parts, first applications only
     ctx->debug_prec_apply -= 1;
