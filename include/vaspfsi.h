@@ -267,6 +267,17 @@ int fsi_set_rccl(FsiCtx* ctx, const void* id128, int32_t rank, int32_t world, co
 /* which: 0 = dvp_["n"], 1 = dvp_["n-1"], 2 = last rhs b, 3 = last update du.  User layout, length ndof. */
 int fsi_get_state(FsiCtx* ctx, int which, double* out);
 int fsi_set_state(FsiCtx* ctx, int which, const double* in);
+/* Replaces: the read loop of vasp-create-hdf5 / create_transformed_matrix that rebuilds a Function from one saved frame
+ * [REF src/vasp/postprocessing/postprocessing_fenics/create_hdf5.py:139-160;
+ *  src/vasp/postprocessing/postprocessing_h5py/postprocessing_h5py_common.py:154-409].  One frame of the Visualization files
+ * into dvp_["n"] (which = 0) or dvp_["n-1"] (1): d and v are [n_nodes][3], p has n_nodes entries of which the first V are used,
+ * all in the files' node order (vertices, then one node per edge).  Any of the three may be null: that field of the state is
+ * left untouched.  n_nodes is N2 (save_deg 2: the values as they are) or V (save_deg 1: a mid-edge node takes 0.5 * (a + b) of
+ * its edge's two vertices - the P1 field the reference's tools see in such a folder); anything else is FSI_ERR_INVALID with
+ * both numbers in fsi_last_error.  The fields are staged in an existing work vector; the table of edge vertices is built at
+ * the first save_deg 1 call and kept.  The copies have finished when the call returns: the caller's arrays may be unmapped.
+ * Not for partitioned contexts. */
+int fsi_set_frame(FsiCtx* ctx, int which, int64_t n_nodes, const double* d, const double* v, const double* p);
 /* out[i] = state[dofs[i]] (user layout): what a hook needs of dvp_ on a patch (the inlet facets of
  * assemble(inner(v, n) * ds(inlet)) [REF src/vasp/simulations/simulation_common.py:276]) without the whole vector
  * crossing PCIe every time step. */

@@ -20,7 +20,7 @@ EXPORTED_SYMBOLS = (
     "fsi_create", "fsi_destroy", "fsi_last_error", "fsi_set_dirichlet", "fsi_set_dirichlet_values",
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
-    "fsi_get_state", "fsi_set_state", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
+    "fsi_get_state", "fsi_set_state", "fsi_set_frame", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
     "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_spec_begin", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
@@ -143,6 +143,7 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_shift.argtypes = [vp]
     lib.fsi_get_state.argtypes = [vp, C.c_int, vp]
     lib.fsi_set_state.argtypes = [vp, C.c_int, vp]
+    lib.fsi_set_frame.argtypes = [vp, C.c_int, i64, vp, vp, vp]
     lib.fsi_get_values.argtypes = [vp, C.c_int, i64, vp, vp]
     lib.fsi_calibration_streams.argtypes = [vp, i64]
     lib.fsi_set_newton_forcing.argtypes = [vp, dbl]
@@ -389,6 +390,27 @@ class HipBackend:
         assert x.shape == (self.ndof,)
         self._flow_stats = None
         self._check(self.lib.fsi_set_state(self.ctx, STATE[which], _ptr(x)))
+
+    def set_frame(self, which, d=None, v=None, p=None) -> None:
+        """One saved Visualization frame into the state (fsi_set_frame): d, v (n, 3) and p (n,) or (n, 1) on the files' n nodes,
+        n the mesh's vertices (save_deg 1: mid-edge nodes take their edge's mean) or its P2 nodes (save_deg 2).  A field that
+        is None keeps what the state holds.  C-contiguous FP64 arrays - the views of a mapped file - are passed as they are."""
+        given = {k: a for k, a in (("d", d), ("v", v), ("p", p)) if a is not None}
+        if not given:
+            return
+        arrs, n = {}, None
+        for k, a in given.items():
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous):
+                a = np.ascontiguousarray(a, dtype=np.float64)
+            rows = a.shape[0] if a.ndim else 0
+            if a.size != rows * (1 if k == "p" else 3):
+                raise ValueError(f"set_frame: {k} of shape {a.shape}, expected (n, {1 if k == 'p' else 3})")
+            if n is not None and rows != n:
+                raise ValueError(f"set_frame: {k} has {rows} nodes, another field {n}")
+            arrs[k], n = a, rows
+        self._flow_stats = None
+        ptr = lambda k: _ptr(arrs[k]) if k in arrs else None
+        self._check(self.lib.fsi_set_frame(self.ctx, STATE[which], n, ptr("d"), ptr("v"), ptr("p")))
 
     # ---- pieces of the hot path (tests, benchmarks) ----------------------------------------------------
     def assemble_residual(self) -> float:

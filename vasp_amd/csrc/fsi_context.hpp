@@ -376,6 +376,7 @@ struct FsiCtx {
   // host copy of the mesh needed after create
   std::vector<double> h_coords;
   std::vector<int32_t> h_tet_nodes;
+  fsi::DevBuf<int32_t> frame_edges;          // fsi_set_frame: [N2 - V][2] the two vertices of every mid-edge node, built at the first save_deg 1 frame
 
   // hemodynamics session (fsi_hemo_begin .. fsi_hemo_end): boundary cells, their facet masks and the user-order facet
   // index of each (cell, local facet), uploaded once; accumulators per DG1 dof of the boundary mesh (fsi_hemo.hip)

@@ -156,7 +156,7 @@ class _Reader:
             val = np.frombuffer(raw, dtype=dt, count=n).reshape(shape).copy()
         return name, val
 
-    def _read_object(self, addr: int):
+    def _read_object(self, addr: int, path: str = ""):
         msgs = self._messages(addr)
         types = [t for t, _ in msgs]
         attrs = {}
@@ -170,13 +170,16 @@ class _Reader:
             g = Group()
             g.attrs = attrs
             for name, child in self._group_entries(btree + self.base, heap + self.base):
-                g[name] = self._read_object(child + self.base)
+                g[name] = self._read_object(child + self.base, f"{path}/{name}")
             return g
         md = {}
         for t, m in msgs:
             md.setdefault(t, m)
         if 0x0001 not in md or 0x0003 not in md or 0x0008 not in md:
             raise H5Error(f"object at {addr:#x} is neither an old-style group nor a simple dataset")
+        return self._read_dataset(md, attrs, path)
+
+    def _read_dataset(self, md, attrs, path: str):
         shape = self._parse_dataspace(md[0x0001])
         dt, esize = self._parse_datatype(md[0x0003])
         lay = md[0x0008]
@@ -247,6 +250,85 @@ def read_h5(path) -> Group:
     with open(path, "rb") as f:
         buf = f.read()
     return _Reader(buf).read()
+
+
+class LazyDataset(Dataset):
+    """A contiguous numeric dataset of a mapped file: ``data`` is a read-only view of its block in the mapping, made when it
+    is first touched - nothing of it is read before, and only the pages that are used afterwards."""
+
+    def __init__(self, buf, offset: int, dtype: np.dtype, shape, attrs=None):
+        self._buf, self._offset, self._dtype, self._shape = buf, offset, dtype, tuple(shape)
+        self._data = None
+        self.attrs = dict(attrs or {})
+
+    @property
+    def data(self) -> np.ndarray:
+        if self._data is None:
+            n = int(np.prod(self._shape)) if self._shape else 1
+            self._data = np.frombuffer(self._buf, dtype=self._dtype, count=n, offset=self._offset).reshape(self._shape)
+        return self._data
+
+    @property
+    def shape(self):
+        return self._shape
+
+
+class _LazyReader(_Reader):
+    """The same object walk over a mapping of the file: headers, group tables and heaps are read where they lie, a numeric
+    dataset's block is only located."""
+
+    def _read_dataset(self, md, attrs, path: str):
+        shape = self._parse_dataspace(md[0x0001])
+        dt, esize = self._parse_datatype(md[0x0003])
+        lay = md[0x0008]
+        if 0x000B in md:
+            raise H5Error(f"dataset {path}: a filter pipeline (compression) is not supported")
+        if lay[0] != 3 or lay[1] not in (0, 1):
+            raise H5Error(f"dataset {path}: layout version {lay[0]} class {lay[1]} not supported (chunked? only contiguous and compact "
+                          "datasets are read)")
+        n = int(np.prod(shape)) if shape else 1
+        if lay[1] == 1 and dt != "string":
+            daddr, _ = struct.unpack_from("<QQ", lay, 2)
+            if daddr != UNDEF:
+                if daddr + self.base + n * esize > len(self.b):
+                    raise H5Error(f"dataset {path}: its {n * esize} bytes at {daddr + self.base:#x} end behind the file")
+                return LazyDataset(self.b, daddr + self.base, dt, shape, attrs)
+        return super()._read_dataset(md, attrs, path)
+
+
+class LazyFile:
+    """``open_h5``'s handle: ``root`` is the tree, whose numeric datasets are views of the mapped file.  ``close`` drops the
+    tree; the mapping goes when the last view of it has gone."""
+
+    def __init__(self, path):
+        import mmap
+        self.path = path
+        with open(path, "rb") as f:
+            self._map = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+        self.root = _LazyReader(self._map).read()
+
+    def __getitem__(self, name):
+        return self.root[name]
+
+    def close(self) -> None:
+        self.root = None
+        try:
+            self._map.close()
+        except BufferError:             # a view handed out is still alive: the mapping is released with it
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def open_h5(path) -> LazyFile:
+    """Open a (large) HDF5 file of the subset above without reading its datasets: the walk of ``read_h5`` over an ``mmap``.
+    The tree is built from the group tables the file's headers point at now - for a series that ``H5Series`` appended to in
+    place these are the re-pointed ones, which list every frame."""
+    return LazyFile(path)
 
 
 # --------------------------------------------------------------------------------------------

@@ -25,7 +25,7 @@ from typing import Dict, List, Tuple
 import numpy as np
 
 from .h5lite import Dataset, Group, H5Series, write_h5
-from .hi_pass import check_fingerprint, load_array, restart_entry, restart_refusal, save_array, sessions_folder, sha256_of
+from .hi_pass import check_fingerprint, frame_spacing, load_array, restart_entry, restart_refusal, save_array, sessions_folder, sha256_of
 from .mesh import FsiMesh
 
 INDEX_NAMES = ("TAWSS", "OSI", "RRT", "ECAP", "TWSSG")
@@ -247,10 +247,11 @@ class HemodynamicsRun:
 
     key, option = "hemodynamics", "--hemodynamics"
     words = "--hemodynamics cannot continue under --restart-folder"
+    reads = ("v",)                                  # the fields of dvp_["n"] the session reads
 
     def __init__(self, backend, mesh: FsiMesh, ns: dict):
         mu = ns["mu_f"][0] if isinstance(ns["mu_f"], (list, tuple)) else ns["mu_f"]
-        dt_sample = float(ns["dt"]) * int(ns["save_step"])
+        dt_sample = frame_spacing(ns)
         _, cells, local = fluid_boundary_facets(mesh, ns["dx_f_id"])
         geometry, topology = boundary_triangles(mesh, cells, local)
         self.backend = backend

@@ -16,7 +16,10 @@ This module holds
   ``--hi-pass-start-time``, ``--hi-pass-end-time``); the raw series of listed nodes (``--hi-pass-point-ids``);
 * what the four post-processing options share to go through a checkpoint: the manifest and the files of
   ``<results>/Checkpoint/sessions/`` and the checks of a restart (``save_sessions``, ``restart_entry``), and the saving and
-  restoring of a recorded history (``SessionRun``).
+  restoring of a recorded history (``SessionRun``);
+* the three parameters by which ``vasp_amd.postprocess`` tells the options the frames of a finished folder instead of a run's
+  ``T`` and ``save_step``: ``frame_times`` (``saved_times``), ``frame_stride`` (``frame_spacing``), ``frame_start``.  A run
+  sets none of them.
 
 What a filter stage and a trace cost on a mesh of the benchmark's size has not been measured.
 The reference's ``strain`` / ``stress`` quantities are ``--hi-pass-tensor`` (``hi_pass_tensor.py``), on the sessions of this module.
@@ -442,6 +445,7 @@ class SessionRun:
     prefix, begin = "", "begin"                     # HipBackend.<prefix>_<begin> opens the device session
 
     key = option = words = ""                       # the manifest's key, the option and its sentence about --restart-folder
+    reads = None                                    # the fields of dvp_["n"] the sessions read, of d, v, p: None - the quantities asked for
 
     def open_sessions(self, backend, ns: dict, begin_args, host_session) -> None:
         """``begin_args(q)``: the device session's arguments before the capacity; ``host_session(q, capacity)``: its host twin.
@@ -623,7 +627,10 @@ def bands(v: dict) -> List[Tuple[float, float]]:
 
 def saved_times(v: dict) -> List[float]:
     """The times of the frames the time loop of ``monolithic`` saves with these parameters (``while t <= T + dt / 10``, a
-    frame when ``counter % save_step == 0``)."""
+    frame when ``counter % save_step == 0``) - or, where ``v["frame_times"]`` lists them, the frames a finished folder hands
+    over (``vasp_amd.postprocess``)."""
+    if v.get("frame_times") is not None:
+        return [float(t) for t in v["frame_times"]]
     dt, T, step = float(v["dt"]), float(v["T"]), int(v["save_step"])
     t, counter, times = float(v.get("t", 0.0)), int(v.get("counter", 0)), []
     while t <= T + dt / 10:
@@ -637,6 +644,19 @@ def saved_times(v: dict) -> List[float]:
 def expected_frames(v: dict) -> int:
     """Frames the time loop saves with these parameters."""
     return len(saved_times(v))
+
+
+def frame_spacing(v: dict) -> float:
+    """Seconds between two frames the sessions are handed: ``dt * save_step`` in a run; times ``v["frame_stride"]`` where a
+    finished folder is read on every S-th frame (``vasp_amd.postprocess --stride``)."""
+    spacing = float(v["dt"]) * int(v["save_step"])
+    return spacing * int(v["frame_stride"]) if v.get("frame_stride") is not None else spacing
+
+
+def frame_start(v: dict, default: float = 0.0) -> float:
+    """The time the written files start at: ``default`` in a run and on a finished folder read without ``--start-time``, else
+    ``v["frame_start"]`` (``vasp_amd.postprocess --start-time``, the reference's ``start_t``)."""
+    return float(v["frame_start"]) if v.get("frame_times") is not None and v.get("frame_start") is not None else default
 
 
 def multiband(v: dict) -> List[str]:
@@ -706,7 +726,7 @@ def hi_pass_refusal(v: dict, world: int, backend_cls) -> str:
             return (f"--hi-pass: the run {saves}, the filter of band {lo:g} - {hi:g} Hz needs at least "
                     f"padlen + 1 = {padlen_of(lo) + 1}")
     if words:
-        dt_files = float(v["dt"]) * int(v["save_step"]) * stride
+        dt_files = frame_spacing(v) * stride
         for lo, hi in bands(v):
             why = stage_refusal(dt_files, lo, hi)
             if why:
@@ -758,10 +778,11 @@ class HiPassRun(SessionRun):
         self.pass_stop = multiband(ns)
         self.point_ids = point_ids(ns)
         self.stride, self.t0, self.t1 = frame_window(ns)
+        self.t0 = frame_start(ns, self.t0)
         self.amplitude = bool(ns.get("hi_pass_amplitude"))
         self.window = int(ns.get("hi_pass_window") or 250)
         self.dt = float(ns["dt"])
-        self.dt_sample = self.dt * int(ns["save_step"])
+        self.dt_sample = frame_spacing(ns)
         self.dt_files = self.dt_sample * self.stride
         self.nodes = {q: output_nodes(mesh, self.save_deg, q) for q in self.quantities}
         if self.save_deg >= 2:

@@ -33,8 +33,8 @@ import numpy as np
 
 from .h5lite import Dataset, Group, H5Series
 from .hemodynamics import XDMF_FOOTER, _dg1_group, _xdmf_grid, _xdmf_head
-from .hi_pass import (CSV_HEADER, SessionRun, amplitude_row, bands, design, frame_times, padlen_of, restart_refusal,
-                      sha256_of)
+from .hi_pass import (CSV_HEADER, SessionRun, amplitude_row, bands, design, frame_spacing, frame_start, frame_times, padlen_of,
+                      restart_refusal, sha256_of)
 from .mesh import FsiMesh
 from .stress_strain import solid_cells, solid_submesh
 
@@ -170,6 +170,7 @@ class HiPassTensorRun(SessionRun):
     prefix, begin = "hi_pass", "begin_cells"
     file_stem = key = "hi_pass_tensor"
     option, words = "--hi-pass-tensor", "--hi-pass-tensor cannot be used with --restart-folder"
+    reads = ("d",)
 
     def __init__(self, backend, mesh: FsiMesh, ns: dict):
         self.backend = backend
@@ -177,8 +178,8 @@ class HiPassTensorRun(SessionRun):
         self.bands = bands(ns)
         self.amplitude = bool(ns.get("hi_pass_amplitude"))
         self.window = window(ns)
-        self.dt_files = self.dt_sample = float(ns["dt"]) * int(ns["save_step"])
-        self.t0 = 0.0
+        self.dt_files = self.dt_sample = frame_spacing(ns)
+        self.t0 = frame_start(ns)
         self.cells = solid_cells(mesh, ns["dx_s_id"])
         if len(self.cells) == 0:
             raise SystemExit(f"--hi-pass-tensor: no cell carries a solid marker (dx_s_id = {ns['dx_s_id']})")

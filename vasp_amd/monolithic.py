@@ -45,28 +45,8 @@ def _coerce(text: str):
         return text
 
 
-def parse(argv: Optional[List[str]] = None) -> Dict[str, object]:
-    ap = argparse.ArgumentParser(prog="vaspfsi", description="MI355X-native monolithic ALE-FSI solver "
-                                 "behind the turtleFSI problem-file API")
-    ap.add_argument("-p", "--problem", default=None)       # "offset_stenosis" unless the command line or the -c file names one
-    ap.add_argument("-dt", "--time-step", dest="dt", type=float, default=None)
-    ap.add_argument("-T", "--end-time", dest="T", type=float, default=None)
-    ap.add_argument("-t", "--theta", dest="theta", type=float, default=None)
-    ap.add_argument("--atol", type=float, default=None)
-    ap.add_argument("--rtol", type=float, default=None)
-    ap.add_argument("--max-it", dest="max_it", type=int, default=None)
-    ap.add_argument("--lmbda", type=float, default=None)
-    ap.add_argument("--recompute", type=int, default=None)
-    ap.add_argument("--recompute-tstep", dest="recompute_tstep", type=int, default=None)
-    ap.add_argument("--verbose", type=_coerce, default=None)
-    ap.add_argument("--folder", default=None)
-    ap.add_argument("--sub-folder", dest="sub_folder", default=None)
-    ap.add_argument("--restart-folder", dest="restart_folder", default=None)
-    ap.add_argument("--save-step", dest="save_step", type=int, default=None)
-    ap.add_argument("--save-deg", dest="save_deg", type=int, default=None)
-    ap.add_argument("--checkpoint-step", dest="checkpoint_step", type=int, default=None)
-    ap.add_argument("--killtime", type=float, default=None)
-    ap.add_argument("--new-arguments", dest="new_arguments", nargs="*", default=[])
+def add_session_arguments(ap) -> None:
+    """The options of the five post-processing sessions (``SESSIONS``), for this parser and ``vasp_amd.postprocess``'s."""
     ap.add_argument("--hemodynamics", action="store_const", const=True, default=None,
                     help="accumulate WSS, TAWSS, OSI, RRT, ECAP and TWSSG on the device over the saved frames and write "
                          "<results>/Hemodynamic_indices/ (what vasp-compute-hemo writes afterwards)")
@@ -105,9 +85,10 @@ def parse(argv: Optional[List[str]] = None) -> Dict[str, object]:
                     help="frames of the RMS window of the --hi-pass-tensor amplitudes (default: 50)")
     from .spectrogram import add_arguments as add_spectrogram_arguments
     add_spectrogram_arguments(ap, _coerce)
-    ap.add_argument("-c", "--config", dest="config", default=None,
-                    help="config file with `key = value` lines (keys: the option names without dashes, or any problem-file "
-                         "parameter); the command line wins over the file [REF docs/simulation.md:19-31]")
+
+
+def resolve_arguments(ap, argv) -> Dict[str, object]:
+    """The options given in the -c file, under those given on the command line, under --new-arguments."""
     ns = ap.parse_args(argv)
     out = {}
     if ns.config is not None:          # turtleFSI's ConfigArgParse behaviour: file < command line
@@ -137,6 +118,36 @@ def parse(argv: Optional[List[str]] = None) -> Dict[str, object]:
             raise SystemExit(f"--new-arguments expects key=value, got {kv!r}")
         k, v = kv.split("=", 1)
         out[k] = _coerce(v)
+    return out
+
+
+def parse(argv: Optional[List[str]] = None) -> Dict[str, object]:
+    ap = argparse.ArgumentParser(prog="vaspfsi", description="MI355X-native monolithic ALE-FSI solver "
+                                 "behind the turtleFSI problem-file API")
+    ap.add_argument("-p", "--problem", default=None)       # "offset_stenosis" unless the command line or the -c file names one
+    ap.add_argument("-dt", "--time-step", dest="dt", type=float, default=None)
+    ap.add_argument("-T", "--end-time", dest="T", type=float, default=None)
+    ap.add_argument("-t", "--theta", dest="theta", type=float, default=None)
+    ap.add_argument("--atol", type=float, default=None)
+    ap.add_argument("--rtol", type=float, default=None)
+    ap.add_argument("--max-it", dest="max_it", type=int, default=None)
+    ap.add_argument("--lmbda", type=float, default=None)
+    ap.add_argument("--recompute", type=int, default=None)
+    ap.add_argument("--recompute-tstep", dest="recompute_tstep", type=int, default=None)
+    ap.add_argument("--verbose", type=_coerce, default=None)
+    ap.add_argument("--folder", default=None)
+    ap.add_argument("--sub-folder", dest="sub_folder", default=None)
+    ap.add_argument("--restart-folder", dest="restart_folder", default=None)
+    ap.add_argument("--save-step", dest="save_step", type=int, default=None)
+    ap.add_argument("--save-deg", dest="save_deg", type=int, default=None)
+    ap.add_argument("--checkpoint-step", dest="checkpoint_step", type=int, default=None)
+    ap.add_argument("--killtime", type=float, default=None)
+    ap.add_argument("--new-arguments", dest="new_arguments", nargs="*", default=[])
+    add_session_arguments(ap)
+    ap.add_argument("-c", "--config", dest="config", default=None,
+                    help="config file with `key = value` lines (keys: the option names without dashes, or any problem-file "
+                         "parameter); the command line wins over the file [REF docs/simulation.md:19-31]")
+    out = resolve_arguments(ap, argv)
     out.setdefault("problem", "offset_stenosis")
     return out
 

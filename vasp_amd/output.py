@@ -43,6 +43,20 @@ def refine_topology(mesh: FsiMesh) -> np.ndarray:
     return np.stack([np.stack(k, axis=1) for k in kids], axis=1).reshape(-1, 4)
 
 
+def xdmf_entries(path) -> list:
+    """(time, h5 file name, index in that file) of every frame a field's XDMF lists, in its order - the lines
+    ``output_file_lists`` parses [REF src/vasp/postprocessing/postprocessing_common.py:63-121]."""
+    import re
+    times, files, idx = [], [], []
+    for line in Path(path).read_text().splitlines():
+        if "<Time Value" in line:
+            times.append(float(re.findall('<Time Value="(.+?)"', line)[0]))
+        if "VisualisationVector" in line:
+            files.append(re.findall('"HDF">(.+?):/', line)[0])
+            idx.append(int(re.findall("VisualisationVector/(.+?)</DataItem", line)[0]))
+    return list(zip(times, files, idx))
+
+
 class VisualizationWriter:
     """Appends every saved frame to ``<name>.h5`` - one file per field and run, as DOLFIN's ``XDMFFile.write`` does.
 
@@ -82,19 +96,11 @@ class VisualizationWriter:
         return f"{name}.h5" if self.run_index == 0 else f"{name}_run_{self.run_index}.h5"
 
     def _adopt_existing(self) -> None:
-        import re
         for name, _, _ in FIELDS:
             path = self.folder / f"{name}.xdmf"
             if not path.exists():
                 continue
-            times, files, idx = [], [], []
-            for line in path.read_text().splitlines():
-                if "<Time Value" in line:
-                    times.append(float(re.findall('<Time Value="(.+?)"', line)[0]))
-                if "VisualisationVector" in line:
-                    files.append(re.findall('"HDF">(.+?):/', line)[0])
-                    idx.append(int(re.findall("VisualisationVector/(.+?)</DataItem", line)[0]))
-            self.entries[name] = list(zip(times, files, idx))
+            self.entries[name] = xdmf_entries(path)
 
     @property
     def times(self):

@@ -21,7 +21,10 @@ whatever ``--spectrogram-window`` says (:410-419).
 Times: the frames are ``dt * save_step`` apart; ``T = frames * dt * save_step``, ``start_t = 0`` (the reference's default),
 ``fs = frames / T``.
 
-Not done: ``domain`` sampling, the ``wss`` quantity, the PNG figures, ``sonify_point``, ``--stride``.
+``--stride`` and a time window are those of ``vasp_amd.postprocess`` on a finished folder: the spacing, ``T`` and ``start_t`` then
+come from the frames that were read.
+
+Not done: ``domain`` sampling, the ``wss`` quantity, the PNG figures, ``sonify_point``.
 """
 from __future__ import annotations
 
@@ -30,7 +33,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from .hi_pass import HostHistory, SessionRun, frame_times, output_nodes, restart_refusal, sha256_of
+from .hi_pass import HostHistory, SessionRun, frame_spacing, frame_start, frame_times, output_nodes, restart_refusal, sha256_of
 from .mesh import FsiMesh
 
 HP_ORDER = 6                                    # filter_time_data(order=6, btype="highpass") [REF spectrograms.py:558]
@@ -443,7 +446,7 @@ def spectrogram_refusal(v: dict, world: int, backend_cls) -> str:
     if frames < HP_PADLEN + 1:
         split = f" ({past} saved before the restart and {frames - past} to come)" if v.get("restart_folder") else ""
         return f"--spectrogram: the run saves {frames} frames{split}, the high-pass filter needs at least padlen + 1 = {HP_PADLEN + 1}"
-    T = frames * float(v["dt"]) * int(v["save_step"])
+    T = frames * frame_spacing(v)
     plan = window_plan(frames, T, o["num_windows_per_sec"], o["overlap_frac"])
     if plan["nseg"] < 2:
         return (f"--spectrogram: {frames} frames over {T:g} s in {plan['num_windows']:g} windows (--spectrogram-num-windows-per-sec) give "
@@ -462,9 +465,10 @@ class SpectrogramRun(SessionRun):
         self.quantities = quantities(ns)
         self.opts = options(ns)
         self.save_deg = int(ns["save_deg"])
-        self.dt_files = float(ns["dt"]) * int(ns["save_step"])
+        self.dt_files = frame_spacing(ns)
+        self.start_t = frame_start(ns)
         self.folder = Path(ns["results_folder"]) / "Spectrograms"
-        self.case = Path(ns["results_folder"]).parent.name
+        self.case = str(ns.get("case") or Path(ns["results_folder"]).parent.name)     # "case": the folder that was read, where the files go elsewhere
         self.sel = {q: select_nodes(mesh, self.save_deg, q, ns, self.opts) for q in self.quantities}     # an empty region ends the run here
         self.open_sessions(backend, ns, lambda q: (self.sel[q]["nodes"], self.sel[q]["nodes_b"], self.opts["component"]),
                            lambda q, capacity: HostSpecSession(self.rows(q), capacity))
@@ -500,7 +504,7 @@ class SpectrogramRun(SessionRun):
                 "nothing written")
             return
         for q, session in self.sessions.items():
-            res = pipeline(session, self.rows(q), n, T, 0.0, self.opts, self.min_color(q))
+            res = pipeline(session, self.rows(q), n, T, self.start_t, self.opts, self.min_color(q))
             write_files(self.folder, self.sel[q]["name"], self.case + self.sel[q]["case_suffix"], res, self.min_color(q))
         out(f"Spectrograms of {n} frames ({', '.join(self.quantities)}; {self.opts['sampling']}, "
             f"{', '.join(str(self.rows(q)) for q in self.quantities)} rows) written to {self.folder}")

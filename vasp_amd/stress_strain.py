@@ -25,7 +25,7 @@ import numpy as np
 
 from .h5lite import Group, write_h5
 from .hemodynamics import XDMF_FOOTER, Dg1Series, _dg1_group, _xdmf_grid, _xdmf_head
-from .hi_pass import check_fingerprint, load_array, restart_entry, restart_refusal, save_array, sessions_folder, sha256_of
+from .hi_pass import check_fingerprint, frame_spacing, load_array, restart_entry, restart_refusal, save_array, sessions_folder, sha256_of
 from .mesh import FsiMesh
 
 FRAME_NAMES = ("TrueStress", "GreenLagrangeStrain", "MaxPrincipalStress", "MaxPrincipalStrain")
@@ -110,6 +110,7 @@ class StressStrainRun:
 
     key, option = "stress_strain", "--stress-strain"
     words = "--stress-strain cannot continue under --restart-folder"
+    reads = ("d",)                                  # the fields of dvp_["n"] the session reads
 
     def __init__(self, backend, mesh: FsiMesh, ns: dict):
         cells = solid_cells(mesh, ns["dx_s_id"])
@@ -117,7 +118,7 @@ class StressStrainRun:
             raise SystemExit(f"--stress-strain: no cell carries a solid marker (dx_s_id = {ns['dx_s_id']})")
         geometry, topology = solid_submesh(mesh, cells)
         self.backend = backend
-        self.fingerprint = dict(dt_sample=float(ns["dt"]) * int(ns["save_step"]), rows=len(cells), cells=sha256_of(cells))
+        self.fingerprint = dict(dt_sample=frame_spacing(ns), rows=len(cells), cells=sha256_of(cells))
         self.times: List[float] = []
         entry = restart_entry(ns, self.key, self.words)
         if entry is not None:
