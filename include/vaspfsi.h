@@ -396,7 +396,7 @@ int fsi_stress_end(FsiCtx* ctx);
  * [REF src/vasp/postprocessing/postprocessing_h5py/postprocessing_h5py_common.py:154-409].  Opens a session on n listed nodes
  * (P2 node ids for d / v, vertex ids for p); where nodes_b (nullable) is >= 0 the row is the mean of the two nodes' values (the
  * pressure at an edge node of the save_deg 2 output).  capacity: frames the history can take.  The bytes of the history, the
- * filtered series (capacity + 66 frames) and three work frames are compared with the free device memory: if less than 1/16
+ * filtered series (capacity + 66 frames) and three work frames (fsi_band_room) are compared with the free device memory: if less than 1/16
  * of the device would stay free for the context, FSI_ERR_INVALID with both byte counts in fsi_last_error and nothing
  * allocated - no paging, no truncation.  Replaces an open session of the quantity; a refused call (node out of range,
  * capacity, device memory) leaves it as it was, its bytes counted as taken.  Not for partitioned contexts. */
@@ -479,6 +479,45 @@ int fsi_band_export(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count,
  * frames + count exceed the capacity, with count < 1 or null frames, without an open session and for a partitioned context;
  * a refused call leaves the session as it was. */
 int fsi_band_import(FsiCtx* ctx, int32_t quantity, int64_t count, const double* frames);
+/* Replaces: the sizing a user of create_transformed_matrix does by hand before the node x time matrix is allocated in host
+ * memory [REF .../postprocessing_h5py_common.py:309-321]: the two byte counts fsi_band_begin and fsi_band_begin_cells compare
+ * for a session of `rows` rows (3 per node for d / v, 1 for p, 24 per cell for strain / stress) and `capacity` frames.
+ * *need: the history, the filtered series (capacity + 66 frames), one frame each of running sums, amplitudes and magnitudes
+ * and the row lists, 8 * rows * (2 * capacity + 70) bytes; *available: the free device memory less the 1/16 of the device
+ * that stays with the context.  A begin call is refused exactly when need > available.  Nothing is allocated. */
+int fsi_band_room(FsiCtx* ctx, int64_t rows, int64_t capacity, double* need, double* available);
+/* Replaces: rms_magnitude, the node x time matrix of amplitude magnitudes create_hi_pass_viz keeps in host memory for its
+ * table [REF .../create_hi_pass_viz.py:244,341,370-376], for a quantity whose rows go through the band-pass sessions in
+ * strips: board[frame][node], FP64, 8 * nodes * frames bytes, one per context.  Refused like a session when it does not fit
+ * beside the context's 1/16 of the device: FSI_ERR_INVALID with both byte counts in fsi_last_error, nothing allocated, an
+ * open board left as it was.  Replaces an open board and detaches every session.  Not for partitioned contexts. */
+int fsi_board_begin(FsiCtx* ctx, int64_t nodes, int64_t frames);
+/* Frees the board and detaches every session (fsi_destroy does the same). */
+int fsi_board_end(FsiCtx* ctx);
+/* Replaces: the row range a strip of nodes takes in rms_magnitude [REF .../create_hi_pass_viz.py:341]: ties the open session of
+ * `quantity` to the board at node offset node0 (0 <= node0, node0 + the session's nodes <= the board's), or detaches it
+ * with node0 = -1.  From then on every fsi_band_fetch of FSI_BAND_AMPLITUDE or FSI_BAND_MAGNITUDE of frame k also stores the
+ * frame's magnitudes - what the fetch forms for max_out / argmax_out - into board[k][node0 .. node0 + n); k must be a frame
+ * of the board.  What a fetch returns does not change.  FSI_ERR_INVALID without a board, without a session, for a range
+ * outside the board and for a partitioned context. */
+int fsi_band_board_attach(FsiCtx* ctx, int32_t quantity, int64_t node0);
+/* Replaces: the eleven np.percentile calls, the np.max and the np.argmax per frame of the amplitude table
+ * [REF .../create_hi_pass_viz.py:377-390].  For board frames first .. first + count - 1: values[count][nranks], the order
+ * statistics of the frame's magnitudes at the zero-based ranks[nranks] (rank 0 the smallest; 0 <= rank < nodes; a rank may be
+ * listed twice; at most 32 distinct ranks) - a percentile is an interpolation of two neighbouring ones, formed by the caller
+ * -, nan_counts[count], the frame's NaNs (they order behind +inf, as numpy sorts them), max_out[count] and argmax_out[count],
+ * the largest magnitude and the first node that has it.  Exact: a radix select on the bits, integer counts only; the same
+ * call returns the same bits.  FSI_ERR_INVALID, with nothing written, without a board, for frames outside it, a rank out of
+ * range, null pointers and a partitioned context. */
+int fsi_board_table(FsiCtx* ctx, int64_t first, int64_t count, int32_t nranks, const int64_t* ranks, double* values,
+                    int64_t* nan_counts, double* max_out, int64_t* argmax_out);
+/* Replaces: np.percentile's partition of one array [REF .../create_hi_pass_viz.py:379-389] for a caller's own data: the
+ * selection of fsi_board_table on values[n] of the host, copied to the device, selected there and copied back.  out[nranks]:
+ * the elements of rank ranks[k] in ascending order (-0 orders below +0, subnormals as their values); *nan_count: the NaNs.
+ * FSI_ERR_INVALID, with nothing written, unless 1 <= n < 2^32, for a rank out of range, more than 32 distinct ranks, null
+ * pointers and a partitioned context. */
+int fsi_order_statistics(FsiCtx* ctx, int64_t n, const double* values, int32_t nranks, const int64_t* ranks, double* out,
+                         int64_t* nan_count);
 /* Closes the session of the quantity and frees its device memory (fsi_destroy does the same). */
 int fsi_band_end(FsiCtx* ctx, int32_t quantity);
 

@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_set_frame", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_spec_begin", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -173,6 +173,12 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_band_export.argtypes = [vp, i32, i64, i64, vp]
     lib.fsi_band_import.argtypes = [vp, i32, i64, vp]
     lib.fsi_band_end.argtypes = [vp, i32]
+    lib.fsi_band_room.argtypes = [vp, i64, i64, C.POINTER(dbl), C.POINTER(dbl)]
+    lib.fsi_board_begin.argtypes = [vp, i64, i64]
+    lib.fsi_board_end.argtypes = [vp]
+    lib.fsi_band_board_attach.argtypes = [vp, i32, i64]
+    lib.fsi_board_table.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp, vp]
+    lib.fsi_order_statistics.argtypes = [vp, i64, vp, i32, vp, vp, C.POINTER(i64)]
     lib.fsi_spec_begin.argtypes = [vp, i32, i64, vp, vp, i32, i64]
     lib.fsi_spec_sample.argtypes = [vp, i32]
     lib.fsi_spec_filter.argtypes = [vp, i32, i32, vp, vp, vp, i32]
@@ -696,6 +702,44 @@ class HipBackend:
 
     def hi_pass_end(self, quantity: str) -> None:
         self._check(self.lib.fsi_band_end(self.ctx, self.BAND_QUANTITY[quantity]))
+
+    def hi_pass_room(self, rows: int, capacity: int):
+        """(need, available) in bytes: what a band-pass session of ``rows`` rows and ``capacity`` frames takes and what the
+        device has for it - the two numbers ``hi_pass_begin`` / ``hi_pass_begin_cells`` compare (fsi_band_room)."""
+        need, avail = C.c_double(0.0), C.c_double(0.0)
+        self._check(self.lib.fsi_band_room(self.ctx, int(rows), int(capacity), C.byref(need), C.byref(avail)))
+        return int(need.value), int(avail.value)
+
+    def hi_pass_board_begin(self, nodes: int, frames: int) -> None:
+        """Open the magnitude board, (frames, nodes) FP64 on the device (fsi_board_begin); replaces an open one."""
+        self._check(self.lib.fsi_board_begin(self.ctx, int(nodes), int(frames)))
+        self._board_shape = (int(frames), int(nodes))
+
+    def hi_pass_board_end(self) -> None:
+        self._check(self.lib.fsi_board_end(self.ctx))
+
+    def hi_pass_board_attach(self, quantity: str, node0: int) -> None:
+        """From now on an 'amplitude' or 'magnitude' fetch of frame k of the session also stores its magnitudes into
+        ``board[k, node0:node0 + n]`` (fsi_band_board_attach); ``node0`` -1 detaches."""
+        self._check(self.lib.fsi_band_board_attach(self.ctx, self.BAND_QUANTITY[quantity], int(node0)))
+
+    def hi_pass_board_table(self, first: int, count: int, ranks):
+        """(values (count, len(ranks)), NaN counts, maxima, first nodes of the maxima) of ``count`` board frames from
+        ``first``: the order statistics at the zero-based ``ranks`` (fsi_board_table)."""
+        r = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        count = int(count)
+        values, nans = np.empty((max(count, 0), len(r))), np.zeros(max(count, 0), dtype=np.int64)
+        mx, am = np.empty(max(count, 0)), np.zeros(max(count, 0), dtype=np.int64)
+        self._check(self.lib.fsi_board_table(self.ctx, int(first), count, len(r), _ptr(r), _ptr(values), _ptr(nans), _ptr(mx), _ptr(am)))
+        return values, nans, mx, am
+
+    def order_statistics(self, values, ranks):
+        """(np.sort(values)[ranks], number of NaNs) of a host array, selected on the device (fsi_order_statistics)."""
+        x = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        r = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        out, nans = np.empty(len(r)), C.c_int64(0)
+        self._check(self.lib.fsi_order_statistics(self.ctx, len(x), _ptr(x), len(r), _ptr(r), _ptr(out), C.byref(nans)))
+        return out, int(nans.value)
 
     SPEC_MODE = {"x": 0, "y": 1, "z": 2, "all": 3, "mag": 4}
     SPEC_SCALING = {"spectrum": 0, "density": 1}

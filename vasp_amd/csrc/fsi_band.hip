@@ -36,6 +36,14 @@
 //                      - an amplitude is never NaN.
 //   k_band_magnitude : |amplitude| over the three components per node (numpy.linalg.norm's order), k_band_argmax_* its
 //                      maximum and the first node that has it (create_hi_pass_viz.py:341,381,390).
+//   k_band_select    : exact order statistics of a frame at up to SEL_MAX_RANKS ranks (the neighbours of the table's
+//                      percentiles, create_hi_pass_viz.py:377-390): a most-significant-digit radix select on the
+//                      order-preserving 64-bit image of the FP64 bits, one workgroup per frame, eight passes of one byte.
+//                      Ranks whose images still share their leading bytes share one LDS histogram of 256 integer counts; a
+//                      pass adds every element whose leading bytes are a rank's to that histogram (integer LDS atomics: the
+//                      counts, and so the result, do not depend on the order the lanes arrive in), then one lane per rank
+//                      walks its histogram to the byte its rank falls in.  Magnitudes of one frame share their leading
+//                      bytes, so a lane sums a run of equal slots in a register and adds once per run, not once per element.
 #include "fsi_band.hpp"
 
 #pragma clang fp contract(off)
@@ -233,6 +241,89 @@ __global__ __launch_bounds__(256) void k_band_argmax_final(int nparts, double* _
   if (threadIdx.x == 0) { pv[0] = bv; pi[0] = bi == INT64_MAX ? 0 : bi; }
 }
 
+// The image orders as the values do: sign bit flipped for v >= +0, every bit for v < 0 (-0 lies below +0); a NaN of either
+// sign takes the largest image, behind +inf, where numpy.sort puts it.
+__device__ __forceinline__ uint64_t sel_image(double v) {
+  if (v != v) return ~0ull;
+  const uint64_t b = (uint64_t)__double_as_longlong(v);
+  return (b >> 63) ? ~b : b | 0x8000000000000000ull;
+}
+__device__ __forceinline__ double sel_value(uint64_t k) {
+  if (k == ~0ull) return __longlong_as_double(0x7FF8000000000000ll);
+  return __longlong_as_double((long long)((k >> 63) ? k & 0x7FFFFFFFFFFFFFFFull : ~k));
+}
+
+// x[frame][.] at distance xs; ranks[nr] ascending and distinct, 0 <= rank < n; out[frame][nr], nans[frame]
+__global__ __launch_bounds__(256) void k_band_select(int64_t n, int64_t xs, const double* __restrict__ x, int nr,
+                                                     const int64_t* __restrict__ ranks, double* __restrict__ out,
+                                                     int64_t* __restrict__ nans) {
+  __shared__ uint32_t hist[BAND_SEL_MAX_RANKS][256];     // one per group of ranks with the same leading bytes
+  __shared__ uint64_t prefix[BAND_SEL_MAX_RANKS];        // per rank: the leading bytes found so far
+  __shared__ uint64_t below[BAND_SEL_MAX_RANKS];         // per rank: its rank among the elements that have those bytes
+  __shared__ uint64_t gprefix[BAND_SEL_MAX_RANKS];       // per group
+  __shared__ int group_of[BAND_SEL_MAX_RANKS];
+  __shared__ int ngroups;
+  __shared__ uint32_t nan_count;
+  const int t = threadIdx.x;
+  const double* f = x + (int64_t)blockIdx.x * xs;
+  if (t < nr) { prefix[t] = 0; below[t] = (uint64_t)ranks[t]; }
+  if (t == 0) nan_count = 0;
+  __syncthreads();
+  for (int pass = 0; pass < 8; ++pass) {
+    const int shift = 56 - 8 * pass;
+    if (t == 0) {
+      int g = 0;
+      for (int r = 0; r < nr; ++r) {
+        if (r == 0 || prefix[r] != prefix[r - 1]) gprefix[g++] = prefix[r];
+        group_of[r] = g - 1;
+      }
+      ngroups = g;
+    }
+    __syncthreads();
+    const int ng = ngroups;
+    for (int k = t; k < ng * 256; k += 256) (&hist[0][0])[k] = 0;
+    __syncthreads();
+    int slot = -1;                  // a run of elements for one slot of the histograms: summed here, added once
+    uint32_t run = 0, my_nans = 0;
+    for (int64_t i = t; i < n; i += 256) {
+      const double v = f[i];
+      const uint64_t key = sel_image(v);
+      if (pass == 0 && v != v) ++my_nans;
+      int g = 0;
+      if (pass > 0) {
+        const uint64_t lead = key >> (shift + 8);
+        for (g = 0; g < ng; ++g)
+          if (gprefix[g] == lead) break;
+        if (g == ng) continue;      // no rank lies among the elements with these leading bytes
+      }
+      const int s = g * 256 + (int)((key >> shift) & 255);
+      if (s != slot) {
+        if (run) atomicAdd(&(&hist[0][0])[slot], run);
+        slot = s;
+        run = 0;
+      }
+      ++run;
+    }
+    if (run) atomicAdd(&(&hist[0][0])[slot], run);
+    if (pass == 0 && my_nans) atomicAdd(&nan_count, my_nans);
+    __syncthreads();
+    if (t < nr) {
+      const uint32_t* h = hist[group_of[t]];
+      uint64_t k = below[t], c = 0;
+      int d = 0;
+      for (; d < 255; ++d) {        // the byte d with c(d) <= k < c(d) + h[d]; every element is counted, so one exists
+        if (k < c + h[d]) break;
+        c += h[d];
+      }
+      prefix[t] = (prefix[t] << 8) | (uint64_t)d;
+      below[t] = k - c;
+    }
+    __syncthreads();
+  }
+  if (t < nr) out[(int64_t)blockIdx.x * nr + t] = sel_value(prefix[t]);
+  if (t == 0) nans[blockIdx.x] = (int64_t)nan_count;
+}
+
 }  // namespace
 
 void launch_band_sample(hipStream_t st, int64_t nrow, const double* U, const int32_t* idx0, const int32_t* idx1, double* dst) {
@@ -272,6 +363,12 @@ void launch_band_argmax(hipStream_t st, int64_t n, const double* mag, double* pa
   const int nb = (int)((n + 255) / 256 < BAND_ARGMAX_BLOCKS ? (n + 255) / 256 : BAND_ARGMAX_BLOCKS);
   hipLaunchKernelGGL(k_band_argmax_part, dim3(nb), dim3(256), 0, st, n, mag, part_val, part_idx);
   hipLaunchKernelGGL(k_band_argmax_final, dim3(1), dim3(256), 0, st, nb, part_val, part_idx);
+}
+
+void launch_band_select(hipStream_t st, int64_t n, int64_t nframes, int64_t stride, const double* x, int nranks, const int64_t* ranks,
+                        double* out, int64_t* nans) {
+  if (n > 0 && nframes > 0 && nranks > 0)
+    hipLaunchKernelGGL(k_band_select, dim3((unsigned)nframes), dim3(256), 0, st, n, stride, x, nranks, ranks, out, nans);
 }
 
 }  // namespace fsi

@@ -37,5 +37,11 @@ void launch_band_rms(hipStream_t st, int64_t nrow, const double* y, int64_t star
 void launch_band_magnitude(hipStream_t st, int64_t nnode, int ncomp, const double* amp, double* mag);
 constexpr int BAND_ARGMAX_BLOCKS = 256;
 void launch_band_argmax(hipStream_t st, int64_t n, const double* mag, double* part_val, int64_t* part_idx);   // result in part_*[0]
+// Exact order statistics: out[frame][k] = the element of rank ranks[k] (0 = the smallest) of x[frame * stride + 0 .. n), for
+// nframes frames; ranks[nranks] on the device, ascending and distinct, nranks <= BAND_SEL_MAX_RANKS, n < 2^32.  nans[frame]:
+// the frame's NaNs, which order behind +inf.  Integer counts only: the same call gives the same bits.
+constexpr int BAND_SEL_MAX_RANKS = 32;
+void launch_band_select(hipStream_t st, int64_t n, int64_t nframes, int64_t stride, const double* x, int nranks, const int64_t* ranks,
+                        double* out, int64_t* nans);
 
 }  // namespace fsi

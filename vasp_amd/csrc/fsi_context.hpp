@@ -429,6 +429,7 @@ struct FsiCtx {
     // the view the filtered series, the amplitude and a trace are formed on (fsi_band_select): frames sel_first, sel_first +
     // sel_stride, ..., sel_count of them; sel_count < 0: every recorded frame.  A raw fetch keeps absolute frame indices.
     int64_t sel_first = 0, sel_stride = 1, sel_count = -1;
+    int64_t board_node0 = -1;                // >= 0: a fetched amplitude's magnitudes also go to board[frame][board_node0 ..)
     fsi::DevBuf<double> acc, amp, mag, part_val;
     fsi::DevBuf<int64_t> part_idx;
     void release() {
@@ -436,8 +437,19 @@ struct FsiCtx {
       acc.release(); amp.release(); mag.release(); part_val.release(); part_idx.release();
       ncomp = 0; window = -1; acc_start = -1;
       sel_first = 0; sel_stride = 1; sel_count = -1;
+      board_node0 = -1;
     }
   } band[5];
+
+  // the magnitude board (fsi_board_begin .. fsi_board_end): board[frame][node], the amplitude magnitudes of all nodes of a
+  // quantity whose rows go through the band-pass sessions in strips; the amplitude table is formed on it (fsi_board_table)
+  struct Board {
+    bool open = false;
+    int64_t nodes = 0, frames = 0;
+    fsi::DevBuf<double> data, part_val;
+    fsi::DevBuf<int64_t> part_idx;
+    void release() { data.release(); part_val.release(); part_idx.release(); open = false; nodes = frames = 0; }
+  } board;
 
   // spectrogram sessions (fsi_spec_begin .. fsi_spec_end), one per quantity d, v, p, with a history of their own on a row
   // list of their own.  mode: 0 / 1 / 2 one component, 3 the three stacked (row = c * nnode + i), 4 the magnitude, taken at

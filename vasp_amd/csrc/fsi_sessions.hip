@@ -77,6 +77,29 @@ int device_room(FsiCtx* ctx, Room* r) {
   return FSI_OK;
 }
 
+// The refusal rule of the band-pass begin calls, once: what a session of `rows` rows and `capacity` frames takes - the history,
+// the filtered series (capacity + 2 BAND_MAX_PADLEN frames), one frame each of running sums, amplitudes and magnitudes (a
+// frame of magnitudes counted as a frame of rows) and the row lists - and what the device has free less the context's 1/16.
+int band_room(FsiCtx* ctx, int64_t rows, int64_t capacity, double* need, double* available, Room* room) {
+  FSICHK(device_room(ctx, room));
+  *need = 8.0 * (double)rows * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN + 4.0);
+  *available = (double)room->free_b - room->reserve;
+  return FSI_OK;
+}
+int band_refused(FsiCtx* ctx, const char* fn, int64_t nrow, int64_t capacity) {
+  double need_d = 0.0, avail = 0.0;
+  Room room;
+  FSICHK(band_room(ctx, nrow, capacity, &need_d, &avail, &room));
+  if (need_d > avail) {
+    char msg[320];
+    snprintf(msg, sizeof msg, "%s: the session needs %.0f bytes (%lld rows x %lld frames, raw and filtered), the device has %zu bytes "
+             "free of which %.0f stay with the context", fn, need_d, (long long)nrow, (long long)capacity, room.free_b, room.reserve);
+    ctx->err = msg;
+    return FSI_ERR_INVALID;
+  }
+  return FSI_OK;
+}
+
 // Opens a session whose begin call has passed its checks and released what the quantity had: hist[capacity][nrow],
 // work[capacity + 2 BAND_MAX_PADLEN][nrow], the row lists and, where the row is the magnitude of three sampled entries, tmp.
 int history_open(FsiCtx* ctx, FsiCtx::History& s, int64_t n, int64_t nrow, int64_t capacity, const std::vector<int32_t>& i0,
@@ -307,6 +330,53 @@ int spec_power(FsiCtx* ctx, FsiCtx::Spec* s, const char* fn, int64_t K, int64_t 
   if (rc != FSI_OK) ctx->err = std::string(fn) + ": " + why;
   return rc;
 }
+
+// The ranks of a selection call: 0 <= rank < n each, at most BAND_SEL_MAX_RANKS distinct ones.  uniq: those, ascending;
+// where[k]: the place of ranks[k] among them (both nullable: the checks alone).
+int ranks_checked(FsiCtx* ctx, const char* fn, int64_t n, int32_t nranks, const int64_t* ranks, std::vector<int64_t>* uniq, std::vector<int>* where) {
+  if (nranks < 1 || !ranks) { ctx->err = std::string(fn) + ": needs nranks >= 1 ranks"; return FSI_ERR_INVALID; }
+  std::vector<int64_t> u(ranks, ranks + nranks);
+  for (int64_t r : u)
+    if (r < 0 || r >= n) { ctx->err = std::string(fn) + ": rank " + std::to_string(r) + " out of range, needs 0 <= rank < " + std::to_string(n); return FSI_ERR_INVALID; }
+  std::sort(u.begin(), u.end());
+  u.erase(std::unique(u.begin(), u.end()), u.end());
+  if ((int64_t)u.size() > BAND_SEL_MAX_RANKS) {
+    ctx->err = std::string(fn) + ": " + std::to_string(u.size()) + " distinct ranks, one call takes " + std::to_string(BAND_SEL_MAX_RANKS);
+    return FSI_ERR_INVALID;
+  }
+  if (where) {
+    where->resize((size_t)nranks);
+    for (int32_t k = 0; k < nranks; ++k) (*where)[k] = (int)(std::lower_bound(u.begin(), u.end(), ranks[k]) - u.begin());
+  }
+  if (uniq) uniq->swap(u);
+  return FSI_OK;
+}
+
+// values[frame][nranks], nan_counts[frame] of `frames` frames of n elements at x (device), `stride` elements apart: the
+// selection kernel on the distinct ranks, copied back and spread over the ranks asked for
+int order_statistics(FsiCtx* ctx, const char* fn, int64_t n, int64_t frames, int64_t stride, const double* x, int32_t nranks, const int64_t* ranks,
+                     double* values, int64_t* nan_counts) {
+  std::vector<int64_t> uniq;
+  std::vector<int> where;
+  FSICHK(ranks_checked(ctx, fn, n, nranks, ranks, &uniq, &where));
+  const size_t nu = uniq.size();
+  DevBuf<int64_t> d_ranks, d_nans;      // live for this call
+  DevBuf<double> d_out;
+  HIPCHK(d_ranks.alloc(nu));
+  HIPCHK(d_nans.alloc((size_t)frames));
+  HIPCHK(d_out.alloc(nu * (size_t)frames));
+  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
+  std::vector<double> got(nu * (size_t)frames);
+  HIPCHK(hipMemcpyAsync(d_ranks.p, uniq.data(), nu * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  launch_band_select(ctx->stream, n, frames, stride, x, (int)nu, d_ranks.p, d_out.p, d_nans.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(got.data(), d_out.p, got.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(nan_counts, d_nans.p, (size_t)frames * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (int64_t f = 0; f < frames; ++f)
+    for (int32_t k = 0; k < nranks; ++k) values[f * nranks + k] = got[(size_t)f * nu + (size_t)where[k]];
+  return FSI_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -527,17 +597,7 @@ int fsi_band_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* node
   const int64_t nrow = (int64_t)i0.size();
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  // history + filtered series + one frame each of sums, amplitudes and magnitudes, against what the device has free
-  const double need_d = 8.0 * (double)nrow * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN + 2.0) + 8.0 * (double)n + 8.0 * (double)nrow;
-  Room room;
-  FSICHK(device_room(ctx, &room));
-  if (need_d > (double)room.free_b - room.reserve) {
-    char msg[320];
-    snprintf(msg, sizeof msg, "fsi_band_begin: the session needs %.0f bytes (%lld rows x %lld frames, raw and filtered), the device has %zu bytes "
-             "free of which %.0f stay with the context", need_d, (long long)nrow, (long long)capacity, room.free_b, room.reserve);
-    ctx->err = msg;
-    return FSI_ERR_INVALID;
-  }
+  FSICHK(band_refused(ctx, "fsi_band_begin", nrow, capacity));      // against what the device has free (fsi_band_room)
   auto& s = ctx->band[quantity];
   s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
   s.ncomp = (int)(nrow / n);
@@ -565,16 +625,7 @@ int fsi_band_begin_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t
   }
   // the bytes of fsi_band_begin with nrow = 24 n rows and nnode = 4 n DG1 dofs
   const int64_t nnode = 4 * n, nrow = 6 * nnode;
-  const double need_d = 8.0 * (double)nrow * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN + 2.0) + 8.0 * (double)nnode + 8.0 * (double)nrow;
-  Room room;
-  FSICHK(device_room(ctx, &room));
-  if (need_d > (double)room.free_b - room.reserve) {
-    char msg[320];
-    snprintf(msg, sizeof msg, "fsi_band_begin_cells: the session needs %.0f bytes (%lld rows x %lld frames, raw and filtered), the device has %zu bytes "
-             "free of which %.0f stay with the context", need_d, (long long)nrow, (long long)capacity, room.free_b, room.reserve);
-    ctx->err = msg;
-    return FSI_ERR_INVALID;
-  }
+  FSICHK(band_refused(ctx, "fsi_band_begin_cells", nrow, capacity));
   auto& s = ctx->band[quantity];
   s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
   s.ncomp = 6;
@@ -702,12 +753,17 @@ int fsi_band_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, d
     }
     src = s->amp.p;
   }
-  if (what == FSI_BAND_MAGNITUDE || max_out || argmax_out) {
+  const bool to_board = what >= FSI_BAND_AMPLITUDE && s->board_node0 >= 0;      // fsi_band_board_attach
+  if (to_board && frame >= ctx->board.frames) { ctx->err = "fsi_band_fetch: the attached board has " + std::to_string(ctx->board.frames) + " frames"; return FSI_ERR_INVALID; }
+  if (what == FSI_BAND_MAGNITUDE || max_out || argmax_out || to_board) {
     if (what < FSI_BAND_AMPLITUDE) { ctx->err = "fsi_band_fetch: maximum / argmax are those of the amplitude magnitude"; return FSI_ERR_INVALID; }
     if (tensor_quantity(quantity)) launch_tensor_principal(ctx->stream, s->nnode, src, s->mag.p);      // window 0: of the series itself (:229-230)
     else launch_band_magnitude(ctx->stream, s->nnode, s->ncomp, src, s->mag.p);
-    launch_band_argmax(ctx->stream, s->nnode, s->mag.p, s->part_val.p, s->part_idx.p);
+    if (what == FSI_BAND_MAGNITUDE || max_out || argmax_out) launch_band_argmax(ctx->stream, s->nnode, s->mag.p, s->part_val.p, s->part_idx.p);
     HIPCHK(hipGetLastError());
+    if (to_board)
+      HIPCHK(hipMemcpyAsync(ctx->board.data.p + (size_t)frame * (size_t)ctx->board.nodes + (size_t)s->board_node0, s->mag.p,
+                            (size_t)s->nnode * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     if (max_out) HIPCHK(hipMemcpyAsync(max_out, s->part_val.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (argmax_out) HIPCHK(hipMemcpyAsync(argmax_out, s->part_idx.p, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     if (what == FSI_BAND_MAGNITUDE) src = s->mag.p;
@@ -767,6 +823,111 @@ int fsi_band_import(FsiCtx* ctx, int32_t quantity, int64_t count, const double* 
   s->window = -1;
   s->sel_first = 0; s->sel_stride = 1; s->sel_count = -1;      // as fsi_band_sample: a selection covers the frames it was made on
   return FSI_OK;
+}
+
+int fsi_band_room(FsiCtx* ctx, int64_t rows, int64_t capacity, double* need, double* available) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (rows < 1 || capacity < 1 || !need || !available) { ctx->err = "fsi_band_room: needs rows >= 1, capacity >= 1 and both outputs"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  double n = 0.0, a = 0.0;
+  Room room;
+  FSICHK(band_room(ctx, rows, capacity, &n, &a, &room));
+  *need = n;
+  *available = a;
+  return FSI_OK;
+}
+
+int fsi_board_begin(FsiCtx* ctx, int64_t nodes, int64_t frames) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (nodes < 1 || frames < 1) { ctx->err = "fsi_board_begin: needs nodes >= 1 and frames >= 1"; return FSI_ERR_INVALID; }
+  if (nodes >= (1ll << 32)) { ctx->err = "fsi_board_begin: more than 2^32 - 1 nodes"; return FSI_ERR_INVALID; }
+  if (partitioned(ctx, "fsi_board_begin")) return FSI_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  Room room;
+  FSICHK(device_room(ctx, &room));
+  const double need_d = 8.0 * (double)nodes * (double)frames;
+  if (need_d > (double)room.free_b - room.reserve) {
+    char msg[320];
+    snprintf(msg, sizeof msg, "fsi_board_begin: the board needs %.0f bytes (%lld nodes x %lld frames), the device has %zu bytes free of which "
+             "%.0f stay with the context", need_d, (long long)nodes, (long long)frames, room.free_b, room.reserve);
+    ctx->err = msg;
+    return FSI_ERR_INVALID;
+  }
+  for (auto& s : ctx->band) s.board_node0 = -1;      // only now: a refused begin leaves an open board and its sessions as they were
+  auto& b = ctx->board;
+  b.release();
+  HIPCHK(b.data.alloc((size_t)nodes * (size_t)frames));
+  HIPCHK(b.part_val.alloc(BAND_ARGMAX_BLOCKS + 1));
+  HIPCHK(b.part_idx.alloc(BAND_ARGMAX_BLOCKS + 1));
+  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
+  b.nodes = nodes; b.frames = frames; b.open = true;
+  return FSI_OK;
+}
+
+int fsi_board_end(FsiCtx* ctx) {
+  if (!ctx) return FSI_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (auto& s : ctx->band) s.board_node0 = -1;
+  ctx->board.release();
+  return FSI_OK;
+}
+
+int fsi_band_board_attach(FsiCtx* ctx, int32_t quantity, int64_t node0) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_board_attach")) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_board_attach");
+  if (!s) return FSI_ERR_INVALID;
+  if (node0 == -1) { s->board_node0 = -1; return FSI_OK; }
+  if (!ctx->board.open) { ctx->err = "fsi_band_board_attach: no board (fsi_board_begin first)"; return FSI_ERR_INVALID; }
+  if (node0 < 0 || node0 > ctx->board.nodes - s->nnode) {
+    ctx->err = "fsi_band_board_attach: nodes " + std::to_string(node0) + " .. " + std::to_string(node0) + " + " + std::to_string(s->nnode) +
+               " of the session do not lie in the board's " + std::to_string(ctx->board.nodes);
+    return FSI_ERR_INVALID;
+  }
+  s->board_node0 = node0;
+  return FSI_OK;
+}
+
+int fsi_board_table(FsiCtx* ctx, int64_t first, int64_t count, int32_t nranks, const int64_t* ranks, double* values, int64_t* nan_counts,
+                    double* max_out, int64_t* argmax_out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_board_table")) return FSI_ERR_INVALID;
+  auto& b = ctx->board;
+  if (!b.open) { ctx->err = "fsi_board_table: no board (fsi_board_begin first)"; return FSI_ERR_INVALID; }
+  if (first < 0 || count < 1 || first > b.frames - count) {
+    ctx->err = "fsi_board_table: needs first >= 0, count >= 1 and first + count <= the board's " + std::to_string(b.frames) + " frames";
+    return FSI_ERR_INVALID;
+  }
+  if (!values || !nan_counts || !max_out || !argmax_out) { ctx->err = "fsi_board_table: null output"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* x = b.data.p + (size_t)first * (size_t)b.nodes;
+  FSICHK(order_statistics(ctx, "fsi_board_table", b.nodes, count, b.nodes, x, nranks, ranks, values, nan_counts));
+  for (int64_t k = 0; k < count; ++k) {      // the frame's maximum and the first node that has it, as fsi_band_fetch forms them
+    launch_band_argmax(ctx->stream, b.nodes, x + (size_t)k * (size_t)b.nodes, b.part_val.p, b.part_idx.p);
+    HIPCHK(hipMemcpyAsync(max_out + k, b.part_val.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(argmax_out + k, b.part_idx.p, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return FSI_OK;
+}
+
+int fsi_order_statistics(FsiCtx* ctx, int64_t n, const double* values, int32_t nranks, const int64_t* ranks, double* out, int64_t* nan_count) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_order_statistics")) return FSI_ERR_INVALID;
+  if (n < 1 || n >= (1ll << 32) || !values || !out || !nan_count) {
+    ctx->err = "fsi_order_statistics: needs 1 <= n < 2^32 values, an output and a NaN count";
+    return FSI_ERR_INVALID;
+  }
+  FSICHK(ranks_checked(ctx, "fsi_order_statistics", n, nranks, ranks, nullptr, nullptr));      // before anything is allocated
+  HIPCHK(hipSetDevice(ctx->device));
+  DevBuf<double> x;             // live for this call
+  HIPCHK(x.alloc((size_t)n));
+  HIPCHK(hipDeviceSynchronize());                                  // the allocation's own fill is done
+  HIPCHK(hipMemcpyAsync(x.p, values, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  return order_statistics(ctx, "fsi_order_statistics", n, 1, n, x.p, nranks, ranks, out, nan_count);
 }
 
 int fsi_band_end(FsiCtx* ctx, int32_t quantity) {

@@ -15,6 +15,7 @@ Only the structures are handled that DOLFIN's serial writer produces; anything e
 """
 from __future__ import annotations
 
+import os
 import struct
 import time
 from typing import Dict, Optional, Tuple, Union
@@ -339,6 +340,13 @@ def _pad8(n: int) -> int:
     return (n + 7) & ~7
 
 
+def _mtime() -> int:
+    """The modification time an object header carries: now, or SOURCE_DATE_EPOCH where it is set (the reproducible-builds
+    convention) - two writes of the same data then give the same bytes."""
+    epoch = os.environ.get("SOURCE_DATE_EPOCH")
+    return (int(epoch) if epoch else int(time.time())) & 0xFFFFFFFF
+
+
 def _dtype_message(dt) -> bytes:
     if isinstance(dt, tuple) and dt[0] == "string":
         size = dt[1]
@@ -419,7 +427,7 @@ class _Writer:
             _message(0x0003, _dtype_message(dtype), flags=1),
             _message(0x0005, bytes([2, 2, 2, 0])),  # fill value v2: late alloc, write-time ifset, undefined
             _message(0x0008, struct.pack("<BBQQ", 3, 1, daddr, nbytes)),
-            _message(0x0012, struct.pack("<B3xI", 1, int(time.time()) & 0xFFFFFFFF)),
+            _message(0x0012, struct.pack("<B3xI", 1, _mtime())),
         ]
         for k, v in (attrs or {}).items():
             msgs.append(_attribute_message(k, v))
@@ -433,6 +441,7 @@ class _Writer:
         daddr = self._alloc(len(raw)) if raw else UNDEF
         if raw:
             self._put(daddr, raw)
+        ds._daddr = daddr                 # where the raw data lies in the file (H5Series.reserve_group)
         return self._dataset_header(arr.shape, arr.dtype, daddr, len(raw), ds.attrs)
 
     def _write_group(self, g: Group) -> int:
@@ -589,6 +598,38 @@ class H5Series:
         self._write_at(w.origin, bytes(w.buf))
         self._eof = w.origin + len(w.buf)
         self._link(name, hdr)
+
+    def reserve(self, name: str, shape, dtype, attrs: Optional[Dict[str, object]] = None) -> int:
+        """``append`` of an array of this shape and type whose data area is left unwritten (a hole of the file, which reads
+        as zeros); returns the file offset of the data, for ``fill``.  A series of ``reserve`` in frame order and fills in any
+        order is, byte for byte, the file ``append`` makes of the same frames."""
+        if name in self.addr:
+            raise H5Error(f"/{self.series}/{name} exists")
+        dtype = np.dtype(dtype)
+        if dtype.byteorder == ">":
+            dtype = dtype.newbyteorder("<")
+        shape = tuple(int(n) for n in shape)
+        nbytes = int(np.prod(shape, dtype=np.int64)) * dtype.itemsize
+        daddr = _pad8(self._eof)
+        w = _Writer(origin=_pad8(daddr + nbytes))
+        hdr = w._dataset_header(shape, dtype, daddr if nbytes else UNDEF, nbytes, attrs)
+        self._write_at(w.origin, bytes(w.buf))
+        self._eof = w.origin + len(w.buf)
+        self._link(name, hdr)
+        return daddr
+
+    def reserve_group(self, name: str, group: Group, key: str) -> int:
+        """``append_group`` of a group whose dataset ``key`` (a direct child) holds a placeholder of the final shape and type,
+        zeros say; returns the file offset of that dataset's data, for ``fill``."""
+        self.append_group(name, group)
+        return group[key]._daddr
+
+    def fill(self, daddr: int, offset: int, block: np.ndarray) -> None:
+        """The bytes of ``block`` at ``offset`` bytes into the data area that ``reserve`` / ``reserve_group`` returned."""
+        block = np.ascontiguousarray(block)
+        if block.dtype.byteorder == ">":
+            block = block.astype(block.dtype.newbyteorder("<"))
+        self._write_at(int(daddr) + int(offset), block.tobytes())
 
     def append_group(self, name: str, group: Group) -> None:
         """``/<series>/<name>`` as a whole group (datasets and subgroups) - one ``write_checkpoint`` frame, say - appended

@@ -21,6 +21,10 @@ This module holds
   ``T`` and ``save_step``: ``frame_times`` (``saved_times``), ``frame_stride`` (``frame_spacing``), ``frame_start``.  A run
   sets none of them.
 
+* what a band-pass in strips of rows (``hi_pass_strips.py``, for a history larger than the device) needs of this module: the
+  strip a ``HiPassRun`` is opened on, the list of the series it writes (``series_list``), numpy's percentile from two order
+  statistics (``percentiles_from_ranks``), the board of all strips' amplitude magnitudes and the table formed on it.
+
 What a filter stage and a trace cost on a mesh of the benchmark's size has not been measured.
 The reference's ``strain`` / ``stress`` quantities are ``--hi-pass-tensor`` (``hi_pass_tensor.py``), on the sessions of this module.
 """
@@ -264,6 +268,7 @@ class HostBandSession(HostHistory):
     def __init__(self, ncomp: int, capacity: int):
         super().__init__((-1, ncomp), capacity)
         self.ncomp, self.amp, self.view = ncomp, None, slice(None)
+        self.board, self.board_node0 = None, -1
 
     def sample(self, frame: np.ndarray) -> None:
         super().sample(frame)
@@ -308,12 +313,19 @@ class HostBandSession(HostHistory):
     def amplitude(self, window: int) -> None:
         self.amp = self.filtered if window == 0 else windowed_rms_running(self.filtered, window)
 
+    def board_attach(self, node0: int, board=None) -> None:
+        """From now on an 'amplitude' or 'magnitude' fetch of frame k also stores its magnitudes into ``board`` (a
+        ``HostBoard``) at ``[k, node0:node0 + n]``; ``node0`` -1 detaches."""
+        self.board, self.board_node0 = (None, -1) if node0 < 0 else (board, int(node0))
+
     def fetch(self, what: str, frame: int, with_max: bool = False):
         if what == "raw":
             return self.raw[frame]
         if what == "filtered":
             return self.filtered[frame]
         mag = amplitude_magnitude(self.amp[frame])
+        if self.board is not None:
+            self.board.store(frame, self.board_node0, mag)
         out = mag if what == "magnitude" else self.amp[frame]
         return (out, float(mag.max()), int(np.argmax(mag))) if with_max else out
 
@@ -587,6 +599,9 @@ class HiPassWriter:
                 raise ValueError(f"{viz_type}: {k + 1} frames, expected {num_ts}")
         finally:
             series.close()
+        self.write_xdmf(viz_type, num_ts, ncomp, time_between_files, start_t)
+
+    def write_xdmf(self, viz_type: str, num_ts: int, ncomp: int, time_between_files: float, start_t: float) -> None:
         (self.folder / f"{viz_type}.xdmf").write_text(xdmf_text(num_ts, time_between_files, start_t, len(self.topology),
                                                                 len(self.geometry), "Scalar" if ncomp == 1 else "Vector", viz_type))
 
@@ -602,6 +617,93 @@ def amplitude_row(t: float, mag: np.ndarray, mx: float, argmax: int) -> np.ndarr
     row[3] = mx
     row[12] = argmax
     return row
+
+
+def percentile_ranks(n: int) -> np.ndarray:
+    """The 22 zero-based ranks of the order statistics ``np.percentile(., q)`` of n values interpolates between, per q of
+    ``CSV_PERCENTILES`` the lower and the upper neighbour: ``vi = q / 100 * (n - 1)``, ``floor(vi)`` and one more, at most n - 1."""
+    vi = np.true_divide(np.asarray(CSV_PERCENTILES, dtype=np.float64), 100) * (n - 1)
+    lo = np.floor(vi).astype(np.int64)
+    return np.stack([lo, np.minimum(lo + 1, n - 1)], axis=1).reshape(-1)
+
+
+def percentiles_from_ranks(n: int, lo_hi_values) -> np.ndarray:
+    """``[np.percentile(x, q) for q in CSV_PERCENTILES]`` of n values x, bit for bit, from ``np.sort(x)[percentile_ranks(n)]``
+    (shape (..., 22): frames may be stacked in front): numpy's ``method="linear"``, ``a + (b - a) * t`` with ``t = vi - lo``
+    and, where ``t >= 0.5``, ``b - (b - a) * (1 - t)``.  A NaN among the values makes the row NaN, as numpy does when the
+    array holds one (NaNs sort last, so the largest order statistic shows it)."""
+    v = np.asarray(lo_hi_values, dtype=np.float64)
+    v = v.reshape(v.shape[:-1] + (len(CSV_PERCENTILES), 2))
+    vi = np.true_divide(np.asarray(CSV_PERCENTILES, dtype=np.float64), 100) * (n - 1)
+    t = vi - np.floor(vi)
+    a, b = v[..., 0], v[..., 1]
+    diff = b - a
+    out = a + diff * t
+    upper = np.broadcast_to(t >= 0.5, out.shape)
+    out[upper] = (b - diff * (1 - t))[upper]
+    out[np.isnan(v).any(axis=(-1, -2))] = np.nan
+    return out
+
+
+def host_room(rows: int, capacity: int) -> Tuple[int, int]:
+    """(need, available) of a host session, in the numbers of the device's (``HipBackend.hi_pass_room``, fsi_band_room): the
+    history, the filtered series with its guard frames, three work frames and the row lists; the host is not asked what it
+    has - ``--history-memory`` is the limit of a backend without the device sessions."""
+    return 8 * int(rows) * (2 * int(capacity) + 2 * 33 + 4), 1 << 62
+
+
+class HostBoard:
+    """``board[frame][node]`` of amplitude magnitudes on the host: the twin of the device's board (``DeviceBoard``), filled by
+    the fetches of attached ``HostBandSession``s."""
+
+    def __init__(self, nodes: int, frames: int):
+        self.a = np.full((int(frames), int(nodes)), np.nan)
+
+    def attach(self, session, node0: int) -> None:
+        session.board_attach(node0, self)
+
+    def store(self, frame: int, node0: int, mag: np.ndarray) -> None:
+        self.a[frame, node0:node0 + len(mag)] = mag
+
+    def table(self, first: int, count: int, ranks):
+        """(order statistics (count, len(ranks)), NaN counts, maxima, first nodes of the maxima) of ``count`` frames."""
+        ranks = np.asarray(ranks, dtype=np.int64)
+        x = self.a[first:first + count]
+        values = np.stack([np.partition(row, np.unique(ranks))[ranks] for row in x])
+        return values, np.isnan(x).sum(axis=1), x.max(axis=1), x.argmax(axis=1)
+
+    def end(self) -> None:
+        self.a = None
+
+
+class DeviceBoard:
+    """The board of the device (``HipBackend.hi_pass_board_*``, fsi_board_*) behind ``HostBoard``'s method names."""
+
+    def __init__(self, backend, nodes: int, frames: int):
+        self.backend = backend
+        backend.hi_pass_board_begin(nodes, frames)
+
+    def attach(self, session, node0: int) -> None:
+        session.board_attach(node0)
+
+    def table(self, first: int, count: int, ranks):
+        return self.backend.hi_pass_board_table(first, count, ranks)
+
+    def end(self) -> None:
+        self.backend.hi_pass_board_end()
+
+
+def board_table(board, n: int, nodes: int, dt_files: float, t0: float) -> np.ndarray:
+    """The 13-column amplitude table of n board frames: ``amplitude_row`` of every frame, its percentiles interpolated from
+    the board's order statistics (``percentiles_from_ranks``), its maximum and the node of it from the board."""
+    values, nans, mx, am = board.table(0, n, percentile_ranks(nodes))
+    table = np.empty((n, 13))
+    table[:, 0] = np.arange(n) * dt_files + t0
+    table[:, 1:12] = percentiles_from_ranks(nodes, values)
+    table[np.asarray(nans) > 0, 1:12] = np.nan
+    table[:, 3] = mx
+    table[:, 12] = am
+    return table
 
 
 # ------------------------------------------------------------------------------------------------
@@ -794,6 +896,11 @@ class HiPassRun(SessionRun):
             bad = [i for i in self.point_ids if i >= n]
             if bad:
                 raise SystemExit(f"--hi-pass-point-ids: {bad} out of range, {VIZ_TYPE[q]} is written on {n} nodes")
+        # a strip (vasp_amd.hi_pass_strips): the session is opened on nodes i0 .. i1 - 1 of the one quantity asked for
+        self.strip = ns.get("hi_pass_strip")
+        if self.strip is not None:
+            i0, i1 = self.strip
+            self.nodes = {q: tuple(None if a is None else a[i0:i1] for a in ab) for q, ab in self.nodes.items()}
         self.writer = HiPassWriter(Path(ns["results_folder"]) / "Visualization_hi_pass", geometry, topology)
         self.trace_folder = Path(ns["results_folder"]) / "Visualization_separate_domain"      # [REF create_hi_pass_viz.py:565,639]
         self.open_sessions(backend, ns, lambda q: self.nodes[q],
@@ -806,6 +913,10 @@ class HiPassRun(SessionRun):
         return dict(save_deg=self.save_deg, dt_sample=self.dt_sample, rows=self.rows(q), nodes=sha256_of(*self.nodes[q]))
 
     def _host_frame(self, q: str, state: np.ndarray) -> np.ndarray:
+        frame = self._whole_host_frame(q, state)
+        return frame if self.strip is None else frame[self.strip[0]:self.strip[1]]
+
+    def _whole_host_frame(self, q: str, state: np.ndarray) -> np.ndarray:
         d, v, p = self.mesh.split(state)
         V = self.mesh.num_vertices
         if q == "p":
@@ -837,16 +948,50 @@ class HiPassRun(SessionRun):
         self.writer.write_series(f"{viz}_amplitude", amp_frames(), n, ncomp, self.dt_files, self.t0)
         self.writer.write_table(viz, table)
 
-    def _write_traces(self, session, q: str, n: int) -> None:
+    def _write_traces(self, session, q: str, n: int, ids=None, local=None) -> None:
         """``<viz_type>_point_id_<id>.csv``: time, magnitude and components of the recorded rows of each listed node
-        [REF postprocessing_h5py_common.py:470-483], the times being T0 + k * time_between_files, one per frame."""
+        [REF postprocessing_h5py_common.py:470-483], the times being T0 + k * time_between_files, one per frame.  ``ids``
+        with ``local``: the ids among ``point_ids`` that a strip holds, and their indices into the strip's nodes."""
+        ids, local = (self.point_ids, self.point_ids) if ids is None else (ids, local)
         self.trace_folder.mkdir(parents=True, exist_ok=True)
-        trace = np.asarray(session.trace("raw", self.point_ids))
-        for i, rows in zip(self.point_ids, trace):
+        trace = np.asarray(session.trace("raw", local))
+        for i, rows in zip(ids, trace):
             data = np.empty((n, rows.shape[1] + 1 if q != "p" else 2))
             data[:, 0] = self.t0 + np.arange(n) * self.dt_files
             data[:, 1:] = rows if q != "p" else rows[:, :1]
             np.savetxt(self.trace_folder / f"{VIZ_TYPE[q]}_point_id_{i}.csv", data, delimiter=",", header=TRACE_HEADER[1 if q == "p" else 3])
+
+    def series_list(self, q: str, n: int, out) -> List[Tuple[str, List[dict], bool]]:
+        """(viz, stages, rms) of every series ``q`` is written as on n frames, in the order they are written: per band its
+        one filter, then with --hi-pass-multiband the chain of all bands.  ``stages``: the designs ``apply`` runs in order;
+        ``rms``: the amplitude is the windowed RMS (False - the reference's low-pass case: the series itself).  A series the
+        frames do not suffice for is named through ``out`` and left out."""
+        series = []
+        for lo, hi in self.bands:
+            prm = design(self.dt_files, lo, hi)
+            viz = f"{VIZ_TYPE[q]}_{prm['name']}"
+            if n <= prm["padlen"]:
+                out(f"Hi-pass {viz}: {n} frames recorded, the filter needs more than {prm['padlen']}: nothing written")
+                continue
+            series.append((viz, [prm], prm["btype"] != "lowpass"))
+        if not self.pass_stop:
+            return series
+        # the recorded rows through all bands in order [REF create_hi_pass_viz.py:191-198].  Its amplitude is the windowed
+        # RMS, as a band-pass's: the reference itself raises NameError here (filter_type_single is undefined, :222)
+        viz = multiband_name(VIZ_TYPE[q], self.bands, self.pass_stop)
+        stages = [design(self.dt_files, lo, hi, "bandpass" if word == "pass" else "bandstop")
+                  for (lo, hi), word in zip(self.bands, self.pass_stop)]
+        if n <= max(prm["padlen"] for prm in stages):
+            out(f"Hi-pass {viz}: {n} frames recorded, the filter needs more than {max(prm['padlen'] for prm in stages)}: nothing written")
+            return series
+        series.append((viz, stages, True))
+        return series
+
+    @staticmethod
+    def apply(session, stages) -> None:
+        """The session's filtered series after ``stages``: the first on the selected frames, every further one on the series."""
+        for k, prm in enumerate(stages):
+            (session.filter_next if k else session.filter)(prm["b"], prm["a"], prm["zi"], prm["padlen"])
 
     def write(self, out) -> None:
         first, n = select_frames(self.times, self.dt, self.stride, self.t0, self.t1)
@@ -858,25 +1003,7 @@ class HiPassRun(SessionRun):
             session.select(first, n, self.stride)
             if self.point_ids:
                 self._write_traces(session, q, n)
-            for lo, hi in self.bands:
-                prm = design(self.dt_files, lo, hi)
-                viz = f"{VIZ_TYPE[q]}_{prm['name']}"
-                if n <= prm["padlen"]:
-                    out(f"Hi-pass {viz}: {n} frames recorded, the filter needs more than {prm['padlen']}: nothing written")
-                    continue
-                session.filter(prm["b"], prm["a"], prm["zi"], prm["padlen"])
-                self._write_filtered(out, session, viz, n, ncomp, prm["btype"] != "lowpass")
-            if not self.pass_stop:
-                continue
-            # the recorded rows through all bands in order [REF create_hi_pass_viz.py:191-198].  Its amplitude is the windowed
-            # RMS, as a band-pass's: the reference itself raises NameError here (filter_type_single is undefined, :222)
-            viz = multiband_name(VIZ_TYPE[q], self.bands, self.pass_stop)
-            stages = [design(self.dt_files, lo, hi, "bandpass" if word == "pass" else "bandstop")
-                      for (lo, hi), word in zip(self.bands, self.pass_stop)]
-            if n <= max(prm["padlen"] for prm in stages):
-                out(f"Hi-pass {viz}: {n} frames recorded, the filter needs more than {max(prm['padlen'] for prm in stages)}: nothing written")
-                continue
-            for k, prm in enumerate(stages):
-                (session.filter_next if k else session.filter)(prm["b"], prm["a"], prm["zi"], prm["padlen"])
-            self._write_filtered(out, session, viz, n, ncomp, True)
+            for viz, stages, rms in self.series_list(q, n, out):
+                self.apply(session, stages)
+                self._write_filtered(out, session, viz, n, ncomp, rms)
         out(f"Hi-pass fields of {n} frames ({', '.join(self.quantities)}) written to {self.writer.folder}")

@@ -154,6 +154,21 @@ class TensorSeries:
         self._h5.append_group(f"{self.viz}_{self.frames}", g)
         self.frames += 1
 
+    def reserve(self) -> int:
+        """``append`` of a frame whose values come later, a block of cells at a time (``fill``); returns what ``fill`` takes."""
+        n = len(self.w.topology)
+        g = _dg1_group(np.zeros((1, 4, 3, 3) if self.ncomp == 9 else (1, 4)), self.w.geometry, self.w.topology, dofmap=self.frames == 0,
+                       celltype="tetrahedron")
+        g["vector"] = Dataset(np.zeros((n * 4 * self.ncomp, 1), dtype=np.float32))
+        addr = self._h5.reserve_group(f"{self.viz}_{self.frames}", g, "vector")
+        self.frames += 1
+        return addr
+
+    def fill(self, addr: int, cell0: int, values) -> None:
+        """The values of cells ``cell0 ...`` (cells x 4 x ncomp, as ``append`` takes them) into a reserved frame."""
+        block = np.asarray(values, dtype=np.float64).reshape(-1, 1).astype(np.float32)
+        self._h5.fill(addr, 4 * (4 * self.ncomp * int(cell0)), block)
+
     def close(self, time_between_files: float, start_t: float) -> None:
         self._h5.close()
         n, nv = len(self.w.topology), len(self.w.geometry)
@@ -184,6 +199,10 @@ class HiPassTensorRun(SessionRun):
         if len(self.cells) == 0:
             raise SystemExit(f"--hi-pass-tensor: no cell carries a solid marker (dx_s_id = {ns['dx_s_id']})")
         self.writer = TensorWriter(Path(ns["results_folder"]) / "Visualization_hi_pass", *solid_submesh(mesh, self.cells))
+        # a strip (vasp_amd.hi_pass_strips): the session is opened on solid cells i0 .. i1 - 1; the writer keeps the whole sub-mesh
+        self.strip = ns.get("hi_pass_tensor_strip")
+        if self.strip is not None:
+            self.cells = self.cells[self.strip[0]:self.strip[1]]
         self.open_sessions(backend, ns, lambda q: (self.cells,), self._no_host_session)
 
     @staticmethod
@@ -220,18 +239,30 @@ class HiPassTensorRun(SessionRun):
             principal.close(self.dt_files, self.t0)
         self.writer.write_table(viz, table)
 
+    def series_list(self, q: str, n: int, out):
+        """(viz, stages, rms) per band, as ``HiPassRun.series_list``: one series per band, no multiband chain."""
+        series = []
+        for lo, hi in self.bands:
+            prm = design(self.dt_files, lo, hi)
+            viz = f"{VIZ_TYPE[q]}_{prm['name']}"
+            if n <= prm["padlen"]:
+                out(f"Hi-pass {viz}: {n} frames recorded, the filter needs more than {prm['padlen']}: nothing written")
+                continue
+            series.append((viz, [prm], prm["btype"] != "lowpass"))
+        return series
+
+    @staticmethod
+    def apply(session, stages) -> None:
+        for prm in stages:
+            session.filter(prm["b"], prm["a"], prm["zi"], prm["padlen"])
+
     def write(self, out) -> None:
         n = self.frames
         if n == 0:
             out("Hi-pass tensors: no frame was recorded, nothing written")
             return
         for q, session in self.sessions.items():
-            for lo, hi in self.bands:
-                prm = design(self.dt_files, lo, hi)
-                viz = f"{VIZ_TYPE[q]}_{prm['name']}"
-                if n <= prm["padlen"]:
-                    out(f"Hi-pass {viz}: {n} frames recorded, the filter needs more than {prm['padlen']}: nothing written")
-                    continue
-                session.filter(prm["b"], prm["a"], prm["zi"], prm["padlen"])
-                self._write_band(out, session, viz, n, prm["btype"] != "lowpass")
+            for viz, stages, rms in self.series_list(q, n, out):
+                self.apply(session, stages)
+                self._write_band(out, session, viz, n, rms)
         out(f"Hi-pass tensors of {n} frames ({', '.join(self.quantities)}) written to {self.writer.folder}")

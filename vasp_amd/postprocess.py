@@ -21,8 +21,15 @@ sample the state while it steps.  Nothing is solved here and no problem file is 
 At ``save_deg 2`` the files hold the whole state in FP64 and the outputs are those of the run, bit for bit.  At ``save_deg 1``
 they hold the vertex values: a mid-edge node takes the mean of its edge's vertices, the P1 field the reference's tools see.
 
-Not done: more than one rank, histories larger than device memory (the refusal of the begin calls applies), reading
-``Checkpoint/sessions/*.f64`` instead of the frames, PNG figures.
+Band-pass histories larger than the device (``--hi-pass``, ``--hi-pass-tensor``): where the histories of all asked quantities
+do not fit into ``--history-memory`` bytes (default: what ``fsi_band_room`` reports as available), each quantity goes through
+its session in strips of rows, one quantity at a time (``hi_pass_strips``): the frames are read once per strip - with
+``--hi-pass-amplitude`` once per strip and series -, the files are those of the unsplit path byte for byte, and the amplitude
+table is formed on the device from a board of the magnitudes.  Where they fit, nothing differs from a call without the option.
+
+Not done: more than one rank, a spectrogram history larger than device memory (the refusal of ``fsi_spec_begin`` applies),
+strips during a run, reading ``Checkpoint/sessions/*.f64`` instead of the frames, overlapping the reads with the device
+work, PNG figures.
 """
 from __future__ import annotations
 
@@ -37,6 +44,7 @@ from typing import Callable, Dict, List, Optional
 
 import numpy as np
 
+from . import hi_pass
 from .fem import FormTerms
 from .frames import FrameSource, selected_indices
 from .mesh import FsiMesh
@@ -62,6 +70,9 @@ def parse(argv: Optional[List[str]] = None) -> Dict[str, object]:
     ap.add_argument("--stride", dest="stride", type=int, default=None, help="read every S-th saved frame (default: 1)")
     ap.add_argument("--new-arguments", dest="new_arguments", nargs="*", default=[])
     add_session_arguments(ap)
+    ap.add_argument("--history-memory", dest="history_memory", type=int, default=None, metavar="BYTES",
+                    help="device memory the band-pass histories of --hi-pass / --hi-pass-tensor may take (default: what the device "
+                         "has free beside the context); quantities that do not fit go through their session in strips of rows")
     ap.add_argument("-c", "--config", dest="config", default=None, help="config file with `key = value` lines, as vasp_amd.monolithic's")
     return resolve_arguments(ap, argv)
 
@@ -169,10 +180,22 @@ def prepare(argv: Optional[List[str]] = None, backend_factory: Callable = defaul
         why = _session_part(module, refusal)(v, world, cls) if v.get(key) else ""
         if why:
             raise SystemExit(why)
+    if v.get("history_memory") is not None and (isinstance(v["history_memory"], bool) or not isinstance(v["history_memory"], (int, np.integer))
+                                                or v["history_memory"] < 1):
+        raise SystemExit(f"--history-memory must be a number of bytes >= 1, got {v['history_memory']!r}")
     if not indices:
         span = f"its {len(source)} frames run from t = {source.times[0]!r} to {source.times[-1]!r}" if len(source) else "it lists no frame"
         raise SystemExit(f"no saved frame of {source.folder} lies in the window and stride asked for (--stride {stride}, --start-time {t0:g}, "
                          f"--end-time {t1}): {span}")
+    if v.get("history_memory") is not None:      # a limit no strip fits into: refused here, in the bytes of hi_pass.host_room, fsi_band_room's twin
+        from . import hi_pass_strips as strips
+        need = lambda rows, capacity: hi_pass.host_room(rows, capacity)[0]
+        band_jobs, amplitude, limit = strips.jobs(mesh, v), bool(v.get("hi_pass_amplitude")), int(v["history_memory"])
+        if not strips.everything_fits(band_jobs, len(indices) + 1, amplitude, limit, need):
+            for j in band_jobs:
+                if j.units:
+                    strips.plan_strips(j.units, j.rows_per_unit, len(indices) + 1, j.board_bytes(amplitude), limit, need,
+                                       "node" if j.kind == "field" else "cell")
     build_properties(v)
     ns: Dict[str, object] = dict(v)
     output = Path(str(v.get("output_folder") or results))
@@ -194,13 +217,26 @@ def run(argv: Optional[List[str]] = None, backend_factory: Callable = default_ba
     backend = backend_factory(desc)
     ns["backend"] = backend
     Path(ns["results_folder"]).mkdir(parents=True, exist_ok=True)
+    # band-pass histories that do not fit the device (or --history-memory) go through their sessions in strips, after the others
+    from . import hi_pass_strips as strips
+    need = (lambda rows, capacity: backend.hi_pass_room(rows, capacity)[0]) if hasattr(backend, "hi_pass_room") else \
+        (lambda rows, capacity: hi_pass.host_room(rows, capacity)[0])
+    band_jobs = strips.jobs(mesh, ns) if indices else []
+    in_strips, limit = set(), None
+    if band_jobs:
+        limit = ns.get("history_memory")
+        if limit is None:
+            limit = (backend.hi_pass_room if hasattr(backend, "hi_pass_room") else hi_pass.host_room)(1, 1)[1]
+        if not strips.everything_fits(band_jobs, len(indices) + 1, bool(ns.get("hi_pass_amplitude")), int(limit), need):
+            in_strips = {"hi_pass", "hi_pass_tensor"}
     sessions = []
     for key, module, _, run_cls, needs in SESSIONS:
         if not ns.get(key):
             continue
         if needs and not hasattr(backend, needs):
             raise SystemExit(f"--{key.replace('_', '-')} needs a backend with {needs} ({type(backend).__name__} has none)")
-        sessions.append(_session_part(module, run_cls)(backend, mesh, ns))
+        if key not in in_strips:
+            sessions.append(_session_part(module, run_cls)(backend, mesh, ns))
     device = hasattr(backend, "set_frame")
     host_state = {}
 
@@ -211,9 +247,12 @@ def run(argv: Optional[List[str]] = None, backend_factory: Callable = default_ba
 
     seconds = dict(read=0.0, set_frame=0.0, sample=0.0)
     tick = _time.perf_counter
-    t_read = tick()
-    try:
-        for t, views in source.frames(indices, fields):
+
+    def sample_frames(read, samplers):
+        """The selected frames, the fields ``read`` of each put into the state and handed to every one of ``samplers``."""
+        nonlocal host_state
+        t_read = tick()
+        for t, views in source.frames(indices, read):
             t_set = tick()
             host_state = dict(views=views)
             if device:
@@ -221,7 +260,7 @@ def run(argv: Optional[List[str]] = None, backend_factory: Callable = default_ba
             elif hasattr(backend, "set_state"):
                 backend.set_state("n", state())
             t_sample = tick()
-            for session in sessions:
+            for session in samplers:
                 session.sample(t, state)
             t_next = tick()
             seconds["read"] += t_set - t_read
@@ -229,15 +268,24 @@ def run(argv: Optional[List[str]] = None, backend_factory: Callable = default_ba
             seconds["sample"] += t_next - t_sample
             t_read = t_next
         host_state = {}
+
+    passes = 0
+    try:
+        if sessions or not in_strips:
+            sample_frames(fields if not in_strips else fields_read({**ns, **{k: None for k in in_strips}}), sessions)
+            passes += 1
+        for session in sessions:
+            session.finish(out)
+        for job in (band_jobs if in_strips else []):
+            passes += strips.run_quantity(job, backend, mesh, ns, int(limit), need, sample_frames, out)["passes"]
     finally:
         source.close()
-    for session in sessions:
-        session.finish(out)
+    ns["strips"] = bool(in_strips)
     if indices:
-        n = len(indices)
+        n = len(indices) * max(passes, 1)
         out("Read %d of %d frames; per frame %.2f ms finding it in the mapped files, %.2f ms reading it into the state (page faults, "
             "host-to-device copy, state kernel), %.2f ms sampling"
-            % (n, len(source), *(1e3 * seconds[k] / n for k in ("read", "set_frame", "sample"))))
+            % (len(indices), len(source), *(1e3 * seconds[k] / n for k in ("read", "set_frame", "sample"))))
     ns["frame_seconds"], ns["frames_read"] = seconds, len(indices)
     return ns
 
