@@ -542,6 +542,25 @@ int fsi_band_end(FsiCtx* ctx, int32_t quantity);
  * refused call leaves it as it was, its bytes counted as taken.  Not for partitioned contexts. */
 int fsi_spec_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* nodes, const int32_t* nodes_b, int32_t ncomp_mode,
                    int64_t capacity);
+/* Replaces: the selection of a range of rows of the sampled matrix, df.iloc[r0:r1] [REF .../spectrograms.py:291-329], for a
+ * history that goes through the session in strips of rows: a session on nrows listed ROWS instead of nodes.  Row r is
+ * component comps[r] (0 = x, 1 = y, 2 = z) of nodes[r], or its mean with that of nodes_b[r] where nodes_b is given and
+ * nodes_b[r] >= 0; for the pressure comps is ignored and may be null.  With FSI_SPEC_ALL the rows of fsi_spec_begin are
+ * component-major (row = c * n + i), so a range of them can cross a component boundary: this call takes any such range.  A
+ * strip of magnitudes is a sub-list of nodes and keeps fsi_spec_begin.  Recording, filtering, fetch, export, import and the
+ * transforms work as for any session.  Checks, the device-room refusal (fsi_spec_room) and the treatment of an open session
+ * as in fsi_spec_begin; FSI_ERR_INVALID also for a component outside 0 .. 2 and for null comps with d or v.  Not for
+ * partitioned contexts. */
+int fsi_spec_begin_rows(FsiCtx* ctx, int32_t quantity, int64_t nrows, const int32_t* nodes, const int32_t* nodes_b,
+                        const int32_t* comps, int64_t capacity);
+/* Replaces: the sizing a user of read_spectrogram_data does by hand before the row x time matrix is read into host memory
+ * [REF .../spectrograms.py:291-329]: the two byte counts fsi_spec_begin and fsi_spec_begin_rows compare for a session of
+ * `rows` rows (`magnitude` != 0: rows of FSI_SPEC_MAG, which sample three entries each) and `capacity` frames.  *need: the raw
+ * and the filtered history (capacity and capacity + 66 frames), the row lists, 64 bins of a periodogram's tables over capacity
+ * frames and the means of capacity / 4 segments, about 8 * rows * (2.25 * capacity + 68) bytes; *available: the free device
+ * memory less the 1/16 of the device that stays with the context.  A begin call is refused exactly when need > available.
+ * Nothing is allocated. */
+int fsi_spec_room(FsiCtx* ctx, int64_t rows, int32_t magnitude, int64_t capacity, double* need, double* available);
 /* Replaces: reading one frame of <quantity>.h5 [REF .../postprocessing_h5py_common.py:154-409, its frame loop]: the session's rows
  * of dvp_["n"] (or their magnitude) go to the next frame of the history, stream-ordered; the host does not wait.
  * FSI_ERR_INVALID when the history is full. */
@@ -569,6 +588,24 @@ int fsi_spec_spectrogram(FsiCtx* ctx, int32_t quantity, int64_t nperseg, int64_t
  * [REF .../spectrograms.py:409-419]: out_power[frames / 2 + 1], the spectrogram of one segment of all recorded frames with nfft =
  * frames (any length, odd included), window[frames]. */
 int fsi_spec_periodogram(FsiCtx* ctx, int32_t quantity, const double* window, int32_t scaling, double fs, double* out_power);
+/* Replaces: the running total `Pxx_matrix + Pxx` of get_spectrogram's row loop and its division by the row count after the
+ * loop [REF .../spectrograms.py:448-463], for a list of total rows that goes through the session in strips: this session holds
+ * rows first_row .. first_row + rows - 1 of it.  Arguments as fsi_spec_spectrogram, then: carry[(nfft / 2 + 1)][nseg], the
+ * layout of out_power, holds the sum over the row blocks (128 rows each) of the rows before first_row; with first_row == 0
+ * its content is ignored and the sum starts from +0.0.  On return it holds that sum with this session's row blocks added, in
+ * index order - the additions fsi_spec_spectrogram makes on all rows, so the bits are those of the unsplit call.  total_rows
+ * == 0: more strips follow; total_rows > 0: this is the last strip and carry returns the mean over total_rows rows.
+ * FSI_ERR_INVALID with one line in fsi_last_error, nothing allocated and carry untouched: first_row < 0 or not a multiple of
+ * 128; total_rows == 0 and the session's row count not a multiple of 128 (a later strip's blocks would be cut differently);
+ * total_rows != 0 and total_rows != first_row + rows; a null carry; and every refusal of fsi_spec_spectrogram, the room check
+ * of the transform included.  No atomics. */
+int fsi_spec_spectrogram_sum(FsiCtx* ctx, int32_t quantity, int64_t nperseg, int64_t noverlap, int64_t nfft, const double* window,
+                             int32_t scaling, double fs, int64_t first_row, int64_t total_rows, double* carry);
+/* Replaces: the running total `Pxx_matrix += Pxx` of get_psd's row loop and its division by the row count
+ * [REF .../spectrograms.py:409-417], in strips of rows: fsi_spec_periodogram with the carry of fsi_spec_spectrogram_sum,
+ * carry[frames / 2 + 1]; the same checks and refusals. */
+int fsi_spec_periodogram_sum(FsiCtx* ctx, int32_t quantity, const double* window, int32_t scaling, double fs, int64_t first_row,
+                             int64_t total_rows, double* carry);
 /* Replaces: reading rows back from <quantity>_<component>.npz [REF .../spectrograms.py:291-329], for a checkpoint:
  * out[count][rows], frames first .. first + count - 1 of the raw history in one copy.  The rows are what was recorded: with
  * FSI_SPEC_MAG the magnitudes.  Checks and refusals as fsi_band_export. */

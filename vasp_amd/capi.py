@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_set_frame", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_begin_rows", "fsi_spec_room", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_spectrogram_sum", "fsi_spec_periodogram_sum", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -180,11 +180,15 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_board_table.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp, vp]
     lib.fsi_order_statistics.argtypes = [vp, i64, vp, i32, vp, vp, C.POINTER(i64)]
     lib.fsi_spec_begin.argtypes = [vp, i32, i64, vp, vp, i32, i64]
+    lib.fsi_spec_begin_rows.argtypes = [vp, i32, i64, vp, vp, vp, i64]
+    lib.fsi_spec_room.argtypes = [vp, i64, i32, i64, C.POINTER(dbl), C.POINTER(dbl)]
     lib.fsi_spec_sample.argtypes = [vp, i32]
     lib.fsi_spec_filter.argtypes = [vp, i32, i32, vp, vp, vp, i32]
     lib.fsi_spec_fetch.argtypes = [vp, i32, i32, i64, vp]
     lib.fsi_spec_spectrogram.argtypes = [vp, i32, i64, i64, i64, vp, i32, dbl, vp]
     lib.fsi_spec_periodogram.argtypes = [vp, i32, vp, i32, dbl, vp]
+    lib.fsi_spec_spectrogram_sum.argtypes = [vp, i32, i64, i64, i64, vp, i32, dbl, i64, i64, vp]
+    lib.fsi_spec_periodogram_sum.argtypes = [vp, i32, vp, i32, dbl, i64, i64, vp]
     lib.fsi_spec_export.argtypes = [vp, i32, i64, i64, vp]
     lib.fsi_spec_import.argtypes = [vp, i32, i64, vp]
     lib.fsi_spec_end.argtypes = [vp, i32]
@@ -756,6 +760,28 @@ class HipBackend:
                                             self.SPEC_MODE[component], int(capacity)))
         self._spec_shape[quantity] = [len(a) * (3 if component == "all" and quantity != "p" else 1), 0]
 
+    def spec_begin_rows(self, quantity: str, nodes, nodes_b=None, comps=None, capacity: int = 1) -> None:
+        """Open the spectrogram session of ``quantity`` on listed rows (fsi_spec_begin_rows): row r is component ``comps[r]``
+        (0 .. 2) of ``nodes[r]``, or its mean with ``nodes_b[r]`` where that is >= 0; the pressure takes no ``comps``.  Any
+        range of the component-major rows of ``spec_begin(..., "all")`` can be opened so - a strip of a history that does
+        not fit the device.  Raises FsiError when the history does not fit."""
+        a = np.ascontiguousarray(nodes, dtype=np.int32)
+        b = None if nodes_b is None else np.ascontiguousarray(nodes_b, dtype=np.int32)
+        c = None if comps is None else np.ascontiguousarray(comps, dtype=np.int32)
+        if any(x is not None and x.shape != a.shape for x in (b, c)):
+            raise ValueError("nodes_b and comps must have the shape of nodes")
+        self._check(self.lib.fsi_spec_begin_rows(self.ctx, self.BAND_QUANTITY[quantity], len(a), _ptr(a), None if b is None else _ptr(b),
+                                                 None if c is None else _ptr(c), int(capacity)))
+        self._spec_shape[quantity] = [len(a), 0]
+
+    def spec_room(self, rows: int, capacity: int, magnitude: bool = False):
+        """(need, available) in bytes: what a spectrogram session of ``rows`` rows (``magnitude``: of component 'mag') and
+        ``capacity`` frames takes and what the device has for it - the two numbers ``spec_begin`` / ``spec_begin_rows``
+        compare (fsi_spec_room)."""
+        need, avail = C.c_double(0.0), C.c_double(0.0)
+        self._check(self.lib.fsi_spec_room(self.ctx, int(rows), int(bool(magnitude)), int(capacity), C.byref(need), C.byref(avail)))
+        return int(need.value), int(avail.value)
+
     def spec_sample(self, quantity: str) -> None:
         """Record the session's rows of dvp_["n"] as the next frame of its history (fsi_spec_sample)."""
         self._check(self.lib.fsi_spec_sample(self.ctx, self.BAND_QUANTITY[quantity]))
@@ -807,6 +833,47 @@ class HipBackend:
         out = np.empty(frames // 2 + 1)
         self._check(self.lib.fsi_spec_periodogram(self.ctx, self.BAND_QUANTITY[quantity], _ptr(w), self.SPEC_SCALING[scaling], float(fs), _ptr(out)))
         return out
+
+    @staticmethod
+    def _spec_carry(carry, shape, first_row: int):
+        """The carry of a ``_sum`` call as the library takes it: a new one for the first strip, else the caller's own array
+        (it is updated in place); none with ``first_row`` > 0 goes to the library as NULL, for its refusal."""
+        if carry is None:
+            return np.zeros(shape) if int(first_row) == 0 else None
+        if not (isinstance(carry, np.ndarray) and carry.dtype == np.float64 and carry.flags.c_contiguous and carry.shape == shape):
+            raise ValueError(f"the carry must be a C-contiguous float64 array of shape {shape}")
+        return carry
+
+    def spec_spectrogram_sum(self, quantity: str, nperseg: int, noverlap: int, nfft: int, window, scaling: str, fs: float,
+                             first_row: int, total_rows: int = 0, carry=None) -> np.ndarray:
+        """``spec_spectrogram`` of a session that holds rows ``first_row ...`` of a longer list (fsi_spec_spectrogram_sum):
+        ``carry``, (nfft // 2 + 1, segments), the sum over the row blocks before ``first_row`` (None with ``first_row`` 0), is
+        updated in place and returned; with ``total_rows`` > 0 - the last strip - it returns the mean over that many rows,
+        the bits of ``spec_spectrogram`` on all rows."""
+        w = np.ascontiguousarray(window, dtype=np.float64)
+        if w.shape != (int(nperseg),):
+            raise ValueError("the window must have nperseg entries")
+        frames = self._spec_open(quantity)[1]
+        if not 0 <= noverlap < nperseg <= max(frames, 1):
+            raise ValueError("needs 0 <= noverlap < nperseg <= recorded frames")
+        nseg = (frames - int(noverlap)) // (int(nperseg) - int(noverlap))
+        carry = self._spec_carry(carry, (int(nfft) // 2 + 1, max(nseg, 0)), first_row)
+        self._check(self.lib.fsi_spec_spectrogram_sum(self.ctx, self.BAND_QUANTITY[quantity], int(nperseg), int(noverlap), int(nfft), _ptr(w),
+                                                      self.SPEC_SCALING[scaling], float(fs), int(first_row), int(total_rows),
+                                                      None if carry is None else _ptr(carry)))
+        return carry
+
+    def spec_periodogram_sum(self, quantity: str, window, scaling: str, fs: float, first_row: int, total_rows: int = 0,
+                             carry=None) -> np.ndarray:
+        """``spec_periodogram`` with the carry of ``spec_spectrogram_sum``, (frames // 2 + 1,) (fsi_spec_periodogram_sum)."""
+        w = np.ascontiguousarray(window, dtype=np.float64)
+        frames = self._spec_open(quantity)[1]
+        if w.shape != (frames,):
+            raise ValueError("the window must have one entry per recorded frame")
+        carry = self._spec_carry(carry, (frames // 2 + 1,), first_row)
+        self._check(self.lib.fsi_spec_periodogram_sum(self.ctx, self.BAND_QUANTITY[quantity], _ptr(w), self.SPEC_SCALING[scaling], float(fs),
+                                                      int(first_row), int(total_rows), None if carry is None else _ptr(carry)))
+        return carry
 
     def spec_export(self, quantity: str, first: int, count: int) -> np.ndarray:
         """Raw frames ``first .. first + count - 1`` of the history as (count, rows), in one copy (fsi_spec_export)."""

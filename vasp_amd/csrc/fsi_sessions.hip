@@ -39,9 +39,10 @@ int64_t band_frames(const FsiCtx::Band* s) { return s->sel_count < 0 ? s->frames
 // The argument checks of a begin call and the solver indices of the entries it samples at n listed nodes: i0 / i1, i1 < 0
 // where an entry is one node's value and not the mean of two.  *mode (FSI_SPEC_*): one component of every node or, from
 // FSI_SPEC_ALL on, the three; the pressure has one and makes *mode FSI_SPEC_X.  Entry (node i, component c of nc) sits at
-// i * nc + c (node_major, the band-pass rows) or at c * n + i (the spectrogram's).
+// i * nc + c (node_major, the band-pass rows) or at c * n + i (the spectrogram's).  With comps (fsi_spec_begin_rows; *mode
+// FSI_SPEC_X) entry i is component comps[i] of nodes[i]: a list of rows, not of nodes.
 int row_lists(FsiCtx* ctx, const char* fn, int32_t quantity, int64_t n, const int32_t* nodes, const int32_t* nodes_b, int64_t capacity,
-              int* mode, bool node_major, std::vector<int32_t>& i0, std::vector<int32_t>& i1) {
+              int* mode, bool node_major, std::vector<int32_t>& i0, std::vector<int32_t>& i1, const int32_t* comps = nullptr) {
   auto refuse = [&](const char* why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
   if (quantity < 0 || quantity > 2) return refuse("quantity must be 0 (d), 1 (v) or 2 (p)");
   if (n <= 0 || !nodes || capacity <= 0) return refuse("needs n > 0 nodes and a capacity > 0 frames");
@@ -57,8 +58,9 @@ int row_lists(FsiCtx* ctx, const char* fn, int32_t quantity, int64_t n, const in
   for (int64_t i = 0; i < n; ++i) {
     const int32_t a = nodes[i], b = nodes_b ? nodes_b[i] : -1;
     if (a < 0 || a >= limit || b >= limit) return refuse("node out of range");
+    if (comps && !scalar && (comps[i] < 0 || comps[i] > 2)) return refuse("component out of range, needs 0 (x), 1 (y) or 2 (z)");
     for (int c = 0; c < nc; ++c) {
-      const int comp = nc == 3 ? c : *mode;
+      const int comp = nc == 3 ? c : comps && !scalar ? comps[i] : *mode;
       const int64_t e = node_major ? i * nc + c : c * n + i;
       i0[e] = ctx->h_user2solver[off + (int64_t)ncomp * a + comp];
       if (b >= 0) i1[e] = ctx->h_user2solver[off + (int64_t)ncomp * b + comp];
@@ -236,10 +238,46 @@ int end_session(FsiCtx* ctx, S (&all)[N], int32_t q, const char* fn) {
   return FSI_OK;
 }
 
+// The refusal rule of the spectrogram begin calls, once: the raw and the filtered history and the sampled vector of the
+// magnitude (nsamp entries, two lists), as band_room; with them what the transforms allocate at the end of the run, so that a
+// history that fits here is not refused there: one pass of SPEC_BINS bins of a periodogram's tables over all frames, and the
+// means of capacity / 4 segments.
+int spec_room(FsiCtx* ctx, int64_t nrow, int64_t nsamp, int64_t capacity, double* need, double* available, Room* room) {
+  FSICHK(device_room(ctx, room));
+  *need = 8.0 * (double)nrow * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN) + 16.0 * (double)nsamp +
+          16.0 * SPEC_BINS * (double)capacity + 8.0 * (double)nrow * ((double)capacity / 4.0 + 2.0);
+  *available = (double)room->free_b - room->reserve;
+  return FSI_OK;
+}
+
+// What fsi_spec_begin and fsi_spec_begin_rows do once their row lists stand: the room check, then the session.
+int spec_open(FsiCtx* ctx, const char* fn, int32_t quantity, int64_t n, int64_t nrow, int mode, int64_t capacity,
+              const std::vector<int32_t>& i0, const std::vector<int32_t>& i1) {
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  double need_d = 0.0, avail = 0.0;
+  Room room;
+  FSICHK(spec_room(ctx, nrow, (int64_t)i0.size(), capacity, &need_d, &avail, &room));
+  if (need_d > avail) {
+    char msg[420];
+    snprintf(msg, sizeof msg, "%s: the session needs %.0f bytes (%lld rows x %lld frames, raw and filtered, and the transforms' tables), the device has %zu bytes "
+             "free of which %.0f stay with the context", fn, need_d, (long long)nrow, (long long)capacity, room.free_b, room.reserve);
+    ctx->err = msg;
+    return FSI_ERR_INVALID;
+  }
+  auto& s = ctx->spec[quantity];
+  s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
+  s.mode = mode;
+  return history_open(ctx, s, n, nrow, capacity, i0, i1, mode == FSI_SPEC_MAG);
+}
+
 // The average over the session's rows of the one-sided power of nseg segments of K frames, `step` frames apart, transformed
 // at length nfft >= K: mean, then per slab of bins the host's tables, k_spec_power and k_spec_reduce.  out[(nfft / 2 + 1)][nseg].
+// carried (fsi_spec_*_sum): the session holds rows first_row ... of a longer list, out is the caller's carry - the sum over the
+// row blocks before first_row on entry (read only where first_row > 0), with this session's blocks added on return, divided by
+// total_rows where that is > 0.  A refused or failed call leaves out untouched either way.
 int spec_power(FsiCtx* ctx, FsiCtx::Spec* s, const char* fn, int64_t K, int64_t step, int64_t nseg, int64_t nfft, const double* window,
-               int32_t scaling, double fs, double* out) {
+               int32_t scaling, double fs, double* out, bool carried = false, int64_t first_row = 0, int64_t total_rows = 0) {
   const int64_t nbins = nfft / 2 + 1, nblk = spec_blocks(s->nrow);
   double sw = 0.0, sw2 = 0.0;
   for (int64_t j = 0; j < K; ++j) { sw += window[j]; sw2 += window[j] * window[j]; }
@@ -306,7 +344,8 @@ int spec_power(FsiCtx* ctx, FsiCtx::Spec* s, const char* fn, int64_t K, int64_t 
     cosm[m] = (double)cosl(ang);
     sinm[m] = (double)sinl(ang);
   }
-  if (chk(hipMemcpyAsync(w.p, window, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "window upload")) {
+  if (carried && first_row > 0) chk(hipMemcpyAsync(res.p, out, (size_t)(nbins * nseg) * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "carry upload");
+  if (rc == FSI_OK && chk(hipMemcpyAsync(w.p, window, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "window upload")) {
     launch_spec_mean(ctx->stream, s->nrow, K, step, nseg, x, mean.p);
     chk(hipGetLastError(), "k_spec_mean");
   }
@@ -321,7 +360,8 @@ int spec_power(FsiCtx* ctx, FsiCtx::Spec* s, const char* fn, int64_t K, int64_t 
     if (!chk(hipMemcpyAsync(Ct.p, hc.data(), (size_t)(K * nb) * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "table upload")) break;
     if (!chk(hipMemcpyAsync(St.p, hs.data(), (size_t)(K * nb) * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "table upload")) break;
     launch_spec_power(ctx->stream, s->nrow, K, step, nseg, nb, bin0, nfft % 2 == 0 ? nfft / 2 : -1, scale, x, mean.p, w.p, Ct.p, St.p, part.p);
-    launch_spec_reduce(ctx->stream, s->nrow, nseg, nb, bin0, part.p, res.p);
+    if (carried) launch_spec_reduce_sum(ctx->stream, s->nrow, nseg, nb, bin0, first_row, total_rows, part.p, res.p);
+    else launch_spec_reduce(ctx->stream, s->nrow, nseg, nb, bin0, part.p, res.p);
     if (!chk(hipGetLastError(), "k_spec_power")) break;
     if (!chk(hipStreamSynchronize(ctx->stream), "k_spec_power")) break;      // the host tables are refilled for the next slab
   }
@@ -329,6 +369,51 @@ int spec_power(FsiCtx* ctx, FsiCtx::Spec* s, const char* fn, int64_t K, int64_t 
     chk(hipStreamSynchronize(ctx->stream), "result");
   if (rc != FSI_OK) ctx->err = std::string(fn) + ": " + why;
   return rc;
+}
+
+// The checks of fsi_spec_spectrogram(_sum) and fsi_spec_periodogram(_sum) (periodogram: nperseg, noverlap and nfft are not
+// read) and the transform.  carried: out_power is the carry of a _sum call (spec_power), whose own checks come first.
+int spec_transform(FsiCtx* ctx, const char* name, bool periodogram, int32_t quantity, int64_t nperseg, int64_t noverlap, int64_t nfft, const double* window,
+                   int32_t scaling, double fs, double* out_power, bool carried, int64_t first_row, int64_t total_rows) {
+  if (!ctx) return FSI_ERR_INVALID;
+  const std::string fn(name);
+  auto* s = spec_session(ctx, quantity, name);
+  if (!s) return FSI_ERR_INVALID;
+  if (!window || !out_power || (scaling != FSI_SPEC_SPECTRUM && scaling != FSI_SPEC_DENSITY) || !(fs > 0.0)) {
+    ctx->err = fn + ": needs a window, " + (carried ? "a carry" : "an output") + ", scaling FSI_SPEC_SPECTRUM or FSI_SPEC_DENSITY and fs > 0";
+    return FSI_ERR_INVALID;
+  }
+  if (carried) {
+    if (first_row < 0 || first_row % SPEC_ROWS != 0) {
+      ctx->err = fn + ": first_row = " + std::to_string(first_row) + ", a strip starts at a multiple of " + std::to_string(SPEC_ROWS) + " rows (the row blocks of the sum)";
+      return FSI_ERR_INVALID;
+    }
+    if (total_rows == 0 && s->nrow % SPEC_ROWS != 0) {
+      ctx->err = fn + ": the session has " + std::to_string(s->nrow) + " rows and is not the last strip (total_rows = 0): a later strip's row blocks would be cut "
+                 "differently, needs a multiple of " + std::to_string(SPEC_ROWS);
+      return FSI_ERR_INVALID;
+    }
+    if (total_rows != 0 && total_rows != first_row + s->nrow) {
+      ctx->err = fn + ": total_rows = " + std::to_string(total_rows) + ", the last strip ends at first_row + rows = " + std::to_string(first_row) + " + " +
+                 std::to_string(s->nrow);
+      return FSI_ERR_INVALID;
+    }
+  }
+  if (periodogram) {
+    if (s->frames < 1) { ctx->err = fn + ": no recorded frames"; return FSI_ERR_INVALID; }
+    return spec_power(ctx, s, name, s->frames, s->frames, 1, s->frames, window, scaling, fs, out_power, carried, first_row, total_rows);
+  }
+  if (nperseg < 1 || noverlap < 0 || noverlap >= nperseg || nfft < nperseg) {
+    ctx->err = fn + ": needs nperseg >= 1, 0 <= noverlap < nperseg and nfft >= nperseg";
+    return FSI_ERR_INVALID;
+  }
+  if (s->frames < nperseg) {
+    ctx->err = fn + ": " + std::to_string(s->frames) + " recorded frames, one segment needs nperseg = " + std::to_string(nperseg);
+    return FSI_ERR_INVALID;
+  }
+  const int64_t step = nperseg - noverlap, nseg = (s->frames - noverlap) / step;
+  if (nseg > 65535) { ctx->err = fn + ": more than 65535 segments"; return FSI_ERR_INVALID; }
+  return spec_power(ctx, s, name, nperseg, step, nseg, nfft, window, scaling, fs, out_power, carried, first_row, total_rows);
 }
 
 // The ranks of a selection call: 0 <= rank < n each, at most BAND_SEL_MAX_RANKS distinct ones.  uniq: those, ascending;
@@ -940,27 +1025,29 @@ int fsi_spec_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* node
   int mode = ncomp_mode;
   std::vector<int32_t> i0, i1;
   FSICHK(row_lists(ctx, "fsi_spec_begin", quantity, n, nodes, nodes_b, capacity, &mode, false, i0, i1));
-  const int64_t nsamp = (int64_t)i0.size(), nrow = mode == FSI_SPEC_MAG ? n : nsamp;
+  return spec_open(ctx, "fsi_spec_begin", quantity, n, mode == FSI_SPEC_MAG ? n : (int64_t)i0.size(), mode, capacity, i0, i1);
+}
+
+int fsi_spec_begin_rows(FsiCtx* ctx, int32_t quantity, int64_t nrows, const int32_t* nodes, const int32_t* nodes_b, const int32_t* comps,
+                        int64_t capacity) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (quantity >= 0 && quantity < 2 && !comps) { ctx->err = "fsi_spec_begin_rows: needs the component of every row of d or v"; return FSI_ERR_INVALID; }
+  int mode = FSI_SPEC_X;        // one entry per row: comps[r] of nodes[r]
+  std::vector<int32_t> i0, i1;
+  FSICHK(row_lists(ctx, "fsi_spec_begin_rows", quantity, nrows, nodes, nodes_b, capacity, &mode, false, i0, i1, comps));
+  return spec_open(ctx, "fsi_spec_begin_rows", quantity, nrows, nrows, mode, capacity, i0, i1);
+}
+
+int fsi_spec_room(FsiCtx* ctx, int64_t rows, int32_t magnitude, int64_t capacity, double* need, double* available) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (rows < 1 || capacity < 1 || !need || !available) { ctx->err = "fsi_spec_room: needs rows >= 1, capacity >= 1 and both outputs"; return FSI_ERR_INVALID; }
   HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  // raw and filtered history and the sampled vector of the magnitude, against what the device has free, as fsi_band_begin;
-  // with them what the transforms allocate at the end of the run, so that a history that fits here is not refused there:
-  // one pass of SPEC_BINS bins of a periodogram's tables over all frames, and the means of capacity / 4 segments
-  const double need_d = 8.0 * (double)nrow * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN) + 16.0 * (double)nsamp +
-                        16.0 * SPEC_BINS * (double)capacity + 8.0 * (double)nrow * ((double)capacity / 4.0 + 2.0);
+  double n = 0.0, a = 0.0;
   Room room;
-  FSICHK(device_room(ctx, &room));
-  if (need_d > (double)room.free_b - room.reserve) {
-    char msg[420];
-    snprintf(msg, sizeof msg, "fsi_spec_begin: the session needs %.0f bytes (%lld rows x %lld frames, raw and filtered, and the transforms' tables), the device has %zu bytes "
-             "free of which %.0f stay with the context", need_d, (long long)nrow, (long long)capacity, room.free_b, room.reserve);
-    ctx->err = msg;
-    return FSI_ERR_INVALID;
-  }
-  auto& s = ctx->spec[quantity];
-  s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
-  s.mode = mode;
-  return history_open(ctx, s, n, nrow, capacity, i0, i1, mode == FSI_SPEC_MAG);
+  FSICHK(spec_room(ctx, rows, magnitude ? 3 * rows : rows, capacity, &n, &a, &room));
+  *need = n;
+  *available = a;
+  return FSI_OK;
 }
 
 int fsi_spec_sample(FsiCtx* ctx, int32_t quantity) {
@@ -993,36 +1080,21 @@ int fsi_spec_fetch(FsiCtx* ctx, int32_t quantity, int32_t filtered, int64_t fram
 
 int fsi_spec_spectrogram(FsiCtx* ctx, int32_t quantity, int64_t nperseg, int64_t noverlap, int64_t nfft, const double* window,
                          int32_t scaling, double fs, double* out_power) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = spec_session(ctx, quantity, "fsi_spec_spectrogram");
-  if (!s) return FSI_ERR_INVALID;
-  if (!window || !out_power || (scaling != FSI_SPEC_SPECTRUM && scaling != FSI_SPEC_DENSITY) || !(fs > 0.0)) {
-    ctx->err = "fsi_spec_spectrogram: needs a window, an output, scaling FSI_SPEC_SPECTRUM or FSI_SPEC_DENSITY and fs > 0";
-    return FSI_ERR_INVALID;
-  }
-  if (nperseg < 1 || noverlap < 0 || noverlap >= nperseg || nfft < nperseg) {
-    ctx->err = "fsi_spec_spectrogram: needs nperseg >= 1, 0 <= noverlap < nperseg and nfft >= nperseg";
-    return FSI_ERR_INVALID;
-  }
-  if (s->frames < nperseg) {
-    ctx->err = "fsi_spec_spectrogram: " + std::to_string(s->frames) + " recorded frames, one segment needs nperseg = " + std::to_string(nperseg);
-    return FSI_ERR_INVALID;
-  }
-  const int64_t step = nperseg - noverlap, nseg = (s->frames - noverlap) / step;
-  if (nseg > 65535) { ctx->err = "fsi_spec_spectrogram: more than 65535 segments"; return FSI_ERR_INVALID; }
-  return spec_power(ctx, s, "fsi_spec_spectrogram", nperseg, step, nseg, nfft, window, scaling, fs, out_power);
+  return spec_transform(ctx, "fsi_spec_spectrogram", false, quantity, nperseg, noverlap, nfft, window, scaling, fs, out_power, false, 0, 0);
 }
 
 int fsi_spec_periodogram(FsiCtx* ctx, int32_t quantity, const double* window, int32_t scaling, double fs, double* out_power) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = spec_session(ctx, quantity, "fsi_spec_periodogram");
-  if (!s) return FSI_ERR_INVALID;
-  if (!window || !out_power || (scaling != FSI_SPEC_SPECTRUM && scaling != FSI_SPEC_DENSITY) || !(fs > 0.0)) {
-    ctx->err = "fsi_spec_periodogram: needs a window, an output, scaling FSI_SPEC_SPECTRUM or FSI_SPEC_DENSITY and fs > 0";
-    return FSI_ERR_INVALID;
-  }
-  if (s->frames < 1) { ctx->err = "fsi_spec_periodogram: no recorded frames"; return FSI_ERR_INVALID; }
-  return spec_power(ctx, s, "fsi_spec_periodogram", s->frames, s->frames, 1, s->frames, window, scaling, fs, out_power);
+  return spec_transform(ctx, "fsi_spec_periodogram", true, quantity, 0, 0, 0, window, scaling, fs, out_power, false, 0, 0);
+}
+
+int fsi_spec_spectrogram_sum(FsiCtx* ctx, int32_t quantity, int64_t nperseg, int64_t noverlap, int64_t nfft, const double* window,
+                             int32_t scaling, double fs, int64_t first_row, int64_t total_rows, double* carry) {
+  return spec_transform(ctx, "fsi_spec_spectrogram_sum", false, quantity, nperseg, noverlap, nfft, window, scaling, fs, carry, true, first_row, total_rows);
+}
+
+int fsi_spec_periodogram_sum(FsiCtx* ctx, int32_t quantity, const double* window, int32_t scaling, double fs, int64_t first_row,
+                             int64_t total_rows, double* carry) {
+  return spec_transform(ctx, "fsi_spec_periodogram_sum", true, quantity, 0, 0, 0, window, scaling, fs, carry, true, first_row, total_rows);
 }
 
 int fsi_spec_export(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count, double* out) {

@@ -21,7 +21,9 @@
 //                      SPEC_ROWS rows: 8 + 8 accumulator tiles.  The power (Re^2 + Im^2) scale of a row is added over the
 //                      wave's rows in a fixed order (tile by tile in a lane, then a four-step butterfly over the 16 lanes of
 //                      a bin) and written as the workgroup's partial sum - one slot per (segment, row block, bin).
-//   k_spec_reduce    : adds the row blocks' partial sums in index order and divides by the number of rows.
+//   k_spec_reduce    : adds the row blocks' partial sums in index order and divides by the number of rows; its carried
+//                      variant starts from the sum of the row blocks before the session's first row and hands the sum on
+//                      (fsi_spec_spectrogram_sum / fsi_spec_periodogram_sum: a history in strips of rows).
 //
 // No floating-point atomics anywhere: the same call gives the same bits.  A periodogram is one segment of all n frames
 // with nfft = n; the C-ABI hands the tables over in slabs of bins (nb, bin0) so that a long run's table never has to fit.
@@ -116,13 +118,25 @@ __global__ __launch_bounds__(256) void k_spec_power(int64_t nrow, int64_t K, int
   }
 }
 
-__global__ __launch_bounds__(256) void k_spec_reduce(int64_t nrow, int64_t nblk, int64_t nseg, int64_t nb, int64_t bin0,
-                                                     const double* __restrict__ part, double* __restrict__ out) {
+// CARRY = false: out = the mean over the nrow rows of this session.  CARRY = true (a session that holds rows first_row ... of
+// total_rows, fsi_spec_*_sum): the sum starts from what out holds of the row blocks before first_row - from +0.0 with
+// first_row == 0, as above -, goes on over this session's blocks and is written back; told the total (total_rows > 0, the
+// last strip) the mean over that many rows is written over it.  One body: the additions are those of one call on all rows.
+template <bool CARRY>
+__global__ __launch_bounds__(256) void k_spec_reduce(int64_t nrow, int64_t nblk, int64_t nseg, int64_t nb, int64_t bin0, int64_t first_row,
+                                                     int64_t total_rows, const double* __restrict__ part, double* __restrict__ out) {
   const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, seg = blockIdx.y;
   if (b >= nb) return;
+  const int64_t o = (bin0 + b) * nseg + seg;
   double s = 0.0;
+  if (CARRY && first_row > 0) s = out[o];
   for (int64_t k = 0; k < nblk; ++k) s += part[(seg * nblk + k) * nb + b];
-  out[(bin0 + b) * nseg + seg] = s / (double)nrow;
+  if (CARRY) {
+    out[o] = s;
+    if (total_rows > 0) out[o] = s / (double)total_rows;
+  } else {
+    out[o] = s / (double)nrow;
+  }
 }
 
 }  // namespace
@@ -146,8 +160,15 @@ void launch_spec_power(hipStream_t st, int64_t nrow, int64_t K, int64_t step, in
 
 void launch_spec_reduce(hipStream_t st, int64_t nrow, int64_t nseg, int64_t nb, int64_t bin0, const double* part, double* out) {
   if (nrow > 0 && nseg > 0 && nb > 0)
-    hipLaunchKernelGGL(k_spec_reduce, dim3((unsigned)((nb + 255) / 256), (unsigned)nseg), dim3(256), 0, st, nrow, spec_blocks(nrow),
-                       nseg, nb, bin0, part, out);
+    hipLaunchKernelGGL(k_spec_reduce<false>, dim3((unsigned)((nb + 255) / 256), (unsigned)nseg), dim3(256), 0, st, nrow, spec_blocks(nrow),
+                       nseg, nb, bin0, (int64_t)0, (int64_t)0, part, out);
+}
+
+void launch_spec_reduce_sum(hipStream_t st, int64_t nrow, int64_t nseg, int64_t nb, int64_t bin0, int64_t first_row, int64_t total_rows,
+                            const double* part, double* carry) {
+  if (nrow > 0 && nseg > 0 && nb > 0)
+    hipLaunchKernelGGL(k_spec_reduce<true>, dim3((unsigned)((nb + 255) / 256), (unsigned)nseg), dim3(256), 0, st, nrow, spec_blocks(nrow),
+                       nseg, nb, bin0, first_row, total_rows, part, carry);
 }
 
 }  // namespace fsi

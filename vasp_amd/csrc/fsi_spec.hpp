@@ -24,6 +24,11 @@ void launch_spec_power(hipStream_t st, int64_t nrow, int64_t K, int64_t step, in
                        const double* Ct, const double* St, double* part);
 // out[(bin0 + b) * nseg + seg] = (part[seg][0][b] + part[seg][1][b] + ...) / nrow, the blocks added in index order
 void launch_spec_reduce(hipStream_t st, int64_t nrow, int64_t nseg, int64_t nb, int64_t bin0, const double* part, double* out);
+// The same additions for a session that holds rows first_row .. first_row + nrow - 1 of a longer list (first_row a multiple of
+// SPEC_ROWS): s = first_row > 0 ? carry[(bin0 + b) * nseg + seg] : +0.0, s += part[seg][0][b], part[seg][1][b], ...;
+// carry[...] = s, or s / total_rows where total_rows > 0 (the last strip).  No atomics: one thread per (bin, segment).
+void launch_spec_reduce_sum(hipStream_t st, int64_t nrow, int64_t nseg, int64_t nb, int64_t bin0, int64_t first_row, int64_t total_rows,
+                            const double* part, double* carry);
 
 inline int64_t spec_blocks(int64_t nrow) { return (nrow + SPEC_ROWS - 1) / SPEC_ROWS; }
 

@@ -27,8 +27,13 @@ its session in strips of rows, one quantity at a time (``hi_pass_strips``): the 
 ``--hi-pass-amplitude`` once per strip and series -, the files are those of the unsplit path byte for byte, and the amplitude
 table is formed on the device from a board of the magnitudes.  Where they fit, nothing differs from a call without the option.
 
-Not done: more than one rank, a spectrogram history larger than device memory (the refusal of ``fsi_spec_begin`` applies),
-strips during a run, reading ``Checkpoint/sessions/*.f64`` instead of the frames, overlapping the reads with the device
+Spectrogram histories larger than the device (``--spectrogram``): the same limit bounds them.  Where the sessions of all
+asked spectrogram quantities do not fit beside the band-pass sessions of the first frame loop, every spectrogram quantity
+goes through its session in strips of rows after that loop, one at a time (``spectrogram_strips``): the three mean powers
+are sums over blocks of rows in a fixed order, carried from strip to strip, so the four CSV files are those of the unsplit
+path byte for byte; the frames are read once per strip.
+
+Not done: more than one rank, strips during a run, reading ``Checkpoint/sessions/*.f64`` instead of the frames, overlapping the reads with the device
 work, PNG figures.
 """
 from __future__ import annotations
@@ -71,8 +76,8 @@ def parse(argv: Optional[List[str]] = None) -> Dict[str, object]:
     ap.add_argument("--new-arguments", dest="new_arguments", nargs="*", default=[])
     add_session_arguments(ap)
     ap.add_argument("--history-memory", dest="history_memory", type=int, default=None, metavar="BYTES",
-                    help="device memory the band-pass histories of --hi-pass / --hi-pass-tensor may take (default: what the device "
-                         "has free beside the context); quantities that do not fit go through their session in strips of rows")
+                    help="device memory the histories of --hi-pass / --hi-pass-tensor / --spectrogram may take (default: what the "
+                         "device has free beside the context); quantities that do not fit go through their session in strips of rows")
     ap.add_argument("-c", "--config", dest="config", default=None, help="config file with `key = value` lines, as vasp_amd.monolithic's")
     return resolve_arguments(ap, argv)
 
@@ -196,6 +201,13 @@ def prepare(argv: Optional[List[str]] = None, backend_factory: Callable = defaul
                 if j.units:
                     strips.plan_strips(j.units, j.rows_per_unit, len(indices) + 1, j.board_bytes(amplitude), limit, need,
                                        "node" if j.kind == "field" else "cell")
+        if v.get("spectrogram"):                  # the same for a spectrogram strip, in the bytes of spectrogram.host_room, fsi_spec_room's twin
+            from . import spectrogram as sg, spectrogram_strips as spec_strips
+            plan = sg.SpectrogramRun(None, mesh, {**v, "results_folder": results}, open_sessions=False)
+            for q in plan.quantities:
+                magnitude = spec_strips.is_magnitude(plan, q)
+                spec_strips.plan_row_strips(plan.rows(q), spec_strips.granule_of(cls), len(indices) + 1, limit,
+                                            lambda rows, capacity: sg.host_room(rows, capacity, magnitude)[0])
     build_properties(v)
     ns: Dict[str, object] = dict(v)
     output = Path(str(v.get("output_folder") or results))
@@ -229,6 +241,21 @@ def run(argv: Optional[List[str]] = None, backend_factory: Callable = default_ba
             limit = (backend.hi_pass_room if hasattr(backend, "hi_pass_room") else hi_pass.host_room)(1, 1)[1]
         if not strips.everything_fits(band_jobs, len(indices) + 1, bool(ns.get("hi_pass_amplitude")), int(limit), need):
             in_strips = {"hi_pass", "hi_pass_tensor"}
+    # the same for the spectrogram histories: where they do not fit beside the band-pass sessions of the first frame loop
+    spec_run = None
+    if ns.get("spectrogram") and indices:
+        from . import spectrogram as sg, spectrogram_strips as spec_strips
+        if limit is None:
+            limit = ns.get("history_memory")
+        if limit is None:
+            limit = (backend.spec_room if hasattr(backend, "spec_room") else sg.host_room)(1, 1)[1]
+        plan = sg.SpectrogramRun(backend, mesh, ns, open_sessions=False)
+        beside = 0 if in_strips or not band_jobs else \
+            sum(need(j.units * j.rows_per_unit, len(indices) + 1) + j.board_bytes(bool(ns.get("hi_pass_amplitude"))) for j in band_jobs if j.units)
+        if spec_strips.total_need(plan, len(indices) + 1) + beside > int(limit):
+            spec_run = plan
+            in_strips = in_strips | {"spectrogram"}
+    band_strips = bool(in_strips & {"hi_pass", "hi_pass_tensor"})
     sessions = []
     for key, module, _, run_cls, needs in SESSIONS:
         if not ns.get(key):
@@ -276,8 +303,10 @@ def run(argv: Optional[List[str]] = None, backend_factory: Callable = default_ba
             passes += 1
         for session in sessions:
             session.finish(out)
-        for job in (band_jobs if in_strips else []):
+        for job in (band_jobs if band_strips else []):
             passes += strips.run_quantity(job, backend, mesh, ns, int(limit), need, sample_frames, out)["passes"]
+        for q in (spec_run.quantities if spec_run is not None else []):
+            passes += spec_strips.run_quantity(q, spec_run, int(limit), sample_frames, out)["passes"]
     finally:
         source.close()
     ns["strips"] = bool(in_strips)

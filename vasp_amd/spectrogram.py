@@ -24,16 +24,20 @@ Times: the frames are ``dt * save_step`` apart; ``T = frames * dt * save_step``,
 ``--stride`` and a time window are those of ``vasp_amd.postprocess`` on a finished folder: the spacing, ``T`` and ``start_t`` then
 come from the frames that were read.
 
+A history larger than the device: on a finished folder the rows go through the session in strips
+(``vasp_amd.spectrogram_strips``); the three mean powers are sums over blocks of rows in a fixed order, so the sum is carried
+from strip to strip (``spectrogram_sum`` / ``periodogram_sum``) and the files are those of one session on all rows.
+
 Not done: ``domain`` sampling, the ``wss`` quantity, the PNG figures, ``sonify_point``.
 """
 from __future__ import annotations
 
 from pathlib import Path
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .hi_pass import HostHistory, SessionRun, frame_spacing, frame_start, frame_times, output_nodes, restart_refusal, sha256_of
+from .hi_pass import DeviceSession, HostHistory, SessionRun, expected_frames, frame_spacing, frame_start, frame_times, output_nodes, restart_refusal, sha256_of
 from .mesh import FsiMesh
 
 HP_ORDER = 6                                    # filter_time_data(order=6, btype="highpass") [REF spectrograms.py:558]
@@ -43,6 +47,7 @@ MIN_COLOR = {"d": -42, "v": -20, "p": -5}       # [REF spectrograms.py:133-147]
 COMPONENTS = ("all", "x", "y", "z", "mag")
 SAMPLINGS = ("RandomPoint", "PointList", "All")
 ROWS = 128                                      # csrc/fsi_spec.hpp: SPEC_ROWS
+HOST_CHUNK = 32 * ROWS                          # columns of one C @ Y product of the host session (mean_power)
 PI_L = np.longdouble("3.14159265358979323846264338327950288")
 
 
@@ -225,11 +230,14 @@ def block_sums(P: np.ndarray) -> np.ndarray:
     return lane[:, :, 0]
 
 
-def mean_power(x: np.ndarray, K: int, step: int, nseg: int, nfft: int, window: np.ndarray, scaling: str, fs: float,
-               max_table_bytes: int = 1 << 27) -> np.ndarray:
-    """(nfft // 2 + 1, nseg): the average over the rows of x (frames, rows) of the one-sided power of nseg segments of K
-    frames, ``step`` apart - fsi_spec.hip operation for operation except the order inside a dot product (BLAS here, the
-    matrix pipe's there)."""
+def sum_power(x: np.ndarray, K: int, step: int, nseg: int, nfft: int, window: np.ndarray, scaling: str, fs: float,
+              carry: Optional[np.ndarray] = None, total_rows: int = 0, max_table_bytes: int = 1 << 27,
+              chunk: int = HOST_CHUNK) -> np.ndarray:
+    """(nfft // 2 + 1, nseg): ``carry`` (None: zeros) plus the sums, over the blocks of ROWS rows of x (frames, rows) in index
+    order, of the one-sided power of nseg segments of K frames, ``step`` apart - fsi_spec.hip operation for operation except
+    the order inside a dot product (BLAS here, the matrix pipe's there); divided by ``total_rows`` where that is > 0.  The
+    rows go through ``C @ Y`` in chunks of ``chunk`` columns: rows handed over in strips that start at multiples of it form
+    the same products and, the carry handed on, the same sum."""
     x = np.asarray(x, dtype=np.float64)
     rows = x.shape[1]
     w = np.asarray(window, dtype=np.float64)
@@ -242,7 +250,6 @@ def mean_power(x: np.ndarray, K: int, step: int, nseg: int, nfft: int, window: n
     last_single = nfft // 2 if nfft % 2 == 0 else -1
     out = np.empty((nbins, nseg))
     slab = max(1, min(nbins, max_table_bytes // (16 * K)))
-    chunk = 32 * ROWS
     for seg in range(nseg):
         xs = x[seg * step:seg * step + K]
         acc = np.zeros(rows)
@@ -254,25 +261,47 @@ def mean_power(x: np.ndarray, K: int, step: int, nseg: int, nfft: int, window: n
             C, S = spec_tables(K, nfft, bin0, nb)
             parts = []
             for r0 in range(0, rows, chunk):
-                re, im = C @ Y[:, r0:r0 + chunk], S @ Y[:, r0:r0 + chunk]
+                Yc = np.ascontiguousarray(Y[:, r0:r0 + chunk])      # the same operand whatever rows lie beside the chunk
+                re, im = C @ Yc, S @ Yc
                 parts.append(block_sums((re * re + im * im) * scale))
             part = np.concatenate(parts, axis=1)
             g = np.arange(bin0, bin0 + nb)
             part = np.where(((g == 0) | (g == last_single))[:, None], part, 2.0 * part)
-            tot = np.zeros(nb)
+            tot = np.zeros(nb) if carry is None else np.array(carry[bin0:bin0 + nb, seg], dtype=np.float64)
             for k in range(part.shape[1]):
                 tot = tot + part[:, k]
-            out[bin0:bin0 + nb, seg] = tot / float(rows)
+            out[bin0:bin0 + nb, seg] = tot / float(total_rows) if total_rows > 0 else tot
     return out
 
 
-class HostSpecSession(HostHistory):
-    """The session of one quantity on the host, method for method ``HipBackend.spec_*`` without the quantity argument."""
-    what = "spectrogram"
+def mean_power(x: np.ndarray, K: int, step: int, nseg: int, nfft: int, window: np.ndarray, scaling: str, fs: float,
+               max_table_bytes: int = 1 << 27, chunk: int = HOST_CHUNK) -> np.ndarray:
+    """(nfft // 2 + 1, nseg): the average over the rows of x (frames, rows) of the one-sided power: ``sum_power`` of one strip
+    that holds every row."""
+    return sum_power(x, K, step, nseg, nfft, window, scaling, fs, None, np.asarray(x).shape[1], max_table_bytes, chunk)
 
-    def __init__(self, nrows: int, capacity: int):
+
+def host_room(rows: int, capacity: int, magnitude: bool = False) -> Tuple[int, int]:
+    """(need, available) of a host session, in the numbers of the device's (``HipBackend.spec_room``, fsi_spec_room): the raw
+    and the filtered history with its guard frames, the row lists (three entries per row of magnitudes), 64 bins of a
+    periodogram's tables and the means of capacity / 4 segments; the host is not asked what it has - ``--history-memory`` is
+    the limit of a backend without the device sessions."""
+    rows, capacity = int(rows), int(capacity)
+    return (8 * rows * (2 * capacity + 2 * 33) + 16 * (3 * rows if magnitude else rows) + 16 * 64 * capacity
+            + 2 * rows * capacity + 16 * rows), 1 << 62
+
+
+class HostSpecSession(HostHistory):
+    """The session of one quantity on the host, method for method ``HipBackend.spec_*`` without the quantity argument.
+    ``granule``: the rows a strip of a longer row list must start at a multiple of for the carried sums to be those of one
+    session on all rows - the column chunk of ``sum_power``."""
+    what = "spectrogram"
+    granule = HOST_CHUNK
+
+    def __init__(self, nrows: int, capacity: int, chunk: int = HOST_CHUNK):
         super().__init__(int(nrows), capacity)
         self.nrows = int(nrows)
+        self.granule = int(chunk)
 
     def fetch(self, frame: int, filtered: bool = False) -> np.ndarray:
         return self.filtered[frame] if filtered else self.raw[frame]
@@ -280,14 +309,59 @@ class HostSpecSession(HostHistory):
     def _source(self) -> np.ndarray:
         return self.filtered if self.filtered is not None else np.stack(self.raw)
 
-    def spectrogram(self, nperseg: int, noverlap: int, nfft: int, window, scaling: str, fs: float) -> np.ndarray:
+    def _carried(self, name: str, shape, first_row: int, total_rows: int, carry):
+        """The refusals of fsi_spec_*_sum in the host's granule; the carry a sum starts from (None: zeros)."""
+        g = self.granule
+        if first_row < 0 or first_row % g:
+            raise RuntimeError(f"spectrogram {name}: first_row = {first_row}, a strip starts at a multiple of {g} rows")
+        if total_rows == 0 and self.nrows % g:
+            raise RuntimeError(f"spectrogram {name}: the session has {self.nrows} rows and is not the last strip (total_rows = 0), "
+                               f"needs a multiple of {g}")
+        if total_rows != 0 and total_rows != first_row + self.nrows:
+            raise RuntimeError(f"spectrogram {name}: total_rows = {total_rows}, the last strip ends at first_row + rows = "
+                               f"{first_row} + {self.nrows}")
+        if first_row == 0:
+            return None
+        if carry is None or np.shape(carry) != shape:
+            raise RuntimeError(f"spectrogram {name}: needs the carry of the rows before first_row, of shape {shape}")
+        return carry
+
+    @staticmethod
+    def _handed_on(carry, result: np.ndarray) -> np.ndarray:
+        if carry is None:
+            return result
+        carry[...] = result                     # in place, as the device call updates the caller's array
+        return carry
+
+    def spectrogram_sum(self, nperseg: int, noverlap: int, nfft: int, window, scaling: str, fs: float, first_row: int,
+                        total_rows: int = 0, carry=None) -> np.ndarray:
         x = self._source()
         step = nperseg - noverlap
-        return mean_power(x, nperseg, step, (len(x) - noverlap) // step, nfft, window, scaling, fs)
+        nseg = (len(x) - noverlap) // step
+        start = self._carried("spectrogram_sum", (nfft // 2 + 1, nseg), int(first_row), int(total_rows), carry)
+        return self._handed_on(carry, sum_power(x, nperseg, step, nseg, nfft, window, scaling, fs, start, int(total_rows), chunk=self.granule))
+
+    def periodogram_sum(self, window, scaling: str, fs: float, first_row: int, total_rows: int = 0, carry=None) -> np.ndarray:
+        x = self._source()
+        start = self._carried("periodogram_sum", (len(x) // 2 + 1,), int(first_row), int(total_rows), carry)
+        res = sum_power(x, len(x), len(x), 1, len(x), window, scaling, fs, None if start is None else np.asarray(start)[:, None],
+                        int(total_rows), chunk=self.granule)[:, 0]
+        return self._handed_on(carry, res)
+
+    def spectrogram(self, nperseg: int, noverlap: int, nfft: int, window, scaling: str, fs: float) -> np.ndarray:
+        return self.spectrogram_sum(nperseg, noverlap, nfft, window, scaling, fs, 0, self.nrows)
 
     def periodogram(self, window, scaling: str, fs: float) -> np.ndarray:
-        x = self._source()
-        return mean_power(x, len(x), len(x), 1, len(x), window, scaling, fs)[:, 0]
+        return self.periodogram_sum(window, scaling, fs, 0, self.nrows)
+
+
+class DeviceSpecSession(DeviceSession):
+    """``HipBackend.spec_*`` of one quantity behind the host session's method names; its granule is the row block of
+    k_spec_power."""
+    granule = ROWS
+
+    def __init__(self, backend, q: str):
+        super().__init__(backend, "spec", q)
 
 
 def component_rows(values: np.ndarray, component: str) -> np.ndarray:
@@ -365,14 +439,46 @@ def select_nodes(mesh: FsiMesh, save_deg: int, quantity: str, v: dict, o: dict) 
 # pipeline and files
 # ------------------------------------------------------------------------------------------------
 
-def pipeline(session, nrows: int, n: int, T: float, start_t: float, o: dict, min_color) -> dict:
-    """``create_spectrogram_composite`` and ``create_spectrum`` on a session (``HostSpecSession`` or its device twin behind
-    the same calls) that holds n frames of nrows rows: the clamped log spectrogram of the high-passed rows, the chromagram
-    and SBI of the raw rows' spectrogram, and the log of the raw rows' average periodogram."""
+def transform_plan(nrows: int, n: int, T: float, o: dict) -> dict:
+    """What the three transforms of n frames over T seconds are called with: the segment sizes and the window of the
+    spectrograms, the high-pass, the periodogram's window and scaling.  ``nrows`` is the number of all rows, wherever they
+    are held: with a single one ``get_psd`` drops the scaling it is given."""
     fs = n / T
     plan = window_plan(n, T, o["num_windows_per_sec"], o["overlap_frac"])
+    return dict(plan=plan, fs=fs, n=n, nrows=nrows, window=window_values(o["window"], plan["nperseg"]), hp=highpass_design(fs, o["lowcut"]),
+                psd_window=window_values("blackmanharris", n), psd_scaling="spectrum" if nrows > 1 else "density")
+
+
+def session_powers(session, tp: dict, strip=None, carries=None):
+    """The three mean powers the pipeline takes from a session (``HostSpecSession`` or its device twin behind the same
+    calls) that holds n frames: the spectrogram of the high-passed rows, that of the raw rows and the raw rows' periodogram.
+    ``strip``: None where the session holds all ``tp["nrows"]`` rows; else ``(first_row, last)`` of a session that holds the
+    rows from ``first_row`` on - ``carries``, the three sums over the rows before (None for the first strip), are handed on
+    through the ``_sum`` calls, and the last strip returns the means."""
+    plan, fs, hp = tp["plan"], tp["fs"], tp["hp"]
     K, nov, nfft = plan["nperseg"], plan["noverlap"], plan["nfft"]
-    w = window_values(o["window"], K)
+    if strip is None:
+        spectrogram = lambda k: session.spectrogram(K, nov, nfft, tp["window"], "spectrum", fs)
+        periodogram = lambda k: session.periodogram(tp["psd_window"], tp["psd_scaling"], fs)
+    else:
+        first_row, total = int(strip[0]), tp["nrows"] if strip[1] else 0
+        c = [None, None, None] if carries is None else carries
+        spectrogram = lambda k: session.spectrogram_sum(K, nov, nfft, tp["window"], "spectrum", fs, first_row, total, c[k])
+        periodogram = lambda k: session.periodogram_sum(tp["psd_window"], tp["psd_scaling"], fs, first_row, total, c[k])
+    session.filter(hp["b"], hp["a"], hp["zi"], hp["padlen"])
+    P_filtered = spectrogram(0)
+    session.filter()
+    P_raw = spectrogram(1)
+    return [P_filtered, P_raw, periodogram(2)]
+
+
+def results(powers, tp: dict, start_t: float, min_color) -> dict:
+    """``create_spectrogram_composite`` and ``create_spectrum`` from the three mean powers of ``session_powers``: the clamped
+    log spectrogram of the high-passed rows, the chromagram and SBI of the raw rows' spectrogram, and the log of the raw
+    rows' average periodogram."""
+    P_filtered, P_raw, P_psd = powers
+    plan, fs, n = tp["plan"], tp["fs"], tp["n"]
+    K, nov, nfft = plan["nperseg"], plan["noverlap"], plan["nfft"]
     freqs = np.fft.rfftfreq(nfft, 1 / fs)
     bins = np.arange(K / 2, n - K / 2 + 1, K - nov) / float(fs) + start_t
 
@@ -384,19 +490,19 @@ def pipeline(session, nrows: int, n: int, T: float, start_t: float, o: dict, min
         L[L < min_color] = min_color
         return L
 
-    hp = highpass_design(fs, o["lowcut"])
-    session.filter(hp["b"], hp["a"], hp["zi"], hp["padlen"])
-    P_filtered = session.spectrogram(K, nov, nfft, w, "spectrum", fs)
-    session.filter()
-    P_raw = session.spectrogram(K, nov, nfft, w, "spectrum", fs)
     chroma = chromagram(np.exp(scaled(P_raw)), fs, nfft)
-    scaling = "spectrum" if nrows > 1 else "density"          # get_psd's single-row branch drops the scaling it is given
-    P_psd = session.periodogram(window_values("blackmanharris", n), scaling, fs)
     with np.errstate(divide="ignore"):
         log_psd = np.log(P_psd)
     return dict(plan=plan, fs=fs, freqs=freqs, bins=bins, spectrogram=scaled(P_filtered), chroma=chroma, sbi=sbi(chroma),
                 psd_freqs=np.fft.rfftfreq(n, 1 / fs), psd=log_psd, power_filtered=P_filtered, power_raw=P_raw, power_psd=P_psd,
-                psd_scaling=scaling)
+                psd_scaling=tp["psd_scaling"])
+
+
+def pipeline(session, nrows: int, n: int, T: float, start_t: float, o: dict, min_color) -> dict:
+    """The three mean powers of a session that holds n frames of nrows rows (``session_powers``), turned into what the files
+    hold (``results``)."""
+    tp = transform_plan(nrows, n, T, o)
+    return results(session_powers(session, tp), tp, start_t, min_color)
 
 
 def file_names(name: str, case: str, num_windows, min_color) -> Dict[str, str]:
@@ -454,24 +560,33 @@ def spectrogram_refusal(v: dict, world: int, backend_cls) -> str:
     return ""
 
 
+def host_chunk(backend) -> int:
+    """The column chunk of the host sessions of a backend (or backend class) without ``spec_begin``: HOST_CHUNK unless it
+    names its own (``spec_host_chunk``)."""
+    return int(getattr(backend, "spec_host_chunk", HOST_CHUNK))
+
+
 class SpectrogramRun(SessionRun):
     """The driver's side of ``--spectrogram``: per quantity one session on the sampled nodes, one recorded frame per saved
     frame, and at the end the four files.  A backend without ``spec_begin`` records and transforms on the host."""
     prefix, file_stem, key = "spec", "spectrogram", "spectrogram"
     option, words = "--spectrogram", "--spectrogram cannot be used with --restart-folder"
 
-    def __init__(self, backend, mesh: FsiMesh, ns: dict):
+    def __init__(self, backend, mesh: FsiMesh, ns: dict, open_sessions: bool = True):
+        """``open_sessions`` False: everything but the sessions - the strips of ``spectrogram_strips`` open their own."""
         self.backend, self.mesh = backend, mesh
         self.quantities = quantities(ns)
         self.opts = options(ns)
         self.save_deg = int(ns["save_deg"])
         self.dt_files = frame_spacing(ns)
         self.start_t = frame_start(ns)
+        self.expected = expected_frames(ns)          # the frames the run saves, or a finished folder hands over
         self.folder = Path(ns["results_folder"]) / "Spectrograms"
         self.case = str(ns.get("case") or Path(ns["results_folder"]).parent.name)     # "case": the folder that was read, where the files go elsewhere
         self.sel = {q: select_nodes(mesh, self.save_deg, q, ns, self.opts) for q in self.quantities}     # an empty region ends the run here
-        self.open_sessions(backend, ns, lambda q: (self.sel[q]["nodes"], self.sel[q]["nodes_b"], self.opts["component"]),
-                           lambda q, capacity: HostSpecSession(self.rows(q), capacity))
+        if open_sessions:
+            self.open_sessions(backend, ns, lambda q: (self.sel[q]["nodes"], self.sel[q]["nodes_b"], self.opts["component"]),
+                               lambda q, capacity: HostSpecSession(self.rows(q), capacity, host_chunk(backend)))
 
     def rows(self, q: str) -> int:
         return len(self.sel[q]["ids"]) * (3 if q != "p" and self.opts["component"] == "all" else 1)
