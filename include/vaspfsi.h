@@ -522,7 +522,8 @@ int fsi_order_statistics(FsiCtx* ctx, int64_t n, const double* values, int32_t n
 int fsi_band_end(FsiCtx* ctx, int32_t quantity);
 
 /* ---- average spectrograms and power spectra over a run (fsi_spec.hip) -------------------------------------- */
-/* One session per quantity (0 = d, 1 = v, 2 = p), with a history of its own on a node list of its own: it can be open beside
+/* One session per quantity (0 = d, 1 = v, 2 = p, 3 = the wall shear stress, opened by fsi_spec_begin_wss), with a history of its
+ * own on a node list of its own: it can be open beside
  * the band-pass session of the same quantity, and beside every other session.  A row is one time series: one component of a
  * listed node, its three components stacked (row = component * n + i), or the magnitude of the vector, taken when the frame is
  * recorded.  The pressure has one component: ncomp_mode is ignored for it.  All data are FP64. */
@@ -531,6 +532,7 @@ int fsi_band_end(FsiCtx* ctx, int32_t quantity);
 #define FSI_SPEC_Z 2
 #define FSI_SPEC_ALL 3
 #define FSI_SPEC_MAG 4
+#define FSI_SPEC_WSS 3 /* the quantity of fsi_spec_begin_wss */
 #define FSI_SPEC_SPECTRUM 0 /* power scaled by 1 / sum(w)^2 */
 #define FSI_SPEC_DENSITY 1  /* power scaled by 1 / (fs sum(w^2)) */
 /* Replaces: read_spectrogram_data's pass over the Visualization files into <quantity>_<component>.npz and its selection of the
@@ -553,6 +555,23 @@ int fsi_spec_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* node
  * partitioned contexts. */
 int fsi_spec_begin_rows(FsiCtx* ctx, int32_t quantity, int64_t nrows, const int32_t* nodes, const int32_t* nodes_b,
                         const int32_t* comps, int64_t capacity);
+/* Replaces: the second tool run (vasp-compute-hemo), the pass of read_spectrogram_data over its WSS.h5 into a host matrix and the
+ * selection of the sampled rows [REF src/vasp/postprocessing/postprocessing_fenics/compute_hemodynamics.py:160-372;
+ * .../spectrograms.py:291-329 with quantity "wss"]: the session of quantity FSI_SPEC_WSS, whose rows are the wall shear stress at
+ * DG1 dofs of the fluid's boundary mesh, formed on the device at every recorded frame by the arithmetic of
+ * fsi_wall_shear_stress and fsi_hemo_sample (the same bits).  facet_cells[nf] / facet_local[nf]: ALL exterior facets of the
+ * fluid, as for fsi_hemo_begin - the projection on a cell couples all of that cell's exterior facets, so the list must be the
+ * full one even when one dof is sampled; mu: the dynamic viscosity.  Dof 3 f + k is vertex k of facet f (the local vertices of
+ * its cell without facet_local[f], ascending).  Row r is component comps[r] (0 = x, 1 = y, 2 = z, 3 = the magnitude
+ * sqrt((x x + y y) + z z), taken when the frame is recorded) of dof dofs[r], 0 <= dofs[r] < 3 nf; a dof may be listed more than
+ * once.  The call is row-based: a strip of a longer row list is a sub-list and needs no second entry point.  The device-room
+ * refusal is that of fsi_spec_begin_rows, a magnitude row counted as in fsi_spec_room(..., magnitude = 1).  FSI_ERR_INVALID with
+ * one line in fsi_last_error and nothing allocated: a partitioned context, nf < 1, mu <= 0, a facet's cell or local index out of
+ * range, a facet of a non-fluid cell, a facet listed twice, a dof or a component out of range, nrows < 1, capacity < 1.
+ * Replaces an open session of the quantity; a refused call leaves it as it was.  fsi_spec_sample, _filter, _fetch, the
+ * transforms, _export, _import and _end serve quantity 3 as the others. */
+int fsi_spec_begin_wss(FsiCtx* ctx, int64_t nf, const int32_t* facet_cells, const int32_t* facet_local, double mu, int64_t nrows,
+                       const int32_t* dofs, const int32_t* comps, int64_t capacity);
 /* Replaces: the sizing a user of read_spectrogram_data does by hand before the row x time matrix is read into host memory
  * [REF .../spectrograms.py:291-329]: the two byte counts fsi_spec_begin and fsi_spec_begin_rows compare for a session of
  * `rows` rows (`magnitude` != 0: rows of FSI_SPEC_MAG, which sample three entries each) and `capacity` frames.  *need: the raw

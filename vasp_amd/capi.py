@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_set_frame", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_begin_rows", "fsi_spec_room", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_spectrogram_sum", "fsi_spec_periodogram_sum", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_begin_rows", "fsi_spec_begin_wss", "fsi_spec_room", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_spectrogram_sum", "fsi_spec_periodogram_sum", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -181,6 +181,7 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_order_statistics.argtypes = [vp, i64, vp, i32, vp, vp, C.POINTER(i64)]
     lib.fsi_spec_begin.argtypes = [vp, i32, i64, vp, vp, i32, i64]
     lib.fsi_spec_begin_rows.argtypes = [vp, i32, i64, vp, vp, vp, i64]
+    lib.fsi_spec_begin_wss.argtypes = [vp, i64, vp, vp, dbl, i64, vp, vp, i64]
     lib.fsi_spec_room.argtypes = [vp, i64, i32, i64, C.POINTER(dbl), C.POINTER(dbl)]
     lib.fsi_spec_sample.argtypes = [vp, i32]
     lib.fsi_spec_filter.argtypes = [vp, i32, i32, vp, vp, vp, i32]
@@ -747,6 +748,7 @@ class HipBackend:
 
     SPEC_MODE = {"x": 0, "y": 1, "z": 2, "all": 3, "mag": 4}
     SPEC_SCALING = {"spectrum": 0, "density": 1}
+    SPEC_QUANTITY = {"d": 0, "v": 1, "p": 2, "wss": 3}
 
     def spec_begin(self, quantity: str, nodes, nodes_b=None, component: str = "all", capacity: int = 1) -> None:
         """Open the spectrogram session of ``quantity`` (fsi_spec_begin) on ``nodes`` (as ``hi_pass_begin``; a node may be
@@ -756,7 +758,7 @@ class HipBackend:
         b = None if nodes_b is None else np.ascontiguousarray(nodes_b, dtype=np.int32)
         if b is not None and b.shape != a.shape:
             raise ValueError("nodes_b must have the shape of nodes")
-        self._check(self.lib.fsi_spec_begin(self.ctx, self.BAND_QUANTITY[quantity], len(a), _ptr(a), None if b is None else _ptr(b),
+        self._check(self.lib.fsi_spec_begin(self.ctx, self.SPEC_QUANTITY[quantity], len(a), _ptr(a), None if b is None else _ptr(b),
                                             self.SPEC_MODE[component], int(capacity)))
         self._spec_shape[quantity] = [len(a) * (3 if component == "all" and quantity != "p" else 1), 0]
 
@@ -770,9 +772,24 @@ class HipBackend:
         c = None if comps is None else np.ascontiguousarray(comps, dtype=np.int32)
         if any(x is not None and x.shape != a.shape for x in (b, c)):
             raise ValueError("nodes_b and comps must have the shape of nodes")
-        self._check(self.lib.fsi_spec_begin_rows(self.ctx, self.BAND_QUANTITY[quantity], len(a), _ptr(a), None if b is None else _ptr(b),
+        self._check(self.lib.fsi_spec_begin_rows(self.ctx, self.SPEC_QUANTITY[quantity], len(a), _ptr(a), None if b is None else _ptr(b),
                                                  None if c is None else _ptr(c), int(capacity)))
         self._spec_shape[quantity] = [len(a), 0]
+
+    def spec_begin_wss(self, facet_cells, facet_local, mu: float, dofs, comps, capacity: int = 1) -> None:
+        """Open the spectrogram session of the wall shear stress (quantity ``"wss"``, fsi_spec_begin_wss).  ``facet_cells`` /
+        ``facet_local``: ALL exterior facets of the fluid, as for ``hemodynamics_begin`` (a cell's projection couples its
+        exterior facets).  Row r is component ``comps[r]`` (0 .. 2, or 3: the magnitude) of DG1 dof ``dofs[r]`` of the
+        boundary mesh, dof 3 f + k being vertex k of facet f; a dof may be listed twice.  A strip of a longer row list is a
+        sub-list.  Raises FsiError when the history does not fit."""
+        fc = np.ascontiguousarray(self.cell_u2i[np.asarray(facet_cells, dtype=np.int64)], dtype=np.int32)
+        fl = np.ascontiguousarray(facet_local, dtype=np.int32)
+        d = np.ascontiguousarray(dofs, dtype=np.int32)
+        c = np.ascontiguousarray(comps, dtype=np.int32)
+        if fl.shape != fc.shape or c.shape != d.shape or d.ndim != 1:
+            raise ValueError("facet_local must have the shape of facet_cells, comps that of dofs")
+        self._check(self.lib.fsi_spec_begin_wss(self.ctx, len(fc), _ptr(fc), _ptr(fl), float(mu), len(d), _ptr(d), _ptr(c), int(capacity)))
+        self._spec_shape["wss"] = [len(d), 0]
 
     def spec_room(self, rows: int, capacity: int, magnitude: bool = False):
         """(need, available) in bytes: what a spectrogram session of ``rows`` rows (``magnitude``: of component 'mag') and
@@ -784,30 +801,30 @@ class HipBackend:
 
     def spec_sample(self, quantity: str) -> None:
         """Record the session's rows of dvp_["n"] as the next frame of its history (fsi_spec_sample)."""
-        self._check(self.lib.fsi_spec_sample(self.ctx, self.BAND_QUANTITY[quantity]))
+        self._check(self.lib.fsi_spec_sample(self.ctx, self.SPEC_QUANTITY[quantity]))
         self._spec_shape[quantity][1] += 1
 
     def spec_filter(self, quantity: str, b=None, a=None, zi=None, padlen: int = 0) -> None:
         """scipy.signal.filtfilt(b, a, .) of every row, the source of the transforms that follow (fsi_spec_filter); without
         coefficients: the raw series."""
         if b is None:
-            self._check(self.lib.fsi_spec_filter(self.ctx, self.BAND_QUANTITY[quantity], 0, None, None, None, 0))
+            self._check(self.lib.fsi_spec_filter(self.ctx, self.SPEC_QUANTITY[quantity], 0, None, None, None, 0))
             return
         b, a, zi = (np.ascontiguousarray(x, dtype=np.float64) for x in (b, a, zi))
         if len(a) != len(b) or len(zi) != len(b) - 1:
             raise ValueError("b and a must have one length, zi one less")
-        self._check(self.lib.fsi_spec_filter(self.ctx, self.BAND_QUANTITY[quantity], len(b), _ptr(b), _ptr(a), _ptr(zi), int(padlen)))
+        self._check(self.lib.fsi_spec_filter(self.ctx, self.SPEC_QUANTITY[quantity], len(b), _ptr(b), _ptr(a), _ptr(zi), int(padlen)))
 
     def _spec_open(self, quantity: str):
         """[rows, recorded frames] of the open session; without one, the library's own refusal."""
         if quantity not in self._spec_shape:
-            self._check(self.lib.fsi_spec_sample(self.ctx, self.BAND_QUANTITY[quantity]))     # "fsi_spec_begin first"
+            self._check(self.lib.fsi_spec_sample(self.ctx, self.SPEC_QUANTITY[quantity]))     # "fsi_spec_begin first"
         return self._spec_shape[quantity]
 
     def spec_fetch(self, quantity: str, frame: int, filtered: bool = False) -> np.ndarray:
         """One frame of the raw or the filtered history: (rows,) (fsi_spec_fetch)."""
         out = np.empty(self._spec_open(quantity)[0])
-        self._check(self.lib.fsi_spec_fetch(self.ctx, self.BAND_QUANTITY[quantity], int(bool(filtered)), int(frame), _ptr(out)))
+        self._check(self.lib.fsi_spec_fetch(self.ctx, self.SPEC_QUANTITY[quantity], int(bool(filtered)), int(frame), _ptr(out)))
         return out
 
     def spec_spectrogram(self, quantity: str, nperseg: int, noverlap: int, nfft: int, window, scaling: str, fs: float) -> np.ndarray:
@@ -820,7 +837,7 @@ class HipBackend:
             raise ValueError("needs 0 <= noverlap < nperseg <= recorded frames")
         nseg = (frames - int(noverlap)) // (int(nperseg) - int(noverlap))
         out = np.empty((int(nfft) // 2 + 1, max(nseg, 0)))
-        self._check(self.lib.fsi_spec_spectrogram(self.ctx, self.BAND_QUANTITY[quantity], int(nperseg), int(noverlap), int(nfft), _ptr(w),
+        self._check(self.lib.fsi_spec_spectrogram(self.ctx, self.SPEC_QUANTITY[quantity], int(nperseg), int(noverlap), int(nfft), _ptr(w),
                                                   self.SPEC_SCALING[scaling], float(fs), _ptr(out)))
         return out
 
@@ -831,7 +848,7 @@ class HipBackend:
         if w.shape != (frames,):
             raise ValueError("the window must have one entry per recorded frame")
         out = np.empty(frames // 2 + 1)
-        self._check(self.lib.fsi_spec_periodogram(self.ctx, self.BAND_QUANTITY[quantity], _ptr(w), self.SPEC_SCALING[scaling], float(fs), _ptr(out)))
+        self._check(self.lib.fsi_spec_periodogram(self.ctx, self.SPEC_QUANTITY[quantity], _ptr(w), self.SPEC_SCALING[scaling], float(fs), _ptr(out)))
         return out
 
     @staticmethod
@@ -858,7 +875,7 @@ class HipBackend:
             raise ValueError("needs 0 <= noverlap < nperseg <= recorded frames")
         nseg = (frames - int(noverlap)) // (int(nperseg) - int(noverlap))
         carry = self._spec_carry(carry, (int(nfft) // 2 + 1, max(nseg, 0)), first_row)
-        self._check(self.lib.fsi_spec_spectrogram_sum(self.ctx, self.BAND_QUANTITY[quantity], int(nperseg), int(noverlap), int(nfft), _ptr(w),
+        self._check(self.lib.fsi_spec_spectrogram_sum(self.ctx, self.SPEC_QUANTITY[quantity], int(nperseg), int(noverlap), int(nfft), _ptr(w),
                                                       self.SPEC_SCALING[scaling], float(fs), int(first_row), int(total_rows),
                                                       None if carry is None else _ptr(carry)))
         return carry
@@ -871,14 +888,14 @@ class HipBackend:
         if w.shape != (frames,):
             raise ValueError("the window must have one entry per recorded frame")
         carry = self._spec_carry(carry, (frames // 2 + 1,), first_row)
-        self._check(self.lib.fsi_spec_periodogram_sum(self.ctx, self.BAND_QUANTITY[quantity], _ptr(w), self.SPEC_SCALING[scaling], float(fs),
+        self._check(self.lib.fsi_spec_periodogram_sum(self.ctx, self.SPEC_QUANTITY[quantity], _ptr(w), self.SPEC_SCALING[scaling], float(fs),
                                                       int(first_row), int(total_rows), None if carry is None else _ptr(carry)))
         return carry
 
     def spec_export(self, quantity: str, first: int, count: int) -> np.ndarray:
         """Raw frames ``first .. first + count - 1`` of the history as (count, rows), in one copy (fsi_spec_export)."""
         out = np.empty((max(int(count), 0), self._spec_open(quantity)[0]))
-        self._check(self.lib.fsi_spec_export(self.ctx, self.BAND_QUANTITY[quantity], int(first), int(count), _ptr(out)))
+        self._check(self.lib.fsi_spec_export(self.ctx, self.SPEC_QUANTITY[quantity], int(first), int(count), _ptr(out)))
         return out
 
     def spec_import(self, quantity: str, frames) -> None:
@@ -887,11 +904,11 @@ class HipBackend:
         x = np.ascontiguousarray(frames, dtype=np.float64)
         if x.ndim < 1 or x.size != len(x) * shape[0]:
             raise FsiError(1, f"spec_import: frames of shape {x.shape}, the open session has {shape[0]} rows")
-        self._check(self.lib.fsi_spec_import(self.ctx, self.BAND_QUANTITY[quantity], len(x), _ptr(x)))
+        self._check(self.lib.fsi_spec_import(self.ctx, self.SPEC_QUANTITY[quantity], len(x), _ptr(x)))
         shape[1] += len(x)
 
     def spec_end(self, quantity: str) -> None:
-        self._check(self.lib.fsi_spec_end(self.ctx, self.BAND_QUANTITY[quantity]))
+        self._check(self.lib.fsi_spec_end(self.ctx, self.SPEC_QUANTITY[quantity]))
         self._spec_shape.pop(quantity, None)
 
     def tuning(self) -> dict:

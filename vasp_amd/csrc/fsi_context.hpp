@@ -451,11 +451,21 @@ struct FsiCtx {
     void release() { data.release(); part_val.release(); part_idx.release(); open = false; nodes = frames = 0; }
   } board;
 
-  // spectrogram sessions (fsi_spec_begin .. fsi_spec_end), one per quantity d, v, p, with a history of their own on a row
+  // spectrogram sessions (fsi_spec_begin .. fsi_spec_end), one per quantity d, v, p, wss, with a history of their own on a row
   // list of their own.  mode: 0 / 1 / 2 one component, 3 the three stacked (row = c * nnode + i), 4 the magnitude, taken at
   // sample time.  Means, tables and partial sums live for one call (fsi_spec.hip).
+  // Slot 3 (fsi_spec_begin_wss): the wall shear stress at listed DG1 dofs of the fluid's boundary mesh - idx0 / idx1 are
+  // unused; instead the boundary cells the sampled dofs touch, each with the mask of ALL its exterior facets (the projection
+  // couples them), and per cell its rows as pairs (row, 4 * local vertex + component, component 3 the magnitude).
   struct Spec : History {
     int mode = 0;
-    void release() { History::release(); mode = 0; }
-  } spec[3];
+    int64_t wncell = 0;
+    double mu = 0.0;
+    fsi::DevBuf<int32_t> wcells, wmask, wptr, went;   // [wncell], [wncell], [wncell + 1], [nrow][2]
+    void release() {
+      History::release();
+      wcells.release(); wmask.release(); wptr.release(); went.release();
+      mode = 0; wncell = 0; mu = 0.0;
+    }
+  } spec[4];
 };

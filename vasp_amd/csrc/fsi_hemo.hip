@@ -17,6 +17,8 @@
 //                   physical weights 2 A w_q the area cancels, proj_a = 6 sum_b (4 delta_ab - 1) sum_q w_q L_qb |D_q|.
 //                   Quirk kept from the reference: tau_prev starts at zero (:244), so the first sample adds |tau_1| / dt
 //                   to TWSSG (:309-316).
+//   k_spec_wss_sample : one lane per boundary cell touched by the sampled dofs of a spectrogram session (--spectrogram wss):
+//                   the same b, written to the session's rows of hist[frame] - a component or the magnitude of a dof.
 //   k_hemo_finish : one lane per dof, plain IEEE arithmetic as the reference's numpy (inf / NaN where a denominator
 //                   vanishes, no clamping): TAWSS = sum_mag / n, m = |sum_tau / n|, RRT = 1 / m, OSI = (1 - m / TAWSS) / 2,
 //                   ECAP = OSI / TAWSS, TWSSG = sum_twssg / n.
@@ -81,6 +83,34 @@ __global__ __launch_bounds__(64) void k_hemo_sample(ElemArrays ea, const double*
   }
 }
 
+// The rows of a spectrogram session of the wall shear stress (fsi_spec_begin_wss): one lane per boundary cell that a sampled
+// dof touches.  fmask is the cell's full exterior-facet mask, so b is what k_wss and k_hemo_sample form on the cell, whichever
+// of its dofs are sampled; the lane then writes its own rows - a dof drawn twice is two entries of its list.
+__global__ __launch_bounds__(64) void k_spec_wss_sample(ElemArrays ea, const double* __restrict__ U, int64_t ncell,
+                                                        const int32_t* __restrict__ cells, const int32_t* __restrict__ fmask,
+                                                        const int32_t* __restrict__ ptr, const int32_t* __restrict__ ent, double mu,
+                                                        double* __restrict__ dst) {
+  const int64_t ci = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (ci >= ncell) return;
+  double b[4][3];
+  wss_dg1_cell(ea, U, cells[ci], fmask[ci], mu, b);
+  for (int32_t e = ptr[ci]; e < ptr[ci + 1]; ++e) {
+    const int32_t row = ent[2 * e], code = ent[2 * e + 1], va = code >> 2, comp = code & 3;
+    double t[3] = {0.0, 0.0, 0.0};
+    for (int a = 0; a < 4; ++a)                                // selects, not indexing: b stays in registers
+      for (int i = 0; i < 3; ++i)
+        if (a == va) t[i] = b[a][i];
+    double val;
+    if (comp == 3) {
+#pragma clang fp contract(off)                                 // the arithmetic of k_spec_magnitude (fsi_spec.hip), bit for bit
+      val = sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
+    } else {
+      val = comp == 0 ? t[0] : comp == 1 ? t[1] : t[2];
+    }
+    dst[row] = val;
+  }
+}
+
 // out[5][ndof]: TAWSS, OSI, RRT, ECAP, TWSSG
 __global__ __launch_bounds__(256) void k_hemo_finish(int64_t ndof, double n, HemoAcc acc, double* __restrict__ out) {
   const int64_t d = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -108,6 +138,12 @@ void launch_hemo_sample(hipStream_t st, int64_t ncell, const ElemArrays& ea, con
   if (ncell > 0)
     hipLaunchKernelGGL(k_hemo_sample, dim3((unsigned)((ncell + 63) / 64)), dim3(64), 0, st, ea, U, ncell, cells, fmask, fidx,
                        mu, dt, acc, wss_out);
+}
+void launch_spec_wss_sample(hipStream_t st, int64_t ncell, const ElemArrays& ea, const double* U, const int32_t* cells,
+                            const int32_t* fmask, const int32_t* ptr, const int32_t* ent, double mu, double* dst) {
+  if (ncell > 0)
+    hipLaunchKernelGGL(k_spec_wss_sample, dim3((unsigned)((ncell + 63) / 64)), dim3(64), 0, st, ea, U, ncell, cells, fmask, ptr, ent,
+                       mu, dst);
 }
 void launch_hemo_finish(hipStream_t st, int64_t ndof, double samples, const HemoAcc& acc, double* out) {
   if (ndof > 0)

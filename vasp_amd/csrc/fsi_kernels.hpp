@@ -156,6 +156,12 @@ hipError_t hemo_upload_tables(const double* w, const double* lam);      // trian
 void launch_hemo_sample(hipStream_t st, int64_t ncell, const ElemArrays& ea, const double* U, const int32_t* cells,
                         const int32_t* fmask, const int32_t* fidx, double mu, double dt, const HemoAcc& acc, double* wss_out);
 void launch_hemo_finish(hipStream_t st, int64_t ndof, double samples, const HemoAcc& acc, double* out);
+// the rows of a spectrogram session on the wall shear stress: for each of the ncell boundary cells `cells` (full exterior-facet
+// mask fmask) one wss_dg1_cell, then for its entries e = ptr[ci] .. ptr[ci + 1] - 1: dst[ent[2 e]] = component (ent[2 e + 1] & 3)
+// of local vertex (ent[2 e + 1] >> 2), component 3 the magnitude sqrt((x x + y y) + z z) without contraction.  Every row is
+// listed once: no atomics.
+void launch_spec_wss_sample(hipStream_t st, int64_t ncell, const ElemArrays& ea, const double* U, const int32_t* cells,
+                            const int32_t* fmask, const int32_t* ptr, const int32_t* ent, double mu, double* dst);
 
 // fsi_solver.hip — sparse / dense vector kernels
 void launch_expand_cols(hipStream_t st, int64_t N2, int64_t V, const int64_t* nadj_ptr, const int32_t* nadj,

@@ -18,9 +18,11 @@ HemoAcc hemo_acc(FsiCtx* ctx) {
 
 // ---- the recorded history of a band-pass or a spectrogram session (FsiCtx::History) ---------------------------------------
 
-// the open session of quantity q (0 d, 1 v, 2 p; among five also 3 strain, 4 stress) among all[N], or null with ctx->err set
+// the open session of quantity q (0 d, 1 v, 2 p; among four also 3 wss; among five 3 strain, 4 stress) among all[N], or null
+// with ctx->err set
 template <int N> const char* quantity_range();
 template <> const char* quantity_range<3>() { return ": quantity must be 0 (d), 1 (v) or 2 (p)"; }
+template <> const char* quantity_range<4>() { return ": quantity must be 0 (d), 1 (v), 2 (p) or 3 (wss)"; }
 template <> const char* quantity_range<5>() { return ": quantity must be 0 (d), 1 (v), 2 (p), 3 (strain) or 4 (stress)"; }
 template <class S, int N>
 S* open_session(FsiCtx* ctx, S (&all)[N], int32_t q, const char* fn, const char* kind, const char* begin) {
@@ -32,7 +34,9 @@ bool tensor_quantity(int32_t q) { return q == FSI_BAND_STRAIN || q == FSI_BAND_S
 FsiCtx::Band* band_session(FsiCtx* ctx, int32_t q, const char* fn) {
   return open_session(ctx, ctx->band, q, fn, "band-pass", tensor_quantity(q) ? "fsi_band_begin_cells" : "fsi_band_begin");
 }
-FsiCtx::Spec* spec_session(FsiCtx* ctx, int32_t q, const char* fn) { return open_session(ctx, ctx->spec, q, fn, "spectrogram", "fsi_spec_begin"); }
+FsiCtx::Spec* spec_session(FsiCtx* ctx, int32_t q, const char* fn) {
+  return open_session(ctx, ctx->spec, q, fn, "spectrogram", q == FSI_SPEC_WSS ? "fsi_spec_begin_wss" : "fsi_spec_begin");
+}
 // frames of the band-pass session's view of its history (fsi_band_select): those the filtered series and the amplitude have
 int64_t band_frames(const FsiCtx::Band* s) { return s->sel_count < 0 ? s->frames : s->sel_count; }
 
@@ -250,14 +254,13 @@ int spec_room(FsiCtx* ctx, int64_t nrow, int64_t nsamp, int64_t capacity, double
   return FSI_OK;
 }
 
-// What fsi_spec_begin and fsi_spec_begin_rows do once their row lists stand: the room check, then the session.
-int spec_open(FsiCtx* ctx, const char* fn, int32_t quantity, int64_t n, int64_t nrow, int mode, int64_t capacity,
-              const std::vector<int32_t>& i0, const std::vector<int32_t>& i1) {
+// The room check of the three spectrogram begin calls: refused, with both byte counts, when the session does not fit.
+int spec_refused(FsiCtx* ctx, const char* fn, int64_t nrow, int64_t nsamp, int64_t capacity) {
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   double need_d = 0.0, avail = 0.0;
   Room room;
-  FSICHK(spec_room(ctx, nrow, (int64_t)i0.size(), capacity, &need_d, &avail, &room));
+  FSICHK(spec_room(ctx, nrow, nsamp, capacity, &need_d, &avail, &room));
   if (need_d > avail) {
     char msg[420];
     snprintf(msg, sizeof msg, "%s: the session needs %.0f bytes (%lld rows x %lld frames, raw and filtered, and the transforms' tables), the device has %zu bytes "
@@ -265,6 +268,13 @@ int spec_open(FsiCtx* ctx, const char* fn, int32_t quantity, int64_t n, int64_t 
     ctx->err = msg;
     return FSI_ERR_INVALID;
   }
+  return FSI_OK;
+}
+
+// What fsi_spec_begin and fsi_spec_begin_rows do once their row lists stand: the room check, then the session.
+int spec_open(FsiCtx* ctx, const char* fn, int32_t quantity, int64_t n, int64_t nrow, int mode, int64_t capacity,
+              const std::vector<int32_t>& i0, const std::vector<int32_t>& i1) {
+  FSICHK(spec_refused(ctx, fn, nrow, (int64_t)i0.size(), capacity));
   auto& s = ctx->spec[quantity];
   s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
   s.mode = mode;
@@ -1038,6 +1048,84 @@ int fsi_spec_begin_rows(FsiCtx* ctx, int32_t quantity, int64_t nrows, const int3
   return spec_open(ctx, "fsi_spec_begin_rows", quantity, nrows, nrows, mode, capacity, i0, i1);
 }
 
+int fsi_spec_begin_wss(FsiCtx* ctx, int64_t nf, const int32_t* facet_cells, const int32_t* facet_local, double mu, int64_t nrows,
+                       const int32_t* dofs, const int32_t* comps, int64_t capacity) {
+  if (!ctx) return FSI_ERR_INVALID;
+  auto refuse = [&](const char* why) { ctx->err = std::string("fsi_spec_begin_wss: ") + why; return FSI_ERR_INVALID; };
+  if (ctx->part) return refuse("partitioned contexts are not supported");
+  if (nf <= 0 || !facet_cells || !facet_local || !(mu > 0.0)) return refuse("needs nf > 0 facets and mu > 0");
+  if (nf > (int64_t)2147483647 / 3) return refuse("more than 2^31 - 1 dofs on the boundary mesh");
+  if (nrows < 1 || !dofs || !comps) return refuse("needs nrows >= 1 rows, the dof and the component of each");
+  if (nrows > (int64_t)2147483647 / 2) return refuse("more than 2^30 rows");
+  if (capacity < 1) return refuse("needs a capacity >= 1 frames");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  std::vector<int32_t> kinds((size_t)ctx->C);      // as fsi_stress_begin: range and kind on the host, before anything is uploaded
+  HIPCHK(hipMemcpy(kinds.data(), ctx->cell_kind.p, (size_t)ctx->C * sizeof(int32_t), hipMemcpyDeviceToHost));
+  // the full exterior-facet mask of every boundary cell, from the whole facet list (as fsi_hemo_begin forms it)
+  std::vector<std::pair<int32_t, int32_t>> cellmask;     // (cell, mask), ascending in the cell
+  {
+    std::vector<std::pair<int32_t, int32_t>> order((size_t)nf);
+    for (int64_t f = 0; f < nf; ++f) {
+      if (facet_cells[f] < 0 || facet_cells[f] >= ctx->C || facet_local[f] < 0 || facet_local[f] > 3) return refuse("facet cell / local index out of range");
+      if (kinds[facet_cells[f]] != 0) return refuse("a facet's cell is not a fluid cell");
+      order[f] = {facet_cells[f], facet_local[f]};
+    }
+    std::sort(order.begin(), order.end());
+    for (int64_t k = 0; k < nf; ++k) {
+      if (k == 0 || order[k].first != order[k - 1].first) cellmask.push_back({order[k].first, 0});
+      if (cellmask.back().second & (1 << order[k].second)) return refuse("a facet is listed twice");
+      cellmask.back().second |= 1 << order[k].second;
+    }
+  }
+  // the touched cells in ascending order, and per cell its rows in row order: (row, 4 * local vertex + component)
+  static const int VERTS[4][3] = {{1, 2, 3}, {0, 2, 3}, {0, 1, 3}, {0, 1, 2}};
+  int64_t nmag = 0;
+  std::vector<std::pair<int32_t, int64_t>> by_cell((size_t)nrows);      // (cell, row)
+  for (int64_t r = 0; r < nrows; ++r) {
+    if (dofs[r] < 0 || dofs[r] >= 3 * nf) return refuse("dof out of range, needs 0 <= dof < 3 nf");
+    if (comps[r] < 0 || comps[r] > 3) return refuse("component out of range, needs 0 (x), 1 (y), 2 (z) or 3 (magnitude)");
+    nmag += comps[r] == 3;
+    by_cell[r] = {facet_cells[dofs[r] / 3], r};
+  }
+  std::sort(by_cell.begin(), by_cell.end());
+  std::vector<int32_t> ucell, mask, ptr, ent((size_t)(2 * nrows));
+  for (int64_t k = 0; k < nrows; ++k) {
+    const int64_t r = by_cell[k].second;
+    if (k == 0 || by_cell[k].first != by_cell[k - 1].first) {
+      const auto it = std::lower_bound(cellmask.begin(), cellmask.end(), std::make_pair(by_cell[k].first, (int32_t)0));
+      ucell.push_back(by_cell[k].first);
+      mask.push_back(it->second);
+      ptr.push_back((int32_t)k);
+    }
+    ent[2 * k] = (int32_t)r;
+    ent[2 * k + 1] = 4 * VERTS[facet_local[dofs[r] / 3]][dofs[r] % 3] + comps[r];
+  }
+  ptr.push_back((int32_t)nrows);
+  FSICHK(spec_refused(ctx, "fsi_spec_begin_wss", nrows, nrows + 2 * nmag, capacity));      // a magnitude row as in fsi_spec_room
+  auto& s = ctx->spec[FSI_SPEC_WSS];
+  s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
+  s.mode = FSI_SPEC_X;
+  s.mu = mu;
+  s.wncell = (int64_t)ucell.size();
+  s.nnode = s.nrow = s.nsamp = nrows;
+  s.capacity = capacity;
+  HIPCHK(s.wcells.alloc(ucell.size()));
+  HIPCHK(s.wmask.alloc(mask.size()));
+  HIPCHK(s.wptr.alloc(ptr.size()));
+  HIPCHK(s.went.alloc(ent.size()));
+  HIPCHK(s.hist.alloc((size_t)nrows * (size_t)capacity));
+  HIPCHK(s.work.alloc((size_t)nrows * (size_t)(capacity + 2 * BAND_MAX_PADLEN)));
+  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
+  HIPCHK(hipMemcpyAsync(s.wcells.p, ucell.data(), ucell.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(s.wmask.p, mask.data(), mask.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(s.wptr.p, ptr.data(), ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(s.went.p, ent.data(), ent.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  s.open = true;
+  return FSI_OK;
+}
+
 int fsi_spec_room(FsiCtx* ctx, int64_t rows, int32_t magnitude, int64_t capacity, double* need, double* available) {
   if (!ctx) return FSI_ERR_INVALID;
   if (rows < 1 || capacity < 1 || !need || !available) { ctx->err = "fsi_spec_room: needs rows >= 1, capacity >= 1 and both outputs"; return FSI_ERR_INVALID; }
@@ -1054,7 +1142,15 @@ int fsi_spec_sample(FsiCtx* ctx, int32_t quantity) {
   if (!ctx) return FSI_ERR_INVALID;
   auto* s = spec_session(ctx, quantity, "fsi_spec_sample");
   if (!s) return FSI_ERR_INVALID;
-  return history_sample(ctx, s, "fsi_spec_sample", "fsi_spec_begin");
+  if (quantity != FSI_SPEC_WSS) return history_sample(ctx, s, "fsi_spec_sample", "fsi_spec_begin");
+  if (s->frames >= s->capacity) { ctx->err = "fsi_spec_sample: the history is full (capacity declared at fsi_spec_begin_wss)"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  launch_spec_wss_sample(ctx->stream, s->wncell, elem_arrays(ctx), ctx->U.p, s->wcells.p, s->wmask.p, s->wptr.p, s->went.p, s->mu,
+                         s->hist.p + (size_t)s->frames * s->nrow);
+  HIPCHK(hipGetLastError());
+  s->frames += 1;
+  s->filtered = false;        // as history_sample
+  return FSI_OK;
 }
 
 int fsi_spec_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* b, const double* a, const double* zi, int32_t padlen) {

@@ -480,13 +480,17 @@ class SessionRun:
         for q in self.quantities:
             if self.device:
                 self.sessions[q] = DeviceSession(backend, self.prefix, q)
-                getattr(self.sessions[q], self.begin)(*begin_args(q), capacity)
+                self.begin_session(self.sessions[q], q, begin_args(q), capacity)
             else:
                 self.sessions[q] = host_session(q, capacity)
         if self.saved:
             folder = sessions_folder(ns["restart_folder"])
             for q in self.quantities:
                 self._read_history(folder / f"{self.file_stem}_{q}.f64", q)
+
+    def begin_session(self, session, q: str, args, capacity: int) -> None:
+        """Open the device session of ``q``: ``HipBackend.<prefix>_<begin>(q, *args, capacity)``."""
+        getattr(session, self.begin)(*args, capacity)
 
     def sample(self, t: float, state) -> None:
         """Record dvp_["n"]; ``state``: a callable giving the host copy, used only without the device session."""

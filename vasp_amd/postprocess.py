@@ -33,6 +33,11 @@ goes through its session in strips of rows after that loop, one at a time (``spe
 are sums over blocks of rows in a fixed order, carried from strip to strip, so the four CSV files are those of the unsplit
 path byte for byte; the frames are read once per strip.
 
+``--spectrogram wss`` reads the velocity; at ``save_deg 1`` its rows differ from a run's as those of ``--hemodynamics`` do.  With
+``--spectrogram-region domain`` the markers are those of the mesh that is read: ``--mesh-path`` supplies a mesh labelled for
+the purpose, as the reference intends.  The sound file of ``--spectrogram-sampling PointList`` is written by the unsplit path
+only - a list of points never needs strips.
+
 Not done: more than one rank, strips during a run, reading ``Checkpoint/sessions/*.f64`` instead of the frames, overlapping the reads with the device
 work, PNG figures.
 """
@@ -130,7 +135,7 @@ def fields_read(v: dict) -> List[str]:
         if not v.get(key):
             continue
         reads = _session_part(module, run_cls).reads
-        need.update(_session_part(module, "quantities")(v) if reads is None else reads)
+        need.update(_session_part(module, "quantities")(v) if reads is None else reads(v) if callable(reads) else reads)
     return [q for q in ("d", "v", "p") if q in need]
 
 

@@ -28,7 +28,21 @@ A history larger than the device: on a finished folder the rows go through the s
 (``vasp_amd.spectrogram_strips``); the three mean powers are sums over blocks of rows in a fixed order, so the sum is carried
 from strip to strip (``spectrogram_sum`` / ``periodogram_sum``) and the files are those of one session on all rows.
 
-Not done: ``domain`` sampling, the ``wss`` quantity, the PNG figures, ``sonify_point``.
+The wall shear stress (``--spectrogram wss``): the rows are components or magnitudes of the DG1 function on the boundary mesh
+of the fluid that ``--hemodynamics`` writes (``hemodynamics.fluid_boundary_facets``; dof 3 f + k is vertex k of facet f, at that
+vertex's coordinate), recorded on the device at every saved frame by the kernel of the hemodynamics session's arithmetic
+(``HipBackend.spec_begin_wss``, k_spec_wss_sample in csrc/fsi_hemo.hip): no second tool run and no pass over ``WSS.h5``.  The
+reference's own ``wss`` path reads a file nothing writes and keeps one entry of the vector as its magnitude
+[REF spectrograms.py:215-217,255-257; postprocessing_h5py_common.py:342-343]; the rows here are what the rest of it implies.
+The region is the dofs inside the sphere or box (``interface_only`` is ignored, as the reference takes ``sphere_ids`` alone);
+``domain`` is refused: the boundary mesh carries no cell markers.  There is no host recording path for it.
+It is a quantity where the parameters hold ``mu_f``, the viscosity it is formed with (``quantities``).
+
+``--spectrogram-region domain`` samples the cells of a marker and asks for at least one of the two sampling-domain ids.
+
+``PointList`` also writes the reference's sound file, ``<quantity>_sound_<case>.wav`` (``sonify_point``, ``sound_of``).
+
+Not done: the PNG figures.
 """
 from __future__ import annotations
 
@@ -37,13 +51,16 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
+from .hemodynamics import FACET_VERTS, fluid_boundary_facets
 from .hi_pass import DeviceSession, HostHistory, SessionRun, expected_frames, frame_spacing, frame_start, frame_times, output_nodes, restart_refusal, sha256_of
 from .mesh import FsiMesh
 
 HP_ORDER = 6                                    # filter_time_data(order=6, btype="highpass") [REF spectrograms.py:558]
 HP_PADLEN = 3 * (HP_ORDER + 1)                  # filtfilt's default for 7 coefficients
 N_CHROMA = 24                                   # [REF create_spectrograms_chromagrams.py:112]
-MIN_COLOR = {"d": -42, "v": -20, "p": -5}       # [REF spectrograms.py:133-147]
+MIN_COLOR = {"d": -42, "v": -20, "p": -5, "wss": -18}      # [REF spectrograms.py:133-150]
+FIELD_OF = {"d": "d", "v": "v", "p": "p", "wss": "v"}     # the field of dvp_["n"] a quantity's rows are formed from
+REGIONS = ("sphere", "box", "domain")
 COMPONENTS = ("all", "x", "y", "z", "mag")
 SAMPLINGS = ("RandomPoint", "PointList", "All")
 ROWS = 128                                      # csrc/fsi_spec.hpp: SPEC_ROWS
@@ -58,10 +75,16 @@ PI_L = np.longdouble("3.14159265358979323846264338327950288")
 def add_arguments(ap, coerce) -> None:
     """The ``--spectrogram*`` options of ``vasp_amd.monolithic`` (defaults: ``options``)."""
     ap.add_argument("--spectrogram", dest="spectrogram", nargs="+", default=None, metavar="Q",
-                    help="record d, v and / or p at every saved frame on the device and write the average spectrogram, "
+                    help="record d, v, p and / or wss (the wall shear stress) at every saved frame on the device and write the average spectrogram, "
                          "chromagram, SBI and power spectrum of a region to <results>/Spectrograms/ (what "
                          "vasp-create-spectrograms-chromagrams and vasp-create-spectrum write afterwards)")
-    ap.add_argument("--spectrogram-region", dest="spectrogram_region", default=None, help="sphere (default) or box")
+    ap.add_argument("--spectrogram-region", dest="spectrogram_region", default=None,
+                    help="sphere (default), box or domain (the nodes of the cells marked --spectrogram-fluid-sampling-domain-id / "
+                         "--spectrogram-solid-sampling-domain-id, of which at least one must be given; not for wss)")
+    ap.add_argument("--spectrogram-fluid-sampling-domain-id", dest="spectrogram_fluid_sampling_domain_id", type=int, default=None,
+                    help="cell marker of the fluid region that --spectrogram-region domain samples (default 1)")
+    ap.add_argument("--spectrogram-solid-sampling-domain-id", dest="spectrogram_solid_sampling_domain_id", type=int, default=None,
+                    help="cell marker of the solid region that --spectrogram-region domain samples (default 2)")
     ap.add_argument("--spectrogram-fsi-region", dest="spectrogram_fsi_region", nargs="+", type=coerce, default=None,
                     help="x y z r of the sphere, or x_min x_max y_min y_max z_min z_max of the box (default: the problem's fsi_region)")
     ap.add_argument("--spectrogram-interface-only", dest="spectrogram_interface_only", action="store_const", const=True, default=None)
@@ -77,16 +100,23 @@ def add_arguments(ap, coerce) -> None:
                     help="a parameter-free scipy.signal.get_window name (default blackmanharris)")
     ap.add_argument("--spectrogram-num-windows-per-sec", dest="spectrogram_num_windows_per_sec", type=coerce, default=None, help="default 4")
     ap.add_argument("--spectrogram-min-color", dest="spectrogram_min_color", type=coerce, default=None,
-                    help="lower clamp of the log spectrogram (default: -42 for d, -20 for v, -5 for p)")
+                    help="lower clamp of the log spectrogram (default: -42 for d, -20 for v, -5 for p, -18 for wss)")
 
 
 def quantities(v: dict) -> List[str]:
     q = v.get("spectrogram") or []
     q = [q] if isinstance(q, str) else list(q)
-    bad = [x for x in q if x not in MIN_COLOR]
+    # the wall shear stress is formed with the fluid's viscosity: it is a quantity only where the parameters hold mu_f, as
+    # those of every run and of every finished folder do
+    bad = [x for x in q if x not in MIN_COLOR or (x == "wss" and v.get("mu_f") is None)]
     if bad:
-        raise SystemExit(f"--spectrogram takes d, v and / or p, got {bad}")
-    return [x for x in ("d", "v", "p") if x in q]
+        raise SystemExit(f"--spectrogram takes d, v and / or p, and wss where the parameters hold the viscosity mu_f, got {bad}")
+    return [x for x in ("d", "v", "p", "wss") if x in q]
+
+
+def fields(v: dict) -> List[str]:
+    """The fields of dvp_["n"] the asked quantities read: the wall shear stress is formed from the velocity."""
+    return sorted({FIELD_OF[q] for q in quantities(v)})
 
 
 def options(v: dict) -> dict:
@@ -97,15 +127,26 @@ def options(v: dict) -> dict:
              sampling=str(get("sampling", "RandomPoint")), n_samples=int(get("n_samples", 1000)),
              point_ids=get("point_ids", None), seed=int(get("seed", 0)), lowcut=float(get("lowcut", 25)),
              overlap_frac=float(get("overlap_frac", 0.75)), window=str(get("window", "blackmanharris")),
-             num_windows_per_sec=get("num_windows_per_sec", 4), min_color=get("min_color", None))
-    if o["region"] not in ("sphere", "box"):
-        raise SystemExit(f"--spectrogram-region takes sphere or box, got {o['region']!r} ('domain' sampling is not built)")
+             num_windows_per_sec=get("num_windows_per_sec", 4), min_color=get("min_color", None),
+             fluid_sampling_domain_id=int(get("fluid_sampling_domain_id", 1)),        # [REF spectrograms.py:66-71]
+             solid_sampling_domain_id=int(get("solid_sampling_domain_id", 2)))
+    # domain samples the cells of a marker: which one is the user's to say - at least one of the two ids must be given (the
+    # other keeps the reference's default), since 1 and 2 by default would silently be the whole fluid or the whole solid
+    named = any(v.get("spectrogram_" + k) is not None for k in ("fluid_sampling_domain_id", "solid_sampling_domain_id"))
+    if o["region"] not in REGIONS or (o["region"] == "domain" and not named):
+        raise SystemExit(f"--spectrogram-region takes sphere or box, or domain together with --spectrogram-fluid-sampling-domain-id and / or "
+                         f"--spectrogram-solid-sampling-domain-id, got {o['region']!r}")
+    if o["region"] == "domain" and "wss" in quantities(v):
+        raise SystemExit("--spectrogram wss with --spectrogram-region domain: the boundary mesh the wall shear stress lives on carries no "
+                         "cell markers; use sphere or box")
     if o["component"] not in COMPONENTS:
         raise SystemExit(f"--spectrogram-component takes one of {', '.join(COMPONENTS)}, got {o['component']!r}")
     if o["sampling"] not in SAMPLINGS:
         raise SystemExit(f"--spectrogram-sampling takes one of {', '.join(SAMPLINGS)}, got {o['sampling']!r}")
     fr = None if o["fsi_region"] is None else [float(x) for x in np.atleast_1d(o["fsi_region"])]
-    if fr is None or len(fr) != (4 if o["region"] == "sphere" else 6):
+    if o["region"] == "domain":
+        fr = None                                 # no sphere or box cut: the markers alone [REF spectrograms.py:235-241]
+    elif fr is None or len(fr) != (4 if o["region"] == "sphere" else 6):
         raise SystemExit("--spectrogram-fsi-region takes x y z r for a sphere and x_min x_max y_min y_max z_min z_max for a box")
     o["fsi_region"] = fr
     if o["point_ids"] is not None:
@@ -390,29 +431,78 @@ def degree_of(quantity: str, save_deg: int) -> int:
 def region_ids(mesh: FsiMesh, deg: int, quantity: str, v: dict, o: dict) -> np.ndarray:
     """Ids, on the degree-``deg`` output node list, of the nodes the spectrogram of ``quantity`` may sample
     [REF spectrograms.py:221-266]: solid nodes for d, fluid nodes for v and p, the nodes the two share with
-    ``interface_only``; of those, the ones strictly inside the sphere or the open box."""
+    ``interface_only``; of those, the ones strictly inside the sphere or the open box.  Region ``domain``
+    [REF spectrograms.py:235-241, postprocessing_h5py_common.py:59-87]: the fluid and the solid nodes are those of the cells
+    whose marker equals the fluid / the solid sampling id, and nothing is cut."""
     cells = mesh.tet_nodes if deg >= 2 else mesh.tets
     coords = mesh.node_coords if deg >= 2 else mesh.coords
     as_list = lambda x: list(x) if isinstance(x, (list, tuple)) else [x]
-    fluid = np.unique(cells[np.isin(mesh.cell_markers, as_list(v["dx_f_id"]))])
-    solid = np.unique(cells[np.isin(mesh.cell_markers, as_list(v["dx_s_id"]))])
+    domain = o["region"] == "domain"
+    fluid = np.unique(cells[np.isin(mesh.cell_markers, [o["fluid_sampling_domain_id"]] if domain else as_list(v["dx_f_id"]))])
+    solid = np.unique(cells[np.isin(mesh.cell_markers, [o["solid_sampling_domain_id"]] if domain else as_list(v["dx_s_id"]))])
     if o["interface_only"]:
         ids = np.intersect1d(fluid, solid)
     else:
         ids = solid if quantity == "d" else fluid
+    if domain:
+        return ids
+    return np.intersect1d(inside_region(coords, o), ids)
+
+
+def inside_region(coords: np.ndarray, o: dict) -> np.ndarray:
+    """Indices of the points strictly inside the sphere or the open box of ``o`` [REF spectrograms.py:221-250]."""
     fr = o["fsi_region"]
     if o["region"] == "sphere":
         inside = np.where(np.linalg.norm(coords - np.array(fr[:3]), axis=1) < fr[3])[0]
     else:
         inside = np.where((coords[:, 0] > fr[0]) & (coords[:, 0] < fr[1]) & (coords[:, 1] > fr[2]) & (coords[:, 1] < fr[3])
                           & (coords[:, 2] > fr[4]) & (coords[:, 2] < fr[5]))[0]
-    return np.intersect1d(inside, ids)
+    return inside
+
+
+def viscosity(v: dict) -> float:
+    """The viscosity ``--hemodynamics`` passes: ``mu_f``, its first entry when it is a list."""
+    return float(v["mu_f"][0] if isinstance(v["mu_f"], (list, tuple)) else v["mu_f"])
+
+
+def select_wss(mesh: FsiMesh, v: dict, o: dict) -> dict:
+    """The sampled rows of the wall shear stress: ``ids``, the sampled DG1 dofs of the boundary mesh of the fluid (dof 3 f + k:
+    vertex k of facet f of ``fluid_boundary_facets``, at that vertex's coordinate), the row lists ``dofs`` / ``comps`` (0 .. 2, 3
+    the magnitude; ``all`` stacks the components component-major), the whole facet list ``facet_cells`` / ``facet_local`` and
+    ``mu``.  The region is the dofs inside the sphere or box; ``interface_only`` is ignored [REF spectrograms.py:255-257]."""
+    _, cells, local = fluid_boundary_facets(mesh, v["dx_f_id"])
+    nd = 3 * len(cells)
+    region = inside_region(mesh.coords[mesh.tets[cells[:, None], FACET_VERTS[local]].reshape(-1)], o) if nd else np.zeros(0, dtype=np.int64)
+    if len(region) == 0:
+        raise SystemExit(f"--spectrogram wss: no nodes found in the specified fsi region: {o['fsi_region']}")
+    comp = o["component"]
+    suffix = ""
+    if o["sampling"] == "RandomPoint":
+        ids = np.random.default_rng(o["seed"]).choice(region, o["n_samples"])
+        name = f"wss_{comp}_n_samples_{o['n_samples']}"
+    elif o["sampling"] == "PointList":
+        ids = np.array(o["point_ids"], dtype=np.int64)
+        if ((ids < 0) | (ids >= nd)).any():
+            raise SystemExit(f"--spectrogram-point-ids: ids must be in 0 .. {nd - 1} (the DG1 dofs of the boundary mesh of wss)")
+        name, suffix = f"wss_{comp}", f"_PointList_{o['point_ids']}"
+    else:
+        ids, name = region, f"wss_{comp}"
+    ids = np.asarray(ids, dtype=np.int64)
+    if comp == "all":
+        dofs, comps = np.tile(ids, 3), np.repeat(np.arange(3), len(ids))
+    else:
+        dofs, comps = ids, np.full(len(ids), ("x", "y", "z", "mag").index(comp))
+    return dict(ids=ids, dofs=dofs.astype(np.int32), comps=comps.astype(np.int32), facet_cells=np.asarray(cells, dtype=np.int64),
+                facet_local=np.asarray(local, dtype=np.int32), mu=viscosity(v), name=name, case_suffix=suffix, degree=None)
 
 
 def select_nodes(mesh: FsiMesh, save_deg: int, quantity: str, v: dict, o: dict) -> dict:
     """The sampled rows of one quantity: ``ids`` on the output node list, the (nodes, nodes_b) a session is opened on, and
     the two name parts of the files [REF spectrograms.py:268-287].  RandomPoint draws n_samples region nodes with
-    replacement, as the reference does, from ``numpy.random.default_rng(seed)``; All is every region node once."""
+    replacement, as the reference does, from ``numpy.random.default_rng(seed)``; All is every region node once.  The wall
+    shear stress has rows of its own (``select_wss``)."""
+    if quantity == "wss":
+        return select_wss(mesh, v, o)
     deg = degree_of(quantity, save_deg)
     region = region_ids(mesh, deg, quantity, v, o)
     if len(region) == 0:
@@ -505,6 +595,36 @@ def pipeline(session, nrows: int, n: int, T: float, start_t: float, o: dict, min
     return results(session_powers(session, tp), tp, start_t, min_color)
 
 
+def sound_of(filtered: np.ndarray):
+    """``sonify_point`` [REF spectrograms.py:817-852] on the high-passed rows, (frames, rows): every row divided by the largest
+    value of the whole matrix, the rows added in order from zero, the sum divided by their number.  ``np.max(DataFrame)``
+    means different things across pandas versions (a scalar, or a per-column reduction); the reading taken here is one
+    signed scalar maximum over all values.  None where that maximum is not finite or not > 0."""
+    x = np.asarray(filtered, dtype=np.float64)
+    m = float(np.max(x)) if x.size else float("nan")
+    if not (np.isfinite(m) and m > 0.0):
+        return None
+    y2 = np.zeros(x.shape[0])
+    for r in range(x.shape[1]):
+        y2 += x[:, r] / m
+    return y2 / x.shape[1]
+
+
+def write_sound(folder, name: str, case: str, fs: float, filtered: np.ndarray, out=print):
+    """``<name>_sound_<case>.wav``: ``scipy.io.wavfile.write(path, int(fs), y2)`` in float64, as the reference writes it; no
+    file and one line where ``sound_of`` gives none."""
+    from scipy.io import wavfile
+    y2 = sound_of(filtered)
+    if y2 is None:
+        out(f"Spectrograms: the high-passed rows of {name} have no finite maximum > 0, no sound file written")
+        return None
+    folder = Path(folder)
+    folder.mkdir(parents=True, exist_ok=True)
+    path = folder / f"{name}_sound_{case}.wav"
+    wavfile.write(path, int(fs), y2)
+    return path
+
+
 def file_names(name: str, case: str, num_windows, min_color) -> Dict[str, str]:
     """[REF create_spectrograms_chromagrams.py:192,203,214; create_spectrum.py:60]"""
     stem = f"{name}_{case}_{num_windows}_windows"
@@ -547,6 +667,8 @@ def spectrogram_refusal(v: dict, world: int, backend_cls) -> str:
             return why
     if world > 1:
         return "--spectrogram runs on one rank only (WORLD_SIZE > 1)"
+    if "wss" in quantities(v) and backend_cls is not None and not hasattr(backend_cls, "spec_begin_wss"):
+        return f"--spectrogram wss needs a backend with spec_begin_wss ({getattr(backend_cls, '__name__', backend_cls)} has none)"
     times, past = frame_times(v, SpectrogramRun.key, SpectrogramRun.words)
     frames = len(times)
     if frames < HP_PADLEN + 1:
@@ -568,14 +690,19 @@ def host_chunk(backend) -> int:
 
 class SpectrogramRun(SessionRun):
     """The driver's side of ``--spectrogram``: per quantity one session on the sampled nodes, one recorded frame per saved
-    frame, and at the end the four files.  A backend without ``spec_begin`` records and transforms on the host."""
+    frame, and at the end the four files.  A backend without ``spec_begin`` records and transforms on the host - but not
+    the wall shear stress, which is an error without ``spec_begin_wss``.  ``PointList`` also writes the sound file, in this
+    unsplit path only: a list of points never needs strips."""
     prefix, file_stem, key = "spec", "spectrogram", "spectrogram"
     option, words = "--spectrogram", "--spectrogram cannot be used with --restart-folder"
+    reads = staticmethod(fields)                    # the fields of dvp_["n"] the sessions read, from the parameters
 
     def __init__(self, backend, mesh: FsiMesh, ns: dict, open_sessions: bool = True):
         """``open_sessions`` False: everything but the sessions - the strips of ``spectrogram_strips`` open their own."""
         self.backend, self.mesh = backend, mesh
         self.quantities = quantities(ns)
+        if "wss" in self.quantities and backend is not None and not hasattr(backend, "spec_begin_wss"):
+            raise SystemExit(f"--spectrogram wss needs a backend with spec_begin_wss ({type(backend).__name__} has none)")
         self.opts = options(ns)
         self.save_deg = int(ns["save_deg"])
         self.dt_files = frame_spacing(ns)
@@ -585,14 +712,30 @@ class SpectrogramRun(SessionRun):
         self.case = str(ns.get("case") or Path(ns["results_folder"]).parent.name)     # "case": the folder that was read, where the files go elsewhere
         self.sel = {q: select_nodes(mesh, self.save_deg, q, ns, self.opts) for q in self.quantities}     # an empty region ends the run here
         if open_sessions:
-            self.open_sessions(backend, ns, lambda q: (self.sel[q]["nodes"], self.sel[q]["nodes_b"], self.opts["component"]),
+            self.open_sessions(backend, ns, self.begin_args,
                                lambda q, capacity: HostSpecSession(self.rows(q), capacity, host_chunk(backend)))
+
+    def begin_args(self, q: str, r0: int = 0, r1: Optional[int] = None):
+        """The arguments of the begin call before the capacity; of the wall shear stress: of its rows ``[r0, r1)``."""
+        sel = self.sel[q]
+        if q == "wss":
+            return sel["facet_cells"], sel["facet_local"], sel["mu"], sel["dofs"][r0:r1], sel["comps"][r0:r1]
+        return sel["nodes"], sel["nodes_b"], self.opts["component"]
+
+    def begin_session(self, session, q: str, args, capacity: int) -> None:
+        if q == "wss":                              # an entry point of its own: the quantity is in its name
+            self.backend.spec_begin_wss(*args, capacity)
+        else:
+            super().begin_session(session, q, args, capacity)
 
     def rows(self, q: str) -> int:
         return len(self.sel[q]["ids"]) * (3 if q != "p" and self.opts["component"] == "all" else 1)
 
     def fingerprint(self, q: str) -> dict:
         sel = self.sel[q]
+        if q == "wss":
+            return dict(dt_sample=self.dt_files, component=self.opts["component"], rows=self.rows(q), mu=sel["mu"],
+                        facets=sha256_of(sel["facet_cells"], sel["facet_local"]), dofs=sha256_of(sel["dofs"]), comps=sha256_of(sel["comps"]))
         return dict(save_deg=self.save_deg, dt_sample=self.dt_files, component="x" if q == "p" else self.opts["component"],
                     rows=self.rows(q), nodes=sha256_of(sel["nodes"], sel["nodes_b"]))
 
@@ -621,5 +764,11 @@ class SpectrogramRun(SessionRun):
         for q, session in self.sessions.items():
             res = pipeline(session, self.rows(q), n, T, self.start_t, self.opts, self.min_color(q))
             write_files(self.folder, self.sel[q]["name"], self.case + self.sel[q]["case_suffix"], res, self.min_color(q))
+            if self.opts["sampling"] == "PointList":      # the rows are few: fetched, and added on the host
+                hp = highpass_design(res["fs"], self.opts["lowcut"])
+                session.filter(hp["b"], hp["a"], hp["zi"], hp["padlen"])
+                filtered = np.stack([np.asarray(session.fetch(k, True)).reshape(-1) for k in range(n)])
+                session.filter()
+                write_sound(self.folder, self.sel[q]["name"], self.case + self.sel[q]["case_suffix"], res["fs"], filtered, out)
         out(f"Spectrograms of {n} frames ({', '.join(self.quantities)}; {self.opts['sampling']}, "
             f"{', '.join(str(self.rows(q)) for q in self.quantities)} rows) written to {self.folder}")

@@ -10,6 +10,9 @@ blocks one session on all rows forms, and the running sum carried from strip to 
 
 The rows of ``--spectrogram-component all`` are component-major (row = c * n + i): a strip of them can cross a component
 boundary and is opened on listed rows (``HipBackend.spec_begin_rows``).  A strip of magnitudes is a sub-list of the nodes.
+The wall shear stress is opened on listed rows from the start (``HipBackend.spec_begin_wss``): a strip is a sub-list of them.
+
+The sound file of ``--spectrogram-sampling PointList`` is not written here: a list of points never needs strips.
 
 One quantity at a time; per quantity the fewest strips of equal size whose session fits (``plan_row_strips``); the frames
 are read once per strip, only the field the quantity reads.  The log names the counts and the seconds.
@@ -90,7 +93,9 @@ class _Strip:
             self.session = sg.HostSpecSession(r1 - r0, capacity, sg.host_chunk(backend))
             return
         self.session = sg.DeviceSpecSession(backend, q)
-        if is_magnitude(run, q):
+        if q == "wss":
+            backend.spec_begin_wss(*run.begin_args(q, r0, r1), capacity)
+        elif is_magnitude(run, q):
             sel = run.sel[q]
             self.session.begin(sel["nodes"][r0:r1], None if sel["nodes_b"] is None else sel["nodes_b"][r0:r1], "mag", capacity)
         else:
@@ -122,7 +127,7 @@ def run_quantity(q: str, run: "sg.SpectrogramRun", limit: int, sample_frames: Ca
         strip = _Strip(run, q, r0, r1, capacity)
         try:
             t = tick()
-            sample_frames([q], [strip])
+            sample_frames([sg.FIELD_OF[q]], [strip])
             seconds["read"] += tick() - t
             if strip.frames != n:
                 raise SystemExit(f"--spectrogram {q} in strips: {strip.frames} frames were read, {n} were planned")
