@@ -136,6 +136,7 @@ typedef struct FsiTuning {
                                /* coupling, bit 2 every Chebyshev chain launches its last sweep (its product is read by nobody; by    */
                                /* default the chain's consumer adds the last direction to x instead: same bits, one launch less)      */
   int32_t cheb4;               /* bit 0 / 1 / 2: 4th-kind Chebyshev sweeps in the solid cycle / displacement cycle / Schur solve   */
+                               /* (bit 2 acts on the FP16 / FP32-matrix Schur sweeps only: the all-FP64 fused sweeps ignore it)    */
   int32_t coarse_power;        /* 1: coarse-level Chebyshev intervals from a power iteration (0: Gershgorin bound)                 */
   int32_t solid_mg, dd_mg;     /* two-level (P2 -> P1) cycles of the solid velocity block / the displacement block                 */
   int32_t mg_keep;             /* 1: keep the displacement block's coarse operator while three checksums say it is unchanged       */

@@ -22,6 +22,30 @@ EXPERIMENT_ALL_SWEEPS = 4          # FsiTuning.experiment bit 2: every chain lau
 # count them: fluid predictor + solid cycle, Schur complement, displacement cycle
 DROPPED_PER_APPLICATION = (2, 1, 1)
 
+# FsiTuning variants of the whole-application test, applied to both contexts: every branch of precondition_block that a
+# tuning field selects.  "one_sweep": chains of one sweep, of which nothing is launched - the consumer adds the first direction.
+VARIANTS = {
+    "default": {}, "prec_streams=0": dict(prec_streams=0), "tiles=0": dict(tiles=0), "fused_sweeps=0": dict(fused_sweeps=0),
+    "solid_mg=0": dict(solid_mg=0), "solid_fused=0": dict(solid_fused=0), "solid_block_jacobi=0": dict(solid_block_jacobi=0),
+    "solid_fp32=0": dict(solid_fp32=0), "solid_coarse_exact=0": dict(solid_coarse_exact=0), "dd_mg=0": dict(dd_mg=0),
+    "scalar_dd=0": dict(scalar_dd=0), "sweeps_fp32=0": dict(sweeps_fp32=0), "cheb4=7": dict(cheb4=7), "pv_fp32=0": dict(pv_fp32=0),
+    "sbmg_post=0": dict(sbmg_post=0), "experiment=1": dict(experiment=1), "experiment=2": dict(experiment=2),
+    "one_sweep": dict(solid_mg=0, dd_mg=0, its_solid=1, its_fluid=1, its_schur=1, its_disp=1),
+}
+
+
+def dropped_per_application(variant: str, storage: str):
+    """DROPPED_PER_APPLICATION of a variant: a chain that runs through the unfused FP64 solve (cheb_solve_op) launches every
+    sweep.  solid_fp32=0: the solid predictor; sweeps_fp32=0: the fluid predictor and the displacement block; fused_sweeps=0
+    with FP64 Schur values (the FP64 storage mode): the Schur solve."""
+    if variant == "solid_fp32=0":
+        return (1, 1, 1)
+    if variant == "sweeps_fp32=0":
+        return (1, 1, 0)
+    if variant == "fused_sweeps=0" and storage == "fp64":
+        return (2, 0, 1)
+    return DROPPED_PER_APPLICATION
+
 
 def load():
     """the shim with the signatures of the x + d entry points set (ks.call then runs them)"""

@@ -39,7 +39,7 @@ _SIGS = {
     "shim_spmv_sb": "lppppp", "shim_sweep_sb_b3": "lppppffppppi", "shim_sweep_sb_h": "lpppffpppp",
     "shim_cheb_init_b3": "lppfppp", "shim_cheb_step_b3": "lppffppp",
     "shim_sweep_csr_f64": "lppppddpppp", "shim_sweep_csr_mixed": "lpppppddpppp", "shim_sweep_schur_tiled": "ilipppppddpppp",
-    "shim_ctx_info": "ppi", "shim_ctx_array": "psppp", "shim_tile_limit": "",
+    "shim_ctx_info": "ppi", "shim_ctx_array": "psppp", "shim_tile_limit": "", "shim_cheb_coefficients": "ddiippp",
     "shim_expand_cols": "llpppppppp", "shim_spmv": "lpppplpi", "shim_spmv_node6": "llpppppplppp", "shim_drows_extract": "lpppppp",
     "shim_pad_cols32": "lpppp", "shim_pad_vals32": "llppplllpli", "shim_spmv_node6p": "llppplpplppplppp",
     "shim_matrix_finish": "lppppplpp", "shim_ctx_spmv": "pippp",

@@ -74,6 +74,40 @@ def test_tile_limit_is_the_librarys():
     assert ks.load().shim_tile_limit() == ks.TILE_LIMIT
 
 
+@pytest.mark.parametrize("fourth", [0, 1])
+@pytest.mark.parametrize("lmax,kappa", [(1.7, 30.0), (2.3841, 4.0), (0.93, 1000.0)])
+def test_chebyshev_schedule_keeps_the_coefficients(lmax, kappa, fourth):
+    """fsi_cheb.hpp against the formulas of the preconditioner before it had one schedule, restated in float64: the
+    float32 coefficients the sweep kernels take, and init(), bit for bit; after restart() the schedule starts again"""
+    n = 40
+    c1, c2, init = np.zeros(2 * n), np.zeros(2 * n), np.zeros(1)
+    ks.call("shim_cheb_coefficients", lmax, kappa, fourth, n, c1, c2, init)
+    lmax, kappa = np.float64(lmax), np.float64(kappa)
+    w1, w2 = np.zeros(n), np.zeros(n)
+    if fourth:
+        winit = np.float64(4.0) / (np.float64(3.0) * lmax)
+        for k in range(n):
+            i = np.float64(k + 1)
+            w1[k] = (2.0 * i - 1.0) / (2.0 * i + 3.0)
+            w2[k] = (8.0 * i + 4.0) / ((2.0 * i + 3.0) * lmax)
+    else:
+        lmin = lmax / kappa
+        th, de = 0.5 * (lmax + lmin), 0.5 * (lmax - lmin)
+        sig = th / de
+        rho = 1.0 / sig
+        winit = 1.0 / th
+        for k in range(n):
+            rn = 1.0 / (2.0 * sig - rho)
+            w1[k], w2[k] = rn * rho, 2.0 * rn / de
+            rho = rn
+    assert init[0].tobytes() == np.float64(winit).tobytes()
+    for got, want, what in ((c1, w1, "c1"), (c2, w2, "c2")):
+        assert np.array_equal(got[:n].view(np.uint64), want.view(np.uint64)), what
+        assert np.array_equal(got[:n].astype(np.float32).view(np.uint32), want.astype(np.float32).view(np.uint32)), what
+        assert np.array_equal(got[n:].view(np.uint64), got[:n].view(np.uint64)), f"{what} after restart()"
+    assert np.all(np.isfinite(c1)) and np.all(c2 > 0) and c1[0] != c1[1]      # (a schedule that moves: the restart is seen)
+
+
 # ---- the monolithic matrix's references (tests/test_gpu_product_kernels.py) ---------------------------------------------------
 def small_mono(N2, V, seed, **kw):
     rng = np.random.default_rng(seed)

@@ -69,6 +69,47 @@ struct PhaseTimer {
   int64_t issued = 0, resolved = 0;          // pairs recorded / pairs already added to ms
 };
 
+// One family of sweep launches whose durations are sampled with event pairs: begin / end bracket one launch, flush waits
+// for the pairs of an application and adds them to t.  The pending count is the next free pair.
+struct SweepSamples {
+  static constexpr int MAX = 8;
+  explicit SweepSamples(int cap_) : cap(cap_) {}
+  int cap;                                   // pairs of one application
+  hipEvent_t ev0[MAX] = {}, ev1[MAX] = {};
+  int pending = 0;
+  bool open = false;
+  PhaseTimer t;                              // ms and calls only
+  hipError_t create() {
+    for (int k = 0; k < cap; ++k) {
+      hipError_t e = hipEventCreate(&ev0[k]);
+      if (e == hipSuccess) e = hipEventCreate(&ev1[k]);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  void destroy() {
+    for (int k = 0; k < MAX; ++k) { if (ev0[k]) (void)hipEventDestroy(ev0[k]); if (ev1[k]) (void)hipEventDestroy(ev1[k]); ev0[k] = ev1[k] = nullptr; }
+  }
+  // on: the caller's rule (the application is sampled, and this launch is one of the chain's first); nothing is sampled
+  // without the events or beyond cap pending pairs
+  void begin(hipStream_t st, bool on) {
+    open = on && ev0[0] && pending < cap;
+    if (open) (void)hipEventRecord(ev0[pending], st);
+  }
+  void end(hipStream_t st) {
+    if (open) { (void)hipEventRecord(ev1[pending], st); pending += 1; open = false; }
+  }
+  void flush() {
+    if (pending <= 0) return;
+    (void)hipEventSynchronize(ev1[pending - 1]);
+    for (int k = 0; k < pending; ++k) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, ev0[k], ev1[k]) == hipSuccess) { t.ms += ms; t.calls += 1; }
+    }
+    pending = 0;
+  }
+};
+
 }  // namespace fsi
 
 struct FsiCtx {
@@ -357,18 +398,10 @@ struct FsiCtx {
   double newton_forcing = 1e-2;              // inexact Newton: linear tolerance = forcing * atol / |b| (FSI_NEWTON_FORCING; 1e-2: same Newton counts as 1e-3 on the bench, 18 % fewer Krylov iterations)
 
   // timers
-  fsi::PhaseTimer t_res, t_jac, t_fac, t_spmv, t_prec, t_ortho, t_flush, t_kry, t_ss;
-  fsi::PhaseTimer t_sch;                     // sampled Schur-complement sweeps
-  hipEvent_t sch_ev0[4] = {}, sch_ev1[4] = {};
-  int sch_samples_pending = 0;
-  hipEvent_t ss_ev0[8] = {}, ss_ev1[8] = {};
-  int ss_samples_pending = 0;
-  fsi::PhaseTimer t_db;
-  hipEvent_t db_ev0[8] = {}, db_ev1[8] = {};
-  int db_samples_pending = 0;
-  fsi::PhaseTimer t_sc;
-  hipEvent_t sc_ev0[4] = {}, sc_ev1[4] = {};
-  int sc_samples_pending = 0;
+  fsi::PhaseTimer t_res, t_jac, t_fac, t_spmv, t_prec, t_ortho, t_flush, t_kry;
+  // sampled launch durations inside precondition_block, at most `cap` launches of an application each: the solid-block
+  // product, the FP32 component-diagonal product, the scalar-ratio displacement product, the Schur-complement sweeps
+  fsi::SweepSamples smp_ss{8}, smp_db{8}, smp_sc{4}, smp_sch{4};
   int64_t kry_iters = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   int sample_budget = 0;                     // preconditioner applications whose sweep kernels are still sampled with events

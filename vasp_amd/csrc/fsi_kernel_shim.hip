@@ -8,6 +8,7 @@
 // the launch refused its arguments and launched nothing; the outputs are still copied back).
 //
 // Vectors of the node-block sweeps are float4 per node (component 3 is padding), as the preconditioner holds them.
+#include "fsi_cheb.hpp"
 #include "fsi_host.hpp"
 #include "fsi_kernels.hpp"
 
@@ -479,6 +480,18 @@ int shim_sweep_schur_tiled_f64(int tile_rows, int64_t n, int max_nu, const int64
 }
 
 int shim_tile_limit() { return tile_limit(); }
+
+// The preconditioner's Chebyshev schedule (fsi_cheb.hpp), host only: init() and 2 n coefficient pairs - n from a new
+// generator, then n more after restart()
+int shim_cheb_coefficients(double lmax, double kappa, int fourth, int n, double* c1, double* c2, double* init) {
+  ChebSchedule gen(lmax, kappa, fourth != 0);
+  *init = gen.init();
+  for (int k = 0; k < 2 * n; ++k) {
+    if (k == n) gen.restart();
+    gen.next(&c1[k], &c2[k]);
+  }
+  return 0;
+}
 
 // ---- fsi_solver.hip: the monolithic matrix's structure and products -----------------------------------------------------------
 // Node graph: nadj_ptr [N2 + 1], nadj [npairs = nadj_ptr[N2]]; pressure graph: padj_ptr [N2 + 1], padj [padj_ptr[N2]]; vrank [V];

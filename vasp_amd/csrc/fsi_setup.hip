@@ -543,10 +543,7 @@ static int build_solid_blocks(FsiCtx* ctx, const FsiMeshDesc* mesh, Setup& s) {
   FSICHK(upload(ctx, ctx->ss_cols, ss_cols));
   FSICHK(upload(ctx, ctx->ss_src, ss_src));
   HIPCHK(ctx->ss_vals.alloc(ss_cols.size()));
-  for (int k = 0; k < 8; ++k) { HIPCHK(hipEventCreate(&ctx->ss_ev0[k])); HIPCHK(hipEventCreate(&ctx->ss_ev1[k])); }
-  for (int k = 0; k < 8; ++k) { HIPCHK(hipEventCreate(&ctx->db_ev0[k])); HIPCHK(hipEventCreate(&ctx->db_ev1[k])); }
-  for (int k = 0; k < 4; ++k) { HIPCHK(hipEventCreate(&ctx->sc_ev0[k])); HIPCHK(hipEventCreate(&ctx->sc_ev1[k])); }
-  for (int k = 0; k < 4; ++k) { HIPCHK(hipEventCreate(&ctx->sch_ev0[k])); HIPCHK(hipEventCreate(&ctx->sch_ev1[k])); }
+  for (SweepSamples* s : {&ctx->smp_ss, &ctx->smp_db, &ctx->smp_sc, &ctx->smp_sch}) HIPCHK(s->create());
   FSICHK(upload(ctx, ctx->mask_s, ms));
   FSICHK(upload(ctx, ctx->mask_f, mf));
   return FSI_OK;
@@ -851,9 +848,8 @@ FsiCtx::~FsiCtx() {
   rccl_destroy(this);
   bcr_free(this);
   auto drop = [](hipEvent_t* e, int n) { for (int k = 0; k < n; ++k) if (e[k]) (void)hipEventDestroy(e[k]); };
-  for (hipEvent_t* e : {ss_ev0, ss_ev1, db_ev0, db_ev1}) drop(e, 8);
-  for (hipEvent_t* e : {sc_ev0, sc_ev1, sch_ev0, sch_ev1}) drop(e, 4);
-  for (PhaseTimer* t : {&t_res, &t_jac, &t_fac, &t_spmv, &t_prec, &t_ortho, &t_flush, &t_kry, &t_ss, &t_db, &t_sc}) { drop(t->e0, PhaseTimer::RING); drop(t->e1, PhaseTimer::RING); }
+  for (SweepSamples* s : {&smp_ss, &smp_db, &smp_sc, &smp_sch}) s->destroy();
+  for (PhaseTimer* t : {&t_res, &t_jac, &t_fac, &t_spmv, &t_prec, &t_ortho, &t_flush, &t_kry}) { drop(t->e0, PhaseTimer::RING); drop(t->e1, PhaseTimer::RING); }
   for (hipEvent_t* e : {&ev0, &ev1, &ev_split, &ev_solid, &ev_b}) drop(e, 1);
   if (stream2) (void)hipStreamDestroy(stream2);
   if (stream) (void)hipStreamDestroy(stream);
