@@ -454,6 +454,37 @@ int fsi_band_filter_next(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const dou
  * window, "valid")) centred by (window - 1) / 2 frames, zero outside; window = 0: the filtered series itself (the reference's
  * low-pass case).  window may not exceed the number of frames. */
 int fsi_band_amplitude(FsiCtx* ctx, int32_t quantity, int32_t window);
+/* Replaces: compute_tke [REF src/vasp/postprocessing/log_plotter.py:928-989], which the reference applies to the probe points
+ * of a log file: the phase-averaged (Reynolds) decomposition of every row of the session over the selected frames
+ * (fsi_band_select sets the cycle range), n = C * period of them, C cycles of `period` frames.  With x[k] selected frame k:
+ *   mean[j]  = (((+0.0 + x[j]) + x[period + j]) + ...) / C     for j < period, a true division;
+ *   fluct[k] = x[k] - mean[k % period],
+ * the reference's operations in its order, bit for bit.  The fluctuation becomes the session's filtered series of n frames
+ * (padlen 0): fsi_band_fetch(FSI_BAND_FILTERED), fsi_band_trace(FSI_BAND_FILTERED), fsi_band_amplitude and the amplitude
+ * fetches serve it - the windowed RMS of u' is the turbulence intensity.  The raw history is kept.  Needs period >= 1 and a
+ * selected count that is a positive multiple of it, else FSI_ERR_INVALID naming both numbers.  The `period` frames of the
+ * mean are an allocation of their own, 8 * period * rows bytes, under the room rule of fsi_band_begin: FSI_ERR_INVALID with
+ * both byte counts when they do not fit beside the context's 1/16 of the device; nothing is paged (fsi_band_room does not
+ * count them).  A refused call leaves the session as it was.  fsi_band_sample, _import, _select, _filter and _filter_next
+ * invalidate the phase average and free the mean; fsi_band_end and fsi_destroy free it.  For d, v, p and, by rows, for the
+ * two tensor quantities.  Not for partitioned contexts. */
+int fsi_band_phase(FsiCtx* ctx, int32_t quantity, int64_t period);
+#define FSI_PHASE_MEAN 0
+#define FSI_PHASE_ENERGY 1
+#define FSI_PHASE_ENERGY_CYCLE_MEAN 2
+#define FSI_PHASE_ENERGY_TIME_MEAN 3
+/* Replaces: the rest of compute_tke, 0.5 * (fx^2 + fy^2 + fz^2) [REF .../log_plotter.py:981-987], and
+ * compute_average_over_cycles of it [REF .../log_plotter.py:902-925], for every node of the session after fsi_band_phase:
+ *   FSI_PHASE_MEAN               frame < period: out[n][ncomp], the mean of phase `frame`;
+ *   FSI_PHASE_ENERGY             frame < the selected count: out[n], e = 0.5 * ((fx fx + fy fy) + fz fz) of fluctuation frame
+ *                                `frame` (for p 0.5 * (f f)), formed when fetched - no nodes x frames array is allocated;
+ *   FSI_PHASE_ENERGY_CYCLE_MEAN  frame < period: out[n], the sum over the cycles c in order of e[c * period + frame], from
+ *                                +0.0, divided by C (compute_average_over_cycles);
+ *   FSI_PHASE_ENERGY_TIME_MEAN   frame == 0: out[n], the sum over all selected frames in order of e, from +0.0, divided by
+ *                                their count (numpy.mean over the frames).
+ * The three energies are refused for the tensor quantities (ncomp 6).  FSI_ERR_INVALID "no phase average (fsi_band_phase
+ * first)" without one, for a frame out of range, a null out and a partitioned context. */
+int fsi_band_phase_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, double* out);
 /* Replaces: the "Saving data" loops of create_hi_pass_viz [REF .../create_hi_pass_viz.py:233-245,327-341,377-390]: one frame
  * of the raw history, the filtered series or its amplitude (out[n][ncomp]), or of the amplitude's magnitude over the
  * components (out[n]; for p the amplitude itself).  For the last two, max_out / argmax_out (nullable) receive the largest

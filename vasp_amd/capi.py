@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_set_frame", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_begin_rows", "fsi_spec_begin_wss", "fsi_spec_room", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_spectrogram_sum", "fsi_spec_periodogram_sum", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_phase", "fsi_band_phase_fetch", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_begin_rows", "fsi_spec_begin_wss", "fsi_spec_room", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_spectrogram_sum", "fsi_spec_periodogram_sum", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -166,6 +166,8 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_band_sample.argtypes = [vp, i32]
     lib.fsi_band_filter.argtypes = [vp, i32, i32, vp, vp, vp, i32]
     lib.fsi_band_amplitude.argtypes = [vp, i32, i32]
+    lib.fsi_band_phase.argtypes = [vp, i32, i64]
+    lib.fsi_band_phase_fetch.argtypes = [vp, i32, i32, i64, vp]
     lib.fsi_band_fetch.argtypes = [vp, i32, i32, i64, vp, C.POINTER(dbl), C.POINTER(i64)]
     lib.fsi_band_select.argtypes = [vp, i32, i64, i64, i64]
     lib.fsi_band_filter_next.argtypes = [vp, i32, i32, vp, vp, vp, i32]
@@ -676,6 +678,23 @@ class HipBackend:
         """Select the amplitude of the filtered series (fsi_band_amplitude): flat-window RMS over ``window`` frames, or the
         series itself with ``window`` 0."""
         self._check(self.lib.fsi_band_amplitude(self.ctx, self.BAND_QUANTITY[quantity], int(window)))
+
+    PHASE_WHAT = {"mean": 0, "energy": 1, "energy_cycle_mean": 2, "energy_time_mean": 3}
+
+    def hi_pass_phase(self, quantity: str, period: int) -> None:
+        """The phase-averaged decomposition of the selected frames, whole cycles of ``period`` frames (fsi_band_phase): the
+        fluctuation about the mean over the cycles becomes the filtered series - 'filtered' and 'amplitude' fetches and a
+        'filtered' trace serve it -, the means and the fluctuation's energy come from ``hi_pass_phase_fetch``."""
+        self._check(self.lib.fsi_band_phase(self.ctx, self.BAND_QUANTITY[quantity], int(period)))
+
+    def hi_pass_phase_fetch(self, quantity: str, what: str, frame: int = 0) -> np.ndarray:
+        """After ``hi_pass_phase``: 'mean' of phase ``frame`` as (n, ncomp); 'energy' 0.5 |u'|^2 of fluctuation frame
+        ``frame``, 'energy_cycle_mean' its mean over the cycles at phase ``frame``, 'energy_time_mean' its mean over all
+        selected frames (``frame`` 0), each as (n,) (fsi_band_phase_fetch)."""
+        n, ncomp = self._band_shape[quantity]
+        out = np.empty((n, ncomp)) if what == "mean" else np.empty(n)
+        self._check(self.lib.fsi_band_phase_fetch(self.ctx, self.BAND_QUANTITY[quantity], self.PHASE_WHAT[what], int(frame), _ptr(out)))
+        return out
 
     def hi_pass_fetch(self, quantity: str, what: str, frame: int, with_max: bool = False):
         """One frame 'raw', 'filtered' or 'amplitude' as (n, ncomp), or 'magnitude' as (n,) (fsi_band_fetch); with

@@ -463,11 +463,16 @@ struct FsiCtx {
     // sel_stride, ..., sel_count of them; sel_count < 0: every recorded frame.  A raw fetch keeps absolute frame indices.
     int64_t sel_first = 0, sel_stride = 1, sel_count = -1;
     int64_t board_node0 = -1;                // >= 0: a fetched amplitude's magnitudes also go to board[frame][board_node0 ..)
-    fsi::DevBuf<double> acc, amp, mag, part_val;
+    // > 0: the filtered series is the fluctuation about the phase average of this period (fsi_band_phase) and phase_mean
+    // holds the period's mean frames [phase_period][nrow], an allocation of their own; 0: no phase average
+    int64_t phase_period = 0;
+    fsi::DevBuf<double> acc, amp, mag, part_val, phase_mean;
     fsi::DevBuf<int64_t> part_idx;
+    void phase_release() { phase_mean.release(); phase_period = 0; }
     void release() {
       History::release();
       acc.release(); amp.release(); mag.release(); part_val.release(); part_idx.release();
+      phase_release();
       ncomp = 0; window = -1; acc_start = -1;
       sel_first = 0; sel_stride = 1; sel_count = -1;
       board_node0 = -1;

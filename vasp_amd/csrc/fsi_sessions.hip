@@ -1,8 +1,9 @@
 // C-ABI of libvaspfsi.so (include/vaspfsi.h): the post-processing sessions that live on the resident state over a run -
 // hemodynamic indices (fsi_hemo_*), solid stress / strain (fsi_stress_*), band-pass filtered fields (fsi_band_*) and
-// spectrograms (fsi_spec_*).  The arithmetic runs in the kernels of fsi_hemo / fsi_stress / fsi_band / fsi_spec .hip; the
+// spectrograms (fsi_spec_*).  The arithmetic runs in the kernels of fsi_hemo / fsi_stress / fsi_band / fsi_phase / fsi_spec .hip; the
 // last two families record into one kind of history (FsiCtx::History) through the helpers below.
 #include "fsi_host.hpp"
+#include "fsi_phase.hpp"
 #include "fsi_spec.hpp"
 
 using namespace fsi;
@@ -748,6 +749,7 @@ int fsi_band_sample(FsiCtx* ctx, int32_t quantity) {
   } else
     FSICHK(history_sample(ctx, s, "fsi_band_sample", "fsi_band_begin"));
   s->window = -1;
+  s->phase_release();           // a phase average covers the frames it was formed on
   s->sel_first = 0; s->sel_stride = 1; s->sel_count = -1;      // a selection covers the frames it was made on
   return FSI_OK;
 }
@@ -766,6 +768,7 @@ int fsi_band_select(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count,
   s->sel_stride = stride;
   s->sel_count = count == -1 ? (s->frames - 1 - first) / stride + 1 : count;
   s->filtered = false;
+  s->phase_release();
   s->window = -1;
   s->acc_start = -1;
   return FSI_OK;
@@ -776,6 +779,7 @@ int fsi_band_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* 
   auto* s = band_session(ctx, quantity, "fsi_band_filter");
   if (!s) return FSI_ERR_INVALID;
   FSICHK(history_filter(ctx, s, "fsi_band_filter", "2 .. 11", ntaps, b, a, zi, padlen, s->sel_first, s->sel_stride, band_frames(s)));
+  s->phase_release();           // the filtered series is the band again
   s->window = -1;
   s->acc_start = -1;
   return FSI_OK;
@@ -800,6 +804,87 @@ int fsi_band_filter_next(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const dou
   s->padlen = padlen;
   s->window = -1;
   s->acc_start = -1;
+  s->phase_release();           // the series is no longer the fluctuation about the mean
+  return FSI_OK;
+}
+
+int fsi_band_phase(FsiCtx* ctx, int32_t quantity, int64_t period) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_phase")) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_phase");
+  if (!s) return FSI_ERR_INVALID;
+  const int64_t n = band_frames(s);
+  if (period < 1 || n < 1 || n % period != 0) {
+    ctx->err = "fsi_band_phase: period = " + std::to_string(period) + " frames, " + std::to_string(n) +
+               " selected frames: needs period >= 1 and a selected count that is a positive multiple of it (fsi_band_select)";
+    return FSI_ERR_INVALID;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  // the period's mean frames are an allocation of their own, under the room rule of the begin calls; the mean frames of an
+  // earlier call are given back first where they are of another size (they count as taken otherwise)
+  const size_t count = (size_t)period * (size_t)s->nrow;
+  if (s->phase_mean.n != count) {
+    Room room;
+    FSICHK(device_room(ctx, &room));
+    const double need_d = 8.0 * (double)period * (double)s->nrow, avail = (double)room.free_b + 8.0 * (double)s->phase_mean.n - room.reserve;
+    if (need_d > avail) {
+      char msg[320];
+      snprintf(msg, sizeof msg, "fsi_band_phase: the phase means need %.0f bytes (%lld rows x %lld frames), the device has %zu bytes free of which "
+               "%.0f stay with the context", need_d, (long long)s->nrow, (long long)period, room.free_b, room.reserve);
+      ctx->err = msg;
+      return FSI_ERR_INVALID;
+    }
+    s->phase_period = 0;
+    HIPCHK(s->phase_mean.alloc(count));
+    HIPCHK(hipDeviceSynchronize());                                // the allocation's own fill is done
+  }
+  launch_phase_decompose(ctx->stream, s->nrow, period, n / period, s->hist.p + (size_t)s->sel_first * s->nrow, s->sel_stride,
+                         s->phase_mean.p, s->work.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  s->padlen = 0;                // the fluctuation is the filtered series, without guard frames
+  s->filtered = true;
+  s->phase_period = period;
+  s->window = -1;
+  s->acc_start = -1;
+  return FSI_OK;
+}
+
+int fsi_band_phase_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, double* out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_phase_fetch")) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_phase_fetch");
+  if (!s) return FSI_ERR_INVALID;
+  if (what < FSI_PHASE_MEAN || what > FSI_PHASE_ENERGY_TIME_MEAN) {
+    ctx->err = "fsi_band_phase_fetch: what must be FSI_PHASE_MEAN .. FSI_PHASE_ENERGY_TIME_MEAN";
+    return FSI_ERR_INVALID;
+  }
+  if (!out) { ctx->err = "fsi_band_phase_fetch: out is NULL"; return FSI_ERR_INVALID; }
+  if (s->phase_period < 1 || !s->filtered) { ctx->err = "fsi_band_phase_fetch: no phase average (fsi_band_phase first)"; return FSI_ERR_INVALID; }
+  if (what != FSI_PHASE_MEAN && s->ncomp != 1 && s->ncomp != 3) {
+    ctx->err = "fsi_band_phase_fetch: a strain / stress session has no energy: 0.5 |u'|^2 is that of a vector or a scalar";
+    return FSI_ERR_INVALID;
+  }
+  const int64_t P = s->phase_period, n = band_frames(s);
+  const int64_t limit = what == FSI_PHASE_ENERGY ? n : what == FSI_PHASE_ENERGY_TIME_MEAN ? 1 : P;
+  if (frame < 0 || frame >= limit) {
+    ctx->err = "fsi_band_phase_fetch: frame " + std::to_string(frame) + " out of range, this kind has " + std::to_string(limit);
+    return FSI_ERR_INVALID;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  const double* src = nullptr;
+  if (what == FSI_PHASE_MEAN) src = s->phase_mean.p + (size_t)frame * s->nrow;
+  else {
+    const double* f = history_frame(s, true, frame);
+    if (what == FSI_PHASE_ENERGY) launch_phase_energy(ctx->stream, s->nnode, s->ncomp, f, 0, 1, false, s->mag.p);
+    else if (what == FSI_PHASE_ENERGY_CYCLE_MEAN) launch_phase_energy(ctx->stream, s->nnode, s->ncomp, f, P * s->nrow, n / P, true, s->mag.p);
+    else launch_phase_energy(ctx->stream, s->nnode, s->ncomp, f, s->nrow, n, true, s->mag.p);
+    HIPCHK(hipGetLastError());
+    src = s->mag.p;
+  }
+  HIPCHK(hipMemcpyAsync(out, src, (size_t)(what == FSI_PHASE_MEAN ? s->nrow : s->nnode) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
   return FSI_OK;
 }
 
@@ -917,6 +1002,7 @@ int fsi_band_import(FsiCtx* ctx, int32_t quantity, int64_t count, const double* 
   FSICHK(history_import(ctx, s, "fsi_band_import", count, frames));
   s->window = -1;
   s->sel_first = 0; s->sel_stride = 1; s->sel_count = -1;      // as fsi_band_sample: a selection covers the frames it was made on
+  s->phase_release();
   return FSI_OK;
 }
 

@@ -14,6 +14,10 @@ This module holds
   ``--hi-pass-multiband`` one more that went through all bands in order, each passed or stopped
   [REF create_hi_pass_viz.py:532-545,191-198,651-657]; a frame window and stride (``--hi-pass-stride``,
   ``--hi-pass-start-time``, ``--hi-pass-end-time``); the raw series of listed nodes (``--hi-pass-point-ids``);
+* the phase-averaged decomposition of ``--hi-pass-phase-average`` - what the reference's ``vasp-log-plotter`` forms at probe
+  points [REF log_plotter.py:902-989], here per written node (csrc/fsi_phase.hip): its NumPy twin (``phase_average``,
+  ``fluctuation_energy``, ``ordered_mean``, ``HostBandSession.phase`` / ``phase_fetch``), the period arithmetic with its
+  refusals (``phase_cycle``, ``phase_period``, ``phase_cycles``) and its files (``HiPassRun._write_phase``);
 * what the four post-processing options share to go through a checkpoint: the manifest and the files of
   ``<results>/Checkpoint/sessions/`` and the checks of a restart (``save_sessions``, ``restart_entry``), and the saving and
   restoring of a recorded history (``SessionRun``);
@@ -203,6 +207,46 @@ def amplitude_magnitude(amp: np.ndarray) -> np.ndarray:
     return np.sqrt((amp[:, 0] * amp[:, 0] + amp[:, 1] * amp[:, 1]) + amp[:, 2] * amp[:, 2])
 
 
+def phase_average(x: np.ndarray, period: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(mean, fluctuation) of whole cycles of ``period`` frames of a frame-major array, as compute_tke forms them
+    [REF log_plotter.py:928-989]: ``mean[j] = (((+0.0 + x[j]) + x[period + j]) + ...) / cycles`` - the sum over the cycles in
+    cycle order, then a true division - and ``fluctuation[k] = x[k] - mean[k % period]``.  What csrc/fsi_phase.hip computes."""
+    x = np.asarray(x, dtype=np.float64)
+    period = int(period)
+    cycles = len(x) // period if period >= 1 else 0
+    if period < 1 or cycles < 1 or cycles * period != len(x):
+        raise RuntimeError(f"hi-pass phase: period = {period} frames, {len(x)} selected frames: needs period >= 1 and a selected "
+                           "count that is a positive multiple of it")
+    with np.errstate(invalid="ignore", over="ignore"):      # an inf in a row makes its mean inf and its fluctuation NaN, quietly
+        s = np.zeros(x[:period].shape)
+        for c in range(cycles):
+            s = s + x[c * period:(c + 1) * period]
+        mean = s / float(cycles)
+        return mean, (x.reshape((cycles, period) + x.shape[1:]) - mean[None]).reshape(x.shape)
+
+
+def fluctuation_energy(f: np.ndarray) -> np.ndarray:
+    """``0.5 * ((fx fx + fy fy) + fz fz)`` per node of (..., nodes, 3) fluctuations [REF log_plotter.py:981-987]; of a scalar
+    (..., nodes, 1) ``0.5 * (f f)``."""
+    f = np.asarray(f, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if f.shape[-1] == 3:
+            return 0.5 * ((f[..., 0] * f[..., 0] + f[..., 1] * f[..., 1]) + f[..., 2] * f[..., 2])
+        if f.shape[-1] == 1:
+            return 0.5 * (f[..., 0] * f[..., 0])
+    raise RuntimeError("hi-pass phase_fetch: a strain / stress session has no energy: 0.5 |u'|^2 is that of a vector or a scalar")
+
+
+def ordered_mean(e: np.ndarray) -> np.ndarray:
+    """The sum over axis 0 in order, from +0.0, divided by the count: compute_average_over_cycles [REF log_plotter.py:902-925]
+    of cycles stacked along axis 0, and ``numpy.mean(axis=0)`` of frames."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = np.zeros(e.shape[1:])
+        for row in e:
+            s = s + row
+        return s / float(len(e))
+
+
 def pass_stop_list(band_list, words=None) -> List[str]:
     """"pass" or "stop" per band of a multiband cascade: the reference's rule - a band wider than 1000 Hz passes, a narrower
     one is stopped [REF create_hi_pass_viz.py:541-545] - or the words given (``--hi-pass-pass-stop``)."""
@@ -269,10 +313,12 @@ class HostBandSession(HostHistory):
         super().__init__((-1, ncomp), capacity)
         self.ncomp, self.amp, self.view = ncomp, None, slice(None)
         self.board, self.board_node0 = None, -1
+        self.phase_mean, self.phase_period = None, 0
 
     def sample(self, frame: np.ndarray) -> None:
         super().sample(frame)
         self.amp, self.view = None, slice(None)
+        self.phase_mean, self.phase_period = None, 0
 
     def selected(self) -> np.ndarray:
         return np.stack(self.raw)[self.view]
@@ -286,17 +332,43 @@ class HostBandSession(HostHistory):
         count = (frames - 1 - first) // stride + 1 if count == -1 else count
         self.view = slice(first, first + (count - 1) * stride + 1, stride)
         self.filtered = self.amp = None
+        self.phase_mean, self.phase_period = None, 0
         return count
 
     def filter(self, b, a, zi, padlen: int) -> None:
         self.filtered = filtfilt_rows(b, a, self.selected(), zi, padlen)
         self.amp = None
+        self.phase_mean, self.phase_period = None, 0
+
+    def phase(self, period: int) -> None:
+        """The selected frames, whole cycles of ``period`` frames, into their mean over the cycles and the fluctuation about
+        it (``phase_average``); the fluctuation becomes the filtered series.  A refused call changes nothing."""
+        mean, fluct = phase_average(self.selected(), period)
+        self.phase_mean, self.phase_period, self.filtered, self.amp = mean, int(period), fluct, None
+
+    def phase_fetch(self, what: str, frame: int = 0) -> np.ndarray:
+        """'mean' of phase ``frame`` (n, ncomp); 'energy' of fluctuation frame ``frame``, 'energy_cycle_mean' at phase ``frame``,
+        'energy_time_mean' (``frame`` 0): (n,) each, summed in order from +0.0 and divided by the count."""
+        if what not in PHASE_WHAT:
+            raise RuntimeError(f"hi-pass phase_fetch: what must be one of {', '.join(PHASE_WHAT)}")
+        if self.phase_mean is None:
+            raise RuntimeError("hi-pass phase_fetch: no phase average (phase first)")
+        P, n = self.phase_period, len(self.filtered)
+        limit = n if what == "energy" else 1 if what == "energy_time_mean" else P
+        if not 0 <= frame < limit:
+            raise RuntimeError(f"hi-pass phase_fetch: frame {frame} out of range, this kind has {limit}")
+        if what == "mean":
+            return self.phase_mean[frame]
+        if what == "energy":
+            return fluctuation_energy(self.filtered[frame])
+        return ordered_mean(fluctuation_energy(self.filtered[frame::P] if what == "energy_cycle_mean" else self.filtered))
 
     def filter_next(self, b, a, zi, padlen: int) -> None:
         if self.filtered is None:
             raise RuntimeError("hi-pass filter_next: no filtered series (filter first)")
         self.filtered = filtfilt_rows(b, a, self.filtered, zi, padlen)
         self.amp = None
+        self.phase_mean, self.phase_period = None, 0
 
     def trace(self, what: str, points) -> np.ndarray:
         """(points, frames, 1 + ncomp): the magnitude, then the row of each listed node over the selected frames."""
@@ -827,8 +899,15 @@ def hi_pass_refusal(v: dict, world: int, backend_cls) -> str:
     saves = f"saves {frames} frames" if whole else f"saves {frames} frames in the window and stride asked for"
     if v.get("restart_folder"):
         saves += f" ({past} saved before the restart and {len(times) - past} to come)"
+    cycle = phase_cycle(v)
+    if cycle is not None:
+        try:
+            phase_cycles(v, phase_period(cycle, frame_spacing(v) * stride), frames)
+        except SystemExit as e:
+            return str(e)
     for lo, hi in bands(v):
-        if frames < padlen_of(lo) + 1:
+        # with a phase average a band the frames do not suffice for is named when the files are written and left out
+        if frames < padlen_of(lo) + 1 and cycle is None:
             return (f"--hi-pass: the run {saves}, the filter of band {lo:g} - {hi:g} Hz needs at least "
                     f"padlen + 1 = {padlen_of(lo) + 1}")
     if words:
@@ -860,6 +939,60 @@ def output_nodes(mesh: FsiMesh, save_deg: int, quantity: str):
             np.concatenate([np.full(V, -1), e[:, 1]]).astype(np.int32))
 
 
+PHASE_WHAT = ("mean", "energy", "energy_cycle_mean", "energy_time_mean")      # HipBackend.PHASE_WHAT, FSI_PHASE_*
+PHASE_STRIPS = ("--hi-pass-phase-average: the history goes through the session in strips of rows, which form no phase average "
+                "(give it room with --history-memory, or fewer frames with --stride)")
+
+
+def phase_cycle(v: dict) -> Optional[float]:
+    """None without ``--hi-pass-phase-average``, else the cycle length in seconds: ``--hi-pass-cycle`` or the resolved
+    parameters' ``T_Cycle``; without either the run is refused."""
+    for key in ("hi_pass_cycle", "hi_pass_start_cycle", "hi_pass_end_cycle"):
+        if v.get(key) is not None and not v.get("hi_pass_phase_average"):
+            raise SystemExit(f"--{key.replace('_', '-')} belongs to --hi-pass-phase-average")
+    if not v.get("hi_pass_phase_average"):
+        return None
+    cycle = v.get("hi_pass_cycle")
+    cycle = v.get("T_Cycle") if cycle is None else cycle
+    if cycle is None:
+        raise SystemExit("--hi-pass-phase-average needs the length of a cycle: give --hi-pass-cycle SECONDS (the parameters hold no T_Cycle)")
+    if isinstance(cycle, bool) or not isinstance(cycle, (int, float, np.integer, np.floating)) or not cycle > 0:
+        raise SystemExit(f"--hi-pass-cycle must be a number of seconds > 0, got {cycle!r}")
+    return float(cycle)
+
+
+def phase_period(cycle: float, time_between_files: float) -> int:
+    """Frames of a cycle, ``cycle / time_between_files``.  The reference rounds the ratio [REF log_plotter.py:944-946], and a
+    ratio that is no integer makes its phases drift from cycle to cycle: here one further than 1e-6 (relative) from an integer
+    is refused, with both numbers."""
+    ratio = cycle / time_between_files
+    period = int(np.rint(ratio))
+    if period < 1 or abs(ratio - period) > 1e-6 * ratio:
+        raise SystemExit(f"--hi-pass-phase-average: a cycle of {cycle!r} s is {ratio!r} frames of {time_between_files!r} s "
+                         "(dt * save_step * stride), not a whole number of them: the phases would drift from cycle to cycle "
+                         "(choose --hi-pass-cycle, --save-step or --hi-pass-stride so that it is)")
+    return period
+
+
+def phase_cycles(v: dict, period: int, frames: int) -> Tuple[int, int]:
+    """(first, last) cycle that is averaged, 1-based and inclusive as in the reference [REF log_plotter.py:928-946]:
+    ``--hi-pass-start-cycle`` (default 1) and ``--hi-pass-end-cycle`` (default: the last whole cycle) among the whole cycles
+    of ``period`` frames that ``frames`` selected frames hold."""
+    whole = frames // period
+    if whole < 1:
+        raise SystemExit(f"--hi-pass-phase-average: the window and stride asked for hold {frames} frames, fewer than one whole "
+                         f"cycle of {period}")
+    c0, c1 = v.get("hi_pass_start_cycle"), v.get("hi_pass_end_cycle")
+    c0, c1 = 1 if c0 is None else c0, whole if c1 is None else c1
+    for c in (c0, c1):
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)):
+            raise SystemExit(f"--hi-pass-start-cycle / --hi-pass-end-cycle must be integers, got {c!r}")
+    if not 1 <= c0 <= c1 <= whole:
+        raise SystemExit(f"--hi-pass-start-cycle {c0} / --hi-pass-end-cycle {c1}: need 1 <= start <= end <= {whole}, the whole "
+                         f"cycles of {period} frames among the {frames} frames of the window and stride asked for")
+    return int(c0), int(c1)
+
+
 TRACE_HEADER = {1: "time (s), Magnitude", 3: "time (s), Magnitude, X Component, Y Component, Z Component"}      # [REF postprocessing_h5py_common.py:482]
 
 
@@ -867,7 +1000,8 @@ class HiPassRun(SessionRun):
     """The driver's side of ``--hi-pass``: one session per quantity on the Visualization writer's nodes, one recorded frame
     per saved frame, and at the end per band the filtered series, with ``--hi-pass-amplitude`` its amplitude and table; with
     ``--hi-pass-multiband`` one more series that went through all bands in order; with ``--hi-pass-point-ids`` the recorded
-    series of those nodes.  All of it on the saved frames k with ``k % stride == 0`` and ``T0 <= t_k <= T1``
+    series of those nodes; with ``--hi-pass-phase-average`` the mean over the cardiac cycles, the fluctuation about it and the
+    velocity's turbulent kinetic energy (``_write_phase``).  All of it on the saved frames k with ``k % stride == 0`` and ``T0 <= t_k <= T1``
     (``--hi-pass-stride``, ``--hi-pass-start-time``, ``--hi-pass-end-time``; every selected frame is kept, where the reference
     drops the last ones, postprocessing_h5py_common.py:285,307).  Times in the files are ``T0 + k * time_between_files``, T0
     being the reference's ``start_t``; ``time_between_files`` is dt * save_step * stride, the spacing of the selected frames
@@ -890,6 +1024,9 @@ class HiPassRun(SessionRun):
         self.dt = float(ns["dt"])
         self.dt_sample = frame_spacing(ns)
         self.dt_files = self.dt_sample * self.stride
+        cycle = phase_cycle(ns)
+        self.period = None if cycle is None else phase_period(cycle, self.dt_files)
+        self.cycle_range = {key: ns.get(key) for key in ("hi_pass_start_cycle", "hi_pass_end_cycle")}
         self.nodes = {q: output_nodes(mesh, self.save_deg, q) for q in self.quantities}
         if self.save_deg >= 2:
             geometry, topology = mesh.node_coords, refine_topology(mesh)
@@ -903,6 +1040,8 @@ class HiPassRun(SessionRun):
         # a strip (vasp_amd.hi_pass_strips): the session is opened on nodes i0 .. i1 - 1 of the one quantity asked for
         self.strip = ns.get("hi_pass_strip")
         if self.strip is not None:
+            if self.period is not None:
+                raise SystemExit(PHASE_STRIPS)
             i0, i1 = self.strip
             self.nodes = {q: tuple(None if a is None else a[i0:i1] for a in ab) for q, ab in self.nodes.items()}
         self.writer = HiPassWriter(Path(ns["results_folder"]) / "Visualization_hi_pass", geometry, topology)
@@ -952,18 +1091,19 @@ class HiPassRun(SessionRun):
         self.writer.write_series(f"{viz}_amplitude", amp_frames(), n, ncomp, self.dt_files, self.t0)
         self.writer.write_table(viz, table)
 
-    def _write_traces(self, session, q: str, n: int, ids=None, local=None) -> None:
+    def _write_traces(self, session, q: str, n: int, ids=None, local=None, what: str = "raw", suffix: str = "") -> None:
         """``<viz_type>_point_id_<id>.csv``: time, magnitude and components of the recorded rows of each listed node
         [REF postprocessing_h5py_common.py:470-483], the times being T0 + k * time_between_files, one per frame.  ``ids``
-        with ``local``: the ids among ``point_ids`` that a strip holds, and their indices into the strip's nodes."""
+        with ``local``: the ids among ``point_ids`` that a strip holds, and their indices into the strip's nodes.  ``what``
+        "filtered" with a ``suffix`` of the file's name: the same of the filtered series (the fluctuation of a phase average)."""
         ids, local = (self.point_ids, self.point_ids) if ids is None else (ids, local)
         self.trace_folder.mkdir(parents=True, exist_ok=True)
-        trace = np.asarray(session.trace("raw", local))
+        trace = np.asarray(session.trace(what, local))
         for i, rows in zip(ids, trace):
             data = np.empty((n, rows.shape[1] + 1 if q != "p" else 2))
             data[:, 0] = self.t0 + np.arange(n) * self.dt_files
             data[:, 1:] = rows if q != "p" else rows[:, :1]
-            np.savetxt(self.trace_folder / f"{VIZ_TYPE[q]}_point_id_{i}.csv", data, delimiter=",", header=TRACE_HEADER[1 if q == "p" else 3])
+            np.savetxt(self.trace_folder / f"{VIZ_TYPE[q]}{suffix}_point_id_{i}.csv", data, delimiter=",", header=TRACE_HEADER[1 if q == "p" else 3])
 
     def series_list(self, q: str, n: int, out) -> List[Tuple[str, List[dict], bool]]:
         """(viz, stages, rms) of every series ``q`` is written as on n frames, in the order they are written: per band its
@@ -991,6 +1131,37 @@ class HiPassRun(SessionRun):
         series.append((viz, stages, True))
         return series
 
+    def _write_phase(self, out, session, q: str, first: int, n: int) -> None:
+        """``--hi-pass-phase-average``: the mean over the cycles, the fluctuation about it with - under --hi-pass-amplitude -
+        its windowed RMS (the turbulence intensity) and, of the velocity, the turbulent kinetic energy 0.5 |u'|^2 per frame,
+        averaged over the cycles and averaged over time [REF log_plotter.py:902-989].  Cycle c is selected frames
+        (c - 1) P ... c P - 1 of the ``n`` frames of the window; the files of the cycle range start at its first frame's time."""
+        P, name, ncomp = self.period, VIZ_TYPE[q], 1 if q == "p" else 3
+        try:
+            c0, c1 = phase_cycles(self.cycle_range, P, n)
+        except SystemExit as why:                 # a run that was stopped early: named and left out, as a band without its frames
+            out(f"Hi-pass {name}: {why}: no phase average written")
+            return
+        m, skipped = (c1 - c0 + 1) * P, (c0 - 1) * P
+        session.select(first + skipped * self.stride, m, self.stride)
+        session.phase(P)
+        t0 = self.t0
+        self.writer.write_series(f"{name}_phase_mean", (session.phase_fetch("mean", j) for j in range(P)), P, ncomp, self.dt_files, t0)
+        self.t0 = t0 + skipped * self.dt_files
+        try:
+            if self.point_ids:
+                self._write_traces(session, q, m, what="filtered", suffix="_fluctuation")
+            self._write_filtered(out, session, f"{name}_fluctuation", m, ncomp, True)
+            if q == "v":
+                self.writer.write_series(f"{name}_tke", (session.phase_fetch("energy", k) for k in range(m)), m, 1, self.dt_files, self.t0)
+        finally:
+            self.t0 = t0
+        if q == "v":
+            self.writer.write_series(f"{name}_tke_phase_mean", (session.phase_fetch("energy_cycle_mean", j) for j in range(P)), P, 1,
+                                     self.dt_files, t0)
+            self.writer.write_series(f"{name}_tke_avg", [session.phase_fetch("energy_time_mean", 0)], 1, 1, self.dt_files, t0)
+        out(f"Hi-pass {name}: phase average over cycles {c0} to {c1} of {P} frames written")
+
     @staticmethod
     def apply(session, stages) -> None:
         """The session's filtered series after ``stages``: the first on the selected frames, every further one on the series."""
@@ -1010,4 +1181,6 @@ class HiPassRun(SessionRun):
             for viz, stages, rms in self.series_list(q, n, out):
                 self.apply(session, stages)
                 self._write_filtered(out, session, viz, n, ncomp, rms)
+            if self.period is not None:
+                self._write_phase(out, session, q, first, n)
         out(f"Hi-pass fields of {n} frames ({', '.join(self.quantities)}) written to {self.writer.folder}")

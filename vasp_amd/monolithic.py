@@ -76,6 +76,16 @@ def add_session_arguments(ap) -> None:
     ap.add_argument("--hi-pass-point-ids", dest="hi_pass_point_ids", nargs="+", type=_coerce, default=None, metavar="ID",
                     help="write the recorded series of these nodes (indices into the nodes of the Visualization files) to "
                          "<results>/Visualization_separate_domain/<field>_point_id_<ID>.csv")
+    ap.add_argument("--hi-pass-phase-average", dest="hi_pass_phase_average", action="store_const", const=True, default=None,
+                    help="also write, per quantity of --hi-pass, the mean over the cardiac cycles at every phase, the fluctuation "
+                         "about it and, of the velocity, the turbulent kinetic energy 0.5 |u'|^2 (what vasp-log-plotter "
+                         "--plot-probe-points-tke forms at the probe points), on every written node")
+    ap.add_argument("--hi-pass-cycle", dest="hi_pass_cycle", type=float, default=None, metavar="SECONDS",
+                    help="length of a cycle for --hi-pass-phase-average, a whole number of dt * save_step * stride (default: T_Cycle)")
+    ap.add_argument("--hi-pass-start-cycle", dest="hi_pass_start_cycle", type=int, default=None, metavar="N",
+                    help="first cycle of the window that --hi-pass-phase-average averages, 1-based (default: 1)")
+    ap.add_argument("--hi-pass-end-cycle", dest="hi_pass_end_cycle", type=int, default=None, metavar="M",
+                    help="last cycle that --hi-pass-phase-average averages, inclusive (default: the last whole cycle)")
     ap.add_argument("--hi-pass-tensor", dest="hi_pass_tensor", nargs="+", default=None, metavar="Q",
                     help="record the Green-Lagrange strain and / or the Cauchy stress (strain, stress) of the solid cells at every "
                          "saved frame on the device and write the band-pass filtered tensors of --hi-pass-bands, with "

@@ -202,6 +202,8 @@ def prepare(argv: Optional[List[str]] = None, backend_factory: Callable = defaul
         need = lambda rows, capacity: hi_pass.host_room(rows, capacity)[0]
         band_jobs, amplitude, limit = strips.jobs(mesh, v), bool(v.get("hi_pass_amplitude")), int(v["history_memory"])
         if not strips.everything_fits(band_jobs, len(indices) + 1, amplitude, limit, need):
+            if v.get("hi_pass") and v.get("hi_pass_phase_average"):
+                raise SystemExit(hi_pass.PHASE_STRIPS)
             for j in band_jobs:
                 if j.units:
                     strips.plan_strips(j.units, j.rows_per_unit, len(indices) + 1, j.board_bytes(amplitude), limit, need,
@@ -246,6 +248,8 @@ def run(argv: Optional[List[str]] = None, backend_factory: Callable = default_ba
             limit = (backend.hi_pass_room if hasattr(backend, "hi_pass_room") else hi_pass.host_room)(1, 1)[1]
         if not strips.everything_fits(band_jobs, len(indices) + 1, bool(ns.get("hi_pass_amplitude")), int(limit), need):
             in_strips = {"hi_pass", "hi_pass_tensor"}
+            if ns.get("hi_pass") and ns.get("hi_pass_phase_average"):
+                raise SystemExit(hi_pass.PHASE_STRIPS)
     # the same for the spectrogram histories: where they do not fit beside the band-pass sessions of the first frame loop
     spec_run = None
     if ns.get("spectrogram") and indices:
