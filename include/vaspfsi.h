@@ -485,6 +485,37 @@ int fsi_band_phase(FsiCtx* ctx, int32_t quantity, int64_t period);
  * The three energies are refused for the tensor quantities (ncomp 6).  FSI_ERR_INVALID "no phase average (fsi_band_phase
  * first)" without one, for a frame out of range, a null out and a partitioned context. */
 int fsi_band_phase_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, double* out);
+/* Replaces: nothing in the reference; VaMPy's metrics on an FSI run.  Attaches n > 0 mesh cells to the open session of
+ * quantity 0 (d) or 1 (v) (fsi_band_begin), for fsi_band_cell_rate.  Every one of a cell's ten P2 nodes must be a node of the
+ * session whose row is the node's own value (nodes_b < 0); of a node listed twice the first occurrence is used.  The range of
+ * the cells is checked on the host before anything is uploaded; a cell with a node the session does not hold is
+ * FSI_ERR_INVALID naming the first such cell and node.  Uploaded: conn[n][10] (indices into the session's nodes, local order:
+ * the vertices, then the edges {2,3},{1,3},{1,2},{0,3},{0,2},{0,1}) and gl[n][4][3], the gradients of the cells' barycentric
+ * coordinates in the undeformed geometry, as wss_dg1_cell and the reference's hemodynamics take them - 136 bytes per cell - and
+ * a result out[n]; under the room rule of fsi_band_begin: FSI_ERR_INVALID with both byte counts when the 144 n bytes do not fit
+ * beside the context's 1/16 of the device.  grad_out (nullable): [n][4][3], the gradients the kernel will use, so that a host
+ * twin works from the same bits.  A second call replaces the list; a refused call leaves the list that stands in place;
+ * fsi_band_begin, fsi_band_end and fsi_destroy free it; fsi_band_sample, _import, _select, _filter, _filter_next and _phase
+ * leave it alone.  Refused for p, the tensor quantities, a quantity without a session and partitioned contexts. */
+int fsi_band_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* cells, double* grad_out);
+#define FSI_RATE_RAW 0
+#define FSI_RATE_SERIES 1
+#define FSI_RATE_PHASE_MEAN 2
+/* Replaces: nothing in the reference; VaMPy's metrics on an FSI run.  out[n], per cell of fsi_band_cells
+ *   out[c] = (((+0.0 + r[first]) + r[first + step]) + ...) / count,     count terms in frame order, a true division,
+ * r[k] being the exact mean over the cell of 2 S:S, S = sym(grad w), of frame k of a series w of the session:
+ *   FSI_RATE_RAW         the selected frames of the history, through the selection's stride (fsi_band_select);
+ *   FSI_RATE_SERIES      the filtered series (fsi_band_filter, _filter_next) or the fluctuation (fsi_band_phase), whichever
+ *                        the session holds;
+ *   FSI_RATE_PHASE_MEAN  the `period` frames of the phase mean (fsi_band_phase).
+ * With G_t = grad w at vertex t (the gradient of a P2 field is linear on the cell) and S_t = 0.5 (G_t + G_t^T):
+ * r = 0.1 * (sum_t S_t:S_t + (sum_t S_t):(sum_t S_t)).  FP64 without contraction, bit-equal to hi_pass.cell_rate; count = 1
+ * gives the frame's own bits; NaN and inf propagate, nothing is clamped.  One frame: (k, 1, 1); the time mean: (0, 1, n); the
+ * cycle mean at phase j: (j, period, C).  sqrt(out) of the velocity is the strain rate |S| = sqrt(2 S:S), nu * out the viscous
+ * dissipation.  FSI_ERR_INVALID, naming what is missing: no cell list (fsi_band_cells first), no filtered series
+ * (fsi_band_filter or fsi_band_phase first), no phase average (fsi_band_phase first), step < 1 or count < 1, a last frame
+ * outside the series, out NULL; p, the tensor quantities, a quantity without a session and partitioned contexts. */
+int fsi_band_cell_rate(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count, double* out);
 /* Replaces: the "Saving data" loops of create_hi_pass_viz [REF .../create_hi_pass_viz.py:233-245,327-341,377-390]: one frame
  * of the raw history, the filtered series or its amplitude (out[n][ncomp]), or of the amplitude's magnitude over the
  * components (out[n]; for p the amplitude itself).  For the last two, max_out / argmax_out (nullable) receive the largest

@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_set_frame", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_phase", "fsi_band_phase_fetch", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_begin_rows", "fsi_spec_begin_wss", "fsi_spec_room", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_spectrogram_sum", "fsi_spec_periodogram_sum", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_phase", "fsi_band_phase_fetch", "fsi_band_cells", "fsi_band_cell_rate", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_begin_rows", "fsi_spec_begin_wss", "fsi_spec_room", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_spectrogram_sum", "fsi_spec_periodogram_sum", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -168,6 +168,8 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_band_amplitude.argtypes = [vp, i32, i32]
     lib.fsi_band_phase.argtypes = [vp, i32, i64]
     lib.fsi_band_phase_fetch.argtypes = [vp, i32, i32, i64, vp]
+    lib.fsi_band_cells.argtypes = [vp, i32, i64, vp, vp]
+    lib.fsi_band_cell_rate.argtypes = [vp, i32, i32, i64, i64, i64, vp]
     lib.fsi_band_fetch.argtypes = [vp, i32, i32, i64, vp, C.POINTER(dbl), C.POINTER(i64)]
     lib.fsi_band_select.argtypes = [vp, i32, i64, i64, i64]
     lib.fsi_band_filter_next.argtypes = [vp, i32, i32, vp, vp, vp, i32]
@@ -621,6 +623,8 @@ class HipBackend:
             self._band_shape, self._band_frames = {}, {}
         self._band_shape[quantity] = (len(a), 1 if quantity == "p" else 3)
         self._band_frames[quantity] = [0, 0]          # frames recorded, frames selected: the size of a trace
+        getattr(self, "_band_cells", {}).pop(quantity, None)      # a new session has no cell list and no phase average
+        getattr(self, "_band_period", {}).pop(quantity, None)
 
     def hi_pass_begin_cells(self, quantity: str, cells, capacity: int = 1) -> None:
         """Open the band-pass session of the tensor ``quantity`` ('strain': Green-Lagrange strain, 'stress': Cauchy stress;
@@ -686,6 +690,9 @@ class HipBackend:
         fluctuation about the mean over the cycles becomes the filtered series - 'filtered' and 'amplitude' fetches and a
         'filtered' trace serve it -, the means and the fluctuation's energy come from ``hi_pass_phase_fetch``."""
         self._check(self.lib.fsi_band_phase(self.ctx, self.BAND_QUANTITY[quantity], int(period)))
+        if not hasattr(self, "_band_period"):
+            self._band_period = {}
+        self._band_period[quantity] = int(period)     # the frames of the phase mean: hi_pass_cell_rate's default count
 
     def hi_pass_phase_fetch(self, quantity: str, what: str, frame: int = 0) -> np.ndarray:
         """After ``hi_pass_phase``: 'mean' of phase ``frame`` as (n, ncomp); 'energy' 0.5 |u'|^2 of fluctuation frame
@@ -694,6 +701,34 @@ class HipBackend:
         n, ncomp = self._band_shape[quantity]
         out = np.empty((n, ncomp)) if what == "mean" else np.empty(n)
         self._check(self.lib.fsi_band_phase_fetch(self.ctx, self.BAND_QUANTITY[quantity], self.PHASE_WHAT[what], int(frame), _ptr(out)))
+        return out
+
+    RATE_SERIES = {"raw": 0, "series": 1, "phase_mean": 2}
+
+    def hi_pass_cells(self, quantity: str, cells) -> np.ndarray:
+        """Attach mesh ``cells`` (user order) to the session of 'd' or 'v' (fsi_band_cells): every P2 node of every cell must be
+        a node of the session.  Returns the gradients of the cells' barycentric coordinates the kernel will use, (n, 4, 3); a
+        second call replaces the list."""
+        ci = np.ascontiguousarray(self.cell_u2i[np.asarray(cells, dtype=np.int64).reshape(-1)], dtype=np.int32)
+        grad = np.empty((len(ci), 4, 3))
+        self._check(self.lib.fsi_band_cells(self.ctx, self.BAND_QUANTITY[quantity], len(ci), _ptr(ci), _ptr(grad)))
+        if not hasattr(self, "_band_cells"):
+            self._band_cells = {}
+        self._band_cells[quantity] = len(ci)
+        return grad
+
+    def hi_pass_cell_rate(self, quantity: str, series: str, first: int = 0, step: int = 1, count: int = -1) -> np.ndarray:
+        """Per attached cell the mean over frames ``first, first + step, ...`` (``count`` of them, -1: as many as the series
+        has) of the cell mean of 2 S:S, S = sym(grad w), summed in frame order from +0.0 and divided by the count
+        (fsi_band_cell_rate).  ``series``: 'raw' the selected frames, 'series' the filtered series or the fluctuation,
+        'phase_mean' the frames of the phase mean.  (n,)."""
+        first, step, count = int(first), int(step), int(count)
+        if count == -1 and step >= 1:
+            frames = getattr(self, "_band_period", {}).get(quantity, 0) if series == "phase_mean" else self._band_frames[quantity][1]
+            count = (frames - 1 - first) // step + 1
+        out = np.empty(getattr(self, "_band_cells", {}).get(quantity, 0))
+        self._check(self.lib.fsi_band_cell_rate(self.ctx, self.BAND_QUANTITY[quantity], self.RATE_SERIES[series], first, step, count,
+                                                _ptr(out) if len(out) else None))
         return out
 
     def hi_pass_fetch(self, quantity: str, what: str, frame: int, with_max: bool = False):

@@ -468,11 +468,21 @@ struct FsiCtx {
     int64_t phase_period = 0;
     fsi::DevBuf<double> acc, amp, mag, part_val, phase_mean;
     fsi::DevBuf<int64_t> part_idx;
+    // the mesh cells attached to a session of d or v (fsi_band_cells): per cell its ten P2 nodes as indices into the session's
+    // nodes, local order, the gradients of its barycentric coordinates and one result (fsi_rate.hip); h_nodes: the P2 node of
+    // every session node as fsi_band_begin was given it, -1 where the row is the mean of two nodes
+    int64_t ncell = 0;
+    std::vector<int32_t> h_nodes;
+    fsi::DevBuf<int32_t> cell_conn;          // [ncell][10]
+    fsi::DevBuf<double> cell_gl, cell_out;   // [ncell][4][3], [ncell]
     void phase_release() { phase_mean.release(); phase_period = 0; }
+    void cells_release() { cell_conn.release(); cell_gl.release(); cell_out.release(); ncell = 0; }
     void release() {
       History::release();
       acc.release(); amp.release(); mag.release(); part_val.release(); part_idx.release();
       phase_release();
+      cells_release();
+      h_nodes.clear();
       ncomp = 0; window = -1; acc_start = -1;
       sel_first = 0; sel_stride = 1; sel_count = -1;
       board_node0 = -1;

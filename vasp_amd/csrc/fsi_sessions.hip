@@ -1,9 +1,10 @@
 // C-ABI of libvaspfsi.so (include/vaspfsi.h): the post-processing sessions that live on the resident state over a run -
 // hemodynamic indices (fsi_hemo_*), solid stress / strain (fsi_stress_*), band-pass filtered fields (fsi_band_*) and
-// spectrograms (fsi_spec_*).  The arithmetic runs in the kernels of fsi_hemo / fsi_stress / fsi_band / fsi_phase / fsi_spec .hip; the
+// spectrograms (fsi_spec_*).  The arithmetic runs in the kernels of fsi_hemo / fsi_stress / fsi_band / fsi_phase / fsi_rate / fsi_spec .hip; the
 // last two families record into one kind of history (FsiCtx::History) through the helpers below.
 #include "fsi_host.hpp"
 #include "fsi_phase.hpp"
+#include "fsi_rate.hpp"
 #include "fsi_spec.hpp"
 
 using namespace fsi;
@@ -702,6 +703,10 @@ int fsi_band_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* node
   HIPCHK(s.mag.alloc((size_t)n));
   HIPCHK(s.part_val.alloc(BAND_ARGMAX_BLOCKS + 1));
   HIPCHK(s.part_idx.alloc(BAND_ARGMAX_BLOCKS + 1));
+  s.h_nodes.assign(nodes, nodes + n);            // for fsi_band_cells: a row that is the mean of two nodes is no node's
+  if (nodes_b)
+    for (int64_t i = 0; i < n; ++i)
+      if (nodes_b[i] >= 0) s.h_nodes[i] = -1;
   return history_open(ctx, s, n, nrow, capacity, i0, i1, false);
 }
 
@@ -884,6 +889,91 @@ int fsi_band_phase_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t fr
     src = s->mag.p;
   }
   HIPCHK(hipMemcpyAsync(out, src, (size_t)(what == FSI_PHASE_MEAN ? s->nrow : s->nnode) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return FSI_OK;
+}
+
+int fsi_band_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* cells, double* grad_out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_cells")) return FSI_ERR_INVALID;
+  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_cells: " + why; return FSI_ERR_INVALID; };
+  if (quantity != 0 && quantity != 1) return refuse("quantity must be 0 (d) or 1 (v): the strain rate is that of a vector on P2 nodes");
+  auto* s = band_session(ctx, quantity, "fsi_band_cells");
+  if (!s) return FSI_ERR_INVALID;
+  if (n <= 0 || !cells) return refuse("needs n > 0 cells");
+  for (int64_t i = 0; i < n; ++i)
+    if (cells[i] < 0 || cells[i] >= ctx->C) return refuse("cell out of range");
+  // the session node of every P2 node: the first occurrence of a node that is listed twice
+  std::vector<int32_t> at((size_t)ctx->N2, -1);
+  for (int64_t i = (int64_t)s->h_nodes.size() - 1; i >= 0; --i)
+    if (s->h_nodes[i] >= 0) at[s->h_nodes[i]] = (int32_t)i;
+  std::vector<int32_t> conn((size_t)n * 10);
+  for (int64_t i = 0; i < n; ++i)
+    for (int a = 0; a < 10; ++a) {
+      const int32_t node = ctx->h_tet_nodes[10 * (int64_t)cells[i] + a];
+      if (at[node] < 0)
+        return refuse("cell " + std::to_string(cells[i]) + " (entry " + std::to_string(i) + " of the list) has P2 node " + std::to_string(node) +
+                      ", which is no node of the session (a session on every P2 node is needed: save_deg 2)");
+      conn[10 * i + a] = at[node];
+    }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  // the room rule of fsi_band_begin; the list that stands is given back only once the new one is in place, so it counts as taken
+  Room room;
+  FSICHK(device_room(ctx, &room));
+  const double need_d = 144.0 * (double)n, avail = (double)room.free_b - room.reserve;
+  if (need_d > avail) {
+    char msg[320];
+    snprintf(msg, sizeof msg, "fsi_band_cells: the cell list needs %.0f bytes (%lld cells x 144: ten nodes, twelve gradients, one result), the "
+             "device has %zu bytes free of which %.0f stay with the context", need_d, (long long)n, room.free_b, room.reserve);
+    ctx->err = msg;
+    return FSI_ERR_INVALID;
+  }
+  DevBuf<int32_t> d_conn, d_cells;
+  DevBuf<double> d_gl, d_out;
+  HIPCHK(d_conn.alloc((size_t)n * 10));
+  HIPCHK(d_cells.alloc((size_t)n));
+  HIPCHK(d_gl.alloc((size_t)n * 12));
+  HIPCHK(d_out.alloc((size_t)n));
+  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
+  HIPCHK(hipMemcpyAsync(d_conn.p, conn.data(), conn.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(d_cells.p, cells, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  launch_cell_gradients(ctx->stream, n, ctx->geom.p, d_cells.p, d_gl.p);
+  HIPCHK(hipGetLastError());
+  if (grad_out) HIPCHK(hipMemcpyAsync(grad_out, d_gl.p, (size_t)n * 12 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  std::swap(s->cell_conn.p, d_conn.p); std::swap(s->cell_conn.n, d_conn.n);      // the earlier list leaves with the locals
+  std::swap(s->cell_gl.p, d_gl.p); std::swap(s->cell_gl.n, d_gl.n);
+  std::swap(s->cell_out.p, d_out.p); std::swap(s->cell_out.n, d_out.n);
+  s->ncell = n;
+  return FSI_OK;
+}
+
+int fsi_band_cell_rate(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count, double* out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_cell_rate")) return FSI_ERR_INVALID;
+  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_cell_rate: " + why; return FSI_ERR_INVALID; };
+  if (quantity != 0 && quantity != 1) return refuse("quantity must be 0 (d) or 1 (v)");
+  auto* s = band_session(ctx, quantity, "fsi_band_cell_rate");
+  if (!s) return FSI_ERR_INVALID;
+  if (series < FSI_RATE_RAW || series > FSI_RATE_PHASE_MEAN) return refuse("series must be FSI_RATE_RAW, FSI_RATE_SERIES or FSI_RATE_PHASE_MEAN");
+  if (s->ncell < 1) return refuse("no cell list (fsi_band_cells first)");
+  if (series == FSI_RATE_SERIES && !s->filtered) return refuse("no filtered series (fsi_band_filter or fsi_band_phase first)");
+  if (series == FSI_RATE_PHASE_MEAN && (s->phase_period < 1 || !s->filtered)) return refuse("no phase average (fsi_band_phase first)");
+  if (!out) return refuse("out is NULL");
+  const int64_t frames = series == FSI_RATE_PHASE_MEAN ? s->phase_period : band_frames(s);
+  if (step < 1 || count < 1) return refuse("needs step >= 1 and count >= 1, got step = " + std::to_string(step) + ", count = " + std::to_string(count));
+  if (first < 0 || first >= frames || count - 1 > (frames - 1 - first) / step)
+    return refuse("frames " + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(step) + ", ... (" + std::to_string(count) +
+                  " of them) fall outside the series of " + std::to_string(frames) + " frames");
+  // the series as frames of nrow doubles, `stride` frames of the underlying array apart
+  const double* x = series == FSI_RATE_RAW ? s->hist.p + (size_t)s->sel_first * s->nrow : series == FSI_RATE_SERIES ? history_frame(s, true, 0) : s->phase_mean.p;
+  const int64_t stride = series == FSI_RATE_RAW ? s->sel_stride : 1;
+  HIPCHK(hipSetDevice(ctx->device));
+  launch_cell_rate(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x + (size_t)(first * stride) * s->nrow, step * stride * s->nrow, count,
+                   s->cell_out.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, s->cell_out.p, (size_t)s->ncell * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return FSI_OK;
 }

@@ -18,6 +18,9 @@ This module holds
   points [REF log_plotter.py:902-989], here per written node (csrc/fsi_phase.hip): its NumPy twin (``phase_average``,
   ``fluctuation_energy``, ``ordered_mean``, ``HostBandSession.phase`` / ``phase_fetch``), the period arithmetic with its
   refusals (``phase_cycle``, ``phase_period``, ``phase_cycles``) and its files (``HiPassRun._write_phase``);
+* the strain rate of a session's vector history on mesh cells, which ``--hi-pass-flow-metrics`` closes into dissipation and
+  resolution metrics (``vasp_amd/flow_metrics.py``): the NumPy twin of csrc/fsi_rate.hip (``cell_rate``,
+  ``HostBandSession.cells`` / ``cell_rate``), and where ``HiPassRun.write`` collects the rates;
 * what the four post-processing options share to go through a checkpoint: the manifest and the files of
   ``<results>/Checkpoint/sessions/`` and the checks of a restart (``save_sessions``, ``restart_entry``), and the saving and
   restoring of a recorded history (``SessionRun``);
@@ -247,6 +250,46 @@ def ordered_mean(e: np.ndarray) -> np.ndarray:
         return s / float(len(e))
 
 
+RATE_SERIES = ("raw", "series", "phase_mean")      # HipBackend.RATE_SERIES, FSI_RATE_*
+
+
+def cell_rate(w: np.ndarray, grad: np.ndarray) -> np.ndarray:
+    """The exact mean over a tetrahedron of ``2 S:S``, ``S = sym(grad w)``, of P2 fields w, (cells, 10, 3) in the local node
+    order (``mesh.TET_EDGES``), with ``grad`` (cells, 4, 3) the gradients of the barycentric coordinates: the arithmetic of
+    k_cell_rate (csrc/fsi_rate.hip) in its order, one IEEE operation per NumPy operation.  ``G_t = grad w`` at vertex t by the
+    expression of wss_dg1_cell (csrc/fsi_wss.hpp), ``S_t = 0.5 (G_t + G_t^T)`` and
+    ``0.1 * (sum_t S_t:S_t + (sum_t S_t):(sum_t S_t))``, since ``int L_a L_b = |K| (1 + delta_ab) / 20``."""
+    from .mesh import TET_EDGES
+    w, g = np.asarray(w, dtype=np.float64), np.asarray(grad, dtype=np.float64)
+    if w.ndim != 3 or w.shape[1:] != (10, 3) or g.shape != (len(w), 4, 3):
+        raise RuntimeError(f"cell_rate: w of shape {w.shape} and grad of shape {g.shape}, expected (n, 10, 3) and (n, 4, 3)")
+    n = len(w)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.zeros(n)
+        T = [[np.zeros(n) for _ in range(3)] for _ in range(3)]
+        for t in range(4):
+            G = [[None] * 3 for _ in range(3)]
+            for i in range(3):
+                for j in range(3):
+                    s = np.zeros(n)
+                    for a in range(4):
+                        s = s + w[:, a, i] * ((3.0 if a == t else -1.0) * g[:, a, j])
+                    for e in range(6):
+                        p, r = int(TET_EDGES[e][0]), int(TET_EDGES[e][1])
+                        s = s + (w[:, 4 + e, i] * 4.0) * ((1.0 if p == t else 0.0) * g[:, r, j] + (1.0 if r == t else 0.0) * g[:, p, j])
+                    G[i][j] = s
+            for i in range(3):
+                for j in range(3):
+                    S = 0.5 * (G[i][j] + G[j][i])
+                    q = q + S * S
+                    T[i][j] = T[i][j] + S
+        p = np.zeros(n)
+        for i in range(3):
+            for j in range(3):
+                p = p + T[i][j] * T[i][j]
+        return 0.1 * (q + p)
+
+
 def pass_stop_list(band_list, words=None) -> List[str]:
     """"pass" or "stop" per band of a multiband cascade: the reference's rule - a band wider than 1000 Hz passes, a narrower
     one is stopped [REF create_hi_pass_viz.py:541-545] - or the words given (``--hi-pass-pass-stop``)."""
@@ -314,6 +357,7 @@ class HostBandSession(HostHistory):
         self.ncomp, self.amp, self.view = ncomp, None, slice(None)
         self.board, self.board_node0 = None, -1
         self.phase_mean, self.phase_period = None, 0
+        self.cell_conn = self.cell_grad = None
 
     def sample(self, frame: np.ndarray) -> None:
         super().sample(frame)
@@ -362,6 +406,54 @@ class HostBandSession(HostHistory):
         if what == "energy":
             return fluctuation_energy(self.filtered[frame])
         return ordered_mean(fluctuation_energy(self.filtered[frame::P] if what == "energy_cycle_mean" else self.filtered))
+
+    def cells(self, conn, grad) -> np.ndarray:
+        """Attach cells for ``cell_rate``: ``conn`` (n, 10) the cells' P2 nodes as indices into the session's nodes, local
+        order, ``grad`` (n, 4, 3) the gradients of their barycentric coordinates (what ``HipBackend.hi_pass_cells`` forms from
+        the mesh cells and returns).  Replaces an earlier list; a refused call leaves it in place.  Returns ``grad``."""
+        if self.ncomp != 3:
+            raise RuntimeError("hi-pass cells: the strain rate is that of a vector on P2 nodes: a session of d or v")
+        conn, grad = np.asarray(conn), np.asarray(grad, dtype=np.float64)
+        if conn.ndim != 2 or conn.shape[1] != 10 or len(conn) < 1 or grad.shape != (len(conn), 4, 3):
+            raise RuntimeError(f"hi-pass cells: needs n > 0 cells, conn (n, 10) and grad (n, 4, 3), got {conn.shape} and {grad.shape}")
+        nodes = len(self.raw[0]) if self.raw else None
+        if conn.min() < 0 or (nodes is not None and conn.max() >= nodes):
+            c, a = np.argwhere((conn < 0) | (conn >= (nodes if nodes is not None else conn.max() + 1)))[0]
+            raise RuntimeError(f"hi-pass cells: cell {c} has node {conn[c, a]}, which is no node of the session")
+        self.cell_conn, self.cell_grad = conn.astype(np.int64), grad.copy()
+        return self.cell_grad
+
+    def cell_rate(self, series: str, first: int = 0, step: int = 1, count: int = -1) -> np.ndarray:
+        """Per attached cell ``(((+0.0 + r[first]) + r[first + step]) + ...) / count`` with ``r[k] = cell_rate`` of frame k of
+        'raw' (the selected frames), 'series' (the filtered series or the fluctuation) or 'phase_mean'; ``count`` -1: as many
+        frames as the series has.  The twin of fsi_band_cell_rate."""
+        if series not in RATE_SERIES:
+            raise RuntimeError(f"hi-pass cell_rate: series must be one of {', '.join(RATE_SERIES)}")
+        if self.cell_conn is None:
+            raise RuntimeError("hi-pass cell_rate: no cell list (cells first)")
+        if series == "series" and self.filtered is None:
+            raise RuntimeError("hi-pass cell_rate: no filtered series (filter or phase first)")
+        if series == "phase_mean" and self.phase_mean is None:
+            raise RuntimeError("hi-pass cell_rate: no phase average (phase first)")
+        x = self.selected() if series == "raw" else self.filtered if series == "series" else self.phase_mean
+        first, step, count = int(first), int(step), int(count)
+        if count == -1 and step >= 1:
+            count = (len(x) - 1 - first) // step + 1
+        if step < 1 or count < 1:
+            raise RuntimeError(f"hi-pass cell_rate: needs step >= 1 and count >= 1, got step = {step}, count = {count}")
+        if not 0 <= first < len(x) or first + (count - 1) * step >= len(x):
+            raise RuntimeError(f"hi-pass cell_rate: frames {first}, {first} + {step}, ... ({count} of them) fall outside the series of "
+                               f"{len(x)} frames")
+        if self.cell_conn.max() >= x.shape[1]:
+            raise RuntimeError(f"hi-pass cell_rate: the cell list names node {self.cell_conn.max()}, the session has {x.shape[1]}")
+        with np.errstate(invalid="ignore", over="ignore"):
+            s = np.zeros(len(self.cell_conn))
+            for k in range(first, first + count * step, step):
+                s = s + cell_rate(x[k][self.cell_conn], self.cell_grad)
+            return s / float(count)
+
+    def end(self) -> None:
+        self.cell_conn = self.cell_grad = None
 
     def filter_next(self, b, a, zi, padlen: int) -> None:
         if self.filtered is None:
@@ -899,6 +991,10 @@ def hi_pass_refusal(v: dict, world: int, backend_cls) -> str:
     saves = f"saves {frames} frames" if whole else f"saves {frames} frames in the window and stride asked for"
     if v.get("restart_folder"):
         saves += f" ({past} saved before the restart and {len(times) - past} to come)"
+    from .flow_metrics import refusal as metrics_refusal
+    why = metrics_refusal(v, quantities(v))
+    if why:
+        return why
     cycle = phase_cycle(v)
     if cycle is not None:
         try:
@@ -940,6 +1036,8 @@ def output_nodes(mesh: FsiMesh, save_deg: int, quantity: str):
 
 
 PHASE_WHAT = ("mean", "energy", "energy_cycle_mean", "energy_time_mean")      # HipBackend.PHASE_WHAT, FSI_PHASE_*
+METRICS_STRIPS = ("--hi-pass-flow-metrics: the history goes through the session in strips of rows, which do not keep a cell's 30 rows "
+                  "together (give it room with --history-memory, or fewer frames with --stride)")
 PHASE_STRIPS = ("--hi-pass-phase-average: the history goes through the session in strips of rows, which form no phase average "
                 "(give it room with --history-memory, or fewer frames with --stride)")
 
@@ -1042,10 +1140,19 @@ class HiPassRun(SessionRun):
         if self.strip is not None:
             if self.period is not None:
                 raise SystemExit(PHASE_STRIPS)
+            if ns.get("hi_pass_flow_metrics"):
+                raise SystemExit(METRICS_STRIPS)
             i0, i1 = self.strip
             self.nodes = {q: tuple(None if a is None else a[i0:i1] for a in ab) for q, ab in self.nodes.items()}
         self.writer = HiPassWriter(Path(ns["results_folder"]) / "Visualization_hi_pass", geometry, topology)
         self.trace_folder = Path(ns["results_folder"]) / "Visualization_separate_domain"      # [REF create_hi_pass_viz.py:565,639]
+        self.metrics = None
+        if ns.get("hi_pass_flow_metrics"):
+            from . import flow_metrics
+            why = flow_metrics.refusal(ns, self.quantities)
+            if why:
+                raise SystemExit(why)
+            self.metrics = flow_metrics.FlowMetrics(mesh, ns)
         self.open_sessions(backend, ns, lambda q: self.nodes[q],
                            lambda q, capacity: HostBandSession(1 if q == "p" else 3, capacity))
 
@@ -1160,6 +1267,9 @@ class HiPassRun(SessionRun):
             self.writer.write_series(f"{name}_tke_phase_mean", (session.phase_fetch("energy_cycle_mean", j) for j in range(P)), P, 1,
                                      self.dt_files, t0)
             self.writer.write_series(f"{name}_tke_avg", [session.phase_fetch("energy_time_mean", 0)], 1, 1, self.dt_files, t0)
+            if self.metrics is not None:      # R(u') over the frames of the chosen cycles, at each phase, and R of the phase means
+                self.metrics.phase = dict(fluctuation=session.cell_rate("series"), mean=session.cell_rate("phase_mean"),
+                                          cycle_mean=np.stack([session.cell_rate("series", j, P, m // P) for j in range(P)]))
         out(f"Hi-pass {name}: phase average over cycles {c0} to {c1} of {P} frames written")
 
     @staticmethod
@@ -1178,9 +1288,17 @@ class HiPassRun(SessionRun):
             session.select(first, n, self.stride)
             if self.point_ids:
                 self._write_traces(session, q, n)
+            metrics = self.metrics if q == "v" else None
+            if metrics is not None:            # the fluid cells stay attached through the filters and the phase average
+                metrics.attach(session, self.device)
+                metrics.raw = session.cell_rate("raw")
             for viz, stages, rms in self.series_list(q, n, out):
                 self.apply(session, stages)
                 self._write_filtered(out, session, viz, n, ncomp, rms)
+                if metrics is not None and len(stages) == 1:
+                    metrics.bands[stages[0]["name"]] = session.cell_rate("series")
             if self.period is not None:
                 self._write_phase(out, session, q, first, n)
+            if metrics is not None:
+                metrics.write(out, self.dt_files, self.t0)
         out(f"Hi-pass fields of {n} frames ({', '.join(self.quantities)}) written to {self.writer.folder}")

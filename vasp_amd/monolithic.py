@@ -86,6 +86,11 @@ def add_session_arguments(ap) -> None:
                     help="first cycle of the window that --hi-pass-phase-average averages, 1-based (default: 1)")
     ap.add_argument("--hi-pass-end-cycle", dest="hi_pass_end_cycle", type=int, default=None, metavar="M",
                     help="last cycle that --hi-pass-phase-average averages, inclusive (default: the last whole cycle)")
+    ap.add_argument("--hi-pass-flow-metrics", dest="hi_pass_flow_metrics", action="store_const", const=True, default=None,
+                    help="also write, from the velocity history of --hi-pass v at --save-deg 2, the flow and simulation metrics on "
+                         "the fluid cells to <results>/FlowMetrics/: strain rate, viscous dissipation, l+ and t+; with "
+                         "--hi-pass-phase-average the turbulent dissipation, the Kolmogorov scales and the ratios h / eta, dt / tau; "
+                         "per band of --hi-pass-bands the dissipation of the band-passed velocity")
     ap.add_argument("--hi-pass-tensor", dest="hi_pass_tensor", nargs="+", default=None, metavar="Q",
                     help="record the Green-Lagrange strain and / or the Cauchy stress (strain, stress) of the solid cells at every "
                          "saved frame on the device and write the band-pass filtered tensors of --hi-pass-bands, with "

@@ -204,6 +204,8 @@ def prepare(argv: Optional[List[str]] = None, backend_factory: Callable = defaul
         if not strips.everything_fits(band_jobs, len(indices) + 1, amplitude, limit, need):
             if v.get("hi_pass") and v.get("hi_pass_phase_average"):
                 raise SystemExit(hi_pass.PHASE_STRIPS)
+            if v.get("hi_pass") and v.get("hi_pass_flow_metrics"):
+                raise SystemExit(hi_pass.METRICS_STRIPS)
             for j in band_jobs:
                 if j.units:
                     strips.plan_strips(j.units, j.rows_per_unit, len(indices) + 1, j.board_bytes(amplitude), limit, need,
@@ -250,6 +252,8 @@ def run(argv: Optional[List[str]] = None, backend_factory: Callable = default_ba
             in_strips = {"hi_pass", "hi_pass_tensor"}
             if ns.get("hi_pass") and ns.get("hi_pass_phase_average"):
                 raise SystemExit(hi_pass.PHASE_STRIPS)
+            if ns.get("hi_pass") and ns.get("hi_pass_flow_metrics"):
+                raise SystemExit(hi_pass.METRICS_STRIPS)
     # the same for the spectrogram histories: where they do not fit beside the band-pass sessions of the first frame loop
     spec_run = None
     if ns.get("spectrogram") and indices:
