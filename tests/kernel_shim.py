@@ -13,7 +13,8 @@ definition of ILU(0) as a check of a given factor and the triangular solves' own
 the element kernels of fsi_assembly.hip the tables fsi_setup.hip hands them (element_structure), cell lists with materials and
 states (ElementCase), the project's oracle in extended precision as the reference of element vectors and matrices with the
 bound per block of a cell (K_RESIDUAL, K_JACOBIAN: four times what the oracle's own FP64 evaluation orders reach), and
-restatements of the geometry, the L2 integrand, the cell statistics and the probe interpolation in np.longdouble.  The
+restatements of the geometry, the L2 integrand, the cell statistics and the probe interpolation in np.longdouble, and the host
+side of the recycled GCR (fsi_gcr_host.hpp: the store's slots, the coefficient algebra of a cycle, the policies).  The
 builders are tested on the CPU (tests/test_kernel_references.py), so that a failure
 of a GPU test is one of the kernel, not of its reference."""
 from __future__ import annotations
@@ -69,6 +70,9 @@ _SIGS = {
     "shim_geometry": "llppp", "shim_elem_residual": "lll" + "p" * 10 + "ll" + "p" * 6,
     "shim_elem_jacobian": "iiilll" + "p" * 14 + "ippp", "shim_l2norm": "llpppp", "shim_stat_parts": "",
     "shim_cell_stats": "lllppppp", "shim_probe": "lllppppp",
+    "shim_gcr_store_op": "ilppppp", "shim_gcr_sizes": "lip", "shim_gcr_cycle_algebra": "lipppppppip",
+    "shim_gcr_cycle_end": "iidddi", "shim_gcr_orth_lost": "piddd", "shim_gcr_verdict_due": "dddiiiiiii",
+    "shim_gcr_verdict_skippable": "dddiiiiiiidd", "shim_gcr_tolerances": "pp",
 }
 LAUNCH_REFUSED = 2           # fsi_kernels.hpp: a launch function refused its arguments and launched nothing
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "d": C.c_double, "s": C.c_char_p}
@@ -2119,3 +2123,179 @@ def probe_reference(case, cells, bary, X):
     ab = np.concatenate([14 * U64 * np.einsum("na,nfa->nf", np.abs(Nb), np.abs(f)),
                          6 * U64 * np.einsum("na,na->n", np.abs(l), np.abs(loc[:, 60:]))[:, None]], axis=1)
     return val, ab
+
+
+# ---- the host side of the recycled GCR (fsi_gcr_host.hpp), restated ----------------------------------------------------------------
+GCR_WINDOW = 32              # columns of the FP64 window
+GCR_FLUSH_BATCH = 32         # directions made before a flush
+
+
+def gcr_ring(cap):
+    return min(64, cap // 2)
+
+
+def gcr_retire_batch(cap):
+    return max(1, min(32, cap // 4))
+
+
+class GcrStoreRef:
+    """GcrStore: slots of the kept directions.  born[slot] is the creation index of the direction in the slot (-1: free); a new
+    direction takes the free list's back, else the high-water mark hw; a full store retires the `batch` oldest directions born
+    at or after cap - ring; the window (a ring of GCR_WINDOW columns) mirrors the latest directions and loses retired ones."""
+
+    def __init__(self, cap):
+        self.cap = cap
+        self.reset()
+
+    def reset(self):
+        self.born = [-1] * self.cap
+        self.free = []
+        self.hw = self.made = 0
+        self.clear_window()
+
+    def clear_window(self):
+        self.hot = [-1] * GCR_WINDOW
+        self.hot_next = 0
+
+    def full(self):
+        return not self.free and self.hw == self.cap
+
+    def take(self):
+        """(slot, whether its column has never been written and must be cleared)"""
+        if self.free:
+            return self.free.pop(), False
+        self.hw += 1
+        return self.hw - 1, True
+
+    def set_born(self, slot):
+        self.born[slot] = self.made
+        self.made += 1
+
+    def retire(self, batch):
+        protect = self.cap - gcr_ring(self.cap)
+        cand = sorted((b, s) for s, b in enumerate(self.born[:self.hw]) if b >= protect)
+        out = [s for _, s in cand[:batch]]
+        for s in out:
+            self.born[s] = -1
+            self.free.append(s)
+        return out
+
+    def window_cols(self):
+        return max([k + 1 for k in range(GCR_WINDOW) if self.hot[k] >= 0], default=0)
+
+    def window_put(self, slot):
+        col = self.hot_next
+        self.hot[col] = slot
+        self.hot_next = (col + 1) % GCR_WINDOW
+        return col
+
+    def window_drop_retired(self):
+        out = [k for k in range(GCR_WINDOW) if self.hot[k] >= 0 and self.born[self.hot[k]] < 0]
+        for k in out:
+            self.hot[k] = -1
+        return out
+
+    def state(self):
+        return list(self.born), list(self.free), list(self.hot), (self.hw, self.made, self.hot_next)
+
+
+GCR_STORE_OPS = {"init": 0, "full": 1, "take": 2, "retire": 3, "window_put": 4, "window_drop_retired": 5, "set_born": 6,
+                 "window_cols": 7, "reset": 8, "clear_window": 9}
+
+
+def gcr_store_op(cap, op, arg=0):
+    """one operation on the shim's GcrStore: (its result as a list of ints, the store's state as GcrStoreRef.state() gives it)"""
+    res = np.full(cap + 2, -7, dtype=np.int32)
+    born, free, hot = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int32), np.zeros(GCR_WINDOW, dtype=np.int32)
+    scal = np.zeros(4, dtype=np.int64)
+    call("shim_gcr_store_op", GCR_STORE_OPS[op], arg, res, born, free, hot, scal)
+    if op in ("retire", "window_drop_retired"):
+        out = [int(v) for v in res[1:1 + res[0]]]
+    elif op == "take":
+        out = [int(res[0]), int(res[1])]
+    else:
+        out = [int(res[0])]
+    return out, ([int(v) for v in born], [int(v) for v in free[:scal[3]]], [int(v) for v in hot], tuple(int(v) for v in scal[:3]))
+
+
+def gcr_cycle_reference(cap, Z, slots, ms, htot, wn, alpha):
+    """GcrCycle's algebra in extended precision.  Z [cap][n]: what the slots hold - an explicit direction in an older slot, the
+    raw preconditioned vector in a slot of this cycle.  Direction k, stored in slots[k] after coefficients htot[k][:ms[k]], is
+        p_k = (Z[slots[k]] - sum_j htot[k][j] P_j) / wn[k],   P_j = p_k' if slots[k'] = j for an earlier k', else Z_j
+    (j = slots[k] and zero coefficients are left out), and x moves by sum_k alpha[k] p_k.  Returns (P [knew][n], X [n], and a
+    function bound(cn) -> (EP [knew][n], EX [n]) from the coefficient columns the library computed).
+
+    Bound: the library builds c_k[j] = (delta - sum_k' h_k' c_k'[j] - h_j) / wn in FP64: one rounding per addition into the
+    entry, one for the product, one for the division, so its own error is at most (additions + 2) 2^-52 times the sum of the
+    absolute values of the terms (2^-52: twice the unit round-off), and it inherits sum_k' |h_k'| E_k'[j] / wn from the
+    earlier directions of the cycle.  y[j] += alpha_k c_k[j]: knew additions and a product, on top of |alpha_k| E_k[j]."""
+    Z = np.asarray(Z, dtype=LD)
+    knew = len(slots)
+    P = np.zeros((knew, Z.shape[1]), dtype=LD)
+    newest = {}
+    terms = []                   # per direction: [(coefficient h, earlier direction k' or None, column j)]
+    for k in range(knew):
+        acc = Z[slots[k]].copy()
+        tk = []
+        for j in range(ms[k]):
+            h = htot[k][j]
+            if h == 0.0 or j == slots[k]:
+                continue
+            acc -= LD(h) * (P[newest[j]] if j in newest else Z[j])
+            tk.append((float(h), newest.get(j), j))
+        P[k] = acc / LD(wn[k])
+        newest[slots[k]] = k
+        terms.append(tk)
+    X = sum((LD(alpha[k]) * P[k] for k in range(knew)), np.zeros(Z.shape[1], dtype=LD))
+
+    def bound(cn):
+        cn = np.abs(np.asarray(cn, dtype=np.float64))
+        EC = np.zeros((knew, cap))
+        for k in range(knew):
+            adds, mag, inherit = np.zeros(cap), np.zeros(cap), np.zeros(cap)
+            mag[slots[k]] = 1.0
+            for h, kp, j in terms[k]:
+                if kp is None:
+                    adds[j] += 1
+                    mag[j] += abs(h)
+                else:
+                    adds += 1
+                    mag += abs(h) * cn[kp]
+                    inherit += abs(h) * EC[kp]
+            EC[k] = ((adds + 2) * 2.0 ** -52 * mag + inherit) / abs(wn[k])
+        a = np.abs(np.asarray(alpha, dtype=np.float64))
+        EY = (knew + 2) * 2.0 ** -52 * (a[:, None] * cn).sum(axis=0) + (a[:, None] * EC).sum(axis=0)
+        absZ = np.abs(Z).astype(np.float64)
+        return EC @ absZ, EY @ absZ
+    return P, X, bound
+
+
+def gcr_cycle_end_ref(since_gain, f32, rnorm, target, r_entry, store_full):
+    """0 go, 1 stagnated, 2 stalled (gcr_cycle_end)"""
+    if since_gain >= 40 and (f32 or rnorm <= 100.0 * target):
+        return 1
+    if f32 and since_gain >= 6 and rnorm <= 1e-4 * r_entry:
+        return 1
+    if since_gain >= 128 and store_full:
+        return 2
+    return 0
+
+
+def gcr_orth_lost_ref(h, w2, wn2, floor):
+    if not (wn2 > 0.0 and w2 > 0.0):
+        return False
+    hsq = 0.0
+    for v in h:
+        hsq += v * v
+    return abs(wn2 - (w2 - hsq)) / wn2 / np.sqrt(w2 / wn2) > floor
+
+
+def gcr_verdict_due_ref(rtol, rnorm, bnorm, cyc, cycle_its, stagnated, stalled, store_full, fell_back, suspect):
+    return bool(rtol < 1e-8 or fell_back or store_full or cycle_its > 64 or stalled or stagnated or suspect or cyc > 0
+                or rnorm > rtol * bnorm)
+
+
+def gcr_verdict_skippable_ref(rtol, rnorm, bnorm, cyc, cycle_its, stagnated, stalled, store_full, in_newton, final_cycle, skip_rtol,
+                              last_drift):
+    return bool(in_newton and final_cycle and rtol >= skip_rtol and rnorm <= rtol * bnorm and cycle_its <= GCR_WINDOW
+                and not stagnated and 0.0 <= last_drift <= 0.01 * rtol)

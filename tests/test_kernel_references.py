@@ -1025,3 +1025,154 @@ def test_l2_statistics_and_probe_references():
     got, b = ks.probe_reference(case, cells, bary, case.to_solver(X))
     x = np.einsum("na,nai->ni", bary, case.coords[case.tets[cells]])
     assert np.abs(got[:, :3] - x @ A.T).max() < 1e-15 and np.abs(got[:, 3:6] - [3.0, 4.0, 12.0]).max() < 1e-14
+
+
+# ---- the host side of the recycled GCR (fsi_gcr_host.hpp through the shim, against kernel_shim's restatements) ----------------
+@pytest.mark.parametrize("cap,ring,batch", [(8, 4, 2), (200, 64, 32)])
+def test_gcr_store_replays_a_scripted_run(cap, ring, batch):
+    """3 cap directions, retiring whenever the store is full: slots, born, free list and window after every operation"""
+    sizes = np.zeros(10, dtype=np.int64)
+    ks.call("shim_gcr_sizes", cap, 5, sizes)
+    assert list(sizes[:4]) == [ks.GCR_WINDOW, ks.GCR_FLUSH_BATCH, ring, batch] == [32, 32, ks.gcr_ring(cap), ks.gcr_retire_batch(cap)]
+    # the staging buffer: coefficients, their two sums, what rides along, the window's area behind the largest pass, all inside
+    coef, sums, lagged, updated, window, size = (int(v) for v in sizes[4:])
+    assert (sums, lagged, updated) == (5, 7, 7) and coef >= cap + 4 and window >= cap + 4 and size >= window + ks.GCR_WINDOW + 2
+    ref = ks.GcrStoreRef(cap)
+
+    def both(op, *arg):
+        got, state = ks.gcr_store_op(cap, op, *arg)
+        want = getattr(ref, op)(*arg) if op != "init" else None
+        assert state == ref.state(), (op, arg)
+        return got, want
+    both("init", cap)
+    cleared, retired_ever = [], set()
+    for k in range(3 * cap):
+        (full,), want = both("full")
+        assert bool(full) == want == (k >= cap and not ref.free)
+        if full:
+            age = list(ref.born)
+            gone, want = both("retire", batch)
+            assert gone == want and len(gone) == batch
+            assert all(age[s] >= cap - ring for s in gone) and all(ref.born[s] < 0 for s in gone)
+            assert sorted(age[s] for s in gone) == sorted(b for b in age if b >= cap - ring)[:batch]          # the oldest of the ring
+            cols, want = both("window_drop_retired")
+            assert cols == want
+            assert not set(gone) & {s for s in ref.hot if s >= 0}                  # a retired slot leaves the window
+            retired_ever |= set(gone)
+        else:
+            gone = []
+        hw_before = ref.hw
+        (slot, clear), want = both("take")
+        assert (slot, bool(clear)) == want
+        assert bool(clear) == (slot >= hw_before)          # beyond the old high-water mark: reported for clearing ...
+        if clear:
+            cleared.append(slot)
+        (col,), want = both("window_put", slot)
+        assert col == want == k % ks.GCR_WINDOW
+        both("set_born", slot)
+        assert ref.born[slot] == k
+        (nh,), want = both("window_cols")
+        assert nh == want
+        # no direction born before cap - ring is ever retired: the first cap - ring directions are all still there
+        assert sorted(b for b in ref.born if 0 <= b < cap - ring) == list(range(min(k + 1, cap - ring)))
+    assert cleared == list(range(cap))                     # ... exactly once
+    assert retired_ever and all(s >= cap - ring for s in retired_ever)          # (slot = birth index while the store grew)
+    both("clear_window")
+    both("reset")
+    assert ref.state() == ([-1] * cap, [], [-1] * ks.GCR_WINDOW, (0, 0, 0))
+
+
+@pytest.mark.parametrize("cap,nold,knew", [(8, 3, 1), (8, 3, 5), (40, 8, 32)])
+def test_gcr_cycle_algebra_expands_the_directions(cap, nold, knew):
+    """sum_j cn[k][j] Z_j against the recursively defined p_k, and sum_j y[j] Z_j against sum_k alpha_k p_k, in np.longdouble,
+    n = 40; coefficients on older slots and on directions of the same cycle, some exactly zero, one on the direction's own
+    slot (ignored).  Every direction of a cycle sits in a slot of its own, so 32 of them need a store of more than 8: that
+    case runs at cap = 40 with 8 older directions.  The flush arrays: y, then gcr_flush_width(knew) columns."""
+    n = 40
+    rng = np.random.default_rng(100 * cap + knew)
+    Z = rng.standard_normal((cap, n))
+    slots = np.arange(nold, nold + knew, dtype=np.int32)
+    ms = (slots + 1).astype(np.int32)                      # the store grows: every pass scans the slots so far, its own included
+    htot = rng.standard_normal((knew, cap))
+    htot[rng.random((knew, cap)) < 0.2] = 0.0
+    for k in range(knew):
+        htot[k, ms[k]:] = np.nan                           # never read
+    wn, alpha = rng.uniform(0.5, 2.0, knew), rng.standard_normal(knew)
+    y, cn = np.full(cap, 7.0), np.full((knew, cap), 7.0)
+    m = int(ms[-1])
+    kw = ks.load().shim_gcr_flush_width(knew)
+    pack = np.full((kw + 1) * m, 7.0)
+    ks.call("shim_gcr_cycle_algebra", cap, knew, slots, ms, htot, wn, alpha, y, cn, m, pack)
+    P, X, bound = ks.gcr_cycle_reference(cap, Z, slots, ms, htot, wn, alpha)
+    EP, EX = bound(cn)
+    LD = np.longdouble
+    ks.check((cn.astype(LD) @ Z.astype(LD)).astype(np.float64), P.astype(np.float64), EP + 1e-18 * np.abs(P).astype(np.float64), "p_k")
+    ks.check((y.astype(LD) @ Z.astype(LD)).astype(np.float64), X.astype(np.float64), EX + 1e-18 * np.abs(X).astype(np.float64), "x")
+    assert np.all(EP <= 1e-9 * (np.abs(cn) @ np.abs(Z))) and np.all(cn[:, m:] == 0) and np.all(y[m:] == 0)
+    want = np.zeros((kw + 1, m))
+    want[0], want[1:knew + 1] = y[:m], cn[:, :m]
+    np.testing.assert_array_equal(pack, want.ravel())
+
+
+def test_gcr_cycle_end_rule_at_its_thresholds():
+    R = 1.0          # |r| the cycle was entered with
+    rows = [  # since_gain, f32, rnorm, target, store_full -> 0 go, 1 stagnated, 2 stalled
+        (39, 0, 99e-9, 1e-9, 0, 0), (40, 0, 99e-9, 1e-9, 0, 1), (40, 0, 101e-9, 1e-9, 0, 0), (39, 0, 101e-9, 1e-9, 0, 0),
+        (39, 1, 1e-2, 1e-9, 0, 0), (40, 1, 1e-2, 1e-9, 0, 1), (40, 1, 101e-9, 1e-9, 0, 1), (39, 1, 99e-9 + 1e-3, 1e-9, 0, 0),
+        (5, 1, 1e-4 * R, 1e-9, 0, 0), (6, 1, 1e-4 * R, 1e-9, 0, 1), (6, 1, 1.01e-4 * R, 1e-9, 0, 0), (6, 0, 1e-4 * R, 1e-9, 0, 0),
+        (127, 0, 1e-2, 1e-9, 1, 0), (128, 0, 1e-2, 1e-9, 1, 2), (128, 0, 1e-2, 1e-9, 0, 0), (127, 0, 1e-2, 1e-9, 0, 0),
+        (128, 1, 1e-2, 1e-9, 1, 1)]
+    for since, f32, rnorm, target, full, want in rows:
+        got = ks.status("shim_gcr_cycle_end", since, f32, rnorm, target, R, full)
+        assert got == want == ks.gcr_cycle_end_ref(since, f32, rnorm, target, R, full), (since, f32, rnorm, target, full)
+
+
+def test_gcr_orthogonality_test_at_the_floors():
+    """disc / canc = | |w'|^2 - (|w|^2 - |h|^2) | / |w'|^2 / sqrt(|w|^2 / |w'|^2) against orth_floor32 = 3e-7 and orth_floor64 = 1e-9"""
+    h = np.array([3.0, 4.0, 0.0, 12.0])                    # |h|^2 = 169, |w|^2 = 170: |w|^2 - |h|^2 = 1 exactly
+    for floor in (3e-7, 1e-9):
+        for factor, want in ((0.9, 0), (1.1, 1)):
+            d = factor * floor * np.sqrt(170.0)            # wn2 = 1 + d: disc = d / wn2, canc = sqrt(170 / wn2)
+            wn2 = 1.0 + d
+            got = ks.status("shim_gcr_orth_lost", h, 4, 170.0, wn2, floor)
+            assert got == want == int(ks.gcr_orth_lost_ref(h, 170.0, wn2, floor)), (floor, factor)
+    assert ks.status("shim_gcr_orth_lost", h, 4, 170.0, 0.0, 1e-9) == 0 and ks.status("shim_gcr_orth_lost", h, 4, 0.0, 1.0, 1e-9) == 0
+
+
+def test_gcr_verdict_policies_term_by_term():
+    # FP64 basis, verdict due: a quiet first cycle is not judged; every term alone makes it due
+    quiet = dict(rtol=1e-5, rnorm=0.9e-5, bnorm=1.0, cyc=0, cycle_its=64, stagnated=0, stalled=0, store_full=0, fell_back=0, suspect=0)
+    cases = [({}, 0), (dict(rtol=0.99e-8, rnorm=1e-9), 1), (dict(rtol=1e-8, rnorm=0.9e-8), 0), (dict(fell_back=1), 1), (dict(store_full=1), 1),
+             (dict(cycle_its=65), 1), (dict(stalled=1), 1), (dict(stagnated=1), 1), (dict(suspect=1), 1), (dict(cyc=1), 1),
+             (dict(rnorm=1.01e-5), 1), (dict(rnorm=1e-5), 0)]
+    for change, want in cases:
+        a = list({**quiet, **change}.values())
+        assert ks.status("shim_gcr_verdict_due", *a) == want == int(ks.gcr_verdict_due_ref(*a)), change
+    # FP32 basis, verdict may be skipped: everything in favour skips; every term alone forbids it
+    fine = dict(rtol=1e-3, rnorm=0.9e-3, bnorm=1.0, cyc=0, cycle_its=32, stagnated=0, stalled=0, store_full=0, in_newton=1, final_cycle=1,
+                skip_rtol=3e-4, last_drift=0.9e-5)
+    cases = [({}, 1), (dict(in_newton=0), 0), (dict(final_cycle=0), 0), (dict(rtol=2.9e-4, rnorm=1e-4, last_drift=1e-6), 0),
+             (dict(rtol=3e-4, rnorm=1e-4, last_drift=1e-6), 1), (dict(rnorm=1.01e-3), 0), (dict(rnorm=1e-3), 1), (dict(cycle_its=33), 0),
+             (dict(stagnated=1), 0), (dict(last_drift=-1.0), 0), (dict(last_drift=0.0), 1), (dict(last_drift=1.01e-5), 0),
+             (dict(stalled=1, store_full=1, cyc=3), 1)]
+    for change, want in cases:
+        a = list({**fine, **change}.values())
+        assert ks.status("shim_gcr_verdict_skippable", *a) == want == int(ks.gcr_verdict_skippable_ref(*a)), change
+
+
+def test_gcr_tolerance_policies():
+    """the second-pass threshold, where an adaptive solve starts and how it tightens, the storage of a lifetime's basis"""
+    def run(f32=0, part=0, rtol_floor=1e-5, forced=0.0, rtol=1e-3, utol=0.0, ratio=0.0, floor=1e-6, bu=1.0, ru=1.0, hint=0.0, f32floor=1e-7):
+        out = np.zeros(4)
+        ks.call("shim_gcr_tolerances", np.array([f32, part, rtol_floor, forced, rtol, utol, ratio, floor, bu, ru, hint, f32floor], dtype=np.float64), out)
+        return out
+    assert run(f32=1)[0] == 0.01 and run(f32=1, part=1)[0] == 0.01 and run(f32=1, forced=0.3)[0] == 0.3
+    assert run(rtol_floor=1e-5)[0] == 0.01 and run(rtol_floor=1e-12)[0] == 0.5 and run(rtol_floor=1e-10)[0] == 1.0 / (1e-10 * 9e10)
+    assert run(rtol_floor=1e-5, part=1)[0] == 0.1 and run(rtol_floor=1e-12, part=1)[0] == 0.5 and run(part=1, forced=0.02)[0] == 0.02
+    assert run(rtol=1e-3)[1] == 1e-3 and run(rtol=1e-3, utol=1e-4, ratio=0.0)[1] == 1e-3          # not adaptive / nothing known yet
+    assert run(rtol=1e-3, utol=1e-4, ratio=2.0)[1] == 0.7 * 1e-4 / 2.0 and run(rtol=1e-3, utol=1e-4, ratio=1e-3)[1] == 1e-3
+    assert run(rtol=1e-3, utol=1e-4, ratio=1e6)[1] == 1e-6 and run(rtol=1e-6, utol=1e-4, ratio=1e6, floor=1e-6)[1] == 1e-6
+    assert run(rtol=1e-3, utol=1e-4, ru=1e-4)[2] == 0.5e-3 and run(rtol=1e-3, utol=1e-4, ru=1e-3)[2] == 1e-3 * 0.05
+    assert run(rtol=1e-3, utol=1e-4, ru=1.0)[2] == 1e-3 * 0.02 and run(rtol=1e-5, utol=1e-4, ru=1.0, floor=1e-6)[2] == 1e-6
+    assert run(rtol=1e-6)[3] == 1 and run(rtol=1e-7)[3] == 0 and run(rtol=1e-3, hint=1e-8)[3] == 0 and run(rtol=1e-8, hint=1e-3)[3] == 0
+    assert run(rtol=1e-3, hint=1.1e-7)[3] == 1

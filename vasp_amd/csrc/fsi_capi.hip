@@ -617,7 +617,7 @@ int fsi_get_timers(FsiCtx* ctx, FsiTimers* out, int reset) {
                    ctx->smp_db.t.ms, ctx->smp_db.t.calls, (int64_t)ctx->dd_db.n / 3, ctx->N2, ctx->smp_sc.t.ms, ctx->smp_sc.t.calls,
                    (int64_t)(ctx->dd_is_scalar && ctx->sweeps_fp32) + (ctx->tiled ? 2 : 0), (int64_t)ctx->tile_ulist.n,
                    ctx->ortho_q_cols, ctx->ortho_q_launches, ctx->ortho_z_cols, ctx->ortho_z_launches,
-                   (int64_t)(ctx->kry_fp32 ? 4 : 8), ctx->ldq, ctx->ldz, ctx->kry_hw, ctx->kry_cap,
+                   (int64_t)(ctx->kry_fp32 ? 4 : 8), ctx->ldq, ctx->ldz, ctx->kry.hw, ctx->kry.cap,
                    (int64_t)ctx->s_cols.n, ctx->V, ctx->t_flush.ms, ctx->t_flush.calls, ctx->smp_sch.t.ms, ctx->smp_sch.t.calls,
                    (int64_t)((ctx->schur_fp32 && ctx->s_vals32.p) ? ((ctx->schur_tiled && ctx->sweeps_fp16 && ctx->s_rec.p) ? 0 : 4) : 8),
                    (int64_t)ctx->h_nadj.size(), (int64_t)ctx->h_padj.size(),

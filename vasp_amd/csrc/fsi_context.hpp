@@ -10,6 +10,7 @@
 #include "../../include/vaspfsi.h"
 #include "fsi_band.hpp"
 #include "fsi_element.hpp"
+#include "fsi_gcr_host.hpp"
 
 namespace fsi {
 struct BcrData;               // exact solve of the solid cycle's coarse level by block cyclic reduction (fsi_bcr.hip)
@@ -303,28 +304,23 @@ struct FsiCtx {
 
   // Krylov recycling space (GCR): Q = A P (orthonormal; FP32 or FP64 storage) and the directions P.  Directions made
   // during the current solve are held as raw preconditioned vectors in KZ plus coefficient columns on the host
-  // (kry_cn), and become explicit at the next flush (fsi_gcr.hip).
-  int64_t kry_cap = 0, kry_m = 0;            // kry_m: directions made since the last Jacobian (statistics / ring age)
-  int64_t kry_hw = 0;                        // slots in use (columns scanned by the kernels), <= kry_cap
+  // (GcrCycle), and become explicit at the next flush (fsi_gcr.hip).
+  fsi::GcrStore kry;                         // capacity, slots in use, age and free list of the slots, the window's slots (fsi_gcr_host.hpp)
   int kry_fp32 = 0;                          // storage of Q during the current Jacobian lifetime: 0 FP64, 1 FP32
   int kry_fp32_policy = 2;                   // (3: was 2, fell back to FP64 after a failed cycle)  FSI_KRYLOV_FP32: 0 never, 1 always, 2 (default) decided by the first solve after a
-                                             // Jacobian refresh: FP32 iff that solve's tolerance is >= 1e-7 (see solve_gcr)
+                                             // Jacobian refresh: FP32 iff the lowest tolerance to expect is above FsiTuning.krylov_fp32_floor (gcr_basis_fp32)
   int64_t ldq = 0, ldz = 0;                  // column strides (elements)
-  fsi::DevBuf<unsigned char> KQ;             // [kry_cap][ldq] float or double
-  fsi::DevBuf<double> KZ;                    // [kry_cap][ldz]
+  fsi::DevBuf<unsigned char> KQ;             // [kry.cap][ldq] float or double
+  fsi::DevBuf<double> KZ;                    // [kry.cap][ldz]
   // FP32 storage only: the directions of the current solve cycle also in FP64 (a window of 32).  A M^-1 r_k is nearly
   // parallel to the previous direction after a step of little progress - a cancellation of 1e5 and more, which is
   // taken out exactly against this window before the FP32 columns see the vector.
-  fsi::DevBuf<double> KQh, hcoef_hot;        // [32][ldq], [40]
-  std::vector<int32_t> hot_slots;            // slot of each window column (-1: empty)
-  int hot_next = 0;
-  fsi::DevBuf<double> hcoef;                 // [kry_cap + 2] device: h = Q^T w, w.w, w.r
+  fsi::DevBuf<double> KQh, hcoef_hot;        // [GCR_WINDOW][ldq], [gcr_coef_len(GCR_WINDOW)]
+  fsi::DevBuf<double> hcoef;                 // [gcr_coef_len(kry.cap)] device: h = Q^T w, w.w, w.r
   fsi::DevBuf<double> gcr_out;               // [8] device: small reduction results
-  fsi::DevBuf<double> gcr_y, gcr_cn;         // [kry_cap], [32][kry_cap] device copies of the flush coefficients
-  fsi::DevBuf<int32_t> gcr_slots;            // [32]
-  double* gcr_host = nullptr;                // pinned [kry_cap + 16]
-  std::vector<int64_t> kry_born;             // [kry_cap] creation index of the direction in each slot (-1: free)
-  std::vector<int32_t> kry_free;             // free slots (retired in batches when the store is full)
+  fsi::DevBuf<double> gcr_y, gcr_cn;         // [kry.cap], [GCR_FLUSH_BATCH][kry.cap] device copies of the flush coefficients
+  fsi::DevBuf<int32_t> gcr_slots;            // [GCR_FLUSH_BATCH]
+  double* gcr_host = nullptr;                // pinned [GcrStaging::size()]
   double gs_rtol = 0.0;                      // tightest linear tolerance asked for since the last Jacobian (re-orthogonalisation criterion)
   int64_t ortho_q_cols = 0, ortho_z_cols = 0, ortho_q_launches = 0, ortho_z_launches = 0;   // columns streamed (exact bytes of the orthogonalisation)
   fsi::DevBuf<float> A32;                         // FP32 copy of A for the products inside the Krylov iterations (FSI_OPERATOR_FP32, default on)
@@ -339,7 +335,7 @@ struct FsiCtx {
   bool drows_ok = false;
   int64_t drows_products = 0;
   bool gcr_stagnated = false;                // the last cycle ended on 40 iterations without a 10 % gain
-  bool gcr_stalled = false;                  // ... on 80 iterations without a 10 % gain far from its target (truncated recurrence stuck)
+  bool gcr_stalled = false;                  // ... on 128 iterations without a 10 % gain far from its target, the store full (truncated recurrence stuck)
   double f32_cycle_floor = 1e-6;             // FP32 basis: a cycle reduces the residual by at most this factor before the FP64 verdict
   double f32_verdict_skip_rtol = 3e-4;       // FP32 basis: answers asked for at or above this may skip the FP64 verdict (see solve_gcr)
   double f32_last_drift = -1.0;              // |true - recurrence residual| / |b| of the last verified FP32 cycle on the present store

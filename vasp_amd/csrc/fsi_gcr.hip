@@ -1,4 +1,4 @@
-// Orthogonalisation kernels of the recycled GCR (solve_gcr in fsi_capi.hip).
+// Orthogonalisation kernels of the recycled GCR (solve_gcr in fsi_krylov.hip).
 //
 // The kept space is  Q = A P  (orthonormal columns) and the search directions P.  What streams through HBM in every
 // Krylov iteration is Q only: the coefficients h = Q^T w (k_gcr_dots) and the update w -= Q h (k_gcr_axpy, which also

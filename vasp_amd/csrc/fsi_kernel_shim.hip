@@ -493,6 +493,83 @@ int shim_cheb_coefficients(double lmax, double kappa, int fourth, int n, double*
   return 0;
 }
 
+// ---- fsi_gcr_host.hpp: the host side of the recycled GCR, no device call ------------------------------------------------------
+// One operation on a store the shim keeps, then the store's whole state: born [cap], free [cap] (the first scal[3] entries),
+// hot [GCR_WINDOW], scal = {hw, made, hot_next, free.size()}.  op 0 init(arg), 1 full() -> res[0], 2 take() -> res[0] slot,
+// res[1] clear, 3 retire(arg) -> res[0] count, res[1..] slots, 4 window_put(arg) -> res[0] column, 5 window_drop_retired() ->
+// res[0] count, res[1..] columns, 6 set_born(arg), 7 window_cols() -> res[0], 8 reset(), 9 clear_window().  res: [cap + 1] at least.
+int shim_gcr_store_op(int op, int64_t arg, int32_t* res, int64_t* born, int32_t* free_slots, int32_t* hot, int64_t* scal) {
+  static GcrStore s;
+  if (op != 0 && s.cap == 0) { g_err = "shim_gcr_store_op: no store (op 0 first)"; return 1; }
+  switch (op) {
+    case 0: s = GcrStore(); s.init(arg); break;
+    case 1: res[0] = s.full(); break;
+    case 2: { bool clear = false; res[0] = s.take(&clear); res[1] = clear; break; }
+    case 3: { const std::vector<int32_t> out = s.retire((int)arg); res[0] = (int32_t)out.size(); std::copy(out.begin(), out.end(), res + 1); break; }
+    case 4: res[0] = s.window_put((int)arg); break;
+    case 5: { const std::vector<int> out = s.window_drop_retired(); res[0] = (int32_t)out.size(); std::copy(out.begin(), out.end(), res + 1); break; }
+    case 6: s.set_born((int)arg); break;
+    case 7: res[0] = s.window_cols(); break;
+    case 8: s.reset(); break;
+    case 9: s.clear_window(); break;
+    default: g_err = "shim_gcr_store_op: unknown operation"; return 1;
+  }
+  std::copy(s.born.begin(), s.born.end(), born);
+  std::copy(s.free.begin(), s.free.end(), free_slots);
+  std::copy(s.hot_slots.begin(), s.hot_slots.end(), hot);
+  scal[0] = s.hw; scal[1] = s.made; scal[2] = s.hot_next; scal[3] = (int64_t)s.free.size();
+  return 0;
+}
+// out = {GCR_WINDOW, GCR_FLUSH_BATCH, gcr_ring(cap), gcr_retire_batch(cap), gcr_coef_len(cap), and of GcrStaging{cap}: sums(m),
+// lagged(m), updated(m), window(), size()}
+int shim_gcr_sizes(int64_t cap, int m, int64_t* out) {
+  const GcrStaging lay{cap};
+  const int64_t v[10] = {GCR_WINDOW, GCR_FLUSH_BATCH, gcr_ring(cap), gcr_retire_batch(cap), (int64_t)gcr_coef_len(cap),
+                         lay.sums(m), lay.lagged(m), lay.updated(m), lay.window(), (int64_t)lay.size()};
+  std::copy(v, v + 10, out);
+  return 0;
+}
+// GcrCycle: knew directions added in turn - slots [knew], over ms[k] columns with coefficients htot [knew][cap], wn, alpha
+// [knew] - give y [cap] and cn [knew][cap]; pack [(gcr_flush_width(knew) + 1) m]: what a flush over m columns uploads; then
+// clear(), after which nothing may be pending
+int shim_gcr_cycle_algebra(int64_t cap, int knew, const int32_t* slots, const int32_t* ms, const double* htot, const double* wn,
+                           const double* alpha, double* y, double* cn, int m, double* pack) {
+  GcrCycle cy(cap);
+  for (int k = 0; k < knew; ++k) cy.add(slots[k], htot + (size_t)k * cap, ms[k], wn[k], alpha[k]);
+  if (cy.knew() != knew || !cy.pending(m)) { g_err = "shim_gcr_cycle_algebra: nothing pending after add()"; return 1; }
+  std::copy(cy.y.begin(), cy.y.end(), y);
+  for (int k = 0; k < knew; ++k) std::copy(cy.cn[k].begin(), cy.cn[k].end(), cn + (size_t)k * cap);
+  const std::vector<double> p = cy.pack(m, gcr_flush_width(knew));
+  std::copy(p.begin(), p.end(), pack);
+  cy.clear();
+  if (cy.knew() != 0 || cy.pending((int)cap)) { g_err = "shim_gcr_cycle_algebra: pending after clear()"; return 1; }
+  return 0;
+}
+// the policies: the status is the answer (gcr_cycle_end: 0 go, 1 stagnated, 2 stalled; the predicates: 0 / 1)
+int shim_gcr_cycle_end(int since_gain, int f32, double rnorm, double target, double r_entry, int store_full) {
+  return (int)gcr_cycle_end(since_gain, f32 != 0, rnorm, target, r_entry, store_full != 0);
+}
+int shim_gcr_orth_lost(const double* h, int m, double w2, double wn2, double floor) { return gcr_orth_lost(h, m, w2, wn2, floor); }
+int shim_gcr_verdict_due(double rtol, double rnorm, double bnorm, int cyc, int cycle_its, int stagnated, int stalled, int store_full,
+                         int fell_back, int suspect) {
+  return gcr_verdict_due(GcrVerdictIn{rtol, rnorm, bnorm, cyc, cycle_its, stagnated != 0, stalled != 0, store_full != 0}, fell_back != 0, suspect != 0);
+}
+int shim_gcr_verdict_skippable(double rtol, double rnorm, double bnorm, int cyc, int cycle_its, int stagnated, int stalled,
+                               int store_full, int in_newton, int final_cycle, double skip_rtol, double last_drift) {
+  return gcr_verdict_skippable(GcrVerdictIn{rtol, rnorm, bnorm, cyc, cycle_its, stagnated != 0, stalled != 0, store_full != 0},
+                               in_newton != 0, final_cycle != 0, skip_rtol, last_drift);
+}
+// out = {gcr_reorth_threshold(f32, part, rtol_floor, forced), gcr_adaptive_start(rtol, utol, utol_ratio, utol_floor),
+// gcr_adaptive_tighten(rtol, utol, b_unscaled, ru, utol_floor), gcr_basis_fp32(tol_hint, rtol, fp32_floor)} from in = {f32, part,
+// rtol_floor, forced, rtol, utol, utol_ratio, utol_floor, b_unscaled, ru, tol_hint, fp32_floor}
+int shim_gcr_tolerances(const double* in, double* out) {
+  out[0] = gcr_reorth_threshold(in[0] != 0.0, in[1] != 0.0, in[2], in[3]);
+  out[1] = gcr_adaptive_start(in[4], in[5], in[6], in[7]);
+  out[2] = gcr_adaptive_tighten(in[4], in[5], in[8], in[9], in[7]);
+  out[3] = gcr_basis_fp32(in[10], in[4], in[11]) ? 1.0 : 0.0;
+  return 0;
+}
+
 // ---- fsi_solver.hip: the monolithic matrix's structure and products -----------------------------------------------------------
 // Node graph: nadj_ptr [N2 + 1], nadj [npairs = nadj_ptr[N2]]; pressure graph: padj_ptr [N2 + 1], padj [padj_ptr[N2]]; vrank [V];
 // rows: 6 N2 node rows then V pressure rows, rowptr [6 N2 + V + 1], nnz = rowptr[6 N2 + V].  x and y: 6 N2 + V entries.

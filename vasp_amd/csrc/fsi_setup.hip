@@ -824,18 +824,16 @@ static int size_krylov_store(FsiCtx* ctx, size_t free_b) {
   // (4.6 Newton iterations per step); a full store rotates, and the 100-step run is 5 % faster without that (12.0 against
   // 11.4 Newton-it/s); the 20-step bench does not notice.  Half of the free HBM remains the upper limit.
   cap = std::max<int64_t>(8, std::min<int64_t>(cap, ctx->tune.krylov_capacity));
-  ctx->kry_cap = cap;
+  ctx->kry.init(cap);
   HIPCHK(ctx->KZ.alloc((size_t)cap * ctx->ldz));
   HIPCHK(ctx->KQ.alloc((size_t)cap * ctx->ldq * (ctx->kry_fp32_policy == 1 ? 4 : 8)));      // FP64-sized unless FP32 is forced
-  HIPCHK(ctx->hcoef.alloc(cap + 4));
-  if (ctx->kry_fp32_policy != 0) { HIPCHK(ctx->KQh.alloc((size_t)32 * ctx->ldq)); HIPCHK(ctx->hcoef_hot.alloc(40)); }
-  ctx->hot_slots.assign(32, -1);
+  HIPCHK(ctx->hcoef.alloc(gcr_coef_len(cap)));
+  if (ctx->kry_fp32_policy != 0) { HIPCHK(ctx->KQh.alloc((size_t)GCR_WINDOW * ctx->ldq)); HIPCHK(ctx->hcoef_hot.alloc(gcr_coef_len(GCR_WINDOW))); }
   HIPCHK(ctx->gcr_out.alloc(8));
   HIPCHK(ctx->gcr_y.alloc(cap));
-  HIPCHK(ctx->gcr_cn.alloc((size_t)32 * cap));
-  HIPCHK(ctx->gcr_slots.alloc(32));
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->gcr_host), (size_t)(cap + 64) * sizeof(double), hipHostMallocDefault));
-  ctx->kry_born.assign(cap, -1);
+  HIPCHK(ctx->gcr_cn.alloc((size_t)GCR_FLUSH_BATCH * cap));
+  HIPCHK(ctx->gcr_slots.alloc(GCR_FLUSH_BATCH));
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->gcr_host), GcrStaging{cap}.size() * sizeof(double), hipHostMallocDefault));
   gcr_reset(ctx);
   HIPCHK(ctx->scratch.alloc(std::max<size_t>(24576, (size_t)(cap + 2) * 256 + 16)));
   return FSI_OK;

@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void k_spmv(int64_t n, const int64_t* __restri
 // 8 + 4/6 instead of 12 bytes per entry, a sixth of the gathers, and six independent value streams in flight per lane.
 // VT = float: the FP32 copy of the (row-equilibrated, |entries| <= 1) Jacobian that the Krylov iterations of a loose-tolerance
 // lifetime multiply with (4 + 4/6 bytes per entry); x, y and the accumulation stay FP64, and every answer is checked
-// against the FP64 matrix before it leaves solve_gcr (fsi_capi.hip).
+// against the FP64 matrix before it leaves solve_gcr (fsi_krylov.hip).
 // XCD = true: workgroups are dealt round-robin to the 8 XCDs, each with its own L2; giving XCD k the k-th eighth of the
 // nodes (instead of every eighth workgroup of one sweep over all nodes) keeps the x entries a node's neighbours gather
 // inside ONE L2 instead of fetching them into all eight.
