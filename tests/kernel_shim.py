@@ -1,7 +1,9 @@
 """ctypes loader of ``vasp_amd/libfsi_kernel_shim.so`` (vasp_amd/csrc/fsi_kernel_shim.hip) and the host-side reference builders
 of the kernel tests (tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py, tests/test_gpu_product_kernels.py,
 tests/test_gpu_coarse_kernels.py, tests/test_gpu_bcr_kernels.py, tests/test_gpu_block_kernels.py, tests/test_gpu_ilu_kernels.py,
-tests/test_gpu_vector_kernels.py, tests/test_gpu_element_kernels.py, tests/test_gpu_element_jacobian.py).
+tests/test_gpu_vector_kernels.py, tests/test_gpu_element_kernels.py, tests/test_gpu_element_jacobian.py).  Helper modules beside
+this one: tests/fp32_records.py, tests/chain_consumers.py, and tests/block_apply.py - one whole application of the block
+preconditioner restated stage by stage (tests/test_block_apply_reference.py on the CPU, tests/test_gpu_block_application.py).
 
 The shim runs ONE ``fsi::launch_*`` call of libvaspfsi.so on host arrays; the builders restate, in numpy, what the library's
 host code hands those kernels: the LDS tiles of a graph (fsi_setup.hip build_tiles, node tiles and Schur tiles), the FP16 records of
@@ -40,7 +42,7 @@ _SIGS = {
     "shim_spmv_sb": "lppppp", "shim_sweep_sb_b3": "lppppffppppi", "shim_sweep_sb_h": "lpppffpppp",
     "shim_cheb_init_b3": "lppfppp", "shim_cheb_step_b3": "lppffppp",
     "shim_sweep_csr_f64": "lppppddpppp", "shim_sweep_csr_mixed": "lpppppddpppp", "shim_sweep_schur_tiled": "ilipppppddpppp",
-    "shim_ctx_info": "ppi", "shim_ctx_array": "psppp", "shim_tile_limit": "", "shim_cheb_coefficients": "ddiippp",
+    "shim_ctx_info": "ppi", "shim_ctx_apply_info": "ppipi", "shim_ctx_array": "psppp", "shim_tile_limit": "", "shim_cheb_coefficients": "ddiippp",
     "shim_expand_cols": "llpppppppp", "shim_spmv": "lpppplpi", "shim_spmv_node6": "llpppppplppp", "shim_drows_extract": "lpppppp",
     "shim_pad_cols32": "lpppp", "shim_pad_vals32": "llppplllpli", "shim_spmv_node6p": "llppplpplppplppp",
     "shim_matrix_finish": "lppppplpp", "shim_ctx_spmv": "pippp",
@@ -142,7 +144,7 @@ _UNSIGNED = {"dd_rec", "vv_rec", "sb_rec", "s_rec"}
 _FLOAT = {"dd_chat", "vv_db32", "sb_vals", "sb_binv12", "s_vals", "s_vals32", "s_dinv", "dd_db", "rowscale", "A", "A32", "Ad64", "Ad32",
           "mg_pw", "mg_chw", "mg_Ac", "mg_cc", "mg_d0", "mg_dcinv4", "sbmg_pw", "sbmg_chw", "sbmg_cvals", "sbmg_cbinv12",
           "sb_binv9", "sb_dinv", "dd_dinv32", "vvf_dinv32", "Mdd.vals", "Mvv.vals", "Adv", "Avp", "Apv", "App", "Avp32", "Apv32",
-          "vv_db", "adv_db", "dd_db32", "vv_dinv", "mask_f", "mask_s", "ss_vals", "LU"}
+          "vv_db", "adv_db", "dd_db32", "vv_dinv", "mask_f", "mask_s", "ss_vals", "LU", "blk", "sbmg_work", "mg_work", "ones32", "mg_cones"}
 
 
 def ctx_info(ctx) -> dict:

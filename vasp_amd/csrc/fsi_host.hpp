@@ -87,6 +87,7 @@ int rebuild_matrix_bc(FsiCtx* ctx);
 // fsi_precond.hip
 int precondition(FsiCtx* ctx, const double* r, double* z);
 int precondition_block(FsiCtx* ctx, const double* r, double* z);
+bool block_two_chains(const FsiCtx* ctx);      // the configuration in which precondition_block issues two chains
 int refresh_preconditioner(FsiCtx* ctx);
 // fsi_bcr.hip: exact solve of the solid cycle's coarse level (block cyclic reduction)
 struct BcrPlanStats {

@@ -8,6 +8,10 @@
 // the launch refused its arguments and launched nothing; the outputs are still copied back).
 //
 // Vectors of the node-block sweeps are float4 per node (component 3 is padding), as the preconditioner holds them.
+//
+// A live context is read through shim_ctx_info / shim_ctx_coarse / shim_ctx_array (device arrays by name; `blk`, the work vectors
+// of one preconditioner application, and the two cycles' coarse work areas `sbmg_work` / `mg_work` among them) and
+// shim_ctx_apply_info (what precondition_block branches on and the sweep counts it takes): tests/block_apply.py.
 #include "fsi_cheb.hpp"
 #include "fsi_host.hpp"
 #include "fsi_kernels.hpp"
@@ -1935,6 +1939,25 @@ int shim_ctx_info(const FsiCtx* ctx, int64_t* out, int nout) {
   for (int i = 0; i < nout && i < k; ++i) out[i] = v[i];
   return k;
 }
+// What precondition_block (fsi_precond.hip) branches on and the sweep counts it takes, by position (new fields go at the end:
+// tests/block_apply.py reads them by position).  iout: two_chains, drop_last_sweep, experiment, vel_jacobi, dd_early, solid_fp32,
+// solid_block_jacobi, solid_fused, sweeps_fp32, sweeps_fp16, fused_sweeps, tiled, schur_fp32, schur_tiled, cheb4, cheb_its_s,
+// cheb_its_f, cheb_its_p, cheb_its_d, sbmg_pre, sbmg_post, sbmg_cits, mg_pre, mg_post, mg_cits, xs_zeroed (0 / 1: the solid
+// predictor's vector is known to be zero off the solid nodes), have s_vals32, s_rec, sb_rec, sb_rec32, vv_rec32 (0 / 1 each),
+// debug_prec_apply.  dout: sbmg_alpha, mg_alpha, sbmg_ckappa, mg_ckappa, bcr_shift.  Returns the number of iout fields.
+int shim_ctx_apply_info(const FsiCtx* ctx, int64_t* iout, int ni, double* dout, int nd) {
+  const int64_t v[] = {fsi::host::block_two_chains(ctx), (ctx->tune.experiment & 4) == 0, ctx->tune.experiment, ctx->vel_jacobi,
+                       ctx->dd_early, ctx->solid_fp32, ctx->solid_block_jacobi, ctx->solid_fused, ctx->sweeps_fp32, ctx->sweeps_fp16,
+                       ctx->fused_sweeps, ctx->tiled, ctx->schur_fp32, ctx->schur_tiled, ctx->cheb4, ctx->cheb_its_s, ctx->cheb_its_f,
+                       ctx->cheb_its_p, ctx->cheb_its_d, ctx->sbmg_pre, ctx->sbmg_post, ctx->sbmg_cits, ctx->mg_pre, ctx->mg_post,
+                       ctx->mg_cits, ctx->xs_zeroed != nullptr, ctx->s_vals32.p != nullptr, ctx->s_rec.p != nullptr,
+                       ctx->sb_rec.p != nullptr, ctx->sb_rec32.p != nullptr, ctx->vv_rec32.p != nullptr, ctx->debug_prec_apply};
+  const double w[] = {ctx->sbmg_alpha, ctx->mg_alpha, ctx->sbmg_ckappa, ctx->mg_ckappa, ctx->tune.bcr_shift};
+  const int k = (int)(sizeof(v) / sizeof(v[0])), kd = (int)(sizeof(w) / sizeof(w[0]));
+  for (int i = 0; i < ni && i < k; ++i) iout[i] = v[i];
+  for (int i = 0; i < nd && i < kd; ++i) dout[i] = w[i];
+  return k;
+}
 // the factor of the solid columns' displacement entries folded into the velocity block (Avv~ = Avv + ktheta Avd, k_extract_blocks)
 double shim_ctx_ktheta(const FsiCtx* ctx) { return ctx->scheme.k * ctx->scheme.th0; }
 // the coarse levels' eigenvalue bounds: 0 mg_gersh, 1 sbmg_gersh (the row-sum bounds of the last rebuild), 2 mg_clmax, 3 sbmg_clmax
@@ -1984,7 +2007,8 @@ int shim_ctx_array(const FsiCtx* ctx, const char* name, void* host, int64_t* cou
                          E(App),        E(Avp32),     E(Apv32),   E(vv_db),      E(adv_db),      E(dd_db32),     E(adv_rowmask),
                          E(vv_dinv),    E(mask_f),    E(mask_s),  E(ss_vals),    E(ss_src),      E(ss_rowptr),   E(ss_cols),
                          E(ss_diagpos), E(fs_rows),   E(fs_ptr),  E(fs_col),     E(fs_src),      E(sb_row),      E(sb_src),
-                         E(sb_stride),  E(s_diagpos),  E(LU),       E(user2solver)};
+                         E(sb_stride),  E(s_diagpos),  E(LU),       E(user2solver), E(blk),        E(sbmg_work),   E(mg_work),
+                         E(ones32),     E(mg_cones)};
 #undef E
   for (const Entry& t : table) {
     if (std::strcmp(t.name, name) != 0) continue;

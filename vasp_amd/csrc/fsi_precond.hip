@@ -416,6 +416,14 @@ void debug_print_parts(const BlockApply& a) {
 namespace fsi {
 namespace host {
 
+// The two-chain condition of precondition_block (see there); the test shim reads it too.
+bool block_two_chains(const FsiCtx* ctx) {
+  return ctx->prec_streams && ctx->stream2 && ctx->solid_fp32 && ctx->solid_block_jacobi && ctx->solid_fused && ctx->sbmg_ready &&
+         ctx->sweeps_fp32 && ctx->tiled && ctx->fused_sweeps && ctx->cheb_its_p > 0 &&
+         ((ctx->schur_fp32 == 1 && ctx->s_vals32.p) || ctx->schur_fp32 == 0) &&      // (round 5: also with the all-FP64 Schur sweeps - the FP64-storage mode ran its ~5 ms application as ONE chain)
+         ctx->pv32_ok && ctx->adv_is_db && ctx->cheb_its_d > 0 && ctx->dd_is_scalar && 4 * ctx->V <= 3 * ctx->N2 && ctx->debug_prec_apply == 0;
+}
+
 // z = M^-1 r with the approximate block factorisation (see fsi_block.hip):  (v,p) by SIMPLE with the d-eliminated
 // velocity block, then d.
 int precondition_block(FsiCtx* ctx, const double* r, double* z) {
@@ -430,10 +438,7 @@ int precondition_block(FsiCtx* ctx, const double* r, double* z) {
   // merge.  Stream B: fluid predictor, then - once the solid predictor is there - pressure right-hand side, Schur sweeps,
   // velocity correction.  Work vectors of the two chains are disjoint: the solid and displacement sweeps use IW[0, 4 n3),
   // the fluid sweeps IW[6 n3, 10 n3), the Schur sweeps the unused tail of rp (V of its n3 entries carry r_p).
-  a.conc = ctx->prec_streams && ctx->stream2 && ctx->solid_fp32 && ctx->solid_block_jacobi && ctx->solid_fused && ctx->sbmg_ready &&
-           ctx->sweeps_fp32 && ctx->tiled && ctx->fused_sweeps && ctx->cheb_its_p > 0 &&
-           ((ctx->schur_fp32 == 1 && ctx->s_vals32.p) || ctx->schur_fp32 == 0) &&      // (round 5: also with the all-FP64 Schur sweeps - the FP64-storage mode ran its ~5 ms application as ONE chain)
-           ctx->pv32_ok && ctx->adv_is_db && ctx->cheb_its_d > 0 && ctx->dd_is_scalar && 4 * V <= n3 && ctx->debug_prec_apply == 0;
+  a.conc = block_two_chains(ctx);
   // (the applications whose sweep launches are timed by event pairs issue both chains on the solver stream - the same arithmetic in
   // the same order per chain, and a pair brackets its kernel alone)
   if (a.conc && !sampled(ctx)) a.sB = ctx->stream2;
