@@ -516,6 +516,30 @@ int fsi_band_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* cell
  * (fsi_band_filter or fsi_band_phase first), no phase average (fsi_band_phase first), step < 1 or count < 1, a last frame
  * outside the series, out NULL; p, the tensor quantities, a quantity without a session and partitioned contexts. */
 int fsi_band_cell_rate(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count, double* out);
+/* Replaces: nothing in the reference; VaMPy's metrics on an FSI run.  fsi_band_cell_rate in the current configuration
+ * x = X + d(X) of an ALE run: quantity, series, first, step and count as there, on the session of `quantity` and its cell list
+ * (fsi_band_cells); the geometry is the displacement the session of quantity 0 (d) holds on the same nodes and frames:
+ *   FSI_RATE_RAW, FSI_RATE_SERIES  the recorded (raw) d frame at the absolute index sel_first + (first + k step) sel_stride of
+ *                                  the selection of the session of `quantity` - the d session's own selection does not matter;
+ *   FSI_RATE_PHASE_MEAN            the d session's phase mean of the same phase (fsi_band_phase with the same period on the
+ *                                  same selection).
+ * With G_t and D_t the vertex gradients of the series' frame and of d in the undeformed geometry, at the four points of the
+ * degree-2 interior rule (weight a = 0.5854101966249685 on vertex q, b = 0.1381966011250105 on the others):
+ * G_q = b (sum_t G_t) + (a - b) G_q and D_q likewise, F_q = I + D_q, J_q = det F_q, L_q = G_q adj(F_q) / J_q,
+ * S_q = 0.5 (L_q + L_q^T), e_q = 2 S_q:S_q and r = (sum_q J_q e_q) / (sum_q J_q), the mean over the deformed cell.  Per cell:
+ *   rate_out[c]          (((+0.0 + r[first]) + r[first + step]) + ...) / count, as fsi_band_cell_rate;
+ *   volume_ratio_out[c]  (nullable) the same ordered mean of 0.25 sum_q J_q, the deformed cell's volume over the undeformed;
+ *   min_jacobian_out[c]  (nullable) the smallest J_q over the frames and points: m = +inf, m = (J_q < m) ? J_q : m, so a NaN
+ *                        never replaces m.
+ * FP64 without contraction, bit-equal to hi_pass.cell_rate_current.  Nothing is clamped: J_q = 0 gives IEEE inf or NaN in the
+ * rate, a negative J_q is carried through, a NaN in a node reaches only the cells that touch it.  The two further result
+ * buffers of n doubles are allocated at the first call under the room rule of fsi_band_begin and freed with the cell list.
+ * FSI_ERR_INVALID, naming what is missing: every refusal of fsi_band_cell_rate (rate_out NULL among them); the d session is not
+ * open, lists other nodes than the session of `quantity` or has recorded another number of frames; for the phase mean, the d
+ * session has no phase average, or one of another period or over another selection; partitioned contexts.  A refused call
+ * leaves the session as it was. */
+int fsi_band_cell_rate_current(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count,
+                               double* rate_out, double* volume_ratio_out, double* min_jacobian_out);
 /* Replaces: the "Saving data" loops of create_hi_pass_viz [REF .../create_hi_pass_viz.py:233-245,327-341,377-390]: one frame
  * of the raw history, the filtered series or its amplitude (out[n][ncomp]), or of the amplitude's magnitude over the
  * components (out[n]; for p the amplitude itself).  For the last two, max_out / argmax_out (nullable) receive the largest

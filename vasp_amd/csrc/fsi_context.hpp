@@ -471,8 +471,9 @@ struct FsiCtx {
     std::vector<int32_t> h_nodes;
     fsi::DevBuf<int32_t> cell_conn;          // [ncell][10]
     fsi::DevBuf<double> cell_gl, cell_out;   // [ncell][4][3], [ncell]
+    fsi::DevBuf<double> cell_vol, cell_minj; // [ncell] each: the two further results of fsi_band_cell_rate_current, at its first call
     void phase_release() { phase_mean.release(); phase_period = 0; }
-    void cells_release() { cell_conn.release(); cell_gl.release(); cell_out.release(); ncell = 0; }
+    void cells_release() { cell_conn.release(); cell_gl.release(); cell_out.release(); cell_vol.release(); cell_minj.release(); ncell = 0; }
     void release() {
       History::release();
       acc.release(); amp.release(); mag.release(); part_val.release(); part_idx.release();

@@ -14,8 +14,20 @@
 //                 L_a L_b over the cell is |K| (1 + delta_ab) / 20.  out = (((+0.0 + r_0) + r_1) + ...) / count: the sum in frame
 //                 order, a true division; one frame gives its own bits.  NaN and inf propagate, nothing is clamped.
 //
+//   k_cell_rate_current : the same in the current configuration x = X + d(X) of an ALE run: one lane per listed cell walks
+//                 `count` frames of a field w and of the displacement d together (480 B gathered per cell and frame).  With
+//                 G_t and D_t the vertex gradients of w and d in the undeformed geometry, at the four points of the degree-2
+//                 interior rule - weight a = 0.5854101966249685 on vertex q, b = 0.1381966011250105 on the other three, so
+//                 G_q = b (sum_t G_t) + (a - b) G_q, exact for a gradient that is linear on the cell -: F_q = I + D_q,
+//                 J_q = det F_q, L_q = G_q adj(F_q) / J_q, S_q = 0.5 (L_q + L_q^T), e_q = 2 S_q:S_q, and the frame's value
+//                 r = (sum_q J_q e_q) / (sum_q J_q), the mean over the deformed cell (with d = 0 the rule is exact and r is the
+//                 r of k_cell_rate to rounding).  Three results per cell: rate, the mean of r over the frames as k_cell_rate
+//                 forms it; volume_ratio, the same ordered mean of 0.25 sum_q J_q; min_jacobian, m = +inf and then per frame
+//                 and point m = (J_q < m) ? J_q : m, so a NaN never replaces m.  Nothing is clamped: J_q = 0 gives inf or NaN,
+//                 a negative J_q is carried through.  256 VGPRs and 22 AGPRs, no scratch, one wave per SIMD (fsi_rate.hpp).
+//
 // No LDS, no atomics, FP64 vector loads and stores.  Floating-point contraction is off, as in fsi_band.hip and fsi_phase.hip:
-// the NumPy twin (hi_pass.cell_rate) rounds every product and every sum, and the device equals it bit for bit.
+// the NumPy twins (hi_pass.cell_rate, hi_pass.cell_rate_current) round every product and every sum, and the device equals them bit for bit.
 #include "fsi_rate.hpp"
 
 #pragma clang fp contract(off)
@@ -113,6 +125,142 @@ __global__ __launch_bounds__(256) void k_cell_rate(int64_t n, const int32_t* __r
   out[c] = s / (double)count;
 }
 
+// G[t] = grad w at the four vertices t: the expression of cell_rate_of, gl kept opaque per vertex for the reason given there
+__device__ __forceinline__ void vertex_gradients_of(const double (&w)[10][3], double (&gl)[4][3], double (&G)[4][3][3]) {
+  const int E[6][2] = {{2, 3}, {1, 3}, {1, 2}, {0, 3}, {0, 2}, {0, 1}};
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) asm volatile("" : "+v"(gl[a][j]));
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        double s = 0.0;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) s = s + w[a][i] * ((a == t ? 3.0 : -1.0) * gl[a][j]);
+#pragma unroll
+        for (int e = 0; e < 6; ++e) {
+          const int p = E[e][0], r = E[e][1];
+          s = s + (w[4 + e][i] * 4.0) * ((p == t ? 1.0 : 0.0) * gl[r][j] + (r == t ? 1.0 : 0.0) * gl[p][j]);
+        }
+        G[t][i][j] = s;
+      }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) asm volatile("" : "+v"(G[t][i][j]));      // this vertex is done before the next begins
+  }
+}
+
+// the sum of the four vertex gradients, in vertex order from +0.0
+__device__ __forceinline__ void vertex_sum_of(const double (&G)[4][3][3], double (&T)[3][3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      double s = 0.0;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) s = s + G[t][i][j];
+      T[i][j] = s;
+    }
+}
+
+// One frame of one cell in the current configuration: G, D the vertex gradients of the field and of the displacement.  r: the
+// mean of 2 S:S over the deformed cell; vol: 0.25 sum_q J_q; m: the running minimum of J_q.  Every operation in the order of
+// hi_pass.cell_rate_current.
+__device__ __forceinline__ void current_rate_of(const double (&G)[4][3][3], const double (&D)[4][3][3], double& r, double& vol, double& m) {
+  const double QA = 0.5854101966249685, QB = 0.1381966011250105, QAB = QA - QB;
+  double TG[3][3], TD[3][3];
+  vertex_sum_of(G, TG);
+  vertex_sum_of(D, TD);
+  double num = 0.0, den = 0.0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    double g[3][3], F[3][3], A[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        g[i][j] = QB * TG[i][j] + QAB * G[q][i][j];
+        const double d = QB * TD[i][j] + QAB * D[q][i][j];
+        F[i][j] = i == j ? 1.0 + d : d;
+      }
+    A[0][0] = F[1][1] * F[2][2] - F[1][2] * F[2][1];      // adj F, the transposed cofactors
+    A[0][1] = F[0][2] * F[2][1] - F[0][1] * F[2][2];
+    A[0][2] = F[0][1] * F[1][2] - F[0][2] * F[1][1];
+    A[1][0] = F[1][2] * F[2][0] - F[1][0] * F[2][2];
+    A[1][1] = F[0][0] * F[2][2] - F[0][2] * F[2][0];
+    A[1][2] = F[0][2] * F[1][0] - F[0][0] * F[1][2];
+    A[2][0] = F[1][0] * F[2][1] - F[1][1] * F[2][0];
+    A[2][1] = F[0][1] * F[2][0] - F[0][0] * F[2][1];
+    A[2][2] = F[0][0] * F[1][1] - F[0][1] * F[1][0];
+    const double J = (F[0][0] * A[0][0] + F[0][1] * A[1][0]) + F[0][2] * A[2][0];
+    double L[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) L[i][j] = ((g[i][0] * A[0][j] + g[i][1] * A[1][j]) + g[i][2] * A[2][j]) / J;
+    double e = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const double S = 0.5 * (L[i][j] + L[j][i]);
+        e = e + S * S;
+      }
+    num = num + J * (2.0 * e);
+    den = den + J;
+    m = J < m ? J : m;
+  }
+  r = num / den;
+  vol = 0.25 * den;
+}
+
+__global__ __launch_bounds__(256) void k_cell_rate_current(int64_t n, const int32_t* __restrict__ conn, const double* __restrict__ gl_all,
+                                                           const double* __restrict__ x, int64_t frame_stride,
+                                                           const double* __restrict__ geo, int64_t geo_stride, int64_t count,
+                                                           double* __restrict__ rate, double* __restrict__ volume_ratio,
+                                                           double* __restrict__ min_jacobian) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n) return;
+  int64_t row[10];
+#pragma unroll
+  for (int a = 0; a < 10; ++a) row[a] = 3 * (int64_t)conn[c * 10 + a];
+  double gl[4][3];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) gl[a][j] = gl_all[c * 12 + a * 3 + j];
+  double s = 0.0, sv = 0.0, m = __builtin_inf();
+  for (int64_t k = 0; k < count; ++k) {
+    // the displacement's ten triples become its vertex gradients before the field's are needed: thirty nodal values and
+    // seventy-two gradient entries are live at most, not the sixty nodal values of both
+    double w[10][3], D[4][3][3], G[4][3][3];
+    const double* f = geo + k * geo_stride;
+#pragma unroll
+    for (int a = 0; a < 10; ++a)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) w[a][i] = f[row[a] + i];
+    vertex_gradients_of(w, gl, D);
+    f = x + k * frame_stride;
+#pragma unroll
+    for (int a = 0; a < 10; ++a)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) w[a][i] = f[row[a] + i];
+    vertex_gradients_of(w, gl, G);
+    double r, vol;
+    current_rate_of(G, D, r, vol, m);
+    s = s + r;
+    sv = sv + vol;
+  }
+  rate[c] = s / (double)count;
+  volume_ratio[c] = sv / (double)count;
+  min_jacobian[c] = m;
+}
+
 }  // namespace
 
 void launch_cell_gradients(hipStream_t st, int64_t n, const double* geom, const int32_t* cells, double* gl) {
@@ -123,6 +271,14 @@ void launch_cell_rate(hipStream_t st, int64_t n, const int32_t* conn, const doub
                       int64_t count, double* out) {
   if (n > 0 && count > 0)
     hipLaunchKernelGGL(k_cell_rate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, conn, gl, x, frame_stride, count, out);
+}
+
+void launch_cell_rate_current(hipStream_t st, int64_t n, const int32_t* conn, const double* gl, const double* x, int64_t frame_stride,
+                              const double* geo, int64_t geo_stride, int64_t count, double* rate, double* volume_ratio,
+                              double* min_jacobian) {
+  if (n > 0 && count > 0)
+    hipLaunchKernelGGL(k_cell_rate_current, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, conn, gl, x, frame_stride, geo,
+                       geo_stride, count, rate, volume_ratio, min_jacobian);
 }
 
 }  // namespace fsi

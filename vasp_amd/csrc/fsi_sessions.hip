@@ -978,6 +978,74 @@ int fsi_band_cell_rate(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t fi
   return FSI_OK;
 }
 
+int fsi_band_cell_rate_current(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count, double* rate_out,
+                               double* volume_ratio_out, double* min_jacobian_out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_cell_rate_current")) return FSI_ERR_INVALID;
+  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_cell_rate_current: " + why; return FSI_ERR_INVALID; };
+  if (quantity != 0 && quantity != 1) return refuse("quantity must be 0 (d) or 1 (v)");
+  auto* s = band_session(ctx, quantity, "fsi_band_cell_rate_current");
+  if (!s) return FSI_ERR_INVALID;
+  if (series < FSI_RATE_RAW || series > FSI_RATE_PHASE_MEAN) return refuse("series must be FSI_RATE_RAW, FSI_RATE_SERIES or FSI_RATE_PHASE_MEAN");
+  if (s->ncell < 1) return refuse("no cell list (fsi_band_cells first)");
+  if (series == FSI_RATE_SERIES && !s->filtered) return refuse("no filtered series (fsi_band_filter or fsi_band_phase first)");
+  if (series == FSI_RATE_PHASE_MEAN && (s->phase_period < 1 || !s->filtered)) return refuse("no phase average (fsi_band_phase first)");
+  if (!rate_out) return refuse("rate_out is NULL");
+  const int64_t frames = series == FSI_RATE_PHASE_MEAN ? s->phase_period : band_frames(s);
+  if (step < 1 || count < 1) return refuse("needs step >= 1 and count >= 1, got step = " + std::to_string(step) + ", count = " + std::to_string(count));
+  if (first < 0 || first >= frames || count - 1 > (frames - 1 - first) / step)
+    return refuse("frames " + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(step) + ", ... (" + std::to_string(count) +
+                  " of them) fall outside the series of " + std::to_string(frames) + " frames");
+  // the geometry: the session of d, on the same nodes and the same recorded frames
+  const FsiCtx::Band* g = &ctx->band[0];
+  if (!g->open) return refuse("no session of quantity 0 (d): the current configuration is x = X + d (fsi_band_begin of d first)");
+  if (g->h_nodes != s->h_nodes) return refuse("the session of d lists other nodes than the session of the quantity: both must be opened on the same node list");
+  if (g->frames != s->frames)
+    return refuse("the session of d has recorded " + std::to_string(g->frames) + " frames, the session of the quantity " + std::to_string(s->frames) +
+                  ": both must hold the same frames");
+  if (series == FSI_RATE_PHASE_MEAN) {
+    if (g->phase_period < 1 || !g->filtered) return refuse("the session of d has no phase average (fsi_band_phase of d first)");
+    if (g->phase_period != s->phase_period)
+      return refuse("the phase average of d has a period of " + std::to_string(g->phase_period) + " frames, that of the quantity " +
+                    std::to_string(s->phase_period));
+    if (g->sel_first != s->sel_first || g->sel_stride != s->sel_stride || band_frames(g) != band_frames(s))
+      return refuse("the phase average of d is over another selection of frames than that of the quantity (fsi_band_select and fsi_band_phase of d "
+                    "as of the quantity)");
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  if (s->cell_vol.n != (size_t)s->ncell || s->cell_minj.n != (size_t)s->ncell) {      // the room rule of fsi_band_begin, as fsi_band_phase applies it
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    Room room;
+    FSICHK(device_room(ctx, &room));
+    const double need_d = 16.0 * (double)s->ncell, avail = (double)room.free_b - room.reserve;
+    if (need_d > avail) {
+      char msg[320];
+      snprintf(msg, sizeof msg, "fsi_band_cell_rate_current: the two further results need %.0f bytes (%lld cells x 16), the device has %zu bytes "
+               "free of which %.0f stay with the context", need_d, (long long)s->ncell, room.free_b, room.reserve);
+      ctx->err = msg;
+      return FSI_ERR_INVALID;
+    }
+    HIPCHK(s->cell_vol.alloc((size_t)s->ncell));
+    HIPCHK(s->cell_minj.alloc((size_t)s->ncell));
+    HIPCHK(hipDeviceSynchronize());                                // the allocations' own fills are done
+  }
+  // the series as in fsi_band_cell_rate; the geometry's frames: the raw history at the selection's absolute indices, or the phase means
+  const double* x = series == FSI_RATE_RAW ? s->hist.p + (size_t)s->sel_first * s->nrow : series == FSI_RATE_SERIES ? history_frame(s, true, 0) : s->phase_mean.p;
+  const int64_t stride = series == FSI_RATE_RAW ? s->sel_stride : 1;
+  const double* geo = series == FSI_RATE_PHASE_MEAN ? g->phase_mean.p : g->hist.p + (size_t)s->sel_first * g->nrow;
+  const int64_t geo_stride = series == FSI_RATE_PHASE_MEAN ? 1 : s->sel_stride;
+  launch_cell_rate_current(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x + (size_t)(first * stride) * s->nrow, step * stride * s->nrow,
+                           geo + (size_t)(first * geo_stride) * g->nrow, step * geo_stride * g->nrow, count, s->cell_out.p, s->cell_vol.p,
+                           s->cell_minj.p);
+  HIPCHK(hipGetLastError());
+  const size_t bytes = (size_t)s->ncell * sizeof(double);
+  HIPCHK(hipMemcpyAsync(rate_out, s->cell_out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (volume_ratio_out) HIPCHK(hipMemcpyAsync(volume_ratio_out, s->cell_vol.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (min_jacobian_out) HIPCHK(hipMemcpyAsync(min_jacobian_out, s->cell_minj.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return FSI_OK;
+}
+
 int fsi_band_amplitude(FsiCtx* ctx, int32_t quantity, int32_t window) {
   if (!ctx) return FSI_ERR_INVALID;
   auto* s = band_session(ctx, quantity, "fsi_band_amplitude");

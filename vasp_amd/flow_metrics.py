@@ -5,8 +5,18 @@ motion dissipate.  Nothing in the reference forms these; the sister tool VaMPy d
 metrics").  Here they are closed, in NumPy, from one device quantity per cell: ``R(x)``, the mean over the frames of a series x
 of the exact cell mean of ``2 S:S``, ``S = sym(grad x)`` (``HipBackend.hi_pass_cell_rate``, csrc/fsi_rate.hip; its NumPy twin
 is ``hi_pass.cell_rate`` / ``HostBandSession.cell_rate``), on the velocity history a ``--hi-pass v`` session holds - the raw
-frames, a band-passed series, and with ``--hi-pass-phase-average`` the phase mean and the fluctuation u'.  The gradient is that
-of the undeformed geometry, as in the hemodynamics of the reference.
+frames, a band-passed series, and with ``--hi-pass-phase-average`` the phase mean and the fluctuation u'.  By default the
+gradient is that of the undeformed geometry, as in the hemodynamics of the reference.
+
+``--hi-pass-flow-metrics-configuration current`` takes every rate in the current configuration ``x = X + d(X)`` of the ALE mesh
+instead: of a series w ``S = sym(grad_X w F^-1)``, ``F = I + grad_X d``, averaged over the deformed cell
+(``HipBackend.hi_pass_cell_rate_current``, k_cell_rate_current; the twin is ``hi_pass.cell_rate_current`` /
+``HostBandSession.cell_rate_current``), with the displacement history of ``--hi-pass d`` on the same nodes and frames - each
+velocity frame with the displacement of the same frame, the phase mean with the displacement's phase mean.  Every metric keeps
+its name and its closing formula.  Two more cell files come from the raw call: ``volume_ratio``, the mean over the frames of
+the deformed cell's volume over the undeformed - how much the ALE extension compresses the fluid mesh - and ``min_jacobian``,
+the smallest ``det F`` met in the cell - how close it comes to inverting one; the table's volume weights become
+``volume * volume_ratio``.  h stays the diameter of the **undeformed** cell in both configurations.
 
 This module holds the fluid cells of ``dx_f_id`` and their sub-mesh, per cell the kinematic viscosity ``nu = mu_f / rho_f`` of
 its region, the cell diameter h (twice the circumradius, what ``FsiMesh.hmin`` takes the minimum of) and the volume, the
@@ -197,14 +207,30 @@ NEEDS_DEG2 = ("--hi-pass-flow-metrics needs --save-deg 2: at save_deg 1 the sess
               "its ten P2 nodes")
 
 
+NEEDS_D = ("--hi-pass-flow-metrics-configuration current needs d among the --hi-pass quantities: the current configuration is "
+           "x = X + d, formed from the displacement history")
+NEEDS_METRICS = "--hi-pass-flow-metrics-configuration chooses the configuration of --hi-pass-flow-metrics: it needs that option"
+CONFIGURATIONS = ("reference", "current")
+
+
+def configuration(v: dict) -> str:
+    """'reference' (the default) or 'current': ``--hi-pass-flow-metrics-configuration``."""
+    word = v.get("hi_pass_flow_metrics_configuration") or "reference"
+    if word not in CONFIGURATIONS:
+        raise SystemExit(f"--hi-pass-flow-metrics-configuration takes {' or '.join(CONFIGURATIONS)}, got {word!r}")
+    return word
+
+
 def refusal(v: dict, quantities: List[str]) -> str:
     """Why ``--hi-pass-flow-metrics`` cannot run with the resolved parameters ('' if it can, or without the option)."""
     if not v.get("hi_pass_flow_metrics"):
-        return ""
+        return NEEDS_METRICS if v.get("hi_pass_flow_metrics_configuration") else ""
     if "v" not in quantities:
         return NEEDS_V
     if int(v.get("save_deg") or 1) != 2:
         return NEEDS_DEG2
+    if configuration(v) == "current" and "d" not in quantities:
+        return NEEDS_D
     return ""
 
 
@@ -220,6 +246,9 @@ class FlowMetrics:
         self.nu = kinematic_viscosity(mesh, self.cells, ns)
         self.h, self.volume = cell_diameters(mesh, self.cells), cell_volumes(mesh, self.cells)
         self.dt = float(ns["dt"])
+        self.configuration = configuration(ns)
+        self.volume_ratio: Optional[np.ndarray] = None       # with 'current', from the raw call
+        self.min_jacobian: Optional[np.ndarray] = None
         self.writer = FlowMetricsWriter(Path(ns["results_folder"]) / "FlowMetrics", *submesh(mesh, self.cells))
         self.raw: Optional[np.ndarray] = None
         self.bands: Dict[str, np.ndarray] = {}
@@ -232,10 +261,25 @@ class FlowMetrics:
         else:
             session.cells(self.mesh.tet_nodes[self.cells], barycentric_gradients(self.mesh, self.cells))
 
+    def rate(self, session, geometry, series: str, *frames) -> np.ndarray:
+        """``R`` of a series of the velocity session in the configuration asked for; ``geometry``: the session of d.  In the
+        current configuration the raw series over all its frames also leaves the volume ratio and the smallest det F."""
+        if self.configuration == "reference":
+            return session.cell_rate(series, *frames)
+        rate, volume_ratio, min_jacobian = session.cell_rate_current(series, geometry, *frames)
+        if series == "raw" and not frames:
+            self.volume_ratio, self.min_jacobian = volume_ratio, min_jacobian
+        return rate
+
     def write(self, out, time_between_files: float, start_t: float) -> None:
         metrics: Dict[str, np.ndarray] = {}
         if self.raw is not None:
             metrics.update(strain_metrics(self.raw, self.nu, self.h, self.dt))
+        volume = self.volume
+        if self.volume_ratio is not None:
+            metrics.update(volume_ratio=self.volume_ratio, min_jacobian=self.min_jacobian)
+            with np.errstate(all="ignore"):
+                volume = self.volume * self.volume_ratio
         if self.phase is not None:
             metrics.update(turbulence_metrics(self.phase["fluctuation"], self.phase["mean"], self.nu, self.h, self.dt))
             metrics["turbulent_dissipation_phase_mean"] = self.nu[None, :] * self.phase["cycle_mean"]
@@ -245,10 +289,11 @@ class FlowMetrics:
         for name, values in metrics.items():
             self.writer.write(name, values, time_between_files, start_t)
             if values.ndim == 1:
-                rows.append((name, *summary_row(values, self.volume, self.cells)))
+                rows.append((name, *summary_row(values, volume, self.cells)))
             else:
-                rows.extend((f"{name}[{j}]", *summary_row(frame, self.volume, self.cells)) for j, frame in enumerate(values))
+                rows.extend((f"{name}[{j}]", *summary_row(frame, volume, self.cells)) for j, frame in enumerate(values))
         self.writer.write_table(rows)
         top = {r[0]: r[3] for r in rows}
         said = ", ".join(f"max {k} = {top[k]:.4g}" for k in ("l_plus", "t_plus", "length_ratio") if k in top)
-        out(f"Flow metrics of {len(self.cells)} fluid cells ({', '.join(metrics)}) written to {self.writer.folder}: {said}")
+        out(f"Flow metrics of {len(self.cells)} fluid cells in the {self.configuration} configuration ({', '.join(metrics)}) written to "
+            f"{self.writer.folder}: {said}")

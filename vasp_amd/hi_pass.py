@@ -20,7 +20,9 @@ This module holds
   refusals (``phase_cycle``, ``phase_period``, ``phase_cycles``) and its files (``HiPassRun._write_phase``);
 * the strain rate of a session's vector history on mesh cells, which ``--hi-pass-flow-metrics`` closes into dissipation and
   resolution metrics (``vasp_amd/flow_metrics.py``): the NumPy twin of csrc/fsi_rate.hip (``cell_rate``,
-  ``HostBandSession.cells`` / ``cell_rate``), and where ``HiPassRun.write`` collects the rates;
+  ``HostBandSession.cells`` / ``cell_rate``; in the current configuration of the ALE mesh ``cell_rate_current`` /
+  ``HostBandSession.cell_rate_current``, which pairs the field's frames with the displacement session's), and where
+  ``HiPassRun.write`` collects the rates;
 * what the four post-processing options share to go through a checkpoint: the manifest and the files of
   ``<results>/Checkpoint/sessions/`` and the checks of a restart (``save_sessions``, ``restart_entry``), and the saving and
   restoring of a recorded history (``SessionRun``);
@@ -290,6 +292,82 @@ def cell_rate(w: np.ndarray, grad: np.ndarray) -> np.ndarray:
         return 0.1 * (q + p)
 
 
+RULE_A, RULE_B = 0.5854101966249685, 0.1381966011250105      # the degree-2 interior rule of the tetrahedron: on vertex q, on the others
+
+
+def vertex_gradients(w: np.ndarray, g: np.ndarray) -> list:
+    """``G[t][i][j]``, (cells,) each: the gradient of P2 fields w (cells, 10, 3) at vertex t, by the expression of ``cell_rate``
+    in its order (vertex_gradients_of, csrc/fsi_rate.hip)."""
+    from .mesh import TET_EDGES
+    n = len(w)
+    G = [[[None] * 3 for _ in range(3)] for _ in range(4)]
+    for t in range(4):
+        for i in range(3):
+            for j in range(3):
+                s = np.zeros(n)
+                for a in range(4):
+                    s = s + w[:, a, i] * ((3.0 if a == t else -1.0) * g[:, a, j])
+                for e in range(6):
+                    p, r = int(TET_EDGES[e][0]), int(TET_EDGES[e][1])
+                    s = s + (w[:, 4 + e, i] * 4.0) * ((1.0 if p == t else 0.0) * g[:, r, j] + (1.0 if r == t else 0.0) * g[:, p, j])
+                G[t][i][j] = s
+    return G
+
+
+def cell_rate_current(v: np.ndarray, d: np.ndarray, grad: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(rate, volume_ratio, min_jacobian)`` of one frame, (cells,) each: the mean of ``2 S:S`` over the **deformed** cell,
+    ``S = sym(grad_X v F^-1)``, ``F = I + grad_X d``, of P2 fields v on the mesh ``x = X + d(X)`` - v and d (cells, 10, 3) in
+    the local node order, ``grad`` (cells, 4, 3) the gradients of the barycentric coordinates of the undeformed cells; the
+    deformed cell's volume over the undeformed; the smallest ``det F`` at the rule's points.  The arithmetic of
+    k_cell_rate_current (csrc/fsi_rate.hip) in its order, one IEEE operation per NumPy operation.
+
+    With ``G_t``, ``D_t`` the vertex gradients of v and d: at the four points of the degree-2 interior rule (``RULE_A`` on
+    vertex q, ``RULE_B`` on the others) ``G_q = b (sum_t G_t) + (a - b) G_q`` - exact, the gradient being linear on the cell -
+    and ``D_q`` likewise; ``F_q = I + D_q``, ``J_q = det F_q``, ``L_q = G_q adj(F_q) / J_q``, ``S_q = 0.5 (L_q + L_q^T)``,
+    ``e_q = 2 S_q:S_q``; ``rate = (sum_q J_q e_q) / (sum_q J_q)``, ``volume_ratio = 0.25 sum_q J_q`` and ``min_jacobian``
+    from +inf by ``m = J_q if J_q < m else m``, which a NaN never replaces.  With d = 0 the integrand is quadratic, the rule
+    exact and ``rate`` is ``cell_rate`` to rounding.  Nothing is clamped: ``J_q = 0`` gives inf or NaN, a negative ``J_q`` is
+    carried through."""
+    v, d, g = np.asarray(v, dtype=np.float64), np.asarray(d, dtype=np.float64), np.asarray(grad, dtype=np.float64)
+    if v.ndim != 3 or v.shape[1:] != (10, 3) or d.shape != v.shape or g.shape != (len(v), 4, 3):
+        raise RuntimeError(f"cell_rate_current: v of shape {v.shape}, d of shape {d.shape} and grad of shape {g.shape}, expected (n, 10, 3) "
+                           "twice and (n, 4, 3)")
+    n = len(v)
+    qab = RULE_A - RULE_B
+    with np.errstate(all="ignore"):
+        D, G = vertex_gradients(d, g), vertex_gradients(v, g)
+        TG, TD = [[None] * 3 for _ in range(3)], [[None] * 3 for _ in range(3)]
+        for T, X in ((TG, G), (TD, D)):
+            for i in range(3):
+                for j in range(3):
+                    s = np.zeros(n)
+                    for t in range(4):
+                        s = s + X[t][i][j]
+                    T[i][j] = s
+        num, den, m = np.zeros(n), np.zeros(n), np.full(n, np.inf)
+        for q in range(4):
+            gq, F = [[None] * 3 for _ in range(3)], [[None] * 3 for _ in range(3)]
+            for i in range(3):
+                for j in range(3):
+                    gq[i][j] = RULE_B * TG[i][j] + qab * G[q][i][j]
+                    dq = RULE_B * TD[i][j] + qab * D[q][i][j]
+                    F[i][j] = 1.0 + dq if i == j else dq
+            A = [[F[1][1] * F[2][2] - F[1][2] * F[2][1], F[0][2] * F[2][1] - F[0][1] * F[2][2], F[0][1] * F[1][2] - F[0][2] * F[1][1]],
+                 [F[1][2] * F[2][0] - F[1][0] * F[2][2], F[0][0] * F[2][2] - F[0][2] * F[2][0], F[0][2] * F[1][0] - F[0][0] * F[1][2]],
+                 [F[1][0] * F[2][1] - F[1][1] * F[2][0], F[0][1] * F[2][0] - F[0][0] * F[2][1], F[0][0] * F[1][1] - F[0][1] * F[1][0]]]
+            J = (F[0][0] * A[0][0] + F[0][1] * A[1][0]) + F[0][2] * A[2][0]
+            L = [[((gq[i][0] * A[0][j] + gq[i][1] * A[1][j]) + gq[i][2] * A[2][j]) / J for j in range(3)] for i in range(3)]
+            e = np.zeros(n)
+            for i in range(3):
+                for j in range(3):
+                    S = 0.5 * (L[i][j] + L[j][i])
+                    e = e + S * S
+            num = num + J * (2.0 * e)
+            den = den + J
+            m = np.where(J < m, J, m)
+        return num / den, 0.25 * den, m
+
+
 def pass_stop_list(band_list, words=None) -> List[str]:
     """"pass" or "stop" per band of a multiband cascade: the reference's rule - a band wider than 1000 Hz passes, a narrower
     one is stopped [REF create_hi_pass_viz.py:541-545] - or the words given (``--hi-pass-pass-stop``)."""
@@ -452,6 +530,58 @@ class HostBandSession(HostHistory):
                 s = s + cell_rate(x[k][self.cell_conn], self.cell_grad)
             return s / float(count)
 
+    def cell_rate_current(self, series: str, geometry, first: int = 0, step: int = 1, count: int = -1):
+        """``cell_rate`` in the current configuration: ``(rate, volume_ratio, min_jacobian)`` per attached cell, the ordered
+        means over the frames of the first two of ``cell_rate_current`` and the smallest of the third.  ``geometry``: the
+        twin session of d, on the same nodes and recorded frames.  Frame k of 'raw' and of 'series' is paired with the
+        recorded d frame of the same absolute index - ``geometry``'s own selection does not matter -, phase j of 'phase_mean'
+        with ``geometry``'s phase mean j.  The twin of fsi_band_cell_rate_current: it refuses what that refuses."""
+        what = "hi-pass cell_rate_current"
+        if series not in RATE_SERIES:
+            raise RuntimeError(f"{what}: series must be one of {', '.join(RATE_SERIES)}")
+        if self.cell_conn is None:
+            raise RuntimeError(f"{what}: no cell list (cells first)")
+        if series == "series" and self.filtered is None:
+            raise RuntimeError(f"{what}: no filtered series (filter or phase first)")
+        if series == "phase_mean" and self.phase_mean is None:
+            raise RuntimeError(f"{what}: no phase average (phase first)")
+        x = self.selected() if series == "raw" else self.filtered if series == "series" else self.phase_mean
+        first, step, count = int(first), int(step), int(count)
+        if count == -1 and step >= 1:
+            count = (len(x) - 1 - first) // step + 1
+        if step < 1 or count < 1:
+            raise RuntimeError(f"{what}: needs step >= 1 and count >= 1, got step = {step}, count = {count}")
+        if not 0 <= first < len(x) or first + (count - 1) * step >= len(x):
+            raise RuntimeError(f"{what}: frames {first}, {first} + {step}, ... ({count} of them) fall outside the series of {len(x)} frames")
+        if self.cell_conn.max() >= x.shape[1]:
+            raise RuntimeError(f"{what}: the cell list names node {self.cell_conn.max()}, the session has {x.shape[1]}")
+        g = geometry
+        if not isinstance(g, HostBandSession) or g.ncomp != 3 or not g.raw:
+            raise RuntimeError(f"{what}: no session of d: the current configuration is x = X + d")
+        if g.raw[0].shape != self.raw[0].shape:
+            raise RuntimeError(f"{what}: the session of d is on {len(g.raw[0])} nodes, the session of the quantity on {len(self.raw[0])}: both "
+                               "must be opened on the same node list")
+        if len(g.raw) != len(self.raw):
+            raise RuntimeError(f"{what}: the session of d has recorded {len(g.raw)} frames, the session of the quantity {len(self.raw)}: both "
+                               "must hold the same frames")
+        if series == "phase_mean":
+            if g.phase_mean is None:
+                raise RuntimeError(f"{what}: the session of d has no phase average (phase of d first)")
+            if g.phase_period != self.phase_period:
+                raise RuntimeError(f"{what}: the phase average of d has a period of {g.phase_period} frames, that of the quantity {self.phase_period}")
+            if g.view.indices(len(g.raw)) != self.view.indices(len(self.raw)):
+                raise RuntimeError(f"{what}: the phase average of d is over another selection of frames than that of the quantity")
+            geo = g.phase_mean
+        else:
+            geo = np.stack(g.raw)[self.view]
+        with np.errstate(invalid="ignore", over="ignore"):
+            n = len(self.cell_conn)
+            s, sv, m = np.zeros(n), np.zeros(n), np.full(n, np.inf)
+            for k in range(first, first + count * step, step):
+                r, vol, mk = cell_rate_current(x[k][self.cell_conn], geo[k][self.cell_conn], self.cell_grad)
+                s, sv, m = s + r, sv + vol, np.where(mk < m, mk, m)
+            return s / float(count), sv / float(count), m
+
     def end(self) -> None:
         self.cell_conn = self.cell_grad = None
 
@@ -503,6 +633,10 @@ class DeviceSession:
     def __getattr__(self, name: str):
         call = getattr(self.backend, f"{self.prefix}_{name.rstrip('_')}")       # import_ -> <prefix>_import
         return lambda *args: call(self.q, *args)
+
+    def cell_rate_current(self, series: str, geometry, *args):
+        """The host session's signature: on the device the geometry is the session of d the context holds."""
+        return self.backend.hi_pass_cell_rate_current(self.q, series, *args)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1268,8 +1402,9 @@ class HiPassRun(SessionRun):
                                      self.dt_files, t0)
             self.writer.write_series(f"{name}_tke_avg", [session.phase_fetch("energy_time_mean", 0)], 1, 1, self.dt_files, t0)
             if self.metrics is not None:      # R(u') over the frames of the chosen cycles, at each phase, and R of the phase means
-                self.metrics.phase = dict(fluctuation=session.cell_rate("series"), mean=session.cell_rate("phase_mean"),
-                                          cycle_mean=np.stack([session.cell_rate("series", j, P, m // P) for j in range(P)]))
+                rate, geometry = self.metrics.rate, self.sessions.get("d")
+                self.metrics.phase = dict(fluctuation=rate(session, geometry, "series"), mean=rate(session, geometry, "phase_mean"),
+                                          cycle_mean=np.stack([rate(session, geometry, "series", j, P, m // P) for j in range(P)]))
         out(f"Hi-pass {name}: phase average over cycles {c0} to {c1} of {P} frames written")
 
     @staticmethod
@@ -1283,7 +1418,12 @@ class HiPassRun(SessionRun):
         if n == 0:
             out(f"Hi-pass: none of the {self.frames} recorded frames lies in the window and stride asked for: nothing written")
             return
-        for q, session in self.sessions.items():
+        order = list(self.sessions)
+        if self.metrics is not None and self.metrics.configuration == "current":
+            # d first: by the time the velocity's phase mean is paired with the displacement's, d holds its phase average
+            order.sort(key=lambda q: q != "d")
+        for q in order:
+            session = self.sessions[q]
             ncomp = 1 if q == "p" else 3
             session.select(first, n, self.stride)
             if self.point_ids:
@@ -1291,12 +1431,12 @@ class HiPassRun(SessionRun):
             metrics = self.metrics if q == "v" else None
             if metrics is not None:            # the fluid cells stay attached through the filters and the phase average
                 metrics.attach(session, self.device)
-                metrics.raw = session.cell_rate("raw")
+                metrics.raw = metrics.rate(session, self.sessions.get("d"), "raw")
             for viz, stages, rms in self.series_list(q, n, out):
                 self.apply(session, stages)
                 self._write_filtered(out, session, viz, n, ncomp, rms)
                 if metrics is not None and len(stages) == 1:
-                    metrics.bands[stages[0]["name"]] = session.cell_rate("series")
+                    metrics.bands[stages[0]["name"]] = metrics.rate(session, self.sessions.get("d"), "series")
             if self.period is not None:
                 self._write_phase(out, session, q, first, n)
             if metrics is not None:

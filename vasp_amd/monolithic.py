@@ -91,6 +91,12 @@ def add_session_arguments(ap) -> None:
                          "the fluid cells to <results>/FlowMetrics/: strain rate, viscous dissipation, l+ and t+; with "
                          "--hi-pass-phase-average the turbulent dissipation, the Kolmogorov scales and the ratios h / eta, dt / tau; "
                          "per band of --hi-pass-bands the dissipation of the band-passed velocity")
+    ap.add_argument("--hi-pass-flow-metrics-configuration", dest="hi_pass_flow_metrics_configuration", choices=("reference", "current"),
+                    default=None,
+                    help="the configuration --hi-pass-flow-metrics takes the velocity gradient in: reference, the undeformed mesh "
+                         "(default), or current, the ALE mesh x = X + d(X) - the strain rate is sym(grad v F^-1), F = I + grad d, and "
+                         "the volume ratio and the smallest det F of every fluid cell are written too; needs d among the --hi-pass "
+                         "quantities")
     ap.add_argument("--hi-pass-tensor", dest="hi_pass_tensor", nargs="+", default=None, metavar="Q",
                     help="record the Green-Lagrange strain and / or the Cauchy stress (strain, stress) of the solid cells at every "
                          "saved frame on the device and write the band-pass filtered tensors of --hi-pass-bands, with "
