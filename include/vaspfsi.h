@@ -485,6 +485,34 @@ int fsi_band_phase(FsiCtx* ctx, int32_t quantity, int64_t period);
  * The three energies are refused for the tensor quantities (ncomp 6).  FSI_ERR_INVALID "no phase average (fsi_band_phase
  * first)" without one, for a frame out of range, a null out and a partitioned context. */
 int fsi_band_phase_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, double* out);
+/* Replaces: nothing in the reference, whose spectrogram reader only prepares for it [REF .../spectrograms.py:203]: the
+ * spectral power index (SPI; Khan et al., J. Biomech. 2017) of every row of the session over the n selected RAW frames
+ * (fsi_band_select), the fraction of the non-mean spectral power at or above a cut-off.  One call runs one slab of the nb
+ * lowest bins bin0 .. bin0 + nb - 1 of the length-n DFT; Ct, St [n][nb] are the slab's cos / sin(2 pi j k / n), frame-major
+ * (Ct[j * nb + b] for frame j, bin bin0 + b), window [n] or NULL for the boxcar.  With m the mean of a row over the frames,
+ * added in frame order, Y[j] = window[j] * (x[j] - m) and X_k = sum_j Y[j] exp(-2 pi i j k / n), a row keeps three sums, each
+ * added in a fixed order (fsi_spi.hip): L2 = sum_{1 <= k < kc} |X_k|^2 over the bins handed over so far, X0^2 = |X_0|^2 and
+ * Q = sum_j Y[j]^2.  The slab with bin0 == 0 starts them (and forms m, X0^2 and Q); a slab with bin0 > 0 adds onto L2 and must
+ * start where the slab before it ended, on the same selection, with the same window.  All slabs together hold bins 0 .. kc - 1,
+ * kc - 1 <= (n - 1) / 2: a low bin lies below the Nyquist frequency.  The raw history and the filtered series are left alone.
+ * The sums, the mean, the window and one slab's tables are allocations of the session's own, 8 * (5 rows + nodes + n + 2 n nb)
+ * bytes, under the room rule of fsi_band_begin: FSI_ERR_INVALID with both byte counts when they do not fit beside the context's
+ * 1/16 of the device, and where an allocation fails; nothing is paged.  FSI_ERR_INVALID also for the tensor quantities, fewer
+ * than 2 selected frames, nb < 1, null tables, a bin at or above the Nyquist bin and a slab out of order; a refused call leaves
+ * the session usable.  fsi_band_sample, _import and _select drop the index; fsi_band_end and fsi_destroy free it.  Not for
+ * partitioned contexts. */
+int fsi_band_spi(FsiCtx* ctx, int32_t quantity, const double* window, int64_t bin0, int64_t nb, const double* Ct, const double* St);
+#define FSI_SPI_ROWS 0
+#define FSI_SPI_NODES 1
+#define FSI_SPI_SUMS 2
+/* After fsi_band_spi, of the slabs run so far, with AC = n Q - X0^2 (all power but bin 0, two-sided, by Parseval) and
+ * H = AC - 2 L2 (what lies at or above the cut-off):
+ *   FSI_SPI_ROWS   out[rows]: H <= 0 ? 0 : H / AC - a row that is exactly constant (AC == 0) gives 0, a NaN stays NaN;
+ *   FSI_SPI_NODES  out[n]: for a vector (sH <= 0 ? 0 : sH / sAC) with sH = (H_x + H_y) + H_z and sAC likewise - the index of
+ *                  the summed power, invariant under a rotation of the axes; for the pressure the row's value;
+ *   FSI_SPI_SUMS   out[3][rows]: L2, X0^2 and Q as they stand.
+ * FSI_ERR_INVALID "no spectral power index (fsi_band_spi first)" without one, for a null out and a partitioned context. */
+int fsi_band_spi_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, double* out);
 /* Replaces: nothing in the reference; VaMPy's metrics on an FSI run.  Attaches n > 0 mesh cells to the open session of
  * quantity 0 (d) or 1 (v) (fsi_band_begin), for fsi_band_cell_rate.  Every one of a cell's ten P2 nodes must be a node of the
  * session whose row is the node's own value (nodes_b < 0); of a node listed twice the first occurrence is used.  The range of

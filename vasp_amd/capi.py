@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_set_frame", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_phase", "fsi_band_phase_fetch", "fsi_band_cells", "fsi_band_cell_rate", "fsi_band_cell_rate_current", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_begin_rows", "fsi_spec_begin_wss", "fsi_spec_room", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_spectrogram_sum", "fsi_spec_periodogram_sum", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_phase", "fsi_band_phase_fetch", "fsi_band_spi", "fsi_band_spi_fetch", "fsi_band_cells", "fsi_band_cell_rate", "fsi_band_cell_rate_current", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_begin_rows", "fsi_spec_begin_wss", "fsi_spec_room", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_spectrogram_sum", "fsi_spec_periodogram_sum", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -168,6 +168,8 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_band_amplitude.argtypes = [vp, i32, i32]
     lib.fsi_band_phase.argtypes = [vp, i32, i64]
     lib.fsi_band_phase_fetch.argtypes = [vp, i32, i32, i64, vp]
+    lib.fsi_band_spi.argtypes = [vp, i32, vp, i64, i64, vp, vp]
+    lib.fsi_band_spi_fetch.argtypes = [vp, i32, i32, vp]
     lib.fsi_band_cells.argtypes = [vp, i32, i64, vp, vp]
     lib.fsi_band_cell_rate.argtypes = [vp, i32, i32, i64, i64, i64, vp]
     lib.fsi_band_cell_rate_current.argtypes = [vp, i32, i32, i64, i64, i64, vp, vp, vp]
@@ -702,6 +704,36 @@ class HipBackend:
         n, ncomp = self._band_shape[quantity]
         out = np.empty((n, ncomp)) if what == "mean" else np.empty(n)
         self._check(self.lib.fsi_band_phase_fetch(self.ctx, self.BAND_QUANTITY[quantity], self.PHASE_WHAT[what], int(frame), _ptr(out)))
+        return out
+
+    SPI_WHAT = {"rows": 0, "nodes": 1, "sums": 2}
+
+    def hi_pass_spi(self, quantity: str, window, bin0: int, nb: int, Ct=None, St=None) -> None:
+        """One slab of the spectral power index of the selected raw frames (fsi_band_spi): the ``nb`` lowest bins from
+        ``bin0`` of the DFT over the n selected frames, ``window`` (n,) or None for the boxcar.  ``Ct`` / ``St`` (n, nb): the
+        slab's cos / sin columns, frame-major; None: ``spectrogram.spec_tables`` of the selected count.  A slab with
+        ``bin0`` > 0 adds onto the slabs before it; the index comes from ``hi_pass_spi_fetch``."""
+        bin0, nb = int(bin0), int(nb)
+        n = getattr(self, "_band_frames", {}).get(quantity, [0, 0])[1]
+        if Ct is None and nb >= 1 and bin0 >= 0 and n >= 1:
+            from .spectrogram import spec_tables
+            C, S = spec_tables(n, n, bin0, nb)
+            Ct, St = C.T, S.T
+        w = None if window is None else np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
+        if w is not None and len(w) != n:
+            raise ValueError(f"the window has {len(w)} values, {n} frames are selected")
+        Ct, St = (None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (Ct, St))
+        if Ct is not None and (Ct.shape != (n, nb) or St.shape != (n, nb)):
+            raise ValueError(f"Ct and St must be (frames, nb) = ({n}, {nb}), got {Ct.shape} and {St.shape}")
+        self._check(self.lib.fsi_band_spi(self.ctx, self.BAND_QUANTITY[quantity], None if w is None else _ptr(w), bin0, nb,
+                                          None if Ct is None else _ptr(Ct), None if St is None else _ptr(St)))
+
+    def hi_pass_spi_fetch(self, quantity: str, what: str = "nodes") -> np.ndarray:
+        """After ``hi_pass_spi``: 'rows' the index of every row as (n, ncomp), 'nodes' the power-summed index of every node as
+        (n,), 'sums' the three sums L2, X0^2, Q of every row as (3, n, ncomp) (fsi_band_spi_fetch)."""
+        n, ncomp = self._band_shape[quantity]
+        out = np.empty(n) if what == "nodes" else np.empty((n, ncomp)) if what == "rows" else np.empty((3, n, ncomp))
+        self._check(self.lib.fsi_band_spi_fetch(self.ctx, self.BAND_QUANTITY[quantity], self.SPI_WHAT[what], _ptr(out)))
         return out
 
     RATE_SERIES = {"raw": 0, "series": 1, "phase_mean": 2}

@@ -464,6 +464,14 @@ struct FsiCtx {
     int64_t phase_period = 0;
     fsi::DevBuf<double> acc, amp, mag, part_val, phase_mean;
     fsi::DevBuf<int64_t> part_idx;
+    // the spectral power index of the selected raw frames (fsi_band_spi, fsi_spi.hip): spi_next is the bin the next slab must
+    // start at (-1: no index is being formed), spi_frames the selected count it is formed on.  spi_acc [3][nrow]: per row
+    // the low bins' power, bin 0's power and the sum of squares; spi_mean [nrow]; spi_out [nrow + nnode]: the index per row,
+    // then per node; spi_w [frames] and spi_tab [2][frames * nb] the window and one slab's cos / sin columns.  Allocations of
+    // their own, at the first slab
+    int64_t spi_next = -1, spi_frames = 0;
+    bool spi_closed = false;                 // spi_out holds the index of the slabs so far
+    fsi::DevBuf<double> spi_acc, spi_mean, spi_out, spi_w, spi_tab;
     // the mesh cells attached to a session of d or v (fsi_band_cells): per cell its ten P2 nodes as indices into the session's
     // nodes, local order, the gradients of its barycentric coordinates and one result (fsi_rate.hip); h_nodes: the P2 node of
     // every session node as fsi_band_begin was given it, -1 where the row is the mean of two nodes
@@ -473,11 +481,16 @@ struct FsiCtx {
     fsi::DevBuf<double> cell_gl, cell_out;   // [ncell][4][3], [ncell]
     fsi::DevBuf<double> cell_vol, cell_minj; // [ncell] each: the two further results of fsi_band_cell_rate_current, at its first call
     void phase_release() { phase_mean.release(); phase_period = 0; }
+    void spi_release() {
+      spi_acc.release(); spi_mean.release(); spi_out.release(); spi_w.release(); spi_tab.release();
+      spi_next = -1; spi_frames = 0; spi_closed = false;
+    }
     void cells_release() { cell_conn.release(); cell_gl.release(); cell_out.release(); cell_vol.release(); cell_minj.release(); ncell = 0; }
     void release() {
       History::release();
       acc.release(); amp.release(); mag.release(); part_val.release(); part_idx.release();
       phase_release();
+      spi_release();
       cells_release();
       h_nodes.clear();
       ncomp = 0; window = -1; acc_start = -1;

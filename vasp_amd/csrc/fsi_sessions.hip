@@ -1,11 +1,12 @@
 // C-ABI of libvaspfsi.so (include/vaspfsi.h): the post-processing sessions that live on the resident state over a run -
 // hemodynamic indices (fsi_hemo_*), solid stress / strain (fsi_stress_*), band-pass filtered fields (fsi_band_*) and
-// spectrograms (fsi_spec_*).  The arithmetic runs in the kernels of fsi_hemo / fsi_stress / fsi_band / fsi_phase / fsi_rate / fsi_spec .hip; the
+// spectrograms (fsi_spec_*).  The arithmetic runs in the kernels of fsi_hemo / fsi_stress / fsi_band / fsi_phase / fsi_rate / fsi_spec / fsi_spi .hip; the
 // last two families record into one kind of history (FsiCtx::History) through the helpers below.
 #include "fsi_host.hpp"
 #include "fsi_phase.hpp"
 #include "fsi_rate.hpp"
 #include "fsi_spec.hpp"
+#include "fsi_spi.hpp"
 
 using namespace fsi;
 using namespace fsi::host;
@@ -755,6 +756,7 @@ int fsi_band_sample(FsiCtx* ctx, int32_t quantity) {
     FSICHK(history_sample(ctx, s, "fsi_band_sample", "fsi_band_begin"));
   s->window = -1;
   s->phase_release();           // a phase average covers the frames it was formed on
+  s->spi_release();             // and so does a spectral power index
   s->sel_first = 0; s->sel_stride = 1; s->sel_count = -1;      // a selection covers the frames it was made on
   return FSI_OK;
 }
@@ -774,6 +776,7 @@ int fsi_band_select(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count,
   s->sel_count = count == -1 ? (s->frames - 1 - first) / stride + 1 : count;
   s->filtered = false;
   s->phase_release();
+  s->spi_release();
   s->window = -1;
   s->acc_start = -1;
   return FSI_OK;
@@ -889,6 +892,101 @@ int fsi_band_phase_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t fr
     src = s->mag.p;
   }
   HIPCHK(hipMemcpyAsync(out, src, (size_t)(what == FSI_PHASE_MEAN ? s->nrow : s->nnode) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return FSI_OK;
+}
+
+int fsi_band_spi(FsiCtx* ctx, int32_t quantity, const double* window, int64_t bin0, int64_t nb, const double* Ct, const double* St) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_spi")) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_spi");
+  if (!s) return FSI_ERR_INVALID;
+  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_spi: " + why; return FSI_ERR_INVALID; };
+  if (tensor_quantity(quantity)) return refuse("a strain / stress session has no spectral power index: it is that of a vector or a scalar (d, v, p)");
+  const int64_t n = band_frames(s);
+  if (n < 2) return refuse(std::to_string(n) + " selected frames, the index needs at least 2 (fsi_band_select)");
+  if (nb < 1 || bin0 < 0 || !Ct || !St) return refuse("needs bin0 >= 0, nb >= 1 bins and their cos / sin columns Ct, St");
+  if (nb - 1 > (n - 1) / 2 - bin0)
+    return refuse("bins " + std::to_string(bin0) + " .. " + std::to_string(bin0 + nb - 1) + " of " + std::to_string(n) + " selected frames: a low bin lies below the Nyquist "
+                  "frequency, at most bin " + std::to_string((n - 1) / 2));
+  if (bin0 > 0 && (s->spi_next != bin0 || s->spi_frames != n))
+    return refuse("a slab out of order: bin0 = " + std::to_string(bin0) + ", " +
+                  (s->spi_next < 0 ? std::string("no slab stands before it (bin0 = 0 first)") : "the next slab starts at bin " + std::to_string(s->spi_next)));
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  // the working buffers are allocations of the session's own, under the room rule of the begin calls; those of an earlier call
+  // are kept where they have the size (they count as taken otherwise)
+  const size_t nrow = (size_t)s->nrow, tab = 2 * (size_t)n * (size_t)nb;
+  struct Want { DevBuf<double>* buf; size_t count; bool grow; };      // grow: a larger buffer serves as well
+  const Want wants[] = {{&s->spi_acc, 3 * nrow, false}, {&s->spi_mean, nrow, false}, {&s->spi_out, nrow + (size_t)s->nnode, false},
+                        {&s->spi_w, (size_t)n, false}, {&s->spi_tab, tab, true}};
+  auto stands = [](const Want& w) { return w.grow ? w.buf->n >= w.count : w.buf->n == w.count; };
+  double need_d = 0.0, back = 0.0;
+  for (const Want& w : wants)
+    if (!stands(w)) { need_d += 8.0 * (double)w.count; back += 8.0 * (double)w.buf->n; }
+  if (bin0 > 0 && (!stands(wants[0]) || !stands(wants[1]) || !stands(wants[2]) || !stands(wants[3])))
+    return refuse("a slab out of order: the sums of the slabs before it are gone (bin0 = 0 first)");
+  if (need_d > 0.0) {
+    Room room;
+    FSICHK(device_room(ctx, &room));
+    if (need_d > (double)room.free_b + back - room.reserve) {
+      char msg[360];
+      snprintf(msg, sizeof msg, "the sums and tables need %.0f bytes (%lld rows, %lld frames x %lld bins of cos and sin), the device has %zu bytes free of "
+               "which %.0f stay with the context", need_d, (long long)s->nrow, (long long)n, (long long)nb, room.free_b, room.reserve);
+      return refuse(msg);
+    }
+    for (const Want& w : wants)
+      if (!stands(w)) {
+        const hipError_t e = w.buf->alloc(w.count);
+        if (e != hipSuccess) {
+          (void)hipGetLastError();
+          s->spi_release();       // the session stands as before any index was asked for
+          return refuse(std::string("hipMalloc: ") + hipGetErrorString(e));
+        }
+      }
+    HIPCHK(hipDeviceSynchronize());                                // the allocations' own fills are done
+  }
+  const double* hist = s->hist.p + (size_t)s->sel_first * s->nrow;
+  double *l2 = s->spi_acc.p, *x0 = l2 + nrow, *q = x0 + nrow, *Cd = s->spi_tab.p, *Sd = Cd + (size_t)n * (size_t)nb;
+  s->spi_next = -1;               // until this slab has run
+  s->spi_closed = false;
+  if (bin0 == 0) {
+    if (window) HIPCHK(hipMemcpyAsync(s->spi_w.p, window, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    launch_spec_mean(ctx->stream, s->nrow, n, 0, 1, hist, s->spi_mean.p, s->sel_stride);
+  }
+  HIPCHK(hipMemcpyAsync(Cd, Ct, (size_t)n * (size_t)nb * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(Sd, St, (size_t)n * (size_t)nb * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  launch_spi_power(ctx->stream, s->nrow, n, s->sel_stride, nb, bin0, hist, s->spi_mean.p, window ? s->spi_w.p : nullptr, Cd, Sd, l2, x0, q);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));                       // the caller's tables are free again
+  s->spi_next = bin0 + nb;
+  s->spi_frames = n;
+  return FSI_OK;
+}
+
+int fsi_band_spi_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, double* out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_spi_fetch")) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_spi_fetch");
+  if (!s) return FSI_ERR_INVALID;
+  if (what < FSI_SPI_ROWS || what > FSI_SPI_SUMS) { ctx->err = "fsi_band_spi_fetch: what must be FSI_SPI_ROWS, FSI_SPI_NODES or FSI_SPI_SUMS"; return FSI_ERR_INVALID; }
+  if (!out) { ctx->err = "fsi_band_spi_fetch: out is NULL"; return FSI_ERR_INVALID; }
+  if (s->spi_next < 1) { ctx->err = "fsi_band_spi_fetch: no spectral power index (fsi_band_spi first)"; return FSI_ERR_INVALID; }
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t nrow = (size_t)s->nrow;
+  const double* src = s->spi_acc.p;
+  size_t count = 3 * nrow;
+  if (what != FSI_SPI_SUMS) {
+    if (!s->spi_closed) {
+      launch_spi_close(ctx->stream, s->nnode, s->ncomp, s->spi_frames, s->spi_acc.p, s->spi_acc.p + nrow, s->spi_acc.p + 2 * nrow, s->spi_out.p,
+                       s->spi_out.p + nrow);
+      HIPCHK(hipGetLastError());
+      s->spi_closed = true;
+    }
+    src = what == FSI_SPI_ROWS ? s->spi_out.p : s->spi_out.p + nrow;
+    count = what == FSI_SPI_ROWS ? nrow : (size_t)s->nnode;
+  }
+  HIPCHK(hipMemcpyAsync(out, src, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return FSI_OK;
 }
@@ -1161,6 +1259,7 @@ int fsi_band_import(FsiCtx* ctx, int32_t quantity, int64_t count, const double* 
   s->window = -1;
   s->sel_first = 0; s->sel_stride = 1; s->sel_count = -1;      // as fsi_band_sample: a selection covers the frames it was made on
   s->phase_release();
+  s->spi_release();
   return FSI_OK;
 }
 

@@ -9,7 +9,8 @@
 //
 //   k_spec_magnitude : the |.| of a sampled vector, taken at sample time (component "mag").
 //   k_spec_mean      : the mean of every (segment, row) over its K frames, added in frame order: scipy's
-//                      detrend="constant", the default of spectrogram and periodogram alike.
+//                      detrend="constant", the default of spectrogram and periodogram alike.  The frames of a segment may
+//                      lie `stride` recorded frames apart (the selected view of a band-pass session, fsi_spi.hip).
 //   k_spec_power     : for one segment and SPEC_ROWS rows, Re = C Y and Im = S Y on v_mfma_f64_16x16x4_f64, with
 //                      Y[j][row] = w[j] (x[j][row] - mean[row]) formed while the tile is staged in LDS - the window and the
 //                      detrend are never folded into the table: a folded table would move the cancellation of a 1e4 Pa mean
@@ -49,13 +50,13 @@ __global__ __launch_bounds__(256) void k_spec_magnitude(int64_t n, const double*
   dst[i] = sqrt((a * a + b * b) + c * c);
 }
 
-__global__ __launch_bounds__(256) void k_spec_mean(int64_t nrow, int64_t K, int64_t step, const double* __restrict__ x,
+__global__ __launch_bounds__(256) void k_spec_mean(int64_t nrow, int64_t K, int64_t step, int64_t pitch, const double* __restrict__ x,
                                                    double* __restrict__ mean) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, seg = blockIdx.y;
   if (r >= nrow) return;
   const double* xs = x + seg * step * nrow + r;
   double s = 0.0;
-  for (int64_t j = 0; j < K; ++j) s += xs[j * nrow];
+  for (int64_t j = 0; j < K; ++j) s += xs[j * pitch];
   mean[seg * nrow + r] = s / (double)K;
 }
 
@@ -145,9 +146,9 @@ void launch_spec_magnitude(hipStream_t st, int64_t n, const double* tmp, double*
   if (n > 0) hipLaunchKernelGGL(k_spec_magnitude, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, tmp, dst);
 }
 
-void launch_spec_mean(hipStream_t st, int64_t nrow, int64_t K, int64_t step, int64_t nseg, const double* x, double* mean) {
+void launch_spec_mean(hipStream_t st, int64_t nrow, int64_t K, int64_t step, int64_t nseg, const double* x, double* mean, int64_t stride) {
   if (nrow > 0 && nseg > 0)
-    hipLaunchKernelGGL(k_spec_mean, dim3((unsigned)((nrow + 255) / 256), (unsigned)nseg), dim3(256), 0, st, nrow, K, step, x, mean);
+    hipLaunchKernelGGL(k_spec_mean, dim3((unsigned)((nrow + 255) / 256), (unsigned)nseg), dim3(256), 0, st, nrow, K, step, stride * nrow, x, mean);
 }
 
 void launch_spec_power(hipStream_t st, int64_t nrow, int64_t K, int64_t step, int64_t nseg, int64_t nb, int64_t bin0,

@@ -13,8 +13,10 @@ constexpr int64_t SPEC_MAX_NFFT = 1ll << 26;      // transform lengths the host 
 
 // tmp[c * n + i] (three sampled components, component-major) -> dst[i] = sqrt((x^2 + y^2) + z^2)
 void launch_spec_magnitude(hipStream_t st, int64_t n, const double* tmp, double* dst);
-// mean[seg][row] = (x[seg * step][row] + ... + x[seg * step + K - 1][row]) / K, summed in frame order
-void launch_spec_mean(hipStream_t st, int64_t nrow, int64_t K, int64_t step, int64_t nseg, const double* x, double* mean);
+// mean[seg][row] = (x[seg * step][row] + ... + x[seg * step + K - 1][row]) / K, summed in frame order; with stride > 1 the
+// K frames of a segment are x[seg * step + j * stride], j < K
+void launch_spec_mean(hipStream_t st, int64_t nrow, int64_t K, int64_t step, int64_t nseg, const double* x, double* mean,
+                      int64_t stride = 1);
 // part[seg][block][b] = sum over the rows of block `block` (SPEC_ROWS rows each, in a fixed order) of
 //   factor(b) * scale * ((C Y)^2 + (S Y)^2)[b][row],  Y[j][row] = w[j] * (x[seg * step + j][row] - mean[seg][row]),
 // for the nb bins of a slab.  Ct / St: [K][nb], the slab's cos / sin columns, frame-major.  factor(b) = 1 for global bin

@@ -18,6 +18,10 @@ This module holds
   points [REF log_plotter.py:902-989], here per written node (csrc/fsi_phase.hip): its NumPy twin (``phase_average``,
   ``fluctuation_energy``, ``ordered_mean``, ``HostBandSession.phase`` / ``phase_fetch``), the period arithmetic with its
   refusals (``phase_cycle``, ``phase_period``, ``phase_cycles``) and its files (``HiPassRun._write_phase``);
+* the spectral power index of ``--hi-pass-spi`` (Khan et al., J. Biomech. 2017), the fraction of a row's non-mean spectral
+  power at or above a cut-off frequency, per written node (csrc/fsi_spi.hip): its NumPy twin (``spi_sums``, ``spi_close``,
+  ``spi_rows``, ``spi_nodes``, ``HostBandSession.spi`` / ``spi_fetch``), the cut-off's bin in exact rationals
+  (``spi_low_bins``), the options with their refusals (``spi_options``) and its files (``HiPassRun._write_spi``);
 * the strain rate of a session's vector history on mesh cells, which ``--hi-pass-flow-metrics`` closes into dissipation and
   resolution metrics (``vasp_amd/flow_metrics.py``): the NumPy twin of csrc/fsi_rate.hip (``cell_rate``,
   ``HostBandSession.cells`` / ``cell_rate``; in the current configuration of the ALE mesh ``cell_rate_current`` /
@@ -252,6 +256,119 @@ def ordered_mean(e: np.ndarray) -> np.ndarray:
         return s / float(len(e))
 
 
+# ------------------------------------------------------------------------------------------------
+# spectral power index (csrc/fsi_spi.hip)
+# ------------------------------------------------------------------------------------------------
+
+SPI_WHAT = ("rows", "nodes", "sums")            # HipBackend.SPI_WHAT, FSI_SPI_*
+SPI_WINDOWS = ("boxcar", "hann")
+
+
+def _rational(x):
+    """A frequency or a time as a rational: an int or a Fraction as it is; a float as the closest rational with a denominator
+    up to 10^12 - 0.001 is 1 / 1000, and 3 * 0.0001 = 0.00030000000000000003 is 3 / 10000, not their binary neighbours."""
+    from fractions import Fraction
+    if isinstance(x, (float, np.floating)):
+        return Fraction(float(x)).limit_denominator(10 ** 12)
+    return Fraction(x)
+
+
+def spi_low_bins(n: int, time_between_files, cutoff) -> int:
+    """kc, the smallest k >= 1 with ``k / (n * time_between_files) >= cutoff``: bins 1 .. kc - 1 of the length-n DFT lie below
+    the cut-off, bin kc and above count as high - a cut-off that falls exactly on a bin counts that bin as high.  Decided in
+    exact rational arithmetic (``_rational``).  A cut-off that is not > 0, or at or above the Nyquist frequency
+    ``1 / (2 time_between_files)``, and fewer than 2 frames are refused."""
+    n, dt, fc = int(n), _rational(time_between_files), _rational(cutoff)
+    if n < 2:
+        raise SystemExit(f"--hi-pass-spi: the window and stride asked for hold {n} frames, the index needs at least 2")
+    if not fc > 0 or not dt > 0:
+        raise SystemExit(f"--hi-pass-spi-cutoff must be a frequency > 0 Hz, got {cutoff!r}")
+    if fc * 2 * dt >= 1:
+        raise SystemExit(f"--hi-pass-spi-cutoff {float(fc):g} Hz is at or above the Nyquist frequency {float(1 / (2 * dt)):g} Hz of frames "
+                         f"{float(dt)!r} s apart (dt * save_step * stride): no power lies above it")
+    x = fc * n * dt                                 # the cut-off in bins
+    kc = x.numerator // x.denominator + (1 if x.numerator % x.denominator else 0)
+    return max(1, kc)
+
+
+def spi_sums(x: np.ndarray, window, bin0: int, nb: int, mean: Optional[np.ndarray] = None):
+    """(L2, X0sq, Q, mean) of frame-major x (n, ...) for the bins bin0 .. bin0 + nb - 1 of the length-n DFT: with the ordered
+    mean m, ``Y[j] = window[j] (x[j] - m)`` (window None: the boxcar) and ``X_k = sum_j Y[j] exp(-2 pi i j k / n)``:
+    ``L2 = sum |X_k|^2`` over the slab's bins k >= 1 in bin order, ``X0sq = |X_0|^2`` (zeros unless the slab holds bin 0),
+    ``Q = sum_j Y[j]^2`` in frame order.  What k_spi_power forms, but for the order inside a sum."""
+    from .spectrogram import spec_tables
+    x = np.asarray(x, dtype=np.float64)
+    n = len(x)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if mean is None:
+            mean = np.zeros(x.shape[1:])
+            for j in range(n):
+                mean = mean + x[j]
+            mean = mean / float(n)
+        y = x - mean[None]
+        if window is not None:
+            y = np.asarray(window, dtype=np.float64).reshape((n,) + (1,) * (x.ndim - 1)) * y
+        flat = y.reshape(n, -1)
+        bad = ~np.isfinite(flat).all(axis=0)        # a NaN stays in its row: BLAS is kept away from it
+        C, S = spec_tables(n, n, bin0, nb)
+        safe = np.where(bad[None], 0.0, flat)
+        re, im = C @ safe, S @ safe
+        P = re * re + im * im
+        P[:, bad] = np.nan
+        L2, X0 = np.zeros(flat.shape[1]), np.zeros(flat.shape[1])
+        for b in range(nb):
+            if bin0 + b == 0:
+                X0 = P[b]
+            else:
+                L2 = L2 + P[b]
+        Q = np.zeros(flat.shape[1])
+        for j in range(n):
+            Q = Q + flat[j] * flat[j]
+    shape = x.shape[1:]
+    return L2.reshape(shape), X0.reshape(shape), Q.reshape(shape), mean
+
+
+def spi_close(L2: np.ndarray, X0sq: np.ndarray, Q: np.ndarray, n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(H, AC): ``AC = n Q - X0sq``, all power but bin 0, two-sided, by Parseval; ``H = AC - 2 L2``, what lies at or above the
+    cut-off."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        AC = float(n) * np.asarray(Q) - np.asarray(X0sq)
+        return AC - 2.0 * np.asarray(L2), AC
+
+
+def spi_ratio(H: np.ndarray, AC: np.ndarray) -> np.ndarray:
+    """``H <= 0 ? 0 : H / AC``: an exactly constant row (AC == 0) gives 0, a NaN stays NaN."""
+    H, AC = np.asarray(H, dtype=np.float64), np.asarray(AC, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        return np.where(H <= 0.0, 0.0, H / np.where(H <= 0.0, 1.0, AC))
+
+
+def spi_node_ratio(H: np.ndarray, AC: np.ndarray) -> np.ndarray:
+    """The index per node of (nodes, ncomp) H and AC: of a vector that of the summed power, ``(H_x + H_y) + H_z`` over
+    ``(AC_x + AC_y) + AC_z`` - invariant under a rotation of the axes -, of a scalar the row's."""
+    H, AC = np.asarray(H, dtype=np.float64), np.asarray(AC, dtype=np.float64)
+    if H.ndim < 2 or H.shape[-1] == 1:
+        return spi_ratio(H.reshape(H.shape[0]), AC.reshape(H.shape[0]))
+    if H.shape[-1] != 3:
+        raise RuntimeError("hi-pass spi: a strain / stress session has no spectral power index: it is that of a vector or a scalar (d, v, p)")
+    with np.errstate(invalid="ignore", over="ignore"):
+        return spi_ratio((H[..., 0] + H[..., 1]) + H[..., 2], (AC[..., 0] + AC[..., 1]) + AC[..., 2])
+
+
+def spi_rows(x: np.ndarray, window, kc: int) -> np.ndarray:
+    """The spectral power index of every row of frame-major x (n, ...): the fraction of the one-sided power of bins >= 1 that
+    lies in the bins >= kc, ``sum_{k >= kc} P_k / sum_{k >= 1} P_k``, formed from the kc lowest bins alone (``spi_sums``,
+    ``spi_close``)."""
+    L2, X0, Q, _ = spi_sums(x, window, 0, int(kc))
+    return spi_ratio(*spi_close(L2, X0, Q, len(x)))
+
+
+def spi_nodes(x: np.ndarray, window, kc: int) -> np.ndarray:
+    """``spi_node_ratio`` of frame-major x (n, nodes, ncomp): (nodes,)."""
+    L2, X0, Q, _ = spi_sums(x, window, 0, int(kc))
+    return spi_node_ratio(*spi_close(L2, X0, Q, len(x)))
+
+
 RATE_SERIES = ("raw", "series", "phase_mean")      # HipBackend.RATE_SERIES, FSI_RATE_*
 
 
@@ -436,11 +553,13 @@ class HostBandSession(HostHistory):
         self.board, self.board_node0 = None, -1
         self.phase_mean, self.phase_period = None, 0
         self.cell_conn = self.cell_grad = None
+        self.spi_state = None
 
     def sample(self, frame: np.ndarray) -> None:
         super().sample(frame)
         self.amp, self.view = None, slice(None)
         self.phase_mean, self.phase_period = None, 0
+        self.spi_state = None
 
     def selected(self) -> np.ndarray:
         return np.stack(self.raw)[self.view]
@@ -455,6 +574,7 @@ class HostBandSession(HostHistory):
         self.view = slice(first, first + (count - 1) * stride + 1, stride)
         self.filtered = self.amp = None
         self.phase_mean, self.phase_period = None, 0
+        self.spi_state = None
         return count
 
     def filter(self, b, a, zi, padlen: int) -> None:
@@ -484,6 +604,47 @@ class HostBandSession(HostHistory):
         if what == "energy":
             return fluctuation_energy(self.filtered[frame])
         return ordered_mean(fluctuation_energy(self.filtered[frame::P] if what == "energy_cycle_mean" else self.filtered))
+
+    def spi(self, window, bin0: int, nb: int, Ct=None, St=None) -> None:
+        """One slab of the spectral power index of the selected raw frames: the ``nb`` lowest bins from ``bin0``, ``window``
+        (n,) or None for the boxcar (``spi_sums``).  A slab with ``bin0`` > 0 adds onto the slabs before it.  The twin of
+        fsi_band_spi: it refuses what that refuses (``Ct`` / ``St`` are the device's: the twin forms its own tables)."""
+        bin0, nb = int(bin0), int(nb)
+        if self.ncomp not in (1, 3):
+            raise RuntimeError("hi-pass spi: a strain / stress session has no spectral power index: it is that of a vector or a scalar (d, v, p)")
+        x = self.selected() if self.raw else np.empty((0,))
+        n, state = len(x), self.spi_state
+        if n < 2:
+            raise RuntimeError(f"hi-pass spi: {n} selected frames, the index needs at least 2 (select)")
+        if nb < 1 or bin0 < 0:
+            raise RuntimeError("hi-pass spi: needs bin0 >= 0 and nb >= 1 bins")
+        if nb - 1 > (n - 1) // 2 - bin0:
+            raise RuntimeError(f"hi-pass spi: bins {bin0} .. {bin0 + nb - 1} of {n} selected frames: a low bin lies below the Nyquist "
+                               f"frequency, at most bin {(n - 1) // 2}")
+        if bin0 > 0 and (state is None or state["next"] != bin0):
+            raise RuntimeError(f"hi-pass spi: a slab out of order: bin0 = {bin0}, " +
+                               ("no slab stands before it (bin0 = 0 first)" if state is None else f"the next slab starts at bin {state['next']}"))
+        if window is not None and len(window) != n:
+            raise ValueError(f"the window has {len(window)} values, {n} frames are selected")
+        L2, X0, Q, mean = spi_sums(x, window, bin0, nb, None if bin0 == 0 else state["mean"])
+        if bin0 == 0:
+            self.spi_state = dict(L2=L2, X0=X0, Q=Q, mean=mean, n=n, next=nb)
+        else:
+            with np.errstate(invalid="ignore", over="ignore"):
+                state.update(L2=state["L2"] + L2, next=bin0 + nb)
+
+    def spi_fetch(self, what: str = "nodes") -> np.ndarray:
+        """'rows' the index of every row (n, ncomp), 'nodes' the power-summed index of every node (n,), 'sums' L2, X0^2, Q of
+        every row (3, n, ncomp), of the slabs run so far.  The twin of fsi_band_spi_fetch."""
+        if what not in SPI_WHAT:
+            raise RuntimeError(f"hi-pass spi_fetch: what must be one of {', '.join(SPI_WHAT)}")
+        state = self.spi_state
+        if state is None:
+            raise RuntimeError("hi-pass spi_fetch: no spectral power index (spi first)")
+        if what == "sums":
+            return np.stack([state["L2"], state["X0"], state["Q"]])
+        H, AC = spi_close(state["L2"], state["X0"], state["Q"], state["n"])
+        return spi_ratio(H, AC) if what == "rows" else spi_node_ratio(H, AC)
 
     def cells(self, conn, grad) -> np.ndarray:
         """Attach cells for ``cell_rate``: ``conn`` (n, 10) the cells' P2 nodes as indices into the session's nodes, local
@@ -1135,9 +1296,15 @@ def hi_pass_refusal(v: dict, world: int, backend_cls) -> str:
             phase_cycles(v, phase_period(cycle, frame_spacing(v) * stride), frames)
         except SystemExit as e:
             return str(e)
+    spi = spi_options(v)
+    if spi is not None:
+        try:
+            spi_low_bins(frames, frame_spacing(v) * stride, spi["cutoff"])
+        except SystemExit as e:
+            return str(e)
     for lo, hi in bands(v):
-        # with a phase average a band the frames do not suffice for is named when the files are written and left out
-        if frames < padlen_of(lo) + 1 and cycle is None:
+        # with a phase average or an index a band the frames do not suffice for is named when the files are written and left out
+        if frames < padlen_of(lo) + 1 and cycle is None and spi is None:
             return (f"--hi-pass: the run {saves}, the filter of band {lo:g} - {hi:g} Hz needs at least "
                     f"padlen + 1 = {padlen_of(lo) + 1}")
     if words:
@@ -1174,6 +1341,32 @@ METRICS_STRIPS = ("--hi-pass-flow-metrics: the history goes through the session 
                   "together (give it room with --history-memory, or fewer frames with --stride)")
 PHASE_STRIPS = ("--hi-pass-phase-average: the history goes through the session in strips of rows, which form no phase average "
                 "(give it room with --history-memory, or fewer frames with --stride)")
+
+
+SPI_STRIPS = ("--hi-pass-spi: the history goes through the session in strips of rows, on which no spectral power index is formed "
+              "(give it room with --history-memory, or fewer frames with --stride)")
+SPI_TABLE_BYTES = 1 << 27                       # cos and sin columns of one slab of low bins (HiPassRun._write_spi)
+SPI_HEADER = ("quantity, cut-off (Hz), window, frames, sampling rate (Hz), bin width (Hz), low bins kc, minimum SPI, mean SPI, "
+              "maximum SPI, ID of node with max SPI")
+
+
+def spi_options(v: dict) -> Optional[dict]:
+    """None without ``--hi-pass-spi``, else ``cutoff`` (``--hi-pass-spi-cutoff``, 25 Hz) and ``window``
+    (``--hi-pass-spi-window``, boxcar)."""
+    for key in ("hi_pass_spi_cutoff", "hi_pass_spi_window"):
+        if v.get(key) is not None and not v.get("hi_pass_spi"):
+            raise SystemExit(f"--{key.replace('_', '-')} belongs to --hi-pass-spi")
+    if not v.get("hi_pass_spi"):
+        return None
+    cutoff = v.get("hi_pass_spi_cutoff")
+    cutoff = 25.0 if cutoff is None else cutoff
+    if isinstance(cutoff, bool) or not isinstance(cutoff, (int, float, np.integer, np.floating)) or not cutoff > 0:
+        raise SystemExit(f"--hi-pass-spi-cutoff must be a frequency > 0 Hz, got {cutoff!r}")
+    window = v.get("hi_pass_spi_window")
+    window = "boxcar" if window is None else window
+    if window not in SPI_WINDOWS:
+        raise SystemExit(f"--hi-pass-spi-window must be one of {', '.join(SPI_WINDOWS)}, got {window!r}")
+    return dict(cutoff=float(cutoff), window=str(window))
 
 
 def phase_cycle(v: dict) -> Optional[float]:
@@ -1233,7 +1426,8 @@ class HiPassRun(SessionRun):
     per saved frame, and at the end per band the filtered series, with ``--hi-pass-amplitude`` its amplitude and table; with
     ``--hi-pass-multiband`` one more series that went through all bands in order; with ``--hi-pass-point-ids`` the recorded
     series of those nodes; with ``--hi-pass-phase-average`` the mean over the cardiac cycles, the fluctuation about it and the
-    velocity's turbulent kinetic energy (``_write_phase``).  All of it on the saved frames k with ``k % stride == 0`` and ``T0 <= t_k <= T1``
+    velocity's turbulent kinetic energy (``_write_phase``); with ``--hi-pass-spi`` the spectral power index of the recorded
+    frames (``_write_spi``).  All of it on the saved frames k with ``k % stride == 0`` and ``T0 <= t_k <= T1``
     (``--hi-pass-stride``, ``--hi-pass-start-time``, ``--hi-pass-end-time``; every selected frame is kept, where the reference
     drops the last ones, postprocessing_h5py_common.py:285,307).  Times in the files are ``T0 + k * time_between_files``, T0
     being the reference's ``start_t``; ``time_between_files`` is dt * save_step * stride, the spacing of the selected frames
@@ -1259,6 +1453,8 @@ class HiPassRun(SessionRun):
         cycle = phase_cycle(ns)
         self.period = None if cycle is None else phase_period(cycle, self.dt_files)
         self.cycle_range = {key: ns.get(key) for key in ("hi_pass_start_cycle", "hi_pass_end_cycle")}
+        self.spi = spi_options(ns)
+        self.spi_lines: List[str] = []
         self.nodes = {q: output_nodes(mesh, self.save_deg, q) for q in self.quantities}
         if self.save_deg >= 2:
             geometry, topology = mesh.node_coords, refine_topology(mesh)
@@ -1276,6 +1472,8 @@ class HiPassRun(SessionRun):
                 raise SystemExit(PHASE_STRIPS)
             if ns.get("hi_pass_flow_metrics"):
                 raise SystemExit(METRICS_STRIPS)
+            if self.spi is not None:
+                raise SystemExit(SPI_STRIPS)
             i0, i1 = self.strip
             self.nodes = {q: tuple(None if a is None else a[i0:i1] for a in ab) for q, ab in self.nodes.items()}
         self.writer = HiPassWriter(Path(ns["results_folder"]) / "Visualization_hi_pass", geometry, topology)
@@ -1407,6 +1605,34 @@ class HiPassRun(SessionRun):
                                           cycle_mean=np.stack([rate(session, geometry, "series", j, P, m // P) for j in range(P)]))
         out(f"Hi-pass {name}: phase average over cycles {c0} to {c1} of {P} frames written")
 
+    def _write_spi(self, out, session, q: str, n: int) -> None:
+        """``--hi-pass-spi``: ``<viz_type>_spi_<cutoff>``, one scalar frame with the spectral power index of every written
+        node over the ``n`` selected raw frames - of d and v the index of the power summed over the components -, and the
+        quantity's line of ``spi.csv``.  The kc lowest bins go through the session in slabs of at most ``SPI_TABLE_BYTES``
+        of tables, a multiple of 64 bins."""
+        cutoff, window = self.spi["cutoff"], self.spi["window"]
+        name = f"{VIZ_TYPE[q]}_spi_{int(np.rint(cutoff))}"
+        try:
+            kc = spi_low_bins(n, self.dt_files, cutoff)
+        except SystemExit as why:                 # a run that was stopped early: named and left out, as a band without its frames
+            out(f"Hi-pass {name}: {why}: no index written")
+            return
+        from .spectrogram import window_values
+        w = None if window == "boxcar" else window_values(window, n)
+        slab = max(64, SPI_TABLE_BYTES // (16 * n) // 64 * 64)
+        for bin0 in range(0, kc, slab):
+            session.spi(w, bin0, min(slab, kc - bin0))
+        field = np.asarray(session.spi_fetch("nodes"), dtype=np.float64).reshape(-1)
+        self.writer.write_series(name, [field], 1, 1, self.dt_files, self.t0)
+        finite = np.isfinite(field)
+        good = field[finite]
+        stats = (float(good.min()), float(good.mean()), float(good.max()), int(np.flatnonzero(finite)[np.argmax(good)])) if len(good) else \
+            (float("nan"), float("nan"), float("nan"), -1)
+        fs, width = 1.0 / self.dt_files, 1.0 / (n * self.dt_files)
+        self.spi_lines.append(f"{VIZ_TYPE[q]}, {cutoff!r}, {window}, {n}, {fs!r}, {width!r}, {kc}, {stats[0]!r}, {stats[1]!r}, {stats[2]!r}, {stats[3]}")
+        out(f"Hi-pass {name}: spectral power index over {n} frames, {kc - 1} bins of {width:g} Hz below the cut-off ({window}), written; "
+            f"mean {stats[1]:.6g}, maximum {stats[2]:.6g} at node {stats[3]}")
+
     @staticmethod
     def apply(session, stages) -> None:
         """The session's filtered series after ``stages``: the first on the selected frames, every further one on the series."""
@@ -1437,8 +1663,12 @@ class HiPassRun(SessionRun):
                 self._write_filtered(out, session, viz, n, ncomp, rms)
                 if metrics is not None and len(stages) == 1:
                     metrics.bands[stages[0]["name"]] = metrics.rate(session, self.sessions.get("d"), "series")
+            if self.spi is not None:            # on the selection of the bands, before the phase average narrows it to whole cycles
+                self._write_spi(out, session, q, n)
             if self.period is not None:
                 self._write_phase(out, session, q, first, n)
             if metrics is not None:
                 metrics.write(out, self.dt_files, self.t0)
+        if self.spi_lines:
+            (self.writer.folder / "spi.csv").write_text("# " + SPI_HEADER + "\n" + "\n".join(self.spi_lines) + "\n")
         out(f"Hi-pass fields of {n} frames ({', '.join(self.quantities)}) written to {self.writer.folder}")

@@ -86,6 +86,14 @@ def add_session_arguments(ap) -> None:
                     help="first cycle of the window that --hi-pass-phase-average averages, 1-based (default: 1)")
     ap.add_argument("--hi-pass-end-cycle", dest="hi_pass_end_cycle", type=int, default=None, metavar="M",
                     help="last cycle that --hi-pass-phase-average averages, inclusive (default: the last whole cycle)")
+    ap.add_argument("--hi-pass-spi", dest="hi_pass_spi", action="store_const", const=True, default=None,
+                    help="also write, per quantity of --hi-pass, the spectral power index of every written node: the fraction of the "
+                         "recorded signal's non-mean spectral power at or above --hi-pass-spi-cutoff, to "
+                         "<results>/Visualization_hi_pass/<field>_spi_<cutoff>.h5 and spi.csv")
+    ap.add_argument("--hi-pass-spi-cutoff", dest="hi_pass_spi_cutoff", type=float, default=None, metavar="HZ",
+                    help="cut-off frequency of --hi-pass-spi, below the Nyquist frequency of the selected frames (default: 25)")
+    ap.add_argument("--hi-pass-spi-window", dest="hi_pass_spi_window", choices=("boxcar", "hann"), default=None,
+                    help="window of --hi-pass-spi (default: boxcar)")
     ap.add_argument("--hi-pass-flow-metrics", dest="hi_pass_flow_metrics", action="store_const", const=True, default=None,
                     help="also write, from the velocity history of --hi-pass v at --save-deg 2, the flow and simulation metrics on "
                          "the fluid cells to <results>/FlowMetrics/: strain rate, viscous dissipation, l+ and t+; with "
@@ -312,6 +320,9 @@ SESSIONS = (("hemodynamics", "hemodynamics", "hemodynamics_refusal", "Hemodynami
             ("spectrogram", "spectrogram", "spectrogram_refusal", "SpectrogramRun", None))
 
 
+SPI_NEEDS_HI_PASS = "--hi-pass-spi needs --hi-pass with at least one of d, v, p: the index is formed on their recorded history"
+
+
 def _session_part(module: str, name: str):
     return getattr(importlib.import_module("." + module, __package__), name)
 
@@ -320,6 +331,8 @@ def _refuse_sessions(argv, backend_factory, world: int) -> None:
     """--hemodynamics, --stress-strain, --hi-pass, --hi-pass-tensor, --spectrogram: refuse before anything is built, on every rank (a refusal on rank 0 alone would leave
     the workers waiting in run_worker)."""
     args = parse(argv)
+    if args.get("hi_pass_spi") and not args.get("hi_pass"):
+        raise SystemExit(SPI_NEEDS_HI_PASS)
     if not any(args.get(key) for key, *_ in SESSIONS):
         return
     with contextlib.redirect_stdout(io.StringIO()):
