@@ -568,6 +568,42 @@ int fsi_band_cell_rate(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t fi
  * leaves the session as it was. */
 int fsi_band_cell_rate_current(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count,
                                double* rate_out, double* volume_ratio_out, double* min_jacobian_out);
+/* Replaces: nothing in the reference.  One weight per cell of the list fsi_band_cells attached to the session of quantity 0 (d)
+ * or 1 (v): weights[n], host doubles in the list's order (the cell volumes, for a bulk integral), copied to the device for the
+ * sums of fsi_band_cell_vortex; NULL drops them.  A call to fsi_band_cells drops them too: the list changed.  The buffer of n
+ * doubles is allocated at the first call under the room rule of fsi_band_begin and freed with the cell list.  FSI_ERR_INVALID
+ * "no cell list (fsi_band_cells first)" without one; p, the tensor quantities, a quantity without a session and partitioned
+ * contexts. */
+int fsi_band_cell_weights(FsiCtx* ctx, int32_t quantity, const double* weights);
+#define FSI_VORTEX_Q 0
+#define FSI_VORTEX_ENSTROPHY 1
+#define FSI_VORTEX_HELICITY 2
+#define FSI_VORTEX_ABS_HELICITY 3
+#define FSI_VORTEX_SPEED2 4
+#define FSI_VORTEX_FIELDS 5
+/* Replaces: nothing in the reference.  Vortex identification on the cells of fsi_band_cells: quantity, series, first, step and
+ * count as fsi_band_cell_rate takes them.  cells_out[5][n] (nullable), per field f and cell c
+ *   cells_out[f][c] = (((+0.0 + r_f[first]) + r_f[first + step]) + ...) / count,     count terms in frame order, a true division,
+ * r_f[k] being an exact mean over the cell of frame k of the series w, with G_t = grad w at vertex t (the gradient of a P2 field
+ * is linear on the cell, so mean(f h) = 0.05 (sum_t f_t h_t + (sum_t f_t)(sum_t h_t)) for entries f, h of it) and
+ * omega_t = (G_t[2][1] - G_t[1][2], G_t[0][2] - G_t[2][0], G_t[1][0] - G_t[0][1]):
+ *   FSI_VORTEX_Q             -0.5 sum_ij mean(G_ij G_ji) = 0.5 (|Omega|^2 - |S|^2), the Q-criterion;
+ *   FSI_VORTEX_ENSTROPHY     mean(|omega|^2);
+ *   FSI_VORTEX_HELICITY      mean(w . omega) = sum_t sum_i (sum_a M[a][t] w[a][i]) omega_t[i], 60 M[a][t] = 0 / -1 for a vertex
+ *                            a == t / a != t, 4 / 2 for an edge that has / has not vertex t;
+ *   FSI_VORTEX_ABS_HELICITY  |FSI_VORTEX_HELICITY| of the frame: the absolute value of the cell mean, not the cell mean of
+ *                            |w . omega|;
+ *   FSI_VORTEX_SPEED2        mean(|w|^2) = sum_i sum_a w[a][i] (sum_b MM[a][b] w[b][i]), MM the P2 mass matrix over |K|.
+ * sums_out[5] (nullable): sums_out[f] = sum_c weights[c] * cells_out[f][c] with the weights of fsi_band_cell_weights, in a fixed
+ * bracket: p_c = weights[c] * value (one rounding); per 256 consecutive cells of the list (+0.0 past n) and inside each 64 of
+ * them a balanced tree over adjacent pairs, the four sums of 64 as ((s0 + s1) + s2) + s3, and the groups of 256 from +0.0 in
+ * ascending order.  FP64 without contraction, bit-equal to hi_pass.cell_vortex and hi_pass.cell_wsum; count = 1 gives the
+ * frame's own bits; NaN and inf propagate, nothing is clamped.  The gradients are those of the undeformed mesh.  The result
+ * and partial buffers (5 n + 5 ceil(n / 256) + 5 doubles) are allocated at the first call under the room rule of fsi_band_begin
+ * and freed with the cell list.  FSI_ERR_INVALID, naming what is missing: every refusal of fsi_band_cell_rate; both outputs
+ * NULL; sums_out without weights (fsi_band_cell_weights first); partitioned contexts.  A refused call changes nothing. */
+int fsi_band_cell_vortex(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count,
+                         double* cells_out, double* sums_out);
 /* Replaces: the "Saving data" loops of create_hi_pass_viz [REF .../create_hi_pass_viz.py:233-245,327-341,377-390]: one frame
  * of the raw history, the filtered series or its amplitude (out[n][ncomp]), or of the amplitude's magnitude over the
  * components (out[n]; for p the amplitude itself).  For the last two, max_out / argmax_out (nullable) receive the largest

@@ -480,12 +480,20 @@ struct FsiCtx {
     fsi::DevBuf<int32_t> cell_conn;          // [ncell][10]
     fsi::DevBuf<double> cell_gl, cell_out;   // [ncell][4][3], [ncell]
     fsi::DevBuf<double> cell_vol, cell_minj; // [ncell] each: the two further results of fsi_band_cell_rate_current, at its first call
+    // fsi_band_cell_weights and fsi_band_cell_vortex (fsi_vortex.hip), at their first calls: one weight per cell (cell_weighted:
+    // they stand for the list that stands), the five results [5][ncell], and [5][ceil(ncell / 256)] partials followed by [5] sums
+    bool cell_weighted = false;
+    fsi::DevBuf<double> cell_weight, vortex_out, vortex_part;
     void phase_release() { phase_mean.release(); phase_period = 0; }
     void spi_release() {
       spi_acc.release(); spi_mean.release(); spi_out.release(); spi_w.release(); spi_tab.release();
       spi_next = -1; spi_frames = 0; spi_closed = false;
     }
-    void cells_release() { cell_conn.release(); cell_gl.release(); cell_out.release(); cell_vol.release(); cell_minj.release(); ncell = 0; }
+    void cells_release() {
+      cell_conn.release(); cell_gl.release(); cell_out.release(); cell_vol.release(); cell_minj.release();
+      cell_weight.release(); vortex_out.release(); vortex_part.release();
+      cell_weighted = false; ncell = 0;
+    }
     void release() {
       History::release();
       acc.release(); amp.release(); mag.release(); part_val.release(); part_idx.release();

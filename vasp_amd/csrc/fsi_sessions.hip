@@ -7,6 +7,7 @@
 #include "fsi_rate.hpp"
 #include "fsi_spec.hpp"
 #include "fsi_spi.hpp"
+#include "fsi_vortex.hpp"
 
 using namespace fsi;
 using namespace fsi::host;
@@ -83,6 +84,25 @@ int device_room(FsiCtx* ctx, Room* r) {
   size_t total_b = 0;
   HIPCHK(hipMemGetInfo(&r->free_b, &total_b));
   r->reserve = (double)total_b / 16.0;
+  return FSI_OK;
+}
+
+// a further buffer of the cell list, at its first use: the room rule of fsi_band_begin, as fsi_band_cell_rate_current applies it
+int cell_buffer(FsiCtx* ctx, const char* fn, const char* what, DevBuf<double>* buf, size_t count, const std::string& layout) {
+  if (buf->n == count) return FSI_OK;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  Room room;
+  FSICHK(device_room(ctx, &room));
+  const double need_d = 8.0 * (double)count, avail = (double)room.free_b - room.reserve;
+  if (need_d > avail) {
+    char msg[400];
+    snprintf(msg, sizeof msg, "%s: %s need %.0f bytes (%s), the device has %zu bytes free of which %.0f stay with the context", fn, what, need_d,
+             layout.c_str(), room.free_b, room.reserve);
+    ctx->err = msg;
+    return FSI_ERR_INVALID;
+  }
+  HIPCHK(buf->alloc(count));
+  HIPCHK(hipDeviceSynchronize());                                  // the allocation's own fill is done
   return FSI_OK;
 }
 
@@ -1044,6 +1064,7 @@ int fsi_band_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* cell
   std::swap(s->cell_gl.p, d_gl.p); std::swap(s->cell_gl.n, d_gl.n);
   std::swap(s->cell_out.p, d_out.p); std::swap(s->cell_out.n, d_out.n);
   s->ncell = n;
+  s->cell_weighted = false;                                        // the weights were those of the earlier list
   return FSI_OK;
 }
 
@@ -1140,6 +1161,65 @@ int fsi_band_cell_rate_current(FsiCtx* ctx, int32_t quantity, int32_t series, in
   HIPCHK(hipMemcpyAsync(rate_out, s->cell_out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
   if (volume_ratio_out) HIPCHK(hipMemcpyAsync(volume_ratio_out, s->cell_vol.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
   if (min_jacobian_out) HIPCHK(hipMemcpyAsync(min_jacobian_out, s->cell_minj.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return FSI_OK;
+}
+
+int fsi_band_cell_weights(FsiCtx* ctx, int32_t quantity, const double* weights) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_cell_weights")) return FSI_ERR_INVALID;
+  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_cell_weights: " + why; return FSI_ERR_INVALID; };
+  if (quantity != 0 && quantity != 1) return refuse("quantity must be 0 (d) or 1 (v)");
+  auto* s = band_session(ctx, quantity, "fsi_band_cell_weights");
+  if (!s) return FSI_ERR_INVALID;
+  if (s->ncell < 1) return refuse("no cell list (fsi_band_cells first)");
+  if (!weights) { s->cell_weighted = false; return FSI_OK; }
+  HIPCHK(hipSetDevice(ctx->device));
+  FSICHK(cell_buffer(ctx, "fsi_band_cell_weights", "the weights", &s->cell_weight, (size_t)s->ncell, std::to_string(s->ncell) + " cells x 8"));
+  HIPCHK(hipMemcpyAsync(s->cell_weight.p, weights, (size_t)s->ncell * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));                       // the caller's array is free again
+  s->cell_weighted = true;
+  return FSI_OK;
+}
+
+int fsi_band_cell_vortex(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count, double* cells_out,
+                         double* sums_out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_cell_vortex")) return FSI_ERR_INVALID;
+  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_cell_vortex: " + why; return FSI_ERR_INVALID; };
+  if (quantity != 0 && quantity != 1) return refuse("quantity must be 0 (d) or 1 (v)");
+  auto* s = band_session(ctx, quantity, "fsi_band_cell_vortex");
+  if (!s) return FSI_ERR_INVALID;
+  if (series < FSI_RATE_RAW || series > FSI_RATE_PHASE_MEAN) return refuse("series must be FSI_RATE_RAW, FSI_RATE_SERIES or FSI_RATE_PHASE_MEAN");
+  if (s->ncell < 1) return refuse("no cell list (fsi_band_cells first)");
+  if (series == FSI_RATE_SERIES && !s->filtered) return refuse("no filtered series (fsi_band_filter or fsi_band_phase first)");
+  if (series == FSI_RATE_PHASE_MEAN && (s->phase_period < 1 || !s->filtered)) return refuse("no phase average (fsi_band_phase first)");
+  if (!cells_out && !sums_out) return refuse("cells_out and sums_out are both NULL");
+  if (sums_out && !s->cell_weighted) return refuse("sums_out without weights (fsi_band_cell_weights first)");
+  const int64_t frames = series == FSI_RATE_PHASE_MEAN ? s->phase_period : band_frames(s);
+  if (step < 1 || count < 1) return refuse("needs step >= 1 and count >= 1, got step = " + std::to_string(step) + ", count = " + std::to_string(count));
+  if (first < 0 || first >= frames || count - 1 > (frames - 1 - first) / step)
+    return refuse("frames " + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(step) + ", ... (" + std::to_string(count) +
+                  " of them) fall outside the series of " + std::to_string(frames) + " frames");
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t n = (size_t)s->ncell, nblock = (size_t)cell_wsum_blocks(s->ncell);
+  FSICHK(cell_buffer(ctx, "fsi_band_cell_vortex", "the five results", &s->vortex_out, FSI_VORTEX_FIELDS * n, std::to_string(s->ncell) + " cells x 40"));
+  if (sums_out)
+    FSICHK(cell_buffer(ctx, "fsi_band_cell_vortex", "the partial sums", &s->vortex_part, FSI_VORTEX_FIELDS * (nblock + 1),
+                       std::to_string(nblock) + " groups of 256 cells and the sums x 40"));
+  // the series as in fsi_band_cell_rate
+  const double* x = series == FSI_RATE_RAW ? s->hist.p + (size_t)s->sel_first * s->nrow : series == FSI_RATE_SERIES ? history_frame(s, true, 0) : s->phase_mean.p;
+  const int64_t stride = series == FSI_RATE_RAW ? s->sel_stride : 1;
+  launch_cell_vortex(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x + (size_t)(first * stride) * s->nrow, step * stride * s->nrow, count,
+                     s->vortex_out.p);
+  HIPCHK(hipGetLastError());
+  if (cells_out) HIPCHK(hipMemcpyAsync(cells_out, s->vortex_out.p, FSI_VORTEX_FIELDS * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (sums_out) {
+    double* sums = s->vortex_part.p + FSI_VORTEX_FIELDS * nblock;
+    launch_cell_wsum(ctx->stream, s->ncell, s->cell_weight.p, s->vortex_out.p, s->vortex_part.p, sums);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sums_out, sums, FSI_VORTEX_FIELDS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return FSI_OK;
 }

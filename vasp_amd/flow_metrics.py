@@ -163,7 +163,8 @@ def xdmf_text(name: str, num_ts: int, time_between_files: float, start_t: float,
 class FlowMetricsWriter:
     """``<results>/FlowMetrics/``: per metric ``<name>.h5`` with ``Mesh/0/mesh/{geometry f32, topology i32}`` of the fluid
     sub-mesh and ``VisualisationVector/<k>`` f32 (cells, 1), the conventions of ``hi_pass.HiPassWriter``, and ``<name>.xdmf``
-    with ``Attribute Center="Cell"``; and the table ``flow_metrics.csv``."""
+    with ``Attribute Center="Cell"``; and the table ``flow_metrics.csv``.  (``vortex.VortexMetrics`` writes
+    ``<results>/VortexMetrics/`` with it.)"""
 
     def __init__(self, folder, geometry: np.ndarray, topology: np.ndarray):
         self.folder = Path(folder)
@@ -171,28 +172,36 @@ class FlowMetricsWriter:
         self.geometry = np.ascontiguousarray(geometry, dtype=np.float32)
         self.topology = np.ascontiguousarray(topology, dtype=np.int32)
 
-    def write(self, name: str, frames, time_between_files: float = 0.0, start_t: float = 0.0) -> None:
-        """frames: (cells,) for one value per cell at ``start_t``, or (k, cells) for a series."""
-        frames = np.atleast_2d(np.asarray(frames, dtype=np.float64))
-        if frames.shape[1] != len(self.topology):
-            raise ValueError(f"{name}: {frames.shape[1]} values, the fluid has {len(self.topology)} cells")
+    def open_series(self, name: str) -> H5Series:
+        """``<name>.h5`` with the sub-mesh, open for ``append(str(k), (cells, 1) f32)``; ``close_series`` ends it."""
         meshg, zero, inner, root = Group(), Group(), Group(), Group()
         inner["geometry"] = Dataset(self.geometry)
         inner["topology"] = Dataset(self.topology)
         zero["mesh"] = inner
         meshg["0"] = zero
         root["Mesh"] = meshg
-        series = H5Series(self.folder / f"{name}.h5", root, "VisualisationVector")
+        return H5Series(self.folder / f"{name}.h5", root, "VisualisationVector")
+
+    def close_series(self, name: str, series: H5Series, count: int, time_between_files: float = 0.0, start_t: float = 0.0) -> None:
+        series.close()
+        (self.folder / f"{name}.xdmf").write_text(xdmf_text(name, count, time_between_files, start_t, len(self.topology), len(self.geometry)))
+
+    def write(self, name: str, frames, time_between_files: float = 0.0, start_t: float = 0.0) -> None:
+        """frames: (cells,) for one value per cell at ``start_t``, or (k, cells) for a series."""
+        frames = np.atleast_2d(np.asarray(frames, dtype=np.float64))
+        if frames.shape[1] != len(self.topology):
+            raise ValueError(f"{name}: {frames.shape[1]} values, the fluid has {len(self.topology)} cells")
+        series = self.open_series(name)
         try:
             for k, frame in enumerate(frames):
                 series.append(str(k), frame.reshape(-1, 1).astype(np.float32))
-        finally:
+        except BaseException:
             series.close()
-        (self.folder / f"{name}.xdmf").write_text(xdmf_text(name, len(frames), time_between_files, start_t, len(self.topology),
-                                                            len(self.geometry)))
+            raise
+        self.close_series(name, series, len(frames), time_between_files, start_t)
 
-    def write_table(self, rows: List[Tuple[str, float, float, float, int]]) -> None:
-        with open(self.folder / "flow_metrics.csv", "w") as f:
+    def write_table(self, rows: List[Tuple[str, float, float, float, int]], file_name: str = "flow_metrics.csv") -> None:
+        with open(self.folder / file_name, "w") as f:
             f.write(CSV_HEADER + "\n")
             for name, mean, lo, hi, cell in rows:
                 f.write(f"{name}, {mean!r}, {lo!r}, {hi!r}, {cell}\n")

@@ -27,6 +27,9 @@ This module holds
   ``HostBandSession.cells`` / ``cell_rate``; in the current configuration of the ALE mesh ``cell_rate_current`` /
   ``HostBandSession.cell_rate_current``, which pairs the field's frames with the displacement session's), and where
   ``HiPassRun.write`` collects the rates;
+* the Q-criterion, enstrophy, helicity and kinetic energy of the same history on the same cells and their ordered weighted
+  sums, which ``--hi-pass-vortex`` closes into the files of ``vasp_amd/vortex.py``: the NumPy twin of csrc/fsi_vortex.hip
+  (``cell_vortex``, ``cell_wsum``, ``HostBandSession.cell_weights`` / ``cell_vortex``);
 * what the four post-processing options share to go through a checkpoint: the manifest and the files of
   ``<results>/Checkpoint/sessions/`` and the checks of a restart (``save_sessions``, ``restart_entry``), and the saving and
   restoring of a recorded history (``SessionRun``);
@@ -485,6 +488,115 @@ def cell_rate_current(v: np.ndarray, d: np.ndarray, grad: np.ndarray) -> Tuple[n
         return num / den, 0.25 * den, m
 
 
+VORTEX_FIELDS = ("Q", "enstrophy", "helicity", "abs_helicity", "speed2")      # HipBackend.VORTEX_FIELDS, FSI_VORTEX_*
+
+
+def vortex_tables() -> Tuple[np.ndarray, np.ndarray]:
+    """``(60 M, 420 MM)`` in integers, (10, 4) and (10, 10), local node order.  ``M[a][t]``: the mean over the cell of P2 basis
+    function a times barycentric coordinate t - vertex a: 0 at t == a, else -1; edge {p, r}: 4 at t in {p, r}, else 2.
+    ``MM``: the P2 mass matrix over the volume - vertex-vertex 6 and 1; vertex-edge -4 if the vertex is an end of the edge,
+    else -6; edge-edge 32, 16 if they share a vertex, 8 if they are opposite.  Both from
+    ``mean(prod L_i^alpha_i) = 6 prod alpha_i! / (|alpha| + 3)!``."""
+    from .mesh import TET_EDGES
+    ends = [{a} for a in range(4)] + [{int(p), int(r)} for p, r in TET_EDGES]
+    M = np.array([[(0 if a == t else -1) if a < 4 else (4 if t in ends[a] else 2) for t in range(4)] for a in range(10)])
+    MM = np.empty((10, 10), dtype=np.int64)
+    for a in range(10):
+        for b in range(10):
+            if a < 4 and b < 4:
+                MM[a, b] = 6 if a == b else 1
+            elif a < 4 or b < 4:
+                MM[a, b] = -4 if ends[min(a, b)] <= ends[max(a, b)] else -6
+            else:
+                MM[a, b] = 32 if a == b else 16 if ends[a] & ends[b] else 8
+    return M, MM
+
+
+VORTEX_M = vortex_tables()[0] / 60.0         # one true division each: the constants of csrc/fsi_vortex.hip
+VORTEX_MM = vortex_tables()[1] / 420.0
+
+
+def cell_vortex(w: np.ndarray, grad: np.ndarray) -> np.ndarray:
+    """(5, cells), the rows ``VORTEX_FIELDS``: exact means over a tetrahedron of P2 fields w, (cells, 10, 3) in the local node
+    order (``mesh.TET_EDGES``), with ``grad`` (cells, 4, 3) the gradients of the barycentric coordinates - the arithmetic of
+    k_cell_vortex (csrc/fsi_vortex.hip) in its order, one IEEE operation per NumPy operation.
+
+    With ``G_t = grad w`` at vertex t (``vertex_gradients``), ``T = sum_t G_t`` and
+    ``omega_t = (G_t[2][1] - G_t[1][2], G_t[0][2] - G_t[2][0], G_t[1][0] - G_t[0][1])``: the gradient is linear on the cell, so
+    the mean of a product of two of its entries is ``0.05 (sum_t f_t h_t + (sum_t f_t)(sum_t h_t))``, and
+
+        Q             -0.5 sum_ij mean(G_ij G_ji) = 0.5 (|Omega|^2 - |S|^2)
+        enstrophy     mean(|omega|^2)
+        helicity      mean(w . omega) = sum_t sum_i (sum_a M[a][t] w[a][i]) omega_t[i]            (``VORTEX_M``)
+        abs_helicity  |helicity|: the absolute value of the cell mean, **not** the cell mean of |w . omega|
+        speed2        mean(|w|^2) = sum_i sum_a w[a][i] (sum_b MM[a][b] w[b][i])                  (``VORTEX_MM``)
+
+    Nothing is clamped; NaN and inf propagate."""
+    w, g = np.asarray(w, dtype=np.float64), np.asarray(grad, dtype=np.float64)
+    if w.ndim != 3 or w.shape[1:] != (10, 3) or g.shape != (len(w), 4, 3):
+        raise RuntimeError(f"cell_vortex: w of shape {w.shape} and grad of shape {g.shape}, expected (n, 10, 3) and (n, 4, 3)")
+    n = len(w)
+    with np.errstate(all="ignore"):
+        Gs = vertex_gradients(w, g)
+        qd, ed, h = np.zeros(n), np.zeros(n), np.zeros(n)
+        T = [[np.zeros(n) for _ in range(3)] for _ in range(3)]
+        for t in range(4):
+            G = Gs[t]
+            for i in range(3):
+                for j in range(3):
+                    qd = qd + G[i][j] * G[j][i]
+                    T[i][j] = T[i][j] + G[i][j]
+            om = [G[2][1] - G[1][2], G[0][2] - G[2][0], G[1][0] - G[0][1]]
+            for i in range(3):
+                ed = ed + om[i] * om[i]
+            for i in range(3):
+                u = np.zeros(n)
+                for a in range(10):
+                    u = u + VORTEX_M[a][t] * w[:, a, i]
+                h = h + u * om[i]
+        qp = np.zeros(n)
+        for i in range(3):
+            for j in range(3):
+                qp = qp + T[i][j] * T[j][i]
+        W = [T[2][1] - T[1][2], T[0][2] - T[2][0], T[1][0] - T[0][1]]
+        ep = np.zeros(n)
+        for i in range(3):
+            ep = ep + W[i] * W[i]
+        s2 = np.zeros(n)
+        for i in range(3):
+            for a in range(10):
+                u = np.zeros(n)
+                for b in range(10):
+                    u = u + VORTEX_MM[a][b] * w[:, b, i]
+                s2 = s2 + w[:, a, i] * u
+        return np.stack([-0.5 * (0.05 * (qd + qp)), 0.05 * (ed + ep), h, np.abs(h), s2])
+
+
+def cell_wsum(values: np.ndarray, weights: np.ndarray) -> np.ndarray:
+    """``sum_c weights[c] * values[..., c]`` in the bracket of k_cell_wsum and k_cell_wsum_close (csrc/fsi_vortex.hip):
+    ``p_c = weights[c] * values[c]``, one rounding; the cells in groups of 256 consecutive ones, +0.0 past the last; inside
+    each 64 of a group a balanced tree over adjacent pairs (strides 1, 2, 4, 8, 16, 32); the group's four sums of 64 as
+    ``((s0 + s1) + s2) + s3``; the groups from +0.0 in ascending order.  ``values`` (n,) gives a scalar array, (k, n) gives (k,)."""
+    v, wt = np.asarray(values, dtype=np.float64), np.asarray(weights, dtype=np.float64).reshape(-1)
+    if v.ndim not in (1, 2) or v.shape[-1] != len(wt) or len(wt) < 1:
+        raise RuntimeError(f"cell_wsum: values of shape {v.shape} and {len(wt)} weights, expected (n,) or (k, n) and n > 0 weights")
+    with np.errstate(all="ignore"):
+        p = np.atleast_2d(wt * v)
+        k, n = p.shape
+        groups = (n + 255) // 256
+        x = np.zeros((k, groups * 256))
+        x[:, :n] = p
+        x = x.reshape(k, groups, 4, 64)
+        for _ in range(6):
+            x = x[..., 0::2] + x[..., 1::2]
+        x = x[..., 0]
+        part = ((x[..., 0] + x[..., 1]) + x[..., 2]) + x[..., 3]
+        s = np.zeros(k)
+        for b in range(groups):
+            s = s + part[:, b]
+        return s[0] if v.ndim == 1 else s
+
+
 def pass_stop_list(band_list, words=None) -> List[str]:
     """"pass" or "stop" per band of a multiband cascade: the reference's rule - a band wider than 1000 Hz passes, a narrower
     one is stopped [REF create_hi_pass_viz.py:541-545] - or the words given (``--hi-pass-pass-stop``)."""
@@ -552,7 +664,7 @@ class HostBandSession(HostHistory):
         self.ncomp, self.amp, self.view = ncomp, None, slice(None)
         self.board, self.board_node0 = None, -1
         self.phase_mean, self.phase_period = None, 0
-        self.cell_conn = self.cell_grad = None
+        self.cell_conn = self.cell_grad = self.cell_weight = None
         self.spi_state = None
 
     def sample(self, frame: np.ndarray) -> None:
@@ -659,7 +771,7 @@ class HostBandSession(HostHistory):
         if conn.min() < 0 or (nodes is not None and conn.max() >= nodes):
             c, a = np.argwhere((conn < 0) | (conn >= (nodes if nodes is not None else conn.max() + 1)))[0]
             raise RuntimeError(f"hi-pass cells: cell {c} has node {conn[c, a]}, which is no node of the session")
-        self.cell_conn, self.cell_grad = conn.astype(np.int64), grad.copy()
+        self.cell_conn, self.cell_grad, self.cell_weight = conn.astype(np.int64), grad.copy(), None
         return self.cell_grad
 
     def cell_rate(self, series: str, first: int = 0, step: int = 1, count: int = -1) -> np.ndarray:
@@ -690,6 +802,55 @@ class HostBandSession(HostHistory):
             for k in range(first, first + count * step, step):
                 s = s + cell_rate(x[k][self.cell_conn], self.cell_grad)
             return s / float(count)
+
+    def cell_weights(self, weights) -> None:
+        """One weight per attached cell for the sums of ``cell_vortex``; None drops them, as a new cell list does.  The twin of
+        fsi_band_cell_weights."""
+        if self.cell_conn is None:
+            raise RuntimeError("hi-pass cell_weights: no cell list (cells first)")
+        if weights is None:
+            self.cell_weight = None
+            return
+        w = np.array(weights, dtype=np.float64).reshape(-1)
+        if len(w) != len(self.cell_conn):
+            raise ValueError(f"{len(w)} weights, the session has {len(self.cell_conn)} cells")
+        self.cell_weight = w
+
+    def cell_vortex(self, series: str, first: int = 0, step: int = 1, count: int = -1, cells: bool = True, sums: bool = False):
+        """``(cells, sums)``: (5, n) or None, per attached cell and row of ``VORTEX_FIELDS``
+        ``(((+0.0 + r[first]) + r[first + step]) + ...) / count`` with ``r[k] = cell_vortex`` of frame k of the series, the
+        frames as ``cell_rate`` takes them - row 3 is the mean over the frames of the absolute value of each frame's cell mean
+        of the helicity, not of the cell mean of |w . omega|; and (5,) or None, ``cell_wsum`` of those rows with the weights of
+        ``cell_weights``.  The twin of fsi_band_cell_vortex: it refuses what that refuses."""
+        what = "hi-pass cell_vortex"
+        if series not in RATE_SERIES:
+            raise RuntimeError(f"{what}: series must be one of {', '.join(RATE_SERIES)}")
+        if self.cell_conn is None:
+            raise RuntimeError(f"{what}: no cell list (cells first)")
+        if series == "series" and self.filtered is None:
+            raise RuntimeError(f"{what}: no filtered series (filter or phase first)")
+        if series == "phase_mean" and self.phase_mean is None:
+            raise RuntimeError(f"{what}: no phase average (phase first)")
+        if not cells and not sums:
+            raise RuntimeError(f"{what}: neither cells nor sums asked for")
+        if sums and self.cell_weight is None:
+            raise RuntimeError(f"{what}: sums without weights (cell_weights first)")
+        x = self.selected() if series == "raw" else self.filtered if series == "series" else self.phase_mean
+        first, step, count = int(first), int(step), int(count)
+        if count == -1 and step >= 1:
+            count = (len(x) - 1 - first) // step + 1
+        if step < 1 or count < 1:
+            raise RuntimeError(f"{what}: needs step >= 1 and count >= 1, got step = {step}, count = {count}")
+        if not 0 <= first < len(x) or first + (count - 1) * step >= len(x):
+            raise RuntimeError(f"{what}: frames {first}, {first} + {step}, ... ({count} of them) fall outside the series of {len(x)} frames")
+        if self.cell_conn.max() >= x.shape[1]:
+            raise RuntimeError(f"{what}: the cell list names node {self.cell_conn.max()}, the session has {x.shape[1]}")
+        with np.errstate(all="ignore"):
+            s = np.zeros((len(VORTEX_FIELDS), len(self.cell_conn)))
+            for k in range(first, first + count * step, step):
+                s = s + cell_vortex(x[k][self.cell_conn], self.cell_grad)
+            out = s / float(count)
+        return (out if cells else None), (cell_wsum(out, self.cell_weight) if sums else None)
 
     def cell_rate_current(self, series: str, geometry, first: int = 0, step: int = 1, count: int = -1):
         """``cell_rate`` in the current configuration: ``(rate, volume_ratio, min_jacobian)`` per attached cell, the ordered
@@ -744,7 +905,7 @@ class HostBandSession(HostHistory):
             return s / float(count), sv / float(count), m
 
     def end(self) -> None:
-        self.cell_conn = self.cell_grad = None
+        self.cell_conn = self.cell_grad = self.cell_weight = None
 
     def filter_next(self, b, a, zi, padlen: int) -> None:
         if self.filtered is None:
@@ -798,6 +959,12 @@ class DeviceSession:
     def cell_rate_current(self, series: str, geometry, *args):
         """The host session's signature: on the device the geometry is the session of d the context holds."""
         return self.backend.hi_pass_cell_rate_current(self.q, series, *args)
+
+    def cell_weights(self, weights) -> None:
+        self.backend.hi_pass_cell_weights(self.q, weights)
+
+    def cell_vortex(self, series: str, *args, **kwargs):
+        return self.backend.hi_pass_cell_vortex(self.q, series, *args, **kwargs)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1290,6 +1457,10 @@ def hi_pass_refusal(v: dict, world: int, backend_cls) -> str:
     why = metrics_refusal(v, quantities(v))
     if why:
         return why
+    from .vortex import refusal as vortex_refusal
+    why = vortex_refusal(v, quantities(v))
+    if why:
+        return why
     cycle = phase_cycle(v)
     if cycle is not None:
         try:
@@ -1427,7 +1598,8 @@ class HiPassRun(SessionRun):
     ``--hi-pass-multiband`` one more series that went through all bands in order; with ``--hi-pass-point-ids`` the recorded
     series of those nodes; with ``--hi-pass-phase-average`` the mean over the cardiac cycles, the fluctuation about it and the
     velocity's turbulent kinetic energy (``_write_phase``); with ``--hi-pass-spi`` the spectral power index of the recorded
-    frames (``_write_spi``).  All of it on the saved frames k with ``k % stride == 0`` and ``T0 <= t_k <= T1``
+    frames (``_write_spi``).  With ``--hi-pass-flow-metrics`` and ``--hi-pass-vortex`` the velocity session also serves the
+    cell quantities of ``flow_metrics.FlowMetrics`` and ``vortex.VortexMetrics``.  All of it on the saved frames k with ``k % stride == 0`` and ``T0 <= t_k <= T1``
     (``--hi-pass-stride``, ``--hi-pass-start-time``, ``--hi-pass-end-time``; every selected frame is kept, where the reference
     drops the last ones, postprocessing_h5py_common.py:285,307).  Times in the files are ``T0 + k * time_between_files``, T0
     being the reference's ``start_t``; ``time_between_files`` is dt * save_step * stride, the spacing of the selected frames
@@ -1472,6 +1644,9 @@ class HiPassRun(SessionRun):
                 raise SystemExit(PHASE_STRIPS)
             if ns.get("hi_pass_flow_metrics"):
                 raise SystemExit(METRICS_STRIPS)
+            if ns.get("hi_pass_vortex"):
+                from .vortex import VORTEX_STRIPS
+                raise SystemExit(VORTEX_STRIPS)
             if self.spi is not None:
                 raise SystemExit(SPI_STRIPS)
             i0, i1 = self.strip
@@ -1485,6 +1660,13 @@ class HiPassRun(SessionRun):
             if why:
                 raise SystemExit(why)
             self.metrics = flow_metrics.FlowMetrics(mesh, ns)
+        self.vortex = None
+        if ns.get("hi_pass_vortex") or ns.get("hi_pass_vortex_series"):
+            from . import vortex
+            why = vortex.refusal(ns, self.quantities)
+            if why:
+                raise SystemExit(why)
+            self.vortex = vortex.VortexMetrics(mesh, ns)
         self.open_sessions(backend, ns, lambda q: self.nodes[q],
                            lambda q, capacity: HostBandSession(1 if q == "p" else 3, capacity))
 
@@ -1603,6 +1785,8 @@ class HiPassRun(SessionRun):
                 rate, geometry = self.metrics.rate, self.sessions.get("d")
                 self.metrics.phase = dict(fluctuation=rate(session, geometry, "series"), mean=rate(session, geometry, "phase_mean"),
                                           cycle_mean=np.stack([rate(session, geometry, "series", j, P, m // P) for j in range(P)]))
+            if self.vortex is not None:
+                self.vortex.collect_phase(session, P)
         out(f"Hi-pass {name}: phase average over cycles {c0} to {c1} of {P} frames written")
 
     def _write_spi(self, out, session, q: str, n: int) -> None:
@@ -1658,6 +1842,10 @@ class HiPassRun(SessionRun):
             if metrics is not None:            # the fluid cells stay attached through the filters and the phase average
                 metrics.attach(session, self.device)
                 metrics.raw = metrics.rate(session, self.sessions.get("d"), "raw")
+            vortex = self.vortex if q == "v" else None
+            if vortex is not None:             # the same cells, with their volumes as weights; the per-frame files are written here
+                vortex.attach(session, self.device, attached=metrics is not None)
+                vortex.collect(session, n, self.dt_files, self.t0)
             for viz, stages, rms in self.series_list(q, n, out):
                 self.apply(session, stages)
                 self._write_filtered(out, session, viz, n, ncomp, rms)
@@ -1669,6 +1857,8 @@ class HiPassRun(SessionRun):
                 self._write_phase(out, session, q, first, n)
             if metrics is not None:
                 metrics.write(out, self.dt_files, self.t0)
+            if vortex is not None:
+                vortex.write(out, self.dt_files, self.t0)
         if self.spi_lines:
             (self.writer.folder / "spi.csv").write_text("# " + SPI_HEADER + "\n" + "\n".join(self.spi_lines) + "\n")
         out(f"Hi-pass fields of {n} frames ({', '.join(self.quantities)}) written to {self.writer.folder}")

@@ -129,6 +129,9 @@ def run_quantity(job: Job, backend, mesh, ns: dict, limit: int, need, sample_fra
     run_cls, key, strip_key = (hp.HiPassRun, "hi_pass", "hi_pass_strip") if field else (hpt.HiPassTensorRun, "hi_pass_tensor", "hi_pass_tensor_strip")
     if field and ns.get("hi_pass_flow_metrics"):
         raise SystemExit(hp.METRICS_STRIPS)
+    if field and ns.get("hi_pass_vortex"):
+        from .vortex import VORTEX_STRIPS
+        raise SystemExit(VORTEX_STRIPS)
     if job.units == 0:
         run_cls(backend, mesh, {**ns, key: [job.q]})      # its own refusal: nothing to record
     strips = plan_strips(job.units, job.rows_per_unit, capacity, job.board_bytes(amplitude), limit, need, "node" if field else "cell")

@@ -105,6 +105,14 @@ def add_session_arguments(ap) -> None:
                          "(default), or current, the ALE mesh x = X + d(X) - the strain rate is sym(grad v F^-1), F = I + grad d, and "
                          "the volume ratio and the smallest det F of every fluid cell are written too; needs d among the --hi-pass "
                          "quantities")
+    ap.add_argument("--hi-pass-vortex", dest="hi_pass_vortex", action="store_const", const=True, default=None,
+                    help="also write, from the velocity history of --hi-pass v at --save-deg 2, the vortex metrics on the fluid cells "
+                         "to <results>/VortexMetrics/: the time means of the Q-criterion, vorticity, helicity and kinetic energy, the "
+                         "curves of their integrals over the fluid (vortex.csv) and the helicity indices h1 to h4; with "
+                         "--hi-pass-phase-average the Q-criterion of the phase mean and the vorticity of the fluctuation")
+    ap.add_argument("--hi-pass-vortex-series", dest="hi_pass_vortex_series", action="store_const", const=True, default=None,
+                    help="with --hi-pass-vortex: also the Q-criterion, the vorticity, the helicity and the localised normalised "
+                         "helicity (LNH) of every selected frame")
     ap.add_argument("--hi-pass-tensor", dest="hi_pass_tensor", nargs="+", default=None, metavar="Q",
                     help="record the Green-Lagrange strain and / or the Cauchy stress (strain, stress) of the solid cells at every "
                          "saved frame on the device and write the band-pass filtered tensors of --hi-pass-bands, with "
@@ -333,6 +341,10 @@ def _refuse_sessions(argv, backend_factory, world: int) -> None:
     args = parse(argv)
     if args.get("hi_pass_spi") and not args.get("hi_pass"):
         raise SystemExit(SPI_NEEDS_HI_PASS)
+    if not args.get("hi_pass"):
+        from .vortex import refusal as vortex_refusal
+        if vortex_refusal(args, []):
+            raise SystemExit(vortex_refusal(args, []))
     if not any(args.get(key) for key, *_ in SESSIONS):
         return
     with contextlib.redirect_stdout(io.StringIO()):

@@ -54,7 +54,7 @@ from typing import Callable, Dict, List, Optional
 
 import numpy as np
 
-from . import hi_pass
+from . import hi_pass, vortex
 from .fem import FormTerms
 from .frames import FrameSource, selected_indices
 from .mesh import FsiMesh
@@ -159,6 +159,8 @@ def prepare(argv: Optional[List[str]] = None, backend_factory: Callable = defaul
         raise SystemExit(f"vasp_amd.postprocess runs on one rank only (WORLD_SIZE = {world})")
     if args.get("hi_pass_spi") and not args.get("hi_pass"):
         raise SystemExit(SPI_NEEDS_HI_PASS)
+    if not args.get("hi_pass") and vortex.refusal(args, []):
+        raise SystemExit(vortex.refusal(args, []))
     if not any(args.get(key) for key, *_ in SESSIONS):
         raise SystemExit("nothing to do: give one of " + ", ".join("--" + key.replace("_", "-") for key, *_ in SESSIONS))
     v = parameters(args)
@@ -208,6 +210,8 @@ def prepare(argv: Optional[List[str]] = None, backend_factory: Callable = defaul
                 raise SystemExit(hi_pass.PHASE_STRIPS)
             if v.get("hi_pass") and v.get("hi_pass_flow_metrics"):
                 raise SystemExit(hi_pass.METRICS_STRIPS)
+            if v.get("hi_pass") and v.get("hi_pass_vortex"):
+                raise SystemExit(vortex.VORTEX_STRIPS)
             if v.get("hi_pass") and v.get("hi_pass_spi"):
                 raise SystemExit(hi_pass.SPI_STRIPS)
             for j in band_jobs:
@@ -258,6 +262,8 @@ def run(argv: Optional[List[str]] = None, backend_factory: Callable = default_ba
                 raise SystemExit(hi_pass.PHASE_STRIPS)
             if ns.get("hi_pass") and ns.get("hi_pass_flow_metrics"):
                 raise SystemExit(hi_pass.METRICS_STRIPS)
+            if ns.get("hi_pass") and ns.get("hi_pass_vortex"):
+                raise SystemExit(vortex.VORTEX_STRIPS)
             if ns.get("hi_pass") and ns.get("hi_pass_spi"):
                 raise SystemExit(hi_pass.SPI_STRIPS)
     # the same for the spectrogram histories: where they do not fit beside the band-pass sessions of the first frame loop
