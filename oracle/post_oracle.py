@@ -30,7 +30,11 @@ from .fsi_oracle import I3, _det3, _inv3, keast24, tabulate_p2, triangle12
 
 
 def second_piola(g, mu, lam, model=0, C10=0.0, C01=0.0, C11=0.0):
-    """S(d) for grad d = g (..., 3, 3): StVenantKirchoff or the compressible Mooney-Rivlin energy of fsi_oracle.py."""
+    """S(d) for grad d = g (..., 3, 3): StVenantKirchoff or the compressible Mooney-Rivlin energy of fsi_oracle.py.
+    The thirds are formed in g's own type (the same bits as before in FP64), so that an np.longdouble g gives an
+    extended-precision S."""
+    g = np.asarray(g)
+    two_thirds = g.dtype.type(2.0) / g.dtype.type(3.0)
     F = I3 + g
     C = np.swapaxes(F, -1, -2) @ F
     if model == 1:
@@ -38,20 +42,21 @@ def second_piola(g, mu, lam, model=0, C10=0.0, C01=0.0, C11=0.0):
         J = _det3(F)
         I1 = np.trace(C, axis1=-2, axis2=-1)
         I2 = 0.5 * (I1 ** 2 - np.einsum("...ij,...ji->...", C, C))
-        Jm23 = J ** (-2.0 / 3.0)
+        Jm23 = J ** (-two_thirds)
         I1b, I2b = Jm23 * I1, Jm23 ** 2 * I2
         a1 = (2.0 * (C10 + C11 * (I2b - 3.0)) * Jm23)[..., None, None]
         a2 = (2.0 * (C01 + C11 * (I1b - 3.0)) * Jm23 ** 2)[..., None, None]
-        K = lam + 2.0 * mu / 3.0
+        K = lam + 2.0 * g.dtype.type(mu) / 3.0
         return (a1 * (I3 - (I1 / 3.0)[..., None, None] * Ci)
-                + a2 * (I1[..., None, None] * I3 - C - (2.0 / 3.0) * I2[..., None, None] * Ci)
+                + a2 * (I1[..., None, None] * I3 - C - two_thirds * I2[..., None, None] * Ci)
                 + (K * np.log(J) * J)[..., None, None] * Ci)
     E = 0.5 * (C - I3)
     return lam * np.trace(E, axis1=-2, axis2=-1)[..., None, None] * I3 + 2.0 * mu * E
 
 
-def stress_strain_dg1(coords, tets, tet_nodes, d_nodal, cells, props, model=0, eig="eigvalsh"):
+def stress_strain_dg1(coords, tets, tet_nodes, d_nodal, cells, props, model=0, eig="eigvalsh", geom=None):
     """DG1 coefficients on ``cells`` (solid cells of one region; props = (rho, mu, lambda[, C10, C01, C11])).
+    ``geom`` (C,10) gives the geometry as data, as FsiOracle takes it: Jinv row-major (9) and |det| per cell.
 
     Returns dict: TrueStress (n,4,3,3), GreenLagrangeStrain (n,4,3,3), MaxPrincipalStress (n,4), MaxPrincipalStrain (n,4);
     coefficient a belongs to local vertex a of the cell (DG1 = P1 on the cell, nodal basis).
@@ -62,6 +67,8 @@ def stress_strain_dg1(coords, tets, tet_nodes, d_nodal, cells, props, model=0, e
     xc = coords[tets[cells]]
     Jm = np.stack([xc[:, 1] - xc[:, 0], xc[:, 2] - xc[:, 0], xc[:, 3] - xc[:, 0]], axis=2)
     Jinv, det = _inv3(Jm)
+    if geom is not None:
+        Jinv, det = np.asarray(geom)[cells, :9].reshape(-1, 3, 3), np.asarray(geom)[cells, 9]
     w = np.abs(det)[:, None] * qw[None, :]
     G = np.einsum("qak,ckj->cqaj", dNref, Jinv)
     g = np.einsum("cai,cqaj->cqij", d_nodal[tet_nodes[cells]], G)              # grad d at the quadrature points
@@ -107,21 +114,29 @@ def kopp_max_eigenvalue(T):
     return 1 / 3 * (np.sqrt(p) * 2 * np.cos(phi) + I1)
 
 
-def wall_shear_stress(coords, tets, tet_nodes, v_nodal, facet_cells, facet_local, mu):
+def wall_shear_stress(coords, tets, tet_nodes, v_nodal, facet_cells, facet_local, mu, geom=None, rule="triangle12"):
     """Tangential traction on exterior facets, DG1-projected per boundary cell.
+    ``geom`` (C,10) gives the geometry as data, as FsiOracle takes it (Jinv row-major and |det| per cell): the outward
+    normal of facet f is then -grad lambda_f / |grad lambda_f| and its area |det| |grad lambda_f| / 2.
+    ``rule``: "triangle12", the degree-6 rule used everywhere else, whose 15-digit points and weights miss the facet mass
+    matrix by 6.7e-15; or "midpoint", the edge-midpoint rule, which integrates the two quadratic integrands here exactly
+    (for the kernel tests, which judge a kernel that integrates exactly to a few units of 2^-53).
 
     ``facet_cells`` (nf,), ``facet_local`` (nf,): the cell of each exterior facet and the local index of the vertex
     opposite to it (UFC facet numbering).  Returns (nf, 3, 3): the projected ``Ft`` at the three facet vertices in the
     order of the cell's local vertices with ``facet_local`` removed."""
     facet_cells = np.asarray(facet_cells)
     facet_local = np.asarray(facet_local)
-    tp, tw = triangle12()
-    lt = np.stack([1 - tp[:, 0] - tp[:, 1], tp[:, 0], tp[:, 1]], axis=1)         # (12,3) facet barycentric
+    tp, tw = triangle12() if rule == "triangle12" else (np.array([[0.5, 0.0], [0.5, 0.5], [0.0, 0.5]]), np.full(3, 1.0 / 6.0))
+    lt = np.stack([1 - tp[:, 0] - tp[:, 1], tp[:, 0], tp[:, 1]], axis=1)         # (Q,3) facet barycentric
     ucells, inv = np.unique(facet_cells, return_inverse=True)
     nc = len(ucells)
     xc = coords[tets[ucells]]
     Jm = np.stack([xc[:, 1] - xc[:, 0], xc[:, 2] - xc[:, 0], xc[:, 3] - xc[:, 0]], axis=2)
     Jinv, _ = _inv3(Jm)
+    if geom is not None:
+        Jinv = np.asarray(geom)[ucells, :9].reshape(-1, 3, 3)
+        gl = np.concatenate([-Jinv.sum(axis=1, keepdims=True), Jinv], axis=1)    # (nc,4,3) grad lambda_k
     Mc = np.zeros((nc, 4, 4))
     bc = np.zeros((nc, 4, 3))
     verts_of = np.array([[1, 2, 3], [0, 2, 3], [0, 1, 3], [0, 1, 2]])
@@ -134,7 +149,10 @@ def wall_shear_stress(coords, tets, tet_nodes, v_nodal, facet_cells, facet_local
         n = nv / (2 * area)
         if np.dot(n, x[0] - xc[c][lf]) < 0:
             n = -n                                                               # outward: away from the opposite vertex
-        lam = np.zeros((12, 4))
+        if geom is not None:
+            gn = np.linalg.norm(gl[c, lf])
+            n, area = -gl[c, lf] / gn, 0.5 * np.asarray(geom)[ucells[c], 9] * gn
+        lam = np.zeros((len(tw), 4))
         lam[:, lv] = lt
         _, dNref, _, _ = tabulate_p2(lam[:, 1:4])
         G = np.einsum("qak,kj->qaj", dNref, Jinv[c])

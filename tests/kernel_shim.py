@@ -1,9 +1,14 @@
 """ctypes loader of ``vasp_amd/libfsi_kernel_shim.so`` (vasp_amd/csrc/fsi_kernel_shim.hip) and the host-side reference builders
 of the kernel tests (tests/test_gpu_gcr_kernels.py, tests/test_gpu_sweep_kernels.py, tests/test_gpu_product_kernels.py,
 tests/test_gpu_coarse_kernels.py, tests/test_gpu_bcr_kernels.py, tests/test_gpu_block_kernels.py, tests/test_gpu_ilu_kernels.py,
-tests/test_gpu_vector_kernels.py, tests/test_gpu_element_kernels.py, tests/test_gpu_element_jacobian.py).  Helper modules beside
-this one: tests/fp32_records.py, tests/chain_consumers.py, and tests/block_apply.py - one whole application of the block
-preconditioner restated stage by stage (tests/test_block_apply_reference.py on the CPU, tests/test_gpu_block_application.py).
+tests/test_gpu_vector_kernels.py, tests/test_gpu_element_kernels.py, tests/test_gpu_element_jacobian.py,
+tests/test_gpu_post_cell_kernels.py).  Helper modules beside
+this one: tests/fp32_records.py, tests/chain_consumers.py, tests/block_apply.py - one whole application of the block
+preconditioner restated stage by stage (tests/test_block_apply_reference.py on the CPU, tests/test_gpu_block_application.py) - and
+tests/post_cells.py: the wall shear stress, hemodynamic sums and indices, solid stress / strain and principal values of
+fsi_post.hip, fsi_hemo.hip and fsi_stress.hip restated per cell in np.longdouble, with their bounds (shim_wss, shim_hemo_sample,
+shim_hemo_finish, shim_spec_wss_sample, shim_stress_strain, shim_stress_sample, shim_stress_average, shim_tensor_sample,
+shim_tensor_principal; tests/test_post_cell_references.py on the CPU, tests/test_gpu_post_cell_kernels.py).
 
 The shim runs ONE ``fsi::launch_*`` call of libvaspfsi.so on host arrays; the builders restate, in numpy, what the library's
 host code hands those kernels: the LDS tiles of a graph (fsi_setup.hip build_tiles, node tiles and Schur tiles), the FP16 records of
@@ -75,6 +80,9 @@ _SIGS = {
     "shim_gcr_store_op": "ilppppp", "shim_gcr_sizes": "lip", "shim_gcr_cycle_algebra": "lipppppppip",
     "shim_gcr_cycle_end": "iidddi", "shim_gcr_orth_lost": "piddd", "shim_gcr_verdict_due": "dddiiiiiii",
     "shim_gcr_verdict_skippable": "dddiiiiiiidd", "shim_gcr_tolerances": "pp",
+    "shim_wss": "lllpppppdp", "shim_hemo_sample": "lllpppppp" + "ldd" + "p" * 7, "shim_hemo_finish": "ldpppp",
+    "shim_spec_wss_sample": "lll" + "p" * 7 + "ldp", "shim_stress_strain": "lll" + "p" * 12, "shim_stress_sample": "lll" + "p" * 13,
+    "shim_stress_average": "ldpp", "shim_tensor_sample": "llli" + "p" * 12, "shim_tensor_principal": "lpp",
 }
 LAUNCH_REFUSED = 2           # fsi_kernels.hpp: a launch function refused its arguments and launched nothing
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "d": C.c_double, "s": C.c_char_p}

@@ -1926,6 +1926,197 @@ int shim_probe(int64_t n, int64_t C, int64_t nu, const int32_t* cell_dofs, const
   SHIM_RUN(c, "launch_probe", launch_probe(c.st, n, ea, dc, db, dX, dout));
 }
 
+// ---- fsi_post.hip, fsi_hemo.hip, fsi_stress.hip: wall shear stress, hemodynamic sums and indices, solid stress / strain and
+// principal values, one cell (or dof) at a time (tests/test_gpu_post_cell_kernels.py; references in tests/post_cells.py) --------------
+// Host arrays throughout, no live context.  The cell arrays are those of a case of C cells (geom [C][10], cell_dofs [C][64],
+// cell_region [C]), the launch runs over the list cells [ncell] (any order, repeats allowed).  Every entry uploads the tables its
+// kernel reads from arrays the caller passes: upload_post_tables (which fills the copies of fsi_stress.hip too) with the Keast-24
+// weights qw [24], dN [24][10][3] and L [24][4]; hemo_upload_tables with the triangle rule tw [12], tl [12][3].  ElemParams as for the
+// element kernels.  Every index array is checked on the host first (status 3, nothing launched): the cell ids against C, cell_dofs
+// against the state's length, the facet masks against 0 .. 15, the regions against the tables, fidx against the accumulators' facets (each named once),
+// the rows of ent against dst.  Every output carries SHIM_TAIL.
+extern "C++" {
+namespace {
+int cell_list_checked(const char* who, int64_t ncell, int64_t C, int64_t nu, const int32_t* cell_dofs, const int32_t* cells) {
+  if (ncell < 1 || C < 1) { g_err = std::string(who) + ": no cells"; return 3; }
+  if (const int rc = indices_checked(who, cell_dofs, NLOC * C, nu)) return rc;
+  return indices_checked(who, cells, ncell, C);
+}
+int masks_checked(const char* who, const int32_t* fmask, int64_t ncell) {
+  for (int64_t i = 0; i < ncell; ++i)
+    if (fmask[i] < 0 || fmask[i] > 15) { g_err = std::string(who) + ": facet mask " + std::to_string(i) + " outside 0 .. 15"; return 3; }
+  return 0;
+}
+int regions_checked(const char* who, const int32_t* region, int64_t C) {
+  for (int64_t c = 0; c < C; ++c)
+    if (region[c] < 0 || region[c] >= MAX_REGIONS) { g_err = std::string(who) + ": region of cell " + std::to_string(c) + " outside the tables"; return 3; }
+  return 0;
+}
+ElemArrays wss_arrays(Call& c, int64_t C, const double* geom, const int32_t* cell_dofs) {
+  ElemArrays ea{};
+  ea.geom = c.in(geom, (size_t)(10 * C));
+  ea.cell_dofs = c.in(cell_dofs, (size_t)(NLOC * C));
+  return ea;
+}
+}  // namespace
+}  // extern "C++"
+// U [nu]; cells, fmask [ncell]; out [12 ncell + SHIM_TAIL]: the traction coefficients [ncell][4][3]
+int shim_wss(int64_t ncell, int64_t C, int64_t nu, const double* geom, const int32_t* cell_dofs, const double* U, const int32_t* cells,
+             const int32_t* fmask, double mu, double* out) {
+  if (const int rc = cell_list_checked("shim_wss", ncell, C, nu, cell_dofs, cells)) return rc;
+  if (const int rc = masks_checked("shim_wss", fmask, ncell)) return rc;
+  Call c;
+  const ElemArrays ea = wss_arrays(c, C, geom, cell_dofs);
+  const double* dU = c.in(U, (size_t)nu);
+  const int32_t* dc = c.in(cells, (size_t)ncell);
+  const int32_t* dm = c.in(fmask, (size_t)ncell);
+  double* dout = c.io(out, (size_t)(12 * ncell) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_wss", launch_wss(c.st, ncell, ea, dU, dc, dm, mu, dout));
+}
+// fidx [ncell][4]: the facet (of nf) of every facet set in the mask, read there only; no facet may be named twice over the whole list
+// (two lanes would then add to the same accumulators: status 3).  Accumulators in / out over 3 nf dofs:
+// sum_tau, tau_prev [9 nf + SHIM_TAIL], sum_mag, sum_twssg [3 nf + SHIM_TAIL]; wss_out [9 nf + SHIM_TAIL] or null.
+int shim_hemo_sample(int64_t ncell, int64_t C, int64_t nu, const double* geom, const int32_t* cell_dofs, const double* U,
+                     const int32_t* cells, const int32_t* fmask, const int32_t* fidx, int64_t nf, double mu, double dt, const double* tw,
+                     const double* tl, double* sum_tau, double* tau_prev, double* sum_mag, double* sum_twssg, double* wss_out) {
+  if (const int rc = cell_list_checked("shim_hemo_sample", ncell, C, nu, cell_dofs, cells)) return rc;
+  if (const int rc = masks_checked("shim_hemo_sample", fmask, ncell)) return rc;
+  std::vector<char> named((size_t)(nf > 0 ? nf : 0), 0);
+  for (int64_t i = 0; i < ncell; ++i)
+    for (int f = 0; f < 4; ++f) {
+      if (!(fmask[i] >> f & 1)) continue;
+      const int32_t k = fidx[4 * i + f];
+      if (k < 0 || k >= nf || named[(size_t)k]) {
+        g_err = "shim_hemo_sample: facet " + std::to_string(f) + " of list entry " + std::to_string(i) +
+                (k < 0 || k >= nf ? " outside the accumulators" : " names a facet of the accumulators a second time");
+        return 3;
+      }
+      named[(size_t)k] = 1;
+    }
+  Call c;
+  c.note(hemo_upload_tables(tw, tl));
+  const ElemArrays ea = wss_arrays(c, C, geom, cell_dofs);
+  const double* dU = c.in(U, (size_t)nu);
+  const int32_t* dc = c.in(cells, (size_t)ncell);
+  const int32_t* dm = c.in(fmask, (size_t)ncell);
+  const int32_t* df = c.in(fidx, (size_t)(4 * ncell));
+  HemoAcc acc;
+  acc.sum_tau = c.io(sum_tau, (size_t)(9 * nf) + SHIM_TAIL);
+  acc.tau_prev = c.io(tau_prev, (size_t)(9 * nf) + SHIM_TAIL);
+  acc.sum_mag = c.io(sum_mag, (size_t)(3 * nf) + SHIM_TAIL);
+  acc.sum_twssg = c.io(sum_twssg, (size_t)(3 * nf) + SHIM_TAIL);
+  double* dw = c.io(wss_out, (size_t)(9 * nf) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_hemo_sample", launch_hemo_sample(c.st, ncell, ea, dU, dc, dm, df, mu, dt, acc, dw));
+}
+// sum_tau [3 ndof], sum_mag, sum_twssg [ndof]; out [5 ndof + SHIM_TAIL] = TAWSS, OSI, RRT, ECAP, TWSSG
+int shim_hemo_finish(int64_t ndof, double samples, const double* sum_tau, const double* sum_mag, const double* sum_twssg, double* out) {
+  if (ndof < 1) { g_err = "shim_hemo_finish: no dofs"; return 3; }
+  Call c;
+  HemoAcc acc{};
+  acc.sum_tau = const_cast<double*>(c.in(sum_tau, (size_t)(3 * ndof)));
+  acc.sum_mag = const_cast<double*>(c.in(sum_mag, (size_t)ndof));
+  acc.sum_twssg = const_cast<double*>(c.in(sum_twssg, (size_t)ndof));
+  double* dout = c.io(out, (size_t)(5 * ndof) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_hemo_finish", launch_hemo_finish(c.st, ndof, samples, acc, dout));
+}
+// ptr [ncell + 1] / ent [ptr[ncell]][2] = (row of dst, 4 * local vertex + component code); dst [nrows + SHIM_TAIL] in / out
+int shim_spec_wss_sample(int64_t ncell, int64_t C, int64_t nu, const double* geom, const int32_t* cell_dofs, const double* U,
+                         const int32_t* cells, const int32_t* fmask, const int32_t* ptr, const int32_t* ent, int64_t nrows, double mu,
+                         double* dst) {
+  if (const int rc = cell_list_checked("shim_spec_wss_sample", ncell, C, nu, cell_dofs, cells)) return rc;
+  if (const int rc = masks_checked("shim_spec_wss_sample", fmask, ncell)) return rc;
+  if (ptr[0] != 0 || nrows < 1) { g_err = "shim_spec_wss_sample: the entry ranges do not start at 0, or no rows"; return 3; }
+  for (int64_t i = 0; i < ncell; ++i)
+    if (ptr[i + 1] < ptr[i]) { g_err = "shim_spec_wss_sample: entry range " + std::to_string(i) + " decreases"; return 3; }
+  for (int64_t e = 0; e < ptr[ncell]; ++e)
+    if (ent[2 * e] < 0 || ent[2 * e] >= nrows || ent[2 * e + 1] < 0 || ent[2 * e + 1] > 15) {
+      g_err = "shim_spec_wss_sample: entry " + std::to_string(e) + " outside dst, or no such vertex / component";
+      return 3;
+    }
+  Call c;
+  const ElemArrays ea = wss_arrays(c, C, geom, cell_dofs);
+  const double* dU = c.in(U, (size_t)nu);
+  const int32_t* dc = c.in(cells, (size_t)ncell);
+  const int32_t* dm = c.in(fmask, (size_t)ncell);
+  const int32_t* dp = c.in(ptr, (size_t)ncell + 1);
+  const int32_t* de = c.in(ent, (size_t)(2 * ptr[ncell]));
+  double* dd = c.io(dst, (size_t)nrows + SHIM_TAIL);
+  SHIM_RUN(c, "launch_spec_wss_sample", launch_spec_wss_sample(c.st, ncell, ea, dU, dc, dm, dp, de, mu, dd));
+}
+extern "C++" {
+namespace {
+// the checks and uploads the three cell kernels of the solid tensors share; returns nonzero with nothing uploaded
+int solid_cells(const char* who, Call& c, int64_t ncell, int64_t C, int64_t nu, const double* geom, const int32_t* cell_dofs,
+                const int32_t* cell_region, const double* qw, const double* dN, const double* L, const double* U, const int32_t* cells,
+                ElemArrays& ea, const double*& dU, const int32_t*& dc) {
+  if (const int rc = cell_list_checked(who, ncell, C, nu, cell_dofs, cells)) return rc;
+  if (const int rc = regions_checked(who, cell_region, C)) return rc;
+  c.note(upload_post_tables(qw, dN, L));
+  ea = wss_arrays(c, C, geom, cell_dofs);
+  ea.cell_region = c.in(cell_region, (size_t)C);
+  dU = c.in(U, (size_t)nu);
+  dc = c.in(cells, (size_t)ncell);
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+// out [80 ncell + SHIM_TAIL]: per listed cell TrueStress [4][9], GreenLagrangeStrain [4][9], MaxPrincipalStress [4], MaxPrincipalStrain [4]
+int shim_stress_strain(int64_t ncell, int64_t C, int64_t nu, const double* geom, const int32_t* cell_dofs, const int32_t* cell_region,
+                       const double* sc, const double* fluid, const double* solid, const double* qw, const double* dN, const double* L,
+                       const double* U, const int32_t* cells, double* out) {
+  Call c;
+  ElemArrays ea{};
+  const double* dU = nullptr;
+  const int32_t* dc = nullptr;
+  if (const int rc = solid_cells("shim_stress_strain", c, ncell, C, nu, geom, cell_dofs, cell_region, qw, dN, L, U, cells, ea, dU, dc)) return rc;
+  const ElemParams ep = elem_params(sc, fluid, solid);
+  double* dout = c.io(out, (size_t)(80 * ncell) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_stress_strain", launch_stress_strain(c.st, ncell, ea, ep, dU, dc, dout));
+}
+// frame [80 ncell + SHIM_TAIL] as out of shim_stress_strain; sums [8 ncell + SHIM_TAIL] in / out
+int shim_stress_sample(int64_t ncell, int64_t C, int64_t nu, const double* geom, const int32_t* cell_dofs, const int32_t* cell_region,
+                       const double* sc, const double* fluid, const double* solid, const double* qw, const double* dN, const double* L,
+                       const double* U, const int32_t* cells, double* frame, double* sums) {
+  Call c;
+  ElemArrays ea{};
+  const double* dU = nullptr;
+  const int32_t* dc = nullptr;
+  if (const int rc = solid_cells("shim_stress_sample", c, ncell, C, nu, geom, cell_dofs, cell_region, qw, dN, L, U, cells, ea, dU, dc)) return rc;
+  const ElemParams ep = elem_params(sc, fluid, solid);
+  double* df = c.io(frame, (size_t)(80 * ncell) + SHIM_TAIL);
+  double* ds = c.io(sums, (size_t)(8 * ncell) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_stress_sample", launch_stress_sample(c.st, ncell, ea, ep, dU, dc, df, ds));
+}
+// sums [8 ncell]; out [8 ncell + SHIM_TAIL] = [2][ncell][4]
+int shim_stress_average(int64_t ncell, double samples, const double* sums, double* out) {
+  if (ncell < 1) { g_err = "shim_stress_average: no cells"; return 3; }
+  Call c;
+  const double* ds = c.in(sums, (size_t)(8 * ncell));
+  double* dout = c.io(out, (size_t)(8 * ncell) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_stress_average", launch_stress_average(c.st, ncell, samples, ds, dout));
+}
+// dst [24 ncell + SHIM_TAIL]: rows (4 ci + a) 6 + comp of the strain (strain != 0) or the stress
+int shim_tensor_sample(int64_t ncell, int64_t C, int64_t nu, int strain, const double* geom, const int32_t* cell_dofs,
+                       const int32_t* cell_region, const double* sc, const double* fluid, const double* solid, const double* qw,
+                       const double* dN, const double* L, const double* U, const int32_t* cells, double* dst) {
+  Call c;
+  ElemArrays ea{};
+  const double* dU = nullptr;
+  const int32_t* dc = nullptr;
+  if (const int rc = solid_cells("shim_tensor_sample", c, ncell, C, nu, geom, cell_dofs, cell_region, qw, dN, L, U, cells, ea, dU, dc)) return rc;
+  const ElemParams ep = elem_params(sc, fluid, solid);
+  double* dd = c.io(dst, (size_t)(24 * ncell) + SHIM_TAIL);
+  SHIM_RUN(c, "launch_tensor_sample", launch_tensor_sample(c.st, ncell, ea, ep, dU, dc, strain != 0, dd));
+}
+// amp [6 nnode] = 11, 12, 22, 23, 33, 31 per dof; mag [nnode + SHIM_TAIL]
+int shim_tensor_principal(int64_t nnode, const double* amp, double* mag) {
+  if (nnode < 1) { g_err = "shim_tensor_principal: no dofs"; return 3; }
+  Call c;
+  const double* da = c.in(amp, (size_t)(6 * nnode));
+  double* dm = c.io(mag, (size_t)nnode + SHIM_TAIL);
+  SHIM_RUN(c, "launch_tensor_principal", launch_tensor_principal(c.st, nnode, da, dm));
+}
+
 // ---- a live context's preconditioner arrays (FsiCtx of fsi_context.hpp, as the library was compiled) -----------------------
 // shim_ctx_info: N2, V, nS, sb_nblocks, tiled, tile_nodes, tile_max_nu, schur_tiled, schur_tile, s_tile_max_nu, sweeps_fp16,
 // a32_ptail, a32_tail_src, a32_tail_nnz, op32_ok, kry_fp32, drows_ok, mg_nc, mg_cnnz, mg_ready, sbmg_nc, sbmg_nblk, sbmg_ready,

@@ -38,7 +38,10 @@ __global__ __launch_bounds__(64) void k_stress_sample(ElemArrays ea, ElemParams 
                                                       double* __restrict__ sums) {
   const int64_t ci = blockIdx.x;
   const double pv = stress_strain_cell(ea, ep, U, cells[ci], frame + ci * 80);
-  if (threadIdx.x < 8) sums[ci * 8 + threadIdx.x] += pv;
+  if (threadIdx.x < 8) {
+#pragma clang fp contract(off)   // add the value the frame holds: contracted, the sum would take pv's last product unrounded
+    sums[ci * 8 + threadIdx.x] += pv;
+  }
 }
 
 // out[2][n][4]: MaxPrincipalStress_avg, MaxPrincipalStrain_avg
