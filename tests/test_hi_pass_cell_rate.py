@@ -233,6 +233,33 @@ def test_every_refusal_of_the_twin(mesh, cells):
         s.cell_rate("raw")
 
 
+def same_bits(a, b) -> bool:
+    """Equal values with NaN equal to NaN, and equal signs of the zeros: the rule of the GPU tests."""
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and np.array_equal(a, b, equal_nan=True) and np.array_equal(np.signbit(a[a == 0]), np.signbit(b[b == 0]))
+
+
+def test_twin_bits_are_those_recorded():
+    """The GPU tests hold the device to the twins bit for bit; this holds the twins to their own recorded bits, so that a
+    change to the pieces they share (``hi_pass.vertex_gradients``) cannot move both.  golden/hi_pass/cell_twin_bits.npz
+    (golden/make_cell_twin_bits.py): 7 cells - one with a NaN, one with an inf, one of zeros of both signs, one folded by its
+    displacement so that one ``J_q < 0`` - and what ``cell_rate``, ``cell_rate_current``, ``cell_vortex`` and ``cell_wsum`` of
+    the vortex rows gave for them when the fixture was recorded.  The sums over all seven cells are NaN in every row, so the
+    sums over the cells with finite rows are held as well."""
+    z = np.load(ROOT / "tests" / "golden" / "hi_pass" / "cell_twin_bits.npz")
+    w, d, grad, weights = z["w"], z["d"], z["grad"], z["weights"]
+    assert w.shape == d.shape == (7, 10, 3) and np.isnan(w).any() and np.isinf(w).any() and np.signbit(w[w == 0]).any()
+    assert same_bits(hp.cell_rate(w, grad), z["rate"])
+    for got, name in zip(hp.cell_rate_current(w, d, grad), ("rate_current", "volume_ratio", "min_jacobian")):
+        assert same_bits(got, z[name]), name
+    assert (z["min_jacobian"] < 0).sum() == 1 and np.isnan(z["rate"]).any() and (z["rate"] == 0).any()
+    vortex = hp.cell_vortex(w, grad)
+    assert same_bits(vortex, z["vortex"])
+    finite = np.isfinite(vortex).all(axis=0)
+    assert same_bits(hp.cell_wsum(vortex, weights), z["wsum"]) and same_bits(hp.cell_wsum(vortex[:, finite], weights[finite]), z["wsum_finite"])
+    assert finite.sum() == 5 and np.isfinite(z["wsum_finite"]).all()
+
+
 # ---- the closing formulas -------------------------------------------------------------------------------------------------
 
 def test_closing_formulas_on_hand_made_arrays():

@@ -752,15 +752,20 @@ class HipBackend:
         self._band_cells[quantity] = len(ci)
         return grad
 
+    def _cell_frames(self, quantity: str, series: str, first: int, step: int, count: int) -> tuple:
+        """``(first, step, count)`` as integers, ``count`` -1 made as many frames as the series has; refusing is the entry point's."""
+        first, step, count = int(first), int(step), int(count)
+        if count == -1 and step >= 1:
+            frames = getattr(self, "_band_period", {}).get(quantity, 0) if series == "phase_mean" else self._band_frames[quantity][1]
+            count = (frames - 1 - first) // step + 1
+        return first, step, count
+
     def hi_pass_cell_rate(self, quantity: str, series: str, first: int = 0, step: int = 1, count: int = -1) -> np.ndarray:
         """Per attached cell the mean over frames ``first, first + step, ...`` (``count`` of them, -1: as many as the series
         has) of the cell mean of 2 S:S, S = sym(grad w), summed in frame order from +0.0 and divided by the count
         (fsi_band_cell_rate).  ``series``: 'raw' the selected frames, 'series' the filtered series or the fluctuation,
         'phase_mean' the frames of the phase mean.  (n,)."""
-        first, step, count = int(first), int(step), int(count)
-        if count == -1 and step >= 1:
-            frames = getattr(self, "_band_period", {}).get(quantity, 0) if series == "phase_mean" else self._band_frames[quantity][1]
-            count = (frames - 1 - first) // step + 1
+        first, step, count = self._cell_frames(quantity, series, first, step, count)
         out = np.empty(getattr(self, "_band_cells", {}).get(quantity, 0))
         self._check(self.lib.fsi_band_cell_rate(self.ctx, self.BAND_QUANTITY[quantity], self.RATE_SERIES[series], first, step, count,
                                                 _ptr(out) if len(out) else None))
@@ -771,10 +776,7 @@ class HipBackend:
         history of the 'd' session on the same nodes and frames.  Returns ``(rate, volume_ratio, min_jacobian)``, (n,) each:
         the mean over the frames of the mean of 2 S:S over the deformed cell, S = sym(grad w F^-1); the mean over the frames
         of the deformed cell's volume over the undeformed; the smallest det F met at the rule's four points."""
-        first, step, count = int(first), int(step), int(count)
-        if count == -1 and step >= 1:
-            frames = getattr(self, "_band_period", {}).get(quantity, 0) if series == "phase_mean" else self._band_frames[quantity][1]
-            count = (frames - 1 - first) // step + 1
+        first, step, count = self._cell_frames(quantity, series, first, step, count)
         n = getattr(self, "_band_cells", {}).get(quantity, 0)
         rate, volume_ratio, min_jacobian = np.empty(n), np.empty(n), np.empty(n)
         self._check(self.lib.fsi_band_cell_rate_current(self.ctx, self.BAND_QUANTITY[quantity], self.RATE_SERIES[series], first, step, count,
@@ -802,10 +804,7 @@ class HipBackend:
         0.5 (|Omega|^2 - |S|^2), the enstrophy |omega|^2, the helicity w . omega, its absolute value (of the cell mean of each
         frame, not the cell mean of |w . omega|) and |w|^2.  ``sums`` (5,) or None: the ordered sum over the cells of weight
         times each row (``hi_pass_cell_weights`` first; the bracket is that of ``hi_pass.cell_wsum``)."""
-        first, step, count = int(first), int(step), int(count)
-        if count == -1 and step >= 1:
-            frames = getattr(self, "_band_period", {}).get(quantity, 0) if series == "phase_mean" else self._band_frames[quantity][1]
-            count = (frames - 1 - first) // step + 1
+        first, step, count = self._cell_frames(quantity, series, first, step, count)
         n = getattr(self, "_band_cells", {}).get(quantity, 0)
         out = np.empty((len(self.VORTEX_FIELDS), n)) if cells else None
         total = np.empty(len(self.VORTEX_FIELDS)) if sums else None

@@ -9,7 +9,7 @@
 //   k_cell_rate : one lane per listed cell.  The lane keeps the cell's ten node indices and its twelve gradient values in
 //                 registers and walks `count` frames of one series.  Per frame it gathers the ten nodes' triples (240 B), forms
 //                 G_t = grad w at the four vertices t - the gradient of a P2 field is linear on the cell, so they determine it;
-//                 the expression is that of wss_dg1_cell (fsi_wss.hpp), restated -, S_t = 0.5 (G_t + G_t^T) and
+//                 the lane state, the gather and the expression are those of fsi_cell.hpp -, S_t = 0.5 (G_t + G_t^T) and
 //                 r = 0.1 * (sum_t S_t:S_t + (sum_t S_t):(sum_t S_t)), the exact cell mean of 2 S:S, since the integral of
 //                 L_a L_b over the cell is |K| (1 + delta_ab) / 20.  out = (((+0.0 + r_0) + r_1) + ...) / count: the sum in frame
 //                 order, a true division; one frame gives its own bits.  NaN and inf propagate, nothing is clamped.
@@ -29,6 +29,7 @@
 // No LDS, no atomics, FP64 vector loads and stores.  Floating-point contraction is off, as in fsi_band.hip and fsi_phase.hip:
 // the NumPy twins (hi_pass.cell_rate, hi_pass.cell_rate_current) round every product and every sum, and the device equals them bit for bit.
 #include "fsi_rate.hpp"
+#include "fsi_cell.hpp"
 
 #pragma clang fp contract(off)
 
@@ -51,7 +52,6 @@ __global__ __launch_bounds__(256) void k_cell_gl(int64_t n, const double* __rest
 // the cell mean of 2 sym(grad w):sym(grad w): w[a][i] component i of local node a, gl[a][j] the gradient of barycentric
 // coordinate a.  Every operation in the order of hi_pass.cell_rate.
 __device__ __forceinline__ double cell_rate_of(const double (&w)[10][3], double (&gl)[4][3]) {
-  const int E[6][2] = {{2, 3}, {1, 3}, {1, 2}, {0, 3}, {0, 2}, {0, 1}};
   double q = 0.0, T[3][3];
 #pragma unroll
   for (int i = 0; i < 3; ++i)
@@ -59,29 +59,9 @@ __device__ __forceinline__ double cell_rate_of(const double (&w)[10][3], double 
     for (int j = 0; j < 3; ++j) T[i][j] = 0.0;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    // The products of the gradient values with the basis coefficients below do not depend on the frame: left alone, the
-    // compiler forms all 78 of them once and keeps them in registers across the frame loop (256 VGPRs + 68 AGPRs, one wave per
-    // SIMD).  Making gl opaque here has them formed again per vertex and frame - a quarter more multiplications, the same bits -
-    // and leaves room for two waves per SIMD, which the gather needs to hide its latency.
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) asm volatile("" : "+v"(gl[a][j]));
-    double G[3][3];                                   // grad w at vertex t
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        double s = 0.0;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) s = s + w[a][i] * ((a == t ? 3.0 : -1.0) * gl[a][j]);
-#pragma unroll
-        for (int e = 0; e < 6; ++e) {
-          const int p = E[e][0], r = E[e][1];
-          s = s + (w[4 + e][i] * 4.0) * ((p == t ? 1.0 : 0.0) * gl[r][j] + (r == t ? 1.0 : 0.0) * gl[p][j]);
-        }
-        G[i][j] = s;
-      }
+    fence_cell_gradients(gl);
+    double G[3][3];
+    vertex_gradient_of(w, gl, t, G);
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -104,54 +84,24 @@ __global__ __launch_bounds__(256) void k_cell_rate(int64_t n, const int32_t* __r
                                                    double* __restrict__ out) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n) return;
-  int64_t row[10];
-#pragma unroll
-  for (int a = 0; a < 10; ++a) row[a] = 3 * (int64_t)conn[c * 10 + a];
-  double gl[4][3];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) gl[a][j] = gl_all[c * 12 + a * 3 + j];
+  CellLane lane;
+  load_cell_lane(conn, gl_all, c, lane);
   double s = 0.0;
   for (int64_t k = 0; k < count; ++k) {
-    const double* f = x + k * frame_stride;
     double w[10][3];
-#pragma unroll
-    for (int a = 0; a < 10; ++a)
-#pragma unroll
-      for (int i = 0; i < 3; ++i) w[a][i] = f[row[a] + i];
-    s = s + cell_rate_of(w, gl);
+    gather_cell_frame(x + k * frame_stride, lane, w);
+    s = s + cell_rate_of(w, lane.gl);
   }
   out[c] = s / (double)count;
 }
 
-// G[t] = grad w at the four vertices t: the expression of cell_rate_of, gl kept opaque per vertex for the reason given there
+// G[t] = grad w at the four vertices t, one vertex after the other (the two fences: fsi_cell.hpp)
 __device__ __forceinline__ void vertex_gradients_of(const double (&w)[10][3], double (&gl)[4][3], double (&G)[4][3][3]) {
-  const int E[6][2] = {{2, 3}, {1, 3}, {1, 2}, {0, 3}, {0, 2}, {0, 1}};
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) asm volatile("" : "+v"(gl[a][j]));
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        double s = 0.0;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) s = s + w[a][i] * ((a == t ? 3.0 : -1.0) * gl[a][j]);
-#pragma unroll
-        for (int e = 0; e < 6; ++e) {
-          const int p = E[e][0], r = E[e][1];
-          s = s + (w[4 + e][i] * 4.0) * ((p == t ? 1.0 : 0.0) * gl[r][j] + (r == t ? 1.0 : 0.0) * gl[p][j]);
-        }
-        G[t][i][j] = s;
-      }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) asm volatile("" : "+v"(G[t][i][j]));      // this vertex is done before the next begins
+    fence_cell_gradients(gl);
+    vertex_gradient_of(w, gl, t, G[t]);
+    fence_vertex_gradient(G[t]);
   }
 }
 
@@ -226,31 +176,17 @@ __global__ __launch_bounds__(256) void k_cell_rate_current(int64_t n, const int3
                                                            double* __restrict__ min_jacobian) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n) return;
-  int64_t row[10];
-#pragma unroll
-  for (int a = 0; a < 10; ++a) row[a] = 3 * (int64_t)conn[c * 10 + a];
-  double gl[4][3];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) gl[a][j] = gl_all[c * 12 + a * 3 + j];
+  CellLane lane;
+  load_cell_lane(conn, gl_all, c, lane);
   double s = 0.0, sv = 0.0, m = __builtin_inf();
   for (int64_t k = 0; k < count; ++k) {
     // the displacement's ten triples become its vertex gradients before the field's are needed: thirty nodal values and
     // seventy-two gradient entries are live at most, not the sixty nodal values of both
     double w[10][3], D[4][3][3], G[4][3][3];
-    const double* f = geo + k * geo_stride;
-#pragma unroll
-    for (int a = 0; a < 10; ++a)
-#pragma unroll
-      for (int i = 0; i < 3; ++i) w[a][i] = f[row[a] + i];
-    vertex_gradients_of(w, gl, D);
-    f = x + k * frame_stride;
-#pragma unroll
-    for (int a = 0; a < 10; ++a)
-#pragma unroll
-      for (int i = 0; i < 3; ++i) w[a][i] = f[row[a] + i];
-    vertex_gradients_of(w, gl, G);
+    gather_cell_frame(geo + k * geo_stride, lane, w);
+    vertex_gradients_of(w, lane.gl, D);
+    gather_cell_frame(x + k * frame_stride, lane, w);
+    vertex_gradients_of(w, lane.gl, G);
     double r, vol;
     current_rate_of(G, D, r, vol, m);
     s = s + r;

@@ -1,15 +1,18 @@
 // Cell means of the strain rate of a recorded vector history (fsi_rate.hip): the launchers the C-ABI (fsi_band_cells,
 // fsi_band_cell_rate, fsi_band_cell_rate_current in fsi_sessions.hip) calls.
 //
-// Compiler's resource report of k_cell_rate for gfx950 (-Rpass-analysis=kernel-resource-usage): 180 VGPRs, no AGPRs, 22 SGPRs,
+// The lane state, the gather and the vertex gradient are those of fsi_cell.hpp, shared with k_cell_vortex (fsi_vortex.hip).
+//
+// Compiler's resource report of k_cell_rate for gfx950 (-Rpass-analysis=kernel-resource-usage): 180 VGPRs, no AGPRs, 20 SGPRs,
 // no scratch, no LDS; two waves per SIMD.  (With the frame loop's invariants - the 78 products of the gradient values with the
-// basis coefficients of the restated expression - kept in registers it took 256 VGPRs and 68 AGPRs, one wave per SIMD; see the
-// comment in cell_rate_of and DESIGN.md section 8.)
+// basis coefficients of vertex_gradient_of - kept in registers it took 256 VGPRs and 68 AGPRs, one wave per SIMD; see the
+// comment at fence_cell_gradients (fsi_cell.hpp) and DESIGN.md section 8.)
 //
 // The same report of k_cell_rate_current: 256 VGPRs, 22 AGPRs, 28 SGPRs, no scratch, no LDS; one wave per SIMD.  The vertex
 // gradients are formed one vertex after the other (vertex_gradients_of makes each vertex's nine values opaque before the next
-// begins): left to the scheduler, the 36 x 22 independent products are formed ahead of their sums and the kernel takes all 512
-// registers and 332 bytes of scratch per lane.  Asking for two waves per SIMD costs 92 bytes of scratch, so it is one wave.
+// begins, fence_vertex_gradient): left to the scheduler, the 36 x 22 independent products are formed ahead of their sums and
+// the kernel takes all 512 registers and 332 bytes of scratch per lane.  Asking for two waves per SIMD costs 92 bytes of
+// scratch, so it is one wave.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

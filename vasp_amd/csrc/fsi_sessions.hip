@@ -207,6 +207,39 @@ bool partitioned(FsiCtx* ctx, const char* fn) {
   return ctx->part;
 }
 
+// The frames of a series of a cell session, for fsi_band_cell_rate, fsi_band_cell_rate_current and fsi_band_cell_vortex, in
+// two steps with the entry point's own checks between them.  First the session of `quantity` with a cell list and the series
+// `series` (FSI_RATE_*) in place, or null with ctx->err set (ctx null: nothing to set it on).
+FsiCtx::Band* cell_series_session(FsiCtx* ctx, const char* fn, int32_t quantity, int32_t series) {
+  if (!ctx || partitioned(ctx, fn)) return nullptr;
+  auto refuse = [&](const char* why) -> FsiCtx::Band* { ctx->err = std::string(fn) + ": " + why; return nullptr; };
+  if (quantity != 0 && quantity != 1) return refuse("quantity must be 0 (d) or 1 (v)");
+  auto* s = band_session(ctx, quantity, fn);
+  if (!s) return nullptr;
+  if (series < FSI_RATE_RAW || series > FSI_RATE_PHASE_MEAN) return refuse("series must be FSI_RATE_RAW, FSI_RATE_SERIES or FSI_RATE_PHASE_MEAN");
+  if (s->ncell < 1) return refuse("no cell list (fsi_band_cells first)");
+  if (series == FSI_RATE_SERIES && !s->filtered) return refuse("no filtered series (fsi_band_filter or fsi_band_phase first)");
+  if (series == FSI_RATE_PHASE_MEAN && (s->phase_period < 1 || !s->filtered)) return refuse("no phase average (fsi_band_phase first)");
+  return s;
+}
+// Then frames first, first + step, ... (`count` of them) of that series, which must hold them all.  *x: frame `first`;
+// *frame_stride: the doubles from one taken frame to the next.  The series is frames of nrow doubles: the raw history from the
+// selection's first frame, sel_stride recorded frames apart; the filtered series; the phase means.
+int cell_series_frames(FsiCtx* ctx, const char* fn, const FsiCtx::Band* s, int32_t series, int64_t first, int64_t step, int64_t count,
+                       const double** x, int64_t* frame_stride) {
+  auto refuse = [&](const std::string& why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
+  const int64_t frames = series == FSI_RATE_PHASE_MEAN ? s->phase_period : band_frames(s);
+  if (step < 1 || count < 1) return refuse("needs step >= 1 and count >= 1, got step = " + std::to_string(step) + ", count = " + std::to_string(count));
+  if (first < 0 || first >= frames || count - 1 > (frames - 1 - first) / step)
+    return refuse("frames " + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(step) + ", ... (" + std::to_string(count) +
+                  " of them) fall outside the series of " + std::to_string(frames) + " frames");
+  const double* x0 = series == FSI_RATE_RAW ? s->hist.p + (size_t)s->sel_first * s->nrow : series == FSI_RATE_SERIES ? history_frame(s, true, 0) : s->phase_mean.p;
+  const int64_t stride = series == FSI_RATE_RAW ? s->sel_stride : 1;
+  *x = x0 + (size_t)(first * stride) * s->nrow;
+  *frame_stride = step * stride * s->nrow;
+  return FSI_OK;
+}
+
 // raw frames first .. first + count - 1 of the history to the host, out[count][nrow]: frame-major, so one copy, behind
 // whatever was sampled on the stream; it has finished when the call returns
 int history_export(FsiCtx* ctx, const FsiCtx::History* s, const char* fn, int64_t first, int64_t count, double* out) {
@@ -1069,28 +1102,15 @@ int fsi_band_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* cell
 }
 
 int fsi_band_cell_rate(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count, double* out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_cell_rate")) return FSI_ERR_INVALID;
-  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_cell_rate: " + why; return FSI_ERR_INVALID; };
-  if (quantity != 0 && quantity != 1) return refuse("quantity must be 0 (d) or 1 (v)");
-  auto* s = band_session(ctx, quantity, "fsi_band_cell_rate");
+  const char* fn = "fsi_band_cell_rate";
+  auto* s = cell_series_session(ctx, fn, quantity, series);
   if (!s) return FSI_ERR_INVALID;
-  if (series < FSI_RATE_RAW || series > FSI_RATE_PHASE_MEAN) return refuse("series must be FSI_RATE_RAW, FSI_RATE_SERIES or FSI_RATE_PHASE_MEAN");
-  if (s->ncell < 1) return refuse("no cell list (fsi_band_cells first)");
-  if (series == FSI_RATE_SERIES && !s->filtered) return refuse("no filtered series (fsi_band_filter or fsi_band_phase first)");
-  if (series == FSI_RATE_PHASE_MEAN && (s->phase_period < 1 || !s->filtered)) return refuse("no phase average (fsi_band_phase first)");
-  if (!out) return refuse("out is NULL");
-  const int64_t frames = series == FSI_RATE_PHASE_MEAN ? s->phase_period : band_frames(s);
-  if (step < 1 || count < 1) return refuse("needs step >= 1 and count >= 1, got step = " + std::to_string(step) + ", count = " + std::to_string(count));
-  if (first < 0 || first >= frames || count - 1 > (frames - 1 - first) / step)
-    return refuse("frames " + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(step) + ", ... (" + std::to_string(count) +
-                  " of them) fall outside the series of " + std::to_string(frames) + " frames");
-  // the series as frames of nrow doubles, `stride` frames of the underlying array apart
-  const double* x = series == FSI_RATE_RAW ? s->hist.p + (size_t)s->sel_first * s->nrow : series == FSI_RATE_SERIES ? history_frame(s, true, 0) : s->phase_mean.p;
-  const int64_t stride = series == FSI_RATE_RAW ? s->sel_stride : 1;
+  if (!out) { ctx->err = std::string(fn) + ": out is NULL"; return FSI_ERR_INVALID; }
+  const double* x = nullptr;
+  int64_t frame_stride = 0;
+  FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x, &frame_stride));
   HIPCHK(hipSetDevice(ctx->device));
-  launch_cell_rate(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x + (size_t)(first * stride) * s->nrow, step * stride * s->nrow, count,
-                   s->cell_out.p);
+  launch_cell_rate(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, count, s->cell_out.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, s->cell_out.p, (size_t)s->ncell * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1099,22 +1119,14 @@ int fsi_band_cell_rate(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t fi
 
 int fsi_band_cell_rate_current(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count, double* rate_out,
                                double* volume_ratio_out, double* min_jacobian_out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_cell_rate_current")) return FSI_ERR_INVALID;
-  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_cell_rate_current: " + why; return FSI_ERR_INVALID; };
-  if (quantity != 0 && quantity != 1) return refuse("quantity must be 0 (d) or 1 (v)");
-  auto* s = band_session(ctx, quantity, "fsi_band_cell_rate_current");
+  const char* fn = "fsi_band_cell_rate_current";
+  auto* s = cell_series_session(ctx, fn, quantity, series);
   if (!s) return FSI_ERR_INVALID;
-  if (series < FSI_RATE_RAW || series > FSI_RATE_PHASE_MEAN) return refuse("series must be FSI_RATE_RAW, FSI_RATE_SERIES or FSI_RATE_PHASE_MEAN");
-  if (s->ncell < 1) return refuse("no cell list (fsi_band_cells first)");
-  if (series == FSI_RATE_SERIES && !s->filtered) return refuse("no filtered series (fsi_band_filter or fsi_band_phase first)");
-  if (series == FSI_RATE_PHASE_MEAN && (s->phase_period < 1 || !s->filtered)) return refuse("no phase average (fsi_band_phase first)");
+  auto refuse = [&](const std::string& why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
   if (!rate_out) return refuse("rate_out is NULL");
-  const int64_t frames = series == FSI_RATE_PHASE_MEAN ? s->phase_period : band_frames(s);
-  if (step < 1 || count < 1) return refuse("needs step >= 1 and count >= 1, got step = " + std::to_string(step) + ", count = " + std::to_string(count));
-  if (first < 0 || first >= frames || count - 1 > (frames - 1 - first) / step)
-    return refuse("frames " + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(step) + ", ... (" + std::to_string(count) +
-                  " of them) fall outside the series of " + std::to_string(frames) + " frames");
+  const double* x = nullptr;
+  int64_t frame_stride = 0;
+  FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x, &frame_stride));
   // the geometry: the session of d, on the same nodes and the same recorded frames
   const FsiCtx::Band* g = &ctx->band[0];
   if (!g->open) return refuse("no session of quantity 0 (d): the current configuration is x = X + d (fsi_band_begin of d first)");
@@ -1148,14 +1160,11 @@ int fsi_band_cell_rate_current(FsiCtx* ctx, int32_t quantity, int32_t series, in
     HIPCHK(s->cell_minj.alloc((size_t)s->ncell));
     HIPCHK(hipDeviceSynchronize());                                // the allocations' own fills are done
   }
-  // the series as in fsi_band_cell_rate; the geometry's frames: the raw history at the selection's absolute indices, or the phase means
-  const double* x = series == FSI_RATE_RAW ? s->hist.p + (size_t)s->sel_first * s->nrow : series == FSI_RATE_SERIES ? history_frame(s, true, 0) : s->phase_mean.p;
-  const int64_t stride = series == FSI_RATE_RAW ? s->sel_stride : 1;
+  // the geometry's frames: the raw history of d at the quantity's selection, also under its filtered series, or d's phase means
   const double* geo = series == FSI_RATE_PHASE_MEAN ? g->phase_mean.p : g->hist.p + (size_t)s->sel_first * g->nrow;
   const int64_t geo_stride = series == FSI_RATE_PHASE_MEAN ? 1 : s->sel_stride;
-  launch_cell_rate_current(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x + (size_t)(first * stride) * s->nrow, step * stride * s->nrow,
-                           geo + (size_t)(first * geo_stride) * g->nrow, step * geo_stride * g->nrow, count, s->cell_out.p, s->cell_vol.p,
-                           s->cell_minj.p);
+  launch_cell_rate_current(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, geo + (size_t)(first * geo_stride) * g->nrow,
+                           step * geo_stride * g->nrow, count, s->cell_out.p, s->cell_vol.p, s->cell_minj.p);
   HIPCHK(hipGetLastError());
   const size_t bytes = (size_t)s->ncell * sizeof(double);
   HIPCHK(hipMemcpyAsync(rate_out, s->cell_out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1184,34 +1193,22 @@ int fsi_band_cell_weights(FsiCtx* ctx, int32_t quantity, const double* weights) 
 
 int fsi_band_cell_vortex(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count, double* cells_out,
                          double* sums_out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_cell_vortex")) return FSI_ERR_INVALID;
-  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_cell_vortex: " + why; return FSI_ERR_INVALID; };
-  if (quantity != 0 && quantity != 1) return refuse("quantity must be 0 (d) or 1 (v)");
-  auto* s = band_session(ctx, quantity, "fsi_band_cell_vortex");
+  const char* fn = "fsi_band_cell_vortex";
+  auto* s = cell_series_session(ctx, fn, quantity, series);
   if (!s) return FSI_ERR_INVALID;
-  if (series < FSI_RATE_RAW || series > FSI_RATE_PHASE_MEAN) return refuse("series must be FSI_RATE_RAW, FSI_RATE_SERIES or FSI_RATE_PHASE_MEAN");
-  if (s->ncell < 1) return refuse("no cell list (fsi_band_cells first)");
-  if (series == FSI_RATE_SERIES && !s->filtered) return refuse("no filtered series (fsi_band_filter or fsi_band_phase first)");
-  if (series == FSI_RATE_PHASE_MEAN && (s->phase_period < 1 || !s->filtered)) return refuse("no phase average (fsi_band_phase first)");
+  auto refuse = [&](const char* why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
   if (!cells_out && !sums_out) return refuse("cells_out and sums_out are both NULL");
   if (sums_out && !s->cell_weighted) return refuse("sums_out without weights (fsi_band_cell_weights first)");
-  const int64_t frames = series == FSI_RATE_PHASE_MEAN ? s->phase_period : band_frames(s);
-  if (step < 1 || count < 1) return refuse("needs step >= 1 and count >= 1, got step = " + std::to_string(step) + ", count = " + std::to_string(count));
-  if (first < 0 || first >= frames || count - 1 > (frames - 1 - first) / step)
-    return refuse("frames " + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(step) + ", ... (" + std::to_string(count) +
-                  " of them) fall outside the series of " + std::to_string(frames) + " frames");
+  const double* x = nullptr;
+  int64_t frame_stride = 0;
+  FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x, &frame_stride));
   HIPCHK(hipSetDevice(ctx->device));
   const size_t n = (size_t)s->ncell, nblock = (size_t)cell_wsum_blocks(s->ncell);
-  FSICHK(cell_buffer(ctx, "fsi_band_cell_vortex", "the five results", &s->vortex_out, FSI_VORTEX_FIELDS * n, std::to_string(s->ncell) + " cells x 40"));
+  FSICHK(cell_buffer(ctx, fn, "the five results", &s->vortex_out, FSI_VORTEX_FIELDS * n, std::to_string(s->ncell) + " cells x 40"));
   if (sums_out)
-    FSICHK(cell_buffer(ctx, "fsi_band_cell_vortex", "the partial sums", &s->vortex_part, FSI_VORTEX_FIELDS * (nblock + 1),
+    FSICHK(cell_buffer(ctx, fn, "the partial sums", &s->vortex_part, FSI_VORTEX_FIELDS * (nblock + 1),
                        std::to_string(nblock) + " groups of 256 cells and the sums x 40"));
-  // the series as in fsi_band_cell_rate
-  const double* x = series == FSI_RATE_RAW ? s->hist.p + (size_t)s->sel_first * s->nrow : series == FSI_RATE_SERIES ? history_frame(s, true, 0) : s->phase_mean.p;
-  const int64_t stride = series == FSI_RATE_RAW ? s->sel_stride : 1;
-  launch_cell_vortex(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x + (size_t)(first * stride) * s->nrow, step * stride * s->nrow, count,
-                     s->vortex_out.p);
+  launch_cell_vortex(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, count, s->vortex_out.p);
   HIPCHK(hipGetLastError());
   if (cells_out) HIPCHK(hipMemcpyAsync(cells_out, s->vortex_out.p, FSI_VORTEX_FIELDS * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (sums_out) {

@@ -6,8 +6,8 @@
 //
 //   k_cell_vortex : one lane per listed cell, the geometry of k_cell_rate.  The lane keeps the cell's ten node indices and its
 //                 twelve gradient values in registers and walks `count` frames of one series.  Per frame it gathers the ten
-//                 nodes' triples w (240 B) and forms G_t = grad w at the four vertices t by the expression of
-//                 vertex_gradients_of (fsi_rate.hip), one vertex after the other.  The gradient of a P2 field is linear on the
+//                 nodes' triples w (240 B) and forms G_t = grad w at the four vertices t by vertex_gradient_of (fsi_cell.hpp,
+//                 with the lane state and the gather), one vertex after the other.  The gradient of a P2 field is linear on the
 //                 cell, so the cell mean of a product of two linear f, h is 0.05 (sum_t f_t h_t + (sum_t f_t)(sum_t h_t)), and
 //                 with omega_t = (G_t[2][1] - G_t[1][2], G_t[0][2] - G_t[2][0], G_t[1][0] - G_t[0][1]), T = sum_t G_t:
 //                   field 0  Q            -0.5 * (0.05 * (sum_t sum_ij G_t[i][j] G_t[j][i] + sum_ij T[i][j] T[j][i]))
@@ -29,6 +29,7 @@
 // FP64 vector loads and stores only.  Floating-point contraction is off: the NumPy twins (hi_pass.cell_vortex, hi_pass.cell_wsum)
 // round every product and every sum, and the device equals them bit for bit.
 #include "fsi_vortex.hpp"
+#include "fsi_cell.hpp"
 
 #pragma clang fp contract(off)
 
@@ -39,8 +40,6 @@ namespace {
 // 60 M[a][t]: the mean over the cell of P2 basis function a times barycentric coordinate t.  Vertex a: 0 at t == a, else -1;
 // edge {p, r}: 4 at t in {p, r}, else 2.  420 MM[a][b]: the P2 mass matrix over |K|.  Vertex-vertex 6 / 1; vertex-edge -4 if
 // the vertex is an end of the edge, else -6; edge-edge 32 / 16 sharing a vertex / 8 opposite.  (hi_pass.VORTEX_M, VORTEX_MM)
-__device__ constexpr int kEdge[6][2] = {{2, 3}, {1, 3}, {1, 2}, {0, 3}, {0, 2}, {0, 1}};
-
 __device__ constexpr int m60(int a, int t) {
   return a < 4 ? (a == t ? 0 : -1) : ((kEdge[a - 4][0] == t || kEdge[a - 4][1] == t) ? 4 : 2);
 }
@@ -54,24 +53,6 @@ __device__ constexpr int mm420(int a, int b) {
   return (p == s || p == u || r == s || r == u) ? 16 : 8;
 }
 
-// G = grad w at vertex t: the expression of vertex_gradients_of (fsi_rate.hip) for one vertex, in its order
-__device__ __forceinline__ void vertex_gradient_of(const double (&w)[10][3], const double (&gl)[4][3], int t, double (&G)[3][3]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      double s = 0.0;
-#pragma unroll
-      for (int a = 0; a < 4; ++a) s = s + w[a][i] * ((a == t ? 3.0 : -1.0) * gl[a][j]);
-#pragma unroll
-      for (int e = 0; e < 6; ++e) {
-        const int p = kEdge[e][0], r = kEdge[e][1];
-        s = s + (w[4 + e][i] * 4.0) * ((p == t ? 1.0 : 0.0) * gl[r][j] + (r == t ? 1.0 : 0.0) * gl[p][j]);
-      }
-      G[i][j] = s;
-    }
-}
-
 // The five values of one frame of one cell.  Every operation in the order of hi_pass.cell_vortex.
 __device__ __forceinline__ void cell_vortex_of(const double (&w)[10][3], double (&gl)[4][3], double (&r)[FSI_VORTEX_FIELDS]) {
   double qd = 0.0, ed = 0.0, h = 0.0, T[3][3];
@@ -81,12 +62,7 @@ __device__ __forceinline__ void cell_vortex_of(const double (&w)[10][3], double 
     for (int j = 0; j < 3; ++j) T[i][j] = 0.0;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    // gl opaque per vertex, for the reason given in cell_rate_of (fsi_rate.hip): its products with the basis coefficients are
-    // formed again per vertex and frame and not kept across the frame loop
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) asm volatile("" : "+v"(gl[a][j]));
+    fence_cell_gradients(gl);
     double G[3][3];
     vertex_gradient_of(w, gl, t, G);
 #pragma unroll
@@ -140,25 +116,15 @@ __global__ __launch_bounds__(256) void k_cell_vortex(int64_t n, const int32_t* _
                                                      double* __restrict__ out) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n) return;
-  int64_t row[10];
-#pragma unroll
-  for (int a = 0; a < 10; ++a) row[a] = 3 * (int64_t)conn[c * 10 + a];
-  double gl[4][3];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) gl[a][j] = gl_all[c * 12 + a * 3 + j];
+  CellLane lane;
+  load_cell_lane(conn, gl_all, c, lane);
   double s[FSI_VORTEX_FIELDS];
 #pragma unroll
   for (int f = 0; f < FSI_VORTEX_FIELDS; ++f) s[f] = 0.0;
   for (int64_t k = 0; k < count; ++k) {
-    const double* fr = x + k * frame_stride;
     double w[10][3], r[FSI_VORTEX_FIELDS];
-#pragma unroll
-    for (int a = 0; a < 10; ++a)
-#pragma unroll
-      for (int i = 0; i < 3; ++i) w[a][i] = fr[row[a] + i];
-    cell_vortex_of(w, gl, r);
+    gather_cell_frame(x + k * frame_stride, lane, w);
+    cell_vortex_of(w, lane.gl, r);
 #pragma unroll
     for (int f = 0; f < FSI_VORTEX_FIELDS; ++f) s[f] = s[f] + r[f];
   }

@@ -1,5 +1,6 @@
 // Q-criterion, enstrophy, helicity and kinetic energy of a recorded vector history on mesh cells, and their ordered weighted
-// sums (fsi_vortex.hip): the launchers the C-ABI (fsi_band_cell_vortex in fsi_sessions.hip) calls.
+// sums (fsi_vortex.hip): the launchers the C-ABI (fsi_band_cell_vortex in fsi_sessions.hip) calls.  The lane state, the gather
+// and the vertex gradient of k_cell_vortex are those of fsi_cell.hpp, shared with the kernels of fsi_rate.hip.
 //
 // Compiler's resource report of k_cell_vortex for gfx950 (-Rpass-analysis=kernel-resource-usage): 256 VGPRs, 32 AGPRs, 46 SGPRs,
 // no scratch, no LDS; one wave per SIMD - the thirty nodal values stay live to the end of a frame for the helicity and the

@@ -378,10 +378,9 @@ RATE_SERIES = ("raw", "series", "phase_mean")      # HipBackend.RATE_SERIES, FSI
 def cell_rate(w: np.ndarray, grad: np.ndarray) -> np.ndarray:
     """The exact mean over a tetrahedron of ``2 S:S``, ``S = sym(grad w)``, of P2 fields w, (cells, 10, 3) in the local node
     order (``mesh.TET_EDGES``), with ``grad`` (cells, 4, 3) the gradients of the barycentric coordinates: the arithmetic of
-    k_cell_rate (csrc/fsi_rate.hip) in its order, one IEEE operation per NumPy operation.  ``G_t = grad w`` at vertex t by the
-    expression of wss_dg1_cell (csrc/fsi_wss.hpp), ``S_t = 0.5 (G_t + G_t^T)`` and
+    k_cell_rate (csrc/fsi_rate.hip) in its order, one IEEE operation per NumPy operation.  ``G_t = grad w`` at vertex t
+    (``vertex_gradients``), ``S_t = 0.5 (G_t + G_t^T)`` and
     ``0.1 * (sum_t S_t:S_t + (sum_t S_t):(sum_t S_t))``, since ``int L_a L_b = |K| (1 + delta_ab) / 20``."""
-    from .mesh import TET_EDGES
     w, g = np.asarray(w, dtype=np.float64), np.asarray(grad, dtype=np.float64)
     if w.ndim != 3 or w.shape[1:] != (10, 3) or g.shape != (len(w), 4, 3):
         raise RuntimeError(f"cell_rate: w of shape {w.shape} and grad of shape {g.shape}, expected (n, 10, 3) and (n, 4, 3)")
@@ -389,17 +388,7 @@ def cell_rate(w: np.ndarray, grad: np.ndarray) -> np.ndarray:
     with np.errstate(invalid="ignore", over="ignore"):
         q = np.zeros(n)
         T = [[np.zeros(n) for _ in range(3)] for _ in range(3)]
-        for t in range(4):
-            G = [[None] * 3 for _ in range(3)]
-            for i in range(3):
-                for j in range(3):
-                    s = np.zeros(n)
-                    for a in range(4):
-                        s = s + w[:, a, i] * ((3.0 if a == t else -1.0) * g[:, a, j])
-                    for e in range(6):
-                        p, r = int(TET_EDGES[e][0]), int(TET_EDGES[e][1])
-                        s = s + (w[:, 4 + e, i] * 4.0) * ((1.0 if p == t else 0.0) * g[:, r, j] + (1.0 if r == t else 0.0) * g[:, p, j])
-                    G[i][j] = s
+        for G in vertex_gradients(w, g):
             for i in range(3):
                 for j in range(3):
                     S = 0.5 * (G[i][j] + G[j][i])
@@ -416,8 +405,11 @@ RULE_A, RULE_B = 0.5854101966249685, 0.1381966011250105      # the degree-2 inte
 
 
 def vertex_gradients(w: np.ndarray, g: np.ndarray) -> list:
-    """``G[t][i][j]``, (cells,) each: the gradient of P2 fields w (cells, 10, 3) at vertex t, by the expression of ``cell_rate``
-    in its order (vertex_gradients_of, csrc/fsi_rate.hip)."""
+    """``G[t][i][j]``, (cells,) each: the gradient of P2 fields w (cells, 10, 3) at vertex t, ``g`` (cells, 4, 3) the gradients
+    of the barycentric coordinates - it is linear on the cell, so the four vertices determine it.  The arithmetic of
+    vertex_gradient_of (csrc/fsi_cell.hpp) in its order: the one expression ``cell_rate``, ``cell_rate_current`` and
+    ``cell_vortex`` share, as their kernels do.  (wss_dg1_cell, csrc/fsi_wss.hpp, has the same expression compiled with
+    contraction; it is no twin of this.)"""
     from .mesh import TET_EDGES
     n = len(w)
     G = [[[None] * 3 for _ in range(3)] for _ in range(4)]
@@ -774,29 +766,38 @@ class HostBandSession(HostHistory):
         self.cell_conn, self.cell_grad, self.cell_weight = conn.astype(np.int64), grad.copy(), None
         return self.cell_grad
 
-    def cell_rate(self, series: str, first: int = 0, step: int = 1, count: int = -1) -> np.ndarray:
-        """Per attached cell ``(((+0.0 + r[first]) + r[first + step]) + ...) / count`` with ``r[k] = cell_rate`` of frame k of
-        'raw' (the selected frames), 'series' (the filtered series or the fluctuation) or 'phase_mean'; ``count`` -1: as many
-        frames as the series has.  The twin of fsi_band_cell_rate."""
+    def _cell_frames(self, what: str, series: str, first: int, step: int, count: int, own: Optional[str] = None):
+        """``(x, first, step, count)`` for ``cell_rate``, ``cell_vortex`` and ``cell_rate_current``: the frames x of 'raw' (the
+        selected frames), 'series' or 'phase_mean', and ``count`` with -1 made as many frames as x has from ``first`` in steps
+        of ``step`` - or the refusal of the C-ABI's entry point, prefixed ``what``, in its order: ``own``, the caller's own
+        refusal if it has one, comes after those of the series and before those of the frames."""
         if series not in RATE_SERIES:
-            raise RuntimeError(f"hi-pass cell_rate: series must be one of {', '.join(RATE_SERIES)}")
+            raise RuntimeError(f"{what}: series must be one of {', '.join(RATE_SERIES)}")
         if self.cell_conn is None:
-            raise RuntimeError("hi-pass cell_rate: no cell list (cells first)")
+            raise RuntimeError(f"{what}: no cell list (cells first)")
         if series == "series" and self.filtered is None:
-            raise RuntimeError("hi-pass cell_rate: no filtered series (filter or phase first)")
+            raise RuntimeError(f"{what}: no filtered series (filter or phase first)")
         if series == "phase_mean" and self.phase_mean is None:
-            raise RuntimeError("hi-pass cell_rate: no phase average (phase first)")
+            raise RuntimeError(f"{what}: no phase average (phase first)")
+        if own is not None:
+            raise RuntimeError(own)
         x = self.selected() if series == "raw" else self.filtered if series == "series" else self.phase_mean
         first, step, count = int(first), int(step), int(count)
         if count == -1 and step >= 1:
             count = (len(x) - 1 - first) // step + 1
         if step < 1 or count < 1:
-            raise RuntimeError(f"hi-pass cell_rate: needs step >= 1 and count >= 1, got step = {step}, count = {count}")
+            raise RuntimeError(f"{what}: needs step >= 1 and count >= 1, got step = {step}, count = {count}")
         if not 0 <= first < len(x) or first + (count - 1) * step >= len(x):
-            raise RuntimeError(f"hi-pass cell_rate: frames {first}, {first} + {step}, ... ({count} of them) fall outside the series of "
-                               f"{len(x)} frames")
+            raise RuntimeError(f"{what}: frames {first}, {first} + {step}, ... ({count} of them) fall outside the series of {len(x)} frames")
         if self.cell_conn.max() >= x.shape[1]:
-            raise RuntimeError(f"hi-pass cell_rate: the cell list names node {self.cell_conn.max()}, the session has {x.shape[1]}")
+            raise RuntimeError(f"{what}: the cell list names node {self.cell_conn.max()}, the session has {x.shape[1]}")
+        return x, first, step, count
+
+    def cell_rate(self, series: str, first: int = 0, step: int = 1, count: int = -1) -> np.ndarray:
+        """Per attached cell ``(((+0.0 + r[first]) + r[first + step]) + ...) / count`` with ``r[k] = cell_rate`` of frame k of
+        'raw' (the selected frames), 'series' (the filtered series or the fluctuation) or 'phase_mean'; ``count`` -1: as many
+        frames as the series has.  The twin of fsi_band_cell_rate."""
+        x, first, step, count = self._cell_frames("hi-pass cell_rate", series, first, step, count)
         with np.errstate(invalid="ignore", over="ignore"):
             s = np.zeros(len(self.cell_conn))
             for k in range(first, first + count * step, step):
@@ -823,28 +824,9 @@ class HostBandSession(HostHistory):
         of the helicity, not of the cell mean of |w . omega|; and (5,) or None, ``cell_wsum`` of those rows with the weights of
         ``cell_weights``.  The twin of fsi_band_cell_vortex: it refuses what that refuses."""
         what = "hi-pass cell_vortex"
-        if series not in RATE_SERIES:
-            raise RuntimeError(f"{what}: series must be one of {', '.join(RATE_SERIES)}")
-        if self.cell_conn is None:
-            raise RuntimeError(f"{what}: no cell list (cells first)")
-        if series == "series" and self.filtered is None:
-            raise RuntimeError(f"{what}: no filtered series (filter or phase first)")
-        if series == "phase_mean" and self.phase_mean is None:
-            raise RuntimeError(f"{what}: no phase average (phase first)")
-        if not cells and not sums:
-            raise RuntimeError(f"{what}: neither cells nor sums asked for")
-        if sums and self.cell_weight is None:
-            raise RuntimeError(f"{what}: sums without weights (cell_weights first)")
-        x = self.selected() if series == "raw" else self.filtered if series == "series" else self.phase_mean
-        first, step, count = int(first), int(step), int(count)
-        if count == -1 and step >= 1:
-            count = (len(x) - 1 - first) // step + 1
-        if step < 1 or count < 1:
-            raise RuntimeError(f"{what}: needs step >= 1 and count >= 1, got step = {step}, count = {count}")
-        if not 0 <= first < len(x) or first + (count - 1) * step >= len(x):
-            raise RuntimeError(f"{what}: frames {first}, {first} + {step}, ... ({count} of them) fall outside the series of {len(x)} frames")
-        if self.cell_conn.max() >= x.shape[1]:
-            raise RuntimeError(f"{what}: the cell list names node {self.cell_conn.max()}, the session has {x.shape[1]}")
+        own = (f"{what}: neither cells nor sums asked for" if not cells and not sums else
+               f"{what}: sums without weights (cell_weights first)" if sums and self.cell_weight is None else None)
+        x, first, step, count = self._cell_frames(what, series, first, step, count, own)
         with np.errstate(all="ignore"):
             s = np.zeros((len(VORTEX_FIELDS), len(self.cell_conn)))
             for k in range(first, first + count * step, step):
@@ -859,24 +841,7 @@ class HostBandSession(HostHistory):
         recorded d frame of the same absolute index - ``geometry``'s own selection does not matter -, phase j of 'phase_mean'
         with ``geometry``'s phase mean j.  The twin of fsi_band_cell_rate_current: it refuses what that refuses."""
         what = "hi-pass cell_rate_current"
-        if series not in RATE_SERIES:
-            raise RuntimeError(f"{what}: series must be one of {', '.join(RATE_SERIES)}")
-        if self.cell_conn is None:
-            raise RuntimeError(f"{what}: no cell list (cells first)")
-        if series == "series" and self.filtered is None:
-            raise RuntimeError(f"{what}: no filtered series (filter or phase first)")
-        if series == "phase_mean" and self.phase_mean is None:
-            raise RuntimeError(f"{what}: no phase average (phase first)")
-        x = self.selected() if series == "raw" else self.filtered if series == "series" else self.phase_mean
-        first, step, count = int(first), int(step), int(count)
-        if count == -1 and step >= 1:
-            count = (len(x) - 1 - first) // step + 1
-        if step < 1 or count < 1:
-            raise RuntimeError(f"{what}: needs step >= 1 and count >= 1, got step = {step}, count = {count}")
-        if not 0 <= first < len(x) or first + (count - 1) * step >= len(x):
-            raise RuntimeError(f"{what}: frames {first}, {first} + {step}, ... ({count} of them) fall outside the series of {len(x)} frames")
-        if self.cell_conn.max() >= x.shape[1]:
-            raise RuntimeError(f"{what}: the cell list names node {self.cell_conn.max()}, the session has {x.shape[1]}")
+        x, first, step, count = self._cell_frames(what, series, first, step, count)
         g = geometry
         if not isinstance(g, HostBandSession) or g.ncomp != 3 or not g.raw:
             raise RuntimeError(f"{what}: no session of d: the current configuration is x = X + d")
