@@ -598,12 +598,48 @@ int fsi_band_cell_weights(FsiCtx* ctx, int32_t quantity, const double* weights);
  * bracket: p_c = weights[c] * value (one rounding); per 256 consecutive cells of the list (+0.0 past n) and inside each 64 of
  * them a balanced tree over adjacent pairs, the four sums of 64 as ((s0 + s1) + s2) + s3, and the groups of 256 from +0.0 in
  * ascending order.  FP64 without contraction, bit-equal to hi_pass.cell_vortex and hi_pass.cell_wsum; count = 1 gives the
- * frame's own bits; NaN and inf propagate, nothing is clamped.  The gradients are those of the undeformed mesh.  The result
+ * frame's own bits; NaN and inf propagate, nothing is clamped.  The gradients are those of the undeformed mesh
+ * (fsi_band_cell_vortex_current: those of the current configuration).  The result
  * and partial buffers (5 n + 5 ceil(n / 256) + 5 doubles) are allocated at the first call under the room rule of fsi_band_begin
  * and freed with the cell list.  FSI_ERR_INVALID, naming what is missing: every refusal of fsi_band_cell_rate; both outputs
  * NULL; sums_out without weights (fsi_band_cell_weights first); partitioned contexts.  A refused call changes nothing. */
 int fsi_band_cell_vortex(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count,
                          double* cells_out, double* sums_out);
+#define FSI_VORTEX_VOLUME_RATIO 5
+#define FSI_VORTEX_CURRENT_FIELDS 6
+/* Replaces: nothing in the reference.  fsi_band_cell_vortex in the current configuration x = X + d(X) of an ALE run: quantity,
+ * series, first, step and count as there, on the session of `quantity`, its cell list and its weights; the geometry is the
+ * displacement the session of quantity 0 (d) holds on the same nodes and frames, paired as fsi_band_cell_rate_current pairs it:
+ *   FSI_RATE_RAW, FSI_RATE_SERIES  the recorded (raw) d frame at the absolute index sel_first + (first + k step) sel_stride of
+ *                                  the selection of the session of `quantity` - the d session's own selection does not matter;
+ *   FSI_RATE_PHASE_MEAN            the d session's phase mean of the same phase (the same period on the same selection).
+ * With G_t and D_t the vertex gradients of the series' frame w and of d in the undeformed geometry, at the 14 points p of the
+ * positive interior rule of degree 5 (barycentrics lam_p, weights om_p, sum_p om_p = 1):
+ *   p = 0..3    1 - 3 a1 on vertex p, a1 = 0.31088591926330060980 on the other three       om = 0.11268792571801585080
+ *   p = 4..7    the same with a2 = 0.092735250310891226402, vertex p - 4                    om = 0.073493043116361949544
+ *   p = 8..13   0.5 - b on the two ends of local edge p - 8, b = 0.045503704125649649492
+ *               on the other two                                                            om = 0.042546020777081466438
+ * G_p = sum_t lam_p[t] G_t and D_p likewise (exact: the gradients are linear on the cell), F_p = I + D_p, A_p = adj F_p,
+ * J_p = det F_p, L_p = (G_p A_p) (1 / J_p), v_p = sum_a N_a(lam_p) w[a] with the P2 basis N_a = lam_a (2 lam_a - 1) at a
+ * vertex and 4 lam_r lam_s on the edge {r, s}, omega_p = (L_p[2][1] - L_p[1][2], L_p[0][2] - L_p[2][0], L_p[1][0] - L_p[0][1]),
+ * and the integrands
+ *   f_0 = -0.5 sum_ij L_ij L_ji    f_1 = |omega_p|^2    f_2 = v_p . omega_p    f_4 = |v_p|^2.
+ * Per frame Jbar = sum_p om_p J_p - for a P2 displacement the exact volume of the deformed cell over the undeformed -, the
+ * numerators n_f = sum_p (om_p J_p) f_p, n_3 = |n_2|, and the means over the deformed cell r_f = n_f / Jbar, r_3 = |r_2|.  With
+ * d = 0 the rule is exact for all of them and r_f is field f of fsi_band_cell_vortex to rounding.
+ * cells_out[6][n] (nullable): per cell the means over the frames - (((+0.0 + x[first]) + x[first + step]) + ...) / count, a
+ * true division - of r_0 .. r_4 (FSI_VORTEX_Q .. FSI_VORTEX_SPEED2) and, as FSI_VORTEX_VOLUME_RATIO, of Jbar.
+ * sums_out[6] (nullable): sums_out[f] = sum_c weights[c] * m_f[c] in the bracket of fsi_band_cell_vortex, m_f the same means
+ * over the frames of the numerators n_0 .. n_4 and of Jbar: integrals per undeformed volume, so that with the undeformed cell
+ * volumes as weights and count = 1 they are the frame's integrals over the current fluid domain and sums_out[5] is its current
+ * volume.  FP64 without contraction, bit-equal to hi_pass.cell_vortex_current and hi_pass.cell_wsum.  Nothing is clamped:
+ * J_p = 0 gives IEEE inf or NaN, a negative J_p is carried through, a NaN in a node reaches only the cells that touch it.  The
+ * result and partial buffers (12 n + 6 ceil(n / 256) + 6 doubles) are allocated at the first call under the room rule of
+ * fsi_band_begin and freed with the cell list.  FSI_ERR_INVALID, naming what is missing: every refusal of fsi_band_cell_vortex
+ * and every refusal of fsi_band_cell_rate_current about the session of d, under this function's name.  A refused call changes
+ * nothing. */
+int fsi_band_cell_vortex_current(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count,
+                                 double* cells_out, double* sums_out);
 /* Replaces: the "Saving data" loops of create_hi_pass_viz [REF .../create_hi_pass_viz.py:233-245,327-341,377-390]: one frame
  * of the raw history, the filtered series or its amplitude (out[n][ncomp]), or of the amplitude's magnitude over the
  * components (out[n]; for p the amplitude itself).  For the last two, max_out / argmax_out (nullable) receive the largest

@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_set_frame", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_phase", "fsi_band_phase_fetch", "fsi_band_spi", "fsi_band_spi_fetch", "fsi_band_cells", "fsi_band_cell_rate", "fsi_band_cell_rate_current", "fsi_band_cell_weights", "fsi_band_cell_vortex", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_begin_rows", "fsi_spec_begin_wss", "fsi_spec_room", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_spectrogram_sum", "fsi_spec_periodogram_sum", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_phase", "fsi_band_phase_fetch", "fsi_band_spi", "fsi_band_spi_fetch", "fsi_band_cells", "fsi_band_cell_rate", "fsi_band_cell_rate_current", "fsi_band_cell_weights", "fsi_band_cell_vortex", "fsi_band_cell_vortex_current", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_begin_rows", "fsi_spec_begin_wss", "fsi_spec_room", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_spectrogram_sum", "fsi_spec_periodogram_sum", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -175,6 +175,7 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_band_cell_rate_current.argtypes = [vp, i32, i32, i64, i64, i64, vp, vp, vp]
     lib.fsi_band_cell_weights.argtypes = [vp, i32, vp]
     lib.fsi_band_cell_vortex.argtypes = [vp, i32, i32, i64, i64, i64, vp, vp]
+    lib.fsi_band_cell_vortex_current.argtypes = [vp, i32, i32, i64, i64, i64, vp, vp]
     lib.fsi_band_fetch.argtypes = [vp, i32, i32, i64, vp, C.POINTER(dbl), C.POINTER(i64)]
     lib.fsi_band_select.argtypes = [vp, i32, i64, i64, i64]
     lib.fsi_band_filter_next.argtypes = [vp, i32, i32, vp, vp, vp, i32]
@@ -810,6 +811,25 @@ class HipBackend:
         total = np.empty(len(self.VORTEX_FIELDS)) if sums else None
         self._check(self.lib.fsi_band_cell_vortex(self.ctx, self.BAND_QUANTITY[quantity], self.RATE_SERIES[series], first, step, count,
                                                   _ptr(out) if cells and n else None, _ptr(total) if sums else None))
+        return out, total
+
+    VORTEX_CURRENT_FIELDS = VORTEX_FIELDS + ("volume_ratio",)      # FSI_VORTEX_VOLUME_RATIO, hi_pass.VORTEX_CURRENT_FIELDS
+
+    def hi_pass_cell_vortex_current(self, quantity: str, series: str, first: int = 0, step: int = 1, count: int = -1, cells: bool = True,
+                                    sums: bool = False):
+        """``hi_pass_cell_vortex`` in the current configuration x = X + d(X) (fsi_band_cell_vortex_current): the geometry is the
+        history of the 'd' session on the same nodes and frames, paired as ``hi_pass_cell_rate_current`` pairs it.  ``cells``
+        (6, n) or None: per attached cell the ordered mean over the frames of the means over the **deformed** cell
+        ``VORTEX_CURRENT_FIELDS`` - the five of ``hi_pass_cell_vortex`` with ``grad w F^-1`` for the gradient, and the deformed
+        cell's volume over the undeformed.  ``sums`` (6,) or None: the ordered sum over the cells of weight times the same mean
+        of each integral per undeformed volume; with the undeformed volumes as weights and one frame, the integrals over the
+        current fluid domain and its volume."""
+        first, step, count = self._cell_frames(quantity, series, first, step, count)
+        n = getattr(self, "_band_cells", {}).get(quantity, 0)
+        out = np.empty((len(self.VORTEX_CURRENT_FIELDS), n)) if cells else None
+        total = np.empty(len(self.VORTEX_CURRENT_FIELDS)) if sums else None
+        self._check(self.lib.fsi_band_cell_vortex_current(self.ctx, self.BAND_QUANTITY[quantity], self.RATE_SERIES[series], first, step, count,
+                                                          _ptr(out) if cells and n else None, _ptr(total) if sums else None))
         return out, total
 
     def hi_pass_fetch(self, quantity: str, what: str, frame: int, with_max: bool = False):

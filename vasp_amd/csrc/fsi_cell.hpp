@@ -1,5 +1,5 @@
-// One lane per listed cell of a recorded P2 vector history: what k_cell_rate, k_cell_rate_current (fsi_rate.hip) and
-// k_cell_vortex (fsi_vortex.hip) share.  Device code only, included by those two files and nothing else.
+// One lane per listed cell of a recorded P2 vector history: what k_cell_rate, k_cell_rate_current (fsi_rate.hip),
+// k_cell_vortex and k_cell_vortex_current (fsi_vortex.hip) share.  Device code only, included by those two files and nothing else.
 //
 // A lane keeps its cell's ten row indices and twelve gradient values in registers (CellLane), gathers the ten nodes' triples
 // of a frame (240 B) and forms G_t = grad w at a vertex t - the gradient of a P2 field is linear on the cell, so the four
@@ -80,6 +80,17 @@ __device__ __forceinline__ void vertex_gradient_of(const double (&w)[10][3], con
       }
       G[i][j] = s;
     }
+}
+
+// G[t] = grad w at the four vertices t, one vertex after the other (the two fences above): what the kernels of the current
+// configuration keep of a frame of the field and of the displacement
+__device__ __forceinline__ void vertex_gradients_of(const double (&w)[10][3], double (&gl)[4][3], double (&G)[4][3][3]) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    fence_cell_gradients(gl);
+    vertex_gradient_of(w, gl, t, G[t]);
+    fence_vertex_gradient(G[t]);
+  }
 }
 
 }  // namespace fsi

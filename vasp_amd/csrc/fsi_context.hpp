@@ -484,6 +484,9 @@ struct FsiCtx {
     // they stand for the list that stands), the five results [5][ncell], and [5][ceil(ncell / 256)] partials followed by [5] sums
     bool cell_weighted = false;
     fsi::DevBuf<double> cell_weight, vortex_out, vortex_part;
+    // fsi_band_cell_vortex_current, at its first calls: the six means and the six numerator means [12][ncell], and
+    // [6][ceil(ncell / 256)] partials followed by [6] sums
+    fsi::DevBuf<double> vortex_cur_out, vortex_cur_part;
     void phase_release() { phase_mean.release(); phase_period = 0; }
     void spi_release() {
       spi_acc.release(); spi_mean.release(); spi_out.release(); spi_w.release(); spi_tab.release();
@@ -491,7 +494,7 @@ struct FsiCtx {
     }
     void cells_release() {
       cell_conn.release(); cell_gl.release(); cell_out.release(); cell_vol.release(); cell_minj.release();
-      cell_weight.release(); vortex_out.release(); vortex_part.release();
+      cell_weight.release(); vortex_out.release(); vortex_part.release(); vortex_cur_out.release(); vortex_cur_part.release();
       cell_weighted = false; ncell = 0;
     }
     void release() {

@@ -95,16 +95,6 @@ __global__ __launch_bounds__(256) void k_cell_rate(int64_t n, const int32_t* __r
   out[c] = s / (double)count;
 }
 
-// G[t] = grad w at the four vertices t, one vertex after the other (the two fences: fsi_cell.hpp)
-__device__ __forceinline__ void vertex_gradients_of(const double (&w)[10][3], double (&gl)[4][3], double (&G)[4][3][3]) {
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    fence_cell_gradients(gl);
-    vertex_gradient_of(w, gl, t, G[t]);
-    fence_vertex_gradient(G[t]);
-  }
-}
-
 // the sum of the four vertex gradients, in vertex order from +0.0
 __device__ __forceinline__ void vertex_sum_of(const double (&G)[4][3][3], double (&T)[3][3]) {
 #pragma unroll

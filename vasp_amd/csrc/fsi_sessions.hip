@@ -207,8 +207,8 @@ bool partitioned(FsiCtx* ctx, const char* fn) {
   return ctx->part;
 }
 
-// The frames of a series of a cell session, for fsi_band_cell_rate, fsi_band_cell_rate_current and fsi_band_cell_vortex, in
-// two steps with the entry point's own checks between them.  First the session of `quantity` with a cell list and the series
+// The frames of a series of a cell session, for fsi_band_cell_rate, fsi_band_cell_rate_current, fsi_band_cell_vortex and
+// fsi_band_cell_vortex_current, in two steps with the entry point's own checks between them.  First the session of `quantity` with a cell list and the series
 // `series` (FSI_RATE_*) in place, or null with ctx->err set (ctx null: nothing to set it on).
 FsiCtx::Band* cell_series_session(FsiCtx* ctx, const char* fn, int32_t quantity, int32_t series) {
   if (!ctx || partitioned(ctx, fn)) return nullptr;
@@ -237,6 +237,36 @@ int cell_series_frames(FsiCtx* ctx, const char* fn, const FsiCtx::Band* s, int32
   const int64_t stride = series == FSI_RATE_RAW ? s->sel_stride : 1;
   *x = x0 + (size_t)(first * stride) * s->nrow;
   *frame_stride = step * stride * s->nrow;
+  return FSI_OK;
+}
+
+// The geometry of the current configuration x = X + d, for fsi_band_cell_rate_current and fsi_band_cell_vortex_current: the
+// session of d, which must be on the same nodes and hold the same recorded frames as the session s of the quantity, and for the
+// phase mean a phase average of the same period over the same selection - or the refusal, under the entry point's name.  *geo:
+// the d frame that goes with frame `first` of the series; *geo_stride: the doubles from one taken frame to the next.  The
+// frames are the raw history of d at the quantity's selection, also under its filtered series, or d's phase means.
+int cell_geometry_frames(FsiCtx* ctx, const char* fn, const FsiCtx::Band* s, int32_t series, int64_t first, int64_t step, const double** geo,
+                         int64_t* geo_stride) {
+  auto refuse = [&](const std::string& why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
+  const FsiCtx::Band* g = &ctx->band[0];
+  if (!g->open) return refuse("no session of quantity 0 (d): the current configuration is x = X + d (fsi_band_begin of d first)");
+  if (g->h_nodes != s->h_nodes) return refuse("the session of d lists other nodes than the session of the quantity: both must be opened on the same node list");
+  if (g->frames != s->frames)
+    return refuse("the session of d has recorded " + std::to_string(g->frames) + " frames, the session of the quantity " + std::to_string(s->frames) +
+                  ": both must hold the same frames");
+  if (series == FSI_RATE_PHASE_MEAN) {
+    if (g->phase_period < 1 || !g->filtered) return refuse("the session of d has no phase average (fsi_band_phase of d first)");
+    if (g->phase_period != s->phase_period)
+      return refuse("the phase average of d has a period of " + std::to_string(g->phase_period) + " frames, that of the quantity " +
+                    std::to_string(s->phase_period));
+    if (g->sel_first != s->sel_first || g->sel_stride != s->sel_stride || band_frames(g) != band_frames(s))
+      return refuse("the phase average of d is over another selection of frames than that of the quantity (fsi_band_select and fsi_band_phase of d "
+                    "as of the quantity)");
+  }
+  const double* g0 = series == FSI_RATE_PHASE_MEAN ? g->phase_mean.p : g->hist.p + (size_t)s->sel_first * g->nrow;
+  const int64_t stride = series == FSI_RATE_PHASE_MEAN ? 1 : s->sel_stride;
+  *geo = g0 + (size_t)(first * stride) * g->nrow;
+  *geo_stride = step * stride * g->nrow;
   return FSI_OK;
 }
 
@@ -1127,22 +1157,9 @@ int fsi_band_cell_rate_current(FsiCtx* ctx, int32_t quantity, int32_t series, in
   const double* x = nullptr;
   int64_t frame_stride = 0;
   FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x, &frame_stride));
-  // the geometry: the session of d, on the same nodes and the same recorded frames
-  const FsiCtx::Band* g = &ctx->band[0];
-  if (!g->open) return refuse("no session of quantity 0 (d): the current configuration is x = X + d (fsi_band_begin of d first)");
-  if (g->h_nodes != s->h_nodes) return refuse("the session of d lists other nodes than the session of the quantity: both must be opened on the same node list");
-  if (g->frames != s->frames)
-    return refuse("the session of d has recorded " + std::to_string(g->frames) + " frames, the session of the quantity " + std::to_string(s->frames) +
-                  ": both must hold the same frames");
-  if (series == FSI_RATE_PHASE_MEAN) {
-    if (g->phase_period < 1 || !g->filtered) return refuse("the session of d has no phase average (fsi_band_phase of d first)");
-    if (g->phase_period != s->phase_period)
-      return refuse("the phase average of d has a period of " + std::to_string(g->phase_period) + " frames, that of the quantity " +
-                    std::to_string(s->phase_period));
-    if (g->sel_first != s->sel_first || g->sel_stride != s->sel_stride || band_frames(g) != band_frames(s))
-      return refuse("the phase average of d is over another selection of frames than that of the quantity (fsi_band_select and fsi_band_phase of d "
-                    "as of the quantity)");
-  }
+  const double* geo = nullptr;
+  int64_t geo_stride = 0;
+  FSICHK(cell_geometry_frames(ctx, fn, s, series, first, step, &geo, &geo_stride));
   HIPCHK(hipSetDevice(ctx->device));
   if (s->cell_vol.n != (size_t)s->ncell || s->cell_minj.n != (size_t)s->ncell) {      // the room rule of fsi_band_begin, as fsi_band_phase applies it
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1160,11 +1177,8 @@ int fsi_band_cell_rate_current(FsiCtx* ctx, int32_t quantity, int32_t series, in
     HIPCHK(s->cell_minj.alloc((size_t)s->ncell));
     HIPCHK(hipDeviceSynchronize());                                // the allocations' own fills are done
   }
-  // the geometry's frames: the raw history of d at the quantity's selection, also under its filtered series, or d's phase means
-  const double* geo = series == FSI_RATE_PHASE_MEAN ? g->phase_mean.p : g->hist.p + (size_t)s->sel_first * g->nrow;
-  const int64_t geo_stride = series == FSI_RATE_PHASE_MEAN ? 1 : s->sel_stride;
-  launch_cell_rate_current(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, geo + (size_t)(first * geo_stride) * g->nrow,
-                           step * geo_stride * g->nrow, count, s->cell_out.p, s->cell_vol.p, s->cell_minj.p);
+  launch_cell_rate_current(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, geo, geo_stride, count, s->cell_out.p,
+                           s->cell_vol.p, s->cell_minj.p);
   HIPCHK(hipGetLastError());
   const size_t bytes = (size_t)s->ncell * sizeof(double);
   HIPCHK(hipMemcpyAsync(rate_out, s->cell_out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1213,9 +1227,40 @@ int fsi_band_cell_vortex(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t 
   if (cells_out) HIPCHK(hipMemcpyAsync(cells_out, s->vortex_out.p, FSI_VORTEX_FIELDS * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (sums_out) {
     double* sums = s->vortex_part.p + FSI_VORTEX_FIELDS * nblock;
-    launch_cell_wsum(ctx->stream, s->ncell, s->cell_weight.p, s->vortex_out.p, s->vortex_part.p, sums);
+    launch_cell_wsum(ctx->stream, s->ncell, FSI_VORTEX_FIELDS, s->cell_weight.p, s->vortex_out.p, s->vortex_part.p, sums);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(sums_out, sums, FSI_VORTEX_FIELDS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return FSI_OK;
+}
+
+int fsi_band_cell_vortex_current(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count, double* cells_out,
+                                 double* sums_out) {
+  const char* fn = "fsi_band_cell_vortex_current";
+  auto* s = cell_series_session(ctx, fn, quantity, series);
+  if (!s) return FSI_ERR_INVALID;
+  auto refuse = [&](const char* why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
+  if (!cells_out && !sums_out) return refuse("cells_out and sums_out are both NULL");
+  if (sums_out && !s->cell_weighted) return refuse("sums_out without weights (fsi_band_cell_weights first)");
+  const double *x = nullptr, *geo = nullptr;
+  int64_t frame_stride = 0, geo_stride = 0;
+  FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x, &frame_stride));
+  FSICHK(cell_geometry_frames(ctx, fn, s, series, first, step, &geo, &geo_stride));
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t n = (size_t)s->ncell, nblock = (size_t)cell_wsum_blocks(s->ncell), nf = FSI_VORTEX_CURRENT_FIELDS;
+  FSICHK(cell_buffer(ctx, fn, "the twelve results", &s->vortex_cur_out, 2 * nf * n, std::to_string(s->ncell) + " cells x 96"));
+  if (sums_out)
+    FSICHK(cell_buffer(ctx, fn, "the partial sums", &s->vortex_cur_part, nf * (nblock + 1),
+                       std::to_string(nblock) + " groups of 256 cells and the sums x 48"));
+  launch_cell_vortex_current(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, geo, geo_stride, count, s->vortex_cur_out.p);
+  HIPCHK(hipGetLastError());
+  if (cells_out) HIPCHK(hipMemcpyAsync(cells_out, s->vortex_cur_out.p, nf * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (sums_out) {      // the bulk sums are those of the numerators: rows 6 .. 11
+    double* sums = s->vortex_cur_part.p + nf * nblock;
+    launch_cell_wsum(ctx->stream, s->ncell, FSI_VORTEX_CURRENT_FIELDS, s->cell_weight.p, s->vortex_cur_out.p + nf * n, s->vortex_cur_part.p, sums);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sums_out, sums, nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return FSI_OK;

@@ -29,7 +29,8 @@ This module holds
   ``HiPassRun.write`` collects the rates;
 * the Q-criterion, enstrophy, helicity and kinetic energy of the same history on the same cells and their ordered weighted
   sums, which ``--hi-pass-vortex`` closes into the files of ``vasp_amd/vortex.py``: the NumPy twin of csrc/fsi_vortex.hip
-  (``cell_vortex``, ``cell_wsum``, ``HostBandSession.cell_weights`` / ``cell_vortex``);
+  (``cell_vortex``, ``cell_wsum``, ``HostBandSession.cell_weights`` / ``cell_vortex``; in the current configuration
+  ``cell_vortex_current`` / ``HostBandSession.cell_vortex_current``, on the 14-point rule ``vortex_rule``);
 * what the four post-processing options share to go through a checkpoint: the manifest and the files of
   ``<results>/Checkpoint/sessions/`` and the checks of a restart (``save_sessions``, ``restart_entry``), and the saving and
   restoring of a recorded history (``SessionRun``);
@@ -564,6 +565,105 @@ def cell_vortex(w: np.ndarray, grad: np.ndarray) -> np.ndarray:
         return np.stack([-0.5 * (0.05 * (qd + qp)), 0.05 * (ed + ep), h, np.abs(h), s2])
 
 
+VORTEX_CURRENT_FIELDS = VORTEX_FIELDS + ("volume_ratio",)      # HipBackend.VORTEX_CURRENT_FIELDS, FSI_VORTEX_* and FSI_VORTEX_VOLUME_RATIO
+
+# The 14-point positive interior rule of degree 5 on the tetrahedron (the constants of csrc/fsi_vortex.hip): 1 - 3 a on one
+# vertex and a on the others for a = A1 (weight W1) and a = A2 (W2), 0.5 - B on the two ends of an edge and B on the other two (W3)
+VORTEX_RULE_A1, VORTEX_RULE_W1 = 0.31088591926330060980, 0.11268792571801585080
+VORTEX_RULE_A2, VORTEX_RULE_W2 = 0.092735250310891226402, 0.073493043116361949544
+VORTEX_RULE_B, VORTEX_RULE_W3 = 0.045503704125649649492, 0.042546020777081466438
+
+
+def vortex_rule() -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(lam, om, basis)``: (14, 4) barycentrics, (14,) weights and (14, 10) values of the P2 basis at the points, local node
+    order - ``lam_a (2 lam_a - 1)`` at a vertex, ``(4 lam_r) lam_s`` on the edge {r, s} -, each entry by the operations that
+    form it in RuleTable (csrc/fsi_vortex.hip)."""
+    from .mesh import TET_EDGES
+    edges = [(int(r), int(s)) for r, s in TET_EDGES]
+    lam, om, basis = np.empty((14, 4)), np.empty(14), np.empty((14, 10))
+    for p in range(14):
+        for t in range(4):
+            if p < 4:
+                lam[p, t] = 1.0 - 3.0 * VORTEX_RULE_A1 if t == p else VORTEX_RULE_A1
+            elif p < 8:
+                lam[p, t] = 1.0 - 3.0 * VORTEX_RULE_A2 if t == p - 4 else VORTEX_RULE_A2
+            else:
+                lam[p, t] = 0.5 - VORTEX_RULE_B if t in edges[p - 8] else VORTEX_RULE_B
+        om[p] = VORTEX_RULE_W1 if p < 4 else VORTEX_RULE_W2 if p < 8 else VORTEX_RULE_W3
+        for a in range(4):
+            basis[p, a] = lam[p, a] * (2.0 * lam[p, a] - 1.0)
+        for e, (r, s) in enumerate(edges):
+            basis[p, 4 + e] = (4.0 * lam[p, r]) * lam[p, s]
+    return lam, om, basis
+
+
+VORTEX_RULE_LAM, VORTEX_RULE_OM, VORTEX_RULE_BASIS = vortex_rule()
+
+
+def cell_vortex_current(w: np.ndarray, d: np.ndarray, grad: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """``(means, numerators)`` of one frame, (6, cells) each, the rows ``VORTEX_CURRENT_FIELDS``: ``cell_vortex`` on the mesh
+    ``x = X + d(X)`` - w and d (cells, 10, 3) P2 fields in the local node order, ``grad`` (cells, 4, 3) the gradients of the
+    barycentric coordinates of the **undeformed** cells.  The arithmetic of k_cell_vortex_current (csrc/fsi_vortex.hip) in its
+    order, one IEEE operation per NumPy operation.
+
+    With ``G_t``, ``D_t`` the vertex gradients of w and d, at the 14 points p of the degree-5 rule (``vortex_rule``):
+    ``G_p = ((lam_0 G_0 + lam_1 G_1) + lam_2 G_2) + lam_3 G_3`` - exact, the gradient being linear on the cell - and ``D_p``
+    likewise; ``F_p = I + D_p``, ``A_p = adj F_p``, ``J_p = det F_p``, ``L_p = (G_p A_p) * (1 / J_p)``,
+    ``v_p = sum_a N_a(lam_p) w[a]``, ``omega_p`` the axial vector of ``L_p - L_p^T``, and
+
+        f_0 = -0.5 sum_ij L_ij L_ji      f_1 = |omega_p|^2      f_2 = v_p . omega_p      f_4 = |v_p|^2
+
+    ``Jbar = sum_p om_p J_p`` is the deformed cell's volume over the undeformed, exact for a P2 displacement; the numerators
+    ``n_f = sum_p (om_p J_p) f_p`` and ``n_3 = |n_2|`` are integrals over the deformed cell per undeformed volume, the means
+    ``r_f = n_f / Jbar`` and ``r_3 = |r_2|`` those over the deformed cell; row 5 of both is ``Jbar``.  With d = 0 every
+    integrand is of degree <= 4, the rule exact and the means are ``cell_vortex`` to rounding.  Nothing is clamped: ``J_p = 0``
+    gives inf or NaN, a negative ``J_p`` is carried through."""
+    w, d, g = np.asarray(w, dtype=np.float64), np.asarray(d, dtype=np.float64), np.asarray(grad, dtype=np.float64)
+    if w.ndim != 3 or w.shape[1:] != (10, 3) or d.shape != w.shape or g.shape != (len(w), 4, 3):
+        raise RuntimeError(f"cell_vortex_current: w of shape {w.shape}, d of shape {d.shape} and grad of shape {g.shape}, expected (n, 10, 3) "
+                           "twice and (n, 4, 3)")
+    n = len(w)
+    with np.errstate(all="ignore"):
+        D, G = vertex_gradients(d, g), vertex_gradients(w, g)
+        n0, n1, n2, n4, jb = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
+        for p in range(14):
+            l0, l1, l2, l3 = (float(x) for x in VORTEX_RULE_LAM[p])
+            gp, F = [[None] * 3 for _ in range(3)], [[None] * 3 for _ in range(3)]
+            for i in range(3):
+                for j in range(3):
+                    gp[i][j] = ((l0 * G[0][i][j] + l1 * G[1][i][j]) + l2 * G[2][i][j]) + l3 * G[3][i][j]
+                    dp = ((l0 * D[0][i][j] + l1 * D[1][i][j]) + l2 * D[2][i][j]) + l3 * D[3][i][j]
+                    F[i][j] = 1.0 + dp if i == j else dp
+            A = [[F[1][1] * F[2][2] - F[1][2] * F[2][1], F[0][2] * F[2][1] - F[0][1] * F[2][2], F[0][1] * F[1][2] - F[0][2] * F[1][1]],
+                 [F[1][2] * F[2][0] - F[1][0] * F[2][2], F[0][0] * F[2][2] - F[0][2] * F[2][0], F[0][2] * F[1][0] - F[0][0] * F[1][2]],
+                 [F[1][0] * F[2][1] - F[1][1] * F[2][0], F[0][1] * F[2][0] - F[0][0] * F[2][1], F[0][0] * F[1][1] - F[0][1] * F[1][0]]]
+            J = (F[0][0] * A[0][0] + F[0][1] * A[1][0]) + F[0][2] * A[2][0]
+            rJ = 1.0 / J
+            L = [[((gp[i][0] * A[0][j] + gp[i][1] * A[1][j]) + gp[i][2] * A[2][j]) * rJ for j in range(3)] for i in range(3)]
+            q = np.zeros(n)
+            for i in range(3):
+                for j in range(3):
+                    q = q + L[i][j] * L[j][i]
+            om = [L[2][1] - L[1][2], L[0][2] - L[2][0], L[1][0] - L[0][1]]
+            e, h, s2 = np.zeros(n), np.zeros(n), np.zeros(n)
+            for i in range(3):
+                e = e + om[i] * om[i]
+            for i in range(3):
+                v = np.zeros(n)
+                for a in range(10):
+                    v = v + float(VORTEX_RULE_BASIS[p][a]) * w[:, a, i]
+                h = h + v * om[i]
+                s2 = s2 + v * v
+            wj = float(VORTEX_RULE_OM[p]) * J
+            jb = jb + wj
+            n0 = n0 + wj * (-0.5 * q)
+            n1 = n1 + wj * e
+            n2 = n2 + wj * h
+            n4 = n4 + wj * s2
+        r2 = n2 / jb
+        return np.stack([n0 / jb, n1 / jb, r2, np.abs(r2), n4 / jb, jb]), np.stack([n0, n1, n2, np.abs(n2), n4, jb])
+
+
 def cell_wsum(values: np.ndarray, weights: np.ndarray) -> np.ndarray:
     """``sum_c weights[c] * values[..., c]`` in the bracket of k_cell_wsum and k_cell_wsum_close (csrc/fsi_vortex.hip):
     ``p_c = weights[c] * values[c]``, one rounding; the cells in groups of 256 consecutive ones, +0.0 past the last; inside
@@ -767,7 +867,7 @@ class HostBandSession(HostHistory):
         return self.cell_grad
 
     def _cell_frames(self, what: str, series: str, first: int, step: int, count: int, own: Optional[str] = None):
-        """``(x, first, step, count)`` for ``cell_rate``, ``cell_vortex`` and ``cell_rate_current``: the frames x of 'raw' (the
+        """``(x, first, step, count)`` for ``cell_rate``, ``cell_vortex`` and their ``_current`` forms: the frames x of 'raw' (the
         selected frames), 'series' or 'phase_mean', and ``count`` with -1 made as many frames as x has from ``first`` in steps
         of ``step`` - or the refusal of the C-ABI's entry point, prefixed ``what``, in its order: ``own``, the caller's own
         refusal if it has one, comes after those of the series and before those of the frames."""
@@ -834,14 +934,10 @@ class HostBandSession(HostHistory):
             out = s / float(count)
         return (out if cells else None), (cell_wsum(out, self.cell_weight) if sums else None)
 
-    def cell_rate_current(self, series: str, geometry, first: int = 0, step: int = 1, count: int = -1):
-        """``cell_rate`` in the current configuration: ``(rate, volume_ratio, min_jacobian)`` per attached cell, the ordered
-        means over the frames of the first two of ``cell_rate_current`` and the smallest of the third.  ``geometry``: the
-        twin session of d, on the same nodes and recorded frames.  Frame k of 'raw' and of 'series' is paired with the
-        recorded d frame of the same absolute index - ``geometry``'s own selection does not matter -, phase j of 'phase_mean'
-        with ``geometry``'s phase mean j.  The twin of fsi_band_cell_rate_current: it refuses what that refuses."""
-        what = "hi-pass cell_rate_current"
-        x, first, step, count = self._cell_frames(what, series, first, step, count)
+    def _cell_geometry(self, what: str, series: str, geometry) -> np.ndarray:
+        """The frames of ``geometry``, the twin session of d, that go with the frames of ``series`` of this session - for
+        ``cell_rate_current`` and ``cell_vortex_current``: the recorded d frames at this session's selection for 'raw' and
+        'series', ``geometry``'s phase means for 'phase_mean' - or the refusal of the C-ABI's entry point, prefixed ``what``."""
         g = geometry
         if not isinstance(g, HostBandSession) or g.ncomp != 3 or not g.raw:
             raise RuntimeError(f"{what}: no session of d: the current configuration is x = X + d")
@@ -851,16 +947,47 @@ class HostBandSession(HostHistory):
         if len(g.raw) != len(self.raw):
             raise RuntimeError(f"{what}: the session of d has recorded {len(g.raw)} frames, the session of the quantity {len(self.raw)}: both "
                                "must hold the same frames")
-        if series == "phase_mean":
-            if g.phase_mean is None:
-                raise RuntimeError(f"{what}: the session of d has no phase average (phase of d first)")
-            if g.phase_period != self.phase_period:
-                raise RuntimeError(f"{what}: the phase average of d has a period of {g.phase_period} frames, that of the quantity {self.phase_period}")
-            if g.view.indices(len(g.raw)) != self.view.indices(len(self.raw)):
-                raise RuntimeError(f"{what}: the phase average of d is over another selection of frames than that of the quantity")
-            geo = g.phase_mean
-        else:
-            geo = np.stack(g.raw)[self.view]
+        if series != "phase_mean":
+            return np.stack(g.raw)[self.view]
+        if g.phase_mean is None:
+            raise RuntimeError(f"{what}: the session of d has no phase average (phase of d first)")
+        if g.phase_period != self.phase_period:
+            raise RuntimeError(f"{what}: the phase average of d has a period of {g.phase_period} frames, that of the quantity {self.phase_period}")
+        if g.view.indices(len(g.raw)) != self.view.indices(len(self.raw)):
+            raise RuntimeError(f"{what}: the phase average of d is over another selection of frames than that of the quantity")
+        return g.phase_mean
+
+    def cell_vortex_current(self, series: str, geometry, first: int = 0, step: int = 1, count: int = -1, cells: bool = True,
+                            sums: bool = False):
+        """``cell_vortex`` in the current configuration: ``(cells, sums)``, (6, n) or None - per attached cell and row of
+        ``VORTEX_CURRENT_FIELDS`` the ordered mean over the frames of the means of ``cell_vortex_current`` - and (6,) or None,
+        ``cell_wsum`` with the weights of ``cell_weights`` of the same ordered means of its **numerators**: with the undeformed
+        volumes as weights and one frame, the integrals over the current fluid domain and, last, its volume.  ``geometry`` and
+        the pairing of the frames as ``cell_rate_current`` has them.  The twin of fsi_band_cell_vortex_current: it refuses what
+        that refuses."""
+        what = "hi-pass cell_vortex_current"
+        own = (f"{what}: neither cells nor sums asked for" if not cells and not sums else
+               f"{what}: sums without weights (cell_weights first)" if sums and self.cell_weight is None else None)
+        x, first, step, count = self._cell_frames(what, series, first, step, count, own)
+        geo = self._cell_geometry(what, series, geometry)
+        with np.errstate(all="ignore"):
+            shape = (len(VORTEX_CURRENT_FIELDS), len(self.cell_conn))
+            sr, sn = np.zeros(shape), np.zeros(shape)
+            for k in range(first, first + count * step, step):
+                r, num = cell_vortex_current(x[k][self.cell_conn], geo[k][self.cell_conn], self.cell_grad)
+                sr, sn = sr + r, sn + num
+            out, num = sr / float(count), sn / float(count)
+        return (out if cells else None), (cell_wsum(num, self.cell_weight) if sums else None)
+
+    def cell_rate_current(self, series: str, geometry, first: int = 0, step: int = 1, count: int = -1):
+        """``cell_rate`` in the current configuration: ``(rate, volume_ratio, min_jacobian)`` per attached cell, the ordered
+        means over the frames of the first two of ``cell_rate_current`` and the smallest of the third.  ``geometry``: the
+        twin session of d, on the same nodes and recorded frames.  Frame k of 'raw' and of 'series' is paired with the
+        recorded d frame of the same absolute index - ``geometry``'s own selection does not matter -, phase j of 'phase_mean'
+        with ``geometry``'s phase mean j.  The twin of fsi_band_cell_rate_current: it refuses what that refuses."""
+        what = "hi-pass cell_rate_current"
+        x, first, step, count = self._cell_frames(what, series, first, step, count)
+        geo = self._cell_geometry(what, series, geometry)
         with np.errstate(invalid="ignore", over="ignore"):
             n = len(self.cell_conn)
             s, sv, m = np.zeros(n), np.zeros(n), np.full(n, np.inf)
@@ -924,6 +1051,10 @@ class DeviceSession:
     def cell_rate_current(self, series: str, geometry, *args):
         """The host session's signature: on the device the geometry is the session of d the context holds."""
         return self.backend.hi_pass_cell_rate_current(self.q, series, *args)
+
+    def cell_vortex_current(self, series: str, geometry, *args, **kwargs):
+        """The host session's signature: on the device the geometry is the session of d the context holds."""
+        return self.backend.hi_pass_cell_vortex_current(self.q, series, *args, **kwargs)
 
     def cell_weights(self, weights) -> None:
         self.backend.hi_pass_cell_weights(self.q, weights)
@@ -1626,7 +1757,7 @@ class HiPassRun(SessionRun):
                 raise SystemExit(why)
             self.metrics = flow_metrics.FlowMetrics(mesh, ns)
         self.vortex = None
-        if ns.get("hi_pass_vortex") or ns.get("hi_pass_vortex_series"):
+        if ns.get("hi_pass_vortex") or ns.get("hi_pass_vortex_series") or ns.get("hi_pass_vortex_configuration"):
             from . import vortex
             why = vortex.refusal(ns, self.quantities)
             if why:
@@ -1751,7 +1882,7 @@ class HiPassRun(SessionRun):
                 self.metrics.phase = dict(fluctuation=rate(session, geometry, "series"), mean=rate(session, geometry, "phase_mean"),
                                           cycle_mean=np.stack([rate(session, geometry, "series", j, P, m // P) for j in range(P)]))
             if self.vortex is not None:
-                self.vortex.collect_phase(session, P)
+                self.vortex.collect_phase(session, P, self.sessions.get("d"))
         out(f"Hi-pass {name}: phase average over cycles {c0} to {c1} of {P} frames written")
 
     def _write_spi(self, out, session, q: str, n: int) -> None:
@@ -1794,7 +1925,7 @@ class HiPassRun(SessionRun):
             out(f"Hi-pass: none of the {self.frames} recorded frames lies in the window and stride asked for: nothing written")
             return
         order = list(self.sessions)
-        if self.metrics is not None and self.metrics.configuration == "current":
+        if any(m is not None and m.configuration == "current" for m in (self.metrics, self.vortex)):
             # d first: by the time the velocity's phase mean is paired with the displacement's, d holds its phase average
             order.sort(key=lambda q: q != "d")
         for q in order:
@@ -1810,7 +1941,7 @@ class HiPassRun(SessionRun):
             vortex = self.vortex if q == "v" else None
             if vortex is not None:             # the same cells, with their volumes as weights; the per-frame files are written here
                 vortex.attach(session, self.device, attached=metrics is not None)
-                vortex.collect(session, n, self.dt_files, self.t0)
+                vortex.collect(session, n, self.dt_files, self.t0, self.sessions.get("d"))
             for viz, stages, rms in self.series_list(q, n, out):
                 self.apply(session, stages)
                 self._write_filtered(out, session, viz, n, ncomp, rms)

@@ -113,6 +113,11 @@ def add_session_arguments(ap) -> None:
     ap.add_argument("--hi-pass-vortex-series", dest="hi_pass_vortex_series", action="store_const", const=True, default=None,
                     help="with --hi-pass-vortex: also the Q-criterion, the vorticity, the helicity and the localised normalised "
                          "helicity (LNH) of every selected frame")
+    ap.add_argument("--hi-pass-vortex-configuration", dest="hi_pass_vortex_configuration", choices=("reference", "current"), default=None,
+                    help="the configuration --hi-pass-vortex takes the velocity gradient in: reference, the undeformed mesh (default), "
+                         "or current, the ALE mesh x = X + d(X) - the gradient is grad v F^-1, F = I + grad d, every field a mean over "
+                         "the deformed cell, the integrals of vortex.csv over the current fluid domain, and the volume ratio of every "
+                         "fluid cell is written too; needs d among the --hi-pass quantities")
     ap.add_argument("--hi-pass-tensor", dest="hi_pass_tensor", nargs="+", default=None, metavar="Q",
                     help="record the Green-Lagrange strain and / or the Cauchy stress (strain, stress) of the solid cells at every "
                          "saved frame on the device and write the band-pass filtered tensors of --hi-pass-bands, with "
