@@ -79,7 +79,7 @@ _SIGS = {
     "shim_cell_stats": "lllppppp", "shim_probe": "lllppppp",
     "shim_gcr_store_op": "ilppppp", "shim_gcr_sizes": "lip", "shim_gcr_cycle_algebra": "lipppppppip",
     "shim_gcr_cycle_end": "iidddi", "shim_gcr_orth_lost": "piddd", "shim_gcr_verdict_due": "dddiiiiiii",
-    "shim_gcr_verdict_skippable": "dddiiiiiiidd", "shim_gcr_tolerances": "pp",
+    "shim_gcr_verdict_skippable": "dddiiiiiiidd", "shim_gcr_tolerances": "pp", "shim_room_refusal": "ssdsldpl",
     "shim_wss": "lllpppppdp", "shim_hemo_sample": "lllpppppp" + "ldd" + "p" * 7, "shim_hemo_finish": "ldpppp",
     "shim_spec_wss_sample": "lll" + "p" * 7 + "ldp", "shim_stress_strain": "lll" + "p" * 12, "shim_stress_sample": "lll" + "p" * 13,
     "shim_stress_average": "ldpp", "shim_tensor_sample": "llli" + "p" * 12, "shim_tensor_principal": "lpp",

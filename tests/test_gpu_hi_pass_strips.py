@@ -180,6 +180,22 @@ def test_board_table_is_np_sort_max_and_argmax_over_the_strips(cyl):
         hb.hi_pass_board_table(0, 1, [0])
 
 
+def test_a_board_that_does_not_fit_is_refused_before_anything_is_allocated(cyl):
+    """2^31 nodes x 2^20 frames: the room rule's text, from the host; the board that stood is still open."""
+    from vasp_amd.capi import FsiError
+    hb, _ = cyl
+    hb.hi_pass_board_begin(4, 2)
+    try:
+        with pytest.raises(FsiError) as e:
+            hb.hi_pass_board_begin(1 << 31, 1 << 20)
+        assert re.search(r"fsi_board_begin: the board needs \d+ bytes \(2147483648 nodes x 1048576 frames\), the device has \d+ bytes free of "
+                         r"which \d+ stay with the context$", str(e.value))
+        values, nans, mx, am = hb.hi_pass_board_table(0, 2, [0, 3])
+        assert not values.any() and not nans.any() and not mx.any() and am.tolist() == [0, 0]
+    finally:
+        hb.hi_pass_board_end()
+
+
 # ---- 3. fsi_band_room and the begin call -------------------------------------------------------------------------------
 
 def test_band_room_agrees_with_the_begin_call(cyl):

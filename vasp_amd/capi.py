@@ -283,6 +283,9 @@ class HipBackend:
         import os
         self.lib = load_library()
         self.ctx = C.c_void_p()
+        # the sizes of the open sessions, for the arrays handed to the library: a begin replaces a record whole, an end removes it
+        self._hemo_nf = self._stress_n = 0      # facets / cells of the hemodynamics and the stress / strain session; 0: none
+        self._band = {}              # hi_pass_begin(_cells): quantity -> its NO_BAND with the session's numbers
         self._spec_shape = {}        # spec_begin: quantity -> [rows, recorded frames]
         self.lin_rtol, self.lin_max_it, self.lin_solver = lin_rtol, lin_max_it, lin_solver
         coords = np.ascontiguousarray(desc["coords"], dtype=np.float64)
@@ -533,13 +536,13 @@ class HipBackend:
     def hemodynamics_sample(self, wss: bool = False):
         """Add the WSS of dvp_["n"] to the session's sums (fsi_hemo_sample); with ``wss`` return it, (nf, 3, 3) as
         ``wall_shear_stress``, else None."""
-        out = np.empty((getattr(self, "_hemo_nf", 0), 3, 3)) if wss else None
+        out = np.empty((self._hemo_nf, 3, 3)) if wss else None
         self._check(self.lib.fsi_hemo_sample(self.ctx, _ptr(out) if wss else None))
         return out
 
     def hemodynamics_indices(self) -> dict:
         """TAWSS, OSI, RRT, ECAP, TWSSG as (nf, 3) arrays (DG1 dofs of the boundary mesh) and ``samples``."""
-        out = np.empty((5, getattr(self, "_hemo_nf", 0), 3))
+        out = np.empty((5, self._hemo_nf, 3))
         n = C.c_int64(0)
         self._check(self.lib.fsi_hemo_indices(self.ctx, _ptr(out), C.byref(n)))
         res = {k: out[i].copy() for i, k in enumerate(self.HEMO_INDICES)}
@@ -556,7 +559,7 @@ class HipBackend:
 
     def hemodynamics_export(self):
         """(acc, samples): the session's accumulator, (24 nf,) in the layout of fsi_hemo_export, and its sample count."""
-        out = np.empty(24 * getattr(self, "_hemo_nf", 0))
+        out = np.empty(24 * self._hemo_nf)
         n = C.c_int64(0)
         self._check(self.lib.fsi_hemo_export(self.ctx, _ptr(out), C.byref(n)))
         return out, int(n.value)
@@ -564,11 +567,12 @@ class HipBackend:
     def hemodynamics_import(self, acc, samples: int) -> None:
         """Replace the open session's accumulator and sample count by exported ones (fsi_hemo_import); an accumulator of
         another number of facets is refused."""
-        a = self._sums("hemodynamics_import", acc, 24 * getattr(self, "_hemo_nf", 0))
+        a = self._sums("hemodynamics_import", acc, 24 * self._hemo_nf)
         self._check(self.lib.fsi_hemo_import(self.ctx, _ptr(a), int(samples)))
 
     def hemodynamics_end(self) -> None:
         self._check(self.lib.fsi_hemo_end(self.ctx))
+        self._hemo_nf = 0
 
     @staticmethod
     def _stress_frame(out: np.ndarray) -> dict:
@@ -585,20 +589,20 @@ class HipBackend:
     def stress_strain_sample(self, frame: bool = False):
         """Sample dvp_["n"] (fsi_stress_sample): the principal values go to the session's sums; with ``frame`` return the
         frame, keyed as ``stress_strain`` (bitwise equal to it), else None."""
-        out = np.empty((getattr(self, "_stress_n", 0), 80)) if frame else None
+        out = np.empty((self._stress_n, 80)) if frame else None
         self._check(self.lib.fsi_stress_sample(self.ctx, _ptr(out) if frame else None))
         return self._stress_frame(out) if frame else None
 
     def stress_strain_averages(self) -> dict:
         """MaxPrincipalStress_avg and MaxPrincipalStrain_avg as (n, 4) arrays (DG1 coefficients per cell) and ``samples``."""
-        out = np.empty((2, getattr(self, "_stress_n", 0), 4))
+        out = np.empty((2, self._stress_n, 4))
         k = C.c_int64(0)
         self._check(self.lib.fsi_stress_averages(self.ctx, _ptr(out), C.byref(k)))
         return dict(MaxPrincipalStress_avg=out[0].copy(), MaxPrincipalStrain_avg=out[1].copy(), samples=int(k.value))
 
     def stress_strain_export(self):
         """(sums, samples): the session's sums, (n, 8) as fsi_stress_export, and its sample count."""
-        out = np.empty((getattr(self, "_stress_n", 0), 8))
+        out = np.empty((self._stress_n, 8))
         k = C.c_int64(0)
         self._check(self.lib.fsi_stress_export(self.ctx, _ptr(out), C.byref(k)))
         return out, int(k.value)
@@ -606,14 +610,19 @@ class HipBackend:
     def stress_strain_import(self, sums, samples: int) -> None:
         """Replace the open session's sums and sample count by exported ones (fsi_stress_import); sums of another number of
         cells are refused."""
-        a = self._sums("stress_strain_import", sums, 8 * getattr(self, "_stress_n", 0))
+        a = self._sums("stress_strain_import", sums, 8 * self._stress_n)
         self._check(self.lib.fsi_stress_import(self.ctx, _ptr(a), int(samples)))
 
     def stress_strain_end(self) -> None:
         self._check(self.lib.fsi_stress_end(self.ctx))
+        self._stress_n = 0
 
     BAND_QUANTITY = {"d": 0, "v": 1, "p": 2, "strain": 3, "stress": 4}
     BAND_WHAT = {"raw": 0, "filtered": 1, "amplitude": 2, "magnitude": 3}
+    # The record of a band-pass session: a frame is shape = (nodes, ncomp), the history has `recorded` frames of which `selected`
+    # are selected (the size of a trace), `cells` cells are attached and the phase mean has `period` frames.  As it stands here:
+    # no session - the arrays sized from it are empty and the library, which looks for the session first, refuses the call.
+    NO_BAND = dict(shape=(0, 0), recorded=0, selected=0, cells=0, period=0)
 
     def hi_pass_begin(self, quantity: str, nodes, nodes_b=None, capacity: int = 1) -> None:
         """Open the band-pass session of ``quantity`` ('d', 'v' or 'p'; fsi_band_begin) on ``nodes`` (P2 node ids, vertex
@@ -625,12 +634,7 @@ class HipBackend:
         if b is not None and b.shape != a.shape:
             raise ValueError("nodes_b must have the shape of nodes")
         self._check(self.lib.fsi_band_begin(self.ctx, q, len(a), _ptr(a), None if b is None else _ptr(b), int(capacity)))
-        if not hasattr(self, "_band_shape"):
-            self._band_shape, self._band_frames = {}, {}
-        self._band_shape[quantity] = (len(a), 1 if quantity == "p" else 3)
-        self._band_frames[quantity] = [0, 0]          # frames recorded, frames selected: the size of a trace
-        getattr(self, "_band_cells", {}).pop(quantity, None)      # a new session has no cell list and no phase average
-        getattr(self, "_band_period", {}).pop(quantity, None)
+        self._band[quantity] = dict(self.NO_BAND, shape=(len(a), 1 if quantity == "p" else 3))
 
     def hi_pass_begin_cells(self, quantity: str, cells, capacity: int = 1) -> None:
         """Open the band-pass session of the tensor ``quantity`` ('strain': Green-Lagrange strain, 'stress': Cauchy stress;
@@ -640,17 +644,14 @@ class HipBackend:
         q = self.BAND_QUANTITY[quantity]
         ci = np.ascontiguousarray(self.cell_u2i[np.asarray(cells, dtype=np.int64).reshape(-1)], dtype=np.int32)
         self._check(self.lib.fsi_band_begin_cells(self.ctx, q, len(ci), _ptr(ci), int(capacity)))
-        if not hasattr(self, "_band_shape"):
-            self._band_shape, self._band_frames = {}, {}
-        self._band_shape[quantity] = (4 * len(ci), 6)
-        self._band_frames[quantity] = [0, 0]
+        self._band[quantity] = dict(self.NO_BAND, shape=(4 * len(ci), 6))
 
     def hi_pass_sample(self, quantity: str) -> None:
         """Record the session's rows of dvp_["n"] as the next frame of its history (fsi_band_sample)."""
         self._check(self.lib.fsi_band_sample(self.ctx, self.BAND_QUANTITY[quantity]))
-        frames = self._band_frames[quantity]
-        frames[0] += 1
-        frames[1] = frames[0]                         # a new frame resets the selection to every recorded frame
+        rec = self._band[quantity]
+        rec["recorded"] += 1
+        rec["selected"] = rec["recorded"]             # a new frame resets the selection to every recorded frame
 
     def hi_pass_filter(self, quantity: str, b, a, zi, padlen: int) -> None:
         """scipy.signal.filtfilt(b, a, .) of every row over the recorded frames (fsi_band_filter); zi = lfilter_zi(b, a)."""
@@ -665,9 +666,9 @@ class HipBackend:
         number of selected frames."""
         first, count, stride = int(first), int(count), int(stride)
         self._check(self.lib.fsi_band_select(self.ctx, self.BAND_QUANTITY[quantity], first, count, stride))
-        frames = self._band_frames[quantity]
-        frames[1] = (frames[0] - 1 - first) // stride + 1 if count == -1 else count
-        return frames[1]
+        rec = self._band[quantity]
+        rec["selected"] = (rec["recorded"] - 1 - first) // stride + 1 if count == -1 else count
+        return rec["selected"]
 
     def hi_pass_filter_next(self, quantity: str, b, a, zi, padlen: int) -> None:
         """One more stage on the filtered series, y <- filtfilt(b, a, y), in place on the device (fsi_band_filter_next)."""
@@ -680,7 +681,8 @@ class HipBackend:
         """The series of the listed nodes (indices into the session's node list) over the selected frames, 'raw' or
         'filtered', as (points, frames, 1 + ncomp) with the magnitude first (fsi_band_trace): one copy from the device."""
         pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1)
-        out = np.empty((len(pts), self._band_frames[quantity][1], 1 + self._band_shape[quantity][1]))
+        rec = self._band.get(quantity, self.NO_BAND)
+        out = np.empty((len(pts), rec["selected"], 1 + rec["shape"][1]))
         self._check(self.lib.fsi_band_trace(self.ctx, self.BAND_QUANTITY[quantity], self.BAND_WHAT[what], len(pts), _ptr(pts), _ptr(out)))
         return out
 
@@ -696,15 +698,13 @@ class HipBackend:
         fluctuation about the mean over the cycles becomes the filtered series - 'filtered' and 'amplitude' fetches and a
         'filtered' trace serve it -, the means and the fluctuation's energy come from ``hi_pass_phase_fetch``."""
         self._check(self.lib.fsi_band_phase(self.ctx, self.BAND_QUANTITY[quantity], int(period)))
-        if not hasattr(self, "_band_period"):
-            self._band_period = {}
-        self._band_period[quantity] = int(period)     # the frames of the phase mean: hi_pass_cell_rate's default count
+        self._band[quantity]["period"] = int(period)
 
     def hi_pass_phase_fetch(self, quantity: str, what: str, frame: int = 0) -> np.ndarray:
         """After ``hi_pass_phase``: 'mean' of phase ``frame`` as (n, ncomp); 'energy' 0.5 |u'|^2 of fluctuation frame
         ``frame``, 'energy_cycle_mean' its mean over the cycles at phase ``frame``, 'energy_time_mean' its mean over all
         selected frames (``frame`` 0), each as (n,) (fsi_band_phase_fetch)."""
-        n, ncomp = self._band_shape[quantity]
+        n, ncomp = self._band.get(quantity, self.NO_BAND)["shape"]
         out = np.empty((n, ncomp)) if what == "mean" else np.empty(n)
         self._check(self.lib.fsi_band_phase_fetch(self.ctx, self.BAND_QUANTITY[quantity], self.PHASE_WHAT[what], int(frame), _ptr(out)))
         return out
@@ -717,7 +717,7 @@ class HipBackend:
         slab's cos / sin columns, frame-major; None: ``spectrogram.spec_tables`` of the selected count.  A slab with
         ``bin0`` > 0 adds onto the slabs before it; the index comes from ``hi_pass_spi_fetch``."""
         bin0, nb = int(bin0), int(nb)
-        n = getattr(self, "_band_frames", {}).get(quantity, [0, 0])[1]
+        n = self._band.get(quantity, self.NO_BAND)["selected"]
         if Ct is None and nb >= 1 and bin0 >= 0 and n >= 1:
             from .spectrogram import spec_tables
             C, S = spec_tables(n, n, bin0, nb)
@@ -734,7 +734,7 @@ class HipBackend:
     def hi_pass_spi_fetch(self, quantity: str, what: str = "nodes") -> np.ndarray:
         """After ``hi_pass_spi``: 'rows' the index of every row as (n, ncomp), 'nodes' the power-summed index of every node as
         (n,), 'sums' the three sums L2, X0^2, Q of every row as (3, n, ncomp) (fsi_band_spi_fetch)."""
-        n, ncomp = self._band_shape[quantity]
+        n, ncomp = self._band.get(quantity, self.NO_BAND)["shape"]
         out = np.empty(n) if what == "nodes" else np.empty((n, ncomp)) if what == "rows" else np.empty((3, n, ncomp))
         self._check(self.lib.fsi_band_spi_fetch(self.ctx, self.BAND_QUANTITY[quantity], self.SPI_WHAT[what], _ptr(out)))
         return out
@@ -748,26 +748,24 @@ class HipBackend:
         ci = np.ascontiguousarray(self.cell_u2i[np.asarray(cells, dtype=np.int64).reshape(-1)], dtype=np.int32)
         grad = np.empty((len(ci), 4, 3))
         self._check(self.lib.fsi_band_cells(self.ctx, self.BAND_QUANTITY[quantity], len(ci), _ptr(ci), _ptr(grad)))
-        if not hasattr(self, "_band_cells"):
-            self._band_cells = {}
-        self._band_cells[quantity] = len(ci)
+        self._band[quantity]["cells"] = len(ci)
         return grad
 
     def _cell_frames(self, quantity: str, series: str, first: int, step: int, count: int) -> tuple:
-        """``(first, step, count)`` as integers, ``count`` -1 made as many frames as the series has; refusing is the entry point's."""
-        first, step, count = int(first), int(step), int(count)
+        """``(first, step, count)`` as integers, ``count`` -1 made as many frames as the series has, and the number of attached
+        cells; refusing is the entry point's."""
+        first, step, count, rec = int(first), int(step), int(count), self._band.get(quantity, self.NO_BAND)
         if count == -1 and step >= 1:
-            frames = getattr(self, "_band_period", {}).get(quantity, 0) if series == "phase_mean" else self._band_frames[quantity][1]
-            count = (frames - 1 - first) // step + 1
-        return first, step, count
+            count = ((rec["period"] if series == "phase_mean" else rec["selected"]) - 1 - first) // step + 1
+        return first, step, count, rec["cells"]
 
     def hi_pass_cell_rate(self, quantity: str, series: str, first: int = 0, step: int = 1, count: int = -1) -> np.ndarray:
         """Per attached cell the mean over frames ``first, first + step, ...`` (``count`` of them, -1: as many as the series
         has) of the cell mean of 2 S:S, S = sym(grad w), summed in frame order from +0.0 and divided by the count
         (fsi_band_cell_rate).  ``series``: 'raw' the selected frames, 'series' the filtered series or the fluctuation,
         'phase_mean' the frames of the phase mean.  (n,)."""
-        first, step, count = self._cell_frames(quantity, series, first, step, count)
-        out = np.empty(getattr(self, "_band_cells", {}).get(quantity, 0))
+        first, step, count, n = self._cell_frames(quantity, series, first, step, count)
+        out = np.empty(n)
         self._check(self.lib.fsi_band_cell_rate(self.ctx, self.BAND_QUANTITY[quantity], self.RATE_SERIES[series], first, step, count,
                                                 _ptr(out) if len(out) else None))
         return out
@@ -777,8 +775,7 @@ class HipBackend:
         history of the 'd' session on the same nodes and frames.  Returns ``(rate, volume_ratio, min_jacobian)``, (n,) each:
         the mean over the frames of the mean of 2 S:S over the deformed cell, S = sym(grad w F^-1); the mean over the frames
         of the deformed cell's volume over the undeformed; the smallest det F met at the rule's four points."""
-        first, step, count = self._cell_frames(quantity, series, first, step, count)
-        n = getattr(self, "_band_cells", {}).get(quantity, 0)
+        first, step, count, n = self._cell_frames(quantity, series, first, step, count)
         rate, volume_ratio, min_jacobian = np.empty(n), np.empty(n), np.empty(n)
         self._check(self.lib.fsi_band_cell_rate_current(self.ctx, self.BAND_QUANTITY[quantity], self.RATE_SERIES[series], first, step, count,
                                                         *(_ptr(a) if n else None for a in (rate, volume_ratio, min_jacobian))))
@@ -793,7 +790,7 @@ class HipBackend:
             self._check(self.lib.fsi_band_cell_weights(self.ctx, self.BAND_QUANTITY[quantity], None))
             return
         w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-        n = getattr(self, "_band_cells", {}).get(quantity, 0)
+        n = self._band.get(quantity, self.NO_BAND)["cells"]
         if n and len(w) != n:
             raise ValueError(f"{len(w)} weights, the session has {n} cells")
         self._check(self.lib.fsi_band_cell_weights(self.ctx, self.BAND_QUANTITY[quantity], _ptr(w) if len(w) else None))
@@ -805,12 +802,15 @@ class HipBackend:
         0.5 (|Omega|^2 - |S|^2), the enstrophy |omega|^2, the helicity w . omega, its absolute value (of the cell mean of each
         frame, not the cell mean of |w . omega|) and |w|^2.  ``sums`` (5,) or None: the ordered sum over the cells of weight
         times each row (``hi_pass_cell_weights`` first; the bracket is that of ``hi_pass.cell_wsum``)."""
-        first, step, count = self._cell_frames(quantity, series, first, step, count)
-        n = getattr(self, "_band_cells", {}).get(quantity, 0)
-        out = np.empty((len(self.VORTEX_FIELDS), n)) if cells else None
-        total = np.empty(len(self.VORTEX_FIELDS)) if sums else None
-        self._check(self.lib.fsi_band_cell_vortex(self.ctx, self.BAND_QUANTITY[quantity], self.RATE_SERIES[series], first, step, count,
-                                                  _ptr(out) if cells and n else None, _ptr(total) if sums else None))
+        return self._cell_vortex(self.lib.fsi_band_cell_vortex, len(self.VORTEX_FIELDS), quantity, series, first, step, count, cells, sums)
+
+    def _cell_vortex(self, entry, fields: int, quantity: str, series: str, first: int, step: int, count: int, cells: bool, sums: bool):
+        """``hi_pass_cell_vortex`` and ``hi_pass_cell_vortex_current``: ``entry`` with outputs of ``fields`` rows."""
+        first, step, count, n = self._cell_frames(quantity, series, first, step, count)
+        out = np.empty((fields, n)) if cells else None
+        total = np.empty(fields) if sums else None
+        self._check(entry(self.ctx, self.BAND_QUANTITY[quantity], self.RATE_SERIES[series], first, step, count,
+                          _ptr(out) if cells and n else None, _ptr(total) if sums else None))
         return out, total
 
     VORTEX_CURRENT_FIELDS = VORTEX_FIELDS + ("volume_ratio",)      # FSI_VORTEX_VOLUME_RATIO, hi_pass.VORTEX_CURRENT_FIELDS
@@ -824,18 +824,13 @@ class HipBackend:
         cell's volume over the undeformed.  ``sums`` (6,) or None: the ordered sum over the cells of weight times the same mean
         of each integral per undeformed volume; with the undeformed volumes as weights and one frame, the integrals over the
         current fluid domain and its volume."""
-        first, step, count = self._cell_frames(quantity, series, first, step, count)
-        n = getattr(self, "_band_cells", {}).get(quantity, 0)
-        out = np.empty((len(self.VORTEX_CURRENT_FIELDS), n)) if cells else None
-        total = np.empty(len(self.VORTEX_CURRENT_FIELDS)) if sums else None
-        self._check(self.lib.fsi_band_cell_vortex_current(self.ctx, self.BAND_QUANTITY[quantity], self.RATE_SERIES[series], first, step, count,
-                                                          _ptr(out) if cells and n else None, _ptr(total) if sums else None))
-        return out, total
+        return self._cell_vortex(self.lib.fsi_band_cell_vortex_current, len(self.VORTEX_CURRENT_FIELDS), quantity, series, first, step, count,
+                                 cells, sums)
 
     def hi_pass_fetch(self, quantity: str, what: str, frame: int, with_max: bool = False):
         """One frame 'raw', 'filtered' or 'amplitude' as (n, ncomp), or 'magnitude' as (n,) (fsi_band_fetch); with
         ``with_max`` (amplitude, magnitude) also the frame's largest magnitude and the first node that has it."""
-        n, ncomp = self._band_shape[quantity]
+        n, ncomp = self._band.get(quantity, self.NO_BAND)["shape"]
         out = np.empty(n) if what == "magnitude" else np.empty((n, ncomp))
         mx, am = C.c_double(0.0), C.c_int64(0)
         self._check(self.lib.fsi_band_fetch(self.ctx, self.BAND_QUANTITY[quantity], self.BAND_WHAT[what], int(frame), _ptr(out),
@@ -844,24 +839,25 @@ class HipBackend:
 
     def hi_pass_export(self, quantity: str, first: int, count: int) -> np.ndarray:
         """Raw frames ``first .. first + count - 1`` of the history as (count, n, ncomp), in one copy (fsi_band_export)."""
-        n, ncomp = self._band_shape[quantity]
+        n, ncomp = self._band.get(quantity, self.NO_BAND)["shape"]
         out = np.empty((max(int(count), 0), n, ncomp))
         self._check(self.lib.fsi_band_export(self.ctx, self.BAND_QUANTITY[quantity], int(first), int(count), _ptr(out)))
         return out
 
     def hi_pass_import(self, quantity: str, frames) -> None:
         """Append exported frames, (count, n, ncomp), to the history as that many samples would have (fsi_band_import)."""
-        n, ncomp = self._band_shape[quantity]
+        n, ncomp = self._band.get(quantity, self.NO_BAND)["shape"]
         x = np.ascontiguousarray(frames, dtype=np.float64)
-        if x.ndim < 1 or x.size != len(x) * n * ncomp:
+        if x.ndim < 1 or (n and x.size != len(x) * n * ncomp):
             raise FsiError(1, f"hi_pass_import: frames of shape {x.shape}, the open session has frames of {(n, ncomp)}")
         self._check(self.lib.fsi_band_import(self.ctx, self.BAND_QUANTITY[quantity], len(x), _ptr(x)))
-        rec = self._band_frames[quantity]
-        rec[0] += len(x)
-        rec[1] = rec[0]
+        rec = self._band[quantity]
+        rec["recorded"] += len(x)
+        rec["selected"] = rec["recorded"]
 
     def hi_pass_end(self, quantity: str) -> None:
         self._check(self.lib.fsi_band_end(self.ctx, self.BAND_QUANTITY[quantity]))
+        self._band.pop(quantity, None)
 
     def hi_pass_room(self, rows: int, capacity: int):
         """(need, available) in bytes: what a band-pass session of ``rows`` rows and ``capacity`` frames takes and what the
@@ -873,7 +869,6 @@ class HipBackend:
     def hi_pass_board_begin(self, nodes: int, frames: int) -> None:
         """Open the magnitude board, (frames, nodes) FP64 on the device (fsi_board_begin); replaces an open one."""
         self._check(self.lib.fsi_board_begin(self.ctx, int(nodes), int(frames)))
-        self._board_shape = (int(frames), int(nodes))
 
     def hi_pass_board_end(self) -> None:
         self._check(self.lib.fsi_board_end(self.ctx))

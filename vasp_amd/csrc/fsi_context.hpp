@@ -487,6 +487,18 @@ struct FsiCtx {
     // fsi_band_cell_vortex_current, at its first calls: the six means and the six numerator means [12][ncell], and
     // [6][ceil(ncell / 256)] partials followed by [6] sums
     fsi::DevBuf<double> vortex_cur_out, vortex_cur_part;
+    // The ladder.  The derived state forms a chain, and replacing one link drops everything after it:
+    //   recorded frames -> selection -> series (filtered / fluctuation) -> amplitude
+    //                                \-> spectral power index (of the selected RAW frames: survives a new series)
+    //   cell list -> weights               (independent of the frames)
+    // A call that replaces a link calls that link's function, once, and resets nothing by hand: fsi_band_sample and _import
+    // frames_changed, _select selection_changed, _filter, _filter_next and _phase series_changed, _amplitude amplitude_changed,
+    // _cells cell_list_changed.  keep_mean (fsi_band_phase): the mean frames are the caller's - it reuses them where they fit.
+    void frames_changed() { sel_first = 0; sel_stride = 1; sel_count = -1; selection_changed(); }
+    void selection_changed() { filtered = false; spi_release(); series_changed(); }
+    void series_changed(bool keep_mean = false) { if (!keep_mean) phase_release(); amplitude_changed(-1); }
+    void amplitude_changed(int to) { window = to; acc_start = -1; }
+    void cell_list_changed() { cell_weighted = false; }
     void phase_release() { phase_mean.release(); phase_period = 0; }
     void spi_release() {
       spi_acc.release(); spi_mean.release(); spi_out.release(); spi_w.release(); spi_tab.release();
@@ -500,12 +512,10 @@ struct FsiCtx {
     void release() {
       History::release();
       acc.release(); amp.release(); mag.release(); part_val.release(); part_idx.release();
-      phase_release();
-      spi_release();
+      frames_changed();         // no frames: the whole chain goes
       cells_release();
       h_nodes.clear();
-      ncomp = 0; window = -1; acc_start = -1;
-      sel_first = 0; sel_stride = 1; sel_count = -1;
+      ncomp = 0;
       board_node0 = -1;
     }
   } band[5];

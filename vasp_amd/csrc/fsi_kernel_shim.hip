@@ -15,6 +15,7 @@
 #include "fsi_cheb.hpp"
 #include "fsi_host.hpp"
 #include "fsi_kernels.hpp"
+#include "fsi_room.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -531,6 +532,14 @@ int shim_gcr_sizes(int64_t cap, int m, int64_t* out) {
   const int64_t v[10] = {GCR_WINDOW, GCR_FLUSH_BATCH, gcr_ring(cap), gcr_retire_batch(cap), (int64_t)gcr_coef_len(cap),
                          lay.sums(m), lay.lagged(m), lay.updated(m), lay.window(), (int64_t)lay.size()};
   std::copy(v, v + 10, out);
+  return 0;
+}
+// the text of a room-rule refusal (fsi_room.hpp) into out[cap], zero-terminated; host only
+int shim_room_refusal(const char* fn, const char* subject, double need, const char* layout, int64_t free_b, double reserve, char* out,
+                      int64_t cap) {
+  const std::string text = host::room_refusal(fn, subject, need, layout, (size_t)free_b, reserve);
+  if ((int64_t)text.size() >= cap) { g_err = "shim_room_refusal: the text does not fit"; return 1; }
+  std::copy(text.c_str(), text.c_str() + text.size() + 1, out);
   return 0;
 }
 // GcrCycle: knew directions added in turn - slots [knew], over ms[k] columns with coefficients htot [knew][cap], wn, alpha

@@ -5,6 +5,7 @@
 #include "fsi_host.hpp"
 #include "fsi_phase.hpp"
 #include "fsi_rate.hpp"
+#include "fsi_room.hpp"
 #include "fsi_spec.hpp"
 #include "fsi_spi.hpp"
 #include "fsi_vortex.hpp"
@@ -77,57 +78,49 @@ int row_lists(FsiCtx* ctx, const char* fn, int32_t quantity, int64_t n, const in
   return FSI_OK;
 }
 
-// What the device has free, and the 1/16 of the device the context keeps for what it allocates later (a refreshed
-// preconditioner, staging buffers): a session or a transform that does not fit beside it is refused - nothing is paged or cut.
-struct Room { size_t free_b = 0; double reserve = 0.0; };
+// The room rule, once.  What the device has free, and the 1/16 of the device the context keeps for what it allocates later (a
+// refreshed preconditioner, staging buffers): a session, a transform or a further buffer of one that does not fit beside it
+// is refused - nothing is paged or cut.
+struct Room {
+  size_t free_b = 0;
+  double reserve = 0.0;
+  double available(double back = 0.0) const { return (double)free_b + back - reserve; }      // back: bytes the call gives back first
+};
 int device_room(FsiCtx* ctx, Room* r) {
   size_t total_b = 0;
   HIPCHK(hipMemGetInfo(&r->free_b, &total_b));
   r->reserve = (double)total_b / 16.0;
   return FSI_OK;
 }
-
-// a further buffer of the cell list, at its first use: the room rule of fsi_band_begin, as fsi_band_cell_rate_current applies it
-int cell_buffer(FsiCtx* ctx, const char* fn, const char* what, DevBuf<double>* buf, size_t count, const std::string& layout) {
-  if (buf->n == count) return FSI_OK;
+// `need` bytes of entry point fn, once the stream has drained: FSI_OK, or the refusal with ctx->err set (fsi_room.hpp: subject,
+// layout).  back: the bytes of buffers the call releases before it allocates; what it replaces only afterwards counts as taken.
+int room_for(FsiCtx* ctx, const char* fn, const char* subject, double need, const std::string& layout, double back = 0.0) {
   HIPCHK(hipStreamSynchronize(ctx->stream));
   Room room;
   FSICHK(device_room(ctx, &room));
-  const double need_d = 8.0 * (double)count, avail = (double)room.free_b - room.reserve;
-  if (need_d > avail) {
-    char msg[400];
-    snprintf(msg, sizeof msg, "%s: %s need %.0f bytes (%s), the device has %zu bytes free of which %.0f stay with the context", fn, what, need_d,
-             layout.c_str(), room.free_b, room.reserve);
-    ctx->err = msg;
+  if (need > room.available(back)) {
+    ctx->err = room_refusal(fn, subject, need, layout, room.free_b, room.reserve);
     return FSI_ERR_INVALID;
   }
+  return FSI_OK;
+}
+std::string counted(int64_t a, const char* of_a, int64_t b, const char* of_b) {      // "<a><of_a><b><of_b>": the layouts are mostly two counts
+  return std::to_string(a) + of_a + std::to_string(b) + of_b;
+}
+
+// a further buffer of the cell list, at its first use, under the room rule
+int cell_buffer(FsiCtx* ctx, const char* fn, const char* subject, DevBuf<double>* buf, size_t count, const std::string& layout) {
+  if (buf->n == count) return FSI_OK;
+  FSICHK(room_for(ctx, fn, subject, 8.0 * (double)count, layout));
   HIPCHK(buf->alloc(count));
   HIPCHK(hipDeviceSynchronize());                                  // the allocation's own fill is done
   return FSI_OK;
 }
 
-// The refusal rule of the band-pass begin calls, once: what a session of `rows` rows and `capacity` frames takes - the history,
-// the filtered series (capacity + 2 BAND_MAX_PADLEN frames), one frame each of running sums, amplitudes and magnitudes (a
-// frame of magnitudes counted as a frame of rows) and the row lists - and what the device has free less the context's 1/16.
-int band_room(FsiCtx* ctx, int64_t rows, int64_t capacity, double* need, double* available, Room* room) {
-  FSICHK(device_room(ctx, room));
-  *need = 8.0 * (double)rows * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN + 4.0);
-  *available = (double)room->free_b - room->reserve;
-  return FSI_OK;
-}
-int band_refused(FsiCtx* ctx, const char* fn, int64_t nrow, int64_t capacity) {
-  double need_d = 0.0, avail = 0.0;
-  Room room;
-  FSICHK(band_room(ctx, nrow, capacity, &need_d, &avail, &room));
-  if (need_d > avail) {
-    char msg[320];
-    snprintf(msg, sizeof msg, "%s: the session needs %.0f bytes (%lld rows x %lld frames, raw and filtered), the device has %zu bytes "
-             "free of which %.0f stay with the context", fn, need_d, (long long)nrow, (long long)capacity, room.free_b, room.reserve);
-    ctx->err = msg;
-    return FSI_ERR_INVALID;
-  }
-  return FSI_OK;
-}
+// What a band-pass session of `rows` rows and `capacity` frames takes (fsi_band_room, the begin calls): the history, the
+// filtered series (capacity + 2 BAND_MAX_PADLEN frames), one frame each of running sums, amplitudes and magnitudes (a frame of
+// magnitudes counted as a frame of rows) and the row lists.
+double band_need(int64_t rows, int64_t capacity) { return 8.0 * (double)rows * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN + 4.0); }
 
 // Opens a session whose begin call has passed its checks and released what the quantity had: hist[capacity][nrow],
 // work[capacity + 2 BAND_MAX_PADLEN][nrow], the row lists and, where the row is the magnitude of three sampled entries, tmp.
@@ -148,17 +141,41 @@ int history_open(FsiCtx* ctx, FsiCtx::History& s, int64_t n, int64_t nrow, int64
   return FSI_OK;
 }
 
-// the session's entries of dvp_["n"] (or their magnitude) into the next frame of the history
-int history_sample(FsiCtx* ctx, FsiCtx::History* s, const char* fn, const char* begin) {
+// What the two band-pass begin calls do once their lists stand: the room check (fsi_band_room), then the session of nnode
+// nodes of ncomp components each
+int band_open(FsiCtx* ctx, const char* fn, int32_t quantity, int64_t nnode, int ncomp, int64_t capacity, const std::vector<int32_t>& i0,
+              const std::vector<int32_t>& i1) {
+  const int64_t nrow = nnode * ncomp;
+  HIPCHK(hipSetDevice(ctx->device));
+  FSICHK(room_for(ctx, fn, "the session needs", band_need(nrow, capacity), counted(nrow, " rows x ", capacity, " frames, raw and filtered")));
+  auto& s = ctx->band[quantity];
+  s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
+  s.ncomp = ncomp;
+  HIPCHK(s.acc.alloc((size_t)nrow));
+  HIPCHK(s.amp.alloc((size_t)nrow));
+  HIPCHK(s.mag.alloc((size_t)nnode));
+  HIPCHK(s.part_val.alloc(BAND_ARGMAX_BLOCKS + 1));
+  HIPCHK(s.part_idx.alloc(BAND_ARGMAX_BLOCKS + 1));
+  return history_open(ctx, s, nnode, nrow, capacity, i0, i1, false);
+}
+
+// The next frame of the history: sample(dst) launches what fills it from dvp_["n"]; begin: the call that declared the capacity
+template <class Sample>
+int history_append(FsiCtx* ctx, FsiCtx::History* s, const char* fn, const char* begin, Sample sample) {
   if (s->frames >= s->capacity) { ctx->err = std::string(fn) + ": the history is full (capacity declared at " + begin + ")"; return FSI_ERR_INVALID; }
   HIPCHK(hipSetDevice(ctx->device));
-  double* dst = s->hist.p + (size_t)s->frames * s->nrow;
-  launch_band_sample(ctx->stream, s->nsamp, ctx->U.p, s->idx0.p, s->idx1.p, s->tmp.p ? s->tmp.p : dst);
-  if (s->tmp.p) launch_spec_magnitude(ctx->stream, s->nnode, s->tmp.p, dst);
+  sample(s->hist.p + (size_t)s->frames * s->nrow);
   HIPCHK(hipGetLastError());
   s->frames += 1;
   s->filtered = false;        // a filtered series no longer covers the history
   return FSI_OK;
+}
+// the session's entries of dvp_["n"] (or their magnitude) into the next frame of the history
+int history_sample(FsiCtx* ctx, FsiCtx::History* s, const char* fn, const char* begin) {
+  return history_append(ctx, s, fn, begin, [&](double* dst) {
+    launch_band_sample(ctx->stream, s->nsamp, ctx->U.p, s->idx0.p, s->idx1.p, s->tmp.p ? s->tmp.p : dst);
+    if (s->tmp.p) launch_spec_magnitude(ctx->stream, s->nnode, s->tmp.p, dst);
+  });
 }
 
 // The checks of a filter call on a series of `frames` frames, and its coefficients as the kernels take them; ntaps_range: the
@@ -270,6 +287,42 @@ int cell_geometry_frames(FsiCtx* ctx, const char* fn, const FsiCtx::Band* s, int
   return FSI_OK;
 }
 
+// fsi_band_cell_vortex and, current, fsi_band_cell_vortex_current: per cell the nf means over the taken frames of the series -
+// current: on the geometry of the d frames that go with them, and behind the means their nf numerator means - and the
+// weighted sums over the cells of the means (current: of the numerators)
+int cell_vortex(FsiCtx* ctx, const char* fn, bool current, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count,
+                double* cells_out, double* sums_out) {
+  auto* s = cell_series_session(ctx, fn, quantity, series);
+  if (!s) return FSI_ERR_INVALID;
+  auto refuse = [&](const char* why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
+  if (!cells_out && !sums_out) return refuse("cells_out and sums_out are both NULL");
+  if (sums_out && !s->cell_weighted) return refuse("sums_out without weights (fsi_band_cell_weights first)");
+  const double *x = nullptr, *geo = nullptr;
+  int64_t frame_stride = 0, geo_stride = 0;
+  FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x, &frame_stride));
+  if (current) FSICHK(cell_geometry_frames(ctx, fn, s, series, first, step, &geo, &geo_stride));
+  HIPCHK(hipSetDevice(ctx->device));
+  const int nf = current ? FSI_VORTEX_CURRENT_FIELDS : FSI_VORTEX_FIELDS;
+  const size_t n = (size_t)s->ncell, nblock = (size_t)cell_wsum_blocks(s->ncell), rows = current ? 2 * nf : nf;
+  DevBuf<double>&out = current ? s->vortex_cur_out : s->vortex_out, &part = current ? s->vortex_cur_part : s->vortex_part;
+  FSICHK(cell_buffer(ctx, fn, current ? "the twelve results need" : "the five results need", &out, rows * n,
+                     counted(s->ncell, " cells x ", 8 * rows, "")));
+  if (sums_out)
+    FSICHK(cell_buffer(ctx, fn, "the partial sums need", &part, nf * (nblock + 1), counted(nblock, " groups of 256 cells and the sums x ", 8 * nf, "")));
+  if (current) launch_cell_vortex_current(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, geo, geo_stride, count, out.p);
+  else launch_cell_vortex(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, count, out.p);
+  HIPCHK(hipGetLastError());
+  if (cells_out) HIPCHK(hipMemcpyAsync(cells_out, out.p, nf * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (sums_out) {      // current: the bulk sums are those of the numerators, rows 6 .. 11
+    double* sums = part.p + nf * nblock;
+    launch_cell_wsum(ctx->stream, s->ncell, nf, s->cell_weight.p, out.p + (rows - nf) * n, part.p, sums);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sums_out, sums, nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return FSI_OK;
+}
+
 // raw frames first .. first + count - 1 of the history to the host, out[count][nrow]: frame-major, so one copy, behind
 // whatever was sampled on the stream; it has finished when the call returns
 int history_export(FsiCtx* ctx, const FsiCtx::History* s, const char* fn, int64_t first, int64_t count, double* out) {
@@ -328,39 +381,25 @@ int end_session(FsiCtx* ctx, S (&all)[N], int32_t q, const char* fn) {
   return FSI_OK;
 }
 
-// The refusal rule of the spectrogram begin calls, once: the raw and the filtered history and the sampled vector of the
-// magnitude (nsamp entries, two lists), as band_room; with them what the transforms allocate at the end of the run, so that a
+// What a spectrogram session takes (fsi_spec_room, the begin calls): the raw and the filtered history and the sampled vector of
+// the magnitude (nsamp entries, two lists), as band_need; with them what the transforms allocate at the end of the run, so that a
 // history that fits here is not refused there: one pass of SPEC_BINS bins of a periodogram's tables over all frames, and the
 // means of capacity / 4 segments.
-int spec_room(FsiCtx* ctx, int64_t nrow, int64_t nsamp, int64_t capacity, double* need, double* available, Room* room) {
-  FSICHK(device_room(ctx, room));
-  *need = 8.0 * (double)nrow * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN) + 16.0 * (double)nsamp +
-          16.0 * SPEC_BINS * (double)capacity + 8.0 * (double)nrow * ((double)capacity / 4.0 + 2.0);
-  *available = (double)room->free_b - room->reserve;
-  return FSI_OK;
+double spec_need(int64_t nrow, int64_t nsamp, int64_t capacity) {
+  return 8.0 * (double)nrow * (2.0 * (double)capacity + 2.0 * BAND_MAX_PADLEN) + 16.0 * (double)nsamp +
+         16.0 * SPEC_BINS * (double)capacity + 8.0 * (double)nrow * ((double)capacity / 4.0 + 2.0);
 }
-
-// The room check of the three spectrogram begin calls: refused, with both byte counts, when the session does not fit.
-int spec_refused(FsiCtx* ctx, const char* fn, int64_t nrow, int64_t nsamp, int64_t capacity) {
+// The room check of the three spectrogram begin calls
+int spec_room_for(FsiCtx* ctx, const char* fn, int64_t nrow, int64_t nsamp, int64_t capacity) {
   HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  double need_d = 0.0, avail = 0.0;
-  Room room;
-  FSICHK(spec_room(ctx, nrow, nsamp, capacity, &need_d, &avail, &room));
-  if (need_d > avail) {
-    char msg[420];
-    snprintf(msg, sizeof msg, "%s: the session needs %.0f bytes (%lld rows x %lld frames, raw and filtered, and the transforms' tables), the device has %zu bytes "
-             "free of which %.0f stay with the context", fn, need_d, (long long)nrow, (long long)capacity, room.free_b, room.reserve);
-    ctx->err = msg;
-    return FSI_ERR_INVALID;
-  }
-  return FSI_OK;
+  return room_for(ctx, fn, "the session needs", spec_need(nrow, nsamp, capacity),
+                  counted(nrow, " rows x ", capacity, " frames, raw and filtered, and the transforms' tables"));
 }
 
 // What fsi_spec_begin and fsi_spec_begin_rows do once their row lists stand: the room check, then the session.
 int spec_open(FsiCtx* ctx, const char* fn, int32_t quantity, int64_t n, int64_t nrow, int mode, int64_t capacity,
               const std::vector<int32_t>& i0, const std::vector<int32_t>& i1) {
-  FSICHK(spec_refused(ctx, fn, nrow, (int64_t)i0.size(), capacity));
+  FSICHK(spec_room_for(ctx, fn, nrow, (int64_t)i0.size(), capacity));
   auto& s = ctx->spec[quantity];
   s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
   s.mode = mode;
@@ -391,12 +430,10 @@ int spec_power(FsiCtx* ctx, FsiCtx::Spec* s, const char* fn, int64_t K, int64_t 
   FSICHK(device_room(ctx, &room));
   const double avail = (double)room.free_b - room.reserve - fixed;
   if (avail < per_bin * (double)min_slab) {
-    char msg[460];
-    snprintf(msg, sizeof msg, "%s: the transform needs %.0f bytes (tables of %lld frames x %lld of %lld bins, cos and sin, %lld segments x %lld rows of "
-             "means and partial sums, and the result), the device has %zu bytes free of which %.0f stay with the context", fn,
-             fixed + per_bin * (double)min_slab, (long long)K, (long long)min_slab, (long long)nbins, (long long)nseg, (long long)s->nrow,
-             room.free_b, room.reserve);
-    ctx->err = msg;
+    ctx->err = room_refusal(fn, "the transform needs", fixed + per_bin * (double)min_slab,
+                            "tables of " + counted(K, " frames x ", min_slab, " of ") + counted(nbins, " bins, cos and sin, ", nseg, " segments x ") +
+                                std::to_string(s->nrow) + " rows of means and partial sums, and the result",
+                            room.free_b, room.reserve);
     return FSI_ERR_INVALID;
   }
   // the host makes the tables: cos / sin of nfft angles and one slab's columns.  A transform length whose tables the host
@@ -775,23 +812,13 @@ int fsi_band_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* node
   int mode = FSI_SPEC_ALL;      // every component of a node, node-major: a frame is the (n, ncomp) array of a Visualization file
   std::vector<int32_t> i0, i1;
   FSICHK(row_lists(ctx, "fsi_band_begin", quantity, n, nodes, nodes_b, capacity, &mode, true, i0, i1));
-  const int64_t nrow = (int64_t)i0.size();
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  FSICHK(band_refused(ctx, "fsi_band_begin", nrow, capacity));      // against what the device has free (fsi_band_room)
+  FSICHK(band_open(ctx, "fsi_band_begin", quantity, n, (int)((int64_t)i0.size() / n), capacity, i0, i1));
   auto& s = ctx->band[quantity];
-  s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
-  s.ncomp = (int)(nrow / n);
-  HIPCHK(s.acc.alloc((size_t)nrow));
-  HIPCHK(s.amp.alloc((size_t)nrow));
-  HIPCHK(s.mag.alloc((size_t)n));
-  HIPCHK(s.part_val.alloc(BAND_ARGMAX_BLOCKS + 1));
-  HIPCHK(s.part_idx.alloc(BAND_ARGMAX_BLOCKS + 1));
   s.h_nodes.assign(nodes, nodes + n);            // for fsi_band_cells: a row that is the mean of two nodes is no node's
   if (nodes_b)
     for (int64_t i = 0; i < n; ++i)
       if (nodes_b[i] >= 0) s.h_nodes[i] = -1;
-  return history_open(ctx, s, n, nrow, capacity, i0, i1, false);
+  return FSI_OK;
 }
 
 int fsi_band_begin_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* cells, int64_t capacity) {
@@ -808,39 +835,22 @@ int fsi_band_begin_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t
     if (cells[i] < 0 || cells[i] >= ctx->C) return refuse("cell out of range");
     if (kinds[cells[i]] != 1) return refuse("cell is not a solid cell");
   }
-  // the bytes of fsi_band_begin with nrow = 24 n rows and nnode = 4 n DG1 dofs
-  const int64_t nnode = 4 * n, nrow = 6 * nnode;
-  FSICHK(band_refused(ctx, "fsi_band_begin_cells", nrow, capacity));
-  auto& s = ctx->band[quantity];
-  s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
-  s.ncomp = 6;
-  HIPCHK(s.acc.alloc((size_t)nrow));
-  HIPCHK(s.amp.alloc((size_t)nrow));
-  HIPCHK(s.mag.alloc((size_t)nnode));
-  HIPCHK(s.part_val.alloc(BAND_ARGMAX_BLOCKS + 1));
-  HIPCHK(s.part_idx.alloc(BAND_ARGMAX_BLOCKS + 1));
+  // the bytes of fsi_band_begin with nnode = 4 n DG1 dofs of six components: nrow = 24 n rows
   const std::vector<int32_t> list(cells, cells + n), unused((size_t)n, -1);      // idx0: the cells
-  return history_open(ctx, s, nnode, nrow, capacity, list, unused, false);
+  return band_open(ctx, "fsi_band_begin_cells", quantity, 4 * n, 6, capacity, list, unused);
 }
 
 int fsi_band_sample(FsiCtx* ctx, int32_t quantity) {
   if (!ctx) return FSI_ERR_INVALID;
   auto* s = band_session(ctx, quantity, "fsi_band_sample");
   if (!s) return FSI_ERR_INVALID;
-  if (tensor_quantity(quantity)) {
-    if (s->frames >= s->capacity) { ctx->err = "fsi_band_sample: the history is full (capacity declared at fsi_band_begin_cells)"; return FSI_ERR_INVALID; }
-    HIPCHK(hipSetDevice(ctx->device));
-    launch_tensor_sample(ctx->stream, s->nsamp, elem_arrays(ctx), elem_params(ctx), ctx->U.p, s->idx0.p, quantity == FSI_BAND_STRAIN,
-                         s->hist.p + (size_t)s->frames * s->nrow);
-    HIPCHK(hipGetLastError());
-    s->frames += 1;
-    s->filtered = false;        // as history_sample
-  } else
+  if (tensor_quantity(quantity))
+    FSICHK(history_append(ctx, s, "fsi_band_sample", "fsi_band_begin_cells", [&](double* dst) {
+      launch_tensor_sample(ctx->stream, s->nsamp, elem_arrays(ctx), elem_params(ctx), ctx->U.p, s->idx0.p, quantity == FSI_BAND_STRAIN, dst);
+    }));
+  else
     FSICHK(history_sample(ctx, s, "fsi_band_sample", "fsi_band_begin"));
-  s->window = -1;
-  s->phase_release();           // a phase average covers the frames it was formed on
-  s->spi_release();             // and so does a spectral power index
-  s->sel_first = 0; s->sel_stride = 1; s->sel_count = -1;      // a selection covers the frames it was made on
+  s->frames_changed();
   return FSI_OK;
 }
 
@@ -857,11 +867,7 @@ int fsi_band_select(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count,
   s->sel_first = first;
   s->sel_stride = stride;
   s->sel_count = count == -1 ? (s->frames - 1 - first) / stride + 1 : count;
-  s->filtered = false;
-  s->phase_release();
-  s->spi_release();
-  s->window = -1;
-  s->acc_start = -1;
+  s->selection_changed();
   return FSI_OK;
 }
 
@@ -870,9 +876,7 @@ int fsi_band_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* 
   auto* s = band_session(ctx, quantity, "fsi_band_filter");
   if (!s) return FSI_ERR_INVALID;
   FSICHK(history_filter(ctx, s, "fsi_band_filter", "2 .. 11", ntaps, b, a, zi, padlen, s->sel_first, s->sel_stride, band_frames(s)));
-  s->phase_release();           // the filtered series is the band again
-  s->window = -1;
-  s->acc_start = -1;
+  s->series_changed();          // the filtered series is the band again: no phase average
   return FSI_OK;
 }
 
@@ -893,9 +897,7 @@ int fsi_band_filter_next(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const dou
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));
   s->padlen = padlen;
-  s->window = -1;
-  s->acc_start = -1;
-  s->phase_release();           // the series is no longer the fluctuation about the mean
+  s->series_changed();          // the series is no longer the fluctuation about the mean
   return FSI_OK;
 }
 
@@ -912,20 +914,12 @@ int fsi_band_phase(FsiCtx* ctx, int32_t quantity, int64_t period) {
   }
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  // the period's mean frames are an allocation of their own, under the room rule of the begin calls; the mean frames of an
-  // earlier call are given back first where they are of another size (they count as taken otherwise)
+  // the period's mean frames are an allocation of their own, under the room rule; the mean frames of an earlier call are
+  // given back first where they are of another size, and serve again otherwise
   const size_t count = (size_t)period * (size_t)s->nrow;
   if (s->phase_mean.n != count) {
-    Room room;
-    FSICHK(device_room(ctx, &room));
-    const double need_d = 8.0 * (double)period * (double)s->nrow, avail = (double)room.free_b + 8.0 * (double)s->phase_mean.n - room.reserve;
-    if (need_d > avail) {
-      char msg[320];
-      snprintf(msg, sizeof msg, "fsi_band_phase: the phase means need %.0f bytes (%lld rows x %lld frames), the device has %zu bytes free of which "
-               "%.0f stay with the context", need_d, (long long)s->nrow, (long long)period, room.free_b, room.reserve);
-      ctx->err = msg;
-      return FSI_ERR_INVALID;
-    }
+    FSICHK(room_for(ctx, "fsi_band_phase", "the phase means need", 8.0 * (double)period * (double)s->nrow,
+                    counted(s->nrow, " rows x ", period, " frames"), 8.0 * (double)s->phase_mean.n));
     s->phase_period = 0;
     HIPCHK(s->phase_mean.alloc(count));
     HIPCHK(hipDeviceSynchronize());                                // the allocation's own fill is done
@@ -934,11 +928,10 @@ int fsi_band_phase(FsiCtx* ctx, int32_t quantity, int64_t period) {
                          s->phase_mean.p, s->work.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  s->series_changed(true);      // the mean frames are this call's own
   s->padlen = 0;                // the fluctuation is the filtered series, without guard frames
   s->filtered = true;
   s->phase_period = period;
-  s->window = -1;
-  s->acc_start = -1;
   return FSI_OK;
 }
 
@@ -1010,14 +1003,8 @@ int fsi_band_spi(FsiCtx* ctx, int32_t quantity, const double* window, int64_t bi
   if (bin0 > 0 && (!stands(wants[0]) || !stands(wants[1]) || !stands(wants[2]) || !stands(wants[3])))
     return refuse("a slab out of order: the sums of the slabs before it are gone (bin0 = 0 first)");
   if (need_d > 0.0) {
-    Room room;
-    FSICHK(device_room(ctx, &room));
-    if (need_d > (double)room.free_b + back - room.reserve) {
-      char msg[360];
-      snprintf(msg, sizeof msg, "the sums and tables need %.0f bytes (%lld rows, %lld frames x %lld bins of cos and sin), the device has %zu bytes free of "
-               "which %.0f stay with the context", need_d, (long long)s->nrow, (long long)n, (long long)nb, room.free_b, room.reserve);
-      return refuse(msg);
-    }
+    FSICHK(room_for(ctx, "fsi_band_spi", "the sums and tables need", need_d,
+                    std::to_string(s->nrow) + " rows, " + counted(n, " frames x ", nb, " bins of cos and sin"), back));
     for (const Want& w : wants)
       if (!stands(w)) {
         const hipError_t e = w.buf->alloc(w.count);
@@ -1098,18 +1085,9 @@ int fsi_band_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* cell
       conn[10 * i + a] = at[node];
     }
   HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  // the room rule of fsi_band_begin; the list that stands is given back only once the new one is in place, so it counts as taken
-  Room room;
-  FSICHK(device_room(ctx, &room));
-  const double need_d = 144.0 * (double)n, avail = (double)room.free_b - room.reserve;
-  if (need_d > avail) {
-    char msg[320];
-    snprintf(msg, sizeof msg, "fsi_band_cells: the cell list needs %.0f bytes (%lld cells x 144: ten nodes, twelve gradients, one result), the "
-             "device has %zu bytes free of which %.0f stay with the context", need_d, (long long)n, room.free_b, room.reserve);
-    ctx->err = msg;
-    return FSI_ERR_INVALID;
-  }
+  // the list that stands is given back only once the new one is in place, so it counts as taken
+  FSICHK(room_for(ctx, "fsi_band_cells", "the cell list needs", 144.0 * (double)n,
+                  std::to_string(n) + " cells x 144: ten nodes, twelve gradients, one result"));
   DevBuf<int32_t> d_conn, d_cells;
   DevBuf<double> d_gl, d_out;
   HIPCHK(d_conn.alloc((size_t)n * 10));
@@ -1127,7 +1105,7 @@ int fsi_band_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* cell
   std::swap(s->cell_gl.p, d_gl.p); std::swap(s->cell_gl.n, d_gl.n);
   std::swap(s->cell_out.p, d_out.p); std::swap(s->cell_out.n, d_out.n);
   s->ncell = n;
-  s->cell_weighted = false;                                        // the weights were those of the earlier list
+  s->cell_list_changed();
   return FSI_OK;
 }
 
@@ -1161,18 +1139,8 @@ int fsi_band_cell_rate_current(FsiCtx* ctx, int32_t quantity, int32_t series, in
   int64_t geo_stride = 0;
   FSICHK(cell_geometry_frames(ctx, fn, s, series, first, step, &geo, &geo_stride));
   HIPCHK(hipSetDevice(ctx->device));
-  if (s->cell_vol.n != (size_t)s->ncell || s->cell_minj.n != (size_t)s->ncell) {      // the room rule of fsi_band_begin, as fsi_band_phase applies it
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    Room room;
-    FSICHK(device_room(ctx, &room));
-    const double need_d = 16.0 * (double)s->ncell, avail = (double)room.free_b - room.reserve;
-    if (need_d > avail) {
-      char msg[320];
-      snprintf(msg, sizeof msg, "fsi_band_cell_rate_current: the two further results need %.0f bytes (%lld cells x 16), the device has %zu bytes "
-               "free of which %.0f stay with the context", need_d, (long long)s->ncell, room.free_b, room.reserve);
-      ctx->err = msg;
-      return FSI_ERR_INVALID;
-    }
+  if (s->cell_vol.n != (size_t)s->ncell || s->cell_minj.n != (size_t)s->ncell) {
+    FSICHK(room_for(ctx, fn, "the two further results need", 16.0 * (double)s->ncell, std::to_string(s->ncell) + " cells x 16"));
     HIPCHK(s->cell_vol.alloc((size_t)s->ncell));
     HIPCHK(s->cell_minj.alloc((size_t)s->ncell));
     HIPCHK(hipDeviceSynchronize());                                // the allocations' own fills are done
@@ -1198,7 +1166,7 @@ int fsi_band_cell_weights(FsiCtx* ctx, int32_t quantity, const double* weights) 
   if (s->ncell < 1) return refuse("no cell list (fsi_band_cells first)");
   if (!weights) { s->cell_weighted = false; return FSI_OK; }
   HIPCHK(hipSetDevice(ctx->device));
-  FSICHK(cell_buffer(ctx, "fsi_band_cell_weights", "the weights", &s->cell_weight, (size_t)s->ncell, std::to_string(s->ncell) + " cells x 8"));
+  FSICHK(cell_buffer(ctx, "fsi_band_cell_weights", "the weights need", &s->cell_weight, (size_t)s->ncell, std::to_string(s->ncell) + " cells x 8"));
   HIPCHK(hipMemcpyAsync(s->cell_weight.p, weights, (size_t)s->ncell * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));                       // the caller's array is free again
   s->cell_weighted = true;
@@ -1207,63 +1175,12 @@ int fsi_band_cell_weights(FsiCtx* ctx, int32_t quantity, const double* weights) 
 
 int fsi_band_cell_vortex(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count, double* cells_out,
                          double* sums_out) {
-  const char* fn = "fsi_band_cell_vortex";
-  auto* s = cell_series_session(ctx, fn, quantity, series);
-  if (!s) return FSI_ERR_INVALID;
-  auto refuse = [&](const char* why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
-  if (!cells_out && !sums_out) return refuse("cells_out and sums_out are both NULL");
-  if (sums_out && !s->cell_weighted) return refuse("sums_out without weights (fsi_band_cell_weights first)");
-  const double* x = nullptr;
-  int64_t frame_stride = 0;
-  FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x, &frame_stride));
-  HIPCHK(hipSetDevice(ctx->device));
-  const size_t n = (size_t)s->ncell, nblock = (size_t)cell_wsum_blocks(s->ncell);
-  FSICHK(cell_buffer(ctx, fn, "the five results", &s->vortex_out, FSI_VORTEX_FIELDS * n, std::to_string(s->ncell) + " cells x 40"));
-  if (sums_out)
-    FSICHK(cell_buffer(ctx, fn, "the partial sums", &s->vortex_part, FSI_VORTEX_FIELDS * (nblock + 1),
-                       std::to_string(nblock) + " groups of 256 cells and the sums x 40"));
-  launch_cell_vortex(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, count, s->vortex_out.p);
-  HIPCHK(hipGetLastError());
-  if (cells_out) HIPCHK(hipMemcpyAsync(cells_out, s->vortex_out.p, FSI_VORTEX_FIELDS * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (sums_out) {
-    double* sums = s->vortex_part.p + FSI_VORTEX_FIELDS * nblock;
-    launch_cell_wsum(ctx->stream, s->ncell, FSI_VORTEX_FIELDS, s->cell_weight.p, s->vortex_out.p, s->vortex_part.p, sums);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(sums_out, sums, FSI_VORTEX_FIELDS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return FSI_OK;
+  return cell_vortex(ctx, "fsi_band_cell_vortex", false, quantity, series, first, step, count, cells_out, sums_out);
 }
 
 int fsi_band_cell_vortex_current(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t first, int64_t step, int64_t count, double* cells_out,
                                  double* sums_out) {
-  const char* fn = "fsi_band_cell_vortex_current";
-  auto* s = cell_series_session(ctx, fn, quantity, series);
-  if (!s) return FSI_ERR_INVALID;
-  auto refuse = [&](const char* why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
-  if (!cells_out && !sums_out) return refuse("cells_out and sums_out are both NULL");
-  if (sums_out && !s->cell_weighted) return refuse("sums_out without weights (fsi_band_cell_weights first)");
-  const double *x = nullptr, *geo = nullptr;
-  int64_t frame_stride = 0, geo_stride = 0;
-  FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x, &frame_stride));
-  FSICHK(cell_geometry_frames(ctx, fn, s, series, first, step, &geo, &geo_stride));
-  HIPCHK(hipSetDevice(ctx->device));
-  const size_t n = (size_t)s->ncell, nblock = (size_t)cell_wsum_blocks(s->ncell), nf = FSI_VORTEX_CURRENT_FIELDS;
-  FSICHK(cell_buffer(ctx, fn, "the twelve results", &s->vortex_cur_out, 2 * nf * n, std::to_string(s->ncell) + " cells x 96"));
-  if (sums_out)
-    FSICHK(cell_buffer(ctx, fn, "the partial sums", &s->vortex_cur_part, nf * (nblock + 1),
-                       std::to_string(nblock) + " groups of 256 cells and the sums x 48"));
-  launch_cell_vortex_current(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, geo, geo_stride, count, s->vortex_cur_out.p);
-  HIPCHK(hipGetLastError());
-  if (cells_out) HIPCHK(hipMemcpyAsync(cells_out, s->vortex_cur_out.p, nf * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (sums_out) {      // the bulk sums are those of the numerators: rows 6 .. 11
-    double* sums = s->vortex_cur_part.p + nf * nblock;
-    launch_cell_wsum(ctx->stream, s->ncell, FSI_VORTEX_CURRENT_FIELDS, s->cell_weight.p, s->vortex_cur_out.p + nf * n, s->vortex_cur_part.p, sums);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(sums_out, sums, nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return FSI_OK;
+  return cell_vortex(ctx, "fsi_band_cell_vortex_current", true, quantity, series, first, step, count, cells_out, sums_out);
 }
 
 int fsi_band_amplitude(FsiCtx* ctx, int32_t quantity, int32_t window) {
@@ -1275,8 +1192,7 @@ int fsi_band_amplitude(FsiCtx* ctx, int32_t quantity, int32_t window) {
     ctx->err = "fsi_band_amplitude: window of " + std::to_string(window) + " frames, the series has " + std::to_string(band_frames(s));
     return FSI_ERR_INVALID;
   }
-  s->window = window;
-  s->acc_start = -1;
+  s->amplitude_changed(window);
   return FSI_OK;
 }
 
@@ -1378,10 +1294,7 @@ int fsi_band_import(FsiCtx* ctx, int32_t quantity, int64_t count, const double* 
   auto* s = band_session(ctx, quantity, "fsi_band_import");
   if (!s) return FSI_ERR_INVALID;
   FSICHK(history_import(ctx, s, "fsi_band_import", count, frames));
-  s->window = -1;
-  s->sel_first = 0; s->sel_stride = 1; s->sel_count = -1;      // as fsi_band_sample: a selection covers the frames it was made on
-  s->phase_release();
-  s->spi_release();
+  s->frames_changed();
   return FSI_OK;
 }
 
@@ -1389,11 +1302,10 @@ int fsi_band_room(FsiCtx* ctx, int64_t rows, int64_t capacity, double* need, dou
   if (!ctx) return FSI_ERR_INVALID;
   if (rows < 1 || capacity < 1 || !need || !available) { ctx->err = "fsi_band_room: needs rows >= 1, capacity >= 1 and both outputs"; return FSI_ERR_INVALID; }
   HIPCHK(hipSetDevice(ctx->device));
-  double n = 0.0, a = 0.0;
   Room room;
-  FSICHK(band_room(ctx, rows, capacity, &n, &a, &room));
-  *need = n;
-  *available = a;
+  FSICHK(device_room(ctx, &room));
+  *need = band_need(rows, capacity);
+  *available = room.available();
   return FSI_OK;
 }
 
@@ -1403,17 +1315,7 @@ int fsi_board_begin(FsiCtx* ctx, int64_t nodes, int64_t frames) {
   if (nodes >= (1ll << 32)) { ctx->err = "fsi_board_begin: more than 2^32 - 1 nodes"; return FSI_ERR_INVALID; }
   if (partitioned(ctx, "fsi_board_begin")) return FSI_ERR_INVALID;
   HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  Room room;
-  FSICHK(device_room(ctx, &room));
-  const double need_d = 8.0 * (double)nodes * (double)frames;
-  if (need_d > (double)room.free_b - room.reserve) {
-    char msg[320];
-    snprintf(msg, sizeof msg, "fsi_board_begin: the board needs %.0f bytes (%lld nodes x %lld frames), the device has %zu bytes free of which "
-             "%.0f stay with the context", need_d, (long long)nodes, (long long)frames, room.free_b, room.reserve);
-    ctx->err = msg;
-    return FSI_ERR_INVALID;
-  }
+  FSICHK(room_for(ctx, "fsi_board_begin", "the board needs", 8.0 * (double)nodes * (double)frames, counted(nodes, " nodes x ", frames, " frames")));
   for (auto& s : ctx->band) s.board_node0 = -1;      // only now: a refused begin leaves an open board and its sessions as they were
   auto& b = ctx->board;
   b.release();
@@ -1567,7 +1469,7 @@ int fsi_spec_begin_wss(FsiCtx* ctx, int64_t nf, const int32_t* facet_cells, cons
     ent[2 * k + 1] = 4 * VERTS[facet_local[dofs[r] / 3]][dofs[r] % 3] + comps[r];
   }
   ptr.push_back((int32_t)nrows);
-  FSICHK(spec_refused(ctx, "fsi_spec_begin_wss", nrows, nrows + 2 * nmag, capacity));      // a magnitude row as in fsi_spec_room
+  FSICHK(spec_room_for(ctx, "fsi_spec_begin_wss", nrows, nrows + 2 * nmag, capacity));      // a magnitude row as in fsi_spec_room
   auto& s = ctx->spec[FSI_SPEC_WSS];
   s.release();                  // only now: a refused begin leaves an open session of the quantity as it was
   s.mode = FSI_SPEC_X;
@@ -1595,11 +1497,10 @@ int fsi_spec_room(FsiCtx* ctx, int64_t rows, int32_t magnitude, int64_t capacity
   if (!ctx) return FSI_ERR_INVALID;
   if (rows < 1 || capacity < 1 || !need || !available) { ctx->err = "fsi_spec_room: needs rows >= 1, capacity >= 1 and both outputs"; return FSI_ERR_INVALID; }
   HIPCHK(hipSetDevice(ctx->device));
-  double n = 0.0, a = 0.0;
   Room room;
-  FSICHK(spec_room(ctx, rows, magnitude ? 3 * rows : rows, capacity, &n, &a, &room));
-  *need = n;
-  *available = a;
+  FSICHK(device_room(ctx, &room));
+  *need = spec_need(rows, magnitude ? 3 * rows : rows, capacity);
+  *available = room.available();
   return FSI_OK;
 }
 
@@ -1608,14 +1509,9 @@ int fsi_spec_sample(FsiCtx* ctx, int32_t quantity) {
   auto* s = spec_session(ctx, quantity, "fsi_spec_sample");
   if (!s) return FSI_ERR_INVALID;
   if (quantity != FSI_SPEC_WSS) return history_sample(ctx, s, "fsi_spec_sample", "fsi_spec_begin");
-  if (s->frames >= s->capacity) { ctx->err = "fsi_spec_sample: the history is full (capacity declared at fsi_spec_begin_wss)"; return FSI_ERR_INVALID; }
-  HIPCHK(hipSetDevice(ctx->device));
-  launch_spec_wss_sample(ctx->stream, s->wncell, elem_arrays(ctx), ctx->U.p, s->wcells.p, s->wmask.p, s->wptr.p, s->went.p, s->mu,
-                         s->hist.p + (size_t)s->frames * s->nrow);
-  HIPCHK(hipGetLastError());
-  s->frames += 1;
-  s->filtered = false;        // as history_sample
-  return FSI_OK;
+  return history_append(ctx, s, "fsi_spec_sample", "fsi_spec_begin_wss", [&](double* dst) {
+    launch_spec_wss_sample(ctx->stream, s->wncell, elem_arrays(ctx), ctx->U.p, s->wcells.p, s->wmask.p, s->wptr.p, s->went.p, s->mu, dst);
+  });
 }
 
 int fsi_spec_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* b, const double* a, const double* zi, int32_t padlen) {

@@ -753,17 +753,32 @@ class HostBandSession(HostHistory):
 
     def __init__(self, ncomp: int, capacity: int):
         super().__init__((-1, ncomp), capacity)
-        self.ncomp, self.amp, self.view = ncomp, None, slice(None)
+        self.ncomp = ncomp
         self.board, self.board_node0 = None, -1
-        self.phase_mean, self.phase_period = None, 0
         self.cell_conn = self.cell_grad = self.cell_weight = None
+        self.frames_changed()
+
+    # The ladder of FsiCtx::Band (csrc/fsi_context.hpp), function for function: recorded frames -> selection ->
+    # series -> amplitude, the spectral power index hanging on the selection.  A method that replaces a link calls that link's
+    # function, once, and resets nothing by hand.
+    def frames_changed(self) -> None:
+        self.view = slice(None)
+        self.selection_changed()
+
+    def selection_changed(self) -> None:
         self.spi_state = None
+        self.series_changed(None)
+
+    def series_changed(self, series, phase_mean=None, phase_period: int = 0) -> None:
+        self.filtered, self.phase_mean, self.phase_period = series, phase_mean, phase_period
+        self.amplitude_changed(None)
+
+    def amplitude_changed(self, amp) -> None:
+        self.amp = amp
 
     def sample(self, frame: np.ndarray) -> None:
         super().sample(frame)
-        self.amp, self.view = None, slice(None)
-        self.phase_mean, self.phase_period = None, 0
-        self.spi_state = None
+        self.frames_changed()
 
     def selected(self) -> np.ndarray:
         return np.stack(self.raw)[self.view]
@@ -776,21 +791,17 @@ class HostBandSession(HostHistory):
                                f"< the {frames} recorded frames")
         count = (frames - 1 - first) // stride + 1 if count == -1 else count
         self.view = slice(first, first + (count - 1) * stride + 1, stride)
-        self.filtered = self.amp = None
-        self.phase_mean, self.phase_period = None, 0
-        self.spi_state = None
+        self.selection_changed()
         return count
 
     def filter(self, b, a, zi, padlen: int) -> None:
-        self.filtered = filtfilt_rows(b, a, self.selected(), zi, padlen)
-        self.amp = None
-        self.phase_mean, self.phase_period = None, 0
+        self.series_changed(filtfilt_rows(b, a, self.selected(), zi, padlen))
 
     def phase(self, period: int) -> None:
         """The selected frames, whole cycles of ``period`` frames, into their mean over the cycles and the fluctuation about
         it (``phase_average``); the fluctuation becomes the filtered series.  A refused call changes nothing."""
         mean, fluct = phase_average(self.selected(), period)
-        self.phase_mean, self.phase_period, self.filtered, self.amp = mean, int(period), fluct, None
+        self.series_changed(fluct, mean, int(period))
 
     def phase_fetch(self, what: str, frame: int = 0) -> np.ndarray:
         """'mean' of phase ``frame`` (n, ncomp); 'energy' of fluctuation frame ``frame``, 'energy_cycle_mean' at phase ``frame``,
@@ -923,16 +934,23 @@ class HostBandSession(HostHistory):
         frames as ``cell_rate`` takes them - row 3 is the mean over the frames of the absolute value of each frame's cell mean
         of the helicity, not of the cell mean of |w . omega|; and (5,) or None, ``cell_wsum`` of those rows with the weights of
         ``cell_weights``.  The twin of fsi_band_cell_vortex: it refuses what that refuses."""
-        what = "hi-pass cell_vortex"
+        return self._cell_vortex("hi-pass cell_vortex", False, series, None, first, step, count, cells, sums)
+
+    def _cell_vortex(self, what: str, current: bool, series: str, geometry, first: int, step: int, count: int, cells: bool, sums: bool):
+        """``cell_vortex`` and, ``current``, ``cell_vortex_current``: the ordered means of the rows, and the sums of those means
+        (``current``: of the means of the numerators)."""
         own = (f"{what}: neither cells nor sums asked for" if not cells and not sums else
                f"{what}: sums without weights (cell_weights first)" if sums and self.cell_weight is None else None)
         x, first, step, count = self._cell_frames(what, series, first, step, count, own)
+        geo = self._cell_geometry(what, series, geometry) if current else None
+        conn, grad = self.cell_conn, self.cell_grad
         with np.errstate(all="ignore"):
-            s = np.zeros((len(VORTEX_FIELDS), len(self.cell_conn)))
+            sr = sn = np.zeros((len(VORTEX_CURRENT_FIELDS if current else VORTEX_FIELDS), len(conn)))
             for k in range(first, first + count * step, step):
-                s = s + cell_vortex(x[k][self.cell_conn], self.cell_grad)
-            out = s / float(count)
-        return (out if cells else None), (cell_wsum(out, self.cell_weight) if sums else None)
+                r, num = cell_vortex_current(x[k][conn], geo[k][conn], grad) if current else (cell_vortex(x[k][conn], grad),) * 2
+                sr, sn = sr + r, sn + num
+            out, num = sr / float(count), sn / float(count)
+        return (out if cells else None), (cell_wsum(num, self.cell_weight) if sums else None)
 
     def _cell_geometry(self, what: str, series: str, geometry) -> np.ndarray:
         """The frames of ``geometry``, the twin session of d, that go with the frames of ``series`` of this session - for
@@ -965,19 +983,7 @@ class HostBandSession(HostHistory):
         volumes as weights and one frame, the integrals over the current fluid domain and, last, its volume.  ``geometry`` and
         the pairing of the frames as ``cell_rate_current`` has them.  The twin of fsi_band_cell_vortex_current: it refuses what
         that refuses."""
-        what = "hi-pass cell_vortex_current"
-        own = (f"{what}: neither cells nor sums asked for" if not cells and not sums else
-               f"{what}: sums without weights (cell_weights first)" if sums and self.cell_weight is None else None)
-        x, first, step, count = self._cell_frames(what, series, first, step, count, own)
-        geo = self._cell_geometry(what, series, geometry)
-        with np.errstate(all="ignore"):
-            shape = (len(VORTEX_CURRENT_FIELDS), len(self.cell_conn))
-            sr, sn = np.zeros(shape), np.zeros(shape)
-            for k in range(first, first + count * step, step):
-                r, num = cell_vortex_current(x[k][self.cell_conn], geo[k][self.cell_conn], self.cell_grad)
-                sr, sn = sr + r, sn + num
-            out, num = sr / float(count), sn / float(count)
-        return (out if cells else None), (cell_wsum(num, self.cell_weight) if sums else None)
+        return self._cell_vortex("hi-pass cell_vortex_current", True, series, geometry, first, step, count, cells, sums)
 
     def cell_rate_current(self, series: str, geometry, first: int = 0, step: int = 1, count: int = -1):
         """``cell_rate`` in the current configuration: ``(rate, volume_ratio, min_jacobian)`` per attached cell, the ordered
@@ -1002,9 +1008,7 @@ class HostBandSession(HostHistory):
     def filter_next(self, b, a, zi, padlen: int) -> None:
         if self.filtered is None:
             raise RuntimeError("hi-pass filter_next: no filtered series (filter first)")
-        self.filtered = filtfilt_rows(b, a, self.filtered, zi, padlen)
-        self.amp = None
-        self.phase_mean, self.phase_period = None, 0
+        self.series_changed(filtfilt_rows(b, a, self.filtered, zi, padlen))
 
     def trace(self, what: str, points) -> np.ndarray:
         """(points, frames, 1 + ncomp): the magnitude, then the row of each listed node over the selected frames."""
@@ -1019,7 +1023,7 @@ class HostBandSession(HostHistory):
         return np.concatenate([mag[:, :, None], rows], axis=2)
 
     def amplitude(self, window: int) -> None:
-        self.amp = self.filtered if window == 0 else windowed_rms_running(self.filtered, window)
+        self.amplitude_changed(self.filtered if window == 0 else windowed_rms_running(self.filtered, window))
 
     def board_attach(self, node0: int, board=None) -> None:
         """From now on an 'amplitude' or 'magnitude' fetch of frame k also stores its magnitudes into ``board`` (a
@@ -1046,21 +1050,15 @@ class DeviceSession:
 
     def __getattr__(self, name: str):
         call = getattr(self.backend, f"{self.prefix}_{name.rstrip('_')}")       # import_ -> <prefix>_import
-        return lambda *args: call(self.q, *args)
+        return lambda *args, **kwargs: call(self.q, *args, **kwargs)
 
-    def cell_rate_current(self, series: str, geometry, *args):
+    def cell_rate_current(self, series: str, geometry, *args, **kwargs):
         """The host session's signature: on the device the geometry is the session of d the context holds."""
-        return self.backend.hi_pass_cell_rate_current(self.q, series, *args)
+        return self.backend.hi_pass_cell_rate_current(self.q, series, *args, **kwargs)
 
     def cell_vortex_current(self, series: str, geometry, *args, **kwargs):
         """The host session's signature: on the device the geometry is the session of d the context holds."""
         return self.backend.hi_pass_cell_vortex_current(self.q, series, *args, **kwargs)
-
-    def cell_weights(self, weights) -> None:
-        self.backend.hi_pass_cell_weights(self.q, weights)
-
-    def cell_vortex(self, series: str, *args, **kwargs):
-        return self.backend.hi_pass_cell_vortex(self.q, series, *args, **kwargs)
 
 
 # ------------------------------------------------------------------------------------------------
