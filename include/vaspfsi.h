@@ -513,6 +513,40 @@ int fsi_band_spi(FsiCtx* ctx, int32_t quantity, const double* window, int64_t bi
  *   FSI_SPI_SUMS   out[3][rows]: L2, X0^2 and Q as they stand.
  * FSI_ERR_INVALID "no spectral power index (fsi_band_spi first)" without one, for a null out and a partitioned context. */
 int fsi_band_spi_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, double* out);
+/* Replaces: nothing in the reference: the Gram matrix of the snapshot proper orthogonal decomposition (POD) of the session's
+ * n >= 2 selected frames (fsi_pod.hip).  series: FSI_RATE_RAW the selected raw frames through the selection's stride,
+ * FSI_RATE_SERIES the filtered series or the fluctuation, whichever stands; FSI_RATE_PHASE_MEAN is refused.  node_weights: a
+ * host array of one value >= 0 and finite per node of the session, or NULL for 1; checked on the host, the refusal names the
+ * first offending node.  With m[r] the mean of row r over the n frames, added in frame order (k_spec_mean), y_j = x_j - m and
+ * a_j[r] = w_r y_j[r] rounded once (NULL: y_j itself, no product):
+ *   G[i][j] = sum_r a_i[r] y_j[r],
+ * formed for i <= j and mirrored, so G is symmetric bit for bit.  The rows are added in slabs of 6144 rows, four rows at a time
+ * in ascending order inside a slab, the slabs in ascending order: an order that depends on the numbers of rows and frames
+ * alone; no atomics, the same call gives the same bits.  A sum over the rows: one NaN or inf in the history makes every entry
+ * of G non-finite.  The call replaces a decomposition that stood, its modes included.  G, the slabs' partial sums, the mean and
+ * the weights are allocations of the session's own under the room rule of the begin calls: FSI_ERR_INVALID with both byte
+ * counts where they do not fit beside 1/16 of the device; a refused call changes nothing.  FSI_ERR_INVALID also without a
+ * session, for the tensor quantities (ncomp 6), a partitioned context, fewer than 2 selected frames (more than 16384),
+ * FSI_RATE_SERIES without a series.  fsi_band_sample, _import and _select drop the decomposition; fsi_band_filter,
+ * _filter_next and _phase drop one of the series and leave one of the raw frames; fsi_band_end and fsi_destroy free it. */
+int fsi_band_pod_gram(FsiCtx* ctx, int32_t quantity, int32_t series, const double* node_weights);
+/* Replaces: nothing in the reference: the modes of the decomposition whose Gram matrix stands (fsi_band_pod_gram),
+ *   Phi_m[r] = sum_j table[j * nmodes + m] * y_j[r],   m < nmodes, 1 <= nmodes <= 64,
+ * table[frames][nmodes] from the host - for orthonormal modes T[j][m] = V[j][m] / sqrt(lambda_m) of G V = V diag(lambda) - on
+ * the source and the mean the Gram matrix was formed on; the frames are added four at a time in ascending order.  Replaces the
+ * modes that stood.  The table and the modes are allocations of the session's own under the room rule.  FSI_ERR_INVALID
+ * "no Gram matrix (fsi_band_pod_gram first)" without one, for nmodes out of range, a null table, a partitioned context. */
+int fsi_band_pod_modes(FsiCtx* ctx, int32_t quantity, int32_t nmodes, const double* table);
+#define FSI_POD_GRAM 0
+#define FSI_POD_MEAN 1
+#define FSI_POD_MODE 2
+/* Replaces: nothing in the reference: what the decomposition holds, to the host.
+ *   FSI_POD_GRAM  out[n][n], the Gram matrix (index is not read);
+ *   FSI_POD_MEAN  out[nodes][ncomp], the mean the frames were taken about (index is not read);
+ *   FSI_POD_MODE  out[nodes][ncomp], mode `index` of fsi_band_pod_modes.
+ * FSI_ERR_INVALID "no Gram matrix (fsi_band_pod_gram first)" without one, "no modes (fsi_band_pod_modes first)" for a mode
+ * without them, for an index out of range, a null out and a partitioned context. */
+int fsi_band_pod_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t index, double* out);
 /* Replaces: nothing in the reference; VaMPy's metrics on an FSI run.  Attaches n > 0 mesh cells to the open session of
  * quantity 0 (d) or 1 (v) (fsi_band_begin), for fsi_band_cell_rate.  Every one of a cell's ten P2 nodes must be a node of the
  * session whose row is the node's own value (nodes_b < 0); of a node listed twice the first occurrence is used.  The range of

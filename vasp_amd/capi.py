@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "fsi_set_pressure_facets", "fsi_set_interface_pressure", "fsi_set_robin_facets", "fsi_solver_setup",
     "fsi_assemble_residual", "fsi_assemble_jacobian", "fsi_solve", "fsi_newton_solve", "fsi_shift",
     "fsi_get_state", "fsi_set_state", "fsi_set_frame", "fsi_num_dofs", "fsi_matrix_nnz", "fsi_device_memory", "fsi_apply_preconditioner", "fsi_get_matrix", "fsi_spmv",
-    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_phase", "fsi_band_phase_fetch", "fsi_band_spi", "fsi_band_spi_fetch", "fsi_band_cells", "fsi_band_cell_rate", "fsi_band_cell_rate_current", "fsi_band_cell_weights", "fsi_band_cell_vortex", "fsi_band_cell_vortex_current", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_begin_rows", "fsi_spec_begin_wss", "fsi_spec_room", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_spectrogram_sum", "fsi_spec_periodogram_sum", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
+    "fsi_get_timers", "fsi_get_solver_events", "fsi_xcd_order", "fsi_bcr_plan_graph", "fsi_solid_coarse_info", "fsi_solid_coarse_matrix", "fsi_solid_coarse_solve", "fsi_get_values", "fsi_stress_strain", "fsi_wall_shear_stress", "fsi_hemo_begin", "fsi_hemo_sample", "fsi_hemo_indices", "fsi_hemo_export", "fsi_hemo_import", "fsi_hemo_end", "fsi_stress_begin", "fsi_stress_sample", "fsi_stress_averages", "fsi_stress_export", "fsi_stress_import", "fsi_stress_end", "fsi_band_begin", "fsi_band_begin_cells", "fsi_band_sample", "fsi_band_filter", "fsi_band_select", "fsi_band_filter_next", "fsi_band_trace", "fsi_band_amplitude", "fsi_band_phase", "fsi_band_phase_fetch", "fsi_band_spi", "fsi_band_spi_fetch", "fsi_band_pod_gram", "fsi_band_pod_modes", "fsi_band_pod_fetch", "fsi_band_cells", "fsi_band_cell_rate", "fsi_band_cell_rate_current", "fsi_band_cell_weights", "fsi_band_cell_vortex", "fsi_band_cell_vortex_current", "fsi_band_fetch", "fsi_band_export", "fsi_band_import", "fsi_band_end", "fsi_band_room", "fsi_board_begin", "fsi_board_end", "fsi_band_board_attach", "fsi_board_table", "fsi_order_statistics", "fsi_spec_begin", "fsi_spec_begin_rows", "fsi_spec_begin_wss", "fsi_spec_room", "fsi_spec_sample", "fsi_spec_filter", "fsi_spec_fetch", "fsi_spec_spectrogram", "fsi_spec_periodogram", "fsi_spec_spectrogram_sum", "fsi_spec_periodogram_sum", "fsi_spec_export", "fsi_spec_import", "fsi_spec_end", "fsi_calibration_streams", "fsi_set_newton_forcing", "fsi_set_linear_solver", "fsi_set_chebyshev", "fsi_probe", "fsi_flow_stats", "fsi_set_partition",
     "fsi_rccl_unique_id", "fsi_set_rccl", "fsi_create_tuned", "fsi_get_tuning", "fsi_tuning_defaults", "fsi_tuning_from_env", "fsi_tuning_copy_out",
 )
 
@@ -170,6 +170,9 @@ def load_library(path: Optional[Path] = None):
     lib.fsi_band_phase_fetch.argtypes = [vp, i32, i32, i64, vp]
     lib.fsi_band_spi.argtypes = [vp, i32, vp, i64, i64, vp, vp]
     lib.fsi_band_spi_fetch.argtypes = [vp, i32, i32, vp]
+    lib.fsi_band_pod_gram.argtypes = [vp, i32, i32, vp]
+    lib.fsi_band_pod_modes.argtypes = [vp, i32, i32, vp]
+    lib.fsi_band_pod_fetch.argtypes = [vp, i32, i32, i64, vp]
     lib.fsi_band_cells.argtypes = [vp, i32, i64, vp, vp]
     lib.fsi_band_cell_rate.argtypes = [vp, i32, i32, i64, i64, i64, vp]
     lib.fsi_band_cell_rate_current.argtypes = [vp, i32, i32, i64, i64, i64, vp, vp, vp]
@@ -737,6 +740,39 @@ class HipBackend:
         n, ncomp = self._band.get(quantity, self.NO_BAND)["shape"]
         out = np.empty(n) if what == "nodes" else np.empty((n, ncomp)) if what == "rows" else np.empty((3, n, ncomp))
         self._check(self.lib.fsi_band_spi_fetch(self.ctx, self.BAND_QUANTITY[quantity], self.SPI_WHAT[what], _ptr(out)))
+        return out
+
+    POD_WHAT = {"gram": 0, "mean": 1, "mode": 2}
+
+    def hi_pass_pod_gram(self, quantity: str, series: str = "raw", weights=None) -> None:
+        """The Gram matrix of the proper orthogonal decomposition of the selected frames (fsi_band_pod_gram): ``series`` 'raw'
+        the selected raw frames, 'series' the filtered series or the fluctuation; ``weights`` one value >= 0 per node of the
+        session, or None for 1.  Replaces a decomposition that stood, its modes included; the matrix and the mean come from
+        ``hi_pass_pod_fetch``, the eigen step is ``hi_pass.pod_eig``."""
+        if series not in ("raw", "series"):
+            raise FsiError(1, "hi_pass_pod_gram: series must be 'raw' or 'series'")
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        n = self._band.get(quantity, self.NO_BAND)["shape"][0]
+        if w is not None and n and len(w) != n:
+            raise ValueError(f"{len(w)} weights, the session has {n} nodes")
+        self._check(self.lib.fsi_band_pod_gram(self.ctx, self.BAND_QUANTITY[quantity], self.RATE_SERIES[series], None if w is None else _ptr(w)))
+
+    def hi_pass_pod_modes(self, quantity: str, table) -> None:
+        """The modes ``Phi_m = sum_j table[j, m] y_j`` of the decomposition whose Gram matrix stands (fsi_band_pod_modes):
+        ``table`` (frames, nmodes), 1 <= nmodes <= 64, ``hi_pass.pod_table`` of the eigen step."""
+        T = np.ascontiguousarray(table, dtype=np.float64)
+        frames = self._band.get(quantity, self.NO_BAND)["selected"]      # a decomposition stands on the selection that stands
+        if T.ndim != 2 or (frames and T.shape[0] != frames):
+            raise ValueError(f"the table must be (frames, nmodes) = ({frames}, nmodes), got {T.shape}")
+        self._check(self.lib.fsi_band_pod_modes(self.ctx, self.BAND_QUANTITY[quantity], T.shape[1], _ptr(T) if T.size else None))
+
+    def hi_pass_pod_fetch(self, quantity: str, what: str, index: int = 0) -> np.ndarray:
+        """After ``hi_pass_pod_gram``: 'gram' the matrix (frames, frames), 'mean' the mean the frames were taken about
+        (n, ncomp); after ``hi_pass_pod_modes``: 'mode' ``index`` as (n, ncomp) (fsi_band_pod_fetch)."""
+        rec = self._band.get(quantity, self.NO_BAND)
+        frames = rec["selected"]
+        out = np.empty((frames, frames)) if what == "gram" else np.empty(rec["shape"])
+        self._check(self.lib.fsi_band_pod_fetch(self.ctx, self.BAND_QUANTITY[quantity], self.POD_WHAT[what], int(index), _ptr(out) if out.size else None))
         return out
 
     RATE_SERIES = {"raw": 0, "series": 1, "phase_mean": 2}

@@ -472,6 +472,13 @@ struct FsiCtx {
     int64_t spi_next = -1, spi_frames = 0;
     bool spi_closed = false;                 // spi_out holds the index of the slabs so far
     fsi::DevBuf<double> spi_acc, spi_mean, spi_out, spi_w, spi_tab;
+    // the proper orthogonal decomposition (fsi_band_pod_gram, fsi_pod.hip): pod_source is the series it was formed on (-1: none;
+    // FSI_RATE_RAW the selected raw frames, FSI_RATE_SERIES the series that stood), pod_frames the selected count, pod_nmodes
+    // the modes that stand (0: none).  pod_g [frames][frames]; pod_part the slabs' partial tiles; pod_mean [nrow]; pod_w [nrow]
+    // the weight of every row's node (empty: none); pod_tab [frames][nmodes]; pod_modes [nmodes][nrow].  Allocations of their own
+    int pod_source = -1;
+    int64_t pod_frames = 0, pod_nmodes = 0;
+    fsi::DevBuf<double> pod_g, pod_part, pod_mean, pod_w, pod_tab, pod_modes;
     // the mesh cells attached to a session of d or v (fsi_band_cells): per cell its ten P2 nodes as indices into the session's
     // nodes, local order, the gradients of its barycentric coordinates and one result (fsi_rate.hip); h_nodes: the P2 node of
     // every session node as fsi_band_begin was given it, -1 where the row is the mean of two nodes
@@ -490,19 +497,29 @@ struct FsiCtx {
     // The ladder.  The derived state forms a chain, and replacing one link drops everything after it:
     //   recorded frames -> selection -> series (filtered / fluctuation) -> amplitude
     //                                \-> spectral power index (of the selected RAW frames: survives a new series)
+    //                                \-> proper orthogonal decomposition (of the selected raw frames: survives a new series; of
+    //                                    the series: goes with it)
     //   cell list -> weights               (independent of the frames)
     // A call that replaces a link calls that link's function, once, and resets nothing by hand: fsi_band_sample and _import
     // frames_changed, _select selection_changed, _filter, _filter_next and _phase series_changed, _amplitude amplitude_changed,
     // _cells cell_list_changed.  keep_mean (fsi_band_phase): the mean frames are the caller's - it reuses them where they fit.
     void frames_changed() { sel_first = 0; sel_stride = 1; sel_count = -1; selection_changed(); }
-    void selection_changed() { filtered = false; spi_release(); series_changed(); }
-    void series_changed(bool keep_mean = false) { if (!keep_mean) phase_release(); amplitude_changed(-1); }
+    void selection_changed() { filtered = false; spi_release(); pod_release(); series_changed(); }
+    void series_changed(bool keep_mean = false) {
+      if (!keep_mean) phase_release();
+      if (pod_source == FSI_RATE_SERIES) pod_release();      // the decomposition was of the series that is replaced
+      amplitude_changed(-1);
+    }
     void amplitude_changed(int to) { window = to; acc_start = -1; }
     void cell_list_changed() { cell_weighted = false; }
     void phase_release() { phase_mean.release(); phase_period = 0; }
     void spi_release() {
       spi_acc.release(); spi_mean.release(); spi_out.release(); spi_w.release(); spi_tab.release();
       spi_next = -1; spi_frames = 0; spi_closed = false;
+    }
+    void pod_release() {
+      pod_g.release(); pod_part.release(); pod_mean.release(); pod_w.release(); pod_tab.release(); pod_modes.release();
+      pod_source = -1; pod_frames = pod_nmodes = 0;
     }
     void cells_release() {
       cell_conn.release(); cell_gl.release(); cell_out.release(); cell_vol.release(); cell_minj.release();

@@ -1,9 +1,10 @@
 // C-ABI of libvaspfsi.so (include/vaspfsi.h): the post-processing sessions that live on the resident state over a run -
 // hemodynamic indices (fsi_hemo_*), solid stress / strain (fsi_stress_*), band-pass filtered fields (fsi_band_*) and
-// spectrograms (fsi_spec_*).  The arithmetic runs in the kernels of fsi_hemo / fsi_stress / fsi_band / fsi_phase / fsi_rate / fsi_spec / fsi_spi .hip; the
+// spectrograms (fsi_spec_*).  The arithmetic runs in the kernels of fsi_hemo / fsi_stress / fsi_band / fsi_phase / fsi_rate / fsi_spec / fsi_spi / fsi_pod .hip; the
 // last two families record into one kind of history (FsiCtx::History) through the helpers below.
 #include "fsi_host.hpp"
 #include "fsi_phase.hpp"
+#include "fsi_pod.hpp"
 #include "fsi_rate.hpp"
 #include "fsi_room.hpp"
 #include "fsi_spec.hpp"
@@ -1056,6 +1057,121 @@ int fsi_band_spi_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, double* out)
     src = what == FSI_SPI_ROWS ? s->spi_out.p : s->spi_out.p + nrow;
     count = what == FSI_SPI_ROWS ? nrow : (size_t)s->nnode;
   }
+  HIPCHK(hipMemcpyAsync(out, src, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return FSI_OK;
+}
+
+int fsi_band_pod_gram(FsiCtx* ctx, int32_t quantity, int32_t series, const double* node_weights) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_pod_gram")) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_pod_gram");
+  if (!s) return FSI_ERR_INVALID;
+  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_pod_gram: " + why; return FSI_ERR_INVALID; };
+  if (tensor_quantity(quantity)) return refuse("a strain / stress session has no proper orthogonal decomposition: it is that of a vector or a scalar (d, v, p)");
+  if (series != FSI_RATE_RAW && series != FSI_RATE_SERIES) return refuse("series must be FSI_RATE_RAW or FSI_RATE_SERIES");
+  const int64_t n = band_frames(s);
+  if (n < 2) return refuse(std::to_string(n) + " selected frames, the decomposition needs at least 2 (fsi_band_select)");
+  if (n > POD_MAX_FRAMES) return refuse(std::to_string(n) + " selected frames, the decomposition takes at most " + std::to_string(POD_MAX_FRAMES));
+  if (series == FSI_RATE_SERIES && !s->filtered) return refuse("no filtered series (fsi_band_filter or fsi_band_phase first)");
+  const size_t nrow = (size_t)s->nrow;
+  std::vector<double> hw;                   // the weight of every row's node
+  if (node_weights) {
+    for (int64_t i = 0; i < s->nnode; ++i)
+      if (!(node_weights[i] >= 0.0) || !std::isfinite(node_weights[i])) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "the weight of node %lld is %g: a weight is >= 0 and finite", (long long)i, node_weights[i]);
+        return refuse(msg);
+      }
+    hw.resize(nrow);
+    for (size_t r = 0; r < nrow; ++r) hw[r] = node_weights[r / (size_t)s->ncomp];
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  // G, the slabs' partial tiles, the mean and the weights are allocations of the session's own, under the room rule of the begin
+  // calls; what a decomposition that stands holds is given back first - but only once the call is known to fit
+  const size_t npart = pod_part_count(s->nrow, n), nw = node_weights ? nrow : 0;
+  const double need = 8.0 * ((double)n * (double)n + (double)npart + (double)nrow + (double)nw);
+  const double back = 8.0 * (double)(s->pod_g.n + s->pod_part.n + s->pod_mean.n + s->pod_w.n + s->pod_tab.n + s->pod_modes.n);
+  FSICHK(room_for(ctx, "fsi_band_pod_gram", "the Gram matrix needs", need,
+                  counted(n, " x ", n, " entries, ") + counted(pod_slabs(s->nrow), " slabs x ", pod_pairs(n), " tiles of partial sums, ") +
+                      std::to_string(s->nrow) + " rows of means" + (node_weights ? " and weights" : ""), back));
+  s->pod_release();
+  struct Want { DevBuf<double>* buf; size_t count; };
+  for (const Want& w : {Want{&s->pod_g, (size_t)(n * n)}, Want{&s->pod_part, npart}, Want{&s->pod_mean, nrow}, Want{&s->pod_w, nw}}) {
+    const hipError_t e = w.buf->alloc(w.count);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      s->pod_release();
+      return refuse(std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+  }
+  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
+  const double* x = series == FSI_RATE_RAW ? s->hist.p + (size_t)s->sel_first * s->nrow : history_frame(s, true, 0);
+  const int64_t stride = series == FSI_RATE_RAW ? s->sel_stride : 1;
+  if (node_weights) HIPCHK(hipMemcpyAsync(s->pod_w.p, hw.data(), nrow * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  launch_spec_mean(ctx->stream, s->nrow, n, 0, 1, x, s->pod_mean.p, stride);
+  launch_pod_gram(ctx->stream, s->nrow, n, stride * s->nrow, x, s->pod_mean.p, node_weights ? s->pod_w.p : nullptr, s->pod_part.p);
+  launch_pod_gram_close(ctx->stream, s->nrow, n, s->pod_part.p, s->pod_g.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));                       // the host's weights are free again
+  s->pod_source = series;
+  s->pod_frames = n;
+  return FSI_OK;
+}
+
+int fsi_band_pod_modes(FsiCtx* ctx, int32_t quantity, int32_t nmodes, const double* table) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_pod_modes")) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_pod_modes");
+  if (!s) return FSI_ERR_INVALID;
+  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_pod_modes: " + why; return FSI_ERR_INVALID; };
+  if (s->pod_source < 0) return refuse("no Gram matrix (fsi_band_pod_gram first)");
+  if (nmodes < 1 || nmodes > POD_MAX_MODES || !table) return refuse("needs 1 <= nmodes <= " + std::to_string(POD_MAX_MODES) + " modes and their table [frames][nmodes]");
+  HIPCHK(hipSetDevice(ctx->device));
+  const int64_t n = s->pod_frames;
+  const size_t nrow = (size_t)s->nrow, ntab = (size_t)n * (size_t)nmodes, nmod = (size_t)nmodes * nrow;
+  if (s->pod_tab.n != ntab || s->pod_modes.n != nmod) {
+    FSICHK(room_for(ctx, "fsi_band_pod_modes", "the modes need", 8.0 * ((double)ntab + (double)nmod),
+                    counted(nmodes, " modes x ", s->nrow, " rows and their table of ") + std::to_string(n) + " frames",
+                    8.0 * (double)(s->pod_tab.n + s->pod_modes.n)));
+    s->pod_nmodes = 0;
+    hipError_t e = s->pod_tab.alloc(ntab);
+    if (e == hipSuccess) e = s->pod_modes.alloc(nmod);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      s->pod_tab.release(); s->pod_modes.release();
+      return refuse(std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+    HIPCHK(hipDeviceSynchronize());                                // the allocations' own fills are done
+  }
+  const bool raw = s->pod_source == FSI_RATE_RAW;
+  const double* x = raw ? s->hist.p + (size_t)s->sel_first * s->nrow : history_frame(s, true, 0);
+  s->pod_nmodes = 0;                // until the launch has run
+  HIPCHK(hipMemcpyAsync(s->pod_tab.p, table, ntab * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  launch_pod_modes(ctx->stream, s->nrow, n, (raw ? s->sel_stride : 1) * s->nrow, nmodes, x, s->pod_mean.p, s->pod_tab.p, s->pod_modes.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));                       // the caller's table is free again
+  s->pod_nmodes = nmodes;
+  return FSI_OK;
+}
+
+int fsi_band_pod_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t index, double* out) {
+  if (!ctx) return FSI_ERR_INVALID;
+  if (partitioned(ctx, "fsi_band_pod_fetch")) return FSI_ERR_INVALID;
+  auto* s = band_session(ctx, quantity, "fsi_band_pod_fetch");
+  if (!s) return FSI_ERR_INVALID;
+  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_pod_fetch: " + why; return FSI_ERR_INVALID; };
+  if (what < FSI_POD_GRAM || what > FSI_POD_MODE) return refuse("what must be FSI_POD_GRAM, FSI_POD_MEAN or FSI_POD_MODE");
+  if (!out) return refuse("out is NULL");
+  if (s->pod_source < 0) return refuse("no Gram matrix (fsi_band_pod_gram first)");
+  const double* src = what == FSI_POD_GRAM ? s->pod_g.p : s->pod_mean.p;
+  size_t count = what == FSI_POD_GRAM ? (size_t)(s->pod_frames * s->pod_frames) : (size_t)s->nrow;
+  if (what == FSI_POD_MODE) {
+    if (s->pod_nmodes < 1) return refuse("no modes (fsi_band_pod_modes first)");
+    if (index < 0 || index >= s->pod_nmodes) return refuse("mode " + std::to_string(index) + " out of range, " + std::to_string(s->pod_nmodes) + " modes stand");
+    src = s->pod_modes.p + (size_t)index * (size_t)s->nrow;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipMemcpyAsync(out, src, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return FSI_OK;

@@ -22,6 +22,10 @@ This module holds
   power at or above a cut-off frequency, per written node (csrc/fsi_spi.hip): its NumPy twin (``spi_sums``, ``spi_close``,
   ``spi_rows``, ``spi_nodes``, ``HostBandSession.spi`` / ``spi_fetch``), the cut-off's bin in exact rationals
   (``spi_low_bins``), the options with their refusals (``spi_options``) and its files (``HiPassRun._write_spi``);
+* the snapshot proper orthogonal decomposition of ``--hi-pass-pod`` - modes, energies and time coefficients of the selected frames
+  and of every band's filtered series (csrc/fsi_pod.hip): its NumPy twin (``pod_gram``, ``pod_modes``, ``HostBandSession.pod_gram`` /
+  ``pod_modes`` / ``pod_fetch``), the one eigen step of device and twin with its resolution floor (``pod_eig``, ``pod_table``), the
+  lumped volumes of the written nodes (``pod_volume_weights``), the options (``pod_options``) and the files (``HiPassRun._write_pod``);
 * the strain rate of a session's vector history on mesh cells, which ``--hi-pass-flow-metrics`` closes into dissipation and
   resolution metrics (``vasp_amd/flow_metrics.py``): the NumPy twin of csrc/fsi_rate.hip (``cell_rate``,
   ``HostBandSession.cells`` / ``cell_rate``; in the current configuration of the ALE mesh ``cell_rate_current`` /
@@ -371,6 +375,142 @@ def spi_nodes(x: np.ndarray, window, kc: int) -> np.ndarray:
     """``spi_node_ratio`` of frame-major x (n, nodes, ncomp): (nodes,)."""
     L2, X0, Q, _ = spi_sums(x, window, 0, int(kc))
     return spi_node_ratio(*spi_close(L2, X0, Q, len(x)))
+
+
+# ------------------------------------------------------------------------------------------------
+# snapshot proper orthogonal decomposition (csrc/fsi_pod.hip)
+# ------------------------------------------------------------------------------------------------
+
+POD_WHAT = ("gram", "mean", "mode")             # HipBackend.POD_WHAT, FSI_POD_*
+POD_SERIES = ("raw", "series")                  # FSI_RATE_RAW, FSI_RATE_SERIES
+POD_WEIGHTS = ("volume", "uniform")
+POD_SLAB = 6144                                 # rows of a slab of the Gram matrix's row sum (csrc/fsi_pod.hpp)
+POD_MAX_MODES = 64
+
+
+def _pod_weights(weights, x: np.ndarray):
+    """None, or the weight of every node shaped to multiply a frame of x (n, nodes, ...): refused if one is negative or not
+    finite, naming the first such node."""
+    if weights is None:
+        return None
+    w = np.array(weights, dtype=np.float64).reshape(-1)
+    if len(w) != x.shape[1]:
+        raise ValueError(f"{len(w)} weights, the frames have {x.shape[1]} nodes")
+    bad = np.flatnonzero(~(np.isfinite(w) & (w >= 0)))
+    if len(bad):
+        raise RuntimeError(f"hi-pass pod_gram: the weight of node {bad[0]} is {w[bad[0]]:g}: a weight is >= 0 and finite")
+    return w.reshape((len(w),) + (1,) * (x.ndim - 2))
+
+
+def pod_gram(x: np.ndarray, weights=None) -> Tuple[np.ndarray, np.ndarray]:
+    """``(G, mean)`` of frame-major x (n, nodes, ...): with m the ordered mean over the frames, ``y_j = x_j - m`` and
+    ``a_j = w y_j`` rounded once (``weights`` one value >= 0 per node; None: ``a_j`` is ``y_j`` itself),
+    ``G[i][j] = sum_r a_i[r] y_j[r]`` over the rows r (node, component).  The rows are added in slabs of ``POD_SLAB``, the
+    slabs in ascending order from +0.0; only ``i <= j`` is formed and mirrored, so G is symmetric bit for bit.  What
+    k_pod_gram and k_pod_gram_close form, but for the order inside a slab.  A sum over the rows: unlike the spectral power
+    index, where a NaN stays in its row, one NaN or inf poisons every entry."""
+    x = np.asarray(x, dtype=np.float64)
+    n = len(x)
+    w = _pod_weights(weights, x)
+    with np.errstate(invalid="ignore", over="ignore"):
+        mean = np.zeros(x.shape[1:])
+        for j in range(n):
+            mean = mean + x[j]
+        mean = mean / float(n)
+        y = x - mean[None]
+        a = y if w is None else w[None] * y
+        y, a = y.reshape(n, -1), a.reshape(n, -1)
+        G = np.zeros((n, n))
+        for r0 in range(0, y.shape[1], POD_SLAB):       # a copy: numpy hands a @ a.T of one array to another BLAS routine, with other bits
+            G = G + np.array(a[:, r0:r0 + POD_SLAB]) @ y[:, r0:r0 + POD_SLAB].T
+    G = np.triu(G)
+    return G + np.triu(G, 1).T, mean
+
+
+def pod_floor(rows: int, trace: float) -> float:
+    """``(rows + 2) * 2^-53 * trace``: below it an eigenvalue of the computed Gram matrix is rounding (``pod_eig``)."""
+    return (int(rows) + 2) * 2.0 ** -53 * float(trace)
+
+
+def pod_eig(G: np.ndarray, rows: int, modes: int) -> dict:
+    """The eigen step of the snapshot POD, the one of the device path and of the twin: ``G V = V diag(lam)`` by
+    ``numpy.linalg.eigh`` with lam descending and, in each column of V, the entry of largest magnitude positive (on a tie the
+    first such entry decides).  ``sigma = sqrt(lam)``, ``trace`` the ordered sum of G's diagonal from +0.0.
+
+    The resolution floor.  G is a sum over ``rows`` rows, ``G_ij = sum_r a_i[r] y_j[r]``.  With u = 2^-53 the computed entry is
+    off by at most ``(rows + 2) u sum_r |a_i[r] y_j[r]|`` (one rounding each for the product and for a = w y, rows for the
+    additions, to first order); by Cauchy-Schwarz in the w inner product that is ``<= (rows + 2) u sqrt(G_ii G_jj)``, so
+    ``||dG||_F <= (rows + 2) u sqrt(sum_ij G_ii G_jj) = (rows + 2) u trace``.  By Weyl's inequality every eigenvalue of the
+    computed G lies within ``||dG||_2 <= ||dG||_F`` of the exact one: mode m is **resolved** iff
+    ``lam_m > (rows + 2) * 2^-53 * trace`` - derived, not measured.  An unresolved mode is neither formed nor written.
+
+    Returns the leading ``min(modes, n)`` modes: ``lam``, ``V`` (n, M), ``sigma`` (0 where lam < 0), ``resolved``, ``fraction``
+    ``lam / trace``; ``trace``, ``floor``; ``spectrum`` every eigenvalue.  Raises on a G that is not finite: a Gram matrix sums
+    over the rows, so one recorded NaN or inf makes every entry non-finite."""
+    G = np.asarray(G, dtype=np.float64)
+    n = len(G)
+    if G.shape != (n, n) or n < 2:
+        raise ValueError(f"pod_eig: G must be (n, n) with n >= 2, got {G.shape}")
+    if not np.isfinite(G).all():
+        raise RuntimeError("hi-pass pod: the Gram matrix is not finite: a recorded value is NaN or inf (the matrix sums over the "
+                           "rows, so one such value reaches every entry)")
+    lam, V = np.linalg.eigh(G)
+    lam, V = lam[::-1].copy(), V[:, ::-1].copy()
+    for m in range(n):
+        if V[np.argmax(np.abs(V[:, m])), m] < 0:      # argmax: the first of equal magnitudes
+            V[:, m] = -V[:, m]
+    trace = 0.0
+    for k in range(n):
+        trace = trace + float(G[k, k])
+    M = max(1, min(int(modes), n))
+    floor = pod_floor(rows, trace)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        fraction = lam[:M] / trace if trace > 0 else np.zeros(M)
+    return dict(lam=lam[:M], V=V[:, :M], sigma=np.sqrt(np.maximum(lam[:M], 0.0)), resolved=lam[:M] > floor, fraction=fraction,
+                trace=trace, floor=floor, spectrum=lam)
+
+
+def pod_table(eig: dict) -> np.ndarray:
+    """``T[j][m] = V[j][m] / sigma_m`` for the resolved modes of ``pod_eig``, (n, resolved): ``Phi_m = sum_j T[j][m] y_j`` are
+    orthonormal in the w inner product, ``Phi_a^T W Phi_b = V_a^T G V_b / (sigma_a sigma_b)``."""
+    K = int(np.count_nonzero(eig["resolved"]))
+    return np.ascontiguousarray(eig["V"][:, :K] / eig["sigma"][None, :K])
+
+
+def pod_coefficients(eig: dict) -> np.ndarray:
+    """``a_m(j) = sigma_m V[j][m]``, (n, M): ``y_j = sum_m a_m(j) Phi_m``."""
+    return eig["V"] * eig["sigma"][None]
+
+
+def pod_modes(x: np.ndarray, mean: np.ndarray, T: np.ndarray) -> np.ndarray:
+    """``Phi_m = sum_j T[j][m] (x_j - mean)`` of frame-major x (n, ...): (modes, ...).  What k_pod_modes forms, but for the order
+    inside a sum."""
+    x, T = np.asarray(x, dtype=np.float64), np.asarray(T, dtype=np.float64)
+    n = len(x)
+    if T.ndim != 2 or T.shape[0] != n:
+        raise ValueError(f"the table must be (frames, modes) = ({n}, modes), got {T.shape}")
+    with np.errstate(invalid="ignore", over="ignore"):
+        y = (x - np.asarray(mean)[None]).reshape(n, -1)
+        return (T.T @ y).reshape((T.shape[1],) + x.shape[1:])
+
+
+def pod_volume_weights(mesh, save_deg: int) -> np.ndarray:
+    """One weight per written node (``output_nodes``), summed over the cells of the mesh - every quantity of ``--hi-pass`` is
+    written on all of it.  ``save_deg`` 2: a cell of volume |K| gives |K| / 32 to each vertex and 7 |K| / 48 to each edge
+    midpoint - the P1 lumping of the once-refined cell: a corner tetrahedron of volume |K| / 8 gives a quarter of it to its
+    vertex and to each of its three midpoints, and the inner octahedron of volume |K| / 2 is shared equally by its six
+    midpoints, so that the weights do not depend on the diagonal it is cut along; 4 / 32 + 6 * 7 / 48 = 1.  ``save_deg`` 1:
+    |K| / 4 to each vertex."""
+    xk = mesh.coords[mesh.tets]
+    vol = np.abs(np.einsum("ij,ij->i", xk[:, 1] - xk[:, 0], np.cross(xk[:, 2] - xk[:, 0], xk[:, 3] - xk[:, 0]))) / 6.0
+    if save_deg < 2:
+        w = np.zeros(mesh.num_vertices)
+        np.add.at(w, mesh.tets, (vol / 4.0)[:, None])
+        return w
+    w = np.zeros(mesh.num_nodes)
+    np.add.at(w, mesh.tet_nodes[:, :4], (vol / 32.0)[:, None])
+    np.add.at(w, mesh.tet_nodes[:, 4:], (7.0 * vol / 48.0)[:, None])
+    return w
 
 
 RATE_SERIES = ("raw", "series", "phase_mean")      # HipBackend.RATE_SERIES, FSI_RATE_*
@@ -759,18 +899,22 @@ class HostBandSession(HostHistory):
         self.frames_changed()
 
     # The ladder of FsiCtx::Band (csrc/fsi_context.hpp), function for function: recorded frames -> selection ->
-    # series -> amplitude, the spectral power index hanging on the selection.  A method that replaces a link calls that link's
-    # function, once, and resets nothing by hand.
+    # series -> amplitude, the spectral power index hanging on the selection, the proper orthogonal decomposition on the
+    # selection (of the raw frames) or on the series (of the series).  A method that replaces a link calls that link's function,
+    # once, and resets nothing by hand.
     def frames_changed(self) -> None:
         self.view = slice(None)
         self.selection_changed()
 
     def selection_changed(self) -> None:
         self.spi_state = None
+        self.pod_state = None
         self.series_changed(None)
 
     def series_changed(self, series, phase_mean=None, phase_period: int = 0) -> None:
         self.filtered, self.phase_mean, self.phase_period = series, phase_mean, phase_period
+        if self.pod_state is not None and self.pod_state["source"] == "series":
+            self.pod_state = None                   # the decomposition was of the series that is replaced
         self.amplitude_changed(None)
 
     def amplitude_changed(self, amp) -> None:
@@ -860,6 +1004,53 @@ class HostBandSession(HostHistory):
             return np.stack([state["L2"], state["X0"], state["Q"]])
         H, AC = spi_close(state["L2"], state["X0"], state["Q"], state["n"])
         return spi_ratio(H, AC) if what == "rows" else spi_node_ratio(H, AC)
+
+    def pod_gram(self, series: str = "raw", weights=None) -> None:
+        """The Gram matrix of the proper orthogonal decomposition of the selected frames: 'raw' the selected raw frames, 'series'
+        the filtered series or the fluctuation; ``weights`` one value >= 0 per node or None (``pod_gram``).  Replaces a
+        decomposition that stood, its modes included.  The twin of fsi_band_pod_gram: it refuses what that refuses."""
+        if self.ncomp not in (1, 3):
+            raise RuntimeError("hi-pass pod_gram: a strain / stress session has no proper orthogonal decomposition: it is that of a "
+                               "vector or a scalar (d, v, p)")
+        if series not in POD_SERIES:
+            raise RuntimeError(f"hi-pass pod_gram: series must be one of {', '.join(POD_SERIES)}")
+        n = len(range(*self.view.indices(len(self.raw))))
+        if n < 2:
+            raise RuntimeError(f"hi-pass pod_gram: {n} selected frames, the decomposition needs at least 2 (select)")
+        if series == "series" and self.filtered is None:
+            raise RuntimeError("hi-pass pod_gram: no filtered series (filter or phase first)")
+        x = self.selected() if series == "raw" else self.filtered
+        G, mean = pod_gram(x, weights)
+        self.pod_state = dict(source=series, G=G, mean=mean, n=n, modes=None)
+
+    def _pod_source(self) -> np.ndarray:
+        return self.selected() if self.pod_state["source"] == "raw" else self.filtered
+
+    def pod_modes(self, table) -> None:
+        """The modes ``Phi_m = sum_j table[j, m] y_j`` of the decomposition whose Gram matrix stands, ``table`` (frames, nmodes)
+        with 1 <= nmodes <= 64 (``pod_modes``).  The twin of fsi_band_pod_modes."""
+        if self.pod_state is None:
+            raise RuntimeError("hi-pass pod_modes: no Gram matrix (pod_gram first)")
+        T = np.asarray(table, dtype=np.float64)
+        if T.ndim != 2 or not 1 <= T.shape[1] <= POD_MAX_MODES:
+            raise RuntimeError(f"hi-pass pod_modes: needs 1 <= nmodes <= {POD_MAX_MODES} modes and their table (frames, nmodes)")
+        self.pod_state["modes"] = pod_modes(self._pod_source(), self.pod_state["mean"], T)
+
+    def pod_fetch(self, what: str, index: int = 0) -> np.ndarray:
+        """'gram' the matrix (frames, frames), 'mean' the mean the frames were taken about (n, ncomp), 'mode' ``index``
+        (n, ncomp).  The twin of fsi_band_pod_fetch."""
+        if what not in POD_WHAT:
+            raise RuntimeError(f"hi-pass pod_fetch: what must be one of {', '.join(POD_WHAT)}")
+        state = self.pod_state
+        if state is None:
+            raise RuntimeError("hi-pass pod_fetch: no Gram matrix (pod_gram first)")
+        if what != "mode":
+            return state["G"] if what == "gram" else state["mean"]
+        if state["modes"] is None:
+            raise RuntimeError("hi-pass pod_fetch: no modes (pod_modes first)")
+        if not 0 <= index < len(state["modes"]):
+            raise RuntimeError(f"hi-pass pod_fetch: mode {index} out of range, {len(state['modes'])} modes stand")
+        return state["modes"][index]
 
     def cells(self, conn, grad) -> np.ndarray:
         """Attach cells for ``cell_rate``: ``conn`` (n, 10) the cells' P2 nodes as indices into the session's nodes, local
@@ -1567,9 +1758,13 @@ def hi_pass_refusal(v: dict, world: int, backend_cls) -> str:
             spi_low_bins(frames, frame_spacing(v) * stride, spi["cutoff"])
         except SystemExit as e:
             return str(e)
+    pod = pod_options(v)
+    if pod is not None and frames < 2:
+        return f"--hi-pass-pod: the run {saves}, the decomposition needs at least 2"
     for lo, hi in bands(v):
-        # with a phase average or an index a band the frames do not suffice for is named when the files are written and left out
-        if frames < padlen_of(lo) + 1 and cycle is None and spi is None:
+        # with a phase average, an index or a decomposition a band the frames do not suffice for is named when the files are
+        # written and left out
+        if frames < padlen_of(lo) + 1 and cycle is None and spi is None and pod is None:
             return (f"--hi-pass: the run {saves}, the filter of band {lo:g} - {hi:g} Hz needs at least "
                     f"padlen + 1 = {padlen_of(lo) + 1}")
     if words:
@@ -1632,6 +1827,38 @@ def spi_options(v: dict) -> Optional[dict]:
     if window not in SPI_WINDOWS:
         raise SystemExit(f"--hi-pass-spi-window must be one of {', '.join(SPI_WINDOWS)}, got {window!r}")
     return dict(cutoff=float(cutoff), window=str(window))
+
+
+POD_STRIPS = ("--hi-pass-pod: the history goes through the session in strips of rows, on which no proper orthogonal decomposition is "
+              "formed (give it room with --history-memory, or fewer frames with --stride)")
+POD_COLUMNS = "mode, eigenvalue, energy fraction, cumulative fraction, resolved (0: below the floor, neither formed nor written)"
+
+
+def pod_options(v: dict) -> Optional[dict]:
+    """None without ``--hi-pass-pod``, else ``modes`` (``--hi-pass-pod-modes``, 10, from 1 to 64) and ``weights``
+    (``--hi-pass-pod-weights``, volume)."""
+    for key in ("hi_pass_pod_modes", "hi_pass_pod_weights"):
+        if v.get(key) is not None and not v.get("hi_pass_pod"):
+            raise SystemExit(f"--{key.replace('_', '-')} belongs to --hi-pass-pod")
+    if not v.get("hi_pass_pod"):
+        return None
+    modes = v.get("hi_pass_pod_modes")
+    modes = 10 if modes is None else modes
+    if isinstance(modes, bool) or not isinstance(modes, (int, np.integer)) or not 1 <= modes <= POD_MAX_MODES:
+        raise SystemExit(f"--hi-pass-pod-modes must be an integer from 1 to {POD_MAX_MODES}, got {modes!r}")
+    weights = v.get("hi_pass_pod_weights")
+    weights = "volume" if weights is None else weights
+    if weights not in POD_WEIGHTS:
+        raise SystemExit(f"--hi-pass-pod-weights must be one of {', '.join(POD_WEIGHTS)}, got {weights!r}")
+    return dict(modes=int(modes), weights=str(weights))
+
+
+def pod_energy_counts(spectrum: np.ndarray, trace: float) -> Tuple[int, int]:
+    """The number of leading modes whose eigenvalues, added in order, reach 90 % and 99 % of the trace (0, 0 for a trace of 0)."""
+    if not trace > 0:
+        return 0, 0
+    cum = np.cumsum(np.asarray(spectrum, dtype=np.float64)) / trace
+    return tuple(int(min(np.count_nonzero(cum < level) + 1, len(cum))) for level in (0.9, 0.99))
 
 
 def phase_cycle(v: dict) -> Optional[float]:
@@ -1721,6 +1948,8 @@ class HiPassRun(SessionRun):
         self.cycle_range = {key: ns.get(key) for key in ("hi_pass_start_cycle", "hi_pass_end_cycle")}
         self.spi = spi_options(ns)
         self.spi_lines: List[str] = []
+        self.pod = pod_options(ns)
+        self.pod_weights = pod_volume_weights(mesh, self.save_deg) if self.pod is not None and self.pod["weights"] == "volume" else None
         self.nodes = {q: output_nodes(mesh, self.save_deg, q) for q in self.quantities}
         if self.save_deg >= 2:
             geometry, topology = mesh.node_coords, refine_topology(mesh)
@@ -1743,6 +1972,8 @@ class HiPassRun(SessionRun):
                 raise SystemExit(VORTEX_STRIPS)
             if self.spi is not None:
                 raise SystemExit(SPI_STRIPS)
+            if self.pod is not None:
+                raise SystemExit(POD_STRIPS)
             i0, i1 = self.strip
             self.nodes = {q: tuple(None if a is None else a[i0:i1] for a in ab) for q, ab in self.nodes.items()}
         self.writer = HiPassWriter(Path(ns["results_folder"]) / "Visualization_hi_pass", geometry, topology)
@@ -1911,6 +2142,47 @@ class HiPassRun(SessionRun):
         out(f"Hi-pass {name}: spectral power index over {n} frames, {kc - 1} bins of {width:g} Hz below the cut-off ({window}), written; "
             f"mean {stats[1]:.6g}, maximum {stats[2]:.6g} at node {stats[3]}")
 
+    def _write_pod(self, out, session, q: str, n: int, series: str, stem: str) -> None:
+        """``--hi-pass-pod``: the snapshot proper orthogonal decomposition of the ``n`` selected raw frames (``series`` 'raw') or
+        of the series that stands ('series').  ``<stem>_modes``: one dataset per resolved mode, the xdmf time being the mode
+        number; ``<stem>.csv``: eigenvalue, energy fraction, cumulative fraction and resolved flag per mode, its header line
+        with the frames, the weights, the trace, the floor and the modes that 90 % and 99 % of the energy take;
+        ``<stem>_coefficients.csv``: the time and a_1 .. a_M.  The Gram matrix and the modes are the session's, the eigen step
+        between them is ``pod_eig`` on the host."""
+        ncomp, want = 1 if q == "p" else 3, self.pod["modes"]
+        if n < 2:
+            out(f"Hi-pass {stem}: {n} frames recorded, the decomposition needs at least 2: nothing written")
+            return
+        M = min(want, n - 1)
+        if M < want:
+            out(f"Hi-pass {stem}: --hi-pass-pod-modes {want} clipped to {M}, the {n} frames less one")
+        session.pod_gram(series, self.pod_weights)
+        try:
+            eig = pod_eig(np.asarray(session.pod_fetch("gram")), self.rows(q), M)
+        except RuntimeError as why:               # a NaN or an inf among the recorded values: named and left out
+            out(f"Hi-pass {stem}: {why}: no decomposition written")
+            return
+        T = pod_table(eig)
+        K = T.shape[1]
+        if K:
+            session.pod_modes(T)
+            self.writer.write_series(f"{stem}_modes", (session.pod_fetch("mode", m) for m in range(K)), K, ncomp, 1, 1)
+        k90, k99 = pod_energy_counts(eig["spectrum"], eig["trace"])
+        header = (f"# {POD_COLUMNS}; frames = {n}, weights = {self.pod['weights']}, trace = {eig['trace']!r}, floor = {eig['floor']!r}, "
+                  f"modes for 90 % = {k90}, modes for 99 % = {k99}")
+        lines, cum = [header], 0.0
+        for m in range(M):
+            cum = cum + float(eig["fraction"][m])
+            lines.append(f"{m + 1}, {float(eig['lam'][m])!r}, {float(eig['fraction'][m])!r}, {cum!r}, {int(eig['resolved'][m])}")
+        (self.writer.folder / f"{stem}.csv").write_text("\n".join(lines) + "\n")
+        table = np.empty((n, M + 1))
+        table[:, 0] = self.t0 + np.arange(n) * self.dt_files
+        table[:, 1:] = pod_coefficients(eig)
+        np.savetxt(self.writer.folder / f"{stem}_coefficients.csv", table, delimiter=",",
+                   header="time (s), " + ", ".join(f"a_{m + 1}" for m in range(M)))
+        out(f"Hi-pass {stem}: proper orthogonal decomposition of {n} frames ({self.pod['weights']} weights), {K} of {M} modes resolved and "
+            f"written; mode 1 carries {float(eig['fraction'][0]):.6g} of the energy, {k90} modes 90 %, {k99} modes 99 %")
+
     @staticmethod
     def apply(session, stages) -> None:
         """The session's filtered series after ``stages``: the first on the selected frames, every further one on the series."""
@@ -1945,8 +2217,12 @@ class HiPassRun(SessionRun):
                 self._write_filtered(out, session, viz, n, ncomp, rms)
                 if metrics is not None and len(stages) == 1:
                     metrics.bands[stages[0]["name"]] = metrics.rate(session, self.sessions.get("d"), "series")
+                if self.pod is not None and len(stages) == 1:      # of a band's filtered series; the chain of all bands is not decomposed
+                    self._write_pod(out, session, q, n, "series", f"{viz}_pod")
             if self.spi is not None:            # on the selection of the bands, before the phase average narrows it to whole cycles
                 self._write_spi(out, session, q, n)
+            if self.pod is not None:            # of the selected raw frames, on the selection of the bands
+                self._write_pod(out, session, q, n, "raw", f"{VIZ_TYPE[q]}_pod")
             if self.period is not None:
                 self._write_phase(out, session, q, first, n)
             if metrics is not None:

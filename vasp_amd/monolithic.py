@@ -94,6 +94,14 @@ def add_session_arguments(ap) -> None:
                     help="cut-off frequency of --hi-pass-spi, below the Nyquist frequency of the selected frames (default: 25)")
     ap.add_argument("--hi-pass-spi-window", dest="hi_pass_spi_window", choices=("boxcar", "hann"), default=None,
                     help="window of --hi-pass-spi (default: boxcar)")
+    ap.add_argument("--hi-pass-pod", dest="hi_pass_pod", action="store_const", const=True, default=None,
+                    help="also write, per quantity of --hi-pass, the snapshot proper orthogonal decomposition of the selected frames "
+                         "and of every band's filtered series: modes, energies and time coefficients, to "
+                         "<results>/Visualization_hi_pass/<field>[_<lo>_to_<hi>]_pod_modes.h5, _pod.csv and _pod_coefficients.csv")
+    ap.add_argument("--hi-pass-pod-modes", dest="hi_pass_pod_modes", type=int, default=None, metavar="M",
+                    help="modes of --hi-pass-pod, 1 to 64, clipped to the frames less one (default: 10)")
+    ap.add_argument("--hi-pass-pod-weights", dest="hi_pass_pod_weights", choices=("volume", "uniform"), default=None,
+                    help="inner product of --hi-pass-pod: the nodes' lumped volumes, or 1 for every node (default: volume)")
     ap.add_argument("--hi-pass-flow-metrics", dest="hi_pass_flow_metrics", action="store_const", const=True, default=None,
                     help="also write, from the velocity history of --hi-pass v at --save-deg 2, the flow and simulation metrics on "
                          "the fluid cells to <results>/FlowMetrics/: strain rate, viscous dissipation, l+ and t+; with "
@@ -334,6 +342,7 @@ SESSIONS = (("hemodynamics", "hemodynamics", "hemodynamics_refusal", "Hemodynami
 
 
 SPI_NEEDS_HI_PASS = "--hi-pass-spi needs --hi-pass with at least one of d, v, p: the index is formed on their recorded history"
+POD_NEEDS_HI_PASS = "--hi-pass-pod needs --hi-pass with at least one of d, v, p: the decomposition is that of their recorded history"
 
 
 def _session_part(module: str, name: str):
@@ -346,6 +355,8 @@ def _refuse_sessions(argv, backend_factory, world: int) -> None:
     args = parse(argv)
     if args.get("hi_pass_spi") and not args.get("hi_pass"):
         raise SystemExit(SPI_NEEDS_HI_PASS)
+    if args.get("hi_pass_pod") and not args.get("hi_pass"):
+        raise SystemExit(POD_NEEDS_HI_PASS)
     if not args.get("hi_pass"):
         from .vortex import refusal as vortex_refusal
         if vortex_refusal(args, []):

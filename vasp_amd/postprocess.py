@@ -58,7 +58,7 @@ from . import hi_pass, vortex
 from .fem import FormTerms
 from .frames import FrameSource, selected_indices
 from .mesh import FsiMesh
-from .monolithic import (SESSIONS, SPI_NEEDS_HI_PASS, _session_part, add_session_arguments, build_description, build_properties,
+from .monolithic import (POD_NEEDS_HI_PASS, SESSIONS, SPI_NEEDS_HI_PASS, _session_part, add_session_arguments, build_description, build_properties,
                          resolve_arguments)
 
 # what build_description and the sessions read of the run's parameters: without the JSON all of it must be given
@@ -159,6 +159,8 @@ def prepare(argv: Optional[List[str]] = None, backend_factory: Callable = defaul
         raise SystemExit(f"vasp_amd.postprocess runs on one rank only (WORLD_SIZE = {world})")
     if args.get("hi_pass_spi") and not args.get("hi_pass"):
         raise SystemExit(SPI_NEEDS_HI_PASS)
+    if args.get("hi_pass_pod") and not args.get("hi_pass"):
+        raise SystemExit(POD_NEEDS_HI_PASS)
     if not args.get("hi_pass") and vortex.refusal(args, []):
         raise SystemExit(vortex.refusal(args, []))
     if not any(args.get(key) for key, *_ in SESSIONS):
@@ -214,6 +216,8 @@ def prepare(argv: Optional[List[str]] = None, backend_factory: Callable = defaul
                 raise SystemExit(vortex.VORTEX_STRIPS)
             if v.get("hi_pass") and v.get("hi_pass_spi"):
                 raise SystemExit(hi_pass.SPI_STRIPS)
+            if v.get("hi_pass") and v.get("hi_pass_pod"):
+                raise SystemExit(hi_pass.POD_STRIPS)
             for j in band_jobs:
                 if j.units:
                     strips.plan_strips(j.units, j.rows_per_unit, len(indices) + 1, j.board_bytes(amplitude), limit, need,
@@ -266,6 +270,8 @@ def run(argv: Optional[List[str]] = None, backend_factory: Callable = default_ba
                 raise SystemExit(vortex.VORTEX_STRIPS)
             if ns.get("hi_pass") and ns.get("hi_pass_spi"):
                 raise SystemExit(hi_pass.SPI_STRIPS)
+            if ns.get("hi_pass") and ns.get("hi_pass_pod"):
+                raise SystemExit(hi_pass.POD_STRIPS)
     # the same for the spectrogram histories: where they do not fit beside the band-pass sessions of the first frame loop
     spec_run = None
     if ns.get("spectrogram") and indices:
