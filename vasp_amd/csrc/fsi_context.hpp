@@ -42,6 +42,7 @@ struct DevBuf {      // owns its device memory: freed with the buffer, never cop
     p = nullptr;
     n = 0;
   }
+  void swap(DevBuf& o) { T* op = o.p; const size_t on = o.n; o.p = p; o.n = n; p = op; n = on; }
 };
 
 // One colour of the multicolour ordering: `ngroups` groups of `group_rows` consecutive rows starting at `first_row`
@@ -459,78 +460,82 @@ struct FsiCtx {
     // sel_stride, ..., sel_count of them; sel_count < 0: every recorded frame.  A raw fetch keeps absolute frame indices.
     int64_t sel_first = 0, sel_stride = 1, sel_count = -1;
     int64_t board_node0 = -1;                // >= 0: a fetched amplitude's magnitudes also go to board[frame][board_node0 ..)
-    // > 0: the filtered series is the fluctuation about the phase average of this period (fsi_band_phase) and phase_mean
-    // holds the period's mean frames [phase_period][nrow], an allocation of their own; 0: no phase average
-    int64_t phase_period = 0;
-    fsi::DevBuf<double> acc, amp, mag, part_val, phase_mean;
+    fsi::DevBuf<double> acc, amp, mag, part_val;
     fsi::DevBuf<int64_t> part_idx;
-    // the spectral power index of the selected raw frames (fsi_band_spi, fsi_spi.hip): spi_next is the bin the next slab must
-    // start at (-1: no index is being formed), spi_frames the selected count it is formed on.  spi_acc [3][nrow]: per row
-    // the low bins' power, bin 0's power and the sum of squares; spi_mean [nrow]; spi_out [nrow + nnode]: the index per row,
-    // then per node; spi_w [frames] and spi_tab [2][frames * nb] the window and one slab's cos / sin columns.  Allocations of
-    // their own, at the first slab
-    int64_t spi_next = -1, spi_frames = 0;
-    bool spi_closed = false;                 // spi_out holds the index of the slabs so far
-    fsi::DevBuf<double> spi_acc, spi_mean, spi_out, spi_w, spi_tab;
-    // the proper orthogonal decomposition (fsi_band_pod_gram, fsi_pod.hip): pod_source is the series it was formed on (-1: none;
-    // FSI_RATE_RAW the selected raw frames, FSI_RATE_SERIES the series that stood), pod_frames the selected count, pod_nmodes
-    // the modes that stand (0: none).  pod_g [frames][frames]; pod_part the slabs' partial tiles; pod_mean [nrow]; pod_w [nrow]
-    // the weight of every row's node (empty: none); pod_tab [frames][nmodes]; pod_modes [nmodes][nrow].  Allocations of their own
-    int pod_source = -1;
-    int64_t pod_frames = 0, pod_nmodes = 0;
-    fsi::DevBuf<double> pod_g, pod_part, pod_mean, pod_w, pod_tab, pod_modes;
-    // the mesh cells attached to a session of d or v (fsi_band_cells): per cell its ten P2 nodes as indices into the session's
-    // nodes, local order, the gradients of its barycentric coordinates and one result (fsi_rate.hip); h_nodes: the P2 node of
-    // every session node as fsi_band_begin was given it, -1 where the row is the mean of two nodes
-    int64_t ncell = 0;
-    std::vector<int32_t> h_nodes;
-    fsi::DevBuf<int32_t> cell_conn;          // [ncell][10]
-    fsi::DevBuf<double> cell_gl, cell_out;   // [ncell][4][3], [ncell]
-    fsi::DevBuf<double> cell_vol, cell_minj; // [ncell] each: the two further results of fsi_band_cell_rate_current, at its first call
-    // fsi_band_cell_weights and fsi_band_cell_vortex (fsi_vortex.hip), at their first calls: one weight per cell (cell_weighted:
-    // they stand for the list that stands), the five results [5][ncell], and [5][ceil(ncell / 256)] partials followed by [5] sums
-    bool cell_weighted = false;
-    fsi::DevBuf<double> cell_weight, vortex_out, vortex_part;
-    // fsi_band_cell_vortex_current, at its first calls: the six means and the six numerator means [12][ncell], and
-    // [6][ceil(ncell / 256)] partials followed by [6] sums
-    fsi::DevBuf<double> vortex_cur_out, vortex_cur_part;
+    std::vector<int32_t> h_nodes;            // the P2 node of every session node as fsi_band_begin was given it, -1 where the row is the mean of two nodes
+    // The derived state, one group per link of the ladder below; a group's buffers are allocations of their own, at first use
+    // (room_for of a list of buffers, in fsi_sessions.hip), and its release() lists them all.
+    // period > 0: the filtered series is the fluctuation about the phase average of this period (fsi_band_phase) and mean holds
+    // the period's mean frames [period][nrow]; 0: no phase average
+    struct Phase {
+      int64_t period = 0;
+      fsi::DevBuf<double> mean;
+      void release() { mean.release(); period = 0; }
+    } phase;
+    // the spectral power index of the selected raw frames (fsi_band_spi, fsi_spi.hip): next is the bin the next slab must start
+    // at (-1: no index is being formed), frames the selected count it is formed on, closed: out holds the index of the slabs so
+    // far.  acc [3][nrow]: per row the low bins' power, bin 0's power and the sum of squares; mean [nrow]; out [nrow + nnode]:
+    // the index per row, then per node; w [frames] and tab [2][frames * nb] the window and one slab's cos / sin columns
+    struct Spi {
+      int64_t next = -1, frames = 0;
+      bool closed = false;
+      fsi::DevBuf<double> acc, mean, out, w, tab;
+      void release() { acc.release(); mean.release(); out.release(); w.release(); tab.release(); next = -1; frames = 0; closed = false; }
+    } spi;
+    // the proper orthogonal decomposition (fsi_band_pod_gram, fsi_pod.hip): source is the series it was formed on (-1: none;
+    // FSI_RATE_RAW the selected raw frames, FSI_RATE_SERIES the series that stood), frames the selected count, nmodes the modes
+    // that stand (0: none).  g [frames][frames]; part the slabs' partial tiles; mean [nrow]; w [nrow] the weight of every row's
+    // node (empty: none); tab [frames][nmodes]; modes [nmodes][nrow]
+    struct Pod {
+      int source = -1;
+      int64_t frames = 0, nmodes = 0;
+      fsi::DevBuf<double> g, part, mean, w, tab, modes;
+      void release() { g.release(); part.release(); mean.release(); w.release(); tab.release(); modes.release(); source = -1; frames = nmodes = 0; }
+    } pod;
+    // the n mesh cells attached to a session of d or v (fsi_band_cells): per cell its ten P2 nodes as indices into the session's
+    // nodes, local order, the gradients of its barycentric coordinates and one result (fsi_rate.hip); vol and minj: the two further
+    // results of fsi_band_cell_rate_current.  fsi_band_cell_weights: one weight per cell (weighted: they stand for the list that
+    // stands).  vortex[current] (fsi_vortex.hip), 0 fsi_band_cell_vortex, 1 fsi_band_cell_vortex_current: out the five results
+    // [5][n], or the six means and the six numerator means [12][n]; part [nf][ceil(n / 256)] partials followed by [nf] sums
+    struct Cells {
+      int64_t n = 0;
+      fsi::DevBuf<int32_t> conn;             // [n][10]
+      fsi::DevBuf<double> gl, out;           // [n][4][3], [n]
+      fsi::DevBuf<double> vol, minj;         // [n] each
+      bool weighted = false;
+      fsi::DevBuf<double> weight;
+      struct Vortex {
+        fsi::DevBuf<double> out, part;
+        void release() { out.release(); part.release(); }
+      } vortex[2];
+      void release() {
+        conn.release(); gl.release(); out.release(); vol.release(); minj.release(); weight.release(); vortex[0].release(); vortex[1].release();
+        weighted = false; n = 0;
+      }
+    } cells;
     // The ladder.  The derived state forms a chain, and replacing one link drops everything after it:
-    //   recorded frames -> selection -> series (filtered / fluctuation) -> amplitude
-    //                                \-> spectral power index (of the selected RAW frames: survives a new series)
-    //                                \-> proper orthogonal decomposition (of the selected raw frames: survives a new series; of
-    //                                    the series: goes with it)
-    //   cell list -> weights               (independent of the frames)
+    //   recorded frames -> selection -> series (filtered / fluctuation; phase) -> amplitude
+    //                                \-> spectral power index (spi: of the selected RAW frames, survives a new series)
+    //                                \-> proper orthogonal decomposition (pod: of the selected raw frames, survives a new series; of
+    //                                    the series, goes with it)
+    //   cell list (cells) -> weights       (independent of the frames)
     // A call that replaces a link calls that link's function, once, and resets nothing by hand: fsi_band_sample and _import
     // frames_changed, _select selection_changed, _filter, _filter_next and _phase series_changed, _amplitude amplitude_changed,
     // _cells cell_list_changed.  keep_mean (fsi_band_phase): the mean frames are the caller's - it reuses them where they fit.
     void frames_changed() { sel_first = 0; sel_stride = 1; sel_count = -1; selection_changed(); }
-    void selection_changed() { filtered = false; spi_release(); pod_release(); series_changed(); }
+    void selection_changed() { filtered = false; spi.release(); pod.release(); series_changed(); }
     void series_changed(bool keep_mean = false) {
-      if (!keep_mean) phase_release();
-      if (pod_source == FSI_RATE_SERIES) pod_release();      // the decomposition was of the series that is replaced
+      if (!keep_mean) phase.release();
+      if (pod.source == FSI_RATE_SERIES) pod.release();      // the decomposition was of the series that is replaced
       amplitude_changed(-1);
     }
     void amplitude_changed(int to) { window = to; acc_start = -1; }
-    void cell_list_changed() { cell_weighted = false; }
-    void phase_release() { phase_mean.release(); phase_period = 0; }
-    void spi_release() {
-      spi_acc.release(); spi_mean.release(); spi_out.release(); spi_w.release(); spi_tab.release();
-      spi_next = -1; spi_frames = 0; spi_closed = false;
-    }
-    void pod_release() {
-      pod_g.release(); pod_part.release(); pod_mean.release(); pod_w.release(); pod_tab.release(); pod_modes.release();
-      pod_source = -1; pod_frames = pod_nmodes = 0;
-    }
-    void cells_release() {
-      cell_conn.release(); cell_gl.release(); cell_out.release(); cell_vol.release(); cell_minj.release();
-      cell_weight.release(); vortex_out.release(); vortex_part.release(); vortex_cur_out.release(); vortex_cur_part.release();
-      cell_weighted = false; ncell = 0;
-    }
+    void cell_list_changed() { cells.weighted = false; }
     void release() {
       History::release();
       acc.release(); amp.release(); mag.release(); part_val.release(); part_idx.release();
       frames_changed();         // no frames: the whole chain goes
-      cells_release();
+      cells.release();
       h_nodes.clear();
       ncomp = 0;
       board_node0 = -1;

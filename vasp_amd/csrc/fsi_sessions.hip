@@ -2,6 +2,8 @@
 // hemodynamic indices (fsi_hemo_*), solid stress / strain (fsi_stress_*), band-pass filtered fields (fsi_band_*) and
 // spectrograms (fsi_spec_*).  The arithmetic runs in the kernels of fsi_hemo / fsi_stress / fsi_band / fsi_phase / fsi_rate / fsi_spec / fsi_spi / fsi_pod .hip; the
 // last two families record into one kind of history (FsiCtx::History) through the helpers below.
+#include <functional>
+
 #include "fsi_host.hpp"
 #include "fsi_phase.hpp"
 #include "fsi_pod.hpp"
@@ -21,6 +23,14 @@ HemoAcc hemo_acc(FsiCtx* ctx) {
   const int64_t nd = 3 * ctx->hemo.nf;
   return HemoAcc{a, a + 3 * nd, a + 6 * nd, a + 7 * nd};
 }
+
+// the refusal of entry point fn: ctx->err = "<fn>: <why>" and FSI_ERR_INVALID, or null for the helpers that return a pointer
+struct Refusal {
+  FsiCtx* ctx;
+  const char* fn;
+  int operator()(const std::string& why) const { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; }
+  std::nullptr_t null(const std::string& why) const { (*this)(why); return nullptr; }
+};
 
 // ---- the recorded history of a band-pass or a spectrogram session (FsiCtx::History) ---------------------------------------
 
@@ -43,6 +53,21 @@ FsiCtx::Band* band_session(FsiCtx* ctx, int32_t q, const char* fn) {
 FsiCtx::Spec* spec_session(FsiCtx* ctx, int32_t q, const char* fn) {
   return open_session(ctx, ctx->spec, q, fn, "spectrogram", q == FSI_SPEC_WSS ? "fsi_spec_begin_wss" : "fsi_spec_begin");
 }
+// the export and import calls refuse a partitioned context before anything else, as the begin calls do
+bool partitioned(FsiCtx* ctx, const char* fn) {
+  if (ctx->part) ctx->err = std::string(fn) + ": partitioned contexts are not supported";
+  return ctx->part;
+}
+// The prologue of a band-pass entry point: the open session of `quantity`, or null - with ctx->err set, unless ctx itself is
+// null.  The checks an entry point asks for come in this order, which is part of its interface: the context, WHOLE_CONTEXT
+// (a partitioned context is refused), VECTOR_ONLY (the quantity is d or v; vector_note: what the entry point adds to that
+// refusal), the session.  A refusal of a strain / stress session is worded by its entry point and stays there.
+enum BandEntry : unsigned { ANY_CONTEXT = 0, WHOLE_CONTEXT = 1, VECTOR_ONLY = 2 };
+FsiCtx::Band* band_entry(FsiCtx* ctx, const char* fn, int32_t quantity, unsigned what, const char* vector_note = "") {
+  if (!ctx || ((what & WHOLE_CONTEXT) && partitioned(ctx, fn))) return nullptr;
+  if ((what & VECTOR_ONLY) && quantity != 0 && quantity != 1) return Refusal{ctx, fn}.null(std::string("quantity must be 0 (d) or 1 (v)") + vector_note);
+  return band_session(ctx, quantity, fn);
+}
 // frames of the band-pass session's view of its history (fsi_band_select): those the filtered series and the amplitude have
 int64_t band_frames(const FsiCtx::Band* s) { return s->sel_count < 0 ? s->frames : s->sel_count; }
 
@@ -53,7 +78,7 @@ int64_t band_frames(const FsiCtx::Band* s) { return s->sel_count < 0 ? s->frames
 // FSI_SPEC_X) entry i is component comps[i] of nodes[i]: a list of rows, not of nodes.
 int row_lists(FsiCtx* ctx, const char* fn, int32_t quantity, int64_t n, const int32_t* nodes, const int32_t* nodes_b, int64_t capacity,
               int* mode, bool node_major, std::vector<int32_t>& i0, std::vector<int32_t>& i1, const int32_t* comps = nullptr) {
-  auto refuse = [&](const char* why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
+  const Refusal refuse{ctx, fn};
   if (quantity < 0 || quantity > 2) return refuse("quantity must be 0 (d), 1 (v) or 2 (p)");
   if (n <= 0 || !nodes || capacity <= 0) return refuse("needs n > 0 nodes and a capacity > 0 frames");
   if (*mode < FSI_SPEC_X || *mode > FSI_SPEC_MAG) return refuse("ncomp_mode must be FSI_SPEC_X .. FSI_SPEC_MAG");
@@ -109,13 +134,45 @@ std::string counted(int64_t a, const char* of_a, int64_t b, const char* of_b) { 
   return std::to_string(a) + of_a + std::to_string(b) + of_b;
 }
 
-// a further buffer of the cell list, at its first use, under the room rule
-int cell_buffer(FsiCtx* ctx, const char* fn, const char* subject, DevBuf<double>* buf, size_t count, const std::string& layout) {
-  if (buf->n == count) return FSI_OK;
-  FSICHK(room_for(ctx, fn, subject, 8.0 * (double)count, layout));
-  HIPCHK(buf->alloc(count));
-  HIPCHK(hipDeviceSynchronize());                                  // the allocation's own fill is done
+// A buffer a session wants at `count` elements: it stands if it has them (grow: or more), and is allocated otherwise.  given_back:
+// what it holds now is free again before the allocation; false: it counts as taken (the buffers that go with a cell list)
+struct Want {
+  std::function<hipError_t()> alloc;
+  double need, held;
+  bool stands;
+  template <class T>
+  Want(DevBuf<T>* b, size_t count, bool grow = false, bool given_back = true)
+      : alloc([=] { return b->alloc(count); }), need((double)(count * sizeof(T))), held(given_back ? (double)(b->n * sizeof(T)) : 0.0),
+        stands(grow ? b->n >= count : b->n == count) {}
+};
+// The room rule for the buffers a session allocates at first use: those of `wants` that stand are kept, the rest pass one room
+// check together (subject, layout: its refusal) and are allocated, their fills done when the call returns.  replace: none is kept,
+// and once the call is known to fit release() gives back what they hold first.  A hipMalloc that fails behind the room check:
+// release() puts the group back to nothing, and the call is refused.
+template <size_t N, class Release>
+int room_for(FsiCtx* ctx, const char* fn, const char* subject, const std::string& layout, const Want (&wants)[N], Release release, bool replace = false) {
+  double need = 0.0, back = 0.0;
+  for (const Want& w : wants)
+    if (replace || !w.stands) { need += w.need; back += w.held; }
+  if (need == 0.0) return FSI_OK;
+  FSICHK(room_for(ctx, fn, subject, need, layout, back));
+  if (replace) release();
+  for (const Want& w : wants)
+    if (replace || !w.stands) {
+      const hipError_t e = w.alloc();
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        release();
+        return Refusal{ctx, fn}(std::string("hipMalloc: ") + hipGetErrorString(e));
+      }
+    }
+  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
   return FSI_OK;
+}
+// a further buffer of the cell list, at its first use
+int cell_buffer(FsiCtx* ctx, const char* fn, const char* subject, DevBuf<double>* buf, size_t count, const std::string& layout) {
+  const Want wants[] = {{buf, count, false, false}};
+  return room_for(ctx, fn, subject, layout, wants, [&] { buf->release(); });
 }
 
 // What a band-pass session of `rows` rows and `capacity` frames takes (fsi_band_room, the begin calls): the history, the
@@ -198,15 +255,20 @@ int filter_coef(FsiCtx* ctx, const char* fn, const char* ntaps_range, int32_t nt
   return FSI_OK;
 }
 
-// scipy.signal.filtfilt of every row into work, over the frames recorded so far or, with count >= 0, over the count frames
-// first, first + stride, ... of them
+// Frames of nrow doubles each on the device: frame k starts at x + k * frame_stride (in doubles; a launch that takes its stride
+// in frames gets frame_stride / nrow)
+struct SeriesView {
+  const double* x;
+  int64_t frames, frame_stride;
+};
+
+// scipy.signal.filtfilt of every row into work, over the frames of the raw history that v holds
 int history_filter(FsiCtx* ctx, FsiCtx::History* s, const char* fn, const char* ntaps_range, int32_t ntaps, const double* b,
-                   const double* a, const double* zi, int32_t padlen, int64_t first = 0, int64_t stride = 1, int64_t count = -1) {
-  const int64_t frames = count < 0 ? s->frames : count;
+                   const double* a, const double* zi, int32_t padlen, const SeriesView& v) {
   BandCoef c;
-  FSICHK(filter_coef(ctx, fn, ntaps_range, ntaps, b, a, zi, padlen, frames, &c));
+  FSICHK(filter_coef(ctx, fn, ntaps_range, ntaps, b, a, zi, padlen, v.frames, &c));
   HIPCHK(hipSetDevice(ctx->device));
-  launch_band_filter(ctx->stream, s->nrow, frames, padlen, c, s->hist.p + (size_t)first * s->nrow, stride, s->work.p);
+  launch_band_filter(ctx->stream, s->nrow, v.frames, padlen, c, v.x, v.frame_stride / s->nrow, s->work.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));
   s->padlen = padlen;
@@ -219,53 +281,54 @@ const double* history_frame(const FsiCtx::History* s, bool filtered, int64_t k) 
   return (filtered ? s->work.p + (size_t)s->padlen * s->nrow : s->hist.p) + (size_t)k * s->nrow;
 }
 
-// the export and import calls refuse a partitioned context before anything else, as the begin calls do
-bool partitioned(FsiCtx* ctx, const char* fn) {
-  if (ctx->part) ctx->err = std::string(fn) + ": partitioned contexts are not supported";
-  return ctx->part;
+// Where a series of a band-pass session lies, and nowhere else.  The raw frames of session g at the selection of session s (g = s:
+// its own selected frames; g the session of d: the geometry that goes with them)
+SeriesView raw_view(const FsiCtx::Band* g, const FsiCtx::Band* s) {
+  return SeriesView{g->hist.p + (size_t)s->sel_first * g->nrow, band_frames(s), s->sel_stride * g->nrow};
 }
+// the series `series` (FSI_RATE_*) of s: the selected raw frames, the filtered series or fluctuation without its guard frames, the
+// period's mean frames.  That the series stands is the caller's check, under its own name.
+SeriesView series_view(const FsiCtx::Band* s, int32_t series) {
+  if (series == FSI_RATE_RAW) return raw_view(s, s);
+  if (series == FSI_RATE_SERIES) return SeriesView{history_frame(s, true, 0), band_frames(s), s->nrow};
+  return SeriesView{s->phase.mean.p, s->phase.period, s->nrow};
+}
+// frames first, first + step, ... of a view
+SeriesView taken(const SeriesView& v, int64_t first, int64_t step, int64_t count) { return SeriesView{v.x + first * v.frame_stride, count, step * v.frame_stride}; }
 
 // The frames of a series of a cell session, for fsi_band_cell_rate, fsi_band_cell_rate_current, fsi_band_cell_vortex and
-// fsi_band_cell_vortex_current, in two steps with the entry point's own checks between them.  First the session of `quantity` with a cell list and the series
-// `series` (FSI_RATE_*) in place, or null with ctx->err set (ctx null: nothing to set it on).
+// fsi_band_cell_vortex_current, in two steps with the entry point's own checks between them.  First the session of `quantity` with a
+// cell list and the series `series` (FSI_RATE_*) in place, or null with ctx->err set (ctx null: nothing to set it on).
 FsiCtx::Band* cell_series_session(FsiCtx* ctx, const char* fn, int32_t quantity, int32_t series) {
-  if (!ctx || partitioned(ctx, fn)) return nullptr;
-  auto refuse = [&](const char* why) -> FsiCtx::Band* { ctx->err = std::string(fn) + ": " + why; return nullptr; };
-  if (quantity != 0 && quantity != 1) return refuse("quantity must be 0 (d) or 1 (v)");
-  auto* s = band_session(ctx, quantity, fn);
+  auto* s = band_entry(ctx, fn, quantity, WHOLE_CONTEXT | VECTOR_ONLY);
   if (!s) return nullptr;
-  if (series < FSI_RATE_RAW || series > FSI_RATE_PHASE_MEAN) return refuse("series must be FSI_RATE_RAW, FSI_RATE_SERIES or FSI_RATE_PHASE_MEAN");
-  if (s->ncell < 1) return refuse("no cell list (fsi_band_cells first)");
-  if (series == FSI_RATE_SERIES && !s->filtered) return refuse("no filtered series (fsi_band_filter or fsi_band_phase first)");
-  if (series == FSI_RATE_PHASE_MEAN && (s->phase_period < 1 || !s->filtered)) return refuse("no phase average (fsi_band_phase first)");
+  const Refusal refuse{ctx, fn};
+  if (series < FSI_RATE_RAW || series > FSI_RATE_PHASE_MEAN) return refuse.null("series must be FSI_RATE_RAW, FSI_RATE_SERIES or FSI_RATE_PHASE_MEAN");
+  if (s->cells.n < 1) return refuse.null("no cell list (fsi_band_cells first)");
+  if (series == FSI_RATE_SERIES && !s->filtered) return refuse.null("no filtered series (fsi_band_filter or fsi_band_phase first)");
+  if (series == FSI_RATE_PHASE_MEAN && (s->phase.period < 1 || !s->filtered)) return refuse.null("no phase average (fsi_band_phase first)");
   return s;
 }
-// Then frames first, first + step, ... (`count` of them) of that series, which must hold them all.  *x: frame `first`;
-// *frame_stride: the doubles from one taken frame to the next.  The series is frames of nrow doubles: the raw history from the
-// selection's first frame, sel_stride recorded frames apart; the filtered series; the phase means.
-int cell_series_frames(FsiCtx* ctx, const char* fn, const FsiCtx::Band* s, int32_t series, int64_t first, int64_t step, int64_t count,
-                       const double** x, int64_t* frame_stride) {
-  auto refuse = [&](const std::string& why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
-  const int64_t frames = series == FSI_RATE_PHASE_MEAN ? s->phase_period : band_frames(s);
+// Then *x: frames first, first + step, ... (`count` of them) of that series, which must hold them all
+int cell_series_frames(FsiCtx* ctx, const char* fn, const FsiCtx::Band* s, int32_t series, int64_t first, int64_t step, int64_t count, SeriesView* x) {
+  const Refusal refuse{ctx, fn};
+  const SeriesView v = series_view(s, series);
   if (step < 1 || count < 1) return refuse("needs step >= 1 and count >= 1, got step = " + std::to_string(step) + ", count = " + std::to_string(count));
-  if (first < 0 || first >= frames || count - 1 > (frames - 1 - first) / step)
+  if (first < 0 || first >= v.frames || count - 1 > (v.frames - 1 - first) / step)
     return refuse("frames " + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(step) + ", ... (" + std::to_string(count) +
-                  " of them) fall outside the series of " + std::to_string(frames) + " frames");
-  const double* x0 = series == FSI_RATE_RAW ? s->hist.p + (size_t)s->sel_first * s->nrow : series == FSI_RATE_SERIES ? history_frame(s, true, 0) : s->phase_mean.p;
-  const int64_t stride = series == FSI_RATE_RAW ? s->sel_stride : 1;
-  *x = x0 + (size_t)(first * stride) * s->nrow;
-  *frame_stride = step * stride * s->nrow;
+                  " of them) fall outside the series of " + std::to_string(v.frames) + " frames");
+  *x = taken(v, first, step, count);
   return FSI_OK;
 }
 
 // The geometry of the current configuration x = X + d, for fsi_band_cell_rate_current and fsi_band_cell_vortex_current: the
 // session of d, which must be on the same nodes and hold the same recorded frames as the session s of the quantity, and for the
 // phase mean a phase average of the same period over the same selection - or the refusal, under the entry point's name.  *geo:
-// the d frame that goes with frame `first` of the series; *geo_stride: the doubles from one taken frame to the next.  The
-// frames are the raw history of d at the quantity's selection, also under its filtered series, or d's phase means.
-int cell_geometry_frames(FsiCtx* ctx, const char* fn, const FsiCtx::Band* s, int32_t series, int64_t first, int64_t step, const double** geo,
-                         int64_t* geo_stride) {
-  auto refuse = [&](const std::string& why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
+// the d frames that go with the `count` taken frames of the series: the raw history of d at the quantity's selection, also under
+// its filtered series, or d's phase means.
+int cell_geometry_frames(FsiCtx* ctx, const char* fn, const FsiCtx::Band* s, int32_t series, int64_t first, int64_t step, int64_t count,
+                         SeriesView* geo) {
+  const Refusal refuse{ctx, fn};
   const FsiCtx::Band* g = &ctx->band[0];
   if (!g->open) return refuse("no session of quantity 0 (d): the current configuration is x = X + d (fsi_band_begin of d first)");
   if (g->h_nodes != s->h_nodes) return refuse("the session of d lists other nodes than the session of the quantity: both must be opened on the same node list");
@@ -273,18 +336,15 @@ int cell_geometry_frames(FsiCtx* ctx, const char* fn, const FsiCtx::Band* s, int
     return refuse("the session of d has recorded " + std::to_string(g->frames) + " frames, the session of the quantity " + std::to_string(s->frames) +
                   ": both must hold the same frames");
   if (series == FSI_RATE_PHASE_MEAN) {
-    if (g->phase_period < 1 || !g->filtered) return refuse("the session of d has no phase average (fsi_band_phase of d first)");
-    if (g->phase_period != s->phase_period)
-      return refuse("the phase average of d has a period of " + std::to_string(g->phase_period) + " frames, that of the quantity " +
-                    std::to_string(s->phase_period));
+    if (g->phase.period < 1 || !g->filtered) return refuse("the session of d has no phase average (fsi_band_phase of d first)");
+    if (g->phase.period != s->phase.period)
+      return refuse("the phase average of d has a period of " + std::to_string(g->phase.period) + " frames, that of the quantity " +
+                    std::to_string(s->phase.period));
     if (g->sel_first != s->sel_first || g->sel_stride != s->sel_stride || band_frames(g) != band_frames(s))
       return refuse("the phase average of d is over another selection of frames than that of the quantity (fsi_band_select and fsi_band_phase of d "
                     "as of the quantity)");
   }
-  const double* g0 = series == FSI_RATE_PHASE_MEAN ? g->phase_mean.p : g->hist.p + (size_t)s->sel_first * g->nrow;
-  const int64_t stride = series == FSI_RATE_PHASE_MEAN ? 1 : s->sel_stride;
-  *geo = g0 + (size_t)(first * stride) * g->nrow;
-  *geo_stride = step * stride * g->nrow;
+  *geo = taken(series == FSI_RATE_PHASE_MEAN ? series_view(g, series) : raw_view(g, s), first, step, count);
   return FSI_OK;
 }
 
@@ -295,28 +355,27 @@ int cell_vortex(FsiCtx* ctx, const char* fn, bool current, int32_t quantity, int
                 double* cells_out, double* sums_out) {
   auto* s = cell_series_session(ctx, fn, quantity, series);
   if (!s) return FSI_ERR_INVALID;
-  auto refuse = [&](const char* why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
+  const Refusal refuse{ctx, fn};
   if (!cells_out && !sums_out) return refuse("cells_out and sums_out are both NULL");
-  if (sums_out && !s->cell_weighted) return refuse("sums_out without weights (fsi_band_cell_weights first)");
-  const double *x = nullptr, *geo = nullptr;
-  int64_t frame_stride = 0, geo_stride = 0;
-  FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x, &frame_stride));
-  if (current) FSICHK(cell_geometry_frames(ctx, fn, s, series, first, step, &geo, &geo_stride));
+  if (sums_out && !s->cells.weighted) return refuse("sums_out without weights (fsi_band_cell_weights first)");
+  SeriesView x{}, geo{};
+  FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x));
+  if (current) FSICHK(cell_geometry_frames(ctx, fn, s, series, first, step, count, &geo));
   HIPCHK(hipSetDevice(ctx->device));
+  auto& c = s->cells;
   const int nf = current ? FSI_VORTEX_CURRENT_FIELDS : FSI_VORTEX_FIELDS;
-  const size_t n = (size_t)s->ncell, nblock = (size_t)cell_wsum_blocks(s->ncell), rows = current ? 2 * nf : nf;
-  DevBuf<double>&out = current ? s->vortex_cur_out : s->vortex_out, &part = current ? s->vortex_cur_part : s->vortex_part;
-  FSICHK(cell_buffer(ctx, fn, current ? "the twelve results need" : "the five results need", &out, rows * n,
-                     counted(s->ncell, " cells x ", 8 * rows, "")));
+  const size_t n = (size_t)c.n, nblock = (size_t)cell_wsum_blocks(c.n), rows = current ? 2 * nf : nf;
+  DevBuf<double>&out = c.vortex[current].out, &part = c.vortex[current].part;
+  FSICHK(cell_buffer(ctx, fn, current ? "the twelve results need" : "the five results need", &out, rows * n, counted(c.n, " cells x ", 8 * rows, "")));
   if (sums_out)
     FSICHK(cell_buffer(ctx, fn, "the partial sums need", &part, nf * (nblock + 1), counted(nblock, " groups of 256 cells and the sums x ", 8 * nf, "")));
-  if (current) launch_cell_vortex_current(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, geo, geo_stride, count, out.p);
-  else launch_cell_vortex(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, count, out.p);
+  if (current) launch_cell_vortex_current(ctx->stream, c.n, c.conn.p, c.gl.p, x.x, x.frame_stride, geo.x, geo.frame_stride, count, out.p);
+  else launch_cell_vortex(ctx->stream, c.n, c.conn.p, c.gl.p, x.x, x.frame_stride, count, out.p);
   HIPCHK(hipGetLastError());
   if (cells_out) HIPCHK(hipMemcpyAsync(cells_out, out.p, nf * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (sums_out) {      // current: the bulk sums are those of the numerators, rows 6 .. 11
     double* sums = part.p + nf * nblock;
-    launch_cell_wsum(ctx->stream, s->ncell, nf, s->cell_weight.p, out.p + (rows - nf) * n, part.p, sums);
+    launch_cell_wsum(ctx->stream, c.n, nf, c.weight.p, out.p + (rows - nf) * n, part.p, sums);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(sums_out, sums, nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   }
@@ -824,7 +883,7 @@ int fsi_band_begin(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* node
 
 int fsi_band_begin_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* cells, int64_t capacity) {
   if (!ctx) return FSI_ERR_INVALID;
-  auto refuse = [&](const char* why) { ctx->err = std::string("fsi_band_begin_cells: ") + why; return FSI_ERR_INVALID; };
+  const Refusal refuse{ctx, "fsi_band_begin_cells"};
   if (!tensor_quantity(quantity)) return refuse("quantity must be 3 (strain) or 4 (stress)");
   if (n <= 0 || !cells || capacity <= 0) return refuse("needs n > 0 cells and a capacity > 0 frames");
   if (ctx->part) return refuse("partitioned contexts are not supported");
@@ -842,8 +901,7 @@ int fsi_band_begin_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t
 }
 
 int fsi_band_sample(FsiCtx* ctx, int32_t quantity) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_sample");
+  auto* s = band_entry(ctx, "fsi_band_sample", quantity, ANY_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
   if (tensor_quantity(quantity))
     FSICHK(history_append(ctx, s, "fsi_band_sample", "fsi_band_begin_cells", [&](double* dst) {
@@ -856,8 +914,7 @@ int fsi_band_sample(FsiCtx* ctx, int32_t quantity) {
 }
 
 int fsi_band_select(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count, int64_t stride) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_select");
+  auto* s = band_entry(ctx, "fsi_band_select", quantity, ANY_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
   const bool fits = stride >= 1 && first >= 0 && first < s->frames && (count == -1 || (count >= 1 && count - 1 <= (s->frames - 1 - first) / stride));
   if (!fits) {
@@ -873,17 +930,15 @@ int fsi_band_select(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count,
 }
 
 int fsi_band_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* b, const double* a, const double* zi, int32_t padlen) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_filter");
+  auto* s = band_entry(ctx, "fsi_band_filter", quantity, ANY_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
-  FSICHK(history_filter(ctx, s, "fsi_band_filter", "2 .. 11", ntaps, b, a, zi, padlen, s->sel_first, s->sel_stride, band_frames(s)));
+  FSICHK(history_filter(ctx, s, "fsi_band_filter", "2 .. 11", ntaps, b, a, zi, padlen, raw_view(s, s)));
   s->series_changed();          // the filtered series is the band again: no phase average
   return FSI_OK;
 }
 
 int fsi_band_filter_next(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* b, const double* a, const double* zi, int32_t padlen) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_filter_next");
+  auto* s = band_entry(ctx, "fsi_band_filter_next", quantity, ANY_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
   BandCoef c;
   FSICHK(filter_coef(ctx, "fsi_band_filter_next", "2 .. 11", ntaps, b, a, zi, padlen, band_frames(s), &c));
@@ -903,11 +958,10 @@ int fsi_band_filter_next(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const dou
 }
 
 int fsi_band_phase(FsiCtx* ctx, int32_t quantity, int64_t period) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_phase")) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_phase");
+  auto* s = band_entry(ctx, "fsi_band_phase", quantity, WHOLE_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
-  const int64_t n = band_frames(s);
+  const SeriesView v = raw_view(s, s);
+  const int64_t n = v.frames;
   if (period < 1 || n < 1 || n % period != 0) {
     ctx->err = "fsi_band_phase: period = " + std::to_string(period) + " frames, " + std::to_string(n) +
                " selected frames: needs period >= 1 and a selected count that is a positive multiple of it (fsi_band_select)";
@@ -915,51 +969,35 @@ int fsi_band_phase(FsiCtx* ctx, int32_t quantity, int64_t period) {
   }
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  // the period's mean frames are an allocation of their own, under the room rule; the mean frames of an earlier call are
-  // given back first where they are of another size, and serve again otherwise
-  const size_t count = (size_t)period * (size_t)s->nrow;
-  if (s->phase_mean.n != count) {
-    FSICHK(room_for(ctx, "fsi_band_phase", "the phase means need", 8.0 * (double)period * (double)s->nrow,
-                    counted(s->nrow, " rows x ", period, " frames"), 8.0 * (double)s->phase_mean.n));
-    s->phase_period = 0;
-    HIPCHK(s->phase_mean.alloc(count));
-    HIPCHK(hipDeviceSynchronize());                                // the allocation's own fill is done
-  }
-  launch_phase_decompose(ctx->stream, s->nrow, period, n / period, s->hist.p + (size_t)s->sel_first * s->nrow, s->sel_stride,
-                         s->phase_mean.p, s->work.p);
+  // the period's mean frames: those of an earlier call are given back first where they are of another size, and serve again otherwise
+  const Want wants[] = {{&s->phase.mean, (size_t)period * (size_t)s->nrow}};
+  const bool fresh = !wants[0].stands;
+  FSICHK(room_for(ctx, "fsi_band_phase", "the phase means need", counted(s->nrow, " rows x ", period, " frames"), wants, [&] { s->phase.release(); }));
+  if (fresh) s->phase.period = 0;
+  launch_phase_decompose(ctx->stream, s->nrow, period, n / period, v.x, v.frame_stride / s->nrow, s->phase.mean.p, s->work.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));
   s->series_changed(true);      // the mean frames are this call's own
   s->padlen = 0;                // the fluctuation is the filtered series, without guard frames
   s->filtered = true;
-  s->phase_period = period;
+  s->phase.period = period;
   return FSI_OK;
 }
 
 int fsi_band_phase_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, double* out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_phase_fetch")) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_phase_fetch");
+  auto* s = band_entry(ctx, "fsi_band_phase_fetch", quantity, WHOLE_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
-  if (what < FSI_PHASE_MEAN || what > FSI_PHASE_ENERGY_TIME_MEAN) {
-    ctx->err = "fsi_band_phase_fetch: what must be FSI_PHASE_MEAN .. FSI_PHASE_ENERGY_TIME_MEAN";
-    return FSI_ERR_INVALID;
-  }
-  if (!out) { ctx->err = "fsi_band_phase_fetch: out is NULL"; return FSI_ERR_INVALID; }
-  if (s->phase_period < 1 || !s->filtered) { ctx->err = "fsi_band_phase_fetch: no phase average (fsi_band_phase first)"; return FSI_ERR_INVALID; }
-  if (what != FSI_PHASE_MEAN && s->ncomp != 1 && s->ncomp != 3) {
-    ctx->err = "fsi_band_phase_fetch: a strain / stress session has no energy: 0.5 |u'|^2 is that of a vector or a scalar";
-    return FSI_ERR_INVALID;
-  }
-  const int64_t P = s->phase_period, n = band_frames(s);
+  const Refusal refuse{ctx, "fsi_band_phase_fetch"};
+  if (what < FSI_PHASE_MEAN || what > FSI_PHASE_ENERGY_TIME_MEAN) return refuse("what must be FSI_PHASE_MEAN .. FSI_PHASE_ENERGY_TIME_MEAN");
+  if (!out) return refuse("out is NULL");
+  if (s->phase.period < 1 || !s->filtered) return refuse("no phase average (fsi_band_phase first)");
+  if (what != FSI_PHASE_MEAN && s->ncomp != 1 && s->ncomp != 3) return refuse("a strain / stress session has no energy: 0.5 |u'|^2 is that of a vector or a scalar");
+  const int64_t P = s->phase.period, n = band_frames(s);
   const int64_t limit = what == FSI_PHASE_ENERGY ? n : what == FSI_PHASE_ENERGY_TIME_MEAN ? 1 : P;
-  if (frame < 0 || frame >= limit) {
-    ctx->err = "fsi_band_phase_fetch: frame " + std::to_string(frame) + " out of range, this kind has " + std::to_string(limit);
-    return FSI_ERR_INVALID;
-  }
+  if (frame < 0 || frame >= limit) return refuse("frame " + std::to_string(frame) + " out of range, this kind has " + std::to_string(limit));
   HIPCHK(hipSetDevice(ctx->device));
   const double* src = nullptr;
-  if (what == FSI_PHASE_MEAN) src = s->phase_mean.p + (size_t)frame * s->nrow;
+  if (what == FSI_PHASE_MEAN) src = s->phase.mean.p + (size_t)frame * s->nrow;
   else {
     const double* f = history_frame(s, true, frame);
     if (what == FSI_PHASE_ENERGY) launch_phase_energy(ctx->stream, s->nnode, s->ncomp, f, 0, 1, false, s->mag.p);
@@ -974,87 +1012,66 @@ int fsi_band_phase_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t fr
 }
 
 int fsi_band_spi(FsiCtx* ctx, int32_t quantity, const double* window, int64_t bin0, int64_t nb, const double* Ct, const double* St) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_spi")) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_spi");
+  auto* s = band_entry(ctx, "fsi_band_spi", quantity, WHOLE_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
-  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_spi: " + why; return FSI_ERR_INVALID; };
+  const Refusal refuse{ctx, "fsi_band_spi"};
   if (tensor_quantity(quantity)) return refuse("a strain / stress session has no spectral power index: it is that of a vector or a scalar (d, v, p)");
-  const int64_t n = band_frames(s);
+  const SeriesView v = raw_view(s, s);
+  const int64_t n = v.frames, stride = v.frame_stride / s->nrow;
+  auto& spi = s->spi;
   if (n < 2) return refuse(std::to_string(n) + " selected frames, the index needs at least 2 (fsi_band_select)");
   if (nb < 1 || bin0 < 0 || !Ct || !St) return refuse("needs bin0 >= 0, nb >= 1 bins and their cos / sin columns Ct, St");
   if (nb - 1 > (n - 1) / 2 - bin0)
     return refuse("bins " + std::to_string(bin0) + " .. " + std::to_string(bin0 + nb - 1) + " of " + std::to_string(n) + " selected frames: a low bin lies below the Nyquist "
                   "frequency, at most bin " + std::to_string((n - 1) / 2));
-  if (bin0 > 0 && (s->spi_next != bin0 || s->spi_frames != n))
+  if (bin0 > 0 && (spi.next != bin0 || spi.frames != n))
     return refuse("a slab out of order: bin0 = " + std::to_string(bin0) + ", " +
-                  (s->spi_next < 0 ? std::string("no slab stands before it (bin0 = 0 first)") : "the next slab starts at bin " + std::to_string(s->spi_next)));
+                  (spi.next < 0 ? std::string("no slab stands before it (bin0 = 0 first)") : "the next slab starts at bin " + std::to_string(spi.next)));
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  // the working buffers are allocations of the session's own, under the room rule of the begin calls; those of an earlier call
-  // are kept where they have the size (they count as taken otherwise)
-  const size_t nrow = (size_t)s->nrow, tab = 2 * (size_t)n * (size_t)nb;
-  struct Want { DevBuf<double>* buf; size_t count; bool grow; };      // grow: a larger buffer serves as well
-  const Want wants[] = {{&s->spi_acc, 3 * nrow, false}, {&s->spi_mean, nrow, false}, {&s->spi_out, nrow + (size_t)s->nnode, false},
-                        {&s->spi_w, (size_t)n, false}, {&s->spi_tab, tab, true}};
-  auto stands = [](const Want& w) { return w.grow ? w.buf->n >= w.count : w.buf->n == w.count; };
-  double need_d = 0.0, back = 0.0;
-  for (const Want& w : wants)
-    if (!stands(w)) { need_d += 8.0 * (double)w.count; back += 8.0 * (double)w.buf->n; }
-  if (bin0 > 0 && (!stands(wants[0]) || !stands(wants[1]) || !stands(wants[2]) || !stands(wants[3])))
+  // the working buffers: those of an earlier call are kept where they have the size, and a larger table serves as well
+  const size_t nrow = (size_t)s->nrow;
+  const Want wants[] = {{&spi.acc, 3 * nrow}, {&spi.mean, nrow}, {&spi.out, nrow + (size_t)s->nnode}, {&spi.w, (size_t)n}, {&spi.tab, 2 * (size_t)n * (size_t)nb, true}};
+  if (bin0 > 0 && !(wants[0].stands && wants[1].stands && wants[2].stands && wants[3].stands))
     return refuse("a slab out of order: the sums of the slabs before it are gone (bin0 = 0 first)");
-  if (need_d > 0.0) {
-    FSICHK(room_for(ctx, "fsi_band_spi", "the sums and tables need", need_d,
-                    std::to_string(s->nrow) + " rows, " + counted(n, " frames x ", nb, " bins of cos and sin"), back));
-    for (const Want& w : wants)
-      if (!stands(w)) {
-        const hipError_t e = w.buf->alloc(w.count);
-        if (e != hipSuccess) {
-          (void)hipGetLastError();
-          s->spi_release();       // the session stands as before any index was asked for
-          return refuse(std::string("hipMalloc: ") + hipGetErrorString(e));
-        }
-      }
-    HIPCHK(hipDeviceSynchronize());                                // the allocations' own fills are done
-  }
-  const double* hist = s->hist.p + (size_t)s->sel_first * s->nrow;
-  double *l2 = s->spi_acc.p, *x0 = l2 + nrow, *q = x0 + nrow, *Cd = s->spi_tab.p, *Sd = Cd + (size_t)n * (size_t)nb;
-  s->spi_next = -1;               // until this slab has run
-  s->spi_closed = false;
+  FSICHK(room_for(ctx, "fsi_band_spi", "the sums and tables need", std::to_string(s->nrow) + " rows, " + counted(n, " frames x ", nb, " bins of cos and sin"),
+                         wants, [&] { spi.release(); }));      // the session stands as before any index was asked for
+  double *l2 = spi.acc.p, *x0 = l2 + nrow, *q = x0 + nrow, *Cd = spi.tab.p, *Sd = Cd + (size_t)n * (size_t)nb;
+  spi.next = -1;                  // until this slab has run
+  spi.closed = false;
   if (bin0 == 0) {
-    if (window) HIPCHK(hipMemcpyAsync(s->spi_w.p, window, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    launch_spec_mean(ctx->stream, s->nrow, n, 0, 1, hist, s->spi_mean.p, s->sel_stride);
+    if (window) HIPCHK(hipMemcpyAsync(spi.w.p, window, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    launch_spec_mean(ctx->stream, s->nrow, n, 0, 1, v.x, spi.mean.p, stride);
   }
   HIPCHK(hipMemcpyAsync(Cd, Ct, (size_t)n * (size_t)nb * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(Sd, St, (size_t)n * (size_t)nb * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  launch_spi_power(ctx->stream, s->nrow, n, s->sel_stride, nb, bin0, hist, s->spi_mean.p, window ? s->spi_w.p : nullptr, Cd, Sd, l2, x0, q);
+  launch_spi_power(ctx->stream, s->nrow, n, stride, nb, bin0, v.x, spi.mean.p, window ? spi.w.p : nullptr, Cd, Sd, l2, x0, q);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));                       // the caller's tables are free again
-  s->spi_next = bin0 + nb;
-  s->spi_frames = n;
+  spi.next = bin0 + nb;
+  spi.frames = n;
   return FSI_OK;
 }
 
 int fsi_band_spi_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, double* out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_spi_fetch")) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_spi_fetch");
+  auto* s = band_entry(ctx, "fsi_band_spi_fetch", quantity, WHOLE_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
-  if (what < FSI_SPI_ROWS || what > FSI_SPI_SUMS) { ctx->err = "fsi_band_spi_fetch: what must be FSI_SPI_ROWS, FSI_SPI_NODES or FSI_SPI_SUMS"; return FSI_ERR_INVALID; }
-  if (!out) { ctx->err = "fsi_band_spi_fetch: out is NULL"; return FSI_ERR_INVALID; }
-  if (s->spi_next < 1) { ctx->err = "fsi_band_spi_fetch: no spectral power index (fsi_band_spi first)"; return FSI_ERR_INVALID; }
+  const Refusal refuse{ctx, "fsi_band_spi_fetch"};
+  auto& spi = s->spi;
+  if (what < FSI_SPI_ROWS || what > FSI_SPI_SUMS) return refuse("what must be FSI_SPI_ROWS, FSI_SPI_NODES or FSI_SPI_SUMS");
+  if (!out) return refuse("out is NULL");
+  if (spi.next < 1) return refuse("no spectral power index (fsi_band_spi first)");
   HIPCHK(hipSetDevice(ctx->device));
   const size_t nrow = (size_t)s->nrow;
-  const double* src = s->spi_acc.p;
+  const double* src = spi.acc.p;
   size_t count = 3 * nrow;
   if (what != FSI_SPI_SUMS) {
-    if (!s->spi_closed) {
-      launch_spi_close(ctx->stream, s->nnode, s->ncomp, s->spi_frames, s->spi_acc.p, s->spi_acc.p + nrow, s->spi_acc.p + 2 * nrow, s->spi_out.p,
-                       s->spi_out.p + nrow);
+    if (!spi.closed) {
+      launch_spi_close(ctx->stream, s->nnode, s->ncomp, spi.frames, spi.acc.p, spi.acc.p + nrow, spi.acc.p + 2 * nrow, spi.out.p, spi.out.p + nrow);
       HIPCHK(hipGetLastError());
-      s->spi_closed = true;
+      spi.closed = true;
     }
-    src = what == FSI_SPI_ROWS ? s->spi_out.p : s->spi_out.p + nrow;
+    src = what == FSI_SPI_ROWS ? spi.out.p : spi.out.p + nrow;
     count = what == FSI_SPI_ROWS ? nrow : (size_t)s->nnode;
   }
   HIPCHK(hipMemcpyAsync(out, src, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -1063,11 +1080,9 @@ int fsi_band_spi_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, double* out)
 }
 
 int fsi_band_pod_gram(FsiCtx* ctx, int32_t quantity, int32_t series, const double* node_weights) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_pod_gram")) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_pod_gram");
+  auto* s = band_entry(ctx, "fsi_band_pod_gram", quantity, WHOLE_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
-  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_pod_gram: " + why; return FSI_ERR_INVALID; };
+  const Refusal refuse{ctx, "fsi_band_pod_gram"};
   if (tensor_quantity(quantity)) return refuse("a strain / stress session has no proper orthogonal decomposition: it is that of a vector or a scalar (d, v, p)");
   if (series != FSI_RATE_RAW && series != FSI_RATE_SERIES) return refuse("series must be FSI_RATE_RAW or FSI_RATE_SERIES");
   const int64_t n = band_frames(s);
@@ -1087,89 +1102,64 @@ int fsi_band_pod_gram(FsiCtx* ctx, int32_t quantity, int32_t series, const doubl
     for (size_t r = 0; r < nrow; ++r) hw[r] = node_weights[r / (size_t)s->ncomp];
   }
   HIPCHK(hipSetDevice(ctx->device));
-  // G, the slabs' partial tiles, the mean and the weights are allocations of the session's own, under the room rule of the begin
-  // calls; what a decomposition that stands holds is given back first - but only once the call is known to fit
-  const size_t npart = pod_part_count(s->nrow, n), nw = node_weights ? nrow : 0;
-  const double need = 8.0 * ((double)n * (double)n + (double)npart + (double)nrow + (double)nw);
-  const double back = 8.0 * (double)(s->pod_g.n + s->pod_part.n + s->pod_mean.n + s->pod_w.n + s->pod_tab.n + s->pod_modes.n);
-  FSICHK(room_for(ctx, "fsi_band_pod_gram", "the Gram matrix needs", need,
-                  counted(n, " x ", n, " entries, ") + counted(pod_slabs(s->nrow), " slabs x ", pod_pairs(n), " tiles of partial sums, ") +
-                      std::to_string(s->nrow) + " rows of means" + (node_weights ? " and weights" : ""), back));
-  s->pod_release();
-  struct Want { DevBuf<double>* buf; size_t count; };
-  for (const Want& w : {Want{&s->pod_g, (size_t)(n * n)}, Want{&s->pod_part, npart}, Want{&s->pod_mean, nrow}, Want{&s->pod_w, nw}}) {
-    const hipError_t e = w.buf->alloc(w.count);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      s->pod_release();
-      return refuse(std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-  }
-  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
-  const double* x = series == FSI_RATE_RAW ? s->hist.p + (size_t)s->sel_first * s->nrow : history_frame(s, true, 0);
-  const int64_t stride = series == FSI_RATE_RAW ? s->sel_stride : 1;
-  if (node_weights) HIPCHK(hipMemcpyAsync(s->pod_w.p, hw.data(), nrow * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  launch_spec_mean(ctx->stream, s->nrow, n, 0, 1, x, s->pod_mean.p, stride);
-  launch_pod_gram(ctx->stream, s->nrow, n, stride * s->nrow, x, s->pod_mean.p, node_weights ? s->pod_w.p : nullptr, s->pod_part.p);
-  launch_pod_gram_close(ctx->stream, s->nrow, n, s->pod_part.p, s->pod_g.p);
+  // G, the slabs' partial tiles, the mean and the weights; what a decomposition that stands holds, its table and modes included,
+  // is given back first - but only once the call is known to fit
+  auto& pod = s->pod;
+  const Want wants[] = {{&pod.g, (size_t)(n * n)}, {&pod.part, pod_part_count(s->nrow, n)}, {&pod.mean, nrow}, {&pod.w, node_weights ? nrow : 0},
+                        {&pod.tab, 0}, {&pod.modes, 0}};
+  FSICHK(room_for(ctx, "fsi_band_pod_gram", "the Gram matrix needs",
+                         counted(n, " x ", n, " entries, ") + counted(pod_slabs(s->nrow), " slabs x ", pod_pairs(n), " tiles of partial sums, ") +
+                             std::to_string(s->nrow) + " rows of means" + (node_weights ? " and weights" : ""),
+                         wants, [&] { pod.release(); }, true));
+  const SeriesView v = series_view(s, series);
+  if (node_weights) HIPCHK(hipMemcpyAsync(pod.w.p, hw.data(), nrow * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  launch_spec_mean(ctx->stream, s->nrow, n, 0, 1, v.x, pod.mean.p, v.frame_stride / s->nrow);
+  launch_pod_gram(ctx->stream, s->nrow, n, v.frame_stride, v.x, pod.mean.p, node_weights ? pod.w.p : nullptr, pod.part.p);
+  launch_pod_gram_close(ctx->stream, s->nrow, n, pod.part.p, pod.g.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));                       // the host's weights are free again
-  s->pod_source = series;
-  s->pod_frames = n;
+  pod.source = series;
+  pod.frames = n;
   return FSI_OK;
 }
 
 int fsi_band_pod_modes(FsiCtx* ctx, int32_t quantity, int32_t nmodes, const double* table) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_pod_modes")) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_pod_modes");
+  auto* s = band_entry(ctx, "fsi_band_pod_modes", quantity, WHOLE_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
-  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_pod_modes: " + why; return FSI_ERR_INVALID; };
-  if (s->pod_source < 0) return refuse("no Gram matrix (fsi_band_pod_gram first)");
+  const Refusal refuse{ctx, "fsi_band_pod_modes"};
+  auto& pod = s->pod;
+  if (pod.source < 0) return refuse("no Gram matrix (fsi_band_pod_gram first)");
   if (nmodes < 1 || nmodes > POD_MAX_MODES || !table) return refuse("needs 1 <= nmodes <= " + std::to_string(POD_MAX_MODES) + " modes and their table [frames][nmodes]");
   HIPCHK(hipSetDevice(ctx->device));
-  const int64_t n = s->pod_frames;
-  const size_t nrow = (size_t)s->nrow, ntab = (size_t)n * (size_t)nmodes, nmod = (size_t)nmodes * nrow;
-  if (s->pod_tab.n != ntab || s->pod_modes.n != nmod) {
-    FSICHK(room_for(ctx, "fsi_band_pod_modes", "the modes need", 8.0 * ((double)ntab + (double)nmod),
-                    counted(nmodes, " modes x ", s->nrow, " rows and their table of ") + std::to_string(n) + " frames",
-                    8.0 * (double)(s->pod_tab.n + s->pod_modes.n)));
-    s->pod_nmodes = 0;
-    hipError_t e = s->pod_tab.alloc(ntab);
-    if (e == hipSuccess) e = s->pod_modes.alloc(nmod);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      s->pod_tab.release(); s->pod_modes.release();
-      return refuse(std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-    HIPCHK(hipDeviceSynchronize());                                // the allocations' own fills are done
-  }
-  const bool raw = s->pod_source == FSI_RATE_RAW;
-  const double* x = raw ? s->hist.p + (size_t)s->sel_first * s->nrow : history_frame(s, true, 0);
-  s->pod_nmodes = 0;                // until the launch has run
-  HIPCHK(hipMemcpyAsync(s->pod_tab.p, table, ntab * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  launch_pod_modes(ctx->stream, s->nrow, n, (raw ? s->sel_stride : 1) * s->nrow, nmodes, x, s->pod_mean.p, s->pod_tab.p, s->pod_modes.p);
+  const int64_t n = pod.frames;
+  const size_t ntab = (size_t)n * (size_t)nmodes;
+  const Want wants[] = {{&pod.tab, ntab}, {&pod.modes, (size_t)nmodes * (size_t)s->nrow}};      // one count of modes: both stand or neither
+  FSICHK(room_for(ctx, "fsi_band_pod_modes", "the modes need", counted(nmodes, " modes x ", s->nrow, " rows and their table of ") + std::to_string(n) + " frames",
+                         wants, [&] { pod.tab.release(); pod.modes.release(); pod.nmodes = 0; }));
+  const SeriesView v = series_view(s, pod.source);
+  pod.nmodes = 0;                   // until the launch has run
+  HIPCHK(hipMemcpyAsync(pod.tab.p, table, ntab * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  launch_pod_modes(ctx->stream, s->nrow, n, v.frame_stride, nmodes, v.x, pod.mean.p, pod.tab.p, pod.modes.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));                       // the caller's table is free again
-  s->pod_nmodes = nmodes;
+  pod.nmodes = nmodes;
   return FSI_OK;
 }
 
 int fsi_band_pod_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t index, double* out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_pod_fetch")) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_pod_fetch");
+  auto* s = band_entry(ctx, "fsi_band_pod_fetch", quantity, WHOLE_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
-  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_pod_fetch: " + why; return FSI_ERR_INVALID; };
+  const Refusal refuse{ctx, "fsi_band_pod_fetch"};
+  const auto& pod = s->pod;
   if (what < FSI_POD_GRAM || what > FSI_POD_MODE) return refuse("what must be FSI_POD_GRAM, FSI_POD_MEAN or FSI_POD_MODE");
   if (!out) return refuse("out is NULL");
-  if (s->pod_source < 0) return refuse("no Gram matrix (fsi_band_pod_gram first)");
-  const double* src = what == FSI_POD_GRAM ? s->pod_g.p : s->pod_mean.p;
-  size_t count = what == FSI_POD_GRAM ? (size_t)(s->pod_frames * s->pod_frames) : (size_t)s->nrow;
+  if (pod.source < 0) return refuse("no Gram matrix (fsi_band_pod_gram first)");
+  const double* src = what == FSI_POD_GRAM ? pod.g.p : pod.mean.p;
+  size_t count = what == FSI_POD_GRAM ? (size_t)(pod.frames * pod.frames) : (size_t)s->nrow;
   if (what == FSI_POD_MODE) {
-    if (s->pod_nmodes < 1) return refuse("no modes (fsi_band_pod_modes first)");
-    if (index < 0 || index >= s->pod_nmodes) return refuse("mode " + std::to_string(index) + " out of range, " + std::to_string(s->pod_nmodes) + " modes stand");
-    src = s->pod_modes.p + (size_t)index * (size_t)s->nrow;
+    if (pod.nmodes < 1) return refuse("no modes (fsi_band_pod_modes first)");
+    if (index < 0 || index >= pod.nmodes) return refuse("mode " + std::to_string(index) + " out of range, " + std::to_string(pod.nmodes) + " modes stand");
+    src = pod.modes.p + (size_t)index * (size_t)s->nrow;
   }
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipMemcpyAsync(out, src, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -1178,12 +1168,9 @@ int fsi_band_pod_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t inde
 }
 
 int fsi_band_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* cells, double* grad_out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_cells")) return FSI_ERR_INVALID;
-  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_cells: " + why; return FSI_ERR_INVALID; };
-  if (quantity != 0 && quantity != 1) return refuse("quantity must be 0 (d) or 1 (v): the strain rate is that of a vector on P2 nodes");
-  auto* s = band_session(ctx, quantity, "fsi_band_cells");
+  auto* s = band_entry(ctx, "fsi_band_cells", quantity, WHOLE_CONTEXT | VECTOR_ONLY, ": the strain rate is that of a vector on P2 nodes");
   if (!s) return FSI_ERR_INVALID;
+  const Refusal refuse{ctx, "fsi_band_cells"};
   if (n <= 0 || !cells) return refuse("needs n > 0 cells");
   for (int64_t i = 0; i < n; ++i)
     if (cells[i] < 0 || cells[i] >= ctx->C) return refuse("cell out of range");
@@ -1201,26 +1188,23 @@ int fsi_band_cells(FsiCtx* ctx, int32_t quantity, int64_t n, const int32_t* cell
       conn[10 * i + a] = at[node];
     }
   HIPCHK(hipSetDevice(ctx->device));
-  // the list that stands is given back only once the new one is in place, so it counts as taken
-  FSICHK(room_for(ctx, "fsi_band_cells", "the cell list needs", 144.0 * (double)n,
-                  std::to_string(n) + " cells x 144: ten nodes, twelve gradients, one result"));
-  DevBuf<int32_t> d_conn, d_cells;
+  // the list that stands is given back only once the new one is in place, so it counts as taken: the new one is made beside it
+  DevBuf<int32_t> d_conn, d_cells;                                 // d_cells: live for this call
   DevBuf<double> d_gl, d_out;
-  HIPCHK(d_conn.alloc((size_t)n * 10));
+  const Want wants[] = {{&d_conn, (size_t)n * 10}, {&d_gl, (size_t)n * 12}, {&d_out, (size_t)n}};
+  FSICHK(room_for(ctx, "fsi_band_cells", "the cell list needs", std::to_string(n) + " cells x 144: ten nodes, twelve gradients, one result", wants, [] {}));
   HIPCHK(d_cells.alloc((size_t)n));
-  HIPCHK(d_gl.alloc((size_t)n * 12));
-  HIPCHK(d_out.alloc((size_t)n));
-  HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
+  HIPCHK(hipDeviceSynchronize());                                  // the allocation's own fill is done
   HIPCHK(hipMemcpyAsync(d_conn.p, conn.data(), conn.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(d_cells.p, cells, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   launch_cell_gradients(ctx->stream, n, ctx->geom.p, d_cells.p, d_gl.p);
   HIPCHK(hipGetLastError());
   if (grad_out) HIPCHK(hipMemcpyAsync(grad_out, d_gl.p, (size_t)n * 12 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  std::swap(s->cell_conn.p, d_conn.p); std::swap(s->cell_conn.n, d_conn.n);      // the earlier list leaves with the locals
-  std::swap(s->cell_gl.p, d_gl.p); std::swap(s->cell_gl.n, d_gl.n);
-  std::swap(s->cell_out.p, d_out.p); std::swap(s->cell_out.n, d_out.n);
-  s->ncell = n;
+  s->cells.conn.swap(d_conn);      // the earlier list leaves with the locals
+  s->cells.gl.swap(d_gl);
+  s->cells.out.swap(d_out);
+  s->cells.n = n;
   s->cell_list_changed();
   return FSI_OK;
 }
@@ -1229,14 +1213,14 @@ int fsi_band_cell_rate(FsiCtx* ctx, int32_t quantity, int32_t series, int64_t fi
   const char* fn = "fsi_band_cell_rate";
   auto* s = cell_series_session(ctx, fn, quantity, series);
   if (!s) return FSI_ERR_INVALID;
-  if (!out) { ctx->err = std::string(fn) + ": out is NULL"; return FSI_ERR_INVALID; }
-  const double* x = nullptr;
-  int64_t frame_stride = 0;
-  FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x, &frame_stride));
+  if (!out) return Refusal{ctx, fn}("out is NULL");
+  SeriesView x{};
+  FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x));
   HIPCHK(hipSetDevice(ctx->device));
-  launch_cell_rate(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, count, s->cell_out.p);
+  auto& c = s->cells;
+  launch_cell_rate(ctx->stream, c.n, c.conn.p, c.gl.p, x.x, x.frame_stride, count, c.out.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, s->cell_out.p, (size_t)s->ncell * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(out, c.out.p, (size_t)c.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return FSI_OK;
 }
@@ -1246,46 +1230,35 @@ int fsi_band_cell_rate_current(FsiCtx* ctx, int32_t quantity, int32_t series, in
   const char* fn = "fsi_band_cell_rate_current";
   auto* s = cell_series_session(ctx, fn, quantity, series);
   if (!s) return FSI_ERR_INVALID;
-  auto refuse = [&](const std::string& why) { ctx->err = std::string(fn) + ": " + why; return FSI_ERR_INVALID; };
-  if (!rate_out) return refuse("rate_out is NULL");
-  const double* x = nullptr;
-  int64_t frame_stride = 0;
-  FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x, &frame_stride));
-  const double* geo = nullptr;
-  int64_t geo_stride = 0;
-  FSICHK(cell_geometry_frames(ctx, fn, s, series, first, step, &geo, &geo_stride));
+  if (!rate_out) return Refusal{ctx, fn}("rate_out is NULL");
+  SeriesView x{}, geo{};
+  FSICHK(cell_series_frames(ctx, fn, s, series, first, step, count, &x));
+  FSICHK(cell_geometry_frames(ctx, fn, s, series, first, step, count, &geo));
   HIPCHK(hipSetDevice(ctx->device));
-  if (s->cell_vol.n != (size_t)s->ncell || s->cell_minj.n != (size_t)s->ncell) {
-    FSICHK(room_for(ctx, fn, "the two further results need", 16.0 * (double)s->ncell, std::to_string(s->ncell) + " cells x 16"));
-    HIPCHK(s->cell_vol.alloc((size_t)s->ncell));
-    HIPCHK(s->cell_minj.alloc((size_t)s->ncell));
-    HIPCHK(hipDeviceSynchronize());                                // the allocations' own fills are done
-  }
-  launch_cell_rate_current(ctx->stream, s->ncell, s->cell_conn.p, s->cell_gl.p, x, frame_stride, geo, geo_stride, count, s->cell_out.p,
-                           s->cell_vol.p, s->cell_minj.p);
+  auto& c = s->cells;
+  const Want wants[] = {{&c.vol, (size_t)c.n, false, false}, {&c.minj, (size_t)c.n, false, false}};      // made together: both stand or neither
+  FSICHK(room_for(ctx, fn, "the two further results need", std::to_string(c.n) + " cells x 16", wants, [&] { c.vol.release(); c.minj.release(); }));
+  launch_cell_rate_current(ctx->stream, c.n, c.conn.p, c.gl.p, x.x, x.frame_stride, geo.x, geo.frame_stride, count, c.out.p, c.vol.p, c.minj.p);
   HIPCHK(hipGetLastError());
-  const size_t bytes = (size_t)s->ncell * sizeof(double);
-  HIPCHK(hipMemcpyAsync(rate_out, s->cell_out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  if (volume_ratio_out) HIPCHK(hipMemcpyAsync(volume_ratio_out, s->cell_vol.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  if (min_jacobian_out) HIPCHK(hipMemcpyAsync(min_jacobian_out, s->cell_minj.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  const size_t bytes = (size_t)c.n * sizeof(double);
+  HIPCHK(hipMemcpyAsync(rate_out, c.out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (volume_ratio_out) HIPCHK(hipMemcpyAsync(volume_ratio_out, c.vol.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (min_jacobian_out) HIPCHK(hipMemcpyAsync(min_jacobian_out, c.minj.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return FSI_OK;
 }
 
 int fsi_band_cell_weights(FsiCtx* ctx, int32_t quantity, const double* weights) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_cell_weights")) return FSI_ERR_INVALID;
-  auto refuse = [&](const std::string& why) { ctx->err = "fsi_band_cell_weights: " + why; return FSI_ERR_INVALID; };
-  if (quantity != 0 && quantity != 1) return refuse("quantity must be 0 (d) or 1 (v)");
-  auto* s = band_session(ctx, quantity, "fsi_band_cell_weights");
+  auto* s = band_entry(ctx, "fsi_band_cell_weights", quantity, WHOLE_CONTEXT | VECTOR_ONLY);
   if (!s) return FSI_ERR_INVALID;
-  if (s->ncell < 1) return refuse("no cell list (fsi_band_cells first)");
-  if (!weights) { s->cell_weighted = false; return FSI_OK; }
+  auto& c = s->cells;
+  if (c.n < 1) return Refusal{ctx, "fsi_band_cell_weights"}("no cell list (fsi_band_cells first)");
+  if (!weights) { c.weighted = false; return FSI_OK; }
   HIPCHK(hipSetDevice(ctx->device));
-  FSICHK(cell_buffer(ctx, "fsi_band_cell_weights", "the weights need", &s->cell_weight, (size_t)s->ncell, std::to_string(s->ncell) + " cells x 8"));
-  HIPCHK(hipMemcpyAsync(s->cell_weight.p, weights, (size_t)s->ncell * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  FSICHK(cell_buffer(ctx, "fsi_band_cell_weights", "the weights need", &c.weight, (size_t)c.n, std::to_string(c.n) + " cells x 8"));
+  HIPCHK(hipMemcpyAsync(c.weight.p, weights, (size_t)c.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));                       // the caller's array is free again
-  s->cell_weighted = true;
+  c.weighted = true;
   return FSI_OK;
 }
 
@@ -1300,8 +1273,7 @@ int fsi_band_cell_vortex_current(FsiCtx* ctx, int32_t quantity, int32_t series, 
 }
 
 int fsi_band_amplitude(FsiCtx* ctx, int32_t quantity, int32_t window) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_amplitude");
+  auto* s = band_entry(ctx, "fsi_band_amplitude", quantity, ANY_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
   if (!s->filtered) { ctx->err = "fsi_band_amplitude: no filtered series (fsi_band_filter first)"; return FSI_ERR_INVALID; }
   if (window < 0 || window > band_frames(s)) {
@@ -1313,8 +1285,7 @@ int fsi_band_amplitude(FsiCtx* ctx, int32_t quantity, int32_t window) {
 }
 
 int fsi_band_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, double* out, double* max_out, int64_t* argmax_out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_fetch");
+  auto* s = band_entry(ctx, "fsi_band_fetch", quantity, ANY_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
   if (what < FSI_BAND_RAW || what > FSI_BAND_MAGNITUDE) { ctx->err = "fsi_band_fetch: what must be FSI_BAND_RAW .. FSI_BAND_MAGNITUDE"; return FSI_ERR_INVALID; }
   if (what != FSI_BAND_RAW && !s->filtered) { ctx->err = "fsi_band_fetch: no filtered series (fsi_band_filter first)"; return FSI_ERR_INVALID; }
@@ -1364,8 +1335,7 @@ int fsi_band_fetch(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t frame, d
 }
 
 int fsi_band_trace(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t npoints, const int32_t* points, double* out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_trace");
+  auto* s = band_entry(ctx, "fsi_band_trace", quantity, ANY_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
   if (tensor_quantity(quantity)) {      // the reference writes no point traces for these quantities (create_hi_pass_viz.py:636-643)
     ctx->err = "fsi_band_trace: a strain / stress session has no point traces";
@@ -1386,10 +1356,8 @@ int fsi_band_trace(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t npoints,
   HIPCHK(res.alloc(nout));
   HIPCHK(hipDeviceSynchronize());                                  // the allocations' own fills are done
   HIPCHK(hipMemcpyAsync(pts.p, points, (size_t)npoints * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  if (what == FSI_BAND_RAW)
-    launch_band_trace(ctx->stream, s->nrow, s->ncomp, npoints, pts.p, frames, s->hist.p + (size_t)s->sel_first * s->nrow, s->sel_stride, res.p);
-  else
-    launch_band_trace(ctx->stream, s->nrow, s->ncomp, npoints, pts.p, frames, history_frame(s, true, 0), 1, res.p);
+  const SeriesView v = series_view(s, what == FSI_BAND_RAW ? FSI_RATE_RAW : FSI_RATE_SERIES);
+  launch_band_trace(ctx->stream, s->nrow, s->ncomp, npoints, pts.p, frames, v.x, v.frame_stride / s->nrow, res.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, res.p, nout * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1397,17 +1365,13 @@ int fsi_band_trace(FsiCtx* ctx, int32_t quantity, int32_t what, int64_t npoints,
 }
 
 int fsi_band_export(FsiCtx* ctx, int32_t quantity, int64_t first, int64_t count, double* out) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_export")) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_export");
+  auto* s = band_entry(ctx, "fsi_band_export", quantity, WHOLE_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
   return history_export(ctx, s, "fsi_band_export", first, count, out);
 }
 
 int fsi_band_import(FsiCtx* ctx, int32_t quantity, int64_t count, const double* frames) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_import")) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_import");
+  auto* s = band_entry(ctx, "fsi_band_import", quantity, WHOLE_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
   FSICHK(history_import(ctx, s, "fsi_band_import", count, frames));
   s->frames_changed();
@@ -1453,9 +1417,7 @@ int fsi_board_end(FsiCtx* ctx) {
 }
 
 int fsi_band_board_attach(FsiCtx* ctx, int32_t quantity, int64_t node0) {
-  if (!ctx) return FSI_ERR_INVALID;
-  if (partitioned(ctx, "fsi_band_board_attach")) return FSI_ERR_INVALID;
-  auto* s = band_session(ctx, quantity, "fsi_band_board_attach");
+  auto* s = band_entry(ctx, "fsi_band_board_attach", quantity, WHOLE_CONTEXT);
   if (!s) return FSI_ERR_INVALID;
   if (node0 == -1) { s->board_node0 = -1; return FSI_OK; }
   if (!ctx->board.open) { ctx->err = "fsi_band_board_attach: no board (fsi_board_begin first)"; return FSI_ERR_INVALID; }
@@ -1534,7 +1496,7 @@ int fsi_spec_begin_rows(FsiCtx* ctx, int32_t quantity, int64_t nrows, const int3
 int fsi_spec_begin_wss(FsiCtx* ctx, int64_t nf, const int32_t* facet_cells, const int32_t* facet_local, double mu, int64_t nrows,
                        const int32_t* dofs, const int32_t* comps, int64_t capacity) {
   if (!ctx) return FSI_ERR_INVALID;
-  auto refuse = [&](const char* why) { ctx->err = std::string("fsi_spec_begin_wss: ") + why; return FSI_ERR_INVALID; };
+  const Refusal refuse{ctx, "fsi_spec_begin_wss"};
   if (ctx->part) return refuse("partitioned contexts are not supported");
   if (nf <= 0 || !facet_cells || !facet_local || !(mu > 0.0)) return refuse("needs nf > 0 facets and mu > 0");
   if (nf > (int64_t)2147483647 / 3) return refuse("more than 2^31 - 1 dofs on the boundary mesh");
@@ -1635,7 +1597,7 @@ int fsi_spec_filter(FsiCtx* ctx, int32_t quantity, int32_t ntaps, const double* 
   auto* s = spec_session(ctx, quantity, "fsi_spec_filter");
   if (!s) return FSI_ERR_INVALID;
   if (ntaps == 0) { s->filtered = false; return FSI_OK; }      // back to the raw series
-  return history_filter(ctx, s, "fsi_spec_filter", "0 (the raw series) or 2 .. 11", ntaps, b, a, zi, padlen);
+  return history_filter(ctx, s, "fsi_spec_filter", "0 (the raw series) or 2 .. 11", ntaps, b, a, zi, padlen, SeriesView{s->hist.p, s->frames, s->nrow});
 }
 
 int fsi_spec_fetch(FsiCtx* ctx, int32_t quantity, int32_t filtered, int64_t frame, double* out) {

@@ -927,6 +927,12 @@ class HostBandSession(HostHistory):
     def selected(self) -> np.ndarray:
         return np.stack(self.raw)[self.view]
 
+    def series(self, name: str):
+        """The (frames, nodes, ncomp) array of 'raw' (the selected raw frames), 'series' (the filtered series or the fluctuation,
+        without guard frames) or 'phase_mean' (the period's mean frames), None where it does not stand: the one place that says
+        where a series lies (series_view in csrc/fsi_sessions.hip).  Refusing is the caller's, under its own name."""
+        return self.selected() if name == "raw" else self.filtered if name == "series" else self.phase_mean
+
     def select(self, first: int = 0, count: int = -1, stride: int = 1) -> int:
         frames = len(self.raw)
         fits = stride >= 1 and 0 <= first < frames and (count == -1 or (count >= 1 and first + (count - 1) * stride < frames))
@@ -1019,12 +1025,8 @@ class HostBandSession(HostHistory):
             raise RuntimeError(f"hi-pass pod_gram: {n} selected frames, the decomposition needs at least 2 (select)")
         if series == "series" and self.filtered is None:
             raise RuntimeError("hi-pass pod_gram: no filtered series (filter or phase first)")
-        x = self.selected() if series == "raw" else self.filtered
-        G, mean = pod_gram(x, weights)
+        G, mean = pod_gram(self.series(series), weights)
         self.pod_state = dict(source=series, G=G, mean=mean, n=n, modes=None)
-
-    def _pod_source(self) -> np.ndarray:
-        return self.selected() if self.pod_state["source"] == "raw" else self.filtered
 
     def pod_modes(self, table) -> None:
         """The modes ``Phi_m = sum_j table[j, m] y_j`` of the decomposition whose Gram matrix stands, ``table`` (frames, nmodes)
@@ -1034,7 +1036,7 @@ class HostBandSession(HostHistory):
         T = np.asarray(table, dtype=np.float64)
         if T.ndim != 2 or not 1 <= T.shape[1] <= POD_MAX_MODES:
             raise RuntimeError(f"hi-pass pod_modes: needs 1 <= nmodes <= {POD_MAX_MODES} modes and their table (frames, nmodes)")
-        self.pod_state["modes"] = pod_modes(self._pod_source(), self.pod_state["mean"], T)
+        self.pod_state["modes"] = pod_modes(self.series(self.pod_state["source"]), self.pod_state["mean"], T)
 
     def pod_fetch(self, what: str, index: int = 0) -> np.ndarray:
         """'gram' the matrix (frames, frames), 'mean' the mean the frames were taken about (n, ncomp), 'mode' ``index``
@@ -1083,7 +1085,7 @@ class HostBandSession(HostHistory):
             raise RuntimeError(f"{what}: no phase average (phase first)")
         if own is not None:
             raise RuntimeError(own)
-        x = self.selected() if series == "raw" else self.filtered if series == "series" else self.phase_mean
+        x = self.series(series)
         first, step, count = int(first), int(step), int(count)
         if count == -1 and step >= 1:
             count = (len(x) - 1 - first) // step + 1
@@ -1199,13 +1201,13 @@ class HostBandSession(HostHistory):
     def filter_next(self, b, a, zi, padlen: int) -> None:
         if self.filtered is None:
             raise RuntimeError("hi-pass filter_next: no filtered series (filter first)")
-        self.series_changed(filtfilt_rows(b, a, self.filtered, zi, padlen))
+        self.series_changed(filtfilt_rows(b, a, self.series("series"), zi, padlen))
 
     def trace(self, what: str, points) -> np.ndarray:
         """(points, frames, 1 + ncomp): the magnitude, then the row of each listed node over the selected frames."""
         if what == "filtered" and self.filtered is None:
             raise RuntimeError("hi-pass trace: no filtered series (filter first)")
-        x = self.selected() if what == "raw" else self.filtered
+        x = self.series("raw" if what == "raw" else "series")
         pts = np.asarray(points, dtype=np.int64).reshape(-1)
         if len(pts) and (pts.min() < 0 or pts.max() >= x.shape[1]):
             raise RuntimeError("hi-pass trace: node out of range")
