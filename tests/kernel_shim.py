@@ -8,7 +8,10 @@ preconditioner restated stage by stage (tests/test_block_apply_reference.py on t
 tests/post_cells.py: the wall shear stress, hemodynamic sums and indices, solid stress / strain and principal values of
 fsi_post.hip, fsi_hemo.hip and fsi_stress.hip restated per cell in np.longdouble, with their bounds (shim_wss, shim_hemo_sample,
 shim_hemo_finish, shim_spec_wss_sample, shim_stress_strain, shim_stress_sample, shim_stress_average, shim_tensor_sample,
-shim_tensor_principal; tests/test_post_cell_references.py on the CPU, tests/test_gpu_post_cell_kernels.py).
+shim_tensor_principal; tests/test_post_cell_references.py on the CPU, tests/test_gpu_post_cell_kernels.py), and
+tests/gcr_solve.py: the properties of a recycled GCR solve and of its kept store, and a host twin of the solve (ctx_krylov_info,
+ctx_krylov_columns, ctx_solve_gcr, ctx_precondition here; tests/test_gcr_solve_reference.py on the CPU,
+tests/test_gpu_gcr_solve.py).
 
 The shim runs ONE ``fsi::launch_*`` call of libvaspfsi.so on host arrays; the builders restate, in numpy, what the library's
 host code hands those kernels: the LDS tiles of a graph (fsi_setup.hip build_tiles, node tiles and Schur tiles), the FP16 records of
@@ -51,6 +54,8 @@ _SIGS = {
     "shim_expand_cols": "llpppppppp", "shim_spmv": "lpppplpi", "shim_spmv_node6": "llpppppplppp", "shim_drows_extract": "lpppppp",
     "shim_pad_cols32": "lpppp", "shim_pad_vals32": "llppplllpli", "shim_spmv_node6p": "llppplpplppplppp",
     "shim_matrix_finish": "lppppplpp", "shim_ctx_spmv": "pippp",
+    "shim_ctx_krylov_info": "ppipippp", "shim_ctx_krylov_columns": "ppppp", "shim_ctx_solve_gcr": "pppdippp",
+    "shim_ctx_precondition": "ppp",
     "shim_mg_d0": "lppppppp", "shim_mg_rap": "llpppppppppppppp", "shim_mg_coarse_finish": "llppppppppp",
     "shim_mg_restrict": "llpppppppfppp", "shim_mg_prolong": "llppppp", "shim_sbmg_flags": "lpppp",
     "shim_sbmg_rap": "lllppppppppppppppp", "shim_sbmg_coarse_finish": "llpppppppp", "shim_sbmg_restrict": "lllpppppppppppl",
@@ -152,7 +157,7 @@ _UNSIGNED = {"dd_rec", "vv_rec", "sb_rec", "s_rec"}
 _FLOAT = {"dd_chat", "vv_db32", "sb_vals", "sb_binv12", "s_vals", "s_vals32", "s_dinv", "dd_db", "rowscale", "A", "A32", "Ad64", "Ad32",
           "mg_pw", "mg_chw", "mg_Ac", "mg_cc", "mg_d0", "mg_dcinv4", "sbmg_pw", "sbmg_chw", "sbmg_cvals", "sbmg_cbinv12",
           "sb_binv9", "sb_dinv", "dd_dinv32", "vvf_dinv32", "Mdd.vals", "Mvv.vals", "Adv", "Avp", "Apv", "App", "Avp32", "Apv32",
-          "vv_db", "adv_db", "dd_db32", "vv_dinv", "mask_f", "mask_s", "ss_vals", "LU", "blk", "sbmg_work", "mg_work", "ones32", "mg_cones"}
+          "vv_db", "adv_db", "dd_db32", "vv_dinv", "mask_f", "mask_s", "ss_vals", "LU", "blk", "sbmg_work", "mg_work", "ones32", "mg_cones", "bs"}
 
 
 def ctx_info(ctx) -> dict:
@@ -168,6 +173,62 @@ def ctx_spmv(ctx, working, x, y):
     cnt = np.zeros(2, dtype=np.int64)
     rc = status("shim_ctx_spmv", ctx, int(working), x, y, cnt)
     return rc, int(cnt[0]), int(cnt[1])
+
+
+KRYLOV_INFO = ("cap", "hw", "made", "nfree", "kry_fp32", "kry_fp32_policy", "ldq", "ldz", "hot_next", "window_cols", "gcr_restarts",
+               "kry_fp32_failures_total", "gcr_reorth_forced", "gcr_arnoldi_steps", "verdicts_skipped", "gcr_stagnated", "gcr_stalled",
+               "f64_suspect", "ndof")
+KRYLOV_INFO_D = ("f32_last_drift", "gcr_escape")
+
+
+def ctx_krylov_info(ctx) -> dict:
+    """the store and the counters of a live context's recycled GCR (shim_ctx_krylov_info): the KRYLOV_INFO fields as ints, the
+    KRYLOV_INFO_D fields as floats, born [cap], free (the free list, in its order) and hot_slots [GCR_WINDOW] as int lists"""
+    lib = load()
+    iout, dout = np.zeros(len(KRYLOV_INFO), dtype=np.int64), np.zeros(len(KRYLOV_INFO_D))
+    lib.shim_ctx_krylov_info(ctx, _arg(iout), len(iout), _arg(dout), len(dout), None, None, None)
+    cap = int(iout[0])
+    born, free, hot = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int32), np.zeros(32, dtype=np.int32)
+    k = lib.shim_ctx_krylov_info(ctx, _arg(iout), len(iout), _arg(dout), len(dout), _arg(born), _arg(free), _arg(hot))
+    assert k == len(KRYLOV_INFO), (k, len(KRYLOV_INFO))
+    info = dict(zip(KRYLOV_INFO, (int(v) for v in iout)))
+    info.update(zip(KRYLOV_INFO_D, (float(v) for v in dout)))
+    info.update(born=[int(v) for v in born], free=[int(v) for v in free[:info["nfree"]]], hot_slots=[int(v) for v in hot])
+    return info
+
+
+def ctx_krylov_columns(ctx, info=None):
+    """(Q [hw][ldq] float32 or float64 as the store holds it, Z [hw][ldz], Qh [GCR_WINDOW][ldq]) of a live context, padding rows
+    included.  Qh is NaN throughout where the context has no window."""
+    info = ctx_krylov_info(ctx) if info is None else info
+    hw, ldq, ldz = info["hw"], info["ldq"], info["ldz"]
+    sz = C.c_int32(0)
+    call("shim_ctx_krylov_columns", ctx, None, None, None, C.byref(sz))
+    assert sz.value == (4 if info["kry_fp32"] else 8), (sz.value, info["kry_fp32"])
+    Q = np.zeros((hw, ldq), dtype=np.float32 if sz.value == 4 else np.float64)
+    Z = np.zeros((hw, ldz))
+    Qh = np.full((32, ldq), np.nan)
+    call("shim_ctx_krylov_columns", ctx, Q, Z, Qh, C.byref(sz))
+    return Q, Z, Qh
+
+
+def ctx_solve_gcr(ctx, rhs, rtol, max_it=4000, fill=-7.25):
+    """fsi::host::solve_gcr on the equilibrated system in solver ordering: (status, message, x [ndof + TAIL] whose tail started as
+    `fill`, iterations, relres, monolithic products launched)"""
+    n = len(rhs)
+    x = np.full(n + TAIL, fill)
+    it, rr, cnt = C.c_int32(0), C.c_double(0.0), np.zeros(1, dtype=np.int64)
+    rc = status("shim_ctx_solve_gcr", ctx, np.ascontiguousarray(rhs, dtype=np.float64), x, float(rtol), int(max_it), C.byref(it),
+                C.byref(rr), cnt)
+    return rc, (load().shim_last_error().decode() if rc else ""), x, it.value, rr.value, int(cnt[0])
+
+
+def ctx_precondition(ctx, r, fill=-7.25):
+    """z = M^-1 r of the context's active preconditioner in solver ordering (fsi::host::precondition)"""
+    z = np.full(len(r) + TAIL, fill)
+    call("shim_ctx_precondition", ctx, np.ascontiguousarray(r, dtype=np.float64), z)
+    assert np.all(z[len(r):] == fill), "precondition wrote behind z"
+    return z[:len(r)].copy()
 
 
 def ctx_ktheta(ctx) -> float:

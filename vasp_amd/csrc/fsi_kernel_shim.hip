@@ -11,7 +11,9 @@
 //
 // A live context is read through shim_ctx_info / shim_ctx_coarse / shim_ctx_array (device arrays by name; `blk`, the work vectors
 // of one preconditioner application, and the two cycles' coarse work areas `sbmg_work` / `mg_work` among them) and
-// shim_ctx_apply_info (what precondition_block branches on and the sweep counts it takes): tests/block_apply.py.
+// shim_ctx_apply_info (what precondition_block branches on and the sweep counts it takes): tests/block_apply.py.  Its recycled
+// GCR is read and run through shim_ctx_krylov_info / shim_ctx_krylov_columns / shim_ctx_solve_gcr / shim_ctx_precondition
+// (whole host functions of fsi_krylov.hip and fsi_precond.hip on the context's own stream): tests/gcr_solve.py.
 #include "fsi_cheb.hpp"
 #include "fsi_host.hpp"
 #include "fsi_kernels.hpp"
@@ -2208,7 +2210,7 @@ int shim_ctx_array(const FsiCtx* ctx, const char* name, void* host, int64_t* cou
                          E(vv_dinv),    E(mask_f),    E(mask_s),  E(ss_vals),    E(ss_src),      E(ss_rowptr),   E(ss_cols),
                          E(ss_diagpos), E(fs_rows),   E(fs_ptr),  E(fs_col),     E(fs_src),      E(sb_row),      E(sb_src),
                          E(sb_stride),  E(s_diagpos),  E(LU),       E(user2solver), E(blk),        E(sbmg_work),   E(mg_work),
-                         E(ones32),     E(mg_cones)};
+                         E(ones32),     E(mg_cones),  E(bs)};
 #undef E
   for (const Entry& t : table) {
     if (std::strcmp(t.name, name) != 0) continue;
@@ -2254,6 +2256,82 @@ int shim_ctx_spmv(FsiCtx* ctx, int working, const double* x, double* y, int64_t*
   counters[1] = ctx->drows_products - dr0;
   if (const int e = c.finish("host::spmv")) return e;
   if (rc) g_err = "host::spmv: " + ctx->err;
+  return rc;
+}
+
+// ---- the recycled GCR of a live context (fsi_krylov.hip): its store, one solve, one preconditioner application -----------------
+// iout, by position (new fields go at the end: tests/kernel_shim.py reads them by position): cap, hw, made, free.size(), kry_fp32,
+// kry_fp32_policy, ldq, ldz, hot_next, window_cols(), gcr_restarts, kry_fp32_failures_total, gcr_reorth_forced, gcr_arnoldi_steps,
+// verdicts_skipped, gcr_stagnated, gcr_stalled, f64_suspect, ndof.  dout: f32_last_drift, gcr_escape.  born [cap], free_slots
+// [cap] (the first free.size() are set), hot [GCR_WINDOW]; any of the three may be null.  Returns the number of iout fields.
+int shim_ctx_krylov_info(const FsiCtx* ctx, int64_t* iout, int ni, double* dout, int nd, int64_t* born, int32_t* free_slots,
+                         int32_t* hot) {
+  const GcrStore& s = ctx->kry;
+  const int64_t v[] = {s.cap, s.hw, s.made, (int64_t)s.free.size(), ctx->kry_fp32, ctx->kry_fp32_policy, ctx->ldq, ctx->ldz,
+                       s.hot_next, s.window_cols(), ctx->gcr_restarts, ctx->kry_fp32_failures_total, ctx->gcr_reorth_forced,
+                       ctx->gcr_arnoldi_steps, ctx->verdicts_skipped, ctx->gcr_stagnated, ctx->gcr_stalled, ctx->f64_suspect,
+                       ctx->ndof};
+  const double w[] = {ctx->f32_last_drift, ctx->gcr_escape};
+  const int k = (int)(sizeof(v) / sizeof(v[0])), kd = (int)(sizeof(w) / sizeof(w[0]));
+  for (int i = 0; i < ni && i < k; ++i) iout[i] = v[i];
+  for (int i = 0; i < nd && i < kd; ++i) dout[i] = w[i];
+  if (born) std::copy(s.born.begin(), s.born.end(), born);
+  if (free_slots) std::copy(s.free.begin(), s.free.end(), free_slots);
+  if (hot) std::copy(s.hot_slots.begin(), s.hot_slots.end(), hot);
+  return k;
+}
+// Columns [0, hw) of the store, padding rows included: Q [hw][ldq] as raw bytes of *qelem (4 or 8) each, Z [hw][ldz], and the
+// whole window Qh [GCR_WINDOW][ldq] (left alone where the context has none: FSI_KRYLOV_FP32=0).  Null pointers: *qelem only.
+int shim_ctx_krylov_columns(const FsiCtx* ctx, void* Q, double* Z, double* Qh, int* qelem) {
+  const size_t hw = (size_t)ctx->kry.hw, qb = ctx->kry_fp32 ? sizeof(float) : sizeof(double);
+  *qelem = (int)qb;
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess && Q && hw) e = hipMemcpy(Q, ctx->KQ.p, hw * (size_t)ctx->ldq * qb, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && Z && hw) e = hipMemcpy(Z, ctx->KZ.p, hw * (size_t)ctx->ldz * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && Qh && ctx->KQh.p) e = hipMemcpy(Qh, ctx->KQh.p, (size_t)GCR_WINDOW * ctx->ldq * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) return 0;
+  g_err = std::string("shim_ctx_krylov_columns: ") + hipGetErrorName(e);
+  return 1;
+}
+// fsi::host::solve_gcr on the equilibrated system in solver ordering: rhs [ndof], x [ndof + SHIM_TAIL] (written whatever the
+// status).  counters [1]: the monolithic products the solve launched (one per iteration and one per FP64 verdict).
+// Status: 0, 1 = HIP error, else the FSI_ERR_* of solve_gcr (ctx->err in shim_last_error()).
+int shim_ctx_solve_gcr(FsiCtx* ctx, const double* rhs, double* x, double rtol, int max_it, int32_t* iters, double* relres,
+                       int64_t* counters) {
+  Call c;
+  const int64_t n = ctx->ndof;
+  const double* drhs = c.in(rhs, (size_t)n);
+  double* dx = c.io(x, (size_t)n + SHIM_TAIL);
+  if (c.ok()) c.note(hipSetDevice(ctx->device));
+  const int64_t sp0 = ctx->t_spmv.calls;
+  int rc = 0, it = 0;
+  double rr = 0.0;
+  if (c.ok()) {
+    rc = fsi::host::solve_gcr(ctx, drhs, dx, rtol, max_it, &it, &rr);
+    c.note(hipStreamSynchronize(ctx->stream));
+  }
+  *iters = it;
+  *relres = rr;
+  counters[0] = ctx->t_spmv.calls - sp0;
+  if (const int e = c.finish("host::solve_gcr")) return e;
+  if (rc) g_err = "host::solve_gcr: " + ctx->err;
+  return rc;
+}
+// z = M^-1 r through fsi::host::precondition (solver ordering); r [ndof], z [ndof + SHIM_TAIL]
+int shim_ctx_precondition(FsiCtx* ctx, const double* r, double* z) {
+  Call c;
+  const int64_t n = ctx->ndof;
+  const double* dr = c.in(r, (size_t)n);
+  double* dz = c.io(z, (size_t)n + SHIM_TAIL);
+  if (c.ok()) c.note(hipSetDevice(ctx->device));
+  int rc = 0;
+  if (c.ok()) {
+    rc = fsi::host::precondition(ctx, dr, dz);
+    c.note(hipStreamSynchronize(ctx->stream));
+  }
+  if (const int e = c.finish("host::precondition")) return e;
+  if (rc) g_err = "host::precondition: " + ctx->err;
   return rc;
 }
 
