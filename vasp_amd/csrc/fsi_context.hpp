@@ -335,6 +335,12 @@ struct FsiCtx {
   fsi::DevBuf<float> Ad32;                   // ... rounded, for the products on the FP32 copy
   bool drows_ok = false;
   int64_t drows_products = 0;
+  // ... and split for the FP64 products (k_spmv_node6s): dd for every pair, dv for the pairs of the nodes whose d rows hold a
+  // non-zero dv entry (the solid's), found from the values at every refresh; drows_split_ok only while drows_ok
+  fsi::DevBuf<double> Add, Adv3;             // [3 x node pairs], [3 x pairs of coupled nodes] (grows when a refresh finds more)
+  fsi::DevBuf<int32_t> drows_cdeg;           // [N2] degree of a coupled node, 0 of an uncoupled one
+  fsi::DevBuf<int64_t> drows_off;            // [N2 + 1] first pair of a coupled node in Adv3, -1: uncoupled; [N2]: pairs in Adv3
+  bool drows_split_ok = false;
   bool gcr_stagnated = false;                // the last cycle ended on 40 iterations without a 10 % gain
   bool gcr_stalled = false;                  // ... on 128 iterations without a 10 % gain far from its target, the store full (truncated recurrence stuck)
   double f32_cycle_floor = 1e-6;             // FP32 basis: a cycle reduces the residual by at most this factor before the FP64 verdict

@@ -13,7 +13,8 @@
 // Layout: column k of Q starts at Q + k * ldq (ldq = n rounded up to 4, so every column is 16-byte aligned for float4 /
 // double2 loads); column k of Z at Z + k * ldz (ldz = n rounded up to 2).  Algorithmic bytes per launch:
 //   k_gcr_dots   m ldq sizeof(QT) + n 8 (+ n 8 with r)          k_gcr_axpy   m ldq sizeof(QT) + n 24
-//   k_gcr_flush  m ldz 8 + n 16 + knew n 8                      k_gcr_update n (8 + 8 + 16 + 16 + sizeof(QT))
+//   k_gcr_flush  m ldz 8 + n 16 + knew n 8                      k_gcr_update n (8 + 8 + 16 + 16 + sizeof(QT)), 8 less without qd
+// (m: the columns that hold data - a slot just taken beyond the high-water mark is not read, see k_gcr_dots)
 #include "fsi_kernels.hpp"
 
 namespace fsi {
@@ -60,8 +61,10 @@ __device__ inline void load4(const double* p, double& a, double& b, double& c, d
 // part[k * gridDim.x + bx] = partial of Q_k . w (k < m);  k = m: w . w;  k = m + 1: w . r (0 when r == nullptr).
 // blockIdx.y selects NC directions (or, in the last row, the two vector products): one read of w feeds NC products, so
 // the FP32 form takes eight columns per block (w is FP64: with four, re-reading it would add half of Q's bytes again).
+// md <= m: only the leading md columns hold data; the others (the slot just taken beyond the high-water mark, not written
+// yet) count as zero columns and are never loaded - their products are the +0 a column of zeros gives.
 template <class QT, int NC, bool NT>
-__global__ __launch_bounds__(256) void k_gcr_dots(const QT* __restrict__ Q, int64_t ldq, int64_t n, int m,
+__global__ __launch_bounds__(256) void k_gcr_dots(const QT* __restrict__ Q, int64_t ldq, int64_t n, int m, int md,
                                                   const double* __restrict__ w, const double* __restrict__ r,
                                                   double* __restrict__ part) {
   const int64_t n4 = n >> 2;
@@ -84,10 +87,15 @@ __global__ __launch_bounds__(256) void k_gcr_dots(const QT* __restrict__ Q, int6
     return;
   }
   const int k0 = NC * blockIdx.y;
+  if (k0 >= md) {                                       // a group of empty columns only
+    if (threadIdx.x == 0)
+      for (int c = 0; c < NC && k0 + c < m; ++c) part[(int64_t)(k0 + c) * gridDim.x + blockIdx.x] = 0.0;
+    return;
+  }
   const QT* q[NC];
   double s[NC];
 #pragma unroll
-  for (int c = 0; c < NC; ++c) { q[c] = Q + (int64_t)(k0 + c < m ? k0 + c : k0) * ldq; s[c] = 0.0; }
+  for (int c = 0; c < NC; ++c) { q[c] = Q + (int64_t)(k0 + c < md ? k0 + c : k0) * ldq; s[c] = 0.0; }
   for (int64_t t = t0; t < n4; t += stride) {
     const int64_t i = t << 2;
     const double2 wa = *reinterpret_cast<const double2*>(w + i);
@@ -108,7 +116,7 @@ __global__ __launch_bounds__(256) void k_gcr_dots(const QT* __restrict__ Q, int6
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const double v = block_sum256(s[c]);
-    if (threadIdx.x == 0 && k0 + c < m) part[(int64_t)(k0 + c) * gridDim.x + blockIdx.x] = v;
+    if (threadIdx.x == 0 && k0 + c < m) part[(int64_t)(k0 + c) * gridDim.x + blockIdx.x] = k0 + c < md ? v : 0.0;
   }
 }
 
@@ -121,8 +129,10 @@ __global__ __launch_bounds__(256) void k_gcr_sum(const double* __restrict__ part
 }
 
 // w -= sum_k h[k] Q_k;  part[bx] = partial |w'|^2,  part[gridDim.x + bx] = partial w'.r
+// md <= m as in k_gcr_dots: a column at or beyond md enters its group of four as zeros, unloaded, so the sums are grouped
+// and rounded exactly as with a stored column of zeros.
 template <class QT, bool NT>
-__global__ __launch_bounds__(256) void k_gcr_axpy(const QT* __restrict__ Q, int64_t ldq, int64_t n, int m,
+__global__ __launch_bounds__(256) void k_gcr_axpy(const QT* __restrict__ Q, int64_t ldq, int64_t n, int m, int md,
                                                   const double* __restrict__ h, double* __restrict__ w,
                                                   const double* __restrict__ r, double* __restrict__ part) {
   const int64_t n4 = n >> 2;
@@ -133,7 +143,7 @@ __global__ __launch_bounds__(256) void k_gcr_axpy(const QT* __restrict__ Q, int6
     const QT* q = Q + i;
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0, b3 = 0.0;
     int k = 0;
-    for (; k + 4 <= m; k += 4) {            // four independent 16-byte (FP32) / 32-byte (FP64) loads in flight
+    for (; k + 4 <= md; k += 4) {           // four independent 16-byte (FP32) / 32-byte (FP64) loads in flight
       double x0, x1, x2, x3, y0, y1, y2, y3, z0, z1, z2, z3, u0, u1, u2, u3;
       load4<NT>(q + (int64_t)k * ldq, x0, x1, x2, x3);
       load4<NT>(q + (int64_t)(k + 1) * ldq, y0, y1, y2, y3);
@@ -143,7 +153,18 @@ __global__ __launch_bounds__(256) void k_gcr_axpy(const QT* __restrict__ Q, int6
       a0 += h0 * x0 + h2 * z0; a1 += h0 * x1 + h2 * z1; a2 += h0 * x2 + h2 * z2; a3 += h0 * x3 + h2 * z3;
       b0 += h1 * y0 + h3 * u0; b1 += h1 * y1 + h3 * u1; b2 += h1 * y2 + h3 * u2; b3 += h1 * y3 + h3 * u3;
     }
-    for (; k < m; ++k) {
+    if (k < md && k + 4 <= m) {             // the group that data and empty columns share: the same sums, zeros for the empty ones
+      double x0, x1, x2, x3, y0 = 0.0, y1 = 0.0, y2 = 0.0, y3 = 0.0, z0 = 0.0, z1 = 0.0, z2 = 0.0, z3 = 0.0;
+      const double u0 = 0.0, u1 = 0.0, u2 = 0.0, u3 = 0.0;
+      load4<NT>(q + (int64_t)k * ldq, x0, x1, x2, x3);
+      if (k + 1 < md) load4<NT>(q + (int64_t)(k + 1) * ldq, y0, y1, y2, y3);
+      if (k + 2 < md) load4<NT>(q + (int64_t)(k + 2) * ldq, z0, z1, z2, z3);
+      const double h0 = h[k], h1 = h[k + 1], h2 = h[k + 2], h3 = h[k + 3];
+      a0 += h0 * x0 + h2 * z0; a1 += h0 * x1 + h2 * z1; a2 += h0 * x2 + h2 * z2; a3 += h0 * x3 + h2 * z3;
+      b0 += h1 * y0 + h3 * u0; b1 += h1 * y1 + h3 * u1; b2 += h1 * y2 + h3 * u2; b3 += h1 * y3 + h3 * u3;
+      k += 4;
+    }
+    for (; k < md; ++k) {                   // (an empty column here, or a whole group of them, adds +0 to sums that are never -0)
       double x0, x1, x2, x3;
       load4<NT>(q + (int64_t)k * ldq, x0, x1, x2, x3);
       const double h0 = h[k];
@@ -162,7 +183,7 @@ __global__ __launch_bounds__(256) void k_gcr_axpy(const QT* __restrict__ Q, int6
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const int64_t i = (n4 << 2) + threadIdx.x;
     double a = 0.0;
-    for (int k = 0; k < m; ++k) a += h[k] * (double)Q[(int64_t)k * ldq + i];
+    for (int k = 0; k < md; ++k) a += h[k] * (double)Q[(int64_t)k * ldq + i];
     const double wv = w[i] - a;
     w[i] = wv;
     sww += wv * wv;
@@ -177,8 +198,8 @@ __global__ __launch_bounds__(256) void k_gcr_axpy(const QT* __restrict__ Q, int6
 }
 
 // q = w * inv_wn  ->  Q_slot (rounded to QT) and qd (FP64: the vector the next direction is made from), raw z -> Z_slot,
-// r -= alpha q;  part[bx] = partial |r'|^2
-template <class QT>
+// r -= alpha q;  part[bx] = partial |r'|^2.  QD = false: no qd - an FP64 column is the exact q already
+template <class QT, bool QD>
 __global__ __launch_bounds__(256) void k_gcr_update(QT* __restrict__ qcol, double* __restrict__ zcol, int64_t n,
                                                     const double* __restrict__ w, const double* __restrict__ z,
                                                     double inv_wn, double alpha, double* __restrict__ r,
@@ -188,7 +209,7 @@ __global__ __launch_bounds__(256) void k_gcr_update(QT* __restrict__ qcol, doubl
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) {
     const double q = w[i] * inv_wn;
     qcol[i] = (QT)q;
-    qd[i] = q;
+    if (QD) qd[i] = q;
     zcol[i] = z[i];
     const double rv = r[i] - alpha * q;
     r[i] = rv;
@@ -247,7 +268,7 @@ inline bool stream_once(int64_t ldq, int m) {      // (FP32 columns only: an FP6
   return sizeof(QT) == 4 && (double)ldq * (double)m * sizeof(QT) > FSI_GCR_STREAM_MIB * 1048576.0;
 }
 template <class QT>
-void dots_t(hipStream_t st, const void* Q, int64_t ldq, int64_t n, int m, const double* w, const double* r,
+void dots_t(hipStream_t st, const void* Q, int64_t ldq, int64_t n, int m, int md, const double* w, const double* r,
             double* scratch, double* out) {
   // row parts: 128 at a full store (3 000 workgroups at m = 180; 64: 4 % slower, 256: same) and more when there are few columns - the
   // FP64 window's 1 - 8 columns were 256 workgroups on 256 CUs (212 us for 0.4 GB) - so that the grid has ~2 000 workgroups either way
@@ -260,21 +281,21 @@ void dots_t(hipStream_t st, const void* Q, int64_t ldq, int64_t n, int m, const 
   // 20 bench steps)
   const int ngroups = (m + 7) / 8;
   if (stream_once<QT>(ldq, m))
-    hipLaunchKernelGGL((k_gcr_dots<QT, 8, true>), dim3(np, ngroups + 1), dim3(256), 0, st, static_cast<const QT*>(Q), ldq, n, m, w, r, scratch);
+    hipLaunchKernelGGL((k_gcr_dots<QT, 8, true>), dim3(np, ngroups + 1), dim3(256), 0, st, static_cast<const QT*>(Q), ldq, n, m, md, w, r, scratch);
   else
-    hipLaunchKernelGGL((k_gcr_dots<QT, 8, false>), dim3(np, ngroups + 1), dim3(256), 0, st, static_cast<const QT*>(Q), ldq, n, m, w, r, scratch);
+    hipLaunchKernelGGL((k_gcr_dots<QT, 8, false>), dim3(np, ngroups + 1), dim3(256), 0, st, static_cast<const QT*>(Q), ldq, n, m, md, w, r, scratch);
   hipLaunchKernelGGL(k_gcr_sum, dim3(m + 2), dim3(256), 0, st, scratch, np, out);
 }
 template <class QT>
-void axpy_t(hipStream_t st, const void* Q, int64_t ldq, int64_t n, int m, const double* h, double* w, const double* r,
+void axpy_t(hipStream_t st, const void* Q, int64_t ldq, int64_t n, int m, int md, const double* h, double* w, const double* r,
             double* scratch, double* out2) {
   int64_t blocks = ((n >> 2) + 255) / 256;
   if (blocks < 1) blocks = 1;
   if (blocks > 2048) blocks = 2048;               // 1024 ... 8192 measured: no difference
   if (stream_once<QT>(ldq, m))
-    hipLaunchKernelGGL((k_gcr_axpy<QT, true>), dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const QT*>(Q), ldq, n, m, h, w, r, scratch);
+    hipLaunchKernelGGL((k_gcr_axpy<QT, true>), dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const QT*>(Q), ldq, n, m, md, h, w, r, scratch);
   else
-    hipLaunchKernelGGL((k_gcr_axpy<QT, false>), dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const QT*>(Q), ldq, n, m, h, w, r, scratch);
+    hipLaunchKernelGGL((k_gcr_axpy<QT, false>), dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const QT*>(Q), ldq, n, m, md, h, w, r, scratch);
   hipLaunchKernelGGL(k_gcr_sum, dim3(2), dim3(256), 0, st, scratch, (int)blocks, out2);
 }
 template <class QT>
@@ -282,8 +303,12 @@ void update_t(hipStream_t st, void* Q, int64_t ldq, double* Z, int64_t ldz, int 
               const double* z, double inv_wn, double alpha, double* r, double* qd, double* scratch, double* out1) {
   int64_t blocks = (n + 255) / 256;
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(k_gcr_update<QT>, dim3((unsigned)blocks), dim3(256), 0, st, static_cast<QT*>(Q) + (int64_t)slot * ldq,
-                     Z + (int64_t)slot * ldz, n, w, z, inv_wn, alpha, r, qd, scratch);
+  if (qd)
+    hipLaunchKernelGGL((k_gcr_update<QT, true>), dim3((unsigned)blocks), dim3(256), 0, st, static_cast<QT*>(Q) + (int64_t)slot * ldq,
+                       Z + (int64_t)slot * ldz, n, w, z, inv_wn, alpha, r, qd, scratch);
+  else
+    hipLaunchKernelGGL((k_gcr_update<QT, false>), dim3((unsigned)blocks), dim3(256), 0, st, static_cast<QT*>(Q) + (int64_t)slot * ldq,
+                       Z + (int64_t)slot * ldz, n, w, z, inv_wn, alpha, r, qd, scratch);
   hipLaunchKernelGGL(k_gcr_sum, dim3(1), dim3(256), 0, st, scratch, (int)blocks, out1);
 }
 
@@ -291,13 +316,24 @@ void update_t(hipStream_t st, void* Q, int64_t ldq, double* Z, int64_t ldz, int 
 
 void launch_gcr_dots(hipStream_t st, bool fp32, const void* Q, int64_t ldq, int64_t n, int m, const double* w,
                      const double* r, double* scratch, double* out) {
-  if (fp32) dots_t<float>(st, Q, ldq, n, m, w, r, scratch, out);
-  else dots_t<double>(st, Q, ldq, n, m, w, r, scratch, out);
+  launch_gcr_dots_lead(st, fp32, Q, ldq, n, m, m, w, r, scratch, out);
+}
+// ... over m columns of which only the leading md hold data: the others are taken as zeros and not read
+void launch_gcr_dots_lead(hipStream_t st, bool fp32, const void* Q, int64_t ldq, int64_t n, int m, int md, const double* w,
+                          const double* r, double* scratch, double* out) {
+  md = std::max(0, std::min(md, m));
+  if (fp32) dots_t<float>(st, Q, ldq, n, m, md, w, r, scratch, out);
+  else dots_t<double>(st, Q, ldq, n, m, md, w, r, scratch, out);
 }
 void launch_gcr_axpy(hipStream_t st, bool fp32, const void* Q, int64_t ldq, int64_t n, int m, const double* h, double* w,
                      const double* r, double* scratch, double* out2) {
-  if (fp32) axpy_t<float>(st, Q, ldq, n, m, h, w, r, scratch, out2);
-  else axpy_t<double>(st, Q, ldq, n, m, h, w, r, scratch, out2);
+  launch_gcr_axpy_lead(st, fp32, Q, ldq, n, m, m, h, w, r, scratch, out2);
+}
+void launch_gcr_axpy_lead(hipStream_t st, bool fp32, const void* Q, int64_t ldq, int64_t n, int m, int md, const double* h, double* w,
+                          const double* r, double* scratch, double* out2) {
+  md = std::max(0, std::min(md, m));
+  if (fp32) axpy_t<float>(st, Q, ldq, n, m, md, h, w, r, scratch, out2);
+  else axpy_t<double>(st, Q, ldq, n, m, md, h, w, r, scratch, out2);
 }
 void launch_gcr_update(hipStream_t st, bool fp32, void* Q, int64_t ldq, double* Z, int64_t ldz, int slot, int64_t n,
                        const double* w, const double* z, double inv_wn, double alpha, double* r, double* qd,

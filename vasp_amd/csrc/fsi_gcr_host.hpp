@@ -28,6 +28,7 @@ struct GcrStore {
   std::vector<int32_t> free;           // free slots (retired in batches when the store is full)
   std::vector<int32_t> hot_slots;      // [GCR_WINDOW] slot of each window column (-1: empty)
   int hot_next = 0;
+  int32_t fresh = -1;                  // the slot hw - 1 while it has been taken beyond the high-water mark and its q column not written yet
 
   void init(int64_t cap_) {
     cap = cap_;
@@ -39,13 +40,16 @@ struct GcrStore {
     clear_window();
     made = 0;
     hw = 0;
+    fresh = -1;
     free.clear();
     std::fill(born.begin(), born.end(), (int64_t)-1);
   }
   bool full() const { return free.empty() && hw == cap; }
   int64_t kept() const { return hw - (int64_t)free.size(); }
   // a slot for a new direction: the free list's back, else the high-water mark.  *clear: the slot's q column has never been
-  // written - garbage the kernels are about to scan - and must be zeroed first (a retired column was zeroed when it left)
+  // written (a retired column was zeroed when it left).  It is the last of the hw columns, and the Gram-Schmidt kernels are
+  // told to take it as zeros without reading it - lead() - until the update kernel has written it (set_born); an iteration
+  // that leaves before that hands the slot to abandon() and zeroes the column it names, so that no later scan meets garbage.
   int take(bool* clear) {
     *clear = free.empty();
     if (!free.empty()) {
@@ -54,11 +58,22 @@ struct GcrStore {
       return slot;
     }
     hw += 1;
+    fresh = (int32_t)hw - 1;
     return (int)hw - 1;
   }
+  // the leading columns that hold data (directions, or the zeros of retired ones): all hw but an unwritten fresh slot
+  int64_t lead() const { return fresh >= 0 ? hw - 1 : hw; }
   void set_born(int slot) {
     born[slot] = made;
     made += 1;
+    if (slot == fresh) fresh = -1;
+  }
+  // the iteration that took `slot` ends without writing it: the column to zero now, or -1 (a retired slot's column is zero already).
+  // The slot stays taken, as it always did: hw, and with it every count of columns scanned, moves as before.
+  int abandon(int slot) {
+    if (slot < 0 || slot != fresh) return -1;
+    fresh = -1;
+    return slot;
   }
   // retire the oldest directions of the rotating part (everything explicit: call after a flush); the caller zeroes the columns
   std::vector<int32_t> retire(int batch) {

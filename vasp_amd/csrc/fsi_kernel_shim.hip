@@ -120,7 +120,31 @@ int shim_gcr_axpy(int fp32, const void* Q, int64_t ldq, int64_t n, int m, const 
   double* dout = c.io(out2, (size_t)nout);
   SHIM_RUN(c, "launch_gcr_axpy", launch_gcr_axpy(c.st, fp32 != 0, dQ, ldq, n, m, dh, dw, dr, scratch, dout));
 }
-// Q: ncols columns of ldq (in place), Z: ncols columns of ldz (in place), r, qd (n, in place); out1: nout >= 1
+// the two above over m columns of which the leading md hold data (launch_gcr_dots_lead / launch_gcr_axpy_lead)
+int shim_gcr_dots_lead(int fp32, const void* Q, int64_t ldq, int64_t n, int m, int md, const double* w, const double* r, double* out,
+                       int64_t nout) {
+  Call c;
+  const void* dQ = c.in(static_cast<const char*>(Q), (size_t)ldq * (size_t)m * (fp32 ? 4 : 8));
+  const double* dw = c.in(w, (size_t)n);
+  const double* dr = c.in(r, (size_t)n);
+  std::vector<double> hs((size_t)(m + 2) * 1024 + 16);
+  double* scratch = c.in(hs.data(), hs.size());
+  double* dout = c.io(out, (size_t)nout);
+  SHIM_RUN(c, "launch_gcr_dots_lead", launch_gcr_dots_lead(c.st, fp32 != 0, dQ, ldq, n, m, md, dw, dr, scratch, dout));
+}
+int shim_gcr_axpy_lead(int fp32, const void* Q, int64_t ldq, int64_t n, int m, int md, const double* h, double* w, const double* r,
+                       double* out2, int64_t nout) {
+  Call c;
+  const void* dQ = c.in(static_cast<const char*>(Q), (size_t)ldq * (size_t)m * (fp32 ? 4 : 8));
+  const double* dh = c.in(h, (size_t)(m > 0 ? m : 0));
+  double* dw = c.io(w, (size_t)n);
+  const double* dr = c.in(r, (size_t)n);
+  std::vector<double> hs(2 * 2048 + 16);
+  double* scratch = c.in(hs.data(), hs.size());
+  double* dout = c.io(out2, (size_t)nout);
+  SHIM_RUN(c, "launch_gcr_axpy_lead", launch_gcr_axpy_lead(c.st, fp32 != 0, dQ, ldq, n, m, md, dh, dw, dr, scratch, dout));
+}
+// Q: ncols columns of ldq (in place), Z: ncols columns of ldz (in place), r, qd (n, in place; qd may be null); out1: nout >= 1
 int shim_gcr_update(int fp32, void* Q, int64_t ldq, double* Z, int64_t ldz, int ncols, int slot, int64_t n, const double* w,
                     const double* z, double inv_wn, double alpha, double* r, double* qd, double* out1, int64_t nout) {
   Call c;
@@ -504,7 +528,8 @@ int shim_cheb_coefficients(double lmax, double kappa, int fourth, int n, double*
 // One operation on a store the shim keeps, then the store's whole state: born [cap], free [cap] (the first scal[3] entries),
 // hot [GCR_WINDOW], scal = {hw, made, hot_next, free.size()}.  op 0 init(arg), 1 full() -> res[0], 2 take() -> res[0] slot,
 // res[1] clear, 3 retire(arg) -> res[0] count, res[1..] slots, 4 window_put(arg) -> res[0] column, 5 window_drop_retired() ->
-// res[0] count, res[1..] columns, 6 set_born(arg), 7 window_cols() -> res[0], 8 reset(), 9 clear_window().  res: [cap + 1] at least.
+// res[0] count, res[1..] columns, 6 set_born(arg), 7 window_cols() -> res[0], 8 reset(), 9 clear_window(), 10 lead() -> res[0],
+// 11 abandon(arg) -> res[0] the column to zero or -1.  res: [cap + 1] at least.
 int shim_gcr_store_op(int op, int64_t arg, int32_t* res, int64_t* born, int32_t* free_slots, int32_t* hot, int64_t* scal) {
   static GcrStore s;
   if (op != 0 && s.cap == 0) { g_err = "shim_gcr_store_op: no store (op 0 first)"; return 1; }
@@ -519,6 +544,8 @@ int shim_gcr_store_op(int op, int64_t arg, int32_t* res, int64_t* born, int32_t*
     case 7: res[0] = s.window_cols(); break;
     case 8: s.reset(); break;
     case 9: s.clear_window(); break;
+    case 10: res[0] = (int32_t)s.lead(); break;
+    case 11: res[0] = s.abandon((int)arg); break;
     default: g_err = "shim_gcr_store_op: unknown operation"; return 1;
   }
   std::copy(s.born.begin(), s.born.end(), born);
@@ -638,6 +665,48 @@ int shim_drows_extract(int64_t N2, const int64_t* rowptr, const double* A, const
   float* d32 = c.io(ad32, (size_t)(6 * npairs));
   int32_t* df = c.io(flag, 1);
   SHIM_RUN(c, "launch_drows_extract", launch_drows_extract(c.st, N2, drp, dA, dnp, d64, d32, df));
+}
+// the split pair form as a refresh builds it: launch_drows_extract_split, launch_drows_offsets and, when doff[N2] <= dvcap pairs,
+// launch_drows_gather_dv.  Node rows only as above; dd [3 npairs], cdeg [N2], doff [N2 + 1], dv [3 dvcap]
+int shim_drows_split(int64_t N2, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr, double* ad64, int32_t* flag,
+                     double* dd, int32_t* cdeg, int64_t* doff, double* dv, int64_t dvcap) {
+  Call c;
+  const int64_t npairs = nadj_ptr[N2];
+  const int64_t* drp = c.in(rowptr, (size_t)(6 * N2) + 1);
+  const double* dA = c.in(A, (size_t)rowptr[6 * N2]);
+  const int64_t* dnp = c.in(nadj_ptr, (size_t)N2 + 1);
+  double* d64 = c.io(ad64, (size_t)(6 * npairs));
+  int32_t* df = c.io(flag, 1);
+  double* ddd = c.io(dd, (size_t)(3 * npairs));
+  int32_t* dcd = c.io(cdeg, (size_t)N2);
+  int64_t* dof = c.io(doff, (size_t)N2 + 1);
+  double* ddv = c.io(dv, (size_t)(3 * dvcap));
+  if (c.ok()) {
+    launch_drows_extract_split(c.st, N2, drp, dA, dnp, d64, nullptr, df, ddd, dcd);
+    launch_drows_offsets(c.st, N2, dcd, dof);
+    int64_t total = -1;
+    c.note(hipMemcpyAsync(&total, dof + N2, sizeof total, hipMemcpyDeviceToHost, c.st));
+    c.note(hipStreamSynchronize(c.st));
+    if (c.ok() && total > 0 && total <= dvcap) launch_drows_gather_dv(c.st, N2, dnp, dof, d64, ddv);
+  }
+  return c.finish("launch_drows_extract_split / launch_drows_offsets / launch_drows_gather_dv");
+}
+// launch_spmv_node6s: dd [3 npairs], dv [3 ndv] (may be null), doff [N2 + 1]; the rest as shim_spmv_node6
+int shim_spmv_node6s(int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals, const int32_t* vrank,
+                     const int64_t* nadj_ptr, const int32_t* nadj, int64_t npairs, const double* x, double* y, const double* dd,
+                     const double* dv, int64_t ndv, const int64_t* doff) {
+  Call c;
+  const int64_t n = 6 * N2 + V;
+  const int64_t* drp = c.in(rowptr, (size_t)n + 1);
+  const int32_t* dc = c.in(cols, (size_t)rowptr[n]);
+  const double* dvl = c.in(vals, (size_t)rowptr[n]);
+  const PRowGraph g{c.in(vrank, (size_t)V), c.in(nadj_ptr, (size_t)N2 + 1), c.in(nadj, (size_t)npairs)};
+  const double* dx = c.in(x, (size_t)n);
+  double* dy = c.io(y, (size_t)n);
+  const double* ddd = c.in(dd, (size_t)(3 * npairs));
+  const double* ddv = c.in(dv, (size_t)(3 * ndv));
+  const int64_t* dof = c.in(doff, (size_t)N2 + 1);
+  SHIM_RUN_STATUS(c, "launch_spmv_node6s", launch_spmv_node6s(c.st, N2, V, drp, dc, dvl, g, dx, dy, ddd, ddv, dof));
 }
 // p32 [N2 + 1] (entries, six value rows per node block); cols32 [p32[N2] / 6]
 int shim_pad_cols32(int64_t N2, const int64_t* rowptr, const int32_t* cols, const int64_t* p32, int32_t* cols32) {

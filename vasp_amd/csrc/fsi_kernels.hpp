@@ -202,6 +202,15 @@ void launch_pad_vals32(hipStream_t st, int64_t N2, int64_t V, const int64_t* row
 // something else and the products must keep the full rows
 void launch_drows_extract(hipStream_t st, int64_t N2, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr, double* ad64,
                           float* ad32, int32_t* flag);
+// The pair form split (FP64): dd [pairs][3] for every node and dv [pairs of coupled nodes][3], a node being coupled when any dv
+// entry of its three d rows is not exactly zero - found from the values at every refresh, like the verdict in `flag`.
+//   launch_drows_extract_split   launch_drows_extract, and dd and cdeg [N2]: the node's degree if it is coupled, else 0
+//   launch_drows_offsets         doff [N2 + 1]: first pair of node r in dv, -1 for an uncoupled node; doff[N2] = pairs in dv
+//   launch_drows_gather_dv       dv from the pair form ad64 through doff (dv holds at least doff[N2] pairs)
+void launch_drows_extract_split(hipStream_t st, int64_t N2, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr,
+                                double* ad64, float* ad32, int32_t* flag, double* dd, int32_t* cdeg);
+void launch_drows_offsets(hipStream_t st, int64_t N2, const int32_t* cdeg, int64_t* doff);
+void launch_drows_gather_dv(hipStream_t st, int64_t N2, const int64_t* nadj_ptr, const int64_t* doff, const double* ad64, double* dv);
 // status of the products that can refuse their arguments: 0 launched, LAUNCH_REFUSED nothing launched (d rows in pair form without
 // the node graph they are indexed by)
 constexpr int LAUNCH_REFUSED = 2;
@@ -223,7 +232,13 @@ void launch_gcr_dots(hipStream_t st, bool fp32, const void* Q, int64_t ldq, int6
 // w -= sum_k h[k] Q_k; out2[0] = |w'|^2, out2[1] = w' . r
 void launch_gcr_axpy(hipStream_t st, bool fp32, const void* Q, int64_t ldq, int64_t n, int m, const double* h, double* w,
                      const double* r, double* scratch, double* out2);
-// Q_slot = qd = w * inv_wn, Z_slot = z, r -= alpha w * inv_wn; out1[0] = |r'|^2
+// the same two over m columns of which only the leading md (0 <= md <= m) hold data: the columns behind them are taken as
+// zeros and never read (the slot just taken beyond the store's high-water mark); sums grouped and rounded as with stored zeros
+void launch_gcr_dots_lead(hipStream_t st, bool fp32, const void* Q, int64_t ldq, int64_t n, int m, int md, const double* w,
+                          const double* r, double* scratch, double* out);
+void launch_gcr_axpy_lead(hipStream_t st, bool fp32, const void* Q, int64_t ldq, int64_t n, int m, int md, const double* h, double* w,
+                          const double* r, double* scratch, double* out2);
+// Q_slot = qd = w * inv_wn, Z_slot = z, r -= alpha w * inv_wn; out1[0] = |r'|^2.  qd may be null: q goes to the column only
 void launch_gcr_update(hipStream_t st, bool fp32, void* Q, int64_t ldq, double* Z, int64_t ldz, int slot, int64_t n,
                        const double* w, const double* z, double inv_wn, double alpha, double* r, double* qd,
                        double* scratch, double* out1);
@@ -342,6 +357,9 @@ void launch_residual_rows(hipStream_t st, int64_t nrows, const int32_t* rows, co
                           const int64_t* src, const double* vals, const double* x, const double* b, double* y);
 int launch_spmv_node6(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals,
                       const PRowGraph& g, const double* x, double* y, const double* ad64 = nullptr);      // status: LAUNCH_REFUSED above
+// ... with the d rows from the split pair form (launch_drows_extract_split): bit for bit what the pair form gives
+int launch_spmv_node6s(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals,
+                       const PRowGraph& g, const double* x, double* y, const double* dd, const double* dv, const int64_t* doff);
 void launch_sweep_csr_mixed(hipStream_t st, int64_t n, const int64_t* rowptr, const int32_t* cols, const float* vals,
                             const int64_t* diagpos, const double* dvals, double c1, double c2, const double* din, double* dout,
                             double* x, double* r);

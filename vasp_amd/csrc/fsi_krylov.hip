@@ -25,8 +25,12 @@ int spmv(FsiCtx* ctx, const double* x, double* y, bool working) {
     if (ctx->drows_ok) ctx->drows_products += 1;
     return FSI_OK;
   }
-  // (drows_ok: the d rows from their pair form - six values per node pair, checked at the refresh - instead of 18 + pressure columns)
-  if (launch_spmv_node6(ctx->stream, ctx->N2, ctx->V, ctx->rowptr.p, ctx->cols.p, ctx->A.p, g, x, y, ctx->drows_ok ? ctx->Ad64.p : nullptr) != 0) {
+  // (drows_ok: the d rows from their pair form - six values per node pair, checked at the refresh - instead of 18 + pressure columns;
+  // drows_split_ok: three per pair on the nodes whose dv values are all zero, the same bits)
+  const int rc = ctx->drows_ok && ctx->drows_split_ok
+                     ? launch_spmv_node6s(ctx->stream, ctx->N2, ctx->V, ctx->rowptr.p, ctx->cols.p, ctx->A.p, g, x, y, ctx->Add.p, ctx->Adv3.p, ctx->drows_off.p)
+                     : launch_spmv_node6(ctx->stream, ctx->N2, ctx->V, ctx->rowptr.p, ctx->cols.p, ctx->A.p, g, x, y, ctx->drows_ok ? ctx->Ad64.p : nullptr);
+  if (rc != 0) {
     ctx->err = "spmv: d rows in pair form without the node graph";
     return FSI_ERR_INVALID;
   }
@@ -75,7 +79,7 @@ struct Cycle {
   double reorth = 0.0;
   double rn2 = 0.0, r_entry = 0.0, rnorm = 0.0;
   const double* src = nullptr; // what the next direction is made from
-  double* qd = nullptr;        // where the update kernel leaves the exact q
+  double* qd = nullptr;        // where the update kernel leaves the exact q: a window column (FP32 basis) or the store column itself
   bool rr_pending = false;     // partitioned: the last update's local |r|^2 has not been all-reduced yet (it rides with the next pass)
   // the iteration under way
   int slot = 0, m = 0;         // the new direction's slot; columns scanned
@@ -102,6 +106,7 @@ struct GsBasis {
   const void* Q;
   bool f32;            // storage of the columns
   int cols;
+  int lead;            // how many of them, from the first, hold data; the others are taken as zeros unread (GcrStore::lead)
   double* hcoef;       // device [gcr_coef_len(cols)]
   double* stage;       // pinned [gcr_coef_len(cols)]: where the host finds the coefficients and |w|^2, w.r (GcrStaging)
   int weight;          // ortho_q_cols counts a column this many times (FP64 columns counted as two FP32 ones)
@@ -118,9 +123,11 @@ struct GsPass {
   bool defer = false;               // none: leave the read queued - the next pass's wait brings it (stream order: the copy sees the values before hcoef is reused)
   bool entry = false;               // the projection on entry: the caller brackets the whole pass, waits included, and its reductions are not the iterations'
 };
-GsBasis store_basis(FsiCtx* ctx, int m) { return {ctx->KQ.p, ctx->kry_fp32 != 0, m, ctx->hcoef.p, ctx->gcr_host, 1}; }
+GsBasis store_basis(FsiCtx* ctx, int m) {
+  return {ctx->KQ.p, ctx->kry_fp32 != 0, m, (int)std::min<int64_t>(m, ctx->kry.lead()), ctx->hcoef.p, ctx->gcr_host, 1};
+}
 GsBasis window_basis(FsiCtx* ctx, int nh) {
-  return {ctx->KQh.p, false, nh, ctx->hcoef_hot.p, ctx->gcr_host + GcrStaging{ctx->kry.cap}.window(), 2};
+  return {ctx->KQh.p, false, nh, nh, ctx->hcoef_hot.p, ctx->gcr_host + GcrStaging{ctx->kry.cap}.window(), 2};
 }
 
 // after[0..2): |w'|^2 and w'.r as the update kernel measured them (p.after > 0 and not deferred)
@@ -133,8 +140,8 @@ int gs_pass(FsiCtx* ctx, const GsPass& p, double* after) {
   const int nsum = (int)lag, nred = nsum + (p.lagged_slot ? 1 : 0);             // the coefficients and their two sums; what a reduction carries
   double* hh = b.stage;
   int launches = 0;
-  auto dots = [&](const double* r) { launch_gcr_dots(st, b.f32, b.Q, ctx->ldq, n, m, p.w, r, ctx->scratch.p, b.hcoef); launches += 1; };
-  auto axpy = [&] { launch_gcr_axpy(st, b.f32, b.Q, ctx->ldq, n, m, b.hcoef, p.w, p.r, ctx->scratch.p, p.out); launches += 1; };
+  auto dots = [&](const double* r) { launch_gcr_dots_lead(st, b.f32, b.Q, ctx->ldq, n, m, b.lead, p.w, r, ctx->scratch.p, b.hcoef); launches += 1; };
+  auto axpy = [&] { launch_gcr_axpy_lead(st, b.f32, b.Q, ctx->ldq, n, m, b.lead, b.hcoef, p.w, p.r, ctx->scratch.p, p.out); launches += 1; };
   // The phase timer brackets the kernels only, not the host's wait.
   auto timed = [&](auto&& launch) {
     if (p.entry) { launch(); return; }
@@ -271,10 +278,18 @@ int gcr_make_room(FsiCtx* ctx, Cycle& c) {
   }
   bool clear = false;
   c.slot = s.take(&clear);
-  // the slot's old q column is zero (retired) or about to be scanned as garbage: a fresh slot beyond the previous
-  // high-water mark must not contribute, so it is cleared once here
-  if (clear) HIPCHK(hipMemsetAsync(ctx->KQ.p + (size_t)c.slot * ctx->ldq * qbytes(ctx), 0, (size_t)ctx->ldq * qbytes(ctx), st));
+  // the slot's old q column is zero (retired) or has never been written: a fresh slot beyond the previous high-water mark must
+  // not contribute, and does not - the store tells the Gram-Schmidt kernels to take it as zeros without reading it
+  // (GcrStore::lead via store_basis) until gcr_store's update kernel has written it in full
   c.m = (int)s.hw;
+  return FSI_OK;
+}
+
+// the iteration under way ends before gcr_store: a fresh slot's column, which nothing has written, is zeroed as the columns
+// of retired slots are, because the slot stays inside the scanned range
+int gcr_abandon_slot(FsiCtx* ctx, Cycle& c) {
+  const int slot = ctx->kry.abandon(c.slot);
+  if (slot >= 0) HIPCHK(hipMemsetAsync(ctx->KQ.p + (size_t)slot * ctx->ldq * qbytes(ctx), 0, (size_t)ctx->ldq * qbytes(ctx), ctx->stream));
   return FSI_OK;
 }
 
@@ -357,9 +372,12 @@ int gcr_orthogonalise(FsiCtx* ctx, Cycle& c, double* w) {
 int gcr_store(FsiCtx* ctx, Cycle& c, const double* z, const double* w) {
   const bool f32 = ctx->kry_fp32 != 0;
   const double alpha = c.wr / c.wn;          // q . r with q = w / wn
-  if (f32) c.qd = ctx->KQh.p + (size_t)ctx->kry.window_put(c.slot) * ctx->ldq;      // the exact q goes into the FP64 window (ring of 32)
-  launch_gcr_update(ctx->stream, f32, ctx->KQ.p, ctx->ldq, ctx->KZ.p, ctx->ldz, c.slot, ctx->ndof, w, z, 1.0 / c.wn, alpha, c.r, c.qd,
-                    ctx->scratch.p, ctx->gcr_out.p + 4);
+  // the exact q: with an FP32 basis it goes into the FP64 window (ring of 32) beside the rounded column; an FP64 column IS the
+  // exact q, written once, and an Arnoldi step below reads it where it is
+  if (f32) c.qd = ctx->KQh.p + (size_t)ctx->kry.window_put(c.slot) * ctx->ldq;
+  else c.qd = reinterpret_cast<double*>(ctx->KQ.p) + (size_t)c.slot * ctx->ldq;
+  launch_gcr_update(ctx->stream, f32, ctx->KQ.p, ctx->ldq, ctx->KZ.p, ctx->ldz, c.slot, ctx->ndof, w, z, 1.0 / c.wn, alpha, c.r,
+                    f32 ? c.qd : nullptr, ctx->scratch.p, ctx->gcr_out.p + 4);
   c.src = c.r;
   // A direction that left the residual where it was (alpha^2 below 1e-3 |r|^2): A M^-1 r lies in the kept space, and as r
   // has not moved the next A M^-1 r is the same vector again - GCR proper cannot leave this point (seen on the 100 k-tet
@@ -411,7 +429,6 @@ int gcr_cycle(FsiCtx* ctx, double* r, double* x, double target, double rtol_floo
   // of little progress) - measured on the 6.6 k-tet fixture: twice the iterations and stagnation near 1e-3, because the
   // FP32 sweeps of the preconditioner resolve what is large in their input, and only the residual has the components
   // that still matter as its large ones.
-  c.qd = ctx->tmp5.p;
   c.src = r;
   double best = c.rnorm;
   int since_gain = 0;
@@ -423,8 +440,9 @@ int gcr_cycle(FsiCtx* ctx, double* r, double* x, double target, double rtol_floo
     if (end == GcrEnd::stalled) { ctx->gcr_stalled = true; break; }
     FSICHK(gcr_precondition_product(ctx, c, z, w));
     FSICHK(gcr_make_room(ctx, c));
-    FSICHK(gcr_orthogonalise(ctx, c, w));
+    if (const int rc = gcr_orthogonalise(ctx, c, w)) { (void)gcr_abandon_slot(ctx, c); return rc; }
     if (!(c.wn > 0.0) || !std::isfinite(c.wn)) {
+      FSICHK(gcr_abandon_slot(ctx, c));
       char buf[200];
       snprintf(buf, sizeof buf, "GCR breakdown (A M^-1 r vanished or is not finite): |w'| %.3e, |w| %.3e, w.r %.3e, %d kept, iteration %d", c.wn, c.w0, c.wr, c.m, *iters);
       ctx->err = buf;

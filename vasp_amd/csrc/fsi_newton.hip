@@ -61,6 +61,7 @@ int fsi_assemble_jacobian(FsiCtx* ctx) {
   // the d rows in pair form for the outer products (FsiTuning.compact_drows): extracted from THIS matrix, and adopted only if the
   // kernel found nothing else in those rows (one flag read per refresh)
   ctx->drows_ok = false;
+  ctx->drows_split_ok = false;
   if (getenv("FSI_DEBUG_DROWS_INJECT") && ctx->nnz > 1) {
     // test hook: a value where the forms leave a structural zero - entry 1 of the first d row (column d_y of node 0's first
     // neighbour in a d_x row) - so that the check below has a matrix to refuse
@@ -77,12 +78,27 @@ int fsi_assemble_jacobian(FsiCtx* ctx) {
     if (!ctx->Ad64.p) HIPCHK(ctx->Ad64.alloc(npairs6));
     if (copy32 && !ctx->Ad32.p) HIPCHK(ctx->Ad32.alloc(npairs6));
     HIPCHK(hipMemsetAsync(ctx->iflags.p + FsiCtx::IFLAG_DROWS, 0, sizeof(int32_t), ctx->stream));
-    launch_drows_extract(ctx->stream, ctx->N2, ctx->rowptr.p, ctx->A.p, ctx->nadj_ptr.p, ctx->Ad64.p, copy32 ? ctx->Ad32.p : nullptr, ctx->iflags.p + FsiCtx::IFLAG_DROWS);
+    // ... and split for the FP64 products: dd for every pair, the nodes classified by their dv values, offsets by a scan
+    if (!ctx->Add.p) HIPCHK(ctx->Add.alloc(npairs6 / 2));
+    if (!ctx->drows_cdeg.p) HIPCHK(ctx->drows_cdeg.alloc((size_t)ctx->N2));
+    if (!ctx->drows_off.p) HIPCHK(ctx->drows_off.alloc((size_t)ctx->N2 + 1));
+    launch_drows_extract_split(ctx->stream, ctx->N2, ctx->rowptr.p, ctx->A.p, ctx->nadj_ptr.p, ctx->Ad64.p, copy32 ? ctx->Ad32.p : nullptr,
+                               ctx->iflags.p + FsiCtx::IFLAG_DROWS, ctx->Add.p, ctx->drows_cdeg.p);
+    launch_drows_offsets(ctx->stream, ctx->N2, ctx->drows_cdeg.p, ctx->drows_off.p);
     int32_t found = 1;
+    int64_t coupled_pairs = -1;
     HIPCHK(hipMemcpyAsync(&found, ctx->iflags.p + FsiCtx::IFLAG_DROWS, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&coupled_pairs, ctx->drows_off.p + ctx->N2, sizeof coupled_pairs, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ctx->drows_ok = found == 0;
-    if (getenv("FSI_DEBUG")) fprintf(stderr, "[fsi] displacement rows of the outer product in pair form: %s\n", ctx->drows_ok ? "yes" : "no (other entries found)");
+    ctx->drows_split_ok = false;
+    if (ctx->drows_ok && coupled_pairs >= 0 && (size_t)coupled_pairs <= ctx->nadj.n) {
+      if (3 * (size_t)coupled_pairs > ctx->Adv3.n) HIPCHK(ctx->Adv3.alloc(3 * (size_t)coupled_pairs));
+      if (coupled_pairs > 0) launch_drows_gather_dv(ctx->stream, ctx->N2, ctx->nadj_ptr.p, ctx->drows_off.p, ctx->Ad64.p, ctx->Adv3.p);
+      ctx->drows_split_ok = true;
+    }
+    if (getenv("FSI_DEBUG")) fprintf(stderr, "[fsi] displacement rows of the outer product in pair form: %s; %lld of %lld pairs belong to nodes with dv entries\n",
+                                     ctx->drows_ok ? "yes" : "no (other entries found)", (long long)coupled_pairs, (long long)ctx->nadj.n);
   }
   if (copy32) {
     launch_pad_vals32(ctx->stream, ctx->N2, ctx->V, ctx->rowptr.p, ctx->A.p, ctx->a32_ptr.p, ctx->a32_ptail, ctx->a32_tail_nnz,

@@ -252,15 +252,22 @@ __global__ __launch_bounds__(256) void k_spmv_node6(int64_t N2, const int64_t* _
 // neighbour): 24 deg + 3 pdeg values + 6 deg pair values per node instead of 36 deg + 6 pdeg.
 // (Round 2's "compact node rows" re-laid ALL 24 non-zeros as 24 short runs per node and was latency-bound: 3.46 against 3.20 ms.
 // Here the v rows keep their three long streams.)
+// The split form (dd != nullptr; FP64 products): A_dv has entries in the rows of solid nodes only, so on a fluid node - nine in ten
+// on the bench mesh - the dv half of every pair is three exact zeros.  The kernel also writes dd [pairs][3] and classifies each node
+// FROM THE VALUES IT READS: cdeg[r] = its degree if any dv entry of its three d rows is non-zero ("coupled"), else 0.  A scan turns
+// cdeg into offsets (k_drows_offsets: doff[r] = first pair of r in dv, -1 for an uncoupled node) and k_drows_gather_dv copies the dv
+// halves of the coupled nodes to dv [coupled pairs][3].  k_spmv_node6s then reads 24 bytes per pair on an uncoupled node instead of 48.
 template <class DT>
 __global__ __launch_bounds__(256) void k_drows_extract(int64_t N2, const int64_t* __restrict__ rowptr, const double* __restrict__ A,
                                                        const int64_t* __restrict__ nadj_ptr, double* __restrict__ ad64,
-                                                       DT* __restrict__ ad32, int32_t* __restrict__ flag) {
+                                                       DT* __restrict__ ad32, int32_t* __restrict__ flag, double* __restrict__ dd,
+                                                       int32_t* __restrict__ cdeg) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   bool bad = false;
   for (int64_t r = wave; r < N2; r += nwaves) {
     const int64_t s0 = rowptr[6 * r], L = rowptr[6 * r + 1] - s0, a = nadj_ptr[r], deg6 = 6 * (nadj_ptr[r + 1] - a);
+    bool coupled = false;
     for (int i = 0; i < 3; ++i)
       for (int64_t t = lane; t < L; t += 64) {
         const double v = A[s0 + i * L + t];
@@ -269,16 +276,80 @@ __global__ __launch_bounds__(256) void k_drows_extract(int64_t N2, const int64_t
           const int64_t o = 6 * (a + t / 6) + (c == i ? i : 3 + i);
           ad64[o] = v;
           if (ad32) ad32[o] = (DT)v;
+          if (dd && c == i) dd[3 * (a + t / 6) + i] = v;
+          if (c != i && v != 0.0) coupled = true;
         } else if (v != 0.0) bad = true;
       }
+    if (cdeg) {                                                   // (r is the wave's: every lane is here)
+      const bool any = __ballot(coupled) != 0;
+      if (lane == 0) cdeg[r] = any ? (int32_t)(deg6 / 6) : 0;
+    }
   }
   if (bad) atomicOr(flag, 1);
 }
-void launch_drows_extract(hipStream_t st, int64_t N2, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr, double* ad64,
-                          float* ad32, int32_t* flag) {
+void launch_drows_extract_split(hipStream_t st, int64_t N2, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr,
+                                double* ad64, float* ad32, int32_t* flag, double* dd, int32_t* cdeg) {
   int64_t blocks = std::min<int64_t>((N2 + 3) / 4, 16384);
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_drows_extract<float>, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, A, nadj_ptr, ad64, ad32, flag);
+  hipLaunchKernelGGL(k_drows_extract<float>, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, A, nadj_ptr, ad64, ad32, flag, dd, cdeg);
+}
+void launch_drows_extract(hipStream_t st, int64_t N2, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr, double* ad64,
+                          float* ad32, int32_t* flag) {
+  launch_drows_extract_split(st, N2, rowptr, A, nadj_ptr, ad64, ad32, flag, nullptr, nullptr);
+}
+// doff[r] = sum of cdeg[0 .. r) where cdeg[r] > 0, else -1; doff[N2] = the whole sum.  One block: the scan runs once per Jacobian
+// over one number per node, in tiles of 8192 nodes with the running sum carried along.
+__global__ __launch_bounds__(1024) void k_drows_offsets(int64_t N2, const int32_t* __restrict__ cdeg, int64_t* __restrict__ doff) {
+  __shared__ int64_t wsum[16];
+  __shared__ int64_t carry;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (int64_t base = 0; base < N2; base += 8192) {              // eight consecutive nodes per thread
+    const int64_t i0 = base + 8 * (int64_t)threadIdx.x;
+    int32_t c[8];
+    int64_t mine = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { c[j] = i0 + j < N2 ? cdeg[i0 + j] : 0; mine += c[j]; }
+    int64_t incl = mine;                                         // inclusive scan inside the wave
+    for (int off = 1; off < 64; off <<= 1) {
+      const int64_t up = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += up;
+    }
+    if (lane == 63) wsum[wv] = incl;
+    __syncthreads();
+    int64_t before = carry;
+    for (int k = 0; k < wv; ++k) before += wsum[k];
+    int64_t at = before + incl - mine;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (i0 + j < N2) doff[i0 + j] = c[j] > 0 ? at : -1;
+      at += c[j];
+    }
+    __syncthreads();
+    if (threadIdx.x == 1023) carry = before + incl;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) doff[N2] = carry;
+}
+void launch_drows_offsets(hipStream_t st, int64_t N2, const int32_t* cdeg, int64_t* doff) {
+  hipLaunchKernelGGL(k_drows_offsets, dim3(1), dim3(1024), 0, st, N2, cdeg, doff);
+}
+__global__ __launch_bounds__(256) void k_drows_gather_dv(int64_t N2, const int64_t* __restrict__ nadj_ptr, const int64_t* __restrict__ doff,
+                                                         const double* __restrict__ ad64, double* __restrict__ dv) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t r = wave; r < N2; r += nwaves) {
+    const int64_t o = doff[r];
+    if (o < 0) continue;
+    const int64_t a = nadj_ptr[r], deg = nadj_ptr[r + 1] - a;
+    for (int64_t t = lane; t < 3 * deg; t += 64) dv[3 * o + t] = ad64[6 * (a + t / 3) + 3 + t % 3];
+  }
+}
+void launch_drows_gather_dv(hipStream_t st, int64_t N2, const int64_t* nadj_ptr, const int64_t* doff, const double* ad64, double* dv) {
+  int64_t blocks = std::min<int64_t>((N2 + 3) / 4, 16384);
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_drows_gather_dv, dim3((unsigned)blocks), dim3(256), 0, st, N2, nadj_ptr, doff, ad64, dv);
 }
 // the d rows of node r from the pair array: lane k takes neighbour k (AT: double | float)
 template <class AT>
@@ -334,6 +405,73 @@ __global__ __launch_bounds__(256) void k_spmv_node6c(int64_t N2, const int64_t* 
     const double* v = vals + s0 + 3 * L;
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0, a5 = 0.0;
     drows_pairs<double>(ad, nadj, a, deg, lane, x, a0, a1, a2);
+    for (int64_t t = lane; t < L; t += 64) {
+      const double xv = x[cols[s0 + t]];
+      a3 += v[t] * xv; a4 += v[L + t] * xv; a5 += v[2 * L + t] * xv;
+    }
+    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3); a4 = wave_sum(a4); a5 = wave_sum(a5);
+    if (lane == 0) { double* o = y + 6 * r; o[0] = a0; o[1] = a1; o[2] = a2; o[3] = a3; o[4] = a4; o[5] = a5; }
+  }
+}
+// The d rows of node r from the split pair form (k_drows_extract with dd): o = doff[r] is wave-uniform.  What the six-value form
+// computes per pair is  t = fma(d, x_d, v * x_v)  and then  a + t  (the ISA of drows_pairs: v_mul_f64, v_fma_f64, v_add_f64 - the sum
+// of two products contracts to one FMA, the accumulation cannot).  With v == 0 that t is the ROUNDED product d * x_d, so the
+// uncoupled node does one multiply and one add, kept apart (an FMA into the accumulator would round once instead of twice); the
+// coupled node spells the same three operations out.  The results are those of drows_pairs bit for bit: an accumulator that starts
+// as +0 never becomes -0, so not even the sign of the zero  v * x_v  shows.
+__device__ inline void drows_split(const double* __restrict__ dd, const double* __restrict__ dv, int64_t o,
+                                   const int32_t* __restrict__ nadj, int64_t a, int64_t deg, int lane,
+                                   const double* __restrict__ x, double& a0, double& a1, double& a2) {
+#pragma clang fp contract(off)
+  if (o < 0) {
+    for (int64_t k = lane; k < deg; k += 64) {
+      const double* xp = x + 6 * (int64_t)nadj[a + k];
+      const double* p = dd + 3 * (a + k);
+      const double d0 = p[0], d1 = p[1], d2 = p[2];
+      const double2 x0 = *reinterpret_cast<const double2*>(xp);      // d_x d_y | d_z of the neighbour
+      const double x2 = xp[2];
+      const double t0 = d0 * x0.x, t1 = d1 * x0.y, t2 = d2 * x2;
+      a0 = a0 + t0; a1 = a1 + t1; a2 = a2 + t2;
+    }
+  } else {
+    for (int64_t k = lane; k < deg; k += 64) {
+      const double2* xp = reinterpret_cast<const double2*>(x + 6 * (int64_t)nadj[a + k]);
+      const double* p = dd + 3 * (a + k);
+      const double* q = dv + 3 * (o + k);
+      const double d0 = p[0], d1 = p[1], d2 = p[2], v0 = q[0], v1 = q[1], v2 = q[2];
+      const double2 x0 = xp[0], x1 = xp[1], x2 = xp[2];      // d_x d_y | d_z v_x | v_y v_z of the neighbour
+      const double t0 = __builtin_fma(d0, x0.x, v0 * x1.y), t1 = __builtin_fma(d1, x0.y, v1 * x2.x), t2 = __builtin_fma(d2, x1.x, v2 * x2.y);
+      a0 = a0 + t0; a1 = a1 + t1; a2 = a2 + t2;
+    }
+  }
+}
+// k_spmv_node6c with the d rows from the split pair form; everything else as there
+template <bool XCD>
+__global__ __launch_bounds__(256) void k_spmv_node6s(int64_t N2, const int64_t* __restrict__ rowptr,
+                                                     const int32_t* __restrict__ cols, const double* __restrict__ vals,
+                                                     const int64_t* __restrict__ nadj_ptr, const int32_t* __restrict__ nadj,
+                                                     const double* __restrict__ dd, const double* __restrict__ dv,
+                                                     const int64_t* __restrict__ doff, const double* __restrict__ x, double* __restrict__ y) {
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  int64_t first, last, stride;
+  if (XCD) {
+    const int64_t chunk = (N2 + 7) >> 3, k = blockIdx.x & 7;
+    first = k * chunk + (blockIdx.x >> 3) * (int64_t)(blockDim.x >> 6) + wid;
+    last = (k + 1) * chunk < N2 ? (k + 1) * chunk : N2;
+    stride = (int64_t)(gridDim.x >> 3) * (blockDim.x >> 6);
+  } else {
+    first = blockIdx.x * (int64_t)(blockDim.x >> 6) + wid;
+    last = N2;
+    stride = (int64_t)gridDim.x * (blockDim.x >> 6);
+  }
+  for (int64_t r = first; r < last; r += stride) {
+    const int64_t s0 = rowptr[6 * r];
+    const int64_t L = rowptr[6 * r + 1] - s0;
+    const int64_t a = nadj_ptr[r], deg = nadj_ptr[r + 1] - a;
+    const double* v = vals + s0 + 3 * L;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0, a5 = 0.0;
+    drows_split(dd, dv, doff[r], nadj, a, deg, lane, x, a0, a1, a2);
     for (int64_t t = lane; t < L; t += 64) {
       const double xv = x[cols[s0 + t]];
       a3 += v[t] * xv; a4 += v[L + t] * xv; a5 += v[2 * L + t] * xv;
@@ -407,6 +545,17 @@ int launch_spmv_node6(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowp
     return 0;
   }
   spmv_node6_any<double>(st, N2, V, rowptr, cols, vals, g, x, y);
+  return 0;
+}
+// the d rows from the split pair form (dd, dv, doff: launch_drows_extract_split and what follows it); refused like the pair form
+// without the node graph, and without all three arrays
+int launch_spmv_node6s(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals,
+                       const PRowGraph& g, const double* x, double* y, const double* dd, const double* dv, const int64_t* doff) {
+  if (!g.nadj_ptr || !g.nadj || !dd || !doff) return LAUNCH_REFUSED;      // (dv may be null: no coupled node)
+  int64_t blocks = (N2 + 3) / 4;
+  blocks = (blocks + 7) & ~(int64_t)7;
+  if (blocks > 0) hipLaunchKernelGGL(k_spmv_node6s<true>, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, vals, g.nadj_ptr, g.nadj, dd, dv, doff, x, y);
+  spmv_prows<double>(st, N2, V, rowptr, cols, vals, g, x, y);
   return 0;
 }
 // ---- FP32 copy of the Jacobian in its own layout --------------------------------------------------------------------
