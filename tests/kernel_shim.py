@@ -150,11 +150,11 @@ def check(got, ref, bound, what):
 
 CTX_INFO = ("N2", "V", "nS", "sb_nblocks", "tiled", "tile_nodes", "tile_max_nu", "schur_tiled", "schur_tile", "s_tile_max_nu",
             "sweeps_fp16", "a32_ptail", "a32_tail_src", "a32_tail_nnz", "op32_ok", "kry_fp32", "drows_ok",
-            "mg_nc", "mg_cnnz", "mg_ready", "sbmg_nc", "sbmg_nblk", "sbmg_ready", "bcr_ready")
+            "mg_nc", "mg_cnnz", "mg_ready", "sbmg_nc", "sbmg_nblk", "sbmg_ready", "bcr_ready", "product_form64", "product_form32")
 _ELEM = {("f", 4): np.float32, ("f", 8): np.float64, ("i", 1): np.uint8, ("i", 2): np.uint16, ("i", 4): np.int32,
          ("i", 8): np.int64}
 _UNSIGNED = {"dd_rec", "vv_rec", "sb_rec", "s_rec"}
-_FLOAT = {"dd_chat", "vv_db32", "sb_vals", "sb_binv12", "s_vals", "s_vals32", "s_dinv", "dd_db", "rowscale", "A", "A32", "Ad64", "Ad32",
+_FLOAT = {"dd_chat", "vv_db32", "sb_vals", "sb_binv12", "s_vals", "s_vals32", "s_dinv", "dd_db", "rowscale", "A", "A32", "Ad64", "Ad32", "drows_dd", "drows_dv",
           "mg_pw", "mg_chw", "mg_Ac", "mg_cc", "mg_d0", "mg_dcinv4", "sbmg_pw", "sbmg_chw", "sbmg_cvals", "sbmg_cbinv12",
           "sb_binv9", "sb_dinv", "dd_dinv32", "vvf_dinv32", "Mdd.vals", "Mvv.vals", "Adv", "Avp", "Apv", "App", "Avp32", "Apv32",
           "vv_db", "adv_db", "dd_db32", "vv_dinv", "mask_f", "mask_s", "ss_vals", "LU", "blk", "sbmg_work", "mg_work", "ones32", "mg_cones", "bs"}
@@ -370,7 +370,7 @@ def local_graph(n, rng, reach=24, max_deg=40, diag_only=()):
     return rowptr, cols
 
 
-# ---- the monolithic matrix: structure, padded FP32 copy, d rows in pair form (fsi_solver.hip, fsi_setup.hip) -----------------
+# ---- the monolithic matrix: structure, padded FP32 copy, d rows in pair form (fsi_solver.hip, fsi_product.hip) ---------------
 def mono_graph(N2, V, rng, reach=24, max_deg=12, heavy=(), heavy_deg=(), diag_only=(), no_padj=()):
     """A node graph as the monolithic layout reads it.  nadj_ptr / nadj: every node's neighbour ranks, ascending, itself included
     (up to max_deg random ones within `reach`; node heavy[k] gets heavy_deg[k] neighbours from anywhere; diag_only nodes itself

@@ -1,4 +1,4 @@
-"""The displacement rows of the outer product without the zero dv values (vasp_amd/csrc/fsi_solver.hip): the split pair form
+"""The displacement rows of the outer product without the zero dv values (vasp_amd/csrc/fsi_product.hip): the split pair form
 a Jacobian refresh builds - k_drows_extract with its node classification, k_drows_offsets, k_drows_gather_dv - and the product
 that reads it, k_spmv_node6s, through the test shim (shim_drows_split, shim_spmv_node6s).
 

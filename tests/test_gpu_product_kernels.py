@@ -1,5 +1,5 @@
-"""The monolithic matrix's structure kernels and outer products (vasp_amd/csrc/fsi_solver.hip), one launch at a time through the
-test shim, against FP64 restatements of their contracts (tests/kernel_shim.py) on the exact values the kernels hold:
+"""The monolithic matrix's structure kernels (vasp_amd/csrc/fsi_solver.hip) and outer products (fsi_product.hip), one launch at a
+time through the test shim, against FP64 restatements of their contracts (tests/kernel_shim.py) on the exact values the kernels hold:
 
     k_expand_cols, k_pad_cols32, k_pad_vals32 (+ k_round_to_f32), k_drows_extract, k_matrix_finish     bitwise
     k_spmv, k_spmv_node6 (+ k_spmv_prow), k_spmv_node6c, k_spmv_node6p, k_spmv_node6pc                |y - A x| <= (L + 8) eps S

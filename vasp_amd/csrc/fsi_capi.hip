@@ -621,10 +621,10 @@ int fsi_get_timers(FsiCtx* ctx, FsiTimers* out, int reset) {
                    (int64_t)ctx->s_cols.n, ctx->V, ctx->t_flush.ms, ctx->t_flush.calls, ctx->smp_sch.t.ms, ctx->smp_sch.t.calls,
                    (int64_t)((ctx->schur_fp32 && ctx->s_vals32.p) ? ((ctx->schur_tiled && ctx->sweeps_fp16 && ctx->s_rec.p) ? 0 : 4) : 8),
                    (int64_t)ctx->h_nadj.size(), (int64_t)ctx->h_padj.size(),
-                   ctx->op32_products,
+                   ctx->prod.products32,
                    (int64_t)((ctx->tiled && ctx->fused_sweeps ? 1 : 0) | (ctx->tiled && ctx->fused_sweeps && ctx->sweeps_fp16 ? 2 : 0) |
                              (ctx->solid_fp32 ? 4 : 0) | (ctx->solid_fp32 && ctx->solid_block_jacobi && ctx->solid_fused ? 8 : 0) |
-                             (ctx->sbmg_ready ? 16 : 0) | (ctx->mg_ready ? 32 : 0) | (ctx->drows_ok ? 64 : 0)),
+                             (ctx->sbmg_ready ? 16 : 0) | (ctx->mg_ready ? 32 : 0) | (ctx->prod.pairs() ? 64 : 0)),
                    ctx->part_allreduces, (int64_t)ctx->ncellcol, ctx->gcr_arnoldi_steps, ctx->gcr_restarts, ctx->newton_retries,
                    (int64_t)ctx->kry_fp32_failures_total, ctx->verdicts_skipped, ctx->gcr_reorth_forced, ctx->dd_cache_hits,
                    ctx->newton_late_solves};
@@ -634,7 +634,7 @@ int fsi_get_timers(FsiCtx* ctx, FsiTimers* out, int reset) {
       t->calls = 0;
     }
     ctx->kry_iters = 0;
-    ctx->op32_products = 0;
+    ctx->prod.products32 = 0;
     ctx->inner_its[0] = ctx->inner_its[1] = ctx->inner_its[2] = 0;
     ctx->inner_calls = 0;
     ctx->ortho_q_cols = ctx->ortho_q_launches = ctx->ortho_z_cols = ctx->ortho_z_launches = 0;

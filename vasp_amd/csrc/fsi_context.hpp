@@ -3,14 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
-#include <type_traits>
 #include <string>
 #include <vector>
 
 #include "../../include/vaspfsi.h"
 #include "fsi_band.hpp"
+#include "fsi_devbuf.hpp"
 #include "fsi_element.hpp"
 #include "fsi_gcr_host.hpp"
+#include "fsi_product.hpp"
 
 namespace fsi {
 struct BcrData;               // exact solve of the solid cycle's coarse level by block cyclic reduction (fsi_bcr.hip)
@@ -18,32 +19,6 @@ struct BcrData;               // exact solve of the solid cycle's coarse level b
 constexpr int NQ = 24;        // Keast degree-6 rule
 constexpr int NLOC = 64;      // local dofs per tet: 30 (d) + 30 (v) + 4 (p)
 constexpr int MAX_REGIONS = 8;
-
-template <class T>
-struct DevBuf {      // owns its device memory: freed with the buffer, never copied
-  T* p = nullptr;
-  size_t n = 0;
-  DevBuf() = default; DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  hipError_t alloc(size_t count) {
-    release();
-    n = count;
-    if (count == 0) return hipSuccess;
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-    if (e != hipSuccess) return e;
-    // Fresh device memory is whatever the previous owner left (another context of the same process included): every buffer
-    // starts from zeros, so that no result can depend on it.  FSI_DEBUG_POISON=1 fills the floating-point buffers with NaN
-    // bit patterns instead - a read before the first write then shows up in the first norm that is taken.
-    static const bool poison = getenv("FSI_DEBUG_POISON") != nullptr;
-    return hipMemset(p, (poison && std::is_floating_point<T>::value) ? 0xFF : 0, count * sizeof(T));
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  void swap(DevBuf& o) { T* op = o.p; const size_t on = o.n; o.p = p; o.n = n; p = op; n = on; }
-};
 
 // One colour of the multicolour ordering: `ngroups` groups of `group_rows` consecutive rows starting at `first_row`
 // (6 rows per P2 node for the d/v block, 1 row per vertex for the pressure block).
@@ -324,23 +299,10 @@ struct FsiCtx {
   double* gcr_host = nullptr;                // pinned [GcrStaging::size()]
   double gs_rtol = 0.0;                      // tightest linear tolerance asked for since the last Jacobian (re-orthogonalisation criterion)
   int64_t ortho_q_cols = 0, ortho_z_cols = 0, ortho_q_launches = 0, ortho_z_launches = 0;   // columns streamed (exact bytes of the orthogonalisation)
-  fsi::DevBuf<float> A32;                         // FP32 copy of A for the products inside the Krylov iterations (FSI_OPERATOR_FP32, default on)
-  bool op32_ok = false; int op32_policy = 1; int64_t op32_products = 0;
-  fsi::DevBuf<int64_t> a32_ptr;              // [N2 + 1] first entry of a node's padded block in A32 (k_spmv_node6p)
-  fsi::DevBuf<int32_t> a32_cols;             // padded index rows
-  int64_t a32_ptail = 0, a32_tail_src = 0, a32_tail_nnz = 0;     // pressure rows: behind the padded node blocks, unpadded
-  // d rows of the node blocks in pair form (k_drows_extract: six values per node pair instead of 18; FsiTuning.compact_drows):
-  // refreshed and CHECKED with every Jacobian - drows_ok only while nothing else was found in those rows
-  fsi::DevBuf<double> Ad64;                  // [6 x node pairs]
-  fsi::DevBuf<float> Ad32;                   // ... rounded, for the products on the FP32 copy
-  bool drows_ok = false;
-  int64_t drows_products = 0;
-  // ... and split for the FP64 products (k_spmv_node6s): dd for every pair, dv for the pairs of the nodes whose d rows hold a
-  // non-zero dv entry (the solid's), found from the values at every refresh; drows_split_ok only while drows_ok
-  fsi::DevBuf<double> Add, Adv3;             // [3 x node pairs], [3 x pairs of coupled nodes] (grows when a refresh finds more)
-  fsi::DevBuf<int32_t> drows_cdeg;           // [N2] degree of a coupled node, 0 of an uncoupled one
-  fsi::DevBuf<int64_t> drows_off;            // [N2 + 1] first pair of a coupled node in Adv3, -1: uncoupled; [N2]: pairs in Adv3
-  bool drows_split_ok = false;
+  // The monolithic operator beside A itself (fsi_product.hpp): the FP32 copy of A for the products inside the Krylov iterations
+  // (FsiTuning.operator_fp32, default on), the d rows in pair and split form (FsiTuning.compact_drows), the form each kind of
+  // product runs until the next refresh, and the counters op32_products / drows_products of fsi_get_timers
+  fsi::MonoProduct prod;
   bool gcr_stagnated = false;                // the last cycle ended on 40 iterations without a 10 % gain
   bool gcr_stalled = false;                  // ... on 128 iterations without a 10 % gain far from its target, the store full (truncated recurrence stuck)
   double f32_cycle_floor = 1e-6;             // FP32 basis: a cycle reduces the residual by at most this factor before the FP64 verdict

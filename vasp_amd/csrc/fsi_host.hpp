@@ -2,12 +2,15 @@
 //   fsi_capi.hip     the ABI itself: boundary data, partition, state access, products, probes, timers
 //   fsi_setup.hip    fsi_create / fsi_create_tuned as a sequence of stages, fsi_destroy and the context's destructor
 //   fsi_newton.hip   fsi_assemble_residual / _jacobian, fsi_solve, fsi_newton_solve (turtleFSI's newtonsolver policy)
-//   fsi_krylov.hip   recycled GCR (solve_gcr), BiCGStab, the monolithic product
+//   fsi_krylov.hip   recycled GCR (solve_gcr), BiCGStab, the callers' entry of the monolithic product (host::spmv)
+//   fsi_product.hip  the monolithic product: its kernels, launch_product, and MonoProduct (layout / refresh / apply), the context's
+//                    operator; fsi_product_host.hpp holds what of it needs no device (the forms and their choice, the padded layout)
 //   fsi_gcr_host.hpp what of the recycled GCR needs no device (plain C++, read by the test shim too): the store's slots, the
 //                    staging buffer's layout, the coefficient algebra of a cycle, the policies of a cycle and of a solve
 //   fsi_sessions.hip the post-processing sessions of a run: fsi_hemo_* / fsi_stress_* / fsi_band_* / fsi_spec_*
 //   fsi_precond.hip  the field-split block preconditioner: one application (two streams), refresh at a new Jacobian
-// The kernels are in fsi_assembly / fsi_solver / fsi_block / fsi_gcr / fsi_post .hip (declared in fsi_kernels.hpp).
+// The kernels are in fsi_assembly / fsi_solver / fsi_product / fsi_block / fsi_gcr / fsi_post .hip (declared in fsi_kernels.hpp
+// and fsi_product.hpp).
 #pragma once
 #include <algorithm>
 #include <cmath>

@@ -612,7 +612,7 @@ int shim_gcr_tolerances(const double* in, double* out) {
   return 0;
 }
 
-// ---- fsi_solver.hip: the monolithic matrix's structure and products -----------------------------------------------------------
+// ---- fsi_solver.hip / fsi_product.hip: the monolithic matrix's structure and products -----------------------------------------
 // Node graph: nadj_ptr [N2 + 1], nadj [npairs = nadj_ptr[N2]]; pressure graph: padj_ptr [N2 + 1], padj [padj_ptr[N2]]; vrank [V];
 // rows: 6 N2 node rows then V pressure rows, rowptr [6 N2 + V + 1], nnz = rowptr[6 N2 + V].  x and y: 6 N2 + V entries.
 int shim_expand_cols(int64_t N2, int64_t V, const int64_t* nadj_ptr, const int32_t* nadj, const int64_t* padj_ptr, const int32_t* padj,
@@ -639,7 +639,8 @@ int shim_spmv(int64_t n, const int64_t* rowptr, const int32_t* cols, const doubl
   double* dy = c.io(y, (size_t)n);
   SHIM_RUN(c, "launch_spmv", launch_spmv(c.st, n, drp, dc, dv, dx, dy, tag));
 }
-// vrank, nadj_ptr, nadj may each be null (npairs: the length of nadj, and ad64 holds 6 npairs)
+// launch_product on the FP64 matrix, all six value rows (ad64 null) or the d rows in pair form; vrank, nadj_ptr, nadj may each
+// be null (npairs: the length of nadj, and ad64 holds 6 npairs)
 int shim_spmv_node6(int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals, const int32_t* vrank,
                     const int64_t* nadj_ptr, const int32_t* nadj, int64_t npairs, const double* x, double* y, const double* ad64) {
   Call c;
@@ -647,11 +648,13 @@ int shim_spmv_node6(int64_t N2, int64_t V, const int64_t* rowptr, const int32_t*
   const int64_t* drp = c.in(rowptr, (size_t)n + 1);
   const int32_t* dc = c.in(cols, (size_t)rowptr[n]);
   const double* dv = c.in(vals, (size_t)rowptr[n]);
-  const PRowGraph g{c.in(vrank, (size_t)V), c.in(nadj_ptr, (size_t)N2 + 1), c.in(nadj, (size_t)npairs)};
+  ProductView m;
+  m.N2 = N2; m.V = V; m.rowptr = drp; m.cols = dc; m.vals = dv;
+  m.g = PRowGraph{c.in(vrank, (size_t)V), c.in(nadj_ptr, (size_t)N2 + 1), c.in(nadj, (size_t)npairs)};
   const double* dx = c.in(x, (size_t)n);
   double* dy = c.io(y, (size_t)n);
-  const double* dad = c.in(ad64, (size_t)(6 * npairs));
-  SHIM_RUN_STATUS(c, "launch_spmv_node6", launch_spmv_node6(c.st, N2, V, drp, dc, dv, g, dx, dy, dad));
+  m.ad64 = c.in(ad64, (size_t)(6 * npairs));
+  SHIM_RUN_STATUS(c, "launch_product (six rows / pair form)", launch_product(c.st, m, m.ad64 ? PRODUCT_PAIR64 : PRODUCT_SIX64, dx, dy));
 }
 // node rows only: rowptr [6 N2 + 1], A [rowptr[6 N2]]; ad64 / ad32 [6 nadj_ptr[N2]] (ad32 may be null); flag [1]
 int shim_drows_extract(int64_t N2, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr, double* ad64, float* ad32,
@@ -691,7 +694,7 @@ int shim_drows_split(int64_t N2, const int64_t* rowptr, const double* A, const i
   }
   return c.finish("launch_drows_extract_split / launch_drows_offsets / launch_drows_gather_dv");
 }
-// launch_spmv_node6s: dd [3 npairs], dv [3 ndv] (may be null), doff [N2 + 1]; the rest as shim_spmv_node6
+// launch_product in the split form: dd [3 npairs], dv [3 ndv] (may be null), doff [N2 + 1]; the rest as shim_spmv_node6
 int shim_spmv_node6s(int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals, const int32_t* vrank,
                      const int64_t* nadj_ptr, const int32_t* nadj, int64_t npairs, const double* x, double* y, const double* dd,
                      const double* dv, int64_t ndv, const int64_t* doff) {
@@ -700,13 +703,15 @@ int shim_spmv_node6s(int64_t N2, int64_t V, const int64_t* rowptr, const int32_t
   const int64_t* drp = c.in(rowptr, (size_t)n + 1);
   const int32_t* dc = c.in(cols, (size_t)rowptr[n]);
   const double* dvl = c.in(vals, (size_t)rowptr[n]);
-  const PRowGraph g{c.in(vrank, (size_t)V), c.in(nadj_ptr, (size_t)N2 + 1), c.in(nadj, (size_t)npairs)};
+  ProductView m;
+  m.N2 = N2; m.V = V; m.rowptr = drp; m.cols = dc; m.vals = dvl;
+  m.g = PRowGraph{c.in(vrank, (size_t)V), c.in(nadj_ptr, (size_t)N2 + 1), c.in(nadj, (size_t)npairs)};
   const double* dx = c.in(x, (size_t)n);
   double* dy = c.io(y, (size_t)n);
-  const double* ddd = c.in(dd, (size_t)(3 * npairs));
-  const double* ddv = c.in(dv, (size_t)(3 * ndv));
-  const int64_t* dof = c.in(doff, (size_t)N2 + 1);
-  SHIM_RUN_STATUS(c, "launch_spmv_node6s", launch_spmv_node6s(c.st, N2, V, drp, dc, dvl, g, dx, dy, ddd, ddv, dof));
+  m.dd = c.in(dd, (size_t)(3 * npairs));
+  m.dv = c.in(dv, (size_t)(3 * ndv));
+  m.doff = c.in(doff, (size_t)N2 + 1);
+  SHIM_RUN_STATUS(c, "launch_product (split form)", launch_product(c.st, m, PRODUCT_SPLIT64, dx, dy));
 }
 // p32 [N2 + 1] (entries, six value rows per node block); cols32 [p32[N2] / 6]
 int shim_pad_cols32(int64_t N2, const int64_t* rowptr, const int32_t* cols, const int64_t* p32, int32_t* cols32) {
@@ -727,7 +732,7 @@ int shim_pad_vals32(int64_t N2, int64_t V, const int64_t* rowptr, const double* 
   float* d32 = c.io(A32, (size_t)n32);
   SHIM_RUN(c, "launch_pad_vals32", launch_pad_vals32(c.st, N2, V, drp, dA, dp, ptail, nnz_tail, tail_src, d32, v_rows_only != 0));
 }
-// vals [n32]; the pressure rows' values at vals + tail_shift + rowptr[row]; ad32 [6 npairs] or null
+// launch_product on the padded FP32 copy, six rows (ad32 null) or pair form.  vals [n32]; the pressure rows' values at vals + tail_shift + rowptr[row]; ad32 [6 npairs] or null
 int shim_spmv_node6p(int64_t N2, int64_t V, const int64_t* p32, const int32_t* cols32, const float* vals, int64_t n32, const int64_t* rowptr,
                      const int32_t* cols, int64_t tail_shift, const int32_t* vrank, const int64_t* nadj_ptr, const int32_t* nadj, int64_t npairs,
                      const double* x, double* y, const float* ad32) {
@@ -738,11 +743,13 @@ int shim_spmv_node6p(int64_t N2, int64_t V, const int64_t* p32, const int32_t* c
   const float* dv = c.in(vals, (size_t)n32);
   const int64_t* drp = c.in(rowptr, (size_t)n + 1);
   const int32_t* dc = c.in(cols, (size_t)rowptr[n]);
-  const PRowGraph g{c.in(vrank, (size_t)V), c.in(nadj_ptr, (size_t)N2 + 1), c.in(nadj, (size_t)npairs)};
+  ProductView m;
+  m.N2 = N2; m.V = V; m.rowptr = drp; m.cols = dc; m.p32 = dp; m.cols32 = dc32; m.vals32 = dv; m.tail_shift = tail_shift;
+  m.g = PRowGraph{c.in(vrank, (size_t)V), c.in(nadj_ptr, (size_t)N2 + 1), c.in(nadj, (size_t)npairs)};
   const double* dx = c.in(x, (size_t)n);
   double* dy = c.io(y, (size_t)n);
-  const float* dad = c.in(ad32, (size_t)(6 * npairs));
-  SHIM_RUN_STATUS(c, "launch_spmv_node6p", launch_spmv_node6p(c.st, N2, V, dp, dc32, dv, drp, dc, tail_shift, g, dx, dy, dad));
+  m.ad32 = c.in(ad32, (size_t)(6 * npairs));
+  SHIM_RUN_STATUS(c, "launch_product (padded FP32 copy)", launch_product(c.st, m, m.ad32 ? PRODUCT_PAIR32 : PRODUCT_SIX32, dx, dy));
 }
 // n rows; A (in place), Apre [rowptr[n]]; bc [nbc] (may repeat); rowscale, bcmask [n]
 int shim_matrix_finish(int64_t n, const int64_t* rowptr, const int64_t* diagpos, double* A, const double* Apre, const int32_t* bc,
@@ -2200,12 +2207,14 @@ int shim_tensor_principal(int64_t nnode, const double* amp, double* mag) {
 // ---- a live context's preconditioner arrays (FsiCtx of fsi_context.hpp, as the library was compiled) -----------------------
 // shim_ctx_info: N2, V, nS, sb_nblocks, tiled, tile_nodes, tile_max_nu, schur_tiled, schur_tile, s_tile_max_nu, sweeps_fp16,
 // a32_ptail, a32_tail_src, a32_tail_nnz, op32_ok, kry_fp32, drows_ok, mg_nc, mg_cnnz, mg_ready, sbmg_nc, sbmg_nblk, sbmg_ready,
-// bcr_ready (new fields go at the end: tests/kernel_shim.py reads them by position)
+// bcr_ready, the ProductForm of the FP64 products and of those on the FP32 copy (new fields go at the end: tests/kernel_shim.py
+// reads them by position)
 int shim_ctx_info(const FsiCtx* ctx, int64_t* out, int nout) {
   const int64_t v[] = {ctx->N2, ctx->V, ctx->nS, ctx->sb_nblocks, ctx->tiled, ctx->tile_nodes, ctx->tile_max_nu,
                        ctx->schur_tiled, ctx->schur_tile, ctx->s_tile_max_nu, ctx->sweeps_fp16,
-                       ctx->a32_ptail, ctx->a32_tail_src, ctx->a32_tail_nnz, ctx->op32_ok, ctx->kry_fp32, ctx->drows_ok,
-                       ctx->mg_nc, ctx->mg_cnnz, ctx->mg_ready, ctx->sbmg_nc, ctx->sbmg_nblk, ctx->sbmg_ready, fsi::host::bcr_ready(ctx)};
+                       ctx->prod.tail.ptail, ctx->prod.tail.src, ctx->prod.tail.nnz, ctx->prod.copy_ok, ctx->kry_fp32, ctx->prod.pairs(),
+                       ctx->mg_nc, ctx->mg_cnnz, ctx->mg_ready, ctx->sbmg_nc, ctx->sbmg_nblk, ctx->sbmg_ready, fsi::host::bcr_ready(ctx),
+                       ctx->prod.form.f64, ctx->prod.form.f32};
   const int k = (int)(sizeof(v) / sizeof(v[0]));
   for (int i = 0; i < nout && i < k; ++i) out[i] = v[i];
   return k;
@@ -2262,12 +2271,14 @@ double shim_ctx_coarse(const FsiCtx* ctx, int which) {
 int shim_ctx_array(const FsiCtx* ctx, const char* name, void* host, int64_t* count, int* elem) {
   struct Entry { const char* name; const void* p; size_t n, sz; };
 #define E(f) Entry{#f, ctx->f.p, ctx->f.n, sizeof(*ctx->f.p)}
+#define EP(name, f) Entry{name, ctx->prod.f.p, ctx->prod.f.n, sizeof(*ctx->prod.f.p)}      // the monolithic operator's (MonoProduct)
   const Entry table[] = {E(nadj_ptr), E(nadj),        E(dd_chat), E(dd_rowflag), E(dd_rec),      E(tile_ploc),   E(tile_uptr),
                          E(tile_ulist), E(vv_db32),   E(vv_rec),  E(sb_ptr),     E(sb_col),      E(sb_vals),     E(sb_rec),
                          E(sb_binv12),  E(s_rowptr),  E(s_cols),  E(s_diagpos),  E(s_vals),      E(s_vals32),    E(s_rec),
                          E(s_ploc),     E(s_tile_uptr), E(s_tile_ulist), E(s_dinv), E(dd_db),    E(rowscale),    E(snode),
                          E(solver2user), E(node_solid), E(rowptr),    E(cols),        E(diagpos),     E(A),           E(vrank),
-                         E(padj_ptr),   E(padj),      E(A32),     E(a32_ptr),    E(a32_cols),    E(Ad64),        E(Ad32),
+                         E(padj_ptr),   E(padj),      EP("A32", A32), EP("a32_ptr", a32_ptr), EP("a32_cols", a32_cols), EP("Ad64", Ad64), EP("Ad32", Ad32),
+                         EP("drows_dd", Add), EP("drows_dv", Adv3), EP("drows_off", doff), EP("drows_cdeg", cdeg),
                          E(mg_par),     E(mg_pw),     E(mg_chptr), E(mg_child),  E(mg_chw),      E(mg_cptr),     E(mg_ccol),
                          E(mg_cfine),   E(mg_Ac),     E(mg_cc),   E(mg_d0),      E(mg_dcinv4),   E(mg_cflag),    E(sbmg_par),
                          E(sbmg_pw),    E(sbmg_chptr), E(sbmg_child), E(sbmg_chw), E(sbmg_cptr),  E(sbmg_ccol),   E(sbmg_cfine),
@@ -2281,6 +2292,7 @@ int shim_ctx_array(const FsiCtx* ctx, const char* name, void* host, int64_t* cou
                          E(sb_stride),  E(s_diagpos),  E(LU),       E(user2solver), E(blk),        E(sbmg_work),   E(mg_work),
                          E(ones32),     E(mg_cones),  E(bs)};
 #undef E
+#undef EP
   for (const Entry& t : table) {
     if (std::strcmp(t.name, name) != 0) continue;
     *count = (int64_t)t.n;
@@ -2315,14 +2327,14 @@ int shim_ctx_spmv(FsiCtx* ctx, int working, const double* x, double* y, int64_t*
   const double* dx = c.in(x, (size_t)n);
   double* dy = c.io(y, (size_t)n);
   if (c.ok()) c.note(hipSetDevice(ctx->device));
-  const int64_t op0 = ctx->op32_products, dr0 = ctx->drows_products;
+  const int64_t op0 = ctx->prod.products32, dr0 = ctx->prod.pair_products;
   int rc = 0;
   if (c.ok()) {
     rc = fsi::host::spmv(ctx, dx, dy, working != 0);
     c.note(hipStreamSynchronize(ctx->stream));
   }
-  counters[0] = ctx->op32_products - op0;
-  counters[1] = ctx->drows_products - dr0;
+  counters[0] = ctx->prod.products32 - op0;
+  counters[1] = ctx->prod.pair_products - dr0;
   if (const int e = c.finish("host::spmv")) return e;
   if (rc) g_err = "host::spmv: " + ctx->err;
   return rc;

@@ -187,39 +187,6 @@ void launch_matrix_finish(hipStream_t st, int64_t n, const int64_t* rowptr, cons
 void launch_robin_residual(hipStream_t st, int64_t nrows, const int32_t* urow, const int32_t* ptr, const int32_t* col,
                            const double* val, double th0, double th1, const double* U, const double* U1, double* F);
 void launch_add_at(hipStream_t st, double* vals, const int64_t* pos, const double* v, double a, int64_t n);
-enum SpmvTag : int { SPMV_MONOLITHIC = 0, SPMV_SOLID_BLOCK = 1, SPMV_FIELD_BLOCK = 2 };
-// the node graph the pressure rows of the monolithic matrix were laid out from (k_expand_cols): with it the products read one
-// neighbour rank per six entries (k_spmv_prow); all null: the generic CSR kernel
-struct PRowGraph {
-  const int32_t* vrank = nullptr;
-  const int64_t* nadj_ptr = nullptr;
-  const int32_t* nadj = nullptr;
-};
-void launch_pad_cols32(hipStream_t st, int64_t N2, const int64_t* rowptr, const int32_t* cols, const int64_t* p32, int32_t* cols32);
-void launch_pad_vals32(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const double* A, const int64_t* p32,
-                       int64_t ptail, int64_t nnz_tail, int64_t tail_src, float* A32, bool v_rows_only = false);
-// d rows of the node blocks in pair form [dd_0 dd_1 dd_2 dv_0 dv_1 dv_2] per node pair (fsi_solver.hip); flag bit 0: a d row holds
-// something else and the products must keep the full rows
-void launch_drows_extract(hipStream_t st, int64_t N2, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr, double* ad64,
-                          float* ad32, int32_t* flag);
-// The pair form split (FP64): dd [pairs][3] for every node and dv [pairs of coupled nodes][3], a node being coupled when any dv
-// entry of its three d rows is not exactly zero - found from the values at every refresh, like the verdict in `flag`.
-//   launch_drows_extract_split   launch_drows_extract, and dd and cdeg [N2]: the node's degree if it is coupled, else 0
-//   launch_drows_offsets         doff [N2 + 1]: first pair of node r in dv, -1 for an uncoupled node; doff[N2] = pairs in dv
-//   launch_drows_gather_dv       dv from the pair form ad64 through doff (dv holds at least doff[N2] pairs)
-void launch_drows_extract_split(hipStream_t st, int64_t N2, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr,
-                                double* ad64, float* ad32, int32_t* flag, double* dd, int32_t* cdeg);
-void launch_drows_offsets(hipStream_t st, int64_t N2, const int32_t* cdeg, int64_t* doff);
-void launch_drows_gather_dv(hipStream_t st, int64_t N2, const int64_t* nadj_ptr, const int64_t* doff, const double* ad64, double* dv);
-// status of the products that can refuse their arguments: 0 launched, LAUNCH_REFUSED nothing launched (d rows in pair form without
-// the node graph they are indexed by)
-constexpr int LAUNCH_REFUSED = 2;
-int launch_spmv_node6p(hipStream_t st, int64_t N2, int64_t V, const int64_t* p32, const int32_t* cols32, const float* vals,
-                       const int64_t* rowptr, const int32_t* cols, int64_t tail_shift, const PRowGraph& g, const double* x, double* y,
-                       const float* ad32 = nullptr);
-void launch_round_to_f32(hipStream_t st, int64_t n, const double* a, float* b);
-void launch_spmv(hipStream_t st, int64_t n, const int64_t* rowptr, const int32_t* cols, const double* vals,
-                 const double* x, double* y, int tag = SPMV_FIELD_BLOCK);
 // reductions: out[0] = x.y (deterministic two-stage); scratch must hold >= 4096 doubles
 void launch_dot(hipStream_t st, const double* x, const double* y, int64_t n, double* scratch, double* out);
 void launch_hashed_sum(hipStream_t st, const double* x, int64_t first, int64_t stride, int64_t n, double* scratch, double* out);
@@ -355,11 +322,6 @@ void launch_mg_prolong(hipStream_t st, int64_t N2, const int32_t* par, const flo
                        float* e4, const float* dc4 = nullptr);      // dc4: prolongs xc4 + dc4
 void launch_residual_rows(hipStream_t st, int64_t nrows, const int32_t* rows, const int64_t* ptr, const int32_t* col,
                           const int64_t* src, const double* vals, const double* x, const double* b, double* y);
-int launch_spmv_node6(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals,
-                      const PRowGraph& g, const double* x, double* y, const double* ad64 = nullptr);      // status: LAUNCH_REFUSED above
-// ... with the d rows from the split pair form (launch_drows_extract_split): bit for bit what the pair form gives
-int launch_spmv_node6s(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals,
-                       const PRowGraph& g, const double* x, double* y, const double* dd, const double* dv, const int64_t* doff);
 void launch_sweep_csr_mixed(hipStream_t st, int64_t n, const int64_t* rowptr, const int32_t* cols, const float* vals,
                             const int64_t* diagpos, const double* dvals, double c1, double c2, const double* din, double* dout,
                             double* x, double* r);

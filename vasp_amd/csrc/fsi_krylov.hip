@@ -1,7 +1,8 @@
 // Krylov methods on the row-equilibrated monolithic Jacobian: right-preconditioned GCR whose directions are kept while the
 // Jacobian is kept (solve_gcr: FP32 / FP64 basis, restarts from the FP64 residual, safeguards of DESIGN.md section 5), BiCGStab
-// (FsiNewtonOpts.lin_solver = 1), and the monolithic product.  Kernels: fsi_gcr.hip, fsi_solver.hip.  What of GCR needs no
-// device - the store's slots, the coefficient algebra, the policies - is in fsi_gcr_host.hpp.
+// (FsiNewtonOpts.lin_solver = 1), and the callers' entry of the monolithic product (the product itself: fsi_product.hip).
+// Kernels: fsi_gcr.hip, fsi_solver.hip.  What of GCR needs no device - the store's slots, the coefficient algebra, the
+// policies - is in fsi_gcr_host.hpp.
 #include "fsi_host.hpp"
 
 using namespace fsi;
@@ -10,31 +11,13 @@ using namespace fsi::host;
 namespace fsi {
 namespace host {
 
-// working = true: the product inside a Krylov iteration, which may run on the FP32 copy of the matrix while the basis of this
-// Jacobian's lifetime is kept in FP32 (see solve_gcr); every other product (true residuals, the other solvers) is FP64
+// working = true: the product inside a Krylov iteration (MonoProduct::apply decides what it runs on)
 int spmv(FsiCtx* ctx, const double* x, double* y, bool working) {
   Phase ph(ctx, &ctx->t_spmv);
-  const PRowGraph g{ctx->vrank.p, ctx->nadj_ptr.p, ctx->nadj.p};
-  if (working && ctx->op32_ok && ctx->kry_fp32) {
-    if (launch_spmv_node6p(ctx->stream, ctx->N2, ctx->V, ctx->a32_ptr.p, ctx->a32_cols.p, ctx->A32.p, ctx->rowptr.p, ctx->cols.p,
-                           ctx->a32_ptail - ctx->a32_tail_src, g, x, y, ctx->drows_ok ? ctx->Ad32.p : nullptr) != 0) {
-      ctx->err = "spmv: d rows in pair form without the node graph";
-      return FSI_ERR_INVALID;
-    }
-    ctx->op32_products += 1;
-    if (ctx->drows_ok) ctx->drows_products += 1;
-    return FSI_OK;
-  }
-  // (drows_ok: the d rows from their pair form - six values per node pair, checked at the refresh - instead of 18 + pressure columns;
-  // drows_split_ok: three per pair on the nodes whose dv values are all zero, the same bits)
-  const int rc = ctx->drows_ok && ctx->drows_split_ok
-                     ? launch_spmv_node6s(ctx->stream, ctx->N2, ctx->V, ctx->rowptr.p, ctx->cols.p, ctx->A.p, g, x, y, ctx->Add.p, ctx->Adv3.p, ctx->drows_off.p)
-                     : launch_spmv_node6(ctx->stream, ctx->N2, ctx->V, ctx->rowptr.p, ctx->cols.p, ctx->A.p, g, x, y, ctx->drows_ok ? ctx->Ad64.p : nullptr);
-  if (rc != 0) {
+  if (ctx->prod.apply(ctx, x, y, working) != 0) {
     ctx->err = "spmv: d rows in pair form without the node graph";
     return FSI_ERR_INVALID;
   }
-  if (ctx->drows_ok) ctx->drows_products += 1;
   return FSI_OK;
 }
 
@@ -517,7 +500,7 @@ int judge_fp64_cycle(FsiCtx* ctx, Solve& s, const GcrVerdictIn& v, bool* done) {
 int judge_fp32_cycle(FsiCtx* ctx, Solve& s, const GcrVerdictIn& v, double target, bool* done) {
   *done = true;
   const bool final_cycle = target <= s.rtol * s.bnorm * (1.0 + 1e-12);
-  if (final_cycle && s.rtol >= 1e-4 && !ctx->op32_ok) return FSI_OK;
+  if (final_cycle && s.rtol >= 1e-4 && !ctx->prod.copy_ok) return FSI_OK;
   if (gcr_verdict_skippable(v, ctx->in_newton, final_cycle, ctx->f32_verdict_skip_rtol, ctx->f32_last_drift)) {
     ctx->verdicts_skipped += 1;
     return FSI_OK;

@@ -56,55 +56,7 @@ int fsi_assemble_jacobian(FsiCtx* ctx) {
     HIPCHK(hipGetLastError());
     if (getenv("FSI_DEBUG")) { HIPCHK(hipStreamSynchronize(ctx->stream)); fprintf(stderr, "[fsi] matrix finish done\n"); fflush(stderr); }
   }
-  ctx->op32_ok = false;
-  const bool copy32 = ctx->op32_policy && ctx->kry_fp32_policy != 0 && ctx->precond == 0 && ctx->A32.p;
-  // the d rows in pair form for the outer products (FsiTuning.compact_drows): extracted from THIS matrix, and adopted only if the
-  // kernel found nothing else in those rows (one flag read per refresh)
-  ctx->drows_ok = false;
-  ctx->drows_split_ok = false;
-  if (getenv("FSI_DEBUG_DROWS_INJECT") && ctx->nnz > 1) {
-    // test hook: a value where the forms leave a structural zero - entry 1 of the first d row (column d_y of node 0's first
-    // neighbour in a d_x row) - so that the check below has a matrix to refuse
-    const int64_t pos = 1;
-    const double val = 0.125;
-    int64_t* dpos = reinterpret_cast<int64_t*>(ctx->scratch.p + 4098);
-    HIPCHK(hipMemcpyAsync(dpos, &pos, sizeof pos, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->scratch.p + 4099, &val, sizeof val, hipMemcpyHostToDevice, ctx->stream));
-    launch_add_at(ctx->stream, ctx->A.p, dpos, ctx->scratch.p + 4099, 1.0, 1);
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  if (ctx->tune.compact_drows && ctx->N2 > 0) {
-    const size_t npairs6 = 6 * (size_t)ctx->nadj.n;
-    if (!ctx->Ad64.p) HIPCHK(ctx->Ad64.alloc(npairs6));
-    if (copy32 && !ctx->Ad32.p) HIPCHK(ctx->Ad32.alloc(npairs6));
-    HIPCHK(hipMemsetAsync(ctx->iflags.p + FsiCtx::IFLAG_DROWS, 0, sizeof(int32_t), ctx->stream));
-    // ... and split for the FP64 products: dd for every pair, the nodes classified by their dv values, offsets by a scan
-    if (!ctx->Add.p) HIPCHK(ctx->Add.alloc(npairs6 / 2));
-    if (!ctx->drows_cdeg.p) HIPCHK(ctx->drows_cdeg.alloc((size_t)ctx->N2));
-    if (!ctx->drows_off.p) HIPCHK(ctx->drows_off.alloc((size_t)ctx->N2 + 1));
-    launch_drows_extract_split(ctx->stream, ctx->N2, ctx->rowptr.p, ctx->A.p, ctx->nadj_ptr.p, ctx->Ad64.p, copy32 ? ctx->Ad32.p : nullptr,
-                               ctx->iflags.p + FsiCtx::IFLAG_DROWS, ctx->Add.p, ctx->drows_cdeg.p);
-    launch_drows_offsets(ctx->stream, ctx->N2, ctx->drows_cdeg.p, ctx->drows_off.p);
-    int32_t found = 1;
-    int64_t coupled_pairs = -1;
-    HIPCHK(hipMemcpyAsync(&found, ctx->iflags.p + FsiCtx::IFLAG_DROWS, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(&coupled_pairs, ctx->drows_off.p + ctx->N2, sizeof coupled_pairs, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->drows_ok = found == 0;
-    ctx->drows_split_ok = false;
-    if (ctx->drows_ok && coupled_pairs >= 0 && (size_t)coupled_pairs <= ctx->nadj.n) {
-      if (3 * (size_t)coupled_pairs > ctx->Adv3.n) HIPCHK(ctx->Adv3.alloc(3 * (size_t)coupled_pairs));
-      if (coupled_pairs > 0) launch_drows_gather_dv(ctx->stream, ctx->N2, ctx->nadj_ptr.p, ctx->drows_off.p, ctx->Ad64.p, ctx->Adv3.p);
-      ctx->drows_split_ok = true;
-    }
-    if (getenv("FSI_DEBUG")) fprintf(stderr, "[fsi] displacement rows of the outer product in pair form: %s; %lld of %lld pairs belong to nodes with dv entries\n",
-                                     ctx->drows_ok ? "yes" : "no (other entries found)", (long long)coupled_pairs, (long long)ctx->nadj.n);
-  }
-  if (copy32) {
-    launch_pad_vals32(ctx->stream, ctx->N2, ctx->V, ctx->rowptr.p, ctx->A.p, ctx->a32_ptr.p, ctx->a32_ptail, ctx->a32_tail_nnz,
-                      ctx->a32_tail_src, ctx->A32.p, ctx->drows_ok);       // rows are equilibrated: |entries| <= 1
-    ctx->op32_ok = true;
-  }
+  FSICHK(ctx->prod.refresh(ctx));      // the forms of this matrix the products run on (fsi_product.hip)
   gcr_reset(ctx);          // the recycled directions belong to the previous matrix
   for (double& h : ctx->nw_hist) h = 0.0;      // ... and so does what was learnt about the Newton iteration's contraction
   ctx->utol_ratio = 0.0;                       // ... and about the row scaling's effect on its residuals

@@ -20,7 +20,7 @@ struct Setup {
 // FsiTuning -> the context's fields (the kernels and the solver read those)
 static void apply_tuning(FsiCtx* ctx, const FsiTuning& t) {
   ctx->tune = t;
-  ctx->kry_fp32_policy = t.krylov_fp32; ctx->op32_policy = t.operator_fp32; ctx->schur_fp32 = t.schur_fp32 != 0;
+  ctx->kry_fp32_policy = t.krylov_fp32; ctx->prod.policy32 = t.operator_fp32; ctx->schur_fp32 = t.schur_fp32 != 0;
   ctx->sweeps_fp32 = t.sweeps_fp32; ctx->solid_fp32 = t.solid_fp32;
   ctx->fused_sweeps = t.fused_sweeps != 0; ctx->sweeps_fp16 = ctx->fused_sweeps && t.sweeps_fp16 != 0;
   ctx->coloured = t.node_order == 2;
@@ -794,23 +794,6 @@ static int build_schur_pattern(FsiCtx* ctx, const Setup& s) {
   return FSI_OK;
 }
 
-// produces: a32_* / A32 - the FP32 copy's layout (k_spmv_node6p): node blocks padded to multiples of four entries, pressure rows behind
-static int pad_operator_fp32(FsiCtx* ctx, const std::vector<int64_t>& rp) {
-  std::vector<int64_t> p32((size_t)ctx->N2 + 1, 0);
-  for (int64_t r = 0; r < ctx->N2; ++r) {
-    const int64_t L = rp[6 * r + 1] - rp[6 * r];
-    p32[r + 1] = p32[r] + 6 * ((L + 3) & ~(int64_t)3);
-  }
-  ctx->a32_ptail = p32[ctx->N2];
-  ctx->a32_tail_src = rp[6 * (size_t)ctx->N2];
-  ctx->a32_tail_nnz = ctx->nnz - ctx->a32_tail_src;
-  FSICHK(upload(ctx, ctx->a32_ptr, p32));
-  HIPCHK(ctx->a32_cols.alloc((size_t)(ctx->a32_ptail / 6)));
-  launch_pad_cols32(ctx->stream, ctx->N2, ctx->rowptr.p, ctx->cols.p, ctx->a32_ptr.p, ctx->a32_cols.p);
-  HIPCHK(ctx->A32.alloc((size_t)(ctx->a32_ptail + ctx->a32_tail_nnz)));
-  return FSI_OK;
-}
-
 // produces: the Krylov store, sized from `free_b` bytes of free device memory (the recycled directions are what 288 GB of HBM are used for)
 static int size_krylov_store(FsiCtx* ctx, size_t free_b) {
   const int64_t n = ctx->ndof;
@@ -897,8 +880,8 @@ int fsi_create_tuned(const FsiMeshDesc* mesh, const FsiParams* prm, int device, 
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
   ctx->kry_fp32 = ctx->kry_fp32_policy == 1;
-  if (ctx->op32_policy && ctx->kry_fp32_policy != 0) {
-    FSICHK(pad_operator_fp32(ctx, s.rowptr));
+  if (ctx->prod.policy32 && ctx->kry_fp32_policy != 0) {
+    FSICHK(ctx->prod.layout(ctx, s.rowptr));      // the FP32 copy of the monolithic operator
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
   }
   FSICHK(size_krylov_store(ctx, free_b));

@@ -1,11 +1,11 @@
-// Sparse and vector kernels of the linear solve (gfx950): CSR expansion, SpMV, row equilibration and boundary rows,
-// ILU(0) factorisation, triangular solves, BLAS-1 and the batched dot/axpy used by the Krylov methods.
+// Sparse and vector kernels of the linear solve (gfx950): CSR expansion, BLAS-1, row equilibration and boundary rows, the
+// deterministic reductions, ILU(0) factorisation and triangular solves, and the streams that calibrate the byte counters.
+// (The products with the monolithic matrix and the generic CSR product are in fsi_product.hip.)
 //
 // Replaces what PETSc/MUMPS do behind `up_sol.set_operator(A)` / `up_sol.solve(dvp_res.vector(), b)` in turtleFSI's
 // newtonsolver.  All of these kernels are HBM-bound; algorithmic bytes per call:
-//   SpMV     nnz*(8+4) + n*(8+8) + (n+1)*8
 //   SpTRSV   (nnz/2)*(8+4) + n*24           per triangle
-//   multi_*  m*n*8 + n*16
+//   dot      n*16
 // The factorisation and the triangular solves run colour by colour on a multicolour ordering of the mesh nodes
 // (one launch per colour, one wave per node, no spinning): see k_ilu0_level / k_sptrsv_level.
 #include <algorithm>
@@ -182,548 +182,6 @@ void launch_matrix_finish(hipStream_t st, int64_t n, const int64_t* rowptr, cons
   LAUNCH1D(k_izero, st, n, bcmask, n);
   if (nbc > 0) LAUNCH1D(k_mark, st, nbc, bcmask, bc, nbc);
   hipLaunchKernelGGL(k_matrix_finish, dim3(grid_for(n * 64)), dim3(256), 0, st, n, rowptr, diagpos, A, Apre, bcmask, rowscale);
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// SpMV, one wave per row (rows have ~100-400 entries)
-// ---------------------------------------------------------------------------------------------------------
-// TAG only names the instantiation (profiles list the monolithic, solid-block and other-block products separately)
-template <int TAG, class VT = double>
-__global__ __launch_bounds__(256) void k_spmv(int64_t n, const int64_t* __restrict__ rowptr,
-                                              const int32_t* __restrict__ cols, const VT* __restrict__ vals,
-                                              const double* __restrict__ x, double* __restrict__ y) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t row = wave; row < n; row += nwaves) {
-    const int64_t s = rowptr[row], e = rowptr[row + 1];
-    double sum = 0.0;
-    for (int64_t t = s + lane; t < e; t += 64) sum += (double)vals[t] * x[cols[t]];
-    sum = wave_sum(sum);
-    if (lane == 0) y[row] = sum;
-  }
-}
-// Monolithic SpMV, velocity / displacement rows: the six rows of a node share their column pattern (k_expand_cols), so
-// one wave takes a node, reads the column indices and gathers x ONCE and streams the six value rows against them -
-// 8 + 4/6 instead of 12 bytes per entry, a sixth of the gathers, and six independent value streams in flight per lane.
-// VT = float: the FP32 copy of the (row-equilibrated, |entries| <= 1) Jacobian that the Krylov iterations of a loose-tolerance
-// lifetime multiply with (4 + 4/6 bytes per entry); x, y and the accumulation stay FP64, and every answer is checked
-// against the FP64 matrix before it leaves solve_gcr (fsi_krylov.hip).
-// XCD = true: workgroups are dealt round-robin to the 8 XCDs, each with its own L2; giving XCD k the k-th eighth of the
-// nodes (instead of every eighth workgroup of one sweep over all nodes) keeps the x entries a node's neighbours gather
-// inside ONE L2 instead of fetching them into all eight.
-template <class VT, bool XCD>
-__global__ __launch_bounds__(256) void k_spmv_node6(int64_t N2, const int64_t* __restrict__ rowptr,
-                                                    const int32_t* __restrict__ cols, const VT* __restrict__ vals,
-                                                    const double* __restrict__ x, double* __restrict__ y) {
-  const int lane = threadIdx.x & 63;
-  int64_t first, last, stride;
-  if (XCD) {                                                    // gridDim.x is a multiple of 8
-    const int64_t chunk = (N2 + 7) >> 3, k = blockIdx.x & 7;
-    first = k * chunk + (blockIdx.x >> 3) * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6);
-    last = (k + 1) * chunk < N2 ? (k + 1) * chunk : N2;
-    stride = (int64_t)(gridDim.x >> 3) * (blockDim.x >> 6);
-  } else {
-    first = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
-    last = N2;
-    stride = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  }
-  for (int64_t r = first; r < last; r += stride) {
-    const int64_t s0 = rowptr[6 * r];
-    const int64_t L = rowptr[6 * r + 1] - s0;                  // the six rows are stored back to back with equal lengths
-    const VT* v = vals + s0;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0, a5 = 0.0;
-    for (int64_t t = lane; t < L; t += 64) {
-      const double xv = x[cols[s0 + t]];
-      a0 += (double)v[t] * xv; a1 += (double)v[L + t] * xv; a2 += (double)v[2 * L + t] * xv;
-      a3 += (double)v[3 * L + t] * xv; a4 += (double)v[4 * L + t] * xv; a5 += (double)v[5 * L + t] * xv;
-    }
-    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3); a4 = wave_sum(a4); a5 = wave_sum(a5);
-    if (lane == 0) { double* o = y + 6 * r; o[0] = a0; o[1] = a1; o[2] = a2; o[3] = a3; o[4] = a4; o[5] = a5; }
-  }
-}
-// ---- displacement rows in pair form (round 5) -------------------------------------------------------------------------------
-// The three d rows of a node hold 6 deg + pdeg entries each, of which at most 2 deg are structurally non-zero for the forms VaSP
-// uses: the mesh-extension Laplacian and the solid's d - v relation act per component, so row (r, i) has dd_ii and dv_ii per
-// neighbour and no pressure entry - 18 of the 36 values of a node pair carry 6 numbers.  k_drows_extract copies those six per
-// pair [dd_0 dd_1 dd_2 dv_0 dv_1 dv_2] at every Jacobian refresh AND checks that every other entry of the d rows is exactly zero
-// (flag bit 0 otherwise: the full product stays).  The products then stream the three v rows as before and take the d rows
-// from the pair array with one lane per neighbour (48 contiguous bytes of values against the 48 contiguous bytes of x of that
-// neighbour): 24 deg + 3 pdeg values + 6 deg pair values per node instead of 36 deg + 6 pdeg.
-// (Round 2's "compact node rows" re-laid ALL 24 non-zeros as 24 short runs per node and was latency-bound: 3.46 against 3.20 ms.
-// Here the v rows keep their three long streams.)
-// The split form (dd != nullptr; FP64 products): A_dv has entries in the rows of solid nodes only, so on a fluid node - nine in ten
-// on the bench mesh - the dv half of every pair is three exact zeros.  The kernel also writes dd [pairs][3] and classifies each node
-// FROM THE VALUES IT READS: cdeg[r] = its degree if any dv entry of its three d rows is non-zero ("coupled"), else 0.  A scan turns
-// cdeg into offsets (k_drows_offsets: doff[r] = first pair of r in dv, -1 for an uncoupled node) and k_drows_gather_dv copies the dv
-// halves of the coupled nodes to dv [coupled pairs][3].  k_spmv_node6s then reads 24 bytes per pair on an uncoupled node instead of 48.
-template <class DT>
-__global__ __launch_bounds__(256) void k_drows_extract(int64_t N2, const int64_t* __restrict__ rowptr, const double* __restrict__ A,
-                                                       const int64_t* __restrict__ nadj_ptr, double* __restrict__ ad64,
-                                                       DT* __restrict__ ad32, int32_t* __restrict__ flag, double* __restrict__ dd,
-                                                       int32_t* __restrict__ cdeg) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  bool bad = false;
-  for (int64_t r = wave; r < N2; r += nwaves) {
-    const int64_t s0 = rowptr[6 * r], L = rowptr[6 * r + 1] - s0, a = nadj_ptr[r], deg6 = 6 * (nadj_ptr[r + 1] - a);
-    bool coupled = false;
-    for (int i = 0; i < 3; ++i)
-      for (int64_t t = lane; t < L; t += 64) {
-        const double v = A[s0 + i * L + t];
-        const int c = (int)(t % 6);
-        if (t < deg6 && (c == i || c == i + 3)) {
-          const int64_t o = 6 * (a + t / 6) + (c == i ? i : 3 + i);
-          ad64[o] = v;
-          if (ad32) ad32[o] = (DT)v;
-          if (dd && c == i) dd[3 * (a + t / 6) + i] = v;
-          if (c != i && v != 0.0) coupled = true;
-        } else if (v != 0.0) bad = true;
-      }
-    if (cdeg) {                                                   // (r is the wave's: every lane is here)
-      const bool any = __ballot(coupled) != 0;
-      if (lane == 0) cdeg[r] = any ? (int32_t)(deg6 / 6) : 0;
-    }
-  }
-  if (bad) atomicOr(flag, 1);
-}
-void launch_drows_extract_split(hipStream_t st, int64_t N2, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr,
-                                double* ad64, float* ad32, int32_t* flag, double* dd, int32_t* cdeg) {
-  int64_t blocks = std::min<int64_t>((N2 + 3) / 4, 16384);
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_drows_extract<float>, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, A, nadj_ptr, ad64, ad32, flag, dd, cdeg);
-}
-void launch_drows_extract(hipStream_t st, int64_t N2, const int64_t* rowptr, const double* A, const int64_t* nadj_ptr, double* ad64,
-                          float* ad32, int32_t* flag) {
-  launch_drows_extract_split(st, N2, rowptr, A, nadj_ptr, ad64, ad32, flag, nullptr, nullptr);
-}
-// doff[r] = sum of cdeg[0 .. r) where cdeg[r] > 0, else -1; doff[N2] = the whole sum.  One block: the scan runs once per Jacobian
-// over one number per node, in tiles of 8192 nodes with the running sum carried along.
-__global__ __launch_bounds__(1024) void k_drows_offsets(int64_t N2, const int32_t* __restrict__ cdeg, int64_t* __restrict__ doff) {
-  __shared__ int64_t wsum[16];
-  __shared__ int64_t carry;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int64_t base = 0; base < N2; base += 8192) {              // eight consecutive nodes per thread
-    const int64_t i0 = base + 8 * (int64_t)threadIdx.x;
-    int32_t c[8];
-    int64_t mine = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { c[j] = i0 + j < N2 ? cdeg[i0 + j] : 0; mine += c[j]; }
-    int64_t incl = mine;                                         // inclusive scan inside the wave
-    for (int off = 1; off < 64; off <<= 1) {
-      const int64_t up = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += up;
-    }
-    if (lane == 63) wsum[wv] = incl;
-    __syncthreads();
-    int64_t before = carry;
-    for (int k = 0; k < wv; ++k) before += wsum[k];
-    int64_t at = before + incl - mine;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (i0 + j < N2) doff[i0 + j] = c[j] > 0 ? at : -1;
-      at += c[j];
-    }
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = before + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) doff[N2] = carry;
-}
-void launch_drows_offsets(hipStream_t st, int64_t N2, const int32_t* cdeg, int64_t* doff) {
-  hipLaunchKernelGGL(k_drows_offsets, dim3(1), dim3(1024), 0, st, N2, cdeg, doff);
-}
-__global__ __launch_bounds__(256) void k_drows_gather_dv(int64_t N2, const int64_t* __restrict__ nadj_ptr, const int64_t* __restrict__ doff,
-                                                         const double* __restrict__ ad64, double* __restrict__ dv) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t r = wave; r < N2; r += nwaves) {
-    const int64_t o = doff[r];
-    if (o < 0) continue;
-    const int64_t a = nadj_ptr[r], deg = nadj_ptr[r + 1] - a;
-    for (int64_t t = lane; t < 3 * deg; t += 64) dv[3 * o + t] = ad64[6 * (a + t / 3) + 3 + t % 3];
-  }
-}
-void launch_drows_gather_dv(hipStream_t st, int64_t N2, const int64_t* nadj_ptr, const int64_t* doff, const double* ad64, double* dv) {
-  int64_t blocks = std::min<int64_t>((N2 + 3) / 4, 16384);
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_drows_gather_dv, dim3((unsigned)blocks), dim3(256), 0, st, N2, nadj_ptr, doff, ad64, dv);
-}
-// the d rows of node r from the pair array: lane k takes neighbour k (AT: double | float)
-template <class AT>
-__device__ inline void drows_pairs(const AT* __restrict__ ad, const int32_t* __restrict__ nadj, int64_t a, int64_t deg, int lane,
-                                   const double* __restrict__ x, double& a0, double& a1, double& a2) {
-  for (int64_t k = lane; k < deg; k += 64) {
-    const double2* xp = reinterpret_cast<const double2*>(x + 6 * (int64_t)nadj[a + k]);
-    double d0, d1, d2, v0, v1, v2;
-    if (sizeof(AT) == 8) {
-      const double2* p = reinterpret_cast<const double2*>(ad + 6 * (a + k));
-      const double2 p0 = p[0], p1 = p[1], p2 = p[2];
-      d0 = p0.x; d1 = p0.y; d2 = p1.x; v0 = p1.y; v1 = p2.x; v2 = p2.y;
-    } else {
-      const float2* p = reinterpret_cast<const float2*>(ad + 6 * (a + k));
-      const float2 p0 = p[0], p1 = p[1], p2 = p[2];
-      d0 = p0.x; d1 = p0.y; d2 = p1.x; v0 = p1.y; v1 = p2.x; v2 = p2.y;
-    }
-    const double2 x0 = xp[0], x1 = xp[1], x2 = xp[2];      // d_x d_y | d_z v_x | v_y v_z of the neighbour
-    a0 += d0 * x0.x + v0 * x1.y;
-    a1 += d1 * x0.y + v1 * x2.x;
-    a2 += d2 * x1.x + v2 * x2.y;
-  }
-}
-// k_spmv_node6 with the d rows in pair form: value rows 3 .. 5 of the node's block only.  The node index is made wave-uniform
-// for the compiler (readfirstlane), so the row and graph pointers come through the scalar cache.
-// (Also measured at 1.12 M tets, FP64 / FP32 copy, ms per product; this form 2.27 / 1.67, all six rows 2.56 - 2.72 / 1.73 - 1.82:
-// the v rows taken neighbour by neighbour like the d rows - no column indices, x gathered once per neighbour, 48 contiguous bytes
-// per lane and row - 2.27 / 1.93: 45 % of the lanes idle on a 29-neighbour node, 90 - 100 VGPRs; four strips of 64 entries issued
-// together, a 182-entry row in one round of index -> gather: 2.45, two strips: 2.14 (the same): the product wants many small waves,
-// not deep ones.  The scalar pointers took this form from 2.27 / 1.67 to 2.14 / 1.58.)
-template <bool XCD>
-__global__ __launch_bounds__(256) void k_spmv_node6c(int64_t N2, const int64_t* __restrict__ rowptr,
-                                                     const int32_t* __restrict__ cols, const double* __restrict__ vals,
-                                                     const int64_t* __restrict__ nadj_ptr, const int32_t* __restrict__ nadj,
-                                                     const double* __restrict__ ad, const double* __restrict__ x, double* __restrict__ y) {
-  const int lane = threadIdx.x & 63;
-  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  int64_t first, last, stride;
-  if (XCD) {
-    const int64_t chunk = (N2 + 7) >> 3, k = blockIdx.x & 7;
-    first = k * chunk + (blockIdx.x >> 3) * (int64_t)(blockDim.x >> 6) + wid;
-    last = (k + 1) * chunk < N2 ? (k + 1) * chunk : N2;
-    stride = (int64_t)(gridDim.x >> 3) * (blockDim.x >> 6);
-  } else {
-    first = blockIdx.x * (int64_t)(blockDim.x >> 6) + wid;
-    last = N2;
-    stride = (int64_t)gridDim.x * (blockDim.x >> 6);
-  }
-  for (int64_t r = first; r < last; r += stride) {
-    const int64_t s0 = rowptr[6 * r];
-    const int64_t L = rowptr[6 * r + 1] - s0;
-    const int64_t a = nadj_ptr[r], deg = nadj_ptr[r + 1] - a;
-    const double* v = vals + s0 + 3 * L;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0, a5 = 0.0;
-    drows_pairs<double>(ad, nadj, a, deg, lane, x, a0, a1, a2);
-    for (int64_t t = lane; t < L; t += 64) {
-      const double xv = x[cols[s0 + t]];
-      a3 += v[t] * xv; a4 += v[L + t] * xv; a5 += v[2 * L + t] * xv;
-    }
-    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3); a4 = wave_sum(a4); a5 = wave_sum(a5);
-    if (lane == 0) { double* o = y + 6 * r; o[0] = a0; o[1] = a1; o[2] = a2; o[3] = a3; o[4] = a4; o[5] = a5; }
-  }
-}
-// The d rows of node r from the split pair form (k_drows_extract with dd): o = doff[r] is wave-uniform.  What the six-value form
-// computes per pair is  t = fma(d, x_d, v * x_v)  and then  a + t  (the ISA of drows_pairs: v_mul_f64, v_fma_f64, v_add_f64 - the sum
-// of two products contracts to one FMA, the accumulation cannot).  With v == 0 that t is the ROUNDED product d * x_d, so the
-// uncoupled node does one multiply and one add, kept apart (an FMA into the accumulator would round once instead of twice); the
-// coupled node spells the same three operations out.  The results are those of drows_pairs bit for bit: an accumulator that starts
-// as +0 never becomes -0, so not even the sign of the zero  v * x_v  shows.
-__device__ inline void drows_split(const double* __restrict__ dd, const double* __restrict__ dv, int64_t o,
-                                   const int32_t* __restrict__ nadj, int64_t a, int64_t deg, int lane,
-                                   const double* __restrict__ x, double& a0, double& a1, double& a2) {
-#pragma clang fp contract(off)
-  if (o < 0) {
-    for (int64_t k = lane; k < deg; k += 64) {
-      const double* xp = x + 6 * (int64_t)nadj[a + k];
-      const double* p = dd + 3 * (a + k);
-      const double d0 = p[0], d1 = p[1], d2 = p[2];
-      const double2 x0 = *reinterpret_cast<const double2*>(xp);      // d_x d_y | d_z of the neighbour
-      const double x2 = xp[2];
-      const double t0 = d0 * x0.x, t1 = d1 * x0.y, t2 = d2 * x2;
-      a0 = a0 + t0; a1 = a1 + t1; a2 = a2 + t2;
-    }
-  } else {
-    for (int64_t k = lane; k < deg; k += 64) {
-      const double2* xp = reinterpret_cast<const double2*>(x + 6 * (int64_t)nadj[a + k]);
-      const double* p = dd + 3 * (a + k);
-      const double* q = dv + 3 * (o + k);
-      const double d0 = p[0], d1 = p[1], d2 = p[2], v0 = q[0], v1 = q[1], v2 = q[2];
-      const double2 x0 = xp[0], x1 = xp[1], x2 = xp[2];      // d_x d_y | d_z v_x | v_y v_z of the neighbour
-      const double t0 = __builtin_fma(d0, x0.x, v0 * x1.y), t1 = __builtin_fma(d1, x0.y, v1 * x2.x), t2 = __builtin_fma(d2, x1.x, v2 * x2.y);
-      a0 = a0 + t0; a1 = a1 + t1; a2 = a2 + t2;
-    }
-  }
-}
-// k_spmv_node6c with the d rows from the split pair form; everything else as there
-template <bool XCD>
-__global__ __launch_bounds__(256) void k_spmv_node6s(int64_t N2, const int64_t* __restrict__ rowptr,
-                                                     const int32_t* __restrict__ cols, const double* __restrict__ vals,
-                                                     const int64_t* __restrict__ nadj_ptr, const int32_t* __restrict__ nadj,
-                                                     const double* __restrict__ dd, const double* __restrict__ dv,
-                                                     const int64_t* __restrict__ doff, const double* __restrict__ x, double* __restrict__ y) {
-  const int lane = threadIdx.x & 63;
-  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  int64_t first, last, stride;
-  if (XCD) {
-    const int64_t chunk = (N2 + 7) >> 3, k = blockIdx.x & 7;
-    first = k * chunk + (blockIdx.x >> 3) * (int64_t)(blockDim.x >> 6) + wid;
-    last = (k + 1) * chunk < N2 ? (k + 1) * chunk : N2;
-    stride = (int64_t)(gridDim.x >> 3) * (blockDim.x >> 6);
-  } else {
-    first = blockIdx.x * (int64_t)(blockDim.x >> 6) + wid;
-    last = N2;
-    stride = (int64_t)gridDim.x * (blockDim.x >> 6);
-  }
-  for (int64_t r = first; r < last; r += stride) {
-    const int64_t s0 = rowptr[6 * r];
-    const int64_t L = rowptr[6 * r + 1] - s0;
-    const int64_t a = nadj_ptr[r], deg = nadj_ptr[r + 1] - a;
-    const double* v = vals + s0 + 3 * L;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0, a5 = 0.0;
-    drows_split(dd, dv, doff[r], nadj, a, deg, lane, x, a0, a1, a2);
-    for (int64_t t = lane; t < L; t += 64) {
-      const double xv = x[cols[s0 + t]];
-      a3 += v[t] * xv; a4 += v[L + t] * xv; a5 += v[2 * L + t] * xv;
-    }
-    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3); a4 = wave_sum(a4); a5 = wave_sum(a5);
-    if (lane == 0) { double* o = y + 6 * r; o[0] = a0; o[1] = a1; o[2] = a2; o[3] = a3; o[4] = a4; o[5] = a5; }
-  }
-}
-// Monolithic SpMV, pressure rows.  The row of vertex q (node rank r = vrank[q]) holds, for every neighbour node s of r in
-// ascending order, the six columns 6 s .. 6 s + 5, then the pressure columns (k_expand_cols): a lane takes a neighbour, reads
-// its rank from the node graph (4 bytes instead of six column indices), the six values and the six x entries - 48 contiguous,
-// 16-byte aligned bytes - and the pressure part follows entry by entry.  One wave per row.  (The generic kernel this replaces
-// read 12 bytes per entry and gathered x entry by entry: 222 us of a 1.53 ms product at 1.12 M tets.)
-template <class VT>
-__global__ __launch_bounds__(256) void k_spmv_prow(int64_t V, const int64_t* __restrict__ prowptr, const int32_t* __restrict__ cols,
-                                                   const VT* __restrict__ vals, const int32_t* __restrict__ vrank,
-                                                   const int64_t* __restrict__ nadj_ptr, const int32_t* __restrict__ nadj,
-                                                   const double* __restrict__ x, double* __restrict__ y) {
-  const int lane = threadIdx.x & 63;
-  // (wave-uniform for the compiler: the row's three levels of pointers - row, node rank, node graph - come through the scalar cache)
-  const int64_t wave = blockIdx.x * (int64_t)(blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-  for (int64_t q = wave; q < V; q += nwaves) {
-    const int64_t s = prowptr[q], e = prowptr[q + 1];
-    const int32_t r = vrank[q];
-    const int64_t a = nadj_ptr[r], deg = nadj_ptr[r + 1] - a;
-    double sum = 0.0;
-    for (int64_t k = lane; k < deg; k += 64) {
-      const double2* xp = reinterpret_cast<const double2*>(x + 6 * (int64_t)nadj[a + k]);
-      const VT* v = vals + s + 6 * k;
-      const double2 x0 = xp[0], x1 = xp[1], x2 = xp[2];
-      sum += ((double)v[0] * x0.x + (double)v[1] * x0.y) + ((double)v[2] * x1.x + (double)v[3] * x1.y) + ((double)v[4] * x2.x + (double)v[5] * x2.y);
-    }
-    for (int64_t t = s + 6 * deg + lane; t < e; t += 64) sum += (double)vals[t] * x[cols[t]];
-    sum = wave_sum(sum);
-    if (lane == 0) y[q] = sum;
-  }
-}
-template <class VT>
-static void spmv_prows(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const VT* vals_rowptr_based,
-                       const PRowGraph& g, const double* x, double* y) {
-  if (V <= 0) return;
-  const int64_t pb = (V + 3) / 4;
-  if (g.vrank && g.nadj_ptr && g.nadj)
-    hipLaunchKernelGGL(k_spmv_prow<VT>, dim3((unsigned)pb), dim3(256), 0, st, V, rowptr + 6 * N2, cols, vals_rowptr_based, g.vrank, g.nadj_ptr, g.nadj, x, y + 6 * N2);
-  else      // no node graph at hand: the generic kernel on the tail of the matrix
-    hipLaunchKernelGGL((k_spmv<SPMV_MONOLITHIC, VT>), dim3((unsigned)pb), dim3(256), 0, st, V, rowptr + 6 * N2, cols, vals_rowptr_based, x, y + 6 * N2);
-}
-template <class VT>
-static void spmv_node6_any(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const VT* vals,
-                           const PRowGraph& g, const double* x, double* y) {
-  constexpr bool xcd = true;        // XCD-aware node mapping: -9 % HBM traffic (round 2)
-  int64_t blocks = (N2 + 3) / 4;                                 // one wave per node (see launch_spmv_node6p)
-  blocks = (blocks + 7) & ~(int64_t)7;
-  if (blocks <= 0) {}      // no node rows (an empty grid is an invalid launch)
-  else if (xcd) hipLaunchKernelGGL((k_spmv_node6<VT, true>), dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, vals, x, y);
-  else hipLaunchKernelGGL((k_spmv_node6<VT, false>), dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, vals, x, y);
-  spmv_prows<VT>(st, N2, V, rowptr, cols, vals, g, x, y);      // pressure rows
-}
-// ad64 != nullptr: the d rows from their pair form (k_drows_extract found nothing else in them).  The pair form is indexed by the
-// node graph: without it nothing is launched and LAUNCH_REFUSED returned (the six-row kernel instead would read d rows that a
-// pair-form copy need not hold).
-int launch_spmv_node6(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals,
-                      const PRowGraph& g, const double* x, double* y, const double* ad64) {
-  if (ad64) {
-    if (!g.nadj_ptr || !g.nadj) return LAUNCH_REFUSED;
-    int64_t blocks = (N2 + 3) / 4;
-    blocks = (blocks + 7) & ~(int64_t)7;
-    if (blocks > 0) hipLaunchKernelGGL(k_spmv_node6c<true>, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, vals, g.nadj_ptr, g.nadj, ad64, x, y);
-    spmv_prows<double>(st, N2, V, rowptr, cols, vals, g, x, y);
-    return 0;
-  }
-  spmv_node6_any<double>(st, N2, V, rowptr, cols, vals, g, x, y);
-  return 0;
-}
-// the d rows from the split pair form (dd, dv, doff: launch_drows_extract_split and what follows it); refused like the pair form
-// without the node graph, and without all three arrays
-int launch_spmv_node6s(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const int32_t* cols, const double* vals,
-                       const PRowGraph& g, const double* x, double* y, const double* dd, const double* dv, const int64_t* doff) {
-  if (!g.nadj_ptr || !g.nadj || !dd || !doff) return LAUNCH_REFUSED;      // (dv may be null: no coupled node)
-  int64_t blocks = (N2 + 3) / 4;
-  blocks = (blocks + 7) & ~(int64_t)7;
-  if (blocks > 0) hipLaunchKernelGGL(k_spmv_node6s<true>, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, vals, g.nadj_ptr, g.nadj, dd, dv, doff, x, y);
-  spmv_prows<double>(st, N2, V, rowptr, cols, vals, g, x, y);
-  return 0;
-}
-// ---- FP32 copy of the Jacobian in its own layout --------------------------------------------------------------------
-// The copy only serves k_spmv_node6p, so it is laid out for it: the six value rows of a node (and one row of column
-// indices) padded to a multiple of four entries and 16-byte aligned, p32[r] = first entry of node r's block in units of
-// ENTRIES (block = 6 Lp values; the index row has Lp entries at p32[r] / 6).  One float4 / int4 load per lane then covers
-// 256 entries: the ~170 entries of a P2 edge node take ONE round of 6 + 1 loads and 4 gathers per lane instead of three
-// rounds of 6 + 1 + 1 - the FP32 product was paced by its memory instructions, not by its 7.5 GB.  Padding entries carry
-// value 0 and column 0.  The pressure rows follow unpadded (k_spmv on them as before).
-__global__ __launch_bounds__(256) void k_pad_cols32(int64_t N2, const int64_t* __restrict__ rowptr, const int32_t* __restrict__ cols,
-                                                    const int64_t* __restrict__ p32, int32_t* __restrict__ cols32) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t r = wave; r < N2; r += nwaves) {
-    const int64_t s0 = rowptr[6 * r], L = rowptr[6 * r + 1] - s0, Lp = (L + 3) & ~(int64_t)3, o = p32[r] / 6;
-    for (int64_t t = lane; t < Lp; t += 64) cols32[o + t] = t < L ? cols[s0 + t] : 0;
-  }
-}
-__global__ __launch_bounds__(256) void k_pad_vals32(int64_t N2, const int64_t* __restrict__ rowptr, const double* __restrict__ A,
-                                                    const int64_t* __restrict__ p32, float* __restrict__ A32, int row0) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t r = wave; r < N2; r += nwaves) {
-    const int64_t s0 = rowptr[6 * r], L = rowptr[6 * r + 1] - s0, Lp = (L + 3) & ~(int64_t)3, o = p32[r];
-    for (int k = row0; k < 6; ++k)
-      for (int64_t t = lane; t < Lp; t += 64) A32[o + k * Lp + t] = t < L ? (float)A[s0 + k * L + t] : 0.f;
-  }
-}
-template <bool XCD>
-__global__ __launch_bounds__(256) void k_spmv_node6p(int64_t N2, const int64_t* __restrict__ p32, const int32_t* __restrict__ cols32,
-                                                     const float* __restrict__ vals, const double* __restrict__ x,
-                                                     double* __restrict__ y) {
-  const int lane = threadIdx.x & 63;
-  int64_t first, last, stride;
-  if (XCD) {
-    const int64_t chunk = (N2 + 7) >> 3, k = blockIdx.x & 7;
-    first = k * chunk + (blockIdx.x >> 3) * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6);
-    last = (k + 1) * chunk < N2 ? (k + 1) * chunk : N2;
-    stride = (int64_t)(gridDim.x >> 3) * (blockDim.x >> 6);
-  } else {
-    first = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
-    last = N2;
-    stride = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  }
-  for (int64_t r = first; r < last; r += stride) {
-    const int64_t o = p32[r];
-    const int Lp = (int)((p32[r + 1] - o) / 6);
-    const float* v = vals + o;
-    const int32_t* c = cols32 + o / 6;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0, a5 = 0.0;
-    for (int t = 4 * lane; t < Lp; t += 256) {
-      const int4 cc = *reinterpret_cast<const int4*>(c + t);
-      const float4 v0 = *reinterpret_cast<const float4*>(v + t), v1 = *reinterpret_cast<const float4*>(v + Lp + t),
-                   v2 = *reinterpret_cast<const float4*>(v + 2 * Lp + t), v3 = *reinterpret_cast<const float4*>(v + 3 * Lp + t),
-                   v4 = *reinterpret_cast<const float4*>(v + 4 * Lp + t), v5 = *reinterpret_cast<const float4*>(v + 5 * Lp + t);
-      const double x0 = x[cc.x], x1 = x[cc.y], x2 = x[cc.z], x3 = x[cc.w];
-      a0 += ((double)v0.x * x0 + (double)v0.y * x1) + ((double)v0.z * x2 + (double)v0.w * x3);
-      a1 += ((double)v1.x * x0 + (double)v1.y * x1) + ((double)v1.z * x2 + (double)v1.w * x3);
-      a2 += ((double)v2.x * x0 + (double)v2.y * x1) + ((double)v2.z * x2 + (double)v2.w * x3);
-      a3 += ((double)v3.x * x0 + (double)v3.y * x1) + ((double)v3.z * x2 + (double)v3.w * x3);
-      a4 += ((double)v4.x * x0 + (double)v4.y * x1) + ((double)v4.z * x2 + (double)v4.w * x3);
-      a5 += ((double)v5.x * x0 + (double)v5.y * x1) + ((double)v5.z * x2 + (double)v5.w * x3);
-    }
-    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3); a4 = wave_sum(a4); a5 = wave_sum(a5);
-    if (lane == 0) { double* o6 = y + 6 * r; o6[0] = a0; o6[1] = a1; o6[2] = a2; o6[3] = a3; o6[4] = a4; o6[5] = a5; }
-  }
-}
-// k_spmv_node6p with the d rows in pair form (FP32 pair values): value rows 3 .. 5 of the padded block only
-template <bool XCD>
-__global__ __launch_bounds__(256) void k_spmv_node6pc(int64_t N2, const int64_t* __restrict__ p32, const int32_t* __restrict__ cols32,
-                                                      const float* __restrict__ vals, const int64_t* __restrict__ nadj_ptr,
-                                                      const int32_t* __restrict__ nadj, const float* __restrict__ ad,
-                                                      const double* __restrict__ x, double* __restrict__ y) {
-  const int lane = threadIdx.x & 63;
-  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  int64_t first, last, stride;
-  if (XCD) {
-    const int64_t chunk = (N2 + 7) >> 3, k = blockIdx.x & 7;
-    first = k * chunk + (blockIdx.x >> 3) * (int64_t)(blockDim.x >> 6) + wid;
-    last = (k + 1) * chunk < N2 ? (k + 1) * chunk : N2;
-    stride = (int64_t)(gridDim.x >> 3) * (blockDim.x >> 6);
-  } else {
-    first = blockIdx.x * (int64_t)(blockDim.x >> 6) + wid;
-    last = N2;
-    stride = (int64_t)gridDim.x * (blockDim.x >> 6);
-  }
-  for (int64_t r = first; r < last; r += stride) {
-    const int64_t o = p32[r];
-    const int Lp = (int)((p32[r + 1] - o) / 6);
-    const int64_t a = nadj_ptr[r], deg = nadj_ptr[r + 1] - a;
-    const float* v = vals + o + 3 * (int64_t)Lp;
-    const int32_t* c = cols32 + o / 6;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0, a5 = 0.0;
-    drows_pairs<float>(ad, nadj, a, deg, lane, x, a0, a1, a2);
-    for (int t = 4 * lane; t < Lp; t += 256) {
-      const int4 cc = *reinterpret_cast<const int4*>(c + t);
-      const float4 v3 = *reinterpret_cast<const float4*>(v + t), v4 = *reinterpret_cast<const float4*>(v + Lp + t),
-                   v5 = *reinterpret_cast<const float4*>(v + 2 * Lp + t);
-      const double x0 = x[cc.x], x1 = x[cc.y], x2 = x[cc.z], x3 = x[cc.w];
-      a3 += ((double)v3.x * x0 + (double)v3.y * x1) + ((double)v3.z * x2 + (double)v3.w * x3);
-      a4 += ((double)v4.x * x0 + (double)v4.y * x1) + ((double)v4.z * x2 + (double)v4.w * x3);
-      a5 += ((double)v5.x * x0 + (double)v5.y * x1) + ((double)v5.z * x2 + (double)v5.w * x3);
-    }
-    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3); a4 = wave_sum(a4); a5 = wave_sum(a5);
-    if (lane == 0) { double* o6 = y + 6 * r; o6[0] = a0; o6[1] = a1; o6[2] = a2; o6[3] = a3; o6[4] = a4; o6[5] = a5; }
-  }
-}
-void launch_pad_cols32(hipStream_t st, int64_t N2, const int64_t* rowptr, const int32_t* cols, const int64_t* p32, int32_t* cols32) {
-  int64_t blocks = std::min<int64_t>((N2 + 3) / 4, 8192);
-  if (blocks > 0) hipLaunchKernelGGL(k_pad_cols32, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, cols, p32, cols32);
-}
-// node rows padded (k_pad_vals32), pressure rows as they are behind them at entry offset ptail
-// (v_rows_only: the d rows are served from their pair form - k_spmv_node6pc never reads value rows 0 .. 2 of the copy)
-void launch_pad_vals32(hipStream_t st, int64_t N2, int64_t V, const int64_t* rowptr, const double* A, const int64_t* p32,
-                       int64_t ptail, int64_t nnz_tail, int64_t tail_src, float* A32, bool v_rows_only) {
-  int64_t blocks = std::min<int64_t>((N2 + 3) / 4, 8192);
-  if (blocks > 0) hipLaunchKernelGGL(k_pad_vals32, dim3((unsigned)blocks), dim3(256), 0, st, N2, rowptr, A, p32, A32, v_rows_only ? 3 : 0);
-  if (V > 0 && nnz_tail > 0) launch_round_to_f32(st, nnz_tail, A + tail_src, A32 + ptail);
-}
-// y = A32 x: padded node rows, then the pressure rows (their values at vals + ptail, indexed by the rows' own pointers
-// shifted by tail_shift = ptail - rowptr[6 N2]).  ad32 != nullptr: the d rows in pair form, which needs the node graph; without it
-// nothing is launched and LAUNCH_REFUSED returned (value rows 0 .. 2 of a copy made with v_rows_only hold nothing).
-int launch_spmv_node6p(hipStream_t st, int64_t N2, int64_t V, const int64_t* p32, const int32_t* cols32, const float* vals,
-                       const int64_t* rowptr, const int32_t* cols, int64_t tail_shift, const PRowGraph& g, const double* x, double* y,
-                       const float* ad32) {
-  constexpr bool xcd = true;        // XCD-aware node mapping: -9 % HBM traffic (round 2)
-  if (ad32) {      // d rows in pair form
-    if (!g.nadj_ptr || !g.nadj) return LAUNCH_REFUSED;
-    int64_t blocks = (N2 + 3) / 4;
-    blocks = (blocks + 7) & ~(int64_t)7;
-    if (blocks > 0) hipLaunchKernelGGL(k_spmv_node6pc<true>, dim3((unsigned)blocks), dim3(256), 0, st, N2, p32, cols32, vals, g.nadj_ptr, g.nadj, ad32, x, y);
-    spmv_prows<float>(st, N2, V, rowptr, cols, vals + tail_shift, g, x, y);
-    return 0;
-  }
-  // one wave per node, no grid-stride loop: measured 1.87 ms per product against 2.23 ms with 8192 workgroups looping
-  // (row lengths differ by 3x between edge and vertex nodes; the hardware scheduler balances what a static stride cannot)
-  constexpr int64_t bmax = (int64_t)1 << 30;      // one wave per node, no grid-stride loop (round 2)
-  int64_t blocks = (N2 + 3) / 4;
-  if (blocks > bmax) blocks = bmax;
-  blocks = (blocks + 7) & ~(int64_t)7;
-  if (blocks <= 0) {}      // no node rows
-  else if (xcd) hipLaunchKernelGGL(k_spmv_node6p<true>, dim3((unsigned)blocks), dim3(256), 0, st, N2, p32, cols32, vals, x, y);
-  else hipLaunchKernelGGL(k_spmv_node6p<false>, dim3((unsigned)blocks), dim3(256), 0, st, N2, p32, cols32, vals, x, y);
-  // the pressure-row kernels index values and columns with the rows' own pointers: hand them the value array shifted so that
-  // vals32[rowptr[row]] is the row's first value
-  spmv_prows<float>(st, N2, V, rowptr, cols, vals + tail_shift, g, x, y);
-  return 0;
-}
-__global__ __launch_bounds__(256) void k_round_to_f32(int64_t n, const double* __restrict__ a, float* __restrict__ b) {
-  GRID_STRIDE(i, n) b[i] = (float)a[i];
-}
-void launch_round_to_f32(hipStream_t st, int64_t n, const double* a, float* b) {
-  if (n <= 0) return;      // nothing to round (an empty grid is an invalid launch)
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(k_round_to_f32, dim3((unsigned)blocks), dim3(256), 0, st, n, a, b);
-}
-void launch_spmv(hipStream_t st, int64_t n, const int64_t* rowptr, const int32_t* cols, const double* vals,
-                 const double* x, double* y, int tag) {
-  if (n <= 0) return;      // no rows (an empty grid is an invalid launch)
-  int64_t blocks = (n + 3) / 4;
-  if (blocks > 8192) blocks = 8192;
-  if (tag == SPMV_MONOLITHIC)
-    hipLaunchKernelGGL(k_spmv<SPMV_MONOLITHIC>, dim3((unsigned)blocks), dim3(256), 0, st, n, rowptr, cols, vals, x, y);
-  else if (tag == SPMV_SOLID_BLOCK)
-    hipLaunchKernelGGL(k_spmv<SPMV_SOLID_BLOCK>, dim3((unsigned)blocks), dim3(256), 0, st, n, rowptr, cols, vals, x, y);
-  else
-    hipLaunchKernelGGL(k_spmv<SPMV_FIELD_BLOCK>, dim3((unsigned)blocks), dim3(256), 0, st, n, rowptr, cols, vals, x, y);
 }
 
 // ---------------------------------------------------------------------------------------------------------
